@@ -1,8 +1,12 @@
 """bench.py — rollout timesteps/s of the graphs4cfd message-passing hot path on MI355X.
 
-    python bench.py [--workload headline|c2|c3|c5-1gpu] [--gpus 1] [--steps 200] [--warmup 5]
+    python bench.py [--workload headline|c2|c3|c5-1gpu] [--gpus 1] [--steps 200] [--warmup 5] [--dump-outputs DIR] [--full]
     python bench.py --gpus N ...          (N > 1 outside a torch.distributed.run job: starts its own N ranks, same line as below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps replayed steps and prints the line (metric, value, ms_per_step, ...).
+--dump-outputs DIR  after the timed steps, writes what the last of them computed as a caller receives it (DIR/*.npy, float32).
+--full              also runs the extra objects below (each still switched off by its --no-* option).
 
 Workloads (BASELINE.json `configs`):
   headline  NsThreeScaleGNN (published arch, H = 128, 4/2/4/2/4 MP layers), synthetic 100 000-node 2-D mesh (uniform random
@@ -13,7 +17,7 @@ Workloads (BASELINE.json `configs`):
   c5-1gpu   NsFourScaleGNN, 1 000 000-node 3-D mesh on ONE GPU (config 5's mesh and model without the partition).
 A step = one forward of the whole model + the rollout bookkeeping kernel, replayed from a hipGraph.
 
-One JSON line on stdout (rank 0).  Extra objects:
+One JSON line on stdout (rank 0).  Extra objects (--full only):
   roofline         — dominant kernel (fused MLP): algorithmic FLOP / measured duration, from HIP-event pairs around every launch
                      of an eager pass of the same step, on the launch stream.
   roofline_scatter — the CSR segment-reduce ("scatter-sum") against the HBM roofline: level-1 messages in ROTATING buffers (no
@@ -21,6 +25,8 @@ One JSON line on stdout (rank 0).  Extra objects:
   cpu_baseline     — the oracle (pure-torch restatement of the reference CPU path) timed on this host, bounded sample.
   partition_check  — (N > 1) two partitioned steps against a single-rank rollout of the same mesh, per-rank compute time,
                      per-exchange time, halo bytes, whether the step was captured.
+  range_safety.fallback_arithmetic — (f16x3) the same rollout timed in bf16x6.
+  configs          — (default headline run) short legs of BASELINE configs 1 - 3 in the same process.
 """
 import argparse
 import json
@@ -71,6 +77,11 @@ def parse():
     ap.add_argument("--no-side-configs", action="store_true", help="skip the short legs of BASELINE configs 2 and 3 beside the default headline run")
     ap.add_argument("--no-partition-check", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=75.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs, as a caller receives them, to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check what the headline figure does not need: CPU baseline, bf16x6 fallback rate, roofline, "
+                         "side configs, partition check")
     a = ap.parse_args()
     w = WORKLOADS[a.workload]
     a.custom = a.nodes is not None or a.model is not None or (a.precision is not None and a.precision != w["precision"])
@@ -684,6 +695,29 @@ def side_config(name, gfd, S, ops, Rollout, dev, steps, warmup=3):
         ops.set_mlp_precision(old)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, runner, world, rank):
+    """--dump-outputs: the last timed step as its caller receives it — the predicted fields of that step, [N, nf] in the caller's
+    node numbering (`Rollout.result()` / `gather_outputs()`: validated, rows mapped back) — as DIR/last_step_prediction.npy, float32.
+    A mesh too large for DUMP_LIMIT_BYTES is sampled: a fixed, seeded set of rows (their indices in last_step_prediction_rows.npy,
+    float64).  Collective over the ranks (gather_outputs)."""
+    import numpy as np
+    full = runner.gather_outputs() if world > 1 else runner.result()
+    t, nf = runner.steps_done, runner.nf
+    last = full[:, nf * (t - 1): nf * t].float()
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    if last.numel() * 4 > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (4 * nf + 8)
+        rows = torch.randperm(last.size(0), generator=torch.Generator().manual_seed(0))[:k].sort().values
+        last = last[rows.to(last.device)]
+        np.save(os.path.join(dirname, "last_step_prediction_rows.npy"), rows.to(torch.float64).numpy())
+    np.save(os.path.join(dirname, "last_step_prediction.npy"), last.cpu().numpy())
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -718,7 +752,7 @@ def main():
     if world > 1:
         from graphs4cfd_amd import partition
         runner = partition.DistributedRollout(model, graph_cpu, total_steps + 6, rank, world, dev, capture=not same_gpu)
-        if not args.no_partition_check:
+        if args.full and not args.no_partition_check:
             check = partition_check(args, runner, model, graph_cpu, dev, rank, world, Rollout)
     else:
         runner = Rollout(model, graph_cpu.clone().to(dev), total_steps + 2, capture=True)
@@ -745,6 +779,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     finite = bool(torch.isfinite(runner.outputs).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, world, rank)
 
     if remus:
         n_mp = 16                          # 4/2/4/2/4 EdgeMP layers (+ 2 DownEdgeMP, 2 UpEdgeMP)
@@ -787,7 +823,7 @@ def main():
                       "flags are read INSIDE the timed region (Rollout.validate); a rollout that reached +-65504 anywhere is recomputed "
                       "from its input window in bf16x6 (fp32 exponent range) and stays there, so a delivered result never holds a clipped value",
             "recomputed_in_bf16x6": recomputed}
-    if rank == 0 and world == 1 and args.precision == "f16x3" and not args.no_strict_range:
+    if rank == 0 and world == 1 and args.full and args.precision == "f16x3" and not args.no_strict_range:
         # the same workload, same process, in the arithmetic a clipped rollout falls back to (three-way bf16 split, six products):
         # the rate of a model whose activations DO leave the fp16 range (the reference computes in fp32: nn/model.py:303-321)
         ops.set_mlp_precision("bf16x6")
@@ -814,7 +850,7 @@ def main():
                                             "angle encoders) run once per rollout, in the first eager step; a bare forward() recomputes them")
 
     clk = None
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         try:
             clk = clock_under_load(runner, dev)
         except Exception as exc:          # (no rocm-smi on the box: the line simply has no clock)
@@ -831,7 +867,7 @@ def main():
                                "(HBM peaks do not scale with the shader clock)")
             r["clock_sampling"] = clk
 
-    if rank == 0 and world == 1 and args.workload == "headline" and not args.custom and not args.no_side_configs:
+    if rank == 0 and world == 1 and args.full and args.workload == "headline" and not args.custom and not args.no_side_configs:
         # BASELINE configs 2 and 3 as short legs of the same process (their own meshes, models and arithmetic), so that the
         # driver-timed line carries them; `python bench.py --workload c2|c3` gives the full lines
         del runner
@@ -848,7 +884,7 @@ def main():
                 result["configs"][name] = {"error": f"{type(exc).__name__}: {exc}"}
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         weights = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         result["cpu_baseline"] = cpu_baseline(args, S, weights, nf, args.cpu_budget_s)
 

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc_traffic_$TAG$SFX
 rm -rf $OUT; mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/A_$c -o p -- python bench.py --workload $WL --steps 4 --warmup 1 --no-cpu-baseline --no-strict-range --no-side-configs > $OUT/A_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/A_$c -o p -- python bench.py --full --workload $WL --steps 4 --warmup 1 --no-cpu-baseline --no-strict-range --no-side-configs > $OUT/A_$c.log 2>&1
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/B_$c -o p -- python bench.py --workload $WL --steps 6 --warmup 1 --no-cpu-baseline --no-roofline --no-strict-range --no-side-configs > $OUT/B_$c.log 2>&1
 done
 python - "$OUT" "$TAG" "$SFX" "$WL" <<'PY'
@@ -58,7 +58,7 @@ if steps.get("FETCH_SIZE") and steps.get("WRITE_SIZE"):
                                              for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]["FETCH_SIZE"])[:12]},
                 "note": "includes the one-off first step (plans, weight packing) spread over the steps executed"}
 json.dump({"workload": wl,
-           "how": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over `bench.py --workload {wl} --steps 4 --warmup 1 --no-cpu-baseline` (hipGraph steps + the instrumented eager pass + the standalone level-1 aggregation); "
+           "how": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over `bench.py --full --workload {wl} --steps 4 --warmup 1 --no-cpu-baseline` (hipGraph steps + the instrumented eager pass + the standalone level-1 aggregation); "
                   "bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950: FETCH_SIZE halves wide coalesced reads); `per_step`: the same two passes over "
                   "the bench with --no-roofline (only rollout steps run), all dispatches / steps executed",
            "kernels": res, "per_step": per_step},

@@ -15,36 +15,36 @@ timeout 1200 bash scripts/collect_pmc_traffic.sh $TAG c3 > $A/pmc_c3.log 2>&1; c
 # launch (mlp_ws_kernel) and node launch (mlp_bx6_kernel)
 bash scripts/pmc_ws.sh ws ${TAG}_ws util sq3 lds sq2 tcc mix mix2 coexec > profiles/${TAG}_pmc_mlp_ws.txt 2>&1; cp profiles/${TAG}_pmc_mlp_ws.txt $A/
 PMC_EXTRA_ARGS=--node bash scripts/pmc_ws.sh tile ${TAG}_node util sq3 lds sq2 tcc mix mix2 coexec > profiles/${TAG}_pmc_mlp_bx6_node.txt 2>&1; cp profiles/${TAG}_pmc_mlp_bx6_node.txt $A/
-timeout 900 python bench.py > $A/bench_stdout.log 2> $A/bench_stderr.log; tail -1 $A/bench_stdout.log > $A/${TAG}_bench_n1.json
+timeout 900 python bench.py --full > $A/bench_stdout.log 2> $A/bench_stderr.log; tail -1 $A/bench_stdout.log > $A/${TAG}_bench_n1.json
 for wl in c2 c3 c5-1gpu; do
-  timeout 900 python bench.py --workload $wl 2> $A/bench_${wl}_stderr.log | tail -1 > $A/${TAG}_bench_${wl}.json
+  timeout 900 python bench.py --full --workload $wl 2> $A/bench_${wl}_stderr.log | tail -1 > $A/${TAG}_bench_${wl}.json
 done
 for wl in headline c3; do
   ( cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $A/prof_$wl -o p -- \
-      python bench.py --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-strict-range --no-side-configs > $A/prof_${wl}_stdout.log 2> $A/prof_${wl}_stderr.log )
+      python bench.py --full --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-strict-range --no-side-configs > $A/prof_${wl}_stdout.log 2> $A/prof_${wl}_stderr.log )
   tail -1 $A/prof_${wl}_stdout.log > $A/${TAG}_bench_${wl}_under_rocprofv3.json
   cp $(find $A/prof_$wl -name '*kernel_stats.csv' | head -1) $A/${TAG}_rocprofv3_kernel_stats_${wl}.csv
   rm -rf $A/prof_$wl
 done
 hipcc -w --offload-arch=gfx950 -O3 -o /tmp/mfma_peak scripts/micro/mfma_peak.hip && /tmp/mfma_peak 2000 > $A/${TAG}_mfma_peak.log 2>&1
 {
-  echo "# side configurations (bench.py --no-cpu-baseline --no-roofline), one JSON line each"
-  timeout 300 python bench.py --nodes 12500 --steps 50 --no-cpu-baseline --no-roofline | tail -1
-  timeout 300 python bench.py --model NsFourScaleGNN --nodes 100000 --steps 20 --no-cpu-baseline --no-roofline | tail -1
-  timeout 300 python bench.py --model NsRotEquiTreeScaleGNN --nodes 100000 --steps 20 --no-cpu-baseline --no-roofline | tail -1
+  echo "# side configurations (bench.py --full --no-cpu-baseline --no-roofline), one JSON line each"
+  timeout 300 python bench.py --full --nodes 12500 --steps 50 --no-cpu-baseline --no-roofline | tail -1
+  timeout 300 python bench.py --full --model NsFourScaleGNN --nodes 100000 --steps 20 --no-cpu-baseline --no-roofline | tail -1
+  timeout 300 python bench.py --full --model NsRotEquiTreeScaleGNN --nodes 100000 --steps 20 --no-cpu-baseline --no-roofline | tail -1
   timeout 300 python scripts/bench_mugs.py 2>&1 | tail -2
-  timeout 300 python bench.py --precision fp32 --steps 20 --no-cpu-baseline | tail -1
-  timeout 300 python bench.py --precision bf16x6 --steps 100 --no-cpu-baseline | tail -1
+  timeout 300 python bench.py --full --precision fp32 --steps 20 --no-cpu-baseline | tail -1
+  timeout 300 python bench.py --full --precision bf16x6 --steps 100 --no-cpu-baseline | tail -1
   timeout 300 python bench.py --precision bf16 --steps 50 --no-cpu-baseline --no-roofline | tail -1
 } > $A/${TAG}_side_configs.log 2>&1
 # functional check of the partitioned path on the one GPU of the box (both ranks on cuda:0, gloo transport): partition_check in the line
 for wl in headline c3; do
   G4C_BENCH_SAME_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus 2 --workload $wl --steps 20 --warmup 3 2> $A/bench_${wl}_2rank_stderr.log | tail -1 > $A/${TAG}_bench_${wl}_2rank_samegpu.json
+      bench.py --full --gpus 2 --workload $wl --steps 20 --warmup 3 2> $A/bench_${wl}_2rank_stderr.log | tail -1 > $A/${TAG}_bench_${wl}_2rank_samegpu.json
 done
 # the driver's command shape: bench.py --gpus N as a PLAIN command starts its own ranks
 for n in 2 4; do
-  G4C_BENCH_SAME_GPU=1 timeout 900 python bench.py --gpus $n --steps 5 --warmup 2 2> $A/bench_${n}rank_plain_stderr.log | tail -1 > $A/${TAG}_bench_headline_${n}rank_plain_cmd.json
+  G4C_BENCH_SAME_GPU=1 timeout 900 python bench.py --full --gpus $n --steps 5 --warmup 2 2> $A/bench_${n}rank_plain_stderr.log | tail -1 > $A/${TAG}_bench_headline_${n}rank_plain_cmd.json
 done
 bash scripts/size_sweep.sh > $A/${TAG}_size_sweep.log 2>&1
 timeout 300 python scripts/step_breakdown.py > $A/${TAG}_step_breakdown.log 2>&1

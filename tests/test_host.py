@@ -268,6 +268,43 @@ def test_bench_starts_its_own_ranks_when_not_under_torchrun(monkeypatch):
     assert exc.value.code == 7 and seen == {"gpus": 2, "argv": ["--gpus", "2", "--steps", "2", "--warmup", "1"]}
 
 
+def test_bench_plain_run_options_and_output_dump(monkeypatch, tmp_path):
+    """A plain `bench.py` run leaves the extra measurements to --full; --dump-outputs writes the last timed step's block of the
+    caller's [N, nf * steps] result (float32), and a fixed, seeded sample of its rows when the whole block is over the limit."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("g4c_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+
+    class FakeRollout:
+        nf, steps_done = 3, 4
+
+        def __init__(self, n):
+            self.res = torch.arange(n * self.nf * 5, dtype=torch.float32).reshape(n, self.nf * 5)
+
+        def result(self):
+            return self.res
+    ro = FakeRollout(50)
+    bench.dump_outputs(str(tmp_path / "all"), ro, 1, 0)
+    got = np.load(tmp_path / "all" / "last_step_prediction.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ro.res[:, 9:12].numpy())
+    assert not (tmp_path / "all" / "last_step_prediction_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20 * (4 * 3 + 8))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), ro, 1, 0)
+    rows = np.load(tmp_path / "s1" / "last_step_prediction_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 20 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "last_step_prediction_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "last_step_prediction.npy"), ro.res[rows.astype(np.int64), 9:12].numpy())
+
+
 def test_range_watch_hands_every_hit_to_all_live_consumers_before_clearing():
     """ops.RangeWatch / f16_range_poll (host logic; the flag array stands on the CPU here): whoever reads the shared per-site flags
     distributes each hit to every live consumer that named the site, keeps what nobody asked for for f16_range_report, and only
