@@ -1653,6 +1653,11 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
     }
     if (bx6 && !force_tiles && ws_eligible(p, round1, agg != nullptr, save != nullptr, f16x2, row_count)) {
         // weight-stationary persistent kernel (mlp_ws.hip): pairs of 32-row tiles (whole segments with aggregation), one workgroup per CU
+        // (uniform segments, G4C_AGG_UNIFORM: ws_launch's dense mode derives segments as row / k over [0, p.M) and cannot honour a
+        // sub-range — refused like rs_eligible does.  A guard only: every entry point with an aggregation passes the whole row range.)
+        G4C_REQUIRE(!(agg && p.agg_deg >= 4 && p.agg_deg <= 8) || row_begin == 0, G4C_EINVAL,
+                    "g4c_mlp_forward: uniform segments (G4C_AGG_UNIFORM) need the whole row range, got rows [%lld, %lld)",
+                    (long long)row_begin, (long long)p.M);
         p.n_tiles = agg ? agg->n_tiles : (int)((row_count + 31) / 32);
         if (p.n_tiles == 0) return G4C_OK;          // (nothing launches: g4c_mlp_last_kernel stays G4C_KERNEL_NONE — ADVICE r04)
         g_last_kernel = G4C_KERNEL_MLP_WS;

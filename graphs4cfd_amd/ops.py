@@ -555,13 +555,54 @@ class RsOrderedRows(Tensor):
     """bf16 [n, 128] rows whose columns are in the row-split kernel's order (`_rs_k_order`): the compact message rows and the hoisted
     product tables its launches exchange (mlp_rs.hip, rounded-bf16 mode).  The subclass is only a tag that travels with the tensor
     (row slices and views keep it): `mlp_forward` hands such rows to that kernel as they are and restores the natural column order
-    for every other reader."""
+    for every other reader.
+
+    The tag survives only what keeps every row's 128 columns as they are (`_rs_keeps`): row slices / row gathers, views and reshapes to
+    [n, 128], contiguous, clone, detach and moves between devices.  Everything else — a column slice, a dtype change, a cat, a column
+    gather, arithmetic — returns a plain Tensor: a caller who reorders the columns by hand must not hand the reader a tag that makes it
+    reorder them a second time."""
 
     @staticmethod
     def tag(t: Tensor) -> Tensor:
         if t.dtype != torch.bfloat16 or t.dim() != 2 or t.size(1) != 128:
             raise ValueError("RsOrderedRows: bf16 [n, 128] rows only")
         return t.as_subclass(RsOrderedRows)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        with torch._C.DisableTorchFunctionSubclass():
+            out = func(*args, **kwargs)
+        if not isinstance(out, Tensor):
+            if isinstance(out, (tuple, list)):           # (split, chunk, unbind, ...: plain pieces)
+                return type(out)(t.as_subclass(Tensor) if isinstance(t, RsOrderedRows) else t for t in out)
+            return out
+        keep = (_rs_keeps(func, args, kwargs) and out.dtype == torch.bfloat16 and out.dim() == 2 and out.size(1) == 128)
+        if keep:
+            return out if isinstance(out, RsOrderedRows) else out.as_subclass(RsOrderedRows)
+        return out.as_subclass(Tensor) if isinstance(out, RsOrderedRows) else out
+
+
+def _row_index(ix) -> bool:
+    """`t[ix]` selects rows only: an int / slice / index tensor on dim 0, optionally followed by a full `:` on dim 1."""
+    if isinstance(ix, tuple):
+        if len(ix) == 1:
+            return _row_index(ix[0])
+        return len(ix) == 2 and _row_index(ix[0]) and isinstance(ix[1], slice) and ix[1] == slice(None)
+    return ix is not Ellipsis and ix is not None and not isinstance(ix, int)
+
+
+def _rs_keeps(func, args, kwargs) -> bool:
+    """Whether `func(*args, **kwargs)` keeps each row's columns where they were (RsOrderedRows.__torch_function__)."""
+    name = getattr(func, "__name__", "")
+    if name in ("contiguous", "clone", "detach", "cuda", "cpu", "to", "view", "reshape", "requires_grad_", "pin_memory"):
+        return True
+    if name == "__getitem__":
+        return _row_index(args[1])
+    if name in ("narrow", "index_select"):
+        dim = args[1] if len(args) > 1 else kwargs.get("dim")
+        return dim == 0
+    return False
 
 
 def rs_rows_to_natural(t: Tensor) -> Tensor:

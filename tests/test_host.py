@@ -369,6 +369,35 @@ def test_row_split_column_order_is_the_mfma_lane_order():
         ops.RsOrderedRows.tag(rows.float())
 
 
+def test_row_split_tag_is_dropped_by_anything_that_moves_columns():
+    """ops.RsOrderedRows tells a reader to put the columns back in feature order.  An operation that changes columns, their type or their
+    values must therefore return a plain Tensor — otherwise rows a caller already reordered by hand (t.index_select(1, inv)) would be
+    reordered a second time by mlp_forward, silently.  Row selections, views, contiguous, clone, detach and device moves keep it."""
+    import torch
+    from graphs4cfd_amd import ops
+    R = ops.RsOrderedRows
+    order = ops._rs_k_order(torch.device("cpu"))
+    inv = torch.argsort(order)
+    t = R.tag(torch.randn(12, 128).to(torch.bfloat16)[:, order].contiguous())
+    plain = {"column slice": t[:, :64], "column gather": t[:, inv], "float": t.float(), "cat dim 1": torch.cat([t, t], 1),
+             "cat dim 0": torch.cat([t, t], 0), "index_select dim 1": t.index_select(1, inv), "add": t + 1, "mul": t * 2, "neg": -t,
+             "sub tagged": t - t, "transpose": t.t(), "one row": t[3], "as_subclass": t.as_subclass(torch.Tensor), "split": torch.split(t, 5)[0]}
+    for name, x in plain.items():
+        assert type(x) is torch.Tensor, (name, type(x))
+    kept = {"row slice": t[2:7], "row slice, all columns": t[2:7, :], "row gather": t[torch.tensor([0, 5, 5])],
+            "index_select dim 0": t.index_select(0, torch.tensor([1, 2])), "narrow dim 0": t.narrow(0, 1, 4), "view": t.view(12, 128),
+            "reshape": t.reshape(-1, 128), "contiguous": t.contiguous(), "clone": t.clone(), "detach": t.detach(), "to device": t.to("cpu"),
+            "cpu": t.cpu(), "to same dtype": t.to(torch.bfloat16)}
+    for name, x in kept.items():
+        assert type(x) is R, (name, type(x))
+    assert torch.equal(kept["row slice"].as_subclass(torch.Tensor), t.as_subclass(torch.Tensor)[2:7])
+    # the reader's guard sees what the caller did: a hand-made natural copy is no longer tagged, rs_rows_to_natural's result is not either
+    by_hand = t.index_select(1, inv)
+    assert type(by_hand) is torch.Tensor and torch.equal(by_hand, ops.rs_rows_to_natural(t))
+    if torch.cuda.is_available():
+        assert type(t.to("cuda")) is R and type(t.cuda().cpu()) is R
+
+
 def test_remus_program_knows_which_run_outputs_only_mlps_read():
     """remus_gnn._mlp_readers_only: the edge latents a run of EdgeMPs leaves behind may be stored as the bf16 rows their readers round
     them to (rounded-bf16 mode) exactly where no UpEdgeMP projects them with fp32 arithmetic (edgeScalarToNodeVector, nn/blocks.py:420-430)
