@@ -51,6 +51,25 @@ class g4c_mlp_t(C.Structure):
                 ("range_flag", C.c_void_p), ("range_slot", C.c_int32)]
 
 
+WFMT_FP32, WFMT_F16X2, WFMT_BF16X3, WFMT_BF16_RS, WFMT_BF16_RS2, WFMT_BF16_RS2N, WFMT_BF16 = 0, 1, 2, 3, 4, 5, 6
+
+
+class g4c_mlp_io_t(C.Structure):
+    _fields_ = [("size", C.c_int32), ("act", C.c_int32), ("row_begin", C.c_int64), ("row_count", C.c_int64),
+                ("out", C.c_void_p), ("out_ld", C.c_int32), ("out_dtype", C.c_int32), ("out_idx", C.c_void_p),
+                ("resid", C.c_void_p), ("resid_ld", C.c_int32), ("resid_col0", C.c_int32),
+                ("n_heads", C.c_int32), ("head_ld", C.c_int32), ("head_dtype", C.c_int32), ("head_out", C.c_void_p * MAX_HEADS),
+                ("tile_rows", C.c_void_p), ("tile_seg", C.c_void_p), ("seg_off", C.c_void_p), ("n_tiles", C.c_int32),
+                ("agg", C.c_void_p), ("agg_ld", C.c_int32), ("agg_mode", C.c_int32),
+                ("n_save", C.c_int32), ("save", C.c_void_p * MAX_LAYERS), ("save_ld", C.c_int32),
+                ("mul", C.c_void_p * MAX_LAYERS), ("mul_ld", C.c_int32),
+                ("upd", C.POINTER(g4c_mlp_t)), ("v", C.c_void_p), ("v_ld", C.c_int32), ("v_act", C.c_int32),
+                ("v_out", C.c_void_p), ("v_out_ld", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(g4c_mlp_io_t), **kw)
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -64,53 +83,16 @@ _SIGNATURES = {
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_weighted_segment_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "g4c_mlp_pack_layer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+    "g4c_mlp_pack_layer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_bf16": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p,
-                                       C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_pack_layer_bx6": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                         C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_pack_layer_f16x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                           C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_bx6": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p,
-                                      C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_bx6_save": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                           C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
-                                           C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_heads_bx6": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                            C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_heads_bf16": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                            C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_heads_bf16_out": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                                 C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_heads_bf16_rows": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p]),
-    "g4c_mp_layer_forward_bx6": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                           C.POINTER(g4c_mlp_t), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_bf16_out": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_void_p]),
+    "g4c_mlp_run": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.POINTER(g4c_mlp_io_t), C.c_void_p]),
     "g4c_plan_tiles": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
-    "g4c_mlp_forward_bx6_agg": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                          C.c_void_p]),
-    "g4c_mlp_forward_bf16_agg": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                           C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p,
-                                  C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "g4c_mlp_bx6i_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_ws_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_small_launch_tiles": (C.c_int, [C.c_int]),
     "g4c_layer_norm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_debug_mean_div": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_mlp_last_kernel": (C.c_int, []),
-    "g4c_mlp_forward_rows": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_int64, C.c_int64,
-                                       C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                       C.c_int32, C.c_void_p]),
-    "g4c_mlp_forward_heads": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
-                                        C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "g4c_project_to_edges": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_edge_scalar_to_node_vector": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,

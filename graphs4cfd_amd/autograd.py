@@ -6,7 +6,7 @@ the passes (per MP layer at 100k nodes: the [E, 3H] concatenation, three [E, H] 
 
 Here the forward of a block stays ONE fused launch, recorded by a `torch.autograd.Function`:
 
-  * forward: g4c_mlp_forward_bx6_save — the fused kernel also writes each layer's output rows (SELU(hidden), pre-LayerNorm
+  * forward: g4c_mlp_run with g4c_mlp_io_t.save — the fused kernel also writes each layer's output rows (SELU(hidden), pre-LayerNorm
     rows), so the backward recomputes no product (SAVE_ACTIVATIONS; False keeps only block inputs / outputs and
     re-forms the hidden layers in the backward with single-layer launches of the same kernel);
   * weight + bias gradients of the 128-wide layers: g4c_weight_grad (one pass over dZ and A, fp32 MFMA, partial tiles added in a
@@ -118,7 +118,7 @@ def segment_broadcast(dout: Tensor, csr, mean: bool, n_src_rows: int) -> Tensor:
     return dsrc
 
 
-# keep the hidden activations of every fused MLP from the forward launch (g4c_mlp_forward_bx6_save) instead of recomputing them
+# keep the hidden activations of every fused MLP from the forward launch (g4c_mlp_io_t.save) instead of recomputing them
 # in the backward pass: ~3 x [rows, 128] fp32 more per MLP between the passes (100k nodes, 3-scale: 7.3 -> 27.5 GB peak), no recompute
 # GEMMs.  SAVE_ACTIVATIONS = False: the memory-light recompute path.
 SAVE_ACTIVATIONS = True
@@ -170,7 +170,7 @@ FUSED_CHAIN = True
 
 
 def backward_chain(g: Tensor, weights: Sequence[Tensor], acts: Sequence[Tensor], w_dense: Tensor):
-    """Hidden layers of an MLP backward in ONE launch of the fused kernel (g4c_mlp_forward_bx6_save with `mul`):
+    """Hidden layers of an MLP backward in ONE launch of the fused kernel (g4c_mlp_io_t.save with `mul`):
         D[l] = (D[l+1] W[l]) * selu'(acts[l])   for l = L-1 .. 1,      gX = D[1] W_dense
     with g = D[L] [M, 128], W[l] [128, 128], acts[l] the SELU outputs [M, 128], W_dense [128, 128] the first layer's columns of
     the dense input block.  Returns ({l: D[l]}, gX).  The transposed weights are packed last layer first; every D[l] leaves

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bx6i_kernel(const Params p) {
             }
         }
         if (!BX6I_ROW_STORES && p.out && myrow < nrow[t]) {
-            const long long orow = (!AGG && p.out_idx) ? p.out_idx[row0[t] + myrow] : row0[t] + myrow;      // (g4c_mlp_forward's out_idx)
+            const long long orow = (!AGG && p.out_idx) ? p.out_idx[row0[t] + myrow] : row0[t] + myrow;      // (g4c_mlp_io_t.out_idx)
             float *op = p.out + orow * p.out_ld + cb;
 #pragma unroll
             for (int c = 0; c < 16; c += 4) {
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bx6i_kernel(const Params p) {
     }
     BI_STAMP(21);
     if (!AGG && BX6I_ROW_STORES && p.out) {
-        // whole rows per store instruction from the LDS copy (as with AGG below); out_idx scatters them (g4c_mlp_forward's out_idx)
+        // whole rows per store instruction from the LDS copy (as with AGG below); out_idx scatters them (g4c_mlp_io_t.out_idx)
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -528,7 +528,7 @@ int bx6i_launch(const Params &p, bool agg, bool f16x2, hipStream_t st) {
     if (f16x2) return G4C_EUNSUPPORTED;
     if (agg) G4C_BX6I_LAUNCH(true, 3); else G4C_BX6I_LAUNCH(false, 3);
 #undef G4C_BX6I_LAUNCH
-    return g4c::check_launch("g4c_mlp_forward (bx6i)");
+    return g4c::check_launch("g4c_mlp_run (bx6i)");
 }
 
 }  // namespace g4cm

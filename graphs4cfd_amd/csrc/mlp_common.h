@@ -83,7 +83,7 @@ struct Params {
     // narrow input blocks of the first layer, multiplied in fp32 on the vector ALUs (bf16x6 kernel)
     NarSrc nar[G4C_MAX_SRC];
     int n_nar;
-    // training forward (g4c_mlp_forward_bx6_save): save[l] (or null) receives layer l's output rows, [M, 128] fp32 — the SELU
+    // training forward (g4c_mlp_io_t.save): save[l] (or null) receives layer l's output rows, [M, 128] fp32 — the SELU
     // activations of a hidden layer, the pre-LayerNorm rows of the last one — so the backward pass recomputes nothing
     float *save[G4C_MAX_LAYERS];
     int save_ld;
@@ -97,7 +97,7 @@ struct Params {
     int range_slot;
 };
 
-// The node update fused behind the message launch of an MP layer (g4c_mp_layer_forward_bx6, mlp_ws_kernel<.., NODE>): after its
+// The node update fused behind the message launch of an MP layer (g4c_mlp_io_t.upd, mlp_ws_kernel<.., NODE>): after its
 // last tile pair a workgroup runs the node MLP ([aggregate | v] -> Linear/SELU chain -> LayerNorm -> activation, + heads) on the targets
 // whose aggregates it has just written.  Same depth as the message MLP; f16x3 stream; blocks of the stream in the order
 // [aggregate, v], layer 2, (layer 3), heads.

@@ -204,7 +204,7 @@ __device__ __forceinline__ void split_finish(const Params &p, float *sH, const f
     // (each wave reads back only the rows it normalised itself: no barrier needed)
 
     // ---------------------------------------------------------------- store this wave's rows
-    if (p.out == nullptr) return;          // (only the aggregate of the rows is wanted: g4c_mlp_forward_bx6_agg with out == NULL)
+    if (p.out == nullptr) return;          // (only the aggregate of the rows is wanted: g4c_mlp_io_t.agg with out == NULL)
     const bool fast = (n_out == NP) && ((p.out_ld & 3) == 0) && (((uintptr_t)p.out & 15) == 0) && (p.resid == nullptr);
     if (p.out_bf16) {
         // rows kept in bf16 (the rounded-bf16 mode's message tensors: their consumer rounds them to bf16 anyway): 8 bytes per lane
@@ -540,13 +540,13 @@ __global__ void pack_layer_kernel(const float *__restrict__ W, int n_out, int k_
 
 
 // ======================================================================================================
-// fp32-accurate MLP on the bf16 matrix pipe ("bf16x6", opt-in: g4c_mlp_forward_bx6).  Every fp32 operand is split
+// fp32-accurate MLP on the bf16 matrix pipe ("bf16x6", opt-in: G4C_WFMT_BF16X3).  Every fp32 operand is split
 // EXACTLY into three bf16 terms x = h + m + l (8 + 8 + 8 significand bits); of the nine partial products the six
 // largest are formed (hh, hm, mh, mm, hl, lh — each exact in fp32) and accumulated in fp32 by
 // v_mfma_f32_32x32x16_bf16.  The dropped terms (ml, lm, ll) are <= 2^-23 relative: the same order as ONE fp32 rounding,
 // so the result is as accurate as the fp32-MFMA kernel (tests compare both against fp64), at 6 x 32 = 192 MFMA cycles
 // per 16 k instead of 8 x 64 = 512.  A whole 128-k block is staged per barrier pair; weights are split at pack time
-// (g4c_mlp_pack_layer_bx6: [128-k block][column tile][16-k step][plane][lane][8], 6 bytes per weight).
+// (g4c_mlp_pack_layer: [128-k block][column tile][16-k step][plane][lane][8], 6 bytes per weight).
 // Template parameter SP = 3: the above.  SP = 1: only the leading terms (operands ROUNDED to bf16, one product) — the
 // opt-in "bf16" mode of BASELINE config 3 ("bf16 edge-MLP MFMA", ~1e-2 deviation) on the same stream and structure.
 // weight ring depth in 16-k steps.  2 where the launch fills the chip (4 / 8 measured slower: 483 / 563 us against 446 on the level-1
@@ -1163,246 +1163,41 @@ __global__ void pack_layer_bx6_kernel(const float *__restrict__ W, int n_out, in
 }  // namespace
 
 extern "C" int g4c_mlp_pack_layer(const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
-                                  const int32_t *seg_negate, int32_t n_seg, float *packed,
+                                  const int32_t *seg_negate, int32_t n_seg, int32_t w_format, void *packed,
                                   int32_t k_pad, int32_t n_pad, void *stream) {
     G4C_REQUIRE(W && packed && seg_width, G4C_EINVAL, "g4c_mlp_pack_layer: null pointer");
     G4C_REQUIRE(n_seg >= 1 && n_seg <= G4C_MAX_SRC, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer: %d input blocks (max %d)", n_seg, G4C_MAX_SRC);
     G4C_REQUIRE(n_out >= 1 && n_out <= NP, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer: layer width %d unsupported (max 128)", n_out);
-    G4C_REQUIRE(n_pad == NP, G4C_EINVAL, "g4c_mlp_pack_layer: n_pad must be 128, got %d", n_pad);
+    G4C_REQUIRE(w_format >= G4C_WFMT_FP32 && w_format <= G4C_WFMT_BF16, G4C_EINVAL, "g4c_mlp_pack_layer: unknown w_format %d", w_format);
+    const bool planes = w_format != G4C_WFMT_FP32;     // the three-plane bf16 stream: every input block padded to 128 k
+    if (planes)
+        G4C_REQUIRE(n_pad == NP && k_pad == NP * n_seg, G4C_EINVAL, "g4c_mlp_pack_layer: n_pad must be 128 and k_pad 128 per input block (got %d, %d)",
+                    n_pad, k_pad);
+    else
+        G4C_REQUIRE(n_pad == NP, G4C_EINVAL, "g4c_mlp_pack_layer: n_pad must be 128, got %d", n_pad);
     PackSegs segs;
     segs.n_seg = n_seg;
     int ksum = 0, kpsum = 0;
     for (int s = 0; s < n_seg; ++s) {
-        G4C_REQUIRE(seg_width[s] > 0, G4C_EINVAL, "g4c_mlp_pack_layer: empty input block %d", s);
+        if (planes)
+            G4C_REQUIRE(seg_width[s] > 0 && seg_width[s] <= NP, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer: input block %d is %d wide (1..128)", s, seg_width[s]);
+        else
+            G4C_REQUIRE(seg_width[s] > 0, G4C_EINVAL, "g4c_mlp_pack_layer: empty input block %d", s);
         segs.width[s] = seg_width[s];
-        segs.wpad[s] = (seg_width[s] + KC - 1) / KC * KC;
+        segs.wpad[s] = planes ? NP : (seg_width[s] + KC - 1) / KC * KC;
         segs.neg[s] = seg_negate ? seg_negate[s] : 0;
         ksum += segs.width[s];
         kpsum += segs.wpad[s];
     }
     G4C_REQUIRE(ksum == k_in, G4C_EINVAL, "g4c_mlp_pack_layer: blocks sum to %d columns, weight has %d", ksum, k_in);
     G4C_REQUIRE(kpsum <= k_pad && k_pad % KC == 0, G4C_EINVAL, "g4c_mlp_pack_layer: k_pad %d too small for %d (or not a multiple of 32)", k_pad, kpsum);
-    const int total = k_pad * NP;
+    const dim3 grid((k_pad * NP + 255) / 256), blk(256);
+    hipStream_t st = (hipStream_t)stream;
     g4c::DeviceGuard on_device(packed);
-    pack_layer_kernel<<<dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(W, n_out, k_in, segs, packed, k_pad);
+    if (!planes) pack_layer_kernel<<<grid, blk, 0, st>>>(W, n_out, k_in, segs, (float *)packed, k_pad);
+    else if (w_format == G4C_WFMT_F16X2) pack_layer_bx6_kernel<true><<<grid, blk, 0, st>>>(W, n_out, k_in, segs, (__bf16 *)packed, k_pad);
+    else pack_layer_bx6_kernel<false><<<grid, blk, 0, st>>>(W, n_out, k_in, segs, (__bf16 *)packed, k_pad);
     return g4c::check_launch("g4c_mlp_pack_layer");
-}
-
-static int pack_layer_16(bool f16, const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
-                         const int32_t *seg_negate, int32_t n_seg, void *packed, int32_t k_pad, int32_t n_pad, void *stream);
-
-extern "C" int g4c_mlp_pack_layer_bx6(const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
-                                      const int32_t *seg_negate, int32_t n_seg, void *packed,
-                                      int32_t k_pad, int32_t n_pad, void *stream) {
-    return pack_layer_16(false, W, n_out, k_in, seg_width, seg_negate, n_seg, packed, k_pad, n_pad, stream);
-}
-
-extern "C" int g4c_mlp_pack_layer_f16x3(const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
-                                        const int32_t *seg_negate, int32_t n_seg, void *packed,
-                                        int32_t k_pad, int32_t n_pad, void *stream) {
-    return pack_layer_16(true, W, n_out, k_in, seg_width, seg_negate, n_seg, packed, k_pad, n_pad, stream);
-}
-
-static int pack_layer_16(bool f16, const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
-                         const int32_t *seg_negate, int32_t n_seg, void *packed, int32_t k_pad, int32_t n_pad, void *stream) {
-    G4C_REQUIRE(W && packed && seg_width, G4C_EINVAL, "g4c_mlp_pack_layer_bf16: null pointer");
-    G4C_REQUIRE(n_seg >= 1 && n_seg <= G4C_MAX_SRC, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer_bf16: %d input blocks (max %d)", n_seg, G4C_MAX_SRC);
-    G4C_REQUIRE(n_out >= 1 && n_out <= NP, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer_bf16: layer width %d unsupported (max 128)", n_out);
-    G4C_REQUIRE(n_pad == NP && k_pad == NP * n_seg, G4C_EINVAL, "g4c_mlp_pack_layer_bf16: n_pad must be 128 and k_pad 128 per input block (got %d, %d)", n_pad, k_pad);
-    PackSegs segs;
-    segs.n_seg = n_seg;
-    int ksum = 0;
-    for (int s = 0; s < n_seg; ++s) {
-        G4C_REQUIRE(seg_width[s] > 0 && seg_width[s] <= NP, G4C_EUNSUPPORTED, "g4c_mlp_pack_layer_bf16: input block %d is %d wide (1..128)", s, seg_width[s]);
-        segs.width[s] = seg_width[s];
-        segs.wpad[s] = NP;
-        segs.neg[s] = seg_negate ? seg_negate[s] : 0;
-        ksum += segs.width[s];
-    }
-    G4C_REQUIRE(ksum == k_in, G4C_EINVAL, "g4c_mlp_pack_layer_bf16: blocks sum to %d columns, weight has %d", ksum, k_in);
-    const int total = k_pad * NP;
-    g4c::DeviceGuard on_device(packed);
-    if (f16) pack_layer_bx6_kernel<true><<<dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(W, n_out, k_in, segs, (__bf16 *)packed, k_pad);
-    else pack_layer_bx6_kernel<false><<<dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(W, n_out, k_in, segs, (__bf16 *)packed, k_pad);
-    return g4c::check_launch("g4c_mlp_pack_layer_bx6");
-}
-
-extern "C" int g4c_mlp_forward_rows(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                    int64_t row_begin, int64_t row_count, int32_t tile_rows,
-                                    float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                                    const float *resid, int32_t resid_ld, int32_t resid_col0, void *stream);
-
-extern "C" int g4c_mlp_forward(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                               float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                               const float *resid, int32_t resid_ld, int32_t resid_col0, void *stream) {
-    // fp32 MFMA: one kernel family, the 4-wave column split on 32-row tiles (measured the fastest or within 2 % of the fastest of
-    // the variants tried in round 1 at every launch size from 8k to 1M rows)
-    return g4c_mlp_forward_rows(mlp, srcs, n_src, n_rows, 0, n_rows, 324, out, out_ld, out_idx, act, resid, resid_ld, resid_col0, stream);
-}
-
-struct SaveArgs {          // training forward / backward chain (g4c_mlp_forward_bx6_save)
-    float *const *ptr;     // n_layers entries, each may be null
-    int32_t ld;
-    const float *const *mul;   // null, or n_layers entries, each may be null
-    int32_t mul_ld;
-};
-
-struct AggArgs {           // fused aggregation (g4c_mlp_forward_bx6_agg); all null / 0 otherwise
-    const int32_t *tile_rows, *tile_seg, *seg_off;
-    int32_t n_tiles;
-    float *out;
-    int32_t out_ld, mean;
-    int32_t rows_bf16;       // the MLP's output rows are stored as bf16 (g4c_mlp_forward_bf16_agg, out_dtype)
-};
-// rounded-bf16 mode, plain / heads launches: bf16 output rows (g4c_mlp_forward_bf16_out) and bf16 head rows (g4c_mlp_forward_heads_bf16_out)
-static thread_local int g_out_dtype = 0, g_head_dtype = 0;
-
-struct NodeArgs {          // the node update fused behind the message launch (g4c_mp_layer_forward_bx6)
-    const g4c_mlp_t *upd;
-    const float *v;
-    int32_t v_ld, act;
-    float *v_out;
-    int32_t v_out_ld;
-    const void *head_w;
-    int32_t n_heads;
-    float *const *head_out;
-    int32_t head_ld;
-};
-
-static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                      int64_t row_begin, int64_t row_count, int32_t tile_rows,
-                      float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                      const float *resid, int32_t resid_ld, int32_t resid_col0,
-                      const float *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream,
-                      const AggArgs *agg = nullptr, const SaveArgs *save = nullptr, const NodeArgs *node = nullptr);
-
-extern "C" int g4c_mlp_forward_rows(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                    int64_t row_begin, int64_t row_count, int32_t tile_rows,
-                                    float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                                    const float *resid, int32_t resid_ld, int32_t resid_col0, void *stream) {
-    return mlp_launch(mlp, srcs, n_src, n_rows, row_begin, row_count, tile_rows, out, out_ld, out_idx, act, resid, resid_ld,
-                      resid_col0, nullptr, 0, nullptr, 0, stream);
-}
-
-extern "C" int g4c_mlp_forward_heads(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                     float *out, int32_t out_ld, int32_t act,
-                                     const float *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream) {
-    G4C_REQUIRE(n_heads >= 1 && n_heads <= G4C_MAX_HEADS && head_w && head_out, G4C_EINVAL, "g4c_mlp_forward_heads: bad heads (n=%d)", n_heads);
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 324, out, out_ld, nullptr, act, nullptr, 0, 0,
-                      head_w, n_heads, head_out, head_ld, stream);
-}
-
-extern "C" int g4c_mlp_forward_bf16(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                    float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                                    const float *resid, int32_t resid_ld, int32_t resid_col0, void *stream) {
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, out, out_ld, out_idx, act, resid, resid_ld, resid_col0,
-                      nullptr, 0, nullptr, 0, stream);
-}
-
-extern "C" int g4c_mlp_forward_heads_bx6(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                         float *out, int32_t out_ld, int32_t act,
-                                         const void *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream) {
-    G4C_REQUIRE(n_heads >= 1 && n_heads <= G4C_MAX_HEADS && head_w && head_out, G4C_EINVAL, "g4c_mlp_forward_heads_bx6: bad heads (n=%d)", n_heads);
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3248, out, out_ld, nullptr, act, nullptr, 0, 0,
-                      (const float *)head_w, n_heads, head_out, head_ld, stream);
-}
-
-extern "C" int g4c_mlp_forward_heads_bf16(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                          float *out, int32_t out_ld, int32_t act,
-                                          const void *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream) {
-    G4C_REQUIRE(n_heads >= 1 && n_heads <= G4C_MAX_HEADS && head_w && head_out, G4C_EINVAL, "g4c_mlp_forward_heads_bf16: bad heads (n=%d)", n_heads);
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, out, out_ld, nullptr, act, nullptr, 0, 0,
-                      (const float *)head_w, n_heads, head_out, head_ld, stream);
-}
-
-extern "C" int g4c_mlp_forward_heads_bf16_out(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                              float *out, int32_t out_ld, int32_t act,
-                                              const void *head_w, int32_t n_heads, void *const *head_out, int32_t head_ld, int32_t head_dtype,
-                                              void *stream) {
-    G4C_REQUIRE(n_heads >= 1 && n_heads <= G4C_MAX_HEADS && head_w && head_out, G4C_EINVAL, "g4c_mlp_forward_heads_bf16_out: bad heads (n=%d)", n_heads);
-    G4C_REQUIRE(head_dtype == G4C_DTYPE_F32 || head_dtype == G4C_DTYPE_BF16, G4C_EINVAL, "g4c_mlp_forward_heads_bf16_out: unknown head_dtype %d", head_dtype);
-    g_head_dtype = head_dtype;
-    const int rc = mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, out, out_ld, nullptr, act, nullptr, 0, 0,
-                              (const float *)head_w, n_heads, (float *const *)head_out, head_ld, stream);
-    g_head_dtype = 0;
-    return rc;
-}
-
-extern "C" int g4c_mlp_forward_heads_bf16_rows(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                               void *out, int32_t out_ld, int32_t out_dtype, int32_t act,
-                                               const void *head_w, int32_t n_heads, void *const *head_out, int32_t head_ld, int32_t head_dtype,
-                                               void *stream) {
-    G4C_REQUIRE(n_heads >= 1 && n_heads <= G4C_MAX_HEADS && head_w && head_out, G4C_EINVAL, "g4c_mlp_forward_heads_bf16_rows: bad heads (n=%d)", n_heads);
-    G4C_REQUIRE((head_dtype == G4C_DTYPE_F32 || head_dtype == G4C_DTYPE_BF16) && (out_dtype == G4C_DTYPE_F32 || out_dtype == G4C_DTYPE_BF16), G4C_EINVAL,
-                "g4c_mlp_forward_heads_bf16_rows: unknown dtype (out %d, heads %d)", out_dtype, head_dtype);
-    g_head_dtype = head_dtype; g_out_dtype = out_dtype;
-    const int rc = mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, (float *)out, out_ld, nullptr, act, nullptr, 0, 0,
-                              (const float *)head_w, n_heads, (float *const *)head_out, head_ld, stream);
-    g_head_dtype = 0; g_out_dtype = 0;
-    return rc;
-}
-
-extern "C" int g4c_mlp_forward_bf16_out(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                        void *out, int32_t out_ld, int32_t out_dtype, int32_t act, void *stream) {
-    G4C_REQUIRE(out_dtype == G4C_DTYPE_F32 || out_dtype == G4C_DTYPE_BF16, G4C_EINVAL, "g4c_mlp_forward_bf16_out: unknown out_dtype %d", out_dtype);
-    g_out_dtype = out_dtype;
-    const int rc = mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, (float *)out, out_ld, nullptr, act, nullptr, 0, 0,
-                              nullptr, 0, nullptr, 0, stream);
-    g_out_dtype = 0;
-    return rc;
-}
-
-extern "C" int g4c_mlp_forward_bx6_agg(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                       float *out, int32_t out_ld, int32_t act,
-                                       const int32_t *tile_rows, const int32_t *tile_seg, const int32_t *seg_off, int32_t n_tiles,
-                                       float *agg, int32_t agg_ld, int32_t agg_mean, void *stream) {
-    G4C_REQUIRE(tile_rows && tile_seg && seg_off && agg && n_tiles >= 0 && agg_ld >= NP, G4C_EINVAL, "g4c_mlp_forward_bx6_agg: bad aggregation plan");
-    const AggArgs a{tile_rows, tile_seg, seg_off, n_tiles, agg, agg_ld, agg_mean, 0};
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3248, out, out_ld, nullptr, act, nullptr, 0, 0,
-                      nullptr, 0, nullptr, 0, stream, &a);
-}
-
-extern "C" int g4c_mp_layer_forward_bx6(const g4c_mlp_t *msg, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                        float *e_out, int32_t e_ld,
-                                        const int32_t *tile_rows, const int32_t *tile_seg, const int32_t *seg_off, int32_t n_tiles,
-                                        float *agg, int32_t agg_ld, int32_t agg_mean,
-                                        const g4c_mlp_t *upd, const float *v, int32_t v_ld, int32_t act, float *v_out, int32_t v_out_ld,
-                                        const void *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream) {
-    G4C_REQUIRE(tile_rows && tile_seg && seg_off && agg && n_tiles >= 0 && agg_ld >= NP, G4C_EINVAL, "g4c_mp_layer_forward_bx6: bad aggregation plan");
-    const AggArgs a{tile_rows, tile_seg, seg_off, n_tiles, agg, agg_ld, agg_mean, 0};
-    const NodeArgs nd{upd, v, v_ld, act, v_out, v_out_ld, head_w, n_heads, head_out, head_ld};
-    return mlp_launch(msg, srcs, n_src, n_rows, 0, n_rows, 3248, e_out, e_ld ? e_ld : NP, nullptr, G4C_ACT_NONE, nullptr, 0, 0,
-                      nullptr, 0, nullptr, 0, stream, &a, nullptr, &nd);
-}
-
-extern "C" int g4c_mlp_forward_bf16_agg(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                        void *out, int32_t out_ld, int32_t out_dtype, int32_t act,
-                                        const int32_t *tile_rows, const int32_t *tile_seg, const int32_t *seg_off, int32_t n_tiles,
-                                        float *agg, int32_t agg_ld, int32_t agg_mean, void *stream) {
-    G4C_REQUIRE(tile_rows && tile_seg && seg_off && agg && n_tiles >= 0 && agg_ld >= NP, G4C_EINVAL, "g4c_mlp_forward_bf16_agg: bad aggregation plan");
-    G4C_REQUIRE(out_dtype == G4C_DTYPE_F32 || out_dtype == G4C_DTYPE_BF16 || out_dtype == G4C_DTYPE_BF16_SELU, G4C_EINVAL,
-                "g4c_mlp_forward_bf16_agg: unknown out_dtype %d", out_dtype);
-    G4C_REQUIRE(out_dtype != G4C_DTYPE_BF16_SELU || act == G4C_ACT_NONE, G4C_EINVAL, "g4c_mlp_forward_bf16_agg: G4C_DTYPE_BF16_SELU with an output activation");
-    const AggArgs a{tile_rows, tile_seg, seg_off, n_tiles, agg, agg_ld, agg_mean, out_dtype};
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3216, (float *)out, out_ld, nullptr, act, nullptr, 0, 0,
-                      nullptr, 0, nullptr, 0, stream, &a);
-}
-
-extern "C" int g4c_mlp_forward_bx6_save(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                        float *out, int32_t out_ld, int32_t act, const float *resid, int32_t resid_ld,
-                                        int32_t resid_col0, float *const *save, int32_t save_ld, const float *const *mul,
-                                        int32_t mul_ld, void *stream) {
-    G4C_REQUIRE(save, G4C_EINVAL, "g4c_mlp_forward_bx6_save: null save list");
-    const SaveArgs sv{save, save_ld, mul, mul_ld};
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3248, out, out_ld, nullptr, act, resid, resid_ld, resid_col0,
-                      nullptr, 0, nullptr, 0, stream, nullptr, &sv);
-}
-
-extern "C" int g4c_mlp_forward_bx6(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                                   float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                                   const float *resid, int32_t resid_ld, int32_t resid_col0, void *stream) {
-    return mlp_launch(mlp, srcs, n_src, n_rows, 0, n_rows, 3248, out, out_ld, out_idx, act, resid, resid_ld, resid_col0,
-                      nullptr, 0, nullptr, 0, stream);
 }
 
 static thread_local int g_last_kernel = G4C_KERNEL_NONE;
@@ -1416,36 +1211,49 @@ extern "C" int g4c_mlp_small_launch_tiles(int n_tiles) {
     return prev;
 }
 
-static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows,
-                      int64_t row_begin, int64_t row_count, int32_t tile_rows,
-                      float *out, int32_t out_ld, const int32_t *out_idx, int32_t act,
-                      const float *resid, int32_t resid_ld, int32_t resid_col0,
-                      const float *head_w, int32_t n_heads, float *const *head_out, int32_t head_ld, void *stream,
-                      const AggArgs *agg, const SaveArgs *save, const NodeArgs *node) {
+static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows, const g4c_mlp_io_t *io,
+                      void *stream) {
     g_last_kernel = G4C_KERNEL_NONE;
-    const bool force_tiles = (tile_rows == 3249) || (tile_rows == 3217);     // 3248 / 3216 on the 32-row-tile kernel only (tests, A/B)
-    if (force_tiles) tile_rows -= 1;
-    const bool round1 = (tile_rows == 3216);     // operands rounded to bf16: only the leading plane of the stream is used
-    const bool bx6 = (tile_rows == 3248) || round1;   // weights: the three-plane stream of g4c_mlp_pack_layer_bx6
-    const bool rs_fmt = round1 && mlp && mlp->w_format == G4C_WFMT_BF16_RS;     // the rounded-bf16 stream in the row-split kernel's k order: that kernel only
-    const bool rs2_fmt = round1 && mlp && (mlp->w_format == G4C_WFMT_BF16_RS2 || mlp->w_format == G4C_WFMT_BF16_RS2N);     // ... its update-MLP form
-    const bool f16x2 = bx6 && mlp && mlp->w_format == G4C_WFMT_F16X2;     // the stream holds the two-way fp16 split (g4c_mlp_pack_layer_f16x3)
-    G4C_REQUIRE(!(f16x2 && round1), G4C_EINVAL, "g4c_mlp_forward_bf16: the weights were packed by g4c_mlp_pack_layer_f16x3 (fp16 planes)");
-    G4C_REQUIRE(!mlp || mlp->w_format == 0 || f16x2 || rs_fmt || rs2_fmt, G4C_EINVAL, "g4c_mlp_forward: w_format %d does not match this entry point", mlp->w_format);
-    const bool bf16 = bx6;                       // input blocks padded to 128 k
+    G4C_REQUIRE(io && io->size == (int32_t)sizeof(g4c_mlp_io_t), G4C_EINVAL,
+                "g4c_mlp_run: io->size %d, this library's g4c_mlp_io_t has %d bytes (a binding out of step with g4c.h)", io ? io->size : 0,
+                (int)sizeof(g4c_mlp_io_t));
+    G4C_REQUIRE(mlp && srcs, G4C_EINVAL, "g4c_mlp_run: null pointer");
+    const int fmt = mlp->w_format;
+    G4C_REQUIRE(fmt >= G4C_WFMT_FP32 && fmt <= G4C_WFMT_BF16, G4C_EINVAL, "g4c_mlp_run: unknown w_format %d", fmt);
+    const bool rs_fmt = fmt == G4C_WFMT_BF16_RS;     // the rounded-bf16 stream in the row-split kernel's k order: that kernel only
+    const bool rs2_fmt = fmt == G4C_WFMT_BF16_RS2 || fmt == G4C_WFMT_BF16_RS2N;     // ... its update-MLP form
+    const bool round1 = fmt == G4C_WFMT_BF16 || rs_fmt || rs2_fmt;     // operands rounded to bf16: only the leading plane of the stream is used
+    const bool f16x2 = fmt == G4C_WFMT_F16X2;    // the stream holds the two-way fp16 split
+    const bool bx6 = fmt != G4C_WFMT_FP32;       // the three-plane stream, input blocks padded to 128 k
     const int wbytes = bx6 ? 6 : 4;
-    if (bf16) tile_rows = 324;
-    G4C_REQUIRE(tile_rows == 324, G4C_EINVAL, "g4c_mlp_forward_rows: tile_rows must be 324 (32-row tiles on 4 waves; the one fp32-MFMA kernel), got %d", tile_rows);
+    const int64_t row_begin = io->row_begin, row_count = io->row_count;
     G4C_REQUIRE(row_begin >= 0 && row_count >= 0 && row_begin + row_count <= n_rows && row_begin % 32 == 0, G4C_EINVAL,
-                "g4c_mlp_forward_rows: bad row range [%lld, +%lld) of %lld", (long long)row_begin, (long long)row_count, (long long)n_rows);
-    G4C_REQUIRE(mlp && srcs, G4C_EINVAL, "g4c_mlp_forward: null pointer");
-    G4C_REQUIRE(n_src >= 1 && n_src <= G4C_MAX_SRC, G4C_EUNSUPPORTED, "g4c_mlp_forward: %d sources (max %d)", n_src, G4C_MAX_SRC);
+                "g4c_mlp_run: bad row range [%lld, +%lld) of %lld (row_begin must be a multiple of 32)", (long long)row_begin,
+                (long long)row_count, (long long)n_rows);
+    G4C_REQUIRE(n_src >= 1 && n_src <= G4C_MAX_SRC, G4C_EUNSUPPORTED, "g4c_mlp_run: %d sources (max %d)", n_src, G4C_MAX_SRC);
     G4C_REQUIRE(mlp->n_layers >= 1 && mlp->n_layers <= G4C_MAX_LAYERS, G4C_EUNSUPPORTED,
-                "g4c_mlp_forward: %d layers (supported 1..%d)", mlp->n_layers, G4C_MAX_LAYERS);
-    G4C_REQUIRE(n_rows >= 0 && n_rows < (1LL << 31), G4C_EINVAL, "g4c_mlp_forward: n_rows %lld out of range", (long long)n_rows);
-    G4C_REQUIRE(act >= 0 && act <= 2, G4C_EINVAL, "g4c_mlp_forward: bad activation %d", act);
+                "g4c_mlp_run: %d layers (supported 1..%d)", mlp->n_layers, G4C_MAX_LAYERS);
+    G4C_REQUIRE(n_rows >= 0 && n_rows < (1LL << 31), G4C_EINVAL, "g4c_mlp_run: n_rows %lld out of range", (long long)n_rows);
+    const int act = io->act;
+    G4C_REQUIRE(act >= 0 && act <= 2, G4C_EINVAL, "g4c_mlp_run: bad activation %d", act);
+    const bool agg = io->agg != nullptr, save = io->n_save != 0, node = io->upd != nullptr;
+    const int n_heads = io->n_heads;
+    G4C_REQUIRE(n_heads >= 0 && n_heads <= G4C_MAX_HEADS, G4C_EINVAL, "g4c_mlp_run: bad heads (n=%d)", n_heads);
+    G4C_REQUIRE((row_begin == 0 && row_count == n_rows) || (!agg && !save && !node && !n_heads && !io->out_dtype), G4C_EUNSUPPORTED,
+                "g4c_mlp_run: a row sub-range needs a plain launch (no heads / aggregation / save / upd / out_dtype)");
+    G4C_REQUIRE(!agg || (io->tile_rows && io->tile_seg && io->seg_off && io->n_tiles >= 0 && io->agg_ld >= NP), G4C_EINVAL,
+                "g4c_mlp_run: bad aggregation plan");
+    G4C_REQUIRE(io->out_dtype == G4C_DTYPE_F32 || io->out_dtype == G4C_DTYPE_BF16 || io->out_dtype == G4C_DTYPE_BF16_SELU, G4C_EINVAL,
+                "g4c_mlp_run: unknown out_dtype %d", io->out_dtype);
+    G4C_REQUIRE(io->out_dtype != G4C_DTYPE_BF16_SELU || (agg && act == G4C_ACT_NONE), G4C_EINVAL,
+                "g4c_mlp_run: G4C_DTYPE_BF16_SELU needs the fused aggregation and no output activation");
+    G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 || io->head_dtype == G4C_DTYPE_BF16, G4C_EINVAL, "g4c_mlp_run: unknown head_dtype %d", io->head_dtype);
     if (n_rows == 0) return G4C_OK;
-    G4C_REQUIRE(out || agg, G4C_EINVAL, "g4c_mlp_forward: null output");
+    float *const out = (float *)io->out;
+    const int32_t out_ld = io->out_ld;
+    const float *const resid = io->resid;
+    const int32_t *const out_idx = io->out_idx;
+    G4C_REQUIRE(out || agg, G4C_EINVAL, "g4c_mlp_run: null output");
     g4c::DeviceGuard on_device(mlp->w[0]);
     Params p;
     int kp = 0;
@@ -1456,11 +1264,11 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
     for (int s = 0; s < n_src; ++s) {
         const g4c_src_t &g = srcs[s];
         G4C_REQUIRE(g.ptr && g.width > 0 && g.ld >= g.col0 + g.width && g.col0 >= 0, G4C_EINVAL,
-                    "g4c_mlp_forward: bad source %d (width=%d ld=%d col0=%d)", s, g.width, g.ld, g.col0);
+                    "g4c_mlp_run: bad source %d (width=%d ld=%d col0=%d)", s, g.width, g.ld, g.col0);
         if (g.additive == 2) {
-            G4C_REQUIRE(bx6, G4C_EUNSUPPORTED, "g4c_mlp_forward: narrow sources (additive == 2) need the bf16x6 kernels");
+            G4C_REQUIRE(bx6, G4C_EUNSUPPORTED, "g4c_mlp_run: narrow sources (additive == 2) need a split-operand w_format");
             G4C_REQUIRE(g.width <= G4C_NARROW_MAX && !g.idx && g.pre_act == G4C_ACT_NONE && g.w && ((uintptr_t)g.w & 15) == 0, G4C_EINVAL,
-                        "g4c_mlp_forward: bad narrow source %d (width %d <= %d, no index, no pre_act, 16-byte aligned weights)", s,
+                        "g4c_mlp_run: bad narrow source %d (width %d <= %d, no index, no pre_act, 16-byte aligned weights)", s,
                         g.width, G4C_NARROW_MAX);
             NarSrc &a = p.nar[p.n_nar++];
             a.ptr = g.ptr + g.col0; a.w = g.w; a.width = g.width; a.ld = g.ld;
@@ -1468,12 +1276,12 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         }
         if (g.additive) {
             G4C_REQUIRE(g.pre_act == G4C_ACT_NONE && g.width <= NP && (g.dtype == G4C_DTYPE_F32 || g.dtype == G4C_DTYPE_BF16), G4C_EINVAL,
-                        "g4c_mlp_forward: bad additive source %d", s);
+                        "g4c_mlp_run: bad additive source %d", s);
             AddSrc &a = p.add[p.n_add++];
             a.idx = g.idx; a.width = g.width; a.ld = g.ld; a.bf16 = g.dtype == G4C_DTYPE_BF16;
             if (a.bf16) {
                 G4C_REQUIRE(round1 && g.width == NP && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 8 == 0, G4C_EUNSUPPORTED,
-                            "g4c_mlp_forward: bf16 additive rows need the rounded-bf16 mode (g4c_mlp_forward_bf16*) and a 128-wide, 8-byte aligned block");
+                            "g4c_mlp_run: bf16 additive rows need the rounded-bf16 mode (w_format G4C_WFMT_BF16*) and a 128-wide, 8-byte aligned block");
                 a.ptr = reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(g.ptr) + g.col0);
             } else {
                 a.ptr = g.ptr + g.col0;
@@ -1481,110 +1289,106 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
             continue;
         }
         G4C_REQUIRE(g.pre_act == G4C_ACT_NONE || g.pre_act == G4C_ACT_SELU, G4C_EUNSUPPORTED,
-                    "g4c_mlp_forward: source %d pre_act %d (only NONE / SELU can be applied on load)", s, g.pre_act);
+                    "g4c_mlp_run: source %d pre_act %d (only NONE / SELU can be applied on load)", s, g.pre_act);
         Src &d = p.src[nk++];
-        if (bf16) G4C_REQUIRE(g.width <= NP, G4C_EUNSUPPORTED, "g4c_mlp_forward_bf16: input block %d is %d wide (max 128)", s, g.width);
-        d.ptr = g.ptr; d.idx = g.idx; d.width = g.width; d.wpad = bf16 ? NP : (g.width + KC - 1) / KC * KC; d.ld = g.ld; d.col0 = g.col0;
+        if (bx6) G4C_REQUIRE(g.width <= NP, G4C_EUNSUPPORTED, "g4c_mlp_run: input block %d is %d wide (max 128 in a split-operand w_format)", s, g.width);
+        d.ptr = g.ptr; d.idx = g.idx; d.width = g.width; d.wpad = bx6 ? NP : (g.width + KC - 1) / KC * KC; d.ld = g.ld; d.col0 = g.col0;
         d.pre_act = g.pre_act;
         d.bf16 = g.dtype == G4C_DTYPE_BF16;
         if (d.bf16)
             G4C_REQUIRE(round1 && g.width == NP && !g.seg_off && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 8 == 0, G4C_EUNSUPPORTED,
-                        "g4c_mlp_forward: bf16 rows need the rounded-bf16 mode (g4c_mlp_forward_bf16*) and a 128-wide, 8-byte aligned block");
+                        "g4c_mlp_run: bf16 rows need the rounded-bf16 mode (w_format G4C_WFMT_BF16*) and a 128-wide, 8-byte aligned block");
         else
-            G4C_REQUIRE(g.dtype == G4C_DTYPE_F32, G4C_EINVAL, "g4c_mlp_forward: source %d has unknown dtype %d", s, g.dtype);
+            G4C_REQUIRE(g.dtype == G4C_DTYPE_F32, G4C_EINVAL, "g4c_mlp_run: source %d has unknown dtype %d", s, g.dtype);
         d.seg_off = g.seg_off; d.seg_mean = g.seg_mean; d.seg_perm = g.seg_off ? g.seg_perm : nullptr;
         if (g.seg_off)
             G4C_REQUIRE(bx6 && !g.idx && g.width == NP && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 16 == 0, G4C_EUNSUPPORTED,
-                        "g4c_mlp_forward: aggregation on load needs the bf16x6 kernels and a 128-wide aligned block without gather index");
+                        "g4c_mlp_run: aggregation on load needs a split-operand w_format and a 128-wide aligned block without gather index");
         d.vec = (g.width % 4 == 0) && (g.ld % 4 == 0) && (g.col0 % 4 == 0) && ((uintptr_t)g.ptr % (d.bf16 ? 8 : 16) == 0);
         all_vec = all_vec && d.vec;
         kp += d.wpad;
     }
-    G4C_REQUIRE(nk >= 1 || p.n_nar >= 1, G4C_EINVAL, "g4c_mlp_forward: no input block goes through the weights");
+    G4C_REQUIRE(nk >= 1 || p.n_nar >= 1, G4C_EINVAL, "g4c_mlp_run: no input block goes through the weights");
     p.n_src = nk;
     if (nk == 0) p.src[0] = Src{nullptr, nullptr, 0, 0, 0, 0, 1, 0, nullptr, 0, nullptr, 0};
     for (int s = (nk ? nk : 1); s < G4C_MAX_SRC; ++s) p.src[s] = p.src[0];
     for (int s = p.n_nar; s < G4C_MAX_SRC; ++s) p.nar[s] = NarSrc{nullptr, nullptr, 0, 0};
     for (int s = p.n_add; s < G4C_MAX_SRC; ++s) p.add[s] = AddSrc{nullptr, nullptr, 0, 0, 0};
-    G4C_REQUIRE(kp == mlp->k_pad[0], G4C_EINVAL, "g4c_mlp_forward: sources give %d padded columns, layer 1 packed for %d", kp, mlp->k_pad[0]);
+    G4C_REQUIRE(kp == mlp->k_pad[0], G4C_EINVAL, "g4c_mlp_run: sources give %d padded columns, layer 1 packed for %d", kp, mlp->k_pad[0]);
     p.n_layers = mlp->n_layers;
     p.chunks0 = kp / KC;
     for (int l = 0; l < mlp->n_layers; ++l) {
-        G4C_REQUIRE(mlp->n_pad[l] == NP, G4C_EINVAL, "g4c_mlp_forward: layer %d n_pad %d (must be 128)", l, mlp->n_pad[l]);
-        if (l > 0) G4C_REQUIRE(mlp->k_pad[l] == NP, G4C_EINVAL, "g4c_mlp_forward: layer %d k_pad %d (must be 128)", l, mlp->k_pad[l]);
+        G4C_REQUIRE(mlp->n_pad[l] == NP, G4C_EINVAL, "g4c_mlp_run: layer %d n_pad %d (must be 128)", l, mlp->n_pad[l]);
+        if (l > 0) G4C_REQUIRE(mlp->k_pad[l] == NP, G4C_EINVAL, "g4c_mlp_run: layer %d k_pad %d (must be 128)", l, mlp->k_pad[l]);
         // one contiguous stream: layer l starts where layer l-1 ends
         if (l > 0) G4C_REQUIRE((const char *)mlp->w[l] == (const char *)mlp->w[l - 1] + (size_t)mlp->k_pad[l - 1] * NP * wbytes, G4C_EINVAL,
-                               "g4c_mlp_forward: packed layers must be contiguous (layer %d)", l);
+                               "g4c_mlp_run: packed layers must be contiguous (layer %d)", l);
         if (l > 0) G4C_REQUIRE((const float *)mlp->b[l] == (const float *)mlp->b[l - 1] + NP, G4C_EINVAL,
-                               "g4c_mlp_forward: padded biases must be contiguous (layer %d)", l);
+                               "g4c_mlp_run: padded biases must be contiguous (layer %d)", l);
     }
     p.w = (const float *)mlp->w[0];
     p.b = (const float *)mlp->b[0];
-    G4C_REQUIRE(p.w && p.b, G4C_EINVAL, "g4c_mlp_forward: null weights");
+    G4C_REQUIRE(p.w && p.b, G4C_EINVAL, "g4c_mlp_run: null weights");
     p.gamma = mlp->ln_gamma; p.beta = mlp->ln_beta; p.eps = mlp->ln_eps;
-    G4C_REQUIRE((p.gamma == nullptr) == (p.beta == nullptr), G4C_EINVAL, "g4c_mlp_forward: LayerNorm needs both gamma and beta");
+    G4C_REQUIRE((p.gamma == nullptr) == (p.beta == nullptr), G4C_EINVAL, "g4c_mlp_run: LayerNorm needs both gamma and beta");
     p.n_out = mlp->n_out;
-    G4C_REQUIRE(p.n_out > 0 && p.n_out <= NP && out_ld >= p.n_out, G4C_EINVAL, "g4c_mlp_forward: n_out=%d out_ld=%d", p.n_out, out_ld);
+    G4C_REQUIRE(p.n_out > 0 && p.n_out <= NP && out_ld >= p.n_out, G4C_EINVAL, "g4c_mlp_run: n_out=%d out_ld=%d", p.n_out, out_ld);
     p.M = n_rows;
     p.out = out; p.out_ld = out_ld; p.out_idx = out_idx; p.act = act;
     p.out_bf16 = 0;
-    if (g_out_dtype) {
-        G4C_REQUIRE(round1 && !agg && !resid && !out_idx && p.n_out == NP && (out_ld & 3) == 0 && ((uintptr_t)out & 7) == 0, G4C_EUNSUPPORTED,
-                    "g4c_mlp_forward_bf16_out: bf16 output rows need the rounded-bf16 mode, a plain 128-wide output, out_ld a multiple of 4 and an 8-byte aligned out");
-        p.out_bf16 = g_out_dtype;
-    }
-    p.resid = resid; p.resid_ld = resid_ld; p.resid_col0 = resid_col0;
+    p.resid = resid; p.resid_ld = io->resid_ld; p.resid_col0 = io->resid_col0;
     p.tile_rows = p.tile_seg = p.seg_off = nullptr; p.agg = nullptr; p.agg_ld = 0; p.agg_mean = 0; p.agg_deg = 0; p.agg_bf16 = 0;
     if (agg) {
-        G4C_REQUIRE(bx6 && mlp->n_out == NP && !out_idx && !resid, G4C_EUNSUPPORTED, "g4c_mlp_forward_bx6_agg: needs the bf16x6 kernel and a plain 128-wide output");
-        p.tile_rows = agg->tile_rows; p.tile_seg = agg->tile_seg; p.seg_off = agg->seg_off;
-        p.agg = agg->out; p.agg_ld = agg->out_ld; p.agg_mean = agg->mean & 1; p.agg_deg = (agg->mean >> 8) & 0xff; p.agg_bf16 = (agg->mean >> 16) & 1;
-        G4C_REQUIRE((agg->mean >> 17) == 0 && (!p.agg_bf16 || rs_fmt) && p.agg_deg <= 32 && (p.agg_deg == 0 || row_count % p.agg_deg == 0), G4C_EINVAL,
-                    "fused aggregation: agg_mean = %d is not 0 / 1 [| G4C_AGG_UNIFORM(k), 1 <= k <= 32, k dividing the %lld rows]", agg->mean,
+        G4C_REQUIRE(bx6 && mlp->n_out == NP && !out_idx && !resid, G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: the fused aggregation needs a split-operand w_format and a plain 128-wide output");
+        const int32_t mode = io->agg_mode;
+        p.tile_rows = io->tile_rows; p.tile_seg = io->tile_seg; p.seg_off = io->seg_off;
+        p.agg = (float *)io->agg; p.agg_ld = io->agg_ld; p.agg_mean = mode & 1; p.agg_deg = (mode >> 8) & 0xff; p.agg_bf16 = (mode >> 16) & 1;
+        G4C_REQUIRE((mode >> 17) == 0 && (!p.agg_bf16 || rs_fmt) && p.agg_deg <= 32 && (p.agg_deg == 0 || row_count % p.agg_deg == 0), G4C_EINVAL,
+                    "fused aggregation: agg_mode = %d is not 0 / 1 [| G4C_AGG_UNIFORM(k), 1 <= k <= 32, k dividing the %lld rows]", mode,
                     (long long)row_count);
-        if (agg->rows_bf16) {
-            G4C_REQUIRE(round1 && (!out || ((out_ld & 3) == 0 && ((uintptr_t)out & 7) == 0)), G4C_EUNSUPPORTED,
-                        "g4c_mlp_forward_bf16_agg: bf16 output rows need the rounded-bf16 mode, out_ld a multiple of 4 and an 8-byte aligned out");
-            p.out_bf16 = agg->rows_bf16;
-        }
+    }
+    if (io->out_dtype) {
+        G4C_REQUIRE(round1 && !resid && !out_idx && p.n_out == NP && (!out || ((out_ld & 3) == 0 && ((uintptr_t)out & 7) == 0)), G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: bf16 output rows need the rounded-bf16 mode, a plain 128-wide output, out_ld a multiple of 4 and an 8-byte aligned out");
+        p.out_bf16 = io->out_dtype;
     }
     for (int l = 0; l < G4C_MAX_LAYERS; ++l) { p.save[l] = nullptr; p.mul[l] = nullptr; }
     p.save_ld = 0; p.mul_ld = 0;
     if (save) {
-        G4C_REQUIRE(bx6 && !round1 && !agg && !n_heads && !out_idx && save->ptr && save->ld >= NP && (save->ld & 3) == 0, G4C_EUNSUPPORTED,
-                    "g4c_mlp_forward_bx6_save: needs the bf16x6 kernel without heads / aggregation / output index, save_ld >= 128 and a multiple of 4");
+        G4C_REQUIRE(bx6 && !round1 && !agg && !n_heads && !out_idx && io->save_ld >= NP && (io->save_ld & 3) == 0, G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: save needs w_format BF16X3 / F16X2 without heads / aggregation / output index, save_ld >= 128 and a multiple of 4");
+        G4C_REQUIRE(io->n_save == mlp->n_layers, G4C_EINVAL, "g4c_mlp_run: n_save %d for %d layers", io->n_save, mlp->n_layers);
+        bool mul = false;
         for (int l = 0; l < mlp->n_layers; ++l) {
-            G4C_REQUIRE(((uintptr_t)save->ptr[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_forward_bx6_save: save[%d] is not 16-byte aligned", l);
-            p.save[l] = save->ptr[l];
+            G4C_REQUIRE(((uintptr_t)io->save[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: save[%d] is not 16-byte aligned", l);
+            p.save[l] = io->save[l];
+            if (l + 1 == mlp->n_layers) break;
+            G4C_REQUIRE(((uintptr_t)io->mul[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: mul[%d] is not 16-byte aligned", l);
+            p.mul[l] = io->mul[l];
+            mul = mul || io->mul[l];
         }
-        p.save_ld = save->ld;
-        if (save->mul) {
-            G4C_REQUIRE(save->mul_ld >= NP && (save->mul_ld & 3) == 0, G4C_EINVAL, "g4c_mlp_forward_bx6_save: mul_ld=%d", save->mul_ld);
-            for (int l = 0; l + 1 < mlp->n_layers; ++l) {
-                G4C_REQUIRE(((uintptr_t)save->mul[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_forward_bx6_save: mul[%d] is not 16-byte aligned", l);
-                p.mul[l] = save->mul[l];
-            }
-            p.mul_ld = save->mul_ld;
-        }
+        p.save_ld = io->save_ld;
+        G4C_REQUIRE(!mul || (io->mul_ld >= NP && (io->mul_ld & 3) == 0), G4C_EINVAL, "g4c_mlp_run: mul_ld=%d", io->mul_ld);
+        p.mul_ld = io->mul_ld;
     }
     p.range_flag = f16x2 ? mlp->range_flag : nullptr; p.range_slot = mlp->range_slot;
-    G4C_REQUIRE(!p.range_flag || p.range_slot >= 0, G4C_EINVAL, "g4c_mlp_forward: negative range_slot");
-    p.n_heads = n_heads; p.head_ld = head_ld; p.head_bf16 = 0;
-    for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) p.head_out[hd] = hd < n_heads ? head_out[hd] : nullptr;
-    if (n_heads && g_head_dtype) {
-        G4C_REQUIRE(round1 && (head_ld & 1) == 0, G4C_EUNSUPPORTED, "g4c_mlp_forward_heads_bf16_out: bf16 head rows need the rounded-bf16 mode and an even head_ld");
+    G4C_REQUIRE(!p.range_flag || p.range_slot >= 0, G4C_EINVAL, "g4c_mlp_run: negative range_slot");
+    // heads (the kernels read their weights where the stream of the MLP that owns them ends; with `upd`, that MLP's)
+    for (int hd = 0; hd < n_heads; ++hd) G4C_REQUIRE(io->head_out[hd], G4C_EINVAL, "g4c_mlp_run: null head output %d", hd);
+    p.n_heads = node ? 0 : n_heads; p.head_ld = p.n_heads ? io->head_ld : 0; p.head_bf16 = 0;
+    for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) p.head_out[hd] = hd < p.n_heads ? (float *)io->head_out[hd] : nullptr;
+    if (p.n_heads && io->head_dtype) {
+        G4C_REQUIRE(round1 && (p.head_ld & 1) == 0, G4C_EUNSUPPORTED, "g4c_mlp_run: bf16 head rows need the rounded-bf16 mode and an even head_ld");
         for (int hd = 0; hd < n_heads; ++hd)
-            G4C_REQUIRE(((uintptr_t)head_out[hd] & 3) == 0, G4C_EINVAL, "g4c_mlp_forward_heads_bf16_out: head output %d is not 4-byte aligned", hd);
+            G4C_REQUIRE(((uintptr_t)io->head_out[hd] & 3) == 0, G4C_EINVAL, "g4c_mlp_run: head output %d is not 4-byte aligned", hd);
         p.head_bf16 = 1;
     }
-    if (n_heads) {
-        G4C_REQUIRE((head_ld & 3) == 0 || !bx6, G4C_EINVAL, "g4c_mlp_forward_heads: head outputs need a leading dimension that is a multiple of 4");
-        G4C_REQUIRE(p.n_out == NP && !resid && !out_idx && head_ld >= NP, G4C_EINVAL,
-                    "g4c_mlp_forward_heads: heads need a 128-wide output without residual / output index (n_out=%d)", p.n_out);
-        const int last = mlp->n_layers - 1;
-        G4C_REQUIRE((const char *)head_w == (const char *)mlp->w[last] + (size_t)mlp->k_pad[last] * NP * wbytes, G4C_EINVAL,
-                    "g4c_mlp_forward_heads: head weights must continue the packed stream");
-        for (int hd = 0; hd < n_heads; ++hd) G4C_REQUIRE(head_out[hd], G4C_EINVAL, "g4c_mlp_forward_heads: null head output %d", hd);
+    if (p.n_heads) {
+        G4C_REQUIRE(!agg, G4C_EUNSUPPORTED, "g4c_mlp_run: heads with the fused aggregation");
+        G4C_REQUIRE((p.head_ld & 3) == 0 || !bx6, G4C_EINVAL, "g4c_mlp_run: head outputs need a leading dimension that is a multiple of 4");
+        G4C_REQUIRE(p.n_out == NP && !resid && !out_idx && p.head_ld >= NP, G4C_EINVAL,
+                    "g4c_mlp_run: heads need a 128-wide output without residual / output index (n_out=%d)", p.n_out);
     }
     hipStream_t st = (hipStream_t)stream;
     if (row_count == 0) return G4C_OK;
@@ -1592,46 +1396,44 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
     p.M = row_begin + row_count;          // rows past the range are neither gathered nor stored
     if (node) {
         // one launch per MP layer: the message MLP on the weight-stationary kernel, the node update behind it (mlp_ws.hip, NODE)
-        const g4c_mlp_t *u = node->upd;
-        G4C_REQUIRE(f16x2 && agg && agg->out && u && u->w_format == G4C_WFMT_F16X2, G4C_EUNSUPPORTED,
-                    "g4c_mp_layer_forward_bx6: both MLPs need the f16x3 stream (g4c_mlp_pack_layer_f16x3) and the aggregation plan");
+        const g4c_mlp_t *u = io->upd;
+        G4C_REQUIRE(f16x2 && agg && u->w_format == G4C_WFMT_F16X2 && act == G4C_ACT_NONE, G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: the fused node update needs the f16x3 format (G4C_WFMT_F16X2) for both MLPs, the aggregation plan and act NONE");
         G4C_REQUIRE(u->n_layers == mlp->n_layers && u->k_pad[0] == 2 * NP && u->n_out == NP && u->w[0] && u->b[0], G4C_EUNSUPPORTED,
-                    "g4c_mp_layer_forward_bx6: the node MLP must have the message MLP's depth (%d), two 128-wide input blocks and a 128-wide output",
+                    "g4c_mlp_run: upd must have the message MLP's depth (%d), two 128-wide input blocks and a 128-wide output",
                     mlp->n_layers);
         for (int l = 0; l < u->n_layers; ++l) {
-            G4C_REQUIRE(u->n_pad[l] == NP && (l == 0 || u->k_pad[l] == NP), G4C_EUNSUPPORTED, "g4c_mp_layer_forward_bx6: node layer %d is not 128 wide", l);
+            G4C_REQUIRE(u->n_pad[l] == NP && (l == 0 || u->k_pad[l] == NP), G4C_EUNSUPPORTED, "g4c_mlp_run: upd layer %d is not 128 wide", l);
             if (l > 0) G4C_REQUIRE((const char *)u->w[l] == (const char *)u->w[l - 1] + (size_t)u->k_pad[l - 1] * NP * 6 &&
                                    (const float *)u->b[l] == (const float *)u->b[l - 1] + NP, G4C_EINVAL,
-                                   "g4c_mp_layer_forward_bx6: the node MLP's packed layers / biases must be contiguous (layer %d)", l);
+                                   "g4c_mlp_run: upd's packed layers / biases must be contiguous (layer %d)", l);
         }
-        G4C_REQUIRE((u->ln_gamma == nullptr) == (u->ln_beta == nullptr), G4C_EINVAL, "g4c_mp_layer_forward_bx6: LayerNorm needs both gamma and beta");
+        G4C_REQUIRE((u->ln_gamma == nullptr) == (u->ln_beta == nullptr), G4C_EINVAL, "g4c_mlp_run: upd's LayerNorm needs both gamma and beta");
         G4C_REQUIRE(!u->ln_gamma || (((uintptr_t)u->ln_gamma & 15) == 0 && ((uintptr_t)u->ln_beta & 15) == 0), G4C_EINVAL,
-                    "g4c_mp_layer_forward_bx6: LayerNorm parameters must be 16-byte aligned");
-        G4C_REQUIRE(node->v && node->v_out && (node->v_ld & 3) == 0 && node->v_ld >= NP && (node->v_out_ld & 3) == 0 && node->v_out_ld >= NP &&
-                    ((uintptr_t)node->v & 15) == 0 && ((uintptr_t)node->v_out & 15) == 0 && (agg->out_ld & 3) == 0 && ((uintptr_t)agg->out & 15) == 0,
-                    G4C_EINVAL, "g4c_mp_layer_forward_bx6: v / v_out / agg need 16-byte aligned rows of at least 128 columns");
-        G4C_REQUIRE(node->act >= 0 && node->act <= 2 && node->n_heads >= 0 && node->n_heads <= G4C_MAX_HEADS, G4C_EINVAL, "g4c_mp_layer_forward_bx6: bad activation / head count");
+                    "g4c_mlp_run: upd's LayerNorm parameters must be 16-byte aligned");
+        G4C_REQUIRE(io->v && io->v_out && (io->v_ld & 3) == 0 && io->v_ld >= NP && (io->v_out_ld & 3) == 0 && io->v_out_ld >= NP &&
+                    ((uintptr_t)io->v & 15) == 0 && ((uintptr_t)io->v_out & 15) == 0 && (io->agg_ld & 3) == 0 && ((uintptr_t)io->agg & 15) == 0,
+                    G4C_EINVAL, "g4c_mlp_run: v / v_out / agg need 16-byte aligned rows of at least 128 columns");
+        G4C_REQUIRE(io->v_act >= 0 && io->v_act <= 2, G4C_EINVAL, "g4c_mlp_run: bad v_act %d", io->v_act);
         NodeParams q{};
-        q.v = node->v; q.v_ld = node->v_ld; q.w = (const float *)u->w[0]; q.b = (const float *)u->b[0];
-        q.gamma = u->ln_gamma; q.beta = u->ln_beta; q.eps = u->ln_eps; q.act = node->act;
-        q.out = node->v_out; q.out_ld = node->v_out_ld; q.n_heads = node->n_heads; q.head_ld = node->head_ld;
+        q.v = io->v; q.v_ld = io->v_ld; q.w = (const float *)u->w[0]; q.b = (const float *)u->b[0];
+        q.gamma = u->ln_gamma; q.beta = u->ln_beta; q.eps = u->ln_eps; q.act = io->v_act;
+        q.out = io->v_out; q.out_ld = io->v_out_ld; q.n_heads = n_heads; q.head_ld = io->head_ld;
         q.range_flag = u->range_flag; q.range_slot = u->range_slot;
-        G4C_REQUIRE(!q.range_flag || q.range_slot >= 0, G4C_EINVAL, "g4c_mp_layer_forward_bx6: negative range_slot");
+        G4C_REQUIRE(!q.range_flag || q.range_slot >= 0, G4C_EINVAL, "g4c_mlp_run: upd's negative range_slot");
         for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) q.head_out[hd] = nullptr;
-        if (node->n_heads) {
-            const int last = u->n_layers - 1;
-            G4C_REQUIRE(node->head_w && node->head_out && (const char *)node->head_w == (const char *)u->w[last] + (size_t)u->k_pad[last] * NP * 6, G4C_EINVAL,
-                        "g4c_mp_layer_forward_bx6: head weights must continue the node MLP's packed stream");
-            G4C_REQUIRE((node->head_ld & 3) == 0 && node->head_ld >= NP, G4C_EINVAL, "g4c_mp_layer_forward_bx6: head_ld must be a multiple of 4 and >= 128");
-            for (int hd = 0; hd < node->n_heads; ++hd) {
-                G4C_REQUIRE(node->head_out[hd] && ((uintptr_t)node->head_out[hd] & 15) == 0, G4C_EINVAL, "g4c_mp_layer_forward_bx6: bad head output %d", hd);
-                q.head_out[hd] = node->head_out[hd];
+        if (n_heads) {
+            G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 && (io->head_ld & 3) == 0 && io->head_ld >= NP, G4C_EINVAL,
+                        "g4c_mlp_run: upd's heads need fp32 rows, head_ld a multiple of 4 and >= 128");
+            for (int hd = 0; hd < n_heads; ++hd) {
+                G4C_REQUIRE(((uintptr_t)io->head_out[hd] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: bad head output %d", hd);
+                q.head_out[hd] = (float *)io->head_out[hd];
             }
         }
         G4C_REQUIRE(ws_eligible(p, false, true, false, true, row_count, true), G4C_EUNSUPPORTED,
-                    "g4c_mp_layer_forward_bx6: the message launch is outside the weight-stationary kernel's envelope (one 128-wide weighted block, "
-                    "two 128-wide additive blocks, two or three 128-wide layers, aligned rows)");
-        p.n_tiles = agg->n_tiles;
+                    "g4c_mlp_run: the message launch of the fused MP layer is outside the weight-stationary kernel's envelope (one 128-wide "
+                    "weighted block, two 128-wide additive blocks, two or three 128-wide layers, aligned rows)");
+        p.n_tiles = io->n_tiles;
         if (p.n_tiles == 0) return G4C_OK;
         g_last_kernel = G4C_KERNEL_MLP_WS;
         return ws_launch(p, true, false, st, &q);
@@ -1640,41 +1442,41 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         // row-split persistent kernel (mlp_rs.hip): a wave owns 16 rows through all layers, the weights stay in LDS, bf16 rows in its
         // own column order.  A stream in its k order can run on no other kernel: outside its envelope the call fails instead of
         // computing something else.
-        G4C_REQUIRE(!save && !node && !force_tiles && rs_eligible(p, agg != nullptr, row_count), G4C_EUNSUPPORTED,
-                    "g4c_mlp_forward_bf16: weights packed for the row-split kernel (G4C_WFMT_BF16_RS), launch outside its envelope");
+        G4C_REQUIRE(!save && rs_eligible(p, agg, row_count), G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: weights packed for the row-split kernel (G4C_WFMT_BF16_RS), launch outside its envelope");
         g_last_kernel = G4C_KERNEL_MLP_RS;
-        return rs_launch(p, agg != nullptr, st);
+        return rs_launch(p, agg, st);
     }
     if (rs2_fmt) {
-        G4C_REQUIRE(!save && !node && !force_tiles && !agg && rs2_eligible(p, row_count), G4C_EUNSUPPORTED,
-                    "g4c_mlp_forward_bf16: weights packed for the row-split update kernel (G4C_WFMT_BF16_RS2), launch outside its envelope");
+        G4C_REQUIRE(!save && !agg && rs2_eligible(p, row_count), G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: weights packed for the row-split update kernel (G4C_WFMT_BF16_RS2), launch outside its envelope");
         g_last_kernel = G4C_KERNEL_MLP_RS2;
-        return rs2_launch(p, mlp->w_format == G4C_WFMT_BF16_RS2N, st);
+        return rs2_launch(p, fmt == G4C_WFMT_BF16_RS2N, st);
     }
-    if (bx6 && !force_tiles && ws_eligible(p, round1, agg != nullptr, save != nullptr, f16x2, row_count)) {
+    if (bx6 && ws_eligible(p, round1, agg, save, f16x2, row_count)) {
         // weight-stationary persistent kernel (mlp_ws.hip): pairs of 32-row tiles (whole segments with aggregation), one workgroup per CU
         // (uniform segments, G4C_AGG_UNIFORM: ws_launch's dense mode derives segments as row / k over [0, p.M) and cannot honour a
-        // sub-range — refused like rs_eligible does.  A guard only: every entry point with an aggregation passes the whole row range.)
+        // sub-range — refused like rs_eligible does.  A guard only: a launch with an aggregation covers all its rows.)
         G4C_REQUIRE(!(agg && p.agg_deg >= 4 && p.agg_deg <= 8) || row_begin == 0, G4C_EINVAL,
-                    "g4c_mlp_forward: uniform segments (G4C_AGG_UNIFORM) need the whole row range, got rows [%lld, %lld)",
+                    "g4c_mlp_run: uniform segments (G4C_AGG_UNIFORM) need the whole row range, got rows [%lld, %lld)",
                     (long long)row_begin, (long long)p.M);
-        p.n_tiles = agg ? agg->n_tiles : (int)((row_count + 31) / 32);
+        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
         if (p.n_tiles == 0) return G4C_OK;          // (nothing launches: g4c_mlp_last_kernel stays G4C_KERNEL_NONE — ADVICE r04)
         g_last_kernel = G4C_KERNEL_MLP_WS;
-        return ws_launch(p, agg != nullptr, round1, st);
-    } else if (bx6 && !force_tiles && bx6i_eligible(p, round1, agg != nullptr, save != nullptr, f16x2, row_count)) {
+        return ws_launch(p, agg, round1, st);
+    } else if (bx6 && bx6i_eligible(p, round1, agg, save, f16x2, row_count)) {
         // dual-tile software-pipelined kernel (mlp_bx6i.hip): pairs of 32-row tiles (whole segments with aggregation)
-        p.n_tiles = agg ? agg->n_tiles : (int)((row_count + 31) / 32);
+        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
         if (p.n_tiles == 0) return G4C_OK;
         g_last_kernel = G4C_KERNEL_MLP_BX6I;
-        return bx6i_launch(p, agg != nullptr, f16x2, st);
+        return bx6i_launch(p, agg, f16x2, st);
     } else if (bx6) {
         bool full = all_vec;
         for (int s2 = 0; s2 < p.n_src; ++s2) full = full && p.src[s2].width == NP;
         for (int a = 0; a < p.n_add; ++a)
             full = full && p.add[a].width == NP && (p.add[a].ld & 3) == 0 && ((uintptr_t)p.add[a].ptr & (p.add[a].bf16 ? 7 : 15)) == 0;
         const dim3 blk(256);
-        p.n_tiles = agg ? agg->n_tiles : (int)((row_count + 31) / 32);
+        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
         if (p.n_tiles == 0) return G4C_OK;
         g_last_kernel = G4C_KERNEL_MLP_BX6;
         const dim3 grid(p.n_tiles);
@@ -1708,5 +1510,10 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         if (all_vec) mlp_split_kernel<4, true><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
         else mlp_split_kernel<4, false><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
     }
-    return g4c::check_launch("g4c_mlp_forward");
+    return g4c::check_launch("g4c_mlp_run");
+}
+
+extern "C" int g4c_mlp_run(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows, const g4c_mlp_io_t *io,
+                           void *stream) {
+    return mlp_launch(mlp, srcs, n_src, n_rows, io, stream);
 }

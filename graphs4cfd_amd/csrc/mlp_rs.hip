@@ -29,7 +29,7 @@
 // aggregate keep the natural order (16 bytes per lane as they are).
 //   XB16  the weighted block's rows are bf16 (already activated: the bf16(SELU(a')) rows an earlier launch of this kind stored)
 //   AB16  the two additive product tables are bf16
-//   OUT   0 fp32 rows, 1 bf16 rows, 2 bf16(SELU(row)) rows (g4c_mlp_forward_bf16_agg out_dtype), 3 rows not stored (aggregate only)
+//   OUT   0 fp32 rows, 1 bf16 rows, 2 bf16(SELU(row)) rows (g4c_mlp_io_t.out_dtype), 3 rows not stored (aggregate only)
 //   AGG   G4C_AGG_UNIFORM(K), 4 <= K <= 8: per chunk of 16 rows the LayerNorm'd fp32 rows are summed per segment by a segmented
 //         inclusive scan over the 16 lanes of a row group (v_fmac_f32 with DPP row_shr 1 / 2 / 4 and per-row masks; a segment cut by the
 //         chunk's end continues with the previous chunk's running sum), and the lanes that hold a segment's last row store its sum /
@@ -591,7 +591,7 @@ int rs_launch(const Params &p, bool agg, hipStream_t st) {
 #undef G4C_RS1_NL
 #undef G4C_RS1_XA
 #undef G4C_RS1
-    return g4c::check_launch("g4c_mlp_forward_bf16 (rs)");
+    return g4c::check_launch("g4c_mlp_run (rs)");
 }
 
 bool rs2_eligible(const Params &p, long long row_count) {
@@ -615,7 +615,7 @@ int rs2_launch(const Params &p, bool e_natural, hipStream_t st) {
     if (p.n_heads) { if (p.out_bf16) G4C_RS2(true, true); else G4C_RS2(false, true); }
     else { if (p.out_bf16) G4C_RS2(true, false); else G4C_RS2(false, false); }
 #undef G4C_RS2
-    return g4c::check_launch("g4c_mlp_forward_bf16 (rs2)");
+    return g4c::check_launch("g4c_mlp_run (rs2)");
 }
 
 }  // namespace g4cm

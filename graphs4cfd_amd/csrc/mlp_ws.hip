@@ -19,7 +19,7 @@
 // Envelope (everything else keeps mlp_bx6_kernel / mlp_bx6i_kernel): f16x3 stream (SP = 2) or the rounded-bf16 mode (SP = 1: one
 // v_mfma_f32_16x16x32_bf16 per multiply-add on the leading plane of the bf16x6 stream, operands rounded to bf16 exactly where
 // mlp_bx6_kernel<.., SP = 1> rounds them; there the rows of the weighted block may be bf16 and the output rows may be stored as bf16 /
-// bf16(SELU) — g4c_mlp_forward_bf16_agg), ONE weighted 128-wide aligned input block (rows direct or through an index, optional SELU on
+// bf16(SELU) — g4c_mlp_io_t.out_dtype), ONE weighted 128-wide aligned input block (rows direct or through an index, optional SELU on
 // load), 0 or 2 additive 128-wide blocks (SP = 1: 2), two or three layers, 128-wide output rows without residual / heads; an output
 // index only without the fused aggregation.
 #include "mlp_common.h"
@@ -535,7 +535,7 @@ __device__ __forceinline__ void node_phase(const NodeCtx &c, const float *x0, co
 }
 
 // SP: 2 the f16x3 stream, 1 the rounded-bf16 mode;  NL: layers (2 or 3);  XB16 (SP = 1): the weighted block's rows are bf16;
-// AB16 (SP = 1): the additive rows are bf16 (the first-layer products a g4c_mlp_forward_heads_bf16_out / _bf16_out launch stored:
+// AB16 (SP = 1): the additive rows are bf16 (the first-layer products a launch stored as bf16 heads / rows:
 // half the bytes of the launch's largest gather stream — REMuS-GNN's level-1 angle launch reads 2 x 2.5 M of them)
 // NODE (SP = 2, with AGG): the node update of the MP layer fused behind the message launch (NodeParams, mlp_common.h): when its tile
 // pairs are done a workgroup holds, in L2, the aggregates of a contiguous range of targets that no other workgroup touches — it runs
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
                 if (p.out && row < mm.n[t]) {
                     const long long orow = (!AGG && p.out_idx) ? p.out_idx[mm.r0[t] + row] : mm.r0[t] + row;
                     if (SP == 1 && p.out_bf16) {
-                        // rows kept in bf16 (g4c_mlp_forward_bf16_agg out_dtype; == 2: the reader's pending SELU applied before the one
+                        // rows kept in bf16 (g4c_mlp_io_t.out_dtype; == 2: the reader's pending SELU applied before the one
                         // rounding — the aggregation below still sees the fp32 rows without it), 16 bytes per lane
                         f32x4 w0 = v0, w1 = v1;
                         if (p.out_bf16 == 2) { w0 = selu4(v0); w1 = selu4(v1); }         // (the formula the reader's SELU on load uses)
@@ -1174,14 +1174,14 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
     const bool direct = p.src[0].idx == nullptr, adds = p.n_add == 2, two = p.n_layers == 2, xb16 = p.src[0].bf16 != 0;
     const bool ab16 = adds && p.add[0].bf16 != 0;
     NodeParams q{};
-    if (node) {          // the fused MP layer (g4c_mp_layer_forward_bx6): f16x3 stream, hoisted message MLP, fused aggregation
-        G4C_REQUIRE(agg && !round1 && adds, G4C_EUNSUPPORTED, "g4c_mp_layer_forward_bx6: needs the hoisted f16x3 message launch with the fused aggregation");
+    if (node) {          // the fused MP layer (g4c_mlp_io_t.upd): f16x3 stream, hoisted message MLP, fused aggregation
+        G4C_REQUIRE(agg && !round1 && adds, G4C_EUNSUPPORTED, "g4c_mlp_run (upd): needs the hoisted f16x3 message launch with the fused aggregation");
         q = *node;
 #define G4C_WS_NODE(DIRECT, NL) mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true><<<grid, blk, 0, st>>>(p, n_pairs, q)
         if (direct) { if (two) G4C_WS_NODE(true, 2); else G4C_WS_NODE(true, 3); }
         else { if (two) G4C_WS_NODE(false, 2); else G4C_WS_NODE(false, 3); }
 #undef G4C_WS_NODE
-        return g4c::check_launch("g4c_mp_layer_forward_bx6");
+        return g4c::check_launch("g4c_mlp_run (ws, upd)");
     }
 #define G4C_WS_GO(AGG, DIRECT, ADDS, SP, NL, XB16)                                                                                      \
     do { if (AGG && dense) mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(p, n_pairs, q);       \
@@ -1207,7 +1207,7 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
 #undef G4C_WS_SHAPE
 #undef G4C_WS_GO1
 #undef G4C_WS_GO
-    return g4c::check_launch("g4c_mlp_forward (ws)");
+    return g4c::check_launch("g4c_mlp_run (ws)");
 }
 
 }  // namespace g4cm

@@ -31,7 +31,7 @@ extern "C" int g4c_plan_csr(const int64_t *keys, int64_t n, int64_t n_seg, int32
 
 // Tiles of whole segments: tile t covers segments [tile_seg[t], tile_seg[t+1]) = rows [tile_rows[t], tile_rows[t+1]), at
 // most max_rows rows (greedy, in order; empty segments ride along).  Lets the edge-MLP kernel reduce the messages of the
-// targets it has just computed (g4c_mlp_forward_bx6_agg).  Returns the tile count, -1 if a segment exceeds max_rows (then
+// targets it has just computed (g4c_mlp_io_t.agg).  Returns the tile count, -1 if a segment exceeds max_rows (then
 // the caller keeps the separate g4c_segment_reduce launch), or a negative G4C_E* code.
 extern "C" int64_t g4c_plan_tiles(const int32_t *off, int32_t n_seg, int32_t max_rows, int32_t *tile_rows, int32_t *tile_seg,
                                   int64_t capacity) {

@@ -291,7 +291,7 @@ class MLP(nn.Module):
                        head_outs: Optional[Sequence[Optional[Tensor]]] = None, rs_rows: bool = False) -> Optional[Tuple[Tensor, List[Tensor]]]:
         """This MLP on `sources`, plus — from the same launch — the first-layer products `consumer` will need from
         this MLP's output y: [W1c[:, a:b] y for consecutive column blocks [a, b) of `widths` after the first `k_cols`
-        columns of consumer's first layer] (see MLP.run_hoisted; g4c_mlp_forward_heads).
+        columns of consumer's first layer] (see MLP.run_hoisted; g4c_mlp_io_t heads).
         Returns None when the launch cannot carry heads (shape envelope / kernel variant): the caller then lets the
         consumer compute its products itself.  `out` / `head_outs` (entries may be None): caller-provided [n_rows, 128]
         destinations (row-sliced views of wider buffers are fine).  `rs_rows` (rounded-bf16 mode, bf16 products: the consumer's message
@@ -347,7 +347,7 @@ class MLP(nn.Module):
         hdt = given[0].dtype if given else (torch.bfloat16 if (prec == "bf16" and PRODUCTS_BF16) else torch.float32)
         outs = [(head_outs[j] if head_outs is not None and head_outs[j] is not None else
                  torch.empty((n_rows, 128), dtype=hdt, device=dev)) for j in range(len(widths))]
-        if any(_ld_of(t) != _ld_of(outs[0]) or t.dtype != hdt for t in outs):        # one leading dimension / type for all heads (g4c_mlp_forward_heads)
+        if any(_ld_of(t) != _ld_of(outs[0]) or t.dtype != hdt for t in outs):        # one leading dimension / type for all heads (g4c_mlp_io_t.head_ld / head_dtype)
             return None
         ops.mlp_forward(pk, sources, n_rows, act_code, out=y, head_outs=outs)
         return y, ([ops.RsOrderedRows.tag(t) for t in outs] if rs_rows else outs)
@@ -386,7 +386,7 @@ class MLP(nn.Module):
         inputs hoisted: W1 [x | t[idx]] = W1x x + (W1t t)[idx] (exact up to fp32 re-association), so `W1t t` costs
         rows(t) instead of n_rows.  `gathered` = [(tensor [n_t, w_t], int32 index [n_rows])] in concat order.
         Below HOIST_MIN_ROWS the launch is latency-bound and the extra product launches cost more than the MFMA
-        work they save (measured crossover ~25k rows, scripts/sweep_tile_modes.py): one plain fused launch then.
+        work they save (measured crossover ~25k rows): one plain fused launch then.
         `products` (from the producer's launch, MLP.run_with_heads): the per-node terms, already multiplied."""
         if self._rs1_takes(k_sources, gathered, n_rows, act_code, products, kw):
             return self._run_rs1(k_sources[0], gathered, n_rows, products, kw)
@@ -609,9 +609,9 @@ COMPACT_MESSAGES = True
 # with the bf16-rounded weights, fp32 accumulate: the operands the unhoisted launch forms, added in another order).  Measured on
 # config 3 (REMuS-GNN, 100k nodes): the level-1 angle launch is not HBM-bound on its gathers (reading them from bf16 copies of the
 # sender rows: 1160 -> 1130 us) but on per-tile latency and vector work; hoisted, with the products from the producer's launch
-# (g4c_mlp_forward_heads_bf16) and the message launch on mlp_ws_kernel<SP = 1>, it takes 1160 -> 800 us.
+# (heads in the rounded-bf16 mode) and the message launch on mlp_ws_kernel<SP = 1>, it takes 1160 -> 800 us.
 HOIST_BF16 = True
-# Round 5, rounded-bf16 mode: those hoisted first-layer products are STORED as bf16 (g4c_mlp_forward_heads_bf16_out / _bf16_out) and
+# Round 5, rounded-bf16 mode: those hoisted first-layer products are STORED as bf16 (head_dtype / out_dtype G4C_DTYPE_BF16) and
 # widened when the message launch adds them: REMuS-GNN's level-1 angle launch gathers 2 x 2.5 M product rows per EdgeMP — its
 # largest stream — at half the bytes.  One more rounding (relative 2^-9) of a pre-activation term whose operands were rounded to
 # bf16 already; error against the fp32 reference restatement: scripts/remus_bf16_err.py and the 20k-node REMuS parity test.
@@ -628,7 +628,7 @@ ROW_SPLIT_BF16 = __import__('os').environ.get('G4C_ROW_SPLIT_BF16', '1') != '0' 
 # angle launch 521 -> 493 us, the 500k-row edge update 284 -> 254 us).
 AGGREGATE_BF16 = __import__('os').environ.get('G4C_AGGREGATE_BF16', '1') != '0'
 # ... and the edge latents BETWEEN consecutive EdgeMPs of a level — read only by the next update MLP, which rounds them to bf16 on load —
-# are stored as bf16 rows by the update launch (g4c_mlp_forward_heads_bf16_rows): the same operand, half the bytes in both launches.
+# are stored as bf16 rows by the update launch (out_dtype G4C_DTYPE_BF16 beside bf16 heads): the same operand, half the bytes in both launches.
 COMPACT_LATENTS = __import__('os').environ.get('G4C_COMPACT_LATENTS', '1') != '0'
 # ... and the update MLP of such a layer — [bf16 aggregate | bf16 e] -> two layers -> LayerNorm -> SELU -> e' (+ the next layer's two
 # product heads) — runs on the row-split UPDATE kernel (mlp_rs.hip, mlp_rs2_kernel: the five 128 x 128 weight blocks are all of a CU's
@@ -637,7 +637,7 @@ UPDATE_ROW_SPLIT = __import__('os').environ.get('G4C_UPDATE_ROW_SPLIT', '1') != 
 RS1_MIN_ROWS = 20000
 
 
-# One launch per MP layer (round 5, ops.mp_layer_forward / g4c_mp_layer_forward_bx6): message MLP + aggregation + node MLP (+ the next
+# One launch per MP layer (round 5, ops.mp_layer_forward / g4c_mlp_io_t.upd): message MLP + aggregation + node MLP (+ the next
 # layer's products) in the same persistent workgroups.  For launches whose time is the dependent chain inside each kernel — the coarse
 # levels of a multi-scale model, whole small meshes (a rank's share of a partitioned mesh) — not for throughput-bound ones: at
 # FUSE_LAYER_MAX_ROWS edge rows and beyond the node update of 100k nodes runs faster as its own chip-filling launch.
@@ -734,7 +734,7 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
         v_new, e_new, nxt = _fused_layer(msg_mlp, upd_mlp, v, e_src, ep, csr, mean, act_code, products, next_msg, keep_e)
         return (v_new, e_new, nxt) if next_msg is not None else (v_new, e_new)
     if ops.can_fuse_aggregation(csr, msg_mlp.output_size):
-        # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_forward_bx6_agg):
+        # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_io_t.agg):
         # no second pass over the messages; with keep_e=False (the model discards e', nn/mus_gnn.py:199-200) they are not
         # even written
         kw = dict(store_rows=keep_e, rows_dtype=torch.bfloat16 if compact_messages and COMPACT_MESSAGES else None,

@@ -18,7 +18,7 @@ Tensor = torch.Tensor
 
 class KernelTimer:
     """Optional per-launch timing with HIP events on the launch stream (bench.py's roofline leg).
-    `with KernelTimer() as kt: ...` brackets every g4c_mlp_forward / g4c_segment_reduce launch with an
+    `with KernelTimer() as kt: ...` brackets every g4c_mlp_run / g4c_segment_reduce launch with an
     event pair and records its algorithmic work; `kt.summary()` after a device sync."""
     active = None
 
@@ -309,22 +309,22 @@ def steps_to_columns(out_steps: Tensor) -> Tensor:
 # Arithmetic of the fused MLPs — all fp32 in, fp32 out:
 #   "f16x3" (default)   fp32-class products on the f16 matrix pipe: both operands split two ways into fp16 terms,
 #                       x = h + l * 2^-11 (22 significand bits), three partial products, the 2^-11 terms in their own fp32
-#                       accumulator (g4c_mlp_pack_layer_f16x3 + the g4c_mlp_forward_bx6* entry points); measured error against fp64
+#                       accumulator (G4C_WFMT_F16X2); measured error against fp64
 #                       below that of the fp32-MFMA kernel (scripts/mlp_accuracy.py, test_mlp_precisions_vs_fp64).  Range: fp16's — an MLP
 #                       input or hidden activation beyond +-65504 is clipped there (no inf / NaN) AND FLAGGED on the device; the
 #                       arithmetic is run optimistically: a rollout reads its flags where it hands out results (Rollout.validate) and
 #                       recomputes itself in "bf16x6" if anything was clipped, so solve() never returns a clipped value (normalised CFD
 #                       fields and LayerNorm'd latents are far inside the range; raw inputs only pass the fp32 vector path);
 #   "bf16x6"            the same kernels with both operands split EXACTLY into three bf16 terms (fp32 exponent range), the six
-#                       largest partial products accumulated in fp32 (g4c_mlp_forward_bx6): twice the matrix-pipe work;
+#                       largest partial products accumulated in fp32 (G4C_WFMT_BF16X3): twice the matrix-pipe work;
 #                       MLPs outside the envelope of these two (an input block wider than 128) use the fp32 kernels;
-#   "fp32"              v_mfma_f32_32x32x2_f32 (g4c_mlp_forward): the original kernel;
+#   "fp32"              v_mfma_f32_32x32x2_f32 (G4C_WFMT_FP32): the original kernel;
 #   "bf16"              operands ROUNDED to bf16 (~1e-2 deviation): BASELINE config 3's "bf16 edge-MLP MFMA", opt-in only.
 PRECISIONS = ("fp32", "bf16", "bf16x6", "f16x3")
 _PRECISION = os.environ.get("G4C_MLP_PRECISION", "f16x3")
 
 
-# Fused aggregation in the edge-MLP launch (g4c_mlp_forward_bx6_agg): bit-identical to the separate g4c_segment_reduce, and the
+# Fused aggregation in the edge-MLP launch (g4c_mlp_io_t.agg): bit-identical to the separate g4c_segment_reduce, and the
 # node launch no longer re-reads the 307 MB of messages (the largest single stream of a level-1 MP layer after the messages'
 # own write).  The launch then runs on tiles of WHOLE segments: with in-degree 6 (or 5) a 32-row tile holds 30 rows, i.e.
 # 6.7 % more tiles — speed-neutral on the 100k rollout (+0.8 %), 2.5 GB less traffic per step.  On from FUSE_AGG_MIN_ROWS
@@ -509,7 +509,7 @@ def grad_mode() -> bool:
 
 
 def can_fuse_aggregation(csr: CsrPlan, width: int) -> bool:
-    """The edge launch itself can reduce its rows per target (g4c_mlp_forward_bx6_agg): rows in segment order, segments of
+    """The edge launch itself can reduce its rows per target (g4c_mlp_io_t.agg): rows in segment order, segments of
     at most 32 rows, the exact-split kernels, a 128-wide output, enough rows to be throughput-bound."""
     return (FUSE_AGG and _PRECISION in ("bf16x6", "f16x3", "bf16") and width == 128 and csr.perm is None and csr.n >= FUSE_AGG_MIN_ROWS
             and not grad_mode() and csr.tiles() is not None)
@@ -618,15 +618,15 @@ class PackedMLP:
                  seg_widths: Sequence[int], seg_negate: Sequence[bool], heads: Sequence[Tensor] = (),
                  precision: str = "fp32", narrow: Optional[Sequence[bool]] = None, site: Optional[str] = None, rs_order: bool = False,
                  rs_blocks: Optional[Sequence[bool]] = None, rs2: int = 0):
-        """`heads`: bias-free [128, 128] weights applied to the MLP's final output row (g4c_mlp_forward_heads); their
-        packed images continue the weight stream after the last layer.  `precision` "bf16": the bf16 stream of
-        g4c_mlp_pack_layer_bx6 (every input block padded to 128 k; "bf16" uses the same stream, leading plane only).
+        """`heads`: bias-free [128, 128] weights applied to the MLP's final output row (g4c_mlp_io_t heads); their
+        packed images continue the weight stream after the last layer.  `precision` "bf16x6" / "f16x3" / "bf16": the three-plane
+        bf16 stream (every input block padded to 128 k; "bf16" uses the G4C_WFMT_BF16X3 stream, leading plane only).
         `narrow[s]` (bf16x6 / bf16 only): input block s (<= 8 columns, read without index or activation) is multiplied in
         fp32 on the vector ALUs by its rows of the first layer's weight (g4c_src_t.additive == 2) instead of being padded
         to a 128-k block of the matrix-pipe stream."""
         lib = _lib.load()
-        # "f16x3" is the "bf16x6" kernel family (same entry points, stream layout and launch envelope) on a stream written by
-        # g4c_mlp_pack_layer_f16x3; desc.w_format tells the library which arithmetic the stream is for
+        # "f16x3" is the "bf16x6" kernel family (same stream layout and launch envelope) on a stream packed as G4C_WFMT_F16X2;
+        # desc.w_format tells the library which arithmetic the stream is for
         self.split = "f16x2" if precision == "f16x3" else ("bf16x3" if precision == "bf16x6" else None)
         if precision == "f16x3":
             precision = "bf16x6"
@@ -662,7 +662,10 @@ class PackedMLP:
                          or len(weights) != 2 or tuple(weights[0].shape) != (128, 256) or tuple(weights[1].shape) != (128, 128)
                          or len(heads) not in (0, 2) or any(tuple(h.shape) != (128, 128) for h in heads) or any(seg_negate)):
             raise NotImplementedError("rs2: rounded-bf16 mode, [128 | 128] -> 128 -> 128, no or two 128 x 128 heads")
-        self.desc.w_format = 1 if self.split == "f16x2" else (3 if self.rs_order else (self.rs2 if self.rs2 else 0))
+        if precision == "bf16":      # rounded bf16: the plain stream, or one in the row-split kernels' order
+            self.desc.w_format = _lib.WFMT_BF16_RS if self.rs_order else (self.rs2 or _lib.WFMT_BF16)
+        else:
+            self.desc.w_format = {"f16x2": _lib.WFMT_F16X2, "bf16x3": _lib.WFMT_BF16X3, None: _lib.WFMT_FP32}[self.split]
         # `rs_blocks[j]` (rounded-bf16 mode): input block j arrives as RsOrderedRows — bf16 rows in the row-split kernel's column order
         # (its aggregate, G4C_AGG_OUT_BF16) — and is read by a kernel that knows nothing of that order: the COLUMNS of the first layer's
         # block j are packed in the same order instead, the product is the same sum in another order.
@@ -694,7 +697,6 @@ class PackedMLP:
         stream_buf = torch.zeros((sum(k_pads) + NP * len(heads) + (NP if bf16 else KC)) * NP * planes,
                                  dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
         esz = 2 * planes if bf16 else 4
-        pack = (lib.g4c_mlp_pack_layer_f16x3 if self.split == "f16x2" else lib.g4c_mlp_pack_layer_bx6) if bf16 else lib.g4c_mlp_pack_layer
         bias_buf = torch.zeros(n_layers * NP, dtype=torch.float32, device=dev)
         self._keep += [stream_buf, bias_buf]
         off = 0
@@ -742,21 +744,22 @@ class PackedMLP:
                     Wc = Wc[:, cols].contiguous()
                 seg_arr = (C.c_int32 * len(segs))(*segs)
                 neg_arr = (C.c_int32 * len(segs))(*negs)
-                _lib.check(pack(_lib.ptr(Wc), n_out, k_in, seg_arr, neg_arr, len(segs), wptr, k_pads[l], NP, stream))
+                _lib.check(lib.g4c_mlp_pack_layer(_lib.ptr(Wc), n_out, k_in, seg_arr, neg_arr, len(segs), self.desc.w_format, wptr,
+                                                  k_pads[l], NP, stream))
             if b is not None:
                 bias_buf[l * NP: l * NP + n_out].copy_(b.detach())
             self.desc.k_pad[l], self.desc.n_pad[l] = k_pads[l], NP
             self.desc.w[l], self.desc.b[l] = wptr, bias_buf.data_ptr() + 4 * l * NP
             off += k_pads[l] * NP
         self.n_heads = len(heads)
-        self.head_w = stream_buf.data_ptr() + esz * off if heads else None
         one = (C.c_int32 * 1)(NP)
         zero = (C.c_int32 * 1)(0)
         for W in heads:
             Wc = W.detach().to(torch.float32).contiguous()
             if self.rs2:
                 Wc = Wc[:, _rs_k_order(dev)].contiguous()
-            _lib.check(pack(_lib.ptr(Wc), NP, NP, one, zero, 1, stream_buf.data_ptr() + esz * off, NP, NP, stream))
+            _lib.check(lib.g4c_mlp_pack_layer(_lib.ptr(Wc), NP, NP, one, zero, 1, self.desc.w_format, stream_buf.data_ptr() + esz * off,
+                                              NP, NP, stream))
             off += NP * NP
         self.n_out = int(weights[-1].size(0))
         self.desc.n_out = self.n_out
@@ -789,28 +792,45 @@ def _src_array(sources: Sequence[Source]):
 
 
 def _agg_mode(agg_mean: bool, csr: CsrPlan) -> int:
-    """`agg_mean` argument of the fused-aggregation launches: bit 0 = mean, G4C_AGG_UNIFORM(k) when every segment has k rows."""
+    """`agg_mode` of a fused-aggregation launch: bit 0 = mean, G4C_AGG_UNIFORM(k) when every segment has k rows."""
     return (1 if agg_mean else 0) | (csr.uniform_deg << 8)
+
+
+def _set_agg(io, csr: CsrPlan, agg_out: Tensor, agg_mean: bool) -> None:
+    t_rows, t_seg, nt = csr.tiles()
+    io.tile_rows, io.tile_seg, io.seg_off, io.n_tiles = _lib.ptr(t_rows), _lib.ptr(t_seg), _lib.ptr(csr.off), nt
+    io.agg, io.agg_ld, io.agg_mode = _lib.ptr(agg_out), _ld(agg_out), _agg_mode(agg_mean, csr)
+
+
+def _set_heads(io, head_outs: Sequence[Tensor]) -> None:
+    io.n_heads, io.head_ld = len(head_outs), _ld(head_outs[0])
+    io.head_dtype = 1 if head_outs[0].dtype == torch.bfloat16 else 0
+    for j, h in enumerate(head_outs):
+        io.head_out[j] = h.data_ptr()
+
+
+def _run(packed: PackedMLP, arr, n_src: int, n_rows: int, io, dev, flops: float, nbytes: float) -> None:
+    """The one launch (g4c_mlp_run), timed when a KernelTimer is active."""
+    kind = "mlp_split_kernel<4>" if packed.precision == "fp32" else "mlp_bx6_kernel"      # (the timer relabels it by what ran)
+    _timed(kind, flops, nbytes, lambda: _lib.check(_lib.load().g4c_mlp_run(C.byref(packed.desc), arr, n_src, n_rows, C.byref(io),
+                                                                           _lib.stream_handle(dev))))
 
 
 def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr: CsrPlan, agg_mean: bool, upd: PackedMLP,
                      v: Tensor, act: int, store_rows: bool = True, head_outs: Optional[Sequence[Tensor]] = None,
                      v_out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor, Optional[Sequence[Tensor]]]:
-    """One launch for a whole MP layer (g4c_mp_layer_forward_bx6; reference nn/blocks.py:175-186): the hoisted message MLP `msg`
+    """One launch for a whole MP layer (g4c_mlp_io_t.upd; reference nn/blocks.py:175-186): the hoisted message MLP `msg`
     on `sources` (one 128-wide weighted block + the two gathered node-side products as additive sources) with the aggregation over
     `csr`, and — in the same persistent workgroups — the node MLP `upd` on [aggregate | v] with LayerNorm / `act` and, when
     `head_outs` is given, the heads packed behind `upd` (the next layer's products).  f16x3 arithmetic only, inference only.
     Returns (e' rows or None, v', head_outs)."""
-    lib = _lib.load()
     dev = _lib.require_hip(*[s.tensor for s in sources], *[s.index for s in sources], v, v_out)
     if msg.split != "f16x2" or upd.split != "f16x2":
         raise NotImplementedError("mp_layer_forward needs both MLPs packed for the f16x3 arithmetic")
-    tiles = csr.tiles()
-    if tiles is None or n_rows != csr.n:
+    if csr.tiles() is None or n_rows != csr.n:
         raise ValueError("mp_layer_forward: the rows must be in segment order with segments of at most 32 rows")
     v = _f32_2d(v, "v")
     n_t = csr.n_seg
-    t_rows, t_seg, nt = tiles
     e_out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev) if store_rows else None
     agg = torch.empty((n_t, 128), dtype=torch.float32, device=dev)          # (scratch: written and re-read by the same workgroup, L2-resident)
     if v_out is None:
@@ -818,35 +838,31 @@ def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr
     n_heads = 0 if head_outs is None else len(head_outs)
     if n_heads and (n_heads != upd.n_heads):
         raise ValueError(f"{n_heads} head outputs for a packing with {upd.n_heads} heads")
-    ho = (C.c_void_p * max(n_heads, 1))(*([h.data_ptr() for h in head_outs] if n_heads else [None]))
-    arr = _src_array(sources)
-    call = lambda: _lib.check(lib.g4c_mp_layer_forward_bx6(
-        C.byref(msg.desc), arr, len(sources), n_rows, _lib.ptr(e_out), 128 if e_out is None else _ld(e_out),
-        _lib.ptr(t_rows), _lib.ptr(t_seg), _lib.ptr(csr.off), nt, _lib.ptr(agg), _ld(agg), _agg_mode(agg_mean, csr),
-        C.byref(upd.desc), _lib.ptr(v), _ld(v), act, _lib.ptr(v_out), _ld(v_out),
-        upd.head_w if n_heads else None, n_heads, ho, _ld(head_outs[0]) if n_heads else 128, _lib.stream_handle(dev)))
-    if KernelTimer.active is None:
-        call()
-    else:
-        in_b = 4.0 * 128 * (n_rows * (2 if store_rows else 1) + n_t * (2 + n_heads))
-        _timed("mlp_bx6_kernel", msg.flops_per_row * n_rows + upd.flops_per_row * n_t, in_b, call)
+    io = _lib.g4c_mlp_io_t(row_count=n_rows, out=_lib.ptr(e_out), out_ld=128 if e_out is None else _ld(e_out), upd=C.pointer(upd.desc),
+                           v=_lib.ptr(v), v_ld=_ld(v), v_act=act, v_out=_lib.ptr(v_out), v_out_ld=_ld(v_out))
+    _set_agg(io, csr, agg, agg_mean)
+    if n_heads:
+        _set_heads(io, head_outs)
+    in_b = 4.0 * 128 * (n_rows * (2 if store_rows else 1) + n_t * (2 + n_heads))
+    _run(msg, _src_array(sources), len(sources), n_rows, io, dev, msg.flops_per_row * n_rows + upd.flops_per_row * n_t, in_b)
     return e_out, v_out, head_outs
 
 
 def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: int = _lib.ACT_NONE,
                 out: Optional[Tensor] = None, out_idx32: Optional[Tensor] = None,
-                resid: Optional[Tensor] = None, resid_col0: int = 0, tile_mode: Optional[int] = None,
+                resid: Optional[Tensor] = None, resid_col0: int = 0, rows: Optional[Tuple[int, int]] = None,
                 head_outs: Optional[Sequence[Tensor]] = None, agg: Optional[Tuple[CsrPlan, Tensor, bool]] = None,
                 save: Optional[Sequence[Optional[Tensor]]] = None, mul: Optional[Sequence[Optional[Tensor]]] = None,
                 store_rows: bool = True, rows_dtype: Optional[torch.dtype] = None, rows_act: int = _lib.ACT_NONE) -> Optional[Tensor]:
-    """One fused MLP launch (g4c_mlp_forward).  `tile_mode` (tests / tuning) runs every row through
-    g4c_mlp_forward_rows with that kernel variant instead of the library's own choice.
-    `head_outs` ([n_rows, 128] tensors, one per head of `packed`): g4c_mlp_forward_heads.
+    """One fused MLP launch (g4c_mlp_run).  `rows` = (begin, count) (tests / tuning): only those rows, begin a multiple of 32 —
+    one MLP split over several launches.
+    `head_outs` ([n_rows, 128] tensors, one per head of `packed`; all fp32, or all bf16 in the rounded-bf16 mode): the heads.
     `agg` = (csr, out [n_seg, 128], mean): also aggregate the output rows over the segments of `csr` (rows must be in segment
-    order) — inside the launch when the kernel can (g4c_mlp_forward_bx6_agg), otherwise with a g4c_segment_reduce afterwards.
-    `save` (training forward, bf16x6 only): one [n_rows, 128] fp32 tensor (or None) per layer, receiving that layer's output rows
-    (g4c_mlp_forward_bx6_save); `mul` (with `save`): per hidden layer the SELU-output rows whose slope multiplies that layer's
-    result instead of bias + SELU (the backward chain of a block, see include/g4c.h).
+    order) — inside the launch when the kernel can, otherwise with a g4c_segment_reduce afterwards.
+    `save` (training forward, bf16x6 / f16x3 only): one [n_rows, 128] fp32 tensor (or None) per layer, receiving that layer's output
+    rows; `mul` (with `save`): per hidden layer the SELU-output rows whose slope multiplies that layer's result instead of bias + SELU
+    (the backward chain of a block, see include/g4c.h).
+    A bf16 `out` (rounded-bf16 mode): the rows are stored as bf16.
     `rows_dtype=torch.bfloat16` (rounded-bf16 mode, with an aggregation the launch fuses; ignored otherwise): the output rows are
     stored as bf16 — their consumer rounds them to bf16 on load anyway, and the launch is HBM-bound on them; the aggregate stays fp32.
     `rows_act=ACT_SELU` (only together with bf16 rows): the stored rows are bf16(SELU(row)) — the activation their reader would apply
@@ -856,11 +872,10 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
     if torch.is_grad_enabled():
         from . import autograd as _ag
         if _ag.wants_grad(packed, sources, resid):
-            if out is not None or out_idx32 is not None or head_outs is not None or agg is not None or tile_mode is not None or save is not None:
+            if out is not None or out_idx32 is not None or head_outs is not None or agg is not None or rows is not None or save is not None:
                 raise NotImplementedError("out= / heads / fused aggregation are inference-only forms of mlp_forward; "
                                           "call under torch.no_grad() or use the plain form")
             return _ag.mlp(packed, sources, n_rows, act, resid, resid_col0)
-    lib = _lib.load()
     if packed.rs2:
         ok = [isinstance(s.tensor, RsOrderedRows) for s in sources]
         if len(sources) != 2 or not ok[0] or ok[1] != (packed.rs2 == 4) or any(s.tensor.dtype != torch.bfloat16 for s in sources):
@@ -901,135 +916,73 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
             j += 1
     # store_rows=False (with a fused aggregation only): the output rows are not written, only their aggregate
     fusable = (agg is not None and FUSE_AGG and packed.precision in ("bf16x6", "bf16") and packed.n_out == 128 and head_outs is None
-               and tile_mode is None and out_idx32 is None and resid is None and n_rows == agg[0].n and agg[0].tiles() is not None)
+               and rows is None and out_idx32 is None and resid is None and n_rows == agg[0].n and agg[0].tiles() is not None)
     if not store_rows and not fusable:
         raise ValueError("store_rows=False needs an aggregation the launch can fuse (ops.can_fuse_aggregation)")
+    reduce_after = None
+    if agg is not None and not fusable:          # the plain launch, then the separate reduction
+        reduce_after, agg = agg, None
     rows16 = bool(fusable and store_rows and rows_dtype == torch.bfloat16 and packed.precision == "bf16" and out is None)
     if out is None and store_rows:
         out = torch.empty((n_rows, packed.n_out), dtype=torch.bfloat16 if rows16 else torch.float32, device=dev)
-    # algorithmic bytes per row of the weighted input blocks (bf16 rows count 2 bytes per value)
+    if out is not None and out.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"out: expected float32 or bfloat16, got {out.dtype}")
+    row_begin, row_count = rows if rows is not None else (0, n_rows)
+    io = _lib.g4c_mlp_io_t(act=act, row_begin=row_begin, row_count=row_count, out=_lib.ptr(out),
+                           out_ld=_ld(out) if out is not None else 128, out_idx=_lib.ptr(out_idx32), resid=_lib.ptr(resid),
+                           resid_ld=_ld(resid) if resid is not None else 0, resid_col0=resid_col0)
+    if out is not None and out.dtype == torch.bfloat16:
+        if agg is None and (packed.precision != "bf16" or out_idx32 is not None or resid is not None):
+            raise TypeError("a bf16 `out` needs the rounded-bf16 mode and no output index / residual")
+        if rows16 and rows_act not in (_lib.ACT_NONE, _lib.ACT_SELU):
+            raise ValueError("rows_act: only ACT_SELU")
+        io.out_dtype = 2 if (rows16 and rows_act == _lib.ACT_SELU) else 1
+    # algorithmic bytes per row: the weighted input blocks (bf16 rows count 2 bytes per value) and the output row
     in_bytes = float(sum(s.width * (2 if s.tensor.dtype == torch.bfloat16 else 4) for s in sources if not s.additive))
-    if store_rows:
-        args = (_lib.ptr(out), _ld(out), _lib.ptr(out_idx32), act, _lib.ptr(resid), _ld(resid) if resid is not None else 0,
-                resid_col0, _lib.stream_handle(dev))
+    nbytes = (in_bytes + 4.0 * packed.n_out) * row_count
+    if head_outs is not None:
+        if len(head_outs) != packed.n_heads or packed.n_heads == 0:
+            raise ValueError(f"{len(head_outs)} head outputs for a packing with {packed.n_heads} heads")
+        if out_idx32 is not None or resid is not None:
+            raise NotImplementedError("heads with an output index / residual")
+        _lib.require_hip(*head_outs)
+        if any(h.dtype == torch.bfloat16 for h in head_outs):
+            # rounded-bf16 mode: the head rows (the next message MLP's first-layer products) stored as bf16
+            if packed.precision != "bf16" or any(h.dtype != torch.bfloat16 for h in head_outs):
+                raise TypeError("bf16 head outputs need the rounded-bf16 mode, and every head in bf16")
+        elif out.dtype != torch.float32:
+            raise TypeError("heads stored as fp32 need fp32 output rows (bf16 rows: bf16 heads)")
+        _set_heads(io, head_outs)
+        if packed.precision == "fp32":
+            nbytes = 4.0 * (sum(packed.seg_widths) + packed.n_out * (1 + packed.n_heads)) * n_rows
     if agg is not None:
         csr, agg_out, agg_mean = agg
-        tiles = csr.tiles() if fusable else None
-        if tiles is None:        # not fusable here: the plain launch, then the separate reduction
-            y = mlp_forward(packed, sources, n_rows, act, out, out_idx32, resid, resid_col0, tile_mode, head_outs)
-            segment_reduce(y, csr, agg_mean, out=agg_out)
-            return y
         _lib.require_hip(agg_out)
-        t_rows, t_seg, nt = tiles
-        mode = _agg_mode(agg_mean, csr)
-        if agg_out.dtype == torch.bfloat16:          # (G4C_AGG_OUT_BF16: bf16 aggregate rows in the row-split kernel's column order)
-            if not (packed.rs_order and packed.precision == "bf16"):
-                raise ValueError("a bf16 aggregate needs weights packed for the row-split kernel (rounded-bf16 mode)")
-            mode |= 1 << 16
-        elif agg_out.dtype != torch.float32:
+        if agg_out.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"aggregate: expected float32 (or bfloat16 on the row-split kernel), got {agg_out.dtype}")
-        tail = (_lib.ptr(t_rows), _lib.ptr(t_seg), _lib.ptr(csr.off), nt, _lib.ptr(agg_out), _ld(agg_out), mode,
-                _lib.stream_handle(dev))
-        o_ld = _ld(out) if out is not None else 128
-        if packed.precision == "bf16x6":
-            call = lambda: _lib.check(lib.g4c_mlp_forward_bx6_agg(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out), o_ld, act, *tail))
-        else:
-            if out is not None and out.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"out: expected float32 or bfloat16, got {out.dtype}")
-            o_dt = 1 if (out is not None and out.dtype == torch.bfloat16) else 0
-            if o_dt and rows_act == _lib.ACT_SELU and rows16:
-                o_dt = 2
-            elif rows_act != _lib.ACT_NONE and rows16:
-                raise ValueError("rows_act: only ACT_SELU")
-            call = lambda: _lib.check(lib.g4c_mlp_forward_bf16_agg(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out), o_ld, o_dt,
-                                                                   act, *tail))
-        if KernelTimer.active is None:
-            call()
-        else:
-            out_b = 0 if not store_rows else packed.n_out * (2 if out.dtype == torch.bfloat16 else 4)
-            _timed("mlp_bx6_kernel", packed.flops_per_row * n_rows, (in_bytes + out_b) * n_rows + 4.0 * packed.n_out * csr.n_seg, call)
-    elif save is not None:
-        if packed.precision != "bf16x6" or head_outs is not None or out_idx32 is not None or tile_mode is not None:
-            raise NotImplementedError("save= needs the bf16x6 kernel without heads / output index / forced tile mode")
-        if len(save) != packed.desc.n_layers:
-            raise ValueError(f"{len(save)} save tensors for {packed.desc.n_layers} layers")
+        _set_agg(io, csr, agg_out, agg_mean)
+        if agg_out.dtype == torch.bfloat16:          # (G4C_AGG_OUT_BF16: bf16 aggregate rows in the row-split kernel's column order)
+            io.agg_mode |= 1 << 16
+        out_b = 0 if not store_rows else packed.n_out * (2 if out.dtype == torch.bfloat16 else 4)
+        nbytes = (in_bytes + out_b) * n_rows + 4.0 * packed.n_out * csr.n_seg
+    if save is not None:
         live = [t for t in save if t is not None]
         _lib.require_hip(*live)
         if any(t.dim() != 2 or t.size(0) < n_rows or t.size(1) < 128 or t.stride(1) != 1 or _ld(t) != _ld(live[0]) for t in live):
             raise ValueError("save tensors must be [n_rows, >= 128] fp32 with one common leading dimension")
-        sv = (C.c_void_p * len(save))(*[None if t is None else t.data_ptr() for t in save])
-        ml, ml_ld = None, 0
+        if len(save) > _lib.MAX_LAYERS:
+            raise ValueError(f"{len(save)} save tensors for {packed.desc.n_layers} layers")
+        io.n_save, io.save_ld = len(save), _ld(live[0]) if live else 128
+        io.save[:len(save)] = [_lib.ptr(t) for t in save]
         if mul is not None:
             lm = [t for t in mul if t is not None]
             _lib.require_hip(*lm)
             if len(mul) != len(save) or any(t.size(0) < n_rows or t.size(1) < 128 or t.stride(1) != 1 or _ld(t) != _ld(lm[0]) for t in lm):
                 raise ValueError("mul tensors must be [n_rows, >= 128] fp32 with one common leading dimension, one entry per layer")
-            ml = (C.c_void_p * len(mul))(*[None if t is None else t.data_ptr() for t in mul])
-            ml_ld = _ld(lm[0]) if lm else 128
-        call = lambda: _lib.check(lib.g4c_mlp_forward_bx6_save(
-            C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out), _ld(out), act, _lib.ptr(resid),
-            _ld(resid) if resid is not None else 0, resid_col0, sv, _ld(live[0]) if live else 128, ml, ml_ld, _lib.stream_handle(dev)))
-        if KernelTimer.active is None:
-            call()
-        else:
-            _timed("mlp_bx6_kernel", packed.flops_per_row * n_rows, 4.0 * (sum(packed.seg_widths) + packed.n_out + 128 * len(live)) * n_rows, call)
-    elif packed.precision != "fp32":
-        if tile_mode is not None:
-            raise NotImplementedError("bf16 MLP with a forced tile mode")
-        if head_outs is not None:
-            if len(head_outs) != packed.n_heads or packed.n_heads == 0:
-                raise ValueError(f"{len(head_outs)} head outputs for a packing with {packed.n_heads} heads")
-            if out_idx32 is not None or resid is not None:
-                raise NotImplementedError("heads with an output index / residual")
-            _lib.require_hip(*head_outs)
-            ho = (C.c_void_p * len(head_outs))(*[h.data_ptr() for h in head_outs])
-            if any(h.dtype == torch.bfloat16 for h in head_outs):
-                # rounded-bf16 mode: the head rows (the next message MLP's first-layer products) stored as bf16 (g4c_mlp_forward_heads_bf16_out)
-                if packed.precision != "bf16" or any(h.dtype != torch.bfloat16 for h in head_outs):
-                    raise TypeError("bf16 head outputs need the rounded-bf16 mode, and every head in bf16")
-                # (a bf16 `out` as well: the launch's own rows stored as bf16 — g4c_mlp_forward_heads_bf16_rows)
-                call = lambda: _lib.check(lib.g4c_mlp_forward_heads_bf16_rows(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out),
-                                                                              _ld(out), 1 if out.dtype == torch.bfloat16 else 0, act, packed.head_w,
-                                                                              len(head_outs), ho, _ld(head_outs[0]), 1, _lib.stream_handle(dev)))
-            else:
-                if out is not None and out.dtype != torch.float32:
-                    raise TypeError("heads stored as fp32 need fp32 output rows (bf16 rows: bf16 heads, g4c_mlp_forward_heads_bf16_rows)")
-                heads_fn = lib.g4c_mlp_forward_heads_bf16 if packed.precision == "bf16" else lib.g4c_mlp_forward_heads_bx6
-                call = lambda: _lib.check(heads_fn(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out),
-                                                   _ld(out), act, packed.head_w, len(head_outs), ho,
-                                                   _ld(head_outs[0]), _lib.stream_handle(dev)))
-        elif out is not None and out.dtype == torch.bfloat16:
-            # rounded-bf16 mode: plain 128-wide output rows stored as bf16 (g4c_mlp_forward_bf16_out: first-layer products)
-            if packed.precision != "bf16" or out_idx32 is not None or resid is not None:
-                raise TypeError("a bf16 `out` needs the rounded-bf16 mode and no output index / residual")
-            call = lambda: _lib.check(lib.g4c_mlp_forward_bf16_out(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out), _ld(out), 1, act,
-                                                                   _lib.stream_handle(dev)))
-        else:
-            fwd = lib.g4c_mlp_forward_bf16 if packed.precision == "bf16" else lib.g4c_mlp_forward_bx6
-            call = lambda: _lib.check(fwd(C.byref(packed.desc), arr, len(sources), n_rows, *args))
-        if KernelTimer.active is None:
-            call()
-        else:
-            _timed("mlp_bx6_kernel", packed.flops_per_row * n_rows, (in_bytes + 4.0 * packed.n_out) * n_rows, call)
-    elif head_outs is not None:
-        if len(head_outs) != packed.n_heads or packed.n_heads == 0:
-            raise ValueError(f"{len(head_outs)} head outputs for a packing with {packed.n_heads} heads")
-        if out_idx32 is not None or resid is not None or tile_mode is not None:
-            raise NotImplementedError("heads with an output index / residual / forced tile mode")
-        _lib.require_hip(*head_outs)
-        ho = (C.c_void_p * len(head_outs))(*[h.data_ptr() for h in head_outs])
-        call = lambda: _lib.check(lib.g4c_mlp_forward_heads(C.byref(packed.desc), arr, len(sources), n_rows, _lib.ptr(out), _ld(out),
-                                                            act, packed.head_w, len(head_outs), ho, _ld(head_outs[0]),
-                                                            _lib.stream_handle(dev)))
-        if KernelTimer.active is None:
-            call()
-        else:
-            _timed("mlp_split_kernel<4>", packed.flops_per_row * n_rows, 4.0 * (sum(packed.seg_widths) + packed.n_out * (1 + packed.n_heads)) * n_rows, call)
-    elif tile_mode is not None:
-        _lib.check(lib.g4c_mlp_forward_rows(C.byref(packed.desc), arr, len(sources), n_rows, 0, n_rows, tile_mode, *args))
-    elif KernelTimer.active is None:
-        _lib.check(lib.g4c_mlp_forward(C.byref(packed.desc), arr, len(sources), n_rows, *args))
-    else:
-        _timed("mlp_split_kernel<4>", packed.flops_per_row * n_rows, 4.0 * (sum(packed.seg_widths) + packed.n_out) * n_rows,
-               lambda: _lib.check(lib.g4c_mlp_forward(C.byref(packed.desc), arr, len(sources), n_rows, *args)))
+            io.mul[:len(mul)] = [_lib.ptr(t) for t in mul]
+            io.mul_ld = _ld(lm[0]) if lm else 128
+        nbytes = 4.0 * (sum(packed.seg_widths) + packed.n_out + 128 * len(live)) * n_rows
+    _run(packed, arr, len(sources), n_rows, io, dev, packed.flops_per_row * row_count, nbytes)
+    if reduce_after is not None:
+        segment_reduce(out, reduce_after[0], reduce_after[2], out=reduce_after[1])
     return out

@@ -5,7 +5,7 @@ packing or column-ordering code of graphs4cfd_amd: a kernel's bf16 rows in the r
 
 Where a launch rounds (derived from csrc/mlp_common.h `split3x4<1>` — one round-to-nearest-even `(__bf16)x` of an fp32 value — the
 `SP == 1` branches of mlp_fused.hip / mlp_ws.hip / mlp_rs.hip, and ops.PackedMLP, whose rounded-bf16 stream is the leading plane of
-`g4c_mlp_pack_layer_bx6`, i.e. bf16_rne(W)):
+`g4c_mlp_pack_layer`, i.e. bf16_rne(W)):
 
 - Wide input blocks: bf16_rne(act(x)[idx]) times bf16_rne(W_block), the products accumulated (fp64 here, fp32 MFMA in the kernel).
 - Narrow blocks (<= 8 columns, read without index or activation, the vector-ALU path): x times W in fp32 class — nothing rounded.

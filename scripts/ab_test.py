@@ -1,5 +1,6 @@
 """Within-process A/B timing of two builds of libg4c.so on the hoisted edge MLP / node MLP (interleaved rounds,
 median + min), because run-to-run (box-to-box, DVFS) noise between separate invocations is ~5 %.
+Both builds must have this tree's ABI version (g4c_version(): the layout of g4c_mlp_io_t / g4c_mlp_t and the entry points).
 Usage: python scripts/ab_test.py libA.so libB.so [--rows 600000] [--rounds 15]"""
 import argparse, ctypes as C, os, statistics, sys
 import torch
@@ -7,20 +8,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from graphs4cfd_amd import _lib, ops
 from graphs4cfd_amd.nn import blocks as B
 
-ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rows", type=int, default=600000)
+ap = argparse.ArgumentParser(description="Within-process A/B timing of builds of libg4c.so of the SAME ABI version (g4c_version).")
+ap.add_argument("libs", nargs="+", help="builds of libg4c.so with this tree's g4c_version(): other versions are refused")
+ap.add_argument("--rows", type=int, default=600000)
 ap.add_argument("--rounds", type=int, default=15); ap.add_argument("--inner", type=int, default=3)
 ap.add_argument("--precision", default="fp32")
-ap.add_argument("--modes", default="", help="comma list of tile modes: each library is timed once per mode (default: the library's own policy)")
 a = ap.parse_args()
-_modes = [int(m) for m in a.modes.split(",")] if a.modes else [None]
-a.libs, modes = [l for l in a.libs for _ in _modes], [m for _ in a.libs for m in _modes]
 
 
 def load(path):
     lib = C.CDLL(os.path.abspath(path))
     for name, (res, args) in _lib._SIGNATURES.items():
-        if hasattr(lib, name):       # older builds lack the newest entry points
-            fn = getattr(lib, name); fn.restype, fn.argtypes = res, args
+        fn = getattr(lib, name); fn.restype, fn.argtypes = res, args
+    if lib.g4c_version() != _lib.load().g4c_version():
+        sys.exit(f"{path}: ABI version {lib.g4c_version()}, this tree's is {_lib.load().g4c_version()}: A/B needs builds of the same version")
     return lib
 
 
@@ -47,8 +48,8 @@ packs = [pack_for(lib) for lib in libs]
 cur = [0]
 src_e = [ops.Source(e), ops.Source(pr, index=row, additive=True), ops.Source(pc, index=col, additive=True)]
 src_v = [ops.Source(agg), ops.Source(v)]
-cases = {"edge(hoisted)": lambda: ops.mlp_forward(packs[cur[0]][0], src_e, rows, 0, out=out_e, tile_mode=modes[cur[0]]),
-         "node": lambda: ops.mlp_forward(packs[cur[0]][1], src_v, n, 1, out=out_v, tile_mode=modes[cur[0]])}
+cases = {"edge(hoisted)": lambda: ops.mlp_forward(packs[cur[0]][0], src_e, rows, 0, out=out_e),
+         "node": lambda: ops.mlp_forward(packs[cur[0]][1], src_v, n, 1, out=out_v)}
 ref = {}
 for cname, fn in cases.items():
     times = [[] for _ in libs]
@@ -63,4 +64,4 @@ for cname, fn in cases.items():
             times[li].append(s.elapsed_time(t) / a.inner * 1e3)
     for li, p in enumerate(a.libs):
         d = (ref[cname][li] - ref[cname][0]).abs().max().item()
-        print(f"{cname:14s} {os.path.basename(p) + ('' if modes[li] is None else f' mode {modes[li]}'):28s} median {statistics.median(times[li]):8.1f} us   min {min(times[li]):8.1f} us   max|out - out_A| {d:.1e}")
+        print(f"{cname:14s} {os.path.basename(p):28s} median {statistics.median(times[li]):8.1f} us   min {min(times[li]):8.1f} us   max|out - out_A| {d:.1e}")

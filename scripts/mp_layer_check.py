@@ -1,4 +1,4 @@
-"""The fused MP layer (ops.mp_layer_forward / g4c_mp_layer_forward_bx6: message MLP + aggregation + node MLP + heads in one launch)
+"""The fused MP layer (ops.mp_layer_forward / g4c_mlp_io_t.upd: message MLP + aggregation + node MLP + heads in one launch)
 against the separate launches of the same GNBlock (blocks.FUSE_LAYER = False): v', e', the next layer's products, over sizes from one
 tile to 200k edges, constant and ragged in-degrees (empty segments, the last targets without edges), with / without stored e', with /
 without heads; then the same step timed both ways.  Usage: python scripts/mp_layer_check.py [--time]"""

@@ -307,11 +307,11 @@ def test_rows_put_back_in_feature_order_by_hand_are_read_as_such():
     assert torch.equal(outs[0], outs[1])
 
 
-def test_uniform_aggregation_refuses_a_row_count_it_cannot_split():
+def test_mlp_run_refuses_a_uniform_row_count_it_cannot_split():
     """G4C_AGG_UNIFORM(k) through the C-ABI (ctypes): a launch whose row count is not a multiple of k is refused with G4C_EINVAL before
     anything runs (the `row_count % k` check of mlp_launch); the same launch with whole segments runs on mlp_ws_kernel's dense mode.
-    (The launcher's refusal of a sub-range in dense mode is a guard no entry point reaches: every launch with an aggregation covers
-    all its rows.)"""
+    (The launcher's refusal of a sub-range in dense mode is a guard only: g4c_mlp_run refuses a row sub-range of any launch with an
+    aggregation before that.)"""
     import ctypes as C
     n, K = 301, 5
     m = make_mlp(3 * H, 2, True, 3)
@@ -326,8 +326,9 @@ def test_uniform_aggregation_refuses_a_row_count_it_cannot_split():
         t_rows, t_seg, nt = csr.tiles()
 
         def call(rows):
-            return lib.g4c_mlp_forward_bf16_agg(C.byref(pk.desc), arr, len(src), rows, _lib.ptr(out), H, 0, _lib.ACT_NONE, _lib.ptr(t_rows),
-                                                _lib.ptr(t_seg), _lib.ptr(csr.off), nt, _lib.ptr(agg), H, 1 | (K << 8), _lib.stream_handle(DEV))
+            io = _lib.g4c_mlp_io_t(row_count=rows, out=_lib.ptr(out), out_ld=H, tile_rows=_lib.ptr(t_rows), tile_seg=_lib.ptr(t_seg),
+                                   seg_off=_lib.ptr(csr.off), n_tiles=nt, agg=_lib.ptr(agg), agg_ld=H, agg_mode=1 | (K << 8))
+            return lib.g4c_mlp_run(C.byref(pk.desc), arr, len(src), rows, C.byref(io), _lib.stream_handle(DEV))
         assert call(E - 1) == _lib.EINVAL and last_kernel() == 0
         assert torch.isnan(agg).all()
         assert call(E) == _lib.OK and last_kernel() == WS

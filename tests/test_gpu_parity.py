@@ -130,10 +130,10 @@ def test_mlp_row_tails_and_leading_dims(golden):
 
 
 @pytest.mark.parametrize("rows", [1, 33, 1000, 20000])
-def test_mlp_kernel_variants_agree(rows, monkeypatch):
-    """The fp32-MFMA kernel (g4c_mlp_forward / g4c_mlp_forward_rows tile_rows = 324), whole and split over two row-range
-    launches: hoisted edge form (gathered additive terms + SELU-on-load) and the two-block node form, against the oracle MLP
-    on the concatenated input.  Any other tile_rows value is an argument error."""
+def test_mlp_kernel_row_range_launches_agree(rows, monkeypatch):
+    """The fp32-MFMA kernel (G4C_WFMT_FP32), whole and split over two row-range launches (g4c_mlp_io_t.row_begin / row_count):
+    hoisted edge form (gathered additive terms + SELU-on-load) and the two-block node form, against the oracle MLP on the
+    concatenated input.  A row range that does not start at a multiple of 32 is an argument error."""
     H, n = 128, max(rows // 6, 1)
     torch.manual_seed(rows)
     monkeypatch.setattr(ops, "_PRECISION", "fp32")      # the tile variants are the fp32-MFMA kernels
@@ -154,13 +154,21 @@ def test_mlp_kernel_variants_agree(rows, monkeypatch):
     src_v = [ops.Source(agg), ops.Source(v, index=idx)]
     wn = {f"m.{k}": t.cpu() for k, t in blk.node_mlp.state_dict().items()}
     ref_v = O.mlp(torch.cat([agg, v[idx.long()]], 1).cpu(), wn, "m")
-    with pytest.raises(ValueError, match="tile_rows"):
-        ops.mlp_forward(pk_e, src_e, rows, tile_mode=64)
-    for mode in (None, 324):
-        y = ops.mlp_forward(pk_e, src_e, rows, tile_mode=mode)
-        torch.testing.assert_close(y.cpu(), ref_e, rtol=2e-4, atol=2e-4, msg=lambda m: f"edge mode {mode}: {m}")
-        y = ops.mlp_forward(pk_v, src_v, n, _lib.ACT_SELU, tile_mode=mode)
-        torch.testing.assert_close(y.cpu(), torch.selu(ref_v), rtol=2e-4, atol=2e-4, msg=lambda m: f"node mode {mode}: {m}")
+    with pytest.raises(ValueError, match="row_begin"):
+        ops.mlp_forward(pk_e, src_e, rows, rows=(16, rows - 16))
+
+    def launches(pk, src, m, act):
+        """The whole range in one launch, and in two launches split at a multiple of 32 into one output."""
+        whole = ops.mlp_forward(pk, src, m, act)
+        cut = min(((m + 1) // 2 + 31) // 32 * 32, m // 32 * 32)
+        split = torch.full_like(whole, float("nan"))
+        for r in ((0, cut), (cut, m - cut)):
+            ops.mlp_forward(pk, src, m, act, out=split, rows=r)
+        return {"whole": whole, "split": split}
+    for mode, y in launches(pk_e, src_e, rows, _lib.ACT_NONE).items():
+        torch.testing.assert_close(y.cpu(), ref_e, rtol=2e-4, atol=2e-4, msg=lambda m: f"edge {mode}: {m}")
+    for mode, y in launches(pk_v, src_v, n, _lib.ACT_SELU).items():
+        torch.testing.assert_close(y.cpu(), torch.selu(ref_v), rtol=2e-4, atol=2e-4, msg=lambda m: f"node {mode}: {m}")
 
 
 @pytest.mark.parametrize("rows", [1, 200, 40000])
@@ -222,7 +230,7 @@ def test_mlp_bf16_variant(rows):
 @pytest.mark.parametrize("prec", ["fp32", "bf16x6", "f16x3"])
 @pytest.mark.parametrize("rows", [33, 5000, 40000])
 def test_mlp_heads(rows, prec, monkeypatch):
-    """g4c_mlp_forward_heads: the node MLP launch also emits W1[:, H:2H] y and W1[:, 2H:] y of the next edge MLP
+    """Heads (g4c_mlp_io_t.n_heads): the node MLP launch also emits W1[:, H:2H] y and W1[:, 2H:] y of the next edge MLP
     == separate products of the stored output."""
     H = 128
     torch.manual_seed(rows)
@@ -246,13 +254,13 @@ def test_mlp_heads(rows, prec, monkeypatch):
 @pytest.mark.parametrize("prec", ["f16x3", "bf16x6", "bf16"])
 @pytest.mark.parametrize("case", ["knn6", "ragged", "unsorted", "long_segment"])
 def test_edge_mlp_with_fused_aggregation(case, prec, monkeypatch):
-    """ops.mlp_forward(agg=...): the edge launch also reduces its output rows per target (g4c_mlp_forward_bx6_agg on tiles
+    """ops.mlp_forward(agg=...): the edge launch also reduces its output rows per target (g4c_mlp_io_t.agg on tiles
     of whole segments) == the plain launch followed by g4c_segment_reduce, bit for bit; inputs the fused kernel cannot
     take (rows not in segment order, a segment longer than a tile) go through the separate reduction transparently."""
     H, n = 128, 700
     torch.manual_seed(21)
     monkeypatch.setattr(ops, "FUSE_AGG", True)
-    monkeypatch.setattr(ops, "_PRECISION", prec)       # ("bf16": g4c_mlp_forward_bf16_agg, the rounded-operand mode of config 3)
+    monkeypatch.setattr(ops, "_PRECISION", prec)       # ("bf16": G4C_WFMT_BF16, the rounded-operand mode of config 3)
     if case == "knn6":
         col = torch.arange(n).repeat_interleave(6)
     elif case == "ragged":                          # degrees 0..9 incl. empty targets at both ends
@@ -1490,7 +1498,7 @@ def test_ws_persistent_kernel_equals_tile_kernel(rows, variant):
     layer hoisted, rows direct / through an index / scattered through an output index), with the fused per-target aggregation on
     regular and ragged segments (bit-exact reduction of the rows it stores, same aggregate when the rows are not stored) — in the
     f16x3 stream and in the rounded-bf16 mode, for three-layer (MuS-GNN) and two-layer (REMuS-GNN) MLPs; in the rounded-bf16 mode
-    also with bf16 rows in and bf16 / bf16(SELU) rows out (g4c_mlp_forward_bf16_agg: REMuS-GNN's angle launches).
+    also with bf16 rows in and bf16 / bf16(SELU) rows out (g4c_mlp_io_t.out_dtype: REMuS-GNN's angle launches).
     Rounded-bf16 tolerance: the kernels add a row's products in different orders, and a last-bit difference of a hidden
     pre-activation can flip its rounding to bf16 (single elements differ by ~1e-3, the mean difference is round-off)."""
     prec, layers = variant
@@ -2061,7 +2069,7 @@ def test_remus_entry_products_come_from_the_producer_launch(prec):
 
 def test_remus_compact_edge_latents_are_the_same_operand():
     """blocks.COMPACT_LATENTS (round 6, rounded-bf16 mode): the edge latents between consecutive EdgeMPs of a level are stored as bf16
-    rows by the update launch (g4c_mlp_forward_heads_bf16_rows) — their only reader, the next update MLP, rounds them to bf16 on load:
+    rows by the update launch (out_dtype G4C_DTYPE_BF16 beside bf16 heads) — their only reader, the next update MLP, rounds them to bf16 on load:
     the forward is bit-identical."""
     old = ops.set_mlp_precision("bf16")
     was, was_u = B.COMPACT_LATENTS, B.UPDATE_ROW_SPLIT
@@ -2279,7 +2287,7 @@ def test_bf16_product_rows_are_exact_copies():
 # ------------------------------------------------------------------ one launch per MP layer (round 5)
 @pytest.mark.parametrize("layers", [3, 2])
 def test_fused_mp_layer_matches_the_separate_launches(layers):
-    """ops.mp_layer_forward / g4c_mp_layer_forward_bx6 (message MLP + aggregation + node MLP + the next layer's products in one
+    """ops.mp_layer_forward / g4c_mlp_io_t.upd (message MLP + aggregation + node MLP + the next layer's products in one
     launch; reference nn/blocks.py:175-186) against the separate launches of the same GNBlock, at sizes from less than one tile to
     several tile pairs per workgroup, constant and ragged in-degrees (empty segments, trailing targets without edges: node tiles of
     1 .. 64 rows per workgroup), with and without heads, with and without stored messages.  Same arithmetic per element; sums over k

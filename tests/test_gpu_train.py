@@ -86,7 +86,7 @@ def test_segment_reduce_autograd_with_permutation_and_activations():
 @pytest.mark.parametrize("hoist_min_rows", [0, 1 << 30])
 def test_fused_mlp_gradients_all_source_kinds(hoist_min_rows, save, monkeypatch):
     """hoist_min_rows 0: the gathered block is differentiated on its tensor's rows (autograd.py), 1 << 30: as a dense block.
-    save: hidden activations kept by the forward launch (g4c_mlp_forward_bx6_save) / recomputed in the backward pass."""
+    save: hidden activations kept by the forward launch (g4c_mlp_io_t.save) / recomputed in the backward pass."""
     from graphs4cfd_amd import autograd as A
     monkeypatch.setattr(A, "HOIST_MIN_ROWS", hoist_min_rows)
     monkeypatch.setattr(A, "SAVE_ACTIVATIONS", save)

@@ -26,6 +26,22 @@ def test_library_exports_every_declared_symbol():
     assert lib.g4c_version() >= 1
 
 
+def test_mlp_run_validates_its_descriptor_before_any_hip_call():
+    """g4c_mlp_run checks g4c_mlp_io_t.size first (a binding out of step with g4c.h gets G4C_EINVAL, not garbage reads) and the
+    launch arguments before it touches the device: both errors come back on a machine without a GPU."""
+    import ctypes as C
+    lib = _lib.load()
+    mlp = _lib.g4c_mlp_t(n_layers=1)
+    src = (_lib.g4c_src_t * 1)()
+    io = _lib.g4c_mlp_io_t(row_count=64)
+    io.size -= 8
+    assert lib.g4c_mlp_run(C.byref(mlp), src, 1, 64, C.byref(io), None) == _lib.EINVAL
+    assert "size" in lib.g4c_last_error().decode()
+    io = _lib.g4c_mlp_io_t(row_count=64, act=7)
+    assert lib.g4c_mlp_run(C.byref(mlp), src, 1, 64, C.byref(io), None) == _lib.EINVAL
+    assert "bad activation 7" in lib.g4c_last_error().decode()
+
+
 def test_plan_csr_matches_stable_argsort():
     rng = np.random.default_rng(0)
     keys = torch.from_numpy(rng.integers(0, 37, size=500))
