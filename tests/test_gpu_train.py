@@ -82,14 +82,46 @@ def test_segment_reduce_autograd_with_permutation_and_activations():
 
 
 # ------------------------------------------------------------------ one fused MLP with every kind of input block
+def _count_saving_forwards(monkeypatch):
+    """Wraps ops.mlp_forward: the returned list receives one entry per launch that saved its activations (`save=` without `mul=`)."""
+    calls, f0 = [], ops.mlp_forward
+
+    def fwd(*a, **k):
+        if k.get("save") is not None and k.get("mul") is None:
+            calls.append(1)
+        return f0(*a, **k)
+    monkeypatch.setattr(ops, "mlp_forward", fwd)
+    return calls
+
+
+def _expect_saves(saves, save, precision):
+    """save=True takes the saving forward in both arithmetics (an f16x3 pack is the bf16x6 kernel family: its `precision` reads
+    "bf16x6", autograd._FusedMLP.forward), save=False never does."""
+    assert (len(saves) > 0) == save, (len(saves), save, precision)
+
+
 @pytest.mark.parametrize("save", [True, False])
 @pytest.mark.parametrize("hoist_min_rows", [0, 1 << 30])
 def test_fused_mlp_gradients_all_source_kinds(hoist_min_rows, save, monkeypatch):
     """hoist_min_rows 0: the gathered block is differentiated on its tensor's rows (autograd.py), 1 << 30: as a dense block.
-    save: hidden activations kept by the forward launch (g4c_mlp_io_t.save) / recomputed in the backward pass."""
+    save: hidden activations kept by the forward launch (g4c_mlp_io_t.save) / recomputed in the backward pass (default f16x3
+    forward)."""
+    _fused_mlp_all_source_kinds(hoist_min_rows, save, "f16x3", monkeypatch)
+
+
+@pytest.mark.parametrize("save", [True, False])
+@pytest.mark.parametrize("hoist_min_rows", [0, 1 << 30])
+def test_fused_mlp_gradients_all_source_kinds_bf16x6(hoist_min_rows, save, monkeypatch):
+    """The same cases with a bf16x6 forward (the bf16x3 weight stream)."""
+    _fused_mlp_all_source_kinds(hoist_min_rows, save, "bf16x6", monkeypatch)
+
+
+def _fused_mlp_all_source_kinds(hoist_min_rows, save, precision, monkeypatch):
     from graphs4cfd_amd import autograd as A
     monkeypatch.setattr(A, "HOIST_MIN_ROWS", hoist_min_rows)
     monkeypatch.setattr(A, "SAVE_ACTIVATIONS", save)
+    monkeypatch.setattr(ops, "_PRECISION", precision)
+    saves = _count_saving_forwards(monkeypatch)
     torch.manual_seed(3)
     M, n_a, n_b, H = 3000, 500, 3000, 128
     mlp = B.MLP(2 + H + H + 3, (H, H, H), True).to(DEV)
@@ -102,6 +134,7 @@ def test_fused_mlp_gradients_all_source_kinds(hoist_min_rows, save, monkeypatch)
     srcs = [ops.Source(rel, negate=True), ops.Source(a, plan.index32(idx), pre_act=_lib.ACT_SELU),
             ops.Source(b, col0=5, width=H), ops.Source(c)]
     y = mlp.run(srcs, M, activation=torch.tanh, resid=resid, resid_col0=2)
+    _expect_saves(saves, save, precision)
     dy = torch.randn_like(y)
     y.backward(dy)
     got = {n: p.grad.clone() for n, p in mlp.named_parameters()}
@@ -178,16 +211,34 @@ def _model_and_oracle_grads(model_name, levels, nodes, hidden, seed):
     return model, float(loss), float(loss_ref), got, {k: v.grad for k, v in w.items()}
 
 
+MODEL_CASES = [("NsOneScaleGNN", 1, 128), ("NsThreeScaleGNN", 3, 128), ("NsTwoScaleGNN", 2, 32), ("NsFourScaleGNN", 4, 64),
+               ("AdvThreeScaleGNN", 3, 128)]
+
+
 @pytest.mark.parametrize("save", [True, False])
-@pytest.mark.parametrize("model_name,levels,hidden", [("NsOneScaleGNN", 1, 128), ("NsThreeScaleGNN", 3, 128), ("NsTwoScaleGNN", 2, 32),
-                                                      ("NsFourScaleGNN", 4, 64), ("AdvThreeScaleGNN", 3, 128)])
+@pytest.mark.parametrize("model_name,levels,hidden", MODEL_CASES)
 def test_model_parameter_gradients_match_oracle_autograd(model_name, levels, hidden, save, monkeypatch):
+    """Default (f16x3) forward; save=True keeps the forward's activations, save=False recomputes them."""
+    _model_parameter_gradients(model_name, levels, hidden, save, "f16x3", monkeypatch)
+
+
+@pytest.mark.parametrize("save", [True, False])
+@pytest.mark.parametrize("model_name,levels,hidden", MODEL_CASES)
+def test_model_parameter_gradients_match_oracle_autograd_bf16x6(model_name, levels, hidden, save, monkeypatch):
+    """The same models with a bf16x6 forward (the bf16x3 weight stream)."""
+    _model_parameter_gradients(model_name, levels, hidden, save, "bf16x6", monkeypatch)
+
+
+def _model_parameter_gradients(model_name, levels, hidden, save, precision, monkeypatch):
     from graphs4cfd_amd import autograd as A
     monkeypatch.setattr(A, "SAVE_ACTIVATIONS", save)
+    monkeypatch.setattr(ops, "_PRECISION", precision)
     if save:       # also the large-launch forms at this small size: single-layer products and the one-launch backward chain
         monkeypatch.setattr(A, "FUSED_LINEAR_MIN_ROWS", 0)
         monkeypatch.setattr(A, "HOIST_MIN_ROWS", 0)
+    saves = _count_saving_forwards(monkeypatch)
     model, loss, loss_ref, got, ref = _model_and_oracle_grads(model_name, levels, 2500, hidden, 7)
+    _expect_saves(saves, save, precision)
     assert abs(loss - loss_ref) <= 1e-4 * max(1.0, abs(loss_ref))
     assert set(got) == set(ref)
     worst = 0.0
