@@ -48,7 +48,7 @@ class g4c_mlp_t(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("k_pad", C.c_int32 * MAX_LAYERS), ("n_pad", C.c_int32 * MAX_LAYERS),
                 ("w", C.c_void_p * MAX_LAYERS), ("b", C.c_void_p * MAX_LAYERS),
                 ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float), ("n_out", C.c_int32), ("w_format", C.c_int32),
-                ("range_flag", C.c_void_p), ("range_slot", C.c_int32)]
+                ("range_slot", C.c_int32)]
 
 
 WFMT_FP32, WFMT_F16X2, WFMT_BF16X3, WFMT_BF16_RS, WFMT_BF16_RS2, WFMT_BF16_RS2N, WFMT_BF16 = 0, 1, 2, 3, 4, 5, 6
@@ -64,7 +64,7 @@ class g4c_mlp_io_t(C.Structure):
                 ("n_save", C.c_int32), ("save", C.c_void_p * MAX_LAYERS), ("save_ld", C.c_int32),
                 ("mul", C.c_void_p * MAX_LAYERS), ("mul_ld", C.c_int32),
                 ("upd", C.POINTER(g4c_mlp_t)), ("v", C.c_void_p), ("v_ld", C.c_int32), ("v_act", C.c_int32),
-                ("v_out", C.c_void_p), ("v_out_ld", C.c_int32)]
+                ("v_out", C.c_void_p), ("v_out_ld", C.c_int32), ("range_flag", C.c_void_p)]
 
     def __init__(self, **kw):
         super().__init__(size=C.sizeof(g4c_mlp_io_t), **kw)

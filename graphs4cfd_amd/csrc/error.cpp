@@ -33,7 +33,7 @@ int cu_count() {
 }
 }  // namespace g4c
 
-extern "C" int g4c_version(void) { return 2; }
+extern "C" int g4c_version(void) { return 3; }
 extern "C" int g4c_device_info(const void *device_ptr, int32_t *device, int32_t *cu_count) {
     G4C_REQUIRE(device_ptr && device && cu_count, G4C_EINVAL, "g4c_device_info: null pointer");
     g4c::DeviceGuard on_device(device_ptr);

@@ -1248,6 +1248,8 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
     G4C_REQUIRE(io->out_dtype != G4C_DTYPE_BF16_SELU || (agg && act == G4C_ACT_NONE), G4C_EINVAL,
                 "g4c_mlp_run: G4C_DTYPE_BF16_SELU needs the fused aggregation and no output activation");
     G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 || io->head_dtype == G4C_DTYPE_BF16, G4C_EINVAL, "g4c_mlp_run: unknown head_dtype %d", io->head_dtype);
+    G4C_REQUIRE(!io->range_flag || (mlp->range_slot >= 0 && (!node || io->upd->range_slot >= 0)), G4C_EINVAL,
+                "g4c_mlp_run: negative range_slot (mlp %d, upd %d)", mlp->range_slot, node ? io->upd->range_slot : 0);
     if (n_rows == 0) return G4C_OK;
     float *const out = (float *)io->out;
     const int32_t out_ld = io->out_ld;
@@ -1372,8 +1374,7 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         G4C_REQUIRE(!mul || (io->mul_ld >= NP && (io->mul_ld & 3) == 0), G4C_EINVAL, "g4c_mlp_run: mul_ld=%d", io->mul_ld);
         p.mul_ld = io->mul_ld;
     }
-    p.range_flag = f16x2 ? mlp->range_flag : nullptr; p.range_slot = mlp->range_slot;
-    G4C_REQUIRE(!p.range_flag || p.range_slot >= 0, G4C_EINVAL, "g4c_mlp_run: negative range_slot");
+    p.range_flag = f16x2 ? io->range_flag : nullptr; p.range_slot = mlp->range_slot;
     // heads (the kernels read their weights where the stream of the MLP that owns them ends; with `upd`, that MLP's)
     for (int hd = 0; hd < n_heads; ++hd) G4C_REQUIRE(io->head_out[hd], G4C_EINVAL, "g4c_mlp_run: null head output %d", hd);
     p.n_heads = node ? 0 : n_heads; p.head_ld = p.n_heads ? io->head_ld : 0; p.head_bf16 = 0;
@@ -1419,8 +1420,7 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         q.v = io->v; q.v_ld = io->v_ld; q.w = (const float *)u->w[0]; q.b = (const float *)u->b[0];
         q.gamma = u->ln_gamma; q.beta = u->ln_beta; q.eps = u->ln_eps; q.act = io->v_act;
         q.out = io->v_out; q.out_ld = io->v_out_ld; q.n_heads = n_heads; q.head_ld = io->head_ld;
-        q.range_flag = u->range_flag; q.range_slot = u->range_slot;
-        G4C_REQUIRE(!q.range_flag || q.range_slot >= 0, G4C_EINVAL, "g4c_mlp_run: upd's negative range_slot");
+        q.range_flag = io->range_flag; q.range_slot = u->range_slot;
         for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) q.head_out[hd] = nullptr;
         if (n_heads) {
             G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 && (io->head_ld & 3) == 0 && io->head_ld >= NP, G4C_EINVAL,

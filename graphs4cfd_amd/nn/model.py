@@ -119,7 +119,7 @@ class GNN(nn.Module):
             if isinstance(m, _MLP):
                 m._site = f"{type(self).__name__}.{name}"
                 sites.append(m._site)
-        self._range_sites = frozenset(sites)     # what a rollout of THIS model clears on entry and reports (ops.check_f16_range(sites=))
+        self._range_sites = frozenset(sites)     # this model's names in a report (ops.check_f16_range(sites=))
 
     def to(self, *args, **kwargs):
         out = super().to(*args, **kwargs)
@@ -248,6 +248,9 @@ def set_forward_validation(on: bool) -> bool:
     return old
 
 
+_spare_flags = {}       # device -> the flag buffer of a validated bare forward that returned (zero: take() clears what it finds)
+
+
 def _range_checked_forward(f):
     import functools
 
@@ -257,12 +260,12 @@ def _range_checked_forward(f):
         if (not FORWARD_VALIDATION or ops.StaticCache.active is not None or ops.mlp_precision() != "f16x3" or ops.grad_mode()
                 or not torch.is_tensor(field) or field.device.type != "cuda" or torch.cuda.is_current_stream_capturing()):
             return f(self, graph, *args, **kwargs)          # (inside a rollout step / training / another arithmetic: validated elsewhere)
-        watch = ops.RangeWatch(field.device, getattr(self, "_range_sites", None), drain=False)
-        try:
+        # this call's launches report into a buffer of its own (a nested call finds none spare and makes one)
+        flags = _spare_flags.pop(field.device, None) or ops.RangeFlags(field.device)
+        with flags:
             out = f(self, graph, *args, **kwargs)
-            hit = watch.take()
-        finally:
-            watch.close()
+        hit = flags.take()
+        _spare_flags[field.device] = flags
         if hit:
             warnings.warn(f"{type(self).__name__}.forward(): the default 'f16x3' MLP arithmetic reached the end of the fp16 range (|x| >= "
                           f"65504) in {', '.join(hit[:8])}{' ...' if len(hit) > 8 else ''}: the forward was computed again in 'bf16x6' (fp32's "
@@ -339,10 +342,9 @@ class Rollout:
         graph.field = self.field
         # per-mesh constants (the encoders of edge_attr / angle_attr*): computed by the first eager step, read by every later one
         self.static = ops.StaticCache()
-        # fp16 range flags: this rollout answers for its own model's launches only — whatever an earlier launch of these MLPs
-        # left behind is dropped here, other models' flags are left alone
-        self.label, self._sites = label, getattr(model, "_range_sites", None)
-        self._watch = ops.RangeWatch(dev, self._sites) if ops.mlp_precision() == "f16x3" else None
+        # fp16 range flags of this rollout's own launches: every step (eager, captured, recomputed) runs in their scope
+        self.label = label
+        self.flags = ops.RangeFlags(dev)
         # The default "f16x3" arithmetic is run OPTIMISTICALLY: its kernels flag every value that reached the end of the fp16 range
         # (|x| >= 65504, clipped there), `result()` reads the flags, and a rollout that clipped anywhere is recomputed from the
         # window it started from in "bf16x6" (fp32's exponent range; the reference's `solve` runs in fp32, nn/model.py:303-321) and
@@ -358,7 +360,7 @@ class Rollout:
         return ops.steps_to_columns(self._out_steps)
 
     def _one(self):
-        with self.static:
+        with self.static, self.flags:
             pred = self.model.forward(self.graph, self.steps_done)
         ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
 
@@ -429,16 +431,18 @@ class Rollout:
             self.step_counter[:1].fill_(self._first_slot)
         self._hipgraph, self._epoch = None, -1
         self.steps_done = self._first_slot
-        self.run(n)
+        field, self.graph.field = self.graph.field, self.field        # (after close() the graph holds its own field again)
+        try:
+            self.run(n)
+        finally:
+            self.graph.field = field
 
     def validate(self) -> bool:
-        """Default "f16x3" arithmetic: read the range flags of this rollout's launches (one synchronisation) and, if a value was
-        clipped at the end of the fp16 range, recompute the steps in "bf16x6" (RuntimeWarning naming the MLPs).  Returns True when
-        that happened.  `result()` calls it; a benchmark calls it inside its timed region."""
+        """Default "f16x3" arithmetic: read the range flags of this rollout's launches (its own buffer, one synchronisation) and, if
+        a value was clipped at the end of the fp16 range, recompute the steps in "bf16x6" (RuntimeWarning naming the MLPs).  Returns
+        True when that happened.  `result()` calls it, before or after close(); a benchmark calls it inside its timed region."""
         if ops.mlp_precision() == "f16x3" and not self.exact_range:
-            if self._watch is None:          # (the arithmetic was switched to f16x3 after this rollout was built)
-                self._watch = ops.RangeWatch(self._out_steps.device, self._sites, drain=False)
-            hit = self._watch.take()
+            hit = self.flags.take()
             if hit:
                 self._recompute_exact(hit)
                 return True
@@ -457,8 +461,6 @@ class Rollout:
 
     def close(self) -> None:
         self.graph.field = self._orig_field
-        if self._watch is not None:
-            self._watch.close()
 
     def __enter__(self):
         return self

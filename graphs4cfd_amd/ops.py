@@ -5,7 +5,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import weakref
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -341,16 +340,17 @@ AGG_ON_LOAD = True
 AGG_ON_LOAD_MIN_ROWS = 50000
 
 
-# ---- fp16 range of the "f16x3" arithmetic made observable (g4c_mlp_t.range_flag): every launch in that arithmetic carries a slot
-# of a per-device int32 array; a kernel that converted a value of magnitude >= 65504 to fp16 (it was clipped there) writes 1 into
-# its slot.  Slots are named after the MLP that launched ("NsThreeScaleGNN.mp112.edge_mlp"); f16_range_report() reads the array
-# (one device synchronisation), check_f16_range() turns a non-empty report into a RuntimeWarning.  Rollout.validate (called by
-# Rollout.result, hence Model.solve) and DistributedRollout.validate (gather_outputs) read it and RECOMPUTE a clipped rollout in "bf16x6";
-# GNN.fit warns per epoch; a rollout clears its own model's slots on entry and looks at those only, so a clip is attributed to the
-# model that launched it (RangeWatch below: every reader hands hits to all live consumers before it clears).  A bare model.forward()
-# validates itself the same way (nn/model.py: GNN.__init_subclass__): one flag read per call, the forward again in "bf16x6" if it clipped.
+# ---- fp16 range of the "f16x3" arithmetic made observable: a kernel that converted a value of magnitude >= 65504 to fp16 (it was
+# clipped there) writes 1 into the slot of its MLP (g4c_mlp_t.range_slot) of the int32 flag buffer its launch names
+# (g4c_mlp_io_t.range_flag).  Slots are named after the MLP that launched ("NsThreeScaleGNN.mp112.edge_mlp").  The flags a launch
+# writes belong to whoever issued it: a consumer — a `Rollout`, a `DistributedRollout`, a validated bare model.forward() — owns a
+# RangeFlags buffer and issues its launches inside its scope, reads it where it hands out results (one synchronisation) and RECOMPUTES
+# in "bf16x6" if anything was clipped (Rollout.validate, hence Model.solve; DistributedRollout.validate; nn/model.py:
+# GNN.__init_subclass__).  Everything launched outside a consumer — training, forwards with validation off or inside a caller's own
+# capture, scripts — writes into its device's default buffer: f16_range_report() reads it, check_f16_range() turns a non-empty report
+# into a RuntimeWarning (GNN.fit: once per epoch).
 RANGE_SLOTS = 4096
-_range_bufs = {}            # device -> int32 [RANGE_SLOTS]
+_range_bufs = {}            # device -> int32 [RANGE_SLOTS]: the default buffer (created when the first f16x3 MLP is packed there)
 _range_sites: List[set] = [set() for _ in range(RANGE_SLOTS)]
 _range_slot_of = {}
 _range_wrapped = False
@@ -388,90 +388,67 @@ def _indexed(device) -> Optional[torch.device]:
     return device
 
 
-def range_slots_of(sites) -> List[int]:
-    """Flag slots of the named MLP sites that have launched in the f16x3 arithmetic so far (others have no slot yet)."""
-    return sorted({_range_slot_of[s] for s in sites if s in _range_slot_of})
+def _read_flags(buf: Tensor) -> List[Tuple[int, str]]:
+    """(slot, site name) of every set word of a flag buffer: its one device -> host copy (synchronises)."""
+    slots = torch.nonzero(buf.cpu()).flatten().tolist()
+    return [(slot, name) for slot in slots for name in sorted(_range_sites[slot]) or [f"slot {slot}"]]
 
 
-class RangeWatch:
-    """One consumer of the fp16 range flags: a `Rollout`, a `DistributedRollout`, a validated bare `forward()`.  The flags are one
-    int per MLP site and device, shared by everything that launches that MLP; whoever reads them (`f16_range_poll`: one
-    synchronisation) hands every hit to ALL live watches that name the site and only then clears the device array — so a second
-    rollout of the same model, a bare forward between two steps or a `check_f16_range()` call can no longer erase the evidence
-    another rollout still has to act on.  A hit that cannot be told apart (two live consumers of one site) reaches
-    both: each recomputes in the exact arithmetic, which is always right.  `drain=True` (a rollout's entry): the flags are read
-    once first, so that what earlier launches of these MLPs left behind goes to the watches that were live then, not to this one."""
-    _live = weakref.WeakSet()
+class RangeFlags:
+    """The fp16 range flags of one consumer: an int32 [RANGE_SLOTS] buffer on its device.  Every f16x3 launch on that device issued
+    inside `with flags:` writes into it (the innermost scope wins; a hipGraph captured there keeps the pointer), so `take()` answers
+    for exactly the launches this consumer issued, before or after it is done with them."""
+    active: Optional["RangeFlags"] = None
 
-    def __init__(self, device, sites=None, drain: bool = True):
-        self.device = _indexed(device)
-        self.sites = None if sites is None else frozenset(sites)
-        self.hits = set()
-        if drain:
-            f16_range_poll(self.device)
-        RangeWatch._live.add(self)
+    def __init__(self, device):
+        self.buf = torch.zeros(RANGE_SLOTS, dtype=torch.int32, device=device)
+        self.device = self.buf.device
+        self._prev = None
 
-    def wants(self, site: str) -> bool:
-        return self.sites is None or site in self.sites
+    def __enter__(self):
+        self._prev, RangeFlags.active = RangeFlags.active, self
+        return self
+
+    def __exit__(self, *exc):
+        RangeFlags.active = self._prev
+        return False
 
     def take(self) -> List[str]:
-        """Names of this watch's MLPs whose launches clipped a value since the last take (synchronises with the device)."""
-        f16_range_poll(self.device)
-        out = sorted(self.hits)
-        self.hits.clear()
-        return out
-
-    def close(self) -> None:
-        RangeWatch._live.discard(self)
+        """Names of the MLPs whose launches in this scope clipped a value since the last take (one synchronisation; the buffer is
+        cleared only if something was set)."""
+        hits = _read_flags(self.buf)
+        if hits:
+            self.buf.zero_()
+        return sorted({name for _, name in hits})
 
 
-_range_unclaimed = set()            # (device, site) of hits no live watch asked for: what f16_range_report / check_f16_range answer from
-
-
-def f16_range_poll(device: Optional[torch.device] = None) -> List[str]:
-    """Read the flag array(s) (one synchronisation per device), distribute the hits to the live watches, clear the array(s).
-    Returns every name that was set."""
-    device = _indexed(device)
-    names_out: List[str] = []
-    for dev, buf in list(_range_bufs.items()):
-        if device is not None and device != dev:
-            continue
-        flags = buf.cpu()
-        slots = torch.nonzero(flags).flatten().tolist()
-        if not slots:
-            continue
-        buf.zero_()
-        watches = [w for w in list(RangeWatch._live) if w.device is None or w.device == dev]
-        for slot in slots:
-            for name in sorted(_range_sites[slot]) or [f"slot {slot}"]:
-                names_out.append(name)
-                claimed = False
-                for w in watches:
-                    if w.wants(name):
-                        w.hits.add(name)
-                        claimed = True
-                if not claimed:
-                    _range_unclaimed.add((dev, name))
-    return names_out
+def _launch_flags(dev: torch.device) -> Tensor:
+    """The buffer an f16x3 launch on `dev` reports into: the innermost active consumer's if it is on `dev`, else the default one."""
+    c = RangeFlags.active
+    return c.buf if c is not None and c.device == dev else _range_buffer(dev)
 
 
 def f16_range_clear(device: Optional[torch.device] = None, sites=None) -> None:
-    """Forget the recorded clips that no live watch is waiting for: every site, or only `sites` (names as in f16_range_report).
-    Synchronises (the flags are read first: what a live `Rollout` still has to see reaches it)."""
+    """Forget the recorded clips of launches outside any consumer: every site, or only `sites` (names as in f16_range_report).
+    Synchronises."""
     f16_range_report(device, clear=True, sites=sites)
 
 
 def f16_range_report(device: Optional[torch.device] = None, clear: bool = True, sites=None) -> List[str]:
-    """Names of the MLPs whose launches clipped a value at the end of the fp16 range and that no rollout / validated forward has
-    dealt with, since the last report / clear (all devices, or one; `sites`: only these names are looked at and cleared).
-    Synchronises with the device(s)."""
-    f16_range_poll(device)
+    """Names of the MLPs whose launches outside any consumer (the default buffers: training, forwards with validation off, scripts)
+    clipped a value at the end of the fp16 range since the last report / clear (all devices, or one; `sites`: only these names are
+    looked at and cleared).  Synchronises with the device(s)."""
     device = _indexed(device)
     only = None if sites is None else set(sites)
-    mine = sorted(k for k in _range_unclaimed if (device is None or k[0] == device) and (only is None or k[1] in only))
-    if clear:
-        _range_unclaimed.difference_update(mine)
-    return [name for _, name in mine]
+    names: List[str] = []
+    for dev, buf in list(_range_bufs.items()):
+        if device is not None and device != dev:
+            continue
+        hits = [(slot, name) for slot, name in _read_flags(buf) if only is None or name in only]
+        if clear and hits:
+            buf[[slot for slot, _ in hits]] = 0
+        names += sorted(name for _, name in hits)
+    return names
 
 
 def check_f16_range(device: Optional[torch.device] = None, where: str = "", sites=None) -> List[str]:
@@ -673,12 +650,11 @@ class PackedMLP:
         if any(self.rs_blocks) and (self.rs_order or precision != "bf16" or any(narrow) or len(self.rs_blocks) != len(seg_widths)
                                     or any(r and w != 128 for r, w in zip(self.rs_blocks, seg_widths))):
             raise NotImplementedError("rs_blocks: rounded-bf16 mode, 128-wide blocks, no narrow blocks")
-        # (`site`: the name a clipped value is reported under — f16_range_report)
+        # (`site`: the name a clipped value is reported under — f16_range_report; the device's default flag buffer exists from here on)
         self.site = site or "an MLP created outside a model"
         if self.split == "f16x2":
-            self.desc.range_flag, self.desc.range_slot = _range_buffer(dev).data_ptr(), _range_slot(self.site)
-        else:
-            self.desc.range_flag, self.desc.range_slot = None, 0
+            _range_buffer(dev)
+            self.desc.range_slot = _range_slot(self.site)
         self._keep: List[Tensor] = []
         stream = _lib.stream_handle(dev)
         KC, NP = 32, 128                       # kernel constants: K chunk, computed layer width
@@ -810,7 +786,10 @@ def _set_heads(io, head_outs: Sequence[Tensor]) -> None:
 
 
 def _run(packed: PackedMLP, arr, n_src: int, n_rows: int, io, dev, flops: float, nbytes: float) -> None:
-    """The one launch (g4c_mlp_run), timed when a KernelTimer is active."""
+    """The one launch (g4c_mlp_run), timed when a KernelTimer is active.  An f16x3 launch reports clips into the flag buffer of
+    whoever issued it (_launch_flags)."""
+    if packed.split == "f16x2":
+        io.range_flag = _launch_flags(dev).data_ptr()
     kind = "mlp_split_kernel<4>" if packed.precision == "fp32" else "mlp_bx6_kernel"      # (the timer relabels it by what ran)
     _timed(kind, flops, nbytes, lambda: _lib.check(_lib.load().g4c_mlp_run(C.byref(packed.desc), arr, n_src, n_rows, C.byref(io),
                                                                            _lib.stream_handle(dev))))

@@ -556,14 +556,13 @@ class DistributedRollout:
         self.capture_error = None if self.capture else "capture not requested"
         self._hipgraph, self._epoch = None, -1
         self.static = ops.StaticCache()        # per-mesh constants (edge / angle encoders), as nn.model.Rollout
-        self._sites = getattr(model, "_range_sites", None)
-        self._watch = ops.RangeWatch(device, self._sites) if ops.mlp_precision() == "f16x3" and device.type == "cuda" else None
+        self.flags = ops.RangeFlags(device)     # fp16 range flags of this rollout's own launches, as nn.model.Rollout
         # optimistic "f16x3" (nn.model.Rollout): the input window the rollout started from, for the exact-range recomputation
         self._field0 = self.field.clone()
         self.exact_range = False
 
     def _one(self) -> None:
-        with self.static:
+        with self.static, self.flags:
             pred = self.fwd.forward()
         ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
 
@@ -586,9 +585,7 @@ class DistributedRollout:
         every rank recomputes its steps in "bf16x6" (the halo exchanges pair up again) and stays in that arithmetic."""
         if ops.mlp_precision() != "f16x3" or self.exact_range or self.device.type != "cuda":
             return False
-        if self._watch is None:
-            self._watch = ops.RangeWatch(self.device, self._sites, drain=False)
-        hit = self._watch.take()
+        hit = self.flags.take()
         clipped = bool(hit)
         import torch.distributed as dist
         if self.world > 1 and dist.is_available() and dist.is_initialized():

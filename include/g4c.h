@@ -148,12 +148,7 @@ typedef struct {
     float ln_eps;
     int32_t n_out;                   /* true output width of the last layer */
     int32_t w_format;                /* G4C_WFMT_*: the stream's layout and the arithmetic of every launch of this MLP */
-    int32_t *range_flag;             /* NULL, or a device array of int32: a launch in the f16x3 arithmetic writes 1 into
-                                        range_flag[range_slot] when an MLP input or a hidden activation it converted to fp16 reached
-                                        the end of fp16's range (|x| >= 65504: the value was CLIPPED there) — never written otherwise,
-                                        never cleared by the library.  The reference computes in fp32 (nn/model.py:303-321), so a set
-                                        slot means the result may differ from it: rerun with the bf16x3 stream (fp32 exponent range). */
-    int32_t range_slot;
+    int32_t range_slot;              /* >= 0: the word of g4c_mlp_io_t.range_flag a clip in a launch of this MLP is reported in */
 } g4c_mlp_t;
 
 /* Weight formats (g4c_mlp_t.w_format, g4c_mlp_pack_layer).  All take fp32 in and give fp32 out.
@@ -167,7 +162,7 @@ typedef struct {
  *   (Wl, xh) in a second one folded in with 2^-11 at the end of the layer; the dropped (Wl, xl) term and the operand representation are
  *   <= 2^-22 relative each: within the rounding error of an fp32 GEMM of the same shape (measured against fp64: scripts/mlp_accuracy.py,
  *   test_mlp_precisions_vs_fp64) at half the matrix-pipe work of BF16X3.  Range: an input or hidden activation with |x| > 65504 is
- *   clipped to +-65504 (1 + 2^-11) when it is converted (MODE.FP16_OVFL; no infinities or NaNs; reported through range_flag); small
+ *   clipped to +-65504 (1 + 2^-11) when it is converted (MODE.FP16_OVFL; no infinities or NaNs; reported through io->range_flag); small
  *   values lose nothing.  Planes 0 / 1 of the same layout, plane 2 zero.
  * G4C_WFMT_BF16 (rounded bf16, BASELINE config 3 "bf16 edge-MLP MFMA", opt-in): the BF16X3 stream, of which only the LEADING plane is
  *   used: weights and the activations entering each Linear are rounded to bf16 (one product per multiply-add), accumulation / bias /
@@ -279,6 +274,12 @@ typedef struct {
     int32_t v_ld, v_act;
     float *v_out;
     int32_t v_out_ld;
+    /* NULL (not tracked), or a device array of int32: a launch in the f16x3 arithmetic writes 1 into range_flag[mlp->range_slot]
+     * (and range_flag[upd->range_slot]) when an MLP input or a hidden activation it converted to fp16 reached the end of fp16's range
+     * (|x| >= 65504: the value was CLIPPED there) — never written otherwise, never cleared by the library.  The reference computes in
+     * fp32 (nn/model.py:303-321), so a set word means the result may differ from it: rerun with the bf16x3 stream (fp32 exponent
+     * range).  The array belongs to the caller of the launch, like every other output here: each consumer can pass its own. */
+    int32_t *range_flag;
 } g4c_mlp_io_t;
 
 /* One fused-MLP launch over `n_rows` rows of the input `srcs`, writing what `io` names. */

@@ -1709,29 +1709,29 @@ def test_f16_range_clip_recomputes_in_bf16x6_and_matches_the_oracle():
         ops.set_mlp_precision(old)
 
 
-def test_bare_forward_is_range_validated_and_rollouts_keep_their_evidence():
+def test_bare_forward_is_range_validated_and_rollouts_keep_their_own_evidence():
     """VERDICT r05 item 6 / ADVICE r05: (a) a bare `model.forward(graph)` in the default arithmetic (the reference's other public
     entry, nn/mus_gnn.py:173-218) returns — with a RuntimeWarning — the "bf16x6" forward bit for bit when a value left the fp16 range,
-    and an ordinary forward costs exactly one read of the flags, no warning, nothing recomputed; (b) a second Rollout on the same
-    model, a bare forward or a check_f16_range() call between the steps of a live rollout no longer erase the clip that rollout
-    still has to act on."""
+    and an ordinary forward costs exactly one read of a flag buffer (ops._read_flags), no warning, nothing recomputed; (b) a second
+    Rollout on the same model, a bare forward or a check_f16_range() call between the steps of a live rollout do not erase the clip
+    that rollout still has to act on (it reads its own flag buffer)."""
     import warnings
     from graphs4cfd_amd.nn.model import Rollout
     torch.manual_seed(8)
     model = gfd.nn.NsOneScaleGNN(arch=S.mus_arch("NsOneScaleGNN", 128), device=DEV)
     old = ops.set_mlp_precision("f16x3")
-    polls = []
-    real_poll = ops.f16_range_poll
+    reads = []
+    real_read = ops._read_flags
     try:
         g = S.mus_graph(2000, levels=1, seed=9).to(DEV)
         big = g.clone(); big.field = big.field * 1e5
         ops.f16_range_report()
-        ops.f16_range_poll = lambda dev=None: (polls.append(1), real_poll(dev))[1]
+        ops._read_flags = lambda buf: (reads.append(1), real_read(buf))[1]
         with torch.no_grad(), warnings.catch_warnings():
             warnings.simplefilter("error", RuntimeWarning)
             y = model.forward(g).clone()
-        assert len(polls) == 1, "an ordinary bare forward reads the range flags once"
-        ops.f16_range_poll = real_poll
+        assert len(reads) == 1, "an ordinary bare forward reads the range flags once"
+        ops._read_flags = real_read
         with torch.no_grad(), pytest.warns(RuntimeWarning, match="computed again in 'bf16x6'"):
             y_big = model.forward(big).clone()
         ops.set_mlp_precision("bf16x6")
@@ -1770,7 +1770,7 @@ def test_bare_forward_is_range_validated_and_rollouts_keep_their_evidence():
             ref_a = model.solve(big.clone(), 4, capture=False)
         assert torch.equal(out_a[:, :6], ref_a[:, :6])
     finally:
-        ops.f16_range_poll = real_poll
+        ops._read_flags = real_read
         ops.set_mlp_precision(old)
 
 
@@ -2430,9 +2430,9 @@ def test_static_encoder_cache_is_bit_identical_and_invalidates(family):
 
 
 def test_f16_range_report_is_scoped_to_the_model_that_clipped():
-    """A clip in model A's launches must not be reported by model B's solve() (the flags are per device, not per model: whoever reads
-    them hands each hit to the consumers that named its site — ops.RangeWatch — and keeps the rest for f16_range_report), and it
-    must still be reported when A is asked."""
+    """A clip in model A's launches must not be reported by model B's solve() (a rollout reads the flags of its own launches only:
+    ops.RangeFlags; launches outside any consumer go to the device's default flags, which f16_range_report reads), and it must still
+    be reported when A is asked."""
     import warnings
     old = ops.set_mlp_precision("f16x3")
     try:
@@ -2463,12 +2463,78 @@ def test_f16_range_report_is_scoped_to_the_model_that_clipped():
         assert any(h.startswith("NsTwoScaleGNN.mp11") for h in hit) and any("outside a model" in h for h in hit), hit
         with pytest.warns(RuntimeWarning, match="NsTwoScaleGNN.mp11"):
             gfd.check_f16_range(torch.device("cuda"), sites=a._range_sites)        # (un-indexed device = the current one)
-        # A's own solve(): the stale flags of its earlier forward are dropped on entry, its own clip is reported, nothing else
+        # A's own solve(): the flags of its earlier forward are not its own, its own clip is reported, nothing else
         with pytest.warns(RuntimeWarning) as rec:
             a.solve(g.clone(), 2)
         msgs = [str(r.message) for r in rec if "fp16 range" in str(r.message)]
         assert msgs and all("outside a model" not in m and "NsOneScaleGNN" not in m for m in msgs), msgs
         assert ops.f16_range_report(DEV) == ["an MLP created outside a model"]
+    finally:
+        ops.set_mlp_precision(old)
+
+
+def test_f16_range_flags_belong_to_the_consumer_that_launched():
+    """The flags a launch writes belong to whoever issued it (ops.RangeFlags).  (a) `with Rollout(...) as ro: ro.run(n)`, then
+    `ro.result()` outside the block: the clip of its steps is still its own — warned and recomputed, the result is the bf16x6 solve
+    bit for bit, and the caller's graph keeps its field.  (b) Live, unclosed rollouts of the same model (a Rollout and a world-1
+    DistributedRollout) neither hide the clip of a bare forward with validation off from f16_range_report() nor are blamed for it.
+    (c) The clip of a forward recorded for autograd is not blamed on the next validated bare forward (no warning, no second pass),
+    and check_f16_range() still reports it."""
+    import warnings
+    from graphs4cfd_amd import partition as P
+    from graphs4cfd_amd.nn.model import Rollout
+    g = S.mus_graph(3000, levels=2, seed=18)
+    torch.manual_seed(19)
+    model = gfd.nn.NsTwoScaleGNN(arch=S.mus_arch("NsTwoScaleGNN", 128), device=DEV)
+    old = ops.set_mlp_precision("f16x3")
+    try:
+        ops.f16_range_clear()                               # (whatever earlier tests left behind)
+        gd = g.clone().to(DEV)
+        gd.batch = torch.zeros(gd.num_nodes, dtype=torch.long, device=DEV)
+        big = gd.clone(); big.field = big.field * 1e5
+        f_big = big.field
+        # (a)
+        with Rollout(model, big, 5, capture=True, reorder=False) as ro:
+            ro.run(5)
+        with pytest.warns(RuntimeWarning, match="recomputed in 'bf16x6'"):
+            got = ro.result().clone()
+        assert ro.exact_range and big.field is f_big
+        assert ops.f16_range_report() == []                 # (the rollout's clip never reached the default flags)
+        ops.set_mlp_precision("bf16x6")
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                 # (solve() notes inputs beyond 4096 in either arithmetic)
+            ref = model.solve(big.clone(), 5, capture=True)
+        ops.set_mlp_precision("f16x3")
+        assert torch.equal(got, ref), (got - ref).abs().max().item()
+        # (b)
+        ro = Rollout(model, gd, 4, capture=True, reorder=False)
+        ro.run(2)
+        dr = P.DistributedRollout(model, g, 4, 0, 1, DEV)
+        dr.run(2)
+        was = gfd.set_forward_validation(False)
+        try:
+            with torch.no_grad(), warnings.catch_warnings():
+                warnings.simplefilter("error", RuntimeWarning)
+                model.forward(big)
+        finally:
+            gfd.set_forward_validation(was)
+        hit = ops.f16_range_report()
+        assert any(h.startswith("NsTwoScaleGNN.") for h in hit), hit
+        with warnings.catch_warnings():
+            warnings.simplefilter("error", RuntimeWarning)
+            assert not ro.validate() and not dr.validate()
+        ro.close()
+        # (c)
+        with torch.enable_grad():
+            y = model.forward(big)
+        assert y.requires_grad
+        del y
+        with torch.no_grad(), warnings.catch_warnings():
+            warnings.simplefilter("error", RuntimeWarning)
+            model.forward(gd)
+        with pytest.warns(RuntimeWarning, match="NsTwoScaleGNN"):
+            assert ops.check_f16_range()
+        assert ops.f16_range_report() == []
     finally:
         ops.set_mlp_precision(old)
 

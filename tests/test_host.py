@@ -40,6 +40,19 @@ def test_mlp_run_validates_its_descriptor_before_any_hip_call():
     io = _lib.g4c_mlp_io_t(row_count=64, act=7)
     assert lib.g4c_mlp_run(C.byref(mlp), src, 1, 64, C.byref(io), None) == _lib.EINVAL
     assert "bad activation 7" in lib.g4c_last_error().decode()
+    # the fp16 range flags a launch writes are named by the launch (io.range_flag), the word by the MLP (range_slot): both checked
+    flags = (C.c_int32 * 8)()
+    f16 = _lib.g4c_mlp_t(n_layers=1, w_format=_lib.WFMT_F16X2, range_slot=-1)
+    io = _lib.g4c_mlp_io_t(row_count=64, range_flag=C.addressof(flags))
+    assert lib.g4c_mlp_run(C.byref(f16), src, 1, 64, C.byref(io), None) == _lib.EINVAL
+    assert "negative range_slot" in lib.g4c_last_error().decode()
+    upd = _lib.g4c_mlp_t(n_layers=1, w_format=_lib.WFMT_F16X2, range_slot=-1)
+    f16.range_slot = 0
+    io = _lib.g4c_mlp_io_t(row_count=64, range_flag=C.addressof(flags), upd=C.pointer(upd))
+    assert lib.g4c_mlp_run(C.byref(f16), src, 1, 64, C.byref(io), None) == _lib.EINVAL
+    assert "negative range_slot" in lib.g4c_last_error().decode()
+    assert list(flags) == [0] * 8
+    assert lib.g4c_version() == 3
 
 
 def test_plan_csr_matches_stable_argsort():
@@ -321,34 +334,76 @@ def test_bench_plain_run_options_and_output_dump(monkeypatch, tmp_path):
     assert np.array_equal(np.load(tmp_path / "s1" / "last_step_prediction.npy"), ro.res[rows.astype(np.int64), 9:12].numpy())
 
 
-def test_range_watch_hands_every_hit_to_all_live_consumers_before_clearing():
-    """ops.RangeWatch / f16_range_poll (host logic; the flag array stands on the CPU here): whoever reads the shared per-site flags
-    distributes each hit to every live consumer that named the site, keeps what nobody asked for for f16_range_report, and only
-    then clears — a second consumer of the same model, or a report in between, cannot erase the first one's evidence."""
+def test_range_flags_belong_to_the_consumer_that_issued_the_launch(monkeypatch):
+    """ops.RangeFlags / ops._run (host logic: the flag buffers stand on the CPU, and a stand-in for g4c_mlp_run writes 1 into
+    io.range_flag[range_slot] — and [upd.range_slot] — as a clipping f16x3 kernel does): a launch issued inside a consumer's scope
+    reports into that consumer's buffer (the innermost scope on the launch's device wins), one outside any scope into the device's
+    default buffer.  take() answers once, also after the consumer has left its scope; f16_range_report / check_f16_range read the
+    default buffer only, and a consumer never sees what was launched outside it."""
+    import ctypes as C
+    import types
+    import warnings
     from graphs4cfd_amd import ops
     dev = torch.device("cpu")
-    saved = (dict(ops._range_bufs), set(ops._range_unclaimed))
-    try:
-        ops._range_bufs.clear(); ops._range_unclaimed.clear()
-        buf = ops._range_buffer(dev)
-        sa, sb, so = ops._range_slot("T.model_a.mlp"), ops._range_slot("T.model_b.mlp"), ops._range_slot("T.orphan.mlp")
-        wa1 = ops.RangeWatch(dev, ["T.model_a.mlp"])
-        buf[sa] = 1                                   # a launch of model A clipped
-        wa2 = ops.RangeWatch(dev, ["T.model_a.mlp"])  # a second rollout of A is built: its entry drain must not eat wa1's hit
-        assert wa2.hits == set() and wa1.hits == {"T.model_a.mlp"} and int(buf.sum()) == 0
-        buf[sb] = 1; buf[so] = 1
-        assert ops.f16_range_report(dev, sites=["T.model_b.mlp"]) == ["T.model_b.mlp"]          # nobody watches B: reported, cleared
-        assert ops.f16_range_report(dev, clear=False) == ["T.orphan.mlp"]
-        assert wa1.take() == ["T.model_a.mlp"] and wa1.take() == [] and wa2.take() == []
-        buf[sa] = 1                                   # indistinguishable: both live consumers of the site get it
-        assert wa2.take() == ["T.model_a.mlp"] and wa1.take() == ["T.model_a.mlp"]
-        wa1.close(); wa2.close()
-        buf[sa] = 1
-        assert sorted(ops.f16_range_report(dev)) == ["T.model_a.mlp", "T.orphan.mlp"]          # no live watch: unclaimed again
-        assert ops.f16_range_report(dev) == []
-    finally:
-        ops._range_bufs.clear(); ops._range_bufs.update(saved[0])
-        ops._range_unclaimed.clear(); ops._range_unclaimed.update(saved[1])
+
+    class ClippingLib:                                        # every launch clips
+        def g4c_mlp_run(self, mlp, srcs, n_src, n_rows, io, stream):
+            mlp, io = mlp._obj, io._obj
+            if io.range_flag is not None:
+                for slot in (mlp.range_slot,) + ((io.upd.contents.range_slot,) if io.upd else ()):
+                    C.c_int32.from_address(io.range_flag + 4 * slot).value = 1
+            return _lib.OK
+    monkeypatch.setattr(_lib, "load", lambda: ClippingLib())
+    monkeypatch.setattr(_lib, "stream_handle", lambda d: None)
+    monkeypatch.setattr(ops, "_range_bufs", {})
+    monkeypatch.setattr(ops.RangeFlags, "active", None)
+    reads = []
+    read_flags = ops._read_flags
+    monkeypatch.setattr(ops, "_read_flags", lambda buf: (reads.append(1), read_flags(buf))[1])
+    sa, su, sb, so = "T.model_a.mlp", "T.model_a.upd", "T.model_b.mlp", "T.outside.mlp"
+
+    def packed(site, split="f16x2"):
+        return types.SimpleNamespace(split=split, precision="bf16x6", desc=_lib.g4c_mlp_t(range_slot=ops._range_slot(site)))
+
+    def launch(p, upd=None):
+        io = _lib.g4c_mlp_io_t(upd=C.pointer(upd.desc) if upd is not None else None)
+        ops._run(p, None, 1, 64, io, dev, 0.0, 0.0)
+        return io
+
+    def set_sites(buf):
+        return sorted(n for s in torch.nonzero(buf).flatten().tolist() for n in ops._range_sites[s])
+    pa, pu, pb, po = packed(sa), packed(su), packed(sb), packed(so)
+    default = ops._range_buffer(dev)
+    a, b = ops.RangeFlags(dev), ops.RangeFlags(dev)
+    elsewhere = ops.RangeFlags(torch.device("meta"))          # a consumer on another device
+    with a:
+        launch(pa, upd=pu)                                    # the fused MP layer: both slots, one buffer
+        with b:
+            launch(pb)                                        # nested scopes: the innermost consumer's
+        assert ops.RangeFlags.active is a
+        with elsewhere:
+            launch(po)                                        # the innermost consumer is not on the launch's device: the default
+    assert ops.RangeFlags.active is None
+    assert launch(packed(so, split="bf16x3")).range_flag is None          # only f16x3 launches carry a buffer
+    assert set_sites(a.buf) == [sa, su] and set_sites(b.buf) == [sb] and set_sites(default) == [so]
+    # the report and the check read the default buffer only; a consumer reads its own, once, after it has left its scope
+    assert ops.f16_range_report(dev, clear=False) == [so]
+    del reads[:]
+    assert a.take() == [sa, su] and len(reads) == 1 and int(a.buf.sum()) == 0
+    assert a.take() == [] and b.take() == [sb] and b.take() == []
+    launch(pa)                                                # model A's MLP launched outside A: never A's
+    assert a.take() == [] and set_sites(default) == [sa, so]
+    with a:
+        launch(pa)
+    assert ops.f16_range_report(dev, clear=False) == [sa, so]          # (clear=False: read, kept)
+    assert ops.f16_range_report(dev, sites=[sa, sb]) == [sa]           # sites=: only these are looked at and cleared
+    assert ops.f16_range_report(dev, clear=False) == [so]
+    with pytest.warns(RuntimeWarning, match="T.outside.mlp"):
+        assert ops.check_f16_range(dev, "test") == [so]
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        assert ops.check_f16_range(dev) == [] and ops.f16_range_report(dev) == []
+    assert a.take() == [sa]
 
 
 def test_csr_plan_knows_a_uniform_in_degree():
