@@ -13,6 +13,7 @@ blocks fuses the `F.selu` the model applies right after the block, nn/mus_gnn.py
 from __future__ import annotations
 
 from collections import OrderedDict
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -62,6 +63,26 @@ def _finish(x: Tensor, activation, code: Optional[int]) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------- MLP
+@dataclass(frozen=True)
+class PackSpec:
+    """Everything but the parameter values that decides the bytes of one packed weight image (ops.PackedMLP) of an MLP: the key of
+    MLP._image's cache, and all that MLP._build reads.  Made by MLP._spec."""
+    layers: Tuple[int, int]                   # Linear layers [i, j) of the MLP
+    rows: Tuple[int, int]                     # output rows [c, c1) of the first of them
+    cols: Tuple[int, int]                     # input columns [a, b) of the first of them
+    bias: bool                                # with the first layer's bias (the layers behind it always have theirs)
+    layer_norm: bool                          # with the MLP's LayerNorm
+    seg_widths: Tuple[int, ...]               # the input blocks (ops.PackedMLP) ...
+    seg_negate: Tuple[bool, ...]
+    narrow: Tuple[bool, ...]
+    rs_blocks: Tuple[bool, ...]
+    precision: str                            # ops.effective_precision of those blocks
+    stream: int                               # 0: the precision's plain stream; the row-split kernels': _lib.WFMT_BF16_RS / _RS2 / _RS2N
+    rs_rows: bool                             # output rows of the heads — without heads: of the one bias-free layer — in the row-split order
+    heads: Optional[Tuple["MLP", int, Tuple[int, ...]]]       # (consumer, k_cols, widths): see MLP.run_with_heads
+    grad: bool                                # a cut first layer stays a view of the parameters (a chain stage recorded for autograd)
+
+
 class MLP(nn.Module):
     r"""Multi-layer perceptron with SELU activations (reference: nn/blocks.py:117-144).
 
@@ -99,25 +120,73 @@ class MLP(nn.Module):
     def _signature(self):
         return (ops.weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in self.parameters())
 
+    def _ln_args(self) -> Optional[Tuple[Tensor, Tensor, float]]:
+        ln = getattr(self.MLP, "layer_norm", None)
+        return None if ln is None else (ln.weight, ln.bias, ln.eps)
+
+    def _spec(self, seg_widths: Sequence[int], seg_negate: Sequence[bool], narrow: Optional[Sequence[bool]] = None,
+              rs_blocks: Optional[Sequence[bool]] = None, *, layers: Optional[Tuple[int, int]] = None, rows: Optional[Tuple[int, int]] = None,
+              cols: Optional[Tuple[int, int]] = None, bias: bool = True, layer_norm: bool = True, stream: int = 0, rs_rows: bool = False,
+              heads: Optional[Tuple["MLP", int, Sequence[int]]] = None, grad: bool = False) -> PackSpec:
+        """The description of one packed image of this MLP, defaults = the whole MLP.  Needs no device and not the library.  `narrow` and
+        `rs_blocks` hold inside the arithmetic that has them only (and a row-split stream orders every block itself); `layer_norm` asks for
+        this MLP's LayerNorm where it has one and the image ends with its last layer; `grad` is kept only where the first layer is cut."""
+        lin = self._linears()
+        i, j = layers if layers is not None else (0, len(lin))
+        c, c1 = rows if rows is not None else (0, lin[i].out_features)
+        a, b = cols if cols is not None else (0, lin[i].in_features)
+        if sum(seg_widths) != b - a:
+            raise ValueError(f"MLP expects {b - a} input columns, got blocks {list(seg_widths)}")
+        if rs_rows and heads is None and (bias or j - i != 1):
+            raise ValueError("rows in the row-split order: heads, or one layer without its bias (nothing behind it reads that order)")
+        prec, none = ops.effective_precision(seg_widths), (False,) * len(seg_widths)
+        cut = (c, c1, a, b) != (0, lin[i].out_features, 0, lin[i].in_features)
+        return PackSpec(layers=(i, j), rows=(c, c1), cols=(a, b), bias=bool(bias),
+                        layer_norm=bool(layer_norm and j == len(lin) and self._ln_args() is not None),
+                        seg_widths=tuple(int(w) for w in seg_widths), seg_negate=tuple(bool(x) for x in seg_negate),
+                        narrow=tuple(bool(x) for x in narrow) if (narrow is not None and prec != "fp32") else none,
+                        rs_blocks=tuple(bool(x) for x in rs_blocks) if (rs_blocks is not None and prec == "bf16" and not stream) else none,
+                        precision=prec, stream=int(stream), rs_rows=bool(rs_rows),
+                        heads=None if heads is None else (heads[0], int(heads[1]), tuple(int(w) for w in heads[2])), grad=bool(grad and cut))
+
+    def _image(self, spec: PackSpec) -> ops.PackedMLP:
+        """The packed image `spec` describes: built on first use and again when a parameter it was packed from has changed (of this MLP,
+        and of the consumer whose first layer the heads are cut from)."""
+        sig = self._signature() if spec.heads is None else (self._signature(), spec.heads[0]._signature())
+        hit = self._packed.get(spec)
+        if hit is None or hit[0] != sig:
+            hit = self._packed[spec] = (sig, self._build(spec))
+        return hit[1]
+
+    def _build(self, s: PackSpec) -> ops.PackedMLP:
+        lin = self._linears()[s.layers[0]:s.layers[1]]
+        (c, c1), (a, b) = s.rows, s.cols
+        w0, b0 = lin[0].weight, lin[0].bias
+        if (c, c1, a, b) != (0, lin[0].out_features, 0, lin[0].in_features):
+            # (a cut of the first layer: a view of the parameters where a chain stage is recorded for autograd, else of their values —
+            # such an image is launched with pre-multiplied blocks beside it, an inference-only form)
+            w0 = (w0 if s.grad else w0.detach())[c:c1, a:b]
+            b0 = None if b0 is None else (b0 if s.grad else b0.detach())[c:c1]
+        heads = []
+        if s.heads is not None:
+            consumer, off, widths = s.heads
+            w1 = consumer._linears()[0].weight.detach()
+            if s.rs_rows:
+                w1 = w1[ops._rs_k_order(w1.device)]
+            for w in widths:
+                heads.append(w1[:, off:off + w])
+                off += w
+        elif s.rs_rows:
+            w0 = w0.detach()[ops._rs_k_order(w0.device)]
+        return ops.PackedMLP([w0] + [l.weight for l in lin[1:]], [b0 if s.bias else None] + [l.bias for l in lin[1:]],
+                             self._ln_args() if s.layer_norm else None, s.seg_widths, s.seg_negate, heads=heads, precision=s.precision,
+                             narrow=s.narrow, site=self._site, rs_order=s.stream == _lib.WFMT_BF16_RS,
+                             rs_blocks=s.rs_blocks if any(s.rs_blocks) else None,
+                             rs2=s.stream if s.stream in (_lib.WFMT_BF16_RS2, _lib.WFMT_BF16_RS2N) else 0)
+
     def packed(self, seg_widths: Sequence[int], seg_negate: Sequence[bool], narrow: Optional[Sequence[bool]] = None,
                rs_blocks: Optional[Sequence[bool]] = None) -> ops.PackedMLP:
-        prec = ops.effective_precision(seg_widths)
-        narrow = tuple(bool(x) for x in narrow) if (narrow is not None and prec != "fp32") else (False,) * len(seg_widths)
-        rs_blocks = tuple(bool(x) for x in rs_blocks) if (rs_blocks is not None and prec == "bf16") else (False,) * len(seg_widths)
-        key = (tuple(seg_widths), tuple(bool(x) for x in seg_negate), prec, narrow, rs_blocks)
-        sig = self._signature()
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            if sum(seg_widths) != self.input_size:
-                raise ValueError(f"MLP expects {self.input_size} input columns, got blocks {list(seg_widths)}")
-            lin = self._linears()
-            ln = getattr(self.MLP, "layer_norm", None)
-            pk = ops.PackedMLP([l.weight for l in lin], [l.bias for l in lin],
-                               None if ln is None else (ln.weight, ln.bias, ln.eps), key[0], key[1], precision=prec, narrow=narrow,
-                               site=self._site, rs_blocks=rs_blocks if any(rs_blocks) else None)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        return hit[1]
+        return self._image(self._spec(seg_widths, seg_negate, narrow, rs_blocks))
 
     # -- MLPs outside the one-launch envelope ---------------------------------------------
     def fits_one_launch(self) -> bool:
@@ -127,17 +196,9 @@ class MLP(nn.Module):
         lin = self._linears()
         return len(lin) <= _lib.MAX_LAYERS and all(l.out_features <= 128 for l in lin)
 
-    def _stage(self, key, weights, biases, ln, sources: Sequence[Source]) -> ops.PackedMLP:
-        prec = ops.effective_precision([s.width for s in sources])
-        narrow = tuple(_narrow_flags(sources)) if prec != "fp32" else (False,) * len(sources)
-        key = ("stage",) + key + (tuple(s.width for s in sources), tuple(s.negate for s in sources), prec, narrow)
-        sig = self._signature()
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            pk = ops.PackedMLP(weights, biases, ln, key[-4], key[-3], precision=prec, narrow=narrow, site=self._site)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        return hit[1]
+    def _stage(self, sources: Sequence[Source], **part) -> ops.PackedMLP:
+        """A launch of `_run_stages`: the `part` of this MLP (`_spec`: layers, rows, cols, bias, layer_norm) that reads `sources`."""
+        return self._image(self._spec(*_blocks(sources)[:3], grad=ops.grad_mode(), **part))
 
     def _run_stages(self, sources: Sequence[Source], n_rows: int, act_code: int, **kw) -> Tensor:
         """Any widths / depth as a chain of fused launches: consecutive layers of <= 128 outputs share a launch (at most
@@ -153,7 +214,7 @@ class MLP(nn.Module):
         if grad and any(kw.get(k) is not None for k in ("out", "out_idx32", "agg", "head_outs")):
             raise NotImplementedError("out= / output index / aggregation / heads are inference-only forms; call under torch.no_grad()")
         lin = self._linears()
-        ln = getattr(self.MLP, "layer_norm", None)
+        ln = self._ln_args()
         dev = sources[0].tensor.device
         cur, i, n = list(_split_wide(sources)), 0, len(lin)
 
@@ -164,9 +225,9 @@ class MLP(nn.Module):
 
         def one_layer(li: int, c: int, c1: int, blocks: Sequence[Source], act: int, ln_args, **kw2) -> Tensor:
             """act(LayerNorm(W[c:c1] cat(blocks) + b[c:c1])) — in groups of blocks when there are more than a launch takes"""
-            w, b = lin[li].weight[c:c1], (lin[li].bias[c:c1] if lin[li].bias is not None else None)
             if len(blocks) <= _lib.MAX_SRC:
-                return ops.mlp_forward(self._stage((li, c), [w], [b], ln_args, blocks), blocks, n_rows, act, **kw2)
+                pk = self._stage(blocks, layers=(li, li + 1), rows=(c, c1), layer_norm=ln_args is not None)
+                return ops.mlp_forward(pk, blocks, n_rows, act, **kw2)
             gsz = _lib.MAX_SRC if grad else _lib.MAX_SRC - 1      # (inference: the previous group's partial sums take a source slot)
             groups = [blocks[g:g + gsz] for g in range(0, len(blocks), gsz)]
             partial, k0 = None, 0
@@ -174,7 +235,7 @@ class MLP(nn.Module):
                 k1 = k0 + sum(s_.width for s_ in grp)
                 last_g = gi == len(groups) - 1
                 fused_tail = last_g and not grad
-                pk = self._stage((li, c, k0, grad), [w[:, k0:k1]], [b if gi == 0 else None], ln_args if fused_tail else None, grp)
+                pk = self._stage(grp, layers=(li, li + 1), rows=(c, c1), cols=(k0, k1), bias=gi == 0, layer_norm=fused_tail and ln_args is not None)
                 srcs = list(grp) + ([Source(partial, additive=True)] if (partial is not None and not grad) else [])
                 y = ops.mlp_forward(pk, srcs, n_rows, act if fused_tail else _lib.ACT_NONE, **(kw2 if fused_tail else {}))
                 partial = y if (partial is None or not grad) else partial + y
@@ -198,7 +259,7 @@ class MLP(nn.Module):
                     parts = [one_layer(i, c, c1, cur, act_i, None) for c, c1 in spans]
                     if last:
                         y = torch.cat(parts, 1)
-                        return torch_tail(y, (ln.weight, ln.bias, ln.eps), act_code) if wide_ln else y
+                        return torch_tail(y, ln, act_code) if wide_ln else y
                     cur = [Source(t) for t in parts]
                     i += 1
                     continue
@@ -206,7 +267,7 @@ class MLP(nn.Module):
                 for c, c1 in spans:
                     one_layer(i, c, c1, cur, act_i, None, out=wide[:, c:c1])
                 if wide_ln:         # (a LayerNorm over more than 128 columns: its own launch, in place)
-                    ops.layer_norm(wide, ln.weight, ln.bias, ln.eps, act_code, out=wide)
+                    ops.layer_norm(wide, *ln, act_code, out=wide)
                 if last:
                     return wide
                 cur = [Source(wide, col0=c, width=c1 - c) for c, c1 in spans]
@@ -214,8 +275,7 @@ class MLP(nn.Module):
                 continue
             if len(cur) > _lib.MAX_SRC:          # (too many input blocks for one launch: this layer alone, group by group)
                 last = i == n - 1
-                ln_args = (ln.weight, ln.bias, ln.eps) if (last and ln is not None) else None
-                y = one_layer(i, 0, lin[i].out_features, cur, act_code if last else _lib.ACT_SELU, ln_args, **(kw if last else {}))
+                y = one_layer(i, 0, lin[i].out_features, cur, act_code if last else _lib.ACT_SELU, ln if last else None, **(kw if last else {}))
                 if last:
                     return y
                 cur, i = [Source(y)], i + 1
@@ -224,8 +284,7 @@ class MLP(nn.Module):
             while j < n and j - i < _lib.MAX_LAYERS and lin[j].out_features <= 128:
                 j += 1
             last = j == n
-            pk = self._stage((i, j), [l.weight for l in lin[i:j]], [l.bias for l in lin[i:j]],
-                             (ln.weight, ln.bias, ln.eps) if (last and ln is not None) else None, cur)
+            pk = self._stage(cur, layers=(i, j))
             if last:
                 return ops.mlp_forward(pk, cur, n_rows, act_code, **kw)
             cur = [Source(ops.mlp_forward(pk, cur, n_rows, _lib.ACT_SELU))]
@@ -243,7 +302,7 @@ class MLP(nn.Module):
                                  resid_col0=resid_col0)
             return _finish(y, activation, code)
         sources = _split_wide(sources)
-        pk = self.packed([s.width for s in sources], [s.negate for s in sources], _narrow_flags(sources), _rs_blocks(sources))
+        pk = self.packed(*_blocks(sources))
         y = ops.mlp_forward(pk, sources, n_rows, _lib.ACT_NONE if code is None else code, out, out_idx32, resid, resid_col0)
         return _finish(y, activation, code)
 
@@ -252,39 +311,20 @@ class MLP(nn.Module):
             return self._run_stages(sources, n_rows, act_code, **kw)
         fmt = self._rs2_format(sources, n_rows, act_code, kw)
         if fmt:
-            y = ops.mlp_forward(self._rs2_packed(fmt, None, 0, ()), sources, n_rows, act_code, **kw)
+            y = ops.mlp_forward(self._image(self._spec(*_blocks(sources), stream=fmt)), sources, n_rows, act_code, **kw)
             return ops.RsOrderedRows.tag(y) if y.dtype == torch.bfloat16 else y
         sources = _split_wide(sources)
-        pk = self.packed([s.width for s in sources], [s.negate for s in sources], _narrow_flags(sources), _rs_blocks(sources))
+        pk = self.packed(*_blocks(sources))
         return ops.mlp_forward(pk, sources, n_rows, act_code, **kw)
 
-    def _heads_packed(self, seg_widths: Sequence[int], consumer: "MLP", k_cols: int, widths: Sequence[int]) -> Optional[ops.PackedMLP]:
-        """This MLP (plain 128-wide input blocks `seg_widths`) packed with heads = the column blocks `widths` behind the first `k_cols`
-        columns of `consumer`'s first layer (see run_with_heads; same cache entry)."""
-        if self.output_size != 128 or any(int(w) != 128 for w in widths) or not 1 <= len(widths) <= _lib.MAX_HEADS or not self.fits_one_launch():
+    def _heads_spec(self, blocks, consumer: "MLP", k_cols: int, widths: Sequence[int], rs_rows: bool = False,
+                    stream: int = 0) -> Optional[PackSpec]:
+        """This MLP on the input `blocks` (`_blocks`) with heads = the column blocks `widths` behind the first `k_cols` columns of `consumer`'s
+        first layer (see run_with_heads); None when no launch carries such heads."""
+        if (self.output_size != 128 or any(int(w) != 128 for w in widths) or not 1 <= len(widths) <= _lib.MAX_HEADS
+                or not self.fits_one_launch() or consumer._linears()[0].out_features != 128):
             return None
-        prec = ops.effective_precision(seg_widths)
-        narrow = (False,) * len(seg_widths)
-        key = ("heads", id(consumer), k_cols, tuple(widths), tuple(seg_widths), (False,) * len(seg_widths), prec, narrow, False,
-               (False,) * len(seg_widths))
-        sig = (self._signature(), consumer._signature())
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            lin = self._linears()
-            ln = getattr(self.MLP, "layer_norm", None)
-            w1 = consumer._linears()[0].weight.detach()
-            if int(w1.size(0)) != 128:
-                return None
-            heads, off = [], k_cols
-            for w in widths:
-                heads.append(w1[:, off:off + w].contiguous())
-                off += w
-            pk = ops.PackedMLP([l.weight for l in lin], [l.bias for l in lin],
-                               None if ln is None else (ln.weight, ln.bias, ln.eps), key[4], key[5], heads=heads, precision=prec,
-                               narrow=narrow, site=self._site)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        return hit[1]
+        return self._spec(*blocks, stream=stream, rs_rows=rs_rows, heads=(consumer, k_cols, widths))
 
     def run_with_heads(self, sources: Sequence[Source], n_rows: int, act_code: int, consumer: "MLP", k_cols: int,
                        widths: Sequence[int], out: Optional[Tensor] = None,
@@ -297,50 +337,27 @@ class MLP(nn.Module):
         destinations (row-sliced views of wider buffers are fine).  `rs_rows` (rounded-bf16 mode, bf16 products: the consumer's message
         launch will run on the row-split kernel, MLP.rs1_ready): the products come back as ops.RsOrderedRows, their columns in that
         kernel's order — the heads' weight rows are permuted, nothing else changes."""
-        if self.output_size != 128 or any(int(w) != 128 for w in widths) or not 1 <= len(widths) <= _lib.MAX_HEADS:
-            return None
-        if not self.fits_one_launch():
-            return None
         if ops.grad_mode():          # recorded for autograd: the plain launches are the differentiable ones
             return None
         if not any(t is not None for t in (head_outs or ())) and PRODUCTS_BF16 and HOIST_BF16:
             fmt = self._rs2_format(sources, n_rows, act_code, {} if out is None else {"out": out}, rs_rows)
-            pk2 = self._rs2_packed(fmt, consumer, k_cols, widths) if fmt else None
-            if pk2 is not None:          # the row-split update kernel: e' (+ the consumer's products) from rows in its own order
+            # (the heads' rows stay in feature order: the kernel's stores order them)
+            spec2 = self._heads_spec(_blocks(sources), consumer, k_cols, widths, stream=fmt) if (fmt and len(widths) == 2) else None
+            if spec2 is not None:        # the row-split update kernel: e' (+ the consumer's products) from rows in its own order
                 dev = sources[0].tensor.device
                 y = out if out is not None else torch.empty((n_rows, 128), dtype=torch.float32, device=dev)
                 outs = [torch.empty((n_rows, 128), dtype=torch.bfloat16, device=dev) for _ in range(2)]
-                ops.mlp_forward(pk2, sources, n_rows, act_code, out=y, head_outs=outs)
+                ops.mlp_forward(self._image(spec2), sources, n_rows, act_code, out=y, head_outs=outs)
                 return (ops.RsOrderedRows.tag(y) if y.dtype == torch.bfloat16 else y), [ops.RsOrderedRows.tag(t) for t in outs]
         sources = _split_wide(sources)
         prec = ops.effective_precision([s.width for s in sources])
         if prec == "bf16" and not HOIST_BF16:
             return None
-        narrow = tuple(_narrow_flags(sources)) if prec != "fp32" else (False,) * len(sources)
         rs_rows = bool(rs_rows and prec == "bf16" and PRODUCTS_BF16 and not any(t is not None for t in (head_outs or ())))
-        rs_blocks = _rs_blocks(sources) if prec == "bf16" else (False,) * len(sources)
-        key = ("heads", id(consumer), k_cols, tuple(widths), tuple(s.width for s in sources), tuple(s.negate for s in sources), prec, narrow, rs_rows,
-               rs_blocks)
-        sig = (self._signature(), consumer._signature())
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            lin = self._linears()
-            ln = getattr(self.MLP, "layer_norm", None)
-            w1 = consumer._linears()[0].weight.detach()
-            if rs_rows and int(w1.size(0)) == 128:
-                w1 = w1[ops._rs_k_order(w1.device)]
-            heads, off = [], k_cols
-            for w in widths:
-                heads.append(w1[:, off:off + w].contiguous())
-                off += w
-            if int(w1.size(0)) != 128:
-                return None
-            pk = ops.PackedMLP([l.weight for l in lin], [l.bias for l in lin],
-                               None if ln is None else (ln.weight, ln.bias, ln.eps), key[4], key[5], heads=heads, precision=prec,
-                               narrow=narrow, site=self._site, rs_blocks=rs_blocks if any(rs_blocks) else None)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        pk = hit[1]
+        spec = self._heads_spec(_blocks(sources), consumer, k_cols, widths, rs_rows)
+        if spec is None:
+            return None
+        pk = self._image(spec)
         dev = sources[0].tensor.device
         y = out if out is not None else torch.empty((n_rows, 128), dtype=torch.float32, device=dev)
         given = [t for t in (head_outs or ()) if t is not None]
@@ -353,32 +370,19 @@ class MLP(nn.Module):
         return y, ([ops.RsOrderedRows.tag(t) for t in outs] if rs_rows else outs)
 
     # -- first-layer hoisting ------------------------------------------------------------------
-    def _packed_cols(self, tag: str, a: int, b: int, seg_widths, seg_negate, first_only: bool, rs_order: bool = False,
-                     rs_rows: bool = False, rs_in: bool = False) -> ops.PackedMLP:
+    def _packed_cols(self, *args, **kw) -> ops.PackedMLP:
+        """The image `_cols_spec` describes (same arguments).  A name in front of them, which callers passed while every call site spelled
+        its own cache key, is accepted and shapes nothing: no part of it reaches the key."""
+        return self._image(self._cols_spec(*(args[1:] if args and isinstance(args[0], str) else args), **kw))
+
+    def _cols_spec(self, a: int, b: int, seg_widths, seg_negate, first_only: bool, rs_order: bool = False,
+                   rs_rows: bool = False, rs_in: bool = False) -> PackSpec:
         """Packed variant using only columns [a, b) of the first Linear layer (`first_only`: that layer alone, no bias).
         `rs_order`: the stream of the row-split kernel (ops.PackedMLP); `rs_rows` (with `first_only`): the product's output columns in that
-        kernel's order (ops.RsOrderedRows) — the weight's rows permuted."""
-        prec = ops.effective_precision(seg_widths)
-        key = (tag, a, b, tuple(seg_widths), tuple(bool(x) for x in seg_negate), prec)
-        sig = self._signature()
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            lin = self._linears()
-            w1 = lin[0].weight.detach()[:, a:b].contiguous()
-            if rs_rows:
-                w1 = w1[ops._rs_k_order(w1.device)].contiguous()
-            if first_only:
-                # (`rs_in`: the one input block arrives as ops.RsOrderedRows — its weight columns are packed in that order)
-                pk = ops.PackedMLP([w1], [None], None, key[3], key[4], precision=prec, site=self._site,
-                                   rs_blocks=[True] if (rs_in and prec == "bf16") else None)
-            else:
-                ln = getattr(self.MLP, "layer_norm", None)
-                pk = ops.PackedMLP([w1] + [l.weight for l in lin[1:]], [l.bias for l in lin],
-                                   None if ln is None else (ln.weight, ln.bias, ln.eps), key[3], key[4], precision=prec, site=self._site,
-                                   rs_order=rs_order)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        return hit[1]
+        kernel's order (ops.RsOrderedRows) — the weight's rows permuted; `rs_in`: the one input block arrives as ops.RsOrderedRows — its
+        weight columns are packed in that order."""
+        return self._spec(seg_widths, seg_negate, None, [rs_in] * len(seg_widths), layers=(0, 1) if first_only else None,
+                          cols=(a, b), bias=not first_only, stream=_lib.WFMT_BF16_RS if rs_order else 0, rs_rows=rs_rows)
 
     def run_hoisted(self, k_sources: Sequence[Source], gathered: Sequence[Tuple[Tensor, Tensor]], n_rows: int,
                     act_code: int = _lib.ACT_NONE, products: Optional[Sequence[Tensor]] = None, **kw) -> Tensor:
@@ -408,7 +412,7 @@ class MLP(nn.Module):
                 part = products[j]
             else:
                 chunks = [(c, min(128, w_t - c)) for c in range(0, w_t, 128)] if (w_t > 128 and not ops.grad_mode()) else [(0, w_t)]
-                pk1 = self._packed_cols("hoist1", off, off + w_t, [w for _, w in chunks], [False] * len(chunks), True)
+                pk1 = self._packed_cols(off, off + w_t, [w for _, w in chunks], [False] * len(chunks), True)
                 part16 = (torch.empty((int(t.size(0)), 128), dtype=torch.bfloat16, device=t.device)
                           if (ops.mlp_precision() == "bf16" and PRODUCTS_BF16 and pk1.n_out == 128 and pk1.precision == "bf16") else None)
                 part = ops.mlp_forward(pk1, [Source(t, col0=c, width=w) for c, w in chunks], int(t.size(0)), out=part16)
@@ -416,7 +420,7 @@ class MLP(nn.Module):
             off += w_t
         if off != self.input_size:
             raise ValueError(f"MLP expects {self.input_size} input columns, got {off}")
-        pk = self._packed_cols("hoist", 0, sum(kw_widths), kw_widths, [s.negate for s in k_sources], False)
+        pk = self._packed_cols(0, sum(kw_widths), kw_widths, [s.negate for s in k_sources], False)
         return ops.mlp_forward(pk, list(k_sources) + adds, n_rows, act_code, **kw)
 
     # -- rounded-bf16 mode: the update MLP of such a layer on the row-split update kernel -------------------------------------
@@ -443,25 +447,6 @@ class MLP(nn.Module):
                                 or out.stride(0) % (8 if out.dtype == torch.bfloat16 else 4)):
             return 0
         return 4 if isinstance(sources[1].tensor, ops.RsOrderedRows) else 5
-
-    def _rs2_packed(self, fmt: int, consumer: Optional["MLP"], k_cols: int, widths) -> Optional[ops.PackedMLP]:
-        key = ("rs2", fmt, None if consumer is None else id(consumer), k_cols, tuple(widths))
-        sig = (self._signature(), None if consumer is None else consumer._signature())
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != sig:
-            lin = self._linears()
-            ln = self.MLP.layer_norm
-            heads = []
-            if consumer is not None:
-                w1 = consumer._linears()[0].weight.detach()
-                if int(w1.size(0)) != 128 or tuple(int(w) for w in widths) != (128, 128):
-                    return None
-                heads = [w1[:, k_cols + 128 * j: k_cols + 128 * (j + 1)].contiguous() for j in range(2)]      # (rows in feature order: the kernel's stores order them)
-            pk = ops.PackedMLP([l.weight for l in lin], [l.bias for l in lin], (ln.weight, ln.bias, ln.eps), [128, 128], [False, False],
-                               heads=heads, precision="bf16", site=self._site, rs2=fmt)
-            self._packed[key] = (sig, pk)
-            hit = self._packed[key]
-        return hit[1]
 
     # -- rounded-bf16 mode: uniform-degree message launches on the row-split kernel ------------------------------------------
     def rs1_ready(self, n_rows: int, csr) -> bool:
@@ -508,13 +493,12 @@ class MLP(nn.Module):
                 part = products[j]
             else:        # this block's product W1[:, 128 (j + 1) : 128 (j + 2)] t, bf16 rows in the kernel's column order
                 tagged = isinstance(t, ops.RsOrderedRows)
-                pk1 = self._packed_cols("hoist1_rs" + ("/rs_in" if tagged else ""), 128 * (j + 1), 128 * (j + 2), [128], [False], True,
-                                        rs_rows=True, rs_in=tagged)
+                pk1 = self._packed_cols(128 * (j + 1), 128 * (j + 2), [128], [False], True, rs_rows=True, rs_in=tagged)
                 part = torch.empty((int(t.size(0)), 128), dtype=torch.bfloat16, device=t.device)
                 ops.mlp_forward(pk1, [Source(t)], int(t.size(0)), out=part)
                 part = ops.RsOrderedRows.tag(part)
             adds.append(Source(part, index=idx, additive=True))
-        pk = self._packed_cols("hoist_rs", 0, 128, [128], [False], False, rs_order=True)
+        pk = self._packed_cols(0, 128, [128], [False], False, rs_order=True)
         y = ops.mlp_forward(pk, [x] + adds, n_rows, _lib.ACT_NONE, **kw)
         return ops.RsOrderedRows.tag(y) if (y is not None and y.dtype == torch.bfloat16) else y
 
@@ -526,6 +510,11 @@ class MLP(nn.Module):
 
 
 # ------------------------------------------------------------------------------------- helpers
+def _blocks(sources: Sequence[Source]):
+    """(seg_widths, seg_negate, narrow, rs_blocks) of MLP._spec for these input blocks."""
+    return [s.width for s in sources], [s.negate for s in sources], _narrow_flags(sources), _rs_blocks(sources)
+
+
 def _rs_blocks(sources: Sequence[Source]) -> Tuple[bool, ...]:
     """Per weighted input block: its rows are ops.RsOrderedRows (128 wide, whole) — the pack then takes that block's weight columns in the
     same order (ops.PackedMLP rs_blocks) instead of the rows being copied back to feature order."""
@@ -681,13 +670,14 @@ def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, 
     dev = v.device
     n_t = int(v.size(0))
     if products is None:          # the node-side products of this layer's first layer: W1[:, H:2H] v, W1[:, 2H:3H] v (MLP.run_hoisted)
-        products = [ops.mlp_forward(msg_mlp._packed_cols("hoist1", H * (1 + j), H * (2 + j), [H], [False], True), [Source(v)], n_t) for j in range(2)]
-    pk_msg = msg_mlp._packed_cols("hoist", 0, H, [H], [e_src.negate], False)
+        products = [ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True), [Source(v)], n_t) for j in range(2)]
+    pk_msg = msg_mlp._packed_cols(0, H, [H], [e_src.negate], False)
     srcs = [e_src, Source(products[0], index=ep.row, additive=True), Source(products[1], index=ep.col, additive=True)]
     heads = None
     if next_msg is not None and next_msg.input_size == 3 * H and next_msg._linears()[0].out_features == H:
-        pk_upd = upd_mlp._heads_packed([H, H], next_msg, next_msg.input_size - 2 * H, [H, H])
-        if pk_upd is not None:
+        spec = upd_mlp._heads_spec(([H, H], [False, False]), next_msg, next_msg.input_size - 2 * H, [H, H])
+        if spec is not None:
+            pk_upd = upd_mlp._image(spec)
             heads = [torch.empty((n_t, H), dtype=torch.float32, device=dev) for _ in range(2)]
     if heads is None:
         pk_upd = upd_mlp.packed([H, H], [False, False])
@@ -766,8 +756,8 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
         e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges,
                                     products=products, agg=(csr, agg, mean))
         agg_src = Source(agg)
-    v16 = (compact_v and COMPACT_LATENTS and PRODUCTS_BF16 and HOIST_BF16 and ops.mlp_precision() == "bf16" and upd_mlp.output_size == 128 and upd_mlp.fits_one_launch()
-           and n_targets is None and v_out is None and not ops.grad_mode() and ops.effective_precision([128, int(v.size(1))]) == "bf16")
+    v16 = (compact_v and compact_latents_now(upd_mlp.output_size) and upd_mlp.fits_one_launch() and n_targets is None and v_out is None
+           and ops.effective_precision([128, int(v.size(1))]) == "bf16")
     if next_msg is not None:
         nxt = None
         nx_rows, nx_csr = (ep.n_edges, csr) if next_graph is None else next_graph

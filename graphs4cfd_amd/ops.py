@@ -658,6 +658,30 @@ class PackedMLP:
         self._keep: List[Tensor] = []
         stream = _lib.stream_handle(dev)
         KC, NP = 32, 128                       # kernel constants: K chunk, computed layer width
+
+        def k_order(l: Optional[int], k_in: int) -> Optional[Tensor]:
+            """Column index by which layer `l` (None: a head) is packed, or None for its columns as they are: `_rs_k_order` inside every
+            128-wide block of a row-split stream, and inside the first layer's `rs_blocks` of any other."""
+            if self.rs_order or self.rs2:
+                widths = [128] * (k_in // 128)
+                marked = [True] * len(widths)
+            elif l == 0 and any(self.rs_blocks):
+                widths, marked = seg_widths, self.rs_blocks
+            else:
+                return None
+            cols, c0 = torch.arange(k_in, device=dev), 0
+            for w, r in zip(widths, marked):
+                if r:
+                    cols[c0:c0 + 128] = c0 + _rs_k_order(dev)
+                c0 += w
+            return cols
+
+        def pack(W: Tensor, l: Optional[int], n_out: int, k_in: int, segs, negs, wptr: int, k_pad: int) -> None:
+            Wc, cols = W.detach().to(torch.float32).contiguous(), k_order(l, k_in)
+            if cols is not None:
+                Wc = Wc[:, cols].contiguous()
+            seg_arr, neg_arr = (C.c_int32 * len(segs))(*segs), (C.c_int32 * len(segs))(*negs)
+            _lib.check(lib.g4c_mlp_pack_layer(_lib.ptr(Wc), n_out, k_in, seg_arr, neg_arr, len(segs), self.desc.w_format, wptr, k_pad, NP, stream))
         if bf16 and any(s > NP for s in seg_widths):
             raise NotImplementedError("bf16 MLP with an input block wider than 128")
         wide = [j for j in range(len(seg_widths)) if not narrow[j]]            # the blocks that go through the packed stream
@@ -705,37 +729,15 @@ class PackedMLP:
                 segs, negs = [k_in], [0]
             wptr = stream_buf.data_ptr() + esz * off
             if W is not None:            # (None: every input block of the first layer is narrow, nothing to stream)
-                Wc = W.detach().to(torch.float32).contiguous()
-                if self.rs_order:
-                    Wc = Wc[:, _rs_k_order(dev)].contiguous()
-                if self.rs2:
-                    o = _rs_k_order(dev)
-                    Wc = Wc[:, torch.cat([c0 + o for c0 in range(0, k_in, 128)])].contiguous()
-                if l == 0 and any(self.rs_blocks):
-                    cols = torch.arange(k_in, device=dev)
-                    for j, r in enumerate(self.rs_blocks):
-                        if r:
-                            c0 = sum(seg_widths[:j])
-                            cols[c0:c0 + 128] = c0 + _rs_k_order(dev)
-                    Wc = Wc[:, cols].contiguous()
-                seg_arr = (C.c_int32 * len(segs))(*segs)
-                neg_arr = (C.c_int32 * len(segs))(*negs)
-                _lib.check(lib.g4c_mlp_pack_layer(_lib.ptr(Wc), n_out, k_in, seg_arr, neg_arr, len(segs), self.desc.w_format, wptr,
-                                                  k_pads[l], NP, stream))
+                pack(W, l, n_out, k_in, segs, negs, wptr, k_pads[l])
             if b is not None:
                 bias_buf[l * NP: l * NP + n_out].copy_(b.detach())
             self.desc.k_pad[l], self.desc.n_pad[l] = k_pads[l], NP
             self.desc.w[l], self.desc.b[l] = wptr, bias_buf.data_ptr() + 4 * l * NP
             off += k_pads[l] * NP
         self.n_heads = len(heads)
-        one = (C.c_int32 * 1)(NP)
-        zero = (C.c_int32 * 1)(0)
         for W in heads:
-            Wc = W.detach().to(torch.float32).contiguous()
-            if self.rs2:
-                Wc = Wc[:, _rs_k_order(dev)].contiguous()
-            _lib.check(lib.g4c_mlp_pack_layer(_lib.ptr(Wc), NP, NP, one, zero, 1, self.desc.w_format, stream_buf.data_ptr() + esz * off,
-                                              NP, NP, stream))
+            pack(W, None, NP, NP, [NP], [0], stream_buf.data_ptr() + esz * off, NP)
             off += NP * NP
         self.n_out = int(weights[-1].size(0))
         self.desc.n_out = self.n_out

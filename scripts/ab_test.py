@@ -41,7 +41,7 @@ out_e, out_v = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
 def pack_for(lib):   # weights are packed by the library that consumes them (the stream layout may differ)
     _lib._lib = lib
     blk.edge_mlp._packed.clear(); blk.node_mlp._packed.clear()
-    return blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False), blk.node_mlp.packed([H, H], [False, False])
+    return blk.edge_mlp._packed_cols(0, H, [H], [False], False), blk.node_mlp.packed([H, H], [False, False])
 
 
 packs = [pack_for(lib) for lib in libs]

@@ -42,7 +42,7 @@ for rows in (600000, 100000, 6001, 999, 65, 64, 33, 32, 7, 1):
     col = (torch.arange(rows, device=dev) // 6).clamp(max=n - 1).to(torch.int32)
     W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
     pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=row, additive=True), ops.Source(pc, index=col, additive=True)]
     cmp(f"edge hoisted rows={rows}", *both(lambda: ops.mlp_forward(pk, src, rows)), 2e-5)
     idx = torch.randint(0, rows, (rows,), device=dev, dtype=torch.int32)
@@ -60,7 +60,7 @@ for rows, ragged in ((600000, False), (19972, True), (116, True)):
     e, v = torch.randn(E, H, device=dev), torch.randn(n, H, device=dev)
     W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
     pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
     for mean in (True, False):
         def run():
@@ -78,7 +78,7 @@ if a.time:
     ei = torch.stack([torch.randint(0, n, (rows,)), colh]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
     pr, pc = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
     out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
     cases = {"edge(hoisted)": lambda: ops.mlp_forward(pk, src, rows, 0, out=out),

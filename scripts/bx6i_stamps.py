@@ -16,7 +16,7 @@ blk = B.GNBlock((3 * H, (H, H, H), True), (2 * H, (H, H, H), True)).to(dev)
 e, pr, pc = torch.randn(rows, H, device=dev), torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
 row = torch.randint(0, n, (rows,), device=dev, dtype=torch.int32)
 col = (torch.arange(rows, device=dev) // 6).clamp(max=n - 1).to(torch.int32)
-pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
 src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=row, additive=True), ops.Source(pc, index=col, additive=True)]
 lib.g4c_mlp_bx6i_enable(2)
 for _ in range(3): ops.mlp_forward(pk, src, rows)

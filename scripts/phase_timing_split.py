@@ -15,7 +15,7 @@ dev = torch.device("cuda", 0); H = 128
 torch.set_grad_enabled(False)
 torch.manual_seed(0)
 blk = B.GNBlock((3 * H, (H, H, H), True), (2 * H, (H, H, H), True)).to(dev)
-pk_e = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+pk_e = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
 pk_v = blk.node_mlp.packed([H, H], [False, False])
 names = ["prologue: indices, bias -> LDS, barrier", "first gather issued + acc-init gathers", "ring fill issue, first park, barrier",
          "layer 0 MFMA", "hidden store 0", "layer 1 MFMA", "hidden store 1", "layer 2 MFMA", "hidden store 2 (last)"]

@@ -30,7 +30,7 @@ for layers in (2, 3):
         ei = torch.stack([torch.randint(0, n, (E,)), torch.arange(n).repeat_interleave(K)]).to(dev)
         ep, csr = plan.edge_csr(ei, n)
         assert csr.uniform_deg == K
-        pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
         lin = blk.edge_mlp._linears(); ln = blk.edge_mlp.MLP.layer_norm
         pk_rs = ops.PackedMLP([lin[0].weight.detach()[:, :H].contiguous()] + [l.weight for l in lin[1:]], [l.bias for l in lin],
                               (ln.weight, ln.bias, ln.eps), [H], [False], precision="bf16", rs_order=True)

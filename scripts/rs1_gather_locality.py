@@ -23,8 +23,8 @@ E = K * n
 blk = B.GNBlock((3 * H, (H,) * layers, True), (2 * H, (H,) * layers, True)).to(dev)
 e32, pr, pc = torch.randn(E, H, device=dev), torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
 e16 = torch.nn.functional.selu(e32).to(torch.bfloat16); pr16, pc16 = pr.to(torch.bfloat16), pc.to(torch.bfloat16)
-pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
-pk_rs = blk.edge_mlp._packed_cols("hoist_rs", 0, H, [H], [False], False, rs_order=True)
+pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
+pk_rs = blk.edge_mlp._packed_cols(0, H, [H], [False], False, rs_order=True)
 tgt = torch.arange(n).repeat_interleave(K)
 for name, snd in (("random senders", torch.randint(0, n, (E,))), ("senders within +-64 rows", (tgt + torch.randint(-64, 65, (E,))).clamp(0, n - 1)),
                   ("senders within +-4096 rows", (tgt + torch.randint(-4096, 4097, (E,))).clamp(0, n - 1)), ("senders = receivers", tgt.clone())):

@@ -35,7 +35,7 @@ for scale in (1.0, 1e-4, 1e3, 3e4):
             lib.g4c_mlp_bx6i_enable(mode)
             if hasattr(lib, "g4c_mlp_ws_enable"): lib.g4c_mlp_ws_enable(0)
             blk.edge_mlp._packed.clear()
-            pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
             src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=row, additive=True), ops.Source(pc, index=col, additive=True)]
             res.append(ops.mlp_forward(pk, src, rows).clone())
         same = torch.equal(res[0], res[1])

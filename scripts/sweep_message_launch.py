@@ -19,7 +19,7 @@ for rows in sizes:
     ei = torch.stack([torch.randint(0, n, (rows,)), colh]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
     out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
-    pks = [b.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False) for b in blks]
+    pks = [b.edge_mlp._packed_cols(0, H, [H], [False], False) for b in blks]
     src = [ops.Source(e), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
     res = {}
     for name, ws, lim in (("tile ring2", 0, 0), ("tile deep", 0, 1 << 30), ("ws", 2, 0)):

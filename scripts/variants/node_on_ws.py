@@ -29,7 +29,7 @@ for rows in (100000, 25000, 12500):
     agg, v = torch.randn(rows, H, device=dev), torch.randn(rows, H, device=dev)
     W0 = node._linears()[0].weight
     pn = (v @ W0[:, H:].T).contiguous()
-    pk = node._packed_cols("hoist_node", 0, H, [H], [False], False)
+    pk = node._packed_cols(0, H, [H], [False], False)
     out = torch.empty(rows, H, device=dev)
     ref = node.run_coded([ops.Source(agg), ops.Source(v)], rows, _lib.ACT_SELU)
     lib.g4c_mlp_ws_enable(2)

@@ -18,7 +18,7 @@ for rows6 in (1, 7, 100, 2999, 20011, 100000):
     col = torch.arange(n).repeat_interleave(6)
     ei = torch.stack([torch.randint(0, n, (E,)), col]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     lin = blk.edge_mlp._linears(); ln = blk.edge_mlp.MLP.layer_norm
     pk_rs = ops.PackedMLP([lin[0].weight.detach()[:, :H].contiguous(), lin[1].weight, lin[2].weight], [l.bias for l in lin],
                           (ln.weight, ln.bias, ln.eps), [H], [False], precision="f16x3", rs_order=True)
@@ -42,7 +42,7 @@ if a.time:
     ei = torch.stack([torch.randint(0, n, (rows,)), torch.arange(n).repeat_interleave(6)]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
     lin = blk.edge_mlp._linears(); ln = blk.edge_mlp.MLP.layer_norm
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     pk_rs = ops.PackedMLP([lin[0].weight.detach()[:, :H].contiguous(), lin[1].weight, lin[2].weight], [l.bias for l in lin],
                           (ln.weight, ln.bias, ln.eps), [H], [False], precision="f16x3", rs_order=True)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]

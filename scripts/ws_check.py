@@ -50,7 +50,7 @@ def check_variant(prec, layers):
     tol, mtol = (2e-5, None) if prec != "bf16" else (3e-2, 2e-5)
     tag = f"[{prec}, {layers} layers] "
     W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     for rows in (600000, 100000, 6001, 999, 65, 64, 33, 32, 7, 1):
         n = max(rows // 6, 2)
         e, v = torch.randn(rows, H, device=dev), torch.randn(n, H, device=dev)
@@ -121,7 +121,7 @@ if a.stress:
         e, v = torch.randn(rows, H, device=dev), torch.randn(n, H, device=dev)
         W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
         pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-        pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
         idx = torch.randint(0, rows, (rows,), device=dev, dtype=torch.int32)
         col = (torch.arange(rows, device=dev) // 6).to(torch.int32)
         ei = torch.stack([torch.randint(0, n, (rows,), device=dev), col.long()])
@@ -152,7 +152,7 @@ if a.time:
     ei = torch.stack([torch.randint(0, n, (rows,)), colh]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
     pr, pc = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
     out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
     cases = {"edge(hoisted)": lambda: ops.mlp_forward(pk, src, rows, 0, out=out),
@@ -183,7 +183,7 @@ if a.time:
     ei = torch.stack([rowh, colh]).to(dev)
     ep, csr = plan.edge_csr(ei, n)
     pr, pc = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
-    pk2 = blk2.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk2 = blk2.edge_mlp._packed_cols(0, H, [H], [False], False)
     src2 = [ops.Source(e16), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
     agg2 = torch.empty(n, H, device=dev)
     src2f = [ops.Source(e16.float())] + src2[1:]

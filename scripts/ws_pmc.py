@@ -16,7 +16,7 @@ e, pr, pc = torch.randn(rows, H, device=dev), torch.randn(n, H, device=dev), tor
 colh = torch.arange(n).repeat_interleave(6)
 ei = torch.stack([torch.randint(0, n, (rows,)), colh]).to(dev)
 ep, csr = plan.edge_csr(ei, n)
-pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
 src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
 out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
 if "--fused" in sys.argv:        # one launch per MP layer (g4c_mlp_io_t.upd) at config 2's level-1 size: 10k nodes, 60k edges, heads

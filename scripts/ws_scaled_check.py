@@ -35,7 +35,7 @@ for scale in (1.0, 1e-4, 1e3, 3e4):
             _lib._lib = lib
             lib.g4c_mlp_bx6i_enable(0); lib.g4c_mlp_ws_enable(2)
             blk.edge_mlp._packed.clear()
-            pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
             src = [ops.Source(e, pre_act=pre), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
             out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
             ops.f16_range_report(dev)          # (clear)

@@ -26,7 +26,7 @@ colh = torch.arange(n).repeat_interleave(deg)
 rowh = (colh + torch.randint(-64, 65, (rows,))).clamp(0, n - 1) if bf16 else torch.randint(0, n, (rows,))
 ei = torch.stack([rowh, colh]).to(dev)
 ep, csr = plan.edge_csr(ei, n)
-pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
 src = [ops.Source(e) if f32in else ops.Source(e.to(torch.bfloat16)) if bf16 else ops.Source(e, pre_act=_lib.ACT_SELU),
        ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
 out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)

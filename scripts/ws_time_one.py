@@ -21,7 +21,7 @@ colh = torch.arange(n).repeat_interleave(6)
 ei = torch.stack([torch.randint(0, n, (rows,)), colh]).to(dev)
 ep, csr = plan.edge_csr(ei, n)
 pr, pc = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
-pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
 src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
 out, agg = torch.empty(rows, H, device=dev), torch.empty(n, H, device=dev)
 fn = lambda: ops.mlp_forward(pk, src, rows, 0, out=out, agg=(csr, agg, True))

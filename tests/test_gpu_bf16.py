@@ -101,7 +101,7 @@ def test_tile_kernel_vs_reference(rows, layers, ln):
         y = node.run_coded([ops.Source(e), ops.Source(e), ops.Source(x3)], rows, _lib.ACT_TANH)
         assert last_kernel() == TILE
         check(y, R.mlp(wn, [R.Block(e), R.Block(e), R.Block(x3, narrow=True)], rows, act="tanh"), "rows32", "narrow block")
-        pk = m._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = m._packed_cols(0, H, [H], [False], False)
         W1 = w["MLP.linear_1.weight"]
         for bf16_adds in (False, True):
             pr, pc = (R.products(W1[:, a:a + H], v, bf16_out=bf16_adds) for a in (H, 2 * H))
@@ -131,7 +131,7 @@ def test_tile_kernel_heads_and_products_vs_reference(rows):
         for j, h in enumerate(heads):
             check(h, R.products(W1[:, H * (j + 1):H * (j + 2)], y_ref), "prod16", f"head {j}")
         for tag, kw in (("hoist1", {}), ("hoist1_rs", dict(rs_rows=True))):
-            pk1 = nxt._packed_cols(tag, H, 2 * H, [H], [False], True, **kw)
+            pk1 = nxt._packed_cols(H, 2 * H, [H], [False], True, **kw)
             out = torch.empty(rows, H, dtype=torch.bfloat16, device=DEV)
             ops.mlp_forward(pk1, [ops.Source(v)], rows, out=out)
             assert last_kernel() == TILE
@@ -159,7 +159,7 @@ def test_ws_kernel_vs_reference(deg, layers):
         ref = R.mlp(w, [R.Block(e, pre_act="selu")], E, additive=[R.Additive(pr, ep.row), R.Additive(pc, ep.col)], first_cols=(0, H))
         agg_ref = R.segment_mean(ref, csr.off)
         with bf16_mode(ws=2):
-            pk = m._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = m._packed_cols(0, H, [H], [False], False)
             for fmt, kw in (("fp32", {}), ("bf16", dict(rows_dtype=torch.bfloat16)),
                             ("bf16_selu", dict(rows_dtype=torch.bfloat16, rows_act=SELU))):
                 a = torch.full((n, H), float("nan"), device=DEV)
@@ -320,7 +320,7 @@ def test_mlp_run_refuses_a_uniform_row_count_it_cannot_split():
     e, p = torch.randn(E, H, generator=g).to(DEV), torch.randn(n, H, generator=g).to(DEV)
     src = [ops.Source(e, pre_act=SELU), ops.Source(p, index=ep.row, additive=True), ops.Source(p, index=ep.col, additive=True)]
     with bf16_mode(ws=2) as lib:
-        pk = m._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = m._packed_cols(0, H, [H], [False], False)
         arr = ops._src_array(src)
         out, agg = torch.empty(E, H, device=DEV), torch.full((n, H), float("nan"), device=DEV)
         t_rows, t_seg, nt = csr.tiles()

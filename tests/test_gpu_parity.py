@@ -147,7 +147,7 @@ def test_mlp_kernel_row_range_launches_agree(rows, monkeypatch):
     # first-layer products of the node-side blocks, as _mp_step's hoisting computes them
     W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
     pr, pc = v @ W1[:, H:2 * H].T, v @ W1[:, 2 * H:].T
-    pk_e = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk_e = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src_e = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=row, additive=True), ops.Source(pc, index=col, additive=True)]
     pk_v = blk.node_mlp.packed([H, H], [False, False])
     idx = torch.randint(0, n, (n,), device=DEV, dtype=torch.int32)
@@ -1396,7 +1396,7 @@ def test_bx6i_dual_tile_kernel_equals_tile_kernel(rows, kernel, prec, monkeypatc
     v, e = torch.randn(n, H, device=DEV), torch.randn(E, H, device=DEV)
     W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
     pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-    pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+    pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
     src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
 
     ids = torch.randperm(E, device=DEV)[: max(E // 2, 1)].to(torch.int32)
@@ -1462,7 +1462,7 @@ def test_small_launch_deep_ring_is_bit_identical(rows, prec):
         ep, csr = plan.edge_csr(edge_index, n)
         W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
         pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-        pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
         adds = [ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
         idx = torch.randint(0, E, (E,), device=DEV, dtype=torch.int32)
 
@@ -1521,7 +1521,7 @@ def test_ws_persistent_kernel_equals_tile_kernel(rows, variant):
         ep, csr = plan.edge_csr(edge_index, n)
         W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
         pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-        pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
         adds = [ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
         src = [ops.Source(e, pre_act=_lib.ACT_SELU)] + adds
         idx = torch.randint(0, E, (E,), device=DEV, dtype=torch.int32)
@@ -1591,7 +1591,7 @@ def test_ws_dense_pairs_of_uniform_segments(deg, prec):
             ep, csr = plan.edge_csr(edge_index, n)
             assert csr.uniform_deg == deg and csr.tiles() is not None
             e, pr, pc = torch.randn(E, H, device=DEV), torch.randn(n, H, device=DEV), torch.randn(n, H, device=DEV)
-            pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
             src = [ops.Source(e, pre_act=_lib.ACT_SELU), ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
             lib.g4c_mlp_ws_enable(0)
             ref = ops.mlp_forward(pk, src, E)
@@ -1635,7 +1635,7 @@ def test_ws_persistent_kernel_repeated_launches_are_identical(variant):
         e, v = torch.randn(rows, H, device=DEV), torch.randn(n, H, device=DEV)
         W1 = blk.edge_mlp.state_dict()["MLP.linear_1.weight"]
         pr, pc = (v @ W1[:, H:2 * H].T).contiguous(), (v @ W1[:, 2 * H:].T).contiguous()
-        pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
         idx = torch.randint(0, rows, (rows,), device=DEV, dtype=torch.int32)
         col = torch.arange(rows, device=DEV) // 6
         ep, csr = plan.edge_csr(torch.stack([torch.randint(0, n, (rows,), device=DEV), col]), n)
@@ -1888,10 +1888,10 @@ def test_row_split_kernel_matches_the_weight_stationary_path(layers):
             assert torch.equal(res[True, "no rows"][1], res[True, "compact"][1])
             # a reader outside the kernel (here: the tile kernel, forced) sees tagged rows in feature order
             tagged = res[True, "compact"][0]
-            pk = blk.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = blk.edge_mlp._packed_cols(0, H, [H], [False], False)
             with torch.no_grad():
-                pr = ops.mlp_forward(blk.edge_mlp._packed_cols("hoist1", H, 2 * H, [H], [False], True), [ops.Source(e_send)], n)
-                pc = ops.mlp_forward(blk.edge_mlp._packed_cols("hoist1", 2 * H, 3 * H, [H], [False], True), [ops.Source(e_recv)], n)
+                pr = ops.mlp_forward(blk.edge_mlp._packed_cols(H, 2 * H, [H], [False], True), [ops.Source(e_send)], n)
+                pc = ops.mlp_forward(blk.edge_mlp._packed_cols(2 * H, 3 * H, [H], [False], True), [ops.Source(e_recv)], n)
                 adds = [ops.Source(pr, index=ep.row, additive=True), ops.Source(pc, index=ep.col, additive=True)]
                 via_guard = ops.mlp_forward(pk, [ops.Source(tagged)] + adds, E)
                 by_hand = ops.mlp_forward(pk, [ops.Source(ops.rs_rows_to_natural(tagged))] + adds, E)
@@ -2254,12 +2254,12 @@ def test_bf16_product_rows_are_exact_copies():
             for a, b in zip(h32, h16):
                 assert torch.equal(a.to(torch.bfloat16), b)
             # plain launch: the first layer's block alone (MLP.run_hoisted's "hoist1" launch)
-            pk1 = nxt.edge_mlp._packed_cols("hoist1", H, 2 * H, [H], [False], True)
+            pk1 = nxt.edge_mlp._packed_cols(H, 2 * H, [H], [False], True)
             p32 = ops.mlp_forward(pk1, [ops.Source(v)], n)
             p16 = ops.mlp_forward(pk1, [ops.Source(v)], n, out=torch.empty(n, H, dtype=torch.bfloat16, device=DEV))
             assert torch.equal(p32.to(torch.bfloat16), p16)
             # the consumer: bf16 additive rows == their fp32 widening
-            pk = nxt.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+            pk = nxt.edge_mlp._packed_cols(0, H, [H], [False], False)
             for rows, deg in ((60000, 6), (900, 6)):
                 nn_ = rows // deg
                 e = torch.randn(rows, H, device=DEV)
@@ -2277,9 +2277,69 @@ def test_bf16_product_rows_are_exact_copies():
                 assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), rows
             # fp32 additive rows in another arithmetic are refused loudly
         ops.set_mlp_precision("f16x3")
-        pkf = nxt.edge_mlp._packed_cols("hoist", 0, H, [H], [False], False)
+        pkf = nxt.edge_mlp._packed_cols(0, H, [H], [False], False)
         with pytest.raises(NotImplementedError, match="rounded-bf16 mode"):
             ops.mlp_forward(pkf, [ops.Source(e), ops.Source(pr16, index=ep.row, additive=True), ops.Source(pc16, index=ep.col, additive=True)], rows)
+    finally:
+        ops.set_mlp_precision(old)
+
+
+def test_product_image_in_row_split_order_is_an_image_of_its_own():
+    """Rounded-bf16 mode: one MLP asked for the first-layer product image of the same columns with and without the row-split output order
+    (MLP._packed_cols rs_rows) packs two images — the order is part of the cache key (blocks.PackSpec) — and the second one's product is
+    the first one's with its columns taken in ops._rs_k_order, bit for bit: the weight's rows are permuted, every output column is the
+    same sum."""
+    old = ops.set_mlp_precision("bf16")
+    try:
+        torch.manual_seed(93)
+        H, n = 128, 3000
+        m = B.MLP(3 * H, (H, H, H), True).to(DEV)
+        v = torch.randn(n, H, device=DEV)
+        pk_nat = m._packed_cols(H, 2 * H, [H], [False], True)
+        pk_rs = m._packed_cols(H, 2 * H, [H], [False], True, rs_rows=True)
+        assert pk_nat is not pk_rs
+        assert m._packed_cols(H, 2 * H, [H], [False], True) is pk_nat and m._packed_cols(H, 2 * H, [H], [False], True, rs_rows=True) is pk_rs
+        order = ops._rs_k_order(DEV)
+        for dtype in (torch.bfloat16, torch.float32):
+            nat = ops.mlp_forward(pk_nat, [ops.Source(v)], n, out=torch.empty(n, H, dtype=dtype, device=DEV))
+            rs = ops.mlp_forward(pk_rs, [ops.Source(v)], n, out=torch.empty(n, H, dtype=dtype, device=DEV))
+            assert nat.abs().max().item() > 0 and not torch.equal(rs, nat)
+            assert torch.equal(rs, nat[:, order]), dtype
+    finally:
+        ops.set_mlp_precision(old)
+
+
+@pytest.mark.parametrize("family", ["mus", "remus"])
+def test_a_warm_forward_packs_no_weights(family, monkeypatch):
+    """Every packed weight image of a model is cached by its MLP: the second forward constructs no ops.PackedMLP, and after
+    model.invalidate_packed() the next forward constructs exactly the images the first one did.  A MuS-GNN in the default arithmetic
+    (hoisted first layers, products from the producer's launch, one launch per MP layer) and REMuS-GNN in the rounded-bf16 mode (the
+    row-split kernels' streams and orders)."""
+    built = []
+    init = ops.PackedMLP.__init__
+
+    def counting(self, *a, **kw):
+        built.append(1)
+        init(self, *a, **kw)
+    monkeypatch.setattr(ops.PackedMLP, "__init__", counting)
+    old = ops.set_mlp_precision("f16x3" if family == "mus" else "bf16")
+    try:
+        torch.manual_seed(94)
+        if family == "mus":
+            g = S.mus_graph(8000, levels=2, seed=3).to(DEV)
+            model = gfd.nn.NsTwoScaleGNN(arch=S.mus_arch("NsTwoScaleGNN", 128), device=DEV)
+        else:
+            g = S.remus_graph(20_000, k=5, seed=31).to(DEV)
+            model = gfd.nn.NsRotEquiTreeScaleGNN(arch=S.remus_arch(128), device=DEV)
+        first = model.forward(g.clone()).clone()
+        n_first = len(built)
+        assert n_first > 0
+        again = model.forward(g.clone()).clone()
+        assert len(built) == n_first, f"a warm forward packed {len(built) - n_first} images"
+        model.invalidate_packed()
+        third = model.forward(g.clone())
+        assert len(built) == 2 * n_first, (n_first, len(built))
+        assert torch.equal(first, again) and torch.equal(first, third)
     finally:
         ops.set_mlp_precision(old)
 

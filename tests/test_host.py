@@ -481,3 +481,144 @@ def test_remus_program_knows_which_run_outputs_only_mlps_read():
     # mp114 -> down_mp12 (products) and up_mp21 (skip input); mp212 -> down_mp23, up_mp32 (skip); mp124 -> decoder: MLP operands only.
     # mp34 -> up_mp32 and mp222 -> up_mp21 project the latents of the coarse side: fp32 readers.
     assert got == {"mp114": True, "mp212": True, "mp34": False, "mp222": False, "mp124": True}, got
+
+
+# ------------------------------------------------------------------ MLP.PackSpec: the key of an MLP's packed weight images
+@pytest.fixture
+def specs_only(monkeypatch):
+    """MLP's packing entry points return the description they would ask MLP._image for; loading the library is an error."""
+    from graphs4cfd_amd import ops
+    from graphs4cfd_amd.nn import blocks as B
+
+    def no_library():
+        raise AssertionError("deriving a PackSpec loaded the library")
+    monkeypatch.setattr(_lib, "load", no_library)
+    monkeypatch.setattr(B.MLP, "_image", lambda self, spec: spec)
+    prev = ops.set_mlp_precision("bf16")          # (the rounded-bf16 mode: the one with row-split streams and orders)
+    yield B
+    ops.set_mlp_precision(prev)
+
+
+def _named_requests(B):
+    """What the call sites of nn/blocks.py ask for, under the names they used when every call site spelled its own key."""
+    H = 128
+    msg, upd = B.MLP(3 * H, (H, H, H), layer_norm=True), B.MLP(2 * H, (H, H), layer_norm=True)
+    two = ([H, H], [False, False])
+    return {
+        "hoist": lambda: msg._packed_cols(0, H, [H], [False], False),
+        "hoist1": lambda: msg._packed_cols(H, 2 * H, [H], [False], True),
+        "hoist_rs": lambda: msg._packed_cols(0, H, [H], [False], False, rs_order=True),
+        "hoist1_rs": lambda: msg._packed_cols(H, 2 * H, [H], [False], True, rs_rows=True),
+        "hoist1_rs/rs_in": lambda: msg._packed_cols(H, 2 * H, [H], [False], True, rs_rows=True, rs_in=True),
+        "hoist1, next block": lambda: msg._packed_cols(2 * H, 3 * H, [H], [False], True),
+        "packed": lambda: msg.packed([H, H, H], [False, False, False]),
+        "packed, a block negated": lambda: msg.packed([H, H, H], [True, False, False]),
+        "packed, a block in the row-split order": lambda: upd.packed(*two, None, [True, False]),
+        "update": lambda: upd.packed(*two),
+        "heads": lambda: upd._heads_spec(two, msg, H, [H, H]),
+        "heads, rs_rows": lambda: upd._heads_spec(two, msg, H, [H, H], rs_rows=True),
+        "heads, one": lambda: upd._heads_spec(two, msg, H, [H]),
+        "rs2 format 4": lambda: upd._image(upd._spec(*two, stream=_lib.WFMT_BF16_RS2)),
+        "rs2 format 5": lambda: upd._image(upd._spec(*two, stream=_lib.WFMT_BF16_RS2N)),
+        "rs2 format 4, heads": lambda: upd._heads_spec(two, msg, H, [H, H], stream=_lib.WFMT_BF16_RS2),
+        "rs2 format 5, heads": lambda: upd._heads_spec(two, msg, H, [H, H], stream=_lib.WFMT_BF16_RS2N),
+    }
+
+
+def test_pack_specs_of_different_images_are_different_keys(specs_only):
+    """One cache per MLP, keyed by the image's description alone: every request the blocks make for a different weight stream is a
+    different dictionary key — among them the pairs that once shared a hand-written tag — and the same request twice is the same key."""
+    requests = _named_requests(specs_only)
+    specs = {name: ask() for name, ask in requests.items()}
+    assert all(isinstance(s, specs_only.PackSpec) for s in specs.values()), specs
+    assert len({s: name for name, s in specs.items()}) == len(specs), "two different images share a key"
+    names = sorted(specs)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            assert specs[a] != specs[b] and hash(specs[a]) is not None, (a, b)
+    # (a name in front of MLP._packed_cols' arguments, as call sites once passed to tell their images apart, reaches no key)
+    H, msg = 128, specs_only.MLP(384, (128, 128, 128), layer_norm=True)
+    for name in ("hoist1", "anything else"):
+        assert msg._packed_cols(name, H, 2 * H, [H], [False], True) == msg._packed_cols(H, 2 * H, [H], [False], True)
+        assert msg._packed_cols(name, H, 2 * H, [H], [False], True, rs_rows=True) != msg._packed_cols(name, H, 2 * H, [H], [False], True)
+    again = {name: ask() for name, ask in requests.items()}
+    assert again == specs and all(hash(again[n]) == hash(specs[n]) for n in names)
+    # the stream's arithmetic is part of the key: the same request in another mode is another image
+    from graphs4cfd_amd import ops
+    prev = ops.set_mlp_precision("f16x3")
+    try:
+        assert requests["hoist"]() != specs["hoist"] and requests["packed"]() != specs["packed"]
+    finally:
+        ops.set_mlp_precision(prev)
+
+
+def test_every_field_of_a_pack_spec_is_part_of_the_key(specs_only):
+    import dataclasses
+    requests = _named_requests(specs_only)
+
+    def other(v):
+        if isinstance(v, bool):
+            return not v
+        if isinstance(v, int):
+            return v + 1
+        if isinstance(v, str):
+            return v + "'"
+        if isinstance(v, tuple):
+            return v + v[:1] if v else (0,)
+        if v is None:
+            return ()
+        raise TypeError(f"no other value known for a field of type {type(v)}")
+
+    for name in ("hoist1_rs/rs_in", "heads, rs_rows", "rs2 format 5"):
+        spec = requests[name]()
+        fields = dataclasses.fields(spec)
+        assert len(fields) >= 13
+        for f in fields:
+            changed = dataclasses.replace(spec, **{f.name: other(getattr(spec, f.name))})
+            assert changed != spec and len({spec: 0, changed: 1}) == 2, (name, f.name)
+            assert dataclasses.replace(changed, **{f.name: getattr(spec, f.name)}) == spec, (name, f.name)
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        spec.rs_rows = True
+
+
+def test_requests_no_launch_can_carry_are_refused_before_anything_is_built(specs_only):
+    """No heads from a consumer whose first layer is not 128 wide, for widths other than 128, for more heads than a launch has, or from an MLP
+    that is a chain of launches: None, decided from shapes — the row-split update format included.  Blocks that do not add up to the
+    image's columns are an error at the same point."""
+    B, H = specs_only, 128
+    msg, upd = B.MLP(3 * H, (H, H, H), layer_norm=True), B.MLP(2 * H, (H, H), layer_norm=True)
+    narrow_consumer, chain = B.MLP(3 * H, (64, H), layer_norm=True), B.MLP(2 * H, (256, H), layer_norm=True)
+    two = ([H, H], [False, False])
+    for stream in (0, _lib.WFMT_BF16_RS2):
+        assert upd._heads_spec(two, narrow_consumer, H, [H, H], stream=stream) is None
+        assert upd._heads_spec(two, msg, H, [64, 64], stream=stream) is None
+        assert upd._heads_spec(two, msg, H, [H] * (_lib.MAX_HEADS + 1), stream=stream) is None
+        assert upd._heads_spec(two, msg, H, [], stream=stream) is None
+        assert chain._heads_spec(two, msg, H, [H, H], stream=stream) is None
+    assert B.MLP(2 * H, (H, 64), layer_norm=True)._heads_spec(two, msg, H, [H, H]) is None          # (heads read a 128-wide output)
+    from graphs4cfd_amd.ops import Source
+    x = [Source(torch.randn(8, H)), Source(torch.randn(8, H))]
+    with torch.no_grad():
+        assert upd.run_with_heads(x, 8, _lib.ACT_SELU, narrow_consumer, H, [H, H]) is None
+        assert upd.run_with_heads(x, 8, _lib.ACT_SELU, msg, H, [64, 64], rs_rows=True) is None
+        assert chain.run_with_heads(x, 8, _lib.ACT_SELU, msg, H, [H, H]) is None
+    assert upd.run_with_heads(x, 8, _lib.ACT_SELU, msg, H, [H, H]) is None          # (recorded for autograd: the plain launches)
+    with pytest.raises(ValueError, match="expects 384 input columns"):
+        msg.packed([H, H], [False, False])
+    with pytest.raises(ValueError, match="row-split order"):
+        msg._packed_cols(0, H, [H], [False], False, rs_rows=True)
+
+
+def test_a_cut_stage_recorded_for_autograd_is_an_image_of_its_own(specs_only):
+    """A launch of a chain of launches (an MLP outside the one-launch envelope) that takes part of a layer's weight keeps a view of the
+    parameter only while the call is recorded for autograd: the image packed for inference holds no path back to the parameter, so the
+    recorded call must not be handed it.  Whole layers are passed as the parameters themselves: one image serves both."""
+    from graphs4cfd_amd.ops import Source
+    chain = specs_only.MLP(128, (256, 128), layer_norm=True)
+    x, halves = [Source(torch.randn(8, 128))], [Source(torch.randn(8, 128)), Source(torch.randn(8, 128))]
+    with torch.no_grad():
+        cut, whole = chain._stage(x, layers=(0, 1), rows=(0, 128)), chain._stage(halves, layers=(1, 2))
+    with torch.enable_grad():
+        cut_g, whole_g = chain._stage(x, layers=(0, 1), rows=(0, 128)), chain._stage(halves, layers=(1, 2))
+    assert cut != cut_g and cut_g.grad and not cut.grad
+    assert whole == whole_g and not whole.grad and whole.layer_norm and not cut.layer_norm
