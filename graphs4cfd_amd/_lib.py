@@ -21,7 +21,10 @@ MAX_HEADS = 2
 NARROW_MAX = 8
 KERNEL_MLP_RS = 5
 KERNEL_MLP_RS2 = 6
-KERNEL_NAMES = {0: "none", 1: "mlp_split_kernel", 2: "mlp_bx6_kernel", 3: "mlp_bx6i_kernel", 4: "mlp_ws_kernel", 5: "mlp_rs1_kernel", 6: "mlp_rs2_kernel"}   # g4c_mlp_last_kernel
+KERNEL_MLP_BX6, KERNEL_MLP_WS = 2, 4
+KERNEL_MLP_BX6_CERT, KERNEL_MLP_WS_CERT = 7, 8      # the instantiations without the fp16 range tracker (g4c_mlp_t.range_certified)
+KERNEL_NAMES = {0: "none", 1: "mlp_split_kernel", 2: "mlp_bx6_kernel", 3: "mlp_bx6i_kernel", 4: "mlp_ws_kernel", 5: "mlp_rs1_kernel", 6: "mlp_rs2_kernel",
+                7: "mlp_bx6_kernel", 8: "mlp_ws_kernel"}   # g4c_mlp_last_kernel
 
 _ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "selu": ACT_SELU, "tanh": ACT_TANH}
 
@@ -48,7 +51,7 @@ class g4c_mlp_t(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("k_pad", C.c_int32 * MAX_LAYERS), ("n_pad", C.c_int32 * MAX_LAYERS),
                 ("w", C.c_void_p * MAX_LAYERS), ("b", C.c_void_p * MAX_LAYERS),
                 ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float), ("n_out", C.c_int32), ("w_format", C.c_int32),
-                ("range_slot", C.c_int32)]
+                ("range_slot", C.c_int32), ("range_certified", C.c_int32)]
 
 
 WFMT_FP32, WFMT_F16X2, WFMT_BF16X3, WFMT_BF16_RS, WFMT_BF16_RS2, WFMT_BF16_RS2N, WFMT_BF16 = 0, 1, 2, 3, 4, 5, 6

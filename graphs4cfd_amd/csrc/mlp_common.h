@@ -95,6 +95,10 @@ struct Params {
     // f16x3 arithmetic: range_flag[range_slot] = 1 when a value converted to fp16 reached the end of the fp16 range (g4c_mlp_t)
     int *range_flag;
     int range_slot;
+    // the caller's certificate (g4c_mlp_t.range_certified, of every MLP of the launch; never with save / mul): no value this launch
+    // converts to fp16 can reach the end of the range — the launchers then pick the instantiation without the tracker where there is
+    // one, and range_flag is null either way (a certified launch never writes its flag word)
+    int range_certified;
 };
 
 // The node update fused behind the message launch of an MP layer (g4c_mlp_io_t.upd, mlp_ws_kernel<.., NODE>): after its
@@ -201,9 +205,14 @@ __device__ __forceinline__ unsigned pack_f16(f32x2 x, f32x2 &back) {
 //   RangeV  one v_max3_f32 per PAIR into a per-lane running maximum of |value| (one live VGPR; mlp_ws_kernel)
 //   RangeS  per QUAD a maximum into a temporary, one v_cmp and an s_or into a wave-uniform lane mask (three vector instructions per
 //           four values, no live VGPR: mlp_bx6_kernel sits at its register limit and spills 10 - 20 registers with RangeV)
+//   RangeNone  no tracking at all: the instantiations of a launch whose caller certifies its range (Params::range_certified)
 constexpr float F16_RANGE_END = 65504.f;
 struct RangeV { float m = 0.f; };
 struct RangeS { unsigned long long any = 0ull; };
+struct RangeNone {};
+__device__ __forceinline__ void range_track(RangeNone &, f32x2) {}
+__device__ __forceinline__ void range_track(RangeNone &, f32x4) {}
+__device__ __forceinline__ bool range_hit(const RangeNone &) { return false; }
 __device__ __forceinline__ void range_track(RangeV &r, f32x2 y) { r.m = fmaxf(fmaxf(r.m, fabsf(y[0])), fabsf(y[1])); }       // v_max3_f32 |.|
 __device__ __forceinline__ void range_track(RangeS &r, f32x2 y) {
     r.any |= __builtin_amdgcn_ballot_w64(fmaxf(fabsf(y[0]), fabsf(y[1])) >= F16_RANGE_END);
@@ -243,8 +252,6 @@ __device__ __forceinline__ void split_pair_f16(f32x2 y, unsigned &hu, unsigned &
     range_track(rng, y);
     split_pair_f16(y, hu, lu);
 }
-struct RangeNone {};
-__device__ __forceinline__ void range_track(RangeNone &, f32x4) {}
 template <class R>
 __device__ __forceinline__ void split2x4(f32x4 x, bf16x4 &h, bf16x4 &l, R &rng) {
     range_track(rng, x);
@@ -311,6 +318,7 @@ int bx6i_launch(const Params &p, bool agg, bool f16x2, hipStream_t st);
 int ws_enable(int on);
 bool ws_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, long long row_count, bool any_size = false);
 int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const NodeParams *node = nullptr);
+int ws_last_certified();          // 1: the last ws_launch of this thread ran an instantiation without the range tracker
 
 
 // row-split persistent kernel (mlp_rs.hip, round 6): f16x3 stream, hoisted three-layer message form

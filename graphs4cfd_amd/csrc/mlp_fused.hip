@@ -646,8 +646,11 @@ constexpr int G4C_F16_MINW = 4;
 // twice the rows.
 // FULL: every weighted input block and every additive block is exactly 128 wide and 16-byte aligned (the MP layers):
 // no column masks anywhere.
-template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2>
+// TRACK (SP = 2): the fp16 range tracker (mlp_common.h RangeS); false for a launch whose caller certifies that nothing it converts can
+// reach the end of the range (Params::range_certified): three vector instructions per four converted values less, no flag word written.
+template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2, bool TRACK = true>
 __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX6_MINW)) void mlp_bx6_kernel(const Params p) {
+    static_assert(TRACK || (SP == 2 && !SAVE), "the tracker-free instantiations: f16x3 stream, inference");
     static_assert(RT == 1, "64-row tiles (RT = 2) measured slower in every arithmetic (split streams, round 3: 480 against 446 us; rounded-bf16 mode, round 6, "
                            "500k-row edge update with heads: 288 against 255 us) and cannot take the fused aggregation: not instantiated");
     constexpr int ROWS = 32 * RT, NW = 4;
@@ -679,7 +682,7 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
     const int i = lane & 31, h = lane >> 5;
     const int ct0 = wave;
     if (SP == 2) f16_range_mode();
-    RangeS rng;                       // lanes that converted a value beyond the fp16 range (SP == 2: mlp_common.h range_track)
+    typename std::conditional<TRACK, RangeS, RangeNone>::type rng;          // lanes that converted a value beyond the fp16 range (SP == 2: mlp_common.h range_track)
 
     int tile;
     {
@@ -1129,7 +1132,7 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         }
     }
     G4C_STAMPW(15);
-    if (SP == 2) range_report(p, rng);
+    if constexpr (SP == 2 && TRACK) range_report(p, rng);
 }
 
 // bf16x6 image of one layer: three planes (h, m, l) of the exact split of every weight.  F16: the two-way fp16 split (h, l * 2^11)
@@ -1374,7 +1377,9 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         G4C_REQUIRE(!mul || (io->mul_ld >= NP && (io->mul_ld & 3) == 0), G4C_EINVAL, "g4c_mlp_run: mul_ld=%d", io->mul_ld);
         p.mul_ld = io->mul_ld;
     }
-    p.range_flag = f16x2 ? io->range_flag : nullptr; p.range_slot = mlp->range_slot;
+    // the caller's certificate (g4c_mlp_t.range_certified): every MLP of the launch, the f16x3 stream, no save / mul — then nothing is tracked
+    p.range_certified = (f16x2 && mlp->range_certified && !save && (!node || io->upd->range_certified)) ? 1 : 0;
+    p.range_flag = (f16x2 && !p.range_certified) ? io->range_flag : nullptr; p.range_slot = mlp->range_slot;
     // heads (the kernels read their weights where the stream of the MLP that owns them ends; with `upd`, that MLP's)
     for (int hd = 0; hd < n_heads; ++hd) G4C_REQUIRE(io->head_out[hd], G4C_EINVAL, "g4c_mlp_run: null head output %d", hd);
     p.n_heads = node ? 0 : n_heads; p.head_ld = p.n_heads ? io->head_ld : 0; p.head_bf16 = 0;
@@ -1420,7 +1425,7 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
         q.v = io->v; q.v_ld = io->v_ld; q.w = (const float *)u->w[0]; q.b = (const float *)u->b[0];
         q.gamma = u->ln_gamma; q.beta = u->ln_beta; q.eps = u->ln_eps; q.act = io->v_act;
         q.out = io->v_out; q.out_ld = io->v_out_ld; q.n_heads = n_heads; q.head_ld = io->head_ld;
-        q.range_flag = io->range_flag; q.range_slot = u->range_slot;
+        q.range_flag = p.range_certified ? nullptr : io->range_flag; q.range_slot = u->range_slot;
         for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) q.head_out[hd] = nullptr;
         if (n_heads) {
             G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 && (io->head_ld & 3) == 0 && io->head_ld >= NP, G4C_EINVAL,
@@ -1435,8 +1440,9 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
                     "weighted block, two 128-wide additive blocks, two or three 128-wide layers, aligned rows)");
         p.n_tiles = io->n_tiles;
         if (p.n_tiles == 0) return G4C_OK;
-        g_last_kernel = G4C_KERNEL_MLP_WS;
-        return ws_launch(p, true, false, st, &q);
+        const int rc = ws_launch(p, true, false, st, &q);
+        g_last_kernel = ws_last_certified() ? G4C_KERNEL_MLP_WS_CERT : G4C_KERNEL_MLP_WS;
+        return rc;
     }
     if (rs_fmt) {
         // row-split persistent kernel (mlp_rs.hip): a wave owns 16 rows through all layers, the weights stay in LDS, bf16 rows in its
@@ -1462,8 +1468,9 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
                     (long long)row_begin, (long long)p.M);
         p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
         if (p.n_tiles == 0) return G4C_OK;          // (nothing launches: g4c_mlp_last_kernel stays G4C_KERNEL_NONE — ADVICE r04)
-        g_last_kernel = G4C_KERNEL_MLP_WS;
-        return ws_launch(p, agg, round1, st);
+        const int rc = ws_launch(p, agg, round1, st);
+        g_last_kernel = ws_last_certified() ? G4C_KERNEL_MLP_WS_CERT : G4C_KERNEL_MLP_WS;
+        return rc;
     } else if (bx6 && bx6i_eligible(p, round1, agg, save, f16x2, row_count)) {
         // dual-tile software-pipelined kernel (mlp_bx6i.hip): pairs of 32-row tiles (whole segments with aggregation)
         p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
@@ -1499,6 +1506,12 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
             if (full) mlp_bx6_kernel<1, true, true, 3, true><<<grid, blk, 0, st>>>(p);
             else if (all_vec) mlp_bx6_kernel<1, true, false, 3, true><<<grid, blk, 0, st>>>(p);
             else mlp_bx6_kernel<1, false, false, 3, true><<<grid, blk, 0, st>>>(p);
+        }
+        else if (f16x2 && p.range_certified && full) {
+            // (the tracker-free instantiations: whole 128-wide aligned blocks — every launch of a model's MP layers, pools and unpools)
+            g_last_kernel = G4C_KERNEL_MLP_BX6_CERT;
+            if (deep) mlp_bx6_kernel<1, true, true, 2, false, 8, false><<<grid, blk, 0, st>>>(p);
+            else mlp_bx6_kernel<1, true, true, 2, false, 2, false><<<grid, blk, 0, st>>>(p);
         }
         else if (f16x2) G4C_BX6_LAUNCH(1, 2);
         else if (round1) G4C_BX6_LAUNCH(1, 1);

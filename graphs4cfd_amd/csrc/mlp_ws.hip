@@ -131,8 +131,12 @@ __device__ __forceinline__ f32x2 selu2w_scaled(f32x2 x) {
     }
     return r;
 }
-__device__ __forceinline__ void put_pair_scaled(__bf16 *d, f32x2 S, RangeV &rng) {
-    rng.m = fmaxf(fmaxf(rng.m, fabsf(S[0])), fabsf(S[1]));          // (v_max3_f32; in units of 2^-11: range_report_scaled)
+// (the tracker sees S: its maximum is in units of 2^-11, scaled back once where the kernel reports; RangeNone: nothing to track)
+__device__ __forceinline__ void range_track_scaled(RangeV &rng, f32x2 S) { rng.m = fmaxf(fmaxf(rng.m, fabsf(S[0])), fabsf(S[1])); }      // v_max3_f32
+__device__ __forceinline__ void range_track_scaled(RangeNone &, f32x2) {}
+template <class R>
+__device__ __forceinline__ void put_pair_scaled(__bf16 *d, f32x2 S, R &rng) {
+    range_track_scaled(rng, S);
     unsigned hu, lu;
     const float up = F16_LO_UNSCALE, dn = -F16_LO_SCALE;
     // (one statement: hipcc pads an s_nop behind every asm statement whose output the next instruction reads — three per pair before)
@@ -147,8 +151,8 @@ __device__ __forceinline__ void put_pair_scaled(__bf16 *d, f32x2 S, RangeV &rng)
 
 // two-way fp16 split of a pair -> one packed pair per plane (split_pair_f16, mlp_common.h: four vector instructions + the range tracker)
 // (SP = 1: the pair rounded to bf16, one plane)
-template <int SP>
-__device__ __forceinline__ void put_pair(__bf16 *d, f32x2 y, RangeV &rng) {
+template <int SP, class R>
+__device__ __forceinline__ void put_pair(__bf16 *d, f32x2 y, R &rng) {
     if constexpr (SP == 1) {
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
         bf16x2 b;
@@ -182,8 +186,8 @@ __device__ __forceinline__ void row16_sum2(float &a, float &b) {
 #undef G4C_DPP_ADD
 }
 
-template <int SP, int EK, bool PACT>
-__device__ __forceinline__ void other_piece(int s, const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, f32x2 &hold, RangeV &rng) {
+template <int SP, int EK, bool PACT, class R>
+__device__ __forceinline__ void other_piece(int s, const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, f32x2 &hold, R &rng) {
     const int u = s >> 2, pc4 = s & 3, pr = pc4 >> 1;
     if (EK == 1) {
         if ((pc4 & 1) == 0) {
@@ -225,9 +229,9 @@ constexpr int WS_FRAG_AHEAD = 2;
 // products each: (Wh, xl) and (Wl, xh) into acc1 (the 2^-11 terms), (Wh, xh) into acc.  pa[ks]: this lane's B-operand address
 // (row n, granule (4 ks + g) ^ n) in the tile's h plane.
 // (SP = 1: the one product (W, x) of the leading planes, no acc1.)
-template <int SP, int EK, bool PACT = false>
+template <int SP, int EK, bool PACT = false, class R>
 __device__ __forceinline__ void m_block(const __bf16 *const (&pa)[4], const bf16x8 (&W)[4][SP], f32x4 (&acc)[2], f32x4 (&acc1)[2],
-                                        const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, RangeV &rng) {
+                                        const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, R &rng) {
     // B fragments (h, l planes) of slice s: row block s % 2, k-step s / 2; fetched WS_FRAG_AHEAD slices ahead of their MFMAs
     constexpr int AH = WS_FRAG_AHEAD, RING = AH + 1;
     bf16x8 fh[RING], fl[RING];
@@ -280,8 +284,8 @@ __device__ __forceinline__ void m_block(const __bf16 *const (&pa)[4], const bf16
 }
 
 // a whole unit outside a matrix phase (the first tile of a pair is parked with nothing to overlap with; B's last rows)
-template <int SP, int EK, bool PACT>
-__device__ __forceinline__ void other_all(const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, RangeV &rng) {
+template <int SP, int EK, bool PACT, class R>
+__device__ __forceinline__ void other_all(const f32x4 (&accE)[2], const f32x4 (&accE1)[2], const f32x4 (&xe)[2], const Other &o, R &rng) {
     f32x2 hold = {0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 8; ++s) other_piece<SP, EK, PACT>(s, accE, accE1, xe, o, hold, rng);
@@ -302,7 +306,7 @@ struct NodeCtx {
     const __bf16 *paA[4], *paB[4];
 };
 
-template <int SP, int NL>
+template <int SP, int NL, bool TRACK>
 __device__ __forceinline__ void node_phase(const NodeCtx &c, const float *x0, const int x0_ld, const NodeParams &q, const int S0, const int S1) {
     const int wave = c.wave, n = c.n, g = c.g, fcol = c.fcol, prow = c.prow, pc = c.pc;
     const unsigned lo_b = c.lo_b;
@@ -313,7 +317,7 @@ __device__ __forceinline__ void node_phase(const NodeCtx &c, const float *x0, co
     const __bf16 *const (&paB)[4] = c.paB;
     f32x4 accA[2], accB[2], accA1[2], accB1[2];
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(q.w), 0, 0x7fffffff, 0x00020000);
-    RangeV rngN;
+    typename std::conditional<TRACK, RangeV, RangeNone>::type rngN;
     const int n_blk = NL + 1 + q.n_heads;          // blocks of the node MLP's stream (a head block that does not exist is not fetched)
     auto ld_block = [&](bf16x8 (&Wb)[4][SP], int blk) __attribute__((always_inline)) {
         if (blk >= n_blk) return;
@@ -528,10 +532,65 @@ __device__ __forceinline__ void node_phase(const NodeCtx &c, const float *x0, co
         }
         __syncthreads();          // (a step of <= 32 rows is the last one)
     }
-    if (G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) rngN.m *= F16_LO_UNSCALE;
-    if (q.range_flag && range_hit(rngN)) {
-        if ((threadIdx.x & 63) == 0) q.range_flag[q.range_slot] = 1;
+    if constexpr (TRACK) {
+        if (G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) rngN.m *= F16_LO_UNSCALE;
+        if (q.range_flag && range_hit(rngN)) {
+            if ((threadIdx.x & 63) == 0) q.range_flag[q.range_slot] = 1;
+        }
     }
+}
+
+// The kernel's argument block: what ws_launch keeps of g4cm::Params (which carries G4C_MAX_SRC sources, additive and narrow blocks,
+// save[] / mul[], heads ...) for this kernel's envelope — one weighted block (its first column folded into the pointer), two
+// additive blocks, rows < 2^31.  Everything in it is wave-uniform and lives in scalar registers for the whole launch.
+struct WsArgs {
+    const float *x;           // weighted block: first used column of row 0 (SP = 1, XB16: a __bf16 pointer in disguise, x_ld in elements)
+    const int *x_idx;
+    int x_ld, x_pact;
+    const float *add_ptr[2];  // additive blocks (AB16: __bf16 pointers in disguise, add_ld in elements)
+    const int *add_idx[2];
+    int add_ld[2];
+    const float *w, *b, *gamma, *beta;
+    float eps;
+    int act;
+    float *out;
+    const int *out_idx;
+    int out_ld, out_bf16;
+    const int *tile_rows, *tile_seg, *seg_off;
+    float *agg;
+    int agg_ld, agg_mean, agg_deg;
+    int M, row_base, n_tiles;
+    int *range_flag;
+    int range_slot;
+};
+// the kernel's one parameter (one struct, so that the place of `q` in the argument segment is offsetof(WsKernArgs, q))
+struct WsKernArgs {
+    WsArgs a;
+    int n_pairs;
+    NodeParams q;
+};
+// NODE: the node update's parameters are needed only behind the pair loop.  As ordinary kernel arguments they are loaded at the top and
+// stay live across the whole loop — two dozen scalar registers the loop does not have, parked in lanes of a vector register; read
+// here instead, from the argument segment, when the loop is over.  (The empty asm keeps hipcc from hoisting the loads back.)
+__device__ __forceinline__ NodeParams node_params_now() {
+    typedef const WsKernArgs __attribute__((address_space(4))) *KernArgPtr;
+    KernArgPtr k = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    NodeParams q;
+    q.v = k->q.v; q.v_ld = k->q.v_ld; q.w = k->q.w; q.b = k->q.b; q.gamma = k->q.gamma; q.beta = k->q.beta; q.eps = k->q.eps; q.act = k->q.act;
+    q.out = k->q.out; q.out_ld = k->q.out_ld; q.n_heads = k->q.n_heads; q.head_ld = k->q.head_ld;
+#pragma unroll
+    for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) q.head_out[hd] = k->q.head_out[hd];
+    q.range_flag = k->q.range_flag; q.range_slot = k->q.range_slot;
+    return q;
+}
+// (likewise the message MLP's flag word, read where the kernel reports: null = not tracked)
+__device__ __forceinline__ int *range_word_now() {
+    typedef const WsKernArgs __attribute__((address_space(4))) *KernArgPtr;
+    KernArgPtr k = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    int *const flag = k->a.range_flag;
+    return flag ? flag + k->a.range_slot : nullptr;
 }
 
 // SP: 2 the f16x3 stream, 1 the rounded-bf16 mode;  NL: layers (2 or 3);  XB16 (SP = 1): the weighted block's rows are bf16;
@@ -545,10 +604,15 @@ __device__ __forceinline__ void node_phase(const NodeCtx &c, const float *x0, co
 // Rounded-bf16 mode (SP = 1): two waves per SIMD as well (four — 128 registers, scratch — measured slower: HISTORY.md 4.1)
 constexpr int G4C_WS_SP1_MINW = 2;
 // DENSE (with AGG): the launch's segments all have the same number of rows, 4 .. 8 (G4C_AGG_UNIFORM) — dense pairs, below
-template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16 = false, bool NODE = false, bool DENSE = false>
-__global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_kernel(const Params p, const int n_pairs, const NodeParams q) {
+// TRACK (SP = 2): the fp16 range tracker (mlp_common.h RangeV) in the message loop and in the node phase; false for a launch whose
+// caller certifies that nothing it converts can reach the end of the range (Params::range_certified) — one v_max3_f32 per converted
+// pair and one register less, and the flag word is never written
+template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16 = false, bool NODE = false, bool DENSE = false, bool TRACK = true>
+__global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_kernel(const WsKernArgs ka) {
+    const WsArgs &p = ka.a;
+    const int n_pairs = ka.n_pairs;
     static_assert((SP == 1 || SP == 2) && (NL == 2 || NL == 3) && (SP == 1 || !XB16) && (SP == 1 || !AB16) && (ADDS || !AB16) &&
-                  (!NODE || (AGG && SP == 2)), "mlp_ws_kernel: unsupported instantiation");
+                  (!NODE || (AGG && SP == 2)) && (TRACK || SP == 2), "mlp_ws_kernel: unsupported instantiation");
     // an additive row piece as loaded: four fp32 values, or four bf16 values in two dwords (widened where they are added)
     typedef typename std::conditional<AB16, u32x2, f32x4>::type AddV;
     __shared__ __attribute__((aligned(16))) __bf16 sP[2 * TILE_BF16];      // operand planes of tiles A, B (34 816 B)
@@ -577,13 +641,13 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     // K = 6 or 5: 6.7 % more tiles) whose segments may straddle tile and pair boundaries: the aggregation works on the pair's 64 fp32
     // rows (fA | fB contiguous) and carries the partial sum of a segment cut by the pair's end to the next pair (agg_tail).
     static_assert((AGG || !DENSE) && !(NODE && DENSE), "dense pairs belong to the fused aggregation of a plain message launch");
-    const int KU = DENSE ? p.agg_deg : 0;
+    const int KU = DENSE ? p.agg_deg : 0;          // (DENSE: 4 .. 8, ws_launch)
     int p_begin, p_end, R0 = 0, R1 = 0;
     {
         const int G = gridDim.x, b = blockIdx.x;
         const int slot = (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3);
-        if (KU) {
-            const long long n_seg = p.M / KU;
+        if constexpr (DENSE) {
+            const int n_seg = p.M / KU;
             R0 = __builtin_amdgcn_readfirstlane((int)(((long long)slot * n_seg) / G) * KU);
             R1 = __builtin_amdgcn_readfirstlane((int)(((long long)(slot + 1) * n_seg) / G) * KU);
             p_begin = 0; p_end = (R1 - R0 + 63) >> 6;          // (local pair numbers)
@@ -599,12 +663,11 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     // (the loads are issued where load_meta is called; fix_meta — the v_readfirstlanes that wait for them — an iteration later)
     auto load_meta = [&](int pair) __attribute__((always_inline)) {
         Meta m;
-        if (AGG && KU) {
+        if constexpr (DENSE) {
             if (pair > p_end - 1) pair = p_end - 1;
             const int r0 = R0 + 64 * pair, nr = (R1 - r0) < 64 ? (R1 - r0) : 64;
             m.r0[0] = r0; m.n[0] = nr < 32 ? nr : 32; m.r0[1] = r0 + 32; m.n[1] = nr - m.n[0];
-            m.s0[0] = r0 / KU;          // the segment the pair's first row belongs to (it started before the pair unless KU s0 == r0)
-            m.s1[0] = m.s0[1] = m.s1[1] = 0;
+            m.s0[0] = m.s1[0] = m.s0[1] = m.s1[1] = 0;          // (the pair's first segment is r0 / K: reduce_uniform, where K is a constant)
             if (m.n[1] == 0) m.r0[1] = m.r0[0];
             return m;
         }
@@ -622,7 +685,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
                 const int tile = t0 + t;
                 m.s0[t] = 0; m.s1[t] = 0;
                 if (tile >= p.n_tiles) { m.r0[t] = 0; m.n[t] = 0; }
-                else { m.r0[t] = (int)p.row_base + tile * 32; const int lim = (int)p.M - m.r0[t]; m.n[t] = lim < 32 ? lim : 32; }
+                else { m.r0[t] = p.row_base + tile * 32; const int lim = p.M - m.r0[t]; m.n[t] = lim < 32 ? lim : 32; }
             }
         }
         if (m.n[1] == 0) m.r0[1] = m.r0[0];       // (odd tile count: the second tile recomputes the first tile's rows and stores nothing)
@@ -639,9 +702,9 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     };
     // one int per thread of a pair's tables: threads [0, 192) the gather indices [tile][kind][row] (rows past a tile's end are
     // clamped copies of its last row: never stored), threads [256, 256 + 2 (SEGCAP + 1)) the segment offsets of the tiles' targets
-    const int *const dummy = reinterpret_cast<const int *>(p.b);
+    const int *const dummy = reinterpret_cast<const int *>(p.x);          // (a valid address that is in a register anyway)
     auto load_tables = [&](const Meta &m) __attribute__((always_inline)) {
-        const int *ix0 = p.src[0].idx, *ix1 = ADDS ? p.add[0].idx : nullptr, *ix2 = ADDS ? p.add[1].idx : nullptr;
+        const int *ix0 = DIRECT ? nullptr : p.x_idx, *ix1 = ADDS ? p.add_idx[0] : nullptr, *ix2 = ADDS ? p.add_idx[1] : nullptr;
         const int tt = tid < 192 ? tid : 0;
         const int t = tt / 96, k = (tt % 96) >> 5, r = tt & 31;
         const int nn = m.n[t] > 0 ? m.n[t] : m.n[0];
@@ -649,7 +712,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         const int *ix = (k == 0) ? ix0 : (k == 1 ? ix1 : ix2);
         const int *addr = ix ? ix + gr : dummy;
         int j = 0, ts = 0;
-        if (AGG && !KU) {
+        if (AGG && !DENSE) {
             const int q = tid - 256;
             const bool is_seg = q >= 0 && q < 2 * (SEGCAP + 1);
             ts = is_seg && q >= SEGCAP + 1 ? 1 : 0;
@@ -663,7 +726,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     };
     auto store_tables = [&](int v, int it) __attribute__((always_inline)) {
         if (tid < 192) sIdx[it & 1][tid] = v;
-        if (AGG && !KU && tid >= 256 && tid < 256 + 2 * (SEGCAP + 1)) sSeg[it & 3][tid - 256] = v;
+        if (AGG && !DENSE && tid >= 256 && tid < 256 + 2 * (SEGCAP + 1)) sSeg[it & 3][tid - 256] = v;
     };
     // input rows of the weighted block (park layout) and additive rows (accumulator layout) of a pair whose indices are in sIdx[ring].
     // Three batches of four 16-byte loads per lane, issued in three different phases: a CU's share of the HBM bandwidth is ~13 bytes
@@ -678,10 +741,10 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
                 const int gr = DIRECT ? m.r0[t] + (r < nn ? r : nn - 1) : sIdx[ring][t * 96 + r];
                 if constexpr (XB16) {       // bf16 rows (8-byte aligned: the launcher checks): widened by a shift / a mask — exact
                     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    const u32x2 w = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.src[0].ptr) + (long long)gr * p.src[0].ld + p.src[0].col0 + pc);
+                    const u32x2 w = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.x) + (long long)gr * p.x_ld + pc);
                     raw[hh][0] = w[0]; raw[hh][1] = w[1];      // (widen_x before use)
                 } else
-                xt[hh] = *reinterpret_cast<const f32x4 *>(p.src[0].ptr + (long long)gr * p.src[0].ld + p.src[0].col0 + pc);
+                xt[hh] = *reinterpret_cast<const f32x4 *>(p.x + (long long)gr * p.x_ld + pc);
             }
         }
     };
@@ -701,11 +764,11 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
             for (int rb = 0; rb < 2; ++rb) {
                 const int r = n + 16 * rb;
                 if constexpr (AB16) {
-                    ad[rb][0] = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.add[0].ptr) + (long long)sIdx[ring][t * 96 + 32 + r] * p.add[0].ld + fcol);
-                    ad[rb][1] = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.add[1].ptr) + (long long)sIdx[ring][t * 96 + 64 + r] * p.add[1].ld + fcol);
+                    ad[rb][0] = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.add_ptr[0]) + (long long)sIdx[ring][t * 96 + 32 + r] * p.add_ld[0] + fcol);
+                    ad[rb][1] = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const __bf16 *>(p.add_ptr[1]) + (long long)sIdx[ring][t * 96 + 64 + r] * p.add_ld[1] + fcol);
                 } else {
-                    ad[rb][0] = *reinterpret_cast<const f32x4 *>(p.add[0].ptr + (long long)sIdx[ring][t * 96 + 32 + r] * p.add[0].ld + fcol);
-                    ad[rb][1] = *reinterpret_cast<const f32x4 *>(p.add[1].ptr + (long long)sIdx[ring][t * 96 + 64 + r] * p.add[1].ld + fcol);
+                    ad[rb][0] = *reinterpret_cast<const f32x4 *>(p.add_ptr[0] + (long long)sIdx[ring][t * 96 + 32 + r] * p.add_ld[0] + fcol);
+                    ad[rb][1] = *reinterpret_cast<const f32x4 *>(p.add_ptr[1] + (long long)sIdx[ring][t * 96 + 64 + r] * p.add_ld[1] + fcol);
                 }
             }
         }
@@ -718,9 +781,17 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     const unsigned lo_b = 2u * (unsigned)((wave >> 1) * 8 * STEP6 + (g >> 1) * STEP6 + ((g & 1) * 32 + 16 * (wave & 1) + n) * 8);
     bf16x8 W[NL][4][SP];
     if (SP == 2) f16_range_mode();
-    RangeV rng;                       // running max |value converted to fp16| (mlp_common.h range_track)
+    typename std::conditional<TRACK, RangeV, RangeNone>::type rng;          // running max |value converted to fp16| (mlp_common.h range_track)
 
     Meta m0 = fix_meta(load_meta(p_begin)), m1 = fix_meta(load_meta(p_begin + 1)), m2 = fix_meta(load_meta(p_begin + 2));
+    // Dense pairs: a pair's meta is a few scalar instructions on (R0, R1, pair), so nothing is carried from iteration to iteration —
+    // each use recomputes it from the pair number.  (Carried, the three metas in flight were 15 scalar registers live across the whole
+    // loop body, and with them the kernel kept 30-odd scalars in lanes of a vector register, read back with v_readlane in the loop.
+    // The empty asm keeps hipcc from merging the recomputations back into one long-lived copy.)
+    auto meta_at = [&](int pair_, const Meta &carried) __attribute__((always_inline)) {
+        if constexpr (DENSE) { asm volatile("" : "+s"(pair_)); return load_meta(pair_); }
+        else return carried;
+    };
     {
         const int v0 = load_tables(m0), v1 = load_tables(m1);
         store_tables(v0, 0);
@@ -735,16 +806,14 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     if (tid < NL * NP) sBias[tid] = p.b[tid];
     if (tid < NP) sZero[tid] = 0.f;
     if (tid < 2 * NP) sGB[tid] = p.gamma ? (tid < NP ? p.gamma[tid] : p.beta[tid - NP]) : 0.f;
-    int S0 = 0, S1 = 0;                   // NODE: this workgroup's targets = the segments of its tiles
     if constexpr (NODE) {
+        const NodeParams &q = ka.q;
         if (tid < NL * NP) sBiasN[tid] = q.b[tid];
         if (tid < 2 * NP) sGBN[tid] = q.gamma ? (tid < NP ? q.gamma[tid] : q.beta[tid - NP]) : 0.f;
-        const int t1 = 2 * p_end < p.n_tiles ? 2 * p_end : p.n_tiles;
-        S0 = __builtin_amdgcn_readfirstlane(p.tile_seg[2 * p_begin]); S1 = __builtin_amdgcn_readfirstlane(p.tile_seg[t1]);
     }
     __syncthreads();
 
-    const bool pact = p.src[0].pre_act != 0;
+    const bool pact = p.x_pact != 0;
     __bf16 *const sA = sP, *const sB = sP + TILE_BF16;
     float *const fA = sF, *const fB = sF + FIN;
     Other oA, oB;       // what to do FOR tile A / FOR tile B while the other multiplies
@@ -934,7 +1003,8 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
             auto reduce_uniform = [&](auto KC) __attribute__((always_inline)) {
                 constexpr int K = decltype(KC)::value;
                 constexpr float cK = (float)K, yK = 1.0f / (float)K;          // (yK: the correctly rounded reciprocal)
-                const int r0 = mm.r0[0], nr = mm.n[0] + mm.n[1], j0 = mm.s0[0];
+                // j0: the segment the pair's first row belongs to (it started before the pair unless K j0 == r0)
+                const int r0 = mm.r0[0], nr = mm.n[0] + mm.n[1], j0 = (int)((unsigned)r0 / (unsigned)K);
                 const int lead = (j0 * K < r0) ? (j0 * K + K - r0) : 0;
                 const int nfull = (nr - lead) / K, rest = nr - lead - nfull * K;
                 const int jf = j0 + (lead ? 1 : 0);          // target of the first whole segment
@@ -975,7 +1045,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
                     if (hi && rest) *reinterpret_cast<f32x4 *>(sCarry + c4) = a;
                 }
             };
-            if (KU) {
+            if constexpr (DENSE) {
                 typedef std::integral_constant<int, 4> K4; typedef std::integral_constant<int, 5> K5; typedef std::integral_constant<int, 6> K6;
                 typedef std::integral_constant<int, 7> K7; typedef std::integral_constant<int, 8> K8;
                 if (KU == 6) reduce_uniform(K6{});
@@ -1023,8 +1093,9 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     for (int it = 0, pair = p_begin; pair < p_end; ++pair, ++it) {
         WS_STAMP(0);
         // ---- tables two pairs ahead (their meta was loaded an iteration ago), meta three pairs ahead
-        const Meta m3raw = load_meta(pair + 3);
-        const int tv = load_tables(m2);
+        Meta m3raw;
+        if constexpr (!DENSE) m3raw = load_meta(pair + 3);
+        const int tv = load_tables(meta_at(pair + 2, m2));
         // (tile A's planes were written in the previous iteration's last matrix phase — before the loop for the first pair — and
         // that phase's barrier lies between; nothing the stragglers of the previous tail still read is written in this phase)
         WS_STAMP(1);
@@ -1038,7 +1109,7 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         f32x4 nxa[2];
         AddV nadA[2][2];
         unsigned nraw[2][2] = {{0u, 0u}, {0u, 0u}};
-        gather_x(m1, (it + 1) & 1, 0, nxa, nraw);
+        gather_x(meta_at(pair + 1, m1), (it + 1) & 1, 0, nxa, nraw);
         m_block<SP, 1>(paB, W[0], accB, accB1, accA, accA1, xr[1], oA, rng);                 // for A: epilogue of layer 0
         bias_init(accA, accA1, 1);
         __syncthreads();
@@ -1075,14 +1146,15 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         asm volatile("" : "+v"(accA[0]), "+v"(accA[1]) :: "memory");
         // (the meta three pairs ahead, requested at the top: taken here, in front of the tail's stores — at the end of the iteration
         // the wait for these loads would also wait for every store of the tail, which memory acknowledges in order)
-        const Meta m3 = fix_meta(m3raw);
-        gather_x(m1, (it + 1) & 1, 1, xr[1], rawB);
+        Meta m3;
+        if constexpr (!DENSE) m3 = fix_meta(m3raw);
+        gather_x(meta_at(pair + 1, m1), (it + 1) & 1, 1, xr[1], rawB);
         // the tables fetched at the top of this iteration (older than every other load in flight) go to the ring slot of the pair
         // whose rows were gathered in the previous iteration; the next iteration's top barrier publishes them
         store_tables(tv, it + 2);
         WS_STAMP(8);
 
-        if (!(G4C_WS_ABLATE & 256)) ln_tail(m0, it);
+        if (!(G4C_WS_ABLATE & 256)) ln_tail(meta_at(pair, m0), it);
         // (rounded-bf16 mode: the row stores are half as many bytes, and the gathers in front of the aggregation's barrier measure
         // 1.8 % faster per pair than behind the aggregation; f16x3 stream: 3 % slower — they queue behind the fp32 row stores)
         if constexpr (SP == 1) gather_adds(1, (it + 1) & 1, adB);
@@ -1092,14 +1164,14 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         if (AGG) {
             __syncthreads();
             WS_STAMP(15);
-            if (!(G4C_WS_ABLATE & 128)) agg_tail(m0, it);
+            if (!(G4C_WS_ABLATE & 128)) agg_tail(meta_at(pair, m0), it);
         }
         // the next pair's tile B additive rows (added after its M(A', 0)): behind this tail's stores — issued together with tile B's
         // rows at the top of the tail, the six loads per lane held up the LayerNorm's stores (tail 3.4 k -> 6.6 k ticks)
         WS_STAMP(16);
         if constexpr (SP != 1) gather_adds(1, (it + 1) & 1, adB);
         WS_STAMP(10);
-        m0 = m1; m1 = m2; m2 = m3;
+        if constexpr (!DENSE) { m0 = m1; m1 = m2; m2 = m3; }
     }
 
     if constexpr (NODE) {
@@ -1115,18 +1187,36 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         nc.sBiasN = sBiasN; nc.sGBN = sGBN; nc.fA = fA; nc.fB = fB; nc.oA = oA; nc.oB = oB;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) { nc.paA[ks] = paA[ks]; nc.paB[ks] = paB[ks]; }
-        node_phase<SP, NL>(nc, p.agg, p.agg_ld, q, S0, S1);
+        // this workgroup's targets = the segments of its tiles
+        const int t1 = 2 * p_end < p.n_tiles ? 2 * p_end : p.n_tiles;
+        const int S0 = __builtin_amdgcn_readfirstlane(p.tile_seg[2 * p_begin]), S1 = __builtin_amdgcn_readfirstlane(p.tile_seg[t1]);
+        const NodeParams q = node_params_now();
+        node_phase<SP, NL, TRACK>(nc, p.agg, p.agg_ld, q, S0, S1);
     }
     WS_STAMP_ONCE(13, __builtin_readcyclecounter());
-    if (SP == 2) {
+    if constexpr (SP == 2 && TRACK) {
         if (G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) rng.m *= F16_LO_UNSCALE;       // (tracked in units of 2^-11)
-        range_report(p, rng);
+        if (range_hit(rng)) {
+            int *const word = range_word_now();
+            if (word && (threadIdx.x & 63) == 0) *word = 1;
+        }
     }
 }
 
 
+#ifdef G4C_WS_ISA_ONLY
+// -DG4C_WS_ISA_ONLY (tests/test_ws_isa.py, with --cuda-device-only -S): nothing but the headline step's four instantiations — the level-1
+// message launch <.., DENSE> and the fused MP layer <.., NODE>, tracked and certified — for a look at their registers and instructions
+// in seconds instead of the minute the whole file takes
+template __global__ void mlp_ws_kernel<true, true, true, 2, 3, false, false, false, true, true>(const WsKernArgs);
+template __global__ void mlp_ws_kernel<true, true, true, 2, 3, false, false, false, true, false>(const WsKernArgs);
+template __global__ void mlp_ws_kernel<true, true, true, 2, 3, false, false, true, false, true>(const WsKernArgs);
+template __global__ void mlp_ws_kernel<true, true, true, 2, 3, false, false, true, false, false>(const WsKernArgs);
+#endif
+
 }  // namespace
 
+#ifndef G4C_WS_ISA_ONLY
 namespace g4cm {
 
 // 0 off, 1 (default) launches of at least 20 000 rows (measured on the level-1 message launch against
@@ -1162,40 +1252,69 @@ bool ws_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, 
     return true;
 }
 
+static thread_local int g_ws_certified = 0;
+int ws_last_certified() { return g_ws_certified; }
+
 int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const NodeParams *node) {
     // (dense mode — uniform segments of 4 .. 8 rows — cuts the rows into pairs of 64 itself: n_pairs only sizes the grid there)
     // Not for the fused MP layer: its launches are a few pairs per workgroup (nothing to win from denser pairs), and its three-layer
     // instantiation sits at 256 registers — with the dense bookkeeping it spills (config 2: 1 786 -> 1 734 steps/s, same box).
     const bool dense = agg && !node && p.agg_deg >= 4 && p.agg_deg <= 8;
     const int n_pairs = dense ? (int)((p.M + 63) / 64) : (p.n_tiles + 1) / 2;
+    g_ws_certified = 0;
     if (n_pairs == 0) return G4C_OK;
     const int n_wg = g4c::cu_count() * (round1 ? G4C_WS_SP1_MINW / 2 : 1);          // persistent workgroups: one (SP = 1: G4C_WS_SP1_MINW / 2) per CU
     const dim3 grid(n_pairs < n_wg ? n_pairs : n_wg), blk(512);
     const bool direct = p.src[0].idx == nullptr, adds = p.n_add == 2, two = p.n_layers == 2, xb16 = p.src[0].bf16 != 0;
     const bool ab16 = adds && p.add[0].bf16 != 0;
+    // the tracker-free instantiations: the f16x3 stream with the two additive blocks (the hoisted message form every MP layer of a
+    // model launches); a certified launch of another shape runs the tracked kernel with a null flag pointer
+    const bool cert = p.range_certified && !round1 && adds;
+    g_ws_certified = cert ? 1 : 0;
+    WsArgs a{};
+    const Src &s = p.src[0];
+    a.x = s.bf16 ? reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(s.ptr) + s.col0) : s.ptr + s.col0;
+    a.x_idx = s.idx; a.x_ld = s.ld; a.x_pact = s.pre_act;
+    for (int j = 0; j < 2; ++j) { a.add_ptr[j] = adds ? p.add[j].ptr : nullptr; a.add_idx[j] = adds ? p.add[j].idx : nullptr; a.add_ld[j] = adds ? p.add[j].ld : 0; }
+    a.w = p.w; a.b = p.b; a.gamma = p.gamma; a.beta = p.beta; a.eps = p.eps; a.act = p.act;
+    a.out = p.out; a.out_idx = p.out_idx; a.out_ld = p.out_ld; a.out_bf16 = p.out_bf16;
+    a.tile_rows = p.tile_rows; a.tile_seg = p.tile_seg; a.seg_off = p.seg_off;
+    a.agg = p.agg; a.agg_ld = p.agg_ld; a.agg_mean = p.agg_mean; a.agg_deg = p.agg_deg;
+    a.M = (int)p.M; a.row_base = (int)p.row_base; a.n_tiles = p.n_tiles;          // (ws_eligible: M < 2^31)
+    a.range_flag = p.range_certified ? nullptr : p.range_flag; a.range_slot = p.range_slot;
     NodeParams q{};
     if (node) {          // the fused MP layer (g4c_mlp_io_t.upd): f16x3 stream, hoisted message MLP, fused aggregation
         G4C_REQUIRE(agg && !round1 && adds, G4C_EUNSUPPORTED, "g4c_mlp_run (upd): needs the hoisted f16x3 message launch with the fused aggregation");
         q = *node;
-#define G4C_WS_NODE(DIRECT, NL) mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true><<<grid, blk, 0, st>>>(p, n_pairs, q)
+        if (p.range_certified) q.range_flag = nullptr;
+        const WsKernArgs ka{a, n_pairs, q};
+#define G4C_WS_NODE(DIRECT, NL)                                                                                                        \
+    do { if (cert) mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true, false, false><<<grid, blk, 0, st>>>(ka);    \
+         else mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true><<<grid, blk, 0, st>>>(ka); } while (0)
         if (direct) { if (two) G4C_WS_NODE(true, 2); else G4C_WS_NODE(true, 3); }
         else { if (two) G4C_WS_NODE(false, 2); else G4C_WS_NODE(false, 3); }
 #undef G4C_WS_NODE
         return g4c::check_launch("g4c_mlp_run (ws, upd)");
     }
+    const WsKernArgs ka{a, n_pairs, q};
 #define G4C_WS_GO(AGG, DIRECT, ADDS, SP, NL, XB16)                                                                                      \
-    do { if (AGG && dense) mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(p, n_pairs, q);       \
-         else mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16><<<grid, blk, 0, st>>>(p, n_pairs, q); } while (0)
+    do { if (AGG && dense) mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(ka);       \
+         else mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16><<<grid, blk, 0, st>>>(ka); } while (0)
+#define G4C_WS_GOC(AGG, DIRECT, NL)          /* certified: f16x3 stream, additive blocks, no tracker */                                 \
+    do { if (AGG && dense) mlp_ws_kernel<AGG, DIRECT, true, 2, NL, false, false, false, AGG, false><<<grid, blk, 0, st>>>(ka);       \
+         else mlp_ws_kernel<AGG, DIRECT, true, 2, NL, false, false, false, false, false><<<grid, blk, 0, st>>>(ka); } while (0)
 #define G4C_WS_GO1(AGG, DIRECT, NL, XB16)                                                                                               \
-    do { if (AGG && dense) { if (ab16) mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, true, false, AGG><<<grid, blk, 0, st>>>(p, n_pairs, q);       \
-                             else mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(p, n_pairs, q); }        \
-         else if (ab16) mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, true><<<grid, blk, 0, st>>>(p, n_pairs, q);                        \
-         else mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, false><<<grid, blk, 0, st>>>(p, n_pairs, q); } while (0)
+    do { if (AGG && dense) { if (ab16) mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, true, false, AGG><<<grid, blk, 0, st>>>(ka);       \
+                             else mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(ka); }        \
+         else if (ab16) mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, true><<<grid, blk, 0, st>>>(ka);                        \
+         else mlp_ws_kernel<AGG, DIRECT, true, 1, NL, XB16, false><<<grid, blk, 0, st>>>(ka); } while (0)
 #define G4C_WS_SHAPE(AGG, DIRECT)                                                                    \
     do {                                                                                             \
         if (round1) {                                                                                \
             if (two) { if (xb16) G4C_WS_GO1(AGG, DIRECT, 2, true); else G4C_WS_GO1(AGG, DIRECT, 2, false); }      \
             else { if (xb16) G4C_WS_GO1(AGG, DIRECT, 3, true); else G4C_WS_GO1(AGG, DIRECT, 3, false); }          \
+        } else if (cert) {                                                                           \
+            if (two) G4C_WS_GOC(AGG, DIRECT, 2); else G4C_WS_GOC(AGG, DIRECT, 3);                    \
         } else if (two) {                                                                            \
             if (adds) G4C_WS_GO(AGG, DIRECT, true, 2, 2, false); else G4C_WS_GO(AGG, DIRECT, false, 2, 2, false);                 \
         } else {                                                                                     \
@@ -1206,6 +1325,7 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
     else { if (direct) G4C_WS_SHAPE(false, true); else G4C_WS_SHAPE(false, false); }
 #undef G4C_WS_SHAPE
 #undef G4C_WS_GO1
+#undef G4C_WS_GOC
 #undef G4C_WS_GO
     return g4c::check_launch("g4c_mlp_run (ws)");
 }
@@ -1213,3 +1333,4 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
 }  // namespace g4cm
 
 extern "C" int g4c_mlp_ws_enable(int on) { return g4cm::ws_enable(on); }
+#endif

@@ -47,7 +47,7 @@ def _split_wide(sources: Sequence[Source]) -> List[Source]:
     for s in sources:
         if s.width > 128 and not s.additive and s.segments is None:
             for c in range(0, s.width, 128):
-                out.append(Source(s.tensor, s.index, s.col0 + c, min(128, s.width - c), s.negate, s.pre_act))
+                out.append(Source(s.tensor, s.index, s.col0 + c, min(128, s.width - c), s.negate, s.pre_act, bound=s.bound))
         else:
             out.append(s)
     return out if len(out) <= _lib.MAX_SRC else list(sources)
@@ -385,16 +385,22 @@ class MLP(nn.Module):
                           cols=(a, b), bias=not first_only, stream=_lib.WFMT_BF16_RS if rs_order else 0, rs_rows=rs_rows)
 
     def run_hoisted(self, k_sources: Sequence[Source], gathered: Sequence[Tuple[Tensor, Tensor]], n_rows: int,
-                    act_code: int = _lib.ACT_NONE, products: Optional[Sequence[Tensor]] = None, **kw) -> Tensor:
+                    act_code: int = _lib.ACT_NONE, products: Optional[Sequence[Tensor]] = None,
+                    gathered_bounds: Optional[Sequence[Optional[float]]] = None,
+                    product_bounds: Optional[Sequence[Optional[float]]] = None, **kw) -> Tensor:
         """MLP(cat(k_sources..., t0[idx0], t1[idx1], ...)) with the first layer's products of the gathered node-side
         inputs hoisted: W1 [x | t[idx]] = W1x x + (W1t t)[idx] (exact up to fp32 re-association), so `W1t t` costs
         rows(t) instead of n_rows.  `gathered` = [(tensor [n_t, w_t], int32 index [n_rows])] in concat order.
         Below HOIST_MIN_ROWS the launch is latency-bound and the extra product launches cost more than the MFMA
         work they save (measured crossover ~25k rows): one plain fused launch then.
-        `products` (from the producer's launch, MLP.run_with_heads): the per-node terms, already multiplied."""
+        `products` (from the producer's launch, MLP.run_with_heads): the per-node terms, already multiplied.
+        `gathered_bounds` / `product_bounds`: what the caller has proven about |gathered tensors| / |products| (Source.bound), entry by
+        entry; None = nothing."""
+        gb = list(gathered_bounds) if gathered_bounds is not None else [None] * len(gathered)
+        pb = list(product_bounds) if (product_bounds is not None and products is not None) else [None] * len(gathered)
         if self._rs1_takes(k_sources, gathered, n_rows, act_code, products, kw):
             return self._run_rs1(k_sources[0], gathered, n_rows, products, kw)
-        plain = list(k_sources) + [Source(t, index=idx) for t, idx in gathered]
+        plain = list(k_sources) + [Source(t, index=idx, bound=b) for (t, idx), b in zip(gathered, gb)]
         if not self.fits_one_launch():          # (a chain of launches: nothing to hoist into)
             return self.run_coded(plain, n_rows, act_code, **kw)
         # (a gathered block wider than 128 whose chunks would exceed the kernels' block count — gMuS-GNN's 2H-wide latents after an
@@ -409,14 +415,15 @@ class MLP(nn.Module):
         for j, (t, idx) in enumerate(gathered):
             w_t = int(t.size(1))
             if products is not None:
-                part = products[j]
+                part, part_bound = products[j], pb[j]
             else:
                 chunks = [(c, min(128, w_t - c)) for c in range(0, w_t, 128)] if (w_t > 128 and not ops.grad_mode()) else [(0, w_t)]
                 pk1 = self._packed_cols(off, off + w_t, [w for _, w in chunks], [False] * len(chunks), True)
                 part16 = (torch.empty((int(t.size(0)), 128), dtype=torch.bfloat16, device=t.device)
                           if (ops.mlp_precision() == "bf16" and PRODUCTS_BF16 and pk1.n_out == 128 and pk1.precision == "bf16") else None)
-                part = ops.mlp_forward(pk1, [Source(t, col0=c, width=w) for c, w in chunks], int(t.size(0)), out=part16)
-            adds.append(Source(part, index=idx, additive=True))
+                part = ops.mlp_forward(pk1, [Source(t, col0=c, width=w, bound=gb[j]) for c, w in chunks], int(t.size(0)), out=part16)
+                part_bound = ops.take_bounds().out
+            adds.append(Source(part, index=idx, additive=True, bound=part_bound))
             off += w_t
         if off != self.input_size:
             raise ValueError(f"MLP expects {self.input_size} input columns, got {off}")
@@ -664,15 +671,20 @@ def _can_fuse_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e, edge_index: Tensor
 
 
 def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, mean: bool, act_code: int, products,
-                 next_msg: Optional[MLP], keep_e: bool):
-    """The MP layer as one launch.  Returns (v', e' or None, next products or None)."""
+                 next_msg: Optional[MLP], keep_e: bool, rb: ops.RangeBounds):
+    """The MP layer as one launch.  Returns (v', e' or None, next products or None); `rb`: the bounds of v / the products in, of
+    v' / e' / the next products out."""
     H = 128
     dev = v.device
     n_t = int(v.size(0))
+    pb = [rb.product(0), rb.product(1)]
     if products is None:          # the node-side products of this layer's first layer: W1[:, H:2H] v, W1[:, 2H:3H] v (MLP.run_hoisted)
-        products = [ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True), [Source(v)], n_t) for j in range(2)]
+        products = []
+        for j in range(2):
+            products.append(ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True), [Source(v, bound=rb.v)], n_t))
+            pb[j] = ops.take_bounds().out
     pk_msg = msg_mlp._packed_cols(0, H, [H], [e_src.negate], False)
-    srcs = [e_src, Source(products[0], index=ep.row, additive=True), Source(products[1], index=ep.col, additive=True)]
+    srcs = [e_src, Source(products[0], index=ep.row, additive=True, bound=pb[0]), Source(products[1], index=ep.col, additive=True, bound=pb[1])]
     heads = None
     if next_msg is not None and next_msg.input_size == 3 * H and next_msg._linears()[0].out_features == H:
         spec = upd_mlp._heads_spec(([H, H], [False, False]), next_msg, next_msg.input_size - 2 * H, [H, H])
@@ -681,7 +693,10 @@ def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, 
             heads = [torch.empty((n_t, H), dtype=torch.float32, device=dev) for _ in range(2)]
     if heads is None:
         pk_upd = upd_mlp.packed([H, H], [False, False])
-    e_new, v_new, _ = ops.mp_layer_forward(pk_msg, srcs, ep.n_edges, csr, mean, pk_upd, v, act_code, store_rows=keep_e, head_outs=heads)
+    e_new, v_new, _ = ops.mp_layer_forward(pk_msg, srcs, ep.n_edges, csr, mean, pk_upd, v, act_code, store_rows=keep_e, head_outs=heads,
+                                           v_bound=rb.v)
+    lb = ops.take_bounds()
+    rb.v, rb.e, rb.products = lb.out, lb.e, (lb.heads if heads is not None else None)
     return v_new, e_new, heads
 
 
@@ -689,7 +704,8 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
              e_pre_act: int = _lib.ACT_NONE, v_src: Optional[Tensor] = None,
              products: Optional[Sequence[Tensor]] = None, next_msg: Optional[MLP] = None, keep_e: bool = True,
              n_targets: Optional[int] = None, v_out: Optional[Tensor] = None, compact_messages: bool = False,
-             next_graph: Optional[Tuple[int, "plan.CsrPlan"]] = None, compact_v: bool = False):
+             next_graph: Optional[Tuple[int, "plan.CsrPlan"]] = None, compact_v: bool = False,
+             bounds: Optional[ops.RangeBounds] = None):
     """Shared body of GNBlock / EdgeMP / DownEdgeMP (nn/blocks.py:175-186,322-333,360-381):
         e' = msg_mlp([e | s[row] | v[col]]);  agg = reduce(e' -> col);  v' = act(upd_mlp([agg | v])).
     Returns (v', e') where e' is stored WITHOUT the activation: the aggregation consumes the raw
@@ -709,6 +725,9 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
     `compact_v` (rounded-bf16 mode; the caller guarantees that v' is only ever read as an input block of the next layer's update MLP, which
     rounds it to bf16 on load — EdgeMP's edge latents between consecutive EdgeMPs of a level): v' comes back as bf16 rows (feature order),
     the same operand at half the bytes in both launches.
+    `bounds` (ops.RangeBounds; the fp16 range proof of the f16x3 launches): in — what the caller has proven about |v|, |e| as stored and
+    |products|; out — the same for v', e' and the next layer's products.  The caller owns it and passes it from block to block beside
+    the tensors; without one (a user's tensors) nothing is known and every launch is range-tracked.
     `n_targets` / `v_out` (partitioned sub-meshes, partition_remus.py): only the first `n_targets` rows of `v` are targets (the
     rows behind them are halo rows, read as senders only); v' for those rows is written into `v_out`."""
     if aggr not in ("mean", "sum", "add"):
@@ -719,10 +738,14 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
     ep, csr = plan.edge_csr(index, n_t)
     senders = v if v_src is None else v_src
     mean = aggr == "mean"
-    e_src = e if isinstance(e, Source) else Source(e, pre_act=e_pre_act)
+    rb = bounds if bounds is not None else ops.RangeBounds()
+    e_src = e if isinstance(e, Source) else Source(e, pre_act=e_pre_act, bound=rb.e)
     if next_graph is None and _can_fuse_layer(msg_mlp, upd_mlp, v, e, index, csr, v_src, n_targets, v_out, compact_messages):
-        v_new, e_new, nxt = _fused_layer(msg_mlp, upd_mlp, v, e_src, ep, csr, mean, act_code, products, next_msg, keep_e)
+        v_new, e_new, nxt = _fused_layer(msg_mlp, upd_mlp, v, e_src, ep, csr, mean, act_code, products, next_msg, keep_e, rb)
         return (v_new, e_new, nxt) if next_msg is not None else (v_new, e_new)
+    # (the gathered node rows: senders, receivers; the products the caller handed in)
+    hoist_kw = dict(gathered_bounds=[rb.v if v_src is None else None, rb.v], product_bounds=rb.products)
+    v_in = Source(v, bound=rb.v)
     if ops.can_fuse_aggregation(csr, msg_mlp.output_size):
         # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_io_t.agg):
         # no second pass over the messages; with keep_e=False (the model discards e', nn/mus_gnn.py:199-200) they are not
@@ -741,21 +764,25 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
                 agg = agg16
         if agg is None:
             agg = torch.empty((csr.n_seg, msg_mlp.output_size), dtype=torch.float32, device=v.device)
-        e_new = msg_mlp.run_hoisted([e_src], gathered, ep.n_edges, products=products, agg=(csr, agg, mean), **kw)
-        agg_src = Source(ops.RsOrderedRows.tag(agg) if agg.dtype == torch.bfloat16 else agg)
+        e_new = msg_mlp.run_hoisted([e_src], gathered, ep.n_edges, products=products, agg=(csr, agg, mean), **hoist_kw, **kw)
+        rb.e = ops.take_bounds().out
+        agg_src = Source(ops.RsOrderedRows.tag(agg) if agg.dtype == torch.bfloat16 else agg, bound=ops.agg_bound(rb.e, csr, mean))
     elif ops.can_aggregate_on_load(csr, msg_mlp.output_size, [msg_mlp.output_size, int(v.size(1))]):
         # the node launch averages each target's messages while it gathers its input (g4c_src_t.seg_off): no separate
         # aggregation pass, no aggregate written to / re-read from HBM
-        e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges, products=products)
-        agg_src = Source(e_new, segments=csr, seg_mean=mean)
+        e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges, products=products, **hoist_kw)
+        rb.e = ops.take_bounds().out
+        agg_src = Source(e_new, segments=csr, seg_mean=mean, bound=rb.e)
     elif ops.grad_mode():
         e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges)
+        rb.e = None
         agg_src = Source(ops.segment_reduce(e_new, csr, mean))
     else:
         agg = torch.empty((csr.n_seg, msg_mlp.output_size), dtype=torch.float32, device=v.device)
         e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges,
-                                    products=products, agg=(csr, agg, mean))
-        agg_src = Source(agg)
+                                    products=products, agg=(csr, agg, mean), **hoist_kw)
+        rb.e = ops.take_bounds().out
+        agg_src = Source(agg, bound=ops.agg_bound(rb.e, csr, mean))
     v16 = (compact_v and compact_latents_now(upd_mlp.output_size) and upd_mlp.fits_one_launch() and n_targets is None and v_out is None
            and ops.effective_precision([128, int(v.size(1))]) == "bf16")
     if next_msg is not None:
@@ -763,15 +790,20 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
         nx_rows, nx_csr = (ep.n_edges, csr) if next_graph is None else next_graph
         if nx_rows >= HOIST_MIN_ROWS:        # the consumer will hoist: give it its node-side terms from this launch
             w = upd_mlp.output_size          # (width of v', the node input of the next layer's message MLP)
-            nxt = upd_mlp.run_with_heads([agg_src, Source(v)], int(v.size(0)), act_code, next_msg,
+            nxt = upd_mlp.run_with_heads([agg_src, v_in], int(v.size(0)), act_code, next_msg,
                                          next_msg.input_size - 2 * w, [w, w], rs_rows=next_msg.rs1_ready(nx_rows, nx_csr),
                                          out=torch.empty((int(v.size(0)), 128), dtype=torch.bfloat16, device=v.device) if v16 else None)
         if nxt is None:
             out16 = torch.empty((int(v.size(0)), 128), dtype=torch.bfloat16, device=v.device) if v16 else None
-            return upd_mlp.run_coded([agg_src, Source(v)], int(v.size(0)), act_code, out=out16), e_new, None
+            v_new = upd_mlp.run_coded([agg_src, v_in], int(v.size(0)), act_code, out=out16)
+            rb.v, rb.products = ops.take_bounds().out, None
+            return v_new, e_new, None
+        lb = ops.take_bounds()
+        rb.v, rb.products = lb.out, lb.heads
         return nxt[0], e_new, nxt[1]
-    v_new = upd_mlp.run_coded([agg_src, Source(v)], n_t, act_code,
+    v_new = upd_mlp.run_coded([agg_src, v_in], n_t, act_code,
                               out=torch.empty((n_t, 128), dtype=torch.bfloat16, device=v.device) if v16 else v_out)
+    rb.v, rb.products = ops.take_bounds().out, None
     return v_new, e_new
 
 
@@ -821,11 +853,12 @@ class GNBlock(nn.Module):
                 m.reset_parameters()
 
     def step(self, v: Tensor, e: Tensor, edge_index: Tensor, act_code: int, e_pre_act: int = _lib.ACT_NONE,
-             products: Optional[Sequence[Tensor]] = None, next_msg: Optional[MLP] = None, keep_e: bool = True):
+             products: Optional[Sequence[Tensor]] = None, next_msg: Optional[MLP] = None, keep_e: bool = True,
+             bounds: Optional[ops.RangeBounds] = None):
         """Internal form used by the model programs: returns (act(v'), raw e') — and, when `next_msg` (the edge MLP of
-        the next MP layer on the same graph) is given, a third value: that layer's `products` or None (see _mp_step)."""
+        the next MP layer on the same graph) is given, a third value: that layer's `products` or None (see _mp_step; `bounds` too)."""
         return _mp_step(self.edge_mlp, self.node_mlp, v, e, edge_index, self.aggr, act_code, e_pre_act,
-                        products=products, next_msg=next_msg, keep_e=keep_e)
+                        products=products, next_msg=next_msg, keep_e=keep_e, bounds=bounds)
 
     def forward(self, v: Tensor, e: Tensor, edge_index: Tensor, *, activation=None) -> Tuple[Tensor, Tensor]:
         return _public_mp(self.edge_mlp, self.node_mlp, v, e, edge_index, self.aggr, activation)
@@ -856,19 +889,24 @@ class DownMP(nn.Module):
                 item.reset_parameters()
 
     def pool(self, graph: Graph, field: Tensor, edge_index: Tensor, edge_attr: Tensor, activation=None,
-             e_pre_act: int = _lib.ACT_NONE, target_major: bool = False):
+             e_pre_act: int = _lib.ACT_NONE, target_major: bool = False, bounds: Optional[ops.RangeBounds] = None):
         """Functional core: returns (field_l, edge_index_l, edge_attr_l) without touching the Graph.
-        `e_pre_act`: activation still pending on `edge_attr` (applied while pooling)."""
+        `e_pre_act`: activation still pending on `edge_attr` (applied while pooling).
+        `bounds` (_mp_step): |field|, |edge_attr| in; |field_l|, |edge_attr_l| out — both are means over rows, which keep a bound."""
+        rb = bounds if bounds is not None else ops.RangeBounds()
         h, l = self.hr_graph_idx, self.lr_graph_idx
         rel = getattr(graph, f'e_{h}{l}')
         csr = plan.cluster_plan(getattr(graph, f'cluster_{l}'), getattr(graph, f'mask_{l}'))
-        m = self.down_mlp.run([Source(rel), Source(field)], int(field.size(0)))
+        m = self.down_mlp.run([Source(rel), Source(field, bound=rb.v)], int(field.size(0)))
+        m_bound = ops.take_bounds().out
         code = _lib.act_code(activation)
         pooled = ops.segment_reduce(m, csr, True, _lib.ACT_NONE if code is None else code)
         pooled = _finish(pooled, activation, code)
         # (target_major: the models' internal coarse edge order, see plan.pool_edge_plan; the public forward keeps `coalesce` order)
         pp = plan.pool_edge_plan(getattr(graph, f'idx{h}_to_idx{l}'), edge_index, target_major)
         ea_l = ops.segment_reduce(edge_attr, pp.csr, True, src_act=e_pre_act)
+        rb.v = ops.act_bound(m_bound, code) if (activation is None or code is not None) else None
+        rb.e, rb.products = ops.act_bound(rb.e, e_pre_act), None
         return pooled, pp.edge_index, ea_l
 
     def forward(self, graph: Graph, activation: Optional[Callable] = None) -> Graph:
@@ -898,11 +936,14 @@ class UpMP(nn.Module):
             if hasattr(item, 'reset_parameters'):
                 item.reset_parameters()
 
-    def sources(self, graph: Graph, field_lr: Tensor, field_hr_old: Tensor) -> List[Source]:
-        """Input blocks of up_mlp: [-e_hl | field_l[parent] | field_hr_old]; the sign flip is folded into the packed weights."""
+    def sources(self, graph: Graph, field_lr: Tensor, field_hr_old: Tensor,
+                bounds: Tuple[Optional[float], Optional[float]] = (None, None)) -> List[Source]:
+        """Input blocks of up_mlp: [-e_hl | field_l[parent] | field_hr_old]; the sign flip is folded into the packed weights.
+        `bounds`: what the caller has proven about (|field_lr|, |field_hr_old|) (Source.bound)."""
         h, l = self.hr_graph_idx, self.lr_graph_idx
         parent = plan.index32(getattr(graph, f'idx{h}_to_idx{l}'))
-        return [Source(getattr(graph, f'e_{h}{l}'), negate=True), Source(field_lr, parent), Source(field_hr_old)]
+        return [Source(getattr(graph, f'e_{h}{l}'), negate=True), Source(field_lr, parent, bound=bounds[0]),
+                Source(field_hr_old, bound=bounds[1])]
 
     def unpool(self, graph: Graph, field_lr: Tensor, field_hr_old: Tensor, activation=None) -> Tensor:
         return self.up_mlp.run(self.sources(graph, field_lr, field_hr_old), int(field_hr_old.size(0)), activation=activation)

@@ -82,29 +82,38 @@ class _MuSGNN(GNN):
         e = ops.static_launch("edge_encoder", [graph.edge_attr],
                               lambda: self.edge_encoder.run_coded([Source(graph.edge_attr)], int(graph.edge_attr.size(0)), SELU))
         # `products`: first-layer node-side terms of the next MP layer, when the launch producing its `v` made them
+        # `rb`: what is proven about |v|, |e| (as stored) and |products| at this point of the program — the fp16 range proof of the
+        # f16x3 launches (ops.RangeBounds), handed from block to block beside the tensors.  The encoders read data and have no
+        # LayerNorm: their outputs carry no bound, and the launches that read them stay range-tracked.
+        rb = ops.RangeBounds(e=ops.take_bounds().out)
         v, products = self._launch_for(self.node_encoder, inputs, n, SELU, 0, edge_index)
+        lb = ops.take_bounds()
+        rb.v, rb.products = lb.out, (lb.heads if products is not None else None)
         e_pending = NONE          # activation not yet applied to `e` (deferred to its readers)
         stash = []
         prog = self._PROGRAM
         for k, name in enumerate(prog):
             block = getattr(self, name)
             if name.startswith("down_mp"):
-                stash.append((v, edge_index, e, e_pending))
-                v, edge_index, e = block.pool(graph, v, edge_index, e, torch.tanh, e_pre_act=e_pending, target_major=True)
+                stash.append((v, edge_index, e, e_pending, rb.v, rb.e))
+                v, edge_index, e = block.pool(graph, v, edge_index, e, torch.tanh, e_pre_act=e_pending, target_major=True, bounds=rb)
                 e_pending, products = NONE, None
             elif name.startswith("up_mp"):
-                v_old, edge_index, e, e_pending = stash.pop()
-                v, products = self._launch_for(block.up_mlp, block.sources(graph, v, v_old), int(v_old.size(0)), TANH, k + 1, edge_index)
+                v_old, edge_index, e, e_pending, v_old_bound, rb.e = stash.pop()
+                v, products = self._launch_for(block.up_mlp, block.sources(graph, v, v_old, (rb.v, v_old_bound)), int(v_old.size(0)), TANH,
+                                               k + 1, edge_index)
+                lb = ops.take_bounds()
+                rb.v, rb.products = lb.out, (lb.heads if products is not None else None)
             else:
                 nxt = prog[k + 1] if k + 1 < len(prog) else ""
                 if nxt.startswith("mp"):      # next MP layer runs on the same graph: its node-side products ride along
                     v, e, products = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products,
-                                                next_msg=getattr(self, nxt).edge_mlp)
+                                                next_msg=getattr(self, nxt).edge_mlp, bounds=rb)
                 else:
                     # the level's edge latents are dropped after this layer when an UpMP or the decoder follows (the up leg
                     # restores the latents stashed before the DownMP): they then need not be stored
                     drop_e = nxt.startswith("up_mp") or nxt == ""
-                    v, e = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products, keep_e=not drop_e)
+                    v, e = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products, keep_e=not drop_e, bounds=rb)
                     products = None
                 e_pending = SELU
         nf = self.num_fields

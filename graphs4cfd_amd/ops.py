@@ -87,12 +87,14 @@ class StaticCache:
     def get(self, name: str, inputs: Sequence[Tensor], fn):
         key = (weights_epoch(), mlp_precision()) + tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in inputs)
         hit = self.store.get(name)
+        global _last_bounds
         if hit is not None and hit[0] == key:
             self.hits += 1
+            _last_bounds = hit[3]          # (what take_bounds() would have answered behind the launch: same weights epoch, same inputs)
             return hit[1]
         self.misses += 1
         val = fn()
-        self.store[name] = (key, val, tuple(inputs))      # (the inputs are kept alive: the key holds their addresses)
+        self.store[name] = (key, val, tuple(inputs), _last_bounds)      # (the inputs are kept alive: the key holds their addresses)
         return val
 
     def stale(self) -> bool:
@@ -101,7 +103,7 @@ class StaticCache:
         and falls back to one eager step (which recomputes the entry) + a new capture — ADVICE r04: a replay must not keep reading
         latents of an `edge_attr` that was edited since."""
         head = (weights_epoch(), mlp_precision())
-        for key, _, inputs in self.store.values():
+        for key, _, inputs, _ in self.store.values():
             if key != head + tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in inputs):
                 return True
         return False
@@ -138,11 +140,11 @@ def _ld(t: Tensor) -> int:
 class Source:
     """One column block of a virtually concatenated MLP input."""
 
-    __slots__ = ("tensor", "index", "col0", "width", "negate", "pre_act", "additive", "segments", "seg_mean")
+    __slots__ = ("tensor", "index", "col0", "width", "negate", "pre_act", "additive", "segments", "seg_mean", "bound")
 
     def __init__(self, tensor: Tensor, index: Optional[Tensor] = None, col0: int = 0, width: Optional[int] = None,
                  negate: bool = False, pre_act: int = _lib.ACT_NONE, additive: bool = False,
-                 segments: Optional[CsrPlan] = None, seg_mean: bool = True):
+                 segments: Optional[CsrPlan] = None, seg_mean: bool = True, bound: Optional[float] = None):
         # (bf16 rows: the message tensors a fused-aggregation launch stored in the rounded-bf16 mode, mlp_forward(rows_dtype=);
         # only as a plain 128-wide block of a launch in that mode — the C entry point checks)
         self.tensor = _bf16_2d(tensor) if tensor.dtype == torch.bfloat16 else _f32_2d(tensor, "source")
@@ -157,6 +159,10 @@ class Source:
         # scatter(pre_act(tensor), col, reduce) without materialising it
         self.segments = segments
         self.seg_mean = seg_mean
+        # proven bound on |value| of the STORED rows (before `pre_act`), or None = unknown.  Set only by the code that has just launched
+        # the producer of `tensor`, from that launch's weights (take_bounds); it belongs to this use of the tensor, not to the tensor —
+        # nothing survives an in-place edit or a slice that way.  A tensor a user hands in has none, and its launches are range-tracked.
+        self.bound = bound
         if segments is not None and (index is not None or additive or self.width != 128):
             raise ValueError("aggregation on load needs a 128-wide block without gather index")
 
@@ -463,6 +469,162 @@ def check_f16_range(device: Optional[torch.device] = None, where: str = "", site
     return hit
 
 
+# ---- pack-time range proof.  Almost every value the V-cycle converts to fp16 is SELU(LayerNorm(.)) or a bounded linear image of such
+# values, so a bound far below 65504 follows from the weights alone.  PackedMLP reads the norms of its weights back once, when the image
+# is packed (PackedMLP.norms: recomputed exactly when the image is rebuilt); a launch joins them with the bounds its Sources carry
+# (range_bounds) and, when the proof succeeds, passes g4c_mlp_t.range_certified: the library then runs the kernel instantiation without
+# the range tracker.  Everything here is host arithmetic on Python floats (fp64): no device synchronisation per launch.
+RANGE_PROOFS = True                     # (tests / A-B: False tracks every launch, as before)
+SELU_SCALE = 1.0507009873554804934193349852946
+SELU_FLOOR = 1.0507009873554804934193349852946 * 1.6732632423543772848170429916717       # |selu(x)| < scale * alpha for x < 0
+F16_RANGE_END = 65504.0
+
+
+def act_bound(bound: Optional[float], act: int) -> Optional[float]:
+    """Bound on |act(x)| given |x| <= bound (None: unknown).  tanh is bounded whatever its argument."""
+    if act == _lib.ACT_TANH:
+        return 1.0
+    if bound is None:
+        return None
+    if act == _lib.ACT_SELU:          # x >= 0: scale * x;  x < 0: inside (-scale * alpha, 0)
+        return max(SELU_SCALE * bound, SELU_FLOOR)
+    return bound
+
+
+def certifies(converted_bound: Optional[float]) -> bool:
+    """The certificate is given only when TWICE the bound stays below the end of fp16's range: the bound is on the exactly computed
+    activations, the kernels convert the f16x3-computed ones, which differ from them by ~1e-6 relative — a factor 2 covers that (and
+    the rounding of this fp64 evaluation) many times over."""
+    return converted_bound is not None and converted_bound == converted_bound and 2.0 * converted_bound < F16_RANGE_END
+
+
+def weight_norms(weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], ln: Optional[Tuple[Tensor, Tensor, float]],
+                 heads: Sequence[Tensor], seg_widths: Sequence[int], narrow: Optional[Sequence[bool]] = None) -> dict:
+    """The norms range_bounds needs, evaluated in fp64 where the weights live and read back in ONE copy (an image is packed in an eager
+    step, never inside a capture): per weighted (not narrow) input block of the first layer, per later layer and per head the largest
+    row sum of |W|; max|b| per layer; max|gamma|, max|beta| of the LayerNorm."""
+    narrow = tuple(bool(x) for x in narrow) if narrow is not None else (False,) * len(seg_widths)
+
+    def rowsum(W: Tensor) -> Tensor:
+        return W.detach().to(torch.float64).abs().sum(1).max()
+    W0, dev = weights[0], weights[0].device
+    vals, col0, n_wide = [], 0, 0
+    for w_, nar in zip(seg_widths, narrow):
+        if not nar:
+            vals.append(rowsum(W0[:, col0:col0 + int(w_)]))
+            n_wide += 1
+        col0 += int(w_)
+    vals += [rowsum(W) for W in weights[1:]]
+    vals += [rowsum(W) for W in heads]
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    vals += [zero if b is None else b.detach().to(torch.float64).abs().max() for b in biases]
+    if ln is not None:
+        vals += [ln[0].detach().to(torch.float64).abs().max(), ln[1].detach().to(torch.float64).abs().max()]
+    it = iter(torch.stack(vals).cpu().tolist())
+    nl, nh = len(weights), len(heads)
+    norms = {"w0": [next(it) for _ in range(n_wide)], "w": [next(it) for _ in range(nl - 1)], "heads": [next(it) for _ in range(nh)],
+             "b": [next(it) for _ in range(nl)]}
+    norms["ln"] = (next(it), next(it)) if ln is not None else None
+    norms["n_out"] = int(weights[-1].size(0))
+    norms["narrow"] = any(narrow)
+    return norms
+
+
+class LaunchBounds:
+    """What the range proof of one launch gives: `converted` — bound on every value the launch converts to fp16 (None: no proof),
+    `out` — bound on its output rows (after LayerNorm / activation), `heads` — bounds on its head rows, `e` (mp_layer_forward only:
+    `out` is v' there) — bound on the message rows; None where unknown."""
+    __slots__ = ("converted", "out", "heads", "e")
+
+    def __init__(self, converted=None, out=None, heads=None, e=None):
+        self.converted, self.out, self.heads, self.e = converted, out, heads, e
+
+    def head(self, j: int) -> Optional[float]:
+        return None if self.heads is None else self.heads[j]
+
+
+def range_bounds(norms: Optional[dict], sources: Sequence["Source"], act: int, residual: bool = False,
+                 seg_len: Optional[int] = None) -> LaunchBounds:
+    """The proof for one launch of an MLP with the weight norms `norms` (PackedMLP.norms) on `sources`.
+      input that is converted:   act_bound(source.bound, source.pre_act); a mean over rows keeps it, a sum multiplies it by the
+                                 longest segment (`seg_len`; unknown: no proof);
+      additive rows:             their bound enters layer 0's pre-activation;
+      layer l:                   B_l = (largest row sum of |W_l|) . B_{l-1} + max|b_l| (+ additive rows, l = 0); SELU(B_l) is converted
+                                 for every layer but the last;
+      output rows:               LayerNorm: |y| <= sqrt(n - 1) max|gamma| + max|beta| whatever goes in, else B_last; then `act`;
+      heads:                     the output row is converted; head h <= (largest row sum of |W_h|) . out.
+    Unknown producers (a source without a bound), narrow blocks multiplied on the vector ALUs, and arithmetics other than f16x3
+    (norms None) give no proof."""
+    if norms is None:
+        return LaunchBounds()
+    proof = not norms["narrow"]
+    b0, j = norms["b"][0], 0
+    converted = 0.0
+    for s_ in sources:
+        if s_.additive:
+            if s_.bound is None:
+                proof = False
+            else:
+                b0 += s_.bound
+            continue
+        xb = act_bound(s_.bound, s_.pre_act)
+        if xb is not None and s_.segments is not None and not s_.seg_mean:
+            xb = None if seg_len is None else xb * seg_len
+        if xb is None or j >= len(norms["w0"]):
+            proof = False
+        else:
+            converted = max(converted, xb)
+            b0 += norms["w0"][j] * xb
+        j += 1
+    n_layers = len(norms["b"])
+    pre = b0 if proof else None          # bound of the current layer's pre-activation
+    for l in range(1, n_layers):
+        if pre is not None:
+            hid = act_bound(pre, _lib.ACT_SELU)
+            converted = max(converted, hid)
+            pre = norms["w"][l - 1] * hid + norms["b"][l]
+    if norms["ln"] is not None:
+        g, be = norms["ln"]
+        raw = (norms["n_out"] - 1) ** 0.5 * g + be
+    else:
+        raw = pre
+    out = act_bound(raw, act)
+    heads = None
+    if norms["heads"]:
+        if out is None:
+            proof = False
+        else:
+            converted = max(converted, out)
+            heads = [h * out for h in norms["heads"]]
+    return LaunchBounds(converted if proof else None, None if residual else out, heads)
+
+
+_last_bounds: Optional[LaunchBounds] = None
+
+
+def take_bounds() -> LaunchBounds:
+    """The proof of the launch that has just been issued through mlp_forward / mp_layer_forward, handed out ONCE: the caller that builds
+    the next launch's Source from the tensor it has just received asks here, right behind the call.  Every launch entry point clears
+    it first, so a stale answer is never anything but "unknown"."""
+    global _last_bounds
+    got, _last_bounds = _last_bounds, None
+    return got if got is not None else LaunchBounds()
+
+
+class RangeBounds:
+    """The bounds that travel with the latents of one forward, beside the tensors and never on them: of the node latents `v`, of the
+    edge latents `e` as stored (their pending activation not applied) and of the hoisted `products`.  A model's forward owns one and
+    hands it to its blocks, which read their inputs' bounds from it and leave their outputs' bounds in it; a block called without one
+    (GNBlock.forward(v, e, ...) on a user's tensors) knows nothing about its inputs."""
+    __slots__ = ("v", "e", "products")
+
+    def __init__(self, v: Optional[float] = None, e: Optional[float] = None, products: Optional[Sequence[Optional[float]]] = None):
+        self.v, self.e, self.products = v, e, products
+
+    def product(self, j: int) -> Optional[float]:
+        return None if self.products is None else self.products[j]
+
+
 _weights_epoch = 0
 
 
@@ -752,6 +914,8 @@ class PackedMLP:
             self.desc.ln_gamma, self.desc.ln_beta, self.desc.ln_eps = None, None, 0.0
         self.seg_widths = tuple(seg_widths)
         self.device = dev
+        # (the range proof's half of the image: rebuilt with it, under the same cache key — MLP._image)
+        self.norms = weight_norms(weights, biases, ln, heads, seg_widths, narrow) if self.split == "f16x2" else None
         # the parameter tensors this image was packed from (the training path differentiates with respect to them: autograd.py)
         self.params = (list(weights), list(biases), ln)
         self.heads_params = bool(heads)
@@ -767,6 +931,20 @@ def _src_array(sources: Sequence[Source]):
         if s.segments is not None:
             a.seg_off, a.seg_mean, a.seg_perm = _lib.ptr(s.segments.off), 1 if s.seg_mean else 0, _lib.ptr(s.segments.perm)
     return arr
+
+
+def agg_bound(bound: Optional[float], csr: CsrPlan, mean: bool) -> Optional[float]:
+    """Bound on an aggregate of rows bounded by `bound`: a mean keeps it, a sum multiplies it by the plan's longest segment."""
+    return bound if (bound is None or mean) else bound * max(csr.max_deg, 1)
+
+
+def _certify(packed: "PackedMLP", sources: Sequence[Source], act: int, residual: bool, tracked: bool) -> LaunchBounds:
+    """The range proof of the launch that is about to be issued; sets the certificate of its descriptor (g4c_mlp_t.range_certified)
+    for this launch.  `tracked`: the launch keeps its tracker whatever the proof says (save / mul: the training forms)."""
+    seg_len = max((s_.segments.max_deg for s_ in sources if s_.segments is not None), default=None)
+    lb = range_bounds(packed.norms, sources, act, residual, seg_len)
+    packed.desc.range_certified = 1 if (RANGE_PROOFS and not tracked and certifies(lb.converted)) else 0
+    return lb
 
 
 def _agg_mode(agg_mean: bool, csr: CsrPlan) -> int:
@@ -799,12 +977,15 @@ def _run(packed: PackedMLP, arr, n_src: int, n_rows: int, io, dev, flops: float,
 
 def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr: CsrPlan, agg_mean: bool, upd: PackedMLP,
                      v: Tensor, act: int, store_rows: bool = True, head_outs: Optional[Sequence[Tensor]] = None,
-                     v_out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor, Optional[Sequence[Tensor]]]:
+                     v_out: Optional[Tensor] = None, v_bound: Optional[float] = None) -> Tuple[Optional[Tensor], Tensor, Optional[Sequence[Tensor]]]:
     """One launch for a whole MP layer (g4c_mlp_io_t.upd; reference nn/blocks.py:175-186): the hoisted message MLP `msg`
     on `sources` (one 128-wide weighted block + the two gathered node-side products as additive sources) with the aggregation over
     `csr`, and — in the same persistent workgroups — the node MLP `upd` on [aggregate | v] with LayerNorm / `act` and, when
     `head_outs` is given, the heads packed behind `upd` (the next layer's products).  f16x3 arithmetic only, inference only.
-    Returns (e' rows or None, v', head_outs)."""
+    `v_bound`: proven bound on |v| (Source.bound), for the node MLP's half of the range proof.
+    Returns (e' rows or None, v', head_outs); take_bounds() then answers for v' (`out`), the heads and e' (`e`)."""
+    global _last_bounds
+    _last_bounds = None
     dev = _lib.require_hip(*[s.tensor for s in sources], *[s.index for s in sources], v, v_out)
     if msg.split != "f16x2" or upd.split != "f16x2":
         raise NotImplementedError("mp_layer_forward needs both MLPs packed for the f16x3 arithmetic")
@@ -825,7 +1006,15 @@ def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr
     if n_heads:
         _set_heads(io, head_outs)
     in_b = 4.0 * 128 * (n_rows * (2 if store_rows else 1) + n_t * (2 + n_heads))
-    _run(msg, _src_array(sources), len(sources), n_rows, io, dev, msg.flops_per_row * n_rows + upd.flops_per_row * n_t, in_b)
+    # the range proof of both halves: the node MLP reads [aggregate of e' | v], and `v_bound` is what the caller knows about v.  The
+    # library drops the trackers only when BOTH descriptors are certified.
+    lb_msg = _certify(msg, sources, _lib.ACT_NONE, False, False)
+    lb_upd = _certify(upd, [Source(agg, bound=agg_bound(lb_msg.out, csr, agg_mean)), Source(v, bound=v_bound)], act, False, False)
+    try:
+        _run(msg, _src_array(sources), len(sources), n_rows, io, dev, msg.flops_per_row * n_rows + upd.flops_per_row * n_t, in_b)
+    finally:
+        msg.desc.range_certified = upd.desc.range_certified = 0          # (the certificates were for this launch: the descriptors are shared)
+    _last_bounds = LaunchBounds(None, lb_upd.out, lb_upd.heads, e=lb_msg.out)
     return e_out, v_out, head_outs
 
 
@@ -850,6 +1039,8 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
     on load, applied before the one rounding (G4C_DTYPE_BF16_SELU); the aggregate is taken from the un-activated fp32 rows.  Check
     `out.dtype == torch.bfloat16` on the result to know whether the rows came back compact and activated.
     With gradients enabled and a differentiable input / parameter, the call is recorded for autograd (autograd.py)."""
+    global _last_bounds
+    _last_bounds = None
     if torch.is_grad_enabled():
         from . import autograd as _ag
         if _ag.wants_grad(packed, sources, resid):
@@ -963,7 +1154,13 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
             io.mul[:len(mul)] = [_lib.ptr(t) for t in mul]
             io.mul_ld = _ld(lm[0]) if lm else 128
         nbytes = 4.0 * (sum(packed.seg_widths) + packed.n_out + 128 * len(live)) * n_rows
-    _run(packed, arr, len(sources), n_rows, io, dev, packed.flops_per_row * row_count, nbytes)
+    # (a residual adds data to the rows; an output index or a row sub-range writes only some rows of `out`: no bound for the tensor)
+    lb = _certify(packed, sources, act, resid is not None or out_idx32 is not None or rows is not None, save is not None)
+    try:
+        _run(packed, arr, len(sources), n_rows, io, dev, packed.flops_per_row * row_count, nbytes)
+    finally:
+        packed.desc.range_certified = 0          # (the certificate was for this launch: the descriptor is shared)
+    _last_bounds = lb
     if reduce_after is not None:
         segment_reduce(out, reduce_after[0], reduce_after[2], out=reduce_after[1])
     return out

@@ -149,6 +149,14 @@ typedef struct {
     int32_t n_out;                   /* true output width of the last layer */
     int32_t w_format;                /* G4C_WFMT_*: the stream's layout and the arithmetic of every launch of this MLP */
     int32_t range_slot;              /* >= 0: the word of g4c_mlp_io_t.range_flag a clip in a launch of this MLP is reported in */
+    /* The caller's range certificate for the launch this descriptor is passed to (G4C_WFMT_F16X2 only; 0 = unknown, the default):
+     * non-zero states that NO value the launch converts to fp16 for this MLP — its weighted inputs after their activation on load,
+     * every hidden activation, and with heads the final output row — can reach the end of fp16's range, whatever the input data.
+     * That is a proof obligation of the caller (bounds of the producers of its inputs joined with the norms of these weights:
+     * graphs4cfd_amd/ops.py range_bound), not something the library checks.  When every MLP of the launch (mlp, and upd if given) is
+     * certified and io->save / io->mul are not in use, the library may run an instantiation without the range tracker, and the launch
+     * NEVER WRITES its words of io->range_flag; otherwise the field is ignored and the launch is tracked as before. */
+    int32_t range_certified;
 } g4c_mlp_t;
 
 /* Weight formats (g4c_mlp_t.w_format, g4c_mlp_pack_layer).  All take fp32 in and give fp32 out.
@@ -278,7 +286,8 @@ typedef struct {
      * (and range_flag[upd->range_slot]) when an MLP input or a hidden activation it converted to fp16 reached the end of fp16's range
      * (|x| >= 65504: the value was CLIPPED there) — never written otherwise, never cleared by the library.  The reference computes in
      * fp32 (nn/model.py:303-321), so a set word means the result may differ from it: rerun with the bf16x3 stream (fp32 exponent
-     * range).  The array belongs to the caller of the launch, like every other output here: each consumer can pass its own. */
+     * range).  The array belongs to the caller of the launch, like every other output here: each consumer can pass its own.
+     * A launch whose MLPs all carry g4c_mlp_t.range_certified (without save / mul) writes nothing here. */
     int32_t *range_flag;
 } g4c_mlp_io_t;
 
@@ -311,7 +320,9 @@ int g4c_mlp_small_launch_tiles(int n_tiles);
  * row count), so a profiler-free caller that times launches with events (bench.py's roofline leg) can label them by the kernel that
  * executed: G4C_KERNEL_NONE (no launch yet, or the last call launched nothing), _MLP_SPLIT (mlp_split_kernel: fp32 MFMA), _MLP_BX6
  * (mlp_bx6_kernel: split-operand tile kernel), _MLP_BX6I (mlp_bx6i_kernel: dual-tile), _MLP_WS (mlp_ws_kernel: weight-stationary
- * persistent), _MLP_RS / _MLP_RS2 (mlp_rs1_kernel / mlp_rs2_kernel: the row-split formats). */
+ * persistent), _MLP_RS / _MLP_RS2 (mlp_rs1_kernel / mlp_rs2_kernel: the row-split formats), _MLP_BX6_CERT / _MLP_WS_CERT (the
+ * instantiations of mlp_bx6_kernel / mlp_ws_kernel WITHOUT the fp16 range tracker: a launch with g4c_mlp_t.range_certified whose shape
+ * has one — a certified launch of any other shape reports the tracked kernel's code and runs it with no flag to write). */
 #define G4C_KERNEL_NONE 0
 #define G4C_KERNEL_MLP_SPLIT 1
 #define G4C_KERNEL_MLP_BX6 2
@@ -319,6 +330,8 @@ int g4c_mlp_small_launch_tiles(int n_tiles);
 #define G4C_KERNEL_MLP_WS 4
 #define G4C_KERNEL_MLP_RS 5
 #define G4C_KERNEL_MLP_RS2 6
+#define G4C_KERNEL_MLP_BX6_CERT 7
+#define G4C_KERNEL_MLP_WS_CERT 8
 int g4c_mlp_last_kernel(void);
 
 /* Tiles of whole segments for the fused aggregation (g4c_mlp_io_t.tile_rows / tile_seg): returns the tile count, -1 if a segment is
