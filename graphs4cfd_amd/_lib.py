@@ -26,6 +26,8 @@ KERNEL_MLP_BX6_CERT, KERNEL_MLP_WS_CERT = 7, 8      # the instantiations without
 KERNEL_NAMES = {0: "none", 1: "mlp_split_kernel", 2: "mlp_bx6_kernel", 3: "mlp_bx6i_kernel", 4: "mlp_ws_kernel", 5: "mlp_rs1_kernel", 6: "mlp_rs2_kernel",
                 7: "mlp_bx6_kernel", 8: "mlp_ws_kernel"}   # g4c_mlp_last_kernel
 
+TILE_SHAPE_GENERIC, TILE_SHAPE_NODE, TILE_SHAPE_UP, TILE_SHAPE_DOWN = 0, 1, 2, 3      # g4c_mlp_last_shape
+
 _ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "selu": ACT_SELU, "tanh": ACT_TANH}
 
 
@@ -96,6 +98,8 @@ _SIGNATURES = {
     "g4c_layer_norm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_debug_mean_div": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_mlp_last_kernel": (C.c_int, []),
+    "g4c_mlp_shapes_enable": (C.c_int, [C.c_int]),
+    "g4c_mlp_last_shape": (C.c_int, []),
     "g4c_project_to_edges": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_edge_scalar_to_node_vector": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,

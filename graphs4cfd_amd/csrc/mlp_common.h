@@ -101,6 +101,29 @@ struct Params {
     int range_certified;
 };
 
+// Compile-time launch shapes of the tile kernel (mlp_bx6_kernel<.., SH>, mlp_fused.hip): what a family of launches never varies, as
+// constants the kernel tests with `if constexpr` instead of interpreting Params per tile.  ID = g4c_mlp_last_shape()'s answer.
+// Common to every shape other than the generic one: N_SRC weighted sources of fp32 rows, 128 wide, 16-byte aligned, no aggregation on
+// load, no pending activation — the first gathered through an index when IDX0, every other direct; N_NAR narrow blocks (rows = the
+// tile's own); no additive blocks; N_LAYERS 128-wide layers + LayerNorm; plain fp32 output rows (no index, no residual, no fused
+// aggregation); N_HEADS fp32 heads.  The launcher (mlp_launch) picks a shape only when every one of these holds.
+//   TileShapeGeneric  nothing fixed: every field of Params is read at run time (the fallback of every launch no shape matches)
+//   TileShapeNode     the MP layers' node update: [aggregate | v], both direct
+//   TileShapeUp       UpMP's MLP: [-e (narrow) | v_coarse[parent] (indexed) | v_fine_old (direct)]
+//   TileShapeDown     DownMP's MLP: [e (narrow) | v (direct)]
+struct TileShapeGeneric {
+    static constexpr int ID = G4C_TILE_SHAPE_GENERIC;
+};
+template <int ID_, int NS, bool IDX0_, int NNAR, int NL, int NH>
+struct TileShape {
+    static constexpr int ID = ID_, N_SRC = NS, N_NAR = NNAR, N_LAYERS = NL, N_HEADS = NH;
+    static constexpr bool IDX0 = IDX0_;
+    static_assert(ID_ != G4C_TILE_SHAPE_GENERIC && NS >= 1 && NS <= 2 && (NL == 2 || NL == 3) && (NH == 0 || NH == 2), "tile shape out of range");
+};
+template <int NL, int NH> using TileShapeNode = TileShape<G4C_TILE_SHAPE_NODE, 2, false, 0, NL, NH>;
+template <int NL, int NH> using TileShapeUp = TileShape<G4C_TILE_SHAPE_UP, 2, true, 1, NL, NH>;
+template <int NL> using TileShapeDown = TileShape<G4C_TILE_SHAPE_DOWN, 1, false, 1, NL, 0>;
+
 // The node update fused behind the message launch of an MP layer (g4c_mlp_io_t.upd, mlp_ws_kernel<.., NODE>): after its
 // last tile pair a workgroup runs the node MLP ([aggregate | v] -> Linear/SELU chain -> LayerNorm -> activation, + heads) on the targets
 // whose aggregates it has just written.  Same depth as the message MLP; f16x3 stream; blocks of the stream in the order

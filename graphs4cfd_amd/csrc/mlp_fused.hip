@@ -136,7 +136,9 @@ __device__ __forceinline__ void mma_chunk_n(const float *pa, RingN<NCT> &g, cons
 
 // LayerNorm / activation / store of a finished 32-row tile held in sH; rows split over the NW waves of the workgroup.
 // Shared by the column-split kernels.  Needs: all waves' last-layer columns visible in sH (barrier done by the caller).
-template <int NW, int ROWS = 32>
+// PLAIN (the tile kernel's shaped instantiations, mlp_common.h TileShapeNode): LayerNorm present, 128 columns, fp32 rows stored by whole
+// 16-byte groups to their own row numbers — no column masks, no output index / residual / bf16 form.
+template <int NW, int ROWS = 32, bool PLAIN = false>
 __device__ __forceinline__ void split_finish(const Params &p, float *sH, const float *sGB, int wave, int lane, long long row0,
                                              long long mlim = -1) {
     if (mlim < 0) mlim = p.M;          // rows >= mlim are not stored (mlim < p.M: tiles of whole segments)
@@ -144,11 +146,11 @@ __device__ __forceinline__ void split_finish(const Params &p, float *sH, const f
     // ---------------------------------------------------------------- LayerNorm / activation: rows split over the waves
     // wave w owns rows [w*RPW, (w+1)*RPW); lane = part * RPW + row_local, each part = NC consecutive columns
     constexpr int RPW = ROWS / NW, PARTS = 64 / RPW, NC = NP / PARTS;
-    const int n_out = p.n_out;
+    const int n_out = PLAIN ? NP : p.n_out;
     const int rloc = lane % RPW, part = lane / RPW;
     const int myrow = wave * RPW + rloc;
     const int cb = part * NC;
-    if ((p.gamma || p.act) && !(G4C_ABLATE & 4)) {
+    if ((PLAIN || p.gamma || p.act) && !(G4C_ABLATE & 4)) {
         float *rowp = sH + myrow * HS + cb;
         const float inv_n = 1.0f / (float)n_out;
         float x[NC];
@@ -157,7 +159,7 @@ __device__ __forceinline__ void split_finish(const Params &p, float *sH, const f
             const f32x4 t = *reinterpret_cast<const f32x4 *>(rowp + c);
             x[c] = t[0]; x[c + 1] = t[1]; x[c + 2] = t[2]; x[c + 3] = t[3];
         }
-        if (p.gamma) {
+        if (PLAIN || p.gamma) {
             float sum = 0.f;
 #pragma unroll
             for (int c = 0; c < NC; ++c) sum += (cb + c < n_out) ? x[c] : 0.f;
@@ -204,9 +206,9 @@ __device__ __forceinline__ void split_finish(const Params &p, float *sH, const f
     // (each wave reads back only the rows it normalised itself: no barrier needed)
 
     // ---------------------------------------------------------------- store this wave's rows
-    if (p.out == nullptr) return;          // (only the aggregate of the rows is wanted: g4c_mlp_io_t.agg with out == NULL)
+    if (!PLAIN && p.out == nullptr) return;          // (only the aggregate of the rows is wanted: g4c_mlp_io_t.agg with out == NULL)
     const bool fast = (n_out == NP) && ((p.out_ld & 3) == 0) && (((uintptr_t)p.out & 15) == 0) && (p.resid == nullptr);
-    if (p.out_bf16) {
+    if (!PLAIN && p.out_bf16) {
         // rows kept in bf16 (the rounded-bf16 mode's message tensors: their consumer rounds them to bf16 anyway): 8 bytes per lane
         __bf16 *o16 = reinterpret_cast<__bf16 *>(p.out);
 #pragma unroll
@@ -221,6 +223,19 @@ __device__ __forceinline__ void split_finish(const Params &p, float *sH, const f
                 for (int u = 0; u < 4; ++u) b[u] = (__bf16)t[u];
                 *reinterpret_cast<bf16x4 *>(o16 + grow * p.out_ld + 4 * i) = b;
             }
+        }
+    } else if (PLAIN) {
+        // the tile's rows through a buffer descriptor of exactly the rows below mlim (base and extent scalar, a 32-bit lane offset):
+        // a row past mlim falls outside it and the hardware drops the store — no 64-bit row address, no branch per row
+        const int left = __builtin_amdgcn_readfirstlane((int)(mlim - row0 >= ROWS ? ROWS : (mlim - row0 > 0 ? mlim - row0 : 0)));
+        const int ld = p.out_ld;
+        float *const tb = p.out + (long long)__builtin_amdgcn_readfirstlane((int)row0) * ld;
+        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(tb, 0, left ? ((left - 1) * ld + NP) * 4 : 0, 0x00020000);
+#pragma unroll
+        for (int r = h; r < RPW; r += 2) {
+            const int row = wave * RPW + r;
+            const f32x4 t = *reinterpret_cast<const f32x4 *>(sH + row * HS + 4 * i);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), ro, (unsigned)(row * ld + 4 * i) * 4u, 0, 0);
         }
     } else if (fast) {
 #pragma unroll
@@ -567,7 +582,10 @@ constexpr int G4C_BX6_TUNE = 0;      // (1 = s_setprio around the MFMAs, 2 = no 
 // SWAP (the heads): the two MFMA operands trade places, so the accumulator comes out untransposed — a lane holds ONE output feature
 // (lane & 31 of the wave's 32-column slice) of the 16 sample rows 8 (q / 4) + 4 (lane / 32) + q % 4 — and a store instruction writes
 // 128 contiguous bytes of each of two rows (same products, same order of k inside the MFMA).
-template <int RT, int SP, bool SWAP = false, int RD6 = 2>
+// ZC (SP == 2): accumulation chains that START at zero in this block — bit 0: acc1, bit 1: acc.  Their first MFMA takes a zero C operand (an
+// inline constant; 0 + x is exact) instead of reading registers the caller had to clear with 16 moves each; the caller passes them
+// uninitialised.  The first group of steps is peeled off the rolled loop for it.
+template <int RT, int SP, bool SWAP = false, int RD6 = 2, int ZC = 0>
 __device__ __forceinline__ void mma_block_bx6(const __bf16 *pa, int plane, Ring6<RD6> &g, __amdgpu_buffer_rsrc_t rs, unsigned wofs, unsigned lo_b,
                                               f32x16 (&acc)[RT], f32x16 (&acc1)[RT]) {
     bf16x8 ah = *reinterpret_cast<const bf16x8 *>(pa), am = ah, al = ah;
@@ -575,9 +593,11 @@ __device__ __forceinline__ void mma_block_bx6(const __bf16 *pa, int plane, Ring6
     if (SP == 3) al = *reinterpret_cast<const bf16x8 *>(pa + 2 * plane);
     // ROLLED over groups of RD6 steps (ring slots are compile-time inside a group): unrolling all 8 steps lets hipcc give
     // every refill fresh registers, which costs a wave of occupancy
+    static_assert(ZC == 0 || SP == 2, "zero-start chains: the f16x3 products");
     unsigned so = wofs + 2u * RD6 * STEP6;          // byte offset of the step that refills slot 0 (RD6 steps ahead)
-#pragma unroll 1
-    for (int j = 0; j < 8 / RD6; ++j) {
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto group = [&](const int j, auto first_tag) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_tag)::value;          // the peeled first group of a block with zero-start chains
         const __bf16 *pj = pa + j * RD6 * 16;
         if (j == 8 / RD6 - 1) so = wofs + 2u * BLOCK6;      // the last group refills from the NEXT block's first steps
 #pragma unroll
@@ -610,14 +630,15 @@ __device__ __forceinline__ void mma_block_bx6(const __bf16 *pa, int plane, Ring6
                     acc[t][0] += (float)al[0] + (float)am[0] + (float)g.l[r][0] + (float)g.m[r][0];
                 }
                 if (SP == 2) {
+                    const bool z1 = FIRST && r == 0 && (ZC & 1), z0 = FIRST && r == 0 && (ZC & 2);
                     if (SWAP) {
-                        acc1[t] = mfma_f16(am, g.h[r], acc1[t]);
+                        acc1[t] = mfma_f16(am, g.h[r], z1 ? zero16 : acc1[t]);
                         acc1[t] = mfma_f16(ah, g.m[r], acc1[t]);
-                        acc[t] = mfma_f16(ah, g.h[r], acc[t]);
+                        acc[t] = mfma_f16(ah, g.h[r], z0 ? zero16 : acc[t]);
                     } else {
-                        acc1[t] = mfma_f16(g.h[r], am, acc1[t]);
+                        acc1[t] = mfma_f16(g.h[r], am, z1 ? zero16 : acc1[t]);
                         acc1[t] = mfma_f16(g.m[r], ah, acc1[t]);
-                        acc[t] = mfma_f16(g.h[r], ah, acc[t]);
+                        acc[t] = mfma_f16(g.h[r], ah, z0 ? zero16 : acc[t]);
                     }
                 } else
                 acc[t] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, g.h[r], acc[t], 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(g.h[r], ah, acc[t], 0, 0, 0);
@@ -633,6 +654,14 @@ __device__ __forceinline__ void mma_block_bx6(const __bf16 *pa, int plane, Ring6
             }
         }
         so += 2u * RD6 * STEP6;
+    };
+    if constexpr (ZC != 0) {
+        group(0, std::true_type{});
+#pragma unroll 1
+        for (int j = 1; j < 8 / RD6; ++j) group(j, std::false_type{});
+    } else {
+#pragma unroll 1
+        for (int j = 0; j < 8 / RD6; ++j) group(j, std::false_type{});
     }
 }
 
@@ -648,9 +677,16 @@ constexpr int G4C_F16_MINW = 4;
 // no column masks anywhere.
 // TRACK (SP = 2): the fp16 range tracker (mlp_common.h RangeS); false for a launch whose caller certifies that nothing it converts can
 // reach the end of the range (Params::range_certified): three vector instructions per four converted values less, no flag word written.
-template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2, bool TRACK = true>
+// SH: the launch shape (mlp_common.h TileShapeGeneric / TileShapeNode).  A shaped instantiation (SH::ID != 0) reads no field of Params
+// that its shape fixes: no aggregation-on-load path, no index staging, constant trip counts over sources / layers / heads, only its own
+// layers' biases staged, and the input rows loaded through a per-tile buffer descriptor with a 32-bit lane offset (rows of the last
+// tile past M come back as zeros from the descriptor's range check instead of being clamped; they are never stored).  Same
+// arithmetic in the same order: bit-identical to the generic instantiation.
+template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2, bool TRACK = true, class SH = TileShapeGeneric>
 __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX6_MINW)) void mlp_bx6_kernel(const Params p) {
     static_assert(TRACK || (SP == 2 && !SAVE), "the tracker-free instantiations: f16x3 stream, inference");
+    constexpr bool SHAPED = SH::ID != G4C_TILE_SHAPE_GENERIC;
+    static_assert(!SHAPED || (RT == 1 && VEC && FULL && SP == 2 && !SAVE && RD6 == 2), "launch shapes: the chip-filling f16x3 inference form");
     static_assert(RT == 1, "64-row tiles (RT = 2) measured slower in every arithmetic (split streams, round 3: 480 against 446 us; rounded-bf16 mode, round 6, "
                            "500k-row edge update with heads: 288 against 255 us) and cannot take the fused aggregation: not instantiated");
     constexpr int ROWS = 32 * RT, NW = 4;
@@ -693,8 +729,10 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
     // (wave-uniform 32-bit values in scalar registers — the launcher checks n_rows < 2^31: as 64-bit per-lane values they were the
     // registers the SP == 2 instantiations spilled, and a spilled uniform costs 64 lanes of scratch traffic per wave)
     int row0 = __builtin_amdgcn_readfirstlane((int)(p.row_base + (long long)tile * ROWS)), mlim = __builtin_amdgcn_readfirstlane((int)p.M);
-    if (p.tile_rows) {      // tile of whole segments (<= ROWS rows)
-        row0 = __builtin_amdgcn_readfirstlane(p.tile_rows[tile]); mlim = __builtin_amdgcn_readfirstlane(p.tile_rows[tile + 1]);
+    if constexpr (!SHAPED) {
+        if (p.tile_rows) {      // tile of whole segments (<= ROWS rows)
+            row0 = __builtin_amdgcn_readfirstlane(p.tile_rows[tile]); mlim = __builtin_amdgcn_readfirstlane(p.tile_rows[tile + 1]);
+        }
     }
     G4C_STAMPW(0);
 
@@ -707,9 +745,26 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
     // 4*(lane&7) of each 32-k chunk.  A block whose rows are not gathered through an index can start right away.
     const int grow_l = (lane >> 3) + 8 * wave, c4 = (lane & 7) * 4;
     f32x4 xp[RT][4];
+    // (shaped: rows of this tile present in the launch — the record count of the tile's row descriptors)
+    const int trows = SHAPED ? __builtin_amdgcn_readfirstlane(mlim - row0 >= ROWS ? ROWS : (mlim - row0 > 0 ? mlim - row0 : 0)) : 0;
     auto gather = [&](int sidx, bool direct) __attribute__((always_inline)) {
+        if constexpr (SHAPED) if (direct || !SH::IDX0) {
+            // the tile's rows of a direct 128-wide fp32 source through a buffer descriptor of exactly those rows (base and extent are
+            // scalar; one 32-bit lane offset per source instead of a 64-bit address and a row clamp per load).  (A shape's indexed
+            // source — `direct` false where the shape has one — goes on below: its extent is not part of the launch.)
+            const int ld = p.src[sidx].ld;
+            const float *tb = p.src[sidx].ptr + p.src[sidx].col0 + (long long)row0 * ld;
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tb), 0, trows ? ((trows - 1) * ld + NP) * 4 : 0, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+                const unsigned vo = (unsigned)((grow_l + 32 * t) * ld + c4) * 4u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) xp[t][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo + q * KC * 4u, 0, 0));
+            }
+            return;
+        }
         const int width = p.src[sidx].width;
-        if (p.src[sidx].seg_off) {
+        if (!SHAPED && p.src[sidx].seg_off) {
             // aggregation on load: this lane's row is the sum / mean of a CSR segment of the source's rows, added in
             // order (bit-identical to segment_reduce_kernel); four rows in flight per column chunk
             const int *so = p.src[sidx].seg_off, *sp = p.src[sidx].seg_perm;
@@ -821,12 +876,21 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         }
     };
     auto park = [&](int sidx) __attribute__((always_inline)) {            // one uniform branch per block, not one per element
+        if constexpr (SHAPED) park_impl(sidx, std::false_type{});
+        else
         if (p.src[sidx].pre_act && !p.src[sidx].seg_off) park_impl(sidx, std::true_type{});
         else park_impl(sidx, std::false_type{});
     };
     // Memory instructions return in order per wave, so the loads that head a dependent chain go FIRST: row indices (the
     // additive gathers wait for them), then the parameters, then the long-latency streams (weights, directly indexed input).
+    // (a shape without indexed sources stages none: no loads, no select chains, no sRow read-backs)
     int idx_v[(2 * NSLOT * ROWS + 64 * NW - 1) / (64 * NW)];
+    if constexpr (SHAPED) {
+        if constexpr (SH::IDX0) {          // slot 0 only: ROWS entries, one thread each
+            const int gr = row0 + tid < mlim ? row0 + tid : mlim - 1;
+            idx_v[0] = tid < ROWS ? p.src[0].idx[gr] : 0;
+        }
+    } else
 #pragma unroll
     for (int it = 0; it < (2 * NSLOT * ROWS + 64 * NW - 1) / (64 * NW); ++it) {
         const int e = tid + it * 64 * NW;
@@ -843,15 +907,19 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         }
         idx_v[it] = ix ? ix[gr] : (int)gr;
     }
-    float bias_v[(G4C_MAX_LAYERS * NP) / (64 * NW)], gb_v = 0.f;
+    const int n_layers = [&] { if constexpr (SHAPED) return SH::N_LAYERS; else return p.n_layers; }();
+    const int n_out = SHAPED ? NP : p.n_out;
+    const bool has_ln = SHAPED || p.gamma;
+    constexpr int BIAS_IT = ([] { if constexpr (SHAPED) return SH::N_LAYERS; else return G4C_MAX_LAYERS; }() * NP + 64 * NW - 1) / (64 * NW);
+    float bias_v[BIAS_IT], gb_v = 0.f;          // (shaped: only the shape's own layers)
 #pragma unroll
-    for (int it = 0; it < (G4C_MAX_LAYERS * NP) / (64 * NW); ++it) {
+    for (int it = 0; it < BIAS_IT; ++it) {
         const int e = tid + it * 64 * NW;
-        bias_v[it] = LDS_BIAS ? p.b[e < p.n_layers * NP ? e : 0] : 0.f;
+        bias_v[it] = LDS_BIAS ? p.b[e < n_layers * NP ? e : 0] : 0.f;
     }
-    if (p.gamma) {
+    if (has_ln) {
         const int e = tid & (NP - 1);
-        const int ee = e < p.n_out ? e : 0;
+        const int ee = e < n_out ? e : 0;
         gb_v = tid < NP ? p.gamma[ee] : p.beta[ee];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -861,9 +929,12 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         if (SP >= 2) ring.m[s] = ldw(rs, lo_b + 1024u, 2u * s * STEP6);
         if (SP == 3) ring.l[s] = ldw(rs, lo_b + 2048u, 2u * s * STEP6);
     }
-    const bool direct0 = p.n_src > 0 && (p.src[0].idx == nullptr);
+    const bool direct0 = [&] { if constexpr (SHAPED) return !SH::IDX0; else return p.n_src > 0 && (p.src[0].idx == nullptr); }();
     if (direct0) gather(0, true);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (SHAPED) {
+        if constexpr (SH::IDX0) { if (tid < ROWS) sRow[tid] = idx_v[0]; }
+    } else
 #pragma unroll
     for (int it = 0; it < (2 * NSLOT * ROWS + 64 * NW - 1) / (64 * NW); ++it) {
         const int e = tid + it * 64 * NW;
@@ -871,15 +942,15 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
     }
     if (LDS_BIAS) {
 #pragma unroll
-        for (int it = 0; it < (G4C_MAX_LAYERS * NP) / (64 * NW); ++it) sBias[tid + it * 64 * NW] = bias_v[it];
+        for (int it = 0; it < BIAS_IT; ++it) sBias[tid + it * 64 * NW] = bias_v[it];
     }
-    if (p.gamma) sGB[tid] = gb_v;          // [gamma(128) | beta(128)] = 256 threads
-    __syncthreads();
+    if (has_ln) sGB[tid] = gb_v;          // [gamma(128) | beta(128)] = 256 threads
+    __syncthreads();          // (publishes the biases and gamma / beta too: stays where no index is staged)
     G4C_STAMPW(1);
-    if (!direct0 && p.n_src > 0) gather(0, false);
+    if (!direct0 && (SHAPED || p.n_src > 0)) gather(0, false);
     __builtin_amdgcn_sched_barrier(0);
 
-    if (p.n_src > 0) park(0);          // (before the additive gathers: the input registers are free again while those are in flight)
+    if (SHAPED || p.n_src > 0) park(0);          // (before the additive gathers: the input registers are free again while those are in flight)
     G4C_STAMPW(2);
     // Operands are swapped in the MFMAs (weights as A, activations as B), so the accumulators are TRANSPOSED: this lane
     // holds sample row i (= lane & 31, + 32 per row tile) and the 16 output features 32*ct0 + 8*(q>>2) + 4*h + (q&3):
@@ -895,10 +966,11 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
 #pragma unroll
             for (int t = 0; t < RT; ++t)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { acc[t][4 * gq + e] = b4[e]; acc1[t][4 * gq + e] = 0.f; }
+                for (int e = 0; e < 4; ++e) { acc[t][4 * gq + e] = b4[e]; if (!SHAPED) acc1[t][4 * gq + e] = 0.f; }          // (shaped: ZC of mma_block_bx6)
         }
     };
     bias_start(0);
+    if constexpr (!SHAPED)
     for (int a = 0; a < p.n_add; ++a) {
         const int width = p.add[a].width;
         const bool vec = FULL || (((p.add[a].ld & 3) == 0) && ((width & 3) == 0) && (((uintptr_t)p.add[a].ptr & 15) == 0));
@@ -938,7 +1010,8 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
     }
     // narrow input blocks (2..8 columns): x[row, k] * W1^T[k, :] in fp32 on the vector ALUs — a padded 128-k block of
     // six-product MFMAs for 2 columns of input would cost 48 MFMAs per wave; this costs 16 FMAs per column
-    for (int a = 0; a < p.n_nar; ++a) {
+    const int n_nar = [&] { if constexpr (SHAPED) return SH::N_NAR; else return p.n_nar; }();
+    for (int a = 0; a < n_nar; ++a) {
         const float *wn = p.nar[a].w + fbase;
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
@@ -961,22 +1034,28 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
 
     // ---------------------------------------------------------------- layer 0: one (padded) 128-k input block at a time
     const __bf16 *pa = sB + i * HB + 8 * h;
-    for (int s = 0; s < p.n_src; ++s) {
-        const bool more = s + 1 < p.n_src;
-        if (more && RT == 1) gather(s + 1, false);          // (RT = 2: 32 more live registers would cost a wave per SIMD)
+    auto block0 = [&](int s, bool more, auto zc_tag) __attribute__((always_inline)) {
+        if (more && RT == 1) gather(s + 1, SHAPED);          // (RT = 2: 32 more live registers would cost a wave per SIMD; a shape's sources behind the first are direct)
         __builtin_amdgcn_sched_barrier(0);
-        mma_block_bx6<RT, SP, false, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
+        mma_block_bx6<RT, SP, false, RD6, decltype(zc_tag)::value>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
         wofs += 2u * BLOCK6;
         __syncthreads();                   // everybody is done reading the planes
         if (more) {
-            if (RT != 1) gather(s + 1, false);
+            if (RT != 1) gather(s + 1, SHAPED);
             park(s + 1);
             __syncthreads();
         }
+    };
+    if constexpr (SHAPED) {
+        block0(0, 1 < SH::N_SRC, std::integral_constant<int, 1>{});          // (acc1 starts at zero here)
+#pragma unroll
+        for (int s = 1; s < SH::N_SRC; ++s) block0(s, s + 1 < SH::N_SRC, std::integral_constant<int, 0>{});
+    } else {
+        for (int s = 0; s < p.n_src; ++s) block0(s, s + 1 < p.n_src, std::integral_constant<int, 0>{});
     }
     G4C_STAMPW(4);
     for (int l = 0;; ++l) {
-        const bool last = (l == p.n_layers - 1);
+        const bool last = (l == n_layers - 1);
         if (last) {
             // final tile in fp32 for the LayerNorm / store epilogue (aliases the operand planes: everybody finished
             // reading them at the barrier that closed the previous block)
@@ -1030,14 +1109,15 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         __syncthreads();
         G4C_STAMPW(5 + 2 * l);
         bias_start(l + 1);
-        mma_block_bx6<RT, SP, false, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
+        mma_block_bx6<RT, SP, false, RD6, SHAPED ? 1 : 0>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
         wofs += 2u * BLOCK6;
         __syncthreads();
         G4C_STAMPW(6 + 2 * l);
     }
     G4C_STAMPW(12);
-    split_finish<NW, ROWS>(p, sH, sGB, wave, lane, row0, mlim);
+    split_finish<NW, ROWS, SHAPED>(p, sH, sGB, wave, lane, row0, mlim);
     G4C_STAMPW(13);
+    if constexpr (!SHAPED)
     if (p.agg) {
         // aggregation of the targets whose messages this tile holds (rows in CSR order): same summation order and the
         // same mean formula as segment_reduce_kernel, so the result is bit-identical to the separate launch
@@ -1052,7 +1132,8 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
             p.agg[(long long)sg * p.agg_ld + col] = a;
         }
     }
-    if (p.n_heads) {
+    const int n_heads = [&] { if constexpr (SHAPED) return SH::N_HEADS; else return p.n_heads; }();
+    if (n_heads) {
         // heads (see Params): the finished fp32 tile -> three operand planes (they alias it: read everything, barrier,
         // then overwrite), then one 128-k block per head whose weights continue the stream
         __syncthreads();
@@ -1119,13 +1200,13 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
             head_zero(acc, acc1); head_zero(acc2, acc21);
             mma_block_bx6<RT, SP, true, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
             wofs += 2u * BLOCK6;
-            if (p.n_heads > 1) mma_block_bx6<RT, SP, true, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc2, acc21);
+            if (n_heads > 1) mma_block_bx6<RT, SP, true, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc2, acc21);
             head_store(0, acc, acc1);
-            if (p.n_heads > 1) head_store(1, acc2, acc21);
+            if (n_heads > 1) head_store(1, acc2, acc21);
         } else {
-            for (int hd = 0; hd < p.n_heads; ++hd) {
-                head_zero(acc, acc1);
-                mma_block_bx6<RT, SP, true, RD6>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
+            for (int hd = 0; hd < n_heads; ++hd) {
+                if (!SHAPED) head_zero(acc, acc1);
+                mma_block_bx6<RT, SP, true, RD6, SHAPED ? 3 : 0>(pa, PLN, ring, rs, wofs, lo_b, acc, acc1);
                 wofs += 2u * BLOCK6;
                 head_store(hd, acc, acc1);
             }
@@ -1163,8 +1244,27 @@ __global__ void pack_layer_bx6_kernel(const float *__restrict__ W, int n_out, in
     d[0] = a; d[512] = b; d[1024] = c;
 }
 
+#ifdef G4C_TILE_ISA_ONLY
+// -DG4C_TILE_ISA_ONLY (tests/test_tile_isa.py, with --cuda-device-only -S): nothing but the chip-filling f16x3 inference instantiations —
+// the node-update shapes, the generic kernel they replace (tracked and certified) and the three-layer UpMP / DownMP shapes (tracked) — — for a look at their registers and instructions
+// in seconds instead of the minute the whole file takes
+#define G4C_TILE_ISA(TRACK)                                                                                              \
+    template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, TileShapeGeneric>(const Params);          \
+    template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, TileShapeNode<2, 0>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, TileShapeNode<2, 2>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, TileShapeNode<3, 0>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, TileShapeNode<3, 2>>(const Params);
+G4C_TILE_ISA(true)
+G4C_TILE_ISA(false)
+#undef G4C_TILE_ISA
+template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeUp<3, 0>>(const Params);
+template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeUp<3, 2>>(const Params);
+template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeDown<3>>(const Params);
+#endif
+
 }  // namespace
 
+#ifndef G4C_TILE_ISA_ONLY
 extern "C" int g4c_mlp_pack_layer(const float *W, int32_t n_out, int32_t k_in, const int32_t *seg_width,
                                   const int32_t *seg_negate, int32_t n_seg, int32_t w_format, void *packed,
                                   int32_t k_pad, int32_t n_pad, void *stream) {
@@ -1214,9 +1314,65 @@ extern "C" int g4c_mlp_small_launch_tiles(int n_tiles) {
     return prev;
 }
 
+// compile-time launch shapes of the tile kernel (mlp_common.h TileShape*): on by default (-DG4C_TILE_SHAPES_DEFAULT=0: a library for
+// whole-benchmark A/B legs, scripts/ab_bench.sh)
+#ifndef G4C_TILE_SHAPES_DEFAULT
+#define G4C_TILE_SHAPES_DEFAULT 1
+#endif
+static std::atomic<int> g_tile_shapes{G4C_TILE_SHAPES_DEFAULT};
+static thread_local int g_last_shape = G4C_TILE_SHAPE_GENERIC;
+extern "C" int g4c_mlp_shapes_enable(int on) {
+    const int prev = g_tile_shapes.load(std::memory_order_relaxed);
+    if (on >= 0) g_tile_shapes.store(on ? 1 : 0, std::memory_order_relaxed);
+    return prev;
+}
+extern "C" int g4c_mlp_last_shape(void) { return g_last_shape; }
+
+// The shape whose every field this f16x3 inference launch of whole 128-wide aligned blocks on the two-step ring matches, or
+// G4C_TILE_SHAPE_GENERIC.  (`full` has checked: every weighted source 128 wide, fp32 rows on 16-byte boundaries.)
+static int tile_shape_of(const Params &p) {
+    const int G = G4C_TILE_SHAPE_GENERIC;
+    if (p.n_src < 1 || p.n_src > 2 || p.n_add || p.n_nar > 1 || (p.n_layers != 2 && p.n_layers != 3) || (p.n_heads != 0 && p.n_heads != 2)) return G;
+    for (int s = 0; s < p.n_src; ++s) {
+        const Src &d = p.src[s];
+        if (d.seg_off || d.pre_act != G4C_ACT_NONE || d.bf16 || d.width != NP || !d.vec) return G;
+        // a direct source's rows go through a buffer descriptor with 32-bit offsets: its byte extent (a whole last tile included) stays below 2^31
+        if (!d.idx && (p.M + 32) * (long long)d.ld * 4 >= (1LL << 31)) return G;
+    }
+    if ((p.M + 32) * (long long)p.out_ld * 4 >= (1LL << 31)) return G;          // (the output rows likewise)
+    if (!p.gamma || p.n_out != NP || !p.out || ((uintptr_t)p.out & 15) || (p.out_ld & 3) || p.out_idx || p.resid || p.out_bf16 || p.agg ||
+        p.tile_rows || p.head_bf16)
+        return G;
+    const bool idx0 = p.src[0].idx != nullptr, idx1 = p.n_src > 1 && p.src[1].idx != nullptr;
+    if (p.n_src == 2 && p.n_nar == 0 && !idx0 && !idx1) return G4C_TILE_SHAPE_NODE;
+    // (a narrow block has no range proof — ops.range_bounds — so the launches that carry one are tracked: no tracker-free form of their shapes)
+    if (p.n_nar != 1 || p.range_certified) return G;
+    if (p.n_src == 2 && idx0 && !idx1) return G4C_TILE_SHAPE_UP;
+    if (p.n_src == 1 && !idx0 && p.n_heads == 0) return G4C_TILE_SHAPE_DOWN;
+    return G;
+}
+template <bool TRACK>
+static void launch_tile_shape(int shape, const Params &p, dim3 grid, dim3 blk, hipStream_t st) {
+#define G4C_SHAPED(...) mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, __VA_ARGS__><<<grid, blk, 0, st>>>(p)
+    const bool l3 = p.n_layers == 3, h2 = p.n_heads == 2;
+    if (shape == G4C_TILE_SHAPE_NODE) {
+        if (l3) { if (h2) G4C_SHAPED(TileShapeNode<3, 2>); else G4C_SHAPED(TileShapeNode<3, 0>); }
+        else { if (h2) G4C_SHAPED(TileShapeNode<2, 2>); else G4C_SHAPED(TileShapeNode<2, 0>); }
+    } else if constexpr (TRACK) {
+        if (shape == G4C_TILE_SHAPE_UP) {
+            if (l3) { if (h2) G4C_SHAPED(TileShapeUp<3, 2>); else G4C_SHAPED(TileShapeUp<3, 0>); }
+            else { if (h2) G4C_SHAPED(TileShapeUp<2, 2>); else G4C_SHAPED(TileShapeUp<2, 0>); }
+        } else {
+            if (l3) G4C_SHAPED(TileShapeDown<3>); else G4C_SHAPED(TileShapeDown<2>);
+        }
+    }
+#undef G4C_SHAPED
+}
+
 static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows, const g4c_mlp_io_t *io,
                       void *stream) {
     g_last_kernel = G4C_KERNEL_NONE;
+    g_last_shape = G4C_TILE_SHAPE_GENERIC;
     G4C_REQUIRE(io && io->size == (int32_t)sizeof(g4c_mlp_io_t), G4C_EINVAL,
                 "g4c_mlp_run: io->size %d, this library's g4c_mlp_io_t has %d bytes (a binding out of step with g4c.h)", io ? io->size : 0,
                 (int)sizeof(g4c_mlp_io_t));
@@ -1507,6 +1663,12 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
             else if (all_vec) mlp_bx6_kernel<1, true, false, 3, true><<<grid, blk, 0, st>>>(p);
             else mlp_bx6_kernel<1, false, false, 3, true><<<grid, blk, 0, st>>>(p);
         }
+        else if (f16x2 && full && !deep && g_tile_shapes.load(std::memory_order_relaxed) && tile_shape_of(p) != G4C_TILE_SHAPE_GENERIC) {
+            // (a launch every field of which matches a compile-time shape: same kernel code, tracked or certified)
+            g_last_shape = tile_shape_of(p);
+            if (p.range_certified) { g_last_kernel = G4C_KERNEL_MLP_BX6_CERT; launch_tile_shape<false>(g_last_shape, p, grid, blk, st); }
+            else launch_tile_shape<true>(g_last_shape, p, grid, blk, st);
+        }
         else if (f16x2 && p.range_certified && full) {
             // (the tracker-free instantiations: whole 128-wide aligned blocks — every launch of a model's MP layers, pools and unpools)
             g_last_kernel = G4C_KERNEL_MLP_BX6_CERT;
@@ -1530,3 +1692,4 @@ extern "C" int g4c_mlp_run(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t 
                            void *stream) {
     return mlp_launch(mlp, srcs, n_src, n_rows, io, stream);
 }
+#endif  // G4C_TILE_ISA_ONLY

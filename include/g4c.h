@@ -334,6 +334,25 @@ int g4c_mlp_small_launch_tiles(int n_tiles);
 #define G4C_KERNEL_MLP_WS_CERT 8
 int g4c_mlp_last_kernel(void);
 
+/* Compile-time launch shapes of the tile kernel (mlp_bx6_kernel): a launch of G4C_WFMT_F16X2 whose every field matches a shape runs an
+ * instantiation in which that shape's fields are constants — no source interpretation, index staging only for a source that has an
+ * index, 32-bit row addressing of direct sources through a buffer descriptor; same arithmetic, bit-identical results, same
+ * g4c_mlp_last_kernel() code.  Common to the shapes: the chip-filling (two-step ring) form; weighted sources of fp32 rows, 128 wide,
+ * 16-byte aligned, no pending activation, no aggregation on load, a direct one of less than 2^31 bytes; no additive blocks; 2 or 3 layers
+ * with LayerNorm; plain fp32 128-wide output rows (16-byte aligned; no out_idx, resid, agg, save); 0 or 2 fp32 heads.
+ *   G4C_TILE_SHAPE_NODE  the MP layers' node update: two direct sources, no narrow block
+ *   G4C_TILE_SHAPE_UP    UpMP: one narrow block, an indexed source, a direct source (in this order of weighted sources)
+ *   G4C_TILE_SHAPE_DOWN  DownMP: one narrow block, one direct source, no heads
+ * Everything else runs the all-runtime kernel (shape 0).
+ * g4c_mlp_shapes_enable: 0 = never, 1 = every launch a shape matches (the default); a negative argument only queries.  Returns the
+ * previous setting.  g4c_mlp_last_shape: the shape of the calling thread's most recent g4c_mlp_run (0 when it launched nothing). */
+#define G4C_TILE_SHAPE_GENERIC 0
+#define G4C_TILE_SHAPE_NODE 1
+#define G4C_TILE_SHAPE_UP 2
+#define G4C_TILE_SHAPE_DOWN 3
+int g4c_mlp_shapes_enable(int on);
+int g4c_mlp_last_shape(void);
+
 /* Tiles of whole segments for the fused aggregation (g4c_mlp_io_t.tile_rows / tile_seg): returns the tile count, -1 if a segment is
  * longer than max_rows. */
 int64_t g4c_plan_tiles(const int32_t *off /*host*/, int32_t n_seg, int32_t max_rows, int32_t *tile_rows /*host, out*/,
