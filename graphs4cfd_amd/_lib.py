@@ -129,6 +129,8 @@ _SIGNATURES = {
     "g4c_weight_grad_scratch_floats": (C.c_int64, [C.c_int64]),
     "g4c_weight_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p]),
+    "g4c_weight_grad_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p]),
     "g4c_segment_broadcast": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int32, C.c_void_p]),
 }

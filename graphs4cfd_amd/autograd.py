@@ -20,6 +20,11 @@ Here the forward of a block stays ONE fused launch, recorded by a `torch.autogra
     reference's autograd does this scatter with atomics), of an aggregation g4c_segment_broadcast.
 
 No atomics anywhere: two runs of a training step produce bit-identical gradients.
+
+Mixed precision (`ops.set_train_precision("bf16")`, selected by `fit` for `TrainConfig(mixed_precision=True)` together with the
+rounded-bf16 forward): every product above takes both operands rounded once to bf16 and accumulates in fp32 — `linear` and
+`backward_chain` pack the rounded-bf16 stream (which saves and takes `mul` like the split streams), `weight_bias_grad` launches
+g4c_weight_grad_bf16 for every tile.  Bias gradients, LayerNorm / activation adjoints, segmented sums and gathers are unchanged.
 """
 from __future__ import annotations
 
@@ -145,6 +150,8 @@ def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: int = _lib.AC
     blocks = [(k0, min(128, k - k0)) for k0 in range(0, k, 128)]
     prec = ops.effective_precision([w for _, w in blocks])
     prec = "bf16x6" if prec in ("f16x3", "bf16") else prec          # (the rounded-bf16 forward too — as backward_chain does)
+    if ops.train_precision() == "bf16":                             # mixed-precision training: one rounded product per element
+        prec = "bf16"
     out = None if n_out <= 128 else torch.empty((M, n_out), dtype=torch.float32, device=x.device)
     w_d, b_d = weight.detach(), (None if bias is None else bias.detach())
     y = None
@@ -179,7 +186,7 @@ def backward_chain(g: Tensor, weights: Sequence[Tensor], acts: Sequence[Tensor],
     L = len(weights)                                  # weights[l] for l = 0 .. L-1 (weights[0] unused: W_dense replaces it)
     M, dev = int(g.size(0)), g.device
     ws = [weights[l].t() for l in range(L - 1, 0, -1)] + [w_dense.t()]
-    pk = ops.PackedMLP(ws, [None] * len(ws), None, [128], [False], precision="bf16x6")
+    pk = ops.PackedMLP(ws, [None] * len(ws), None, [128], [False], precision=ops.train_precision())
     pk.params = None
     D = {l: _buf(M, 128, dev) for l in range(L - 1, 0, -1)}
     save = [D[l] for l in range(L - 1, 0, -1)] + [None]
@@ -189,11 +196,13 @@ def backward_chain(g: Tensor, weights: Sequence[Tensor], acts: Sequence[Tensor],
 
 
 def _wgrad_tile(g: Tensor, blk: Tensor, M: int, with_bias: bool, scratch: Tensor) -> Tensor:
-    """One g4c_weight_grad launch: [128 x 128 | 128] = (g^T blk | column sums of g) for 128-wide g and a 128-column window `blk`."""
+    """One g4c_weight_grad launch: [128 x 128 | 128] = (g^T blk | column sums of g) for 128-wide g and a 128-column window `blk`
+    (ops.train_precision() "bf16": g4c_weight_grad_bf16 — both operands rounded to bf16, the column sums from the fp32 g)."""
     lib = _lib.load()
     out = torch.empty(128 * 128 + 128, dtype=torch.float32, device=g.device)
-    _lib.check(lib.g4c_weight_grad(_lib.ptr(g), _ld(g), _lib.ptr(blk), _ld(blk), M, _lib.ptr(scratch), _lib.ptr(out),
-                                   1 if with_bias else 0, _lib.stream_handle(g.device)))
+    fn = lib.g4c_weight_grad_bf16 if ops.train_precision() == "bf16" else lib.g4c_weight_grad
+    _lib.check(fn(_lib.ptr(g), _ld(g), _lib.ptr(blk), _ld(blk), M, _lib.ptr(scratch), _lib.ptr(out), 1 if with_bias else 0,
+                  _lib.stream_handle(g.device)))
     return out
 
 
@@ -272,7 +281,10 @@ class _FusedMLP(torch.autograd.Function):
                                segments=m["segments"], seg_mean=m["seg_mean"]))
         resid = tensors[n_src] if spec.has_resid else None
         saves = None
-        if SAVE_ACTIVATIONS and spec.packed.precision == "bf16x6" and spec.n_rows > 0:
+        # (every image the tile kernel can save from: the split streams and the plain rounded-bf16 stream, not the row-split orders)
+        can_save = spec.packed.precision == "bf16x6" or (spec.packed.precision == "bf16" and not spec.packed.rs_order
+                                                         and not spec.packed.rs2 and not any(spec.packed.rs_blocks))
+        if SAVE_ACTIVATIONS and can_save and spec.n_rows > 0:
             dev = tensors[0].device
             saves = [_buf(spec.n_rows, 128, dev) for _ in range(spec.n_layers - 1)] + \
                     [_buf(spec.n_rows, 128, dev) if spec.has_ln else None]
@@ -383,7 +395,7 @@ class _FusedMLP(torch.autograd.Function):
         db: List[Optional[Tensor]] = [None] * L
         need_dx_dense = any(needs[1 + j] for j in dense)
         gX = None
-        chain = (FUSED_CHAIN and ops.mlp_precision() in ("bf16x6", "f16x3") and M >= FUSED_LINEAR_MIN_ROWS and kd == 128 and need_dx_dense
+        chain = (FUSED_CHAIN and ops.mlp_precision() in ("bf16x6", "f16x3", "bf16") and M >= FUSED_LINEAR_MIN_ROWS and kd == 128 and need_dx_dense
                  and int(g.size(1)) == 128 and all(tuple(W[l].shape) == (128, 128) for l in range(1, L)) and N1 == 128
                  and all(a is not None and a.stride(1) == 1 for a in acts[1:]))
         if chain:

@@ -1517,8 +1517,12 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
     for (int l = 0; l < G4C_MAX_LAYERS; ++l) { p.save[l] = nullptr; p.mul[l] = nullptr; }
     p.save_ld = 0; p.mul_ld = 0;
     if (save) {
-        G4C_REQUIRE(bx6 && !round1 && !agg && !n_heads && !out_idx && io->save_ld >= NP && (io->save_ld & 3) == 0, G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: save needs w_format BF16X3 / F16X2 without heads / aggregation / output index, save_ld >= 128 and a multiple of 4");
+        // (the rounded-bf16 stream saves on the plain tile kernel only: the row-split streams keep refusing; saved / mul rows stay fp32)
+        G4C_REQUIRE(bx6 && (!round1 || fmt == G4C_WFMT_BF16) && !io->out_dtype && !agg && !n_heads && !out_idx && io->save_ld >= NP &&
+                        (io->save_ld & 3) == 0,
+                    G4C_EUNSUPPORTED,
+                    "g4c_mlp_run: save needs w_format BF16X3 / F16X2 / BF16 without heads / aggregation / output index / bf16 rows, save_ld >= 128 "
+                    "and a multiple of 4");
         G4C_REQUIRE(io->n_save == mlp->n_layers, G4C_EINVAL, "g4c_mlp_run: n_save %d for %d layers", io->n_save, mlp->n_layers);
         bool mul = false;
         for (int l = 0; l < mlp->n_layers; ++l) {
@@ -1658,6 +1662,10 @@ static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src
             if (full) mlp_bx6_kernel<1, true, true, 2, true><<<grid, blk, 0, st>>>(p);
             else if (all_vec) mlp_bx6_kernel<1, true, false, 2, true><<<grid, blk, 0, st>>>(p);
             else mlp_bx6_kernel<1, false, false, 2, true><<<grid, blk, 0, st>>>(p);
+        } else if (save && round1) {          // (mixed-precision training: one product per element, fp32 save / mul rows)
+            if (full) mlp_bx6_kernel<1, true, true, 1, true><<<grid, blk, 0, st>>>(p);
+            else if (all_vec) mlp_bx6_kernel<1, true, false, 1, true><<<grid, blk, 0, st>>>(p);
+            else mlp_bx6_kernel<1, false, false, 1, true><<<grid, blk, 0, st>>>(p);
         } else if (save) {
             if (full) mlp_bx6_kernel<1, true, true, 3, true><<<grid, blk, 0, st>>>(p);
             else if (all_vec) mlp_bx6_kernel<1, true, false, 3, true><<<grid, blk, 0, st>>>(p);

@@ -281,6 +281,100 @@ __global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_kernel(const float 
     }
 }
 
+// The same contraction with both operands rounded once to bf16 (round to nearest even, v_cvt_pk_bf16_f32) and fp32 accumulation:
+// the weight gradient of mixed-precision training (ops.set_train_precision("bf16")).  v_mfma_f32_32x32x16_bf16 contracts sixteen
+// rows per instruction (the fp32 form: two), so a slab's matrix work drops from 32 to 4 MFMAs per accumulator pair and only the one
+// pass over g and a is left.  Same roles as weight_grad_kernel (wave = (32-row block of n, half of k), the same accumulator ->
+// element map, the same partial-tile layout, the same two reduction launches), but:
+//  * a slab is 64 rows (four MFMA steps), and both operands are consumed ALONG the row index m, i.e. as column reads of a row-major
+//    slab.  The slab is therefore staged TRANSPOSED: image[column][row] in bf16, WGB_CS = 144 bytes per column (64 rows + 16 bytes
+//    of padding).  A lane's fragment of step s — rows 16 s + 8 h .. + 7 of its column — is one 16-byte read; 144 bytes = 36 dwords
+//    = 4 x an odd number, so the sixteen lanes of every ds_read_b128 group (distinct columns mod 16) cover the 64 banks once.
+//  * a thread stages 4 rows x 4 columns per operand (four 16-byte global loads) and stores, per column, its four rounded rows as
+//    one 8-byte word.  Thread -> (column group cg, row group rg): sixteen consecutive lanes hold 2 column groups x 8 row groups,
+//    which puts their sixteen 8-byte stores on sixteen different bank pairs (bank = 16 (cg & 1) + 2 (rg & 7) + const mod 32); a
+//    wave's global load still reads eight full 128-byte lines (8 column groups) of each of its 8 rows.
+//  * rows past the end of the chunk are zero-filled when they are fetched: every lane reads a full fragment, nothing is masked.
+//  * db: column sums of the UNROUNDED fp32 g, as in weight_grad_kernel.
+constexpr int WGB_SLAB = 64, WGB_CS = 2 * WGB_SLAB + 16;
+typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
+__global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_bf16_kernel(const float *__restrict__ g, int g_ld, const float *__restrict__ a,
+                                                                         int a_ld, long long n_rows, long long chunk,
+                                                                         float *__restrict__ partial, int with_bias) {
+    __shared__ __attribute__((aligned(16))) unsigned char sG[WG_N * WGB_CS];
+    __shared__ __attribute__((aligned(16))) unsigned char sA[WG_N * WGB_CS];
+    static_assert(WG_N * WGB_CS >= 16 * WG_N * (int)sizeof(float), "the db reduction reuses sG");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = wave & 3, kh = wave >> 2;
+    const int i = lane & 31, h = lane >> 5;
+    const long long r0 = (long long)blockIdx.x * chunk;
+    const long long r1 = r0 + chunk < n_rows ? r0 + chunk : n_rows;
+    const int cg = 2 * ((tid >> 4) & 15) + (tid & 1), rg = 8 * (tid >> 8) + ((tid >> 1) & 7);
+    const int c4 = 4 * cg, rr = 4 * rg;                         // this thread's 4 columns / 4 rows inside a slab
+    f32x16 acc[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[kb][j] = 0.f;
+    f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
+    f32x4 pg[4], pa[4];                                         // the slab after the one in LDS
+    auto fetch = [&](long long m0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long long r = m0 + rr + it;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            pg[it] = r < r1 ? *reinterpret_cast<const f32x4 *>(g + r * g_ld + c4) : z;
+            pa[it] = r < r1 ? *reinterpret_cast<const f32x4 *>(a + r * a_ld + c4) : z;
+        }
+    };
+    if (r0 < r1) fetch(r0);
+    for (long long m0 = r0; m0 < r1; m0 += WGB_SLAB) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {                           // one column: rows rr .. rr + 3, rounded, side by side
+            wg_bf16x4 vg, va;
+#pragma unroll
+            for (int it = 0; it < 4; ++it) { vg[it] = (__bf16)pg[it][e]; va[it] = (__bf16)pa[it][e]; }
+            *reinterpret_cast<wg_bf16x4 *>(sG + (c4 + e) * WGB_CS + 2 * rr) = vg;
+            *reinterpret_cast<wg_bf16x4 *>(sA + (c4 + e) * WGB_CS + 2 * rr) = va;
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) bsum += pg[it];
+        __syncthreads();
+        if (m0 + WGB_SLAB < r1) fetch(m0 + WGB_SLAB);           // in flight under the MFMAs and the next barrier
+        const unsigned char *pG = sG + (nb * 32 + i) * WGB_CS + 16 * h, *pA = sA + (kh * 64 + i) * WGB_CS + 16 * h;
+#pragma unroll
+        for (int s = 0; s < WGB_SLAB / 16; ++s) {
+            const wg_bf16x8 av = *reinterpret_cast<const wg_bf16x8 *>(pG + 32 * s);
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const wg_bf16x8 bv = *reinterpret_cast<const wg_bf16x8 *>(pA + kb * 32 * WGB_CS + 32 * s);
+                acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[kb], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    float *out = partial + (long long)blockIdx.x * (WG_N * WG_N + WG_N);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int n = nb * 32 + 4 * h + 8 * (j >> 2) + (j & 3);
+            out[n * WG_N + kh * 64 + kb * 32 + i] = acc[kb][j];
+        }
+    if (with_bias) {                                            // column sums of g: the sixteen threads sharing c4, in order
+        float *red = reinterpret_cast<float *>(sG);
+        *reinterpret_cast<f32x4 *>(red + rg * WG_N + c4) = bsum;
+        __syncthreads();
+        if (tid < WG_N) {
+            float t = red[tid];
+#pragma unroll
+            for (int q = 1; q < 16; ++q) t += red[q * WG_N + tid];
+            out[WG_N * WG_N + tid] = t;
+        }
+    }
+}
+
 // adjoint of the segmented sum / mean: every row of a segment receives the segment's gradient (/ max(count, 1))
 __global__ __launch_bounds__(256) void segment_broadcast_kernel(const float *__restrict__ dout, int dout_ld,
                                                                 const int *__restrict__ off, const int *__restrict__ perm,
@@ -416,6 +510,33 @@ extern "C" int g4c_weight_grad(const float *g, int32_t g_ld, const float *a, int
     colsum_stage_kernel<<<dim3(g2, cb), dim3(256), 0, st>>>(scratch, ld, width, G, chunk2 > 0 ? chunk2 : 1, scratch2, ld);
     colsum_stage_kernel<<<dim3(1, cb), dim3(256), 0, st>>>(scratch2, ld, width, g2, g2, out, ld);
     return g4c::check_launch("g4c_weight_grad");
+}
+
+extern "C" int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch,
+                                    float *out, int32_t with_bias, void *stream) {
+    // (every argument is checked before the first HIP call: a bad call fails the same way with or without a device)
+    G4C_REQUIRE(g && a && scratch && out, G4C_EINVAL, "g4c_weight_grad_bf16: null pointer");
+    G4C_REQUIRE(n_rows >= 0, G4C_EINVAL, "g4c_weight_grad_bf16: n_rows %lld is negative", (long long)n_rows);
+    G4C_REQUIRE(g_ld >= WG_N && a_ld >= WG_N && g_ld % 4 == 0 && a_ld % 4 == 0, G4C_EINVAL,
+                "g4c_weight_grad_bf16: leading dimensions must be >= 128 and multiples of 4 (g_ld=%d a_ld=%d)", g_ld, a_ld);
+    G4C_REQUIRE((uintptr_t)g % 16 == 0 && (uintptr_t)a % 16 == 0, G4C_EINVAL,
+                "g4c_weight_grad_bf16: g and a must be 16-byte aligned (g=%p a=%p)", (const void *)g, (const void *)a);
+    g4c::DeviceGuard on_device(out);
+    // the partial-tile rule of g4c_weight_grad: the same G and the same chunk of whole 32-row units per workgroup (this kernel cuts
+    // its chunk into 64-row slabs and zero-fills the last one)
+    const int G = g4c_weight_grad_partials(n_rows);
+    const long long slabs = (n_rows + WG_SLAB - 1) / WG_SLAB;
+    const long long chunk = ((slabs + G - 1) / G) * WG_SLAB;
+    hipStream_t st = (hipStream_t)stream;
+    weight_grad_bf16_kernel<<<dim3(G), dim3(WG_THREADS), 0, st>>>(g, g_ld, a, a_ld, n_rows, chunk > 0 ? chunk : WG_SLAB, scratch, with_bias);
+    const int width = WG_N * WG_N + (with_bias ? WG_N : 0), ld = WG_N * WG_N + WG_N;
+    float *scratch2 = scratch + (long long)G * ld;
+    const int g2 = wg_stage2_rows(G);
+    const long long chunk2 = (G + g2 - 1) / g2;
+    const unsigned cb = (unsigned)((width + 255) / 256);
+    colsum_stage_kernel<<<dim3(g2, cb), dim3(256), 0, st>>>(scratch, ld, width, G, chunk2 > 0 ? chunk2 : 1, scratch2, ld);
+    colsum_stage_kernel<<<dim3(1, cb), dim3(256), 0, st>>>(scratch2, ld, width, g2, g2, out, ld);
+    return g4c::check_launch("g4c_weight_grad_bf16");
 }
 
 extern "C" int64_t g4c_weight_grad_scratch_floats(int64_t n_rows) {

@@ -151,8 +151,10 @@ class GNN(nn.Module):
         loop itself is nn/training.py (`Trainer`: a rollout curriculum, an optimiser factory, a checkpoint file, one method per pass).
 
         Differences, all deliberate: `scheduler=None` / `tensor_board=None` work (the reference dereferences both
-        unconditionally, :279,:299); `mixed_precision` needs no loss scaling here — gradients and accumulations are fp32
-        whatever `ops.set_mlp_precision` says the MLP products run in — so the flag only prints a note; a clip of the default
+        unconditionally, :279,:299); `mixed_precision` runs every matrix product of the run (forward, input and weight
+        gradients) on bf16-rounded operands with fp32 accumulation (ops.set_mlp_precision("bf16") + ops.set_train_precision("bf16"),
+        both restored when `fit` returns or raises) and needs no loss scaling — bf16 has fp32's exponent range, and master weights,
+        biases, LayerNorm, sums and Adam stay fp32; checkpoints are unchanged; a clip of the default
         fp16-split arithmetic during an epoch is reported (ops.check_f16_range).  `self.history` holds one record per epoch."""
         from .training import Trainer
         Trainer(self, train_config, train_loader, val_loader).run()

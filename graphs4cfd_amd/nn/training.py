@@ -189,9 +189,22 @@ class Trainer:
 
     # ------------------------------------------------------------------ the run
     def run(self) -> None:
+        """The whole run.  `mixed_precision`: every matrix product of training and validation — forward, input gradients, weight
+        gradients — takes operands rounded once to bf16 and accumulates in fp32 (ops.set_mlp_precision("bf16") +
+        ops.set_train_precision("bf16")); both switches are restored when the run ends, however it ends."""
+        if not self.cfg['mixed_precision']:
+            return self._run()
+        old_mlp, old_train = ops.set_mlp_precision("bf16"), ops.set_train_precision("bf16")
+        try:
+            print("[fit] mixed_precision: every matrix product (forward, input and weight gradients) takes bf16-rounded operands "
+                  "with fp32 accumulation; master weights, biases, LayerNorm, sums and Adam stay fp32, no loss scaling")
+            return self._run()
+        finally:
+            ops.set_mlp_precision(old_mlp)
+            ops.set_train_precision(old_train)
+
+    def _run(self) -> None:
         m, cfg, cur = self.model, self.cfg, self.curriculum
-        if cfg['mixed_precision']:
-            print(f"[fit] mixed_precision: MLP products run in ops.mlp_precision() = {ops.mlp_precision()!r}; gradients stay fp32, no loss scaling")
         print(f"[fit] device {m.device}, {m.num_params} trainable parameters, rollout lengths {cur.lengths}")
         m.history = []
         for epoch in range(self.first_epoch, cfg['epochs'] + 1):

@@ -682,6 +682,29 @@ def set_mlp_precision(precision: str) -> str:
     return old
 
 
+TRAIN_PRECISIONS = ("bf16x6", "bf16")
+_TRAIN_PRECISION = "bf16x6"
+
+
+def train_precision() -> str:
+    return _TRAIN_PRECISION
+
+
+def set_train_precision(precision: str) -> str:
+    """Select the arithmetic of the backward pass's matrix products (autograd.py); returns the previous setting.  Independent of
+    `set_mlp_precision`, which selects the forward's.
+    "bf16x6" (default): input gradients on the exact three-way bf16 split, weight gradients on the fp32 MFMA (g4c_weight_grad).
+    "bf16" (mixed-precision training): every product of the backward takes both operands rounded once to bf16 (round to nearest
+    even) and accumulates in fp32 — `autograd.linear` / `backward_chain` pack the rounded-bf16 stream, weight gradients run on
+    g4c_weight_grad_bf16.  Bias gradients, LayerNorm / activation adjoints, segmented sums and gathers stay fp32.  bf16 has fp32's
+    exponent range, so gradient rows of 1e-6 .. 1e-9 need no loss scaling."""
+    global _TRAIN_PRECISION
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f"unknown training precision {precision!r} ({' | '.join(TRAIN_PRECISIONS)})")
+    old, _TRAIN_PRECISION = _TRAIN_PRECISION, precision
+    return old
+
+
 def _rs_k_order(dev) -> Tensor:
     """Column order of the row-split kernel's stream and of its bf16 rows (G4C_ROWS_RS_ORDER): position 32 j + 8 g + 4 h + e holds
     feature 32 j + 16 h + 4 g + e — the eight values a lane of a 16x16x32 MFMA holds of a 32-feature step, side by side."""
@@ -1029,7 +1052,7 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
     `head_outs` ([n_rows, 128] tensors, one per head of `packed`; all fp32, or all bf16 in the rounded-bf16 mode): the heads.
     `agg` = (csr, out [n_seg, 128], mean): also aggregate the output rows over the segments of `csr` (rows must be in segment
     order) — inside the launch when the kernel can, otherwise with a g4c_segment_reduce afterwards.
-    `save` (training forward, bf16x6 / f16x3 only): one [n_rows, 128] fp32 tensor (or None) per layer, receiving that layer's output
+    `save` (training forward; bf16x6 / f16x3 and the plain rounded-bf16 stream, not its row-split orders): one [n_rows, 128] fp32 tensor (or None) per layer, receiving that layer's output
     rows; `mul` (with `save`): per hidden layer the SELU-output rows whose slope multiplies that layer's result instead of bias + SELU
     (the backward chain of a block, see include/g4c.h).
     A bf16 `out` (rounded-bf16 mode): the rows are stored as bf16.

@@ -256,7 +256,8 @@ typedef struct {
     void *agg;
     int32_t agg_ld;             /* >= 128 */
     int32_t agg_mode;           /* bit 0 mean | G4C_AGG_UNIFORM(k) | G4C_AGG_OUT_BF16 */
-    /* training form (G4C_WFMT_BF16X3 / _F16X2, no heads / aggregation / out_idx; n_save = n_layers, 0 = off): save[l] (or NULL)
+    /* training form (G4C_WFMT_BF16X3 / _F16X2, and the plain rounded-bf16 stream G4C_WFMT_BF16 — mixed-precision training; not the
+     * row-split streams _BF16_RS / _RS2 / _RS2N, not with out_dtype; no heads / aggregation / out_idx; n_save = n_layers, 0 = off): save[l] (or NULL)
      * receives the rows layer l produces — SELU(hidden) for l < n_layers-1, the pre-LayerNorm rows for the last layer — as fp32
      * [n_rows, 128] (save_ld >= 128, a multiple of 4; 16-byte aligned), so the backward pass of the block recomputes nothing
      * (autograd.py).  mul[l] != NULL (hidden layers; mul_ld >= 128, a multiple of 4): the same launch as the BACKWARD chain of a block —
@@ -461,6 +462,14 @@ int32_t g4c_weight_grad_partials(int64_t n_rows);
 int64_t g4c_weight_grad_scratch_floats(int64_t n_rows);
 int g4c_weight_grad(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch, float *out,
                     int32_t with_bias, void *stream);
+
+/* The same call for mixed-precision training: dW[n, k] = sum_r bf16(g[r, n]) * bf16(a[r, k]) — both operands rounded once to
+ * bf16 (round to nearest even) as they are staged, products on the bf16 MFMA, fp32 accumulation; db[n] = sum_r g[r, n] from the
+ * UNROUNDED fp32 rows.  Same operands, same scratch (g4c_weight_grad_scratch_floats), same partial-tile rule and fixed-order
+ * reduction: bit-reproducible, no atomics.  Arguments are validated before any HIP call: g / a not 16-byte aligned, a leading
+ * dimension below 128 or not a multiple of 4, or n_rows < 0 return G4C_EINVAL (g4c_last_error() says which). */
+int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch, float *out,
+                         int32_t with_bias, void *stream);
 
 /* Adjoint of g4c_segment_reduce: dsrc[perm ? perm[p] : p] = dout[s] (/ max(count_s, 1) if mean) for p in segment s.
  * Rows of dsrc that belong to no segment are left untouched (zero them first when perm is not a full permutation). */
