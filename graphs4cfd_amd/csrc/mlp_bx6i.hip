@@ -482,55 +482,24 @@ __global__ __launch_bounds__(256, 2) void mlp_bx6i_kernel(const Params p) {
 
 namespace g4cm {
 
-// 0 off, 1 (default) launches of at least BX6I_MIN_ROWS rows (the kernel needs a full machine of its two workgroups per CU: same-box
-// crossover against the tile kernel ~300 k rows), 2 every launch it can take (tests)
-static int g_bx6i = -1;
-int bx6i_enable(int on) {
-    if (g_bx6i < 0) g_bx6i = 1;
-    const int old = g_bx6i;
-    if (on >= 0) g_bx6i = on > 2 ? 2 : on;
-    return old;
+// The envelope: the bf16x6 stream (the f16x3 stream goes to the weight-stationary kernel, mlp_ws.hip, which also tracks the fp16 range;
+// this kernel's two-way instantiation sat at its register limit — one more live register and it spilled a hundred — and is not built),
+// the hoisted or plain three-layer message form.  From which size on the kernel is ahead is the launcher's business (mlp_run.hip).
+bool bx6i_takes(const Launch &L) {
+    const Params &p = L.p;
+    return L.fmt == G4C_WFMT_BF16X3 && message_form(L) && p.n_layers == 3 && !p.out_bf16 && !p.src[0].bf16;
 }
 
-bool bx6i_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, long long row_count) {
-    // f16x3 mode (three workgroups per CU, shorter pairs): the kernel is ahead from ~20 k rows (6k-node mesh +1 %, 12.5k-node mesh and 2-scale 10k-node mesh +5 %, 25k / 50k-node meshes +6 / +10 %, level-2 launches of the 100k mesh +0.5 %
-    // of the step; the interior launches of a 2- / 4-way partition); bf16x6 mode (two workgroups per CU): from ~300 k
-    constexpr long long BX6I_MIN_ROWS = 400000;
-    const long long min_rows = BX6I_MIN_ROWS;
-    const int mode = bx6i_enable(-1);
-    // (the f16x3 stream goes to the weight-stationary kernel, mlp_ws.hip, which also tracks the fp16 range; this kernel's two-way
-    // instantiation sits at its register limit — one more live register and it spills a hundred — and is no longer launched)
-    if (!mode || round1 || save || f16x2) return false;
-    if (mode == 1 && row_count < min_rows) return false;
-    if (p.n_src != 1 || p.n_nar != 0 || (p.n_add != 0 && p.n_add != 2) || p.n_heads) return false;
-    if (p.n_layers != 3 || p.n_out != NP || p.resid || p.out_bf16) return false;
-    if (p.out_idx && (agg || !p.out)) return false;          // (scattered output rows: the plain launch only)
-    const Src &s = p.src[0];
-    if (s.width != NP || !s.vec || s.seg_off || s.bf16) return false;
-    for (int a = 0; a < p.n_add; ++a)
-        if (p.add[a].width != NP || (p.add[a].ld & 3) || ((uintptr_t)p.add[a].ptr & 15)) return false;
-    if (p.out && ((p.out_ld & 3) || ((uintptr_t)p.out & 15))) return false;
-    if (p.gamma && (((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15))) return false;
-    if (((uintptr_t)p.b & 15)) return false;
-    if (p.M >= (1LL << 31)) return false;
-    return true;
-}
-
-int bx6i_launch(const Params &p, bool agg, bool f16x2, hipStream_t st) {
-    const int n_pairs = (p.n_tiles + 1) / 2;
-    if (n_pairs == 0) return G4C_OK;
-    const dim3 grid(n_pairs), blk(256);
-#define G4C_BX6I_LAUNCH(AGG, SP)                                                                     \
-    do {                                                                                             \
-        if (p.src[0].idx) mlp_bx6i_kernel<AGG, SP, false><<<grid, blk, 0, st>>>(p);                  \
-        else mlp_bx6i_kernel<AGG, SP, true><<<grid, blk, 0, st>>>(p);                                \
-    } while (0)
-    if (f16x2) return G4C_EUNSUPPORTED;
-    if (agg) G4C_BX6I_LAUNCH(true, 3); else G4C_BX6I_LAUNCH(false, 3);
-#undef G4C_BX6I_LAUNCH
+int bx6i_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    ran.kernel = G4C_KERNEL_MLP_BX6I;
+    const dim3 grid((p.n_tiles + 1) / 2), blk(256);          // one workgroup per pair of tiles
+    const bool direct = p.src[0].idx == nullptr;
+    if (L.agg && direct) mlp_bx6i_kernel<true, 3, true><<<grid, blk, 0, st>>>(p);
+    else if (L.agg) mlp_bx6i_kernel<true, 3, false><<<grid, blk, 0, st>>>(p);
+    else if (direct) mlp_bx6i_kernel<false, 3, true><<<grid, blk, 0, st>>>(p);
+    else mlp_bx6i_kernel<false, 3, false><<<grid, blk, 0, st>>>(p);
     return g4c::check_launch("g4c_mlp_run (bx6i)");
 }
 
 }  // namespace g4cm
-
-extern "C" int g4c_mlp_bx6i_enable(int on) { return g4cm::bx6i_enable(on); }

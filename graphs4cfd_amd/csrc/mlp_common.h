@@ -1,5 +1,7 @@
-// Shared declarations of the fused-MLP kernels (mlp_fused.hip: tile kernels, mlp_bx6i.hip: dual-tile kernel, mlp_ws.hip: weight-stationary persistent kernel):
-// launch parameter block, LDS / stream constants, operand split and activation helpers.
+// Shared declarations of the fused-MLP kernels (mlp_fused.hip: fp32 and tile kernels, mlp_bx6i.hip: dual-tile kernel, mlp_ws.hip:
+// weight-stationary persistent kernel, mlp_rs.hip: row-split kernels) and of their launcher (mlp_run.hip: g4c_mlp_run):
+// launch parameter block, LDS / stream constants, operand split and activation helpers, and the host-side launch description
+// (Launch) with the two functions — X_takes, X_launch — through which the launcher sees each kernel family.
 #pragma once
 #include "g4c_common.h"
 #include <type_traits>
@@ -106,7 +108,7 @@ struct Params {
 // Common to every shape other than the generic one: N_SRC weighted sources of fp32 rows, 128 wide, 16-byte aligned, no aggregation on
 // load, no pending activation — the first gathered through an index when IDX0, every other direct; N_NAR narrow blocks (rows = the
 // tile's own); no additive blocks; N_LAYERS 128-wide layers + LayerNorm; plain fp32 output rows (no index, no residual, no fused
-// aggregation); N_HEADS fp32 heads.  The launcher (mlp_launch) picks a shape only when every one of these holds.
+// aggregation); N_HEADS fp32 heads.  The tile family (tile_shape_of, mlp_fused.hip) picks a shape only when every one of these holds.
 //   TileShapeGeneric  nothing fixed: every field of Params is read at run time (the fallback of every launch no shape matches)
 //   TileShapeNode     the MP layers' node update: [aggregate | v], both direct
 //   TileShapeUp       UpMP's MLP: [-e (narrow) | v_coarse[parent] (indexed) | v_fine_old (direct)]
@@ -332,23 +334,58 @@ __device__ __forceinline__ void split3(float x, __bf16 &h, __bf16 &m, __bf16 &l)
     l = (__bf16)(r1 - (float)m);
 }
 
-// dual-tile software-pipelined kernel (mlp_bx6i.hip)
-int bx6i_enable(int on);
-bool bx6i_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, long long row_count);
-int bx6i_launch(const Params &p, bool agg, bool f16x2, hipStream_t st);
+// ---- host side: one g4c_mlp_run call as the launcher (mlp_run.hip) hands it to the kernel families ---------------------------------
+// The launcher's stages check the caller's structs and fill this; every family reads it and nothing else.
+struct Launch {
+    Params p;                // the kernels' parameter block (n_tiles included)
+    NodeParams node;         // g4c_mlp_io_t.upd, the node update fused behind the message launch: filled when has_node, else zeros
+    bool has_node;
+    // g4c_mlp_t.w_format, and what follows from it.  round1: operands rounded to bf16, only the leading plane of the stream is used
+    // (G4C_WFMT_BF16 and the row-split formats); f16x2: the stream holds the two-way fp16 split; bx6: a split-operand (three-plane)
+    // stream, input blocks padded to 128 k (every format but G4C_WFMT_FP32); row_split: a stream in the row-split kernels' k order
+    int fmt;
+    bool round1, f16x2, bx6, row_split;
+    bool agg, save;          // the fused aggregation (io->agg) / the training form (io->n_save)
+    bool all_vec;            // every weighted source is 16-byte addressable (Src::vec)
+    long long row_begin, row_count;
+    int io_n_tiles;          // the caller's io->n_tiles (the aggregation plan's tile count)
+    // the tile kernel's two policy inputs, settled by the launcher's choose step: the deep weight ring of a small launch, and whether
+    // a launch that matches a compile-time shape may run it
+    bool deep_ring, shapes;
+};
+// what a family's launch ran: g4c_mlp_last_kernel() / g4c_mlp_last_shape() of the call
+struct Ran { int kernel = G4C_KERNEL_NONE, shape = G4C_TILE_SHAPE_GENERIC; };
 
-// weight-stationary persistent kernel (mlp_ws.hip): f16x3 stream only
-int ws_enable(int on);
-bool ws_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, long long row_count, bool any_size = false);
-int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const NodeParams *node = nullptr);
-int ws_last_certified();          // 1: the last ws_launch of this thread ran an instantiation without the range tracker
+// What the envelopes of the two column-split message kernels (mlp_bx6i.hip, mlp_ws.hip) share: an inference launch of ONE weighted
+// 128-wide 16-byte addressable block and no or two aligned 128-wide additive blocks, no narrow blocks, heads or residual; 128-wide
+// output rows (fp32 ones 16-byte aligned; scattered through out_idx in the plain launch only); aligned LayerNorm / bias vectors
+inline bool message_form(const Launch &L) {
+    const Params &p = L.p;
+    const Src &s = p.src[0];
+    if (L.save || p.n_src != 1 || p.n_nar != 0 || (p.n_add != 0 && p.n_add != 2) || p.n_heads || p.n_out != NP || p.resid) return false;
+    if (p.out_idx && (L.agg || !p.out)) return false;
+    if (s.width != NP || !s.vec || s.seg_off) return false;
+    for (int a = 0; a < p.n_add; ++a)
+        if (p.add[a].width != NP || (p.add[a].ld & 3) || ((uintptr_t)p.add[a].ptr & (p.add[a].bf16 ? 7 : 15))) return false;
+    if (p.out && !p.out_bf16 && ((p.out_ld & 3) || ((uintptr_t)p.out & 15))) return false;
+    if (p.gamma && (((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15))) return false;
+    return ((uintptr_t)p.b & 15) == 0 && p.M < (1LL << 31);
+}
 
-
-// row-split persistent kernel (mlp_rs.hip, round 6): f16x3 stream, hoisted three-layer message form
-bool rs_eligible(const Params &p, bool agg, long long row_count);
-int rs_launch(const Params &p, bool agg, hipStream_t st);
-bool rs2_eligible(const Params &p, long long row_count);
-int rs2_launch(const Params &p, bool e_natural, hipStream_t st);
+// Every family: X_takes = the envelope of its kernels (capability only: sizes and switches are the launcher's business),
+// X_launch = pick the instantiation, launch it, say which.
+bool split_takes(const Launch &L);           // fp32 kernel (mlp_fused.hip): G4C_WFMT_FP32
+int split_launch(const Launch &L, hipStream_t st, Ran &ran);
+bool tile_takes(const Launch &L);            // tile kernel (mlp_fused.hip): every split-operand stream but the row-split ones
+int tile_launch(const Launch &L, hipStream_t st, Ran &ran);
+bool bx6i_takes(const Launch &L);            // dual-tile software-pipelined kernel (mlp_bx6i.hip): bf16x6 stream only
+int bx6i_launch(const Launch &L, hipStream_t st, Ran &ran);
+bool ws_takes(const Launch &L);              // weight-stationary persistent kernel (mlp_ws.hip): f16x3 and rounded-bf16 streams; io->upd
+int ws_launch(const Launch &L, hipStream_t st, Ran &ran);
+bool rs_takes(const Launch &L);              // row-split persistent kernel (mlp_rs.hip): G4C_WFMT_BF16_RS, hoisted message form
+int rs_launch(const Launch &L, hipStream_t st, Ran &ran);
+bool rs2_takes(const Launch &L);             // ... its update-MLP form: G4C_WFMT_BF16_RS2 / _RS2N
+int rs2_launch(const Launch &L, hipStream_t st, Ran &ran);
 
 // four bf16 values (two dwords as loaded) widened to fp32: a shift / a mask each — exact
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));

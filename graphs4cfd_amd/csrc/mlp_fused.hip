@@ -22,8 +22,6 @@
 //
 // MFMA-bound in fp32: 2*K*128 FLOP per row per layer against ~(K_in + N_out)*4 bytes per row.
 #include "mlp_common.h"
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 using namespace g4cm;
 
@@ -1303,30 +1301,21 @@ extern "C" int g4c_mlp_pack_layer(const float *W, int32_t n_out, int32_t k_in, c
     return g4c::check_launch("g4c_mlp_pack_layer");
 }
 
-static thread_local int g_last_kernel = G4C_KERNEL_NONE;
-extern "C" int g4c_mlp_last_kernel(void) { return g_last_kernel; }
+namespace g4cm {
 
-// launches of at most this many 32-row tiles run the tile kernel's deep-ring instantiation (Ring6)
-static std::atomic<int> g_bx6_deep_tiles{512};
-extern "C" int g4c_mlp_small_launch_tiles(int n_tiles) {
-    const int prev = g_bx6_deep_tiles.load(std::memory_order_relaxed);
-    if (n_tiles >= 0) g_bx6_deep_tiles.store(n_tiles, std::memory_order_relaxed);
-    return prev;
+// ---- the fp32 kernel --------------------------------------------------------------------------------------------------------------------
+bool split_takes(const Launch &L) { return !L.bx6; }
+
+int split_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    ran.kernel = G4C_KERNEL_MLP_SPLIT;
+    if (L.all_vec) mlp_split_kernel<4, true><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
+    else mlp_split_kernel<4, false><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
+    return g4c::check_launch("g4c_mlp_run");
 }
 
-// compile-time launch shapes of the tile kernel (mlp_common.h TileShape*): on by default (-DG4C_TILE_SHAPES_DEFAULT=0: a library for
-// whole-benchmark A/B legs, scripts/ab_bench.sh)
-#ifndef G4C_TILE_SHAPES_DEFAULT
-#define G4C_TILE_SHAPES_DEFAULT 1
-#endif
-static std::atomic<int> g_tile_shapes{G4C_TILE_SHAPES_DEFAULT};
-static thread_local int g_last_shape = G4C_TILE_SHAPE_GENERIC;
-extern "C" int g4c_mlp_shapes_enable(int on) {
-    const int prev = g_tile_shapes.load(std::memory_order_relaxed);
-    if (on >= 0) g_tile_shapes.store(on ? 1 : 0, std::memory_order_relaxed);
-    return prev;
-}
-extern "C" int g4c_mlp_last_shape(void) { return g_last_shape; }
+// ---- the tile kernel --------------------------------------------------------------------------------------------------------------------
+bool tile_takes(const Launch &L) { return L.bx6 && !L.row_split; }
 
 // The shape whose every field this f16x3 inference launch of whole 128-wide aligned blocks on the two-step ring matches, or
 // G4C_TILE_SHAPE_GENERIC.  (`full` has checked: every weighted source 128 wide, fp32 rows on 16-byte boundaries.)
@@ -1351,353 +1340,67 @@ static int tile_shape_of(const Params &p) {
     if (p.n_src == 1 && !idx0 && p.n_heads == 0) return G4C_TILE_SHAPE_DOWN;
     return G;
 }
+
+// The instantiation ladder, in two rungs.  tile_go: (VEC, FULL) of an instantiation whose other parameters are fixed, by how the
+// input blocks can be addressed — whole 128-wide aligned blocks, 16-byte addressable ones, anything.
+template <int SP, bool SAVE, int RD6>
+static void tile_go(const Launch &L, bool full, hipStream_t st) {
+    const Params &p = L.p;
+    const dim3 grid(p.n_tiles), blk(256);
+    if (full) mlp_bx6_kernel<1, true, true, SP, SAVE, RD6><<<grid, blk, 0, st>>>(p);
+    else if (L.all_vec) mlp_bx6_kernel<1, true, false, SP, SAVE, RD6><<<grid, blk, 0, st>>>(p);
+    else mlp_bx6_kernel<1, false, false, SP, SAVE, RD6><<<grid, blk, 0, st>>>(p);
+}
+// ... of the instantiations that exist for whole blocks only (f16x3 inference): a compile-time shape on the two-step ring — tracked,
+// or certified where the shape has a tracker-free form — and the tracker-free generic kernel on either ring
 template <bool TRACK>
-static void launch_tile_shape(int shape, const Params &p, dim3 grid, dim3 blk, hipStream_t st) {
-#define G4C_SHAPED(...) mlp_bx6_kernel<1, true, true, 2, false, 2, TRACK, __VA_ARGS__><<<grid, blk, 0, st>>>(p)
+static void tile_go_full(int shape, const Launch &L, hipStream_t st) {
+    const Params &p = L.p;
+#define G4C_FULL(RD6, ...) mlp_bx6_kernel<1, true, true, 2, false, RD6, TRACK, __VA_ARGS__><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p)
     const bool l3 = p.n_layers == 3, h2 = p.n_heads == 2;
     if (shape == G4C_TILE_SHAPE_NODE) {
-        if (l3) { if (h2) G4C_SHAPED(TileShapeNode<3, 2>); else G4C_SHAPED(TileShapeNode<3, 0>); }
-        else { if (h2) G4C_SHAPED(TileShapeNode<2, 2>); else G4C_SHAPED(TileShapeNode<2, 0>); }
+        if (l3) { if (h2) G4C_FULL(2, TileShapeNode<3, 2>); else G4C_FULL(2, TileShapeNode<3, 0>); }
+        else { if (h2) G4C_FULL(2, TileShapeNode<2, 2>); else G4C_FULL(2, TileShapeNode<2, 0>); }
     } else if constexpr (TRACK) {
         if (shape == G4C_TILE_SHAPE_UP) {
-            if (l3) { if (h2) G4C_SHAPED(TileShapeUp<3, 2>); else G4C_SHAPED(TileShapeUp<3, 0>); }
-            else { if (h2) G4C_SHAPED(TileShapeUp<2, 2>); else G4C_SHAPED(TileShapeUp<2, 0>); }
+            if (l3) { if (h2) G4C_FULL(2, TileShapeUp<3, 2>); else G4C_FULL(2, TileShapeUp<3, 0>); }
+            else { if (h2) G4C_FULL(2, TileShapeUp<2, 2>); else G4C_FULL(2, TileShapeUp<2, 0>); }
         } else {
-            if (l3) G4C_SHAPED(TileShapeDown<3>); else G4C_SHAPED(TileShapeDown<2>);
+            if (l3) G4C_FULL(2, TileShapeDown<3>); else G4C_FULL(2, TileShapeDown<2>);
         }
+    } else {
+        if (L.deep_ring) G4C_FULL(8, TileShapeGeneric); else G4C_FULL(2, TileShapeGeneric);
     }
-#undef G4C_SHAPED
+#undef G4C_FULL
+}
+// The other rung: (SAVE, RD6) of a split SP — the training form on the two-step ring; inference on the deep ring when the launch is small
+template <int SP>
+static void tile_go_sp(const Launch &L, bool full, hipStream_t st) {
+    if (L.save) tile_go<SP, true, 2>(L, full, st);
+    else if (L.deep_ring) tile_go<SP, false, 8>(L, full, st);
+    else tile_go<SP, false, 2>(L, full, st);
 }
 
-static int mlp_launch(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows, const g4c_mlp_io_t *io,
-                      void *stream) {
-    g_last_kernel = G4C_KERNEL_NONE;
-    g_last_shape = G4C_TILE_SHAPE_GENERIC;
-    G4C_REQUIRE(io && io->size == (int32_t)sizeof(g4c_mlp_io_t), G4C_EINVAL,
-                "g4c_mlp_run: io->size %d, this library's g4c_mlp_io_t has %d bytes (a binding out of step with g4c.h)", io ? io->size : 0,
-                (int)sizeof(g4c_mlp_io_t));
-    G4C_REQUIRE(mlp && srcs, G4C_EINVAL, "g4c_mlp_run: null pointer");
-    const int fmt = mlp->w_format;
-    G4C_REQUIRE(fmt >= G4C_WFMT_FP32 && fmt <= G4C_WFMT_BF16, G4C_EINVAL, "g4c_mlp_run: unknown w_format %d", fmt);
-    const bool rs_fmt = fmt == G4C_WFMT_BF16_RS;     // the rounded-bf16 stream in the row-split kernel's k order: that kernel only
-    const bool rs2_fmt = fmt == G4C_WFMT_BF16_RS2 || fmt == G4C_WFMT_BF16_RS2N;     // ... its update-MLP form
-    const bool round1 = fmt == G4C_WFMT_BF16 || rs_fmt || rs2_fmt;     // operands rounded to bf16: only the leading plane of the stream is used
-    const bool f16x2 = fmt == G4C_WFMT_F16X2;    // the stream holds the two-way fp16 split
-    const bool bx6 = fmt != G4C_WFMT_FP32;       // the three-plane stream, input blocks padded to 128 k
-    const int wbytes = bx6 ? 6 : 4;
-    const int64_t row_begin = io->row_begin, row_count = io->row_count;
-    G4C_REQUIRE(row_begin >= 0 && row_count >= 0 && row_begin + row_count <= n_rows && row_begin % 32 == 0, G4C_EINVAL,
-                "g4c_mlp_run: bad row range [%lld, +%lld) of %lld (row_begin must be a multiple of 32)", (long long)row_begin,
-                (long long)row_count, (long long)n_rows);
-    G4C_REQUIRE(n_src >= 1 && n_src <= G4C_MAX_SRC, G4C_EUNSUPPORTED, "g4c_mlp_run: %d sources (max %d)", n_src, G4C_MAX_SRC);
-    G4C_REQUIRE(mlp->n_layers >= 1 && mlp->n_layers <= G4C_MAX_LAYERS, G4C_EUNSUPPORTED,
-                "g4c_mlp_run: %d layers (supported 1..%d)", mlp->n_layers, G4C_MAX_LAYERS);
-    G4C_REQUIRE(n_rows >= 0 && n_rows < (1LL << 31), G4C_EINVAL, "g4c_mlp_run: n_rows %lld out of range", (long long)n_rows);
-    const int act = io->act;
-    G4C_REQUIRE(act >= 0 && act <= 2, G4C_EINVAL, "g4c_mlp_run: bad activation %d", act);
-    const bool agg = io->agg != nullptr, save = io->n_save != 0, node = io->upd != nullptr;
-    const int n_heads = io->n_heads;
-    G4C_REQUIRE(n_heads >= 0 && n_heads <= G4C_MAX_HEADS, G4C_EINVAL, "g4c_mlp_run: bad heads (n=%d)", n_heads);
-    G4C_REQUIRE((row_begin == 0 && row_count == n_rows) || (!agg && !save && !node && !n_heads && !io->out_dtype), G4C_EUNSUPPORTED,
-                "g4c_mlp_run: a row sub-range needs a plain launch (no heads / aggregation / save / upd / out_dtype)");
-    G4C_REQUIRE(!agg || (io->tile_rows && io->tile_seg && io->seg_off && io->n_tiles >= 0 && io->agg_ld >= NP), G4C_EINVAL,
-                "g4c_mlp_run: bad aggregation plan");
-    G4C_REQUIRE(io->out_dtype == G4C_DTYPE_F32 || io->out_dtype == G4C_DTYPE_BF16 || io->out_dtype == G4C_DTYPE_BF16_SELU, G4C_EINVAL,
-                "g4c_mlp_run: unknown out_dtype %d", io->out_dtype);
-    G4C_REQUIRE(io->out_dtype != G4C_DTYPE_BF16_SELU || (agg && act == G4C_ACT_NONE), G4C_EINVAL,
-                "g4c_mlp_run: G4C_DTYPE_BF16_SELU needs the fused aggregation and no output activation");
-    G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 || io->head_dtype == G4C_DTYPE_BF16, G4C_EINVAL, "g4c_mlp_run: unknown head_dtype %d", io->head_dtype);
-    G4C_REQUIRE(!io->range_flag || (mlp->range_slot >= 0 && (!node || io->upd->range_slot >= 0)), G4C_EINVAL,
-                "g4c_mlp_run: negative range_slot (mlp %d, upd %d)", mlp->range_slot, node ? io->upd->range_slot : 0);
-    if (n_rows == 0) return G4C_OK;
-    float *const out = (float *)io->out;
-    const int32_t out_ld = io->out_ld;
-    const float *const resid = io->resid;
-    const int32_t *const out_idx = io->out_idx;
-    G4C_REQUIRE(out || agg, G4C_EINVAL, "g4c_mlp_run: null output");
-    g4c::DeviceGuard on_device(mlp->w[0]);
-    Params p;
-    int kp = 0;
-    bool all_vec = true;
-    int nk = 0;
-    p.n_add = 0;
-    p.n_nar = 0;
-    for (int s = 0; s < n_src; ++s) {
-        const g4c_src_t &g = srcs[s];
-        G4C_REQUIRE(g.ptr && g.width > 0 && g.ld >= g.col0 + g.width && g.col0 >= 0, G4C_EINVAL,
-                    "g4c_mlp_run: bad source %d (width=%d ld=%d col0=%d)", s, g.width, g.ld, g.col0);
-        if (g.additive == 2) {
-            G4C_REQUIRE(bx6, G4C_EUNSUPPORTED, "g4c_mlp_run: narrow sources (additive == 2) need a split-operand w_format");
-            G4C_REQUIRE(g.width <= G4C_NARROW_MAX && !g.idx && g.pre_act == G4C_ACT_NONE && g.w && ((uintptr_t)g.w & 15) == 0, G4C_EINVAL,
-                        "g4c_mlp_run: bad narrow source %d (width %d <= %d, no index, no pre_act, 16-byte aligned weights)", s,
-                        g.width, G4C_NARROW_MAX);
-            NarSrc &a = p.nar[p.n_nar++];
-            a.ptr = g.ptr + g.col0; a.w = g.w; a.width = g.width; a.ld = g.ld;
-            continue;
-        }
-        if (g.additive) {
-            G4C_REQUIRE(g.pre_act == G4C_ACT_NONE && g.width <= NP && (g.dtype == G4C_DTYPE_F32 || g.dtype == G4C_DTYPE_BF16), G4C_EINVAL,
-                        "g4c_mlp_run: bad additive source %d", s);
-            AddSrc &a = p.add[p.n_add++];
-            a.idx = g.idx; a.width = g.width; a.ld = g.ld; a.bf16 = g.dtype == G4C_DTYPE_BF16;
-            if (a.bf16) {
-                G4C_REQUIRE(round1 && g.width == NP && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 8 == 0, G4C_EUNSUPPORTED,
-                            "g4c_mlp_run: bf16 additive rows need the rounded-bf16 mode (w_format G4C_WFMT_BF16*) and a 128-wide, 8-byte aligned block");
-                a.ptr = reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(g.ptr) + g.col0);
-            } else {
-                a.ptr = g.ptr + g.col0;
-            }
-            continue;
-        }
-        G4C_REQUIRE(g.pre_act == G4C_ACT_NONE || g.pre_act == G4C_ACT_SELU, G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: source %d pre_act %d (only NONE / SELU can be applied on load)", s, g.pre_act);
-        Src &d = p.src[nk++];
-        if (bx6) G4C_REQUIRE(g.width <= NP, G4C_EUNSUPPORTED, "g4c_mlp_run: input block %d is %d wide (max 128 in a split-operand w_format)", s, g.width);
-        d.ptr = g.ptr; d.idx = g.idx; d.width = g.width; d.wpad = bx6 ? NP : (g.width + KC - 1) / KC * KC; d.ld = g.ld; d.col0 = g.col0;
-        d.pre_act = g.pre_act;
-        d.bf16 = g.dtype == G4C_DTYPE_BF16;
-        if (d.bf16)
-            G4C_REQUIRE(round1 && g.width == NP && !g.seg_off && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 8 == 0, G4C_EUNSUPPORTED,
-                        "g4c_mlp_run: bf16 rows need the rounded-bf16 mode (w_format G4C_WFMT_BF16*) and a 128-wide, 8-byte aligned block");
-        else
-            G4C_REQUIRE(g.dtype == G4C_DTYPE_F32, G4C_EINVAL, "g4c_mlp_run: source %d has unknown dtype %d", s, g.dtype);
-        d.seg_off = g.seg_off; d.seg_mean = g.seg_mean; d.seg_perm = g.seg_off ? g.seg_perm : nullptr;
-        if (g.seg_off)
-            G4C_REQUIRE(bx6 && !g.idx && g.width == NP && g.ld % 4 == 0 && g.col0 % 4 == 0 && (uintptr_t)g.ptr % 16 == 0, G4C_EUNSUPPORTED,
-                        "g4c_mlp_run: aggregation on load needs a split-operand w_format and a 128-wide aligned block without gather index");
-        d.vec = (g.width % 4 == 0) && (g.ld % 4 == 0) && (g.col0 % 4 == 0) && ((uintptr_t)g.ptr % (d.bf16 ? 8 : 16) == 0);
-        all_vec = all_vec && d.vec;
-        kp += d.wpad;
-    }
-    G4C_REQUIRE(nk >= 1 || p.n_nar >= 1, G4C_EINVAL, "g4c_mlp_run: no input block goes through the weights");
-    p.n_src = nk;
-    if (nk == 0) p.src[0] = Src{nullptr, nullptr, 0, 0, 0, 0, 1, 0, nullptr, 0, nullptr, 0};
-    for (int s = (nk ? nk : 1); s < G4C_MAX_SRC; ++s) p.src[s] = p.src[0];
-    for (int s = p.n_nar; s < G4C_MAX_SRC; ++s) p.nar[s] = NarSrc{nullptr, nullptr, 0, 0};
-    for (int s = p.n_add; s < G4C_MAX_SRC; ++s) p.add[s] = AddSrc{nullptr, nullptr, 0, 0, 0};
-    G4C_REQUIRE(kp == mlp->k_pad[0], G4C_EINVAL, "g4c_mlp_run: sources give %d padded columns, layer 1 packed for %d", kp, mlp->k_pad[0]);
-    p.n_layers = mlp->n_layers;
-    p.chunks0 = kp / KC;
-    for (int l = 0; l < mlp->n_layers; ++l) {
-        G4C_REQUIRE(mlp->n_pad[l] == NP, G4C_EINVAL, "g4c_mlp_run: layer %d n_pad %d (must be 128)", l, mlp->n_pad[l]);
-        if (l > 0) G4C_REQUIRE(mlp->k_pad[l] == NP, G4C_EINVAL, "g4c_mlp_run: layer %d k_pad %d (must be 128)", l, mlp->k_pad[l]);
-        // one contiguous stream: layer l starts where layer l-1 ends
-        if (l > 0) G4C_REQUIRE((const char *)mlp->w[l] == (const char *)mlp->w[l - 1] + (size_t)mlp->k_pad[l - 1] * NP * wbytes, G4C_EINVAL,
-                               "g4c_mlp_run: packed layers must be contiguous (layer %d)", l);
-        if (l > 0) G4C_REQUIRE((const float *)mlp->b[l] == (const float *)mlp->b[l - 1] + NP, G4C_EINVAL,
-                               "g4c_mlp_run: padded biases must be contiguous (layer %d)", l);
-    }
-    p.w = (const float *)mlp->w[0];
-    p.b = (const float *)mlp->b[0];
-    G4C_REQUIRE(p.w && p.b, G4C_EINVAL, "g4c_mlp_run: null weights");
-    p.gamma = mlp->ln_gamma; p.beta = mlp->ln_beta; p.eps = mlp->ln_eps;
-    G4C_REQUIRE((p.gamma == nullptr) == (p.beta == nullptr), G4C_EINVAL, "g4c_mlp_run: LayerNorm needs both gamma and beta");
-    p.n_out = mlp->n_out;
-    G4C_REQUIRE(p.n_out > 0 && p.n_out <= NP && out_ld >= p.n_out, G4C_EINVAL, "g4c_mlp_run: n_out=%d out_ld=%d", p.n_out, out_ld);
-    p.M = n_rows;
-    p.out = out; p.out_ld = out_ld; p.out_idx = out_idx; p.act = act;
-    p.out_bf16 = 0;
-    p.resid = resid; p.resid_ld = io->resid_ld; p.resid_col0 = io->resid_col0;
-    p.tile_rows = p.tile_seg = p.seg_off = nullptr; p.agg = nullptr; p.agg_ld = 0; p.agg_mean = 0; p.agg_deg = 0; p.agg_bf16 = 0;
-    if (agg) {
-        G4C_REQUIRE(bx6 && mlp->n_out == NP && !out_idx && !resid, G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: the fused aggregation needs a split-operand w_format and a plain 128-wide output");
-        const int32_t mode = io->agg_mode;
-        p.tile_rows = io->tile_rows; p.tile_seg = io->tile_seg; p.seg_off = io->seg_off;
-        p.agg = (float *)io->agg; p.agg_ld = io->agg_ld; p.agg_mean = mode & 1; p.agg_deg = (mode >> 8) & 0xff; p.agg_bf16 = (mode >> 16) & 1;
-        G4C_REQUIRE((mode >> 17) == 0 && (!p.agg_bf16 || rs_fmt) && p.agg_deg <= 32 && (p.agg_deg == 0 || row_count % p.agg_deg == 0), G4C_EINVAL,
-                    "fused aggregation: agg_mode = %d is not 0 / 1 [| G4C_AGG_UNIFORM(k), 1 <= k <= 32, k dividing the %lld rows]", mode,
-                    (long long)row_count);
-    }
-    if (io->out_dtype) {
-        G4C_REQUIRE(round1 && !resid && !out_idx && p.n_out == NP && (!out || ((out_ld & 3) == 0 && ((uintptr_t)out & 7) == 0)), G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: bf16 output rows need the rounded-bf16 mode, a plain 128-wide output, out_ld a multiple of 4 and an 8-byte aligned out");
-        p.out_bf16 = io->out_dtype;
-    }
-    for (int l = 0; l < G4C_MAX_LAYERS; ++l) { p.save[l] = nullptr; p.mul[l] = nullptr; }
-    p.save_ld = 0; p.mul_ld = 0;
-    if (save) {
-        // (the rounded-bf16 stream saves on the plain tile kernel only: the row-split streams keep refusing; saved / mul rows stay fp32)
-        G4C_REQUIRE(bx6 && (!round1 || fmt == G4C_WFMT_BF16) && !io->out_dtype && !agg && !n_heads && !out_idx && io->save_ld >= NP &&
-                        (io->save_ld & 3) == 0,
-                    G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: save needs w_format BF16X3 / F16X2 / BF16 without heads / aggregation / output index / bf16 rows, save_ld >= 128 "
-                    "and a multiple of 4");
-        G4C_REQUIRE(io->n_save == mlp->n_layers, G4C_EINVAL, "g4c_mlp_run: n_save %d for %d layers", io->n_save, mlp->n_layers);
-        bool mul = false;
-        for (int l = 0; l < mlp->n_layers; ++l) {
-            G4C_REQUIRE(((uintptr_t)io->save[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: save[%d] is not 16-byte aligned", l);
-            p.save[l] = io->save[l];
-            if (l + 1 == mlp->n_layers) break;
-            G4C_REQUIRE(((uintptr_t)io->mul[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: mul[%d] is not 16-byte aligned", l);
-            p.mul[l] = io->mul[l];
-            mul = mul || io->mul[l];
-        }
-        p.save_ld = io->save_ld;
-        G4C_REQUIRE(!mul || (io->mul_ld >= NP && (io->mul_ld & 3) == 0), G4C_EINVAL, "g4c_mlp_run: mul_ld=%d", io->mul_ld);
-        p.mul_ld = io->mul_ld;
-    }
-    // the caller's certificate (g4c_mlp_t.range_certified): every MLP of the launch, the f16x3 stream, no save / mul — then nothing is tracked
-    p.range_certified = (f16x2 && mlp->range_certified && !save && (!node || io->upd->range_certified)) ? 1 : 0;
-    p.range_flag = (f16x2 && !p.range_certified) ? io->range_flag : nullptr; p.range_slot = mlp->range_slot;
-    // heads (the kernels read their weights where the stream of the MLP that owns them ends; with `upd`, that MLP's)
-    for (int hd = 0; hd < n_heads; ++hd) G4C_REQUIRE(io->head_out[hd], G4C_EINVAL, "g4c_mlp_run: null head output %d", hd);
-    p.n_heads = node ? 0 : n_heads; p.head_ld = p.n_heads ? io->head_ld : 0; p.head_bf16 = 0;
-    for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) p.head_out[hd] = hd < p.n_heads ? (float *)io->head_out[hd] : nullptr;
-    if (p.n_heads && io->head_dtype) {
-        G4C_REQUIRE(round1 && (p.head_ld & 1) == 0, G4C_EUNSUPPORTED, "g4c_mlp_run: bf16 head rows need the rounded-bf16 mode and an even head_ld");
-        for (int hd = 0; hd < n_heads; ++hd)
-            G4C_REQUIRE(((uintptr_t)io->head_out[hd] & 3) == 0, G4C_EINVAL, "g4c_mlp_run: head output %d is not 4-byte aligned", hd);
-        p.head_bf16 = 1;
-    }
-    if (p.n_heads) {
-        G4C_REQUIRE(!agg, G4C_EUNSUPPORTED, "g4c_mlp_run: heads with the fused aggregation");
-        G4C_REQUIRE((p.head_ld & 3) == 0 || !bx6, G4C_EINVAL, "g4c_mlp_run: head outputs need a leading dimension that is a multiple of 4");
-        G4C_REQUIRE(p.n_out == NP && !resid && !out_idx && p.head_ld >= NP, G4C_EINVAL,
-                    "g4c_mlp_run: heads need a 128-wide output without residual / output index (n_out=%d)", p.n_out);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (row_count == 0) return G4C_OK;
-    p.row_base = row_begin;
-    p.M = row_begin + row_count;          // rows past the range are neither gathered nor stored
-    if (node) {
-        // one launch per MP layer: the message MLP on the weight-stationary kernel, the node update behind it (mlp_ws.hip, NODE)
-        const g4c_mlp_t *u = io->upd;
-        G4C_REQUIRE(f16x2 && agg && u->w_format == G4C_WFMT_F16X2 && act == G4C_ACT_NONE, G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: the fused node update needs the f16x3 format (G4C_WFMT_F16X2) for both MLPs, the aggregation plan and act NONE");
-        G4C_REQUIRE(u->n_layers == mlp->n_layers && u->k_pad[0] == 2 * NP && u->n_out == NP && u->w[0] && u->b[0], G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: upd must have the message MLP's depth (%d), two 128-wide input blocks and a 128-wide output",
-                    mlp->n_layers);
-        for (int l = 0; l < u->n_layers; ++l) {
-            G4C_REQUIRE(u->n_pad[l] == NP && (l == 0 || u->k_pad[l] == NP), G4C_EUNSUPPORTED, "g4c_mlp_run: upd layer %d is not 128 wide", l);
-            if (l > 0) G4C_REQUIRE((const char *)u->w[l] == (const char *)u->w[l - 1] + (size_t)u->k_pad[l - 1] * NP * 6 &&
-                                   (const float *)u->b[l] == (const float *)u->b[l - 1] + NP, G4C_EINVAL,
-                                   "g4c_mlp_run: upd's packed layers / biases must be contiguous (layer %d)", l);
-        }
-        G4C_REQUIRE((u->ln_gamma == nullptr) == (u->ln_beta == nullptr), G4C_EINVAL, "g4c_mlp_run: upd's LayerNorm needs both gamma and beta");
-        G4C_REQUIRE(!u->ln_gamma || (((uintptr_t)u->ln_gamma & 15) == 0 && ((uintptr_t)u->ln_beta & 15) == 0), G4C_EINVAL,
-                    "g4c_mlp_run: upd's LayerNorm parameters must be 16-byte aligned");
-        G4C_REQUIRE(io->v && io->v_out && (io->v_ld & 3) == 0 && io->v_ld >= NP && (io->v_out_ld & 3) == 0 && io->v_out_ld >= NP &&
-                    ((uintptr_t)io->v & 15) == 0 && ((uintptr_t)io->v_out & 15) == 0 && (io->agg_ld & 3) == 0 && ((uintptr_t)io->agg & 15) == 0,
-                    G4C_EINVAL, "g4c_mlp_run: v / v_out / agg need 16-byte aligned rows of at least 128 columns");
-        G4C_REQUIRE(io->v_act >= 0 && io->v_act <= 2, G4C_EINVAL, "g4c_mlp_run: bad v_act %d", io->v_act);
-        NodeParams q{};
-        q.v = io->v; q.v_ld = io->v_ld; q.w = (const float *)u->w[0]; q.b = (const float *)u->b[0];
-        q.gamma = u->ln_gamma; q.beta = u->ln_beta; q.eps = u->ln_eps; q.act = io->v_act;
-        q.out = io->v_out; q.out_ld = io->v_out_ld; q.n_heads = n_heads; q.head_ld = io->head_ld;
-        q.range_flag = p.range_certified ? nullptr : io->range_flag; q.range_slot = u->range_slot;
-        for (int hd = 0; hd < G4C_MAX_HEADS; ++hd) q.head_out[hd] = nullptr;
-        if (n_heads) {
-            G4C_REQUIRE(io->head_dtype == G4C_DTYPE_F32 && (io->head_ld & 3) == 0 && io->head_ld >= NP, G4C_EINVAL,
-                        "g4c_mlp_run: upd's heads need fp32 rows, head_ld a multiple of 4 and >= 128");
-            for (int hd = 0; hd < n_heads; ++hd) {
-                G4C_REQUIRE(((uintptr_t)io->head_out[hd] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: bad head output %d", hd);
-                q.head_out[hd] = (float *)io->head_out[hd];
-            }
-        }
-        G4C_REQUIRE(ws_eligible(p, false, true, false, true, row_count, true), G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: the message launch of the fused MP layer is outside the weight-stationary kernel's envelope (one 128-wide "
-                    "weighted block, two 128-wide additive blocks, two or three 128-wide layers, aligned rows)");
-        p.n_tiles = io->n_tiles;
-        if (p.n_tiles == 0) return G4C_OK;
-        const int rc = ws_launch(p, true, false, st, &q);
-        g_last_kernel = ws_last_certified() ? G4C_KERNEL_MLP_WS_CERT : G4C_KERNEL_MLP_WS;
-        return rc;
-    }
-    if (rs_fmt) {
-        // row-split persistent kernel (mlp_rs.hip): a wave owns 16 rows through all layers, the weights stay in LDS, bf16 rows in its
-        // own column order.  A stream in its k order can run on no other kernel: outside its envelope the call fails instead of
-        // computing something else.
-        G4C_REQUIRE(!save && rs_eligible(p, agg, row_count), G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: weights packed for the row-split kernel (G4C_WFMT_BF16_RS), launch outside its envelope");
-        g_last_kernel = G4C_KERNEL_MLP_RS;
-        return rs_launch(p, agg, st);
-    }
-    if (rs2_fmt) {
-        G4C_REQUIRE(!save && !agg && rs2_eligible(p, row_count), G4C_EUNSUPPORTED,
-                    "g4c_mlp_run: weights packed for the row-split update kernel (G4C_WFMT_BF16_RS2), launch outside its envelope");
-        g_last_kernel = G4C_KERNEL_MLP_RS2;
-        return rs2_launch(p, fmt == G4C_WFMT_BF16_RS2N, st);
-    }
-    if (bx6 && ws_eligible(p, round1, agg, save, f16x2, row_count)) {
-        // weight-stationary persistent kernel (mlp_ws.hip): pairs of 32-row tiles (whole segments with aggregation), one workgroup per CU
-        // (uniform segments, G4C_AGG_UNIFORM: ws_launch's dense mode derives segments as row / k over [0, p.M) and cannot honour a
-        // sub-range — refused like rs_eligible does.  A guard only: a launch with an aggregation covers all its rows.)
-        G4C_REQUIRE(!(agg && p.agg_deg >= 4 && p.agg_deg <= 8) || row_begin == 0, G4C_EINVAL,
-                    "g4c_mlp_run: uniform segments (G4C_AGG_UNIFORM) need the whole row range, got rows [%lld, %lld)",
-                    (long long)row_begin, (long long)p.M);
-        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
-        if (p.n_tiles == 0) return G4C_OK;          // (nothing launches: g4c_mlp_last_kernel stays G4C_KERNEL_NONE — ADVICE r04)
-        const int rc = ws_launch(p, agg, round1, st);
-        g_last_kernel = ws_last_certified() ? G4C_KERNEL_MLP_WS_CERT : G4C_KERNEL_MLP_WS;
-        return rc;
-    } else if (bx6 && bx6i_eligible(p, round1, agg, save, f16x2, row_count)) {
-        // dual-tile software-pipelined kernel (mlp_bx6i.hip): pairs of 32-row tiles (whole segments with aggregation)
-        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
-        if (p.n_tiles == 0) return G4C_OK;
-        g_last_kernel = G4C_KERNEL_MLP_BX6I;
-        return bx6i_launch(p, agg, f16x2, st);
-    } else if (bx6) {
-        bool full = all_vec;
-        for (int s2 = 0; s2 < p.n_src; ++s2) full = full && p.src[s2].width == NP;
-        for (int a = 0; a < p.n_add; ++a)
-            full = full && p.add[a].width == NP && (p.add[a].ld & 3) == 0 && ((uintptr_t)p.add[a].ptr & (p.add[a].bf16 ? 7 : 15)) == 0;
-        const dim3 blk(256);
-        p.n_tiles = agg ? io->n_tiles : (int)((row_count + 31) / 32);
-        if (p.n_tiles == 0) return G4C_OK;
-        g_last_kernel = G4C_KERNEL_MLP_BX6;
-        const dim3 grid(p.n_tiles);
-        const bool deep = p.n_tiles <= g_bx6_deep_tiles;          // (small launch: whole-block weight ring, see Ring6)
-#define G4C_BX6_LAUNCH(RT, SP)                                                                         \
-        do {                                                                                           \
-            if (deep) {                                                                                \
-                if (full) mlp_bx6_kernel<RT, true, true, SP, false, 8><<<grid, blk, 0, st>>>(p);       \
-                else if (all_vec) mlp_bx6_kernel<RT, true, false, SP, false, 8><<<grid, blk, 0, st>>>(p); \
-                else mlp_bx6_kernel<RT, false, false, SP, false, 8><<<grid, blk, 0, st>>>(p);          \
-            } else if (full) mlp_bx6_kernel<RT, true, true, SP><<<grid, blk, 0, st>>>(p);              \
-            else if (all_vec) mlp_bx6_kernel<RT, true, false, SP><<<grid, blk, 0, st>>>(p);            \
-            else mlp_bx6_kernel<RT, false, false, SP><<<grid, blk, 0, st>>>(p);                        \
-        } while (0)
-        if (save && f16x2) {
-            if (full) mlp_bx6_kernel<1, true, true, 2, true><<<grid, blk, 0, st>>>(p);
-            else if (all_vec) mlp_bx6_kernel<1, true, false, 2, true><<<grid, blk, 0, st>>>(p);
-            else mlp_bx6_kernel<1, false, false, 2, true><<<grid, blk, 0, st>>>(p);
-        } else if (save && round1) {          // (mixed-precision training: one product per element, fp32 save / mul rows)
-            if (full) mlp_bx6_kernel<1, true, true, 1, true><<<grid, blk, 0, st>>>(p);
-            else if (all_vec) mlp_bx6_kernel<1, true, false, 1, true><<<grid, blk, 0, st>>>(p);
-            else mlp_bx6_kernel<1, false, false, 1, true><<<grid, blk, 0, st>>>(p);
-        } else if (save) {
-            if (full) mlp_bx6_kernel<1, true, true, 3, true><<<grid, blk, 0, st>>>(p);
-            else if (all_vec) mlp_bx6_kernel<1, true, false, 3, true><<<grid, blk, 0, st>>>(p);
-            else mlp_bx6_kernel<1, false, false, 3, true><<<grid, blk, 0, st>>>(p);
-        }
-        else if (f16x2 && full && !deep && g_tile_shapes.load(std::memory_order_relaxed) && tile_shape_of(p) != G4C_TILE_SHAPE_GENERIC) {
-            // (a launch every field of which matches a compile-time shape: same kernel code, tracked or certified)
-            g_last_shape = tile_shape_of(p);
-            if (p.range_certified) { g_last_kernel = G4C_KERNEL_MLP_BX6_CERT; launch_tile_shape<false>(g_last_shape, p, grid, blk, st); }
-            else launch_tile_shape<true>(g_last_shape, p, grid, blk, st);
-        }
-        else if (f16x2 && p.range_certified && full) {
-            // (the tracker-free instantiations: whole 128-wide aligned blocks — every launch of a model's MP layers, pools and unpools)
-            g_last_kernel = G4C_KERNEL_MLP_BX6_CERT;
-            if (deep) mlp_bx6_kernel<1, true, true, 2, false, 8, false><<<grid, blk, 0, st>>>(p);
-            else mlp_bx6_kernel<1, true, true, 2, false, 2, false><<<grid, blk, 0, st>>>(p);
-        }
-        else if (f16x2) G4C_BX6_LAUNCH(1, 2);
-        else if (round1) G4C_BX6_LAUNCH(1, 1);
-        else G4C_BX6_LAUNCH(1, 3);
-#undef G4C_BX6_LAUNCH
-    } else {
-        p.n_tiles = (int)((row_count + 31) / 32);
-        g_last_kernel = G4C_KERNEL_MLP_SPLIT;
-        if (all_vec) mlp_split_kernel<4, true><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
-        else mlp_split_kernel<4, false><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p);
-    }
+int tile_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    bool full = L.all_vec;
+    for (int s2 = 0; s2 < p.n_src; ++s2) full = full && p.src[s2].width == NP;
+    for (int a = 0; a < p.n_add; ++a)
+        full = full && p.add[a].width == NP && (p.add[a].ld & 3) == 0 && ((uintptr_t)p.add[a].ptr & (p.add[a].bf16 ? 7 : 15)) == 0;
+    const bool infer_full = L.f16x2 && !L.save && full;
+    // (a launch every field of which matches a compile-time shape: same kernel code, tracked or certified)
+    const int shape = infer_full && !L.deep_ring && L.shapes ? tile_shape_of(p) : G4C_TILE_SHAPE_GENERIC;
+    // (the tracker-free instantiations: whole 128-wide aligned blocks — every launch of a model's MP layers, pools and unpools)
+    const bool cert = infer_full && p.range_certified;
+    ran.kernel = cert ? G4C_KERNEL_MLP_BX6_CERT : G4C_KERNEL_MLP_BX6;
+    ran.shape = shape;
+    if (cert) tile_go_full<false>(shape, L, st);
+    else if (shape != G4C_TILE_SHAPE_GENERIC) tile_go_full<true>(shape, L, st);
+    else if (L.f16x2) tile_go_sp<2>(L, full, st);
+    else if (L.round1) tile_go_sp<1>(L, full, st);          // (with save: mixed-precision training, one product per element, fp32 save / mul rows)
+    else tile_go_sp<3>(L, full, st);
     return g4c::check_launch("g4c_mlp_run");
 }
 
-extern "C" int g4c_mlp_run(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64_t n_rows, const g4c_mlp_io_t *io,
-                           void *stream) {
-    return mlp_launch(mlp, srcs, n_src, n_rows, io, stream);
-}
+}  // namespace g4cm
 #endif  // G4C_TILE_ISA_ONLY

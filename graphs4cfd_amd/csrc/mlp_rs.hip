@@ -36,7 +36,7 @@
 //         mean.  Fixed order, deterministic; NOT the sequential order of g4c_segment_reduce (last-bit differences: tests allow 1e-6).
 //         AGG = 2 (G4C_AGG_OUT_BF16): the aggregate is stored as bf16 rows in the same column order — what its one reader, the update
 //         MLP of the layer, rounds it to on load anyway (same operand, half the bytes of two launches).
-// Envelope (rs_eligible): rounded-bf16 stream in this kernel's k order, ONE weighted 128-wide direct block (fp32 with optional SELU on
+// Envelope (rs_takes): rounded-bf16 stream in this kernel's k order, ONE weighted 128-wide direct block (fp32 with optional SELU on
 // load, or bf16), two additive 128-wide blocks through indices, two or three 128-wide layers, LayerNorm, no output activation / residual /
 // heads / output index.  A stream in this k order runs on no other kernel: outside the envelope the call fails.
 #include "mlp_common.h"
@@ -558,7 +558,15 @@ __global__ __launch_bounds__(RS_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2
 
 namespace g4cm {
 
-bool rs_eligible(const Params &p, bool agg, long long row_count) {
+// persistent workgroups: a wave owns chunks of 16 rows, at most one workgroup per CU
+static unsigned rs_grid(const Params &p) {
+    const long long chunks = (p.M + 15) / 16, want = (chunks + RS_WAVES - 1) / RS_WAVES, n_cu = g4c::cu_count();
+    return (unsigned)(want < n_cu ? want : n_cu);
+}
+
+bool rs_takes(const Launch &L) {
+    const Params &p = L.p;
+    const bool agg = L.agg;
     if (agg && (p.agg_deg < 4 || p.agg_deg > 8)) return false;
     if (p.n_src != 1 || p.n_nar != 0 || p.n_add != 2 || p.n_heads || (p.n_layers != 2 && p.n_layers != 3) || p.n_out != NP || p.resid || p.out_idx) return false;
     const Src &s = p.src[0];
@@ -569,15 +577,15 @@ bool rs_eligible(const Params &p, bool agg, long long row_count) {
     if (agg && (!p.agg || (p.agg_ld & (p.agg_bf16 ? 7 : 3)) || ((uintptr_t)p.agg & 15) || p.M % p.agg_deg != 0)) return false;
     if (p.out && ((p.out_ld & 7) || ((uintptr_t)p.out & 15))) return false;
     if (!p.gamma || p.act != G4C_ACT_NONE || ((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15) || ((uintptr_t)p.b & 15)) return false;
-    return p.M < (1LL << 31) && p.row_base == 0 && row_count == p.M;
+    return p.M < (1LL << 31) && p.row_base == 0 && L.row_count == p.M;
 }
 
-int rs_launch(const Params &p, bool agg, hipStream_t st) {
-    if (p.M == 0) return G4C_OK;
-    const int n_cu = g4c::cu_count();
-    const long long chunks = (p.M + 15) / 16, want = (chunks + RS_WAVES - 1) / RS_WAVES;
+int rs_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    const bool agg = L.agg;
+    ran.kernel = G4C_KERNEL_MLP_RS;
     const bool xb = p.src[0].bf16 != 0, ab = p.add[0].bf16 != 0;
-    const dim3 grid((unsigned)(want < n_cu ? want : n_cu)), blk(RS_WAVES * 64);
+    const dim3 grid(rs_grid(p)), blk(RS_WAVES * 64);
     const int od = p.out ? p.out_bf16 : 3;
 #define G4C_RS1(NL, XB, AB, OD) do { if (agg && p.agg_bf16) mlp_rs1_kernel<NL, XB, AB, OD, 2><<<grid, blk, 0, st>>>(p); \
                                      else if (agg) mlp_rs1_kernel<NL, XB, AB, OD, 1><<<grid, blk, 0, st>>>(p); \
@@ -594,7 +602,8 @@ int rs_launch(const Params &p, bool agg, hipStream_t st) {
     return g4c::check_launch("g4c_mlp_run (rs)");
 }
 
-bool rs2_eligible(const Params &p, long long row_count) {
+bool rs2_takes(const Launch &L) {
+    const Params &p = L.p;
     if (p.n_src != 2 || p.n_nar != 0 || p.n_add != 0 || p.n_layers != 2 || p.n_out != NP || p.resid || p.out_idx || p.agg || !p.out) return false;
     if (p.n_heads != 0 && (p.n_heads != 2 || !p.head_bf16 || (p.head_ld & 7) || ((uintptr_t)p.head_out[0] & 15) || ((uintptr_t)p.head_out[1] & 15))) return false;
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -603,14 +612,14 @@ bool rs2_eligible(const Params &p, long long row_count) {
     }
     if ((p.out_ld & (p.out_bf16 ? 7 : 3)) || ((uintptr_t)p.out & 15) || p.out_bf16 > 1) return false;
     if (!p.gamma || (p.act != G4C_ACT_NONE && p.act != G4C_ACT_SELU) || ((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15) || ((uintptr_t)p.b & 15)) return false;
-    return p.M < (1LL << 31) && p.row_base == 0 && row_count == p.M;
+    return p.M < (1LL << 31) && p.row_base == 0 && L.row_count == p.M;
 }
 
-int rs2_launch(const Params &p, bool e_natural, hipStream_t st) {
-    if (p.M == 0) return G4C_OK;
-    const int n_cu = g4c::cu_count();
-    const long long chunks = (p.M + 15) / 16, want = (chunks + RS_WAVES - 1) / RS_WAVES;
-    const dim3 grid((unsigned)(want < n_cu ? want : n_cu)), blk(RS_WAVES * 64);
+int rs2_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    const bool e_natural = L.fmt == G4C_WFMT_BF16_RS2N;
+    ran.kernel = G4C_KERNEL_MLP_RS2;
+    const dim3 grid(rs_grid(p)), blk(RS_WAVES * 64);
 #define G4C_RS2(O16, HD) do { if (e_natural) mlp_rs2_kernel<O16, HD, true><<<grid, blk, 0, st>>>(p); else mlp_rs2_kernel<O16, HD, false><<<grid, blk, 0, st>>>(p); } while (0)
     if (p.n_heads) { if (p.out_bf16) G4C_RS2(true, true); else G4C_RS2(false, true); }
     else { if (p.out_bf16) G4C_RS2(true, false); else G4C_RS2(false, false); }

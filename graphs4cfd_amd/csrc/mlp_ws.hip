@@ -1219,50 +1219,29 @@ template __global__ void mlp_ws_kernel<true, true, true, 2, 3, false, false, tru
 #ifndef G4C_WS_ISA_ONLY
 namespace g4cm {
 
-// 0 off, 1 (default) launches of at least 20 000 rows (measured on the level-1 message launch against
-// the two-way instantiation of mlp_bx6i_kernel, which it replaces: 322 us against 339 us with the fused aggregation, 288 against 292
-// without), 2 every launch it can take (tests)
-static int g_ws = -1;
-int ws_enable(int on) {
-    if (g_ws < 0) g_ws = 1;
-    const int old = g_ws;
-    if (on >= 0) g_ws = on > 2 ? 2 : on;
-    return old;
-}
-
-bool ws_eligible(const Params &p, bool round1, bool agg, bool save, bool f16x2, long long row_count, bool any_size) {
-    constexpr long long min_rows = 20000;          // (same-box sweeps of round 3: ahead of the tile kernel from ~20 k rows)
-    const int mode = any_size ? 2 : ws_enable(-1);          // (any_size: the fused MP layer asks whether the SHAPE fits, whatever the mode)
-    if (!mode || save || !(f16x2 || round1)) return false;          // (the bf16x6 stream keeps mlp_bx6i_kernel / mlp_bx6_kernel)
-    if (mode == 1 && row_count < min_rows) return false;
-    if (p.n_src != 1 || p.n_nar != 0 || (p.n_add != 0 && p.n_add != 2) || p.n_heads) return false;
-    if (round1 && p.n_add != 2) return false;
-    if ((p.n_layers != 3 && p.n_layers != 2) || p.n_out != NP || p.resid) return false;
+// The envelope: the f16x3 or a rounded-bf16 stream (the bf16x6 stream keeps mlp_bx6i_kernel / mlp_bx6_kernel), the hoisted or plain message
+// form of two or three layers.  From which size on the kernel is ahead is the launcher's business (mlp_run.hip).
+bool ws_takes(const Launch &L) {
+    const Params &p = L.p;
+    const bool round1 = L.round1;
+    if (!(L.f16x2 || round1) || !message_form(L)) return false;
+    if ((round1 && p.n_add != 2) || (p.n_layers != 3 && p.n_layers != 2)) return false;
     if (p.out_bf16 && (!round1 || (p.out_ld & 7) || ((uintptr_t)p.out & 15))) return false;
-    if (p.out_idx && (agg || !p.out)) return false;          // (scattered output rows: the plain launch only)
-    const Src &s = p.src[0];
-    if (s.width != NP || !s.vec || s.seg_off || (s.bf16 && !round1)) return false;
+    if (p.src[0].bf16 && !round1) return false;
     for (int a = 0; a < p.n_add; ++a)
-        if (p.add[a].width != NP || (p.add[a].ld & 3) || ((uintptr_t)p.add[a].ptr & (p.add[a].bf16 ? 7 : 15)) || p.add[a].bf16 != p.add[0].bf16 ||
-            (p.add[a].bf16 && !round1)) return false;
-    if (p.out && !p.out_bf16 && ((p.out_ld & 3) || ((uintptr_t)p.out & 15))) return false;
-    if (p.gamma && (((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15))) return false;
-    if (((uintptr_t)p.b & 15)) return false;
-    if (p.M >= (1LL << 31)) return false;
+        if (p.add[a].bf16 != p.add[0].bf16 || (p.add[a].bf16 && !round1)) return false;
     return true;
 }
 
-static thread_local int g_ws_certified = 0;
-int ws_last_certified() { return g_ws_certified; }
-
-int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const NodeParams *node) {
+int ws_launch(const Launch &L, hipStream_t st, Ran &ran) {
+    const Params &p = L.p;
+    const bool agg = L.agg, round1 = L.round1, node = L.has_node;
     // (dense mode — uniform segments of 4 .. 8 rows — cuts the rows into pairs of 64 itself: n_pairs only sizes the grid there)
     // Not for the fused MP layer: its launches are a few pairs per workgroup (nothing to win from denser pairs), and its three-layer
     // instantiation sits at 256 registers — with the dense bookkeeping it spills (config 2: 1 786 -> 1 734 steps/s, same box).
     const bool dense = agg && !node && p.agg_deg >= 4 && p.agg_deg <= 8;
     const int n_pairs = dense ? (int)((p.M + 63) / 64) : (p.n_tiles + 1) / 2;
-    g_ws_certified = 0;
-    if (n_pairs == 0) return G4C_OK;
+    ran.kernel = G4C_KERNEL_MLP_WS;
     const int n_wg = g4c::cu_count() * (round1 ? G4C_WS_SP1_MINW / 2 : 1);          // persistent workgroups: one (SP = 1: G4C_WS_SP1_MINW / 2) per CU
     const dim3 grid(n_pairs < n_wg ? n_pairs : n_wg), blk(512);
     const bool direct = p.src[0].idx == nullptr, adds = p.n_add == 2, two = p.n_layers == 2, xb16 = p.src[0].bf16 != 0;
@@ -1270,7 +1249,7 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
     // the tracker-free instantiations: the f16x3 stream with the two additive blocks (the hoisted message form every MP layer of a
     // model launches); a certified launch of another shape runs the tracked kernel with a null flag pointer
     const bool cert = p.range_certified && !round1 && adds;
-    g_ws_certified = cert ? 1 : 0;
+    if (cert) ran.kernel = G4C_KERNEL_MLP_WS_CERT;
     WsArgs a{};
     const Src &s = p.src[0];
     a.x = s.bf16 ? reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(s.ptr) + s.col0) : s.ptr + s.col0;
@@ -1280,14 +1259,11 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
     a.out = p.out; a.out_idx = p.out_idx; a.out_ld = p.out_ld; a.out_bf16 = p.out_bf16;
     a.tile_rows = p.tile_rows; a.tile_seg = p.tile_seg; a.seg_off = p.seg_off;
     a.agg = p.agg; a.agg_ld = p.agg_ld; a.agg_mean = p.agg_mean; a.agg_deg = p.agg_deg;
-    a.M = (int)p.M; a.row_base = (int)p.row_base; a.n_tiles = p.n_tiles;          // (ws_eligible: M < 2^31)
+    a.M = (int)p.M; a.row_base = (int)p.row_base; a.n_tiles = p.n_tiles;          // (ws_takes: M < 2^31)
     a.range_flag = p.range_certified ? nullptr : p.range_flag; a.range_slot = p.range_slot;
-    NodeParams q{};
+    const WsKernArgs ka{a, n_pairs, L.node};          // (the node update's parameters: zeros without one)
     if (node) {          // the fused MP layer (g4c_mlp_io_t.upd): f16x3 stream, hoisted message MLP, fused aggregation
         G4C_REQUIRE(agg && !round1 && adds, G4C_EUNSUPPORTED, "g4c_mlp_run (upd): needs the hoisted f16x3 message launch with the fused aggregation");
-        q = *node;
-        if (p.range_certified) q.range_flag = nullptr;
-        const WsKernArgs ka{a, n_pairs, q};
 #define G4C_WS_NODE(DIRECT, NL)                                                                                                        \
     do { if (cert) mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true, false, false><<<grid, blk, 0, st>>>(ka);    \
          else mlp_ws_kernel<true, DIRECT, true, 2, NL, false, false, true><<<grid, blk, 0, st>>>(ka); } while (0)
@@ -1296,7 +1272,6 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
 #undef G4C_WS_NODE
         return g4c::check_launch("g4c_mlp_run (ws, upd)");
     }
-    const WsKernArgs ka{a, n_pairs, q};
 #define G4C_WS_GO(AGG, DIRECT, ADDS, SP, NL, XB16)                                                                                      \
     do { if (AGG && dense) mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16, false, false, AGG><<<grid, blk, 0, st>>>(ka);       \
          else mlp_ws_kernel<AGG, DIRECT, ADDS, SP, NL, XB16><<<grid, blk, 0, st>>>(ka); } while (0)
@@ -1331,6 +1306,4 @@ int ws_launch(const Params &p, bool agg, bool round1, hipStream_t st, const Node
 }
 
 }  // namespace g4cm
-
-extern "C" int g4c_mlp_ws_enable(int on) { return g4cm::ws_enable(on); }
 #endif

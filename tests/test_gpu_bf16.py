@@ -309,7 +309,7 @@ def test_rows_put_back_in_feature_order_by_hand_are_read_as_such():
 
 def test_mlp_run_refuses_a_uniform_row_count_it_cannot_split():
     """G4C_AGG_UNIFORM(k) through the C-ABI (ctypes): a launch whose row count is not a multiple of k is refused with G4C_EINVAL before
-    anything runs (the `row_count % k` check of mlp_launch); the same launch with whole segments runs on mlp_ws_kernel's dense mode.
+    anything runs (the `row_count % k` check of g4c_mlp_run's output stage, csrc/mlp_run.hip); the same launch with whole segments runs on mlp_ws_kernel's dense mode.
     (The launcher's refusal of a sub-range in dense mode is a guard only: g4c_mlp_run refuses a row sub-range of any launch with an
     aggregation before that.)"""
     import ctypes as C
