@@ -107,11 +107,11 @@ __global__ __launch_bounds__(256) void add_cols_kernel(const float *__restrict__
 
 extern "C" int g4c_project_to_edges(const float *v, int32_t v_ld, const int32_t *node, const float *unit,
                                     int64_t n_edges, int32_t n_feat, float *out, int32_t out_ld, void *stream) {
-    G4C_REQUIRE(v && unit && out, G4C_EINVAL, "g4c_project_to_edges: null pointer");
-    g4c::DeviceGuard on_device(out);
     G4C_REQUIRE(n_edges >= 0 && n_feat > 0 && v_ld >= 2 * n_feat && out_ld >= n_feat && v_ld % 2 == 0 && ((uintptr_t)v % 8 == 0),
                 G4C_EINVAL, "g4c_project_to_edges: bad sizes n_feat=%d v_ld=%d out_ld=%d", n_feat, v_ld, out_ld);
-    if (n_edges == 0) return G4C_OK;
+    if (n_edges == 0) return G4C_OK;    // (before the pointers: the unit vectors and the output of no edges have no address)
+    G4C_REQUIRE(v && unit && out, G4C_EINVAL, "g4c_project_to_edges: null pointer");
+    g4c::DeviceGuard on_device(out);
     const long long total = n_edges * n_feat;
     project_to_edges_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
         v, v_ld, node, unit, n_edges, n_feat, out, out_ld);
@@ -120,11 +120,11 @@ extern "C" int g4c_project_to_edges(const float *v, int32_t v_ld, const int32_t 
 
 extern "C" int g4c_edge_scalar_to_node_vector(const float *e, int32_t e_ld, const float *unit_inv, int32_t k,
                                               int64_t n_nodes, int32_t n_feat, float *out, int32_t out_ld, void *stream) {
-    G4C_REQUIRE(e && unit_inv && out, G4C_EINVAL, "g4c_edge_scalar_to_node_vector: null pointer");
-    g4c::DeviceGuard on_device(out);
     G4C_REQUIRE(n_nodes >= 0 && k > 0 && n_feat > 0 && e_ld >= n_feat && out_ld >= 2 * n_feat && out_ld % 2 == 0 && ((uintptr_t)out % 8 == 0),
                 G4C_EINVAL, "g4c_edge_scalar_to_node_vector: bad sizes k=%d n_feat=%d e_ld=%d out_ld=%d", k, n_feat, e_ld, out_ld);
-    if (n_nodes == 0) return G4C_OK;
+    if (n_nodes == 0) return G4C_OK;    // (before the pointers: the tensors of no nodes have no address)
+    G4C_REQUIRE(e && unit_inv && out, G4C_EINVAL, "g4c_edge_scalar_to_node_vector: null pointer");
+    g4c::DeviceGuard on_device(out);
     const long long total = n_nodes * n_feat;
     edge_scalar_to_node_vector_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
         e, e_ld, unit_inv, k, n_nodes, n_feat, out, out_ld);
@@ -169,8 +169,9 @@ extern "C" int g4c_copy_cols(const float *src, int32_t src_ld, int32_t scol0, co
 
 extern "C" int g4c_rollout_advance(float *field, int32_t field_cols, const float *pred, int32_t nf,
                                    float *outputs, int32_t out_ld, int32_t *step, int64_t n_nodes, void *stream) {
-    G4C_REQUIRE(field && pred && outputs && step, G4C_EINVAL, "g4c_rollout_advance: null pointer");
-    g4c::DeviceGuard on_device(field);
+    // (no nodes: field, pred and outputs are empty and have no address; the launch still advances the step index)
+    G4C_REQUIRE(step && (n_nodes == 0 || (field && pred && outputs)), G4C_EINVAL, "g4c_rollout_advance: null pointer");
+    g4c::DeviceGuard on_device(step);
     G4C_REQUIRE(nf > 0 && field_cols >= nf && (out_ld >= nf || out_ld == 0) && n_nodes >= 0, G4C_EINVAL,
                 "g4c_rollout_advance: bad sizes nf=%d field_cols=%d out_ld=%d", nf, field_cols, out_ld);
     hipStream_t s = (hipStream_t)stream;

@@ -206,9 +206,9 @@ extern "C" int g4c_weighted_segment_mean(const float *x, int32_t x_ld, const int
                                          float *out, int32_t out_ld, const int32_t *out_idx, void *stream) {
     G4C_REQUIRE(n_seg >= 0 && width > 0 && x_ld >= width && out_ld >= width, G4C_EINVAL,
                 "g4c_weighted_segment_mean: bad sizes n_seg=%d width=%d", n_seg, width);
+    if (n_seg == 0) return G4C_OK;      // (before the pointers: the empty index and weight arrays of no segments have no address)
     G4C_REQUIRE(x && x_idx && w && off && out, G4C_EINVAL, "g4c_weighted_segment_mean: null pointer");
     g4c::DeviceGuard on_device(out);
-    if (n_seg == 0) return G4C_OK;
     hipStream_t s = (hipStream_t)stream;
     const long long total = (long long)n_seg * 64;
     weighted_segment_mean_kernel<64><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(

@@ -167,6 +167,72 @@ class Source:
             raise ValueError("aggregation on load needs a 128-wide block without gather index")
 
 
+# ---- argument checks of the helper launches below: shapes, strides and dtypes only (host metadata — never index VALUES, which would
+# synchronise the stream and break graph capture), and before require_hip, so that a malformed call is refused the same way with or
+# without a device.  TypeError for a dtype, ValueError for a shape; the message names the argument.
+def _rows_f32(t: Tensor, name: str, cols: Optional[int] = None, min_rows: int = 0, min_cols: int = 0) -> Tensor:
+    """A float32 [rows, cols] tensor the launch addresses as t[r * ld + c]: unit column stride, rows that do not overlap."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a 2-D tensor, got shape {tuple(t.shape)}")
+    if t.size(1) > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: expected unit column stride, got strides {tuple(t.stride())}")
+    if t.size(0) > 1 and t.stride(0) < t.size(1):
+        raise ValueError(f"{name}: rows overlap (row stride {t.stride(0)} < {t.size(1)} columns)")
+    if cols is not None and int(t.size(1)) != cols:
+        raise ValueError(f"{name}: expected {cols} columns, got shape {tuple(t.shape)}")
+    if int(t.size(1)) < min_cols:
+        raise ValueError(f"{name}: expected at least {min_cols} columns, got shape {tuple(t.shape)}")
+    if int(t.size(0)) < min_rows:
+        raise ValueError(f"{name}: expected at least {min_rows} rows, got shape {tuple(t.shape)}")
+    return t
+
+
+def _index_i32(t: Optional[Tensor], name: str, n: Optional[int] = None, at_least: Optional[int] = None) -> Optional[Tensor]:
+    """An int32 index vector (contiguous, 1-D) of exactly `n` / at least `at_least` entries; None passes."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name}: expected int32, got {t.dtype}")
+    if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+        raise ValueError(f"{name}: expected a contiguous 1-D tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{name}: expected {n} entries, got {t.numel()}")
+    if at_least is not None and t.numel() < at_least:
+        raise ValueError(f"{name}: expected at least {at_least} entries, got {t.numel()}")
+    return t
+
+
+def _vector_f32(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if t.dim() != 1 or t.numel() != n or (n > 1 and t.stride(0) != 1):
+        raise ValueError(f"{name}: expected a contiguous vector of {n} entries, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def _act_arg(act, name: str) -> int:
+    if act not in (_lib.ACT_NONE, _lib.ACT_SELU, _lib.ACT_TANH):
+        raise ValueError(f"{name}: unknown activation code {act!r}")
+    return int(act)
+
+
+def _csr_arg(csr: CsrPlan, name: str) -> None:
+    if csr.n < 0 or csr.n_seg < 0:
+        raise ValueError(f"{name}: negative sizes n={csr.n} n_seg={csr.n_seg}")
+    _index_i32(csr.off, f"{name}.off", n=csr.n_seg + 1)
+    _index_i32(csr.perm, f"{name}.perm", at_least=csr.n)
+
+
 def segment_reduce(src: Tensor, csr: CsrPlan, mean: bool, act: int = _lib.ACT_NONE, out: Optional[Tensor] = None,
                    src_act: int = _lib.ACT_NONE) -> Tensor:
     """out[s] = act(sum|mean of src_act(src[perm[p]]) over the plan's segments) (g4c_segment_reduce)."""
@@ -175,10 +241,18 @@ def segment_reduce(src: Tensor, csr: CsrPlan, mean: bool, act: int = _lib.ACT_NO
             raise NotImplementedError("segment_reduce(out=...) is not differentiable")
         from . import autograd as _ag
         return _ag.segment_reduce(src, csr, mean, act, src_act)
-    lib = _lib.load()
     src = _f32_2d(src, "src")
-    dev = _lib.require_hip(src, csr.off, csr.perm)
     width = int(src.size(1))
+    _csr_arg(csr, "csr")
+    act, src_act = _act_arg(act, "act"), _act_arg(src_act, "src_act")
+    if csr.perm is None and int(src.size(0)) < csr.n:          # (through a permutation the rows it names cannot be checked here)
+        raise ValueError(f"src: the plan reads rows 0 .. {csr.n - 1}, got shape {tuple(src.shape)}")
+    if csr.perm is not None and csr.n > 0 and int(src.size(0)) == 0:
+        raise ValueError(f"src: the plan reads {csr.n} rows through its permutation, got shape {tuple(src.shape)}")
+    if out is not None:
+        _rows_f32(out, "out", cols=width, min_rows=csr.n_seg)
+    lib = _lib.load()
+    dev = _lib.require_hip(src, csr.off, csr.perm, out)
     if out is None:
         out = torch.empty((csr.n_seg, width), dtype=torch.float32, device=dev)
     # algorithmic bytes: messages read + rows written + offsets (+ permutation)
@@ -191,10 +265,13 @@ def segment_reduce(src: Tensor, csr: CsrPlan, mean: bool, act: int = _lib.ACT_NO
 
 def activation_(x: Tensor, act: int) -> Tensor:
     """In-place activation of a contiguous tensor (g4c_activation_inplace)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise TypeError(f"x: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if not x.is_contiguous():
+        raise ValueError("x: activation_ needs a contiguous tensor")
+    act = _act_arg(act, "act")
     lib = _lib.load()
     dev = _lib.require_hip(x)
-    if not x.is_contiguous():
-        raise ValueError("activation_: tensor must be contiguous")
     _lib.check(lib.g4c_activation_inplace(_lib.ptr(x), x.numel(), act, _lib.stream_handle(dev)))
     return x
 
@@ -207,13 +284,28 @@ def weighted_segment_mean(x: Tensor, x_idx32: Tensor, w: Tensor, csr: CsrPlan, o
                                       "returns the full tensor)")
         from . import autograd as _ag
         return _ag.weighted_segment_mean(x, x_idx32, w, csr)
-    lib = _lib.load()
     x = _f32_2d(x, "x")
+    width = int(x.size(1))
+    if not torch.is_tensor(w) or w.dtype != torch.float32:
+        raise TypeError(f"w: expected a float32 tensor, got {getattr(w, 'dtype', type(w).__name__)}")
     w = w.reshape(-1).contiguous()
-    dev = _lib.require_hip(x, x_idx32, w, csr.off)
+    _csr_arg(csr, "csr")
     if csr.perm is not None:
         raise NotImplementedError("knn_interpolate needs y_idx sorted (the BuildKnnInterpWeights layout)")
-    width = int(x.size(1))
+    if x_idx32 is None:
+        raise TypeError("x_idx32: expected an int32 tensor, got None")
+    _index_i32(x_idx32, "x_idx32", n=csr.n)
+    if w.numel() != csr.n:
+        raise ValueError(f"w: expected {csr.n} weights (one per entry of x_idx32), got {w.numel()}")
+    if csr.n > 0 and int(x.size(0)) == 0:
+        raise ValueError(f"x: x_idx32 reads {csr.n} rows, got shape {tuple(x.shape)}")
+    _index_i32(out_idx32, "out_idx32", n=csr.n_seg)
+    if out is not None:       # (the rows out_idx32 names cannot be checked here; without it the launch writes rows 0 .. n_seg - 1)
+        _rows_f32(out, "out", cols=width, min_rows=csr.n_seg if out_idx32 is None else min(csr.n_seg, 1))
+    elif out_idx32 is not None:
+        raise ValueError("out_idx32: scattered output rows need `out`")
+    lib = _lib.load()
+    dev = _lib.require_hip(x, x_idx32, w, csr.off, out, out_idx32)
     if out is None:
         out = torch.empty((csr.n_seg, width), dtype=torch.float32, device=dev)
     _lib.check(lib.g4c_weighted_segment_mean(_lib.ptr(x), _ld(x), _lib.ptr(x_idx32), _lib.ptr(w), _lib.ptr(csr.off),
@@ -226,9 +318,21 @@ def project_to_edges(v: Tensor, node32: Optional[Tensor], unit: Tensor, n_edges:
     if torch.is_grad_enabled() and v.requires_grad:
         from . import autograd as _ag
         return _ag.project_to_edges(v, node32, unit, n_edges, n_feat)
-    lib = _lib.load()
     v = _f32_2d(v, "v")
     unit = _f32_2d(unit, "edgeUnitVector").contiguous()
+    n_edges, n_feat = int(n_edges), int(n_feat)
+    if n_edges < 0 or n_feat <= 0:
+        raise ValueError(f"n_edges / n_feat: expected n_edges >= 0 and n_feat > 0, got {n_edges}, {n_feat}")
+    if int(v.size(1)) < 2 * n_feat:
+        raise ValueError(f"v: {n_feat} features need {2 * n_feat} columns, got shape {tuple(v.shape)}")
+    if tuple(unit.shape) != (n_edges, 2):
+        raise ValueError(f"edgeUnitVector: expected shape ({n_edges}, 2), got {tuple(unit.shape)}")
+    _index_i32(node32, "node32", n=n_edges)
+    if node32 is None and int(v.size(0)) < n_edges:
+        raise ValueError(f"v: without node32 edge e reads row e, {n_edges} edges, got shape {tuple(v.shape)}")
+    if node32 is not None and n_edges > 0 and int(v.size(0)) == 0:
+        raise ValueError(f"v: node32 reads {n_edges} rows, got shape {tuple(v.shape)}")
+    lib = _lib.load()
     dev = _lib.require_hip(v, node32, unit)
     out = torch.empty((n_edges, n_feat), dtype=torch.float32, device=dev)
     _lib.check(lib.g4c_project_to_edges(_lib.ptr(v), _ld(v), _lib.ptr(node32), _lib.ptr(unit), n_edges, n_feat,
@@ -242,17 +346,27 @@ def edge_scalar_to_node_vector(e: Tensor, unit_inv: Tensor, n_nodes: int, k: int
             raise NotImplementedError("edge_scalar_to_node_vector(out=...) is not differentiable")
         from . import autograd as _ag
         return _ag.edge_scalar_to_node_vector(e, unit_inv, n_nodes, k)
-    lib = _lib.load()
     e = _f32_2d(e, "edge_attr")
+    n_nodes, k = int(n_nodes), int(k)
+    if n_nodes < 0 or k <= 0:
+        raise ValueError(f"n_nodes / k: expected n_nodes >= 0 and k > 0, got {n_nodes}, {k}")
+    if not torch.is_tensor(unit_inv) or unit_inv.dtype != torch.float32:
+        raise TypeError(f"edgeUnitVectorInverse: expected a float32 tensor, got {getattr(unit_inv, 'dtype', type(unit_inv).__name__)}")
+    if unit_inv.numel() != n_nodes * 2 * k:
+        raise ValueError(f"edgeUnitVectorInverse: expected {n_nodes} x 2 x {k} entries, got shape {tuple(unit_inv.shape)}")
     unit_inv = unit_inv.contiguous()
-    dev = _lib.require_hip(e, unit_inv, out)
     n_feat = int(e.size(1))
     if int(e.size(0)) != n_nodes * k:
-        raise ValueError(f"{int(e.size(0))} edges cannot be viewed as {n_nodes} nodes x {k} incoming edges")
+        raise ValueError(f"edge_attr: {int(e.size(0))} edges cannot be viewed as {n_nodes} nodes x {k} incoming edges")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32:
+            raise TypeError(f"out: expected a float32 tensor, got {getattr(out, 'dtype', type(out).__name__)}")
+        if tuple(out.shape) != (n_nodes, 2 * n_feat) or out.stride(1) != 1:
+            raise ValueError(f"out must be a float32 [{n_nodes}, {2 * n_feat}] tensor with unit column stride")
+    lib = _lib.load()
+    dev = _lib.require_hip(e, unit_inv, out)
     if out is None:
         out = torch.empty((n_nodes, 2 * n_feat), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (n_nodes, 2 * n_feat) or out.dtype != torch.float32 or out.stride(1) != 1:
-        raise ValueError(f"out must be a float32 [{n_nodes}, {2 * n_feat}] tensor with unit column stride")
     _lib.check(lib.g4c_edge_scalar_to_node_vector(_lib.ptr(e), _ld(e), _lib.ptr(unit_inv), k, n_nodes, n_feat,
                                                   _lib.ptr(out), _ld(out), _lib.stream_handle(dev)))
     return out
@@ -260,50 +374,96 @@ def edge_scalar_to_node_vector(e: Tensor, unit_inv: Tensor, n_nodes: int, k: int
 
 def copy_cols(src: Tensor, dst: Tensor, dcol0: int, scol0: int = 0, width: Optional[int] = None,
               idx32: Optional[Tensor] = None, n_rows: Optional[int] = None) -> None:
-    lib = _lib.load()
-    dev = _lib.require_hip(src, dst, idx32)
+    _rows_f32(src, "src")
+    _rows_f32(dst, "dst")
+    dcol0, scol0 = int(dcol0), int(scol0)
     width = int(src.size(1) - scol0 if width is None else width)
     n_rows = int(dst.size(0) if n_rows is None else n_rows)
+    if width <= 0 or scol0 < 0 or scol0 + width > int(src.size(1)):
+        raise ValueError(f"scol0 / width: columns {scol0} .. {scol0 + width - 1} of src with shape {tuple(src.shape)}")
+    if dcol0 < 0 or dcol0 + width > int(dst.size(1)):
+        raise ValueError(f"dcol0 / width: columns {dcol0} .. {dcol0 + width - 1} of dst with shape {tuple(dst.shape)}")
+    if n_rows < 0 or n_rows > int(dst.size(0)):
+        raise ValueError(f"n_rows: {n_rows} rows of dst with shape {tuple(dst.shape)}")
+    _index_i32(idx32, "idx32", at_least=n_rows)
+    if idx32 is None and int(src.size(0)) < n_rows:
+        raise ValueError(f"src: {n_rows} rows are copied, got shape {tuple(src.shape)}")
+    if idx32 is not None and n_rows > 0 and int(src.size(0)) == 0:
+        raise ValueError(f"src: idx32 reads {n_rows} rows, got shape {tuple(src.shape)}")
+    lib = _lib.load()
+    dev = _lib.require_hip(src, dst, idx32)
     _lib.check(lib.g4c_copy_cols(_lib.ptr(src), _ld(src), scol0, _lib.ptr(idx32), _lib.ptr(dst), _ld(dst), dcol0, width,
                                  n_rows, _lib.stream_handle(dev)))
 
 
 def add_cols(a: Tensor, a_col0: int, b: Tensor, out: Tensor) -> Tensor:
     """out = a[:, a_col0:a_col0+w] + b (g4c_add_cols)."""
+    _rows_f32(b, "b", min_cols=1)
+    n_rows, width, a_col0 = int(b.size(0)), int(b.size(1)), int(a_col0)
+    _rows_f32(a, "a", min_rows=n_rows)
+    if a_col0 < 0 or a_col0 + width > int(a.size(1)):
+        raise ValueError(f"a_col0: columns {a_col0} .. {a_col0 + width - 1} of a with shape {tuple(a.shape)}")
+    _rows_f32(out, "out", cols=width, min_rows=n_rows)
     lib = _lib.load()
     dev = _lib.require_hip(a, b, out)
     _lib.check(lib.g4c_add_cols(_lib.ptr(a), _ld(a), a_col0, _lib.ptr(b), _ld(b), _lib.ptr(out), _ld(out),
-                                int(b.size(1)), int(b.size(0)), _lib.stream_handle(dev)))
+                                width, n_rows, _lib.stream_handle(dev)))
     return out
 
 
 def layer_norm(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], eps: float, act: int = _lib.ACT_NONE,
                out: Optional[Tensor] = None) -> Tensor:
     """Row-wise LayerNorm (+ activation) over any width (g4c_layer_norm): the fused MLP kernels' own epilogue covers <= 128 columns."""
-    lib = _lib.load()
     x = _f32_2d(x, "x")
+    n_rows, width = int(x.size(0)), int(x.size(1))
+    if width <= 0:
+        raise ValueError(f"x: expected at least one column, got shape {tuple(x.shape)}")
+    _vector_f32(gamma, "gamma", width)
+    _vector_f32(beta, "beta", width)
+    act = _act_arg(act, "act")
+    if out is not None:
+        _rows_f32(out, "out", cols=width)
+        if int(out.size(0)) != n_rows:
+            raise ValueError(f"out: expected shape ({n_rows}, {width}), got {tuple(out.shape)}")
+    lib = _lib.load()
     dev = _lib.require_hip(x, gamma, beta, out)
     if out is None:
-        out = torch.empty((int(x.size(0)), int(x.size(1))), dtype=torch.float32, device=dev)
-    _lib.check(lib.g4c_layer_norm(_lib.ptr(x), _ld(x), int(x.size(0)), int(x.size(1)), _lib.ptr(gamma), _lib.ptr(beta), float(eps), int(act),
+        out = torch.empty((n_rows, width), dtype=torch.float32, device=dev)
+    _lib.check(lib.g4c_layer_norm(_lib.ptr(x), _ld(x), n_rows, width, _lib.ptr(gamma), _lib.ptr(beta), float(eps), act,
                                   _lib.ptr(out), _ld(out), _lib.stream_handle(dev)))
     return out
 
 
 def rollout_advance(field: Tensor, pred: Tensor, outputs: Tensor, step: Tensor, nf: int) -> None:
+    nf = int(nf)
+    for t, name in ((field, "field"), (pred, "pred"), (outputs, "outputs")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected a float32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: rollout_advance needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if not torch.is_tensor(step) or step.dtype != torch.int32:
+        raise TypeError("step: rollout_advance: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+    if step.dim() != 1 or step.numel() < 2 or not step.is_contiguous():
+        raise ValueError("step: rollout_advance: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+    if field.dim() != 2 or nf <= 0 or int(field.size(1)) < nf:
+        raise ValueError(f"field: expected [n_nodes, >= nf = {nf}], got shape {tuple(field.shape)}")
+    n_nodes = int(field.size(0))
+    if tuple(pred.shape) != (n_nodes, nf):
+        raise ValueError(f"pred: expected shape ({n_nodes}, {nf}), got {tuple(pred.shape)}")
+    if outputs.dim() == 3:          # step-major [steps, n_nodes, nf]: a step writes one contiguous block
+        if outputs.size(1) != n_nodes or outputs.size(2) != nf:
+            raise ValueError(f"outputs: rollout_advance: step-major outputs {tuple(outputs.shape)} for {n_nodes} nodes x {nf} fields")
+        out_ld = 0
+    elif outputs.dim() == 2:        # row-major [n_nodes, nf * steps] (the reference's layout); the step index lives on the device
+        if int(outputs.size(0)) != n_nodes or int(outputs.size(1)) < nf:
+            raise ValueError(f"outputs: expected row-major [{n_nodes}, >= {nf}], got shape {tuple(outputs.shape)}")
+        out_ld = int(outputs.size(1))
+    else:
+        raise ValueError(f"outputs: expected [n_nodes, nf * steps] or [steps, n_nodes, nf], got shape {tuple(outputs.shape)}")
     lib = _lib.load()
     dev = _lib.require_hip(field, pred, outputs, step)
-    assert field.is_contiguous() and pred.is_contiguous() and outputs.is_contiguous()
-    if step.dtype != torch.int32 or step.numel() < 2:
-        raise ValueError("rollout_advance: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
-    if outputs.dim() == 3:          # step-major [steps, n_nodes, nf]: a step writes one contiguous block
-        if outputs.size(1) != field.size(0) or outputs.size(2) != nf:
-            raise ValueError(f"rollout_advance: step-major outputs {tuple(outputs.shape)} for {field.size(0)} nodes x {nf} fields")
-        out_ld = 0
-    else:
-        out_ld = int(outputs.size(1))
     _lib.check(lib.g4c_rollout_advance(_lib.ptr(field), int(field.size(1)), _lib.ptr(pred), nf, _lib.ptr(outputs),
-                                       out_ld, _lib.ptr(step), int(field.size(0)), _lib.stream_handle(dev)))
+                                       out_ld, _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
 def steps_to_columns(out_steps: Tensor) -> Tensor:

@@ -28,6 +28,15 @@ extern "C" {
 #define G4C_ELAUNCH (-2)  /* HIP launch / runtime failure (RuntimeError) */
 #define G4C_EUNSUPPORTED (-3) /* shape outside the kernels' envelope (NotImplementedError) */
 
+/* Activations (every fused epilogue, source activation on load, g4c_activation_inplace): branch-free on the hardware exponential and
+ * reciprocal, fp32 round-off class against F.selu / torch.tanh (bounded per element in tests/test_gpu_mem_ref.py).  Infinities: SELU(+inf)
+ * = +inf, SELU(-inf) = -scale * alpha, tanh(+-inf) = +-1; tanh keeps the sign of zero, SELU(-0) = +0.
+ * DIFFERENCE FROM THE REFERENCE — NaN is NOT propagated (measured on gfx950, pinned by test_activation_nan_is_not_propagated):
+ *   SELU(NaN) = -scale * alpha = -1.7580993 (0xbfe10966), whatever the NaN's sign or payload: max(NaN, 0) = 0 and the [0, 1] clamp of
+ *               exp2(NaN) gives 0, i.e. a NaN is treated like -inf;
+ *   tanh(NaN) = +1 or -1 by the NaN's sign bit: min(|NaN|, 20) = 20.
+ * F.selu and torch.tanh return NaN.  A NaN that enters an activated launch therefore leaves it as a finite number; NaNs in data are
+ * the caller's to find before the rollout (ACT_NONE passes them through unchanged). */
 #define G4C_ACT_NONE 0
 #define G4C_ACT_SELU 1
 #define G4C_ACT_TANH 2
@@ -417,11 +426,11 @@ int g4c_rollout_advance(float *field, int32_t field_cols, const float *pred, int
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
                  float *out, int32_t out_ld, int32_t width, int64_t n_rows, void *stream);
 
-/* dst[r, dcol0 : dcol0+width] = src[r, scol0 : scol0+width]  (torch.cat of the narrow node inputs,
- * nn/mus_gnn.py:71; also used to assemble halo send buffers when idx != NULL: reads src[idx[r]]). */
-/* x[i] = act(x[i]) in place, n contiguous floats (F.selu / torch.tanh on a block output). */
+/* x[i] = act(x[i]) in place, n contiguous floats (F.selu / torch.tanh on a block output; NaN: see G4C_ACT_*). */
 int g4c_activation_inplace(float *x, int64_t n, int32_t act, void *stream);
 
+/* dst[r, dcol0 : dcol0+width] = src[r, scol0 : scol0+width]  (torch.cat of the narrow node inputs,
+ * nn/mus_gnn.py:71; also used to assemble halo send buffers when idx != NULL: reads src[idx[r]]). */
 int g4c_copy_cols(const float *src, int32_t src_ld, int32_t scol0, const int32_t *idx,
                   float *dst, int32_t dst_ld, int32_t dcol0, int32_t width, int64_t n_rows, void *stream);
 
