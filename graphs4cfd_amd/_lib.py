@@ -57,6 +57,7 @@ class g4c_mlp_t(C.Structure):
 
 
 WFMT_FP32, WFMT_F16X2, WFMT_BF16X3, WFMT_BF16_RS, WFMT_BF16_RS2, WFMT_BF16_RS2N, WFMT_BF16 = 0, 1, 2, 3, 4, 5, 6
+DTYPE_F32, DTYPE_BF16 = 0, 1          # g4c_mlp_io_t.save_dtype / mul_dtype
 
 
 class g4c_mlp_io_t(C.Structure):
@@ -69,7 +70,8 @@ class g4c_mlp_io_t(C.Structure):
                 ("n_save", C.c_int32), ("save", C.c_void_p * MAX_LAYERS), ("save_ld", C.c_int32),
                 ("mul", C.c_void_p * MAX_LAYERS), ("mul_ld", C.c_int32),
                 ("upd", C.POINTER(g4c_mlp_t)), ("v", C.c_void_p), ("v_ld", C.c_int32), ("v_act", C.c_int32),
-                ("v_out", C.c_void_p), ("v_out_ld", C.c_int32), ("range_flag", C.c_void_p)]
+                ("v_out", C.c_void_p), ("v_out_ld", C.c_int32), ("range_flag", C.c_void_p),
+                ("save_dtype", C.c_int32), ("mul_dtype", C.c_int32)]
 
     def __init__(self, **kw):
         super().__init__(size=C.sizeof(g4c_mlp_io_t), **kw)
@@ -120,9 +122,13 @@ _SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_act_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),
+    "g4c_act_grad_ref16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_int32, C.c_int64, C.c_void_p]),
     "g4c_layernorm_grad_partials": (C.c_int32, [C.c_int64]),
     "g4c_layernorm_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                      C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p]),
+    "g4c_layernorm_grad_z16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p]),
     "g4c_colsum_partials": (C.c_int32, [C.c_int64]),
     "g4c_colsum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_weight_grad_partials": (C.c_int32, [C.c_int64]),
@@ -131,6 +137,8 @@ _SIGNATURES = {
                                   C.c_void_p]),
     "g4c_weight_grad_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
+    "g4c_weight_grad_bf16_a16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p]),
     "g4c_segment_broadcast": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int32, C.c_void_p]),
 }

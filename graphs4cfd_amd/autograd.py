@@ -25,6 +25,11 @@ Mixed precision (`ops.set_train_precision("bf16")`, selected by `fit` for `Train
 rounded-bf16 forward): every product above takes both operands rounded once to bf16 and accumulates in fp32 — `linear` and
 `backward_chain` pack the rounded-bf16 stream (which saves and takes `mul` like the split streams), `weight_bias_grad` launches
 g4c_weight_grad_bf16 for every tile.  Bias gradients, LayerNorm / activation adjoints, segmented sums and gathers are unchanged.
+
+Saved activations as bf16 (`ops.set_train_precision("bf16", saved="bf16")`, `TrainConfig(saved_activations="bf16")`): the rows a
+recorded forward on the plain rounded-bf16 stream keeps are stored rounded once to bf16, and every consumer widens them exactly —
+`weight_bias_grad` (g4c_weight_grad_bf16_a16 reads a 128-column window in place), `backward_chain` (bf16 `mul`), `act_grad`,
+`layernorm_grad`.  A step is bit for bit the mixed step with its kept rows replaced by their bf16 roundings.
 """
 from __future__ import annotations
 
@@ -84,8 +89,9 @@ def act_grad(dy: Tensor, ref: Tensor, act: int, from_input: bool, out: Optional[
     dev = _lib.require_hip(dy, ref)
     if out is None:
         out = _buf(int(dy.size(0)), int(dy.size(1)), dev)
-    _lib.check(lib.g4c_act_grad(_lib.ptr(dy), _ld(dy), _lib.ptr(ref), _ld(ref), 1 if from_input else 0, act, _lib.ptr(out),
-                                _ld(out), int(dy.size(1)), int(dy.size(0)), _lib.stream_handle(dev)))
+    fn = lib.g4c_act_grad_ref16 if ref.dtype == torch.bfloat16 else lib.g4c_act_grad       # (bf16 rows: widened exactly at the load)
+    _lib.check(fn(_lib.ptr(dy), _ld(dy), _lib.ptr(ref), _ld(ref), 1 if from_input else 0, act, _lib.ptr(out),
+                  _ld(out), int(dy.size(1)), int(dy.size(0)), _lib.stream_handle(dev)))
     return out
 
 
@@ -106,8 +112,9 @@ def layernorm_grad(z: Tensor, gamma: Tensor, dy: Tensor, eps: float):
     rows, width = int(z.size(0)), int(z.size(1))
     dz = _buf(rows, width, dev)
     partial = _buf(int(lib.g4c_layernorm_grad_partials(rows)), 2 * width, dev)
-    _lib.check(lib.g4c_layernorm_grad(_lib.ptr(z), _ld(z), _lib.ptr(gamma), _lib.ptr(dy), _ld(dy), _lib.ptr(dz), _ld(dz),
-                                      _lib.ptr(partial), width, rows, float(eps), _lib.stream_handle(dev)))
+    fn = lib.g4c_layernorm_grad_z16 if z.dtype == torch.bfloat16 else lib.g4c_layernorm_grad       # (bf16 rows: widened exactly at the load)
+    _lib.check(fn(_lib.ptr(z), _ld(z), _lib.ptr(gamma), _lib.ptr(dy), _ld(dy), _lib.ptr(dz), _ld(dz),
+                  _lib.ptr(partial), width, rows, float(eps), _lib.stream_handle(dev)))
     gb = colsum(partial)
     return dz, gb[:width], gb[width:]
 
@@ -191,6 +198,8 @@ def backward_chain(g: Tensor, weights: Sequence[Tensor], acts: Sequence[Tensor],
     D = {l: _buf(M, 128, dev) for l in range(L - 1, 0, -1)}
     save = [D[l] for l in range(L - 1, 0, -1)] + [None]
     mul = [acts[l] for l in range(L - 1, 0, -1)] + [None]
+    if pk.precision != "bf16":          # (rows kept as bf16 by a forward in the mode, differentiated outside it: the split streams read fp32)
+        mul = [t.float() if (t is not None and t.dtype == torch.bfloat16) else t for t in mul]
     gx = ops.mlp_forward(pk, [Source(g)], M, _lib.ACT_NONE, save=save, mul=mul)
     return D, gx
 
@@ -200,7 +209,10 @@ def _wgrad_tile(g: Tensor, blk: Tensor, M: int, with_bias: bool, scratch: Tensor
     (ops.train_precision() "bf16": g4c_weight_grad_bf16 — both operands rounded to bf16, the column sums from the fp32 g)."""
     lib = _lib.load()
     out = torch.empty(128 * 128 + 128, dtype=torch.float32, device=g.device)
-    fn = lib.g4c_weight_grad_bf16 if ops.train_precision() == "bf16" else lib.g4c_weight_grad
+    if blk.dtype == torch.bfloat16:          # rows kept as bf16 (weight_bias_grad): staged as they are, the mode is "bf16"
+        fn = lib.g4c_weight_grad_bf16_a16
+    else:
+        fn = lib.g4c_weight_grad_bf16 if ops.train_precision() == "bf16" else lib.g4c_weight_grad
     _lib.check(fn(_lib.ptr(g), _ld(g), _lib.ptr(blk), _ld(blk), M, _lib.ptr(scratch), _lib.ptr(out), 1 if with_bias else 0,
                   _lib.stream_handle(g.device)))
     return out
@@ -224,6 +236,13 @@ def weight_bias_grad(g: Tensor, a: Tensor, want_bias: bool = True):
     copies of the odd blocks (round 5: those went to a split-row rocBLAS GEMM)."""
     M, N, K = int(g.size(0)), int(g.size(1)), int(a.size(1))
     dev = _lib.require_hip(g, a)
+    if a.dtype == torch.bfloat16:
+        # rows the forward kept as bf16 (ops.saved_precision() "bf16"): a 16-byte aligned 128-column window is read in place by
+        # g4c_weight_grad_bf16_a16 — the bf16 product, so in the mode only; any other shape is widened (exactly) and padded as before
+        in_place = (ops.train_precision() == "bf16" and K == 128 and a.stride(1) == 1 and _ld(a) % 4 == 0 and _ld(a) >= 128
+                    and a.data_ptr() % 16 == 0)
+        if not in_place:
+            a = a.float()
     if M == 0:
         return torch.zeros((N, K), dtype=torch.float32, device=dev), (torch.zeros(N, dtype=torch.float32, device=dev) if want_bias else None)
     lib = _lib.load()
@@ -238,7 +257,7 @@ def weight_bias_grad(g: Tensor, a: Tensor, want_bias: bool = True):
         for j, k0 in enumerate(range(0, K, 128)):
             k1 = min(k0 + 128, K)
             if k0 not in a_blocks:
-                a_blocks[k0] = _pad128(a, k0, k1)
+                a_blocks[k0] = a if a.dtype == torch.bfloat16 else _pad128(a, k0, k1)          # (bf16: the one 128-column window, checked above)
             with_bias = want_bias and j == 0
             out = _wgrad_tile(gp, a_blocks[k0], M, with_bias, scratch)
             tile = out[:128 * 128].view(128, 128)
@@ -286,8 +305,11 @@ class _FusedMLP(torch.autograd.Function):
                                                          and not spec.packed.rs2 and not any(spec.packed.rs_blocks))
         if SAVE_ACTIVATIONS and can_save and spec.n_rows > 0:
             dev = tensors[0].device
-            saves = [_buf(spec.n_rows, 128, dev) for _ in range(spec.n_layers - 1)] + \
-                    [_buf(spec.n_rows, 128, dev) if spec.has_ln else None]
+            # ops.saved_precision() "bf16": the plain rounded-bf16 stream keeps its rows rounded once to bf16 (half the bytes between
+            # the passes); a bf16x6 pack keeps fp32 rows.  The backward goes by each tensor's dtype.
+            dt = torch.bfloat16 if (ops.saved_precision() == "bf16" and spec.packed.precision == "bf16") else torch.float32
+            saves = [torch.empty((spec.n_rows, 128), dtype=dt, device=dev) for _ in range(spec.n_layers - 1)] + \
+                    [torch.empty((spec.n_rows, 128), dtype=dt, device=dev) if spec.has_ln else None]
         y = ops.mlp_forward(spec.packed, srcs, spec.n_rows, spec.act, resid=resid, resid_col0=spec.resid_col0, save=saves)
         ctx.spec, ctx.saves = spec, saves
         ctx.save_for_backward(y, *tensors)

@@ -89,11 +89,13 @@ struct Params {
     // activations of a hidden layer, the pre-LayerNorm rows of the last one — so the backward pass recomputes nothing
     float *save[G4C_MAX_LAYERS];
     int save_ld;
+    int save_bf16;           // plain rounded-bf16 stream only: the kept rows are stored as bf16 (save[] are __bf16 pointers in disguise, save_ld in elements)
     // backward chain (same entry point): mul[l] (or null) = the SELU OUTPUT rows a hidden layer l's result is multiplied by the
     // slope of, instead of bias + SELU:  y = x * selu'(.)  — the launch then computes  g_{k-1} = (g_k W_k) * selu'(a_{k-1})  layer
     // after layer, writing every g through save[]
     const float *mul[G4C_MAX_LAYERS];
     int mul_ld;
+    int mul_bf16;            // plain rounded-bf16 stream only: the mul rows are bf16 (mul[] are __bf16 pointers in disguise, mul_ld in elements), widened exactly
     // f16x3 arithmetic: range_flag[range_slot] = 1 when a value converted to fp16 reached the end of the fp16 range (g4c_mlp_t)
     int *range_flag;
     int range_slot;

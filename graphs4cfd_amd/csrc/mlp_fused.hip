@@ -680,6 +680,24 @@ constexpr int G4C_F16_MINW = 4;
 // layers' biases staged, and the input rows loaded through a per-tile buffer descriptor with a 32-bit lane offset (rows of the last
 // tile past M come back as zeros from the descriptor's range check instead of being clamped; they are never stored).  Same
 // arithmetic in the same order: bit-identical to the generic instantiation.
+// The training forms' rows as bf16, four columns of one thread — the plain rounded-bf16 stream (SP == 1) only, selected by the
+// wave-uniform Params.save_bf16 / mul_bf16, which only the SAVE instantiations read; the SP = 2 / 3 instantiations keep fp32 rows (the
+// launcher refuses bf16 for them).  save: each value rounded once to bf16 (nearest even, v_cvt_pk_bf16_f32), one 8-byte store (save_ld
+// in elements, a multiple of 4, the base 16-byte aligned).  mul: an 8-byte load, widened exactly.
+__device__ __forceinline__ void save_row4_bf16(const Params &p, int l, long long gr, int col, f32x4 x) {
+    bf16x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (__bf16)x[e];
+    *reinterpret_cast<bf16x4 *>(reinterpret_cast<__bf16 *>(p.save[l]) + gr * p.save_ld + col) = v;
+}
+__device__ __forceinline__ f32x4 mul_row4_bf16(const Params &p, int l, long long gr, int col) {
+    const bf16x4 v = *reinterpret_cast<const bf16x4 *>(reinterpret_cast<const __bf16 *>(p.mul[l]) + gr * p.mul_ld + col);
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = (float)v[e];
+    return r;
+}
+
 template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2, bool TRACK = true, class SH = TileShapeGeneric>
 __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX6_MINW)) void mlp_bx6_kernel(const Params p) {
     static_assert(TRACK || (SP == 2 && !SAVE), "the tracker-free instantiations: f16x3 stream, inference");
@@ -1067,7 +1085,10 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
                     *reinterpret_cast<f32x4 *>(sH + (i + 32 * t) * HS + fbase + 8 * gq) = x;
                     if (SAVE) {
                         const long long gr = row0 + i + 32 * t;
-                        if (p.save[l] && gr < mlim) *reinterpret_cast<f32x4 *>(p.save[l] + gr * p.save_ld + fbase + 8 * gq) = x;
+                        if (p.save[l] && gr < mlim) {
+                            if (SP == 1 && p.save_bf16) save_row4_bf16(p, l, gr, fbase + 8 * gq, x);
+                            else *reinterpret_cast<f32x4 *>(p.save[l] + gr * p.save_ld + fbase + 8 * gq) = x;
+                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1086,7 +1107,9 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
                 f32x4 y;
                 if (SAVE && p.mul[l]) {
                     const long long gr = row0 + i + 32 * t;
-                    const f32x4 r = *reinterpret_cast<const f32x4 *>(p.mul[l] + (gr < mlim ? gr : mlim - 1) * p.mul_ld + fbase + 8 * gq);
+                    const f32x4 r = (SP == 1 && p.mul_bf16)
+                                        ? mul_row4_bf16(p, l, gr < mlim ? gr : mlim - 1, fbase + 8 * gq)
+                                        : *reinterpret_cast<const f32x4 *>(p.mul[l] + (gr < mlim ? gr : mlim - 1) * p.mul_ld + fbase + 8 * gq);
                     const float sc = 1.0507009873554804934193349852946f, sa = 1.7580993408473768599402175208123f;   // scale, scale * alpha
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = x[e] * (r[e] > 0.f ? sc : r[e] + sa);
@@ -1095,7 +1118,10 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
                 }
                 if (SAVE) {
                     const long long gr = row0 + i + 32 * t;
-                    if (p.save[l] && gr < mlim) *reinterpret_cast<f32x4 *>(p.save[l] + gr * p.save_ld + fbase + 8 * gq) = y;
+                    if (p.save[l] && gr < mlim) {
+                        if (SP == 1 && p.save_bf16) save_row4_bf16(p, l, gr, fbase + 8 * gq, y);
+                        else *reinterpret_cast<f32x4 *>(p.save[l] + gr * p.save_ld + fbase + 8 * gq) = y;
+                    }
                 }
                 split3x4<SP>(y, vh, vm, vl, rng);
                 __bf16 *d = sB + (i + 32 * t) * HB + fbase + 8 * gq;

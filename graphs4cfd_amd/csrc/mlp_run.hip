@@ -215,22 +215,31 @@ int stage_save(const g4c_mlp_io_t *io, Launch &L) {
     Params &p = L.p;
     const int n_layers = p.n_layers;
     if (!L.save) return G4C_OK;
-    // (the rounded-bf16 stream saves on the plain tile kernel only: the row-split streams keep refusing; saved / mul rows stay fp32)
+    // (the rounded-bf16 stream saves on the plain tile kernel only: the row-split streams keep refusing)
     G4C_REQUIRE(L.bx6 && (!L.round1 || L.fmt == G4C_WFMT_BF16) && !io->out_dtype && !L.agg && !io->n_heads && !p.out_idx && io->save_ld >= NP &&
                     (io->save_ld & 3) == 0,
                 G4C_EUNSUPPORTED,
                 "g4c_mlp_run: save needs w_format BF16X3 / F16X2 / BF16 without heads / aggregation / output index / bf16 rows, save_ld >= 128 "
                 "and a multiple of 4");
     G4C_REQUIRE(io->n_save == n_layers, G4C_EINVAL, "g4c_mlp_run: n_save %d for %d layers", io->n_save, n_layers);
+    // bf16 save / mul rows: the SP = 1 instantiations only (the plain rounded-bf16 stream); the split streams keep fp32 rows
+    G4C_REQUIRE((io->save_dtype == G4C_DTYPE_F32 || io->save_dtype == G4C_DTYPE_BF16) &&
+                    (io->mul_dtype == G4C_DTYPE_F32 || io->mul_dtype == G4C_DTYPE_BF16),
+                G4C_EINVAL, "g4c_mlp_run: save_dtype %d / mul_dtype %d (G4C_DTYPE_F32 or G4C_DTYPE_BF16)", io->save_dtype, io->mul_dtype);
+    G4C_REQUIRE((!io->save_dtype && !io->mul_dtype) || L.fmt == G4C_WFMT_BF16, G4C_EINVAL,
+                "g4c_mlp_run: bf16 save / mul rows need w_format G4C_WFMT_BF16 (the plain rounded-bf16 stream); w_format %d keeps fp32 rows",
+                L.fmt);
     bool mul = false;
     for (int l = 0; l < n_layers; ++l) {
         G4C_REQUIRE(((uintptr_t)io->save[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: save[%d] is not 16-byte aligned", l);
-        p.save[l] = io->save[l];
+        p.save[l] = static_cast<float *>(io->save[l]);
         if (l + 1 == n_layers) break;
         G4C_REQUIRE(((uintptr_t)io->mul[l] & 15) == 0, G4C_EINVAL, "g4c_mlp_run: mul[%d] is not 16-byte aligned", l);
-        p.mul[l] = io->mul[l];
+        p.mul[l] = static_cast<const float *>(io->mul[l]);
         mul = mul || io->mul[l];
     }
+    p.save_bf16 = io->save_dtype == G4C_DTYPE_BF16;
+    p.mul_bf16 = io->mul_dtype == G4C_DTYPE_BF16;
     p.save_ld = io->save_ld;
     G4C_REQUIRE(!mul || (io->mul_ld >= NP && (io->mul_ld & 3) == 0), G4C_EINVAL, "g4c_mlp_run: mul_ld=%d", io->mul_ld);
     p.mul_ld = io->mul_ld;

@@ -7,6 +7,7 @@
 // Reference being differentiated: graphs4cfd/nn/blocks.py:117-144 (MLP), :175-186 (GNBlock), :219-237 (DownMP),
 // :265-290 (UpMP); the reference relies on torch autograd over cat / index / Linear / SELU / LayerNorm / scatter.
 #include "g4c_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -56,8 +57,23 @@ __global__ __launch_bounds__(256) void train_gather_kernel(const float *__restri
     }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void act_grad_kernel(const float *__restrict__ dy, int dy_ld, const float *__restrict__ ref,
+// Rows the forward kept for the backward are fp32 or, with the bf16 saved-activation precision, bf16: a bf16 value is widened
+// exactly at the load and everything after the load is the fp32 code (TR / TZ / TA = float or __bf16 below).
+typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ float widen(float x) { return x; }
+__device__ __forceinline__ float widen(__bf16 x) { return (float)x; }
+__device__ __forceinline__ f32x4 load_row4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+__device__ __forceinline__ f32x4 load_row4(const __bf16 *p) {          // 8 bytes
+    const wg_bf16x4 v = *reinterpret_cast<const wg_bf16x4 *>(p);
+    f32x4 x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = (float)v[e];
+    return x;
+}
+
+template <int V, class TR>
+__global__ __launch_bounds__(256) void act_grad_kernel(const float *__restrict__ dy, int dy_ld, const TR *__restrict__ ref,
                                                        int ref_ld, int from_input, int act, float *__restrict__ dz, int dz_ld,
                                                        int width, long long n_rows) {
     const int wv = width / V;
@@ -67,13 +83,13 @@ __global__ __launch_bounds__(256) void act_grad_kernel(const float *__restrict__
     if (r >= n_rows) return;
     if (V == 4) {
         const f32x4 g = *reinterpret_cast<const f32x4 *>(dy + r * dy_ld + c);
-        const f32x4 x = *reinterpret_cast<const f32x4 *>(ref + r * ref_ld + c);
+        const f32x4 x = load_row4(ref + r * ref_ld + c);
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = g[e] * act_slope(x[e], act, from_input);
         *reinterpret_cast<f32x4 *>(dz + r * dz_ld + c) = o;
     } else {
-        dz[r * dz_ld + c] = dy[r * dy_ld + c] * act_slope(ref[r * ref_ld + c], act, from_input);
+        dz[r * dz_ld + c] = dy[r * dy_ld + c] * act_slope(widen(ref[r * ref_ld + c]), act, from_input);
     }
 }
 
@@ -84,7 +100,11 @@ inline bool vec4_ok(const void *p, int ld, int col0) { return ((uintptr_t)p % 16
 // dgamma / dbeta: every workgroup keeps running column sums over its rows and writes one partial row
 // [dgamma(width) | dbeta(width)]; g4c_colsum adds the partial rows in a fixed order.
 constexpr int LN_MAXC = 4;
-__global__ __launch_bounds__(256) void layernorm_grad_kernel(const float *__restrict__ z, int z_ld, const float *__restrict__ gamma,
+// TZ = __bf16 (g4c_layernorm_grad_z16): the pre-norm rows as the forward kept them, widened at the load; the lane <-> column map, and with
+// it the order of every row reduction, is the fp32 form's.  (Known cost, DESIGN.md 7.2: the compiler puts the widening inside the
+// `c < width` guard behind a wait for the 2-byte load, so a row's z loads complete one after another.)
+template <class TZ>
+__global__ __launch_bounds__(256) void layernorm_grad_kernel(const TZ *__restrict__ z, int z_ld, const float *__restrict__ gamma,
                                                              const float *__restrict__ dy, int dy_ld, float *__restrict__ dz,
                                                              int dz_ld, float *__restrict__ partial, int width,
                                                              long long n_rows, float eps) {
@@ -103,7 +123,7 @@ __global__ __launch_bounds__(256) void layernorm_grad_kernel(const float *__rest
 #pragma unroll
         for (int j = 0; j < LN_MAXC; ++j) {
             const int c = lane + 64 * j;
-            zv[j] = c < width ? z[r * z_ld + c] : 0.f;
+            zv[j] = c < width ? widen(z[r * z_ld + c]) : 0.f;
             gy[j] = c < width ? dy[r * dy_ld + c] : 0.f;
             s += zv[j];
         }
@@ -297,11 +317,18 @@ __global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_kernel(const float 
 //  * rows past the end of the chunk are zero-filled when they are fetched: every lane reads a full fragment, nothing is masked.
 //  * db: column sums of the UNROUNDED fp32 g, as in weight_grad_kernel.
 constexpr int WGB_SLAB = 64, WGB_CS = 2 * WGB_SLAB + 16;
-typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_bf16_kernel(const float *__restrict__ g, int g_ld, const float *__restrict__ a,
+// TA = __bf16 (g4c_weight_grad_bf16_a16): operand a is ALREADY bf16 rows — rows a forward launch kept with the bf16 saved-activation
+// precision.  The thread keeps its map of 4 rows x 4 columns and fetches each of its rows with one 8-byte load (a wave reads 64
+// contiguous bytes of each of its 8 rows; the neighbouring wave reads the other half of the 128-byte line), holds the slab in flight
+// in 8 registers instead of 16, and stages the values as they are: the LDS image, and with it every MFMA operand, is bit for bit the
+// one the fp32 form makes of the widened rows (rounding a widened bf16 value gives it back).  768 instead of 1024 bytes per row.
+// (A map of 2 rows x 8 columns with 16-byte loads and conflict-free 4-byte LDS stores was built and measured: no faster)
+template <class TA>
+__global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_bf16_kernel(const float *__restrict__ g, int g_ld, const TA *__restrict__ a,
                                                                          int a_ld, long long n_rows, long long chunk,
                                                                          float *__restrict__ partial, int with_bias) {
+    constexpr bool A16 = sizeof(TA) == 2;
+    typedef typename std::conditional<A16, wg_bf16x4, f32x4>::type a_row4;      // one row's four columns as fetched
     __shared__ __attribute__((aligned(16))) unsigned char sG[WG_N * WGB_CS];
     __shared__ __attribute__((aligned(16))) unsigned char sA[WG_N * WGB_CS];
     static_assert(WG_N * WGB_CS >= 16 * WG_N * (int)sizeof(float), "the db reduction reuses sG");
@@ -318,14 +345,18 @@ __global__ __launch_bounds__(WG_THREADS, 2) void weight_grad_bf16_kernel(const f
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[kb][j] = 0.f;
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-    f32x4 pg[4], pa[4];                                         // the slab after the one in LDS
+    f32x4 pg[4];                                                // the slab after the one in LDS
+    a_row4 pa[4];
     auto fetch = [&](long long m0) __attribute__((always_inline)) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const long long r = m0 + rr + it;
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            a_row4 za;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) za[e] = 0;
             pg[it] = r < r1 ? *reinterpret_cast<const f32x4 *>(g + r * g_ld + c4) : z;
-            pa[it] = r < r1 ? *reinterpret_cast<const f32x4 *>(a + r * a_ld + c4) : z;
+            pa[it] = r < r1 ? *reinterpret_cast<const a_row4 *>(a + r * a_ld + c4) : za;
         }
     };
     if (r0 < r1) fetch(r0);
@@ -427,9 +458,27 @@ extern "C" int g4c_act_grad(const float *dy, int32_t dy_ld, const float *ref, in
     const bool v4 = width % 4 == 0 && vec4_ok(dy, dy_ld, 0) && vec4_ok(ref, ref_ld, 0) && vec4_ok(dz, dz_ld, 0);
     const long long total = n_rows * (width / (v4 ? 4 : 1));
     const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
-    if (v4) act_grad_kernel<4><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
-    else act_grad_kernel<1><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
+    if (v4) act_grad_kernel<4, float><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
+    else act_grad_kernel<1, float><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
     return g4c::check_launch("g4c_act_grad");
+}
+
+extern "C" int g4c_act_grad_ref16(const float *dy, int32_t dy_ld, const void *ref, int32_t ref_ld, int32_t from_input, int32_t act,
+                                  float *dz, int32_t dz_ld, int32_t width, int64_t n_rows, void *stream) {
+    // (every argument is checked before the first HIP call)
+    G4C_REQUIRE((dy && ref && dz) || n_rows == 0, G4C_EINVAL, "g4c_act_grad_ref16: null pointer");
+    G4C_REQUIRE(width > 0 && n_rows >= 0 && dy_ld >= width && ref_ld >= width && dz_ld >= width && act >= 0 && act <= 2, G4C_EINVAL,
+                "g4c_act_grad_ref16: bad arguments width=%d lds=%d,%d,%d act=%d", width, dy_ld, ref_ld, dz_ld, act);
+    G4C_REQUIRE((uintptr_t)ref % 2 == 0, G4C_EINVAL, "g4c_act_grad_ref16: ref %p is not a bf16 pointer", ref);
+    if (n_rows == 0) return G4C_OK;
+    g4c::DeviceGuard on_device(dz);
+    const __bf16 *ref16 = static_cast<const __bf16 *>(ref);
+    const bool v4 = width % 4 == 0 && vec4_ok(dy, dy_ld, 0) && vec4_ok(dz, dz_ld, 0) && (uintptr_t)ref % 8 == 0 && ref_ld % 4 == 0;
+    const long long total = n_rows * (width / (v4 ? 4 : 1));
+    const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+    if (v4) act_grad_kernel<4, __bf16><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref16, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
+    else act_grad_kernel<1, __bf16><<<grid, blk, 0, (hipStream_t)stream>>>(dy, dy_ld, ref16, ref_ld, from_input, act, dz, dz_ld, width, n_rows);
+    return g4c::check_launch("g4c_act_grad_ref16");
 }
 
 extern "C" int32_t g4c_layernorm_grad_partials(int64_t n_rows) {
@@ -444,9 +493,23 @@ extern "C" int g4c_layernorm_grad(const float *z, int32_t z_ld, const float *gam
     G4C_REQUIRE(width > 0 && width <= 64 * LN_MAXC && n_rows >= 0 && z_ld >= width && dy_ld >= width && dz_ld >= width,
                 G4C_EUNSUPPORTED, "g4c_layernorm_grad: width %d (max %d) / leading dimensions", width, 64 * LN_MAXC);
     const int n_wg = g4c_layernorm_grad_partials(n_rows);
-    layernorm_grad_kernel<<<dim3(n_wg), dim3(256), 0, (hipStream_t)stream>>>(z, z_ld, gamma, dy, dy_ld, dz, dz_ld, partial, width,
-                                                                              n_rows, eps);
+    layernorm_grad_kernel<float><<<dim3(n_wg), dim3(256), 0, (hipStream_t)stream>>>(z, z_ld, gamma, dy, dy_ld, dz, dz_ld, partial, width,
+                                                                                     n_rows, eps);
     return g4c::check_launch("g4c_layernorm_grad");
+}
+
+extern "C" int g4c_layernorm_grad_z16(const void *z, int32_t z_ld, const float *gamma, const float *dy, int32_t dy_ld, float *dz,
+                                      int32_t dz_ld, float *partial, int32_t width, int64_t n_rows, float eps, void *stream) {
+    // (every argument is checked before the first HIP call)
+    G4C_REQUIRE(((z && dy && dz) || n_rows == 0) && gamma && partial, G4C_EINVAL, "g4c_layernorm_grad_z16: null pointer");
+    G4C_REQUIRE((uintptr_t)z % 2 == 0, G4C_EINVAL, "g4c_layernorm_grad_z16: z %p is not a bf16 pointer", z);
+    G4C_REQUIRE(width > 0 && width <= 64 * LN_MAXC && n_rows >= 0 && z_ld >= width && dy_ld >= width && dz_ld >= width,
+                G4C_EUNSUPPORTED, "g4c_layernorm_grad_z16: width %d (max %d) / leading dimensions", width, 64 * LN_MAXC);
+    g4c::DeviceGuard on_device(dz);
+    const int n_wg = g4c_layernorm_grad_partials(n_rows);
+    layernorm_grad_kernel<__bf16><<<dim3(n_wg), dim3(256), 0, (hipStream_t)stream>>>(static_cast<const __bf16 *>(z), z_ld, gamma, dy, dy_ld, dz,
+                                                                                      dz_ld, partial, width, n_rows, eps);
+    return g4c::check_launch("g4c_layernorm_grad_z16");
 }
 
 extern "C" int32_t g4c_colsum_partials(int64_t n_rows) {
@@ -512,15 +575,17 @@ extern "C" int g4c_weight_grad(const float *g, int32_t g_ld, const float *a, int
     return g4c::check_launch("g4c_weight_grad");
 }
 
-extern "C" int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch,
-                                    float *out, int32_t with_bias, void *stream) {
+// g4c_weight_grad_bf16 (TA = float) and g4c_weight_grad_bf16_a16 (TA = __bf16): one body, `who` names the entry point in messages
+template <class TA>
+static int weight_grad_bf16_run(const char *who, const float *g, int32_t g_ld, const TA *a, int32_t a_ld, int64_t n_rows, float *scratch,
+                                float *out, int32_t with_bias, void *stream) {
     // (every argument is checked before the first HIP call: a bad call fails the same way with or without a device)
-    G4C_REQUIRE(g && a && scratch && out, G4C_EINVAL, "g4c_weight_grad_bf16: null pointer");
-    G4C_REQUIRE(n_rows >= 0, G4C_EINVAL, "g4c_weight_grad_bf16: n_rows %lld is negative", (long long)n_rows);
+    G4C_REQUIRE(g && a && scratch && out, G4C_EINVAL, "%s: null pointer", who);
+    G4C_REQUIRE(n_rows >= 0, G4C_EINVAL, "%s: n_rows %lld is negative", who, (long long)n_rows);
     G4C_REQUIRE(g_ld >= WG_N && a_ld >= WG_N && g_ld % 4 == 0 && a_ld % 4 == 0, G4C_EINVAL,
-                "g4c_weight_grad_bf16: leading dimensions must be >= 128 and multiples of 4 (g_ld=%d a_ld=%d)", g_ld, a_ld);
+                "%s: leading dimensions must be >= 128 and multiples of 4 (g_ld=%d a_ld=%d)", who, g_ld, a_ld);
     G4C_REQUIRE((uintptr_t)g % 16 == 0 && (uintptr_t)a % 16 == 0, G4C_EINVAL,
-                "g4c_weight_grad_bf16: g and a must be 16-byte aligned (g=%p a=%p)", (const void *)g, (const void *)a);
+                "%s: g and a must be 16-byte aligned (g=%p a=%p)", who, (const void *)g, (const void *)a);
     g4c::DeviceGuard on_device(out);
     // the partial-tile rule of g4c_weight_grad: the same G and the same chunk of whole 32-row units per workgroup (this kernel cuts
     // its chunk into 64-row slabs and zero-fills the last one)
@@ -528,7 +593,7 @@ extern "C" int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a
     const long long slabs = (n_rows + WG_SLAB - 1) / WG_SLAB;
     const long long chunk = ((slabs + G - 1) / G) * WG_SLAB;
     hipStream_t st = (hipStream_t)stream;
-    weight_grad_bf16_kernel<<<dim3(G), dim3(WG_THREADS), 0, st>>>(g, g_ld, a, a_ld, n_rows, chunk > 0 ? chunk : WG_SLAB, scratch, with_bias);
+    weight_grad_bf16_kernel<TA><<<dim3(G), dim3(WG_THREADS), 0, st>>>(g, g_ld, a, a_ld, n_rows, chunk > 0 ? chunk : WG_SLAB, scratch, with_bias);
     const int width = WG_N * WG_N + (with_bias ? WG_N : 0), ld = WG_N * WG_N + WG_N;
     float *scratch2 = scratch + (long long)G * ld;
     const int g2 = wg_stage2_rows(G);
@@ -536,7 +601,18 @@ extern "C" int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a
     const unsigned cb = (unsigned)((width + 255) / 256);
     colsum_stage_kernel<<<dim3(g2, cb), dim3(256), 0, st>>>(scratch, ld, width, G, chunk2 > 0 ? chunk2 : 1, scratch2, ld);
     colsum_stage_kernel<<<dim3(1, cb), dim3(256), 0, st>>>(scratch2, ld, width, g2, g2, out, ld);
-    return g4c::check_launch("g4c_weight_grad_bf16");
+    return g4c::check_launch(who);
+}
+
+extern "C" int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch,
+                                    float *out, int32_t with_bias, void *stream) {
+    return weight_grad_bf16_run<float>("g4c_weight_grad_bf16", g, g_ld, a, a_ld, n_rows, scratch, out, with_bias, stream);
+}
+
+extern "C" int g4c_weight_grad_bf16_a16(const float *g, int32_t g_ld, const void *a, int32_t a_ld, int64_t n_rows, float *scratch,
+                                        float *out, int32_t with_bias, void *stream) {
+    return weight_grad_bf16_run<__bf16>("g4c_weight_grad_bf16_a16", g, g_ld, static_cast<const __bf16 *>(a), a_ld, n_rows, scratch, out,
+                                        with_bias, stream);
 }
 
 extern "C" int64_t g4c_weight_grad_scratch_floats(int64_t n_rows) {

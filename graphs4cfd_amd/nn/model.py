@@ -50,13 +50,21 @@ class TrainConfig():
     name, folder, checkpoint (resume from), tensor_board (log dir or None), chk_interval (epochs), training_loss /
     validation_loss (callables `(graph, pred, target)`), epochs, num_steps (rollout lengths, advanced when the monitored
     loss falls below `add_steps['tolerance']`), batch_size, lr, grad_clip ({'epoch', 'limit'} or None), scheduler
-    ({'factor', 'patience', 'loss'} or None), stopping (minimum lr), mixed_precision, device."""
+    ({'factor', 'patience', 'loss'} or None), stopping (minimum lr), mixed_precision, device.
+    saved_activations ("fp32" | "bf16", not in the reference; "bf16" needs mixed_precision=True): the format of the rows the forward
+    keeps for the backward — "bf16" halves them (ops.set_train_precision(..., saved="bf16"))."""
 
     def __init__(self, name: str, folder: str = './', checkpoint: Union[None, str] = None, tensor_board: Union[None, str] = None,
                  chk_interval: int = 1, training_loss: Callable = None, validation_loss: Callable = None, epochs: int = 1,
                  num_steps: Union[int, List[int]] = [1], add_steps: dict = {'tolerance': 0, 'loss': 'training'},
                  batch_size: int = 1, lr: float = 1e-3, grad_clip: Union[None, dict] = None, scheduler: Union[None, dict] = None,
-                 stopping: float = 0., mixed_precision: bool = False, device: Optional[torch.device] = None):
+                 stopping: float = 0., mixed_precision: bool = False, device: Optional[torch.device] = None,
+                 saved_activations: str = "fp32"):
+        if saved_activations not in ("fp32", "bf16"):
+            raise ValueError(f"saved_activations {saved_activations!r}: expected 'fp32' or 'bf16'")
+        if saved_activations == "bf16" and not mixed_precision:
+            raise ValueError("saved_activations='bf16' needs mixed_precision=True")
+        self.saved_activations = saved_activations
         self.name, self.folder, self.checkpoint, self.tensor_board, self.chk_interval = name, folder, checkpoint, tensor_board, chk_interval
         self.training_loss, self.validation_loss, self.epochs = training_loss, validation_loss, epochs
         self.num_steps = [num_steps] if isinstance(num_steps, int) else num_steps

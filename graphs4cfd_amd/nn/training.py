@@ -191,17 +191,21 @@ class Trainer:
     def run(self) -> None:
         """The whole run.  `mixed_precision`: every matrix product of training and validation — forward, input gradients, weight
         gradients — takes operands rounded once to bf16 and accumulates in fp32 (ops.set_mlp_precision("bf16") +
-        ops.set_train_precision("bf16")); both switches are restored when the run ends, however it ends."""
+        ops.set_train_precision("bf16")); `saved_activations` "bf16" also keeps the rows the forward saves for the backward as bf16
+        (ops.set_train_precision("bf16", saved="bf16")); every switch is restored when the run ends, however it ends."""
         if not self.cfg['mixed_precision']:
             return self._run()
-        old_mlp, old_train = ops.set_mlp_precision("bf16"), ops.set_train_precision("bf16")
+        saved = self.cfg['saved_activations'] or "fp32"
+        old_saved = ops.saved_precision()
+        old_mlp, old_train = ops.set_mlp_precision("bf16"), ops.set_train_precision("bf16", saved=saved)
         try:
             print("[fit] mixed_precision: every matrix product (forward, input and weight gradients) takes bf16-rounded operands "
-                  "with fp32 accumulation; master weights, biases, LayerNorm, sums and Adam stay fp32, no loss scaling")
+                  "with fp32 accumulation; master weights, biases, LayerNorm, sums and Adam stay fp32, no loss scaling; "
+                  f"saved activations {saved}")
             return self._run()
         finally:
             ops.set_mlp_precision(old_mlp)
-            ops.set_train_precision(old_train)
+            ops.set_train_precision(old_train, saved=old_saved)
 
     def _run(self) -> None:
         m, cfg, cur = self.model, self.cfg, self.curriculum

@@ -850,18 +850,37 @@ def train_precision() -> str:
     return _TRAIN_PRECISION
 
 
-def set_train_precision(precision: str) -> str:
+SAVED_PRECISIONS = ("fp32", "bf16")
+_SAVED_PRECISION = "fp32"
+
+
+def saved_precision() -> str:
+    """The storage format of the rows a recorded forward keeps for the backward (`set_train_precision(..., saved=)`)."""
+    return _SAVED_PRECISION
+
+
+def set_train_precision(precision: str, saved: Optional[str] = None) -> str:
     """Select the arithmetic of the backward pass's matrix products (autograd.py); returns the previous setting.  Independent of
     `set_mlp_precision`, which selects the forward's.
     "bf16x6" (default): input gradients on the exact three-way bf16 split, weight gradients on the fp32 MFMA (g4c_weight_grad).
     "bf16" (mixed-precision training): every product of the backward takes both operands rounded once to bf16 (round to nearest
     even) and accumulates in fp32 — `autograd.linear` / `backward_chain` pack the rounded-bf16 stream, weight gradients run on
     g4c_weight_grad_bf16.  Bias gradients, LayerNorm / activation adjoints, segmented sums and gathers stay fp32.  bf16 has fp32's
-    exponent range, so gradient rows of 1e-6 .. 1e-9 need no loss scaling."""
-    global _TRAIN_PRECISION
+    exponent range, so gradient rows of 1e-6 .. 1e-9 need no loss scaling.
+    `saved` ("fp32", the meaning of None; or "bf16", with precision "bf16" only): the format of the rows a recorded forward keeps
+    for the backward (g4c_mlp_io_t.save).  "bf16": each kept row is stored rounded once to bf16 (nearest even) — half the bytes
+    between the passes; every consumer widens it exactly.  As a product operand the row was rounded to bf16 anyway, so weight
+    gradients do not move; SELU slopes and the LayerNorm adjoint see the rounding (<= 2^-9 relative).  `saved_precision()` reads
+    the setting back."""
+    global _TRAIN_PRECISION, _SAVED_PRECISION
     if precision not in TRAIN_PRECISIONS:
         raise ValueError(f"unknown training precision {precision!r} ({' | '.join(TRAIN_PRECISIONS)})")
-    old, _TRAIN_PRECISION = _TRAIN_PRECISION, precision
+    saved = "fp32" if saved is None else saved
+    if saved not in SAVED_PRECISIONS:
+        raise ValueError(f"unknown saved-activation precision {saved!r} ({' | '.join(SAVED_PRECISIONS)})")
+    if saved == "bf16" and precision != "bf16":
+        raise ValueError(f"saved='bf16' needs the training precision 'bf16' (mixed-precision training), not {precision!r}")
+    old, _TRAIN_PRECISION, _SAVED_PRECISION = _TRAIN_PRECISION, precision, saved
     return old
 
 
@@ -1201,6 +1220,14 @@ def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr
     return e_out, v_out, head_outs
 
 
+def _rows_dtype(what: str, tensors: Sequence[Tensor]) -> int:
+    """G4C_DTYPE_* of the `save` / `mul` rows of one launch: all fp32 or all bf16."""
+    kinds = {t.dtype for t in tensors}
+    if not kinds <= {torch.float32, torch.bfloat16} or len(kinds) > 1:
+        raise TypeError(f"{what} tensors must share one dtype, float32 or bfloat16 (got {sorted(str(k) for k in kinds)})")
+    return _lib.DTYPE_BF16 if kinds == {torch.bfloat16} else _lib.DTYPE_F32
+
+
 def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: int = _lib.ACT_NONE,
                 out: Optional[Tensor] = None, out_idx32: Optional[Tensor] = None,
                 resid: Optional[Tensor] = None, resid_col0: int = 0, rows: Optional[Tuple[int, int]] = None,
@@ -1214,7 +1241,8 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
     order) — inside the launch when the kernel can, otherwise with a g4c_segment_reduce afterwards.
     `save` (training forward; bf16x6 / f16x3 and the plain rounded-bf16 stream, not its row-split orders): one [n_rows, 128] fp32 tensor (or None) per layer, receiving that layer's output
     rows; `mul` (with `save`): per hidden layer the SELU-output rows whose slope multiplies that layer's result instead of bias + SELU
-    (the backward chain of a block, see include/g4c.h).
+    (the backward chain of a block, see include/g4c.h).  On the plain rounded-bf16 stream the `save` tensors, and the `mul` tensors,
+    may be bf16 (one dtype per list, TypeError otherwise): kept rows stored rounded once to bf16, `mul` rows widened exactly.
     A bf16 `out` (rounded-bf16 mode): the rows are stored as bf16.
     `rows_dtype=torch.bfloat16` (rounded-bf16 mode, with an aggregation the launch fuses; ignored otherwise): the output rows are
     stored as bf16 — their consumer rounds them to bf16 on load anyway, and the launch is HBM-bound on them; the aggregate stays fp32.
@@ -1324,19 +1352,22 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
         live = [t for t in save if t is not None]
         _lib.require_hip(*live)
         if any(t.dim() != 2 or t.size(0) < n_rows or t.size(1) < 128 or t.stride(1) != 1 or _ld(t) != _ld(live[0]) for t in live):
-            raise ValueError("save tensors must be [n_rows, >= 128] fp32 with one common leading dimension")
+            raise ValueError("save tensors must be [n_rows, >= 128] fp32 (or bf16) with one common leading dimension")
         if len(save) > _lib.MAX_LAYERS:
             raise ValueError(f"{len(save)} save tensors for {packed.desc.n_layers} layers")
         io.n_save, io.save_ld = len(save), _ld(live[0]) if live else 128
         io.save[:len(save)] = [_lib.ptr(t) for t in save]
+        io.save_dtype = _rows_dtype("save", live)
         if mul is not None:
             lm = [t for t in mul if t is not None]
             _lib.require_hip(*lm)
             if len(mul) != len(save) or any(t.size(0) < n_rows or t.size(1) < 128 or t.stride(1) != 1 or _ld(t) != _ld(lm[0]) for t in lm):
-                raise ValueError("mul tensors must be [n_rows, >= 128] fp32 with one common leading dimension, one entry per layer")
+                raise ValueError("mul tensors must be [n_rows, >= 128] fp32 (or bf16) with one common leading dimension, one entry per layer")
             io.mul[:len(mul)] = [_lib.ptr(t) for t in mul]
             io.mul_ld = _ld(lm[0]) if lm else 128
-        nbytes = 4.0 * (sum(packed.seg_widths) + packed.n_out + 128 * len(live)) * n_rows
+            io.mul_dtype = _rows_dtype("mul", lm)
+        # (bf16 save / mul rows count 2 bytes per value; the fp32 form's count is what it was)
+        nbytes = (4.0 * (sum(packed.seg_widths) + packed.n_out) + 128.0 * sum(t.element_size() for t in live)) * n_rows
     # (a residual adds data to the rows; an output index or a row sub-range writes only some rows of `out`: no bound for the tensor)
     lb = _certify(packed, sources, act, resid is not None or out_idx32 is not None or rows is not None, save is not None)
     try:

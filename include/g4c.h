@@ -268,16 +268,16 @@ typedef struct {
     /* training form (G4C_WFMT_BF16X3 / _F16X2, and the plain rounded-bf16 stream G4C_WFMT_BF16 — mixed-precision training; not the
      * row-split streams _BF16_RS / _RS2 / _RS2N, not with out_dtype; no heads / aggregation / out_idx; n_save = n_layers, 0 = off): save[l] (or NULL)
      * receives the rows layer l produces — SELU(hidden) for l < n_layers-1, the pre-LayerNorm rows for the last layer — as fp32
-     * [n_rows, 128] (save_ld >= 128, a multiple of 4; 16-byte aligned), so the backward pass of the block recomputes nothing
+     * (or, save_dtype, bf16) [n_rows, 128] (save_ld >= 128, a multiple of 4; 16-byte aligned), so the backward pass of the block recomputes nothing
      * (autograd.py).  mul[l] != NULL (hidden layers; mul_ld >= 128, a multiple of 4): the same launch as the BACKWARD chain of a block —
      * hidden layer l's result is multiplied by the SELU slope of the rows mul[l] holds (SELU outputs) instead of bias + SELU.  Packing
      * the transposed weights last layer first (zero biases) and passing the kept activations as `mul` gives
      *   g_{k-1} = (g_k W_k) * selu'(a_{k-1})   for every hidden layer, each g written through save[], and the input gradient as the
      * launch's output — one launch instead of a product + an elementwise pass per layer. */
     int32_t n_save;
-    float *save[G4C_MAX_LAYERS];
+    void *save[G4C_MAX_LAYERS];       /* fp32 rows, or bf16 rows with save_dtype G4C_DTYPE_BF16 (below) */
     int32_t save_ld;
-    const float *mul[G4C_MAX_LAYERS];
+    const void *mul[G4C_MAX_LAYERS];  /* fp32 rows, or bf16 rows with mul_dtype G4C_DTYPE_BF16 (below) */
     int32_t mul_ld;
     /* one launch per MP layer — `GNBlock.forward` (nn/blocks.py:175-186): e' = edge_mlp([e | v[row] | v[col]]), aggregation of e' per
      * target, v' = v_act(upd([aggr | v])) — for the f16x3 format.  `mlp` is the hoisted message MLP (one 128-wide weighted block `e`,
@@ -299,6 +299,14 @@ typedef struct {
      * range).  The array belongs to the caller of the launch, like every other output here: each consumer can pass its own.
      * A launch whose MLPs all carry g4c_mlp_t.range_certified (without save / mul) writes nothing here. */
     int32_t *range_flag;
+    /* Storage format of the save[] / mul[] rows: G4C_DTYPE_F32 (0, the default) or G4C_DTYPE_BF16 — G4C_WFMT_BF16 (the plain
+     * rounded-bf16 stream) only, every other format returns G4C_EINVAL.  save_dtype BF16: every kept row is stored as
+     * bf16(round-to-nearest-even(the fp32 value the launch stores with save_dtype F32)) — save[] are bf16 pointers, save_ld in elements
+     * (a multiple of 4), the bases 16-byte aligned; the launch's output and everything else it computes are bit for bit unchanged.
+     * mul_dtype BF16: the mul[] rows are bf16 (mul_ld in elements, a multiple of 4; 16-byte aligned), widened exactly to fp32 before
+     * the same slope expression.  The two are independent (the backward chain reads bf16 activations and writes fp32 gradients). */
+    int32_t save_dtype;
+    int32_t mul_dtype;
 } g4c_mlp_io_t;
 
 /* One fused-MLP launch over `n_rows` rows of the input `srcs`, writing what `io` names. */
@@ -452,11 +460,22 @@ int g4c_train_gather(const float *src, int32_t src_ld, int32_t scol0, const int3
 int g4c_act_grad(const float *dy, int32_t dy_ld, const float *ref, int32_t ref_ld, int32_t from_input, int32_t act,
                  float *dz, int32_t dz_ld, int32_t width, int64_t n_rows, void *stream);
 
+/* g4c_act_grad with `ref` stored as bf16 rows (ref_ld in elements): each value is widened exactly to fp32, everything after the load
+ * is g4c_act_grad — the result is bit for bit g4c_act_grad's on the widened rows.  Four columns per thread when width % 4 == 0, dy / dz
+ * are 16-byte aligned with leading dimensions that are multiples of 4 and ref is 8-byte aligned with ref_ld % 4 == 0; else one. */
+int g4c_act_grad_ref16(const float *dy, int32_t dy_ld, const void *ref, int32_t ref_ld, int32_t from_input, int32_t act,
+                       float *dz, int32_t dz_ld, int32_t width, int64_t n_rows, void *stream);
+
 /* LayerNorm backward (nn/blocks.py:141, eps 1e-5, affine): dz from the pre-norm rows z, gamma and dy; `partial` receives
  * g4c_layernorm_grad_partials(n_rows) rows of [dgamma(width) | dbeta(width)] partial sums — add them with g4c_colsum. */
 int32_t g4c_layernorm_grad_partials(int64_t n_rows);
 int g4c_layernorm_grad(const float *z, int32_t z_ld, const float *gamma, const float *dy, int32_t dy_ld, float *dz,
                        int32_t dz_ld, float *partial, int32_t width, int64_t n_rows, float eps, void *stream);
+
+/* g4c_layernorm_grad with the pre-norm rows z stored as bf16 (z_ld in elements), widened exactly at the load: bit for bit
+ * g4c_layernorm_grad on the widened rows, the same partials. */
+int g4c_layernorm_grad_z16(const void *z, int32_t z_ld, const float *gamma, const float *dy, int32_t dy_ld, float *dz,
+                           int32_t dz_ld, float *partial, int32_t width, int64_t n_rows, float eps, void *stream);
 
 /* out[c] = sum_r x[r, c] (bias gradients; the LayerNorm partials).  `scratch`: g4c_colsum_partials(n_rows) * width floats. */
 int32_t g4c_colsum_partials(int64_t n_rows);
@@ -479,6 +498,14 @@ int g4c_weight_grad(const float *g, int32_t g_ld, const float *a, int32_t a_ld, 
  * dimension below 128 or not a multiple of 4, or n_rows < 0 return G4C_EINVAL (g4c_last_error() says which). */
 int g4c_weight_grad_bf16(const float *g, int32_t g_ld, const float *a, int32_t a_ld, int64_t n_rows, float *scratch, float *out,
                          int32_t with_bias, void *stream);
+
+/* g4c_weight_grad_bf16 with operand `a` ALREADY stored as bf16 rows (rows a forward launch kept with save_dtype G4C_DTYPE_BF16;
+ * a_ld in elements, a multiple of 4 and >= 128; a 16-byte aligned — a 128-column window of a wider bf16 tensor is fine): the rows
+ * are staged without a conversion, g stays fp32 (rounded as it is staged, db from the unrounded rows).  Same slabs, LDS image, MFMA
+ * sequence, partial-tile rule, scratch and reduction: the result is bit for bit g4c_weight_grad_bf16's on the widened rows, at
+ * 768 instead of 1024 bytes per row.  The same validation before any HIP call. */
+int g4c_weight_grad_bf16_a16(const float *g, int32_t g_ld, const void *a, int32_t a_ld, int64_t n_rows, float *scratch, float *out,
+                             int32_t with_bias, void *stream);
 
 /* Adjoint of g4c_segment_reduce: dsrc[perm ? perm[p] : p] = dout[s] (/ max(count_s, 1) if mean) for p in segment s.
  * Rows of dsrc that belong to no segment are left untouched (zero them first when perm is not a full permutation). */

@@ -1,8 +1,9 @@
 """Training-step throughput of the autograd path: forward + GraphLoss + backward + Adam step of a
 MuS-GNN on a synthetic mesh, on the GPU (fused forward, recompute backward: autograd.py) and — on a bounded sample — with
 the oracle on the host cores (torch autograd over the op-for-op restatement = what the reference's fit() executes).
-Usage: python scripts/bench_train.py [--nodes 100000] [--model NsThreeScaleGNN] [--steps 10] [--cpu-steps 1] [--phases] [--mixed]
---mixed: the same step in mixed precision (what fit(mixed_precision=True) selects: every matrix product on bf16-rounded operands)."""
+Usage: python scripts/bench_train.py [--nodes 100000] [--model NsThreeScaleGNN] [--steps 10] [--cpu-steps 1] [--phases] [--mixed [--saved-bf16]]
+--mixed: the same step in mixed precision (what fit(mixed_precision=True) selects: every matrix product on bf16-rounded operands).
+--saved-bf16 (with --mixed): the rows the forward keeps for the backward as bf16 (TrainConfig(saved_activations="bf16"))."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,10 +17,13 @@ ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--cpu-steps", type=int, default=1)
 ap.add_argument("--phases", action="store_true", help="HIP-event time per phase of the backward pass (one extra step)")
 ap.add_argument("--mixed", action="store_true", help="mixed-precision training: set_mlp_precision('bf16') + set_train_precision('bf16')")
+ap.add_argument("--saved-bf16", action="store_true", help="with --mixed: saved activations as bf16 (set_train_precision('bf16', saved='bf16'))")
 a = ap.parse_args()
+if a.saved_bf16 and not a.mixed:
+    ap.error("--saved-bf16 needs --mixed")
 if a.mixed:
     gfd.ops.set_mlp_precision("bf16")
-    gfd.ops.set_train_precision("bf16")
+    gfd.ops.set_train_precision("bf16", saved="bf16" if a.saved_bf16 else None)
 dev = torch.device("cuda", 0)
 nf = 3
 if a.model == "NsRotEquiTreeScaleGNN":
@@ -75,7 +79,8 @@ with torch.no_grad():
 out = {"workload": f"{a.model} H=128 training step (forward + GraphLoss + backward + Adam) on a {a.nodes}-node synthetic 2D mesh",
        "gpu_ms_per_training_step": 1e3 * dt, "gpu_training_steps_per_s": 1 / dt, "gpu_ms_forward_recorded": 1e3 * fwd,
        "gpu_ms_forward_inference_eager": 1e3 * inf, "gpu_peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30,
-       "loss": float(loss), "mlp_precision": gfd.ops.mlp_precision(), "train_precision": gfd.ops.train_precision()}
+       "loss": float(loss), "mlp_precision": gfd.ops.mlp_precision(), "train_precision": gfd.ops.train_precision(),
+       "saved_precision": gfd.ops.saved_precision()}
 if a.phases:
     from graphs4cfd_amd import autograd as A
     A.PROFILE = {}
