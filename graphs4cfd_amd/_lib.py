@@ -23,8 +23,9 @@ KERNEL_MLP_RS = 5
 KERNEL_MLP_RS2 = 6
 KERNEL_MLP_BX6, KERNEL_MLP_WS = 2, 4
 KERNEL_MLP_BX6_CERT, KERNEL_MLP_WS_CERT = 7, 8      # the instantiations without the fp16 range tracker (g4c_mlp_t.range_certified)
+KERNEL_MLP_WS_PRE = 9                               # mlp_ws_pre_kernel: the first layer precomputed (g4c_mlp_t.k_pad[0] == 0)
 KERNEL_NAMES = {0: "none", 1: "mlp_split_kernel", 2: "mlp_bx6_kernel", 3: "mlp_bx6i_kernel", 4: "mlp_ws_kernel", 5: "mlp_rs1_kernel", 6: "mlp_rs2_kernel",
-                7: "mlp_bx6_kernel", 8: "mlp_ws_kernel"}   # g4c_mlp_last_kernel
+                7: "mlp_bx6_kernel", 8: "mlp_ws_kernel", 9: "mlp_ws_kernel"}   # g4c_mlp_last_kernel (9: its first-layer-precomputed form, one family for the timer)
 
 TILE_SHAPE_GENERIC, TILE_SHAPE_NODE, TILE_SHAPE_UP, TILE_SHAPE_DOWN = 0, 1, 2, 3      # g4c_mlp_last_shape
 

@@ -348,6 +348,9 @@ struct Launch {
     int fmt;
     bool round1, f16x2, bx6, row_split;
     bool agg, save;          // the fused aggregation (io->agg) / the training form (io->n_save)
+    // every source additive (g4c_mlp_t.k_pad[0] == 0 without a narrow block): the first layer is precomputed — the first source direct
+    // (the layer's own product with its bias), the stream and `w` start at layer 1 (the biases keep layer 0's unused slot)
+    bool pre;
     bool all_vec;            // every weighted source is 16-byte addressable (Src::vec)
     long long row_begin, row_count;
     int io_n_tiles;          // the caller's io->n_tiles (the aggregation plan's tile count)
@@ -383,6 +386,7 @@ int tile_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool bx6i_takes(const Launch &L);            // dual-tile software-pipelined kernel (mlp_bx6i.hip): bf16x6 stream only
 int bx6i_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool ws_takes(const Launch &L);              // weight-stationary persistent kernel (mlp_ws.hip): f16x3 and rounded-bf16 streams; io->upd
+bool ws_pre_takes(const Launch &L);          // ... its "first layer precomputed" form (Launch::pre): the one family that runs such a call
 int ws_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool rs_takes(const Launch &L);              // row-split persistent kernel (mlp_rs.hip): G4C_WFMT_BF16_RS, hoisted message form
 int rs_launch(const Launch &L, hipStream_t st, Ran &ran);

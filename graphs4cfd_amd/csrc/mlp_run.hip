@@ -9,6 +9,7 @@
 //
 //   family            when                                                                     if its envelope does not hold
 //   ws  (+ node)      io->upd: the fused MP layer                                              G4C_EUNSUPPORTED
+//   ws  (pre)         every source additive: the first layer precomputed (g4c_mlp_t.k_pad)     G4C_EUNSUPPORTED
 //   rs                w_format G4C_WFMT_BF16_RS (and no save)                                  G4C_EUNSUPPORTED
 //   rs2               w_format G4C_WFMT_BF16_RS2 / _RS2N (and no save, no aggregation)         G4C_EUNSUPPORTED
 //   ws                split-operand stream; g4c_mlp_ws_enable 2, or 1 and >= 20 000 rows       next row
@@ -141,7 +142,9 @@ int stage_sources(const g4c_src_t *srcs, int32_t n_src, int32_t k_pad0, Launch &
         L.all_vec = L.all_vec && d.vec;
         kp += d.wpad;
     }
-    G4C_REQUIRE(nk >= 1 || p.n_nar >= 1, G4C_EINVAL, "g4c_mlp_run: no input block goes through the weights");
+    // (every source additive: the first layer is precomputed, g4c_mlp_t.k_pad — the stream then has no layer 0, checked below)
+    L.pre = nk == 0 && p.n_nar == 0 && p.n_add >= 1;
+    G4C_REQUIRE(nk >= 1 || p.n_nar >= 1 || L.pre, G4C_EINVAL, "g4c_mlp_run: no input block goes through the weights");
     p.n_src = nk;
     if (nk == 0) p.src[0] = Src{nullptr, nullptr, 0, 0, 0, 0, 1, 0, nullptr, 0, nullptr, 0};
     for (int s = (nk ? nk : 1); s < G4C_MAX_SRC; ++s) p.src[s] = p.src[0];
@@ -324,6 +327,17 @@ bool at_size(const std::atomic<int> &mode_knob, long long min_rows, const Launch
 LaunchFn choose(Launch &L) {
     L.deep_ring = L.p.n_tiles <= g_deep_tiles.load(std::memory_order_relaxed);
     L.shapes = g_shapes.load(std::memory_order_relaxed) != 0;
+    if (L.pre) {
+        G4C_REQUIRE(!L.has_node, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) with upd: the fused MP layer has no such form");
+        G4C_REQUIRE(L.f16x2, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the f16x3 format (G4C_WFMT_F16X2), got w_format %d", L.fmt);
+        G4C_REQUIRE(L.p.n_layers == 3, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs three layers (two left), got %d", L.p.n_layers);
+        G4C_REQUIRE(L.agg && !L.save, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the fused aggregation and no save");
+        G4C_REQUIRE(ws_pre_takes(L), nullptr,
+                    "g4c_mlp_run: every source additive (first layer precomputed) is outside the weight-stationary kernel's envelope (three aligned "
+                    "128-wide fp32 additive blocks — the first direct, two through indices —, a plain fp32 128-wide output, no heads / residual "
+                    "/ output index / out_dtype)");
+        return ws_launch;
+    }
     if (L.has_node) {
         G4C_REQUIRE(ws_takes(L), nullptr,
                     "g4c_mlp_run: the message launch of the fused MP layer is outside the weight-stationary kernel's envelope (one 128-wide "

@@ -21,7 +21,8 @@
 // mlp_bx6_kernel<.., SP = 1> rounds them; there the rows of the weighted block may be bf16 and the output rows may be stored as bf16 /
 // bf16(SELU) — g4c_mlp_io_t.out_dtype), ONE weighted 128-wide aligned input block (rows direct or through an index, optional SELU on
 // load), 0 or 2 additive 128-wide blocks (SP = 1: 2), two or three layers, 128-wide output rows without residual / heads; an output
-// index only without the fused aggregation.
+// index only without the fused aggregation.  mlp_ws_pre_kernel (ws_body<.., PRE>): the same body started from a precomputed first layer —
+// three additive blocks, no weighted block, the two layers left of three (f16x3, fused aggregation, tracked).
 #include "mlp_common.h"
 #include <cstdlib>
 using namespace g4cm;
@@ -74,7 +75,8 @@ struct Meta { int r0[2], n[2], s0[2], s1[2]; };
 // row block / row half, piece s % 4):
 //   EK 0 nothing;  1 hidden-layer epilogue of accE[u] (sample rows 16 u + n);  2 park rows prow + 16 u of the gathered input
 //   (PACT: SELU pending on the stored rows);  3 last layer: fp32 rows of accE[u] into the tile's final buffer;  4 (m_block) = 3, then 2
-//   with the next pair's rows.
+//   with the next pair's rows;  5 (first layer precomputed) hidden-layer epilogue of xe[u], a tile's start values = the layer-0
+//   pre-activation itself in accumulator layout: no second accumulator to fold;  6 (m_block) = 3, then 5 with the next pair's tile A.
 // EK 1 / 2 work on one PAIR of values at a time: pieces 0 / 2 = [fold,] SELU of pair 0 / 1, pieces 1 / 3 = fp16 split + plane writes.
 struct Other {
     __bf16 *plane_acc;        // EK 1: this lane's element (row n, feature fcol) of the other tile's planes (swizzled address)
@@ -210,6 +212,16 @@ __device__ __forceinline__ void other_piece(int s, const f32x4 (&accE)[2], const
             if (SP == 2 && G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) put_pair_scaled(o.plane_park + u * 16 * PS + 2 * pr, hold, rng);
             else put_pair<SP>(o.plane_park + u * 16 * PS + 2 * pr, hold, rng);
         }
+    } else if (EK == 5) {
+        if ((pc4 & 1) == 0) {
+            f32x2 x;
+            x[0] = xe[u][2 * pr]; x[1] = xe[u][2 * pr + 1];
+            if (SP == 2 && G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) hold = selu2w_scaled(x);
+            else hold = selu2w(x);
+        } else {
+            if (SP == 2 && G4C_WS_SCALED && !(G4C_WS_ABLATE & 48)) put_pair_scaled(o.plane_acc + u * 16 * PS + 2 * pr, hold, rng);
+            else put_pair<SP>(o.plane_acc + u * 16 * PS + 2 * pr, hold, rng);
+        }
     } else if (EK == 3) {
         if (pc4 == 0) {
             f32x4 x;
@@ -254,6 +266,9 @@ __device__ __forceinline__ void m_block(const __bf16 *const (&pa)[4], const bf16
         if constexpr (EK == 4) {          // last layer's fp32 rows of accE, then the NEXT pair's first tile parked into the same tile's planes
             other_piece<SP, 3, false>(s, accE, accE1, xe, o, hold, rng);
             other_piece<SP, 2, PACT>(s, accE, accE1, xe, o, hold, rng);
+        } else if constexpr (EK == 6) {   // likewise, the NEXT pair's tile-A start values (xe) through the hidden-layer epilogue
+            other_piece<SP, 3, false>(s, accE, accE1, xe, o, hold, rng);
+            other_piece<SP, 5, false>(s, accE, accE1, xe, o, hold, rng);
         } else {
             other_piece<SP, EK, PACT>(s, accE, accE1, xe, o, hold, rng);
         }
@@ -607,12 +622,18 @@ constexpr int G4C_WS_SP1_MINW = 2;
 // TRACK (SP = 2): the fp16 range tracker (mlp_common.h RangeV) in the message loop and in the node phase; false for a launch whose
 // caller certifies that nothing it converts can reach the end of the range (Params::range_certified) — one v_max3_f32 per converted
 // pair and one register less, and the flag word is never written
-template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16 = false, bool NODE = false, bool DENSE = false, bool TRACK = true>
-__global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_kernel(const WsKernArgs ka) {
+// PRE (mlp_ws_pre_kernel below: f16x3 stream, fused aggregation, three layers, tracked): the FIRST LAYER IS PRECOMPUTED.  The launch has
+// no weighted block and no layer-0 weights; `x` is a third additive block T (rows direct, row = the launch's row: b1 + W1e e of an
+// MP layer whose e never changes inside a rollout), and a tile's start values (T + P_r[row]) + P_c[col] are the layer-0
+// pre-activation itself.  What the other forms park is here the hidden-layer epilogue of those start values (EK 5), a pair has four
+// matrix phases instead of six, and every row of the next pair is gathered under this pair's phases (none in the tail).
+template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16, bool NODE, bool DENSE, bool TRACK, bool PRE>
+__device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     const WsArgs &p = ka.a;
     const int n_pairs = ka.n_pairs;
     static_assert((SP == 1 || SP == 2) && (NL == 2 || NL == 3) && (SP == 1 || !XB16) && (SP == 1 || !AB16) && (ADDS || !AB16) &&
                   (!NODE || (AGG && SP == 2)) && (TRACK || SP == 2), "mlp_ws_kernel: unsupported instantiation");
+    static_assert(!PRE || (AGG && DIRECT && ADDS && SP == 2 && NL == 3 && !NODE && TRACK), "mlp_ws_pre_kernel: unsupported instantiation");
     // an additive row piece as loaded: four fp32 values, or four bf16 values in two dwords (widened where they are added)
     typedef typename std::conditional<AB16, u32x2, f32x4>::type AddV;
     __shared__ __attribute__((aligned(16))) __bf16 sP[2 * TILE_BF16];      // operand planes of tiles A, B (34 816 B)
@@ -797,12 +818,13 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
         store_tables(v0, 0);
         store_tables(v1, 1);
     }
+    // (PRE: the stream starts with layer 1 — W[0] is never loaded or read)
 #pragma unroll
-    for (int l = 0; l < NL; ++l)
+    for (int l = PRE ? 1 : 0; l < NL; ++l)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-            for (int pl = 0; pl < SP; ++pl) W[l][ks][pl] = ldw(rs, lo_b + 1024u * pl, (unsigned)l * 2u * BLOCK6 + (unsigned)ks * 4u * STEP6);
+            for (int pl = 0; pl < SP; ++pl) W[l][ks][pl] = ldw(rs, lo_b + 1024u * pl, (unsigned)(l - (PRE ? 1 : 0)) * 2u * BLOCK6 + (unsigned)ks * 4u * STEP6);
     if (tid < NL * NP) sBias[tid] = p.b[tid];
     if (tid < NP) sZero[tid] = 0.f;
     if (tid < 2 * NP) sGB[tid] = p.gamma ? (tid < NP ? p.gamma[tid] : p.beta[tid - NP]) : 0.f;
@@ -849,6 +871,24 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[rb][e] = (acc[rb][e] + a0[e]) + a1[e];
             }
+        }
+    };
+    // PRE: rows of T of tile t of a pair (accumulator layout, rows past the tile's end: clamped copies), and a tile's start values
+    // (T + P_r) + P_c — the layer-0 pre-activation (the bias is in T)
+    auto gather_t = [&](const Meta &m, int t, f32x4 (&tv)[2]) __attribute__((always_inline)) {
+        const int nn = m.n[t] > 0 ? m.n[t] : m.n[0];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            const int r = n + 16 * rb;
+            tv[rb] = *reinterpret_cast<const f32x4 *>(p.x + (long long)(m.r0[t] + (r < nn ? r : nn - 1)) * p.x_ld + fcol);
+        }
+    };
+    auto start_values_pre = [&](f32x4 (&sv)[2], const f32x4 (&tv)[2], const AddV (&a)[2][2]) __attribute__((always_inline)) {
+        if constexpr (PRE) {
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sv[rb][e] = (tv[rb][e] + a[rb][0][e]) + a[rb][1][e];
         }
     };
     // LayerNorm / activation / row stores of a finished pair (its fp32 rows in fA / fB; `mm` = that pair's rows)
@@ -1076,7 +1116,18 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     // added in and after the first matrix phase), accA = tile A's start values, tile A's rows in its planes.
     AddV adB[2][2];
     unsigned rawB[2][2] = {{0u, 0u}, {0u, 0u}};        // (XB16: tile B's bf16 rows as loaded)
-    {
+    if constexpr (PRE) {
+        // PRE, loop-carried: accB = the CURRENT pair's tile-B start values; tile A's are in its planes already (through the epilogue)
+        AddV adA[2][2];
+        f32x4 tA[2], tB[2], sA0[2];
+        gather_t(m0, 0, tA);
+        gather_t(m0, 1, tB);
+        gather_adds(0, 0, adA);
+        gather_adds(1, 0, adB);
+        start_values_pre(sA0, tA, adA);
+        other_all<SP, 5, false>(accA, accA1, sA0, oA, rng);
+        start_values_pre(accB, tB, adB);
+    } else {
         AddV adA[2][2];
         unsigned rawA[2][2] = {{0u, 0u}, {0u, 0u}};
         gather_x(m0, 0, 0, xr[0], rawA);
@@ -1090,6 +1141,59 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
     }
     __syncthreads();                                       // tile A's planes of the first pair visible
 
+    if constexpr (PRE) {
+        for (int it = 0, pair = p_begin; pair < p_end; ++pair, ++it) {
+            // ---- tables two pairs ahead, meta three pairs ahead (as below; the stamps of the instrumented build and the timing-only
+            // ablations of the two tails as well: stamps 5 / 6 — the phases this form does not have — stay unwritten)
+            WS_STAMP(0);
+            Meta m3raw;
+            if constexpr (!DENSE) m3raw = load_meta(pair + 3);
+            const int tv = load_tables(meta_at(pair + 2, m2));
+            // ---- the next pair's rows: T of its tile A here, its additive rows under M(B, 1), T of its tile B under M(A, 2), tile B's
+            // additive rows under M(B, 2) — 2, 4, 2, 4 loads per lane, each batch a phase or more ahead of its use
+            f32x4 ntA[2], ntB[2], nsA[2];
+            AddV nadA[2][2];
+            WS_STAMP(1);
+            bias_init(accA, accA1, 1);
+            gather_t(meta_at(pair + 1, m1), 0, ntA);
+            m_block<SP, 5>(paA, W[1], accA, accA1, accA, accA1, accB, oB, rng);                  // M(A, 1); for B: epilogue of its start values
+            bias_init(accB, accB1, 1);
+            __syncthreads();
+            WS_STAMP(2);
+            gather_adds(0, (it + 1) & 1, nadA);
+            m_block<SP, 1>(paB, W[1], accB, accB1, accA, accA1, ntA, oA, rng);                   // M(B, 1); for A: epilogue of layer 1
+            bias_init(accA, accA1, 2);
+            __syncthreads();
+            WS_STAMP(3);
+            gather_t(meta_at(pair + 1, m1), 1, ntB);
+            m_block<SP, 1>(paA, W[2], accA, accA1, accB, accB1, ntA, oB, rng);                   // M(A, 2); for B: epilogue of layer 1
+            bias_init(accB, accB1, 2);
+            __syncthreads();
+            WS_STAMP(4);
+            start_values_pre(nsA, ntA, nadA);
+            gather_adds(1, (it + 1) & 1, adB);
+            // for A: last layer's fp32 rows — and the NEXT pair's tile A through its layer-0 epilogue into A's planes (their last readers,
+            // M(A, 2), are behind the previous barrier)
+            m_block<SP, 6>(paB, W[2], accB, accB1, accA, accA1, nsA, oA, rng);                   // M(B, 2)
+            other_all<SP, 3, false>(accB, accB1, nsA, oB, rng);                                  // B's last layer -> fp32 rows
+            __syncthreads();
+            WS_STAMP(7);
+            // the next pair's tile-B start values, in front of the tail's stores (a wait behind them would wait for every store too)
+            start_values_pre(accB, ntB, adB);
+            asm volatile("" : "+v"(accB[0]), "+v"(accB[1]) :: "memory");
+            Meta m3;
+            if constexpr (!DENSE) m3 = fix_meta(m3raw);
+            store_tables(tv, it + 2);
+            WS_STAMP(8);
+            if (!(G4C_WS_ABLATE & 256)) ln_tail(meta_at(pair, m0), it);
+            WS_STAMP(9);
+            __syncthreads();
+            WS_STAMP(15);
+            if (!(G4C_WS_ABLATE & 128)) agg_tail(meta_at(pair, m0), it);
+            WS_STAMP(10);
+            if constexpr (!DENSE) { m0 = m1; m1 = m2; m2 = m3; }
+        }
+    } else
     for (int it = 0, pair = p_begin; pair < p_end; ++pair, ++it) {
         WS_STAMP(0);
         // ---- tables two pairs ahead (their meta was loaded an iteration ago), meta three pairs ahead
@@ -1204,7 +1308,22 @@ __global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_ker
 }
 
 
-#ifdef G4C_WS_ISA_ONLY
+template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16 = false, bool NODE = false, bool DENSE = false, bool TRACK = true>
+__global__ __launch_bounds__(512, SP == 1 ? G4C_WS_SP1_MINW : 2) void mlp_ws_kernel(const WsKernArgs ka) {
+    ws_body<AGG, DIRECT, ADDS, SP, NL, XB16, AB16, NODE, DENSE, TRACK, false>(ka);
+}
+// the "first layer precomputed" form (PRE above): what the MuS models' first MP layer reaches — f16x3 stream, fused aggregation, two
+// layers left of three, tracked; dense pairs or table-driven tiles
+template <bool DENSE>
+__global__ __launch_bounds__(512, 2) void mlp_ws_pre_kernel(const WsKernArgs ka) {
+    ws_body<true, true, true, 2, 3, false, false, false, DENSE, true, true>(ka);
+}
+
+#if defined(G4C_WS_ISA_ONLY) && G4C_WS_ISA_ONLY == 2
+// -DG4C_WS_ISA_ONLY=2 (tests/test_ws_pre_isa.py): nothing but the two instantiations of the "first layer precomputed" form
+template __global__ void mlp_ws_pre_kernel<true>(const WsKernArgs);
+template __global__ void mlp_ws_pre_kernel<false>(const WsKernArgs);
+#elif defined(G4C_WS_ISA_ONLY)
 // -DG4C_WS_ISA_ONLY (tests/test_ws_isa.py, with --cuda-device-only -S): nothing but the headline step's four instantiations — the level-1
 // message launch <.., DENSE> and the fused MP layer <.., NODE>, tracked and certified — for a look at their registers and instructions
 // in seconds instead of the minute the whole file takes
@@ -1233,8 +1352,44 @@ bool ws_takes(const Launch &L) {
     return true;
 }
 
+// The "first layer precomputed" form (Launch::pre, mlp_ws_pre_kernel): exactly what is instantiated — f16x3 stream, three layers of
+// which two are left, the fused aggregation, three aligned 128-wide fp32 additive blocks (T direct, the two products through indices),
+// plain fp32 128-wide output rows (or none).  Tracked: a certificate only nulls the flag pointer.
+bool ws_pre_takes(const Launch &L) {
+    const Params &p = L.p;
+    if (!L.f16x2 || !L.agg || L.save || L.has_node || p.n_layers != 3) return false;
+    if (p.n_src != 0 || p.n_nar != 0 || p.n_add != 3 || p.n_heads || p.n_out != NP || p.resid || p.out_idx || p.out_bf16) return false;
+    if (p.add[0].idx || !p.add[1].idx || !p.add[2].idx) return false;
+    for (int a = 0; a < 3; ++a)
+        if (p.add[a].width != NP || p.add[a].bf16 || (p.add[a].ld & 3) || ((uintptr_t)p.add[a].ptr & 15)) return false;
+    if (p.out && ((p.out_ld & 3) || ((uintptr_t)p.out & 15))) return false;
+    if (p.gamma && (((uintptr_t)p.gamma & 15) || ((uintptr_t)p.beta & 15))) return false;
+    return ((uintptr_t)p.b & 15) == 0 && p.M < (1LL << 31);
+}
+
 int ws_launch(const Launch &L, hipStream_t st, Ran &ran) {
     const Params &p = L.p;
+    if (L.pre) {
+        // T takes the weighted block's place in the argument block (rows direct), the products are the two additive blocks
+        const bool dense = p.agg_deg >= 4 && p.agg_deg <= 8;
+        const int n_pairs = dense ? (int)((p.M + 63) / 64) : (p.n_tiles + 1) / 2;
+        const int n_wg = g4c::cu_count();
+        const dim3 grid(n_pairs < n_wg ? n_pairs : n_wg), blk(512);
+        ran.kernel = G4C_KERNEL_MLP_WS_PRE;
+        WsArgs a{};
+        a.x = p.add[0].ptr; a.x_idx = nullptr; a.x_ld = p.add[0].ld; a.x_pact = 0;
+        for (int j = 0; j < 2; ++j) { a.add_ptr[j] = p.add[1 + j].ptr; a.add_idx[j] = p.add[1 + j].idx; a.add_ld[j] = p.add[1 + j].ld; }
+        a.w = p.w; a.b = p.b; a.gamma = p.gamma; a.beta = p.beta; a.eps = p.eps; a.act = p.act;
+        a.out = p.out; a.out_idx = nullptr; a.out_ld = p.out_ld; a.out_bf16 = 0;
+        a.tile_rows = p.tile_rows; a.tile_seg = p.tile_seg; a.seg_off = p.seg_off;
+        a.agg = p.agg; a.agg_ld = p.agg_ld; a.agg_mean = p.agg_mean; a.agg_deg = p.agg_deg;
+        a.M = (int)p.M; a.row_base = (int)p.row_base; a.n_tiles = p.n_tiles;
+        a.range_flag = p.range_certified ? nullptr : p.range_flag; a.range_slot = p.range_slot;
+        const WsKernArgs ka{a, n_pairs, L.node};
+        if (dense) mlp_ws_pre_kernel<true><<<grid, blk, 0, st>>>(ka);
+        else mlp_ws_pre_kernel<false><<<grid, blk, 0, st>>>(ka);
+        return g4c::check_launch("g4c_mlp_run (ws, first layer precomputed)");
+    }
     const bool agg = L.agg, round1 = L.round1, node = L.has_node;
     // (dense mode — uniform segments of 4 .. 8 rows — cuts the rows into pairs of 64 itself: n_pairs only sizes the grid there)
     // Not for the fused MP layer: its launches are a few pairs per workgroup (nothing to win from denser pairs), and its three-layer

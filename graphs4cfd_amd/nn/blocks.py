@@ -670,6 +670,51 @@ def _can_fuse_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e, edge_index: Tensor
     return int(v.size(1)) == 128 and int(e_t.size(1)) == 128 and e_t.dtype == torch.float32
 
 
+def static_first_layer(msg_mlp: MLP, upd_mlp: MLP, e_src: Source, e_static, edge_index: Tensor, n_nodes: int, csr, hoists: bool) -> bool:
+    """Whether an MP layer's message launch starts from its precomputed first layer (ops.mlp_forward_precomputed): the layer reads the
+    program's static edge latents (`e_static`: the tensors they were made from — the caller's statement that `e` is an entry of the
+    active ops.StaticCache, stored activated), a rollout's cache is active, the arithmetic is f16x3, the layer hoists (its node-side
+    products are additive rows), it is not a fused layer (one launch per MP layer has no such form) and the launch reduces its own
+    rows; the message MLP is 384 -> 128 -> 128 -> 128.  Everything else — a bare forward(), training, the other arithmetics,
+    G4C_STATIC_FIRST_LAYER=0 — keeps the launch it had."""
+    if not (ops.STATIC_FIRST_LAYER and e_static and ops.StaticCache.active is not None and not ops.grad_mode() and hoists):
+        return False
+    if ops.mlp_precision() != "f16x3" or ops.effective_precision([128]) != "f16x3":
+        return False
+    lm = msg_mlp._linears()
+    if len(lm) != 3 or any(l.out_features != 128 for l in lm) or msg_mlp.input_size != 384:
+        return False
+    if (e_src.pre_act != _lib.ACT_NONE or e_src.index is not None or e_src.col0 != 0 or e_src.negate or e_src.segments is not None
+            or e_src.additive or e_src.width != 128 or e_src.tensor.dtype != torch.float32):
+        return False
+    if will_fuse_layer(msg_mlp, upd_mlp, edge_index, n_nodes):
+        return False
+    return ops.can_fuse_aggregation(csr, msg_mlp.output_size)
+
+
+def _static_first_message(msg_mlp: MLP, e_src: Source, e_static, gathered, n_rows: int, products, gathered_bounds, product_bounds,
+                          agg, store_rows: bool) -> Optional[Tensor]:
+    """The message launch of `static_first_layer`: T = b1 + W1e e once per rollout (an entry of the StaticCache beside e itself, under
+    the same key: one launch of the first layer alone on its e block, no activation, no LayerNorm, range-tracked like every launch of
+    this MLP), the node-side products as MLP.run_hoisted makes or receives them, then the two layers left."""
+    H = 128
+    first = ops.static_launch(STATIC_FIRST_NAME, list(e_static), lambda: ops.mlp_forward(
+        msg_mlp._image(msg_mlp._spec([H], [False], layers=(0, 1), cols=(0, H), bias=True)), [Source(e_src.tensor, bound=e_src.bound)], n_rows))
+    adds = []
+    for j, (t, idx) in enumerate(gathered):
+        if products is not None:
+            part, part_bound = products[j], (product_bounds[j] if product_bounds is not None else None)
+        else:
+            part = ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True),
+                                   [Source(t, bound=gathered_bounds[j])], int(t.size(0)))
+            part_bound = ops.take_bounds().out
+        adds.append(Source(part, index=idx, additive=True, bound=part_bound))
+    return ops.mlp_forward_precomputed(msg_mlp._packed_cols(0, H, [H], [False], False), first, adds, n_rows, agg, store_rows=store_rows)
+
+
+STATIC_FIRST_NAME = "first_mp_layer.edge_product"          # the StaticCache entry of T
+
+
 def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, mean: bool, act_code: int, products,
                  next_msg: Optional[MLP], keep_e: bool, rb: ops.RangeBounds):
     """The MP layer as one launch.  Returns (v', e' or None, next products or None); `rb`: the bounds of v / the products in, of
@@ -705,7 +750,7 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
              products: Optional[Sequence[Tensor]] = None, next_msg: Optional[MLP] = None, keep_e: bool = True,
              n_targets: Optional[int] = None, v_out: Optional[Tensor] = None, compact_messages: bool = False,
              next_graph: Optional[Tuple[int, "plan.CsrPlan"]] = None, compact_v: bool = False,
-             bounds: Optional[ops.RangeBounds] = None):
+             bounds: Optional[ops.RangeBounds] = None, e_static: Optional[Sequence[Tensor]] = None):
     """Shared body of GNBlock / EdgeMP / DownEdgeMP (nn/blocks.py:175-186,322-333,360-381):
         e' = msg_mlp([e | s[row] | v[col]]);  agg = reduce(e' -> col);  v' = act(upd_mlp([agg | v])).
     Returns (v', e') where e' is stored WITHOUT the activation: the aggregation consumes the raw
@@ -728,6 +773,8 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
     `bounds` (ops.RangeBounds; the fp16 range proof of the f16x3 launches): in — what the caller has proven about |v|, |e| as stored and
     |products|; out — the same for v', e' and the next layer's products.  The caller owns it and passes it from block to block beside
     the tensors; without one (a user's tensors) nothing is known and every launch is range-tracked.
+    `e_static` (the model program's first MP layer): `e` is the rollout's static edge latents, made from these tensors (the key of its
+    ops.StaticCache entry) — the message launch may then start from its precomputed first layer (static_first_layer).
     `n_targets` / `v_out` (partitioned sub-meshes, partition_remus.py): only the first `n_targets` rows of `v` are targets (the
     rows behind them are halo rows, read as senders only); v' for those rows is written into `v_out`."""
     if aggr not in ("mean", "sum", "add"):
@@ -746,7 +793,16 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
     # (the gathered node rows: senders, receivers; the products the caller handed in)
     hoist_kw = dict(gathered_bounds=[rb.v if v_src is None else None, rb.v], product_bounds=rb.products)
     v_in = Source(v, bound=rb.v)
-    if ops.can_fuse_aggregation(csr, msg_mlp.output_size):
+    static_first = (e_static is not None and v_src is None and n_targets is None and v_out is None and not compact_messages
+                    and static_first_layer(msg_mlp, upd_mlp, e_src, e_static, index, int(v.size(0)), csr,
+                                           ep.n_edges >= HOIST_MIN_ROWS or products is not None))
+    if static_first:
+        agg = torch.empty((csr.n_seg, 128), dtype=torch.float32, device=v.device)
+        e_new = _static_first_message(msg_mlp, e_src, e_static, [(senders, ep.row), (v, ep.col)], ep.n_edges, products,
+                                      hoist_kw["gathered_bounds"], hoist_kw["product_bounds"], (csr, agg, mean), keep_e)
+        rb.e = ops.take_bounds().out
+        agg_src = Source(agg, bound=ops.agg_bound(rb.e, csr, mean))
+    elif ops.can_fuse_aggregation(csr, msg_mlp.output_size):
         # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_io_t.agg):
         # no second pass over the messages; with keep_e=False (the model discards e', nn/mus_gnn.py:199-200) they are not
         # even written
@@ -854,11 +910,12 @@ class GNBlock(nn.Module):
 
     def step(self, v: Tensor, e: Tensor, edge_index: Tensor, act_code: int, e_pre_act: int = _lib.ACT_NONE,
              products: Optional[Sequence[Tensor]] = None, next_msg: Optional[MLP] = None, keep_e: bool = True,
-             bounds: Optional[ops.RangeBounds] = None):
+             bounds: Optional[ops.RangeBounds] = None, e_static: Optional[Sequence[Tensor]] = None):
         """Internal form used by the model programs: returns (act(v'), raw e') — and, when `next_msg` (the edge MLP of
-        the next MP layer on the same graph) is given, a third value: that layer's `products` or None (see _mp_step; `bounds` too)."""
+        the next MP layer on the same graph) is given, a third value: that layer's `products` or None (see _mp_step; `bounds`,
+        `e_static` too)."""
         return _mp_step(self.edge_mlp, self.node_mlp, v, e, edge_index, self.aggr, act_code, e_pre_act,
-                        products=products, next_msg=next_msg, keep_e=keep_e, bounds=bounds)
+                        products=products, next_msg=next_msg, keep_e=keep_e, bounds=bounds, e_static=e_static)
 
     def forward(self, v: Tensor, e: Tensor, edge_index: Tensor, *, activation=None) -> Tuple[Tensor, Tensor]:
         return _public_mp(self.edge_mlp, self.node_mlp, v, e, edge_index, self.aggr, activation)

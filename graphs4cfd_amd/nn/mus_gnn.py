@@ -106,14 +106,18 @@ class _MuSGNN(GNN):
                 rb.v, rb.products = lb.out, (lb.heads if products is not None else None)
             else:
                 nxt = prog[k + 1] if k + 1 < len(prog) else ""
+                # (the program's first layer reads the static edge latents themselves: inside a rollout its first layer's product with
+                # them is as static as they are — blocks.static_first_layer)
+                e_static = [graph.edge_attr] if k == 0 else None
                 if nxt.startswith("mp"):      # next MP layer runs on the same graph: its node-side products ride along
                     v, e, products = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products,
-                                                next_msg=getattr(self, nxt).edge_mlp, bounds=rb)
+                                                next_msg=getattr(self, nxt).edge_mlp, bounds=rb, e_static=e_static)
                 else:
                     # the level's edge latents are dropped after this layer when an UpMP or the decoder follows (the up leg
                     # restores the latents stashed before the DownMP): they then need not be stored
                     drop_e = nxt.startswith("up_mp") or nxt == ""
-                    v, e = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products, keep_e=not drop_e, bounds=rb)
+                    v, e = block.step(v, e, edge_index, SELU, e_pre_act=e_pending, products=products, keep_e=not drop_e, bounds=rb,
+                                      e_static=e_static)
                     products = None
                 e_pending = SELU
         nf = self.num_fields

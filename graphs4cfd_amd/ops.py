@@ -62,7 +62,9 @@ def _timed(kind: str, flops: float, nbytes: float, fn):
 class StaticCache:
     """Results of launches whose inputs cannot change between the steps of one rollout (reference: nn/model.py:316-320 — `solve`
     only ever replaces `graph.field`): `selu(edge_encoder(edge_attr))` of the MuS-GNN models (nn/mus_gnn.py:73,178 of the reference)
-    and REMuS-GNN's five angle encoders (nn/remus_gnn.py:136-140).  A `Rollout` / `DistributedRollout` activates its cache around
+    and REMuS-GNN's five angle encoders (nn/remus_gnn.py:136-140), and — an entry of its own beside the edge latents — the product
+    `b1 + W1e e0` of the first MP layer's first edge-MLP layer with them (nn/blocks.py static_first_layer: that layer's message launch
+    then starts from it, mlp_forward_precomputed).  A `Rollout` / `DistributedRollout` activates its cache around
     every step; the first (eager) step fills it, the captured step finds the entries and therefore contains neither the launches
     nor the tensors in its write set.  A bare `model.forward()` has no active cache and recomputes, like the reference.
 
@@ -78,6 +80,12 @@ class StaticCache:
 
     def __enter__(self):
         self._prev, StaticCache.active = StaticCache.active, self
+        # entries of another arithmetic go: what the step still uses is computed again under the current one (a miss either way), and
+        # an entry the step no longer asks for — the first MP layer's product after a rollout has fallen back to bf16x6 — would
+        # otherwise read as stale before every step, and the step would never be captured again
+        prec = mlp_precision()
+        for name in [n for n, hit in self.store.items() if hit[0][1] != prec]:
+            del self.store[name]
         return self
 
     def __exit__(self, *exc):
@@ -1218,6 +1226,55 @@ def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr
         msg.desc.range_certified = upd.desc.range_certified = 0          # (the certificates were for this launch: the descriptors are shared)
     _last_bounds = LaunchBounds(None, lb_upd.out, lb_upd.heads, e=lb_msg.out)
     return e_out, v_out, head_outs
+
+
+# The first MP layer of a MuS model multiplies the same edge latents e0 (StaticCache) by the same W1e in every step of a rollout: with
+# this on, a `Rollout` computes T = b1 + W1e e0 once and the layer's message launch starts from it (mlp_forward_precomputed).
+# G4C_STATIC_FIRST_LAYER=0: today's launch, bit for bit (A/B runs).
+STATIC_FIRST_LAYER = os.environ.get("G4C_STATIC_FIRST_LAYER", "1") != "0"
+
+
+def mlp_forward_precomputed(packed: PackedMLP, first: Tensor, products: Sequence[Source], n_rows: int,
+                            agg: Tuple[CsrPlan, Tensor, bool], act: int = _lib.ACT_NONE, store_rows: bool = True) -> Optional[Tensor]:
+    """The hoisted message launch of `packed` (one 128-wide weighted block, three 128-wide layers, f16x3) WITHOUT its first layer
+    (g4c_mlp_t.k_pad[0] == 0): `first` [n_rows, 128] = b1 + W1x x, computed before, and the two gathered node-side `products`
+    (additive Sources with an index) sum to the layer-0 pre-activation, (first + p0[i0]) + p1[i1]; the launch runs the two layers
+    left, LayerNorm, `act`, the row stores (`store_rows`) and the fused aggregation `agg` = (csr, out [n_seg, 128], mean), bit-identical
+    to segment_reduce of the rows.  Inference only; always range-tracked; a shape the library has not built raises
+    NotImplementedError.  take_bounds() then answers for the output rows."""
+    global _last_bounds
+    _last_bounds = None
+    csr, agg_out, agg_mean = agg
+    dev = _lib.require_hip(first, agg_out, *[s.tensor for s in products], *[s.index for s in products])
+    if dev != packed.device:
+        raise RuntimeError(f"MLP weights on {packed.device}, inputs on {dev}")
+    if packed.split != "f16x2" or packed.desc.n_layers != 3 or packed.seg_widths != (128,) or packed.n_out != 128 or packed.n_heads:
+        raise NotImplementedError("mlp_forward_precomputed: a three-layer 128-wide MLP over one 128-wide block, packed for f16x3, no heads")
+    if len(products) != 2 or any(not s.additive or s.index is None or s.width != 128 or s.tensor.dtype != torch.float32 for s in products):
+        raise ValueError("mlp_forward_precomputed: two additive 128-wide fp32 sources gathered through an index")
+    first = _rows_f32(first, "first", cols=128, min_rows=n_rows)
+    if csr.tiles() is None or n_rows != csr.n:
+        raise ValueError("mlp_forward_precomputed: the rows must be in segment order with segments of at most 32 rows")
+    if agg_out.dtype != torch.float32:
+        raise TypeError(f"aggregate: expected float32, got {agg_out.dtype}")
+    out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev) if store_rows else None
+    # the launch's descriptor: the image's own with layer 0 taken out of the stream (the bias block keeps layer 0's unused slot)
+    desc = _lib.g4c_mlp_t()
+    C.memmove(C.byref(desc), C.byref(packed.desc), C.sizeof(desc))
+    desc.k_pad[0], desc.w[0], desc.range_certified = 0, packed.desc.w[1], 0
+    srcs = [Source(first, additive=True)] + list(products)
+    io = _lib.g4c_mlp_io_t(act=act, row_count=n_rows, out=_lib.ptr(out), out_ld=128 if out is None else _ld(out))
+    _set_agg(io, csr, agg_out, agg_mean)
+    io.range_flag = _launch_flags(dev).data_ptr()
+    flops = float(2 * 2 * 128 * 128) * n_rows
+    nbytes = 4.0 * 128 * (n_rows * (2 if store_rows else 1) + csr.n_seg)
+    arr = _src_array(srcs)
+    _timed("mlp_bx6_kernel", flops, nbytes, lambda: _lib.check(_lib.load().g4c_mlp_run(C.byref(desc), arr, 3, n_rows, C.byref(io),
+                                                                                       _lib.stream_handle(dev))))
+    # (behind a LayerNorm the rows are bounded whatever went in: the bound the unhoisted launch's proof gives them)
+    ln = packed.norms["ln"] if packed.norms is not None else None
+    _last_bounds = LaunchBounds(None, act_bound((packed.norms["n_out"] - 1) ** 0.5 * ln[0] + ln[1], act) if ln is not None else None)
+    return out
 
 
 def _rows_dtype(what: str, tensors: Sequence[Tensor]) -> int:

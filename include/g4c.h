@@ -148,7 +148,16 @@ typedef struct {
 
 typedef struct {
     int32_t n_layers;                /* number of Linear layers, 1..G4C_MAX_LAYERS */
-    int32_t k_pad[G4C_MAX_LAYERS];   /* padded input width of each layer (see g4c_mlp_pack_layer) */
+    int32_t k_pad[G4C_MAX_LAYERS];   /* padded input width of each layer (see g4c_mlp_pack_layer).  k_pad[0] == 0 (w[0] == w[1]: the
+                                        stream starts with layer 1): no block of layer 0 goes through the stream — its blocks are all
+                                        narrow, or, in a call whose sources are ALL ADDITIVE, THE FIRST LAYER IS PRECOMPUTED: b[0] keeps
+                                        its unused slot and the additive sources sum to the layer-0 pre-activation, bias included: rows of layer 0's output = (src0 + src1) + src2
+                                        in fp32, in this order.  Built for one shape (anything else: G4C_EUNSUPPORTED): G4C_WFMT_F16X2,
+                                        three layers, the fused aggregation, three 128-wide 16-byte aligned fp32 additive sources of
+                                        which the first is direct (idx NULL: the static product of an MP layer's first layer with its
+                                        edge block, computed once per rollout) and the other two are gathered, plain fp32 128-wide
+                                        output rows or none, no heads / residual / out_idx / out_dtype / save / upd.  Always
+                                        range-tracked. */
     int32_t n_pad[G4C_MAX_LAYERS];   /* padded output width: 128 */
     const float *w[G4C_MAX_LAYERS];  /* packed weights of each layer: one contiguous stream, layer after layer */
     const float *b[G4C_MAX_LAYERS];  /* bias padded with zeros to n_pad, layer after layer */
@@ -350,6 +359,7 @@ int g4c_mlp_small_launch_tiles(int n_tiles);
 #define G4C_KERNEL_MLP_RS2 6
 #define G4C_KERNEL_MLP_BX6_CERT 7
 #define G4C_KERNEL_MLP_WS_CERT 8
+#define G4C_KERNEL_MLP_WS_PRE 9   /* mlp_ws_pre_kernel: the weight-stationary kernel's "first layer precomputed" form (g4c_mlp_t.k_pad[0] == 0) */
 int g4c_mlp_last_kernel(void);
 
 /* Compile-time launch shapes of the tile kernel (mlp_bx6_kernel): a launch of G4C_WFMT_F16X2 whose every field matches a shape runs an
