@@ -25,26 +25,50 @@ from .graph import Graph
 
 # ------------------------------------------------------------------------------ connectivity
 def knn_neighbours(points: np.ndarray, queries: np.ndarray, k: int) -> np.ndarray:
-    """Indices [len(queries), k] of the k nearest `points` of every query, by ascending distance."""
+    """Indices [len(queries), k] of the k nearest `points` of every query, by ascending distance (k-d tree on the host, float64
+    coordinates as given).  Among exactly equal distances the order, and which of them is kept at the k-th place, is the tree's."""
+    points, queries = np.asarray(points), np.asarray(queries)
+    if points.ndim != 2 or queries.ndim != 2 or points.shape[1] != queries.shape[1]:
+        raise ValueError(f"knn_neighbours: points {points.shape} and queries {queries.shape} must be [n, dim] and [m, dim]")
+    if not 1 <= k <= points.shape[0]:
+        raise ValueError(f"knn_neighbours: k={k} neighbours of n={points.shape[0]} points")
+    if not (np.isfinite(points).all() and np.isfinite(queries).all()):
+        raise ValueError("knn_neighbours: non-finite coordinate")
     _, nbr = cKDTree(points).query(queries, k=k)
     return np.asarray(nbr).reshape(len(queries), k)
 
 
-def _bin_cloud(pos: torch.Tensor, k: int) -> dict:
-    """Uniform cell grid over a device point cloud for `g4c_knn_grid[_query]`: cells of ~2k/pi (2-D) or ~2k/4.2 (3-D)
-    points, so that one ring of cells almost always holds the k neighbours; cell coordinates in fp64 so that a point lies
-    geometrically inside its cell; points stable-sorted by cell id."""
-    import ctypes as C
-    from . import _lib
-    dev = _lib.require_hip(pos)
-    n, dim = int(pos.size(0)), int(pos.size(1))
-    p32 = pos.detach().float().contiguous()
-    lo, hi = p32.min(0)[0].cpu(), p32.max(0)[0].cpu()
+def _grid_shape(lo: torch.Tensor, hi: torch.Tensor, n: int, k: int, who: str = "g4c_knn_grid") -> Tuple[float, List[int]]:
+    """(cell size, cells per axis padded to 3) of the search grid over a cloud of n points with corners lo / hi (host tensors
+    holding float32 values): cells of ~2k/pi (2-D) or ~2k/4.2 (3-D) points; an axis without extent gets one cell and does
+    not enter the cell size."""
+    dim = int(lo.numel())
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(hi).all())):
+        raise ValueError(f"{who}: non-finite coordinate in the point cloud")
     ext = (hi.double() - lo.double())
     live = ext[ext > 0]
     per_cell = 2.0 * k / (np.pi if dim == 2 else 4.0 * np.pi / 3.0)
     h = float(np.float32((float(live.prod()) * per_cell / n) ** (1.0 / live.numel()))) if live.numel() else 1.0
-    n_cells = [int(np.floor(float(e) / h)) + 1 for e in ext] + [1] * (3 - dim)
+    if not (np.isfinite(h) and h > 0.0):
+        raise ValueError(f"{who}: the cloud's extent {[float(e) for e in ext]} gives no usable cell size")
+    return h, [int(np.floor(float(e) / h)) + 1 for e in ext] + [1] * (3 - dim)
+
+
+def _bin_cloud(pos: torch.Tensor, k: int, who: str = "g4c_knn_grid") -> dict:
+    """Uniform cell grid over a device point cloud for `g4c_knn_grid[_query]` (`_grid_shape`: one ring of cells almost always
+    holds the k neighbours); cell coordinates in fp64 so that a point lies geometrically inside its cell; points
+    stable-sorted by cell id.  The cloud is searched as float32: `pos` is rounded once, here."""
+    import ctypes as C
+    from . import _lib
+    dev = _lib.require_hip(pos)
+    if pos.dim() != 2 or int(pos.size(1)) not in (2, 3):
+        raise ValueError(f"{who}: points of shape {tuple(pos.shape)}, must be [n, 2] or [n, 3]")
+    n, dim = int(pos.size(0)), int(pos.size(1))
+    if n < 1:
+        raise ValueError(f"{who}: n=0, an empty point cloud")
+    p32 = pos.detach().float().contiguous()
+    lo, hi = p32.min(0)[0].cpu(), p32.max(0)[0].cpu()
+    h, n_cells = _grid_shape(lo, hi, n, k, who)         # (raises on a non-finite corner: no synchronisation besides this copy)
     grid = dict(dev=dev, n=n, dim=dim, h=h, n_cells=n_cells, lo=lo.double().to(dev),
                 nc=(C.c_int32 * 3)(*n_cells), org=(C.c_float * 3)(*([float(v) for v in lo] + [0.0] * (3 - dim))))
     cell_sorted, order = torch.sort(_cell_ids(p32, grid), stable=True)
@@ -64,39 +88,56 @@ def _cell_ids(p32: torch.Tensor, grid: dict) -> torch.Tensor:
     return cell
 
 
-def knn_neighbours_device(pos: torch.Tensor, k: int) -> torch.Tensor:
+def _knn_out(out: Optional[torch.Tensor], rows: int, k: int, dev, who: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty((rows, k), dtype=torch.long, device=dev)
+    if out.dtype != torch.long or tuple(out.shape) != (rows, k) or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous int64 [{rows}, {k}] tensor on {dev}")
+    return out
+
+
+def knn_neighbours_device(pos: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[n, k] int64 indices of the k nearest OTHER points of every point of `pos` (a device tensor), nearest first:
-    the k-d-tree query of `connect_knn` as an exact cell-grid search on the GPU (`g4c_knn_grid`, csrc/knn_grid.hip)."""
+    the k-d-tree query of `connect_knn` as an exact cell-grid search on the GPU (`g4c_knn_grid`, csrc/knn_grid.hip).
+    The cloud searched is the float32 rounding of `pos`; distances are float64 sums over those coordinates.  The rows are
+    the host path's (`knn_neighbours` on the same float32 cloud) whenever no two candidate distances of a centre are
+    exactly equal; among equal distances both are correct k-nearest sets, and the order among them and which are kept at
+    the k-th distance follow the cell-sorted order here, the k-d tree's on the host.  `out`: written in place if given."""
     import ctypes as C
     from . import _lib
     lib = _lib.load()
-    g = _bin_cloud(pos, k)
-    out = torch.empty((g["n"], k), dtype=torch.long, device=g["dev"])
+    g = _bin_cloud(pos, k, "knn_neighbours_device (g4c_knn_grid)")
+    out = _knn_out(out, g["n"], k, g["dev"], "knn_neighbours_device (g4c_knn_grid)")
     _lib.check(lib.g4c_knn_grid(_lib.ptr(g["pos_sorted"]), _lib.ptr(g["cell_sorted"]), _lib.ptr(g["order"]),
                                 _lib.ptr(g["cell_start"]), g["n"], g["dim"], g["nc"], g["org"], C.c_float(g["h"]), k,
                                 _lib.ptr(out), _lib.stream_handle(g["dev"])))
     return out
 
 
-def knn_query_device(points: torch.Tensor, queries: torch.Tensor, k: int) -> torch.Tensor:
+def knn_query_device(points: torch.Tensor, queries: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[len(queries), k] int64 indices of the k nearest `points` of every query (device tensors), nearest first
-    (`g4c_knn_grid_query`): `knn_neighbours` on the GPU."""
+    (`g4c_knn_grid_query`): `knn_neighbours` on the GPU, over the float32 roundings of both clouds, with the tie rule of
+    `knn_neighbours_device`.  Queries may lie anywhere, outside the cloud's box included; only the cloud's corners are
+    tested for finiteness (the queries' are never brought to the host: finite queries are the caller's to provide).  `out`: written in place if given."""
     import ctypes as C
     from . import _lib
     lib = _lib.load()
-    g = _bin_cloud(points, k)
+    who = "knn_query_device (g4c_knn_grid_query)"
+    if points.dim() != 2 or queries.dim() != 2 or int(queries.size(1)) != int(points.size(1)):
+        raise ValueError(f"{who}: points {tuple(points.shape)} and queries {tuple(queries.shape)} must be [n, dim] and [m, dim]")
+    g = _bin_cloud(points, k, who)
     q32 = queries.detach().float().contiguous()
     _lib.require_hip(g["pos_sorted"], q32)
     q_cell = _cell_ids(q32, g).int()
     m = int(q32.size(0))
-    out = torch.empty((m, k), dtype=torch.long, device=g["dev"])
+    out = _knn_out(out, m, k, g["dev"], who)
     _lib.check(lib.g4c_knn_grid_query(_lib.ptr(g["pos_sorted"]), _lib.ptr(g["order"]), _lib.ptr(g["cell_start"]), g["n"],
                                       g["dim"], g["nc"], g["org"], C.c_float(g["h"]), _lib.ptr(q32), _lib.ptr(q_cell), m, k,
                                       _lib.ptr(out), _lib.stream_handle(g["dev"])))
     return out
 
 
-def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per, why: Optional[list] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
     """connect_knn for device positions with any set of periodic axes.  The reference ranks neighbours by the Euclidean distance
     between the points' embeddings (a periodic axis -> (cos, sin)(2 pi x / period) on the UNIT circle, transforms/connect.py:38-56: such
     an axis counts in radians).  In the coordinates y = (2 pi x / period for a periodic axis, x otherwise) the chord of a periodic axis
@@ -105,21 +146,35 @@ def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per) -> Optional[Tup
     margin of every periodic face are repeated 2 pi away (ghosts, corners included).  The margin is checked per centre after the
     search (its candidates' radius must stay inside the ghosted region) and grown if needed; the candidates are then ordered by their
     float64 embedded distances (stably) and the host path's rule — drop the centre itself, or the farthest hit when coincident points
-    pushed it out — leaves k per centre.  None: the cloud is too small for ghosts (a margin would reach half a period) or k too
-    large for the grid search; the host path takes it."""
+    pushed it out — leaves k per centre.  The candidates come from the float32 rounding of y; the float64 positions as given
+    order them.  None: the host path takes the cloud, and `why` (a list, if given) receives the reason, one of
+      "few points"     at most kc + 1 points, or k > 13 (kc + 1 = 16 candidates, the most the grid search returns, are fewer than k + 3);
+      "extent"         a period that is not positive, or shorter than the cloud's extent along its axis;
+      "margin"         the ghost margin would reach half a period (small or strongly graded clouds);
+      "own image"      a point and its own ghost among one centre's candidates;
+      "completeness"   the (k + 1)-th embedded distance is not provably inside the candidates' radius.
+    (The margin grows at most once: ghosts are only added, so the candidates' radius r cannot grow, the new need is at most the old
+    one and the new margin is 1.25 times the old need; the loop's bound of four attempts is never reached.)"""
+    def give_up(reason):
+        if why is not None:
+            why.append(reason)
+        return None
     dim, n, dev = int(pos.size(1)), int(pos.size(0)), pos.device
     kc = min(2 * k + 4, 15)          # (candidates per centre besides itself; the grid search returns at most 16)
     if n <= kc + 1 or kc < k + 2:
-        return None
+        return give_up("few points")
     x = pos.detach().double()
     lo, hi = x.min(0).values, x.max(0).values
+    extent = (hi - lo).cpu()
+    if not bool(torch.isfinite(extent).all()):
+        raise ValueError("connect_knn: non-finite coordinate in pos")
     lengths = []
     for ax in range(dim):
         d = per[ax]
-        lengths.append(None if d is None else (float(hi[ax] - lo[ax]) if isinstance(d, str) and d == "auto" else float(d)))
+        lengths.append(None if d is None else (float(extent[ax]) if isinstance(d, str) and d == "auto" else float(d)))
     pax = [ax for ax in range(dim) if lengths[ax] is not None]
-    if any(lengths[ax] <= 0.0 or float(hi[ax] - lo[ax]) > lengths[ax] * (1 + 1e-12) for ax in pax):
-        return None
+    if any(not lengths[ax] > 0.0 or float(extent[ax]) > lengths[ax] * (1 + 1e-12) for ax in pax):
+        return give_up("extent")
     two_pi = 2 * np.pi
     y, emb_cols = x.clone(), []
     for ax in range(dim):
@@ -137,7 +192,7 @@ def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per) -> Optional[Tup
     ids = torch.arange(n, device=dev)
     for _attempt in range(4):
         if margin >= 0.5 * two_pi:
-            return None
+            return give_up("margin")
         pts, src = y, ids
         for ax in pax:          # (one axis after the other over the growing set: the corners get their combinations)
             low, high = pts[:, ax] < margin, pts[:, ax] > two_pi - margin
@@ -152,13 +207,15 @@ def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per) -> Optional[Tup
             room = torch.minimum(room, torch.minimum(y[:, ax], two_pi - y[:, ax]))
         need = float((r * (1 + 1e-6) - room).max())
         if need <= margin:
+            if why is not None and _attempt > 0:
+                why.append("margin grown")                                                 # (not a reason to give up: for the tests)
             break
         margin = 1.25 * need
     else:
-        return None
+        return give_up("attempts")                                                         # (unreachable: docstring)
     cand = src[cand_aug]                                                                   # original point numbers
     if bool((torch.sort(cand, dim=1).values.diff(dim=1) == 0).any()):                     # a point AND its own periodic image among one
-        return None                                                                        # centre's candidates (tiny clouds): host path
+        return give_up("own image")                                                        # centre's candidates (tiny clouds): host path
     d2 = ((emb[cand] - emb[:, None, :]) ** 2).sum(-1)
     d2s, order = torch.sort(d2, dim=1, stable=True)
     # Completeness: the candidates are the kc + 1 nearest in the WRAPPED angle metric y, the reference orders by the
@@ -167,7 +224,7 @@ def _connect_knn_periodic_device(pos: torch.Tensor, k: int, per) -> Optional[Tup
     # y-radius; otherwise a true neighbour may be missing: host path.
     dk = d2s[:, k].clamp(min=0).sqrt()
     if bool((dk >= 2.0).any()) or bool((2.0 * torch.asin((dk * 0.5).clamp(max=1.0)) * (1 + 1e-9) > r).any()):
-        return None
+        return give_up("completeness")
     order = order[:, :k + 1]
     nbr = torch.gather(cand, 1, order)
     is_self = nbr == ids[:, None]
@@ -187,15 +244,27 @@ def connect_knn(pos: torch.Tensor, k: int, period=None) -> Tuple[torch.Tensor, t
     """`connect_knn` (transforms/connect.py:9-72): edges neighbour -> centre, grouped by centre, k per centre, nearest
     first; edge_attr = pos[col] - pos[row].  `period`: one entry per axis — None (not periodic), a length, or "auto" (the
     extent of the point cloud along that axis).  A periodic axis enters the neighbour search as a point on a circle,
-    (cos, sin)(2 pi x / period) (:38-56), and its edge components are wrapped into [-period/2, period/2] (:62-71)."""
+    (cos, sin)(2 pi x / period) (:38-56), and its edge components are wrapped into [-period/2, period/2] (:62-71).
+
+    Host and device.  With `pos` on the GPU the search runs there (`g4c_knn_grid`).  The device result equals the host path's
+    whenever no two candidate distances of a centre are exactly equal.  With exact ties (lattices, duplicated points) both are
+    correct k-nearest sets; the order among tied neighbours and the choice at the k-th tier are path-specific: cell-sorted
+    order on the device, the k-d tree's on the host.  The device paths search the float32 rounding of the positions (of the
+    embedding, for a periodic axis: float32 candidates, re-ranked by the float64 embedding); the host path searches `pos` as
+    given, in float64.  One periodic axis of a 2-D cloud takes 2k + 2 candidates from the grid search, which returns at most 16:
+    k <= 7 on the device.  ValueError: a dimension other than 2 or 3, n <= k, a non-finite coordinate."""
+    if pos.dim() != 2 or int(pos.size(1)) not in (2, 3):
+        raise ValueError(f"connect_knn: invalid dimension, pos of shape {tuple(pos.shape)} must be [n, 2] or [n, 3]")
     dim = int(pos.size(1))
-    if dim not in (2, 3):
-        raise ValueError(f"Invalid dimension: {dim}, must be 2 or 3.")
     per = [None] * dim if (period is None or all(d is None for d in period)) else list(period)
     if len(per) != dim:
-        raise ValueError(f"period needs {dim} entries")
+        raise ValueError(f"connect_knn: period needs {dim} entries")
+    if k < 1 or int(pos.size(0)) <= k:
+        raise ValueError(f"connect_knn: n={int(pos.size(0))} points, needs more than k={k} (and k >= 1)")
+    if not pos.is_cuda and not bool(torch.isfinite(pos).all()):
+        raise ValueError("connect_knn: non-finite coordinate in pos")
     if pos.is_cuda and all(d is None for d in per):
-        # positions resident on the GPU, no periodic axis: the search runs there (the result is the host path's)
+        # positions resident on the GPU, no periodic axis: the search runs there (the host path's result unless distances tie)
         n = int(pos.size(0))
         row = knn_neighbours_device(pos, k).reshape(-1)
         col = torch.arange(n, device=pos.device).repeat_interleave(k)
@@ -210,6 +279,8 @@ def connect_knn(pos: torch.Tensor, k: int, period=None) -> Tuple[torch.Tensor, t
         ax = 0 if per[0] is not None else 1
         x = pos[:, ax].detach().double()
         d = float(x.max() - x.min()) if isinstance(per[ax], str) and per[ax] == "auto" else float(per[ax])
+        if not (np.isfinite(d) and d > 0.0):
+            raise ValueError(f"connect_knn: period {d} of axis {ax} (a non-finite coordinate, or no extent for \"auto\")")
         circ = torch.stack((torch.cos(2 * np.pi / d * x), torch.sin(2 * np.pi / d * x)), 1)
         other = pos[:, 1 - ax].detach().double().unsqueeze(1)
         emb = torch.cat((circ, other), 1) if ax == 0 else torch.cat((other, circ), 1)          # (the reference's column order: x part, y part)
@@ -253,7 +324,8 @@ def connect_knn(pos: torch.Tensor, k: int, period=None) -> Tuple[torch.Tensor, t
     centre = np.repeat(np.arange(n), k + 1).reshape(n, k + 1)
     row = torch.from_numpy(nbr[keep].astype(np.int64))
     col = torch.from_numpy(centre[keep].astype(np.int64))
-    edge_index = torch.stack([row, col], 0)
+    edge_index = torch.stack([row, col], 0).to(pos.device)       # (device positions the periodic search handed over: the edges go back)
+    row, col = edge_index
     edge_attr = pos[col] - pos[row]
     for ax, d in enumerate(lengths):
         if d is not None:
@@ -323,7 +395,8 @@ def mus_graph(n: int, levels: int = 1, k: int = 6, dim: int = 2, nf: int = 3, n_
               r: Optional[float] = None, cells: Optional[Sequence[float]] = None, loc: bool = False, device=None) -> Graph:
     """Synthetic MuS-GNN input: uniform random points in [0,1]^dim, kNN edges scaled by 1/(2r),
     grid-clustered coarse levels, `field ~ N(0,1)`, `glob ~ U(0,1)`, `omega = U(0,1) > 0.9`.  With `device` (a GPU) the
-    points are uploaded first and the edges / levels are built there (§4.5 of DESIGN.md): the same graph, bit for bit."""
+    points are uploaded first and the edges / levels are built there (§4.5 of DESIGN.md): the same graph, bit for bit, as long as
+    no two candidate distances of a node are exactly equal (true of these random clouds; `connect_knn` states the tie rule)."""
     gen = torch.Generator().manual_seed(seed)
     pos = torch.rand(n, dim, generator=gen)
     if device is not None:
@@ -447,8 +520,15 @@ def angle_index_down(edge_index1, edge_attr1, edge_index2, edge_attr2, coarse_in
 
 def knn_interp_weights(pos_x: torch.Tensor, pos_y: torch.Tensor, k: int):
     """`get_knn_interpolate_weights` (transforms/interpolate.py:110-131): for every node of pos_y its k
-    nearest nodes of pos_x; weights = 1 / max(squared distance, 1e-16)."""
-    if pos_x.is_cuda:     # both clouds resident on the GPU: the search runs there (same neighbours, same order)
+    nearest nodes of pos_x; weights = 1 / max(squared distance, 1e-16).  On the GPU (`knn_query_device`) the float32 roundings of
+    both clouds are searched, and the neighbours are the host path's whenever no two candidate distances of a node are exactly
+    equal; with exact ties both are correct k-nearest sets in a path-specific order (`connect_knn`).  ValueError: fewer than k
+    points in pos_x, clouds of different width, a non-finite coordinate."""
+    if pos_x.dim() != 2 or pos_y.dim() != 2 or pos_x.size(1) != pos_y.size(1):
+        raise ValueError(f"knn_interp_weights: pos_x {tuple(pos_x.shape)} and pos_y {tuple(pos_y.shape)} must be [n, dim] and [m, dim]")
+    if k < 1 or int(pos_x.size(0)) < k:
+        raise ValueError(f"knn_interp_weights: k={k} neighbours of n={int(pos_x.size(0))} points")
+    if pos_x.is_cuda:     # both clouds resident on the GPU: the search runs there (the host's neighbours unless distances tie)
         x_idx = knn_query_device(pos_x, pos_y, k).reshape(-1)
     else:
         x_idx = torch.from_numpy(knn_neighbours(pos_x.double().numpy(), pos_y.double().numpy(), k).reshape(-1).astype(np.int64))
