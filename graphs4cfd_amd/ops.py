@@ -484,7 +484,9 @@ def steps_to_columns(out_steps: Tensor) -> Tensor:
 #                       x = h + l * 2^-11 (22 significand bits), three partial products, the 2^-11 terms in their own fp32
 #                       accumulator (G4C_WFMT_F16X2); measured error against fp64
 #                       below that of the fp32-MFMA kernel (scripts/mlp_accuracy.py, test_mlp_precisions_vs_fp64).  Range: fp16's — an MLP
-#                       input or hidden activation beyond +-65504 is clipped there (no inf / NaN) AND FLAGGED on the device; the
+#                       input or hidden activation beyond +-65504 is clipped there (no inf / NaN) AND FLAGGED on the device (the WEIGHTS
+#                       are converted when the image is packed, unclipped and unflagged: PackedMLP raises ValueError for a weight of
+#                       magnitude >= 65504 — check_weight_range); the
 #                       arithmetic is run optimistically: a rollout reads its flags where it hands out results (Rollout.validate) and
 #                       recomputes itself in "bf16x6" if anything was clipped, so solve() never returns a clipped value (normalised CFD
 #                       fields and LayerNorm'd latents are far inside the range; raw inputs only pass the fp32 vector path);
@@ -670,32 +672,52 @@ def weight_norms(weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], 
                  heads: Sequence[Tensor], seg_widths: Sequence[int], narrow: Optional[Sequence[bool]] = None) -> dict:
     """The norms range_bounds needs, evaluated in fp64 where the weights live and read back in ONE copy (an image is packed in an eager
     step, never inside a capture): per weighted (not narrow) input block of the first layer, per later layer and per head the largest
-    row sum of |W|; max|b| per layer; max|gamma|, max|beta| of the LayerNorm."""
+    row sum of |W|; max|b| per layer; max|gamma|, max|beta| of the LayerNorm; and, for the same matrices in the same order ("w0_max",
+    "w_max", "heads_max"), max|W| — the weights of an f16x3 image are converted to fp16 when it is packed (check_weight_range)."""
     narrow = tuple(bool(x) for x in narrow) if narrow is not None else (False,) * len(seg_widths)
 
     def rowsum(W: Tensor) -> Tensor:
         return W.detach().to(torch.float64).abs().sum(1).max()
+
+    def largest(W: Tensor) -> Tensor:
+        return W.detach().to(torch.float64).abs().max() if W.numel() else torch.zeros((), dtype=torch.float64, device=W.device)
     W0, dev = weights[0], weights[0].device
-    vals, col0, n_wide = [], 0, 0
+    vals, col0, n_wide, packed = [], 0, 0, []
     for w_, nar in zip(seg_widths, narrow):
         if not nar:
-            vals.append(rowsum(W0[:, col0:col0 + int(w_)]))
+            packed.append(W0[:, col0:col0 + int(w_)])
             n_wide += 1
         col0 += int(w_)
-    vals += [rowsum(W) for W in weights[1:]]
-    vals += [rowsum(W) for W in heads]
+    packed += list(weights[1:]) + list(heads)
+    vals += [rowsum(W) for W in packed]
     zero = torch.zeros((), dtype=torch.float64, device=dev)
     vals += [zero if b is None else b.detach().to(torch.float64).abs().max() for b in biases]
     if ln is not None:
         vals += [ln[0].detach().to(torch.float64).abs().max(), ln[1].detach().to(torch.float64).abs().max()]
+    vals += [largest(W) for W in packed]
     it = iter(torch.stack(vals).cpu().tolist())
     nl, nh = len(weights), len(heads)
     norms = {"w0": [next(it) for _ in range(n_wide)], "w": [next(it) for _ in range(nl - 1)], "heads": [next(it) for _ in range(nh)],
              "b": [next(it) for _ in range(nl)]}
     norms["ln"] = (next(it), next(it)) if ln is not None else None
+    norms["w0_max"], norms["w_max"], norms["heads_max"] = ([next(it) for _ in range(n_wide)], [next(it) for _ in range(nl - 1)],
+                                                           [next(it) for _ in range(nh)])
     norms["n_out"] = int(weights[-1].size(0))
     norms["narrow"] = any(narrow)
     return norms
+
+
+def check_weight_range(norms: dict, site: str) -> None:
+    """An f16x3 image holds its weights as fp16 pairs, converted when it is packed — without the clip and without the flag of the
+    activations' conversions: a weight that rounds beyond 65504 is packed as an infinity (measured from |w| = 65520: wrong finite rows,
+    flagged only where an activation behind it overflows in turn — a head's weight gives head rows of 3.4e38 and no flag;
+    tests/RANGE_SITES_MEASURED.md).  An MLP with |w| >= 65504 cannot run in this arithmetic: ValueError, naming the matrix."""
+    for key, what in (("w0_max", "input block {} of the first layer"), ("w_max", "layer {}"), ("heads_max", "head {}")):
+        for j, m in enumerate(norms[key]):
+            if m >= F16_RANGE_END:          # (a NaN weight is not a range matter: it shows in every row)
+                raise ValueError(f"{site}: {what.format(j + 2 if key == 'w_max' else j)} has a weight of magnitude {m:g}, outside the fp16 range "
+                                 f"(|w| >= {F16_RANGE_END:g}) of the 'f16x3' MLP arithmetic; set_mlp_precision('bf16x6') keeps fp32's "
+                                 "exponent range")
 
 
 class LaunchBounds:
@@ -1126,6 +1148,8 @@ class PackedMLP:
         self.device = dev
         # (the range proof's half of the image: rebuilt with it, under the same cache key — MLP._image)
         self.norms = weight_norms(weights, biases, ln, heads, seg_widths, narrow) if self.split == "f16x2" else None
+        if self.norms is not None:
+            check_weight_range(self.norms, self.site)
         # the parameter tensors this image was packed from (the training path differentiates with respect to them: autograd.py)
         self.params = (list(weights), list(biases), ln)
         self.heads_params = bool(heads)

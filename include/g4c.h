@@ -189,7 +189,9 @@ typedef struct {
  *   <= 2^-22 relative each: within the rounding error of an fp32 GEMM of the same shape (measured against fp64: scripts/mlp_accuracy.py,
  *   test_mlp_precisions_vs_fp64) at half the matrix-pipe work of BF16X3.  Range: an input or hidden activation with |x| > 65504 is
  *   clipped to +-65504 (1 + 2^-11) when it is converted (MODE.FP16_OVFL; no infinities or NaNs; reported through io->range_flag); small
- *   values lose nothing.  Planes 0 / 1 of the same layout, plane 2 zero.
+ *   values lose nothing.  The WEIGHTS are converted by g4c_mlp_pack_layer, in the default rounding mode and with no report: every
+ *   |w| must be below 65504 (the caller's obligation; graphs4cfd_amd/ops.py PackedMLP raises ValueError for a weight beyond it and
+ *   points to "bf16x6").  Planes 0 / 1 of the same layout, plane 2 zero.
  * G4C_WFMT_BF16 (rounded bf16, BASELINE config 3 "bf16 edge-MLP MFMA", opt-in): the BF16X3 stream, of which only the LEADING plane is
  *   used: weights and the activations entering each Linear are rounded to bf16 (one product per multiply-add), accumulation / bias /
  *   SELU / LayerNorm / additive sources / residual stay fp32.  Expected deviation from fp32: ~1e-2 on LayerNorm-scale outputs.  Heads

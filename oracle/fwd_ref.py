@@ -42,6 +42,7 @@ F32 = torch.float32
 MAX_FACTOR, MAX_ABS = 2.0, 1e-6        # test_mlp_precisions_vs_fp64: err_max <= 2.0 err32_max + 1e-6
 MEAN_FACTOR, MEAN_ABS = 1.5, 1e-7      #                              err_mean <= 1.5 err32_mean + 1e-7
 CLASS_NAMES = ("ordinary", "large", "small")
+F16_RANGE_END = 65504.0                # the largest fp16: an f16x3 launch flags a converted value of this magnitude or more
 
 
 # ------------------------------------------------------------------ one launch
@@ -69,6 +70,7 @@ class Launch:
     resid_col0: int = 0
     out_idx: Optional[Tensor] = None          # row r of the launch is stored in row out_idx[r] of `out_init`
     out_init: Optional[Tensor] = None         # what the output tensor held before the launch (rows no index names keep it)
+    narrow: Sequence[bool] = ()               # per weighted block: multiplied in fp32 on the vector ALUs (never converted to fp16)
 
 
 def _segment(v: Tensor, off: Tensor, perm: Optional[Tensor], mean: bool) -> Tensor:
@@ -165,11 +167,126 @@ def mp_layer(msg: Launch, off: Tensor, mean: bool, upd_weights, upd_biases, upd_
     return {"e": e, "agg": agg, "v": evaluate(upd, dtype, linear)["y"]}
 
 
+# ------------------------------------------------------------------ what a launch converts to fp16 (the f16x3 range flags)
+@dataclass
+class MpLayer:
+    """ops.mp_layer_forward: the message launch `msg`, its rows aggregated over `off`, the node MLP on [aggregate | v]."""
+    msg: Launch
+    off: Tensor
+    mean: bool
+    weights: Sequence[Tensor]
+    biases: Sequence[Optional[Tensor]]
+    ln: Optional[Tuple[Tensor, Tensor]]
+    v: Tensor
+    v_act: Optional[str] = None
+
+
+@dataclass
+class Precomputed:
+    """ops.mlp_forward_precomputed: layer 0's pre-activation is (first + adds[0]) + adds[1]; `weights` / `biases` are the layers left."""
+    first: Tensor
+    adds: Sequence[Add]
+    weights: Sequence[Tensor]
+    biases: Sequence[Optional[Tensor]]
+    ln: Optional[Tuple[Tensor, Tensor]] = None
+    act: Optional[str] = None
+
+
+def _hidden(z: Tensor, weights, biases, sites: Dict[str, Tensor], linear, key: str = "") -> Tensor:
+    """The layers behind the first: SELU(z_l) is converted (site h{l}) for every layer but the last; returns the last z."""
+    for l, (W, b) in enumerate(zip(weights, biases), 1):
+        h = _act(z, "selu")
+        sites[f"{key}h{l}"] = h
+        z = linear(h, W)
+        if b is not None:
+            z = z + b.to(z.dtype)
+    return z
+
+
+def converted(L: Launch, dtype=F64, heads: bool = False, linear=plain_linear, key: str = "") -> Dict[str, Tensor]:
+    """The tensors one launch converts to fp16, by site, written out like `evaluate`:
+      in{j}   weighted block j as it is parked: after the column window, `pre_act`, the gather or the sum / mean on load, BEFORE
+              `negate` (the sign is folded into the packed weights).  A narrow block (fp32 vector path) and an additive block are no sites;
+      h{l}    SELU(z_l) for every layer but the last (the additive blocks are inside z_1);
+      heads   the output rows y (after LayerNorm and the output activation), when the launch has heads."""
+    sites: Dict[str, Tensor] = {}
+    X = []
+    for j, s in enumerate(L.srcs):
+        v = block_rows(replace(s, negate=False), dtype)
+        if not (j < len(L.narrow) and L.narrow[j]):
+            sites[f"{key}in{j}"] = v
+        X.append(-v if s.negate else v)
+    z = linear(torch.cat(X, 1), L.weights[0])
+    if L.biases[0] is not None:
+        z = z + L.biases[0].to(dtype)
+    for a in L.adds:
+        z = z + a.rows(dtype, int(z.size(1)))
+    z = _hidden(z, L.weights[1:], L.biases[1:], sites, linear, key)
+    if heads:
+        sites[f"{key}heads"] = _act(z if L.ln is None else layer_norm(z, L.ln[0], L.ln[1]), L.act)
+    return sites
+
+
+def converted_mp_layer(M: MpLayer, dtype=F64, heads: bool = False, linear=plain_linear) -> Dict[str, Tensor]:
+    """`converted` of the one-launch MP layer: msg.in0, msg.h*; upd.in0 (the aggregate), upd.in1 (v), upd.h*, upd.heads."""
+    sites = converted(M.msg, dtype, False, linear, "msg.")
+    e = evaluate(M.msg, dtype, linear)["y"]
+    upd = Launch([Src(_segment(e, M.off, None, M.mean)), Src(M.v)], M.weights, M.biases, M.ln, M.v_act)
+    sites.update(converted(upd, dtype, heads, linear, "upd."))
+    return sites
+
+
+def converted_precomputed(P: Precomputed, dtype=F64, linear=plain_linear) -> Dict[str, Tensor]:
+    """`converted` of the launch without its first layer: no in0; h1 = SELU((first + p0[i0]) + p1[i1]), h2."""
+    z = P.first.to(dtype)
+    for a in P.adds:
+        z = z + a.rows(dtype, int(z.size(1)))
+    sites: Dict[str, Tensor] = {}
+    _hidden(z, P.weights, P.biases, sites, linear)
+    return sites
+
+
+def precomputed_rows(P: Precomputed, dtype=F64, linear=plain_linear) -> Tensor:
+    """The output rows of the launch without its first layer."""
+    z = P.first.to(dtype)
+    for a in P.adds:
+        z = z + a.rows(dtype, int(z.size(1)))
+    z = _hidden(z, P.weights, P.biases, {}, linear)
+    return _act(z if P.ln is None else layer_norm(z, P.ln[0], P.ln[1]), P.act)
+
+
+def sites_of(L, dtype=F64, heads: bool = False, linear=plain_linear) -> Dict[str, Tensor]:
+    if isinstance(L, MpLayer):
+        return converted_mp_layer(L, dtype, heads, linear)
+    if isinstance(L, Precomputed):
+        return converted_precomputed(L, dtype, linear)
+    return converted(L, dtype, heads, linear)
+
+
+def site_maxima(sites: Dict[str, Tensor]) -> Dict[str, float]:
+    return {k: float(v.abs().max()) if v.numel() else 0.0 for k, v in sites.items()}
+
+
+def expected_flag(sites: Dict[str, Tensor]) -> bool:
+    """The contract of the f16x3 range flag: set exactly when a converted value has magnitude >= 65504."""
+    return any(bool((v.abs() >= F16_RANGE_END).any()) for v in sites.values())
+
+
+def emulated_flag(L, skip: Sequence[str] = (), heads: bool = False) -> bool:
+    """The flag an f16x3 kernel would raise: the same sites computed in fp32 through the emulated operand split (conversions clipping
+    at +-65504, as the kernels' do), `skip` naming the sites whose tracker is left out (negative controls)."""
+    sites = sites_of(L, F32, heads, split_linear("f16x3", saturate=True))
+    return expected_flag({k: v for k, v in sites.items() if k not in set(skip)})
+
+
 # ------------------------------------------------------------------ the kernels' operand splits, emulated in torch
-def _split_f16(x: Tensor) -> Tuple[Tensor, Tensor]:
-    """x = h + l 2^-11 (include/g4c.h, G4C_WFMT_F16X2): h = fp16(x), l = fp16((x - h) 2^11), both held in fp32."""
-    h = x.to(torch.float16).to(F32)
-    return h, ((x - h) * 2048.0).to(torch.float16).to(F32)
+def _split_f16(x: Tensor, saturate: bool = False) -> Tuple[Tensor, Tensor]:
+    """x = h + l 2^-11 (include/g4c.h, G4C_WFMT_F16X2): h = fp16(x), l = fp16((x - h) 2^11), both held in fp32.  `saturate`: both
+    conversions clip at +-65504 instead of overflowing (the kernels' conversion mode; the range emulation)."""
+    def f16(t):
+        return (t.clamp(-F16_RANGE_END, F16_RANGE_END) if saturate else t).to(torch.float16).to(F32)
+    h = f16(x)
+    return h, f16((x - h) * 2048.0)
 
 
 def _split_bf16(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -178,12 +295,12 @@ def _split_bf16(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     return h, m, (x - h - m).to(torch.bfloat16).to(F32)
 
 
-def split_linear(split: str, lose: Optional[str] = None) -> Callable[[Tensor, Tensor], Tensor]:
+def split_linear(split: str, lose: Optional[str] = None, saturate: bool = False) -> Callable[[Tensor, Tensor], Tensor]:
     """The product rule of "f16x3" (three products, the 2^-11 terms in an accumulator of their own) or "bf16x6" (the six largest
     products of the exact three-way split), on fp32 tensors with fp32 sums.  `lose` (f16x3; negative controls): "wl_xh", "wh_xl" or
-    "both" of the low products dropped."""
+    "both" of the low products dropped.  `saturate` (f16x3): the row operand's conversions clip at the end of fp16's range."""
     def f16x3(x: Tensor, W: Tensor) -> Tensor:
-        xh, xl = _split_f16(x.to(F32))
+        xh, xl = _split_f16(x.to(F32), saturate)
         wh, wl = _split_f16(W.to(F32))
         low = torch.zeros((), dtype=F32, device=x.device)
         if lose not in ("wh_xl", "both"):
