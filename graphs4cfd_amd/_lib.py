@@ -78,6 +78,17 @@ class g4c_mlp_io_t(C.Structure):
         super().__init__(size=C.sizeof(g4c_mlp_io_t), **kw)
 
 
+REC_SQ_ERR, REC_ABS_ERR, REC_MAX_ABS_ERR, REC_TGT_SUM, REC_TGT_SQ_SUM, REC_ABS_ERR_MASK, REC_NSTAT = range(7)     # G4C_REC_*
+REC_MAX_NF = 8                                      # widest prediction g4c_rollout_advance_record forms statistics of
+
+
+class g4c_rollout_rec_t(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("snap", C.c_void_p), ("every", C.c_int32), ("n_snap", C.c_int32),
+                ("probe_rows", C.c_void_p), ("n_probe", C.c_int32), ("probe_out", C.c_void_p),
+                ("target", C.c_void_p), ("target_ld", C.c_int32), ("mask", C.c_void_p), ("stats", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -113,6 +124,9 @@ _SIGNATURES = {
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "g4c_rollout_advance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
+    "g4c_rollout_record_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
+    "g4c_rollout_advance_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_rec_t),
+                                             C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

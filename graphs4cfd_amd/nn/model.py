@@ -177,12 +177,38 @@ class GNN(nn.Module):
         return float(torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads))))
 
     # ---------------------------------------------------------------------------------- rollout
-    def solve(self, graph: Union[Graph, List[Graph]], n_out: int, *, capture: Optional[bool] = None) -> torch.Tensor:
+    def solve(self, graph: Union[Graph, List[Graph]], n_out: int, *, capture: Optional[bool] = None, every: int = 1) -> torch.Tensor:
         """Evaluate the model on the graph for n_out time-steps. Returns [N, num_fields*n_out].
 
         capture: replay steps 2..n_out from a hipGraph captured on step 2 (default: on when
-        n_out >= 4 and the environment variable G4C_HIPGRAPH is not '0')."""
+        n_out >= 4 and the environment variable G4C_HIPGRAPH is not '0').
+        every (not in the reference): keep only every k-th step — steps k - 1, 2k - 1, ... (0-based) — and return
+        [N, num_fields * (n_out // k)]; the buffer of all n_out steps is then never allocated (`Rollout(every=)`)."""
         assert n_out > 0, "n_out must be greater than 0."
+        if int(every) < 1:
+            raise ValueError(f"every: solve() keeps every k-th step, k >= 1, got {every} (evaluate() runs a rollout without snapshots)")
+        with self._rollout(graph, n_out, capture, "solve()", every=int(every)) as ro:
+            ro.run(n_out)
+            return ro.result()       # (reports a clip of the default arithmetic in this model's own launches)
+
+    def evaluate(self, graph: Union[Graph, List[Graph]], n_out: Optional[int] = None, *, every: int = 0, probes: Optional[torch.Tensor] = None,
+                 capture: Optional[bool] = None) -> "RolloutErrors":
+        """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
+        the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
+        `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
+        predictions of every step are not held.  every = k > 0 also keeps the snapshots solve(every=k)
+        returns (`.snapshots`), probes (1-D integer tensor of node rows) the prediction's time series there (`.probes`,
+        [P, num_fields * n_out]).  A list of graphs is collated as in `solve`."""
+        target = graph[0].target if type(graph) is list else graph.target
+        if n_out is None:
+            n_out = int(target.size(1)) // int(self.num_fields)
+        assert n_out > 0, "n_out must be greater than 0."
+        with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True) as ro:
+            ro.run(n_out)
+            return ro.errors()
+
+    def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
+        """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -194,9 +220,11 @@ class GNN(nn.Module):
                 capture = n_out >= 4 and os.environ.get("G4C_HIPGRAPH", "1") != "0"
             if ops.mlp_precision() == "f16x3":
                 _warn_f16_range(graph)
-            with Rollout(self, graph, n_out, capture=capture, label="solve()") as ro:
-                ro.run(n_out)
-                return ro.result()       # (reports a clip of the default arithmetic in this model's own launches)
+            if evaluate:
+                records["target"] = graph.target
+                omega = getattr(graph, "omega", None)
+                records["mask"] = (omega[:, 0] == 1) if torch.is_tensor(omega) else None
+            return Rollout(self, graph, n_out, capture=capture, label=label, **records)
 
     def invalidate_packed(self) -> None:
         """Declare every packed weight image stale (they are rebuilt on the next launch).  The images are keyed on the parameters'
@@ -325,11 +353,20 @@ class Rollout:
     The caller's `graph.field` is swapped for a private working copy and restored on close()."""
 
     def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
-                 label: str = "Rollout"):
+                 label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
-        just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are."""
+        just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
+
+        Records (all opt-in; with none of them the step ends in `g4c_rollout_advance` and every prediction is kept, as `solve`
+        does; with any, it ends in `g4c_rollout_advance_record`, which writes them inside the step, captured or not):
+        `every` = k: keep steps k - 1, 2k - 1, ... (0-based) only — `result()` is [N, nf * (max_steps // k)] and the buffer has
+        max_steps // k slots; 0 keeps none (`result()` raises).  `probes`: 1-D integer tensor of node rows (repeats allowed) —
+        `probes()` is their predictions at every step, [P, nf * max_steps].  `target` [N, >= nf * max_steps] (and `mask` [N] bool:
+        the Dirichlet nodes): `errors()` is the error of every step against it (`RolloutErrors`).  Rows are the caller's numbering."""
         _lib.require_hip(graph.field)
+        recording = _check_records(graph, int(model.num_fields), int(max_steps), every, probes, target, mask)
         self._caller_graph, self._perm = graph, None
         if reorder is None:
             reorder = graph.num_nodes >= REORDER_MIN_NODES and os.environ.get("G4C_REORDER", "1") != "0"
@@ -345,7 +382,8 @@ class Rollout:
         self._orig_field = graph.field
         self.field = graph.field.to(torch.float32).clone(memory_format=torch.contiguous_format)
         # step-major [steps, N, nf]: a step's predictions are one contiguous block (`outputs` gives the reference's [N, nf * steps])
-        self._out_steps = torch.zeros((self.max_steps, graph.num_nodes, self.nf), dtype=torch.float32, device=dev)
+        self._out_steps = None if recording else torch.zeros((self.max_steps, graph.num_nodes, self.nf), dtype=torch.float32, device=dev)
+        self._rec = _Records(self, int(every), probes, target, mask) if recording else None     # (its snapshots are `_out_steps`)
         self.step_counter = torch.zeros(2, dtype=torch.int32, device=dev)          # [step index, g4c_rollout_advance's ticket]
         self.steps_done = 0
         self._hipgraph, self._epoch, self._pins = None, -1, None
@@ -367,11 +405,16 @@ class Rollout:
     def outputs(self) -> torch.Tensor:
         """[N, nf * max_steps] in the rollout's node numbering, as `GNN.solve` lays its result out (nn/model.py:322-326) — a fresh
         transposed copy of the step-major buffer on every access (no validation: `result()` is the delivered form)."""
+        if self._out_steps is None:
+            raise RuntimeError(f"{self.label}: every=0 keeps no snapshot of the predictions (probes() and errors() hold the records)")
         return ops.steps_to_columns(self._out_steps)
 
     def _one(self):
         with self.static, self.flags:
             pred = self.model.forward(self.graph, self.steps_done)
+        if self._rec is not None:
+            self._rec.advance(self.field, pred, self.step_counter)
+            return
         ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
 
     def step(self) -> None:
@@ -469,6 +512,25 @@ class Rollout:
         out[self._perm] = cols
         return out
 
+    def probes(self) -> torch.Tensor:
+        """[P, nf * max_steps]: the predictions at the `probes=` rows, in the order given, step after step (columns of steps not yet
+        taken are zero) — validated first, like `result()`."""
+        if self._rec is None or self._rec.probe_out is None:
+            raise RuntimeError(f"{self.label}: no probes= were given")
+        self.validate()
+        return ops.steps_to_columns(self._rec.probe_out)
+
+    def errors(self) -> "RolloutErrors":
+        """The error of the `steps_done` steps taken against `target=` (`RolloutErrors`, fp64 host tensors) — validated first, like
+        `result()`; one device -> host copy of [steps_done, nf, 6] sums."""
+        if self._rec is None or self._rec.stats is None:
+            raise RuntimeError(f"{self.label}: no target= was given")
+        self.validate()
+        rec = self._rec
+        return RolloutErrors(rec.stats[:self.steps_done].cpu(), int(self.graph.num_nodes), rec.n_masked,
+                             snapshots=self.result() if self._out_steps is not None else None,
+                             probes=ops.steps_to_columns(rec.probe_out) if rec.probe_out is not None else None)
+
     def close(self) -> None:
         self.graph.field = self._orig_field
 
@@ -478,3 +540,108 @@ class Rollout:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+def _check_records(graph: Graph, nf: int, max_steps: int, every, probes, target, mask) -> bool:
+    """The record arguments of `Rollout` against the caller's graph, on the tensors as they were passed (probe rows are read on the
+    host copy the caller holds: nothing is uploaded first).  Returns whether any record was asked for."""
+    n = int(graph.num_nodes)
+    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+        raise ValueError(f"every: expected an integer >= 0 (0: no snapshots, k: every k-th step), got {every!r}")
+    if probes is not None:
+        if not torch.is_tensor(probes) or probes.dtype.is_floating_point or probes.dtype == torch.bool or probes.is_complex():
+            raise TypeError(f"probes: expected a 1-D integer tensor of node rows, got {getattr(probes, 'dtype', type(probes).__name__)}")
+        if probes.dim() != 1:
+            raise ValueError(f"probes: expected a 1-D integer tensor of node rows, got shape {tuple(probes.shape)}")
+        if probes.numel() and (int(probes.min()) < 0 or int(probes.max()) >= n):
+            raise ValueError(f"probes: rows {int(probes.min())} .. {int(probes.max())} of a graph of {n} nodes")
+    if target is not None:
+        if not torch.is_tensor(target) or not target.dtype.is_floating_point:
+            raise TypeError(f"target: expected a floating-point tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+        if target.dim() != 2 or int(target.size(0)) != n or int(target.size(1)) < nf * max_steps:
+            raise ValueError(f"target: expected [{n}, >= nf * max_steps = {nf * max_steps}], got {tuple(target.shape)}")
+        if nf > _lib.REC_MAX_NF:
+            raise NotImplementedError(f"target: the error statistics cover models of up to {_lib.REC_MAX_NF} fields, this one has {nf}")
+    if mask is not None:
+        if target is None:
+            raise ValueError("mask: given without a target")
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool:
+            raise TypeError(f"mask: expected a bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
+        if tuple(mask.shape) != (n,):
+            raise ValueError(f"mask: expected shape ({n},), got {tuple(mask.shape)}")
+    return every != 1 or probes is not None or target is not None
+
+
+class _Records:
+    """The record buffers of a `Rollout` and the launch that fills them.  Everything is allocated here, once, in the rollout's node
+    numbering (probe rows, target rows and mask rows are mapped through the Morton permutation at construction), so a captured
+    step allocates nothing; every slot is addressed by the device-side step index alone, so `rewind()` and a recomputation
+    (`Rollout._recompute_exact`) overwrite the records of the steps they run again."""
+
+    def __init__(self, ro: "Rollout", every: int, probes, target, mask):
+        dev, n, nf, steps, perm = ro.field.device, int(ro.graph.num_nodes), ro.nf, ro.max_steps, ro._perm
+        self.nf, self.max_steps, self.every = nf, steps, every
+        self.snap = torch.zeros((steps // every, n, nf), dtype=torch.float32, device=dev) if every else None
+        ro._out_steps = self.snap
+        self.probe_rows = self.probe_out = self.target = self.mask = self.stats = self.scratch = None
+        self.n_masked = None
+        if probes is not None:
+            rows = probes.to(dev, torch.long)
+            if perm is not None:                      # caller's row r is the rollout's row inv[r]
+                inv = torch.empty_like(perm)
+                inv[perm] = torch.arange(n, device=perm.device)
+                rows = inv.to(dev)[rows]
+            self.probe_rows = rows.to(torch.int32).contiguous()
+            self.probe_out = torch.zeros((steps, int(rows.numel()), nf), dtype=torch.float32, device=dev)
+        if target is not None:
+            t = target.to(dev, torch.float32)
+            if perm is not None:
+                t = t[perm.to(dev)]
+            if t.stride(1) != 1 or t.stride(0) < t.size(1):
+                t = t.contiguous()
+            self.target = t
+            if mask is not None:
+                m = mask.to(dev)
+                self.n_masked = int(m.sum())
+                self.mask = (m[perm.to(dev)] if perm is not None else m).contiguous()
+            self.stats = torch.zeros((steps, nf, _lib.REC_NSTAT), dtype=torch.float64, device=dev)
+            self.scratch = ops.rollout_record_scratch(n, nf, dev)
+
+    def advance(self, field, pred, step) -> None:
+        ops.rollout_advance_record(field, pred, step, self.nf, self.max_steps, snap=self.snap, every=self.every,
+                                   probe_rows=self.probe_rows, probe_out=self.probe_out, target=self.target, mask=self.mask,
+                                   stats=self.stats, scratch=self.scratch)
+
+
+class RolloutErrors:
+    """Per-step errors of a rollout against its target (`Rollout.errors()`, `GNN.evaluate()`): fp64 host tensors [steps, nf] —
+    `mse` = Σd²/N, `mae` = Σ|d|/N, `max_abs` = max|d|, `r2` = 1 − Σd² / (Σy² − (Σy)²/N) (inf or nan where the target is constant),
+    `mae_masked` = Σ|d| over the masked (Dirichlet) nodes / their number (None without a mask) — with d = prediction − target and
+    y = the target, all from `sums` [steps, nf, 6] = (Σd², Σ|d|, max|d|, Σy, Σy², Σ_masked|d|), which the step's last launch
+    accumulated on the device in fp64 in a fixed order.  `snapshots` / `probes`: the rollout's `result()` / `probes()` when it kept
+    any, else None."""
+
+    def __init__(self, sums: torch.Tensor, n_nodes: int, n_masked: Optional[int] = None, snapshots: Optional[torch.Tensor] = None,
+                 probes: Optional[torch.Tensor] = None):
+        self.sums, self.n_nodes, self.n_masked, self.snapshots, self.probes = sums, int(n_nodes), n_masked, snapshots, probes
+        n = float(n_nodes)
+        sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
+        self.mse, self.mae, self.max_abs = sq / n, ab / n, mx
+        self.r2 = 1.0 - sq / (ty2 - ty * ty / n)
+        self.mae_masked = None if n_masked is None else abm / float(n_masked)
+
+    @property
+    def steps(self) -> int:
+        return int(self.sums.size(0))
+
+    def graph_loss(self, lambda_d: float = 0.0) -> torch.Tensor:
+        """`GraphLoss(lambda_d)` of every step, [steps], from the same sums: Σ_f Σd² / (N nf) + lambda_d Σ_f Σ_masked|d| / (N_masked nf),
+        the second term only with lambda_d > 0 and at least one masked node (nn/losses.py)."""
+        nf = int(self.sums.size(1))
+        loss = self.sums[..., _lib.REC_SQ_ERR].sum(1) / (self.n_nodes * nf)
+        if lambda_d > 0 and self.n_masked:
+            loss = loss + lambda_d * self.sums[..., _lib.REC_ABS_ERR_MASK].sum(1) / (self.n_masked * nf)
+        return loss
+
+    def __repr__(self):
+        return f"RolloutErrors(steps={self.steps}, fields={int(self.sums.size(1))}, nodes={self.n_nodes}, masked={self.n_masked})"

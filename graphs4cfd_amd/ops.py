@@ -474,6 +474,106 @@ def rollout_advance(field: Tensor, pred: Tensor, outputs: Tensor, step: Tensor, 
                                        out_ld, _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def rollout_record_scratch(n_nodes: int, nf: int, device) -> Tensor:
+    """The `scratch` buffer of rollout_advance_record's statistics for a mesh of n_nodes and nf fields (the size is the library's:
+    g4c_rollout_record_scratch_doubles)."""
+    n = int(_lib.load().g4c_rollout_record_scratch_doubles(int(n_nodes), int(nf)))
+    if n < 0:
+        _lib.check(n)
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def rollout_advance_record(field: Tensor, pred: Tensor, step: Tensor, nf: int, max_steps: int, *, snap: Optional[Tensor] = None,
+                           every: int = 0, probe_rows: Optional[Tensor] = None, probe_out: Optional[Tensor] = None,
+                           target: Optional[Tensor] = None, mask: Optional[Tensor] = None, stats: Optional[Tensor] = None,
+                           scratch: Optional[Tensor] = None) -> None:
+    """g4c_rollout_advance_record: rollout_advance's shift of `field` and bump of `step`, and the records of step t = step[0] (read on
+    the device; nothing for t >= max_steps):
+    snap [n_snap, N, nf] with every = k > 0: steps k - 1, 2k - 1, ... in slots 0, 1, ...;
+    probe_out [max_steps, P, nf]: pred's rows probe_rows (int32 [P]; their values are never read here);
+    stats float64 [max_steps, nf, _lib.REC_NSTAT]: the error sums against target[:, nf t : nf (t + 1)] (target: [N, >= nf max_steps],
+    unit stride along its columns, any row stride), Σ|d| also over the rows of `mask` (uint8 / bool [N]); `scratch` comes from
+    rollout_record_scratch."""
+    nf, max_steps, every = int(nf), int(max_steps), int(every)
+    what = "rollout_advance_record"
+
+    def dense(t, name, dtypes, shape=None):
+        if not torch.is_tensor(t) or t.dtype not in dtypes:
+            raise TypeError(f"{name}: {what}: expected a {' / '.join(str(d).replace('torch.', '') for d in dtypes)} tensor, got "
+                            f"{getattr(t, 'dtype', type(t).__name__)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: {what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+    dense(field, "field", (torch.float32,))
+    dense(pred, "pred", (torch.float32,))
+    if not torch.is_tensor(step) or step.dtype != torch.int32:
+        raise TypeError(f"step: {what}: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+    if step.dim() != 1 or step.numel() < 2 or not step.is_contiguous():
+        raise ValueError(f"step: {what}: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+    if field.dim() != 2 or nf <= 0 or int(field.size(1)) < nf:
+        raise ValueError(f"field: expected [n_nodes, >= nf = {nf}], got shape {tuple(field.shape)}")
+    n_nodes = int(field.size(0))
+    if tuple(pred.shape) != (n_nodes, nf):
+        raise ValueError(f"pred: expected shape ({n_nodes}, {nf}), got {tuple(pred.shape)}")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if every < 0:
+        raise ValueError(f"every: {what}: {every} (0 keeps no snapshot, k > 0 every k-th step)")
+    if (every > 0) != (snap is not None):
+        raise ValueError(f"snap: {what}: every = {every} {'needs' if every else 'takes no'} snapshot buffer")
+    if snap is not None:
+        dense(snap, "snap", (torch.float32,))
+        if snap.dim() != 3 or tuple(snap.shape[1:]) != (n_nodes, nf):
+            raise ValueError(f"snap: {what}: expected [n_snap, {n_nodes}, {nf}], got {tuple(snap.shape)}")
+    if (probe_rows is None) != (probe_out is None):
+        raise ValueError(f"probe_{'out' if probe_out is None else 'rows'}: {what}: probe_rows and probe_out come together")
+    n_probe = 0
+    if probe_rows is not None:
+        dense(probe_rows, "probe_rows", (torch.int32,))
+        if probe_rows.dim() != 1:
+            raise ValueError(f"probe_rows: {what}: expected a 1-D index tensor, got shape {tuple(probe_rows.shape)}")
+        n_probe = int(probe_rows.numel())
+        dense(probe_out, "probe_out", (torch.float32,), (max_steps, n_probe, nf))
+    target_ld = 0
+    if target is None:
+        for t, name in ((mask, "mask"), (stats, "stats"), (scratch, "scratch")):
+            if t is not None:
+                raise ValueError(f"{name}: {what}: given without a target")
+    else:
+        if not torch.is_tensor(target) or target.dtype != torch.float32:
+            raise TypeError(f"target: {what}: expected a float32 tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+        if target.dim() != 2 or int(target.size(0)) != n_nodes or int(target.size(1)) < nf * max_steps:
+            raise ValueError(f"target: {what}: expected [{n_nodes}, >= nf * max_steps = {nf * max_steps}], got {tuple(target.shape)}")
+        cols = int(target.size(1))
+        if (cols > 1 and target.stride(1) != 1) or (n_nodes > 1 and target.stride(0) < cols):
+            raise ValueError(f"target: {what} needs rows of unit stride, got shape {tuple(target.shape)} strides {tuple(target.stride())}")
+        target_ld = max(int(target.stride(0)), cols) if n_nodes > 1 else cols
+        if mask is not None:
+            dense(mask, "mask", (torch.uint8, torch.bool), (n_nodes,))
+        if stats is None or scratch is None:
+            raise ValueError(f"{'stats' if stats is None else 'scratch'}: {what}: a target needs stats and scratch")
+        dense(stats, "stats", (torch.float64,), (max_steps, nf, _lib.REC_NSTAT))
+        dense(scratch, "scratch", (torch.float64,))
+        if scratch.dim() != 1:
+            raise ValueError(f"scratch: {what}: expected a 1-D tensor, got shape {tuple(scratch.shape)}")
+    lib = _lib.load()
+    dev = _lib.require_hip(field, pred, step, snap, probe_rows, probe_out, target, mask, stats, scratch)
+    if target is not None:
+        need = int(lib.g4c_rollout_record_scratch_doubles(n_nodes, nf))
+        if need < 0:
+            _lib.check(need)
+        if int(scratch.numel()) < need:
+            raise ValueError(f"scratch: {what}: {need} doubles for {n_nodes} nodes x {nf} fields, got {int(scratch.numel())}")
+    rec = _lib.g4c_rollout_rec_t(max_steps=max_steps, snap=_lib.ptr(snap), every=every, n_snap=0 if snap is None else int(snap.size(0)),
+                                 probe_rows=_lib.ptr(probe_rows), n_probe=n_probe, probe_out=_lib.ptr(probe_out),
+                                 target=_lib.ptr(target), target_ld=target_ld, mask=_lib.ptr(mask), stats=_lib.ptr(stats),
+                                 scratch=_lib.ptr(scratch))
+    _lib.check(lib.g4c_rollout_advance_record(_lib.ptr(field), int(field.size(1)), _lib.ptr(pred), nf, C.byref(rec),
+                                              _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

@@ -441,6 +441,38 @@ int g4c_knn_grid_query(const float *pos_sorted, const int32_t *order, const int3
 int g4c_rollout_advance(float *field, int32_t field_cols, const float *pred, int32_t nf,
                         float *outputs, int32_t out_ld, int32_t *step, int64_t n_nodes, void *stream);
 
+/* The recording form of the launch above (csrc/rollout_record.hip): everything g4c_rollout_advance does to `field` and `step`, and,
+ * addressed by the step index t the launch reads on the device, up to three records of the step — no `outputs` buffer of every step
+ * is needed.  The descriptor is read on the host and travels with the launch by value (a captured launch carries it).
+ * A step index outside [0, max_steps), or a snapshot slot >= n_snap, leaves no record; field and step advance all the same, and no
+ * probe row outside [0, n_nodes) is read.  n_nodes == 0 advances the step and records nothing.
+ * Statistics (target != NULL, 1 <= nf <= 8, G4C_EUNSUPPORTED above): with d = (double)pred - (double)target[:, nf t + f], per field f
+ * stats[t][f] = { sum d^2, sum |d|, max |d|, sum y, sum y^2, sum |d| over the rows with mask != 0 } (y = the target), accumulated in
+ * fp64 without floating-point atomics in an order that depends on (n_nodes, nf) alone: bit-identical between runs and between captured
+ * and eager launches.  stats[t] is overwritten.  The workgroups' partials go through `scratch` and are combined by a second, one-
+ * workgroup launch on the same stream (rollout_record_stats_kernel). */
+typedef struct g4c_rollout_rec {
+    int32_t max_steps;           /* capacity of probe_out / stats / target, in steps */
+    /* snapshots: step t (0-based) is kept iff every > 0 and (t + 1) % every == 0, in slot (t + 1) / every - 1, while slot < n_snap */
+    float  *snap;                /* [n_snap][n_nodes][nf], step-major like `outputs` with out_ld == 0; NULL iff every == 0 (or n_snap == 0) */
+    int32_t every, n_snap;
+    /* probes: rows probe_rows[0 .. n_probe) of every step */
+    const int32_t *probe_rows;   /* NULL iff n_probe == 0 */
+    int32_t n_probe;
+    float  *probe_out;           /* [max_steps][n_probe][nf] */
+    /* error statistics of every step against target[:, nf t : nf (t + 1)] */
+    const float *target;         /* [n_nodes, target_ld], target_ld >= nf * max_steps; NULL: no statistics */
+    int32_t target_ld;
+    const uint8_t *mask;         /* [n_nodes] or NULL: the subset for G4C_REC_ABS_ERR_MASK (Dirichlet nodes) */
+    double *stats;               /* [max_steps][nf][G4C_REC_NSTAT] */
+    double *scratch;             /* g4c_rollout_record_scratch_doubles(n_nodes, nf) doubles */
+} g4c_rollout_rec_t;
+enum { G4C_REC_SQ_ERR, G4C_REC_ABS_ERR, G4C_REC_MAX_ABS_ERR, G4C_REC_TGT_SUM, G4C_REC_TGT_SQ_SUM, G4C_REC_ABS_ERR_MASK, G4C_REC_NSTAT };
+/* Size of `scratch` in doubles (host; negative G4C_E* code for n_nodes < 0, nf < 1 or nf > 8). */
+int64_t g4c_rollout_record_scratch_doubles(int64_t n_nodes, int32_t nf);
+int g4c_rollout_advance_record(float *field, int32_t field_cols, const float *pred, int32_t nf, const g4c_rollout_rec_t *rec /*host*/,
+                               int32_t *step, int64_t n_nodes, void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
