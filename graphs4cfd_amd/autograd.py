@@ -279,7 +279,11 @@ def weight_grad(g: Tensor, a: Tensor) -> Tensor:
 
 
 def _dense(t: Tensor) -> Tensor:
-    return t if (t.dim() == 2 and t.stride(1) == 1) else t.contiguous()
+    """`t` as rows a launch can address as t[r * ld + c]: unit column stride and rows that do not overlap.  A view autograd hands over
+    that is neither — a transposed gradient, or the row-broadcast one behind `out.sum(0)` (strides (0, 1): a leading dimension of 0,
+    which every launch refuses) — is materialised."""
+    ok = t.dim() == 2 and (t.stride(1) == 1 or t.size(1) <= 1) and (t.size(0) <= 1 or t.stride(0) >= t.size(1))
+    return t if ok else t.contiguous()
 
 
 # ------------------------------------------------------------------------------------- fused MLP
@@ -591,11 +595,11 @@ def _segment_coefficients(w: Tensor, csr) -> Tensor:
     """w_p / sum of w over p's segment, [n, 1] (static per interpolation plan; cached on the plan)."""
     hit = getattr(csr, "_coef", None)
     if hit is None or hit[0] != (w.data_ptr(), w._version):
-        deg = (csr.off[1:] - csr.off[:-1]).long()
-        seg = torch.repeat_interleave(torch.arange(csr.n_seg, device=w.device), deg)
-        wf = w.reshape(-1).float()
-        tot = torch.zeros(csr.n_seg, dtype=torch.float32, device=w.device).index_add_(0, seg, wf)
-        csr._coef = ((w.data_ptr(), w._version), (wf / tot[seg]).reshape(-1, 1).contiguous())
+        # the totals by the fixed-order segmented sum on the same plan (each segment's weights added in plan order, as the forward
+        # launch forms its denominator), handed back to the segment's rows: no atomics, the same bits in every run
+        wf = w.detach().reshape(-1, 1).float().contiguous()
+        tot = segment_broadcast(ops.segment_reduce(wf, csr, False), csr, False, int(wf.size(0)))
+        csr._coef = ((w.data_ptr(), w._version), (wf / tot).contiguous())
         hit = csr._coef
     return hit[1]
 
@@ -635,14 +639,18 @@ class _ProjectToEdges(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, v: Tensor, node32: Optional[Tensor], unit: Tensor, n_edges: int, n_feat: int):
-        ctx.args = (node32, unit, n_edges, n_feat, int(v.size(0)))
+        ctx.args = (node32, unit, n_edges, n_feat, int(v.size(0)), int(v.size(1)))
         return ops.project_to_edges(v, node32, unit, n_edges, n_feat)
 
     @staticmethod
     def backward(ctx, dout: Tensor):
-        node32, unit, n_edges, n_feat, n_v = ctx.args
+        node32, unit, n_edges, n_feat, n_v, v_cols = ctx.args
         tmp = (dout.unsqueeze(2) * unit.unsqueeze(1)).reshape(n_edges, 2 * n_feat)
         dv = tmp if node32 is None else ops.segment_reduce(tmp, plan.gather_csr(node32, n_v), False)
+        if tuple(dv.shape) != (n_v, v_cols):          # (the forward read a corner of a larger v: the rows / columns behind it get zero)
+            full = torch.zeros((n_v, v_cols), dtype=torch.float32, device=dv.device)
+            full[:int(dv.size(0)), :2 * n_feat] = dv
+            dv = full
         return dv, None, None, None, None
 
 

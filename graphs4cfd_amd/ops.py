@@ -290,6 +290,8 @@ def weighted_segment_mean(x: Tensor, x_idx32: Tensor, w: Tensor, csr: CsrPlan, o
         if out is not None:
             raise NotImplementedError("weighted_segment_mean(out=...) is not differentiable (autograd.weighted_segment_mean "
                                       "returns the full tensor)")
+        if out_idx32 is not None:         # (as without gradients: there is no `out` here whose rows it could name)
+            raise ValueError("out_idx32: scattered output rows need `out`")
         from . import autograd as _ag
         return _ag.weighted_segment_mean(x, x_idx32, w, csr)
     x = _f32_2d(x, "x")
@@ -340,6 +342,8 @@ def project_to_edges(v: Tensor, node32: Optional[Tensor], unit: Tensor, n_edges:
         raise ValueError(f"v: without node32 edge e reads row e, {n_edges} edges, got shape {tuple(v.shape)}")
     if node32 is not None and n_edges > 0 and int(v.size(0)) == 0:
         raise ValueError(f"v: node32 reads {n_edges} rows, got shape {tuple(v.shape)}")
+    if _ld(v) % 2 or v.data_ptr() % 8:          # (the launch reads (x, y) pairs as 8-byte loads: an odd row stride, a window at an odd column)
+        v = v[:, :2 * n_feat].contiguous()
     lib = _lib.load()
     dev = _lib.require_hip(v, node32, unit)
     out = torch.empty((n_edges, n_feat), dtype=torch.float32, device=dev)

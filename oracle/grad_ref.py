@@ -23,7 +23,11 @@ rows that hold a hidden pre-activation within its worst-case fp32 reach of 0 (|z
 other branch than fp64 must lie among them, and the tests count both.
 
 Perturbations (negative controls, applied to a reference's inputs only): `drop_row`, `move_boundary`, `swap_columns`,
-`zero_last_partial_row`, `flip_slope`."""
+`zero_last_partial_row`, `flip_slope`; for the linear adjoints of the multi-scale / REMuS path also `dedup_index`, `unmask_row`,
+`swap_unit_columns` (and a mean restated as a sum: the `mean` argument of the reference itself).
+
+Linear ops of the multi-scale, gMuS and REMuS models (autograd.py below _FusedMLP) and the blocks made of them: the section
+"linear adjoints" restates each op and its adjoint, "blocks" composes them with `mlp_forward` / `mlp_adjoint` the way `gnblock_*` do."""
 from __future__ import annotations
 
 import math
@@ -72,6 +76,25 @@ def assert_fp32_class(got: Tensor, ref: Tensor, absref: Tensor, n_eff: float, wh
     ratio = float((err / allow.clamp_min(1e-300)).max()) if err.numel() else 0.0
     STATS.append((what, ratio))
     print(f"  {what}: n_eff {n_eff:.0f}, max measured/allowed {ratio:.3e}")
+    return ratio
+
+
+REL_LARGEST = 2e-5                   # assert_rel_largest: what tests/test_gpu_train.py holds GNBlock's gradients to against float64 autograd
+
+
+def assert_rel_largest(got: Tensor, ref: Tensor, what: str = "", rel: float = REL_LARGEST) -> float:
+    """max |got - ref| <= rel * max |ref|: a whole tensor against its largest entry.  Beside `assert_fp32_class` where that bound is
+    loose: through a LayerNorm adjoint and two or three 128-term products of absolute values, c * u * n_eff * absref of a block's
+    gradient exceeds the gradient itself, so a row that is simply missing passes it; fp32 arithmetic itself stays some 1e-6 of the
+    largest entry away from fp64 on these blocks.  Returns measured / allowed (logged like the other ratios)."""
+    assert tuple(got.shape) == tuple(ref.shape), f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    if not ref.numel():
+        return 0.0
+    err, scale = float((got.to(F64) - ref.to(F64)).abs().max()), float(ref.to(F64).abs().max())
+    ratio = err / max(rel * scale, 1e-300)
+    print(f"  {what}: max |diff| {err:.3e}, largest entry {scale:.3e}, measured/allowed {ratio:.3e}")
+    assert err <= rel * scale, f"{what}: max |diff| {err:.3e} above {rel:g} of the largest entry {scale:.3e}"
+    STATS.append((what, ratio))
     return ratio
 
 
@@ -412,12 +435,15 @@ def mlp_forward(srcs: Sequence[Src], weights: Sequence[Tensor], biases: Sequence
 
 def mlp_adjoint(f: Forward, srcs: Sequence[Src], weights: Sequence[Tensor], ln=None, act: Optional[str] = None,
                 dy: Optional[Tensor] = None, acts: Optional[Sequence[Tensor]] = None, z_last: Optional[Tensor] = None,
-                resid: Optional[Tensor] = None, resid_col0: int = 0, dy_abs: Optional[Tensor] = None) -> Dict[str, Tuple[Tensor, Tensor]]:
+                resid: Optional[Tensor] = None, resid_col0: int = 0, dy_abs: Optional[Tensor] = None,
+                y_act: Optional[Tensor] = None) -> Dict[str, Tuple[Tensor, Tensor]]:
     """Every gradient of one launch: {"W{l}", "b{l}", "gamma", "beta", "src{j}", "resid", "D{l}"} -> (value, absolute-value form).
     `acts` (the kernel's saved SELU outputs, acts[l] = input rows of layer l for l >= 1) and `z_last` (its saved pre-LayerNorm rows):
     slopes and products are then taken on those fp32 rows — the backward is checked layer-locally; without them the fp64 forward
     supplies both, and the carried fp32 error of the recomputed activations is folded into the absolute-value form.  `dy_abs`: the
-    magnitude of an upstream gradient that carries fp32 error of its own (|dy| if None)."""
+    magnitude of an upstream gradient that carries fp32 error of its own (|dy| if None).  `y_act`: the activated fp32 rows the launch
+    wrote (before the residual) — the output activation's slope is then taken from them, as the backward does (a SELU output within an
+    ulp of 0 takes the launch's branch, not fp64's)."""
     L = len(weights)
     dy = dy.to(F64)
     out: Dict[str, Tuple[Tensor, Tensor]] = {}
@@ -427,7 +453,7 @@ def mlp_adjoint(f: Forward, srcs: Sequence[Src], weights: Sequence[Tensor], ln=N
         out["resid"] = (r, r.abs())
     g, ga = dy, (dy.abs() if dy_abs is None else dy_abs.to(F64))
     if act is not None:
-        y_act = _act(f.y0, act)
+        y_act = _act(f.y0, act) if y_act is None else y_act.to(F64)
         g = dy * act_slope(y_act, act, False)
         ga = ga * (act_slope_abs(y_act, act, False) + 2.0 * f.Y0)     # (+ the slope's change under y's fp32 error: 2 |y| dy <= 2 Y0 dy)
     own = acts is not None
@@ -534,4 +560,365 @@ def gnblock_adjoint(fe: Forward, fv: Forward, es, ns, edge_params, node_params, 
                 out[pre + k] = val
     out["e"] = ge["src0"]
     out["v"] = (gn["src1"][0] + ge["src1"][0] + ge["src2"][0], gn["src1"][1] + ge["src1"][1] + ge["src2"][1])
+    return out
+
+
+# ------------------------------------------------------------------ linear adjoints (autograd.py below _FusedMLP)
+# Each returns (value, the same computation on absolute values).  An adjoint takes the upstream gradient and, where that carries fp32
+# error of its own, its magnitude (`dout_abs`; |dout| if None).
+def _abs_of(d: Tensor, d_abs: Optional[Tensor]) -> Tensor:
+    return d.to(F64).abs() if d_abs is None else d_abs.to(F64)
+
+
+def _index_add(n: int, idx: Tensor, rows: Tensor) -> Tensor:
+    return torch.zeros((n, int(rows.size(1))), dtype=F64, device=rows.device).index_add_(0, idx.long().to(rows.device), rows)
+
+
+def gather_rows_adjoint(dout: Tensor, idx: Tensor, n: int, dout_abs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Adjoint of out = x[idx] for x [n, w]: row r of dx = the sum of the rows p of dout with idx[p] == r; a row never read gets +0."""
+    return _index_add(n, idx, dout.to(F64)), _index_add(n, idx, _abs_of(dout, dout_abs))
+
+
+def act_terms_abs(x: Tensor, act: Optional[str]) -> Tensor:
+    """Magnitude of the terms of the kernels' activation formulas (g4c_common.h selu_f / tanh_f): SELU = scale * max(x, 0) +
+    (scale alpha e - scale alpha) with e = exp(min(x, 0)), tanh = 1 - 2 / (exp(2 |x|) + 1).  Near 0 both cancel, so the bound there is
+    absolute, not relative to the value."""
+    x = x.to(F64)
+    if act is None:
+        return x.abs()
+    if act == "selu":
+        return SELU_SCALE * x.clamp(min=0.0) + SELU_SA * (torch.exp(x.clamp(max=0.0)) + 1.0)
+    if act == "tanh":
+        return 1.0 + 2.0 / (torch.exp(2.0 * x.abs().clamp(max=20.0)) + 1.0)
+    raise ValueError(act)
+
+
+def segment_reduce(src: Tensor, off: Tensor, perm: Optional[Tensor], mean: bool, act: Optional[str] = None,
+                   src_act: Optional[str] = None) -> Tuple[Tensor, Tensor]:
+    """act(sum | mean of src_act(src[perm[p]]) over segment s) — ops.segment_reduce.  Magnitude: the terms of `src_act`'s formula
+    summed like the rows; through `act` a value s with magnitude S carries L S + the terms of act's formula at s (L the activation's
+    Lipschitz constant: scale * alpha for SELU, 1 for tanh)."""
+    x = src.to(F64)
+    out, mag = segment_sum(_act(x, src_act), off, perm, mean), segment_sum(act_terms_abs(x, src_act), off, perm, mean)
+    if act is None:
+        return out, mag
+    return _act(out, act), (SELU_SA if act == "selu" else 1.0) * mag + act_terms_abs(out, act)
+
+
+def segment_reduce_adjoint(dout: Tensor, src: Tensor, out: Tensor, off: Tensor, perm: Optional[Tensor], mean: bool,
+                           act: Optional[str] = None, src_act: Optional[str] = None, dout_abs: Optional[Tensor] = None):
+    """Adjoint of `segment_reduce` with respect to src [n_src, w]: dout times the slope of `act` at the given fp32 output rows `out`,
+    handed to every row of the segment (divided by the segment's length for a mean), times the slope of `src_act` at the given fp32
+    input; rows of no segment get +0."""
+    n_src = int(src.size(0))
+    g, ga = act_grad(dout, out, act, False)
+    if dout_abs is not None:
+        ga = dout_abs.to(F64) * act_slope_abs(out, act, False)
+    gs = segment_broadcast(g, off, perm, n_src, mean, fp32=False)
+    gsa = segment_broadcast(ga, off, perm, n_src, mean, fp32=False)
+    return gs * act_slope(src, src_act, True), gsa * act_slope_abs(src, src_act, True)
+
+
+def segment_totals_sequential(w: Tensor, off: Tensor) -> Tensor:
+    """fp32 totals of w over each segment, added one after the other in segment order starting from +0 (what a lane of
+    g4c_segment_reduce / g4c_weighted_segment_mean computes): [n_seg] fp32."""
+    w = w.detach().reshape(-1).to(torch.float32).cpu()
+    off = off.long().cpu()
+    lens = off[1:] - off[:-1]
+    tot = torch.zeros(int(lens.numel()), dtype=torch.float32)
+    for j in range(int(lens.max()) if lens.numel() else 0):
+        on = lens > j
+        tot[on] = tot[on] + w[off[:-1][on] + j]               # (one fp32 addition per step: IEEE, no re-association)
+    return tot
+
+
+def segment_coefficients(w: Tensor, off: Tensor) -> Tensor:
+    """w_p / (sum of w over p's segment) as fp32 [n, 1]: the total by `segment_totals_sequential`, then one fp32 division — the value
+    autograd._segment_coefficients holds, bit for bit."""
+    w32 = w.detach().reshape(-1).to(torch.float32).cpu()
+    tot = segment_totals_sequential(w32, off)
+    return (w32 / tot[_seg_ids(off)]).reshape(-1, 1)
+
+
+def weighted_mean(x: Tensor, x_idx: Tensor, w: Tensor, off: Tensor, n_out: Optional[int] = None,
+                  out_idx: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """knn_interpolate: row s = sum_p w_p x[x_idx[p]] / sum_p w_p over segment s (rows in segment order); with `out_idx` row s lands
+    at out_idx[s] of a zero [n_out, w] tensor.  (A segment without rows is 0 / 0 here as in the reference: the plans have none.)"""
+    dev = x.device
+    seg = _seg_ids(off).to(dev)
+    n_seg = int(off.numel()) - 1
+    wd = w.reshape(-1, 1).to(F64).to(dev)
+    xr = x.to(F64)[x_idx.long().to(dev)]
+    den = _index_add(n_seg, seg, wd.abs())
+    rows, mag = _index_add(n_seg, seg, xr * wd) / den, _index_add(n_seg, seg, xr.abs() * wd.abs()) / den
+    if out_idx is None and (n_out is None or n_out == n_seg):
+        return rows, mag
+    full, fulla = (torch.zeros((int(n_out), int(x.size(1))), dtype=F64, device=dev) for _ in range(2))
+    o = torch.arange(n_seg, device=dev) if out_idx is None else out_idx.long().to(dev)
+    full[o], fulla[o] = rows, mag
+    return full, fulla
+
+
+def weighted_mean_adjoint(dout: Tensor, x_idx: Tensor, w: Tensor, off: Tensor, n_x: int, out_idx: Optional[Tensor] = None,
+                          dout_abs: Optional[Tensor] = None, coef: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Adjoint of `weighted_mean` with respect to x [n_x, w]: dx[r] = sum over p with x_idx[p] == r of (w_p / total) dout[row of p's
+    segment]; output rows `out_idx` does not name pass nothing.  `coef`: the coefficients to use instead of w / total in fp64."""
+    dev = dout.device
+    seg = _seg_ids(off).to(dev)
+    n_seg = int(off.numel()) - 1
+    d, da = dout.to(F64), _abs_of(dout, dout_abs)
+    o = torch.arange(n_seg, device=dev) if out_idx is None else out_idx.long().to(dev)
+    d, da = d[o], da[o]
+    if coef is None:
+        wd = w.reshape(-1, 1).to(F64).to(dev)
+        coef = wd / _index_add(n_seg, seg, wd)[seg]
+    coef = coef.reshape(-1, 1).to(F64).to(dev)
+    return _index_add(n_x, x_idx.to(dev), d[seg] * coef), _index_add(n_x, x_idx.to(dev), da[seg] * coef.abs())
+
+
+def project_to_edges(v: Tensor, node: Optional[Tensor], unit: Tensor, n_feat: int, v_abs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(v[node][:, :2F].view(E, F, 2) * unit[:, None]).sum(-1); without `node` edge e reads row e."""
+    E = int(unit.size(0))
+    u = unit.to(F64)
+    rows = v.to(F64) if node is None else v.to(F64)[node.long()]
+    mag = _abs_of(v, v_abs) if node is None else _abs_of(v, v_abs)[node.long()]
+    rows, mag = rows[:E, :2 * n_feat].reshape(E, n_feat, 2), mag[:E, :2 * n_feat].reshape(E, n_feat, 2)
+    return (rows * u[:, None]).sum(-1), (mag * u.abs()[:, None]).sum(-1)
+
+
+def project_to_edges_adjoint(dout: Tensor, node: Optional[Tensor], unit: Tensor, v_shape: Sequence[int],
+                             dout_abs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Adjoint with respect to v of shape `v_shape`: dv[node[e], 2f + c] += dout[e, f] unit[e, c]; rows and columns the forward did
+    not read get +0."""
+    E, n_feat = int(dout.size(0)), int(dout.size(1))
+    u = unit.to(F64)
+    t = (dout.to(F64)[:, :, None] * u[:, None, :]).reshape(E, 2 * n_feat)
+    ta = (_abs_of(dout, dout_abs)[:, :, None] * u.abs()[:, None, :]).reshape(E, 2 * n_feat)
+    dv, dva = (torch.zeros(tuple(v_shape), dtype=F64, device=dout.device) for _ in range(2))
+    if node is None:
+        dv[:E, :2 * n_feat], dva[:E, :2 * n_feat] = t, ta
+    else:
+        dv[:, :2 * n_feat], dva[:, :2 * n_feat] = _index_add(int(v_shape[0]), node, t), _index_add(int(v_shape[0]), node, ta)
+    return dv, dva
+
+
+def edge_scalar_to_node_vector(e: Tensor, unit_inv: Tensor, k: int, e_abs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """out[n, 2 f + c] = sum_j unit_inv[n, c, j] e[n k + j, f] (feature-major flatten of unit_inv @ e.view(n, k, F))."""
+    n, F_ = int(unit_inv.size(0)), int(e.size(1))
+    ui = unit_inv.to(F64).reshape(n, 2, k)
+    out = (ui @ e.to(F64).reshape(n, k, F_)).transpose(1, 2).reshape(n, 2 * F_)
+    mag = (ui.abs() @ _abs_of(e, e_abs).reshape(n, k, F_)).transpose(1, 2).reshape(n, 2 * F_)
+    return out, mag
+
+
+def edge_scalar_to_node_vector_adjoint(dout: Tensor, unit_inv: Tensor, k: int, dout_abs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Adjoint with respect to e [n k, F]: de[n k + j, f] = sum_c unit_inv[n, c, j] dout[n, 2 f + c]."""
+    n = int(unit_inv.size(0))
+    F_ = int(dout.size(1)) // 2
+    ui = unit_inv.to(F64).reshape(n, 2, k)
+    d = dout.to(F64).reshape(n, F_, 2).transpose(1, 2)                     # [n, 2, F]
+    da = _abs_of(dout, dout_abs).reshape(n, F_, 2).transpose(1, 2)
+    return (ui.transpose(1, 2) @ d).reshape(n * k, F_), (ui.abs().transpose(1, 2) @ da).reshape(n * k, F_)
+
+
+# n_eff of these launches, counted from segment_reduce.hip / remus_ops.hip / train_ops.hip and the torch products of autograd.py
+def n_eff_segment_reduce(max_deg: int, mean: bool, act: Optional[str] = None, src_act: Optional[str] = None) -> int:
+    """One lane adds the segment's rows in order (max_deg roundings), one division for a mean, N_EFF_ACT per activation."""
+    return max(max_deg, 1) + (1 if mean else 0) + (N_EFF_ACT if act else 0) + (N_EFF_ACT if src_act else 0)
+
+
+def n_eff_segment_reduce_adjoint(mean: bool, act: Optional[str] = None, src_act: Optional[str] = None) -> int:
+    """No sum: the slope products (N_EFF_ACT each), and for a mean the fp32 reciprocal of the length and its product (2)."""
+    return 1 + (2 if mean else 0) + (N_EFF_ACT if act else 0) + (N_EFF_ACT if src_act else 0)
+
+
+def n_eff_weighted_mean(k: int) -> int:
+    """k products and k additions of the numerator (rounded separately at worst), k additions of the denominator, the quotient."""
+    return 3 * k + 1
+
+
+def n_eff_weighted_mean_adjoint(k: int, max_mult: int) -> int:
+    """The coefficient (k additions of the total, the quotient), its product with the gradient row, then the segmented sum over the
+    positions that read one row of x (max_mult additions in order)."""
+    return k + 2 + max(max_mult, 1)
+
+
+N_EFF_PROJECT = 3                    # project_to_edges_kernel: two products and a sum, rounded separately
+
+
+def n_eff_project_adjoint(max_mult: int) -> int:
+    """One product per element, then (through an index) the segmented sum over the edges of a node."""
+    return 1 + max(max_mult, 1)
+
+
+def n_eff_e2n(k: int) -> int:
+    """edge_scalar_to_node_vector_kernel: k fused multiply-adds in order."""
+    return k
+
+
+# ------------------------------------------------------------------ perturbations of the linear adjoints
+def dedup_index(idx: Tensor) -> Tuple[Tensor, Tensor]:
+    """A duplicated gather index counted once: (positions kept, their indices) with every row of x named by one position only."""
+    i = idx.long().cpu()
+    first = torch.ones_like(i, dtype=torch.bool)
+    order = torch.argsort(i, stable=True)
+    s = i[order]
+    first[order[1:]] = s[1:] != s[:-1]
+    keep = first.nonzero().reshape(-1)
+    return keep.to(idx.device), idx[keep.to(idx.device)]
+
+
+def unmask_row(out_idx: Tensor, n_out: int) -> Tensor:
+    """A masked output row given gradient: the last named row replaced by a row the mask does not name."""
+    named = torch.zeros(n_out, dtype=torch.bool)
+    named[out_idx.long().cpu()] = True
+    free = (~named).nonzero().reshape(-1)
+    o = out_idx.clone()
+    o[-1] = int(free[-1])
+    return o
+
+
+def swap_unit_columns(unit: Tensor) -> Tensor:
+    """The two columns of every unit vector swapped."""
+    return unit.flip(-1)
+
+
+# ------------------------------------------------------------------ blocks (nn/blocks.py other than MLP / GNBlock)
+def _grads(pre: str, gr: Dict[str, Tuple[Tensor, Tensor]], out: Dict[str, Tuple[Tensor, Tensor]]) -> None:
+    for k, val in gr.items():
+        if k[0] in "Wbg":            # W{l}, b{l}, gamma, beta
+            out[pre + k] = val
+
+
+def mp_forward(v: Tensor, e: Tensor, row: Tensor, col: Tensor, msg_params, upd_params, v_src: Optional[Tensor] = None,
+               e_pre_act: Optional[str] = None, act: Optional[str] = None, split: str = "bf16x6"):
+    """The shared body of GNBlock / EdgeMP / DownEdgeMP (blocks._mp_step, mean aggregation): e' = msg([pre_act(e) | s[row] | v[col]])
+    with senders s = v_src or v, v' = act(upd([mean of e' over col | v])).  `gnblock_forward` is this with no activations and
+    v_src None; EdgeMP reads (e, a, angle_index) for (v, e, edge_index), DownEdgeMP (e2, a12, angle_index12) with v_src = e1.
+    Returns (message Forward, update Forward, message sources, update sources)."""
+    n = int(v.size(0))
+    perm = torch.argsort(col, stable=True)
+    off = torch.zeros(n + 1, dtype=torch.int64, device=v.device)
+    off[1:] = torch.cumsum(torch.bincount(col, minlength=n), 0)
+    ms = [Src(e, pre_act=e_pre_act), Src(v if v_src is None else v_src, index=row), Src(v, index=col)]
+    fm = mlp_forward(ms, *msg_params, split=split)
+    us = [Src(fm.y, segments=(off, perm), seg_mean=True, xa=fm.Y0), Src(v)]
+    fu = mlp_forward(us, *upd_params, act=act, split=split)
+    return fm, fu, ms, us
+
+
+def mp_adjoint(fm: Forward, fu: Forward, ms, us, msg_params, upd_params, dv: Tensor, de: Optional[Tensor], act: Optional[str] = None,
+               msg_own=(None, None), upd_own=(None, None), v_act: Optional[Tensor] = None):
+    """Gradients of <dv, v'> + <de, e'> (de None: e' is read by nobody): {"msg.*", "upd.*", "v", "e", "v_src"} -> (value,
+    absolute-value form); "v_src" only when the senders are another tensor.  `*_own` = (acts, z_last) of each launch's backward,
+    `v_act` = the activated fp32 v' the update launch wrote (mlp_adjoint)."""
+    gu = mlp_adjoint(fu, us, upd_params[0], upd_params[2], act, dv, acts=upd_own[0], z_last=upd_own[1], y_act=v_act)
+    d_e, d_ea = gu["src0"]
+    if de is not None:
+        d_e, d_ea = d_e + de.to(F64), d_ea + de.to(F64).abs()
+    gm = mlp_adjoint(fm, ms, msg_params[0], msg_params[2], None, d_e, dy_abs=d_ea, acts=msg_own[0], z_last=msg_own[1])
+    out: Dict[str, Tuple[Tensor, Tensor]] = {}
+    _grads("msg.", gm, out)
+    _grads("upd.", gu, out)
+    out["e"] = gm["src0"]
+    if ms[1].x is ms[2].x:
+        out["v"] = (gu["src1"][0] + gm["src1"][0] + gm["src2"][0], gu["src1"][1] + gm["src1"][1] + gm["src2"][1])
+    else:
+        out["v"] = (gu["src1"][0] + gm["src2"][0], gu["src1"][1] + gm["src2"][1])
+        out["v_src"] = gm["src1"]
+    return out
+
+
+edge_mp_forward, edge_mp_adjoint = mp_forward, mp_adjoint          # EdgeMP: a GNBlock with (edges, angles) for (nodes, edges)
+
+
+def down_edge_mp_forward(e1: Tensor, e2: Tensor, a12: Tensor, row: Tensor, col: Tensor, angle_params, edge_params,
+                         act: Optional[str] = None, split: str = "bf16x6"):
+    """DownEdgeMP: senders are the fine edges e1[row], receivers the coarse edges e2[col]; only e2' leaves the block."""
+    return mp_forward(e2, a12, row, col, angle_params, edge_params, v_src=e1, act=act, split=split)
+
+
+def down_edge_mp_adjoint(fm, fu, ms, us, angle_params, edge_params, de2: Tensor, act: Optional[str] = None, **own):
+    """{"msg.*" (angle MLP), "upd.*" (edge MLP), "e1", "e2", "a12"}."""
+    g = mp_adjoint(fm, fu, ms, us, angle_params, edge_params, de2, None, act, **own)
+    g["e1"], g["e2"], g["a12"] = g.pop("v_src"), g.pop("v"), g.pop("e")
+    return g
+
+
+def pool_edge(edge_attr: Tensor, off: Tensor, perm: Optional[Tensor], mean: bool = True, src_act: Optional[str] = None):
+    """The feature part of pool_edge: coarse edge s = mean | sum of src_act(edge_attr[perm[p]]) over the fine edges of segment s of
+    the pooling plan (fine edges inside one cluster are in no segment)."""
+    return segment_reduce(edge_attr, off, perm, mean, None, src_act)
+
+
+def pool_edge_adjoint(dout: Tensor, edge_attr: Tensor, off: Tensor, perm: Optional[Tensor], mean: bool = True,
+                      src_act: Optional[str] = None):
+    return segment_reduce_adjoint(dout, edge_attr, dout, off, perm, mean, None, src_act)
+
+
+def down_mp_forward(rel: Tensor, field: Tensor, cluster, params, split: str = "bf16x6") -> Tuple[Forward, List[Src], Tensor, Tensor]:
+    """DownMP's node part before its activation: m = down_mlp([rel | field]), pooled = mean of m over the clusters of the plan
+    `cluster` = (off, perm).  Returns (Forward of the MLP, its sources, pooled rows, their magnitude)."""
+    srcs = [Src(rel), Src(field)]
+    f = mlp_forward(srcs, *params, split=split)
+    return f, srcs, segment_sum(f.y, cluster[0], cluster[1], True), segment_sum(f.Y0, cluster[0], cluster[1], True)
+
+
+def down_mp_adjoint(f: Forward, srcs, params, cluster, dpooled: Tensor, pooled_out: Tensor, act: Optional[str] = None, own=(None, None)):
+    """{"W*", "b*", "gamma", "beta", "rel", "field"} of <dpooled, act(pooled)>; the activation's slope at the given fp32 output."""
+    n = int(f.X.size(0))
+    g, ga = act_grad(dpooled, pooled_out, act, False)
+    dm = segment_broadcast(g, cluster[0], cluster[1], n, True, fp32=False)
+    dma = segment_broadcast(ga, cluster[0], cluster[1], n, True, fp32=False)
+    gr = mlp_adjoint(f, srcs, params[0], params[2], None, dm, dy_abs=dma, acts=own[0], z_last=own[1])
+    out: Dict[str, Tuple[Tensor, Tensor]] = {}
+    _grads("", gr, out)
+    out["rel"], out["field"] = gr["src0"], gr["src1"]
+    return out
+
+
+def up_mp_forward(rel: Tensor, field_lr: Tensor, parent: Tensor, field_hr_old: Tensor, params, act: Optional[str] = None,
+                  split: str = "bf16x6") -> Tuple[Forward, List[Src]]:
+    """UpMP: act(up_mlp([-rel | field_lr[parent] | field_hr_old]))."""
+    srcs = [Src(rel, negate=True), Src(field_lr, index=parent), Src(field_hr_old)]
+    return mlp_forward(srcs, *params, act=act, split=split), srcs
+
+
+def up_mp_adjoint(f: Forward, srcs, params, dy: Tensor, act: Optional[str] = None, own=(None, None), y_act: Optional[Tensor] = None):
+    """{"W*", "b*", "gamma", "beta", "rel", "field_lr", "field_hr_old"}."""
+    gr = mlp_adjoint(f, srcs, params[0], params[2], act, dy, acts=own[0], z_last=own[1], y_act=y_act)
+    out: Dict[str, Tuple[Tensor, Tensor]] = {}
+    _grads("", gr, out)
+    out["rel"], out["field_lr"], out["field_hr_old"] = gr["src0"], gr["src1"], gr["src2"]
+    return out
+
+
+def up_edge_mp_forward(edge_attr2: Tensor, unit_inv2: Tensor, k: int, x_idx: Tensor, w: Tensor, off: Tensor, n_total: int,
+                       out_idx: Optional[Tensor], col1: Tensor, unit1: Tensor, edge_attr1: Tensor, params, act: Optional[str] = None,
+                       split: str = "bf16x6"):
+    """UpEdgeMP: coarse edge scalars -> node vectors (edge_scalar_to_node_vector), interpolated to the fine nodes (weighted_mean; the
+    rows `out_idx` names of a zero [n_total, 2F] tensor), projected on the fine edges (project_to_edges through their receivers `col1`),
+    then act(up_mlp([projection | edge_attr1])).  Returns (Forward, sources)."""
+    F_ = int(edge_attr2.size(1))
+    v2, v2a = edge_scalar_to_node_vector(edge_attr2, unit_inv2, k)
+    v1, v1a = weighted_mean(v2, x_idx, w, off, n_total, out_idx)
+    v1a = weighted_mean(v2a, x_idx, w, off, n_total, out_idx)[0]
+    p, pa = project_to_edges(v1, col1, unit1, F_, v_abs=v1a)
+    srcs = [Src(p, xa=pa), Src(edge_attr1)]
+    return mlp_forward(srcs, *params, act=act, split=split), srcs
+
+
+def up_edge_mp_adjoint(f: Forward, srcs, params, dy: Tensor, unit_inv2: Tensor, k: int, x_idx: Tensor, w: Tensor, off: Tensor,
+                       n_total: int, out_idx: Optional[Tensor], col1: Tensor, unit1: Tensor, act: Optional[str] = None,
+                       own=(None, None), y_act: Optional[Tensor] = None):
+    """{"W*", "b*", "gamma", "beta", "edge_attr1", "edge_attr2"}: the MLP's adjoint, then the three linear adjoints in turn."""
+    gr = mlp_adjoint(f, srcs, params[0], params[2], act, dy, acts=own[0], z_last=own[1], y_act=y_act)
+    out: Dict[str, Tuple[Tensor, Tensor]] = {}
+    _grads("", gr, out)
+    out["edge_attr1"] = gr["src1"]
+    n2 = int(unit_inv2.size(0))
+    F_ = int(gr["src0"][0].size(1))
+    dv1, dv1a = project_to_edges_adjoint(gr["src0"][0], col1, unit1, (n_total, 2 * F_), dout_abs=gr["src0"][1])
+    dv2, dv2a = weighted_mean_adjoint(dv1, x_idx, w, off, n2, out_idx, dout_abs=dv1a)
+    out["edge_attr2"] = edge_scalar_to_node_vector_adjoint(dv2, unit_inv2, k, dout_abs=dv2a)
     return out
