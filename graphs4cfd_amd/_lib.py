@@ -89,6 +89,12 @@ class g4c_rollout_rec_t(C.Structure):
                 ("scratch", C.c_void_p)]
 
 
+class g4c_rollout_moments_t(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("stride", C.c_int32), ("window", C.c_void_p), ("sub", C.c_void_p), ("sub_ld", C.c_int32),
+                ("plane_ld", C.c_int64), ("pivot", C.c_void_p), ("sum", C.c_void_p), ("sum2", C.c_void_p), ("lo", C.c_void_p),
+                ("hi", C.c_void_p)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -127,6 +133,7 @@ _SIGNATURES = {
     "g4c_rollout_record_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
     "g4c_rollout_advance_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_rec_t),
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    "g4c_rollout_moments": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_moments_t), C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

@@ -192,20 +192,39 @@ class GNN(nn.Module):
             return ro.result()       # (reports a clip of the default arithmetic in this model's own launches)
 
     def evaluate(self, graph: Union[Graph, List[Graph]], n_out: Optional[int] = None, *, every: int = 0, probes: Optional[torch.Tensor] = None,
-                 capture: Optional[bool] = None) -> "RolloutErrors":
+                 capture: Optional[bool] = None, moments=None, error_moments=None) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
         predictions of every step are not held.  every = k > 0 also keeps the snapshots solve(every=k)
         returns (`.snapshots`), probes (1-D integer tensor of node rows) the prediction's time series there (`.probes`,
-        [P, num_fields * n_out]).  A list of graphs is collated as in `solve`."""
+        [P, num_fields * n_out]).  moments / error_moments (None, True, `start` or `(start, stride)`, as in `Rollout`) also attach the
+        per-node time statistics of the prediction / of prediction − target (`.moments` / `.error_moments`: `RolloutMoments`).
+        A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
             n_out = int(target.size(1)) // int(self.num_fields)
         assert n_out > 0, "n_out must be greater than 0."
-        with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True) as ro:
+        with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True, moments=moments,
+                           error_moments=error_moments) as ro:
             ro.run(n_out)
-            return ro.errors()
+            errs = ro.errors()
+            errs.moments = ro.moments() if ro._moments is not None else None
+            errs.error_moments = ro.error_moments() if ro._error_moments is not None else None
+            return errs
+
+    def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
+                        capture: Optional[bool] = None) -> "RolloutMoments":
+        """Roll the model out for n_out steps and return the time statistics of the prediction at every node (`RolloutMoments`: mean,
+        cov / var / std of the fields, per-node min and max) over the steps discard, discard + stride, ... < n_out (0-based),
+        accumulated on the device inside the step in fp64.  No prediction is held (every = 0); every = k > 0 also keeps the
+        snapshots solve(every=k) returns (`.snapshots`).  A list of graphs is collated as in `solve`."""
+        assert n_out > 0, "n_out must be greater than 0."
+        with self._rollout(graph, n_out, capture, "time_statistics()", every=int(every), moments=(discard, stride)) as ro:
+            ro.run(n_out)
+            mo = ro.moments()
+            mo.snapshots = ro.result() if int(every) else None
+            return mo
 
     def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
         """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
@@ -354,7 +373,7 @@ class Rollout:
 
     def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
                  label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
-                 mask: Optional[torch.Tensor] = None):
+                 mask: Optional[torch.Tensor] = None, moments=None, error_moments=None):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -364,7 +383,17 @@ class Rollout:
         `every` = k: keep steps k - 1, 2k - 1, ... (0-based) only — `result()` is [N, nf * (max_steps // k)] and the buffer has
         max_steps // k slots; 0 keeps none (`result()` raises).  `probes`: 1-D integer tensor of node rows (repeats allowed) —
         `probes()` is their predictions at every step, [P, nf * max_steps].  `target` [N, >= nf * max_steps] (and `mask` [N] bool:
-        the Dirichlet nodes): `errors()` is the error of every step against it (`RolloutErrors`).  Rows are the caller's numbering."""
+        the Dirichlet nodes): `errors()` is the error of every step against it (`RolloutErrors`).  Rows are the caller's numbering.
+
+        Time statistics at every node (opt-in, and no record in the sense above: the step keeps the closing launch it would have
+        had, one `g4c_rollout_moments` launch per statistic goes in front of it): `moments` — of the prediction — and
+        `error_moments` — of prediction − target, needs `target=` — are each None, True (every step), `start` (steps start,
+        start + 1, ...) or `(start, stride)` (steps start, start + stride, ...; 0-based).  `moments()` / `error_moments()` return
+        them (`RolloutMoments`); after `rewind()` or a recomputation they hold the steps taken since."""
+        window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
+        error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
+        if error_window is not None and target is None:
+            raise ValueError("error_moments: the statistics of prediction - target need target=")
         _lib.require_hip(graph.field)
         recording = _check_records(graph, int(model.num_fields), int(max_steps), every, probes, target, mask)
         self._caller_graph, self._perm = graph, None
@@ -400,6 +429,8 @@ class Rollout:
         self._field0 = self.field.clone()        # the input window of slot `_first_slot`
         self._first_slot = 0
         self.exact_range = False                 # True once a clip made this rollout fall back to "bf16x6"
+        self._moments = None if window is None else _Moments(self, *window)
+        self._error_moments = None if error_window is None else _Moments(self, *error_window, sub=self._rec.target)
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -412,6 +443,9 @@ class Rollout:
     def _one(self):
         with self.static, self.flags:
             pred = self.model.forward(self.graph, self.steps_done)
+        for mo in (self._moments, self._error_moments):       # (they read the step index the closing launch below bumps)
+            if mo is not None:
+                mo.accumulate(pred, self.step_counter)
         if self._rec is not None:
             self._rec.advance(self.field, pred, self.step_counter)
             return
@@ -469,6 +503,7 @@ class Rollout:
             self.step_counter[:1].fill_(1)
         self._field0.copy_(self.field)            # (a recomputation restarts here)
         self._first_slot = self.steps_done
+        self._reset_moments()
 
     def _recompute_exact(self, hit) -> None:
         """Steps `_first_slot .. steps_done` again from the saved input window in "bf16x6"; the rollout stays in that arithmetic."""
@@ -484,6 +519,7 @@ class Rollout:
             self.step_counter[:1].fill_(self._first_slot)
         self._hipgraph, self._epoch = None, -1
         self.steps_done = self._first_slot
+        self._reset_moments()
         field, self.graph.field = self.graph.field, self.field        # (after close() the graph holds its own field again)
         try:
             self.run(n)
@@ -531,6 +567,27 @@ class Rollout:
                              snapshots=self.result() if self._out_steps is not None else None,
                              probes=ops.steps_to_columns(rec.probe_out) if rec.probe_out is not None else None)
 
+    def _reset_moments(self) -> None:
+        for mo in (self._moments, self._error_moments):
+            if mo is not None:
+                mo.reset(self._first_slot)
+
+    def _read_moments(self, mo: Optional["_Moments"], name: str) -> "RolloutMoments":
+        if mo is None:
+            raise RuntimeError(f"{self.label}: no {name}= were asked for")
+        self.validate()
+        return mo.read(self._perm)
+
+    def moments(self) -> "RolloutMoments":
+        """The time statistics of the prediction at every node over the window `moments=` asked for (`RolloutMoments`, fp64 device
+        tensors in the caller's rows) — validated first, like `result()`; one device -> host copy of two integers."""
+        return self._read_moments(self._moments, "moments")
+
+    def error_moments(self) -> "RolloutMoments":
+        """The same of prediction − target over the window `error_moments=` asked for: `mean` is the bias field, `mean² + var` the
+        mean-square error at every node."""
+        return self._read_moments(self._error_moments, "error_moments")
+
     def close(self) -> None:
         self.graph.field = self._orig_field
 
@@ -570,6 +627,129 @@ def _check_records(graph: Graph, nf: int, max_steps: int, every, probes, target,
         if tuple(mask.shape) != (n,):
             raise ValueError(f"mask: expected shape ({n},), got {tuple(mask.shape)}")
     return every != 1 or probes is not None or target is not None
+
+
+def _check_moments(name: str, spec, nf: int, max_steps: int):
+    """A `moments=` / `error_moments=` argument of `Rollout` -> (start, stride), or None when the statistic is not asked for."""
+    def integer(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        start, stride = 0, 1
+    elif integer(spec):
+        start, stride = spec, 1
+    elif isinstance(spec, (tuple, list)) and len(spec) == 2 and all(integer(v) for v in spec):
+        start, stride = spec
+    else:
+        raise TypeError(f"{name}: expected None, True, an integer start or a pair of integers (start, stride), got {spec!r}")
+    if start < 0 or start >= max_steps:
+        raise ValueError(f"{name}: start {start} of a rollout of {max_steps} steps (0 <= start < max_steps)")
+    if stride < 1:
+        raise ValueError(f"{name}: stride {stride} (>= 1)")
+    if nf > _lib.REC_MAX_NF:
+        raise NotImplementedError(f"{name}: the time statistics cover models of up to {_lib.REC_MAX_NF} fields, this one has {nf}")
+    return int(start), int(stride)
+
+
+class _Moments:
+    """The accumulators of one per-node time statistic of a `Rollout` and the launch that updates them.  Allocated once, in the
+    rollout's node numbering: one fp64 buffer of 4 nf + nf (nf + 1) / 2 planes of N (pivot, sum, sum2, min, max) and the device-side
+    window {origin, last}.  The captured launch reads the origin on the device, so `reset()` — a two-integer fill on the stream,
+    outside the graph — is all `rewind()` and a recomputation need: the step that finds itself at the origin stores the
+    accumulators without reading them."""
+
+    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None):
+        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf
+        self.nf, self.max_steps, self.start, self.stride, self.sub = nf, ro.max_steps, start, stride, sub
+        pairs = ops.moment_pairs(nf)
+        self.planes = torch.zeros((4 * nf + pairs, n), dtype=torch.float64, device=dev)
+        self.pivot, self.sum, self.sum2, self.lo, self.hi = self.planes.split((nf, nf, pairs, nf, nf))
+        self.window = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.reset(ro._first_slot)
+
+    def reset(self, first_slot: int) -> None:
+        """origin = the first step of the lattice start, start + stride, ... at or after `first_slot`; nothing accumulated yet."""
+        behind = max(first_slot - self.start, 0)
+        self.origin = self.start + -(-behind // self.stride) * self.stride
+        self.window[:1].fill_(self.origin)
+        self.window[1:].fill_(-1)
+
+    def accumulate(self, pred, step) -> None:
+        ops.rollout_moments(pred, step, self.nf, self.max_steps, self.window, self.pivot, self.sum, self.sum2, self.lo, self.hi,
+                            stride=self.stride, sub=self.sub)
+
+    def read(self, perm) -> "RolloutMoments":
+        origin, last = self.window.tolist()
+        count = (last - origin) // self.stride + 1 if last >= origin else 0
+
+        def rows(planes):                       # [planes, N] in the rollout's numbering -> [N, planes] in the caller's
+            cols = planes.t().contiguous()
+            if perm is None:
+                return cols
+            out = torch.empty_like(cols)
+            out[perm] = cols
+            return out
+
+        return RolloutMoments(count, origin, self.stride, rows(self.pivot), rows(self.sum), rows(self.sum2), rows(self.lo), rows(self.hi))
+
+
+class RolloutMoments:
+    """Per-node time statistics of a rollout (`Rollout.moments()` / `error_moments()`, `GNN.time_statistics()`, `GNN.evaluate(moments=)`)
+    over the `count` steps origin, origin + stride, ...: the raw fp64 sums, as the device accumulated them — `pivot` [N, nf] (the
+    first sample), `sum` [N, nf] = Σ d, `sum2` [N, nf (nf + 1) / 2] = Σ d_f d_g over the pairs (0,0), (0,1), ..., (0,nf-1), (1,1), ...,
+    with d = sample − pivot, and `min`, `max` [N, nf] of the samples — and, from them, `mean` = pivot + Σd / count, `cov`
+    [N, nf, nf] = Σ d_f d_g / count − (Σd_f / count)(Σd_g / count) (symmetric, population-normalised; the shift by the first sample
+    keeps it well-conditioned when the mean is far larger than the fluctuation), `var` = its diagonal, `std` = √max(var, 0).
+    `count == 0` (no step of the window was taken) raises on the derived quantities.  Works on tensors of any device.
+    `snapshots`: the rollout's `result()` when `GNN.time_statistics(every=)` kept any, else None."""
+
+    def __init__(self, count: int, origin: int, stride: int, pivot: torch.Tensor, sum: torch.Tensor, sum2: torch.Tensor,
+                 min: torch.Tensor, max: torch.Tensor, snapshots: Optional[torch.Tensor] = None):
+        nf = int(pivot.size(-1))
+        pairs = nf * (nf + 1) // 2
+        for t, name, width in ((pivot, "pivot", nf), (sum, "sum", nf), (sum2, "sum2", pairs), (min, "min", nf), (max, "max", nf)):
+            if t.dim() != 2 or tuple(t.shape) != (int(pivot.size(0)), width):
+                raise ValueError(f"{name}: expected shape ({int(pivot.size(0))}, {width}), got {tuple(t.shape)}")
+        self.count, self.origin, self.stride = int(count), int(origin), int(stride)
+        self.pivot, self.sum, self.sum2, self.min, self.max, self.snapshots = pivot, sum, sum2, min, max, snapshots
+
+    @property
+    def fields(self) -> int:
+        return int(self.pivot.size(1))
+
+    def _n(self) -> float:
+        if self.count <= 0:
+            raise RuntimeError("RolloutMoments: no step of the window was accumulated (count == 0)")
+        return float(self.count)
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self.pivot + self.sum / self._n()
+
+    @property
+    def cov(self) -> torch.Tensor:
+        n, nf = self._n(), self.fields
+        s = self.sum / n
+        f, g = torch.triu_indices(nf, nf, device=self.sum2.device)        # row-major upper triangle: the pair order of sum2
+        c = self.sum2 / n - s[:, f] * s[:, g]
+        out = torch.empty((int(s.size(0)), nf, nf), dtype=c.dtype, device=c.device)
+        out[:, f, g] = c
+        out[:, g, f] = c
+        return out
+
+    @property
+    def var(self) -> torch.Tensor:
+        return torch.diagonal(self.cov, dim1=1, dim2=2)
+
+    @property
+    def std(self) -> torch.Tensor:
+        return self.var.clamp_min(0.0).sqrt()
+
+    def __repr__(self):
+        return (f"RolloutMoments(count={self.count}, origin={self.origin}, stride={self.stride}, fields={self.fields}, "
+                f"nodes={int(self.pivot.size(0))})")
 
 
 class _Records:
@@ -619,11 +799,12 @@ class RolloutErrors:
     `mae_masked` = Σ|d| over the masked (Dirichlet) nodes / their number (None without a mask) — with d = prediction − target and
     y = the target, all from `sums` [steps, nf, 6] = (Σd², Σ|d|, max|d|, Σy, Σy², Σ_masked|d|), which the step's last launch
     accumulated on the device in fp64 in a fixed order.  `snapshots` / `probes`: the rollout's `result()` / `probes()` when it kept
-    any, else None."""
+    any, else None.  `moments` / `error_moments`: None unless `GNN.evaluate` was asked for them."""
 
     def __init__(self, sums: torch.Tensor, n_nodes: int, n_masked: Optional[int] = None, snapshots: Optional[torch.Tensor] = None,
                  probes: Optional[torch.Tensor] = None):
         self.sums, self.n_nodes, self.n_masked, self.snapshots, self.probes = sums, int(n_nodes), n_masked, snapshots, probes
+        self.moments = self.error_moments = None        # `RolloutMoments` when GNN.evaluate(moments= / error_moments=) asked for them
         n = float(n_nodes)
         sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
         self.mse, self.mae, self.max_abs = sq / n, ab / n, mx

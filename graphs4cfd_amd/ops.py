@@ -578,6 +578,65 @@ def rollout_advance_record(field: Tensor, pred: Tensor, step: Tensor, nf: int, m
                                               _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def moment_pairs(nf: int) -> int:
+    """Planes of `sum2`: the pairs f <= g of nf fields, in the order (0,0), (0,1), ..., (0,nf-1), (1,1), ..."""
+    return nf * (nf + 1) // 2
+
+
+def rollout_moments(pred: Tensor, step: Tensor, nf: int, max_steps: int, window: Tensor, pivot: Tensor, sum: Tensor, sum2: Tensor,
+                    lo: Tensor, hi: Tensor, *, stride: int = 1, sub: Optional[Tensor] = None) -> None:
+    """g4c_rollout_moments: accumulate step t = step[0] (read on the device) into the per-node time statistics when t is on the window
+    — 0 <= t < max_steps, t >= origin = window[0] (int32 [2] on the device: {origin, last}), (t - origin) % stride == 0 — and leave
+    window[1] = t; any other step touches nothing.  The sample is pred [N, nf], or pred - sub[:, nf t : nf (t + 1)] with `sub`
+    (float32 [N, >= nf max_steps], unit stride along its columns).  pivot / sum / lo / hi: float64 [nf, N], sum2 float64
+    [moment_pairs(nf), N], unit stride along the nodes and one common plane stride >= N (views of padded buffers are fine).  `step`
+    is not written: the step's closing launch (rollout_advance / rollout_advance_record) bumps it afterwards."""
+    nf, max_steps, stride = int(nf), int(max_steps), int(stride)
+    what = "rollout_moments"
+    if not torch.is_tensor(pred) or pred.dtype != torch.float32:
+        raise TypeError(f"pred: {what}: expected a float32 tensor, got {getattr(pred, 'dtype', type(pred).__name__)}")
+    if nf <= 0 or pred.dim() != 2 or int(pred.size(1)) != nf or not pred.is_contiguous():
+        raise ValueError(f"pred: {what}: expected a contiguous [n_nodes, nf = {nf}], got shape {tuple(pred.shape)} strides {tuple(pred.stride())}")
+    n_nodes = int(pred.size(0))
+    for t, name in ((step, "step"), (window, "window")):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise TypeError(f"{name}: {what}: expected an int32 tensor of two entries, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.dim() != 1 or t.numel() < 2 or not t.is_contiguous():
+            raise ValueError(f"{name}: {what}: expected an int32 tensor of two entries, got shape {tuple(t.shape)}")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if stride < 1:
+        raise ValueError(f"stride: {what}: {stride} (>= 1)")
+    lds = set()
+    for t, name, planes in ((pivot, "pivot", nf), (sum, "sum", nf), (sum2, "sum2", moment_pairs(nf)), (lo, "lo", nf), (hi, "hi", nf)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64:
+            raise TypeError(f"{name}: {what}: expected a float64 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if tuple(t.shape) != (planes, n_nodes):
+            raise ValueError(f"{name}: {what}: expected shape ({planes}, {n_nodes}), got {tuple(t.shape)}")
+        if n_nodes > 1 and t.stride(1) != 1:
+            raise ValueError(f"{name}: {what} needs unit stride along the nodes, got strides {tuple(t.stride())}")
+        if planes > 1 and n_nodes > 0:
+            lds.add(int(t.stride(0)))
+    if len(lds) > 1 or (lds and min(lds) < n_nodes):
+        raise ValueError(f"pivot: {what}: the accumulators need one common plane stride >= n_nodes = {n_nodes}, got {sorted(lds)}")
+    sub_ld = 0
+    if sub is not None:
+        if not torch.is_tensor(sub) or sub.dtype != torch.float32:
+            raise TypeError(f"sub: {what}: expected a float32 tensor, got {getattr(sub, 'dtype', type(sub).__name__)}")
+        if sub.dim() != 2 or int(sub.size(0)) != n_nodes or int(sub.size(1)) < nf * max_steps:
+            raise ValueError(f"sub: {what}: expected [{n_nodes}, >= nf * max_steps = {nf * max_steps}], got {tuple(sub.shape)}")
+        cols = int(sub.size(1))
+        if (n_nodes > 0 and cols > 1 and sub.stride(1) != 1) or (n_nodes > 1 and sub.stride(0) < cols):
+            raise ValueError(f"sub: {what} needs rows of unit stride, got shape {tuple(sub.shape)} strides {tuple(sub.stride())}")
+        sub_ld = max(int(sub.stride(0)), cols) if n_nodes > 1 else cols
+    lib = _lib.load()
+    dev = _lib.require_hip(pred, step, window, pivot, sum, sum2, lo, hi, sub)
+    m = _lib.g4c_rollout_moments_t(max_steps=max_steps, stride=stride, window=_lib.ptr(window), sub=_lib.ptr(sub), sub_ld=sub_ld,
+                                   plane_ld=lds.pop() if lds else max(n_nodes, 1), pivot=_lib.ptr(pivot), sum=_lib.ptr(sum),
+                                   sum2=_lib.ptr(sum2), lo=_lib.ptr(lo), hi=_lib.ptr(hi))
+    _lib.check(lib.g4c_rollout_moments(_lib.ptr(pred), nf, C.byref(m), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

@@ -473,6 +473,31 @@ int64_t g4c_rollout_record_scratch_doubles(int64_t n_nodes, int32_t nf);
 int g4c_rollout_advance_record(float *field, int32_t field_cols, const float *pred, int32_t nf, const g4c_rollout_rec_t *rec /*host*/,
                                int32_t *step, int64_t n_nodes, void *stream);
 
+/* Time statistics of a rollout at every node (csrc/rollout_moments.hip): one launch per step, AFTER the forward and BEFORE the step's
+ * closing launch above (which bumps the step index this one reads, t = step[0], on the same stream).  Writes neither field nor step.
+ * The sample of node n and field f is x = (double)pred[n nf + f], or, with `sub`, x = (double)pred[n nf + f] - (double)sub[n sub_ld +
+ * nf t + f] (statistics of the error against a target).  Step t is accumulated iff 0 <= t < max_steps, t >= origin and (t - origin) %
+ * stride == 0, origin = window[0] read on the device (a captured launch follows a rewritten origin); an accumulated step leaves
+ * window[1] = t, any other step touches nothing.  At t == origin the accumulators are STORED, not read: pivot = lo = hi = x, sum =
+ * sum2 = 0 (no memset is ever needed; running through the origin again replaces the record).  On later steps, with d_f = x_f - pivot_f:
+ * sum_f += d_f, sum2_fg += d_f d_g (the product rounded to fp64 once, then added: no fused multiply-add), lo = fmin(lo, x),
+ * hi = fmax(hi, x).  Every accumulator receives one add per accumulated step, in time order, from one thread: the bits are a function
+ * of the data alone (no atomics, nothing depends on the grid).
+ * All accumulators are fp64 and plane-major: plane p of node n at base[p * plane_ld + n], plane_ld >= n_nodes.  sum2 holds the
+ * nf (nf + 1) / 2 pairs f <= g in the order (0,0), (0,1), ..., (0,nf-1), (1,1), ...   nf = 1 .. 8 (G4C_EUNSUPPORTED above).
+ * n_nodes == 0 launches nothing and succeeds. */
+typedef struct g4c_rollout_moments {
+    int32_t max_steps;           /* capacity of the rollout (and of `sub`), in steps */
+    int32_t stride;              /* >= 1 */
+    int32_t *window;             /* device, {origin, last} */
+    const float *sub;            /* [n_nodes, sub_ld], sub_ld >= nf * max_steps, or NULL */
+    int32_t sub_ld;
+    int64_t plane_ld;
+    double *pivot, *sum, *sum2, *lo, *hi;       /* nf, nf, nf (nf + 1) / 2, nf, nf planes */
+} g4c_rollout_moments_t;
+int g4c_rollout_moments(const float *pred, int32_t nf, const g4c_rollout_moments_t *m /*host*/, const int32_t *step, int64_t n_nodes,
+                        void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
