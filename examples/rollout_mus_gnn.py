@@ -37,3 +37,5 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 out = model.solve(graph, a.steps)                          # [N, 3 * steps], device-resident rollout (hipGraph replay)
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 print(f"{a.steps} steps on {a.nodes} nodes: {a.steps / dt:.1f} steps/s, output {tuple(out.shape)}, finite={bool(torch.isfinite(out).all())}")
+diag = model.diagnostics(graph, a.steps, ("div", "vort"))      # divergence and vorticity of every step, formed on the device: no prediction is held
+print("divergence RMS per step:", " ".join(f"{v:.3e}" for v in diag.rms[:, 0].tolist()))

@@ -95,6 +95,22 @@ class g4c_rollout_moments_t(C.Structure):
                 ("hi", C.c_void_p)]
 
 
+DERIVED_MAX_COLS, DERIVED_MAX_TERMS = 8, 3         # G4C_DERIVED_MAX_COLS / _TERMS
+DERIVED_SQ, DERIVED_ABS, DERIVED_MAX_ABS, DERIVED_NSTAT = range(4)     # G4C_DERIVED_*
+
+
+class g4c_derived_program_t(C.Structure):
+    _fields_ = [("nd", C.c_int32), ("n_terms", C.c_int32 * DERIVED_MAX_COLS),
+                ("field", (C.c_int32 * DERIVED_MAX_TERMS) * DERIVED_MAX_COLS), ("axis", (C.c_int32 * DERIVED_MAX_TERMS) * DERIVED_MAX_COLS),
+                ("coef", (C.c_float * DERIVED_MAX_TERMS) * DERIVED_MAX_COLS)]
+
+
+class g4c_mesh_derived_t(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("nf", C.c_int32), ("x_ld", C.c_int32), ("g", C.c_void_p), ("src", C.c_void_p), ("off", C.c_void_p),
+                ("cur", C.c_void_p), ("step", C.c_void_p), ("every", C.c_int32), ("n_snap", C.c_int32), ("max_steps", C.c_int32),
+                ("snap", C.c_void_p), ("stats", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -134,6 +150,10 @@ _SIGNATURES = {
     "g4c_rollout_advance_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_rec_t),
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_rollout_moments": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_moments_t), C.c_void_p, C.c_int64, C.c_void_p]),
+    "g4c_mesh_gradient_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
+    "g4c_mesh_derived": (C.c_int, [C.c_void_p, C.POINTER(g4c_mesh_derived_t), C.POINTER(g4c_derived_program_t), C.c_int64, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

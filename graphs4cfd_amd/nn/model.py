@@ -192,7 +192,8 @@ class GNN(nn.Module):
             return ro.result()       # (reports a clip of the default arithmetic in this model's own launches)
 
     def evaluate(self, graph: Union[Graph, List[Graph]], n_out: Optional[int] = None, *, every: int = 0, probes: Optional[torch.Tensor] = None,
-                 capture: Optional[bool] = None, moments=None, error_moments=None) -> "RolloutErrors":
+                 capture: Optional[bool] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
+                 derived_moments=None, derived_options: Optional[dict] = None) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -200,18 +201,36 @@ class GNN(nn.Module):
         returns (`.snapshots`), probes (1-D integer tensor of node rows) the prediction's time series there (`.probes`,
         [P, num_fields * n_out]).  moments / error_moments (None, True, `start` or `(start, stride)`, as in `Rollout`) also attach the
         per-node time statistics of the prediction / of prediction − target (`.moments` / `.error_moments`: `RolloutMoments`).
-        A list of graphs is collated as in `solve`."""
+        derived (a tuple of names: 'div', 'vort', 'grad:<f>') with derived_every / derived_moments / derived_options, as in `Rollout`,
+        attaches the flow diagnostics of the prediction (`.derived`: `RolloutDerived`).  A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
             n_out = int(target.size(1)) // int(self.num_fields)
         assert n_out > 0, "n_out must be greater than 0."
         with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True, moments=moments,
-                           error_moments=error_moments) as ro:
+                           error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
+                           derived_options=derived_options) as ro:
             ro.run(n_out)
             errs = ro.errors()
             errs.moments = ro.moments() if ro._moments is not None else None
             errs.error_moments = ro.error_moments() if ro._error_moments is not None else None
+            errs.derived = ro.derived() if ro._derived is not None else None
             return errs
+
+    def diagnostics(self, graph: Union[Graph, List[Graph]], n_out: int, derived=("div", "vort"), *, every: int = 0, discard: Optional[int] = None,
+                    stride: int = 1, capture: Optional[bool] = None, **derived_options) -> "RolloutDerived":
+        """Roll the model out for n_out steps and return the flow diagnostics of every predicted step (`RolloutDerived`): the
+        columns `derived` names — 'div' (divergence of the velocity), 'vort' (vorticity), 'grad:<f>' — formed on the device inside the
+        step by the mesh's least-squares gradient (`gfd.MeshGradient`), with their `rms`, `mean_abs` and `max_abs` over the nodes per
+        step.  No prediction is held.  every = k > 0 also keeps the derived columns of steps k - 1, 2k - 1, ... (`.snapshots`);
+        discard = d (not None) their per-node time statistics over the steps d, d + stride, ... (`.moments`: `RolloutMoments` — the
+        mean vorticity, its fluctuation).  derived_options: power, edge_vectors (periodic meshes: the wrapped, unscaled `edge_attr`
+        of `ConnectKNN`), velocity, field_scale.  A list of graphs is collated as in `solve`."""
+        assert n_out > 0, "n_out must be greater than 0."
+        with self._rollout(graph, n_out, capture, "diagnostics()", every=0, derived=derived, derived_every=every,
+                           derived_moments=None if discard is None else (discard, stride), derived_options=derived_options or None) as ro:
+            ro.run(n_out)
+            return ro.derived()
 
     def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
                         capture: Optional[bool] = None) -> "RolloutMoments":
@@ -228,6 +247,10 @@ class GNN(nn.Module):
 
     def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
         """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
+        if records.get("derived") is not None:            # (argument errors before anything is collated or moved)
+            for gr in (graph if type(graph) is list else [graph]):
+                _check_derived(gr, int(self.num_fields), n_out, records["derived"], records.get("derived_every", 0),
+                               records.get("derived_moments"), records.get("derived_options"), in_list=type(graph) is list)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -373,7 +396,8 @@ class Rollout:
 
     def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
                  label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
-                 mask: Optional[torch.Tensor] = None, moments=None, error_moments=None):
+                 mask: Optional[torch.Tensor] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
+                 derived_moments=None, derived_options: Optional[dict] = None):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -389,7 +413,19 @@ class Rollout:
         had, one `g4c_rollout_moments` launch per statistic goes in front of it): `moments` — of the prediction — and
         `error_moments` — of prediction − target, needs `target=` — are each None, True (every step), `start` (steps start,
         start + 1, ...) or `(start, stride)` (steps start, start + stride, ...; 0-based).  `moments()` / `error_moments()` return
-        them (`RolloutMoments`); after `rewind()` or a recomputation they hold the steps taken since."""
+        them (`RolloutMoments`); after `rewind()` or a recomputation they hold the steps taken since.
+
+        Flow diagnostics (opt-in, no record either): `derived` — a tuple of names, 'div' (divergence of the velocity), 'vort'
+        (vorticity: one column in 2-D, three in 3-D), 'grad:<f>' (dim columns), at most 8 columns — are formed from every prediction
+        by the mesh's least-squares gradient (`gfd.MeshGradient`, built here on the rollout's own numbering): one `g4c_mesh_derived`
+        launch and its statistics launch after the forward, in front of the moments and the closing launch.  `derived()` returns
+        them (`RolloutDerived`): rms / mean_abs / max_abs over the nodes per step; with `derived_every` = k > 0 the columns of steps
+        k - 1, 2k - 1, ...; with `derived_moments` (the forms `moments` takes) their per-node time statistics, by the same
+        `g4c_rollout_moments`.  `derived_options`: power (0, 1, 2; default 2), edge_vectors ([E, dim], caller's edge order: the
+        wrapped, unscaled `edge_attr` of a periodic mesh), velocity (the fields of the velocity components, default 0 .. dim - 1),
+        field_scale ([nf], multiplied into the coefficients).  Steps run again after `rewind()` or a recomputation overwrite
+        their slots."""
+        derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options)
         window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
         error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
         if error_window is not None and target is None:
@@ -431,6 +467,7 @@ class Rollout:
         self.exact_range = False                 # True once a clip made this rollout fall back to "bf16x6"
         self._moments = None if window is None else _Moments(self, *window)
         self._error_moments = None if error_window is None else _Moments(self, *error_window, sub=self._rec.target)
+        self._derived = None if derived_spec is None else _Derived(self, *derived_spec)
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -443,7 +480,9 @@ class Rollout:
     def _one(self):
         with self.static, self.flags:
             pred = self.model.forward(self.graph, self.steps_done)
-        for mo in (self._moments, self._error_moments):       # (they read the step index the closing launch below bumps)
+        if self._derived is not None:                         # (all of these read the step index the closing launch below bumps)
+            self._derived.launch(pred, self.step_counter)
+        for mo in (self._moments, self._error_moments):
             if mo is not None:
                 mo.accumulate(pred, self.step_counter)
         if self._rec is not None:
@@ -568,7 +607,7 @@ class Rollout:
                              probes=ops.steps_to_columns(rec.probe_out) if rec.probe_out is not None else None)
 
     def _reset_moments(self) -> None:
-        for mo in (self._moments, self._error_moments):
+        for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None):
             if mo is not None:
                 mo.reset(self._first_slot)
 
@@ -587,6 +626,14 @@ class Rollout:
         """The same of prediction − target over the window `error_moments=` asked for: `mean` is the bias field, `mean² + var` the
         mean-square error at every node."""
         return self._read_moments(self._error_moments, "error_moments")
+
+    def derived(self) -> "RolloutDerived":
+        """The flow diagnostics `derived=` asked for, of the `steps_done` steps taken (`RolloutDerived`) — validated first, like
+        `result()`; one device -> host copy of [steps_done, nd, 3] sums."""
+        if self._derived is None:
+            raise RuntimeError(f"{self.label}: no derived= were asked for")
+        self.validate()
+        return self._derived.read(self._perm, self.steps_done)
 
     def close(self) -> None:
         self.graph.field = self._orig_field
@@ -660,8 +707,8 @@ class _Moments:
     outside the graph — is all `rewind()` and a recomputation need: the step that finds itself at the origin stores the
     accumulators without reading them."""
 
-    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None):
-        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf
+    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None, nf: Optional[int] = None):
+        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf if nf is None else int(nf)        # (nf: the derived columns)
         self.nf, self.max_steps, self.start, self.stride, self.sub = nf, ro.max_steps, start, stride, sub
         pairs = ops.moment_pairs(nf)
         self.planes = torch.zeros((4 * nf + pairs, n), dtype=torch.float64, device=dev)
@@ -752,6 +799,98 @@ class RolloutMoments:
                 f"nodes={int(self.pivot.size(0))})")
 
 
+def _check_derived(graph: Graph, nf: int, max_steps: int, derived, every, moments, options, in_list: bool = False):
+    """The `derived*=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing is moved, the
+    library is not touched) -> (names, every, window or None, options), or None when no diagnostics are asked for."""
+    from ..mesh_gradient import check_mesh, derived_terms
+    if derived is None or derived is False:
+        if (every not in (0, None)) or moments not in (None, False) or options:
+            raise ValueError("derived: derived_every / derived_moments / derived_options were given without derived=")
+        return None
+    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+        raise ValueError(f"derived_every: expected an integer >= 0 (0: no snapshots, k: every k-th step), got {every!r}")
+    options = dict(options or {})
+    unknown = set(options) - {"power", "edge_vectors", "velocity", "field_scale"}
+    if unknown:
+        raise ValueError(f"derived_options: unknown option(s) {sorted(unknown)} (power, edge_vectors, velocity, field_scale)")
+    if in_list and options.get("edge_vectors") is not None:
+        raise ValueError("derived_options: edge_vectors of a list of graphs: collate the graphs and their edge vectors yourself")
+    dim = check_mesh(graph, options.get("power", 2), options.get("edge_vectors"))
+    names = (derived,) if isinstance(derived, str) else derived
+    terms = derived_terms(names, dim, nf, options.get("velocity"), options.get("field_scale"))
+    window = _check_moments("derived_moments", moments, len(terms), max_steps)
+    return tuple(names), int(every), window, options
+
+
+class _Derived:
+    """The flow diagnostics of a `Rollout` and the launches that form them.  Everything is allocated here, once, in the rollout's
+    node numbering: the operator (`MeshGradient` on the rollout's own graph — the caller's edge vectors follow the renumbered
+    edges), the program, `cur` [N, nd], the per-step sums [max_steps, nd, 3] with their scratch, the snapshot slots, and the
+    accumulators of `g4c_rollout_moments` over `cur`."""
+
+    def __init__(self, ro: "Rollout", names, every: int, window, options: dict):
+        from ..mesh_gradient import MeshGradient
+        dev, n = ro.field.device, int(ro.graph.num_nodes)
+        ev = options.get("edge_vectors")
+        if ev is not None:
+            ev = ev.to(dev)
+            if ro._perm is not None:          # reorder.reorder_nodes: the edges re-sorted stably by their new target
+                inv = torch.empty_like(ro._perm)
+                inv[ro._perm] = torch.arange(n, device=ro._perm.device)
+                ev = ev[torch.argsort(inv[ro._caller_graph.edge_index[1].to(inv.device)], stable=True).to(dev)]
+        self.op = MeshGradient(ro.graph, options.get("power", 2), ev)
+        self.names, self.columns = tuple(names), self.op.columns(names)
+        self.program = self.op.program(names, ro.nf, options.get("velocity"), options.get("field_scale"))
+        self.nd, self.every, self.max_steps = len(self.columns), every, ro.max_steps
+        self.cur = torch.zeros((n, self.nd), dtype=torch.float32, device=dev)
+        self.stats = torch.zeros((ro.max_steps, self.nd, _lib.DERIVED_NSTAT), dtype=torch.float64, device=dev)
+        self.scratch = ops.mesh_derived_scratch(n, self.nd, dev)
+        self.snap = torch.zeros((ro.max_steps // every, n, self.nd), dtype=torch.float32, device=dev) if every else None
+        self.moments = None if window is None else _Moments(ro, *window, nf=self.nd)
+
+    def launch(self, pred, step) -> None:
+        ops.mesh_derived(pred, self.op.off, self.op.g, self.op.src, self.program, self.cur, step=step, every=self.every, snap=self.snap,
+                         stats=self.stats, scratch=self.scratch, max_steps=self.max_steps)
+        if self.moments is not None:
+            self.moments.accumulate(self.cur, step)
+
+    def read(self, perm, steps_done: int) -> "RolloutDerived":
+        def rows(t):
+            if perm is None:
+                return t
+            out = torch.empty_like(t)
+            out[perm] = t
+            return out
+
+        return RolloutDerived(self.names, self.columns, self.stats[:steps_done].cpu(), int(self.cur.size(0)),
+                              snapshots=rows(ops.steps_to_columns(self.snap)) if self.snap is not None else None,
+                              moments=self.moments.read(perm) if self.moments is not None else None, degenerate=rows(self.op.degenerate))
+
+
+class RolloutDerived:
+    """Flow diagnostics of a rollout (`Rollout.derived()`, `GNN.diagnostics()`, `GNN.evaluate(derived=)`): `names` as asked for,
+    `columns` their nd labels, and per step taken `rms` = √(Σq² / N), `mean_abs` = Σ|q| / N and `max_abs` = max|q| over the N nodes,
+    each [steps, nd] — from `sums` [steps, nd, 3] = (Σq², Σ|q|, max|q|), which the step accumulated on the device in fp64 in a fixed
+    order (fp64 host tensors).  `snapshots` [N, nd * (max_steps // k)]: the columns of steps k - 1, 2k - 1, ... (`derived_every=k`), else
+    None; `moments`: their per-node time statistics (`RolloutMoments`, `derived_moments=`), else None; `degenerate` bool [N]: the
+    nodes whose neighbours do not span the space — their derivatives are 0.  Rows are the caller's numbering."""
+
+    def __init__(self, names, columns, sums: torch.Tensor, n_nodes: int, snapshots: Optional[torch.Tensor] = None,
+                 moments: Optional["RolloutMoments"] = None, degenerate: Optional[torch.Tensor] = None):
+        self.names, self.columns, self.sums, self.n_nodes = tuple(names), list(columns), sums, int(n_nodes)
+        self.snapshots, self.moments, self.degenerate = snapshots, moments, degenerate
+        n = float(max(n_nodes, 1))
+        self.rms = (sums[..., _lib.DERIVED_SQ] / n).sqrt()
+        self.mean_abs = sums[..., _lib.DERIVED_ABS] / n
+        self.max_abs = sums[..., _lib.DERIVED_MAX_ABS]
+
+    def column(self, label: str) -> int:
+        return self.columns.index(label)
+
+    def __repr__(self):
+        return f"RolloutDerived(columns={self.columns}, steps={int(self.sums.size(0))}, nodes={self.n_nodes})"
+
+
 class _Records:
     """The record buffers of a `Rollout` and the launch that fills them.  Everything is allocated here, once, in the rollout's node
     numbering (probe rows, target rows and mask rows are mapped through the Morton permutation at construction), so a captured
@@ -805,6 +944,7 @@ class RolloutErrors:
                  probes: Optional[torch.Tensor] = None):
         self.sums, self.n_nodes, self.n_masked, self.snapshots, self.probes = sums, int(n_nodes), n_masked, snapshots, probes
         self.moments = self.error_moments = None        # `RolloutMoments` when GNN.evaluate(moments= / error_moments=) asked for them
+        self.derived = None                             # `RolloutDerived` when GNN.evaluate(derived=) asked for it
         n = float(n_nodes)
         sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
         self.mse, self.mae, self.max_abs = sq / n, ab / n, mx

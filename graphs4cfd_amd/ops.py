@@ -637,6 +637,174 @@ def rollout_moments(pred: Tensor, step: Tensor, nf: int, max_steps: int, window:
     _lib.check(lib.g4c_rollout_moments(_lib.ptr(pred), nf, C.byref(m), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def _mesh_arg(what, t, name, dtype, shape=None, dim=None):
+    """dtype, contiguity and shape of one tensor argument of ops.mesh_*: ValueError naming the argument."""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{name}: {what}: expected a {str(dtype).replace('torch.', '')} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if dim is not None and t.dim() != dim:
+        raise ValueError(f"{name}: {what}: expected a {dim}-D tensor, got shape {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _mesh_devices(what, first, *named):
+    """Every tensor on the HIP device of the first one: ValueError naming the argument (nothing is moved, there is no CPU path)."""
+    name0, t0 = first
+    if t0.device.type != "cuda":
+        raise ValueError(f"{name0}: {what} runs on a HIP device only, got a tensor on '{t0.device}' (there is no CPU fallback)")
+    for name, t in named:
+        if t is not None and t.device != t0.device:
+            raise ValueError(f"{name}: {what}: on '{t.device}', {name0} is on '{t0.device}'")
+    return t0.device
+
+
+def mesh_gradient_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
+    """g4c_mesh_gradient_weights: the least-squares gradient weights of a mesh, once per mesh.  `csr` is the CSR-by-target of its
+    edges (`plan.edge_csr(edge_index, n_nodes)[1]`: off int32 [N + 1], perm int32 [E] or None), src32 int32 [E] their senders and rel
+    float32 [E, dim] their vectors receiver - sender, both in the caller's edge numbering; power 0, 1 or 2 weighs an edge by
+    |rel|^(-power).  Returns (g float32 [E, dim], src int32 [E], degenerate uint8 [N]) with the edges in CSR order: the s-th in-edge
+    of node i at position off[i] + s (include/g4c.h has the arithmetic).  `out`: the three tensors to write into; a mesh without
+    edges or nodes launches nothing (then a fresh `degenerate` is all ones)."""
+    what = "mesh_gradient_weights"
+    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
+    _mesh_arg(what, rel, "rel", torch.float32, dim=2)
+    n_edges, dim = int(rel.size(0)), int(rel.size(1))
+    if dim not in (2, 3):
+        raise ValueError(f"rel: {what}: expected [E, 2] or [E, 3], got shape {tuple(rel.shape)}")
+    off, perm = getattr(csr, "off", None), getattr(csr, "perm", None)
+    _mesh_arg(what, off, "csr.off", torch.int32, dim=1)
+    if off.numel() < 1:
+        raise ValueError(f"csr.off: {what}: expected [n_nodes + 1], got shape {tuple(off.shape)}")
+    n_nodes = int(off.numel()) - 1
+    if int(getattr(csr, "n", n_edges)) != n_edges:
+        raise ValueError(f"csr: {what}: a plan of {csr.n} edges for rel of {n_edges}")
+    if perm is not None:
+        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_edges,))
+    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_edges,))
+    if out is not None:
+        g, src, degenerate = out
+        _mesh_arg(what, g, "out[0]", torch.float32, shape=(n_edges, dim))
+        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_edges,))
+        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
+    else:
+        g = src = degenerate = None
+    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", g), ("out[1]", src),
+                        ("out[2]", degenerate))
+    if out is None:
+        g = torch.empty((n_edges, dim), dtype=torch.float32, device=dev)
+        src = torch.empty((n_edges,), dtype=torch.int32, device=dev)
+        degenerate = torch.ones((n_nodes,), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_mesh_gradient_weights(_lib.ptr(off), _lib.ptr(perm), _lib.ptr(src32), _lib.ptr(rel), dim, power, n_nodes, n_edges,
+                                             _lib.ptr(g), _lib.ptr(src), _lib.ptr(degenerate), _lib.stream_handle(dev)))
+    return g, src, degenerate
+
+
+def derived_program(program, nf: Optional[int] = None, dim: Optional[int] = None) -> "_lib.g4c_derived_program_t":
+    """A program of `mesh_derived` — a sequence of columns, each a sequence of 1 .. 3 terms (field, axis, coef): the column is
+    Σ coef · ∂_axis x[:, field] — as the library's g4c_derived_program_t (returned unchanged if it is one already).  ValueError
+    naming `program` on anything else; fields and axes are checked against nf / dim when those are given."""
+    if isinstance(program, _lib.g4c_derived_program_t):
+        return program
+    what = "mesh_derived"
+    try:
+        cols = [[tuple(t) for t in col] for col in program]
+    except TypeError:
+        raise ValueError(f"program: {what}: expected a sequence of columns of (field, axis, coef) terms, got {program!r}") from None
+    if not 1 <= len(cols) <= _lib.DERIVED_MAX_COLS:
+        raise ValueError(f"program: {what}: {len(cols)} columns (1 .. {_lib.DERIVED_MAX_COLS})")
+    p = _lib.g4c_derived_program_t(nd=len(cols))
+    for c, col in enumerate(cols):
+        if not 1 <= len(col) <= _lib.DERIVED_MAX_TERMS:
+            raise ValueError(f"program: {what}: column {c} has {len(col)} terms (1 .. {_lib.DERIVED_MAX_TERMS})")
+        p.n_terms[c] = len(col)
+        for k, term in enumerate(col):
+            if len(term) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in term[:2]):
+                raise ValueError(f"program: {what}: column {c} term {k}: expected (field, axis, coef), got {term!r}")
+            f, a, coef = term
+            if f < 0 or (nf is not None and f >= nf):
+                raise ValueError(f"program: {what}: column {c} term {k}: field {f} of {nf}")
+            if a < 0 or (dim is not None and a >= dim):
+                raise ValueError(f"program: {what}: column {c} term {k}: axis {a} of {dim}")
+            p.field[c][k], p.axis[c][k], p.coef[c][k] = f, a, float(coef)
+    return p
+
+
+def mesh_derived_scratch(n_nodes: int, nd: int, device) -> Tensor:
+    """The `scratch` buffer of mesh_derived's statistics for a mesh of n_nodes and nd columns (g4c_mesh_derived_scratch_doubles)."""
+    n = int(_lib.load().g4c_mesh_derived_scratch_doubles(int(n_nodes), int(nd)))
+    if n < 0:
+        _lib.check(n)
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: Tensor, *, step: Optional[Tensor] = None, every: int = 0,
+                 snap: Optional[Tensor] = None, stats: Optional[Tensor] = None, scratch: Optional[Tensor] = None, max_steps: int = 0,
+                 nf: Optional[int] = None) -> None:
+    """g4c_mesh_derived: the columns of `program` (see `derived_program`) of the fields x[:, :nf] (float32 [N, x_ld], rows of unit
+    stride; nf defaults to every column) by the least-squares gradient (g float32 [E, dim], src int32 [E], off int32 [N + 1]: the
+    outputs of `mesh_gradient_weights` and the plan's offsets) into cur float32 [N, nd] — one thread per node, fp32, its in-edges in
+    CSR order.  With `step` (int32, t = step[0] is read on the device and not written): every = k > 0 and snap float32 [n_snap, N, nd]
+    keep steps k - 1, 2k - 1, ... in slots 0, 1, ...; stats float64 [max_steps, nd, 3] receives (Σq², Σ|q|, max|q|) over the nodes
+    at row t (overwritten; `scratch` from `mesh_derived_scratch`), in a fixed order: the same bits on every run."""
+    what = "mesh_derived"
+    every, max_steps = int(every), int(max_steps)
+    _mesh_arg(what, g, "g", torch.float32, dim=2)
+    n_edges, dim = int(g.size(0)), int(g.size(1))
+    if dim not in (2, 3):
+        raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or int(x.size(1)) < 1:
+        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
+    n_nodes, cols = int(x.size(0)), int(x.size(1))
+    nf = cols if nf is None else int(nf)
+    if not 1 <= nf <= cols:
+        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
+    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
+        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, src, "src", torch.int32, shape=(n_edges,))
+    prog = derived_program(program, nf, dim)
+    nd = int(prog.nd)
+    _mesh_arg(what, cur, "cur", torch.float32, shape=(n_nodes, nd))
+    if every < 0:
+        raise ValueError(f"every: {what}: {every} (0 keeps no snapshot, k > 0 every k-th step)")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if (every > 0) != (snap is not None):
+        raise ValueError(f"snap: {what}: every = {every} {'needs a' if every else 'takes no'} snapshot buffer")
+    if snap is not None:
+        _mesh_arg(what, snap, "snap", torch.float32, dim=3)
+        if tuple(snap.shape[1:]) != (n_nodes, nd):
+            raise ValueError(f"snap: {what}: expected [n_snap, {n_nodes}, {nd}], got {tuple(snap.shape)}")
+    if (stats is None) != (scratch is None):
+        raise ValueError(f"{'scratch' if scratch is None else 'stats'}: {what}: stats and scratch come together")
+    if stats is not None:
+        _mesh_arg(what, stats, "stats", torch.float64, shape=(max_steps, nd, _lib.DERIVED_NSTAT))
+        _mesh_arg(what, scratch, "scratch", torch.float64, dim=1)
+        need = 8 + min(max(-(-n_nodes // 256), 1), 1024) * nd * _lib.DERIVED_NSTAT
+        if scratch.numel() < need:
+            raise ValueError(f"scratch: {what}: {scratch.numel()} doubles, needs {need} (mesh_derived_scratch)")
+    if step is None:
+        if snap is not None or stats is not None:
+            raise ValueError(f"step: {what}: snapshots and stats are addressed by the step index: pass step=")
+    else:
+        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
+            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
+    dev = _mesh_devices(what, ("x", x), ("off", off), ("g", g), ("src", src), ("cur", cur), ("step", step), ("snap", snap),
+                        ("stats", stats), ("scratch", scratch))
+    lib = _lib.load()
+    d = _lib.g4c_mesh_derived_t(dim=dim, nf=nf, x_ld=x_ld, g=_lib.ptr(g), src=_lib.ptr(src), off=_lib.ptr(off), cur=_lib.ptr(cur),
+                                step=_lib.ptr(step), every=every, n_snap=0 if snap is None else int(snap.size(0)), max_steps=max_steps,
+                                snap=_lib.ptr(snap), stats=_lib.ptr(stats), scratch=_lib.ptr(scratch))
+    _lib.check(lib.g4c_mesh_derived(_lib.ptr(x), C.byref(d), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

@@ -498,6 +498,60 @@ typedef struct g4c_rollout_moments {
 int g4c_rollout_moments(const float *pred, int32_t nf, const g4c_rollout_moments_t *m /*host*/, const int32_t *step, int64_t n_nodes,
                         void *stream);
 
+/* A least-squares gradient over the in-edges of a mesh, and the flow diagnostics of a rollout built on it (csrc/mesh_gradient.hip).
+ *
+ * g4c_mesh_gradient_weights — once per mesh.  Edges grouped by receiver: the s-th in-edge of node i is edge pe = perm[off[i] + s]
+ * (perm == NULL: pe = off[i] + s) of the caller's numbering; src32[E] its senders, rel[E, dim] fp32 its vectors receiver − sender
+ * (the sign of `edge_attr`).  Per node i, over its in-edges in that order, in fp64: d_e = −rel_e, w_e = |d_e|^(−power) (power 0, 1
+ * or 2), M = Σ w_e d_e d_eᵀ.  The node is DEGENERATE iff not det M > 1e-12 (tr M / dim)^dim — that is det M <= the threshold, or a
+ * determinant that is no number (a zero-length edge has no weight under power >= 1): fewer than dim in-edges, collinear / coplanar
+ * neighbours.  Then every g_e = 0 and degenerate[i] = 1; otherwise g_e = w_e M⁻¹ d_e, M⁻¹ = adj M / det M in closed form, rounded to
+ * fp32 once, so that  grad x (i) = Σ_e g_e (x[src_e] − x[i])  is exact on linear fields.
+ * Outputs in CSR order (position off[i] + s): g[E, dim] fp32, src[E] = src32[pe] (the permutation is resolved here), and
+ * degenerate[n_nodes].  n_nodes == 0 or n_edges == 0 launches nothing, writes nothing and succeeds.  dim 2 or 3 (G4C_EUNSUPPORTED). */
+int g4c_mesh_gradient_weights(const int32_t *off, const int32_t *perm /*or NULL*/, const int32_t *src32, const float *rel, int32_t dim,
+                              int32_t power, int64_t n_nodes, int64_t n_edges, float *g, int32_t *src, uint8_t *degenerate, void *stream);
+
+/* g4c_mesh_derived — once per step, AFTER the forward and BEFORE the step's closing launch (it reads the step index t = step[0] and
+ * never writes it).  A program of nd <= 8 columns, each the sum of 1 .. 3 terms coef · ∂_axis x[:, field] (more: G4C_EUNSUPPORTED; a
+ * program may name at most 8 distinct fields).  fp32, no contraction, in this order: for every field f the program names and every
+ * axis a, G[f][a] = 0, then over the in-edges e of node i in CSR order diff = x[src_e, f] − x[i, f], p = g[e][a] · diff (rounded),
+ * G[f][a] += p; column c = (coef₀ G₀ + coef₁ G₁) + coef₂ G₂ with every product rounded and the terms added left to right from the
+ * first.  One thread per node: the bits are a function of the data alone, and a numpy.float32 loop reproduces them.
+ * cur[n_nodes, nd] is written on every call.  If every > 0, (t + 1) % every == 0 and slot = (t + 1) / every − 1 < n_snap (t >= 0), the
+ * same values go to snap[slot][n_nodes][nd] (the records' slot convention).  If stats != NULL and 0 <= t < max_steps, stats[t][c] =
+ * {Σq², Σ|q|, max|q|} over the nodes in fp64 — OVERWRITTEN, never accumulated — by the records' rule: register accumulators, rows dealt
+ * gid, gid + grid, ... over at most 1024 workgroups of 256, a xor butterfly per wave, the waves in order through LDS, one partial set
+ * per workgroup into `scratch` (g4c_mesh_derived_scratch_doubles doubles), and a second one-workgroup launch that adds the partials
+ * in a fixed order.  No floating-point atomics: the bits are the same on every run.
+ * G4C_EINVAL before any launch: a field or axis out of range, negative sizes, x_ld < nf, a column without terms, records without
+ * their buffers.  n_nodes == 0 launches nothing and succeeds. */
+#define G4C_DERIVED_MAX_COLS 8
+#define G4C_DERIVED_MAX_TERMS 3
+enum { G4C_DERIVED_SQ, G4C_DERIVED_ABS, G4C_DERIVED_MAX_ABS, G4C_DERIVED_NSTAT };
+typedef struct g4c_derived_program {
+    int32_t nd;
+    int32_t n_terms[G4C_DERIVED_MAX_COLS];
+    int32_t field[G4C_DERIVED_MAX_COLS][G4C_DERIVED_MAX_TERMS];
+    int32_t axis[G4C_DERIVED_MAX_COLS][G4C_DERIVED_MAX_TERMS];
+    float coef[G4C_DERIVED_MAX_COLS][G4C_DERIVED_MAX_TERMS];
+} g4c_derived_program_t;
+typedef struct g4c_mesh_derived {
+    int32_t dim, nf, x_ld;       /* x[n_nodes, x_ld] fp32, its first nf columns are the fields */
+    const float *g;              /* [E, dim], CSR order (g4c_mesh_gradient_weights); NULL, with src, for a mesh without edges */
+    const int32_t *src;          /* [E], CSR order */
+    const int32_t *off;          /* [n_nodes + 1] */
+    float *cur;                  /* [n_nodes, nd] */
+    const int32_t *step;         /* device; may be NULL without snap and stats */
+    int32_t every, n_snap, max_steps;
+    float *snap;                 /* [n_snap][n_nodes][nd] or NULL */
+    double *stats;               /* [max_steps][nd][G4C_DERIVED_NSTAT] or NULL */
+    double *scratch;             /* g4c_mesh_derived_scratch_doubles(n_nodes, nd) doubles, with stats */
+} g4c_mesh_derived_t;
+int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd);
+int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d /*host*/, const g4c_derived_program_t *prog /*host*/, int64_t n_nodes,
+                     void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
