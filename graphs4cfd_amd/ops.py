@@ -1542,24 +1542,35 @@ def _run(packed: PackedMLP, arr, n_src: int, n_rows: int, io, dev, flops: float,
 
 def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr: CsrPlan, agg_mean: bool, upd: PackedMLP,
                      v: Tensor, act: int, store_rows: bool = True, head_outs: Optional[Sequence[Tensor]] = None,
-                     v_out: Optional[Tensor] = None, v_bound: Optional[float] = None) -> Tuple[Optional[Tensor], Tensor, Optional[Sequence[Tensor]]]:
+                     v_out: Optional[Tensor] = None, v_bound: Optional[float] = None, e_out: Optional[Tensor] = None,
+                     agg_out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor, Optional[Sequence[Tensor]]]:
     """One launch for a whole MP layer (g4c_mlp_io_t.upd; reference nn/blocks.py:175-186): the hoisted message MLP `msg`
     on `sources` (one 128-wide weighted block + the two gathered node-side products as additive sources) with the aggregation over
     `csr`, and — in the same persistent workgroups — the node MLP `upd` on [aggregate | v] with LayerNorm / `act` and, when
     `head_outs` is given, the heads packed behind `upd` (the next layer's products).  f16x3 arithmetic only, inference only.
     `v_bound`: proven bound on |v| (Source.bound), for the node MLP's half of the range proof.
+    `e_out` (float32 [>= n_rows, 128], only with store_rows) / `agg_out` (float32 [>= n_seg, 128]): the caller's tensors for the e' rows
+    and for the aggregate the launch writes and re-reads (views of wider buffers are fine); None allocates them here.
     Returns (e' rows or None, v', head_outs); take_bounds() then answers for v' (`out`), the heads and e' (`e`)."""
     global _last_bounds
     _last_bounds = None
-    dev = _lib.require_hip(*[s.tensor for s in sources], *[s.index for s in sources], v, v_out)
+    if e_out is not None:
+        if not store_rows:
+            raise ValueError("e_out: given with store_rows=False (the launch stores no e' rows)")
+        _rows_f32(e_out, "e_out", cols=128, min_rows=n_rows)
+    if agg_out is not None:
+        _rows_f32(agg_out, "agg_out", cols=128, min_rows=csr.n_seg)
+    dev = _lib.require_hip(*[s.tensor for s in sources], *[s.index for s in sources], v, v_out, e_out, agg_out)
     if msg.split != "f16x2" or upd.split != "f16x2":
         raise NotImplementedError("mp_layer_forward needs both MLPs packed for the f16x3 arithmetic")
     if csr.tiles() is None or n_rows != csr.n:
         raise ValueError("mp_layer_forward: the rows must be in segment order with segments of at most 32 rows")
     v = _f32_2d(v, "v")
     n_t = csr.n_seg
-    e_out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev) if store_rows else None
-    agg = torch.empty((n_t, 128), dtype=torch.float32, device=dev)          # (scratch: written and re-read by the same workgroup, L2-resident)
+    if e_out is None and store_rows:
+        e_out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev)
+    # (scratch: written and re-read by the same workgroup, L2-resident)
+    agg = agg_out if agg_out is not None else torch.empty((n_t, 128), dtype=torch.float32, device=dev)
     if v_out is None:
         v_out = torch.empty((n_t, 128), dtype=torch.float32, device=dev)
     n_heads = 0 if head_outs is None else len(head_outs)
@@ -1590,17 +1601,23 @@ STATIC_FIRST_LAYER = os.environ.get("G4C_STATIC_FIRST_LAYER", "1") != "0"
 
 
 def mlp_forward_precomputed(packed: PackedMLP, first: Tensor, products: Sequence[Source], n_rows: int,
-                            agg: Tuple[CsrPlan, Tensor, bool], act: int = _lib.ACT_NONE, store_rows: bool = True) -> Optional[Tensor]:
+                            agg: Tuple[CsrPlan, Tensor, bool], act: int = _lib.ACT_NONE, store_rows: bool = True,
+                            out: Optional[Tensor] = None) -> Optional[Tensor]:
     """The hoisted message launch of `packed` (one 128-wide weighted block, three 128-wide layers, f16x3) WITHOUT its first layer
     (g4c_mlp_t.k_pad[0] == 0): `first` [n_rows, 128] = b1 + W1x x, computed before, and the two gathered node-side `products`
     (additive Sources with an index) sum to the layer-0 pre-activation, (first + p0[i0]) + p1[i1]; the launch runs the two layers
     left, LayerNorm, `act`, the row stores (`store_rows`) and the fused aggregation `agg` = (csr, out [n_seg, 128], mean), bit-identical
-    to segment_reduce of the rows.  Inference only; always range-tracked; a shape the library has not built raises
+    to segment_reduce of the rows.  `out` (float32 [>= n_rows, 128], only with store_rows): the caller's tensor for the rows (a view of
+    a wider buffer is fine); None allocates it here.  Inference only; always range-tracked; a shape the library has not built raises
     NotImplementedError.  take_bounds() then answers for the output rows."""
     global _last_bounds
     _last_bounds = None
     csr, agg_out, agg_mean = agg
-    dev = _lib.require_hip(first, agg_out, *[s.tensor for s in products], *[s.index for s in products])
+    if out is not None:
+        if not store_rows:
+            raise ValueError("out: given with store_rows=False (the launch stores no rows)")
+        _rows_f32(out, "out", cols=128, min_rows=n_rows)
+    dev = _lib.require_hip(first, agg_out, out, *[s.tensor for s in products], *[s.index for s in products])
     if dev != packed.device:
         raise RuntimeError(f"MLP weights on {packed.device}, inputs on {dev}")
     if packed.split != "f16x2" or packed.desc.n_layers != 3 or packed.seg_widths != (128,) or packed.n_out != 128 or packed.n_heads:
@@ -1612,7 +1629,8 @@ def mlp_forward_precomputed(packed: PackedMLP, first: Tensor, products: Sequence
         raise ValueError("mlp_forward_precomputed: the rows must be in segment order with segments of at most 32 rows")
     if agg_out.dtype != torch.float32:
         raise TypeError(f"aggregate: expected float32, got {agg_out.dtype}")
-    out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev) if store_rows else None
+    if out is None and store_rows:
+        out = torch.empty((n_rows, 128), dtype=torch.float32, device=dev)
     # the launch's descriptor: the image's own with layer 0 taken out of the stream (the bias block keeps layer 0's unused slot)
     desc = _lib.g4c_mlp_t()
     C.memmove(C.byref(desc), C.byref(packed.desc), C.sizeof(desc))

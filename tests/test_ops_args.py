@@ -151,6 +151,40 @@ def _cases():
                 "outputs-narrow": (dict(outputs=f(6, 2) if layout == "rows" else f(4, 6, 2)), ValueError, "outputs"),
                 "outputs-1d": (dict(outputs=f(72)), ValueError, "outputs"),
             })
+    # the caller's row tensors of the two launches that otherwise allocate them: checked before anything else of the call is looked at
+    # (the packed MLPs live on the device; nothing here gets as far as reading them)
+    add("mp_layer_forward", lambda e_out=None, agg_out=None, store_rows=True: ops.mp_layer_forward(
+            None, [ops.Source(f(10, 128))], 10, csr(), True, None, f(4, 128), 0, store_rows=store_rows, e_out=e_out, agg_out=agg_out),
+        dict(e_out=f(10, 128), agg_out=f(4, 128)), {
+            "e_out-f64": (dict(e_out=f(10, 128).double()), TypeError, "e_out"),
+            "e_out-list": (dict(e_out=[0.0]), TypeError, "e_out"),
+            "e_out-3d": (dict(e_out=f(10, 128, 1)), ValueError, "e_out"),
+            "e_out-rows": (dict(e_out=f(9, 128)), ValueError, "e_out"),
+            "e_out-cols": (dict(e_out=f(10, 136)), ValueError, "e_out"),
+            "e_out-colstride": (dict(e_out=f(128, 10).t()), ValueError, "e_out"),
+            "e_out-not-stored": (dict(store_rows=False), ValueError, "e_out"),
+            "agg_out-bf16": (dict(agg_out=f(4, 128).bfloat16()), TypeError, "agg_out"),
+            "agg_out-rows": (dict(agg_out=f(3, 128)), ValueError, "agg_out"),
+            "agg_out-cols": (dict(agg_out=f(4, 64)), ValueError, "agg_out"),
+            "agg_out-colstride": (dict(agg_out=f(128, 4).t()), ValueError, "agg_out"),
+            "agg_out-1d": (dict(agg_out=f(512)), ValueError, "agg_out"),
+        })
+    add("mp_layer_forward[window]", lambda e_out, agg_out: ops.mp_layer_forward(
+            None, [ops.Source(f(10, 128))], 10, csr(), True, None, f(4, 128), 0, e_out=e_out, agg_out=agg_out),
+        dict(e_out=f(12, 144)[1:11, 8:136], agg_out=f(6, 144)[1:5, 8:136]), {
+            "e_out-rows-overlap": (dict(e_out=f(10, 128).as_strided((10, 128), (64, 1))), ValueError, "e_out"),
+        })
+    add("mlp_forward_precomputed", lambda out=None, store_rows=True: ops.mlp_forward_precomputed(
+            None, f(10, 128), [], 10, (csr(), f(4, 128), True), store_rows=store_rows, out=out),
+        dict(out=f(10, 128)), {
+            "out-f64": (dict(out=f(10, 128).double()), TypeError, "out"),
+            "out-none-tensor": (dict(out=(1, 2)), TypeError, "out"),
+            "out-3d": (dict(out=f(10, 128, 1)), ValueError, "out"),
+            "out-rows": (dict(out=f(9, 128)), ValueError, "out"),
+            "out-cols": (dict(out=f(10, 120)), ValueError, "out"),
+            "out-colstride": (dict(out=f(128, 10).t()), ValueError, "out"),
+            "out-not-stored": (dict(store_rows=False), ValueError, "out"),
+        })
     return C
 
 
