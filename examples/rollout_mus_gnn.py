@@ -39,3 +39,5 @@ torch.cuda.synchronize(); dt = time.perf_counter() - t0
 print(f"{a.steps} steps on {a.nodes} nodes: {a.steps / dt:.1f} steps/s, output {tuple(out.shape)}, finite={bool(torch.isfinite(out).all())}")
 diag = model.diagnostics(graph, a.steps, ("div", "vort"))      # divergence and vorticity of every step, formed on the device: no prediction is held
 print("divergence RMS per step:", " ".join(f"{v:.3e}" for v in diag.rms[:, 0].tolist()))
+spec = model.spectrum(graph, a.steps, bins=range(a.steps // 2 + 1))     # Fourier modes of u, v, p at every node, accumulated inside the step
+print(f"dominant frequency of u: {spec.dominant(0):.4f} cycles per step, largest amplitude there {spec.amplitude[:, 0].max():.3e}")

@@ -95,6 +95,15 @@ class g4c_rollout_moments_t(C.Structure):
                 ("hi", C.c_void_p)]
 
 
+SPECTRUM_MAX_BINS = 64                              # most frequencies g4c_rollout_spectrum accumulates
+
+
+class g4c_rollout_spectrum_t(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("stride", C.c_int32), ("n_samples", C.c_int32), ("n_bins", C.c_int32), ("window", C.c_void_p),
+                ("tw", C.c_void_p), ("x_ld", C.c_int32), ("x_step", C.c_int32), ("plane_ld", C.c_int64), ("pivot", C.c_void_p),
+                ("sum", C.c_void_p), ("re", C.c_void_p), ("im", C.c_void_p)]
+
+
 DERIVED_MAX_COLS, DERIVED_MAX_TERMS = 8, 3         # G4C_DERIVED_MAX_COLS / _TERMS
 DERIVED_SQ, DERIVED_ABS, DERIVED_MAX_ABS, DERIVED_NSTAT = range(4)     # G4C_DERIVED_*
 
@@ -150,6 +159,7 @@ _SIGNATURES = {
     "g4c_rollout_advance_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_rec_t),
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_rollout_moments": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_moments_t), C.c_void_p, C.c_int64, C.c_void_p]),
+    "g4c_rollout_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_spectrum_t), C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_mesh_gradient_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),

@@ -193,7 +193,7 @@ class GNN(nn.Module):
 
     def evaluate(self, graph: Union[Graph, List[Graph]], n_out: Optional[int] = None, *, every: int = 0, probes: Optional[torch.Tensor] = None,
                  capture: Optional[bool] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
-                 derived_moments=None, derived_options: Optional[dict] = None) -> "RolloutErrors":
+                 derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -202,16 +202,20 @@ class GNN(nn.Module):
         [P, num_fields * n_out]).  moments / error_moments (None, True, `start` or `(start, stride)`, as in `Rollout`) also attach the
         per-node time statistics of the prediction / of prediction − target (`.moments` / `.error_moments`: `RolloutMoments`).
         derived (a tuple of names: 'div', 'vort', 'grad:<f>') with derived_every / derived_moments / derived_options, as in `Rollout`,
-        attaches the flow diagnostics of the prediction (`.derived`: `RolloutDerived`).  A list of graphs is collated as in `solve`."""
+        attaches the flow diagnostics of the prediction (`.derived`: `RolloutDerived`).  spectrum (a `gfd.Spectrum`) attaches the
+        Fourier modes of the prediction and, by the same table, of the target (`.spectrum` / `.target_spectrum`: `RolloutSpectrum`).
+        A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
             n_out = int(target.size(1)) // int(self.num_fields)
         assert n_out > 0, "n_out must be greater than 0."
         with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True, moments=moments,
                            error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
-                           derived_options=derived_options) as ro:
+                           derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None) as ro:
             ro.run(n_out)
             errs = ro.errors()
+            if spectrum is not None:
+                errs.spectrum, errs.target_spectrum = ro.spectrum(), ro.target_spectrum()
             errs.moments = ro.moments() if ro._moments is not None else None
             errs.error_moments = ro.error_moments() if ro._error_moments is not None else None
             errs.derived = ro.derived() if ro._derived is not None else None
@@ -245,12 +249,33 @@ class GNN(nn.Module):
             mo.snapshots = ro.result() if int(every) else None
             return mo
 
+    def spectrum(self, graph: Union[Graph, List[Graph]], n_out: int, bins=None, freqs=None, *, discard: int = 0, stride: int = 1,
+                 samples: Optional[int] = None, dt: float = 1.0, taper: str = "rect", derived=None, every: int = 0,
+                 capture: Optional[bool] = None, **derived_options) -> "RolloutSpectrum":
+        """Roll the model out for n_out steps and return the Fourier modes of the prediction at every node (`RolloutSpectrum`: coeff,
+        amplitude, phase, power, band_power, dominant) at the frequencies `bins` or `freqs` name (`gfd.Spectrum`), over the samples
+        discard, discard + stride, ... < n_out (0-based; `samples` of them, default all), accumulated on the device inside the step in
+        fp64.  No prediction is held (every = 0); every = k > 0 also keeps the snapshots solve(every=k) returns (`.snapshots`).
+        derived (a tuple of names, as in `diagnostics`, with its derived_options) also carries the spectrum of those columns
+        (`.derived`: the mode shape of the vorticity at the shedding frequency).  A list of graphs is collated as in `solve`."""
+        assert n_out > 0, "n_out must be greater than 0."
+        spec = Spectrum(bins, freqs, start=discard, stride=stride, samples=samples, dt=dt, taper=taper)
+        with self._rollout(graph, n_out, capture, "spectrum()", every=int(every), spectrum=spec, derived=derived,
+                           derived_spectrum=spec if derived is not None else None, derived_options=derived_options or None) as ro:
+            ro.run(n_out)
+            sp = ro.spectrum()
+            sp.snapshots = ro.result() if int(every) else None
+            sp.derived = ro.derived_spectrum() if derived is not None else None
+            return sp
+
     def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
         """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
         if records.get("derived") is not None:            # (argument errors before anything is collated or moved)
             for gr in (graph if type(graph) is list else [graph]):
                 _check_derived(gr, int(self.num_fields), n_out, records["derived"], records.get("derived_every", 0),
-                               records.get("derived_moments"), records.get("derived_options"), in_list=type(graph) is list)
+                               records.get("derived_moments"), records.get("derived_options"), in_list=type(graph) is list,
+                               spectrum=records.get("derived_spectrum"))
+        _check_spectrum("spectrum", records.get("spectrum"), int(self.num_fields), n_out)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -397,7 +422,8 @@ class Rollout:
     def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
                  label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
                  mask: Optional[torch.Tensor] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
-                 derived_moments=None, derived_options: Optional[dict] = None):
+                 derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None,
+                 target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -424,8 +450,21 @@ class Rollout:
         `g4c_rollout_moments`.  `derived_options`: power (0, 1, 2; default 2), edge_vectors ([E, dim], caller's edge order: the
         wrapped, unscaled `edge_attr` of a periodic mesh), velocity (the fields of the velocity components, default 0 .. dim - 1),
         field_scale ([nf], multiplied into the coefficients).  Steps run again after `rewind()` or a recomputation overwrite
-        their slots."""
-        derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options)
+        their slots.
+
+        Fourier modes at every node (opt-in, no record either): `spectrum` — a `gfd.Spectrum`: K frequencies, a lattice of samples
+        start, start + stride, ..., a taper — accumulates the discrete Fourier transform of the prediction at those frequencies, one
+        `g4c_rollout_spectrum` launch per step after the moments, in front of the closing launch; `target_spectrum=True` (needs
+        `target=` and `spectrum=`) the same of the target's columns, by the same table; `derived_spectrum` (a `gfd.Spectrum`, needs
+        `derived=`) of the derived columns.  `spectrum()` / `target_spectrum()` / `derived_spectrum()` return them
+        (`RolloutSpectrum`); after `rewind()` or a recomputation they hold the steps taken since."""
+        derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options,
+                                      spectrum=derived_spectrum)
+        spectrum_spec = _check_spectrum("spectrum", spectrum, int(model.num_fields), int(max_steps))
+        if not isinstance(target_spectrum, bool):
+            raise TypeError(f"target_spectrum: expected a bool, got {target_spectrum!r}")
+        if target_spectrum and (target is None or spectrum_spec is None):
+            raise ValueError("target_spectrum: the spectrum of the target needs target= and spectrum= (it uses the same table)")
         window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
         error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
         if error_window is not None and target is None:
@@ -468,6 +507,8 @@ class Rollout:
         self._moments = None if window is None else _Moments(self, *window)
         self._error_moments = None if error_window is None else _Moments(self, *error_window, sub=self._rec.target)
         self._derived = None if derived_spec is None else _Derived(self, *derived_spec)
+        self._spectrum = None if spectrum_spec is None else _Spectrum(self, spectrum_spec)
+        self._target_spectrum = _Spectrum(self, spectrum_spec, x=self._rec.target, x_step=self.nf) if target_spectrum else None
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -485,6 +526,8 @@ class Rollout:
         for mo in (self._moments, self._error_moments):
             if mo is not None:
                 mo.accumulate(pred, self.step_counter)
+        for sp in self._spectra():
+            sp.accumulate(pred, self.step_counter)
         if self._rec is not None:
             self._rec.advance(self.field, pred, self.step_counter)
             return
@@ -610,6 +653,12 @@ class Rollout:
         for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None):
             if mo is not None:
                 mo.reset(self._first_slot)
+        for sp in self._spectra():
+            sp.reset(self._first_slot)
+
+    def _spectra(self):
+        return [sp for sp in (self._spectrum, self._target_spectrum, self._derived.spectrum if self._derived is not None else None)
+                if sp is not None]
 
     def _read_moments(self, mo: Optional["_Moments"], name: str) -> "RolloutMoments":
         if mo is None:
@@ -626,6 +675,25 @@ class Rollout:
         """The same of prediction − target over the window `error_moments=` asked for: `mean` is the bias field, `mean² + var` the
         mean-square error at every node."""
         return self._read_moments(self._error_moments, "error_moments")
+
+    def _read_spectrum(self, sp: Optional["_Spectrum"], name: str) -> "RolloutSpectrum":
+        if sp is None:
+            raise RuntimeError(f"{self.label}: no {name}= was asked for")
+        self.validate()
+        return sp.read(self._perm)
+
+    def spectrum(self) -> "RolloutSpectrum":
+        """The Fourier modes of the prediction at every node at the frequencies `spectrum=` asked for (`RolloutSpectrum`, fp64 device
+        tensors in the caller's rows) — validated first, like `result()`; one device -> host copy of two integers."""
+        return self._read_spectrum(self._spectrum, "spectrum")
+
+    def target_spectrum(self) -> "RolloutSpectrum":
+        """The same of the target's columns of the steps taken, by the same table (`target_spectrum=True`)."""
+        return self._read_spectrum(self._target_spectrum, "target_spectrum")
+
+    def derived_spectrum(self) -> "RolloutSpectrum":
+        """The same of the derived columns (`derived_spectrum=`): its fields are `derived().columns`."""
+        return self._read_spectrum(self._derived.spectrum if self._derived is not None else None, "derived_spectrum")
 
     def derived(self) -> "RolloutDerived":
         """The flow diagnostics `derived=` asked for, of the `steps_done` steps taken (`RolloutDerived`) — validated first, like
@@ -700,6 +768,12 @@ def _check_moments(name: str, spec, nf: int, max_steps: int):
     return int(start), int(stride)
 
 
+def _lattice_origin(start: int, stride: int, first_slot: int) -> int:
+    """The first step of the lattice start, start + stride, ... at or after `first_slot`."""
+    behind = max(first_slot - start, 0)
+    return start + -(-behind // stride) * stride
+
+
 class _Moments:
     """The accumulators of one per-node time statistic of a `Rollout` and the launch that updates them.  Allocated once, in the
     rollout's node numbering: one fp64 buffer of 4 nf + nf (nf + 1) / 2 planes of N (pivot, sum, sum2, min, max) and the device-side
@@ -718,8 +792,7 @@ class _Moments:
 
     def reset(self, first_slot: int) -> None:
         """origin = the first step of the lattice start, start + stride, ... at or after `first_slot`; nothing accumulated yet."""
-        behind = max(first_slot - self.start, 0)
-        self.origin = self.start + -(-behind // self.stride) * self.stride
+        self.origin = _lattice_origin(self.start, self.stride, first_slot)
         self.window[:1].fill_(self.origin)
         self.window[1:].fill_(-1)
 
@@ -799,13 +872,198 @@ class RolloutMoments:
                 f"nodes={int(self.pivot.size(0))})")
 
 
-def _check_derived(graph: Graph, nf: int, max_steps: int, derived, every, moments, options, in_list: bool = False):
+class Spectrum:
+    """A request for the Fourier modes of a rollout at every node (`Rollout(spectrum=)`, `GNN.evaluate(spectrum=)`; `GNN.spectrum`
+    builds one): the discrete Fourier transform at K chosen frequencies — `bins` (integers 0 <= b <= samples // 2: the frequencies
+    b / (samples stride dt), the exact bins of the window) or `freqs` (cycles per unit of time, at most the Nyquist frequency
+    0.5 / (stride dt)), exactly one of them — over the `samples` steps start, start + stride, ... (0-based; default: all of them up to
+    the rollout's end), `dt` the time of one step, `taper` "rect" or "hann".  Checked when the rollout is built."""
+
+    def __init__(self, bins=None, freqs=None, *, start: int = 0, stride: int = 1, samples: Optional[int] = None, dt: float = 1.0,
+                 taper: str = "rect"):
+        self.bins, self.freqs, self.start, self.stride, self.samples, self.dt, self.taper = bins, freqs, start, stride, samples, dt, taper
+
+    def __repr__(self):
+        which = f"bins={self.bins!r}" if self.bins is not None else f"freqs={self.freqs!r}"
+        return f"Spectrum({which}, start={self.start}, stride={self.stride}, samples={self.samples}, dt={self.dt}, taper={self.taper!r})"
+
+
+def _check_spectrum(name: str, spec, nf: int, max_steps: int):
+    """A `spectrum=` / `derived_spectrum=` argument of `Rollout` -> the window and the host table (a dict: start, stride, samples, dt,
+    taper, tw, w, freqs), or None when no spectrum is asked for.  Nothing is moved or allocated on a device."""
+    def integer(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if spec is None:
+        return None
+    if not isinstance(spec, Spectrum):
+        raise TypeError(f"{name}: expected a gfd.Spectrum or None, got {spec!r}")
+    if not integer(spec.start) or not integer(spec.stride) or not (spec.samples is None or integer(spec.samples)):
+        raise TypeError(f"{name}: start, stride and samples are integers (samples may be None), got {spec!r}")
+    if isinstance(spec.dt, bool) or not isinstance(spec.dt, (int, float)):
+        raise TypeError(f"{name}: dt: expected a number, got {spec.dt!r}")
+    if not isinstance(spec.taper, str):
+        raise TypeError(f"{name}: taper: expected 'rect' or 'hann', got {spec.taper!r}")
+    if spec.start < 0 or spec.start >= max_steps:
+        raise ValueError(f"{name}: start {spec.start} of a rollout of {max_steps} steps (0 <= start < max_steps)")
+    if spec.stride < 1:
+        raise ValueError(f"{name}: stride {spec.stride} (>= 1)")
+    lattice = len(range(spec.start, max_steps, spec.stride))
+    samples = lattice if spec.samples is None else spec.samples
+    if samples < 1 or samples > lattice:
+        raise ValueError(f"{name}: samples {samples} of the {lattice} steps {spec.start}, {spec.start + spec.stride}, ... < {max_steps} (1 <= samples <= {lattice})")
+    try:
+        tw, w, freqs = ops.spectrum_table(bins=spec.bins, freqs=spec.freqs, samples=samples, stride=spec.stride, dt=spec.dt, taper=spec.taper)
+    except (TypeError, ValueError) as e:
+        raise type(e)(f"{name}: {e}") from None
+    if nf > _lib.REC_MAX_NF:
+        raise NotImplementedError(f"{name}: the spectra cover up to {_lib.REC_MAX_NF} fields, got {nf}")
+    if int(tw.size(1)) > _lib.SPECTRUM_MAX_BINS:
+        raise NotImplementedError(f"{name}: {int(tw.size(1))} frequencies (at most {_lib.SPECTRUM_MAX_BINS} per spectrum)")
+    return dict(start=int(spec.start), stride=int(spec.stride), samples=int(samples), dt=float(spec.dt), taper=spec.taper, tw=tw, w=w, freqs=freqs)
+
+
+class _Spectrum:
+    """The accumulators of one per-node spectrum of a `Rollout` and the launch that updates them.  Allocated once, in the rollout's
+    node numbering: one fp64 buffer of `ops.spectrum_planes(nf, K)` planes of N (pivot, sum, re, im), the twiddle table uploaded once,
+    and the device-side window {origin, last}.  As for `_Moments`, `reset()` — a two-integer fill — is all `rewind()` and a
+    recomputation need.  `x`: the tensor sampled instead of the prediction (the records' target with x_step = nf, or the derived
+    columns), in the rollout's numbering."""
+
+    def __init__(self, ro: "Rollout", spec: dict, x: Optional[torch.Tensor] = None, x_step: int = 0, nf: Optional[int] = None):
+        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf if nf is None else int(nf)
+        self.nf, self.max_steps, self.spec, self.x, self.x_step = nf, ro.max_steps, spec, x, x_step
+        self.start, self.stride, self.K = spec["start"], spec["stride"], int(spec["tw"].size(1))
+        self.planes = torch.zeros((ops.spectrum_planes(nf, self.K), n), dtype=torch.float64, device=dev)
+        self.pivot, self.sum, self.re, self.im = self.planes.split((nf, nf, nf * self.K, nf * self.K))
+        self.tw = spec["tw"].to(dev)
+        self.window = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.reset(ro._first_slot)
+
+    def reset(self, first_slot: int) -> None:
+        self.origin = _lattice_origin(self.start, self.stride, first_slot)
+        self.window[:1].fill_(self.origin)
+        self.window[1:].fill_(-1)
+
+    def accumulate(self, pred, step) -> None:
+        ops.rollout_spectrum(pred if self.x is None else self.x, step, self.nf, self.max_steps, self.window, self.tw, self.pivot, self.sum,
+                             self.re, self.im, stride=self.stride, x_step=self.x_step)
+
+    def read(self, perm) -> "RolloutSpectrum":
+        origin, last = self.window.tolist()
+        count = (last - origin) // self.stride + 1 if last >= origin else 0
+
+        def rows(planes):                       # [planes, N] in the rollout's numbering -> [N, planes] in the caller's
+            cols = planes.t().contiguous()
+            if perm is None:
+                return cols
+            out = torch.empty_like(cols)
+            out[perm] = cols
+            return out
+
+        sp = self.spec
+        return RolloutSpectrum(count, origin, self.stride, sp["dt"], sp["taper"], sp["freqs"], sp["tw"], sp["w"], rows(self.pivot), rows(self.sum),
+                               rows(self.re).unflatten(1, (self.nf, self.K)), rows(self.im).unflatten(1, (self.nf, self.K)))
+
+
+class RolloutSpectrum:
+    """Per-node Fourier modes of a rollout (`Rollout.spectrum()` / `target_spectrum()` / `derived_spectrum()`, `GNN.spectrum()`,
+    `GNN.evaluate(spectrum=)`) at the K frequencies `freqs` (cycles per unit of time) over the `count` samples of the steps origin,
+    origin + stride, ... (`samples` make the window `complete`): the raw fp64 sums, as the device accumulated them — `pivot` [N, nf]
+    (the first sample), `sum` [N, nf] = Σ d, `re`, `im` [N, nf, K] = Σ_j d_j tw[j, k, 0 / 1] with d = sample − pivot — and the host table
+    they were formed with (`tw` [samples, K, 2] = (w_j cos θ_jk, −w_j sin θ_jk), `w` [samples]: the taper).  From them, `mean` =
+    pivot + Σd / count; `coeff` [N, nf, K] complex128 = ((re + i im) − (mean − pivot) W_k) / S with W_k = Σ_{j<count} tw[j, k] and S =
+    Σ_{j<count} w_j — the tapered Fourier transform of sample − mean, normalised so that A cos(ωt + φ) on a bin (t counted from the
+    origin) has coeff = (A / 2) e^{iφ}; `amplitude` = 2 |coeff|, `phase` = arg coeff, `power` = |coeff|²; `band_power(mask)` [nf, K]
+    their sum over the (masked) nodes; `dominant(field, mask)` the frequency of the largest band power (× D / U: the Strouhal
+    number).  `count == 0` raises on the derived quantities; a "hann" window that is not complete warns (its weights do not sum as
+    a Hann window's).  Works on tensors of any device.  `snapshots`: the rollout's `result()` when `GNN.spectrum(every=)` kept any;
+    `derived`: the spectrum of the derived columns when `GNN.spectrum(derived=)` asked for it; else None."""
+
+    def __init__(self, count: int, origin: int, stride: int, dt: float, taper: str, freqs: torch.Tensor, tw: torch.Tensor, w: torch.Tensor,
+                 pivot: torch.Tensor, sum: torch.Tensor, re: torch.Tensor, im: torch.Tensor, snapshots: Optional[torch.Tensor] = None):
+        if tw.dim() != 3 or int(tw.size(2)) != 2 or tuple(w.shape) != (int(tw.size(0)),) or tuple(freqs.shape) != (int(tw.size(1)),):
+            raise ValueError(f"tw: expected [samples, K, 2] with w [samples] and freqs [K], got {tuple(tw.shape)}, {tuple(w.shape)}, {tuple(freqs.shape)}")
+        n, nf, K = int(pivot.size(0)), int(pivot.size(-1)), int(tw.size(1))
+        for t, name, shape in ((pivot, "pivot", (n, nf)), (sum, "sum", (n, nf)), (re, "re", (n, nf, K)), (im, "im", (n, nf, K))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        self.count, self.samples, self.origin, self.stride, self.dt, self.taper = int(count), int(tw.size(0)), int(origin), int(stride), float(dt), taper
+        if not 0 <= self.count <= self.samples:
+            raise ValueError(f"count: {self.count} of a window of {self.samples} samples")
+        self.freqs, self.tw, self.w = freqs, tw, w
+        self.pivot, self.sum, self.re, self.im, self.snapshots, self.derived = pivot, sum, re, im, snapshots, None
+
+    @property
+    def fields(self) -> int:
+        return int(self.pivot.size(1))
+
+    @property
+    def complete(self) -> bool:
+        return self.count == self.samples
+
+    def _n(self) -> float:
+        if self.count <= 0:
+            raise RuntimeError("RolloutSpectrum: no sample of the window was accumulated (count == 0)")
+        return float(self.count)
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self.pivot + self.sum / self._n()
+
+    @property
+    def coeff(self) -> torch.Tensor:
+        n = self._n()
+        if self.taper == "hann" and not self.complete:
+            warnings.warn(f"RolloutSpectrum: {self.count} of the {self.samples} samples of a 'hann' window were accumulated: the taper was "
+                          "cut off, the coefficients are those of the truncated weights", RuntimeWarning, stacklevel=2)
+        tw, w = self.tw[:self.count].to(torch.float64), self.w[:self.count].to(torch.float64)
+        W = torch.complex(tw[..., 0].sum(0), tw[..., 1].sum(0)).to(self.re.device)           # [K]
+        S = float(w.sum())
+        shift = (self.sum / n).to(torch.complex128).unsqueeze(-1) * W                          # (mean − pivot) W_k, [N, nf, K]
+        return (torch.complex(self.re, self.im) - shift) / S
+
+    @property
+    def amplitude(self) -> torch.Tensor:
+        return 2.0 * self.coeff.abs()
+
+    @property
+    def phase(self) -> torch.Tensor:
+        return self.coeff.angle()
+
+    @property
+    def power(self) -> torch.Tensor:
+        c = self.coeff
+        return c.real ** 2 + c.imag ** 2
+
+    def band_power(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[nf, K]: the power summed over the nodes (`mask` bool [N]: over those nodes only)."""
+        p = self.power
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (int(p.size(0)),):
+                raise ValueError(f"mask: expected a bool tensor of shape ({int(p.size(0))},), got {getattr(mask, 'dtype', type(mask).__name__)} "
+                                 f"{tuple(getattr(mask, 'shape', ()))}")
+            p = p[mask.to(p.device)]
+        return p.sum(0)
+
+    def dominant(self, field: int = 0, mask: Optional[torch.Tensor] = None) -> float:
+        """The frequency (of `freqs`) with the largest band power of `field`."""
+        return float(self.freqs[int(self.band_power(mask)[field].argmax())])
+
+    def __repr__(self):
+        return (f"RolloutSpectrum(count={self.count}, samples={self.samples}, origin={self.origin}, stride={self.stride}, taper={self.taper!r}, "
+                f"fields={self.fields}, bins={int(self.tw.size(1))}, nodes={int(self.pivot.size(0))})")
+
+
+def _check_derived(graph: Graph, nf: int, max_steps: int, derived, every, moments, options, in_list: bool = False, spectrum=None):
     """The `derived*=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing is moved, the
-    library is not touched) -> (names, every, window or None, options), or None when no diagnostics are asked for."""
+    library is not touched) -> (names, every, window or None, options, spectrum or None), or None when no diagnostics are asked for."""
     from ..mesh_gradient import check_mesh, derived_terms
     if derived is None or derived is False:
         if (every not in (0, None)) or moments not in (None, False) or options:
             raise ValueError("derived: derived_every / derived_moments / derived_options were given without derived=")
+        if spectrum is not None:
+            raise ValueError("derived_spectrum: the spectrum of the derived columns needs derived=")
         return None
     if isinstance(every, bool) or not isinstance(every, int) or every < 0:
         raise ValueError(f"derived_every: expected an integer >= 0 (0: no snapshots, k: every k-th step), got {every!r}")
@@ -819,16 +1077,16 @@ def _check_derived(graph: Graph, nf: int, max_steps: int, derived, every, moment
     names = (derived,) if isinstance(derived, str) else derived
     terms = derived_terms(names, dim, nf, options.get("velocity"), options.get("field_scale"))
     window = _check_moments("derived_moments", moments, len(terms), max_steps)
-    return tuple(names), int(every), window, options
+    return tuple(names), int(every), window, options, _check_spectrum("derived_spectrum", spectrum, len(terms), max_steps)
 
 
 class _Derived:
     """The flow diagnostics of a `Rollout` and the launches that form them.  Everything is allocated here, once, in the rollout's
     node numbering: the operator (`MeshGradient` on the rollout's own graph — the caller's edge vectors follow the renumbered
     edges), the program, `cur` [N, nd], the per-step sums [max_steps, nd, 3] with their scratch, the snapshot slots, and the
-    accumulators of `g4c_rollout_moments` over `cur`."""
+    accumulators of `g4c_rollout_moments` and of `g4c_rollout_spectrum` over `cur`."""
 
-    def __init__(self, ro: "Rollout", names, every: int, window, options: dict):
+    def __init__(self, ro: "Rollout", names, every: int, window, options: dict, spectrum=None):
         from ..mesh_gradient import MeshGradient
         dev, n = ro.field.device, int(ro.graph.num_nodes)
         ev = options.get("edge_vectors")
@@ -847,6 +1105,7 @@ class _Derived:
         self.scratch = ops.mesh_derived_scratch(n, self.nd, dev)
         self.snap = torch.zeros((ro.max_steps // every, n, self.nd), dtype=torch.float32, device=dev) if every else None
         self.moments = None if window is None else _Moments(ro, *window, nf=self.nd)
+        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, nf=self.nd)       # (launched by `Rollout._one`)
 
     def launch(self, pred, step) -> None:
         ops.mesh_derived(pred, self.op.off, self.op.g, self.op.src, self.program, self.cur, step=step, every=self.every, snap=self.snap,
@@ -945,6 +1204,7 @@ class RolloutErrors:
         self.sums, self.n_nodes, self.n_masked, self.snapshots, self.probes = sums, int(n_nodes), n_masked, snapshots, probes
         self.moments = self.error_moments = None        # `RolloutMoments` when GNN.evaluate(moments= / error_moments=) asked for them
         self.derived = None                             # `RolloutDerived` when GNN.evaluate(derived=) asked for it
+        self.spectrum = self.target_spectrum = None     # `RolloutSpectrum` when GNN.evaluate(spectrum=) asked for them
         n = float(n_nodes)
         sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
         self.mse, self.mae, self.max_abs = sq / n, ab / n, mx

@@ -637,6 +637,136 @@ def rollout_moments(pred: Tensor, step: Tensor, nf: int, max_steps: int, window:
     _lib.check(lib.g4c_rollout_moments(_lib.ptr(pred), nf, C.byref(m), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def spectrum_planes(nf: int, K: int) -> int:
+    """Planes of one spectrum's accumulators: pivot and sum (nf each), re and im (nf K each, plane f K + k)."""
+    return 2 * nf + 2 * nf * K
+
+
+def spectrum_table(*, bins=None, freqs=None, samples: int, stride: int = 1, dt: float = 1.0, taper: str = "rect"):
+    """The twiddle table g4c_rollout_spectrum multiplies by, built on the host in numpy fp64 (the kernel calls no sin / cos):
+    (tw [samples, K, 2], w [samples], freqs [K]), fp64 CPU tensors.  Row j, bin k of `tw` is (w_j cos th_jk, -w_j sin th_jk) with
+    th_jk = 2 pi * (phase fraction of sample j at frequency k).  Exactly one of `bins` and `freqs` names the K frequencies:
+    bins — integers 0 <= b <= samples // 2, the frequency b / (samples stride dt), the fraction in exact integer arithmetic,
+    ((b j) mod samples) / samples; freqs — cycles per unit of time, 0 <= f dt stride <= 0.5 (above is aliasing), the fraction
+    fmod(f dt stride j, 1).  `stride` is the number of steps and `dt` the time of one step between two samples' steps.
+    taper: "rect" (w_j = 1) or "hann" (periodic: w_j = 0.5 - 0.5 cos(2 pi j / samples))."""
+    import numpy as np
+
+    def integer(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    def real(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+    what = "spectrum_table"
+    if not integer(samples) or not integer(stride):
+        raise TypeError(f"samples: {what}: samples and stride are integers, got {samples!r} and {stride!r}")
+    if not real(dt):
+        raise TypeError(f"dt: {what}: expected a number, got {dt!r}")
+    if samples < 1 or stride < 1:
+        raise ValueError(f"samples: {what}: samples = {samples} and stride = {stride} (both >= 1)")
+    if not (dt > 0 and dt < float("inf")):
+        raise ValueError(f"dt: {what}: {dt} (a finite time step > 0)")
+    if taper not in ("rect", "hann"):
+        raise ValueError(f"taper: {what}: {taper!r} ('rect' or 'hann')")
+    if (bins is None) == (freqs is None):
+        raise ValueError(f"bins: {what}: exactly one of bins= and freqs= names the frequencies")
+    samples, stride, dt = int(samples), int(stride), float(dt)
+    j = np.arange(samples, dtype=np.int64)
+    if bins is not None:
+        if torch.is_tensor(bins):
+            bins = bins.tolist()
+        if isinstance(bins, (str, bytes)) or not hasattr(bins, "__iter__"):
+            raise TypeError(f"bins: {what}: expected a sequence of integers, got {bins!r}")
+        bins = list(bins)
+        if not all(integer(b) for b in bins):
+            raise TypeError(f"bins: {what}: expected a sequence of integers, got {bins!r}")
+        if not bins:
+            raise ValueError(f"bins: {what}: no frequency was given")
+        if min(bins) < 0 or max(bins) > samples // 2:
+            raise ValueError(f"bins: {what}: bins {min(bins)} .. {max(bins)} of {samples} samples (0 <= b <= samples // 2 = {samples // 2})")
+        b = np.asarray(bins, dtype=np.int64)
+        f = b.astype(np.float64) / (samples * stride * dt)
+        frac = ((j[:, None] * b[None, :]) % samples).astype(np.float64) / samples
+    else:
+        if torch.is_tensor(freqs):
+            freqs = freqs.tolist()
+        if isinstance(freqs, (str, bytes)) or not hasattr(freqs, "__iter__"):
+            raise TypeError(f"freqs: {what}: expected a sequence of numbers, got {freqs!r}")
+        freqs = list(freqs)
+        if not all(real(v) for v in freqs):
+            raise TypeError(f"freqs: {what}: expected a sequence of numbers, got {freqs!r}")
+        if not freqs:
+            raise ValueError(f"freqs: {what}: no frequency was given")
+        f = np.asarray(freqs, dtype=np.float64)
+        per_sample = f * dt * stride                     # cycles between two samples
+        if not np.all((per_sample >= 0) & (per_sample <= 0.5 * (1.0 + 1e-12))):          # (the Nyquist frequency as 0.5 / (stride dt), rounded)
+            raise ValueError(f"freqs: {what}: 0 <= f dt stride <= 0.5 cycles per sample (above is aliasing), got f dt stride = {per_sample.tolist()}")
+        frac = np.fmod(per_sample[None, :] * j[:, None].astype(np.float64), 1.0)
+    w = np.ones(samples, dtype=np.float64) if taper == "rect" else 0.5 - 0.5 * np.cos(2.0 * np.pi * j.astype(np.float64) / samples)
+    th = 2.0 * np.pi * frac
+    tw = np.stack([w[:, None] * np.cos(th), -(w[:, None] * np.sin(th))], axis=-1)
+    return torch.from_numpy(np.ascontiguousarray(tw)), torch.from_numpy(w), torch.from_numpy(np.ascontiguousarray(f))
+
+
+def rollout_spectrum(x: Tensor, step: Tensor, nf: int, max_steps: int, window: Tensor, tw: Tensor, pivot: Tensor, sum: Tensor, re: Tensor,
+                     im: Tensor, *, stride: int = 1, x_step: int = 0) -> None:
+    """g4c_rollout_spectrum: accumulate step t = step[0] (read on the device) into the per-node Fourier sums when t is sample
+    j = (t - origin) / stride of the window — 0 <= t < max_steps, t >= origin = window[0] (int32 [2] on the device: {origin, last}),
+    (t - origin) % stride == 0, j < samples — and leave window[1] = t; any other step touches nothing.  The sample is x [N, nf]
+    (x_step = 0: the prediction) or x[:, nf t : nf (t + 1)] of x [N, >= nf max_steps] (x_step = nf: a target), float32 with rows of
+    unit stride.  tw: float64 [samples, K, 2] (`spectrum_table`, on the device).  pivot / sum: float64 [nf, N]; re / im: float64
+    [nf K, N], plane f K + k; unit stride along the nodes and one common plane stride >= N (views of padded buffers are fine).
+    `step` is not written: the step's closing launch bumps it afterwards."""
+    nf, max_steps, stride, x_step = int(nf), int(max_steps), int(stride), int(x_step)
+    what = "rollout_spectrum"
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise TypeError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if nf <= 0 or x_step not in (0, nf):
+        raise ValueError(f"x_step: {what}: nf = {nf} (>= 1) and x_step = {x_step} (0: x is the sample, nf: x holds every step's columns)")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    cols = nf * max_steps if x_step else nf
+    if x.dim() != 2 or (int(x.size(1)) < cols if x_step else int(x.size(1)) != cols):
+        raise ValueError(f"x: {what}: expected [n_nodes, {'>= nf * max_steps' if x_step else 'nf'} = {cols}], got shape {tuple(x.shape)}")
+    n_nodes, width = int(x.size(0)), int(x.size(1))
+    if (n_nodes > 0 and width > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < width):
+        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    x_ld = max(int(x.stride(0)), width) if n_nodes > 1 else width
+    if x_ld >= 2 ** 31:
+        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
+    for t, name in ((step, "step"), (window, "window")):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise TypeError(f"{name}: {what}: expected an int32 tensor of two entries, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.dim() != 1 or t.numel() < 2 or not t.is_contiguous():
+            raise ValueError(f"{name}: {what}: expected an int32 tensor of two entries, got shape {tuple(t.shape)}")
+    if stride < 1:
+        raise ValueError(f"stride: {what}: {stride} (>= 1)")
+    if not torch.is_tensor(tw) or tw.dtype != torch.float64:
+        raise TypeError(f"tw: {what}: expected a float64 tensor, got {getattr(tw, 'dtype', type(tw).__name__)}")
+    if tw.dim() != 3 or int(tw.size(2)) != 2 or int(tw.size(0)) < 1 or int(tw.size(1)) < 1 or not tw.is_contiguous():
+        raise ValueError(f"tw: {what}: expected a contiguous [samples >= 1, K >= 1, 2], got shape {tuple(tw.shape)} strides {tuple(tw.stride())}")
+    samples, K = int(tw.size(0)), int(tw.size(1))
+    lds = set()
+    for t, name, planes in ((pivot, "pivot", nf), (sum, "sum", nf), (re, "re", nf * K), (im, "im", nf * K)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64:
+            raise TypeError(f"{name}: {what}: expected a float64 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if tuple(t.shape) != (planes, n_nodes):
+            raise ValueError(f"{name}: {what}: expected shape ({planes}, {n_nodes}), got {tuple(t.shape)}")
+        if n_nodes > 1 and t.stride(1) != 1:
+            raise ValueError(f"{name}: {what} needs unit stride along the nodes, got strides {tuple(t.stride())}")
+        if planes > 1 and n_nodes > 0:
+            lds.add(int(t.stride(0)))
+    if len(lds) > 1 or (lds and min(lds) < n_nodes):
+        raise ValueError(f"pivot: {what}: the accumulators need one common plane stride >= n_nodes = {n_nodes}, got {sorted(lds)}")
+    lib = _lib.load()
+    dev = _lib.require_hip(x, step, window, tw, pivot, sum, re, im)
+    s = _lib.g4c_rollout_spectrum_t(max_steps=max_steps, stride=stride, n_samples=samples, n_bins=K, window=_lib.ptr(window), tw=_lib.ptr(tw),
+                                    x_ld=x_ld, x_step=x_step, plane_ld=lds.pop() if lds else max(n_nodes, 1), pivot=_lib.ptr(pivot),
+                                    sum=_lib.ptr(sum), re=_lib.ptr(re), im=_lib.ptr(im))
+    _lib.check(lib.g4c_rollout_spectrum(_lib.ptr(x), nf, C.byref(s), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
+
+
 def _mesh_arg(what, t, name, dtype, shape=None, dim=None):
     """dtype, contiguity and shape of one tensor argument of ops.mesh_*: ValueError naming the argument."""
     if not torch.is_tensor(t) or t.dtype != dtype:

@@ -498,6 +498,39 @@ typedef struct g4c_rollout_moments {
 int g4c_rollout_moments(const float *pred, int32_t nf, const g4c_rollout_moments_t *m /*host*/, const int32_t *step, int64_t n_nodes,
                         void *stream);
 
+/* Fourier modes of a rollout at every node (csrc/rollout_spectrum.hip): a discrete Fourier transform at n_bins chosen frequencies,
+ * accumulated per node and field inside the step.  One launch per step and accumulator set, AFTER the forward (and after
+ * g4c_mesh_derived for derived columns) and BEFORE the step's closing launch (which bumps the step index this one reads, t = step[0],
+ * on the same stream).  Writes neither x nor step.
+ * The sample of node n and field f < nf is x_f = (double)x[n x_ld + x_step t + f]: the prediction has x_ld = nf, x_step = 0; a target
+ * [n_nodes, >= nf max_steps] has x_ld = its row stride and x_step = nf (the spectrum of the ground truth, by the same code).
+ * With origin = window[0] read on the device (a captured launch follows a rewritten origin) and j = (t - origin) / stride, step t is
+ * accumulated iff n_nodes > 0, 0 <= t < max_steps, t >= origin, (t - origin) % stride == 0 and j < n_samples; an accumulated step
+ * leaves window[1] = t, any other step touches nothing.
+ * The twiddles are an input: tw is a device fp64 table [n_samples, n_bins, 2]; row j, bin k holds (w_j cos th_jk, -w_j sin th_jk), built
+ * on the host (the kernel calls no sin / cos, and any table will do).  At j == 0 the accumulators are STORED, not read: pivot = x,
+ * sum = re = im = 0 (no memset is ever needed; running through the origin again replaces the record).  At j > 0, with d_f = x_f -
+ * pivot_f: sum_f += d_f, re_fk += d_f tw[j,k,0], im_fk += d_f tw[j,k,1] (each product rounded to fp64 once, then added: no fused
+ * multiply-add).  Every accumulator receives one add per accumulated step, in time order, from one thread: the bits are a function of
+ * the data and the table alone (no atomics, nothing depends on the grid).
+ * All accumulators are fp64 and plane-major: plane p of node n at base[p * plane_ld + n], plane_ld >= n_nodes.  pivot and sum have nf
+ * planes, re and im nf n_bins planes each, plane f n_bins + k.  nf = 1 .. 8, n_bins = 1 .. 64 (G4C_EUNSUPPORTED above).
+ * n_nodes == 0 launches nothing and succeeds. */
+typedef struct g4c_rollout_spectrum {
+    int32_t max_steps;           /* capacity of the rollout (and of a target `x`), in steps */
+    int32_t stride;              /* >= 1 */
+    int32_t n_samples;           /* >= 1: rows of `tw` */
+    int32_t n_bins;              /* K */
+    int32_t *window;             /* device, {origin, last} */
+    const double *tw;            /* device, [n_samples, n_bins, 2] */
+    int32_t x_ld;                /* >= nf; >= nf * max_steps with x_step == nf */
+    int32_t x_step;              /* 0 or nf */
+    int64_t plane_ld;
+    double *pivot, *sum, *re, *im;              /* nf, nf, nf n_bins, nf n_bins planes */
+} g4c_rollout_spectrum_t;
+int g4c_rollout_spectrum(const float *x, int32_t nf, const g4c_rollout_spectrum_t *s /*host*/, const int32_t *step, int64_t n_nodes,
+                         void *stream);
+
 /* A least-squares gradient over the in-edges of a mesh, and the flow diagnostics of a rollout built on it (csrc/mesh_gradient.hip).
  *
  * g4c_mesh_gradient_weights — once per mesh.  Edges grouped by receiver: the s-th in-edge of node i is edge pe = perm[off[i] + s]
