@@ -72,7 +72,8 @@ class g4c_mlp_io_t(C.Structure):
                 ("mul", C.c_void_p * MAX_LAYERS), ("mul_ld", C.c_int32),
                 ("upd", C.POINTER(g4c_mlp_t)), ("v", C.c_void_p), ("v_ld", C.c_int32), ("v_act", C.c_int32),
                 ("v_out", C.c_void_p), ("v_out_ld", C.c_int32), ("range_flag", C.c_void_p),
-                ("save_dtype", C.c_int32), ("mul_dtype", C.c_int32)]
+                ("save_dtype", C.c_int32), ("mul_dtype", C.c_int32),
+                ("wg_rows", C.c_void_p), ("wg_seg", C.c_void_p), ("n_wg", C.c_int32), ("wg_pairs", C.c_int32), ("wg_max_seg", C.c_int32)]
 
     def __init__(self, **kw):
         super().__init__(size=C.sizeof(g4c_mlp_io_t), **kw)
@@ -137,12 +138,15 @@ _SIGNATURES = {
                                      C.c_int32, C.c_int32, C.c_void_p]),
     "g4c_mlp_run": (C.c_int, [C.POINTER(g4c_mlp_t), C.POINTER(g4c_src_t), C.c_int32, C.c_int64, C.POINTER(g4c_mlp_io_t), C.c_void_p]),
     "g4c_plan_tiles": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    "g4c_plan_row_ranges": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "g4c_mlp_ws_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "g4c_mlp_bx6i_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_ws_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_small_launch_tiles": (C.c_int, [C.c_int]),
     "g4c_layer_norm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_debug_mean_div": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_mlp_last_kernel": (C.c_int, []),
+    "g4c_mlp_last_row_ranges": (C.c_int, []),
     "g4c_mlp_shapes_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_last_shape": (C.c_int, []),
     "g4c_project_to_edges": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,

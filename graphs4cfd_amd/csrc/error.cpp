@@ -1,5 +1,6 @@
 #include "g4c_common.h"
 #include <atomic>
+#include <cstdlib>
 
 namespace g4c {
 static thread_local char g_err[512] = "";
@@ -34,6 +35,22 @@ int cu_count() {
 }  // namespace g4c
 
 extern "C" int g4c_version(void) { return 3; }
+namespace g4c {
+int ws_grid() {
+    int n = cu_count();
+    if (const char *cap = std::getenv("G4C_WS_MAX_GRID")) {
+        const int c = std::atoi(cap);
+        if (c >= 1 && c < n) n = c;
+    }
+    return n;
+}
+}  // namespace g4c
+extern "C" int g4c_mlp_ws_grid(const void *device_ptr, int32_t *n_wg) {
+    G4C_REQUIRE(device_ptr && n_wg, G4C_EINVAL, "g4c_mlp_ws_grid: null pointer");
+    g4c::DeviceGuard on_device(device_ptr);
+    *n_wg = g4c::ws_grid();
+    return G4C_OK;
+}
 extern "C" int g4c_device_info(const void *device_ptr, int32_t *device, int32_t *cu_count) {
     G4C_REQUIRE(device_ptr && device && cu_count, G4C_EINVAL, "g4c_device_info: null pointer");
     g4c::DeviceGuard on_device(device_ptr);

@@ -26,6 +26,7 @@ inline int check_launch(const char *what) {
 int visible_devices();
 // compute units of the CURRENT device (the one a launch that follows goes to); cached per device ordinal, thread-safe
 int cu_count();
+int ws_grid();          // persistent workgroups of a weight-stationary launch: cu_count(), capped by G4C_WS_MAX_GRID
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(const void *device_ptr) {

@@ -82,6 +82,9 @@ struct Params {
     int agg_ld, agg_mean;
     int agg_deg;              // > 0: every segment has exactly this many rows (G4C_AGG_UNIFORM)
     int agg_bf16;             // the aggregate is stored as bf16 rows in the row-split order (G4C_AGG_OUT_BF16; mlp_rs1_kernel only)
+    // row ranges per workgroup for dense pairs over segments of any length (g4c_plan_row_ranges; null: none — mlp_ws.hip, ANY)
+    const int *wg_rows, *wg_seg;
+    int n_wg, wg_pairs, wg_max_seg;
     // narrow input blocks of the first layer, multiplied in fp32 on the vector ALUs (bf16x6 kernel)
     NarSrc nar[G4C_MAX_SRC];
     int n_nar;
@@ -359,7 +362,7 @@ struct Launch {
     bool deep_ring, shapes;
 };
 // what a family's launch ran: g4c_mlp_last_kernel() / g4c_mlp_last_shape() of the call
-struct Ran { int kernel = G4C_KERNEL_NONE, shape = G4C_TILE_SHAPE_GENERIC; };
+struct Ran { int kernel = G4C_KERNEL_NONE, shape = G4C_TILE_SHAPE_GENERIC, ranges = 0; };          // (ranges: workgroups of the row-range form, else 0)
 
 // What the envelopes of the two column-split message kernels (mlp_bx6i.hip, mlp_ws.hip) share: an inference launch of ONE weighted
 // 128-wide 16-byte addressable block and no or two aligned 128-wide additive blocks, no narrow blocks, heads or residual; 128-wide
@@ -386,6 +389,7 @@ int tile_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool bx6i_takes(const Launch &L);            // dual-tile software-pipelined kernel (mlp_bx6i.hip): bf16x6 stream only
 int bx6i_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool ws_takes(const Launch &L);              // weight-stationary persistent kernel (mlp_ws.hip): f16x3 and rounded-bf16 streams; io->upd
+bool ws_any_takes(const Launch &L);          // ... its dense pairs for segments of any length (Params::wg_rows): the one form without tiles of whole segments
 bool ws_pre_takes(const Launch &L);          // ... its "first layer precomputed" form (Launch::pre): the one family that runs such a call
 int ws_launch(const Launch &L, hipStream_t st, Ran &ran);
 bool rs_takes(const Launch &L);              // row-split persistent kernel (mlp_rs.hip): G4C_WFMT_BF16_RS, hoisted message form

@@ -77,8 +77,9 @@ int stage_call(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t n_src, int64
     G4C_REQUIRE(io->n_heads >= 0 && io->n_heads <= G4C_MAX_HEADS, G4C_EINVAL, "g4c_mlp_run: bad heads (n=%d)", io->n_heads);
     G4C_REQUIRE((L.row_begin == 0 && L.row_count == n_rows) || (!L.agg && !L.save && !L.has_node && !io->n_heads && !io->out_dtype),
                 G4C_EUNSUPPORTED, "g4c_mlp_run: a row sub-range needs a plain launch (no heads / aggregation / save / upd / out_dtype)");
-    G4C_REQUIRE(!L.agg || (io->tile_rows && io->tile_seg && io->seg_off && io->n_tiles >= 0 && io->agg_ld >= NP), G4C_EINVAL,
-                "g4c_mlp_run: bad aggregation plan");
+    // (the plan: tiles of whole segments; row ranges alone — segments longer than a tile — run on the one form that needs no tiles)
+    G4C_REQUIRE(!L.agg || (io->seg_off && io->agg_ld >= NP && ((io->tile_rows && io->tile_seg && io->n_tiles >= 0) || (io->wg_rows && !io->tile_rows))),
+                G4C_EINVAL, "g4c_mlp_run: bad aggregation plan");
     G4C_REQUIRE(io->out_dtype == G4C_DTYPE_F32 || io->out_dtype == G4C_DTYPE_BF16 || io->out_dtype == G4C_DTYPE_BF16_SELU, G4C_EINVAL,
                 "g4c_mlp_run: unknown out_dtype %d", io->out_dtype);
     G4C_REQUIRE(io->out_dtype != G4C_DTYPE_BF16_SELU || (L.agg && io->act == G4C_ACT_NONE), G4C_EINVAL,
@@ -204,6 +205,11 @@ int stage_outputs(const g4c_mlp_io_t *io, Launch &L) {
         // already tied an aggregation to the whole row range.)
         G4C_REQUIRE(p.agg_deg == 0 || L.row_begin == 0, G4C_EINVAL,
                     "g4c_mlp_run: uniform segments (G4C_AGG_UNIFORM) need the whole row range, got rows [%lld, %lld)", L.row_begin, p.M);
+        if (io->wg_rows) {
+            G4C_REQUIRE(io->wg_seg && io->n_wg >= 1 && io->n_wg <= g4c::cu_count() && io->wg_pairs >= 1 && io->wg_max_seg >= 1 && L.row_begin == 0,
+                        G4C_EINVAL, "g4c_mlp_run: bad row ranges (n_wg=%d wg_pairs=%d wg_max_seg=%d)", io->n_wg, io->wg_pairs, io->wg_max_seg);
+            p.wg_rows = io->wg_rows; p.wg_seg = io->wg_seg; p.n_wg = io->n_wg; p.wg_pairs = io->wg_pairs; p.wg_max_seg = io->wg_max_seg;
+        }
     }
     if (io->out_dtype) {
         G4C_REQUIRE(L.round1 && !p.resid && !p.out_idx && p.n_out == NP && (!p.out || ((p.out_ld & 3) == 0 && ((uintptr_t)p.out & 7) == 0)), G4C_EUNSUPPORTED,
@@ -332,6 +338,7 @@ LaunchFn choose(Launch &L) {
         G4C_REQUIRE(L.f16x2, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the f16x3 format (G4C_WFMT_F16X2), got w_format %d", L.fmt);
         G4C_REQUIRE(L.p.n_layers == 3, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs three layers (two left), got %d", L.p.n_layers);
         G4C_REQUIRE(L.agg && !L.save, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the fused aggregation and no save");
+        G4C_REQUIRE(L.p.tile_rows, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the tiles of whole segments");
         G4C_REQUIRE(ws_pre_takes(L), nullptr,
                     "g4c_mlp_run: every source additive (first layer precomputed) is outside the weight-stationary kernel's envelope (three aligned "
                     "128-wide fp32 additive blocks — the first direct, two through indices —, a plain fp32 128-wide output, no heads / residual "
@@ -342,6 +349,13 @@ LaunchFn choose(Launch &L) {
         G4C_REQUIRE(ws_takes(L), nullptr,
                     "g4c_mlp_run: the message launch of the fused MP layer is outside the weight-stationary kernel's envelope (one 128-wide "
                     "weighted block, two 128-wide additive blocks, two or three 128-wide layers, aligned rows)");
+        G4C_REQUIRE(L.p.tile_rows || ws_any_takes(L), nullptr, "g4c_mlp_run: a fused MP layer without tiles of whole segments is outside the row-range form's envelope");
+        return ws_launch;
+    }
+    if (L.agg && !L.p.tile_rows) {
+        G4C_REQUIRE(!L.row_split && ws_takes(L) && ws_any_takes(L), nullptr,
+                    "g4c_mlp_run: an aggregation plan of row ranges alone needs the weight-stationary kernel's row-range form (f16x3, one direct "
+                    "128-wide weighted block, two 128-wide additive blocks, two or three layers, fp32 rows, ranges within what it stages on chip)");
         return ws_launch;
     }
     if (L.fmt == G4C_WFMT_BF16_RS) {
@@ -379,7 +393,7 @@ extern "C" int g4c_mlp_run(const g4c_mlp_t *mlp, const g4c_src_t *srcs, int32_t 
     if ((rc = stage_node(io, L))) return rc;
     // tiles: whole segments from the caller's plan with the fused aggregation (the row-split kernels cut the rows themselves and
     // do not look at it), else 32 rows each
-    L.p.n_tiles = (L.agg && !L.row_split) ? L.io_n_tiles : (int)((L.row_count + 31) / 32);
+    L.p.n_tiles = (L.agg && !L.row_split && io->tile_rows) ? L.io_n_tiles : (int)((L.row_count + 31) / 32);
     const LaunchFn launch = choose(L);
     if (!launch) return G4C_EUNSUPPORTED;
     if (L.p.n_tiles == 0) return G4C_OK;          // (nothing launches: g4c_mlp_last_kernel stays G4C_KERNEL_NONE)
@@ -392,3 +406,4 @@ extern "C" int g4c_mlp_small_launch_tiles(int n_tiles) { return knob(g_deep_tile
 extern "C" int g4c_mlp_shapes_enable(int on) { return knob(g_shapes, on, 1); }
 extern "C" int g4c_mlp_last_kernel(void) { return g_last.kernel; }
 extern "C" int g4c_mlp_last_shape(void) { return g_last.shape; }
+extern "C" int g4c_mlp_last_row_ranges(void) { return g_last.ranges; }

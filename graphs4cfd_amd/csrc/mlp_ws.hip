@@ -23,6 +23,8 @@
 // load), 0 or 2 additive 128-wide blocks (SP = 1: 2), two or three layers, 128-wide output rows without residual / heads; an output
 // index only without the fused aggregation.  mlp_ws_pre_kernel (ws_body<.., PRE>): the same body started from a precomputed first layer —
 // three additive blocks, no weighted block, the two layers left of three (f16x3, fused aggregation, tracked).
+// mlp_ws_any_kernel (ws_body<.., ANY>): dense 64-row pairs over segments of any length on one host-planned row range per workgroup
+// (g4c_plan_row_ranges) — the coarse levels' fused MP layers and plain message launches with the aggregation (f16x3, rows direct).
 #include "mlp_common.h"
 #include <cstdlib>
 using namespace g4cm;
@@ -577,6 +579,7 @@ struct WsArgs {
     int M, row_base, n_tiles;
     int *range_flag;
     int range_slot;
+    const int *wg_rows, *wg_seg;          // ANY: rows [wg_rows[i], wg_rows[i + 1]) = segments [wg_seg[i], wg_seg[i + 1]) of workgroup slot i
 };
 // the kernel's one parameter (one struct, so that the place of `q` in the argument segment is offsetof(WsKernArgs, q))
 struct WsKernArgs {
@@ -627,13 +630,23 @@ constexpr int G4C_WS_SP1_MINW = 2;
 // MP layer whose e never changes inside a rollout), and a tile's start values (T + P_r[row]) + P_c[col] are the layer-0
 // pre-activation itself.  What the other forms park is here the hidden-layer epilogue of those start values (EK 5), a pair has four
 // matrix phases instead of six, and every row of the next pair is gathered under this pair's phases (none in the tail).
-template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16, bool NODE, bool DENSE, bool TRACK, bool PRE>
+// ANY (mlp_ws_any_kernel below: f16x3 stream, additive blocks, fused aggregation, with or without NODE): dense pairs for segments of
+// ANY length.  The host splits the rows into one contiguous range per workgroup that starts and ends on a segment boundary
+// (g4c_plan_row_ranges: at most 64 P rows each for the smallest P the grid allows, WsArgs::wg_rows / wg_seg); a workgroup cuts ITS
+// range into pairs of 64 consecutive rows — full 32-row tiles, as DENSE does — and reduces from tables it stages in LDS once, in the
+// prologue: the range's segment offsets (sOff, relative to the range) and, per pair, the first segment that ends behind the pair's
+// first row (sCur).  The segment a pair's end cuts carries its partial sum in sCarry (wave 7 alone reads and writes it).
+constexpr int WS_ANY_MAX_SEG = 2048;          // segments of one workgroup's range (more: the launcher keeps the tiles of whole segments)
+constexpr int WS_ANY_MAX_PAIRS = 256;         // pairs of one workgroup's range
+template <bool AGG, bool DIRECT, bool ADDS, int SP, int NL, bool XB16, bool AB16, bool NODE, bool DENSE, bool TRACK, bool PRE, bool ANY = false>
 __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     const WsArgs &p = ka.a;
     const int n_pairs = ka.n_pairs;
     static_assert((SP == 1 || SP == 2) && (NL == 2 || NL == 3) && (SP == 1 || !XB16) && (SP == 1 || !AB16) && (ADDS || !AB16) &&
                   (!NODE || (AGG && SP == 2)) && (TRACK || SP == 2), "mlp_ws_kernel: unsupported instantiation");
     static_assert(!PRE || (AGG && DIRECT && ADDS && SP == 2 && NL == 3 && !NODE && TRACK), "mlp_ws_pre_kernel: unsupported instantiation");
+    static_assert(!ANY || (AGG && ADDS && SP == 2 && !DENSE && !PRE), "mlp_ws_any_kernel: unsupported instantiation");
+    constexpr bool DP = DENSE || ANY;          // the workgroup cuts its own row range [R0, R1) into pairs of 64 consecutive rows
     // an additive row piece as loaded: four fp32 values, or four bf16 values in two dwords (widened where they are added)
     typedef typename std::conditional<AB16, u32x2, f32x4>::type AddV;
     __shared__ __attribute__((aligned(16))) __bf16 sP[2 * TILE_BF16];      // operand planes of tiles A, B (34 816 B)
@@ -648,6 +661,8 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     __shared__ __attribute__((aligned(16))) float sCarry[NP];              // dense mode: partial sum of the segment cut by the end of a pair
     __shared__ __attribute__((aligned(16))) float sBiasN[NODE ? 3 * NP : 4];    // NODE: the node MLP's biases and LayerNorm parameters
     __shared__ __attribute__((aligned(16))) float sGBN[NODE ? 2 * NP : 4];
+    __shared__ int sOff[ANY ? WS_ANY_MAX_SEG + 2 : 1];          // ANY: seg_off[SG0 + i] - R0 of the range's segments [SG0, SG1]
+    __shared__ int sCur[ANY ? WS_ANY_MAX_PAIRS + 2 : 1];        // ANY: [k] first segment (- SG0) that ends behind row 64 k of the range; [pairs] = SG1 - SG0; last: SG0
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -667,7 +682,11 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     {
         const int G = gridDim.x, b = blockIdx.x;
         const int slot = (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3);
-        if constexpr (DENSE) {
+        if constexpr (ANY) {
+            R0 = __builtin_amdgcn_readfirstlane(p.wg_rows[slot]);
+            R1 = __builtin_amdgcn_readfirstlane(p.wg_rows[slot + 1]);
+            p_begin = 0; p_end = (R1 - R0 + 63) >> 6;          // (local pair numbers)
+        } else if constexpr (DENSE) {
             const int n_seg = p.M / KU;
             R0 = __builtin_amdgcn_readfirstlane((int)(((long long)slot * n_seg) / G) * KU);
             R1 = __builtin_amdgcn_readfirstlane((int)(((long long)(slot + 1) * n_seg) / G) * KU);
@@ -684,7 +703,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     // (the loads are issued where load_meta is called; fix_meta — the v_readfirstlanes that wait for them — an iteration later)
     auto load_meta = [&](int pair) __attribute__((always_inline)) {
         Meta m;
-        if constexpr (DENSE) {
+        if constexpr (DP) {
             if (pair > p_end - 1) pair = p_end - 1;
             const int r0 = R0 + 64 * pair, nr = (R1 - r0) < 64 ? (R1 - r0) : 64;
             m.r0[0] = r0; m.n[0] = nr < 32 ? nr : 32; m.r0[1] = r0 + 32; m.n[1] = nr - m.n[0];
@@ -733,7 +752,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
         const int *ix = (k == 0) ? ix0 : (k == 1 ? ix1 : ix2);
         const int *addr = ix ? ix + gr : dummy;
         int j = 0, ts = 0;
-        if (AGG && !DENSE) {
+        if (AGG && !DP) {
             const int q = tid - 256;
             const bool is_seg = q >= 0 && q < 2 * (SEGCAP + 1);
             ts = is_seg && q >= SEGCAP + 1 ? 1 : 0;
@@ -747,7 +766,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     };
     auto store_tables = [&](int v, int it) __attribute__((always_inline)) {
         if (tid < 192) sIdx[it & 1][tid] = v;
-        if (AGG && !DENSE && tid >= 256 && tid < 256 + 2 * (SEGCAP + 1)) sSeg[it & 3][tid - 256] = v;
+        if (AGG && !DP && tid >= 256 && tid < 256 + 2 * (SEGCAP + 1)) sSeg[it & 3][tid - 256] = v;
     };
     // input rows of the weighted block (park layout) and additive rows (accumulator layout) of a pair whose indices are in sIdx[ring].
     // Three batches of four 16-byte loads per lane, issued in three different phases: a CU's share of the HBM bandwidth is ~13 bytes
@@ -810,7 +829,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     // loop body, and with them the kernel kept 30-odd scalars in lanes of a vector register, read back with v_readlane in the loop.
     // The empty asm keeps hipcc from merging the recomputations back into one long-lived copy.)
     auto meta_at = [&](int pair_, const Meta &carried) __attribute__((always_inline)) {
-        if constexpr (DENSE) { asm volatile("" : "+s"(pair_)); return load_meta(pair_); }
+        if constexpr (DP) { asm volatile("" : "+s"(pair_)); return load_meta(pair_); }
         else return carried;
     };
     {
@@ -828,6 +847,21 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
     if (tid < NL * NP) sBias[tid] = p.b[tid];
     if (tid < NP) sZero[tid] = 0.f;
     if (tid < 2 * NP) sGB[tid] = p.gamma ? (tid < NP ? p.gamma[tid] : p.beta[tid - NP]) : 0.f;
+    if constexpr (ANY) {
+        // the range's tables: segment i (of SG1 - SG0) covers rows [b, e) of the range; it is the first segment that ends behind row
+        // 64 k for every pair start 64 k in [b, e) (k = 0: the range's first segment, whatever empty segments lead it)
+        const int G = gridDim.x, bx = blockIdx.x;
+        const int slot = (G & 7) ? bx : (bx & 7) * (G >> 3) + (bx >> 3);
+        const int SG0 = __builtin_amdgcn_readfirstlane(p.wg_seg[slot]), nseg = __builtin_amdgcn_readfirstlane(p.wg_seg[slot + 1]) - SG0;
+        for (int i = tid; i < nseg; i += 512) {
+            const int b = p.seg_off[SG0 + i] - R0, e = p.seg_off[SG0 + i + 1] - R0;
+            sOff[i] = b;
+            if (i == nseg - 1) sOff[nseg] = e;
+            for (int k = (b + 63) >> 6; (k << 6) < e; ++k)
+                if (k > 0) sCur[k] = i;
+        }
+        if (tid == 0) { sCur[0] = 0; sCur[p_end] = nseg; sCur[WS_ANY_MAX_PAIRS + 1] = SG0; }
+    }
     if constexpr (NODE) {
         const NodeParams &q = ka.q;
         if (tid < NL * NP) sBiasN[tid] = q.b[tid];
@@ -1085,6 +1119,49 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
                     if (hi && rest) *reinterpret_cast<f32x4 *>(sCarry + c4) = a;
                 }
             };
+            if constexpr (ANY) {
+                // The pair holds rows [base, base + nr) of the range as 64 contiguous fp32 rows (fA | fB).  Segments [lo, hi) end inside
+                // it; segment lo may have started before it (its partial sum waits in sCarry), segment hi may start inside it and end
+                // behind it (it leaves its partial sum in sCarry; lo == hi: a segment that spans the whole pair).  Whole segments: 32
+                // lanes per target over all 16 half-waves, as the table-driven path.  The two cut segments are wave 7's (lanes 0 - 31
+                // the leading one, lanes 32 - 63 the trailing one): it reads the carry before it writes the next in program order, and
+                // no other wave touches it.  The adds are in segment order from 0.f: the sums of g4c_segment_reduce, bit for bit.
+                const int base = itp << 6, nr = mm.n[0] + mm.n[1];
+                const int lo = sCur[itp], hi = sCur[itp + 1], sg0 = sCur[WS_ANY_MAX_PAIRS + 1];
+                for (int s = lo + (tid >> 5); s < hi; s += 16) {
+                    const int b = sOff[s] - base, e = sOff[s + 1] - base;
+                    if (b >= 0) reduce_rows(fA, b, e, sg0 + s);
+                }
+                if (wave == 7) {
+                    const bool trail = lane >= 32;
+                    const int s = trail ? hi : lo;
+                    const int b = sOff[s] - base, e = sOff[s + 1] - base;          // (s == SG1 - SG0 behind the last pair: b == nr, e never used)
+                    const bool on = trail ? b < nr : (lo < hi && b < 0);
+                    if (on) {
+                        const int rb = b > 0 ? b : 0, re = trail ? nr : e;
+                        f32x4 a = *reinterpret_cast<const f32x4 *>((b < 0 ? sCarry : sZero) + c4);
+                        for (int r0 = rb; r0 < re; r0 += 8) {
+                            f32x4 v[8];
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4 *>(fA + (r0 + u < re ? r0 + u : re - 1) * HS + c4);
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) {
+                                const bool in = r0 + u < re;
+#pragma unroll
+                                for (int el = 0; el < 4; ++el) a[el] += in ? v[u][el] : 0.f;
+                            }
+                        }
+                        if (trail) {
+                            *reinterpret_cast<f32x4 *>(sCarry + c4) = a;
+                        } else {
+                            const int len = sOff[s + 1] - sOff[s];
+                            if (p.agg_mean) a = g4c::mean_div4(a, len > 1 ? len : 1);
+                            *reinterpret_cast<f32x4 *>(p.agg + (long long)(sg0 + s) * p.agg_ld + c4) = a;
+                        }
+                    }
+                }
+                return;
+            }
             if constexpr (DENSE) {
                 typedef std::integral_constant<int, 4> K4; typedef std::integral_constant<int, 5> K5; typedef std::integral_constant<int, 6> K6;
                 typedef std::integral_constant<int, 7> K7; typedef std::integral_constant<int, 8> K8;
@@ -1147,7 +1224,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
             // ablations of the two tails as well: stamps 5 / 6 — the phases this form does not have — stay unwritten)
             WS_STAMP(0);
             Meta m3raw;
-            if constexpr (!DENSE) m3raw = load_meta(pair + 3);
+            if constexpr (!DP) m3raw = load_meta(pair + 3);
             const int tv = load_tables(meta_at(pair + 2, m2));
             // ---- the next pair's rows: T of its tile A here, its additive rows under M(B, 1), T of its tile B under M(A, 2), tile B's
             // additive rows under M(B, 2) — 2, 4, 2, 4 loads per lane, each batch a phase or more ahead of its use
@@ -1182,7 +1259,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
             start_values_pre(accB, ntB, adB);
             asm volatile("" : "+v"(accB[0]), "+v"(accB[1]) :: "memory");
             Meta m3;
-            if constexpr (!DENSE) m3 = fix_meta(m3raw);
+            if constexpr (!DP) m3 = fix_meta(m3raw);
             store_tables(tv, it + 2);
             WS_STAMP(8);
             if (!(G4C_WS_ABLATE & 256)) ln_tail(meta_at(pair, m0), it);
@@ -1191,14 +1268,14 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
             WS_STAMP(15);
             if (!(G4C_WS_ABLATE & 128)) agg_tail(meta_at(pair, m0), it);
             WS_STAMP(10);
-            if constexpr (!DENSE) { m0 = m1; m1 = m2; m2 = m3; }
+            if constexpr (!DP) { m0 = m1; m1 = m2; m2 = m3; }
         }
     } else
     for (int it = 0, pair = p_begin; pair < p_end; ++pair, ++it) {
         WS_STAMP(0);
         // ---- tables two pairs ahead (their meta was loaded an iteration ago), meta three pairs ahead
         Meta m3raw;
-        if constexpr (!DENSE) m3raw = load_meta(pair + 3);
+        if constexpr (!DP) m3raw = load_meta(pair + 3);
         const int tv = load_tables(meta_at(pair + 2, m2));
         // (tile A's planes were written in the previous iteration's last matrix phase — before the loop for the first pair — and
         // that phase's barrier lies between; nothing the stragglers of the previous tail still read is written in this phase)
@@ -1251,7 +1328,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
         // (the meta three pairs ahead, requested at the top: taken here, in front of the tail's stores — at the end of the iteration
         // the wait for these loads would also wait for every store of the tail, which memory acknowledges in order)
         Meta m3;
-        if constexpr (!DENSE) m3 = fix_meta(m3raw);
+        if constexpr (!DP) m3 = fix_meta(m3raw);
         gather_x(meta_at(pair + 1, m1), (it + 1) & 1, 1, xr[1], rawB);
         // the tables fetched at the top of this iteration (older than every other load in flight) go to the ring slot of the pair
         // whose rows were gathered in the previous iteration; the next iteration's top barrier publishes them
@@ -1275,7 +1352,7 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
         WS_STAMP(16);
         if constexpr (SP != 1) gather_adds(1, (it + 1) & 1, adB);
         WS_STAMP(10);
-        if constexpr (!DENSE) { m0 = m1; m1 = m2; m2 = m3; }
+        if constexpr (!DP) { m0 = m1; m1 = m2; m2 = m3; }
     }
 
     if constexpr (NODE) {
@@ -1292,8 +1369,15 @@ __device__ __forceinline__ void ws_body(const WsKernArgs &ka) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) { nc.paA[ks] = paA[ks]; nc.paB[ks] = paB[ks]; }
         // this workgroup's targets = the segments of its tiles
-        const int t1 = 2 * p_end < p.n_tiles ? 2 * p_end : p.n_tiles;
-        const int S0 = __builtin_amdgcn_readfirstlane(p.tile_seg[2 * p_begin]), S1 = __builtin_amdgcn_readfirstlane(p.tile_seg[t1]);
+        int S0, S1;
+        if constexpr (ANY) {          // the segments of its row range
+            const int G = gridDim.x, bx = blockIdx.x;
+            const int slot = (G & 7) ? bx : (bx & 7) * (G >> 3) + (bx >> 3);
+            S0 = __builtin_amdgcn_readfirstlane(p.wg_seg[slot]); S1 = __builtin_amdgcn_readfirstlane(p.wg_seg[slot + 1]);
+        } else {
+            const int t1 = 2 * p_end < p.n_tiles ? 2 * p_end : p.n_tiles;
+            S0 = __builtin_amdgcn_readfirstlane(p.tile_seg[2 * p_begin]); S1 = __builtin_amdgcn_readfirstlane(p.tile_seg[t1]);
+        }
         const NodeParams q = node_params_now();
         node_phase<SP, NL, TRACK>(nc, p.agg, p.agg_ld, q, S0, S1);
     }
@@ -1319,7 +1403,23 @@ __global__ __launch_bounds__(512, 2) void mlp_ws_pre_kernel(const WsKernArgs ka)
     ws_body<true, true, true, 2, 3, false, false, false, DENSE, true, true>(ka);
 }
 
-#if defined(G4C_WS_ISA_ONLY) && G4C_WS_ISA_ONLY == 2
+// dense pairs for segments of any length (ANY above): the plain message launch with the fused aggregation, and the fused MP layer
+template <int NL, bool NODE, bool TRACK>
+__global__ __launch_bounds__(512, 2) void mlp_ws_any_kernel(const WsKernArgs ka) {
+    ws_body<true, true, true, 2, NL, false, false, NODE, false, TRACK, false, true>(ka);
+}
+
+#if defined(G4C_WS_ISA_ONLY) && G4C_WS_ISA_ONLY == 3
+// -DG4C_WS_ISA_ONLY=3 (tests/test_ws_any_isa.py): nothing but the instantiations of mlp_ws_any_kernel
+template __global__ void mlp_ws_any_kernel<3, false, true>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<3, false, false>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<3, true, true>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<3, true, false>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<2, false, true>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<2, false, false>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<2, true, true>(const WsKernArgs);
+template __global__ void mlp_ws_any_kernel<2, true, false>(const WsKernArgs);
+#elif defined(G4C_WS_ISA_ONLY) && G4C_WS_ISA_ONLY == 2
 // -DG4C_WS_ISA_ONLY=2 (tests/test_ws_pre_isa.py): nothing but the two instantiations of the "first layer precomputed" form
 template __global__ void mlp_ws_pre_kernel<true>(const WsKernArgs);
 template __global__ void mlp_ws_pre_kernel<false>(const WsKernArgs);
@@ -1367,13 +1467,23 @@ bool ws_pre_takes(const Launch &L) {
     return ((uintptr_t)p.b & 15) == 0 && p.M < (1LL << 31);
 }
 
+// Dense pairs for segments of any length (mlp_ws_any_kernel): exactly what is instantiated — inside ws_takes, the f16x3 stream, rows
+// direct, the two additive blocks, the fused aggregation over segments that are not the uniform ones of the dense form, fp32 rows, row
+// ranges within what the kernel stages in LDS.
+bool ws_any_takes(const Launch &L) {
+    const Params &p = L.p;
+    if (!L.f16x2 || !L.agg || L.pre || !p.wg_rows || !p.wg_seg || p.src[0].idx || p.n_add != 2 || p.out_bf16) return false;
+    if (p.agg_deg >= 4 && p.agg_deg <= 8) return false;
+    return p.n_wg >= 1 && p.wg_pairs >= 1 && p.wg_pairs <= WS_ANY_MAX_PAIRS && p.wg_max_seg >= 1 && p.wg_max_seg <= WS_ANY_MAX_SEG;
+}
+
 int ws_launch(const Launch &L, hipStream_t st, Ran &ran) {
     const Params &p = L.p;
     if (L.pre) {
         // T takes the weighted block's place in the argument block (rows direct), the products are the two additive blocks
         const bool dense = p.agg_deg >= 4 && p.agg_deg <= 8;
         const int n_pairs = dense ? (int)((p.M + 63) / 64) : (p.n_tiles + 1) / 2;
-        const int n_wg = g4c::cu_count();
+        const int n_wg = g4c::ws_grid();
         const dim3 grid(n_pairs < n_wg ? n_pairs : n_wg), blk(512);
         ran.kernel = G4C_KERNEL_MLP_WS_PRE;
         WsArgs a{};
@@ -1391,13 +1501,14 @@ int ws_launch(const Launch &L, hipStream_t st, Ran &ran) {
         return g4c::check_launch("g4c_mlp_run (ws, first layer precomputed)");
     }
     const bool agg = L.agg, round1 = L.round1, node = L.has_node;
+    G4C_REQUIRE(!agg || p.tile_rows || ws_any_takes(L), G4C_EUNSUPPORTED, "g4c_mlp_run (ws): the fused aggregation without tiles of whole segments");
     // (dense mode — uniform segments of 4 .. 8 rows — cuts the rows into pairs of 64 itself: n_pairs only sizes the grid there)
     // Not for the fused MP layer: its launches are a few pairs per workgroup (nothing to win from denser pairs), and its three-layer
     // instantiation sits at 256 registers — with the dense bookkeeping it spills (config 2: 1 786 -> 1 734 steps/s, same box).
     const bool dense = agg && !node && p.agg_deg >= 4 && p.agg_deg <= 8;
     const int n_pairs = dense ? (int)((p.M + 63) / 64) : (p.n_tiles + 1) / 2;
     ran.kernel = G4C_KERNEL_MLP_WS;
-    const int n_wg = g4c::cu_count() * (round1 ? G4C_WS_SP1_MINW / 2 : 1);          // persistent workgroups: one (SP = 1: G4C_WS_SP1_MINW / 2) per CU
+    const int n_wg = g4c::ws_grid() * (round1 ? G4C_WS_SP1_MINW / 2 : 1);          // persistent workgroups: one (SP = 1: G4C_WS_SP1_MINW / 2) per CU
     const dim3 grid(n_pairs < n_wg ? n_pairs : n_wg), blk(512);
     const bool direct = p.src[0].idx == nullptr, adds = p.n_add == 2, two = p.n_layers == 2, xb16 = p.src[0].bf16 != 0;
     const bool ab16 = adds && p.add[0].bf16 != 0;
@@ -1417,6 +1528,22 @@ int ws_launch(const Launch &L, hipStream_t st, Ran &ran) {
     a.M = (int)p.M; a.row_base = (int)p.row_base; a.n_tiles = p.n_tiles;          // (ws_takes: M < 2^31)
     a.range_flag = p.range_certified ? nullptr : p.range_flag; a.range_slot = p.range_slot;
     const WsKernArgs ka{a, n_pairs, L.node};          // (the node update's parameters: zeros without one)
+    // Dense pairs for segments of any length (mlp_ws_any_kernel): the caller's row ranges, where the launch is of the instantiated form
+    // (f16x3, additive blocks, rows direct) and its segments are not the uniform ones of the dense form; a range beyond what the kernel
+    // stages in LDS keeps the tiles of whole segments.  One workgroup per range.
+    if (ws_any_takes(L)) {
+        WsKernArgs kr = ka;
+        kr.a.wg_rows = p.wg_rows; kr.a.wg_seg = p.wg_seg;
+        const dim3 grid_r(p.n_wg);
+        ran.ranges = p.n_wg;
+#define G4C_WS_ANY(NL, NODE)                                                                                   \
+    do { if (cert) mlp_ws_any_kernel<NL, NODE, false><<<grid_r, blk, 0, st>>>(kr);                             \
+         else mlp_ws_any_kernel<NL, NODE, true><<<grid_r, blk, 0, st>>>(kr); } while (0)
+        if (node) { if (two) G4C_WS_ANY(2, true); else G4C_WS_ANY(3, true); }
+        else { if (two) G4C_WS_ANY(2, false); else G4C_WS_ANY(3, false); }
+#undef G4C_WS_ANY
+        return g4c::check_launch(node ? "g4c_mlp_run (ws, upd, row ranges)" : "g4c_mlp_run (ws, row ranges)");
+    }
     if (node) {          // the fused MP layer (g4c_mlp_io_t.upd): f16x3 stream, hoisted message MLP, fused aggregation
         G4C_REQUIRE(agg && !round1 && adds, G4C_EUNSUPPORTED, "g4c_mlp_run (upd): needs the hoisted f16x3 message launch with the fused aggregation");
 #define G4C_WS_NODE(DIRECT, NL)                                                                                                        \

@@ -54,6 +54,68 @@ extern "C" int64_t g4c_plan_tiles(const int32_t *off, int32_t n_seg, int32_t max
     return nt;
 }
 
+// Row ranges for dense pairs over segments of any length (mlp_ws.hip, ANY): the rows are cut into n_wg contiguous ranges on segment
+// boundaries, each of at most cap = 64 P rows, for the smallest P for which that many ranges are enough.  What a launch of persistent
+// workgroups pays for is the workgroup with the most pairs, and P is that number: tiles of whole segments leave rows of every tile
+// unused, which on a grid of 256 can cost a whole round of pairs.  Among the plans with that P the rows are spread evenly (each range
+// ends on the boundary nearest to an even share of what is left, as far as the ranges behind it can still hold the rest): a fused
+// layer's node phase is proportional to a workgroup's targets.
+extern "C" int64_t g4c_plan_row_ranges(const int32_t *off, int32_t n_seg, int32_t n_wg, int32_t *wg_rows, int32_t *wg_seg,
+                                       int32_t *max_seg) {
+    G4C_REQUIRE(off && wg_rows && wg_seg && max_seg && n_seg >= 0 && n_wg >= 1 && off[0] == 0, G4C_EINVAL, "g4c_plan_row_ranges: bad arguments");
+    for (int32_t s = 0; s < n_seg; ++s)
+        G4C_REQUIRE(off[s + 1] >= off[s], G4C_EINVAL, "g4c_plan_row_ranges: offsets decrease at segment %d", s);
+    const int64_t rows = off[n_seg];
+    *max_seg = 0;
+    if (rows == 0) {
+        for (int32_t i = 0; i <= n_wg; ++i) { wg_rows[i] = 0; wg_seg[i] = i == 0 ? 0 : n_seg; }
+        // (no rows: nothing to launch; the segments, all empty, are range 0's on paper)
+        *max_seg = n_seg;
+        return 0;
+    }
+    // need[s]: fewest ranges of at most cap rows that cover segments [s, n_seg) (greedy from s is optimal); -1: a segment is too long
+    std::vector<int32_t> nxt((size_t)n_seg + 1), need((size_t)n_seg + 1);
+    auto count = [&](int64_t cap) -> int64_t {
+        int32_t e = n_seg;
+        need[(size_t)n_seg] = 0; nxt[(size_t)n_seg] = n_seg;
+        for (int32_t s = n_seg - 1; s >= 0; --s) {
+            while ((int64_t)off[e] - off[s] > cap) --e;          // furthest boundary a range that starts at s can reach
+            if (e == s) { if (off[s + 1] - off[s] > cap) return -1; }
+            // (trailing empty segments ride along with the last rows)
+            nxt[(size_t)s] = off[e] == off[n_seg] ? n_seg : e;
+            need[(size_t)s] = off[s] == off[n_seg] ? 0 : 1 + need[(size_t)nxt[(size_t)s]];
+        }
+        return need[0];
+    };
+    int64_t lo = (rows + 64LL * n_wg - 1) / (64LL * n_wg), hi = (rows + 63) / 64;          // (hi: one range holds everything)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2, c = count(64 * mid);
+        if (c >= 0 && c <= n_wg) hi = mid; else lo = mid + 1;
+    }
+    const int64_t P = lo, cap = 64 * P;
+    count(cap);
+    int32_t s = 0;
+    wg_rows[0] = 0; wg_seg[0] = 0;
+    for (int32_t i = 0; i < n_wg; ++i) {
+        const int32_t left = n_wg - i;
+        int32_t e;
+        if (off[s] == off[n_seg]) e = n_seg;                      // nothing left (an empty range: s == n_seg already)
+        else if (left == 1) e = n_seg;
+        else {
+            const int64_t want = off[s] + (rows - off[s] + left - 1) / left;
+            e = (int32_t)(std::lower_bound(off + s, off + n_seg + 1, (int32_t)want) - off);          // first boundary at or behind the even share
+            if (e > s && off[e] > want && want - off[e - 1] <= off[e] - want && off[e - 1] > off[s]) --e;      // the nearer one
+            if (e > nxt[(size_t)s]) e = nxt[(size_t)s];
+            while (off[e] == off[s] || need[(size_t)e] > left - 1) ++e;          // rows in every range; the rest must still fit (e <= nxt[s] holds)
+            if (off[e] == off[n_seg]) e = n_seg;
+        }
+        wg_rows[i + 1] = off[e]; wg_seg[i + 1] = e;
+        *max_seg = std::max(*max_seg, e - s);
+        s = e;
+    }
+    return P;
+}
+
 extern "C" int64_t g4c_plan_pool_edge_ordered(const int64_t *idx_hr_to_lr, int64_t n_hr, const int64_t *edge_index,
                                               int64_t n_edges, int32_t target_major, int64_t *coarse_edge_index, int32_t *perm,
                                               int32_t *off, int64_t *n_kept) {

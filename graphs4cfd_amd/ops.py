@@ -3,6 +3,7 @@
 Nothing here computes on the host or with torch ops."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -1647,10 +1648,58 @@ def _agg_mode(agg_mean: bool, csr: CsrPlan) -> int:
     return (1 if agg_mean else 0) | (csr.uniform_deg << 8)
 
 
-def _set_agg(io, csr: CsrPlan, agg_out: Tensor, agg_mean: bool) -> None:
-    t_rows, t_seg, nt = csr.tiles()
-    io.tile_rows, io.tile_seg, io.seg_off, io.n_tiles = _lib.ptr(t_rows), _lib.ptr(t_seg), _lib.ptr(csr.off), nt
+# Dense pairs for segments of any length (csrc/mlp_ws.hip, mlp_ws_any_kernel): an f16x3 launch with the fused aggregation whose segments
+# are not the uniform 4 .. 8 rows of the level-1 form also hands the library one row range per persistent workgroup (CsrPlan.row_ranges);
+# the library uses them where it has the form (the plain hoisted message launch, the fused MP layer) and ignores them elsewhere.
+# G4C_DENSE_ANY=0: the tiles of whole segments, as before (A/B runs) — the same results bit for bit either way.
+DENSE_ANY = os.environ.get("G4C_DENSE_ANY", "1") != "0"
+
+
+@contextlib.contextmanager
+def dense_any(on: bool):
+    """DENSE_ANY and `on` for the launches issued inside (the partitioned forwards: a rank's sub-mesh keeps its launches)."""
+    global DENSE_ANY
+    was, DENSE_ANY = DENSE_ANY, DENSE_ANY and on
+    try:
+        yield
+    finally:
+        DENSE_ANY = was
+
+
+def ws_grid(t: Tensor) -> int:
+    """Persistent workgroups of a weight-stationary launch on `t`'s device (g4c_mlp_ws_grid: one per compute unit, at most
+    G4C_WS_MAX_GRID)."""
+    n = C.c_int32(0)
+    _lib.check(_lib.load().g4c_mlp_ws_grid(t.data_ptr(), C.byref(n)))
+    return int(n.value)
+
+
+def _ranges_only(packed: "PackedMLP", sources: Sequence["Source"], csr: CsrPlan, agg_out: Tensor) -> bool:
+    """A plain message launch whose segments are longer than a tile (no CsrPlan.tiles()) can still reduce its own rows — on the row
+    ranges alone, in the one form that needs no tiles: the f16x3 stream, one direct 128-wide block and two additive 128-wide fp32
+    blocks, two or three layers (ws_any_takes, csrc/mlp_ws.hip)."""
+    if not (DENSE_ANY and packed.split == "f16x2" and packed.desc.n_layers in (2, 3) and packed.seg_widths == (128,) and len(sources) == 3):
+        return False
+    x, adds = sources[0], sources[1:]
+    if x.additive or x.index is not None or x.segments is not None or x.tensor.dtype != torch.float32 or x.col0 % 4 or _ld(x.tensor) % 4 or x.tensor.data_ptr() % 16:
+        return False
+    if any(not s.additive or s.width != 128 or s.tensor.dtype != torch.float32 or s.col0 % 4 or _ld(s.tensor) % 4 or s.tensor.data_ptr() % 16 for s in adds):
+        return False
+    return csr.perm is None and agg_out.dtype == torch.float32 and csr.row_ranges(ws_grid(agg_out)) is not None
+
+
+def _set_agg(io, csr: CsrPlan, agg_out: Tensor, agg_mean: bool, ranges: bool = False) -> None:
+    tiles = csr.tiles()
+    if tiles is not None:
+        io.tile_rows, io.tile_seg, io.n_tiles = _lib.ptr(tiles[0]), _lib.ptr(tiles[1]), tiles[2]
+    elif not (ranges and DENSE_ANY and csr.row_ranges(ws_grid(agg_out)) is not None):
+        raise ValueError("fused aggregation: the rows must be in segment order with segments of at most 32 rows")
+    io.seg_off = _lib.ptr(csr.off)
     io.agg, io.agg_ld, io.agg_mode = _lib.ptr(agg_out), _ld(agg_out), _agg_mode(agg_mean, csr)
+    if ranges and DENSE_ANY and not 4 <= csr.uniform_deg <= 8:
+        plan = csr.row_ranges(ws_grid(agg_out))
+        if plan is not None:
+            io.wg_rows, io.wg_seg, io.n_wg, io.wg_pairs, io.wg_max_seg = _lib.ptr(plan[0]), _lib.ptr(plan[1]), int(plan[0].numel()) - 1, plan[2], plan[3]
 
 
 def _set_heads(io, head_outs: Sequence[Tensor]) -> None:
@@ -1708,7 +1757,7 @@ def mp_layer_forward(msg: PackedMLP, sources: Sequence[Source], n_rows: int, csr
         raise ValueError(f"{n_heads} head outputs for a packing with {upd.n_heads} heads")
     io = _lib.g4c_mlp_io_t(row_count=n_rows, out=_lib.ptr(e_out), out_ld=128 if e_out is None else _ld(e_out), upd=C.pointer(upd.desc),
                            v=_lib.ptr(v), v_ld=_ld(v), v_act=act, v_out=_lib.ptr(v_out), v_out_ld=_ld(v_out))
-    _set_agg(io, csr, agg, agg_mean)
+    _set_agg(io, csr, agg, agg_mean, ranges=True)
     if n_heads:
         _set_heads(io, head_outs)
     in_b = 4.0 * 128 * (n_rows * (2 if store_rows else 1) + n_t * (2 + n_heads))
@@ -1859,7 +1908,8 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
             j += 1
     # store_rows=False (with a fused aggregation only): the output rows are not written, only their aggregate
     fusable = (agg is not None and FUSE_AGG and packed.precision in ("bf16x6", "bf16") and packed.n_out == 128 and head_outs is None
-               and rows is None and out_idx32 is None and resid is None and n_rows == agg[0].n and agg[0].tiles() is not None)
+               and rows is None and out_idx32 is None and resid is None and n_rows == agg[0].n
+               and (agg[0].tiles() is not None or _ranges_only(packed, sources, agg[0], agg[1])))
     if not store_rows and not fusable:
         raise ValueError("store_rows=False needs an aggregation the launch can fuse (ops.can_fuse_aggregation)")
     reduce_after = None
@@ -1903,7 +1953,7 @@ def mlp_forward(packed: PackedMLP, sources: Sequence[Source], n_rows: int, act: 
         _lib.require_hip(agg_out)
         if agg_out.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"aggregate: expected float32 (or bfloat16 on the row-split kernel), got {agg_out.dtype}")
-        _set_agg(io, csr, agg_out, agg_mean)
+        _set_agg(io, csr, agg_out, agg_mean, ranges=packed.split == "f16x2" and save is None)
         if agg_out.dtype == torch.bfloat16:          # (G4C_AGG_OUT_BF16: bf16 aggregate rows in the row-split kernel's column order)
             io.agg_mode |= 1 << 16
         out_b = 0 if not store_rows else packed.n_out * (2 if out.dtype == torch.bfloat16 else 4)

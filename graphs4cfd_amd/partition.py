@@ -463,6 +463,11 @@ class MusPartitionedForward:
         return self.impl.new(m.n_own[level - 1] + m.n_halo[level - 1], self.width, m.device)
 
     def forward(self) -> torch.Tensor:
+        # (a rank's sub-mesh keeps the launches it had: no dense pairs over its ragged segments — ops.DENSE_ANY)
+        with ops.dense_any(False):
+            return self._forward()
+
+    def _forward(self) -> torch.Tensor:
         m, impl = self.mesh, self.impl
         level = 1
         v = self._buf(1)

@@ -337,6 +337,11 @@ class RemusPartitionedForward:
         self.program, self.mesh, self.impl, self.xch = program, mesh, impl, exchanger
 
     def forward(self) -> torch.Tensor:
+        # (a rank's sub-mesh keeps the launches it had: no dense pairs over its ragged segments — ops.DENSE_ANY)
+        with ops.dense_any(False):
+            return self._forward()
+
+    def _forward(self) -> torch.Tensor:
         impl, x = self.impl, self.xch
         e, a, ax = impl.encode()
         fresh = {l: False for l in e}            # whether the halo rows of e[l] hold the peers' current latents

@@ -34,6 +34,7 @@ class CsrPlan:
     max_deg: int
     uniform_deg: int = 0           # k when EVERY segment has exactly k rows (kNN meshes), else 0
     _tiles: object = False         # cache of tiles(): False = not built yet, None = not tileable
+    _ranges: object = None         # cache of row_ranges(): {n_wg: plan or None}
 
     def tiles(self, max_rows: int = 32):
         """(tile_rows int32 [T+1], tile_seg int32 [T+1], T) on the device: tiles of whole segments of at most `max_rows`
@@ -51,6 +52,39 @@ class CsrPlan:
                     dev = self.off.device
                     self._tiles = (_upload(rows[: nt + 1].copy(), dev), _upload(seg[: nt + 1].copy(), dev), nt)
         return self._tiles
+
+    def row_ranges(self, n_wg: int):
+        """(wg_rows int32 [n_wg+1], wg_seg int32 [n_wg+1], P, max_seg) on the device: the rows cut into one contiguous range per
+        persistent workgroup, on segment boundaries, each of at most 64 P rows for the smallest possible P (g4c_plan_row_ranges) — what
+        the weight-stationary kernel's dense pairs for segments of any length run on (g4c_mlp_io_t.wg_rows).  Cached per grid size.
+        None when the rows are not in segment order, there are none, or a range is more than the kernel stages on chip."""
+        if self._ranges is None:
+            self._ranges = {}
+        if n_wg not in self._ranges:
+            out = None
+            if self.perm is None and self.n > 0 and n_wg >= 1:
+                off = np.ascontiguousarray(_host_i64(self.off).astype(np.int32))
+                rows, seg, pairs, max_seg = row_ranges_host(off, n_wg)
+                if pairs <= RANGE_MAX_PAIRS and max_seg <= RANGE_MAX_SEGS:
+                    dev = self.off.device
+                    out = (_upload(rows, dev), _upload(seg, dev), pairs, max_seg)
+            self._ranges[n_wg] = out
+        return self._ranges[n_wg]
+
+
+RANGE_MAX_PAIRS, RANGE_MAX_SEGS = 256, 2048      # WS_ANY_MAX_PAIRS / WS_ANY_MAX_SEG of csrc/mlp_ws.hip
+
+
+def row_ranges_host(off: np.ndarray, n_wg: int):
+    """g4c_plan_row_ranges on host offsets (int32 [n_seg+1], off[0] == 0): (wg_rows, wg_seg, P, max_seg) as numpy / ints."""
+    lib = _lib.load()
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    rows, seg = np.empty(n_wg + 1, np.int32), np.empty(n_wg + 1, np.int32)
+    max_seg = C.c_int32(0)
+    pairs = int(lib.g4c_plan_row_ranges(off.ctypes.data, int(off.shape[0]) - 1, n_wg, rows.ctypes.data, seg.ctypes.data, C.byref(max_seg)))
+    if pairs < 0:
+        _lib.check(pairs)
+    return rows, seg, pairs, int(max_seg.value)
 
 
 @dataclass

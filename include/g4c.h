@@ -318,6 +318,14 @@ typedef struct {
      * the same slope expression.  The two are independent (the backward chain reads bf16 activations and writes fp32 gradients). */
     int32_t save_dtype;
     int32_t mul_dtype;
+    /* Row ranges for the fused aggregation over segments of any length (NULL: none; g4c_plan_row_ranges made them for n_wg =
+     * g4c_mlp_ws_grid workgroups): workgroup slot i takes rows [wg_rows[i], wg_rows[i + 1]) = segments [wg_seg[i], wg_seg[i + 1]) and
+     * cuts them into pairs of full 32-row tiles itself, wg_pairs = the most pairs of a range, wg_max_seg = the most segments of one.
+     * Used by the f16x3 launches of the weight-stationary kernel whose rows are not gathered (plain hoisted message launch with the
+     * aggregation, and the fused MP layer) when the segments are not uniform with 4 .. 8 rows; every other launch ignores them and
+     * runs on the tiles of whole segments above, which stay required.  Same rows, same aggregates, bit for bit. */
+    const int32_t *wg_rows, *wg_seg;
+    int32_t n_wg, wg_pairs, wg_max_seg;
 } g4c_mlp_io_t;
 
 /* One fused-MLP launch over `n_rows` rows of the input `srcs`, writing what `io` names. */
@@ -363,6 +371,10 @@ int g4c_mlp_small_launch_tiles(int n_tiles);
 #define G4C_KERNEL_MLP_WS_CERT 8
 #define G4C_KERNEL_MLP_WS_PRE 9   /* mlp_ws_pre_kernel: the weight-stationary kernel's "first layer precomputed" form (g4c_mlp_t.k_pad[0] == 0) */
 int g4c_mlp_last_kernel(void);
+/* Workgroups (= row ranges, g4c_mlp_io_t.n_wg) of this thread's last g4c_mlp_run call when it ran the weight-stationary kernel's dense
+ * pairs for segments of any length on the caller's row ranges — reported under G4C_KERNEL_MLP_WS / _WS_CERT like the kernel's other
+ * forms —, else 0. */
+int g4c_mlp_last_row_ranges(void);
 
 /* Compile-time launch shapes of the tile kernel (mlp_bx6_kernel): a launch of G4C_WFMT_F16X2 whose every field matches a shape runs an
  * instantiation in which that shape's fields are constants — no source interpretation, index staging only for a source that has an
@@ -387,6 +399,17 @@ int g4c_mlp_last_shape(void);
  * longer than max_rows. */
 int64_t g4c_plan_tiles(const int32_t *off /*host*/, int32_t n_seg, int32_t max_rows, int32_t *tile_rows /*host, out*/,
                        int32_t *tile_seg /*host, out*/, int64_t capacity);
+/* Row ranges for g4c_mlp_io_t.wg_rows / wg_seg: the rows of a CSR (off[0 .. n_seg], off[0] == 0) cut into n_wg contiguous ranges that
+ * start and end on segment boundaries, range i = rows [wg_rows[i], wg_rows[i + 1]) = segments [wg_seg[i], wg_seg[i + 1]) (host int32
+ * [n_wg + 1] each).  Every range holds at most 64 P rows for the smallest P for which n_wg such ranges exist — P = ceil(rows / (64
+ * n_wg)) unless the segment boundaries (one long segment) force more — and among those plans the rows are spread evenly.  A range
+ * without rows has no segments (empty ranges come last); empty segments belong to the range they fall in.  Returns P (0: no rows),
+ * *max_seg = the most segments of a range, or a negative G4C_E* code. */
+int64_t g4c_plan_row_ranges(const int32_t *off /*host*/, int32_t n_seg, int32_t n_wg, int32_t *wg_rows /*host, out*/,
+                            int32_t *wg_seg /*host, out*/, int32_t *max_seg /*out*/);
+/* Persistent workgroups of a weight-stationary launch on the device of `device_ptr`: one per compute unit, at most G4C_WS_MAX_GRID
+ * (environment, read at every call: tests reach workgroups of several tile pairs on small inputs with it). */
+int g4c_mlp_ws_grid(const void *device_ptr, int32_t *n_wg);
 
 /* Row-wise LayerNorm (+ activation G4C_ACT_*) over rows of any width: out[r, :] = act((x[r, :] - mean) * rsqrt(var + eps) * gamma + beta),
  * mean / biased variance over the row's `width` columns in two passes, as torch.nn.functional.layer_norm (nn/blocks.py:137-141: the
