@@ -1,7 +1,7 @@
 """Drop-in use of the MI355X path with the reference's API: build a mesh with `gfd.transforms`, create (or load) a MuS-GNN,
 roll it out with `solve`.  With a trained checkpoint of the reference: `gfd.nn.NsThreeScaleGNN(checkpoint="NsThreeScaleGNN.chk")`.
 
-    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk]
+    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy]
 """
 import argparse, os, sys, time
 import torch
@@ -11,6 +11,7 @@ import graphs4cfd_amd as gfd          # instead of: import graphs4cfd as gfd
 ap = argparse.ArgumentParser()
 ap.add_argument("--nodes", type=int, default=20000); ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--checkpoint", default=None)
+ap.add_argument("--raster", default=None, help="write the vorticity of the last step on a 256 x 256 raster to this .npy file")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -41,3 +42,9 @@ diag = model.diagnostics(graph, a.steps, ("div", "vort"))      # divergence and 
 print("divergence RMS per step:", " ".join(f"{v:.3e}" for v in diag.rms[:, 0].tolist()))
 spec = model.spectrum(graph, a.steps, bins=range(a.steps // 2 + 1))     # Fourier modes of u, v, p at every node, accumulated inside the step
 print(f"dominant frequency of u: {spec.dominant(0):.4f} cycles per step, largest amplitude there {spec.amplitude[:, 0].max():.3e}")
+if a.raster:                                                # the picture of a field: sampled on the device inside the step, no plotting dependency
+    import numpy as np
+    raster = gfd.PointSampler.grid(graph, (256, 256))          # the mesh's bounding box; .distance masks points far from every node
+    rs = model.sample(graph, a.steps, raster, every=a.steps, derived=("vort",))
+    np.save(a.raster, rs.image(-1, "vort").cpu().numpy())      # [256, 256]: entry [i, j] is the vorticity at (x_i, y_j)
+    print(f"vorticity of step {a.steps - 1} on a 256 x 256 raster -> {a.raster}")

@@ -121,6 +121,14 @@ class g4c_mesh_derived_t(C.Structure):
                 ("snap", C.c_void_p), ("stats", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+SAMPLE_MAX_K = 16                                   # G4C_SAMPLE_MAX_K: most neighbours of a sample point (the grid search's limit)
+
+
+class g4c_sample_points_t(C.Structure):
+    _fields_ = [("idx", C.c_void_p), ("coef", C.c_void_p), ("k", C.c_int32), ("nf", C.c_int32), ("x_ld", C.c_int32), ("cur", C.c_void_p),
+                ("step", C.c_void_p), ("every", C.c_int32), ("n_slots", C.c_int32), ("max_steps", C.c_int32), ("series", C.c_void_p)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -168,6 +176,9 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
     "g4c_mesh_derived": (C.c_int, [C.c_void_p, C.POINTER(g4c_mesh_derived_t), C.POINTER(g4c_derived_program_t), C.c_int64, C.c_void_p]),
+    "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

@@ -1,0 +1,255 @@
+// Values at points that are no mesh nodes (include/g4c.h): a moving-least-squares interpolation with a linear basis over the k
+// nearest nodes of every point.
+//   g4c_sample_weights  once per set of points: per point the fp64 fit over its neighbours, centred on their weighted mean, the
+//                       normal matrix inverted in closed form, and per neighbour one fp32 coefficient c_j with
+//                       value(q) = sum_j c_j x[idx_j];
+//   g4c_sample_points   once per step (or once per target): that sum for every point and column, written to `cur` and, on a slot
+//                       step, to a strided slot of a step-major series.
+// A point's sum is taken by ONE thread over its neighbours nearest first, in fp32 without contraction: the bits are a function of
+// the data alone.  The tables are j-major [k, P]: lane p reads consecutive addresses.  Plain loads and stores, no atomics.
+#include "g4c_common.h"
+
+// No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
+// bits, and the fp64 coefficients differ from their restatement by the library's square root and division at most.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int PS_THREADS = 256;
+constexpr int PS_MAX_BLOCKS = 1024;          // as the records: 4 workgroups of 256 per CU on 256 CUs
+constexpr int PS_MAX_K = G4C_SAMPLE_MAX_K;
+constexpr int PS_CHUNK = 4;                  // columns one thread sums: nf = 3 is one chunk, a whole target ceil(F / 4) per point
+
+// ------------------------------------------------------------------------------------------------------------------ weights
+template <int DIM>
+__global__ __launch_bounds__(PS_THREADS) void sample_weights_kernel(const float *__restrict__ pos, const float *__restrict__ q,
+                                                                   const int *__restrict__ idx, int k, int power, long long n_points,
+                                                                   float *__restrict__ coef, float *__restrict__ distance,
+                                                                   unsigned char *__restrict__ degenerate) {
+    const long long p = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+    if (p >= n_points) return;
+    double qd[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) qd[a] = (double)q[p * DIM + a];
+    auto nb = [&](int j, double (&d)[DIM]) -> double {          // d_j = pos[idx_j] - q, returns r2_j
+        const long long i = idx[(long long)j * n_points + p];
+        double r2 = 0.0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            d[a] = (double)pos[i * DIM + a] - qd[a];
+            const double sq = d[a] * d[a];
+            r2 += sq;
+        }
+        return r2;
+    };
+    auto weight = [&](double r2) -> double { return power == 0 ? 1.0 : (power == 1 ? 1.0 / sqrt(r2) : 1.0 / r2); };
+    double d[DIM];
+    const double r20 = nb(0, d);
+    distance[p] = (float)sqrt(r20);
+    if (r20 == 0.0) {          // the point is a node: its row, bit for bit
+        degenerate[p] = 0;
+        for (int j = 0; j < k; ++j) coef[(long long)j * n_points + p] = j == 0 ? 1.f : 0.f;
+        return;
+    }
+    // the weighted mean of the neighbours' offsets
+    double W = 0.0, dbar[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) dbar[a] = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const double w = weight(nb(j, d));
+        W += w;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            const double wd = w * d[a];
+            dbar[a] += wd;
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) dbar[a] = dbar[a] / W;
+    // the normal matrix of the centred offsets, upper triangle row-major: (0,0), (0,1), .., (1,1), ..
+    constexpr int NM = DIM * (DIM + 1) / 2;
+    double m[NM];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) m[i] = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const double w = weight(nb(j, d));
+        double e[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) e[a] = d[a] - dbar[a];
+        int i = 0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+#pragma unroll
+            for (int b = a; b < DIM; ++b, ++i) {
+                const double we = w * e[a];
+                const double t = we * e[b];
+                m[i] += t;
+            }
+        }
+    }
+    // adjugate and determinant, as mesh_gradient_weights_kernel forms them
+    double adj[NM], det, tr;
+    if constexpr (DIM == 2) {
+        adj[0] = m[2];
+        adj[1] = -m[1];
+        adj[2] = m[0];
+        const double p0 = m[0] * m[2], p1 = m[1] * m[1];
+        det = p0 - p1;
+        tr = m[0] + m[2];
+    } else {
+        const double c00a = m[3] * m[5], c00b = m[4] * m[4];
+        const double c01a = m[2] * m[4], c01b = m[1] * m[5];
+        const double c02a = m[1] * m[4], c02b = m[2] * m[3];
+        const double c11a = m[0] * m[5], c11b = m[2] * m[2];
+        const double c12a = m[1] * m[2], c12b = m[0] * m[4];
+        const double c22a = m[0] * m[3], c22b = m[1] * m[1];
+        adj[0] = c00a - c00b;
+        adj[1] = c01a - c01b;
+        adj[2] = c02a - c02b;
+        adj[3] = c11a - c11b;
+        adj[4] = c12a - c12b;
+        adj[5] = c22a - c22b;
+        const double t0 = m[0] * adj[0], t1 = m[1] * adj[1], t2 = m[2] * adj[2];
+        det = (t0 + t1) + t2;
+        tr = (m[0] + m[3]) + m[5];
+    }
+    const double mean = tr / (double)DIM;
+    double thr = mean * mean;
+    if constexpr (DIM == 3) thr = thr * mean;
+    thr = 1e-12 * thr;
+    // the gradient's rule; k <= dim centred offsets span less than the space whatever the rounding made of det
+    const bool degen = k <= DIM || !(det > thr);
+    degenerate[p] = degen ? 1 : 0;
+    // v = adj dbar:  M^-1 dbar = v / det
+    double v[DIM];
+    if constexpr (DIM == 2) {
+        const double a0 = adj[0] * dbar[0], a1 = adj[1] * dbar[1], b0 = adj[1] * dbar[0], b1 = adj[2] * dbar[1];
+        v[0] = a0 + a1;
+        v[1] = b0 + b1;
+    } else {
+        const double a0 = adj[0] * dbar[0], a1 = adj[1] * dbar[1], a2 = adj[2] * dbar[2];
+        const double b0 = adj[1] * dbar[0], b1 = adj[3] * dbar[1], b2 = adj[4] * dbar[2];
+        const double c0 = adj[2] * dbar[0], c1 = adj[4] * dbar[1], c2 = adj[5] * dbar[2];
+        v[0] = (a0 + a1) + a2;
+        v[1] = (b0 + b1) + b2;
+        v[2] = (c0 + c1) + c2;
+    }
+    const double invW = 1.0 / W;
+    for (int j = 0; j < k; ++j) {
+        const double w = weight(nb(j, d));
+        double c;
+        if (degen) {
+            c = w / W;                                   // Shepard: exact on constants only
+        } else {
+            double s = 0.0;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) {
+                const double ea = d[a] - dbar[a];
+                const double t = ea * v[a];
+                s += t;
+            }
+            const double corr = s / det;
+            c = w * (invW - corr);
+        }
+        coef[(long long)j * n_points + p] = (float)c;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ per step
+// One thread per (point, chunk of PS_CHUNK columns); the items are chunk-major — item = chunk * P + p — so the lanes of a wave hold
+// consecutive points of one chunk and read consecutive table entries.
+__global__ __launch_bounds__(PS_THREADS) void sample_points_kernel(const float *__restrict__ x, const g4c_sample_points_t s,
+                                                                  long long n_points) {
+    const int F = s.nf, k = s.k;
+    const int t = s.step ? s.step[0] : -1;
+    // the slot address is formed from a checked t
+    float *series = nullptr;
+    if (s.series && t >= 0 && t < s.max_steps && s.every > 0 && (t + 1) % s.every == 0) {
+        const int slot = (t + 1) / s.every - 1;
+        if (slot < s.n_slots) series = s.series + (long long)slot * n_points * F;
+    }
+    const int n_chunks = (F + PS_CHUNK - 1) / PS_CHUNK;
+    const long long items = n_points * n_chunks;
+    const long long stride = (long long)gridDim.x * PS_THREADS;
+    for (long long it = (long long)blockIdx.x * PS_THREADS + threadIdx.x; it < items; it += stride) {
+        // (no contraction: every product is rounded to fp32 before it is added, so a plain numpy.float32 loop gives the same bits)
+#pragma clang fp contract(off)
+        const long long chunk = n_chunks == 1 ? 0 : it / n_points;          // (nf <= 4, the step's shape: no division)
+        const long long p = it - chunk * n_points;
+        const int c0 = (int)chunk * PS_CHUNK;
+        const int width = F - c0 < PS_CHUNK ? F - c0 : PS_CHUNK;
+        float acc[PS_CHUNK];
+#pragma unroll
+        for (int f = 0; f < PS_CHUNK; ++f) acc[f] = 0.f;
+        // (four neighbours at a time: their index, coefficient and row loads are in flight together — the adds keep the order)
+#pragma unroll 4
+        for (int j = 0; j < k; ++j) {
+            const long long at = (long long)j * n_points + p;
+            const float c = s.coef[at];
+            const float *row = x + (long long)s.idx[at] * s.x_ld + c0;
+#pragma unroll
+            for (int f = 0; f < PS_CHUNK; ++f) {
+                if (f < width) {
+                    const float pr = c * row[f];
+                    acc[f] = j == 0 ? pr : acc[f] + pr;
+                }
+            }
+        }
+        const long long o = p * F + c0;
+#pragma unroll
+        for (int f = 0; f < PS_CHUNK; ++f) {
+            if (f < width) {
+                s.cur[o + f] = acc[f];
+                if (series) series[o + f] = acc[f];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int g4c_sample_weights(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
+                                  int64_t n_nodes, int64_t n_points, float *coef, float *distance, uint8_t *degenerate, void *stream) {
+    const char *me = "g4c_sample_weights";
+    G4C_REQUIRE(n_nodes >= 0 && n_points >= 0 && k >= 1, G4C_EINVAL, "%s: bad sizes n_nodes=%lld n_points=%lld k=%d", me,
+                (long long)n_nodes, (long long)n_points, k);
+    G4C_REQUIRE(power >= 0 && power <= 2, G4C_EINVAL, "%s: power=%d (0, 1 or 2)", me, power);
+    G4C_REQUIRE(dim == 2 || dim == 3, G4C_EUNSUPPORTED, "%s: dim=%d (2 or 3 are supported)", me, dim);
+    G4C_REQUIRE(k <= PS_MAX_K, G4C_EUNSUPPORTED, "%s: k=%d neighbours (1 .. %d are supported)", me, k, PS_MAX_K);
+    if (n_points == 0) return G4C_OK;
+    G4C_REQUIRE(n_nodes >= k, G4C_EINVAL, "%s: k=%d neighbours of n_nodes=%lld", me, k, (long long)n_nodes);
+    G4C_REQUIRE(pos && queries && idx && coef && distance && degenerate, G4C_EINVAL, "%s: null pointer", me);
+    g4c::DeviceGuard on_device(pos);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n_points + PS_THREADS - 1) / PS_THREADS);
+    if (dim == 2)
+        sample_weights_kernel<2><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, coef, distance, degenerate);
+    else
+        sample_weights_kernel<3><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, coef, distance, degenerate);
+    return g4c::check_launch(me);
+}
+
+extern "C" int g4c_sample_points(const float *x, const g4c_sample_points_t *sp, int64_t n_nodes, int64_t n_points, void *stream) {
+    const char *me = "g4c_sample_points";
+    G4C_REQUIRE(sp, G4C_EINVAL, "%s: null pointer", me);
+    G4C_REQUIRE(n_nodes >= 0 && n_points >= 0 && sp->nf >= 1 && sp->k >= 1 && sp->x_ld >= 0 && sp->max_steps >= 0 && sp->every >= 0 &&
+                    sp->n_slots >= 0,
+                G4C_EINVAL, "%s: bad sizes n_nodes=%lld n_points=%lld nf=%d k=%d x_ld=%d max_steps=%d every=%d n_slots=%d", me,
+                (long long)n_nodes, (long long)n_points, sp->nf, sp->k, sp->x_ld, sp->max_steps, sp->every, sp->n_slots);
+    G4C_REQUIRE(sp->x_ld >= sp->nf, G4C_EINVAL, "%s: x_ld=%d < nf=%d", me, sp->x_ld, sp->nf);
+    G4C_REQUIRE(sp->k <= PS_MAX_K, G4C_EUNSUPPORTED, "%s: k=%d neighbours (1 .. %d are supported)", me, sp->k, PS_MAX_K);
+    G4C_REQUIRE(sp->every > 0 || !sp->series, G4C_EINVAL, "%s: a series buffer with every=0", me);
+    G4C_REQUIRE(sp->step || !sp->series, G4C_EINVAL, "%s: a series without a step index", me);
+    if (n_points == 0) return G4C_OK;
+    G4C_REQUIRE(n_nodes >= sp->k, G4C_EINVAL, "%s: k=%d neighbours of n_nodes=%lld", me, sp->k, (long long)n_nodes);
+    G4C_REQUIRE(x && sp->idx && sp->coef && sp->cur, G4C_EINVAL, "%s: null pointer", me);
+    g4c::DeviceGuard on_device(x);
+    hipStream_t s = (hipStream_t)stream;
+    g4c_sample_points_t d = *sp;
+    if (d.every == 0 || d.n_slots == 0) d.series = nullptr;
+    const long long items = (long long)n_points * ((d.nf + PS_CHUNK - 1) / PS_CHUNK);
+    long long blocks = (items + PS_THREADS - 1) / PS_THREADS;
+    if (blocks > PS_MAX_BLOCKS) blocks = PS_MAX_BLOCKS;
+    sample_points_kernel<<<dim3((unsigned)blocks), dim3(PS_THREADS), 0, s>>>(x, d, (long long)n_points);
+    return g4c::check_launch(me);
+}

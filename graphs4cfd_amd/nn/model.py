@@ -193,7 +193,9 @@ class GNN(nn.Module):
 
     def evaluate(self, graph: Union[Graph, List[Graph]], n_out: Optional[int] = None, *, every: int = 0, probes: Optional[torch.Tensor] = None,
                  capture: Optional[bool] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
-                 derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None) -> "RolloutErrors":
+                 derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None, samples=None,
+                 sample_every: int = 1, sample_moments=None, sample_spectrum: Optional["Spectrum"] = None,
+                 sample_derived: bool = False) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -204,6 +206,9 @@ class GNN(nn.Module):
         derived (a tuple of names: 'div', 'vort', 'grad:<f>') with derived_every / derived_moments / derived_options, as in `Rollout`,
         attaches the flow diagnostics of the prediction (`.derived`: `RolloutDerived`).  spectrum (a `gfd.Spectrum`) attaches the
         Fourier modes of the prediction and, by the same table, of the target (`.spectrum` / `.target_spectrum`: `RolloutSpectrum`).
+        samples (a `gfd.PointSampler` or points [P, dim]) with sample_every / sample_moments / sample_spectrum / sample_derived, as in
+        `Rollout`, attaches the prediction at those points (`.samples`: `RolloutSamples`) and, as its `.target`, the target's first
+        num_fields * n_out columns at the same points (one launch, outside the step).
         A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
@@ -211,9 +216,16 @@ class GNN(nn.Module):
         assert n_out > 0, "n_out must be greater than 0."
         with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True, moments=moments,
                            error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
-                           derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None) as ro:
+                           derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None, samples=samples,
+                           sample_every=sample_every, sample_moments=sample_moments, sample_spectrum=sample_spectrum,
+                           sample_derived=sample_derived) as ro:
             ro.run(n_out)
             errs = ro.errors()
+            errs.samples = None
+            if ro._samples is not None:
+                errs.samples = ro.samples()
+                tgt = ro._caller_graph.target.to(torch.float32)
+                errs.samples.target = errs.samples.sampler.sample(tgt[:, :int(self.num_fields) * n_out])
             if spectrum is not None:
                 errs.spectrum, errs.target_spectrum = ro.spectrum(), ro.target_spectrum()
             errs.moments = ro.moments() if ro._moments is not None else None
@@ -235,6 +247,22 @@ class GNN(nn.Module):
                            derived_moments=None if discard is None else (discard, stride), derived_options=derived_options or None) as ro:
             ro.run(n_out)
             return ro.derived()
+
+    def sample(self, graph: Graph, n_out: int, points, *, every: int = 1, discard: Optional[int] = None, stride: int = 1,
+               spectrum: Optional["Spectrum"] = None, derived=None, capture: Optional[bool] = None, **derived_options) -> "RolloutSamples":
+        """Roll the model out for n_out steps and return the prediction at `points` — a `gfd.PointSampler` built on this graph (a
+        rake, a raster), or points [P, dim] off the nodes — (`RolloutSamples`), interpolated on the device inside the step by a
+        linear moving-least-squares fit over the nearest nodes.  No prediction is held at the nodes.  every = k keeps the samples of
+        steps k - 1, 2k - 1, ... (`.series`; 0 keeps none); discard = d (not None) their time statistics at every point over the steps
+        d, d + stride, ... (`.moments`); spectrum (a `gfd.Spectrum`) their Fourier modes (`.spectrum`); derived (a tuple of names, as
+        in `diagnostics`, with its derived_options) also samples those columns (`.derived`, `.columns`: the vorticity on a raster).
+        One graph only: a list of graphs overlaps in space."""
+        assert n_out > 0, "n_out must be greater than 0."
+        with self._rollout(graph, n_out, capture, "sample()", every=0, samples=points, sample_every=every,
+                           sample_moments=None if discard is None else (discard, stride), sample_spectrum=spectrum, derived=derived,
+                           sample_derived=derived is not None, derived_options=derived_options or None) as ro:
+            ro.run(n_out)
+            return ro.samples()
 
     def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
                         capture: Optional[bool] = None) -> "RolloutMoments":
@@ -276,6 +304,9 @@ class GNN(nn.Module):
                                records.get("derived_moments"), records.get("derived_options"), in_list=type(graph) is list,
                                spectrum=records.get("derived_spectrum"))
         _check_spectrum("spectrum", records.get("spectrum"), int(self.num_fields), n_out)
+        _check_samples(graph[0] if type(graph) is list else graph, int(self.num_fields), n_out, records.get("samples"),
+                       records.get("sample_every", 1), records.get("sample_moments"), records.get("sample_spectrum"),
+                       records.get("sample_derived", False), records.get("derived") is not None, in_list=type(graph) is list)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -423,7 +454,8 @@ class Rollout:
                  label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
                  mask: Optional[torch.Tensor] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None,
-                 target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None):
+                 target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None, samples=None, sample_every: int = 1,
+                 sample_moments=None, sample_spectrum: Optional["Spectrum"] = None, sample_derived: bool = False):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -457,7 +489,17 @@ class Rollout:
         `g4c_rollout_spectrum` launch per step after the moments, in front of the closing launch; `target_spectrum=True` (needs
         `target=` and `spectrum=`) the same of the target's columns, by the same table; `derived_spectrum` (a `gfd.Spectrum`, needs
         `derived=`) of the derived columns.  `spectrum()` / `target_spectrum()` / `derived_spectrum()` return them
-        (`RolloutSpectrum`); after `rewind()` or a recomputation they hold the steps taken since."""
+        (`RolloutSpectrum`); after `rewind()` or a recomputation they hold the steps taken since.
+
+        Values off the nodes (opt-in, no record either): `samples` — a `gfd.PointSampler` built on this graph, or points [P, dim] (a
+        sampler with its defaults is built here) — interpolates every prediction to the points: one `g4c_sample_points` launch after
+        the forward and the derived columns, in front of the node moments and spectra and of the closing launch; with
+        `sample_derived=True` (needs `derived=`) one more on the derived columns.  `sample_every` = k keeps the samples of steps
+        k - 1, 2k - 1, ... (0 keeps no series); `sample_moments` (the forms `moments` takes) and `sample_spectrum` (a `gfd.Spectrum`)
+        accumulate the time statistics and Fourier modes of the sampled prediction at every point, by the kernels the nodes use.
+        `samples()` returns them (`RolloutSamples`), the points in the caller's order; after `rewind()` or a recomputation the
+        accumulators hold the steps taken since and the slots of the steps run again are overwritten.  The neighbour search is not
+        periodic (`gfd.PointSampler`), and a list of graphs — they overlap in space — is refused."""
         derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options,
                                       spectrum=derived_spectrum)
         spectrum_spec = _check_spectrum("spectrum", spectrum, int(model.num_fields), int(max_steps))
@@ -465,6 +507,8 @@ class Rollout:
             raise TypeError(f"target_spectrum: expected a bool, got {target_spectrum!r}")
         if target_spectrum and (target is None or spectrum_spec is None):
             raise ValueError("target_spectrum: the spectrum of the target needs target= and spectrum= (it uses the same table)")
+        samples_spec = _check_samples(graph, int(model.num_fields), int(max_steps), samples, sample_every, sample_moments, sample_spectrum,
+                                      sample_derived, derived_spec is not None)
         window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
         error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
         if error_window is not None and target is None:
@@ -509,6 +553,7 @@ class Rollout:
         self._derived = None if derived_spec is None else _Derived(self, *derived_spec)
         self._spectrum = None if spectrum_spec is None else _Spectrum(self, spectrum_spec)
         self._target_spectrum = _Spectrum(self, spectrum_spec, x=self._rec.target, x_step=self.nf) if target_spectrum else None
+        self._samples = None if samples_spec is None else _Samples(self, **samples_spec)
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -523,6 +568,8 @@ class Rollout:
             pred = self.model.forward(self.graph, self.steps_done)
         if self._derived is not None:                         # (all of these read the step index the closing launch below bumps)
             self._derived.launch(pred, self.step_counter)
+        if self._samples is not None:
+            self._samples.launch(pred, self.step_counter, self._derived)
         for mo in (self._moments, self._error_moments):
             if mo is not None:
                 mo.accumulate(pred, self.step_counter)
@@ -650,10 +697,11 @@ class Rollout:
                              probes=ops.steps_to_columns(rec.probe_out) if rec.probe_out is not None else None)
 
     def _reset_moments(self) -> None:
-        for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None):
+        for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None,
+                   self._samples.moments if self._samples is not None else None):
             if mo is not None:
                 mo.reset(self._first_slot)
-        for sp in self._spectra():
+        for sp in self._spectra() + ([self._samples.spectrum] if self._samples is not None and self._samples.spectrum is not None else []):
             sp.reset(self._first_slot)
 
     def _spectra(self):
@@ -702,6 +750,14 @@ class Rollout:
             raise RuntimeError(f"{self.label}: no derived= were asked for")
         self.validate()
         return self._derived.read(self._perm, self.steps_done)
+
+    def samples(self) -> "RolloutSamples":
+        """What `samples=` asked for, of the steps taken (`RolloutSamples`: the series at the points, their time statistics and
+        Fourier modes, the sampled derived columns) — validated first, like `result()`."""
+        if self._samples is None:
+            raise RuntimeError(f"{self.label}: no samples= were asked for")
+        self.validate()
+        return self._samples.read()
 
     def close(self) -> None:
         self.graph.field = self._orig_field
@@ -781,8 +837,10 @@ class _Moments:
     outside the graph — is all `rewind()` and a recomputation need: the step that finds itself at the origin stores the
     accumulators without reading them."""
 
-    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None, nf: Optional[int] = None):
-        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf if nf is None else int(nf)        # (nf: the derived columns)
+    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None, nf: Optional[int] = None,
+                 rows: Optional[int] = None):
+        dev, nf = ro.field.device, ro.nf if nf is None else int(nf)        # (nf: the derived columns)
+        n = int(ro.graph.num_nodes) if rows is None else int(rows)         # (rows: the sample points)
         self.nf, self.max_steps, self.start, self.stride, self.sub = nf, ro.max_steps, start, stride, sub
         pairs = ops.moment_pairs(nf)
         self.planes = torch.zeros((4 * nf + pairs, n), dtype=torch.float64, device=dev)
@@ -930,8 +988,10 @@ class _Spectrum:
     recomputation need.  `x`: the tensor sampled instead of the prediction (the records' target with x_step = nf, or the derived
     columns), in the rollout's numbering."""
 
-    def __init__(self, ro: "Rollout", spec: dict, x: Optional[torch.Tensor] = None, x_step: int = 0, nf: Optional[int] = None):
-        dev, n, nf = ro.field.device, int(ro.graph.num_nodes), ro.nf if nf is None else int(nf)
+    def __init__(self, ro: "Rollout", spec: dict, x: Optional[torch.Tensor] = None, x_step: int = 0, nf: Optional[int] = None,
+                 rows: Optional[int] = None):
+        dev, nf = ro.field.device, ro.nf if nf is None else int(nf)
+        n = int(ro.graph.num_nodes) if rows is None else int(rows)         # (rows: the sample points)
         self.nf, self.max_steps, self.spec, self.x, self.x_step = nf, ro.max_steps, spec, x, x_step
         self.start, self.stride, self.K = spec["start"], spec["stride"], int(spec["tw"].size(1))
         self.planes = torch.zeros((ops.spectrum_planes(nf, self.K), n), dtype=torch.float64, device=dev)
@@ -1148,6 +1208,134 @@ class RolloutDerived:
 
     def __repr__(self):
         return f"RolloutDerived(columns={self.columns}, steps={int(self.sums.size(0))}, nodes={self.n_nodes})"
+
+
+def _check_samples(graph, nf: int, max_steps: int, samples, every, moments, spectrum, sample_derived, has_derived: bool,
+                   in_list: bool = False):
+    """The `samples=` / `sample_*=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing is
+    moved, the library is not touched) -> the arguments of `_Samples`, or None when no samples are asked for."""
+    from ..point_sampler import PointSampler, check_points
+    if not isinstance(sample_derived, bool):
+        raise ValueError(f"sample_derived: expected a bool, got {sample_derived!r}")
+    if samples is None:
+        if moments not in (None, False) or spectrum is not None or sample_derived:
+            raise ValueError("samples: sample_moments / sample_spectrum / sample_derived were given without samples=")
+        return None
+    if in_list:
+        raise ValueError("samples: a list of graphs is collated into one cloud in which the graphs overlap in space: sample each graph on its own")
+    if isinstance(samples, PointSampler):
+        if samples.n_nodes != int(graph.num_nodes):
+            raise ValueError(f"samples: a PointSampler over {samples.n_nodes} nodes for a graph of {int(graph.num_nodes)}")
+    else:
+        try:
+            check_points(graph, samples, None, 2)
+        except ValueError as e:
+            raise ValueError(f"samples: {e}") from None
+    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+        raise ValueError(f"sample_every: expected an integer >= 0 (0: no series, k: every k-th step), got {every!r}")
+    if sample_derived and not has_derived:
+        raise ValueError("sample_derived: the samples of the derived columns need derived=")
+    for name, asked, what in (("sample_moments", moments not in (None, False), "time statistics"), ("sample_spectrum", spectrum is not None, "spectra")):
+        if asked and nf > _lib.REC_MAX_NF:
+            raise ValueError(f"{name}: the {what} cover up to {_lib.REC_MAX_NF} fields, this model has {nf}")
+    try:
+        window = _check_moments("sample_moments", moments, nf, max_steps)
+        table = _check_spectrum("sample_spectrum", spectrum, nf, max_steps)
+    except (TypeError, NotImplementedError) as e:
+        raise ValueError(str(e)) from None
+    return dict(samples=samples, every=int(every), window=window, spectrum=table, sample_derived=sample_derived)
+
+
+class _Samples:
+    """The samples of a `Rollout` at points off the nodes and the launches that form them.  Everything is allocated here, once: the
+    sampler (built on the caller's graph when points were given), its neighbour table mapped through the inverse of the rollout's
+    renumbering — the same values then enter every sum in the same order, so the bits do not depend on `reorder` —, `cur` [P, nf], the
+    series' slots, the same for the derived columns, and the accumulators of `g4c_rollout_moments` and `g4c_rollout_spectrum` over
+    `cur` (P rows).  The points keep the caller's order: nothing is permuted on read."""
+
+    def __init__(self, ro: "Rollout", samples, every: int, window, spectrum, sample_derived: bool):
+        from ..point_sampler import PointSampler
+        dev, nf, steps = ro.field.device, ro.nf, ro.max_steps
+        self.sampler = samples if isinstance(samples, PointSampler) else PointSampler(ro._caller_graph, samples)
+        self.idx, self.coef = self.sampler._idx.to(dev), self.sampler._coef.to(dev)
+        if ro._perm is not None:                      # caller's row r is the rollout's row inv[r]
+            inv = torch.empty_like(ro._perm)
+            inv[ro._perm] = torch.arange(int(ro.graph.num_nodes), device=ro._perm.device)
+            self.idx = inv.to(dev)[self.idx.long()].to(torch.int32).contiguous()
+        n = self.sampler.n_points
+        self.every, self.max_steps = every, steps
+        self.cur = torch.zeros((n, nf), dtype=torch.float32, device=dev)
+        self.series = torch.zeros((steps // every, n, nf), dtype=torch.float32, device=dev) if every else None
+        self.dcur = self.dseries = self.columns = None
+        if sample_derived:
+            self.columns, nd = list(ro._derived.columns), ro._derived.nd
+            self.dcur = torch.zeros((n, nd), dtype=torch.float32, device=dev)
+            self.dseries = torch.zeros((steps // every, n, nd), dtype=torch.float32, device=dev) if every else None
+        self.moments = None if window is None else _Moments(ro, *window, rows=n)
+        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, rows=n)
+
+    def launch(self, pred, step, derived) -> None:
+        ops.sample_points(pred, self.idx, self.coef, self.cur, step=step, every=self.every, series=self.series, max_steps=self.max_steps)
+        if self.dcur is not None:
+            ops.sample_points(derived.cur, self.idx, self.coef, self.dcur, step=step, every=self.every, series=self.dseries,
+                              max_steps=self.max_steps)
+        if self.moments is not None:
+            self.moments.accumulate(self.cur, step)
+        if self.spectrum is not None:
+            self.spectrum.accumulate(self.cur, step)
+
+    def read(self) -> "RolloutSamples":
+        return RolloutSamples(self.sampler, series=ops.steps_to_columns(self.series) if self.series is not None else None,
+                              derived=ops.steps_to_columns(self.dseries) if self.dseries is not None else None, columns=self.columns,
+                              moments=self.moments.read(None) if self.moments is not None else None,
+                              spectrum=self.spectrum.read(None) if self.spectrum is not None else None, fields=int(self.cur.size(1)))
+
+
+class RolloutSamples:
+    """A rollout at points off the nodes (`Rollout.samples()`, `GNN.sample()`, `GNN.evaluate(samples=)`): `sampler` (the
+    `gfd.PointSampler`) with its `points` [P, dim], `distance` [P] (to the nearest node: mask the points inside a body or outside the
+    domain by it) and `degenerate` [P]; `series` [P, nf * slots]: the sampled prediction of steps k - 1, 2k - 1, ... (`sample_every=k`;
+    None with 0), laid out as `Rollout.probes()`; `derived` [P, nd * slots] and `columns`, the labels: the sampled derived columns
+    (`sample_derived=True`), else None; `moments` / `spectrum`: the time statistics (`RolloutMoments`) and Fourier modes
+    (`RolloutSpectrum`) of the sampled prediction at every point, else None; `target`: the ground truth at the points
+    [P, nf * n_out], filled by `GNN.evaluate`.  `image(slot, column)` is one column of one slot as a raster, for a grid sampler.  The
+    points are in the caller's order."""
+
+    def __init__(self, sampler, series: Optional[torch.Tensor] = None, derived: Optional[torch.Tensor] = None, columns=None,
+                 moments: Optional["RolloutMoments"] = None, spectrum: Optional["RolloutSpectrum"] = None, fields: int = 0):
+        self.sampler, self.points, self.distance, self.degenerate = sampler, sampler.points, sampler.distance, sampler.degenerate
+        self.series, self.derived, self.columns, self.moments, self.spectrum, self.fields = series, derived, columns, moments, spectrum, int(fields)
+        self.target = None
+
+    @property
+    def slots(self) -> int:
+        return 0 if self.series is None else int(self.series.size(1)) // max(self.fields, 1)
+
+    def image(self, slot: int = -1, column=0) -> torch.Tensor:
+        """Column `column` — a field number of the prediction, or a label of `columns` (the sampled derived columns) — of slot `slot`
+        (negative: from the last) as a tensor of the sampler's `shape` (`PointSampler.grid`): entry [i, j] is the value at
+        (x_i, y_j).  ValueError for a sampler that is no grid."""
+        shape = getattr(self.sampler, "shape", None)
+        if shape is None:
+            raise ValueError("image: the sampler is no grid (PointSampler.grid builds one)")
+        if isinstance(column, str):
+            if self.derived is None or column not in self.columns:
+                raise ValueError(f"column: {column!r} is no sampled derived column ({self.columns})")
+            data, width, col = self.derived, len(self.columns), self.columns.index(column)
+        else:
+            if isinstance(column, bool) or not isinstance(column, int) or not 0 <= column < self.fields:
+                raise ValueError(f"column: expected a field 0 .. {self.fields - 1} or a derived column's label, got {column!r}")
+            data, width, col = self.series, self.fields, column
+        if data is None:
+            raise ValueError("image: no series was kept (sample_every=0)")
+        slots = int(data.size(1)) // width
+        if isinstance(slot, bool) or not isinstance(slot, int) or not -slots <= slot < slots:
+            raise ValueError(f"slot: expected -{slots} <= slot < {slots}, got {slot!r}")
+        return data[:, width * (slot % slots) + col].reshape(*shape)
+
+    def __repr__(self):
+        return (f"RolloutSamples(points={int(self.points.size(0))}, fields={self.fields}, slots={self.slots}, derived={self.columns}, "
+                f"moments={self.moments is not None}, spectrum={self.spectrum is not None})")
 
 
 class _Records:

@@ -936,6 +936,104 @@ def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: T
     _lib.check(lib.g4c_mesh_derived(_lib.ptr(x), C.byref(d), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
 
 
+def _sample_tables(what, idx, coef):
+    """The j-major tables of ops.sample_*: idx int32 [k, P] (and coef float32 [k, P]) -> (k, P); ValueError naming the argument."""
+    _mesh_arg(what, idx, "idx", torch.int32, dim=2)
+    k, n_points = int(idx.size(0)), int(idx.size(1))
+    if not 1 <= k <= _lib.SAMPLE_MAX_K:
+        raise ValueError(f"idx: {what}: expected [k, P] with 1 <= k <= {_lib.SAMPLE_MAX_K} neighbours, got shape {tuple(idx.shape)}")
+    if coef is not None:
+        _mesh_arg(what, coef, "coef", torch.float32, shape=(k, n_points))
+    return k, n_points
+
+
+def sample_weights(pos: Tensor, queries: Tensor, idx: Tensor, power: int = 2, out=None):
+    """g4c_sample_weights: the coefficients of a moving-least-squares fit with a linear basis, once per set of points.  pos float32
+    [N, dim] the nodes, queries float32 [P, dim] the points, idx int32 [k, P] (j-major, nearest first: `knn_query_device`'s rows,
+    transposed) their k <= 16 nearest nodes; power 0, 1 or 2 weighs a neighbour by its distance^(-power).  Returns (coef float32
+    [k, P], distance float32 [P] — to the nearest node —, degenerate uint8 [P]); include/g4c.h has the arithmetic.  `out`: the three
+    tensors to write into; no points launch nothing."""
+    what = "sample_weights"
+    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
+    _mesh_arg(what, pos, "pos", torch.float32, dim=2)
+    n_nodes, dim = int(pos.size(0)), int(pos.size(1))
+    if dim not in (2, 3):
+        raise ValueError(f"pos: {what}: expected [N, 2] or [N, 3], got shape {tuple(pos.shape)}")
+    k, n_points = _sample_tables(what, idx, None)
+    _mesh_arg(what, queries, "queries", torch.float32, shape=(n_points, dim))
+    if n_points > 0 and n_nodes < k:
+        raise ValueError(f"idx: {what}: k = {k} neighbours of {n_nodes} nodes")
+    if out is not None:
+        coef, distance, degenerate = out
+        _mesh_arg(what, coef, "out[0]", torch.float32, shape=(k, n_points))
+        _mesh_arg(what, distance, "out[1]", torch.float32, shape=(n_points,))
+        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_points,))
+    else:
+        coef = distance = degenerate = None
+    dev = _mesh_devices(what, ("pos", pos), ("queries", queries), ("idx", idx), ("out[0]", coef), ("out[1]", distance), ("out[2]", degenerate))
+    if out is None:
+        coef = torch.empty((k, n_points), dtype=torch.float32, device=dev)
+        distance = torch.empty((n_points,), dtype=torch.float32, device=dev)
+        degenerate = torch.empty((n_points,), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_sample_weights(_lib.ptr(pos), _lib.ptr(queries), _lib.ptr(idx), dim, power, k, n_nodes, n_points, _lib.ptr(coef),
+                                      _lib.ptr(distance), _lib.ptr(degenerate), _lib.stream_handle(dev)))
+    return coef, distance, degenerate
+
+
+def sample_points(x: Tensor, idx: Tensor, coef: Tensor, cur: Optional[Tensor] = None, *, step: Optional[Tensor] = None, every: int = 0,
+                  series: Optional[Tensor] = None, max_steps: int = 0, nf: Optional[int] = None) -> Tensor:
+    """g4c_sample_points: cur[p, f] = Σ_j coef[j, p] · x[idx[j, p], f] over the columns x[:, :nf] (float32 [N, x_ld], rows of unit
+    stride; nf defaults to every column), idx int32 / coef float32 [k, P] (`sample_weights`) — fp32, j ascending, every product
+    rounded before it is added: a numpy.float32 loop gives the same bits.  Returns cur float32 [P, nf] (`cur=`: written in place).
+    With `step` (int32, t = step[0] is read on the device and not written): every = e > 0 and series float32 [max_steps // e, P, nf]
+    keep steps e - 1, 2e - 1, ... in slots 0, 1, ...; any other step writes cur only.  The entries of idx are rows of x: they are
+    not checked."""
+    what = "sample_points"
+    every, max_steps = int(every), int(max_steps)
+    k, n_points = _sample_tables(what, idx, coef)
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or int(x.size(1)) < 1:
+        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
+    n_nodes, cols = int(x.size(0)), int(x.size(1))
+    nf = cols if nf is None else int(nf)
+    if not 1 <= nf <= cols:
+        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
+    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
+        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    if x_ld >= 2 ** 31:
+        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
+    if n_points > 0 and n_nodes < k:
+        raise ValueError(f"idx: {what}: k = {k} neighbours of {n_nodes} nodes")
+    if cur is not None:
+        _mesh_arg(what, cur, "cur", torch.float32, shape=(n_points, nf))
+    if every < 0:
+        raise ValueError(f"every: {what}: {every} (0 keeps no series, e > 0 every e-th step)")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if (every > 0) != (series is not None):
+        raise ValueError(f"series: {what}: every = {every} {'needs a' if every else 'takes no'} series buffer")
+    if series is not None:
+        _mesh_arg(what, series, "series", torch.float32, shape=(max_steps // every, n_points, nf))
+        if step is None:
+            raise ValueError(f"step: {what}: the slots are addressed by the step index: pass step=")
+    if step is not None:
+        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
+            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
+    dev = _mesh_devices(what, ("x", x), ("idx", idx), ("coef", coef), ("cur", cur), ("step", step), ("series", series))
+    if cur is None:
+        cur = torch.empty((n_points, nf), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    s = _lib.g4c_sample_points_t(idx=_lib.ptr(idx), coef=_lib.ptr(coef), k=k, nf=nf, x_ld=x_ld, cur=_lib.ptr(cur), step=_lib.ptr(step),
+                                 every=every, n_slots=0 if series is None else int(series.size(0)), max_steps=max_steps,
+                                 series=_lib.ptr(series))
+    _lib.check(lib.g4c_sample_points(_lib.ptr(x), C.byref(s), n_nodes, n_points, _lib.stream_handle(dev)))
+    return cur
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

@@ -1,0 +1,167 @@
+"""Values of node fields at points that are no nodes (new functionality — the reference interpolates on the host, through matplotlib
+triangulations, in its plot.py): a wake profile along a line, a PIV window, a hot-wire at a coordinate, the raster of a picture.
+
+At point q with its k nearest nodes j = 0 .. k − 1 (nearest first, `knn_query_device` over `graph.pos`; d_j = pos[j] − q), the sample of
+a field x is the value at q of the plane fitted to the neighbours' values by weighted least squares, w_j = |d_j|^(−power) — a
+moving-least-squares fit with a linear basis:  x(q) = Σ_j c_j x[j]  with  c_j = w_j (1/W − e_jᵀ M⁻¹ d̄),  W = Σ w_j,  d̄ = Σ w_j d_j / W,
+e_j = d_j − d̄,  M = Σ w_j e_j e_jᵀ  — exact on constants and on linear fields, whatever the weights, inside the cloud and outside it.
+The coefficients are built once per set of points on the device in fp64 (`g4c_sample_weights`, csrc/point_sample.hip) and kept as
+fp32; every application is one memory-bound launch (`g4c_sample_points`): one thread per point and chunk of columns, fp32, the
+neighbours nearest first, so the bits are a function of the data alone.  A point on a node (distance 0) takes that node's row, bit for
+bit.  A point whose neighbours do not span the space (k <= dim, collinear / coplanar neighbours) is `degenerate`: it gets Shepard's
+c_j = w_j / W, exact on constants only."""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib, ops
+
+MAX_K = _lib.SAMPLE_MAX_K
+DEFAULT_K = {2: 6, 3: 10}
+
+
+def _integer(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _graph_dim(graph) -> int:
+    pos = getattr(graph, "pos", None)
+    if not torch.is_tensor(pos) or pos.dim() != 2 or int(pos.size(1)) not in (2, 3) or not pos.dtype.is_floating_point:
+        raise ValueError("graph: PointSampler needs graph.pos, a floating-point tensor [N, 2] or [N, 3]")
+    return int(pos.size(1))
+
+
+def _coords(name: str, v, dim: int) -> Tuple[float, ...]:
+    """`dim` finite numbers (a sequence or a 1-D tensor) -> a tuple of floats; ValueError naming the argument."""
+    try:
+        vals = [float(c) for c in (v.tolist() if torch.is_tensor(v) else v)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: expected {dim} coordinates, got {v!r}") from None
+    if len(vals) != dim or not all(c == c and abs(c) != float("inf") for c in vals):
+        raise ValueError(f"{name}: expected {dim} finite coordinates, got {v!r}")
+    return tuple(vals)
+
+
+def check_points(graph, points, k, power) -> Tuple[int, int]:
+    """The arguments of `PointSampler` on the tensors as they were passed (nothing is moved, the library is not touched): (the
+    mesh's dimension, k), or ValueError naming the argument."""
+    dim = _graph_dim(graph)
+    n = int(graph.pos.size(0))
+    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+        raise ValueError(f"power: expected 0, 1 or 2 (a neighbour weighs |d|^-power), got {power!r}")
+    if k is None:
+        k = DEFAULT_K[dim]
+    if not _integer(k) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k: expected an integer 1 <= k <= {MAX_K} (the neighbour search's limit), got {k!r}")
+    if k > n:
+        raise ValueError(f"k: {k} neighbours of a graph of {n} nodes")
+    if not torch.is_tensor(points) or not points.dtype.is_floating_point:
+        raise ValueError(f"points: expected a floating-point tensor [P, {dim}], got {getattr(points, 'dtype', type(points).__name__)}")
+    if points.dim() != 2 or int(points.size(1)) != dim:
+        raise ValueError(f"points: expected [P, {dim}] (the mesh has {dim} dimensions), got {tuple(points.shape)}")
+    if points.device.type == "cpu" and not bool(torch.isfinite(points).all()):
+        raise ValueError("points: a coordinate that is not finite")
+    return dim, int(k)
+
+
+class PointSampler:
+    """The interpolation of node fields of `graph` (a Graph on the GPU with `pos` [N, dim]) to `points` [P, dim] (a floating-point
+    tensor, host or device), built once: `k` nearest nodes per point (default 6 in 2-D, 10 in 3-D; 1 <= k <= 16 and k <= N), `power`
+    0, 1 or 2 weighs a neighbour by |d|^(−power).
+
+    `sample(x)` [P, F]: the values of x [N, F] (float32, on the device, rows of unit stride — a column slice of a wider tensor will
+    do) at the points; `idx`, `coef` [P, k]: the neighbours (the caller's node rows, nearest first) and their coefficients;
+    `distance` [P]: the distance to the nearest node — the search knows no boundary, so a point inside a body or outside the domain
+    is sampled from the nodes nearest to it: mask by `distance`; `degenerate` bool [P]: the points whose neighbours do not span the
+    space (Shepard's weights there: exact on constants only).  `PointSampler.line` and `PointSampler.grid` build rakes and rasters.
+
+    The search is NOT periodic: a point near the seam of a periodic mesh uses the neighbours on its own side; the fit is then
+    one-sided, and still exact on linear fields."""
+
+    def __init__(self, graph, points: torch.Tensor, k: Optional[int] = None, power: int = 2):
+        self.dim, self.k = check_points(graph, points, k, power)
+        pos = graph.pos
+        if pos.device.type != "cuda":
+            raise ValueError(f"graph: PointSampler runs on a HIP device only, graph.pos is on '{pos.device}' (there is no CPU fallback)")
+        from .synthetic import knn_query_device
+        self.power, self.n_nodes, self.shape = power, int(pos.size(0)), None
+        dev = pos.device
+        pos32 = pos.detach().to(torch.float32).contiguous()
+        self.points = points.detach().to(dev, torch.float32).contiguous()
+        n_points = int(self.points.size(0))
+        if n_points:
+            nearest = knn_query_device(pos32, self.points, self.k)                          # [P, k] int64, nearest first
+            self._idx = nearest.t().to(torch.int32).contiguous()                            # j-major: lane p reads consecutive entries
+        else:
+            self._idx = torch.empty((self.k, 0), dtype=torch.int32, device=dev)
+        self._coef, self.distance, degenerate = ops.sample_weights(pos32, self.points, self._idx, power)
+        self.degenerate = degenerate.bool()
+
+    @classmethod
+    def line(cls, graph, a: Sequence[float], b: Sequence[float], n: int, **kw) -> "PointSampler":
+        """A rake: `n` >= 2 points from `a` to `b`, both included, equally spaced (formed in fp64)."""
+        dim = _graph_dim(graph)
+        a, b = _coords("a", a, dim), _coords("b", b, dim)
+        if not _integer(n) or n < 2:
+            raise ValueError(f"n: expected an integer >= 2 (the points a and b included), got {n!r}")
+        t = torch.arange(n, dtype=torch.float64) / (n - 1)
+        a64, b64 = torch.tensor(a, dtype=torch.float64), torch.tensor(b, dtype=torch.float64)
+        return cls(graph, (a64 + t[:, None] * (b64 - a64)).to(torch.float32), **kw)
+
+    @classmethod
+    def grid(cls, graph, shape: Sequence[int], box=None, **kw) -> "PointSampler":
+        """A raster: `shape` = (n_x, n_y[, n_z]) points along the axes, equally spaced from corner to corner of `box` = (lo, hi), both
+        included (an axis of one point sits at the middle); `box` defaults to the bounding box of `graph.pos`.  The points are in C
+        order of `shape` — the last axis runs fastest —, so `sample(x).view(*s.shape, F)[i, j]` is the value at (x_i, y_j); `s.shape`
+        keeps the shape."""
+        dim = _graph_dim(graph)
+        try:
+            shape = tuple(shape)
+        except TypeError:
+            raise ValueError(f"shape: expected {dim} integers >= 1, got {shape!r}") from None
+        if len(shape) != dim or not all(_integer(s) and s >= 1 for s in shape):
+            raise ValueError(f"shape: expected {dim} integers >= 1 (points along each axis), got {shape!r}")
+        if box is None:
+            if int(graph.pos.size(0)) < 1:
+                raise ValueError("box: a graph without nodes has no bounding box")
+            p = graph.pos.detach()
+            lo, hi = _coords("box", p.min(0).values.double().cpu(), dim), _coords("box", p.max(0).values.double().cpu(), dim)
+        else:
+            try:
+                lo, hi = box
+            except (TypeError, ValueError):
+                raise ValueError(f"box: expected (lo, hi), two corners of {dim} coordinates, got {box!r}") from None
+            lo, hi = _coords("box", lo, dim), _coords("box", hi, dim)
+        axes = [l + (h - l) * (torch.arange(s, dtype=torch.float64) / (s - 1)) if s > 1 else torch.tensor([0.5 * (l + h)], dtype=torch.float64)
+                for l, h, s in zip(lo, hi, shape)]
+        pts = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, dim)
+        s = cls(graph, pts.to(torch.float32), **kw)
+        s.shape = shape
+        return s
+
+    @property
+    def n_points(self) -> int:
+        return int(self.points.size(0))
+
+    @property
+    def idx(self) -> torch.Tensor:
+        """[P, k] int32: the neighbours' node rows, nearest first (a view of the j-major table)."""
+        return self._idx.t()
+
+    @property
+    def coef(self) -> torch.Tensor:
+        """[P, k] float32: their coefficients (a view of the j-major table)."""
+        return self._coef.t()
+
+    def sample(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[P, F]: x [N, F] (float32, on the device, rows of unit stride, any leading dimension) at the points — one launch."""
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or int(x.size(0)) != self.n_nodes or int(x.size(1)) < 1:
+            raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, F], got {getattr(x, 'dtype', type(x).__name__)} "
+                             f"{tuple(getattr(x, 'shape', ()))}")
+        return ops.sample_points(x, self._idx, self._coef, out)
+
+    def __repr__(self):
+        return (f"PointSampler(points={self.n_points}, nodes={self.n_nodes}, dim={self.dim}, k={self.k}, power={self.power}"
+                f"{'' if self.shape is None else f', shape={self.shape}'})")

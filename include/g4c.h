@@ -608,6 +608,43 @@ int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd);
 int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d /*host*/, const g4c_derived_program_t *prog /*host*/, int64_t n_nodes,
                      void *stream);
 
+/* Values at points that are no mesh nodes (csrc/point_sample.hip): a moving-least-squares interpolation with a linear basis over the
+ * k nearest nodes of every point, 1 <= k <= G4C_SAMPLE_MAX_K (above: G4C_EUNSUPPORTED).  The tables idx and coef are j-major, [k, P]:
+ * neighbour j of point p at [j * n_points + p], nearest first, node rows of `x` / `pos`.
+ *
+ * g4c_sample_weights — once per set of points, one thread per point, fp64.  pos[n_nodes, dim] and queries[n_points, dim] are fp32.
+ * For point q and j = 0 .. k − 1, every sum over j ascending: d_j = (double)pos[idx_j] − (double)q, r2_j = Σ_a d_j,a².
+ *   exact hit   r2_0 == 0: c = (1, 0, .., 0), not degenerate;
+ *   linear fit  w_j = 1, r2_j^(−1/2) or 1 / r2_j (power 0, 1, 2), W = Σ w_j, d̄ = Σ w_j d_j / W, e_j = d_j − d̄, M = Σ w_j e_j e_jᵀ,
+ *               M⁻¹ = adj M / det M in closed form, c_j = w_j (1 / W − e_jᵀ M⁻¹ d̄): Σ c_j = 1 and Σ c_j d_j = 0, so constants and
+ *               linear fields are reproduced (the centred form: when one weight dominates, d̄ → 0 and the correction vanishes);
+ *   degenerate  k <= dim, or not det M > 1e-12 (tr M / dim)^dim (the gradient's rule): Shepard's c_j = w_j / W, exact on constants.
+ * Outputs: coef[k, P] (each rounded to fp32 once), distance[P] = (float)sqrt(r2_0), degenerate[P].  n_points == 0 launches nothing
+ * and succeeds; n_points > 0 with n_nodes < k is G4C_EINVAL; dim 2 or 3 (G4C_EUNSUPPORTED). */
+#define G4C_SAMPLE_MAX_K 16
+int g4c_sample_weights(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
+                       int64_t n_nodes, int64_t n_points, float *coef, float *distance, uint8_t *degenerate, void *stream);
+
+/* g4c_sample_points — cur[p, f] = Σ_j coef[j, p] · x[idx[j, p], f] for f < nf, fp32, j ascending, every product rounded before it is
+ * added (the first product starts the sum): one thread per (point, chunk of 4 columns), so the bits are a function of the data alone
+ * and a numpy.float32 loop reproduces them.  The same launch serves nf = 3 inside a step (AFTER the forward, BEFORE the step's closing
+ * launch: it reads the step index t = step[0] and never writes it) and nf = all the columns of a target, once.  At most 1024
+ * workgroups of 256, the items dealt gid, gid + grid, ...  cur[n_points, nf] is written on every call.  If series != NULL, every > 0,
+ * 0 <= t < max_steps, (t + 1) % every == 0 and slot = (t + 1) / every − 1 < n_slots, the same values go to series[slot][n_points][nf]
+ * (the records' slot convention); any other step writes cur only.  Every idx must be a row of x (0 <= idx < n_nodes: not checked on
+ * the device).  G4C_EINVAL before any launch: negative sizes, x_ld < nf, k < 1, a series without a step index or with every == 0,
+ * n_points > 0 with n_nodes < k.  n_points == 0 launches nothing and succeeds.  No atomics. */
+typedef struct g4c_sample_points {
+    const int32_t *idx;          /* [k, n_points] */
+    const float *coef;           /* [k, n_points] */
+    int32_t k, nf, x_ld;         /* x[n_nodes, x_ld] fp32, its first nf columns are sampled */
+    float *cur;                  /* [n_points, nf] */
+    const int32_t *step;         /* device; may be NULL without series */
+    int32_t every, n_slots, max_steps;
+    float *series;               /* [n_slots][n_points][nf] or NULL */
+} g4c_sample_points_t;
+int g4c_sample_points(const float *x, const g4c_sample_points_t *s /*host*/, int64_t n_nodes, int64_t n_points, void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
