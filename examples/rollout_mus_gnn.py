@@ -1,7 +1,7 @@
 """Drop-in use of the MI355X path with the reference's API: build a mesh with `gfd.transforms`, create (or load) a MuS-GNN,
 roll it out with `solve`.  With a trained checkpoint of the reference: `gfd.nn.NsThreeScaleGNN(checkpoint="NsThreeScaleGNN.chk")`.
 
-    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy]
+    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy] [--streak streak.npy]
 """
 import argparse, os, sys, time
 import torch
@@ -12,6 +12,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--nodes", type=int, default=20000); ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--checkpoint", default=None)
 ap.add_argument("--raster", default=None, help="write the vorticity of the last step on a 256 x 256 raster to this .npy file")
+ap.add_argument("--streak", default=None, help="write the streaklines of five seeds after the last step to this .npy file")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -48,3 +49,13 @@ if a.raster:                                                # the picture of a f
     rs = model.sample(graph, a.steps, raster, every=a.steps, derived=("vort",))
     np.save(a.raster, rs.image(-1, "vort").cpu().numpy())      # [256, 256]: entry [i, j] is the vorticity at (x_i, y_j)
     print(f"vorticity of step {a.steps - 1} on a 256 x 256 raster -> {a.raster}")
+if a.streak:                                                # smoke released at five points: particles carried by (u, v) inside the step
+    import numpy as np
+    seeds = torch.stack([torch.full((5,), 0.1), torch.linspace(0.3, 0.7, 5)], dim=1)
+    smoke = gfd.Tracers.streak(graph.to(dev), seeds, dt=0.2 * h, release_every=2, releases=max(a.steps // 2, 1), max_distance=2 * h)
+    rt = model.trace(graph, a.steps, smoke)                    # RolloutTracers: paths, status, stopped; no prediction is held
+    line, released = rt.streakline(-1)                         # [5, releases, 2]: each seed's particles, the oldest first
+    np.save(a.streak, torch.where(released[:, :, None], line, torch.full_like(line, float("nan"))).cpu().numpy())
+    gone = rt.status >= 2                                      # frozen: left the mesh (farther than 2 h from every node)
+    stay = f"{rt.residence()[gone].float().mean():.1f} steps in the domain on average" if bool(gone.any()) else "none has left the domain"
+    print(f"streaklines of 5 seeds after step {a.steps - 1} -> {a.streak}; {int(gone.sum())} of {gone.numel()} particles stopped, {stay}")

@@ -16,6 +16,7 @@ from . import nn, plan, ops, synthetic, transforms, metrics, datasets
 from .loader import DataLoader, Collater
 from .mesh_gradient import MeshGradient                # least-squares gradient over the mesh's edges: divergence, vorticity, gradients
 from .point_sampler import PointSampler                # node fields at points, rakes and rasters: a linear moving-least-squares fit over the k nearest nodes
+from .tracers import Tracers                           # Lagrangian tracers: pathlines and streaklines through the velocity at the nodes
 from .ops import check_f16_range, f16_range_report     # clipped values of the default arithmetic are reported, never silent (ops.py)
 from .nn.model import Spectrum                           # a request for per-node Fourier modes of a rollout (Rollout(spectrum=), GNN.spectrum)
 from .nn.model import set_forward_validation            # bare forward() calls validate their own fp16 range (one flag read per call)

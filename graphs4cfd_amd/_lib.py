@@ -129,6 +129,21 @@ class g4c_sample_points_t(C.Structure):
                 ("step", C.c_void_p), ("every", C.c_int32), ("n_slots", C.c_int32), ("max_steps", C.c_int32), ("series", C.c_void_p)]
 
 
+# g4c_tracer_advance (csrc/tracer.hip): the integration schemes and a particle's states
+TRACER_EULER, TRACER_HEUN = 0, 1
+TRACER_WAITING, TRACER_MOVING, TRACER_LEFT, TRACER_FAR, TRACER_NONFINITE = 0, 1, 2, 3, 4
+
+
+class g4c_tracer_t(C.Structure):
+    _fields_ = [("pos_sorted", C.c_void_p), ("order", C.c_void_p), ("cell_start", C.c_void_p), ("n_cells", C.c_int32 * 3),
+                ("origin", C.c_float * 3), ("cell_size", C.c_float), ("dim", C.c_int32), ("k", C.c_int32), ("power", C.c_int32),
+                ("x0", C.c_void_p), ("x1", C.c_void_p), ("x0_ld", C.c_int32), ("x1_ld", C.c_int32), ("vcol", C.c_int32 * 3),
+                ("scale", C.c_float * 3), ("shift", C.c_float * 3), ("dt", C.c_float), ("scheme", C.c_int32), ("box_lo", C.c_float * 3),
+                ("box_hi", C.c_float * 3), ("max_distance", C.c_float), ("step", C.c_void_p), ("t_host", C.c_int32),
+                ("max_steps", C.c_int32), ("every", C.c_int32), ("n_slots", C.c_int32), ("series", C.c_void_p), ("q", C.c_void_p),
+                ("status", C.c_void_p), ("stopped", C.c_void_p), ("release", C.c_void_p), ("vel", C.c_void_p)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -179,6 +194,7 @@ _SIGNATURES = {
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_tracer_advance": (C.c_int, [C.POINTER(g4c_tracer_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

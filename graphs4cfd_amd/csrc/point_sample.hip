@@ -8,6 +8,7 @@
 // A point's sum is taken by ONE thread over its neighbours nearest first, in fp32 without contraction: the bits are a function of
 // the data alone.  The tables are j-major [k, P]: lane p reads consecutive addresses.  Plain loads and stores, no atomics.
 #include "g4c_common.h"
+#include "point_fit.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
 // bits, and the fp64 coefficients differ from their restatement by the library's square root and division at most.
@@ -42,117 +43,9 @@ __global__ __launch_bounds__(PS_THREADS) void sample_weights_kernel(const float 
         }
         return r2;
     };
-    auto weight = [&](double r2) -> double { return power == 0 ? 1.0 : (power == 1 ? 1.0 / sqrt(r2) : 1.0 / r2); };
-    double d[DIM];
-    const double r20 = nb(0, d);
-    distance[p] = (float)sqrt(r20);
-    if (r20 == 0.0) {          // the point is a node: its row, bit for bit
-        degenerate[p] = 0;
-        for (int j = 0; j < k; ++j) coef[(long long)j * n_points + p] = j == 0 ? 1.f : 0.f;
-        return;
-    }
-    // the weighted mean of the neighbours' offsets
-    double W = 0.0, dbar[DIM];
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) dbar[a] = 0.0;
-    for (int j = 0; j < k; ++j) {
-        const double w = weight(nb(j, d));
-        W += w;
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) {
-            const double wd = w * d[a];
-            dbar[a] += wd;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) dbar[a] = dbar[a] / W;
-    // the normal matrix of the centred offsets, upper triangle row-major: (0,0), (0,1), .., (1,1), ..
-    constexpr int NM = DIM * (DIM + 1) / 2;
-    double m[NM];
-#pragma unroll
-    for (int i = 0; i < NM; ++i) m[i] = 0.0;
-    for (int j = 0; j < k; ++j) {
-        const double w = weight(nb(j, d));
-        double e[DIM];
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) e[a] = d[a] - dbar[a];
-        int i = 0;
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) {
-#pragma unroll
-            for (int b = a; b < DIM; ++b, ++i) {
-                const double we = w * e[a];
-                const double t = we * e[b];
-                m[i] += t;
-            }
-        }
-    }
-    // adjugate and determinant, as mesh_gradient_weights_kernel forms them
-    double adj[NM], det, tr;
-    if constexpr (DIM == 2) {
-        adj[0] = m[2];
-        adj[1] = -m[1];
-        adj[2] = m[0];
-        const double p0 = m[0] * m[2], p1 = m[1] * m[1];
-        det = p0 - p1;
-        tr = m[0] + m[2];
-    } else {
-        const double c00a = m[3] * m[5], c00b = m[4] * m[4];
-        const double c01a = m[2] * m[4], c01b = m[1] * m[5];
-        const double c02a = m[1] * m[4], c02b = m[2] * m[3];
-        const double c11a = m[0] * m[5], c11b = m[2] * m[2];
-        const double c12a = m[1] * m[2], c12b = m[0] * m[4];
-        const double c22a = m[0] * m[3], c22b = m[1] * m[1];
-        adj[0] = c00a - c00b;
-        adj[1] = c01a - c01b;
-        adj[2] = c02a - c02b;
-        adj[3] = c11a - c11b;
-        adj[4] = c12a - c12b;
-        adj[5] = c22a - c22b;
-        const double t0 = m[0] * adj[0], t1 = m[1] * adj[1], t2 = m[2] * adj[2];
-        det = (t0 + t1) + t2;
-        tr = (m[0] + m[3]) + m[5];
-    }
-    const double mean = tr / (double)DIM;
-    double thr = mean * mean;
-    if constexpr (DIM == 3) thr = thr * mean;
-    thr = 1e-12 * thr;
-    // the gradient's rule; k <= dim centred offsets span less than the space whatever the rounding made of det
-    const bool degen = k <= DIM || !(det > thr);
+    const bool degen = g4c::mls_fit<DIM, 0>(k, power, nb, [&](double r20) { distance[p] = (float)sqrt(r20); },          // point_fit.h
+                                            [&](int j, float c) { coef[(long long)j * n_points + p] = c; });
     degenerate[p] = degen ? 1 : 0;
-    // v = adj dbar:  M^-1 dbar = v / det
-    double v[DIM];
-    if constexpr (DIM == 2) {
-        const double a0 = adj[0] * dbar[0], a1 = adj[1] * dbar[1], b0 = adj[1] * dbar[0], b1 = adj[2] * dbar[1];
-        v[0] = a0 + a1;
-        v[1] = b0 + b1;
-    } else {
-        const double a0 = adj[0] * dbar[0], a1 = adj[1] * dbar[1], a2 = adj[2] * dbar[2];
-        const double b0 = adj[1] * dbar[0], b1 = adj[3] * dbar[1], b2 = adj[4] * dbar[2];
-        const double c0 = adj[2] * dbar[0], c1 = adj[4] * dbar[1], c2 = adj[5] * dbar[2];
-        v[0] = (a0 + a1) + a2;
-        v[1] = (b0 + b1) + b2;
-        v[2] = (c0 + c1) + c2;
-    }
-    const double invW = 1.0 / W;
-    for (int j = 0; j < k; ++j) {
-        const double w = weight(nb(j, d));
-        double c;
-        if (degen) {
-            c = w / W;                                   // Shepard: exact on constants only
-        } else {
-            double s = 0.0;
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) {
-                const double ea = d[a] - dbar[a];
-                const double t = ea * v[a];
-                s += t;
-            }
-            const double corr = s / det;
-            c = w * (invW - corr);
-        }
-        coef[(long long)j * n_points + p] = (float)c;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ per step

@@ -4,4 +4,5 @@ from .mus_gnn import *
 from .mugs_gnn import NsTwoGuillardScaleGNN, NsThreeGuillardScaleGNN, NsFourGuillardScaleGNN
 from .remus_gnn import NsRotEquiTreeScaleGNN
 from .model import GNN, TrainConfig, collate, Rollout, RolloutErrors, RolloutMoments, RolloutDerived, RolloutSpectrum, RolloutSamples, Spectrum
+from ..tracers import RolloutTracers
 from .losses import GraphLoss

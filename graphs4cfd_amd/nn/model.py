@@ -195,7 +195,7 @@ class GNN(nn.Module):
                  capture: Optional[bool] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None, samples=None,
                  sample_every: int = 1, sample_moments=None, sample_spectrum: Optional["Spectrum"] = None,
-                 sample_derived: bool = False) -> "RolloutErrors":
+                 sample_derived: bool = False, tracers=None, tracer_every: int = 1) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -209,6 +209,9 @@ class GNN(nn.Module):
         samples (a `gfd.PointSampler` or points [P, dim]) with sample_every / sample_moments / sample_spectrum / sample_derived, as in
         `Rollout`, attaches the prediction at those points (`.samples`: `RolloutSamples`) and, as its `.target`, the target's first
         num_fields * n_out columns at the same points (one launch, outside the step).
+        tracers (a `gfd.Tracers` or a tuple (seeds, dt)) with tracer_every, as in `Rollout`, attaches the particles carried by the
+        prediction (`.tracers`: `RolloutTracers`) and, as its `.target_paths`, the paths of the same particles carried by the target:
+        n_out launches outside the step, from the input field through the target's columns.
         A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
@@ -218,9 +221,13 @@ class GNN(nn.Module):
                            error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
                            derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None, samples=samples,
                            sample_every=sample_every, sample_moments=sample_moments, sample_spectrum=sample_spectrum,
-                           sample_derived=sample_derived) as ro:
+                           sample_derived=sample_derived, tracers=tracers, tracer_every=tracer_every) as ro:
             ro.run(n_out)
             errs = ro.errors()
+            errs.tracers = None
+            if ro._tracers is not None:
+                errs.tracers = ro.tracers()
+                errs.tracers.target_paths = ro._tracers.through_target(ro, n_out)
             errs.samples = None
             if ro._samples is not None:
                 errs.samples = ro.samples()
@@ -263,6 +270,25 @@ class GNN(nn.Module):
                            sample_derived=derived is not None, derived_options=derived_options or None) as ro:
             ro.run(n_out)
             return ro.samples()
+
+    def trace(self, graph: Graph, n_out: int, seeds, dt: Optional[float] = None, *, every: int = 1, capture: Optional[bool] = None,
+              **options) -> "RolloutTracers":
+        """Roll the model out for n_out steps and return the particles its velocity carried (`RolloutTracers`: paths, last positions,
+        status, stopped) — `seeds` [S, dim] with `dt` and the options of `gfd.Tracers` (scheme, k, power, velocity, scale, shift, box,
+        max_distance, release), or a `gfd.Tracers` built on this graph (a streak) — advected on the device inside the step.  No
+        prediction is held.  every = k keeps the positions after steps k - 1, 2k - 1, ... (`.paths`; 0 keeps none).  One graph only:
+        a list of graphs overlaps in space."""
+        assert n_out > 0, "n_out must be greater than 0."
+        from ..tracers import Tracers
+        if isinstance(seeds, Tracers):
+            if dt is not None or options:
+                raise ValueError("tracers: a gfd.Tracers carries its own dt and options")
+            tracers = seeds
+        else:
+            tracers = (seeds, dt, options)
+        with self._rollout(graph, n_out, capture, "trace()", every=0, tracers=tracers, tracer_every=every) as ro:
+            ro.run(n_out)
+            return ro.tracers()
 
     def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
                         capture: Optional[bool] = None) -> "RolloutMoments":
@@ -307,6 +333,8 @@ class GNN(nn.Module):
         _check_samples(graph[0] if type(graph) is list else graph, int(self.num_fields), n_out, records.get("samples"),
                        records.get("sample_every", 1), records.get("sample_moments"), records.get("sample_spectrum"),
                        records.get("sample_derived", False), records.get("derived") is not None, in_list=type(graph) is list)
+        _check_tracers(graph[0] if type(graph) is list else graph, int(self.num_fields), records.get("tracers"),
+                       records.get("tracer_every", 1), in_list=type(graph) is list)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -455,7 +483,8 @@ class Rollout:
                  mask: Optional[torch.Tensor] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None,
                  target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None, samples=None, sample_every: int = 1,
-                 sample_moments=None, sample_spectrum: Optional["Spectrum"] = None, sample_derived: bool = False):
+                 sample_moments=None, sample_spectrum: Optional["Spectrum"] = None, sample_derived: bool = False, tracers=None,
+                 tracer_every: int = 1):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -499,7 +528,15 @@ class Rollout:
         accumulate the time statistics and Fourier modes of the sampled prediction at every point, by the kernels the nodes use.
         `samples()` returns them (`RolloutSamples`), the points in the caller's order; after `rewind()` or a recomputation the
         accumulators hold the steps taken since and the slots of the steps run again are overwritten.  The neighbour search is not
-        periodic (`gfd.PointSampler`), and a list of graphs — they overlap in space — is refused."""
+        periodic (`gfd.PointSampler`), and a list of graphs — they overlap in space — is refused.
+
+        Lagrangian tracers (opt-in, no record either): `tracers` — a `gfd.Tracers` built on this graph, or a tuple (seeds [S, dim], dt)
+        (tracers with their defaults are built here) — moves a copy of the particles through every step: one `g4c_tracer_advance`
+        launch after the forward, in front of the closing launch (it reads the field window — time level t — and the prediction —
+        level t + 1 — before the window is shifted); the velocity must be among the model's fields.  `tracer_every` = k keeps the
+        positions after steps k - 1, 2k - 1, ... (0 keeps no series).  `tracers()` returns them (`RolloutTracers`), the particles in
+        the caller's order.  `rewind()` continues from the current positions (release steps then count from the rewound step index); a
+        recomputation starts again from the positions of the last `rewind()` (the seeds, without one).  A list of graphs is refused."""
         derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options,
                                       spectrum=derived_spectrum)
         spectrum_spec = _check_spectrum("spectrum", spectrum, int(model.num_fields), int(max_steps))
@@ -509,6 +546,7 @@ class Rollout:
             raise ValueError("target_spectrum: the spectrum of the target needs target= and spectrum= (it uses the same table)")
         samples_spec = _check_samples(graph, int(model.num_fields), int(max_steps), samples, sample_every, sample_moments, sample_spectrum,
                                       sample_derived, derived_spec is not None)
+        tracer_spec = _check_tracers(graph, int(model.num_fields), tracers, tracer_every)
         window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
         error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
         if error_window is not None and target is None:
@@ -554,6 +592,7 @@ class Rollout:
         self._spectrum = None if spectrum_spec is None else _Spectrum(self, spectrum_spec)
         self._target_spectrum = _Spectrum(self, spectrum_spec, x=self._rec.target, x_step=self.nf) if target_spectrum else None
         self._samples = None if samples_spec is None else _Samples(self, **samples_spec)
+        self._tracers = None if tracer_spec is None else _Tracers(self, *tracer_spec)
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -575,6 +614,8 @@ class Rollout:
                 mo.accumulate(pred, self.step_counter)
         for sp in self._spectra():
             sp.accumulate(pred, self.step_counter)
+        if self._tracers is not None:                         # (reads the window of level t before the closing launch shifts it)
+            self._tracers.launch(self.field, pred, self.step_counter)
         if self._rec is not None:
             self._rec.advance(self.field, pred, self.step_counter)
             return
@@ -633,6 +674,8 @@ class Rollout:
         self._field0.copy_(self.field)            # (a recomputation restarts here)
         self._first_slot = self.steps_done
         self._reset_moments()
+        if self._tracers is not None:
+            self._tracers.state.save()
 
     def _recompute_exact(self, hit) -> None:
         """Steps `_first_slot .. steps_done` again from the saved input window in "bf16x6"; the rollout stays in that arithmetic."""
@@ -649,6 +692,8 @@ class Rollout:
         self._hipgraph, self._epoch = None, -1
         self.steps_done = self._first_slot
         self._reset_moments()
+        if self._tracers is not None:
+            self._tracers.state.restore()
         field, self.graph.field = self.graph.field, self.field        # (after close() the graph holds its own field again)
         try:
             self.run(n)
@@ -758,6 +803,14 @@ class Rollout:
             raise RuntimeError(f"{self.label}: no samples= were asked for")
         self.validate()
         return self._samples.read()
+
+    def tracers(self) -> "RolloutTracers":
+        """What `tracers=` asked for, after the steps taken (`RolloutTracers`: the paths, the last positions, status, stopped) —
+        validated first, like `result()`."""
+        if self._tracers is None:
+            raise RuntimeError(f"{self.label}: no tracers= were asked for")
+        self.validate()
+        return self._tracers.read()
 
     def close(self) -> None:
         self.graph.field = self._orig_field
@@ -1336,6 +1389,73 @@ class RolloutSamples:
     def __repr__(self):
         return (f"RolloutSamples(points={int(self.points.size(0))}, fields={self.fields}, slots={self.slots}, derived={self.columns}, "
                 f"moments={self.moments is not None}, spectrum={self.spectrum is not None})")
+
+
+def _check_tracers(graph, nf: int, tracers, every, in_list: bool = False):
+    """The `tracers=` / `tracer_every=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing
+    is moved, the library is not touched) -> (the particles' description, every), or None when no tracers are asked for."""
+    from ..tracers import Tracers, check_tracers
+    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+        raise ValueError(f"tracer_every: expected an integer >= 0 (0: no series, k: every k-th step), got {every!r}")
+    if tracers is None:
+        if every != 1:
+            raise ValueError("tracers: tracer_every was given without tracers=")
+        return None
+    if in_list:
+        raise ValueError("tracers: a list of graphs is collated into one cloud in which the graphs overlap in space: trace each graph on its own")
+    if isinstance(tracers, Tracers):
+        spec = tracers._spec
+        if spec["n_nodes"] != int(graph.num_nodes):
+            raise ValueError(f"tracers: Tracers over {spec['n_nodes']} nodes for a graph of {int(graph.num_nodes)}")
+        if max(spec["velocity"]) >= nf:
+            raise ValueError(f"tracers: velocity: fields {spec['velocity']} of a model of {nf} (the velocity must be among the model's fields)")
+        return spec, int(every)
+    if not isinstance(tracers, tuple) or len(tracers) not in (2, 3) or (len(tracers) == 3 and not isinstance(tracers[2], dict)):
+        raise TypeError(f"tracers: expected a gfd.Tracers or a tuple (seeds, dt), got {type(tracers).__name__}")
+    try:
+        return check_tracers(graph, tracers[0], tracers[1], nf=nf, **(tracers[2] if len(tracers) == 3 else {})), int(every)
+    except ValueError as e:
+        raise ValueError(f"tracers: {e}") from None
+    except TypeError as e:
+        raise TypeError(f"tracers: {e}") from None
+
+
+class _Tracers:
+    """The tracers of a `Rollout` and the launch that moves them.  Everything is allocated here, once: the cell grid over the
+    rollout's own (possibly renumbered) positions, a copy of the particles, the series' slots.  The particles keep the caller's order
+    and a neighbour sum runs nearest first whatever the nodes are called, so nothing is permuted on read and the bits do not depend on
+    `reorder`.  x0 is the last nf columns of the field window, x1 the prediction."""
+
+    def __init__(self, ro: "Rollout", spec: dict, every: int):
+        from ..tracers import TracerState
+        self.state = TracerState(spec, ro.graph.pos.detach().to(ro.field.device, torch.float32).contiguous(), every, ro.max_steps)
+        self.state.save()                              # (a recomputation starts again from here)
+        self.nf = ro.nf
+
+    def launch(self, field, pred, step) -> None:
+        self.state.launch(field[:, int(field.size(1)) - self.nf:], pred, step=step)
+
+    def through_target(self, ro: "Rollout", n_out: int) -> Optional[torch.Tensor]:
+        """[P, dim * slots]: a copy of the same particles carried by the target instead — n_out launches outside the step: the first
+        from the input field (level 0) to the target's first nf columns (level 1), then from column block to column block."""
+        from ..tracers import TracerState
+        st, nf, target = self.state, self.nf, ro._rec.target
+        if not st.every:
+            return None
+        other = TracerState(st.spec, ro.graph.pos.detach().to(target.device, torch.float32).contiguous(), st.every, n_out)
+        x0 = ro._orig_field.to(target.device, torch.float32)
+        x0 = x0[:, int(x0.size(1)) - nf:]
+        for t in range(n_out):
+            x1 = target[:, nf * t:nf * (t + 1)]
+            other.launch(x0, x1, t=t)
+            x0 = x1
+        return ops.steps_to_columns(other.series)
+
+    def read(self) -> "RolloutTracers":
+        from ..tracers import RolloutTracers
+        st = self.state
+        return RolloutTracers(ops.steps_to_columns(st.series) if st.series is not None else None, st.q.clone(), st.status.clone(),
+                              st.stopped.clone(), st.release, st.seeds, every=st.every, groups=st.spec["groups"])
 
 
 class _Records:

@@ -1034,6 +1034,119 @@ def sample_points(x: Tensor, idx: Tensor, coef: Tensor, cur: Optional[Tensor] = 
     return cur
 
 
+def _tracer_nodes(what, x, name, n_nodes):
+    """A node tensor of tracer_advance: float32 [n_nodes, >= 1], rows of unit stride, any leading dimension -> its leading dimension."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or int(x.size(0)) != n_nodes or int(x.size(1)) < 1:
+        raise ValueError(f"{name}: {what}: expected [{n_nodes}, >= 1], got shape {tuple(x.shape)}")
+    cols = int(x.size(1))
+    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
+        raise ValueError(f"{name}: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    if ld >= 2 ** 31:
+        raise ValueError(f"{name}: {what}: a row stride of {ld} elements does not fit the descriptor")
+    return ld
+
+
+def _tracer_triple(what, name, v, dim, default):
+    """`dim` numbers (or None: `default`) -> a list of 3 floats, padded with `default`."""
+    if v is None:
+        return [float(default)] * 3
+    try:
+        vals = [float(c) for c in (v.tolist() if torch.is_tensor(v) else v)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: {what}: expected {dim} numbers, got {v!r}") from None
+    if len(vals) != dim:
+        raise ValueError(f"{name}: {what}: expected {dim} numbers, got {v!r}")
+    return vals + [float(default)] * (3 - dim)
+
+
+def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, status: Tensor, stopped: Tensor, release: Tensor, *, dt: float,
+                   k: int, power: int = 2, scheme: int = _lib.TRACER_HEUN, vcol=None, scale=None, shift=None, box_lo=None, box_hi=None,
+                   max_distance: float = float("inf"), step: Optional[Tensor] = None, t: int = 0, max_steps: int = 2 ** 31 - 1,
+                   every: int = 0, series: Optional[Tensor] = None, vel: Optional[Tensor] = None) -> Tensor:
+    """g4c_tracer_advance: one step of P massless particles through a velocity at the nodes — per particle the k nearest nodes (the
+    ring search of `knn_query_device`), the coefficients of `sample_weights`, the sum of `sample_points`, and q += dt v (scheme 0,
+    Euler, on x0) or Heun's two stages (scheme 1: x0 at q, x1 at q + dt v0).  `grid`: the cloud's cell grid (`synthetic._bin_cloud` of
+    the node positions, built once per mesh); x0, x1 float32 [N, >= 1] (rows of unit stride, any leading dimension; x1 None for Euler);
+    vcol the velocity's columns in both (default 0 .. dim - 1), v = scale u + shift; q float32 [P, dim] (updated in place), status uint8
+    [P] (0 waiting, 1 moving, 2 left the box, 3 farther than max_distance from every node, 4 a position that is not finite), stopped
+    int32 [P], release int32 [P] (the first step a particle moves at), vel float32 [P, dim] (optional: the first stage's velocity).
+    The step index is `step[0]` (int32, read on the device, never written) or, without `step`, `t`; steps outside 0 <= t < max_steps
+    move nothing.  every = e > 0 and series float32 [n_slots, P, dim] keep every particle's position after steps e - 1, 2e - 1, ... in
+    slots 0, 1, ...  include/g4c.h has the rule.  Returns q."""
+    what = "tracer_advance"
+    for key in ("pos_sorted", "order", "cell_start", "n_cells", "org", "h", "dim", "n"):
+        if not isinstance(grid, dict) or key not in grid:
+            raise ValueError(f"grid: {what}: expected the cell grid of the node cloud (synthetic._bin_cloud), got {type(grid).__name__}"
+                             f"{'' if not isinstance(grid, dict) else f' without {key!r}'}")
+    dim, n_nodes = int(grid["dim"]), int(grid["n"])
+    every, max_steps, t = int(every), int(max_steps), int(t)
+    _mesh_arg(what, grid["pos_sorted"], "grid['pos_sorted']", torch.float32, shape=(n_nodes, dim))
+    _mesh_arg(what, grid["order"], "grid['order']", torch.int32, shape=(n_nodes,))
+    cells = [int(c) for c in grid["n_cells"]]
+    if len(cells) == 3 and all(c >= 1 for c in cells):          # (the entry point refuses any other grid: the kernel reads cell_start by it)
+        _mesh_arg(what, grid["cell_start"], "grid['cell_start']", torch.int32, shape=(cells[0] * cells[1] * cells[2] + 1,))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.SAMPLE_MAX_K:
+        raise ValueError(f"k: {what}: expected an integer 1 <= k <= {_lib.SAMPLE_MAX_K}, got {k!r}")
+    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
+    if scheme not in (_lib.TRACER_EULER, _lib.TRACER_HEUN) or isinstance(scheme, bool):
+        raise ValueError(f"scheme: {what}: expected 0 (Euler) or 1 (Heun), got {scheme!r}")
+    x0_ld = _tracer_nodes(what, x0, "x0", n_nodes)
+    if x1 is None:
+        if scheme == _lib.TRACER_HEUN:
+            raise ValueError(f"x1: {what}: Heun's second stage reads the node tensor of the next time level: pass x1=")
+        x1_ld = 0
+    else:
+        x1_ld = _tracer_nodes(what, x1, "x1", n_nodes)
+    _mesh_arg(what, q, "q", torch.float32, dim=2)
+    n_particles = int(q.size(0))
+    if int(q.size(1)) != dim:
+        raise ValueError(f"q: {what}: expected [P, {dim}] (the mesh has {dim} dimensions), got {tuple(q.shape)}")
+    _mesh_arg(what, status, "status", torch.uint8, shape=(n_particles,))
+    _mesh_arg(what, stopped, "stopped", torch.int32, shape=(n_particles,))
+    _mesh_arg(what, release, "release", torch.int32, shape=(n_particles,))
+    if vel is not None:
+        _mesh_arg(what, vel, "vel", torch.float32, shape=(n_particles, dim))
+    if n_particles > 0 and n_nodes < k:
+        raise ValueError(f"k: {what}: {k} neighbours of {n_nodes} nodes")
+    vcol = list(range(dim)) if vcol is None else [v for v in vcol]
+    width = min(int(x0.size(1)), int(x1.size(1))) if x1 is not None else int(x0.size(1))
+    if len(vcol) != dim or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < width for v in vcol):
+        raise ValueError(f"vcol: {what}: expected {dim} columns of node tensors with {width} columns, got {vcol!r}")
+    scale, shift = _tracer_triple(what, "scale", scale, dim, 1.0), _tracer_triple(what, "shift", shift, dim, 0.0)
+    box_lo = _tracer_triple(what, "box_lo", box_lo, dim, float("-inf"))
+    box_hi = _tracer_triple(what, "box_hi", box_hi, dim, float("inf"))
+    if every < 0:
+        raise ValueError(f"every: {what}: {every} (0 keeps no series, e > 0 every e-th step)")
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if (every > 0) != (series is not None):
+        raise ValueError(f"series: {what}: every = {every} {'needs a' if every else 'takes no'} series buffer")
+    if series is not None:
+        _mesh_arg(what, series, "series", torch.float32, dim=3)
+        if tuple(series.shape[1:]) != (n_particles, dim):
+            raise ValueError(f"series: {what}: expected [n_slots, {n_particles}, {dim}], got {tuple(series.shape)}")
+    if step is not None:
+        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
+            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
+    dev = _mesh_devices(what, ("q", q), ("x0", x0), ("x1", x1), ("status", status), ("stopped", stopped), ("release", release),
+                        ("vel", vel), ("step", step), ("series", series), ("grid", grid["pos_sorted"]))
+    tr = _lib.g4c_tracer_t(pos_sorted=_lib.ptr(grid["pos_sorted"]), order=_lib.ptr(grid["order"]), cell_start=_lib.ptr(grid["cell_start"]),
+                           n_cells=(C.c_int32 * 3)(*grid["n_cells"]), origin=grid["org"], cell_size=float(grid["h"]), dim=dim, k=k,
+                           power=power, x0=_lib.ptr(x0), x1=_lib.ptr(x1), x0_ld=x0_ld, x1_ld=x1_ld, vcol=(C.c_int32 * 3)(*(vcol + [0] * (3 - dim))),
+                           scale=(C.c_float * 3)(*scale), shift=(C.c_float * 3)(*shift), dt=float(dt), scheme=int(scheme),
+                           box_lo=(C.c_float * 3)(*box_lo), box_hi=(C.c_float * 3)(*box_hi), max_distance=float(max_distance),
+                           step=_lib.ptr(step), t_host=t, max_steps=max_steps, every=every,
+                           n_slots=0 if series is None else int(series.size(0)), series=_lib.ptr(series), q=_lib.ptr(q),
+                           status=_lib.ptr(status), stopped=_lib.ptr(stopped), release=_lib.ptr(release), vel=_lib.ptr(vel))
+    lib = _lib.load()
+    _lib.check(lib.g4c_tracer_advance(C.byref(tr), n_nodes, n_particles, _lib.stream_handle(dev)))
+    return q
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

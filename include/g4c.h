@@ -645,6 +645,66 @@ typedef struct g4c_sample_points {
 } g4c_sample_points_t;
 int g4c_sample_points(const float *x, const g4c_sample_points_t *s /*host*/, int64_t n_nodes, int64_t n_points, void *stream);
 
+/* Lagrangian tracers (csrc/tracer.hip): massless particles carried by a velocity that lives at the nodes.  g4c_tracer_advance moves
+ * every particle one step in one launch — one thread per particle, at most 1024 workgroups of 256, the particles dealt gid, gid + grid,
+ * ..., plain loads and stores, no atomics — and may sit inside a captured step: AFTER the forward, BEFORE the step's closing launch
+ * (it reads the field window and the step index t = step[0], and never writes the index).  With step == NULL, t = t_host.
+ *
+ * The cloud's cell grid (pos_sorted, order, cell_start, n_cells, origin, cell_size) is the one g4c_knn_grid_query takes, built once
+ * per mesh by the caller.  For particle p, with t read once:
+ *   1. t < 0, t >= max_steps or t < release[p]: nothing of p changes (status 0, waiting).  status[p] >= 2: frozen, nothing changes.
+ *      Otherwise status[p] = 1 (moving) and
+ *   2. a coordinate of q[p] that is not finite: status 4, stopped[p] = t, no search (the test comes before any cell arithmetic, and a
+ *      cell coordinate is clamped as a double before it becomes an integer);
+ *   3. a stage at position r on the node tensor x: the cell floor(((double)r − (double)origin) / (double)cell_size) clamped per axis;
+ *      the k nearest nodes by g4c_knn_grid_query's ring search (same scan order, strict <, same termination), rows through `order`;
+ *      g4c_sample_weights' coefficients c_j over them (fp64, exact-hit and degenerate rules, one rounding to fp32); u_a = Σ_j c_j
+ *      x[idx_j ld + vcol_a] as g4c_sample_points sums (fp32, j ascending, each product rounded, the first starts the sum); the
+ *      physical velocity v_a = scale_a u_a + shift_a, the product rounded, then added;
+ *   4. the first stage's distance to the nearest node, (float)sqrt(r2_0), above max_distance: status 3, stopped[p] = t, q unchanged,
+ *      vel[p] not written;
+ *   5. Euler: q'_a = q_a + dt v0_a, v0 from the stage at q on x0.  Heun: q*_a = q_a + dt v0_a, v1 from the stage at q* on x1,
+ *      q'_a = q_a + (0.5f dt)(v0_a + v1_a); a q* that is not finite: status 4 as in 2, q unchanged.  All fp32, every product rounded
+ *      before its add.  vel[p] (if given) = v0;
+ *   6. q' is stored; outside [box_lo, box_hi] (a NaN is outside; the corners may be infinite): status 2, stopped[p] = t — the particle
+ *      stays where it left.
+ *   7. If series != NULL, every > 0, 0 <= t < max_steps, (t + 1) % every == 0 and slot = (t + 1) / every − 1 < n_slots (the records'
+ *      slot convention), the current q of EVERY particle — waiting, moving or frozen — goes to series[slot][n_particles][dim].
+ * G4C_EINVAL before any launch: negative sizes, k < 1, power, scheme, a vcol outside its tensor's row, a bad grid, a series with
+ * every == 0, n_particles > 0 with n_nodes < k or a null pointer (x1 may be NULL for Euler; step, series and vel may be NULL).
+ * n_particles == 0 launches nothing and succeeds.  dim 2 or 3, k <= G4C_SAMPLE_MAX_K (G4C_EUNSUPPORTED). */
+#define G4C_TRACER_EULER 0
+#define G4C_TRACER_HEUN 1
+#define G4C_TRACER_WAITING 0
+#define G4C_TRACER_MOVING 1
+#define G4C_TRACER_LEFT 2        /* left the box */
+#define G4C_TRACER_FAR 3         /* farther than max_distance from every node */
+#define G4C_TRACER_NONFINITE 4   /* a position that is not finite */
+typedef struct g4c_tracer {
+    const float *pos_sorted;     /* [n_nodes, dim] the cloud in cell-sorted order */
+    const int32_t *order;        /* [n_nodes] node row of each sorted point */
+    const int32_t *cell_start;   /* [n_cells + 1] first sorted point of each cell */
+    int32_t n_cells[3];
+    float origin[3], cell_size;
+    int32_t dim, k, power;
+    const float *x0;             /* [n_nodes, x0_ld] time level t */
+    const float *x1;             /* [n_nodes, x1_ld] time level t + 1; may be NULL for Euler */
+    int32_t x0_ld, x1_ld;
+    int32_t vcol[3];             /* the velocity's columns, in x0 and in x1 */
+    float scale[3], shift[3], dt;
+    int32_t scheme;              /* G4C_TRACER_EULER / G4C_TRACER_HEUN */
+    float box_lo[3], box_hi[3], max_distance;
+    const int32_t *step;         /* device; NULL: t = t_host */
+    int32_t t_host, max_steps, every, n_slots;
+    float *series;               /* [n_slots][n_particles][dim] or NULL */
+    float *q;                    /* [n_particles, dim], updated in place */
+    uint8_t *status;             /* [n_particles] G4C_TRACER_WAITING .. */
+    int32_t *stopped;            /* [n_particles] the step at which status became >= 2 */
+    const int32_t *release;      /* [n_particles] the first step at which the particle moves */
+    float *vel;                  /* [n_particles, dim] the first stage's physical velocity, or NULL */
+} g4c_tracer_t;
+int g4c_tracer_advance(const g4c_tracer_t *tr /*host*/, int64_t n_nodes, int64_t n_particles, void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
