@@ -1,7 +1,7 @@
 """Drop-in use of the MI355X path with the reference's API: build a mesh with `gfd.transforms`, create (or load) a MuS-GNN,
 roll it out with `solve`.  With a trained checkpoint of the reference: `gfd.nn.NsThreeScaleGNN(checkpoint="NsThreeScaleGNN.chk")`.
 
-    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy] [--streak streak.npy]
+    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy] [--streak streak.npy] [--body 64]
 """
 import argparse, os, sys, time
 import torch
@@ -13,6 +13,7 @@ ap.add_argument("--nodes", type=int, default=20000); ap.add_argument("--steps", 
 ap.add_argument("--checkpoint", default=None)
 ap.add_argument("--raster", default=None, help="write the vorticity of the last step on a 256 x 256 raster to this .npy file")
 ap.add_argument("--streak", default=None, help="write the streaklines of five seeds after the last step to this .npy file")
+ap.add_argument("--body", type=int, default=0, help="mark the W nodes nearest to a circle as a wall (bound == 4) and print its force coefficients")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -28,6 +29,10 @@ graph = gfd.transforms.Compose([
 graph.field = torch.randn(a.nodes, 3)                      # u, v, p at the last time step
 graph.glob = torch.rand(a.nodes, 1)                        # e.g. the Reynolds number
 graph.omega = (torch.rand(a.nodes, 1) > 0.9).float()       # boundary marker
+if a.body:                                                 # the reference's NsCircle / NsEllipse records carry `bound` already (4: a wall node)
+    ring = torch.argsort(((graph.pos - 0.5).norm(dim=1) - 0.1).abs())[:a.body]
+    graph.bound = torch.zeros(a.nodes, dtype=torch.uint8)
+    graph.bound[ring] = 4
 
 if a.checkpoint:
     model = gfd.nn.NsThreeScaleGNN(checkpoint=a.checkpoint, device=dev)
@@ -43,6 +48,11 @@ diag = model.diagnostics(graph, a.steps, ("div", "vort"))      # divergence and 
 print("divergence RMS per step:", " ".join(f"{v:.3e}" for v in diag.rms[:, 0].tolist()))
 spec = model.spectrum(graph, a.steps, bins=range(a.steps // 2 + 1))     # Fourier modes of u, v, p at every node, accumulated inside the step
 print(f"dominant frequency of u: {spec.dominant(0):.4f} cycles per step, largest amplitude there {spec.amplitude[:, 0].max():.3e}")
+if getattr(graph, "bound", None) is not None and bool((graph.bound == 4).any()):      # a body in the flow: its drag, lift and shedding frequency
+    D, U, rho, nu = 0.2, 1.0, 1.0, 1e-3
+    fo = model.forces(graph, a.steps, mu=rho * nu, discard=a.steps // 4, spectrum=gfd.Spectrum(bins=range(a.steps // 2 + 1)))
+    cd, cl, _ = fo.coefficients(rho, U, D)
+    print(f"mean Cd {float(cd[a.steps // 4:, 0].mean()):.4f}, r.m.s. Cl {float(cl[a.steps // 4:, 0].std(unbiased=False)):.4f}, St {fo.strouhal(D, U):.4f} (dt = 1)")
 if a.raster:                                                # the picture of a field: sampled on the device inside the step, no plotting dependency
     import numpy as np
     raster = gfd.PointSampler.grid(graph, (256, 256))          # the mesh's bounding box; .distance masks points far from every node

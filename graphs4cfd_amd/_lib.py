@@ -121,7 +121,18 @@ class g4c_mesh_derived_t(C.Structure):
                 ("snap", C.c_void_p), ("stats", C.c_void_p), ("scratch", C.c_void_p)]
 
 
-SAMPLE_MAX_K = 16                                   # G4C_SAMPLE_MAX_K: most neighbours of a sample point (the grid search's limit)
+FORCES_FPX, FORCES_FPY, FORCES_FVX, FORCES_FVY, FORCES_MP, FORCES_MV, FORCES_NSUM = range(7)     # G4C_FORCES_*
+
+
+class g4c_body_forces_t(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_ld", C.c_int32), ("x_step", C.c_int32), ("step", C.c_void_p), ("t0", C.c_int32),
+                ("pcol", C.c_int32), ("ucol", C.c_int32), ("vcol", C.c_int32), ("mu", C.c_double), ("p_scale", C.c_double),
+                ("p_shift", C.c_double), ("u_scale", C.c_double), ("v_scale", C.c_double), ("g", C.c_void_p), ("src", C.c_void_p),
+                ("off", C.c_void_p), ("item", C.c_void_p), ("body_off", C.c_void_p), ("area", C.c_void_p), ("unit", C.c_void_p),
+                ("arm", C.c_void_p), ("stats", C.c_void_p), ("cur", C.c_void_p), ("wall", C.c_void_p), ("max_steps", C.c_int32)]
+
+
+SAMPLE_MAX_K = 16                                  # G4C_SAMPLE_MAX_K: most neighbours of a sample point (the grid search's limit)
 
 
 class g4c_sample_points_t(C.Structure):
@@ -191,6 +202,7 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
     "g4c_mesh_derived": (C.c_int, [C.c_void_p, C.POINTER(g4c_mesh_derived_t), C.POINTER(g4c_derived_program_t), C.c_int64, C.c_void_p]),
+    "g4c_body_forces": (C.c_int, [C.POINTER(g4c_body_forces_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),

@@ -3,6 +3,6 @@ from . import blocks
 from .mus_gnn import *
 from .mugs_gnn import NsTwoGuillardScaleGNN, NsThreeGuillardScaleGNN, NsFourGuillardScaleGNN
 from .remus_gnn import NsRotEquiTreeScaleGNN
-from .model import GNN, TrainConfig, collate, Rollout, RolloutErrors, RolloutMoments, RolloutDerived, RolloutSpectrum, RolloutSamples, Spectrum
+from .model import GNN, TrainConfig, collate, Rollout, RolloutErrors, RolloutMoments, RolloutDerived, RolloutSpectrum, RolloutSamples, RolloutForces, Spectrum
 from ..tracers import RolloutTracers
 from .losses import GraphLoss

@@ -195,7 +195,8 @@ class GNN(nn.Module):
                  capture: Optional[bool] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None, samples=None,
                  sample_every: int = 1, sample_moments=None, sample_spectrum: Optional["Spectrum"] = None,
-                 sample_derived: bool = False, tracers=None, tracer_every: int = 1) -> "RolloutErrors":
+                 sample_derived: bool = False, tracers=None, tracer_every: int = 1, forces=None, force_moments=None,
+                 force_spectrum: Optional["Spectrum"] = None, wall_moments=None) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -212,6 +213,9 @@ class GNN(nn.Module):
         tracers (a `gfd.Tracers` or a tuple (seeds, dt)) with tracer_every, as in `Rollout`, attaches the particles carried by the
         prediction (`.tracers`: `RolloutTracers`) and, as its `.target_paths`, the paths of the same particles carried by the target:
         n_out launches outside the step, from the input field through the target's columns.
+        forces (a `gfd.BodyForces` built on this graph) with force_moments / force_spectrum / wall_moments, as in `Rollout`, attaches
+        the forces of the prediction on the bodies (`.forces`: `RolloutForces`) and, as its `.target`, those of the target's columns
+        (one more launch inside the step).
         A list of graphs is collated as in `solve`."""
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
@@ -221,9 +225,12 @@ class GNN(nn.Module):
                            error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
                            derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None, samples=samples,
                            sample_every=sample_every, sample_moments=sample_moments, sample_spectrum=sample_spectrum,
-                           sample_derived=sample_derived, tracers=tracers, tracer_every=tracer_every) as ro:
+                           sample_derived=sample_derived, tracers=tracers, tracer_every=tracer_every, forces=forces,
+                           force_moments=force_moments, force_spectrum=force_spectrum, wall_moments=wall_moments,
+                           target_forces=forces is not None) as ro:
             ro.run(n_out)
             errs = ro.errors()
+            errs.forces = ro.forces() if ro._forces is not None else None
             errs.tracers = None
             if ro._tracers is not None:
                 errs.tracers = ro.tracers()
@@ -290,6 +297,39 @@ class GNN(nn.Module):
             ro.run(n_out)
             return ro.tracers()
 
+    def forces(self, graph: Graph, n_out: int, bodies=None, *, discard: Optional[int] = None, stride: int = 1,
+               spectrum: Optional["Spectrum"] = None, wall: bool = False, capture: Optional[bool] = None, **options) -> "RolloutForces":
+        """Roll the model out for n_out steps and return the forces of every predicted step on the bodies in the flow
+        (`RolloutForces`: pressure and viscous force and moment per step and body, `coefficients`, `strouhal`) — `bodies` a
+        `gfd.BodyForces` built on this graph, or None / an integer label per wall node with the options of `gfd.BodyForces` (nodes,
+        loops, centre, mu, pressure, velocity, scale, shift, gradient, power, edge_vectors), from which one is built here — formed on
+        the device inside the step.  No prediction is held.  discard = d (not None) also accumulates the time statistics of the
+        total force over the steps d, d + stride, ... (`.moments`: the mean drag, the r.m.s. lift) and, with wall=True, of the
+        surface pressure and wall shear (`.wall_moments`); spectrum (a `gfd.Spectrum`) the Fourier modes of the total (`.spectrum`).
+        One graph only: a list of graphs overlaps in space."""
+        assert n_out > 0, "n_out must be greater than 0."
+        from ..body_forces import BodyForces, check_forces
+        if not isinstance(wall, bool):
+            raise ValueError(f"wall: expected a bool, got {wall!r}")
+        if wall and discard is None:
+            raise ValueError("wall: the wall's time statistics need discard=")
+        if type(graph) is list:
+            raise ValueError("forces: a list of graphs is collated into one cloud in which the graphs overlap in space: take each graph's forces on its own")
+        if isinstance(bodies, BodyForces):
+            if options:
+                raise ValueError(f"forces: a gfd.BodyForces carries its own options, got {sorted(options)}")
+        else:
+            check_forces(graph, options.get("nodes"), bodies, options.get("loops"), options.get("centre"),
+                         **{k: v for k, v in options.items() if k not in ("nodes", "loops", "centre")})
+            graph.to(self.device)
+            bodies = BodyForces(graph, options.get("nodes"), bodies, options.get("loops"), options.get("centre"),
+                                **{k: v for k, v in options.items() if k not in ("nodes", "loops", "centre")})
+        window = None if discard is None else (discard, stride)
+        with self._rollout(graph, n_out, capture, "forces()", every=0, forces=bodies, force_moments=window, force_spectrum=spectrum,
+                           wall_moments=window if wall else None) as ro:
+            ro.run(n_out)
+            return ro.forces()
+
     def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
                         capture: Optional[bool] = None) -> "RolloutMoments":
         """Roll the model out for n_out steps and return the time statistics of the prediction at every node (`RolloutMoments`: mean,
@@ -335,6 +375,9 @@ class GNN(nn.Module):
                        records.get("sample_derived", False), records.get("derived") is not None, in_list=type(graph) is list)
         _check_tracers(graph[0] if type(graph) is list else graph, int(self.num_fields), records.get("tracers"),
                        records.get("tracer_every", 1), in_list=type(graph) is list)
+        _check_forces(graph[0] if type(graph) is list else graph, int(self.num_fields), n_out, records.get("forces"),
+                      records.get("force_moments"), records.get("force_spectrum"), records.get("wall_moments"),
+                      records.get("target_forces", False), evaluate, in_list=type(graph) is list)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -484,7 +527,8 @@ class Rollout:
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None,
                  target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None, samples=None, sample_every: int = 1,
                  sample_moments=None, sample_spectrum: Optional["Spectrum"] = None, sample_derived: bool = False, tracers=None,
-                 tracer_every: int = 1):
+                 tracer_every: int = 1, forces=None, force_moments=None, force_spectrum: Optional["Spectrum"] = None, wall_moments=None,
+                 target_forces: bool = False):
         """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
         nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
         just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
@@ -536,7 +580,16 @@ class Rollout:
         level t + 1 — before the window is shifted); the velocity must be among the model's fields.  `tracer_every` = k keeps the
         positions after steps k - 1, 2k - 1, ... (0 keeps no series).  `tracers()` returns them (`RolloutTracers`), the particles in
         the caller's order.  `rewind()` continues from the current positions (release steps then count from the rewound step index); a
-        recomputation starts again from the positions of the last `rewind()` (the seeds, without one).  A list of graphs is refused."""
+        recomputation starts again from the positions of the last `rewind()` (the seeds, without one).  A list of graphs is refused.
+
+        Body forces (opt-in, no record either): `forces` — a `gfd.BodyForces` built on this graph — forms the pressure and viscous
+        force and moment on every body from every prediction: one `g4c_body_forces` launch (one workgroup per body) after the forward,
+        the derived columns and the samples, in front of the node moments and spectra and of the closing launch.  `force_moments` and
+        `wall_moments` (the forms `moments` takes) accumulate the time statistics of the total (F_x, F_y, M) of every body and of
+        (pressure, wall shear) at every wall item, `force_spectrum` (a `gfd.Spectrum`) the Fourier modes of the total — the lift's
+        dominant frequency is the shedding frequency —, by the kernels the nodes use.  `target_forces=True` (needs `target=`) adds one
+        more launch per step on the target's columns.  `forces()` returns them (`RolloutForces`); steps run again after `rewind()` or
+        a recomputation overwrite their rows, the accumulators hold the steps taken since.  A list of graphs is refused."""
         derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options,
                                       spectrum=derived_spectrum)
         spectrum_spec = _check_spectrum("spectrum", spectrum, int(model.num_fields), int(max_steps))
@@ -547,6 +600,8 @@ class Rollout:
         samples_spec = _check_samples(graph, int(model.num_fields), int(max_steps), samples, sample_every, sample_moments, sample_spectrum,
                                       sample_derived, derived_spec is not None)
         tracer_spec = _check_tracers(graph, int(model.num_fields), tracers, tracer_every)
+        forces_spec = _check_forces(graph, int(model.num_fields), int(max_steps), forces, force_moments, force_spectrum, wall_moments,
+                                    target_forces, target is not None)
         window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
         error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
         if error_window is not None and target is None:
@@ -593,6 +648,7 @@ class Rollout:
         self._target_spectrum = _Spectrum(self, spectrum_spec, x=self._rec.target, x_step=self.nf) if target_spectrum else None
         self._samples = None if samples_spec is None else _Samples(self, **samples_spec)
         self._tracers = None if tracer_spec is None else _Tracers(self, *tracer_spec)
+        self._forces = None if forces_spec is None else _Forces(self, **forces_spec)
 
     @property
     def outputs(self) -> torch.Tensor:
@@ -609,6 +665,8 @@ class Rollout:
             self._derived.launch(pred, self.step_counter)
         if self._samples is not None:
             self._samples.launch(pred, self.step_counter, self._derived)
+        if self._forces is not None:
+            self._forces.launch(pred, self.step_counter)
         for mo in (self._moments, self._error_moments):
             if mo is not None:
                 mo.accumulate(pred, self.step_counter)
@@ -743,7 +801,7 @@ class Rollout:
 
     def _reset_moments(self) -> None:
         for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None,
-                   self._samples.moments if self._samples is not None else None):
+                   self._samples.moments if self._samples is not None else None) + (self._forces.accumulators() if self._forces is not None else ()):
             if mo is not None:
                 mo.reset(self._first_slot)
         for sp in self._spectra() + ([self._samples.spectrum] if self._samples is not None and self._samples.spectrum is not None else []):
@@ -811,6 +869,15 @@ class Rollout:
             raise RuntimeError(f"{self.label}: no tracers= were asked for")
         self.validate()
         return self._tracers.read()
+
+    def forces(self) -> "RolloutForces":
+        """What `forces=` asked for, of the `steps_done` steps taken (`RolloutForces`: the pressure and viscous force and moment on
+        every body per step, their time statistics and Fourier modes, the wall's statistics) — validated first, like `result()`; one
+        device -> host copy of [steps_done, B, 6] sums."""
+        if self._forces is None:
+            raise RuntimeError(f"{self.label}: no forces= were asked for")
+        self.validate()
+        return self._forces.read(self.steps_done)
 
     def close(self) -> None:
         self.graph.field = self._orig_field
@@ -1456,6 +1523,153 @@ class _Tracers:
         st = self.state
         return RolloutTracers(ops.steps_to_columns(st.series) if st.series is not None else None, st.q.clone(), st.status.clone(),
                               st.stopped.clone(), st.release, st.seeds, every=st.every, groups=st.spec["groups"])
+
+
+def _check_forces(graph, nf: int, max_steps: int, forces, force_moments, force_spectrum, wall_moments, target_forces, has_target: bool,
+                  in_list: bool = False):
+    """The `forces=` / `force_*=` / `wall_moments=` / `target_forces=` arguments of `Rollout` against the caller's graph, on the
+    tensors as they were passed (nothing is moved, the library is not touched) -> the arguments of `_Forces`, or None when no forces
+    are asked for."""
+    from ..body_forces import BodyForces
+    if not isinstance(target_forces, bool):
+        raise TypeError(f"target_forces: expected a bool, got {target_forces!r}")
+    if forces is None:
+        if force_moments not in (None, False) or wall_moments not in (None, False) or force_spectrum is not None or target_forces:
+            raise ValueError("forces: force_moments / force_spectrum / wall_moments / target_forces were given without forces=")
+        return None
+    if in_list:
+        raise ValueError("forces: a list of graphs is collated into one cloud in which the graphs overlap in space: take each graph's forces on its own")
+    if not isinstance(forces, BodyForces):
+        raise TypeError(f"forces: expected a gfd.BodyForces built on this graph, got {type(forces).__name__}")
+    if forces.n_nodes != int(graph.num_nodes):
+        raise ValueError(f"forces: a BodyForces over {forces.n_nodes} nodes for a graph of {int(graph.num_nodes)}")
+    if forces.fields_needed() > nf:
+        raise ValueError(f"forces: the operator reads field {forces.fields_needed() - 1}, the model has {nf} field(s)")
+    for name, v in (("scale", forces.scale), ("shift", forces.shift)):
+        if v is not None and len(v) != nf:
+            raise ValueError(f"forces: {name}: {len(v)} numbers for a model of {nf} field(s)")
+    if target_forces and not has_target:
+        raise ValueError("target_forces: the forces of the target need target=")
+    window = _check_moments("force_moments", force_moments, 3, max_steps)
+    wall_window = _check_moments("wall_moments", wall_moments, 2, max_steps)
+    table = _check_spectrum("force_spectrum", force_spectrum, 3, max_steps)
+    return dict(forces=forces, window=window, wall_window=wall_window, spectrum=table, target_forces=target_forces)
+
+
+class _Forces:
+    """The body forces of a `Rollout` and the launches that form them.  Everything is allocated here, once: the wall items mapped
+    through the inverse of the rollout's renumbering, the gradient's tables re-indexed to it — every node keeps its in-edges in the
+    caller's CSR order, so the same values enter every sum in the same order and the bits do not depend on `reorder` —, the per-step
+    sums [max_steps, B, 6], `cur` [B, 3], `wall` [W, 2], the same sums for the target, and the accumulators of `g4c_rollout_moments`
+    and `g4c_rollout_spectrum` over `cur` (B rows) and `wall` (W rows).  Bodies and items keep the caller's order: nothing is permuted
+    on read."""
+
+    def __init__(self, ro: "Rollout", forces, window, wall_window, spectrum, target_forces: bool):
+        dev, steps = ro.field.device, ro.max_steps
+        self.op, self.nf, self.max_steps = forces, ro.nf, steps
+        self.item, self.body_off = forces._item32.to(dev), forces.body_offsets.to(dev)
+        self.area, self.unit, self.arm = forces.area.to(dev), forces.unit.to(dev), forces.arm.to(dev)
+        self.constants = forces.constants()
+        grad = forces.gradient if forces.mu != 0 else None
+        self.off, self.g, self.src = (None, None, None) if grad is None else (grad.off.to(dev), grad.g.to(dev), grad.src.to(dev))
+        if ro._perm is not None:                      # caller's row r is the rollout's row inv[r]
+            perm = ro._perm.to(dev)
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(int(ro.graph.num_nodes), device=dev)
+            self.item = inv[self.item.long()].to(torch.int32).contiguous()
+            if grad is not None:                      # the rollout's node j owns the caller's segment of node perm[j], in its order
+                off = self.off.long()
+                deg = (off[1:] - off[:-1])[perm]
+                new_off = torch.zeros_like(off)
+                new_off[1:] = torch.cumsum(deg, 0)
+                e = torch.arange(int(new_off[-1]), device=dev) + torch.repeat_interleave(off[:-1][perm] - new_off[:-1], deg)
+                self.off, self.g = new_off.to(torch.int32), self.g[e].contiguous()
+                self.src = inv[self.src[e].long()].to(torch.int32).contiguous()
+        n_bodies, n_items = forces.n_bodies, forces.n_items
+        self.stats = torch.zeros((steps, n_bodies, _lib.FORCES_NSUM), dtype=torch.float64, device=dev)
+        self.cur = torch.zeros((n_bodies, 3), dtype=torch.float32, device=dev)
+        self.wall = torch.zeros((n_items, 2), dtype=torch.float32, device=dev)
+        self.moments = None if window is None else _Moments(ro, *window, nf=3, rows=n_bodies)
+        self.wall_moments = None if wall_window is None else _Moments(ro, *wall_window, nf=2, rows=n_items)
+        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, nf=3, rows=n_bodies)
+        self.target = ro._rec.target if target_forces else None
+        self.target_stats = torch.zeros_like(self.stats) if target_forces else None
+        self.target_cur = torch.zeros_like(self.cur) if target_forces else None
+
+    def accumulators(self):
+        return (self.moments, self.wall_moments, self.spectrum)
+
+    def _launch(self, x, step, stats, cur, wall, x_step) -> None:
+        ops.body_forces(x, self.item, self.body_off, self.area, self.unit, self.arm, cur, **self.constants, off=self.off, g=self.g,
+                        src=self.src, wall=wall, stats=stats, max_steps=self.max_steps, step=step, x_step=x_step)
+
+    def launch(self, pred, step) -> None:
+        self._launch(pred, step, self.stats, self.cur, self.wall, 0)
+        if self.moments is not None:
+            self.moments.accumulate(self.cur, step)
+        if self.wall_moments is not None:
+            self.wall_moments.accumulate(self.wall, step)
+        if self.spectrum is not None:
+            self.spectrum.accumulate(self.cur, step)
+        if self.target is not None:
+            self._launch(self.target, step, self.target_stats, self.target_cur, None, self.nf)
+
+    def read(self, steps_done: int) -> "RolloutForces":
+        return RolloutForces(self.stats[:steps_done].cpu(), angle=self.op.angle, body_offsets=self.op.body_offsets,
+                             moments=self.moments.read(None) if self.moments is not None else None,
+                             wall_moments=self.wall_moments.read(None) if self.wall_moments is not None else None,
+                             spectrum=self.spectrum.read(None) if self.spectrum is not None else None,
+                             target=self.target_stats[:steps_done].cpu() if self.target_stats is not None else None)
+
+
+class RolloutForces:
+    """The forces of a rollout on the bodies in the flow (`Rollout.forces()`, `GNN.forces()`, `GNN.evaluate(forces=)`), per step
+    taken and body, fp64 host tensors: `pressure` [n, B, 3] = (F_x, F_y, M) of the pressure, `viscous` [n, B, 3] the same of the
+    viscous stress, `total` their sum — from `sums` [n, B, 6] = (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv), which the step formed on the device
+    in fp64 in a fixed order.  `moments`: the time statistics of the total (F_x, F_y, M) of every body (`RolloutMoments` over B rows,
+    `force_moments=`), `wall_moments`: of (pressure, wall shear) at every wall item (W rows, `wall_moments=` — the mean Cp(θ) against
+    `angle` [W]; `body_offsets` [B + 1] delimits the bodies), `spectrum`: the Fourier modes of the total (`RolloutSpectrum`,
+    `force_spectrum=`), each None when not asked for; `target` [n, B, 6]: the sums of the target's fields (`target_forces=True`,
+    `GNN.evaluate(forces=)`), else None.  `coefficients(rho, U, D)` = (Cd, Cl, Cm) [n, B] = (F_x, F_y, M / D) / (½ rho U² D);
+    `strouhal(D, U, body)` = the dominant frequency of that body's lift × D / U."""
+
+    def __init__(self, sums: torch.Tensor, angle: Optional[torch.Tensor] = None, body_offsets: Optional[torch.Tensor] = None,
+                 moments: Optional["RolloutMoments"] = None, wall_moments: Optional["RolloutMoments"] = None,
+                 spectrum: Optional["RolloutSpectrum"] = None, target: Optional[torch.Tensor] = None):
+        if sums.dim() != 3 or int(sums.size(2)) != _lib.FORCES_NSUM:
+            raise ValueError(f"sums: expected [steps, bodies, {_lib.FORCES_NSUM}], got {tuple(sums.shape)}")
+        self.sums, self.angle, self.body_offsets = sums, angle, body_offsets
+        self.moments, self.wall_moments, self.spectrum, self.target = moments, wall_moments, spectrum, target
+        self.pressure = sums[..., [_lib.FORCES_FPX, _lib.FORCES_FPY, _lib.FORCES_MP]]
+        self.viscous = sums[..., [_lib.FORCES_FVX, _lib.FORCES_FVY, _lib.FORCES_MV]]
+        self.total = self.pressure + self.viscous
+
+    @property
+    def steps(self) -> int:
+        return int(self.sums.size(0))
+
+    def coefficients(self, rho: float, U: float, D: float):
+        """(Cd, Cl, Cm), each [steps, B]: the total (F_x, F_y, M / D) over ½ rho U² D."""
+        for name, v in (("rho", rho), ("U", U), ("D", D)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+                raise ValueError(f"{name}: expected a positive number, got {v!r}")
+        q = 0.5 * float(rho) * float(U) * float(U) * float(D)
+        return self.total[..., 0] / q, self.total[..., 1] / q, self.total[..., 2] / (q * float(D))
+
+    def strouhal(self, D: float, U: float, body: int = 0) -> float:
+        """The frequency with the largest power of the lift of `body` (`spectrum.dominant(field=1)` of that body) × D / U."""
+        if self.spectrum is None:
+            raise RuntimeError("RolloutForces: no force_spectrum= was asked for")
+        n_bodies = int(self.spectrum.pivot.size(0))
+        if isinstance(body, bool) or not isinstance(body, int) or not 0 <= body < n_bodies:
+            raise ValueError(f"body: expected 0 .. {n_bodies - 1}, got {body!r}")
+        mask = torch.zeros(n_bodies, dtype=torch.bool)
+        mask[body] = True
+        return self.spectrum.dominant(1, mask) * float(D) / float(U)
+
+    def __repr__(self):
+        return (f"RolloutForces(steps={self.steps}, bodies={int(self.sums.size(1))}, moments={self.moments is not None}, "
+                f"wall_moments={self.wall_moments is not None}, spectrum={self.spectrum is not None}, target={self.target is not None})")
 
 
 class _Records:

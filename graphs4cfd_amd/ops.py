@@ -936,6 +936,89 @@ def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: T
     _lib.check(lib.g4c_mesh_derived(_lib.ptr(x), C.byref(d), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
 
 
+def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: Tensor, arm: Tensor, cur: Tensor, *, pcol: int,
+                ucol: int = 0, vcol: int = 1, mu: float = 0.0, p_scale: float = 1.0, p_shift: float = 0.0, u_scale: float = 1.0,
+                v_scale: float = 1.0, off: Optional[Tensor] = None, g: Optional[Tensor] = None, src: Optional[Tensor] = None,
+                wall: Optional[Tensor] = None, stats: Optional[Tensor] = None, max_steps: int = 0, step: Optional[Tensor] = None,
+                t: int = 0, x_step: int = 0) -> Tensor:
+    """g4c_body_forces: the force of the 2-D fields x (float32 [N, x_ld], rows of unit stride) on B bodies whose walls are the W
+    items `item` int32 [W] (node rows, body after body: body b holds item[body_off[b] : body_off[b + 1]], body_off int32 [B + 1]) with
+    the fp64 tables area / unit / arm [W, 2] (`gfd.BodyForces` builds them).  The pressure is p_scale x[:, pcol] + p_shift, the
+    velocity (u_scale x[:, ucol], v_scale x[:, vcol]); mu != 0 adds the viscous traction by the least-squares gradient (off int32
+    [N + 1], g float32 [E, 2], src int32 [E]: `gfd.MeshGradient`), mu == 0 reads neither the gradient nor the velocity.  x_step = nf
+    reads the columns nf t .. of a target that holds every step's fields.  The step index is `step[0]` (int32, read on the device,
+    never written) or, without `step`, `t`.  Writes cur float32 [B, 3] = (F_x, F_y, M) and wall float32 [W, 2] = (pressure, wall
+    shear) on every call, and stats float64 [max_steps, B, 6] = (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv) at row t when 0 <= t < max_steps
+    (overwritten), in a fixed order: the same bits on every run.  include/g4c.h has the arithmetic.  The entries of item are rows
+    of x: they are not checked.  Returns cur."""
+    what = "body_forces"
+    max_steps, t, x_step = int(max_steps), int(t), int(x_step)
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or int(x.size(1)) < 1:
+        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
+    n_nodes, cols = int(x.size(0)), int(x.size(1))
+    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
+        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    if x_ld >= 2 ** 31:
+        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
+    _mesh_arg(what, item, "item", torch.int32, dim=1)
+    n_items = int(item.size(0))
+    _mesh_arg(what, body_off, "body_off", torch.int32, dim=1)
+    n_bodies = int(body_off.size(0)) - 1
+    if n_bodies < 0:
+        raise ValueError(f"body_off: {what}: expected [n_bodies + 1], got shape {tuple(body_off.shape)}")
+    for name, tab in (("area", area), ("unit", unit), ("arm", arm)):
+        _mesh_arg(what, tab, name, torch.float64, shape=(n_items, 2))
+    _mesh_arg(what, cur, "cur", torch.float32, shape=(n_bodies, 3))
+    for name, v in (("mu", mu), ("p_scale", p_scale), ("p_shift", p_shift), ("u_scale", u_scale), ("v_scale", v_scale)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name}: {what}: expected a number, got {v!r}")
+    viscous = float(mu) != 0.0
+    if max_steps < 0:
+        raise ValueError(f"max_steps: {what}: {max_steps}")
+    if x_step < 0 or (x_step > 0 and max_steps < 1):
+        raise ValueError(f"x_step: {what}: {x_step} (0: x holds the fields, nf: x holds the nf fields of each of max_steps = {max_steps} >= 1 steps)")
+    width = x_step if x_step else cols
+    for name, c in (("pcol", pcol),) + ((("ucol", ucol), ("vcol", vcol)) if viscous else ()):
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < width:
+            raise ValueError(f"{name}: {what}: expected a column 0 .. {width - 1}, got {c!r}")
+    if x_step and cols < x_step * max_steps:
+        raise ValueError(f"x: {what}: {cols} columns, x_step = {x_step} and max_steps = {max_steps} need {x_step * max_steps}")
+    if viscous:
+        for name, tab in (("off", off), ("g", g), ("src", src)):
+            if tab is None:
+                raise ValueError(f"{name}: {what}: mu != 0 needs the gradient's off, g and src")
+        _mesh_arg(what, g, "g", torch.float32, dim=2)
+        if int(g.size(1)) != 2:
+            raise ValueError(f"g: {what}: expected [E, 2] (the operator is 2-D), got shape {tuple(g.shape)}")
+        _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+        _mesh_arg(what, src, "src", torch.int32, shape=(int(g.size(0)),))
+    else:
+        off = g = src = None
+        ucol = vcol = 0
+    if wall is not None:
+        _mesh_arg(what, wall, "wall", torch.float32, shape=(n_items, 2))
+    if stats is not None:
+        if max_steps < 1:
+            raise ValueError(f"max_steps: {what}: stats need max_steps >= 1, got {max_steps}")
+        _mesh_arg(what, stats, "stats", torch.float64, shape=(max_steps, n_bodies, _lib.FORCES_NSUM))
+    if step is not None:
+        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
+            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
+    dev = _mesh_devices(what, ("x", x), ("item", item), ("body_off", body_off), ("area", area), ("unit", unit), ("arm", arm), ("cur", cur),
+                        ("off", off), ("g", g), ("src", src), ("wall", wall), ("stats", stats), ("step", step))
+    lib = _lib.load()
+    bf = _lib.g4c_body_forces_t(x=_lib.ptr(x), x_ld=x_ld, x_step=x_step, step=_lib.ptr(step), t0=t, pcol=pcol, ucol=ucol, vcol=vcol,
+                                mu=float(mu), p_scale=float(p_scale), p_shift=float(p_shift), u_scale=float(u_scale), v_scale=float(v_scale),
+                                g=_lib.ptr(g), src=_lib.ptr(src), off=_lib.ptr(off), item=_lib.ptr(item), body_off=_lib.ptr(body_off),
+                                area=_lib.ptr(area), unit=_lib.ptr(unit), arm=_lib.ptr(arm), stats=_lib.ptr(stats), cur=_lib.ptr(cur),
+                                wall=_lib.ptr(wall), max_steps=max_steps)
+    _lib.check(lib.g4c_body_forces(C.byref(bf), n_bodies, n_items, _lib.stream_handle(dev)))
+    return cur
+
+
 def _sample_tables(what, idx, coef):
     """The j-major tables of ops.sample_*: idx int32 [k, P] (and coef float32 [k, P]) -> (k, P); ValueError naming the argument."""
     _mesh_arg(what, idx, "idx", torch.int32, dim=2)

@@ -608,6 +608,54 @@ int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd);
 int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d /*host*/, const g4c_derived_program_t *prog /*host*/, int64_t n_nodes,
                      void *stream);
 
+/* g4c_body_forces (csrc/body_forces.hip) — the force of a 2-D flow on the bodies it passes, once per step: AFTER the forward and
+ * BEFORE the step's closing launch (it reads the step index t = step[0] and never writes it; with step == NULL, t = t0).  A body's
+ * wall is a closed polygon of W_b items, each a mesh node with an area vector (the outward normal times the length lumped at the
+ * node), a unit normal and a moment arm, all fp64 and built once by the caller; the items of body b are item[body_off[b] ..
+ * body_off[b + 1]).  The fields are x[i, col] (x_step == 0: a prediction) or x[i, x_step t + col] (x_step = nf: a target holding
+ * every step's columns; a step outside 0 <= t < max_steps then reads and writes nothing).
+ * For item w at node i = item[w], no contraction anywhere (every product is rounded before it is added):
+ *   1. fp32, as g4c_mesh_derived: G[f][a] = 0 for f = u, v and a = 0, 1, then over the in-edges e of i in CSR order
+ *      diff = x[src_e, f] − x[i, f], p = g[e][a] · diff, G[f][a] += p — bit for bit that launch's 'grad:u', 'grad:v' at row i (zero
+ *      at a degenerate node).  Skipped entirely when mu == 0: the velocity columns are then not read.
+ *   2. fp64: P = p_scale (double)x[i, pcol] + p_shift; sxx = 2 u_scale G[u][0], sxy = u_scale G[u][1] + v_scale G[v][0],
+ *      syy = 2 v_scale G[v][1]; with a = area[w], r = arm[w], n̂ = unit[w], t̂ = (−n̂_y, n̂_x):
+ *      pressure traction tp = (−P a_x, −P a_y); viscous traction tv = mu (sxx a_x + sxy a_y, sxy a_x + syy a_y);
+ *      the moments r_x t_y − r_y t_x of each;
+ *      wall[w] = ((float)P, (float)(mu ((t̂_x sxx + t̂_y sxy) n̂_x + (t̂_x sxy + t̂_y syy) n̂_y))), written on every call (if not NULL).
+ *   3. per body the six sums {Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv} by the records' rule with ONE workgroup of 256 per body: thread tid
+ *      adds the items tid, tid + 256, ... of its body, in that order, into fp64 registers; a 6-level xor butterfly per wave; the four
+ *      waves in order through LDS.  If stats != NULL and 0 <= t < max_steps, stats[t][b] = the six sums — OVERWRITTEN, never
+ *      accumulated; any other t writes no stats.  cur[b] = ((float)(Fp_x + Fv_x), (float)(Fp_y + Fv_y), (float)(Mp + Mv)), each
+ *      sum formed in fp64 first, is written on every call.
+ * Plain loads and stores, no atomics, nothing passes between workgroups: the bits are a function of the data alone.  Every item
+ * must be a row of x (not checked on the device).
+ * G4C_EINVAL before any launch: negative sizes, a column out of range (negative, or >= x_step when x_step != 0), x_ld below a
+ * column the launch reads, mu != 0 without g / src / off, stats (or x_step != 0) without max_steps, a null pointer.  n_bodies == 0
+ * or n_items == 0 launches nothing, writes nothing and succeeds. */
+enum { G4C_FORCES_FPX, G4C_FORCES_FPY, G4C_FORCES_FVX, G4C_FORCES_FVY, G4C_FORCES_MP, G4C_FORCES_MV, G4C_FORCES_NSUM };
+typedef struct g4c_body_forces {
+    const float *x;              /* [n_nodes, x_ld] fp32 */
+    int32_t x_ld, x_step;        /* x_step 0: the fields are columns pcol, ucol, vcol; nf: columns nf t + pcol, .. of a target */
+    const int32_t *step;         /* device; NULL: t = t0 */
+    int32_t t0;
+    int32_t pcol, ucol, vcol;    /* ucol, vcol are not read when mu == 0 */
+    double mu, p_scale, p_shift, u_scale, v_scale;
+    const float *g;              /* [E, 2], CSR order (g4c_mesh_gradient_weights); may be NULL, with src and off, when mu == 0 */
+    const int32_t *src;          /* [E], CSR order */
+    const int32_t *off;          /* [n_nodes + 1] */
+    const int32_t *item;         /* [n_items] node rows, body after body, each body in counter-clockwise order */
+    const int32_t *body_off;     /* [n_bodies + 1] */
+    const double *area;          /* [n_items, 2] */
+    const double *unit;          /* [n_items, 2] */
+    const double *arm;           /* [n_items, 2] */
+    double *stats;               /* [max_steps][n_bodies][G4C_FORCES_NSUM] or NULL */
+    float *cur;                  /* [n_bodies, 3] */
+    float *wall;                 /* [n_items, 2] or NULL */
+    int32_t max_steps;
+} g4c_body_forces_t;
+int g4c_body_forces(const g4c_body_forces_t *bf /*host*/, int64_t n_bodies, int64_t n_items, void *stream);
+
 /* Values at points that are no mesh nodes (csrc/point_sample.hip): a moving-least-squares interpolation with a linear basis over the
  * k nearest nodes of every point, 1 <= k <= G4C_SAMPLE_MAX_K (above: G4C_EUNSUPPORTED).  The tables idx and coef are j-major, [k, P]:
  * neighbour j of point p at [j * n_points + p], nearest first, node rows of `x` / `pos`.
