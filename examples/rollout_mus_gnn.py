@@ -48,6 +48,17 @@ diag = model.diagnostics(graph, a.steps, ("div", "vort"))      # divergence and 
 print("divergence RMS per step:", " ".join(f"{v:.3e}" for v in diag.rms[:, 0].tolist()))
 spec = model.spectrum(graph, a.steps, bins=range(a.steps // 2 + 1))     # Fourier modes of u, v, p at every node, accumulated inside the step
 print(f"dominant frequency of u: {spec.dominant(0):.4f} cycles per step, largest amplitude there {spec.amplitude[:, 0].max():.3e}")
+# the coherent structures of the same rollout: POD of the fluctuation and DMD of the snapshots, from one fp64 Gram matrix formed on the
+# device (every second step is kept as a snapshot; pressure is left out of the inner product; dt = 1 per step)
+every = 2 if a.steps >= 8 else 1
+pod = model.modes(graph, a.steps, every=every, rank=6, field_weights=[1.0, 1.0, 0.0], dt=float(every), dmd=True)
+print("POD energy of the first modes:", " ".join(f"{e:.3f}" for e in pod.energy.tolist()), f"({pod.dropped} unresolved of {pod.gram.size(0)})")
+try:
+    k = pod.dmd.dominant()
+    print(f"dominant DMD mode: {float(pod.dmd.frequency[k]):.4f} cycles per step (the spectrum's: {spec.dominant(0):.4f}), "
+          f"growth {float(pod.dmd.growth[k]):+.4f} per step, |mu| {float(pod.dmd.eigenvalues[k].abs()):.4f}")
+except ValueError:                                          # (no oscillating mode among the first six)
+    print("no dynamic mode of the first six oscillates")
 if getattr(graph, "bound", None) is not None and bool((graph.bound == 4).any()):      # a body in the flow: its drag, lift and shedding frequency
     D, U, rho, nu = 0.2, 1.0, 1.0, 1e-3
     fo = model.forces(graph, a.steps, mu=rho * nu, discard=a.steps // 4, spectrum=gfd.Spectrum(bins=range(a.steps // 2 + 1)))

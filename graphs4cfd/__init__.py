@@ -9,11 +9,11 @@ import sys as _sys
 
 import graphs4cfd_amd as _impl
 from graphs4cfd_amd import *                                                                                # noqa: F401,F403
-from graphs4cfd_amd import Graph, DataLoader, Collater, MeshGradient, BodyForces, PointSampler, Tracers, nn, transforms, metrics, datasets, plan, ops, synthetic      # noqa: F401
+from graphs4cfd_amd import Graph, DataLoader, Collater, MeshGradient, BodyForces, PointSampler, Tracers, Modes, SnapshotModes, DynamicModes, nn, transforms, metrics, datasets, plan, ops, synthetic      # noqa: F401
 
 __version__ = _impl.__version__
 
-for _name in ("graph", "loader", "nn", "transforms", "metrics", "datasets", "plan", "ops", "synthetic", "partition", "augment", "mesh_gradient", "body_forces", "point_sampler"):
+for _name in ("graph", "loader", "nn", "transforms", "metrics", "datasets", "plan", "ops", "synthetic", "partition", "augment", "mesh_gradient", "body_forces", "point_sampler", "modes"):
     _mod = __import__(f"graphs4cfd_amd.{_name}", fromlist=["_"])
     _sys.modules[f"{__name__}.{_name}"] = _mod
     globals()[_name] = _mod

@@ -19,6 +19,7 @@ from .body_forces import BodyForces                    # drag, lift and wall loa
 from .point_sampler import PointSampler                # node fields at points, rakes and rasters: a linear moving-least-squares fit over the k nearest nodes
 from .tracers import Tracers                           # Lagrangian tracers: pathlines and streaklines through the velocity at the nodes
 from .ops import check_f16_range, f16_range_report     # clipped values of the default arithmetic are reported, never silent (ops.py)
+from .modes import Modes, SnapshotModes, DynamicModes    # POD and DMD of a rollout's snapshots from a device Gram matrix (Rollout.modes, GNN.modes)
 from .nn.model import Spectrum                           # a request for per-node Fourier modes of a rollout (Rollout(spectrum=), GNN.spectrum)
 from .nn.model import set_forward_validation            # bare forward() calls validate their own fp16 range (one flag read per call)
 from .ops import mlp_precision, set_mlp_precision      # "f16x3" (default: fp32-class two-way fp16 split on the matrix pipe) | "bf16x6" | "fp32" | "bf16" (opt-in)

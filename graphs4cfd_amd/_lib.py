@@ -155,6 +155,16 @@ class g4c_tracer_t(C.Structure):
                 ("status", C.c_void_p), ("stopped", C.c_void_p), ("release", C.c_void_p), ("vel", C.c_void_p)]
 
 
+# g4c_snapshot_* (csrc/snapshot_modes.hip): the envelope and the tile sizes the tests walk
+SNAPSHOT_MAX_ROWS = 1024                           # G4C_SNAPSHOT_MAX_ROWS: Ma, Mb, R
+SNAPSHOT_MAX_COLUMNS = 2 ** 31 - 1                 # G4C_SNAPSHOT_MAX_COLUMNS: L
+SNAPSHOT_GRAM_BLOCK, SNAPSHOT_GRAM_CHUNK, SNAPSHOT_COMBINE_BLOCK = 64, 2048, 8
+
+
+class g4c_snapshot_sel_t(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("first", C.c_int32), ("stride", C.c_int32), ("count", C.c_int32)]
+
+
 _SIGNATURES = {
     "g4c_version": (C.c_int, []),
     "g4c_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -207,6 +217,12 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_tracer_advance": (C.c_int, [C.POINTER(g4c_tracer_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_snapshot_mean": (C.c_int, [C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_int64, C.c_void_p, C.c_void_p]),
+    "g4c_snapshot_gram_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "g4c_snapshot_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t),
+                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "g4c_snapshot_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
+                                       C.c_void_p, C.c_void_p]),
     "g4c_activation_inplace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "g4c_add_cols": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int64, C.c_void_p]),

@@ -5,4 +5,5 @@ from .mugs_gnn import NsTwoGuillardScaleGNN, NsThreeGuillardScaleGNN, NsFourGuil
 from .remus_gnn import NsRotEquiTreeScaleGNN
 from .model import GNN, TrainConfig, collate, Rollout, RolloutErrors, RolloutMoments, RolloutDerived, RolloutSpectrum, RolloutSamples, RolloutForces, Spectrum
 from ..tracers import RolloutTracers
+from ..modes import Modes, SnapshotModes, DynamicModes
 from .losses import GraphLoss

@@ -196,7 +196,7 @@ class GNN(nn.Module):
                  derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None, samples=None,
                  sample_every: int = 1, sample_moments=None, sample_spectrum: Optional["Spectrum"] = None,
                  sample_derived: bool = False, tracers=None, tracer_every: int = 1, forces=None, force_moments=None,
-                 force_spectrum: Optional["Spectrum"] = None, wall_moments=None) -> "RolloutErrors":
+                 force_spectrum: Optional["Spectrum"] = None, wall_moments=None, modes=None) -> "RolloutErrors":
         """Roll the model out against `graph.target` ([N, >= num_fields * n_out]; n_out defaults to all the steps it holds) and return
         the error of every step (`RolloutErrors`: mse, mae, max_abs, r2 per step and field, `mae_masked` over the Dirichlet nodes
         `graph.omega[:, 0] == 1` when the graph has `omega`, `graph_loss(lambda_d)`), formed on the device inside the step — the
@@ -216,7 +216,16 @@ class GNN(nn.Module):
         forces (a `gfd.BodyForces` built on this graph) with force_moments / force_spectrum / wall_moments, as in `Rollout`, attaches
         the forces of the prediction on the bodies (`.forces`: `RolloutForces`) and, as its `.target`, those of the target's columns
         (one more launch inside the step).
+        modes (a `gfd.Modes`; needs every >= 1: the kept snapshots are its data) attaches the modal analysis of the prediction and of
+        the target's columns of the same steps (`.modes`: `.prediction`, `.target` — `SnapshotModes` — and `.alignment`, the principal
+        cosines between the two mode subspaces), formed after the rollout: no launch inside the step.
         A list of graphs is collated as in `solve`."""
+        if modes is not None:
+            from ..modes import Modes
+            if not isinstance(modes, Modes):
+                raise TypeError(f"modes: expected a gfd.Modes, got {type(modes).__name__}")
+            if int(every) < 1:
+                raise ValueError("modes: the modes are formed from the kept snapshots: give every=k >= 1 (every=0 keeps none)")
         target = graph[0].target if type(graph) is list else graph.target
         if n_out is None:
             n_out = int(target.size(1)) // int(self.num_fields)
@@ -245,6 +254,12 @@ class GNN(nn.Module):
             errs.moments = ro.moments() if ro._moments is not None else None
             errs.error_moments = ro.error_moments() if ro._error_moments is not None else None
             errs.derived = ro.derived() if ro._derived is not None else None
+            errs.modes = None
+            if modes is not None:
+                from ..modes import ModesComparison
+                nf, k = int(self.num_fields), int(every)
+                tgt = ro._rec.target[:, :nf * n_out].reshape(-1, n_out, nf).permute(1, 0, 2)[k - 1::k].contiguous()    # (the rollout's rows)
+                errs.modes = ModesComparison(ro.modes(modes), modes._fit_steps(tgt, int(tgt.size(0)), ro._perm))
             return errs
 
     def diagnostics(self, graph: Union[Graph, List[Graph]], n_out: int, derived=("div", "vort"), *, every: int = 0, discard: Optional[int] = None,
@@ -361,6 +376,28 @@ class GNN(nn.Module):
             sp.snapshots = ro.result() if int(every) else None
             sp.derived = ro.derived_spectrum() if derived is not None else None
             return sp
+
+    def modes(self, graph: Union[Graph, List[Graph]], n_out: int, modes=None, *, every: int = 1, capture: Optional[bool] = None, **spec):
+        """Roll the model out for n_out steps and return the modal analysis of the predictions kept (`SnapshotModes`: POD singular
+        values, energies, time coefficients and modes; with dmd=True the dynamic modes, their frequencies and growth rates) — `modes` a
+        `gfd.Modes`, or its arguments as keywords (rank, energy, centre, node_weights, field_weights, start, stride, count, dt, dmd).
+        every = k keeps steps k - 1, 2k - 1, ... as the snapshots; start / stride / count are in those.  Formed after the rollout from
+        its own step-major buffer: a fp64 Gram matrix in a fixed order of summation (`g4c_snapshot_gram`), no launch inside the step.
+        A list of graphs is collated as in `solve`: the modes are over the batched node set."""
+        assert n_out > 0, "n_out must be greater than 0."
+        from ..modes import Modes
+        if modes is None:
+            modes = Modes(**spec)
+        elif not isinstance(modes, Modes):
+            raise TypeError(f"modes: expected a gfd.Modes or None, got {type(modes).__name__}")
+        elif spec:
+            raise ValueError(f"modes: a gfd.Modes carries its own options, got {sorted(spec)}")
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"every: modes() keeps every k-th step as a snapshot, k >= 1, got {every!r}")
+        modes.selection(n_out // every)                   # (argument errors before anything is moved)
+        with self._rollout(graph, n_out, capture, "modes()", every=every) as ro:
+            ro.run(n_out)
+            return ro.modes(modes)
 
     def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
         """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
@@ -878,6 +915,20 @@ class Rollout:
             raise RuntimeError(f"{self.label}: no forces= were asked for")
         self.validate()
         return self._forces.read(self.steps_done)
+
+    def modes(self, spec) -> "SnapshotModes":
+        """The modal analysis `spec` (a `gfd.Modes`) asks for of the snapshots kept so far (`SnapshotModes`; mean and modes in the
+        caller's rows) — validated first, like `result()`.  It reads the step-major buffer `result()` is a transposed copy of, and of it
+        only the slots of steps taken; start / stride / count of `spec` are in kept slots.  Nothing is allocated or launched for it
+        before this call."""
+        from ..modes import Modes
+        if not isinstance(spec, Modes):
+            raise TypeError(f"modes: expected a gfd.Modes, got {type(spec).__name__}")
+        if self._out_steps is None:
+            raise RuntimeError(f"{self.label}: every=0 keeps no snapshot of the predictions to form modes of")
+        self.validate()
+        every = self._rec.every if self._rec is not None else 1
+        return spec._fit_steps(self._out_steps, self.steps_done // every, self._perm)
 
     def close(self) -> None:
         self.graph.field = self._orig_field

@@ -1230,6 +1230,158 @@ def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, stat
     return q
 
 
+def _snapshot_rows(what: str, x, name: str):
+    """A snapshot matrix float32 [rows >= 1, L >= 1] (or [rows, N, nf], read as L = N nf), contiguous -> (rows, L)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise TypeError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() not in (2, 3) or int(x.size(0)) < 1 or x.numel() == 0:
+        raise ValueError(f"{name}: {what}: expected snapshots [rows >= 1, L >= 1] or [rows, N, nf], got shape {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name}: {what} needs step-major contiguous snapshots, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    rows, L = int(x.size(0)), x.numel() // int(x.size(0))
+    if L > _lib.SNAPSHOT_MAX_COLUMNS:
+        raise NotImplementedError(f"{name}: {what}: L = {L} values in a snapshot (at most {_lib.SNAPSHOT_MAX_COLUMNS})")
+    return rows, L
+
+
+def _snapshot_sel(what: str, sel, name: str, rows: int) -> "_lib.g4c_snapshot_sel_t":
+    """(first, stride, count) — None: every row — against a buffer of `rows` snapshots."""
+    if sel is None:
+        sel = (0, 1, rows)
+    if not isinstance(sel, (tuple, list)) or len(sel) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in sel):
+        raise TypeError(f"{name}: {what}: expected (first, stride, count) as three integers, got {sel!r}")
+    first, stride, count = sel
+    if first < 0 or stride < 1 or count < 1 or first + (count - 1) * stride >= rows:
+        raise ValueError(f"{name}: {what}: first = {first} (>= 0), stride = {stride} (>= 1), count = {count} (>= 1) select rows up to "
+                         f"{first + (count - 1) * stride} of {rows} snapshots")
+    return _lib.g4c_snapshot_sel_t(rows=rows, first=first, stride=stride, count=count)
+
+
+def _snapshot_vector(what: str, t, name: str, L: int, dev) -> None:
+    """An optional float64 [L] (or [N, nf] with N nf = L), contiguous, on the snapshots' device."""
+    if t is None:
+        return
+    if not torch.is_tensor(t) or t.dtype != torch.float64:
+        raise TypeError(f"{name}: {what}: expected a float64 tensor or None, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.numel() != L or not t.is_contiguous():
+        raise ValueError(f"{name}: {what}: expected {L} contiguous values, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if t.device != dev:
+        raise ValueError(f"{name}: {what}: on '{t.device}', the snapshots are on '{dev}'")
+
+
+def snapshot_mean(x: Tensor, sel=None, out: Optional[Tensor] = None) -> Tensor:
+    """g4c_snapshot_mean: the fp64 mean over the selected snapshots of every column, float64 [L] — the rows first, first + stride, ...
+    (sel = (first, stride, count); None: all) of x float32 [rows, L] (or [rows, N, nf]) added in slot order, one division: bit for
+    bit the plain fp64 loop."""
+    what = "snapshot_mean"
+    rows, L = _snapshot_rows(what, x, "x")
+    s = _snapshot_sel(what, sel, "sel", rows)
+    dev = x.device
+    _snapshot_vector(what, out, "out", L, dev)
+    _lib.require_hip(x)
+    if out is None:
+        out = torch.empty(L, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().g4c_snapshot_mean(_lib.ptr(x), C.byref(s), L, _lib.ptr(out), _lib.stream_handle(dev)))
+    return out
+
+
+def _gram_symmetric(a, mean_a, sa, b, mean_b, sb) -> bool:
+    same_mean = (mean_a is None and mean_b is None) or (mean_a is not None and mean_b is not None and mean_a.data_ptr() == mean_b.data_ptr())
+    return (a.data_ptr() == b.data_ptr() and same_mean and (sa.first, sa.stride, sa.count) == (sb.first, sb.stride, sb.count))
+
+
+def snapshot_gram_scratch_bytes(Ma: int, Mb: int, L: int, symmetric: bool) -> int:
+    """g4c_snapshot_gram_scratch_bytes: what one g4c_snapshot_gram launch of these sizes writes into its scratch, in bytes."""
+    n = int(_lib.load().g4c_snapshot_gram_scratch_bytes(int(Ma), int(Mb), int(L), 1 if symmetric else 0))
+    if n < 0:
+        raise NotImplementedError(f"snapshot_gram: Ma = {Ma}, Mb = {Mb} (1 .. {_lib.SNAPSHOT_MAX_ROWS}, equal in the symmetric form), L = {L} "
+                                  f"(1 .. {_lib.SNAPSHOT_MAX_COLUMNS})")
+    return n
+
+
+def snapshot_gram(a: Tensor, b: Optional[Tensor] = None, *, mean_a: Optional[Tensor] = None, mean_b: Optional[Tensor] = None, sel_a=None,
+                  sel_b=None, w: Optional[Tensor] = None, out: Optional[Tensor] = None, scratch: Optional[Tensor] = None) -> Tensor:
+    """g4c_snapshot_gram: G[i][j] = Σ_l w[l] (a_i[l] − mean_a[l]) (b_j[l] − mean_b[l]) in fp64, float64 [Ma, Mb], over the selected rows
+    of a, b float32 [rows, L] (b None: b = a with a's mean and selection — the symmetric form, whose G is symmetric bit for bit).
+    mean_* float64 [L] or None (no centring), w float64 [L] or None (ones).  The order of the sum is a function of (Ma, Mb, L) alone.
+    out: float64 [Ma, Mb] with rows of unit stride; scratch: a contiguous uint8 / float64 buffer of at least
+    `snapshot_gram_scratch_bytes` bytes (allocated here when None)."""
+    what = "snapshot_gram"
+    if b is None:
+        if mean_b is not None or sel_b is not None:
+            raise ValueError(f"mean_b: {what}: mean_b / sel_b were given without b")
+        b, mean_b, sel_b = a, mean_a, sel_a
+    rows_a, L = _snapshot_rows(what, a, "a")
+    rows_b, Lb = _snapshot_rows(what, b, "b")
+    if Lb != L:
+        raise ValueError(f"b: {what}: snapshots of {Lb} values, a's hold {L}")
+    sa, sb = _snapshot_sel(what, sel_a, "sel_a", rows_a), _snapshot_sel(what, sel_b, "sel_b", rows_b)
+    for s, name in ((sa, "sel_a"), (sb, "sel_b")):
+        if s.count > _lib.SNAPSHOT_MAX_ROWS:
+            raise NotImplementedError(f"{name}: {what}: {s.count} snapshots (at most {_lib.SNAPSHOT_MAX_ROWS})")
+    dev = a.device
+    if b.device != dev:
+        raise ValueError(f"b: {what}: on '{b.device}', a is on '{dev}'")
+    for t, name in ((mean_a, "mean_a"), (mean_b, "mean_b"), (w, "w")):
+        _snapshot_vector(what, t, name, L, dev)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float64 or out.device != dev:
+            raise TypeError(f"out: {what}: expected a float64 tensor on '{dev}', got {getattr(out, 'dtype', type(out).__name__)}")
+        if tuple(out.shape) != (sa.count, sb.count) or (sb.count > 1 and out.stride(1) != 1) or (sa.count > 1 and out.stride(0) < sb.count):
+            raise ValueError(f"out: {what}: expected [{sa.count}, {sb.count}] with rows of unit stride, got shape {tuple(out.shape)} strides "
+                             f"{tuple(out.stride())}")
+    # (g4c_snapshot_gram_scratch_bytes restated, so that a scratch that is too small is refused before the library is touched)
+    nbi, nbj = -(-sa.count // _lib.SNAPSHOT_GRAM_BLOCK), -(-sb.count // _lib.SNAPSHOT_GRAM_BLOCK)
+    blocks = nbi * (nbi + 1) // 2 if _gram_symmetric(a, mean_a, sa, b, mean_b, sb) else nbi * nbj
+    need = 8 * _lib.SNAPSHOT_GRAM_BLOCK ** 2 * blocks * -(-L // _lib.SNAPSHOT_GRAM_CHUNK)
+    if scratch is not None and (not torch.is_tensor(scratch) or scratch.device != dev or not scratch.is_contiguous()
+                                or scratch.numel() * scratch.element_size() < need or scratch.data_ptr() % 8):
+        raise ValueError(f"scratch: {what}: expected a contiguous 8-byte aligned buffer of at least {need} bytes on '{dev}'")
+    _lib.require_hip(a, b)
+    if out is None:
+        out = torch.empty((sa.count, sb.count), dtype=torch.float64, device=dev)
+    if scratch is None:
+        scratch = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    ld = int(out.stride(0)) if sa.count > 1 else sb.count
+    _lib.check(_lib.load().g4c_snapshot_gram(_lib.ptr(a), _lib.ptr(mean_a), C.byref(sa), _lib.ptr(b), _lib.ptr(mean_b), C.byref(sb), _lib.ptr(w),
+                                             L, _lib.ptr(out), ld, _lib.ptr(scratch), _lib.stream_handle(dev)))
+    return out
+
+
+def snapshot_combine(x: Tensor, coef: Tensor, *, mean: Optional[Tensor] = None, sel=None, out: Optional[Tensor] = None) -> Tensor:
+    """g4c_snapshot_combine: out[r][l] = (float) Σ_i coef[i][r] ((double)x_i[l] − mean[l]), float32 [R, L], over the selected rows of x
+    float32 [rows, L] in slot order; coef float64 [count, R] with rows of unit stride (on the device), mean float64 [L] or None.
+    Product and sum are rounded separately: bit for bit a plain fp64 loop rounded once to fp32."""
+    what = "snapshot_combine"
+    rows, L = _snapshot_rows(what, x, "x")
+    s = _snapshot_sel(what, sel, "sel", rows)
+    dev = x.device
+    if not torch.is_tensor(coef) or coef.dtype != torch.float64:
+        raise TypeError(f"coef: {what}: expected a float64 tensor, got {getattr(coef, 'dtype', type(coef).__name__)}")
+    if coef.dim() != 2 or int(coef.size(0)) != s.count or int(coef.size(1)) < 1 or (coef.size(1) > 1 and coef.stride(1) != 1) \
+            or (s.count > 1 and coef.stride(0) < coef.size(1)):
+        raise ValueError(f"coef: {what}: expected [count = {s.count}, R >= 1] with rows of unit stride, got shape {tuple(coef.shape)} strides "
+                         f"{tuple(coef.stride())}")
+    if coef.device != dev:
+        raise ValueError(f"coef: {what}: on '{coef.device}', the snapshots are on '{dev}'")
+    R = int(coef.size(1))
+    if R > _lib.SNAPSHOT_MAX_ROWS or s.count > _lib.SNAPSHOT_MAX_ROWS:
+        raise NotImplementedError(f"coef: {what}: {s.count} snapshots into {R} combinations (at most {_lib.SNAPSHOT_MAX_ROWS} each)")
+    _snapshot_vector(what, mean, "mean", L, dev)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev:
+            raise TypeError(f"out: {what}: expected a float32 tensor on '{dev}', got {getattr(out, 'dtype', type(out).__name__)}")
+        if out.numel() != R * L or int(out.size(0)) != R or not out.is_contiguous():
+            raise ValueError(f"out: {what}: expected a contiguous [{R}, {L}], got shape {tuple(out.shape)} strides {tuple(out.stride())}")
+    _lib.require_hip(x)
+    if out is None:
+        out = torch.empty((R, L), dtype=torch.float32, device=dev)
+    ldc = int(coef.stride(0)) if s.count > 1 else R
+    _lib.check(_lib.load().g4c_snapshot_combine(_lib.ptr(x), _lib.ptr(mean), C.byref(s), _lib.ptr(coef), ldc, R, L, _lib.ptr(out),
+                                                _lib.stream_handle(dev)))
+    return out
+
+
 def steps_to_columns(out_steps: Tensor) -> Tensor:
     """Step-major rollout outputs [steps, n_nodes, nf] -> the reference's layout [n_nodes, nf * steps] (nn/model.py:322-326)."""
     return out_steps.permute(1, 0, 2).reshape(out_steps.size(1), -1)

@@ -753,6 +753,40 @@ typedef struct g4c_tracer {
 } g4c_tracer_t;
 int g4c_tracer_advance(const g4c_tracer_t *tr /*host*/, int64_t n_nodes, int64_t n_particles, void *stream);
 
+/* g4c_snapshot_mean / _gram / _combine (csrc/snapshot_modes.hip) — the three launches of POD and DMD by the method of snapshots that
+ * touch L-sized data (graphs4cfd_amd/modes.py holds the M-sized algebra; the reference has no counterpart).  They run AFTER a
+ * rollout, outside the step.  A snapshot matrix is float32 [rows, L], rows contiguous with leading dimension L — a rollout's
+ * step-major buffer [slots, N, nf] with L = N nf — and a selection names the rows first, first + stride, ... (count of them).  All sums
+ * are fp64 in an order that is a function of the shapes alone; no floating-point atomics.
+ *   mean[l]  = (sum_i (double)x[first + i stride][l]) / count, i in slot order: bit for bit the plain fp64 loop.
+ *   G[i][j]  = sum_l w[l] ((double)a_i[l] - mean_a[l]) ((double)b_j[l] - mean_b[l]); mean_* NULL: no centring; w NULL: ones.  The product
+ *              of two fp32 values is exact in fp64, so the uncentred unweighted form is a sum of exact terms.  A workgroup owns a block
+ *              of G4C_SNAPSHOT_GRAM_BLOCK^2 entries and a chunk of G4C_SNAPSHOT_GRAM_CHUNK columns, stages (a - mean_a) w and b - mean_b
+ *              through LDS as fp64 and accumulates with v_mfma_f64_16x16x4_f64 (four columns a step, in the pipe's own order); a second
+ *              launch adds the chunks' partial blocks in chunk order.  When a == b, mean_a == mean_b and the selections are equal only
+ *              the blocks on and below the diagonal are computed, and that launch writes each entry below the diagonal and its mirror
+ *              image: G is symmetric bit for bit.  scratch: g4c_snapshot_gram_scratch_bytes(Ma, Mb, L, symmetric) bytes, all written
+ *              (-1 for sizes outside the envelope).
+ *   out[r][l] = (float) sum_i C[i][r] ((double)x_i[l] - mean[l]), i in slot order, product and sum rounded separately: bit for bit a
+ *              plain fp64 loop rounded once to fp32.  C: float64 [count, R] with leading dimension ldc, read uniformly; a thread owns
+ *              one column and G4C_SNAPSHOT_COMBINE_BLOCK values of r, so x is read once per block of r. */
+#define G4C_SNAPSHOT_MAX_ROWS 1024              /* Ma, Mb, R: G4C_EUNSUPPORTED above */
+#define G4C_SNAPSHOT_MAX_COLUMNS 2147483647LL   /* L: 32-bit indices within one snapshot */
+#define G4C_SNAPSHOT_GRAM_BLOCK 64
+#define G4C_SNAPSHOT_GRAM_CHUNK 2048
+#define G4C_SNAPSHOT_COMBINE_BLOCK 8
+typedef struct g4c_snapshot_sel {
+    int32_t rows;                /* snapshots in the buffer */
+    int32_t first, stride, count; /* the rows first + i stride, i < count, all < rows */
+} g4c_snapshot_sel_t;
+int g4c_snapshot_mean(const float *x, const g4c_snapshot_sel_t *sel /*host*/, int64_t L, double *mean_out /*[L]*/, void *stream);
+int64_t g4c_snapshot_gram_scratch_bytes(int32_t Ma, int32_t Mb, int64_t L, int32_t symmetric);
+int g4c_snapshot_gram(const float *a, const double *mean_a, const g4c_snapshot_sel_t *sel_a /*host*/, const float *b, const double *mean_b,
+                      const g4c_snapshot_sel_t *sel_b /*host*/, const double *w, int64_t L, double *G_out /*[Ma, Mb]*/, int64_t ld,
+                      void *scratch, void *stream);
+int g4c_snapshot_combine(const float *x, const double *mean, const g4c_snapshot_sel_t *sel /*host*/, const double *C, int64_t ldc, int32_t R,
+                         int64_t L, float *out /*[R, L]*/, void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
