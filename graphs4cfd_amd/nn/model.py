@@ -1,4 +1,5 @@
-"""`GNN` base class: model construction / checkpoint loading and the rollout loop.
+"""`GNN` base class: model construction / checkpoint loading and the entry points that roll a model out (the rollout itself —
+`Rollout`, what rides along in its step, the result classes — is rollout.py; its names are re-exported here).
 
 Mirrors the inference-side surface of the reference's graphs4cfd/nn/model.py: constructor
 `(arch, weights, checkpoint, device)`, `load_model` (:112-130), `solve` (:303-321),
@@ -19,8 +20,11 @@ from typing import Callable, List, Optional, Union
 import torch
 from torch import nn
 
-from .. import _lib, ops, plan
+from .. import _lib, ops
 from ..graph import Graph
+# the rollout and what rides along in its step live in rollout.py; every name stays importable from here
+from .rollout import (KEYWORDS, REORDER_MIN_NODES, Rollout, RolloutDerived, RolloutErrors, RolloutForces, RolloutMoments,      # noqa: F401
+                      RolloutSamples, RolloutSpectrum, Spectrum, _check_moments, _check_parts, _check_records, _check_spectrum)
 
 
 def collate(graphs: List[Graph]) -> Graph:
@@ -220,6 +224,7 @@ class GNN(nn.Module):
         the target's columns of the same steps (`.modes`: `.prediction`, `.target` — `SnapshotModes` — and `.alignment`, the principal
         cosines between the two mode subspaces), formed after the rollout: no launch inside the step.
         A list of graphs is collated as in `solve`."""
+        records = {k: v for k, v in locals().items() if k in KEYWORDS}          # (the keywords this signature shares with `Rollout`)
         if modes is not None:
             from ..modes import Modes
             if not isinstance(modes, Modes):
@@ -230,30 +235,17 @@ class GNN(nn.Module):
         if n_out is None:
             n_out = int(target.size(1)) // int(self.num_fields)
         assert n_out > 0, "n_out must be greater than 0."
-        with self._rollout(graph, n_out, capture, "evaluate()", every=int(every), probes=probes, evaluate=True, moments=moments,
-                           error_moments=error_moments, derived=derived, derived_every=derived_every, derived_moments=derived_moments,
-                           derived_options=derived_options, spectrum=spectrum, target_spectrum=spectrum is not None, samples=samples,
-                           sample_every=sample_every, sample_moments=sample_moments, sample_spectrum=sample_spectrum,
-                           sample_derived=sample_derived, tracers=tracers, tracer_every=tracer_every, forces=forces,
-                           force_moments=force_moments, force_spectrum=force_spectrum, wall_moments=wall_moments,
-                           target_forces=forces is not None) as ro:
+        records.update(every=int(every), target_spectrum=spectrum is not None, target_forces=forces is not None)
+        with self._rollout(graph, n_out, capture, "evaluate()", evaluate=True, **records) as ro:
             ro.run(n_out)
             errs = ro.errors()
-            errs.forces = ro.forces() if ro._forces is not None else None
-            errs.tracers = None
-            if ro._tracers is not None:
-                errs.tracers = ro.tracers()
-                errs.tracers.target_paths = ro._tracers.through_target(ro, n_out)
-            errs.samples = None
-            if ro._samples is not None:
-                errs.samples = ro.samples()
+            for name in ("forces", "tracers", "samples", "spectrum", "target_spectrum", "moments", "error_moments", "derived"):
+                setattr(errs, name, getattr(ro, name)() if name in ro._parts else None)
+            if errs.tracers is not None:
+                errs.tracers.target_paths = ro._parts["tracers"].through_target(ro, n_out)
+            if errs.samples is not None:
                 tgt = ro._caller_graph.target.to(torch.float32)
                 errs.samples.target = errs.samples.sampler.sample(tgt[:, :int(self.num_fields) * n_out])
-            if spectrum is not None:
-                errs.spectrum, errs.target_spectrum = ro.spectrum(), ro.target_spectrum()
-            errs.moments = ro.moments() if ro._moments is not None else None
-            errs.error_moments = ro.error_moments() if ro._error_moments is not None else None
-            errs.derived = ro.derived() if ro._derived is not None else None
             errs.modes = None
             if modes is not None:
                 from ..modes import ModesComparison
@@ -401,20 +393,7 @@ class GNN(nn.Module):
 
     def _rollout(self, graph, n_out: int, capture: Optional[bool], label: str, evaluate: bool = False, **records) -> "Rollout":
         """The Rollout of solve() / evaluate(): the graph (or the collated list) on the model's device, the capture default."""
-        if records.get("derived") is not None:            # (argument errors before anything is collated or moved)
-            for gr in (graph if type(graph) is list else [graph]):
-                _check_derived(gr, int(self.num_fields), n_out, records["derived"], records.get("derived_every", 0),
-                               records.get("derived_moments"), records.get("derived_options"), in_list=type(graph) is list,
-                               spectrum=records.get("derived_spectrum"))
-        _check_spectrum("spectrum", records.get("spectrum"), int(self.num_fields), n_out)
-        _check_samples(graph[0] if type(graph) is list else graph, int(self.num_fields), n_out, records.get("samples"),
-                       records.get("sample_every", 1), records.get("sample_moments"), records.get("sample_spectrum"),
-                       records.get("sample_derived", False), records.get("derived") is not None, in_list=type(graph) is list)
-        _check_tracers(graph[0] if type(graph) is list else graph, int(self.num_fields), records.get("tracers"),
-                       records.get("tracer_every", 1), in_list=type(graph) is list)
-        _check_forces(graph[0] if type(graph) is list else graph, int(self.num_fields), n_out, records.get("forces"),
-                      records.get("force_moments"), records.get("force_spectrum"), records.get("wall_moments"),
-                      records.get("target_forces", False), evaluate, in_list=type(graph) is list)
+        specs = _check_parts(records, graph, int(self.num_fields), n_out, evaluate)        # (argument errors before anything is collated or moved)
         self.eval()
         with torch.no_grad():
             if type(graph) is list:
@@ -430,7 +409,7 @@ class GNN(nn.Module):
                 records["target"] = graph.target
                 omega = getattr(graph, "omega", None)
                 records["mask"] = (omega[:, 0] == 1) if torch.is_tensor(omega) else None
-            return Rollout(self, graph, n_out, capture=capture, label=label, **records)
+            return Rollout._checked(specs, self, graph, n_out, capture, label, **records)
 
     def invalidate_packed(self) -> None:
         """Declare every packed weight image stale (they are rebuilt on the next launch).  The images are keyed on the parameters'
@@ -525,9 +504,6 @@ def _range_checked_forward(f):
     return forward
 
 
-REORDER_MIN_NODES = 50_000      # below, the gathered rows stay in L2 whatever the numbering
-
-
 F16_INPUT_WARN = 4096.0
 
 
@@ -547,1255 +523,3 @@ def _warn_f16_range(graph: Graph) -> None:
                       "gfd.set_mlp_precision('bf16x6') runs un-normalised data in the full fp32 range straight away.",
                       RuntimeWarning)
 
-
-class Rollout:
-    """Device-resident autoregressive rollout state for one (model, Graph) pair (GNN.solve,
-    nn/model.py:303-321).
-
-    `step()` = one forward + one `g4c_rollout_advance` (writes outputs[:, nf*t:nf*(t+1)], shifts the
-    history window, bumps the device-side step counter).  The first step runs eagerly and builds all
-    static plans / packed weights; with `capture=True` the second step is captured into a hipGraph and
-    every later step is a replay: no host synchronisation, no per-kernel launch cost.
-    The caller's `graph.field` is swapped for a private working copy and restored on close()."""
-
-    def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
-                 label: str = "Rollout", every: int = 1, probes: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
-                 mask: Optional[torch.Tensor] = None, moments=None, error_moments=None, derived=None, derived_every: int = 0,
-                 derived_moments=None, derived_options: Optional[dict] = None, spectrum: Optional["Spectrum"] = None,
-                 target_spectrum: bool = False, derived_spectrum: Optional["Spectrum"] = None, samples=None, sample_every: int = 1,
-                 sample_moments=None, sample_spectrum: Optional["Spectrum"] = None, sample_derived: bool = False, tracers=None,
-                 tracer_every: int = 1, forces=None, force_moments=None, force_spectrum: Optional["Spectrum"] = None, wall_moments=None,
-                 target_forces: bool = False):
-        """`reorder` (default: meshes of >= REORDER_MIN_NODES nodes, unless G4C_REORDER=0): run on a copy of the Graph whose level-1
-        nodes are numbered along a Morton curve (reorder.py: the senders an edge tile gathers are then rows its neighbours
-        just touched) and map the output rows back in `result()`; Graph layouts the renumbering does not know run as they are.
-
-        Records (all opt-in; with none of them the step ends in `g4c_rollout_advance` and every prediction is kept, as `solve`
-        does; with any, it ends in `g4c_rollout_advance_record`, which writes them inside the step, captured or not):
-        `every` = k: keep steps k - 1, 2k - 1, ... (0-based) only — `result()` is [N, nf * (max_steps // k)] and the buffer has
-        max_steps // k slots; 0 keeps none (`result()` raises).  `probes`: 1-D integer tensor of node rows (repeats allowed) —
-        `probes()` is their predictions at every step, [P, nf * max_steps].  `target` [N, >= nf * max_steps] (and `mask` [N] bool:
-        the Dirichlet nodes): `errors()` is the error of every step against it (`RolloutErrors`).  Rows are the caller's numbering.
-
-        Time statistics at every node (opt-in, and no record in the sense above: the step keeps the closing launch it would have
-        had, one `g4c_rollout_moments` launch per statistic goes in front of it): `moments` — of the prediction — and
-        `error_moments` — of prediction − target, needs `target=` — are each None, True (every step), `start` (steps start,
-        start + 1, ...) or `(start, stride)` (steps start, start + stride, ...; 0-based).  `moments()` / `error_moments()` return
-        them (`RolloutMoments`); after `rewind()` or a recomputation they hold the steps taken since.
-
-        Flow diagnostics (opt-in, no record either): `derived` — a tuple of names, 'div' (divergence of the velocity), 'vort'
-        (vorticity: one column in 2-D, three in 3-D), 'grad:<f>' (dim columns), at most 8 columns — are formed from every prediction
-        by the mesh's least-squares gradient (`gfd.MeshGradient`, built here on the rollout's own numbering): one `g4c_mesh_derived`
-        launch and its statistics launch after the forward, in front of the moments and the closing launch.  `derived()` returns
-        them (`RolloutDerived`): rms / mean_abs / max_abs over the nodes per step; with `derived_every` = k > 0 the columns of steps
-        k - 1, 2k - 1, ...; with `derived_moments` (the forms `moments` takes) their per-node time statistics, by the same
-        `g4c_rollout_moments`.  `derived_options`: power (0, 1, 2; default 2), edge_vectors ([E, dim], caller's edge order: the
-        wrapped, unscaled `edge_attr` of a periodic mesh), velocity (the fields of the velocity components, default 0 .. dim - 1),
-        field_scale ([nf], multiplied into the coefficients).  Steps run again after `rewind()` or a recomputation overwrite
-        their slots.
-
-        Fourier modes at every node (opt-in, no record either): `spectrum` — a `gfd.Spectrum`: K frequencies, a lattice of samples
-        start, start + stride, ..., a taper — accumulates the discrete Fourier transform of the prediction at those frequencies, one
-        `g4c_rollout_spectrum` launch per step after the moments, in front of the closing launch; `target_spectrum=True` (needs
-        `target=` and `spectrum=`) the same of the target's columns, by the same table; `derived_spectrum` (a `gfd.Spectrum`, needs
-        `derived=`) of the derived columns.  `spectrum()` / `target_spectrum()` / `derived_spectrum()` return them
-        (`RolloutSpectrum`); after `rewind()` or a recomputation they hold the steps taken since.
-
-        Values off the nodes (opt-in, no record either): `samples` — a `gfd.PointSampler` built on this graph, or points [P, dim] (a
-        sampler with its defaults is built here) — interpolates every prediction to the points: one `g4c_sample_points` launch after
-        the forward and the derived columns, in front of the node moments and spectra and of the closing launch; with
-        `sample_derived=True` (needs `derived=`) one more on the derived columns.  `sample_every` = k keeps the samples of steps
-        k - 1, 2k - 1, ... (0 keeps no series); `sample_moments` (the forms `moments` takes) and `sample_spectrum` (a `gfd.Spectrum`)
-        accumulate the time statistics and Fourier modes of the sampled prediction at every point, by the kernels the nodes use.
-        `samples()` returns them (`RolloutSamples`), the points in the caller's order; after `rewind()` or a recomputation the
-        accumulators hold the steps taken since and the slots of the steps run again are overwritten.  The neighbour search is not
-        periodic (`gfd.PointSampler`), and a list of graphs — they overlap in space — is refused.
-
-        Lagrangian tracers (opt-in, no record either): `tracers` — a `gfd.Tracers` built on this graph, or a tuple (seeds [S, dim], dt)
-        (tracers with their defaults are built here) — moves a copy of the particles through every step: one `g4c_tracer_advance`
-        launch after the forward, in front of the closing launch (it reads the field window — time level t — and the prediction —
-        level t + 1 — before the window is shifted); the velocity must be among the model's fields.  `tracer_every` = k keeps the
-        positions after steps k - 1, 2k - 1, ... (0 keeps no series).  `tracers()` returns them (`RolloutTracers`), the particles in
-        the caller's order.  `rewind()` continues from the current positions (release steps then count from the rewound step index); a
-        recomputation starts again from the positions of the last `rewind()` (the seeds, without one).  A list of graphs is refused.
-
-        Body forces (opt-in, no record either): `forces` — a `gfd.BodyForces` built on this graph — forms the pressure and viscous
-        force and moment on every body from every prediction: one `g4c_body_forces` launch (one workgroup per body) after the forward,
-        the derived columns and the samples, in front of the node moments and spectra and of the closing launch.  `force_moments` and
-        `wall_moments` (the forms `moments` takes) accumulate the time statistics of the total (F_x, F_y, M) of every body and of
-        (pressure, wall shear) at every wall item, `force_spectrum` (a `gfd.Spectrum`) the Fourier modes of the total — the lift's
-        dominant frequency is the shedding frequency —, by the kernels the nodes use.  `target_forces=True` (needs `target=`) adds one
-        more launch per step on the target's columns.  `forces()` returns them (`RolloutForces`); steps run again after `rewind()` or
-        a recomputation overwrite their rows, the accumulators hold the steps taken since.  A list of graphs is refused."""
-        derived_spec = _check_derived(graph, int(model.num_fields), int(max_steps), derived, derived_every, derived_moments, derived_options,
-                                      spectrum=derived_spectrum)
-        spectrum_spec = _check_spectrum("spectrum", spectrum, int(model.num_fields), int(max_steps))
-        if not isinstance(target_spectrum, bool):
-            raise TypeError(f"target_spectrum: expected a bool, got {target_spectrum!r}")
-        if target_spectrum and (target is None or spectrum_spec is None):
-            raise ValueError("target_spectrum: the spectrum of the target needs target= and spectrum= (it uses the same table)")
-        samples_spec = _check_samples(graph, int(model.num_fields), int(max_steps), samples, sample_every, sample_moments, sample_spectrum,
-                                      sample_derived, derived_spec is not None)
-        tracer_spec = _check_tracers(graph, int(model.num_fields), tracers, tracer_every)
-        forces_spec = _check_forces(graph, int(model.num_fields), int(max_steps), forces, force_moments, force_spectrum, wall_moments,
-                                    target_forces, target is not None)
-        window = _check_moments("moments", moments, int(model.num_fields), int(max_steps))
-        error_window = _check_moments("error_moments", error_moments, int(model.num_fields), int(max_steps))
-        if error_window is not None and target is None:
-            raise ValueError("error_moments: the statistics of prediction - target need target=")
-        _lib.require_hip(graph.field)
-        recording = _check_records(graph, int(model.num_fields), int(max_steps), every, probes, target, mask)
-        self._caller_graph, self._perm = graph, None
-        if reorder is None:
-            reorder = graph.num_nodes >= REORDER_MIN_NODES and os.environ.get("G4C_REORDER", "1") != "0"
-        if reorder:
-            from ..reorder import reorder_nodes
-            re = reorder_nodes(graph)
-            if re is not None:
-                graph, self._perm = re
-        self.model, self.graph, self.capture = model, graph, capture
-        self.nf = int(model.num_fields)
-        self.max_steps = int(max_steps)
-        dev = graph.field.device
-        self._orig_field = graph.field
-        self.field = graph.field.to(torch.float32).clone(memory_format=torch.contiguous_format)
-        # step-major [steps, N, nf]: a step's predictions are one contiguous block (`outputs` gives the reference's [N, nf * steps])
-        self._out_steps = None if recording else torch.zeros((self.max_steps, graph.num_nodes, self.nf), dtype=torch.float32, device=dev)
-        self._rec = _Records(self, int(every), probes, target, mask) if recording else None     # (its snapshots are `_out_steps`)
-        self.step_counter = torch.zeros(2, dtype=torch.int32, device=dev)          # [step index, g4c_rollout_advance's ticket]
-        self.steps_done = 0
-        self._hipgraph, self._epoch, self._pins = None, -1, None
-        graph.field = self.field
-        # per-mesh constants (the encoders of edge_attr / angle_attr*): computed by the first eager step, read by every later one
-        self.static = ops.StaticCache()
-        # fp16 range flags of this rollout's own launches: every step (eager, captured, recomputed) runs in their scope
-        self.label = label
-        self.flags = ops.RangeFlags(dev)
-        # The default "f16x3" arithmetic is run OPTIMISTICALLY: its kernels flag every value that reached the end of the fp16 range
-        # (|x| >= 65504, clipped there), `result()` reads the flags, and a rollout that clipped anywhere is recomputed from the
-        # window it started from in "bf16x6" (fp32's exponent range; the reference's `solve` runs in fp32, nn/model.py:303-321) and
-        # stays in that arithmetic — so what `result()` hands out never contains a clipped value.
-        self._field0 = self.field.clone()        # the input window of slot `_first_slot`
-        self._first_slot = 0
-        self.exact_range = False                 # True once a clip made this rollout fall back to "bf16x6"
-        self._moments = None if window is None else _Moments(self, *window)
-        self._error_moments = None if error_window is None else _Moments(self, *error_window, sub=self._rec.target)
-        self._derived = None if derived_spec is None else _Derived(self, *derived_spec)
-        self._spectrum = None if spectrum_spec is None else _Spectrum(self, spectrum_spec)
-        self._target_spectrum = _Spectrum(self, spectrum_spec, x=self._rec.target, x_step=self.nf) if target_spectrum else None
-        self._samples = None if samples_spec is None else _Samples(self, **samples_spec)
-        self._tracers = None if tracer_spec is None else _Tracers(self, *tracer_spec)
-        self._forces = None if forces_spec is None else _Forces(self, **forces_spec)
-
-    @property
-    def outputs(self) -> torch.Tensor:
-        """[N, nf * max_steps] in the rollout's node numbering, as `GNN.solve` lays its result out (nn/model.py:322-326) — a fresh
-        transposed copy of the step-major buffer on every access (no validation: `result()` is the delivered form)."""
-        if self._out_steps is None:
-            raise RuntimeError(f"{self.label}: every=0 keeps no snapshot of the predictions (probes() and errors() hold the records)")
-        return ops.steps_to_columns(self._out_steps)
-
-    def _one(self):
-        with self.static, self.flags:
-            pred = self.model.forward(self.graph, self.steps_done)
-        if self._derived is not None:                         # (all of these read the step index the closing launch below bumps)
-            self._derived.launch(pred, self.step_counter)
-        if self._samples is not None:
-            self._samples.launch(pred, self.step_counter, self._derived)
-        if self._forces is not None:
-            self._forces.launch(pred, self.step_counter)
-        for mo in (self._moments, self._error_moments):
-            if mo is not None:
-                mo.accumulate(pred, self.step_counter)
-        for sp in self._spectra():
-            sp.accumulate(pred, self.step_counter)
-        if self._tracers is not None:                         # (reads the window of level t before the closing launch shifts it)
-            self._tracers.launch(self.field, pred, self.step_counter)
-        if self._rec is not None:
-            self._rec.advance(self.field, pred, self.step_counter)
-            return
-        ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
-
-    def step(self) -> None:
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"rollout buffer holds {self.max_steps} steps")
-        if self.exact_range and ops.mlp_precision() == "f16x3":
-            old = ops.set_mlp_precision("bf16x6")
-            try:
-                self._step()
-            finally:
-                ops.set_mlp_precision(old)
-        else:
-            self._step()
-
-    def _step(self) -> None:
-        with torch.no_grad():
-            if self._epoch != -1 and ops.weights_epoch() != self._epoch:
-                # the weights changed since the last eager step (captured or not yet): the packed images are stale, and repacking
-                # (allocations + pack launches) must not happen inside a capture — one eager step first
-                self._hipgraph, self._epoch = None, -1
-            elif self.static.stale():
-                # a per-mesh constant (edge_attr / angle_attr*) was edited in place, or the arithmetic changed: a captured step
-                # contains neither the encoder launches nor a look-up of their cached results, and a step ABOUT to be captured
-                # (ADVICE r05) would bake the recomputation — and, after a precision change, the repacking — into every replay:
-                # one eager step recomputes them, then the step is captured (again)
-                self._hipgraph, self._epoch = None, -1
-            if self.steps_done == 0 or not self.capture or self._epoch == -1:
-                self._one()                               # eager: builds the plans and the packed weight images
-                self._epoch = ops.weights_epoch()
-            elif self._hipgraph is None:
-                torch.cuda.synchronize(self.field.device)
-                self._pins = plan.snapshot()              # the graph bakes these pointers in: keep them past cache eviction
-                self._hipgraph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._hipgraph):   # records only; nothing executes during capture
-                    self._one()
-                self._hipgraph.replay()
-            else:
-                self._hipgraph.replay()
-        self.steps_done += 1
-
-    def run(self, n: int) -> None:
-        for _ in range(n):
-            self.step()
-
-    def rewind(self) -> None:
-        """Restart writing at step 0 (benchmarks: keeps the captured hipGraph and the current field).  Validates first: the
-        field a later recomputation restarts from must not come from steps that clipped."""
-        self.validate()
-        self.step_counter.zero_()
-        self.steps_done = 1 if self.steps_done > 0 else 0
-        if self.steps_done:   # slot 0 is kept so that replays continue from slot 1
-            self.step_counter[:1].fill_(1)
-        self._field0.copy_(self.field)            # (a recomputation restarts here)
-        self._first_slot = self.steps_done
-        self._reset_moments()
-        if self._tracers is not None:
-            self._tracers.state.save()
-
-    def _recompute_exact(self, hit) -> None:
-        """Steps `_first_slot .. steps_done` again from the saved input window in "bf16x6"; the rollout stays in that arithmetic."""
-        n = self.steps_done - self._first_slot
-        warnings.warn(f"{self.label}: the default 'f16x3' MLP arithmetic reached the end of the fp16 range (|x| >= 65504) in "
-                      f"{', '.join(hit[:8])}{' ...' if len(hit) > 8 else ''}: the {n} step(s) were recomputed in 'bf16x6' (fp32's exponent "
-                      "range) and this rollout continues in it — the result holds no clipped value.  gfd.set_mlp_precision('bf16x6') "
-                      "avoids the second pass for this model.", RuntimeWarning, stacklevel=3)
-        self.exact_range = True
-        self.field.copy_(self._field0)
-        self.step_counter.zero_()
-        if self._first_slot:
-            self.step_counter[:1].fill_(self._first_slot)
-        self._hipgraph, self._epoch = None, -1
-        self.steps_done = self._first_slot
-        self._reset_moments()
-        if self._tracers is not None:
-            self._tracers.state.restore()
-        field, self.graph.field = self.graph.field, self.field        # (after close() the graph holds its own field again)
-        try:
-            self.run(n)
-        finally:
-            self.graph.field = field
-
-    def validate(self) -> bool:
-        """Default "f16x3" arithmetic: read the range flags of this rollout's launches (its own buffer, one synchronisation) and, if
-        a value was clipped at the end of the fp16 range, recompute the steps in "bf16x6" (RuntimeWarning naming the MLPs).  Returns
-        True when that happened.  `result()` calls it, before or after close(); a benchmark calls it inside its timed region."""
-        if ops.mlp_precision() == "f16x3" and not self.exact_range:
-            hit = self.flags.take()
-            if hit:
-                self._recompute_exact(hit)
-                return True
-        return False
-
-    def result(self) -> torch.Tensor:
-        """`outputs` with its rows in the caller's node numbering — validated first (`validate()`): the tensor returned never
-        contains a value the default arithmetic clipped."""
-        self.validate()
-        cols = self.outputs
-        if self._perm is None:
-            return cols
-        out = torch.empty_like(cols)
-        out[self._perm] = cols
-        return out
-
-    def probes(self) -> torch.Tensor:
-        """[P, nf * max_steps]: the predictions at the `probes=` rows, in the order given, step after step (columns of steps not yet
-        taken are zero) — validated first, like `result()`."""
-        if self._rec is None or self._rec.probe_out is None:
-            raise RuntimeError(f"{self.label}: no probes= were given")
-        self.validate()
-        return ops.steps_to_columns(self._rec.probe_out)
-
-    def errors(self) -> "RolloutErrors":
-        """The error of the `steps_done` steps taken against `target=` (`RolloutErrors`, fp64 host tensors) — validated first, like
-        `result()`; one device -> host copy of [steps_done, nf, 6] sums."""
-        if self._rec is None or self._rec.stats is None:
-            raise RuntimeError(f"{self.label}: no target= was given")
-        self.validate()
-        rec = self._rec
-        return RolloutErrors(rec.stats[:self.steps_done].cpu(), int(self.graph.num_nodes), rec.n_masked,
-                             snapshots=self.result() if self._out_steps is not None else None,
-                             probes=ops.steps_to_columns(rec.probe_out) if rec.probe_out is not None else None)
-
-    def _reset_moments(self) -> None:
-        for mo in (self._moments, self._error_moments, self._derived.moments if self._derived is not None else None,
-                   self._samples.moments if self._samples is not None else None) + (self._forces.accumulators() if self._forces is not None else ()):
-            if mo is not None:
-                mo.reset(self._first_slot)
-        for sp in self._spectra() + ([self._samples.spectrum] if self._samples is not None and self._samples.spectrum is not None else []):
-            sp.reset(self._first_slot)
-
-    def _spectra(self):
-        return [sp for sp in (self._spectrum, self._target_spectrum, self._derived.spectrum if self._derived is not None else None)
-                if sp is not None]
-
-    def _read_moments(self, mo: Optional["_Moments"], name: str) -> "RolloutMoments":
-        if mo is None:
-            raise RuntimeError(f"{self.label}: no {name}= were asked for")
-        self.validate()
-        return mo.read(self._perm)
-
-    def moments(self) -> "RolloutMoments":
-        """The time statistics of the prediction at every node over the window `moments=` asked for (`RolloutMoments`, fp64 device
-        tensors in the caller's rows) — validated first, like `result()`; one device -> host copy of two integers."""
-        return self._read_moments(self._moments, "moments")
-
-    def error_moments(self) -> "RolloutMoments":
-        """The same of prediction − target over the window `error_moments=` asked for: `mean` is the bias field, `mean² + var` the
-        mean-square error at every node."""
-        return self._read_moments(self._error_moments, "error_moments")
-
-    def _read_spectrum(self, sp: Optional["_Spectrum"], name: str) -> "RolloutSpectrum":
-        if sp is None:
-            raise RuntimeError(f"{self.label}: no {name}= was asked for")
-        self.validate()
-        return sp.read(self._perm)
-
-    def spectrum(self) -> "RolloutSpectrum":
-        """The Fourier modes of the prediction at every node at the frequencies `spectrum=` asked for (`RolloutSpectrum`, fp64 device
-        tensors in the caller's rows) — validated first, like `result()`; one device -> host copy of two integers."""
-        return self._read_spectrum(self._spectrum, "spectrum")
-
-    def target_spectrum(self) -> "RolloutSpectrum":
-        """The same of the target's columns of the steps taken, by the same table (`target_spectrum=True`)."""
-        return self._read_spectrum(self._target_spectrum, "target_spectrum")
-
-    def derived_spectrum(self) -> "RolloutSpectrum":
-        """The same of the derived columns (`derived_spectrum=`): its fields are `derived().columns`."""
-        return self._read_spectrum(self._derived.spectrum if self._derived is not None else None, "derived_spectrum")
-
-    def derived(self) -> "RolloutDerived":
-        """The flow diagnostics `derived=` asked for, of the `steps_done` steps taken (`RolloutDerived`) — validated first, like
-        `result()`; one device -> host copy of [steps_done, nd, 3] sums."""
-        if self._derived is None:
-            raise RuntimeError(f"{self.label}: no derived= were asked for")
-        self.validate()
-        return self._derived.read(self._perm, self.steps_done)
-
-    def samples(self) -> "RolloutSamples":
-        """What `samples=` asked for, of the steps taken (`RolloutSamples`: the series at the points, their time statistics and
-        Fourier modes, the sampled derived columns) — validated first, like `result()`."""
-        if self._samples is None:
-            raise RuntimeError(f"{self.label}: no samples= were asked for")
-        self.validate()
-        return self._samples.read()
-
-    def tracers(self) -> "RolloutTracers":
-        """What `tracers=` asked for, after the steps taken (`RolloutTracers`: the paths, the last positions, status, stopped) —
-        validated first, like `result()`."""
-        if self._tracers is None:
-            raise RuntimeError(f"{self.label}: no tracers= were asked for")
-        self.validate()
-        return self._tracers.read()
-
-    def forces(self) -> "RolloutForces":
-        """What `forces=` asked for, of the `steps_done` steps taken (`RolloutForces`: the pressure and viscous force and moment on
-        every body per step, their time statistics and Fourier modes, the wall's statistics) — validated first, like `result()`; one
-        device -> host copy of [steps_done, B, 6] sums."""
-        if self._forces is None:
-            raise RuntimeError(f"{self.label}: no forces= were asked for")
-        self.validate()
-        return self._forces.read(self.steps_done)
-
-    def modes(self, spec) -> "SnapshotModes":
-        """The modal analysis `spec` (a `gfd.Modes`) asks for of the snapshots kept so far (`SnapshotModes`; mean and modes in the
-        caller's rows) — validated first, like `result()`.  It reads the step-major buffer `result()` is a transposed copy of, and of it
-        only the slots of steps taken; start / stride / count of `spec` are in kept slots.  Nothing is allocated or launched for it
-        before this call."""
-        from ..modes import Modes
-        if not isinstance(spec, Modes):
-            raise TypeError(f"modes: expected a gfd.Modes, got {type(spec).__name__}")
-        if self._out_steps is None:
-            raise RuntimeError(f"{self.label}: every=0 keeps no snapshot of the predictions to form modes of")
-        self.validate()
-        every = self._rec.every if self._rec is not None else 1
-        return spec._fit_steps(self._out_steps, self.steps_done // every, self._perm)
-
-    def close(self) -> None:
-        self.graph.field = self._orig_field
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-
-def _check_records(graph: Graph, nf: int, max_steps: int, every, probes, target, mask) -> bool:
-    """The record arguments of `Rollout` against the caller's graph, on the tensors as they were passed (probe rows are read on the
-    host copy the caller holds: nothing is uploaded first).  Returns whether any record was asked for."""
-    n = int(graph.num_nodes)
-    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
-        raise ValueError(f"every: expected an integer >= 0 (0: no snapshots, k: every k-th step), got {every!r}")
-    if probes is not None:
-        if not torch.is_tensor(probes) or probes.dtype.is_floating_point or probes.dtype == torch.bool or probes.is_complex():
-            raise TypeError(f"probes: expected a 1-D integer tensor of node rows, got {getattr(probes, 'dtype', type(probes).__name__)}")
-        if probes.dim() != 1:
-            raise ValueError(f"probes: expected a 1-D integer tensor of node rows, got shape {tuple(probes.shape)}")
-        if probes.numel() and (int(probes.min()) < 0 or int(probes.max()) >= n):
-            raise ValueError(f"probes: rows {int(probes.min())} .. {int(probes.max())} of a graph of {n} nodes")
-    if target is not None:
-        if not torch.is_tensor(target) or not target.dtype.is_floating_point:
-            raise TypeError(f"target: expected a floating-point tensor, got {getattr(target, 'dtype', type(target).__name__)}")
-        if target.dim() != 2 or int(target.size(0)) != n or int(target.size(1)) < nf * max_steps:
-            raise ValueError(f"target: expected [{n}, >= nf * max_steps = {nf * max_steps}], got {tuple(target.shape)}")
-        if nf > _lib.REC_MAX_NF:
-            raise NotImplementedError(f"target: the error statistics cover models of up to {_lib.REC_MAX_NF} fields, this one has {nf}")
-    if mask is not None:
-        if target is None:
-            raise ValueError("mask: given without a target")
-        if not torch.is_tensor(mask) or mask.dtype != torch.bool:
-            raise TypeError(f"mask: expected a bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
-        if tuple(mask.shape) != (n,):
-            raise ValueError(f"mask: expected shape ({n},), got {tuple(mask.shape)}")
-    return every != 1 or probes is not None or target is not None
-
-
-def _check_moments(name: str, spec, nf: int, max_steps: int):
-    """A `moments=` / `error_moments=` argument of `Rollout` -> (start, stride), or None when the statistic is not asked for."""
-    def integer(v):
-        return isinstance(v, int) and not isinstance(v, bool)
-
-    if spec is None or spec is False:
-        return None
-    if spec is True:
-        start, stride = 0, 1
-    elif integer(spec):
-        start, stride = spec, 1
-    elif isinstance(spec, (tuple, list)) and len(spec) == 2 and all(integer(v) for v in spec):
-        start, stride = spec
-    else:
-        raise TypeError(f"{name}: expected None, True, an integer start or a pair of integers (start, stride), got {spec!r}")
-    if start < 0 or start >= max_steps:
-        raise ValueError(f"{name}: start {start} of a rollout of {max_steps} steps (0 <= start < max_steps)")
-    if stride < 1:
-        raise ValueError(f"{name}: stride {stride} (>= 1)")
-    if nf > _lib.REC_MAX_NF:
-        raise NotImplementedError(f"{name}: the time statistics cover models of up to {_lib.REC_MAX_NF} fields, this one has {nf}")
-    return int(start), int(stride)
-
-
-def _lattice_origin(start: int, stride: int, first_slot: int) -> int:
-    """The first step of the lattice start, start + stride, ... at or after `first_slot`."""
-    behind = max(first_slot - start, 0)
-    return start + -(-behind // stride) * stride
-
-
-class _Moments:
-    """The accumulators of one per-node time statistic of a `Rollout` and the launch that updates them.  Allocated once, in the
-    rollout's node numbering: one fp64 buffer of 4 nf + nf (nf + 1) / 2 planes of N (pivot, sum, sum2, min, max) and the device-side
-    window {origin, last}.  The captured launch reads the origin on the device, so `reset()` — a two-integer fill on the stream,
-    outside the graph — is all `rewind()` and a recomputation need: the step that finds itself at the origin stores the
-    accumulators without reading them."""
-
-    def __init__(self, ro: "Rollout", start: int, stride: int, sub: Optional[torch.Tensor] = None, nf: Optional[int] = None,
-                 rows: Optional[int] = None):
-        dev, nf = ro.field.device, ro.nf if nf is None else int(nf)        # (nf: the derived columns)
-        n = int(ro.graph.num_nodes) if rows is None else int(rows)         # (rows: the sample points)
-        self.nf, self.max_steps, self.start, self.stride, self.sub = nf, ro.max_steps, start, stride, sub
-        pairs = ops.moment_pairs(nf)
-        self.planes = torch.zeros((4 * nf + pairs, n), dtype=torch.float64, device=dev)
-        self.pivot, self.sum, self.sum2, self.lo, self.hi = self.planes.split((nf, nf, pairs, nf, nf))
-        self.window = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.reset(ro._first_slot)
-
-    def reset(self, first_slot: int) -> None:
-        """origin = the first step of the lattice start, start + stride, ... at or after `first_slot`; nothing accumulated yet."""
-        self.origin = _lattice_origin(self.start, self.stride, first_slot)
-        self.window[:1].fill_(self.origin)
-        self.window[1:].fill_(-1)
-
-    def accumulate(self, pred, step) -> None:
-        ops.rollout_moments(pred, step, self.nf, self.max_steps, self.window, self.pivot, self.sum, self.sum2, self.lo, self.hi,
-                            stride=self.stride, sub=self.sub)
-
-    def read(self, perm) -> "RolloutMoments":
-        origin, last = self.window.tolist()
-        count = (last - origin) // self.stride + 1 if last >= origin else 0
-
-        def rows(planes):                       # [planes, N] in the rollout's numbering -> [N, planes] in the caller's
-            cols = planes.t().contiguous()
-            if perm is None:
-                return cols
-            out = torch.empty_like(cols)
-            out[perm] = cols
-            return out
-
-        return RolloutMoments(count, origin, self.stride, rows(self.pivot), rows(self.sum), rows(self.sum2), rows(self.lo), rows(self.hi))
-
-
-class RolloutMoments:
-    """Per-node time statistics of a rollout (`Rollout.moments()` / `error_moments()`, `GNN.time_statistics()`, `GNN.evaluate(moments=)`)
-    over the `count` steps origin, origin + stride, ...: the raw fp64 sums, as the device accumulated them — `pivot` [N, nf] (the
-    first sample), `sum` [N, nf] = Σ d, `sum2` [N, nf (nf + 1) / 2] = Σ d_f d_g over the pairs (0,0), (0,1), ..., (0,nf-1), (1,1), ...,
-    with d = sample − pivot, and `min`, `max` [N, nf] of the samples — and, from them, `mean` = pivot + Σd / count, `cov`
-    [N, nf, nf] = Σ d_f d_g / count − (Σd_f / count)(Σd_g / count) (symmetric, population-normalised; the shift by the first sample
-    keeps it well-conditioned when the mean is far larger than the fluctuation), `var` = its diagonal, `std` = √max(var, 0).
-    `count == 0` (no step of the window was taken) raises on the derived quantities.  Works on tensors of any device.
-    `snapshots`: the rollout's `result()` when `GNN.time_statistics(every=)` kept any, else None."""
-
-    def __init__(self, count: int, origin: int, stride: int, pivot: torch.Tensor, sum: torch.Tensor, sum2: torch.Tensor,
-                 min: torch.Tensor, max: torch.Tensor, snapshots: Optional[torch.Tensor] = None):
-        nf = int(pivot.size(-1))
-        pairs = nf * (nf + 1) // 2
-        for t, name, width in ((pivot, "pivot", nf), (sum, "sum", nf), (sum2, "sum2", pairs), (min, "min", nf), (max, "max", nf)):
-            if t.dim() != 2 or tuple(t.shape) != (int(pivot.size(0)), width):
-                raise ValueError(f"{name}: expected shape ({int(pivot.size(0))}, {width}), got {tuple(t.shape)}")
-        self.count, self.origin, self.stride = int(count), int(origin), int(stride)
-        self.pivot, self.sum, self.sum2, self.min, self.max, self.snapshots = pivot, sum, sum2, min, max, snapshots
-
-    @property
-    def fields(self) -> int:
-        return int(self.pivot.size(1))
-
-    def _n(self) -> float:
-        if self.count <= 0:
-            raise RuntimeError("RolloutMoments: no step of the window was accumulated (count == 0)")
-        return float(self.count)
-
-    @property
-    def mean(self) -> torch.Tensor:
-        return self.pivot + self.sum / self._n()
-
-    @property
-    def cov(self) -> torch.Tensor:
-        n, nf = self._n(), self.fields
-        s = self.sum / n
-        f, g = torch.triu_indices(nf, nf, device=self.sum2.device)        # row-major upper triangle: the pair order of sum2
-        c = self.sum2 / n - s[:, f] * s[:, g]
-        out = torch.empty((int(s.size(0)), nf, nf), dtype=c.dtype, device=c.device)
-        out[:, f, g] = c
-        out[:, g, f] = c
-        return out
-
-    @property
-    def var(self) -> torch.Tensor:
-        return torch.diagonal(self.cov, dim1=1, dim2=2)
-
-    @property
-    def std(self) -> torch.Tensor:
-        return self.var.clamp_min(0.0).sqrt()
-
-    def __repr__(self):
-        return (f"RolloutMoments(count={self.count}, origin={self.origin}, stride={self.stride}, fields={self.fields}, "
-                f"nodes={int(self.pivot.size(0))})")
-
-
-class Spectrum:
-    """A request for the Fourier modes of a rollout at every node (`Rollout(spectrum=)`, `GNN.evaluate(spectrum=)`; `GNN.spectrum`
-    builds one): the discrete Fourier transform at K chosen frequencies — `bins` (integers 0 <= b <= samples // 2: the frequencies
-    b / (samples stride dt), the exact bins of the window) or `freqs` (cycles per unit of time, at most the Nyquist frequency
-    0.5 / (stride dt)), exactly one of them — over the `samples` steps start, start + stride, ... (0-based; default: all of them up to
-    the rollout's end), `dt` the time of one step, `taper` "rect" or "hann".  Checked when the rollout is built."""
-
-    def __init__(self, bins=None, freqs=None, *, start: int = 0, stride: int = 1, samples: Optional[int] = None, dt: float = 1.0,
-                 taper: str = "rect"):
-        self.bins, self.freqs, self.start, self.stride, self.samples, self.dt, self.taper = bins, freqs, start, stride, samples, dt, taper
-
-    def __repr__(self):
-        which = f"bins={self.bins!r}" if self.bins is not None else f"freqs={self.freqs!r}"
-        return f"Spectrum({which}, start={self.start}, stride={self.stride}, samples={self.samples}, dt={self.dt}, taper={self.taper!r})"
-
-
-def _check_spectrum(name: str, spec, nf: int, max_steps: int):
-    """A `spectrum=` / `derived_spectrum=` argument of `Rollout` -> the window and the host table (a dict: start, stride, samples, dt,
-    taper, tw, w, freqs), or None when no spectrum is asked for.  Nothing is moved or allocated on a device."""
-    def integer(v):
-        return isinstance(v, int) and not isinstance(v, bool)
-
-    if spec is None:
-        return None
-    if not isinstance(spec, Spectrum):
-        raise TypeError(f"{name}: expected a gfd.Spectrum or None, got {spec!r}")
-    if not integer(spec.start) or not integer(spec.stride) or not (spec.samples is None or integer(spec.samples)):
-        raise TypeError(f"{name}: start, stride and samples are integers (samples may be None), got {spec!r}")
-    if isinstance(spec.dt, bool) or not isinstance(spec.dt, (int, float)):
-        raise TypeError(f"{name}: dt: expected a number, got {spec.dt!r}")
-    if not isinstance(spec.taper, str):
-        raise TypeError(f"{name}: taper: expected 'rect' or 'hann', got {spec.taper!r}")
-    if spec.start < 0 or spec.start >= max_steps:
-        raise ValueError(f"{name}: start {spec.start} of a rollout of {max_steps} steps (0 <= start < max_steps)")
-    if spec.stride < 1:
-        raise ValueError(f"{name}: stride {spec.stride} (>= 1)")
-    lattice = len(range(spec.start, max_steps, spec.stride))
-    samples = lattice if spec.samples is None else spec.samples
-    if samples < 1 or samples > lattice:
-        raise ValueError(f"{name}: samples {samples} of the {lattice} steps {spec.start}, {spec.start + spec.stride}, ... < {max_steps} (1 <= samples <= {lattice})")
-    try:
-        tw, w, freqs = ops.spectrum_table(bins=spec.bins, freqs=spec.freqs, samples=samples, stride=spec.stride, dt=spec.dt, taper=spec.taper)
-    except (TypeError, ValueError) as e:
-        raise type(e)(f"{name}: {e}") from None
-    if nf > _lib.REC_MAX_NF:
-        raise NotImplementedError(f"{name}: the spectra cover up to {_lib.REC_MAX_NF} fields, got {nf}")
-    if int(tw.size(1)) > _lib.SPECTRUM_MAX_BINS:
-        raise NotImplementedError(f"{name}: {int(tw.size(1))} frequencies (at most {_lib.SPECTRUM_MAX_BINS} per spectrum)")
-    return dict(start=int(spec.start), stride=int(spec.stride), samples=int(samples), dt=float(spec.dt), taper=spec.taper, tw=tw, w=w, freqs=freqs)
-
-
-class _Spectrum:
-    """The accumulators of one per-node spectrum of a `Rollout` and the launch that updates them.  Allocated once, in the rollout's
-    node numbering: one fp64 buffer of `ops.spectrum_planes(nf, K)` planes of N (pivot, sum, re, im), the twiddle table uploaded once,
-    and the device-side window {origin, last}.  As for `_Moments`, `reset()` — a two-integer fill — is all `rewind()` and a
-    recomputation need.  `x`: the tensor sampled instead of the prediction (the records' target with x_step = nf, or the derived
-    columns), in the rollout's numbering."""
-
-    def __init__(self, ro: "Rollout", spec: dict, x: Optional[torch.Tensor] = None, x_step: int = 0, nf: Optional[int] = None,
-                 rows: Optional[int] = None):
-        dev, nf = ro.field.device, ro.nf if nf is None else int(nf)
-        n = int(ro.graph.num_nodes) if rows is None else int(rows)         # (rows: the sample points)
-        self.nf, self.max_steps, self.spec, self.x, self.x_step = nf, ro.max_steps, spec, x, x_step
-        self.start, self.stride, self.K = spec["start"], spec["stride"], int(spec["tw"].size(1))
-        self.planes = torch.zeros((ops.spectrum_planes(nf, self.K), n), dtype=torch.float64, device=dev)
-        self.pivot, self.sum, self.re, self.im = self.planes.split((nf, nf, nf * self.K, nf * self.K))
-        self.tw = spec["tw"].to(dev)
-        self.window = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.reset(ro._first_slot)
-
-    def reset(self, first_slot: int) -> None:
-        self.origin = _lattice_origin(self.start, self.stride, first_slot)
-        self.window[:1].fill_(self.origin)
-        self.window[1:].fill_(-1)
-
-    def accumulate(self, pred, step) -> None:
-        ops.rollout_spectrum(pred if self.x is None else self.x, step, self.nf, self.max_steps, self.window, self.tw, self.pivot, self.sum,
-                             self.re, self.im, stride=self.stride, x_step=self.x_step)
-
-    def read(self, perm) -> "RolloutSpectrum":
-        origin, last = self.window.tolist()
-        count = (last - origin) // self.stride + 1 if last >= origin else 0
-
-        def rows(planes):                       # [planes, N] in the rollout's numbering -> [N, planes] in the caller's
-            cols = planes.t().contiguous()
-            if perm is None:
-                return cols
-            out = torch.empty_like(cols)
-            out[perm] = cols
-            return out
-
-        sp = self.spec
-        return RolloutSpectrum(count, origin, self.stride, sp["dt"], sp["taper"], sp["freqs"], sp["tw"], sp["w"], rows(self.pivot), rows(self.sum),
-                               rows(self.re).unflatten(1, (self.nf, self.K)), rows(self.im).unflatten(1, (self.nf, self.K)))
-
-
-class RolloutSpectrum:
-    """Per-node Fourier modes of a rollout (`Rollout.spectrum()` / `target_spectrum()` / `derived_spectrum()`, `GNN.spectrum()`,
-    `GNN.evaluate(spectrum=)`) at the K frequencies `freqs` (cycles per unit of time) over the `count` samples of the steps origin,
-    origin + stride, ... (`samples` make the window `complete`): the raw fp64 sums, as the device accumulated them — `pivot` [N, nf]
-    (the first sample), `sum` [N, nf] = Σ d, `re`, `im` [N, nf, K] = Σ_j d_j tw[j, k, 0 / 1] with d = sample − pivot — and the host table
-    they were formed with (`tw` [samples, K, 2] = (w_j cos θ_jk, −w_j sin θ_jk), `w` [samples]: the taper).  From them, `mean` =
-    pivot + Σd / count; `coeff` [N, nf, K] complex128 = ((re + i im) − (mean − pivot) W_k) / S with W_k = Σ_{j<count} tw[j, k] and S =
-    Σ_{j<count} w_j — the tapered Fourier transform of sample − mean, normalised so that A cos(ωt + φ) on a bin (t counted from the
-    origin) has coeff = (A / 2) e^{iφ}; `amplitude` = 2 |coeff|, `phase` = arg coeff, `power` = |coeff|²; `band_power(mask)` [nf, K]
-    their sum over the (masked) nodes; `dominant(field, mask)` the frequency of the largest band power (× D / U: the Strouhal
-    number).  `count == 0` raises on the derived quantities; a "hann" window that is not complete warns (its weights do not sum as
-    a Hann window's).  Works on tensors of any device.  `snapshots`: the rollout's `result()` when `GNN.spectrum(every=)` kept any;
-    `derived`: the spectrum of the derived columns when `GNN.spectrum(derived=)` asked for it; else None."""
-
-    def __init__(self, count: int, origin: int, stride: int, dt: float, taper: str, freqs: torch.Tensor, tw: torch.Tensor, w: torch.Tensor,
-                 pivot: torch.Tensor, sum: torch.Tensor, re: torch.Tensor, im: torch.Tensor, snapshots: Optional[torch.Tensor] = None):
-        if tw.dim() != 3 or int(tw.size(2)) != 2 or tuple(w.shape) != (int(tw.size(0)),) or tuple(freqs.shape) != (int(tw.size(1)),):
-            raise ValueError(f"tw: expected [samples, K, 2] with w [samples] and freqs [K], got {tuple(tw.shape)}, {tuple(w.shape)}, {tuple(freqs.shape)}")
-        n, nf, K = int(pivot.size(0)), int(pivot.size(-1)), int(tw.size(1))
-        for t, name, shape in ((pivot, "pivot", (n, nf)), (sum, "sum", (n, nf)), (re, "re", (n, nf, K)), (im, "im", (n, nf, K))):
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        self.count, self.samples, self.origin, self.stride, self.dt, self.taper = int(count), int(tw.size(0)), int(origin), int(stride), float(dt), taper
-        if not 0 <= self.count <= self.samples:
-            raise ValueError(f"count: {self.count} of a window of {self.samples} samples")
-        self.freqs, self.tw, self.w = freqs, tw, w
-        self.pivot, self.sum, self.re, self.im, self.snapshots, self.derived = pivot, sum, re, im, snapshots, None
-
-    @property
-    def fields(self) -> int:
-        return int(self.pivot.size(1))
-
-    @property
-    def complete(self) -> bool:
-        return self.count == self.samples
-
-    def _n(self) -> float:
-        if self.count <= 0:
-            raise RuntimeError("RolloutSpectrum: no sample of the window was accumulated (count == 0)")
-        return float(self.count)
-
-    @property
-    def mean(self) -> torch.Tensor:
-        return self.pivot + self.sum / self._n()
-
-    @property
-    def coeff(self) -> torch.Tensor:
-        n = self._n()
-        if self.taper == "hann" and not self.complete:
-            warnings.warn(f"RolloutSpectrum: {self.count} of the {self.samples} samples of a 'hann' window were accumulated: the taper was "
-                          "cut off, the coefficients are those of the truncated weights", RuntimeWarning, stacklevel=2)
-        tw, w = self.tw[:self.count].to(torch.float64), self.w[:self.count].to(torch.float64)
-        W = torch.complex(tw[..., 0].sum(0), tw[..., 1].sum(0)).to(self.re.device)           # [K]
-        S = float(w.sum())
-        shift = (self.sum / n).to(torch.complex128).unsqueeze(-1) * W                          # (mean − pivot) W_k, [N, nf, K]
-        return (torch.complex(self.re, self.im) - shift) / S
-
-    @property
-    def amplitude(self) -> torch.Tensor:
-        return 2.0 * self.coeff.abs()
-
-    @property
-    def phase(self) -> torch.Tensor:
-        return self.coeff.angle()
-
-    @property
-    def power(self) -> torch.Tensor:
-        c = self.coeff
-        return c.real ** 2 + c.imag ** 2
-
-    def band_power(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """[nf, K]: the power summed over the nodes (`mask` bool [N]: over those nodes only)."""
-        p = self.power
-        if mask is not None:
-            if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (int(p.size(0)),):
-                raise ValueError(f"mask: expected a bool tensor of shape ({int(p.size(0))},), got {getattr(mask, 'dtype', type(mask).__name__)} "
-                                 f"{tuple(getattr(mask, 'shape', ()))}")
-            p = p[mask.to(p.device)]
-        return p.sum(0)
-
-    def dominant(self, field: int = 0, mask: Optional[torch.Tensor] = None) -> float:
-        """The frequency (of `freqs`) with the largest band power of `field`."""
-        return float(self.freqs[int(self.band_power(mask)[field].argmax())])
-
-    def __repr__(self):
-        return (f"RolloutSpectrum(count={self.count}, samples={self.samples}, origin={self.origin}, stride={self.stride}, taper={self.taper!r}, "
-                f"fields={self.fields}, bins={int(self.tw.size(1))}, nodes={int(self.pivot.size(0))})")
-
-
-def _check_derived(graph: Graph, nf: int, max_steps: int, derived, every, moments, options, in_list: bool = False, spectrum=None):
-    """The `derived*=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing is moved, the
-    library is not touched) -> (names, every, window or None, options, spectrum or None), or None when no diagnostics are asked for."""
-    from ..mesh_gradient import check_mesh, derived_terms
-    if derived is None or derived is False:
-        if (every not in (0, None)) or moments not in (None, False) or options:
-            raise ValueError("derived: derived_every / derived_moments / derived_options were given without derived=")
-        if spectrum is not None:
-            raise ValueError("derived_spectrum: the spectrum of the derived columns needs derived=")
-        return None
-    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
-        raise ValueError(f"derived_every: expected an integer >= 0 (0: no snapshots, k: every k-th step), got {every!r}")
-    options = dict(options or {})
-    unknown = set(options) - {"power", "edge_vectors", "velocity", "field_scale"}
-    if unknown:
-        raise ValueError(f"derived_options: unknown option(s) {sorted(unknown)} (power, edge_vectors, velocity, field_scale)")
-    if in_list and options.get("edge_vectors") is not None:
-        raise ValueError("derived_options: edge_vectors of a list of graphs: collate the graphs and their edge vectors yourself")
-    dim = check_mesh(graph, options.get("power", 2), options.get("edge_vectors"))
-    names = (derived,) if isinstance(derived, str) else derived
-    terms = derived_terms(names, dim, nf, options.get("velocity"), options.get("field_scale"))
-    window = _check_moments("derived_moments", moments, len(terms), max_steps)
-    return tuple(names), int(every), window, options, _check_spectrum("derived_spectrum", spectrum, len(terms), max_steps)
-
-
-class _Derived:
-    """The flow diagnostics of a `Rollout` and the launches that form them.  Everything is allocated here, once, in the rollout's
-    node numbering: the operator (`MeshGradient` on the rollout's own graph — the caller's edge vectors follow the renumbered
-    edges), the program, `cur` [N, nd], the per-step sums [max_steps, nd, 3] with their scratch, the snapshot slots, and the
-    accumulators of `g4c_rollout_moments` and of `g4c_rollout_spectrum` over `cur`."""
-
-    def __init__(self, ro: "Rollout", names, every: int, window, options: dict, spectrum=None):
-        from ..mesh_gradient import MeshGradient
-        dev, n = ro.field.device, int(ro.graph.num_nodes)
-        ev = options.get("edge_vectors")
-        if ev is not None:
-            ev = ev.to(dev)
-            if ro._perm is not None:          # reorder.reorder_nodes: the edges re-sorted stably by their new target
-                inv = torch.empty_like(ro._perm)
-                inv[ro._perm] = torch.arange(n, device=ro._perm.device)
-                ev = ev[torch.argsort(inv[ro._caller_graph.edge_index[1].to(inv.device)], stable=True).to(dev)]
-        self.op = MeshGradient(ro.graph, options.get("power", 2), ev)
-        self.names, self.columns = tuple(names), self.op.columns(names)
-        self.program = self.op.program(names, ro.nf, options.get("velocity"), options.get("field_scale"))
-        self.nd, self.every, self.max_steps = len(self.columns), every, ro.max_steps
-        self.cur = torch.zeros((n, self.nd), dtype=torch.float32, device=dev)
-        self.stats = torch.zeros((ro.max_steps, self.nd, _lib.DERIVED_NSTAT), dtype=torch.float64, device=dev)
-        self.scratch = ops.mesh_derived_scratch(n, self.nd, dev)
-        self.snap = torch.zeros((ro.max_steps // every, n, self.nd), dtype=torch.float32, device=dev) if every else None
-        self.moments = None if window is None else _Moments(ro, *window, nf=self.nd)
-        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, nf=self.nd)       # (launched by `Rollout._one`)
-
-    def launch(self, pred, step) -> None:
-        ops.mesh_derived(pred, self.op.off, self.op.g, self.op.src, self.program, self.cur, step=step, every=self.every, snap=self.snap,
-                         stats=self.stats, scratch=self.scratch, max_steps=self.max_steps)
-        if self.moments is not None:
-            self.moments.accumulate(self.cur, step)
-
-    def read(self, perm, steps_done: int) -> "RolloutDerived":
-        def rows(t):
-            if perm is None:
-                return t
-            out = torch.empty_like(t)
-            out[perm] = t
-            return out
-
-        return RolloutDerived(self.names, self.columns, self.stats[:steps_done].cpu(), int(self.cur.size(0)),
-                              snapshots=rows(ops.steps_to_columns(self.snap)) if self.snap is not None else None,
-                              moments=self.moments.read(perm) if self.moments is not None else None, degenerate=rows(self.op.degenerate))
-
-
-class RolloutDerived:
-    """Flow diagnostics of a rollout (`Rollout.derived()`, `GNN.diagnostics()`, `GNN.evaluate(derived=)`): `names` as asked for,
-    `columns` their nd labels, and per step taken `rms` = √(Σq² / N), `mean_abs` = Σ|q| / N and `max_abs` = max|q| over the N nodes,
-    each [steps, nd] — from `sums` [steps, nd, 3] = (Σq², Σ|q|, max|q|), which the step accumulated on the device in fp64 in a fixed
-    order (fp64 host tensors).  `snapshots` [N, nd * (max_steps // k)]: the columns of steps k - 1, 2k - 1, ... (`derived_every=k`), else
-    None; `moments`: their per-node time statistics (`RolloutMoments`, `derived_moments=`), else None; `degenerate` bool [N]: the
-    nodes whose neighbours do not span the space — their derivatives are 0.  Rows are the caller's numbering."""
-
-    def __init__(self, names, columns, sums: torch.Tensor, n_nodes: int, snapshots: Optional[torch.Tensor] = None,
-                 moments: Optional["RolloutMoments"] = None, degenerate: Optional[torch.Tensor] = None):
-        self.names, self.columns, self.sums, self.n_nodes = tuple(names), list(columns), sums, int(n_nodes)
-        self.snapshots, self.moments, self.degenerate = snapshots, moments, degenerate
-        n = float(max(n_nodes, 1))
-        self.rms = (sums[..., _lib.DERIVED_SQ] / n).sqrt()
-        self.mean_abs = sums[..., _lib.DERIVED_ABS] / n
-        self.max_abs = sums[..., _lib.DERIVED_MAX_ABS]
-
-    def column(self, label: str) -> int:
-        return self.columns.index(label)
-
-    def __repr__(self):
-        return f"RolloutDerived(columns={self.columns}, steps={int(self.sums.size(0))}, nodes={self.n_nodes})"
-
-
-def _check_samples(graph, nf: int, max_steps: int, samples, every, moments, spectrum, sample_derived, has_derived: bool,
-                   in_list: bool = False):
-    """The `samples=` / `sample_*=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing is
-    moved, the library is not touched) -> the arguments of `_Samples`, or None when no samples are asked for."""
-    from ..point_sampler import PointSampler, check_points
-    if not isinstance(sample_derived, bool):
-        raise ValueError(f"sample_derived: expected a bool, got {sample_derived!r}")
-    if samples is None:
-        if moments not in (None, False) or spectrum is not None or sample_derived:
-            raise ValueError("samples: sample_moments / sample_spectrum / sample_derived were given without samples=")
-        return None
-    if in_list:
-        raise ValueError("samples: a list of graphs is collated into one cloud in which the graphs overlap in space: sample each graph on its own")
-    if isinstance(samples, PointSampler):
-        if samples.n_nodes != int(graph.num_nodes):
-            raise ValueError(f"samples: a PointSampler over {samples.n_nodes} nodes for a graph of {int(graph.num_nodes)}")
-    else:
-        try:
-            check_points(graph, samples, None, 2)
-        except ValueError as e:
-            raise ValueError(f"samples: {e}") from None
-    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
-        raise ValueError(f"sample_every: expected an integer >= 0 (0: no series, k: every k-th step), got {every!r}")
-    if sample_derived and not has_derived:
-        raise ValueError("sample_derived: the samples of the derived columns need derived=")
-    for name, asked, what in (("sample_moments", moments not in (None, False), "time statistics"), ("sample_spectrum", spectrum is not None, "spectra")):
-        if asked and nf > _lib.REC_MAX_NF:
-            raise ValueError(f"{name}: the {what} cover up to {_lib.REC_MAX_NF} fields, this model has {nf}")
-    try:
-        window = _check_moments("sample_moments", moments, nf, max_steps)
-        table = _check_spectrum("sample_spectrum", spectrum, nf, max_steps)
-    except (TypeError, NotImplementedError) as e:
-        raise ValueError(str(e)) from None
-    return dict(samples=samples, every=int(every), window=window, spectrum=table, sample_derived=sample_derived)
-
-
-class _Samples:
-    """The samples of a `Rollout` at points off the nodes and the launches that form them.  Everything is allocated here, once: the
-    sampler (built on the caller's graph when points were given), its neighbour table mapped through the inverse of the rollout's
-    renumbering — the same values then enter every sum in the same order, so the bits do not depend on `reorder` —, `cur` [P, nf], the
-    series' slots, the same for the derived columns, and the accumulators of `g4c_rollout_moments` and `g4c_rollout_spectrum` over
-    `cur` (P rows).  The points keep the caller's order: nothing is permuted on read."""
-
-    def __init__(self, ro: "Rollout", samples, every: int, window, spectrum, sample_derived: bool):
-        from ..point_sampler import PointSampler
-        dev, nf, steps = ro.field.device, ro.nf, ro.max_steps
-        self.sampler = samples if isinstance(samples, PointSampler) else PointSampler(ro._caller_graph, samples)
-        self.idx, self.coef = self.sampler._idx.to(dev), self.sampler._coef.to(dev)
-        if ro._perm is not None:                      # caller's row r is the rollout's row inv[r]
-            inv = torch.empty_like(ro._perm)
-            inv[ro._perm] = torch.arange(int(ro.graph.num_nodes), device=ro._perm.device)
-            self.idx = inv.to(dev)[self.idx.long()].to(torch.int32).contiguous()
-        n = self.sampler.n_points
-        self.every, self.max_steps = every, steps
-        self.cur = torch.zeros((n, nf), dtype=torch.float32, device=dev)
-        self.series = torch.zeros((steps // every, n, nf), dtype=torch.float32, device=dev) if every else None
-        self.dcur = self.dseries = self.columns = None
-        if sample_derived:
-            self.columns, nd = list(ro._derived.columns), ro._derived.nd
-            self.dcur = torch.zeros((n, nd), dtype=torch.float32, device=dev)
-            self.dseries = torch.zeros((steps // every, n, nd), dtype=torch.float32, device=dev) if every else None
-        self.moments = None if window is None else _Moments(ro, *window, rows=n)
-        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, rows=n)
-
-    def launch(self, pred, step, derived) -> None:
-        ops.sample_points(pred, self.idx, self.coef, self.cur, step=step, every=self.every, series=self.series, max_steps=self.max_steps)
-        if self.dcur is not None:
-            ops.sample_points(derived.cur, self.idx, self.coef, self.dcur, step=step, every=self.every, series=self.dseries,
-                              max_steps=self.max_steps)
-        if self.moments is not None:
-            self.moments.accumulate(self.cur, step)
-        if self.spectrum is not None:
-            self.spectrum.accumulate(self.cur, step)
-
-    def read(self) -> "RolloutSamples":
-        return RolloutSamples(self.sampler, series=ops.steps_to_columns(self.series) if self.series is not None else None,
-                              derived=ops.steps_to_columns(self.dseries) if self.dseries is not None else None, columns=self.columns,
-                              moments=self.moments.read(None) if self.moments is not None else None,
-                              spectrum=self.spectrum.read(None) if self.spectrum is not None else None, fields=int(self.cur.size(1)))
-
-
-class RolloutSamples:
-    """A rollout at points off the nodes (`Rollout.samples()`, `GNN.sample()`, `GNN.evaluate(samples=)`): `sampler` (the
-    `gfd.PointSampler`) with its `points` [P, dim], `distance` [P] (to the nearest node: mask the points inside a body or outside the
-    domain by it) and `degenerate` [P]; `series` [P, nf * slots]: the sampled prediction of steps k - 1, 2k - 1, ... (`sample_every=k`;
-    None with 0), laid out as `Rollout.probes()`; `derived` [P, nd * slots] and `columns`, the labels: the sampled derived columns
-    (`sample_derived=True`), else None; `moments` / `spectrum`: the time statistics (`RolloutMoments`) and Fourier modes
-    (`RolloutSpectrum`) of the sampled prediction at every point, else None; `target`: the ground truth at the points
-    [P, nf * n_out], filled by `GNN.evaluate`.  `image(slot, column)` is one column of one slot as a raster, for a grid sampler.  The
-    points are in the caller's order."""
-
-    def __init__(self, sampler, series: Optional[torch.Tensor] = None, derived: Optional[torch.Tensor] = None, columns=None,
-                 moments: Optional["RolloutMoments"] = None, spectrum: Optional["RolloutSpectrum"] = None, fields: int = 0):
-        self.sampler, self.points, self.distance, self.degenerate = sampler, sampler.points, sampler.distance, sampler.degenerate
-        self.series, self.derived, self.columns, self.moments, self.spectrum, self.fields = series, derived, columns, moments, spectrum, int(fields)
-        self.target = None
-
-    @property
-    def slots(self) -> int:
-        return 0 if self.series is None else int(self.series.size(1)) // max(self.fields, 1)
-
-    def image(self, slot: int = -1, column=0) -> torch.Tensor:
-        """Column `column` — a field number of the prediction, or a label of `columns` (the sampled derived columns) — of slot `slot`
-        (negative: from the last) as a tensor of the sampler's `shape` (`PointSampler.grid`): entry [i, j] is the value at
-        (x_i, y_j).  ValueError for a sampler that is no grid."""
-        shape = getattr(self.sampler, "shape", None)
-        if shape is None:
-            raise ValueError("image: the sampler is no grid (PointSampler.grid builds one)")
-        if isinstance(column, str):
-            if self.derived is None or column not in self.columns:
-                raise ValueError(f"column: {column!r} is no sampled derived column ({self.columns})")
-            data, width, col = self.derived, len(self.columns), self.columns.index(column)
-        else:
-            if isinstance(column, bool) or not isinstance(column, int) or not 0 <= column < self.fields:
-                raise ValueError(f"column: expected a field 0 .. {self.fields - 1} or a derived column's label, got {column!r}")
-            data, width, col = self.series, self.fields, column
-        if data is None:
-            raise ValueError("image: no series was kept (sample_every=0)")
-        slots = int(data.size(1)) // width
-        if isinstance(slot, bool) or not isinstance(slot, int) or not -slots <= slot < slots:
-            raise ValueError(f"slot: expected -{slots} <= slot < {slots}, got {slot!r}")
-        return data[:, width * (slot % slots) + col].reshape(*shape)
-
-    def __repr__(self):
-        return (f"RolloutSamples(points={int(self.points.size(0))}, fields={self.fields}, slots={self.slots}, derived={self.columns}, "
-                f"moments={self.moments is not None}, spectrum={self.spectrum is not None})")
-
-
-def _check_tracers(graph, nf: int, tracers, every, in_list: bool = False):
-    """The `tracers=` / `tracer_every=` arguments of `Rollout` against the caller's graph, on the tensors as they were passed (nothing
-    is moved, the library is not touched) -> (the particles' description, every), or None when no tracers are asked for."""
-    from ..tracers import Tracers, check_tracers
-    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
-        raise ValueError(f"tracer_every: expected an integer >= 0 (0: no series, k: every k-th step), got {every!r}")
-    if tracers is None:
-        if every != 1:
-            raise ValueError("tracers: tracer_every was given without tracers=")
-        return None
-    if in_list:
-        raise ValueError("tracers: a list of graphs is collated into one cloud in which the graphs overlap in space: trace each graph on its own")
-    if isinstance(tracers, Tracers):
-        spec = tracers._spec
-        if spec["n_nodes"] != int(graph.num_nodes):
-            raise ValueError(f"tracers: Tracers over {spec['n_nodes']} nodes for a graph of {int(graph.num_nodes)}")
-        if max(spec["velocity"]) >= nf:
-            raise ValueError(f"tracers: velocity: fields {spec['velocity']} of a model of {nf} (the velocity must be among the model's fields)")
-        return spec, int(every)
-    if not isinstance(tracers, tuple) or len(tracers) not in (2, 3) or (len(tracers) == 3 and not isinstance(tracers[2], dict)):
-        raise TypeError(f"tracers: expected a gfd.Tracers or a tuple (seeds, dt), got {type(tracers).__name__}")
-    try:
-        return check_tracers(graph, tracers[0], tracers[1], nf=nf, **(tracers[2] if len(tracers) == 3 else {})), int(every)
-    except ValueError as e:
-        raise ValueError(f"tracers: {e}") from None
-    except TypeError as e:
-        raise TypeError(f"tracers: {e}") from None
-
-
-class _Tracers:
-    """The tracers of a `Rollout` and the launch that moves them.  Everything is allocated here, once: the cell grid over the
-    rollout's own (possibly renumbered) positions, a copy of the particles, the series' slots.  The particles keep the caller's order
-    and a neighbour sum runs nearest first whatever the nodes are called, so nothing is permuted on read and the bits do not depend on
-    `reorder`.  x0 is the last nf columns of the field window, x1 the prediction."""
-
-    def __init__(self, ro: "Rollout", spec: dict, every: int):
-        from ..tracers import TracerState
-        self.state = TracerState(spec, ro.graph.pos.detach().to(ro.field.device, torch.float32).contiguous(), every, ro.max_steps)
-        self.state.save()                              # (a recomputation starts again from here)
-        self.nf = ro.nf
-
-    def launch(self, field, pred, step) -> None:
-        self.state.launch(field[:, int(field.size(1)) - self.nf:], pred, step=step)
-
-    def through_target(self, ro: "Rollout", n_out: int) -> Optional[torch.Tensor]:
-        """[P, dim * slots]: a copy of the same particles carried by the target instead — n_out launches outside the step: the first
-        from the input field (level 0) to the target's first nf columns (level 1), then from column block to column block."""
-        from ..tracers import TracerState
-        st, nf, target = self.state, self.nf, ro._rec.target
-        if not st.every:
-            return None
-        other = TracerState(st.spec, ro.graph.pos.detach().to(target.device, torch.float32).contiguous(), st.every, n_out)
-        x0 = ro._orig_field.to(target.device, torch.float32)
-        x0 = x0[:, int(x0.size(1)) - nf:]
-        for t in range(n_out):
-            x1 = target[:, nf * t:nf * (t + 1)]
-            other.launch(x0, x1, t=t)
-            x0 = x1
-        return ops.steps_to_columns(other.series)
-
-    def read(self) -> "RolloutTracers":
-        from ..tracers import RolloutTracers
-        st = self.state
-        return RolloutTracers(ops.steps_to_columns(st.series) if st.series is not None else None, st.q.clone(), st.status.clone(),
-                              st.stopped.clone(), st.release, st.seeds, every=st.every, groups=st.spec["groups"])
-
-
-def _check_forces(graph, nf: int, max_steps: int, forces, force_moments, force_spectrum, wall_moments, target_forces, has_target: bool,
-                  in_list: bool = False):
-    """The `forces=` / `force_*=` / `wall_moments=` / `target_forces=` arguments of `Rollout` against the caller's graph, on the
-    tensors as they were passed (nothing is moved, the library is not touched) -> the arguments of `_Forces`, or None when no forces
-    are asked for."""
-    from ..body_forces import BodyForces
-    if not isinstance(target_forces, bool):
-        raise TypeError(f"target_forces: expected a bool, got {target_forces!r}")
-    if forces is None:
-        if force_moments not in (None, False) or wall_moments not in (None, False) or force_spectrum is not None or target_forces:
-            raise ValueError("forces: force_moments / force_spectrum / wall_moments / target_forces were given without forces=")
-        return None
-    if in_list:
-        raise ValueError("forces: a list of graphs is collated into one cloud in which the graphs overlap in space: take each graph's forces on its own")
-    if not isinstance(forces, BodyForces):
-        raise TypeError(f"forces: expected a gfd.BodyForces built on this graph, got {type(forces).__name__}")
-    if forces.n_nodes != int(graph.num_nodes):
-        raise ValueError(f"forces: a BodyForces over {forces.n_nodes} nodes for a graph of {int(graph.num_nodes)}")
-    if forces.fields_needed() > nf:
-        raise ValueError(f"forces: the operator reads field {forces.fields_needed() - 1}, the model has {nf} field(s)")
-    for name, v in (("scale", forces.scale), ("shift", forces.shift)):
-        if v is not None and len(v) != nf:
-            raise ValueError(f"forces: {name}: {len(v)} numbers for a model of {nf} field(s)")
-    if target_forces and not has_target:
-        raise ValueError("target_forces: the forces of the target need target=")
-    window = _check_moments("force_moments", force_moments, 3, max_steps)
-    wall_window = _check_moments("wall_moments", wall_moments, 2, max_steps)
-    table = _check_spectrum("force_spectrum", force_spectrum, 3, max_steps)
-    return dict(forces=forces, window=window, wall_window=wall_window, spectrum=table, target_forces=target_forces)
-
-
-class _Forces:
-    """The body forces of a `Rollout` and the launches that form them.  Everything is allocated here, once: the wall items mapped
-    through the inverse of the rollout's renumbering, the gradient's tables re-indexed to it — every node keeps its in-edges in the
-    caller's CSR order, so the same values enter every sum in the same order and the bits do not depend on `reorder` —, the per-step
-    sums [max_steps, B, 6], `cur` [B, 3], `wall` [W, 2], the same sums for the target, and the accumulators of `g4c_rollout_moments`
-    and `g4c_rollout_spectrum` over `cur` (B rows) and `wall` (W rows).  Bodies and items keep the caller's order: nothing is permuted
-    on read."""
-
-    def __init__(self, ro: "Rollout", forces, window, wall_window, spectrum, target_forces: bool):
-        dev, steps = ro.field.device, ro.max_steps
-        self.op, self.nf, self.max_steps = forces, ro.nf, steps
-        self.item, self.body_off = forces._item32.to(dev), forces.body_offsets.to(dev)
-        self.area, self.unit, self.arm = forces.area.to(dev), forces.unit.to(dev), forces.arm.to(dev)
-        self.constants = forces.constants()
-        grad = forces.gradient if forces.mu != 0 else None
-        self.off, self.g, self.src = (None, None, None) if grad is None else (grad.off.to(dev), grad.g.to(dev), grad.src.to(dev))
-        if ro._perm is not None:                      # caller's row r is the rollout's row inv[r]
-            perm = ro._perm.to(dev)
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(int(ro.graph.num_nodes), device=dev)
-            self.item = inv[self.item.long()].to(torch.int32).contiguous()
-            if grad is not None:                      # the rollout's node j owns the caller's segment of node perm[j], in its order
-                off = self.off.long()
-                deg = (off[1:] - off[:-1])[perm]
-                new_off = torch.zeros_like(off)
-                new_off[1:] = torch.cumsum(deg, 0)
-                e = torch.arange(int(new_off[-1]), device=dev) + torch.repeat_interleave(off[:-1][perm] - new_off[:-1], deg)
-                self.off, self.g = new_off.to(torch.int32), self.g[e].contiguous()
-                self.src = inv[self.src[e].long()].to(torch.int32).contiguous()
-        n_bodies, n_items = forces.n_bodies, forces.n_items
-        self.stats = torch.zeros((steps, n_bodies, _lib.FORCES_NSUM), dtype=torch.float64, device=dev)
-        self.cur = torch.zeros((n_bodies, 3), dtype=torch.float32, device=dev)
-        self.wall = torch.zeros((n_items, 2), dtype=torch.float32, device=dev)
-        self.moments = None if window is None else _Moments(ro, *window, nf=3, rows=n_bodies)
-        self.wall_moments = None if wall_window is None else _Moments(ro, *wall_window, nf=2, rows=n_items)
-        self.spectrum = None if spectrum is None else _Spectrum(ro, spectrum, x=self.cur, nf=3, rows=n_bodies)
-        self.target = ro._rec.target if target_forces else None
-        self.target_stats = torch.zeros_like(self.stats) if target_forces else None
-        self.target_cur = torch.zeros_like(self.cur) if target_forces else None
-
-    def accumulators(self):
-        return (self.moments, self.wall_moments, self.spectrum)
-
-    def _launch(self, x, step, stats, cur, wall, x_step) -> None:
-        ops.body_forces(x, self.item, self.body_off, self.area, self.unit, self.arm, cur, **self.constants, off=self.off, g=self.g,
-                        src=self.src, wall=wall, stats=stats, max_steps=self.max_steps, step=step, x_step=x_step)
-
-    def launch(self, pred, step) -> None:
-        self._launch(pred, step, self.stats, self.cur, self.wall, 0)
-        if self.moments is not None:
-            self.moments.accumulate(self.cur, step)
-        if self.wall_moments is not None:
-            self.wall_moments.accumulate(self.wall, step)
-        if self.spectrum is not None:
-            self.spectrum.accumulate(self.cur, step)
-        if self.target is not None:
-            self._launch(self.target, step, self.target_stats, self.target_cur, None, self.nf)
-
-    def read(self, steps_done: int) -> "RolloutForces":
-        return RolloutForces(self.stats[:steps_done].cpu(), angle=self.op.angle, body_offsets=self.op.body_offsets,
-                             moments=self.moments.read(None) if self.moments is not None else None,
-                             wall_moments=self.wall_moments.read(None) if self.wall_moments is not None else None,
-                             spectrum=self.spectrum.read(None) if self.spectrum is not None else None,
-                             target=self.target_stats[:steps_done].cpu() if self.target_stats is not None else None)
-
-
-class RolloutForces:
-    """The forces of a rollout on the bodies in the flow (`Rollout.forces()`, `GNN.forces()`, `GNN.evaluate(forces=)`), per step
-    taken and body, fp64 host tensors: `pressure` [n, B, 3] = (F_x, F_y, M) of the pressure, `viscous` [n, B, 3] the same of the
-    viscous stress, `total` their sum — from `sums` [n, B, 6] = (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv), which the step formed on the device
-    in fp64 in a fixed order.  `moments`: the time statistics of the total (F_x, F_y, M) of every body (`RolloutMoments` over B rows,
-    `force_moments=`), `wall_moments`: of (pressure, wall shear) at every wall item (W rows, `wall_moments=` — the mean Cp(θ) against
-    `angle` [W]; `body_offsets` [B + 1] delimits the bodies), `spectrum`: the Fourier modes of the total (`RolloutSpectrum`,
-    `force_spectrum=`), each None when not asked for; `target` [n, B, 6]: the sums of the target's fields (`target_forces=True`,
-    `GNN.evaluate(forces=)`), else None.  `coefficients(rho, U, D)` = (Cd, Cl, Cm) [n, B] = (F_x, F_y, M / D) / (½ rho U² D);
-    `strouhal(D, U, body)` = the dominant frequency of that body's lift × D / U."""
-
-    def __init__(self, sums: torch.Tensor, angle: Optional[torch.Tensor] = None, body_offsets: Optional[torch.Tensor] = None,
-                 moments: Optional["RolloutMoments"] = None, wall_moments: Optional["RolloutMoments"] = None,
-                 spectrum: Optional["RolloutSpectrum"] = None, target: Optional[torch.Tensor] = None):
-        if sums.dim() != 3 or int(sums.size(2)) != _lib.FORCES_NSUM:
-            raise ValueError(f"sums: expected [steps, bodies, {_lib.FORCES_NSUM}], got {tuple(sums.shape)}")
-        self.sums, self.angle, self.body_offsets = sums, angle, body_offsets
-        self.moments, self.wall_moments, self.spectrum, self.target = moments, wall_moments, spectrum, target
-        self.pressure = sums[..., [_lib.FORCES_FPX, _lib.FORCES_FPY, _lib.FORCES_MP]]
-        self.viscous = sums[..., [_lib.FORCES_FVX, _lib.FORCES_FVY, _lib.FORCES_MV]]
-        self.total = self.pressure + self.viscous
-
-    @property
-    def steps(self) -> int:
-        return int(self.sums.size(0))
-
-    def coefficients(self, rho: float, U: float, D: float):
-        """(Cd, Cl, Cm), each [steps, B]: the total (F_x, F_y, M / D) over ½ rho U² D."""
-        for name, v in (("rho", rho), ("U", U), ("D", D)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
-                raise ValueError(f"{name}: expected a positive number, got {v!r}")
-        q = 0.5 * float(rho) * float(U) * float(U) * float(D)
-        return self.total[..., 0] / q, self.total[..., 1] / q, self.total[..., 2] / (q * float(D))
-
-    def strouhal(self, D: float, U: float, body: int = 0) -> float:
-        """The frequency with the largest power of the lift of `body` (`spectrum.dominant(field=1)` of that body) × D / U."""
-        if self.spectrum is None:
-            raise RuntimeError("RolloutForces: no force_spectrum= was asked for")
-        n_bodies = int(self.spectrum.pivot.size(0))
-        if isinstance(body, bool) or not isinstance(body, int) or not 0 <= body < n_bodies:
-            raise ValueError(f"body: expected 0 .. {n_bodies - 1}, got {body!r}")
-        mask = torch.zeros(n_bodies, dtype=torch.bool)
-        mask[body] = True
-        return self.spectrum.dominant(1, mask) * float(D) / float(U)
-
-    def __repr__(self):
-        return (f"RolloutForces(steps={self.steps}, bodies={int(self.sums.size(1))}, moments={self.moments is not None}, "
-                f"wall_moments={self.wall_moments is not None}, spectrum={self.spectrum is not None}, target={self.target is not None})")
-
-
-class _Records:
-    """The record buffers of a `Rollout` and the launch that fills them.  Everything is allocated here, once, in the rollout's node
-    numbering (probe rows, target rows and mask rows are mapped through the Morton permutation at construction), so a captured
-    step allocates nothing; every slot is addressed by the device-side step index alone, so `rewind()` and a recomputation
-    (`Rollout._recompute_exact`) overwrite the records of the steps they run again."""
-
-    def __init__(self, ro: "Rollout", every: int, probes, target, mask):
-        dev, n, nf, steps, perm = ro.field.device, int(ro.graph.num_nodes), ro.nf, ro.max_steps, ro._perm
-        self.nf, self.max_steps, self.every = nf, steps, every
-        self.snap = torch.zeros((steps // every, n, nf), dtype=torch.float32, device=dev) if every else None
-        ro._out_steps = self.snap
-        self.probe_rows = self.probe_out = self.target = self.mask = self.stats = self.scratch = None
-        self.n_masked = None
-        if probes is not None:
-            rows = probes.to(dev, torch.long)
-            if perm is not None:                      # caller's row r is the rollout's row inv[r]
-                inv = torch.empty_like(perm)
-                inv[perm] = torch.arange(n, device=perm.device)
-                rows = inv.to(dev)[rows]
-            self.probe_rows = rows.to(torch.int32).contiguous()
-            self.probe_out = torch.zeros((steps, int(rows.numel()), nf), dtype=torch.float32, device=dev)
-        if target is not None:
-            t = target.to(dev, torch.float32)
-            if perm is not None:
-                t = t[perm.to(dev)]
-            if t.stride(1) != 1 or t.stride(0) < t.size(1):
-                t = t.contiguous()
-            self.target = t
-            if mask is not None:
-                m = mask.to(dev)
-                self.n_masked = int(m.sum())
-                self.mask = (m[perm.to(dev)] if perm is not None else m).contiguous()
-            self.stats = torch.zeros((steps, nf, _lib.REC_NSTAT), dtype=torch.float64, device=dev)
-            self.scratch = ops.rollout_record_scratch(n, nf, dev)
-
-    def advance(self, field, pred, step) -> None:
-        ops.rollout_advance_record(field, pred, step, self.nf, self.max_steps, snap=self.snap, every=self.every,
-                                   probe_rows=self.probe_rows, probe_out=self.probe_out, target=self.target, mask=self.mask,
-                                   stats=self.stats, scratch=self.scratch)
-
-
-class RolloutErrors:
-    """Per-step errors of a rollout against its target (`Rollout.errors()`, `GNN.evaluate()`): fp64 host tensors [steps, nf] —
-    `mse` = Σd²/N, `mae` = Σ|d|/N, `max_abs` = max|d|, `r2` = 1 − Σd² / (Σy² − (Σy)²/N) (inf or nan where the target is constant),
-    `mae_masked` = Σ|d| over the masked (Dirichlet) nodes / their number (None without a mask) — with d = prediction − target and
-    y = the target, all from `sums` [steps, nf, 6] = (Σd², Σ|d|, max|d|, Σy, Σy², Σ_masked|d|), which the step's last launch
-    accumulated on the device in fp64 in a fixed order.  `snapshots` / `probes`: the rollout's `result()` / `probes()` when it kept
-    any, else None.  `moments` / `error_moments`: None unless `GNN.evaluate` was asked for them."""
-
-    def __init__(self, sums: torch.Tensor, n_nodes: int, n_masked: Optional[int] = None, snapshots: Optional[torch.Tensor] = None,
-                 probes: Optional[torch.Tensor] = None):
-        self.sums, self.n_nodes, self.n_masked, self.snapshots, self.probes = sums, int(n_nodes), n_masked, snapshots, probes
-        self.moments = self.error_moments = None        # `RolloutMoments` when GNN.evaluate(moments= / error_moments=) asked for them
-        self.derived = None                             # `RolloutDerived` when GNN.evaluate(derived=) asked for it
-        self.spectrum = self.target_spectrum = None     # `RolloutSpectrum` when GNN.evaluate(spectrum=) asked for them
-        n = float(n_nodes)
-        sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
-        self.mse, self.mae, self.max_abs = sq / n, ab / n, mx
-        self.r2 = 1.0 - sq / (ty2 - ty * ty / n)
-        self.mae_masked = None if n_masked is None else abm / float(n_masked)
-
-    @property
-    def steps(self) -> int:
-        return int(self.sums.size(0))
-
-    def graph_loss(self, lambda_d: float = 0.0) -> torch.Tensor:
-        """`GraphLoss(lambda_d)` of every step, [steps], from the same sums: Σ_f Σd² / (N nf) + lambda_d Σ_f Σ_masked|d| / (N_masked nf),
-        the second term only with lambda_d > 0 and at least one masked node (nn/losses.py)."""
-        nf = int(self.sums.size(1))
-        loss = self.sums[..., _lib.REC_SQ_ERR].sum(1) / (self.n_nodes * nf)
-        if lambda_d > 0 and self.n_masked:
-            loss = loss + lambda_d * self.sums[..., _lib.REC_ABS_ERR_MASK].sum(1) / (self.n_masked * nf)
-        return loss
-
-    def __repr__(self):
-        return f"RolloutErrors(steps={self.steps}, fields={int(self.sums.size(1))}, nodes={self.n_nodes}, masked={self.n_masked})"

@@ -560,9 +560,9 @@ class DistributedRollout:
         self.capture = capture and device.type == "cuda"
         self.capture_error = None if self.capture else "capture not requested"
         self._hipgraph, self._epoch = None, -1
-        self.static = ops.StaticCache()        # per-mesh constants (edge / angle encoders), as nn.model.Rollout
-        self.flags = ops.RangeFlags(device)     # fp16 range flags of this rollout's own launches, as nn.model.Rollout
-        # optimistic "f16x3" (nn.model.Rollout): the input window the rollout started from, for the exact-range recomputation
+        self.static = ops.StaticCache()        # per-mesh constants (edge / angle encoders), as nn.rollout.Rollout
+        self.flags = ops.RangeFlags(device)     # fp16 range flags of this rollout's own launches, as nn.rollout.Rollout
+        # optimistic "f16x3" (nn.rollout.Rollout): the input window the rollout started from, for the exact-range recomputation
         self._field0 = self.field.clone()
         self.exact_range = False
 
@@ -586,7 +586,7 @@ class DistributedRollout:
             self._step()
 
     def validate(self) -> bool:
-        """As nn.model.Rollout.validate, decided jointly: if ANY rank's launches clipped a value at the end of the fp16 range,
+        """As nn.rollout.Rollout.validate, decided jointly: if ANY rank's launches clipped a value at the end of the fp16 range,
         every rank recomputes its steps in "bf16x6" (the halo exchanges pair up again) and stays in that arithmetic."""
         if ops.mlp_precision() != "f16x3" or self.exact_range or self.device.type != "cuda":
             return False
@@ -615,12 +615,12 @@ class DistributedRollout:
     def _step(self) -> None:
         with torch.no_grad():
             if self._epoch != -1 and ops.weights_epoch() != self._epoch:
-                # (as nn.model.Rollout: the weights changed — load_state_dict, fit, invalidate_packed — so the captured step's packed
+                # (as nn.rollout.Rollout: the weights changed — load_state_dict, fit, invalidate_packed — so the captured step's packed
                 # images are stale or freed; one eager step repacks, then the step is captured again.  Every rank sees the same
                 # epoch sequence as long as every rank updates its replica of the model, which a partitioned rollout requires anyway)
                 self._hipgraph, self._epoch = None, -1
             elif self.static.stale():
-                # (a per-mesh constant edited in place, or another arithmetic — also just BEFORE the capture: as nn.model.Rollout — and, like new weights, something
+                # (a per-mesh constant edited in place, or another arithmetic — also just BEFORE the capture: as nn.rollout.Rollout — and, like new weights, something
                 # every rank has to do alike, or a replaying rank would pair its captured collectives with an eager rank's)
                 self._hipgraph, self._epoch = None, -1
             if self.steps_done == 0 or not self.capture or self._epoch == -1:

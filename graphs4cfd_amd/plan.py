@@ -239,7 +239,7 @@ _cluster_plans = _Cache()
 
 def snapshot() -> list:
     """References to everything the caches hold right now.  A captured hipGraph bakes the plans' device pointers in, so its
-    owner (nn.model.Rollout, partition.DistributedRollout) keeps this list for as long as it may replay: eviction from the
+    owner (nn.rollout.Rollout, partition.DistributedRollout) keeps this list for as long as it may replay: eviction from the
     caches then cannot free memory the graph still reads."""
     return [entry for c in (_edge_plans, _pool_plans, _index_plans, _cluster_plans) for entry in c.data.values()]
 

@@ -197,6 +197,47 @@ def test_the_model_refuses_before_anything_is_moved(label):
     refused(word, call, fake_model(), error=error)
 
 
+SIGNATURES = {          # (name,) or (name, default); "=name": keyword-only, "**name": the rest
+    "Rollout.__init__": [('self',), ('model',), ('graph',), ('max_steps',), ('capture', True), ('reorder', None), ('label', 'Rollout'), ('every', 1),
+                         ('probes', None), ('target', None), ('mask', None), ('moments', None), ('error_moments', None), ('derived', None),
+                         ('derived_every', 0), ('derived_moments', None), ('derived_options', None), ('spectrum', None), ('target_spectrum', False),
+                         ('derived_spectrum', None), ('samples', None), ('sample_every', 1), ('sample_moments', None), ('sample_spectrum', None),
+                         ('sample_derived', False), ('tracers', None), ('tracer_every', 1), ('forces', None), ('force_moments', None),
+                         ('force_spectrum', None), ('wall_moments', None), ('target_forces', False)],
+    "GNN.evaluate": [('self',), ('graph',), ('n_out', None), ('=every', 0), ('=probes', None), ('=capture', None), ('=moments', None),
+                     ('=error_moments', None), ('=derived', None), ('=derived_every', 0), ('=derived_moments', None), ('=derived_options', None),
+                     ('=spectrum', None), ('=samples', None), ('=sample_every', 1), ('=sample_moments', None), ('=sample_spectrum', None),
+                     ('=sample_derived', False), ('=tracers', None), ('=tracer_every', 1), ('=forces', None), ('=force_moments', None),
+                     ('=force_spectrum', None), ('=wall_moments', None), ('=modes', None)],
+    "GNN._rollout": [('self',), ('graph',), ('n_out',), ('capture',), ('label',), ('evaluate', False), ('**records',)],
+    "GNN.solve": [('self',), ('graph',), ('n_out',), ('=capture', None), ('=every', 1)],
+    "GNN.diagnostics": [('self',), ('graph',), ('n_out',), ('derived', ('div', 'vort')), ('=every', 0), ('=discard', None), ('=stride', 1),
+                        ('=capture', None), ('**derived_options',)],
+    "GNN.sample": [('self',), ('graph',), ('n_out',), ('points',), ('=every', 1), ('=discard', None), ('=stride', 1), ('=spectrum', None),
+                   ('=derived', None), ('=capture', None), ('**derived_options',)],
+    "GNN.trace": [('self',), ('graph',), ('n_out',), ('seeds',), ('dt', None), ('=every', 1), ('=capture', None), ('**options',)],
+    "GNN.forces": [('self',), ('graph',), ('n_out',), ('bodies', None), ('=discard', None), ('=stride', 1), ('=spectrum', None), ('=wall', False),
+                   ('=capture', None), ('**options',)],
+    "GNN.time_statistics": [('self',), ('graph',), ('n_out',), ('=discard', 0), ('=stride', 1), ('=every', 0), ('=capture', None)],
+    "GNN.spectrum": [('self',), ('graph',), ('n_out',), ('bins', None), ('freqs', None), ('=discard', 0), ('=stride', 1), ('=samples', None),
+                     ('=dt', 1.0), ('=taper', 'rect'), ('=derived', None), ('=every', 0), ('=capture', None), ('**derived_options',)],
+    "GNN.modes": [('self',), ('graph',), ('n_out',), ('modes', None), ('=every', 1), ('=capture', None), ('**spec',)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(SIGNATURES))
+def test_the_public_signatures_of_the_rollout_stand(name):
+    """Names, order, kinds and defaults of `Rollout.__init__` and of every `GNN` entry point that builds one, as literals."""
+    import inspect
+    owner, attr = name.split(".")
+    got = []
+    for p in inspect.signature(getattr({"Rollout": Rollout, "GNN": GNN}[owner], attr)).parameters.values():
+        assert p.kind != p.VAR_POSITIONAL
+        label = {p.VAR_KEYWORD: "**", p.KEYWORD_ONLY: "="}.get(p.kind, "") + p.name
+        got.append((label,) if p.default is p.empty else (label, p.default))
+    assert got == SIGNATURES[name]
+
+
 def test_streaklines_and_residence_read_the_paths():
     m, n_seeds, dim, slots, every = 3, 2, 2, 4, 2
     paths = torch.arange(m * n_seeds * dim * slots, dtype=torch.float32).reshape(m * n_seeds, dim * slots)
