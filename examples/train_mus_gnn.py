@@ -6,7 +6,12 @@ The NsCircle HDF5 file is replaced by a synthetic array in the same record layou
 code | u v p per time step], NaN-padded to the largest mesh): decaying travelling waves on random point clouds — there is no
 network / h5py here; with the real file pass path="NsCircle.h5" instead of data=.
 
-    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8]
+    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss]
+
+--flow-loss trains with gfd.nn.FlowLoss: GraphLoss plus a continuity penalty (the divergence of the predicted velocity) and a
+vorticity-matching term, both through the differentiable least-squares mesh gradient (gfd.MeshGradient).  The mesh is periodic in y,
+so the operator is built from the wrapped `edge_attr`, not from differences of `pos`; `ScaleEdgeAttr(0.1)` has divided those vectors by
+0.2, so every derivative comes out 0.2 times its size in mesh units — a constant the weights absorb.
 """
 import argparse, math, os, sys
 import torch
@@ -16,6 +21,7 @@ import graphs4cfd_amd as gfd          # instead of: import graphs4cfd as gfd
 ap = argparse.ArgumentParser()
 ap.add_argument("--samples", type=int, default=24); ap.add_argument("--nodes", type=int, default=3000)
 ap.add_argument("--epochs", type=int, default=8); ap.add_argument("--folder", default="/tmp")
+ap.add_argument("--flow-loss", action="store_true", help="train with FlowLoss (continuity + vorticity terms) instead of GraphLoss")
 a = ap.parse_args()
 T = 20                                                        # time steps per simulation
 
@@ -24,7 +30,8 @@ train_config = gfd.nn.TrainConfig(
     name            = 'NsTwoScaleGNN_synthetic',
     folder          = a.folder,
     chk_interval    = 1,
-    training_loss   = gfd.nn.losses.GraphLoss(lambda_d=0.25),
+    training_loss   = (gfd.nn.losses.FlowLoss(lambda_d=0.25, terms={"div": 0.1, "vort": 0.05}, zero=("div",), edge_vectors="edge_attr")
+                       if a.flow_loss else gfd.nn.losses.GraphLoss(lambda_d=0.25)),
     validation_loss = gfd.nn.losses.GraphLoss(),
     epochs          = a.epochs,
     num_steps       = [1, 2, 3],

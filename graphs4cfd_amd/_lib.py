@@ -212,6 +212,8 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
     "g4c_mesh_derived": (C.c_int, [C.c_void_p, C.POINTER(g4c_mesh_derived_t), C.POINTER(g4c_derived_program_t), C.c_int64, C.c_void_p]),
+    "g4c_mesh_derived_adjoint": (C.c_int, [C.c_void_p, C.POINTER(g4c_derived_program_t), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_body_forces": (C.c_int, [C.POINTER(g4c_body_forces_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

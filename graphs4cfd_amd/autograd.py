@@ -570,6 +570,29 @@ def segment_reduce(src: Tensor, csr, mean: bool, act: int, src_act: int) -> Tens
     return _SegmentReduce.apply(src, csr, mean, act, src_act)
 
 
+# ------------------------------------------------------------------------------------- mesh derivatives
+class _MeshDerived(torch.autograd.Function):
+    """`MeshGradient.derived`: today's launch forward, its transpose (g4c_mesh_derived_adjoint) backward.  The map is linear in x and
+    the weights are constants: nothing is saved but the operator and the program."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, op, prog):
+        cur = _buf(op.n_nodes, int(prog.nd), op.g.device)
+        ops.mesh_derived(x.detach(), op.off, op.g, op.src, prog, cur)
+        ctx.op, ctx.prog, ctx.nf = op, prog, int(x.size(1))
+        return cur
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy: Tensor):
+        # (`derived(x).sum().backward()` hands over a stride-0 expanded tensor, a column slice a strided one: made dense first)
+        return ctx.op._adjoint(gy.contiguous(), ctx.prog, ctx.nf), None, None
+
+
+def mesh_derived(op, x: Tensor, prog) -> Tensor:
+    return _MeshDerived.apply(x, op, prog)
+
+
 # ------------------------------------------------------------------------------------- gathers / interpolation / projections
 # (gMuS-GNN and REMuS-GNN: nn/mugs_gnn.py restriction + knn_interpolate, nn/blocks.py:34-48,88-114,408-456).  Forward: the
 # inference kernels.  The adjoints are linear maps with static coefficients: an elementwise product (torch) followed, where rows

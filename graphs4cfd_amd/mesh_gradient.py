@@ -140,7 +140,11 @@ class MeshGradient:
     `gradient(x)` [N, F, dim]; `derived(x, names)` [N, nd] with names 'div' (Σ_a ∂_a of the velocity components), 'vort' (one column
     in 2-D, ∂₀v − ∂₁u; three in 3-D) and 'grad:<f>' (dim columns); `columns(names)` their labels; `degenerate` bool [N]: the nodes
     whose neighbours do not span the space — their derivatives are 0.  Works on any [N, F] float32 device tensor: `graph.target`'s
-    columns of a step as well as a prediction."""
+    columns of a step as well as a prediction.
+
+    `derived` (and `gradient`) of an x that requires grad is recorded for autograd: its backward is `adjoint(gy, names, nf)` [N, nf],
+    the transpose of the same linear map (`g4c_mesh_derived_adjoint`; the weights g are constants: no gradient reaches the mesh).  The
+    sender-side tables the adjoint walks are built on its first use."""
 
     def __init__(self, graph, power: int = 2, edge_vectors: Optional[torch.Tensor] = None):
         self.dim = check_mesh(graph, power, edge_vectors)
@@ -157,6 +161,7 @@ class MeshGradient:
         self.off, self.max_deg = csr.off, csr.max_deg
         self.g, self.src, degenerate = ops.mesh_gradient_weights(rel, csr, ep.row, power)
         self.degenerate = degenerate.bool()
+        self._adjoint_tables = None
 
     def columns(self, names) -> List[str]:
         return derived_columns(names, self.dim)
@@ -175,10 +180,51 @@ class MeshGradient:
         0 .. dim − 1; `field_scale` [F] (default ones) multiplies into the coefficients — it undoes an affine scaling of the fields
         (the offsets drop out of a gradient)."""
         x = self._x(x)
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd as _ag
+            return _ag.mesh_derived(self, x, self.program(names, int(x.size(1)), velocity, field_scale))
         prog = self.program(names, int(x.size(1)), velocity, field_scale)
         cur = torch.empty((self.n_nodes, int(prog.nd)), dtype=torch.float32, device=self.g.device)
         ops.mesh_derived(x, self.off, self.g, self.src, prog, cur)
         return cur
+
+    def _sender_side(self):
+        """(out_off, out_g, out_dst): the edges grouped by sender, ascending CSR position within a sender — the offsets of that
+        grouping, and the weights and receivers copied into its order.  Built on the first adjoint and kept: the plain forward pays
+        nothing."""
+        if self._adjoint_tables is None:
+            n_edges = int(self.src.numel())
+            deg = (self.off[1:] - self.off[:-1]).to(torch.int64)
+            dst = torch.repeat_interleave(torch.arange(self.n_nodes, dtype=torch.int32, device=self.off.device), deg, output_size=n_edges)
+            out = plan.gather_csr(self.src, self.n_nodes)
+            if out.perm is not None:          # (None: the senders are grouped already)
+                perm = out.perm.to(torch.int64)
+                self._adjoint_tables = (out.off, self.g.index_select(0, perm).contiguous(), dst.index_select(0, perm).contiguous())
+            else:
+                self._adjoint_tables = (out.off, self.g, dst.contiguous())
+        return self._adjoint_tables
+
+    def _gy(self, gy, nd: int) -> torch.Tensor:
+        if not torch.is_tensor(gy) or gy.dtype != torch.float32 or gy.dim() != 2 or tuple(gy.shape) != (self.n_nodes, nd):
+            raise ValueError(f"gy: expected a float32 tensor [{self.n_nodes}, {nd}] (one column per derived column), got "
+                             f"{getattr(gy, 'dtype', type(gy).__name__)} {tuple(getattr(gy, 'shape', ()))}")
+        if gy.device != self.g.device:
+            raise ValueError(f"gy: on '{gy.device}', the operator is on '{self.g.device}' (there is no CPU fallback)")
+        return gy.detach().contiguous()
+
+    def _adjoint(self, gy: torch.Tensor, prog, nf: int) -> torch.Tensor:
+        out_off, out_g, out_dst = self._sender_side()
+        return ops.mesh_derived_adjoint(gy, self.off, self.g, out_off, out_g, out_dst, prog, nf)
+
+    def adjoint(self, gy: torch.Tensor, names, nf: int, velocity=None, field_scale=None) -> torch.Tensor:
+        """[N, nf]: the transpose of `derived(·, names, velocity, field_scale)` on nf fields, applied to gy [N, nd] (float32; made
+        dense first) — for all x and gy, ⟨derived(x), gy⟩ = ⟨x, adjoint(gy)⟩ up to rounding.  One launch (`g4c_mesh_derived_adjoint`): a
+        gather over the edges a node SENDS, in a fixed order, no atomics.  A field `names` does not differentiate gets zeros."""
+        if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
+            raise ValueError(f"nf: expected the number of fields (>= 1), got {nf!r}")
+        terms = derived_terms(names, self.dim, nf, velocity, field_scale)
+        gy = self._gy(gy, len(terms))
+        return self._adjoint(gy, ops.derived_program(terms, nf, self.dim), nf)
 
     def gradient(self, x: torch.Tensor) -> torch.Tensor:
         """[N, F, dim]: ∂_a x[:, f]."""

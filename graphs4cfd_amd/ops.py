@@ -936,6 +936,44 @@ def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: T
     _lib.check(lib.g4c_mesh_derived(_lib.ptr(x), C.byref(d), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
 
 
+def mesh_derived_adjoint(gy: Tensor, off: Tensor, g: Tensor, out_off: Tensor, out_g: Tensor, out_dst: Tensor, program, nf: int,
+                         gx: Optional[Tensor] = None) -> Tensor:
+    """g4c_mesh_derived_adjoint: the transpose of `mesh_derived`'s map x[:, :nf] -> cur, applied to gy float32 [N, nd] (contiguous):
+    gx float32 [N, nf], every column written (a field the program does not differentiate gets zeros).  off int32 [N + 1] and g
+    float32 [E, dim] as for `mesh_derived`.  The sender side, built once per mesh: with perm the CSR positions grouped by SENDER,
+    ascending within a sender (`plan.gather_csr(src, N)`), out_off int32 [N + 1] its offsets, out_g float32 [E, dim] = g[perm] and
+    out_dst int32 [E] the receivers of those positions.  One thread per node, fp32, a fixed order (include/g4c.h), no atomics: the
+    same bits on every run.  `gx`: the tensor to write into (not gy)."""
+    what = "mesh_derived_adjoint"
+    _mesh_arg(what, g, "g", torch.float32, dim=2)
+    n_edges, dim = int(g.size(0)), int(g.size(1))
+    if dim not in (2, 3):
+        raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
+    if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
+        raise ValueError(f"nf: {what}: expected a number of fields >= 1, got {nf!r}")
+    prog = derived_program(program, nf, dim)
+    nd = int(prog.nd)
+    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
+    if int(gy.size(1)) != nd:
+        raise ValueError(f"gy: {what}: expected [n_nodes, {nd}] (one column per column of the program), got shape {tuple(gy.shape)}")
+    n_nodes = int(gy.size(0))
+    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, out_g, "out_g", torch.float32, shape=(n_edges, dim))
+    _mesh_arg(what, out_dst, "out_dst", torch.int32, shape=(n_edges,))
+    if gx is not None:
+        _mesh_arg(what, gx, "gx", torch.float32, shape=(n_nodes, nf))
+        if gx is gy or (gx.numel() and gy.numel() and gx.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
+            raise ValueError(f"gx: {what}: gx shares its storage with gy")
+    dev = _mesh_devices(what, ("gy", gy), ("off", off), ("g", g), ("out_off", out_off), ("out_g", out_g), ("out_dst", out_dst), ("gx", gx))
+    if gx is None:
+        gx = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_mesh_derived_adjoint(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(g), _lib.ptr(off), _lib.ptr(out_g), _lib.ptr(out_dst),
+                                            _lib.ptr(out_off), n_nodes, n_edges, _lib.ptr(gx), _lib.stream_handle(dev)))
+    return gx
+
+
 def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: Tensor, arm: Tensor, cur: Tensor, *, pcol: int,
                 ucol: int = 0, vcol: int = 1, mu: float = 0.0, p_scale: float = 1.0, p_shift: float = 0.0, u_scale: float = 1.0,
                 v_scale: float = 1.0, off: Optional[Tensor] = None, g: Optional[Tensor] = None, src: Optional[Tensor] = None,

@@ -608,6 +608,29 @@ int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd);
 int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d /*host*/, const g4c_derived_program_t *prog /*host*/, int64_t n_nodes,
                      void *stream);
 
+/* g4c_mesh_derived_adjoint — the transpose of g4c_mesh_derived's map x -> cur (the map is linear: its backward).  With
+ * G_i[f][a] = Σ_{e in in(i)} g[e][a] (x[src_e, f] − x[i, f]) and cur[i, c] = Σ_k coef[c][k] G_i[row(c, k)], for gy[n_nodes, nd] (dense):
+ *   H_i[f][a] = Σ_{(c, k): row(c, k) = (f, a)} coef[c][k] gy[i, c]
+ *   gx[j, f]  = Σ_{e: src_e = j} Σ_a g[e][a] H_{dst_e}[f][a]  −  Σ_{e in in(j)} Σ_a g[e][a] H_j[f][a]
+ * A scatter to the senders, taken as a gather: ONE thread per node j walks j's out-edges through a sender-side CSR built once per
+ * mesh.  With perm the CSR positions e grouped by sender, ASCENDING within a sender (a stable grouping of src), and dst[e] the
+ * receiver of position e (`off` expanded): out_off[n_nodes + 1] the offsets of that grouping, out_g[E, dim] = g[perm[q]] and
+ * out_dst[E] = dst[perm[q]] the weights and receivers copied into its order — so the walk streams them as the forward streams g and
+ * src, and only the receiver's row of gy is a gather.  fp32, no contraction, every product rounded before it is added, in this order:
+ *   H_i[f][a] = +0, then += coef[c][k] · gy[i, c] over the terms that pick (f, a), in program order (c ascending, then k);
+ *   acc[f] = +0; over j's out-edges q = out_off[j] .. (ascending CSR position), i = out_dst[q]: for every field f the program names,
+ *   for a = 0 .. dim − 1: acc[f] += out_g[q][a] · H_i[f][a]; then over j's own in-edges e = off[j] .. in CSR order, for a = 0 ..
+ *   dim − 1: acc[f] −= g[e][a] · H_j[f][a].
+ * No atomics, no reduction across threads: the bits are a function of the data alone, and a numpy.float32 loop reproduces them.
+ * EVERY column of gx[n_nodes, nf] (dense) is written: a field the program does not differentiate gets +0.  n_edges == 0 still zero-fills
+ * gx (the tables may then be NULL); n_nodes == 0 launches nothing.  The tables are trusted as g4c_mesh_derived trusts src: out_dst in
+ * [0, n_nodes), both offset arrays ascending from 0 to n_edges.
+ * G4C_EINVAL before any launch: null pointers, negative sizes, gx == gy (or overlapping), a field or axis out of range, a column
+ * without terms; G4C_EUNSUPPORTED: dim not 2 or 3, nd > 8, more than 3 terms, more than 8 distinct fields. */
+int g4c_mesh_derived_adjoint(const float *gy, const g4c_derived_program_t *prog /*host*/, int32_t dim, int32_t nf, const float *g,
+                             const int32_t *off, const float *out_g, const int32_t *out_dst, const int32_t *out_off,
+                             int64_t n_nodes, int64_t n_edges, float *gx, void *stream);
+
 /* g4c_body_forces (csrc/body_forces.hip) — the force of a 2-D flow on the bodies it passes, once per step: AFTER the forward and
  * BEFORE the step's closing launch (it reads the step index t = step[0] and never writes it; with step == NULL, t = t0).  A body's
  * wall is a closed polygon of W_b items, each a mesh node with an area vector (the outward normal times the length lumped at the

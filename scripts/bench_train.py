@@ -2,6 +2,9 @@
 MuS-GNN on a synthetic mesh, on the GPU (fused forward, recompute backward: autograd.py) and — on a bounded sample — with
 the oracle on the host cores (torch autograd over the op-for-op restatement = what the reference's fit() executes).
 Usage: python scripts/bench_train.py [--nodes 100000] [--model NsThreeScaleGNN] [--steps 10] [--cpu-steps 1] [--phases] [--mixed [--saved-bf16]]
+       [--flow-loss]
+--flow-loss: the same run with FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) on the GPU (a continuity penalty and a vorticity-matching
+term through the differentiable mesh gradient: two `derived` launches and their adjoints per step; the host-side sample keeps GraphLoss).
 --mixed: the same step in mixed precision (what fit(mixed_precision=True) selects: every matrix product on bf16-rounded operands).
 --saved-bf16 (with --mixed): the rows the forward keeps for the backward as bf16 (TrainConfig(saved_activations="bf16"))."""
 import argparse, json, os, sys, time
@@ -18,6 +21,7 @@ ap.add_argument("--cpu-steps", type=int, default=1)
 ap.add_argument("--phases", action="store_true", help="HIP-event time per phase of the backward pass (one extra step)")
 ap.add_argument("--mixed", action="store_true", help="mixed-precision training: set_mlp_precision('bf16') + set_train_precision('bf16')")
 ap.add_argument("--saved-bf16", action="store_true", help="with --mixed: saved activations as bf16 (set_train_precision('bf16', saved='bf16'))")
+ap.add_argument("--flow-loss", action="store_true", help="FlowLoss(0.25, terms={'div': 0.1, 'vort': 0.05}) instead of GraphLoss(0.25) on the GPU")
 a = ap.parse_args()
 if a.saved_bf16 and not a.mixed:
     ap.error("--saved-bf16 needs --mixed")
@@ -37,7 +41,7 @@ g_cpu.target = torch.randn(a.nodes, nf)
 torch.manual_seed(0)
 model = getattr(gfd.nn, a.model)(arch=arch, device=dev)
 g = g_cpu.clone().to(dev)
-crit = gfd.nn.GraphLoss(lambda_d=0.25)
+crit = gfd.nn.FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) if a.flow_loss else gfd.nn.GraphLoss(lambda_d=0.25)
 opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)        # (as GNN.fit does on the GPU)
 model.train()
 
@@ -76,11 +80,11 @@ with torch.no_grad():
         model.forward(g, 0)
     torch.cuda.synchronize()
     inf = (time.perf_counter() - t0) / a.steps
-out = {"workload": f"{a.model} H=128 training step (forward + GraphLoss + backward + Adam) on a {a.nodes}-node synthetic 2D mesh",
+out = {"workload": f"{a.model} H=128 training step (forward + {type(crit).__name__} + backward + Adam) on a {a.nodes}-node synthetic 2D mesh",
        "gpu_ms_per_training_step": 1e3 * dt, "gpu_training_steps_per_s": 1 / dt, "gpu_ms_forward_recorded": 1e3 * fwd,
        "gpu_ms_forward_inference_eager": 1e3 * inf, "gpu_peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30,
        "loss": float(loss), "mlp_precision": gfd.ops.mlp_precision(), "train_precision": gfd.ops.train_precision(),
-       "saved_precision": gfd.ops.saved_precision()}
+       "saved_precision": gfd.ops.saved_precision(), "loss_function": type(crit).__name__}
 if a.phases:
     from graphs4cfd_amd import autograd as A
     A.PROFILE = {}
