@@ -218,6 +218,8 @@ _SIGNATURES = {
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_sample_points_adjoint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                            C.c_void_p]),
     "g4c_tracer_advance": (C.c_int, [C.POINTER(g4c_tracer_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_snapshot_mean": (C.c_int, [C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_snapshot_gram_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),

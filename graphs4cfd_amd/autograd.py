@@ -593,6 +593,27 @@ def mesh_derived(op, x: Tensor, prog) -> Tensor:
     return _MeshDerived.apply(x, op, prog)
 
 
+# ------------------------------------------------------------------------------------- off-node samples
+class _SamplePoints(torch.autograd.Function):
+    """`PointSampler.sample`: today's launch forward, its transpose (g4c_sample_points_adjoint) backward.  The map is linear in x and
+    the coefficients are constants: nothing is saved but the sampler."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, sampler):
+        ctx.sampler = sampler
+        return ops.sample_points(x.detach(), sampler._idx, sampler._coef)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy: Tensor):
+        # (`sample(x).sum().backward()` hands over a stride-0 expanded tensor, a column slice a strided one: made dense first)
+        return ctx.sampler._adjoint(gy.contiguous()), None
+
+
+def sample_points(sampler, x: Tensor) -> Tensor:
+    return _SamplePoints.apply(x, sampler)
+
+
 # ------------------------------------------------------------------------------------- gathers / interpolation / projections
 # (gMuS-GNN and REMuS-GNN: nn/mugs_gnn.py restriction + knn_interpolate, nn/blocks.py:34-48,88-114,408-456).  Forward: the
 # inference kernels.  The adjoints are linear maps with static coefficients: an elementwise product (torch) followed, where rows

@@ -4,7 +4,10 @@
 //                       normal matrix inverted in closed form, and per neighbour one fp32 coefficient c_j with
 //                       value(q) = sum_j c_j x[idx_j];
 //   g4c_sample_points   once per step (or once per target): that sum for every point and column, written to `cur` and, on a slot
-//                       step, to a strided slot of a step-major series.
+//                       step, to a strided slot of a step-major series;
+//   g4c_sample_points_adjoint  the transpose of that sum (its backward): the scatter from points to nodes taken as a gather — one
+//                       thread per (node, chunk of columns) walks the table entries that name its node, through a node-side table
+//                       built once per set of points, in ascending table position.
 // A point's sum is taken by ONE thread over its neighbours nearest first, in fp32 without contraction: the bits are a function of
 // the data alone.  The tables are j-major [k, P]: lane p reads consecutive addresses.  Plain loads and stores, no atomics.
 #include "g4c_common.h"
@@ -99,6 +102,49 @@ __global__ __launch_bounds__(PS_THREADS) void sample_points_kernel(const float *
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ adjoint
+// gx[i, f] = Σ_{q in list(i)} in_coef[q] · gy[in_pt[q], f]: one thread per (node, chunk of PS_CHUNK columns), items chunk-major — item =
+// chunk * N + i — so the lanes of a wave hold consecutive nodes of one chunk, and their lists lie one after the other in the tables.
+// A node's list is walked by ONE thread in ascending position, whatever its length: a node that very many points use (a raster far
+// finer than the mesh) makes its thread the launch's last; there is no second summation order for it.
+__global__ __launch_bounds__(PS_THREADS) void sample_points_adjoint_kernel(const float *__restrict__ gy, const int *__restrict__ in_off,
+                                                                          const int *__restrict__ in_pt, const float *__restrict__ in_coef,
+                                                                          int F, long long n_nodes, float *__restrict__ gx) {
+    const int n_chunks = (F + PS_CHUNK - 1) / PS_CHUNK;
+    const long long items = n_nodes * n_chunks;
+    const long long stride = (long long)gridDim.x * PS_THREADS;
+    for (long long it = (long long)blockIdx.x * PS_THREADS + threadIdx.x; it < items; it += stride) {
+#pragma clang fp contract(off)
+        const long long chunk = n_chunks == 1 ? 0 : it / n_nodes;
+        const long long i = it - chunk * n_nodes;
+        const int c0 = (int)chunk * PS_CHUNK;
+        const int width = F - c0 < PS_CHUNK ? F - c0 : PS_CHUNK;
+        float acc[PS_CHUNK];
+#pragma unroll
+        for (int f = 0; f < PS_CHUNK; ++f) acc[f] = 0.f;
+        if (in_off) {          // (no points: no tables, every row is +0)
+            const int q0 = in_off[i], q1 = in_off[i + 1];
+            // (four entries at a time: their point, coefficient and row loads are in flight together — the adds keep the order)
+#pragma unroll 4
+            for (int q = q0; q < q1; ++q) {
+                const float c = in_coef[q];
+                const float *row = gy + (long long)in_pt[q] * F + c0;
+#pragma unroll
+                for (int f = 0; f < PS_CHUNK; ++f) {
+                    if (f < width) {
+                        const float pr = c * row[f];
+                        acc[f] = acc[f] + pr;
+                    }
+                }
+            }
+        }
+        const long long o = i * F + c0;
+#pragma unroll
+        for (int f = 0; f < PS_CHUNK; ++f)
+            if (f < width) gx[o + f] = acc[f];
+    }
+}
+
 }  // namespace
 
 extern "C" int g4c_sample_weights(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
@@ -144,5 +190,29 @@ extern "C" int g4c_sample_points(const float *x, const g4c_sample_points_t *sp, 
     long long blocks = (items + PS_THREADS - 1) / PS_THREADS;
     if (blocks > PS_MAX_BLOCKS) blocks = PS_MAX_BLOCKS;
     sample_points_kernel<<<dim3((unsigned)blocks), dim3(PS_THREADS), 0, s>>>(x, d, (long long)n_points);
+    return g4c::check_launch(me);
+}
+
+extern "C" int g4c_sample_points_adjoint(const float *gy, const int32_t *in_off, const int32_t *in_pt, const float *in_coef, int32_t nf,
+                                         int64_t n_nodes, int64_t n_points, float *gx, void *stream) {
+    const char *me = "g4c_sample_points_adjoint";
+    G4C_REQUIRE(n_nodes >= 0 && n_points >= 0 && nf >= 1, G4C_EINVAL, "%s: bad sizes n_nodes=%lld n_points=%lld nf=%d", me,
+                (long long)n_nodes, (long long)n_points, nf);
+    if (n_nodes == 0) return G4C_OK;
+    G4C_REQUIRE(gx, G4C_EINVAL, "%s: null pointer", me);
+    // (without points the tables and gy are empty and may have no address: gx is zero-filled)
+    G4C_REQUIRE(n_points == 0 || (gy && in_off && in_pt && in_coef), G4C_EINVAL, "%s: null pointer", me);
+    if (n_points > 0) {          // gx [n_nodes, nf] and gy [n_points, nf] must not share a byte: a thread reads rows of gy that other threads' rows of gx would cover
+        const char *a = (const char *)gy, *b = (const char *)gx;
+        const long long na = (long long)n_points * nf * 4ll, nb = (long long)n_nodes * nf * 4ll;
+        G4C_REQUIRE(a + na <= b || b + nb <= a, G4C_EINVAL, "%s: gx aliases gy", me);
+    }
+    g4c::DeviceGuard on_device(gx);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_points == 0) in_off = nullptr;
+    const long long items = (long long)n_nodes * ((nf + PS_CHUNK - 1) / PS_CHUNK);
+    long long blocks = (items + PS_THREADS - 1) / PS_THREADS;
+    if (blocks > PS_MAX_BLOCKS) blocks = PS_MAX_BLOCKS;
+    sample_points_adjoint_kernel<<<dim3((unsigned)blocks), dim3(PS_THREADS), 0, s>>>(gy, in_off, in_pt, in_coef, nf, (long long)n_nodes, gx);
     return g4c::check_launch(me);
 }

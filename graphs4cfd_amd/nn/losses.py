@@ -138,3 +138,136 @@ class FlowLoss(nn.Module):
                 loss = loss + w * d[:, c0:c1].square().mean()
                 c0 = c1
         return loss
+
+
+class SampleLoss(nn.Module):
+    """`GraphLoss(lambda_d)` plus the error at points that are no nodes — sparse, off-node observations: a PIV window, a wake rake, a
+    few taps (new functionality — the reference has none):
+
+        node_weight · GraphLoss(lambda_d)(graph, pred, target) + weight · mean over the kept points and the chosen fields of (S·pred − ref)²
+
+    S is `gfd.PointSampler(graph, points, k, power)`: the moving-least-squares interpolation from the nodes to `points` [P, dim].  The
+    points are FIXED in the coordinates of `graph.pos` as the loss sees it — sensors in the lab frame: an augmentation that moves or
+    scales the mesh does not move the points.  `fields`: the columns of the prediction that were observed (default: all; PIV gives
+    no pressure), F' of them.  ref is S·target when `values` is None (a loss weighted towards a region: no data beyond the node
+    targets), otherwise `getattr(graph, values)[:, F'·t : F'·(t + 1)]` — observations [P, F'·T] per graph, for output step t = `step`
+    (`takes_step`: `Trainer` passes step=t; `values=` without a step is a ValueError).  `max_distance` drops the points farther than
+    that from their nearest node (inside a body, outside the domain); with no point kept the term is 0.
+
+    `node_weight == 0` skips `GraphLoss` (training on observations alone); `weight == 0` launches nothing, builds nothing and is
+    node_weight · GraphLoss bit for bit.  The sample is differentiable (`g4c_sample_points_adjoint` in the backward).
+
+    A collated batch: graphs of a batch usually overlap in space, so every graph gets a search of its own over its node range of
+    `graph.batch` (contiguous, ascending), its neighbours are offset by the range's start, and the tables are joined along P,
+    graph-major, into one sampler (`PointSampler.from_tables`); observations collate along dim 0 by `collate`'s rule (`values` must
+    not contain 'index') into [B·P, F'·T], the same order.  The sampler is kept (one entry) while `graph.pos` and `graph.batch` are
+    the same tensor objects, unmodified — `Trainer.train_epoch` calls the loss once per output step of the same batch; `builds`
+    counts the samplers built.  HIP device only."""
+
+    takes_step = True
+
+    def __init__(self, points, lambda_d=0, weight=1.0, node_weight=1.0, values=None, fields=None, k=None, power=2, max_distance=None):
+        super().__init__()
+        from ..point_sampler import MAX_K
+        if not torch.is_tensor(points) or not points.dtype.is_floating_point or points.dim() != 2 or int(points.size(1)) not in (2, 3):
+            raise ValueError(f"points: expected a floating-point tensor [P, 2] or [P, 3], got "
+                             f"{getattr(points, 'dtype', type(points).__name__)} {tuple(getattr(points, 'shape', ()))}")
+        if points.device.type == "cpu" and not bool(torch.isfinite(points).all()):
+            raise ValueError("points: a coordinate that is not finite")
+        self.lambda_d = _number(lambda_d, "lambda_d")
+        self.weight = _number(weight, "weight", "a finite weight >= 0")
+        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
+        if values is not None and (not isinstance(values, str) or not values or "index" in values):
+            raise ValueError(f"values: expected None or the name of a graph attribute holding [P, F'·T] observations (without 'index' in "
+                             f"it: such attributes collate along the last dimension), got {values!r}")
+        if fields is not None:
+            try:
+                fields = tuple(fields)
+            except TypeError:
+                raise ValueError(f"fields: expected distinct column numbers >= 0, got {fields!r}") from None
+            if not fields or any(isinstance(f, bool) or not isinstance(f, int) or f < 0 for f in fields) or len(set(fields)) != len(fields):
+                raise ValueError(f"fields: expected distinct column numbers >= 0, got {fields!r}")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K):
+            raise ValueError(f"k: expected None or an integer 1 <= k <= {MAX_K}, got {k!r}")
+        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+            raise ValueError(f"power: expected 0, 1 or 2 (a neighbour weighs |d|^-power), got {power!r}")
+        if max_distance is not None:
+            max_distance = _number(max_distance, "max_distance", "None or a finite distance >= 0")
+        self.base = GraphLoss(lambda_d)
+        self.points, self.values, self.fields, self.k, self.power, self.max_distance = points.detach(), values, fields, k, power, max_distance
+        self._cache = None          # (pos, its version, batch, its version, sampler, kept mask or None, kept count)
+        self.builds = 0             # samplers built so far (a batch seen again costs none)
+
+    def sampler(self, graph):
+        """(the `PointSampler` of `graph` — of all its graphs, when it is a batch —, the bool [P] mask of the kept points or None for
+        all, their number): the cached ones while graph.pos and graph.batch are the objects they were built from, unmodified
+        (identity and `_version`, never an address)."""
+        from ..graph import Graph
+        from ..point_sampler import PointSampler
+        pos, batch = getattr(graph, "pos", None), getattr(graph, "batch", None)
+        if not torch.is_tensor(pos):
+            raise ValueError("graph: SampleLoss needs graph.pos")
+        hit = self._cache
+        if (hit is not None and hit[0] is pos and hit[1] == pos._version and hit[2] is batch
+                and (batch is None or hit[3] == batch._version)):
+            return hit[4:]
+        n = int(pos.size(0))
+        counts = [n] if batch is None else torch.bincount(batch).tolist()
+        if sum(counts) != n:
+            raise ValueError(f"graph: graph.batch names {sum(counts)} nodes, graph.pos has {n}")
+        if len(counts) == 1:
+            s = PointSampler(graph, self.points, k=self.k, power=self.power)
+        else:
+            parts, a = [], 0
+            for c in counts:          # (contiguous ranges: `collate` numbers the nodes graph after graph)
+                one = PointSampler(Graph(pos=pos[a:a + c]), self.points, k=self.k, power=self.power)
+                parts.append((one._idx + a, one._coef, one.distance, one.degenerate))
+                a += c
+            idx, coef, distance, degenerate = (torch.cat(t, dim=-1).contiguous() for t in zip(*parts))
+            s = PointSampler.from_tables(idx, coef, n, points=self.points.repeat(len(counts), 1), distance=distance, degenerate=degenerate)
+        mask, kept = None, s.n_points
+        if self.max_distance is not None:
+            mask = s.distance <= self.max_distance
+            kept = int(mask.sum())
+        self._cache = (pos, pos._version, batch, None if batch is None else batch._version, s, mask, kept)
+        self.builds += 1
+        return s, mask, kept
+
+    def forward(self, graph, pred, target, step=None):
+        loss = None
+        if self.node_weight > 0:
+            loss = self.base(graph, pred, target)
+            if self.node_weight != 1.0:
+                loss = self.node_weight * loss
+        if self.weight == 0:
+            return pred.sum() * 0.0 if loss is None else loss
+        if self.values is not None and step is None:
+            raise ValueError("step: SampleLoss(values=...) needs the output step: call loss(graph, pred, target, step=t)")
+        s, mask, kept = self.sampler(graph)
+        cols = list(range(int(pred.size(1)))) if self.fields is None else list(self.fields)
+        if max(cols) >= int(pred.size(1)):
+            raise ValueError(f"fields: column {max(cols)} of a prediction with {int(pred.size(1))} columns")
+        nfp = len(cols)
+        if kept == 0:
+            return pred.sum() * 0.0 if loss is None else loss
+        if self.values is None:
+            d = s.sample(pred - target)          # S is linear: S·pred − S·target in one launch
+            if self.fields is not None:
+                d = d[:, cols]
+        else:
+            obs = getattr(graph, self.values, None)
+            if not torch.is_tensor(obs) or obs.dim() != 2 or int(obs.size(0)) != s.n_points:
+                raise ValueError(f"values: graph.{self.values}: expected observations [{s.n_points}, F'·T], got "
+                                 f"{tuple(getattr(obs, 'shape', ()))}")
+            t = int(step)
+            if t < 0 or nfp * (t + 1) > int(obs.size(1)):
+                raise ValueError(f"step: {t}: graph.{self.values} holds {int(obs.size(1))} columns, {nfp} per step")
+            sp = s.sample(pred)
+            if self.fields is not None:
+                sp = sp[:, cols]
+            d = sp - obs[:, nfp * t: nfp * (t + 1)].to(sp.dtype)
+        sq = d.square()
+        if mask is not None:
+            sq = sq * mask[:, None].to(sq.dtype)
+        term = self.weight * (sq.sum() / (kept * nfp))
+        return term if loss is None else loss + term

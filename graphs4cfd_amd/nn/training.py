@@ -131,6 +131,14 @@ class Trainer:
         nf = self.model.num_fields
         return data.target[:, nf * t: nf * (t + 1)]
 
+    @staticmethod
+    def _loss(loss_fn, data, pred, target, t: int):
+        """A loss that declares `takes_step = True` (gfd.nn.SampleLoss: observations per output step) also gets step=t; every other
+        loss is called with (graph, pred, target) alone."""
+        if getattr(loss_fn, "takes_step", False):
+            return loss_fn(data, pred, target, step=t)
+        return loss_fn(data, pred, target)
+
     def train_epoch(self, epoch: int):
         m, cfg, n_out = self.model, self.cfg, self.curriculum.n_out
         loss_fn, clip = cfg['training_loss'], cfg['grad_clip']
@@ -144,7 +152,7 @@ class Trainer:
                 if t:
                     data.field = m.shift_and_replace(data.field, pred.detach())
                 pred = m.forward(data, t)
-                loss = loss_fn(data, pred, self._targets(data, t))
+                loss = self._loss(loss_fn, data, pred, self._targets(data, t), t)
                 loss.backward()
                 loss_sum += loss.item() / n_out
                 norm_sum += m.grad_norm2() / n_out
@@ -172,7 +180,7 @@ class Trainer:
                     if t:
                         data.field = m.shift_and_replace(data.field, pred)
                     pred = m.forward(data, t)
-                    total += loss_fn(data, pred, self._targets(data, t)).item() / n_out
+                    total += self._loss(loss_fn, data, pred, self._targets(data, t), t).item() / n_out
                 batches += 1
         return total / max(batches, 1)
 

@@ -1155,6 +1155,42 @@ def sample_points(x: Tensor, idx: Tensor, coef: Tensor, cur: Optional[Tensor] = 
     return cur
 
 
+def sample_points_adjoint(gy: Tensor, in_off: Tensor, in_pt: Tensor, in_coef: Tensor, n_nodes: int, out: Optional[Tensor] = None) -> Tensor:
+    """g4c_sample_points_adjoint: the transpose of `sample_points`' map x -> cur, applied to gy float32 [P, nf] (contiguous): gx float32
+    [n_nodes, nf], every element written (a node no point uses gets +0).  The node side, built once per set of points
+    (`PointSampler` does it): with the entries of the j-major [k, P] tables grouped by the node they name, ascending flat position
+    within a node (`plan.gather_csr(idx.reshape(-1), n_nodes)`), in_off int32 [n_nodes + 1] the offsets of that grouping, in_pt int32
+    [k·P] the point (position mod P) and in_coef float32 [k·P] the coefficient of each entry, in its order.  One thread per (node,
+    chunk of 4 columns), fp32, a fixed order (include/g4c.h), no atomics: the same bits on every run.  The index values are never
+    read here.  `out`: the tensor to write into (not gy)."""
+    what = "sample_points_adjoint"
+    if isinstance(n_nodes, bool) or not isinstance(n_nodes, int) or n_nodes < 0:
+        raise ValueError(f"n_nodes: {what}: expected a number of nodes >= 0, got {n_nodes!r}")
+    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
+    n_points, nf = int(gy.size(0)), int(gy.size(1))
+    if nf < 1:
+        raise ValueError(f"gy: {what}: expected [n_points, >= 1], got shape {tuple(gy.shape)}")
+    _mesh_arg(what, in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, in_pt, "in_pt", torch.int32, dim=1)
+    n_entries = int(in_pt.size(0))
+    if n_entries >= 2 ** 31:
+        raise NotImplementedError(f"in_pt: {what}: {n_entries} table entries do not fit the int32 offsets")
+    if (n_entries > 0) != (n_points > 0) or (n_points > 0 and n_entries % n_points):
+        raise ValueError(f"in_pt: {what}: expected [k * {n_points}] (k entries per point), got shape {tuple(in_pt.shape)}")
+    _mesh_arg(what, in_coef, "in_coef", torch.float32, shape=(n_entries,))
+    if out is not None:
+        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nf))
+        if out is gy or (out.numel() and gy.numel() and out.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
+            raise ValueError(f"out: {what}: out shares its storage with gy")
+    dev = _mesh_devices(what, ("gy", gy), ("in_off", in_off), ("in_pt", in_pt), ("in_coef", in_coef), ("out", out))
+    if out is None:
+        out = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_sample_points_adjoint(_lib.ptr(gy), _lib.ptr(in_off), _lib.ptr(in_pt), _lib.ptr(in_coef), nf, n_nodes, n_points,
+                                             _lib.ptr(out), _lib.stream_handle(dev)))
+    return out
+
+
 def _tracer_nodes(what, x, name, n_nodes):
     """A node tensor of tracer_advance: float32 [n_nodes, >= 1], rows of unit stride, any leading dimension -> its leading dimension."""
     if not torch.is_tensor(x) or x.dtype != torch.float32:

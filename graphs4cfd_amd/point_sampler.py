@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, plan
 
 MAX_K = _lib.SAMPLE_MAX_K
 DEFAULT_K = {2: 6, 3: 10}
@@ -78,7 +78,11 @@ class PointSampler:
     space (Shepard's weights there: exact on constants only).  `PointSampler.line` and `PointSampler.grid` build rakes and rasters.
 
     The search is NOT periodic: a point near the seam of a periodic mesh uses the neighbours on its own side; the fit is then
-    one-sided, and still exact on linear fields."""
+    one-sided, and still exact on linear fields.
+
+    `sample` of an x that requires grad is recorded for autograd: its backward is `adjoint(gy)` [N, F], the transpose of the same
+    linear map (`g4c_sample_points_adjoint`; the coefficients are constants: no gradient reaches the points or the mesh).  The
+    node-side tables the adjoint walks are built on its first use.  `PointSampler.from_tables` takes tables fitted elsewhere."""
 
     def __init__(self, graph, points: torch.Tensor, k: Optional[int] = None, power: int = 2):
         self.dim, self.k = check_points(graph, points, k, power)
@@ -98,6 +102,38 @@ class PointSampler:
             self._idx = torch.empty((self.k, 0), dtype=torch.int32, device=dev)
         self._coef, self.distance, degenerate = ops.sample_weights(pos32, self.points, self._idx, power)
         self.degenerate = degenerate.bool()
+        self._adjoint_tables = None
+
+    @classmethod
+    def from_tables(cls, idx: torch.Tensor, coef: torch.Tensor, n_nodes: int, points: Optional[torch.Tensor] = None,
+                    distance: Optional[torch.Tensor] = None, degenerate: Optional[torch.Tensor] = None) -> "PointSampler":
+        """A sampler from given tables, without a search: `idx` int32 and `coef` float32, both j-major [k, P] (neighbour j of point
+        p in row j; `sampler.idx.t()` of another sampler), contiguous and on the HIP device, over `n_nodes` node rows — the
+        concatenation of the samplers of a batch's graphs, or a fit computed elsewhere.  Every idx must be a row 0 .. n_nodes − 1:
+        the values are not read here.  `points` [P, dim], `distance` [P] and `degenerate` bool [P] are kept as given (None: the
+        attribute is None, and `dim`, `power` are None)."""
+        if isinstance(n_nodes, bool) or not isinstance(n_nodes, int) or n_nodes < 0:
+            raise ValueError(f"n_nodes: expected a number of nodes >= 0, got {n_nodes!r}")
+        k, n_points = ops._sample_tables("PointSampler.from_tables", idx, coef)
+        if idx.device.type != "cuda" or coef.device != idx.device:
+            raise ValueError(f"idx: PointSampler runs on a HIP device only, idx is on '{idx.device}' and coef on '{coef.device}' "
+                             "(there is no CPU fallback)")
+        if n_points and k > n_nodes:
+            raise ValueError(f"idx: {k} neighbours of {n_nodes} nodes")
+        if points is not None and (not torch.is_tensor(points) or points.dim() != 2 or int(points.size(0)) != n_points):
+            raise ValueError(f"points: expected a tensor [{n_points}, dim], got {tuple(getattr(points, 'shape', ()))}")
+        for name, t in (("distance", distance), ("degenerate", degenerate)):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (n_points,)):
+                raise ValueError(f"{name}: expected a tensor [{n_points}], got {tuple(getattr(t, 'shape', ()))}")
+        s = cls.__new__(cls)
+        s.dim = None if points is None else int(points.size(1))
+        s.k, s.power, s.n_nodes, s.shape = k, None, n_nodes, None
+        s.points = None if points is None else points.detach().to(idx.device, torch.float32).contiguous()
+        s._idx, s._coef = idx, coef.detach()
+        s.distance = None if distance is None else distance.detach().to(idx.device, torch.float32)
+        s.degenerate = None if degenerate is None else degenerate.detach().to(idx.device).bool()
+        s._adjoint_tables = None
+        return s
 
     @classmethod
     def line(cls, graph, a: Sequence[float], b: Sequence[float], n: int, **kw) -> "PointSampler":
@@ -143,7 +179,7 @@ class PointSampler:
 
     @property
     def n_points(self) -> int:
-        return int(self.points.size(0))
+        return int(self._idx.size(1))
 
     @property
     def idx(self) -> torch.Tensor:
@@ -156,11 +192,57 @@ class PointSampler:
         return self._coef.t()
 
     def sample(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """[P, F]: x [N, F] (float32, on the device, rows of unit stride, any leading dimension) at the points — one launch."""
+        """[P, F]: x [N, F] (float32, on the device, rows of unit stride, any leading dimension) at the points — one launch.  Of an x
+        that requires grad (with grad enabled) the result carries a `grad_fn` whose backward is `adjoint`; `out=` is then refused."""
         if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or int(x.size(0)) != self.n_nodes or int(x.size(1)) < 1:
             raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, F], got {getattr(x, 'dtype', type(x).__name__)} "
                              f"{tuple(getattr(x, 'shape', ()))}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            if out is not None:
+                raise NotImplementedError("PointSampler.sample(out=...) is an inference-only path (the input requires grad)")
+            from . import autograd as _ag
+            return _ag.sample_points(self, x)
         return ops.sample_points(x, self._idx, self._coef, out)
+
+    def _node_side(self):
+        """(in_off, in_pt, in_coef): the entries of the j-major tables grouped by the node they name, ascending flat position j·P + p
+        within a node — the offsets of that grouping, and the points (position mod P) and coefficients copied into its order.  Built
+        on the first adjoint and kept: the plain forward pays nothing."""
+        if self._adjoint_tables is None:
+            n_entries = self.k * self.n_points
+            if n_entries > 2 ** 31 - 1:
+                raise NotImplementedError(f"PointSampler.adjoint: k·P = {self.k} · {self.n_points} table entries do not fit the int32 offsets")
+            flat = self._idx.reshape(-1)
+            if n_entries == 0:          # (no points: every list is empty)
+                dev = flat.device
+                self._adjoint_tables = (torch.zeros(self.n_nodes + 1, dtype=torch.int32, device=dev), flat,
+                                        torch.empty(0, dtype=torch.float32, device=dev))
+                return self._adjoint_tables
+            csr = plan.gather_csr(flat, self.n_nodes)
+            if csr.perm is not None:
+                perm = csr.perm.to(torch.int64)
+                in_pt = (csr.perm % self.n_points).to(torch.int32).contiguous()
+                in_coef = self._coef.reshape(-1).index_select(0, perm).contiguous()
+            else:          # (None: the entries are grouped already)
+                in_pt = (torch.arange(n_entries, dtype=torch.int32, device=flat.device) % self.n_points).contiguous()
+                in_coef = self._coef.reshape(-1).contiguous()
+            self._adjoint_tables = (csr.off, in_pt, in_coef)
+        return self._adjoint_tables
+
+    def _adjoint(self, gy: torch.Tensor) -> torch.Tensor:
+        in_off, in_pt, in_coef = self._node_side()
+        return ops.sample_points_adjoint(gy, in_off, in_pt, in_coef, self.n_nodes)
+
+    def adjoint(self, gy: torch.Tensor) -> torch.Tensor:
+        """[N, F]: the transpose of `sample`, applied to gy [P, F] (float32; made dense first) — for all x and gy, ⟨sample(x), gy⟩ =
+        ⟨x, adjoint(gy)⟩ up to rounding.  One launch (`g4c_sample_points_adjoint`): a gather over the table entries that name a node,
+        in a fixed order, no atomics.  A node no point uses gets zeros."""
+        if not torch.is_tensor(gy) or gy.dtype != torch.float32 or gy.dim() != 2 or int(gy.size(0)) != self.n_points or int(gy.size(1)) < 1:
+            raise ValueError(f"gy: expected a float32 tensor [{self.n_points}, F], got {getattr(gy, 'dtype', type(gy).__name__)} "
+                             f"{tuple(getattr(gy, 'shape', ()))}")
+        if gy.device != self._idx.device:
+            raise ValueError(f"gy: on '{gy.device}', the sampler is on '{self._idx.device}' (there is no CPU fallback)")
+        return self._adjoint(gy.detach().contiguous())
 
     def __repr__(self):
         return (f"PointSampler(points={self.n_points}, nodes={self.n_nodes}, dim={self.dim}, k={self.k}, power={self.power}"

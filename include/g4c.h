@@ -716,6 +716,24 @@ typedef struct g4c_sample_points {
 } g4c_sample_points_t;
 int g4c_sample_points(const float *x, const g4c_sample_points_t *s /*host*/, int64_t n_nodes, int64_t n_points, void *stream);
 
+/* g4c_sample_points_adjoint — the transpose of g4c_sample_points' map x -> cur (the map is linear with constant coefficients: its
+ * backward).  Forward: y[p, f] = Σ_j coef[j, p] · x[idx[j, p], f].  Adjoint of gy[n_points, nf] (dense):
+ *   gx[i, f] = Σ_{q in list(i)} in_coef[q] · gy[in_pt[q], f],   list(i) = in_off[i] .. in_off[i + 1] − 1
+ * A scatter from the points to the nodes, taken as a gather through a node-side table built once per set of points: list(i) holds the
+ * entries of the j-major [k, P] tables whose idx is i, in ASCENDING flat position j · P + p (slot first, then point — a stable grouping
+ * of the flattened idx); in_off[n_nodes + 1] its offsets, in_pt[k · P] = position mod P the point of each entry and in_coef[k · P] its
+ * coefficient, both copied into that order, so a walk streams them and only the point's row of gy is a gather.
+ * fp32, no contraction, in this order: acc[f] = +0; for q ascending over list(i): acc[f] = acc[f] + (in_coef[q] · gy[in_pt[q], f]),
+ * the product rounded before it is added.  One thread per (node, chunk of 4 columns), at most 1024 workgroups of 256, the items dealt
+ * gid, gid + grid, ...; plain loads and stores, no atomics, nothing passes between threads: the bits are a function of the data alone
+ * and a numpy.float32 loop reproduces them.  A node's list is walked by one thread whatever its length.
+ * EVERY element of gx[n_nodes, nf] (dense) is written: a node that no point uses gets +0 (sign bit clear).  n_points == 0 still
+ * zero-fills gx (gy and the tables may then be NULL); n_nodes == 0 launches nothing.  The tables are trusted as g4c_sample_points trusts
+ * idx: in_pt in [0, n_points), in_off ascending from 0 to at most 2^31 − 1 entries.
+ * G4C_EINVAL before any launch: negative sizes, nf < 1, a null pointer, gx overlapping gy (by their sizes). */
+int g4c_sample_points_adjoint(const float *gy, const int32_t *in_off, const int32_t *in_pt, const float *in_coef, int32_t nf,
+                              int64_t n_nodes, int64_t n_points, float *gx, void *stream);
+
 /* Lagrangian tracers (csrc/tracer.hip): massless particles carried by a velocity that lives at the nodes.  g4c_tracer_advance moves
  * every particle one step in one launch — one thread per particle, at most 1024 workgroups of 256, the particles dealt gid, gid + grid,
  * ..., plain loads and stores, no atomics — and may sit inside a captured step: AFTER the forward, BEFORE the step's closing launch
