@@ -6,7 +6,7 @@ The NsCircle HDF5 file is replaced by a synthetic array in the same record layou
 code | u v p per time step], NaN-padded to the largest mesh): decaying travelling waves on random point clouds — there is no
 network / h5py here; with the real file pass path="NsCircle.h5" instead of data=.
 
-    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss]
+    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss | --force-loss]
 
 --flow-loss trains with gfd.nn.FlowLoss: GraphLoss plus a continuity penalty (the divergence of the predicted velocity) and a
 vorticity-matching term, both through the differentiable least-squares mesh gradient (gfd.MeshGradient).  The mesh is periodic in y,
@@ -17,6 +17,12 @@ so the operator is built from the wrapped `edge_attr`, not from differences of `
 the wake (values=None: no data beyond the node targets — the error simply weighs more where the raster is), through the differentiable
 point sampler (gfd.PointSampler).  The raster is fixed in the coordinates of `graph.pos`: the random rotations and flips below move the
 mesh under it, not the raster with the mesh — with real sensor data (values=) leave such augmentations out.
+
+--force-loss trains with gfd.nn.ForceLoss: GraphLoss plus the error of the pressure drag and lift on the cylinder and of the surface pressure
+round it, through the differentiable body forces (gfd.BodyForces): the wall is `graph.bound == 4`, one body per graph of the batch, ordered
+by angle round the mean of its nodes (the synthetic records mark a small disc of nodes; in the real file the code marks the cylinder's
+surface).  The wall moves with the mesh, so the augmentations stay.  mu = 0: the pressure force alone — on this mesh, periodic in y, a viscous
+term would take edge_vectors="edge_attr" as --flow-loss does.  The loads are in the scaled units of the fields (values=None: those of the target).
 """
 import argparse, math, os, sys
 import torch
@@ -28,9 +34,10 @@ ap.add_argument("--samples", type=int, default=24); ap.add_argument("--nodes", t
 ap.add_argument("--epochs", type=int, default=8); ap.add_argument("--folder", default="/tmp")
 ap.add_argument("--flow-loss", action="store_true", help="train with FlowLoss (continuity + vorticity terms) instead of GraphLoss")
 ap.add_argument("--sample-loss", action="store_true", help="train with SampleLoss (GraphLoss plus the error on a raster over the wake) instead of GraphLoss")
+ap.add_argument("--force-loss", action="store_true", help="train with ForceLoss (GraphLoss plus the error of the loads on the cylinder) instead of GraphLoss")
 a = ap.parse_args()
-if a.flow_loss and a.sample_loss:
-    ap.error("--flow-loss and --sample-loss are two runs")
+if a.flow_loss + a.sample_loss + a.force_loss > 1:
+    ap.error("--flow-loss, --sample-loss and --force-loss are separate runs")
 T = 20                                                        # time steps per simulation
 # a 64 x 32 raster over the wake of the cylinder at (1, 0.5), in the coordinates of graph.pos
 WAKE = torch.stack(torch.meshgrid(torch.linspace(1.2, 3.0, 64), torch.linspace(0.1, 0.9, 32), indexing="ij"), -1).reshape(-1, 2)
@@ -42,6 +49,7 @@ train_config = gfd.nn.TrainConfig(
     chk_interval    = 1,
     training_loss   = (gfd.nn.losses.FlowLoss(lambda_d=0.25, terms={"div": 0.1, "vort": 0.05}, zero=("div",), edge_vectors="edge_attr")
                        if a.flow_loss else gfd.nn.losses.SampleLoss(WAKE, lambda_d=0.25, weight=1.0) if a.sample_loss
+                       else gfd.nn.losses.ForceLoss(lambda_d=0.25, weight=1.0, pressure=2, wall={"pressure": 0.5}) if a.force_loss
                        else gfd.nn.losses.GraphLoss(lambda_d=0.25)),
     validation_loss = gfd.nn.losses.GraphLoss(),
     epochs          = a.epochs,

@@ -132,6 +132,14 @@ class g4c_body_forces_t(C.Structure):
                 ("arm", C.c_void_p), ("stats", C.c_void_p), ("cur", C.c_void_p), ("wall", C.c_void_p), ("max_steps", C.c_int32)]
 
 
+class g4c_body_forces_adjoint_t(C.Structure):
+    _fields_ = [("gF", C.c_void_p), ("gwall", C.c_void_p), ("nf", C.c_int32), ("pcol", C.c_int32), ("ucol", C.c_int32), ("vcol", C.c_int32),
+                ("mu", C.c_double), ("p_scale", C.c_double), ("u_scale", C.c_double), ("v_scale", C.c_double), ("g", C.c_void_p),
+                ("off", C.c_void_p), ("item_body", C.c_void_p), ("area", C.c_void_p), ("unit", C.c_void_p), ("arm", C.c_void_p),
+                ("own_off", C.c_void_p), ("own_item", C.c_void_p), ("in_off", C.c_void_p), ("in_item", C.c_void_p), ("in_g", C.c_void_p),
+                ("hw", C.c_void_p), ("gx", C.c_void_p)]
+
+
 SAMPLE_MAX_K = 16                                  # G4C_SAMPLE_MAX_K: most neighbours of a sample point (the grid search's limit)
 
 
@@ -215,6 +223,7 @@ _SIGNATURES = {
     "g4c_mesh_derived_adjoint": (C.c_int, [C.c_void_p, C.POINTER(g4c_derived_program_t), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_body_forces": (C.c_int, [C.POINTER(g4c_body_forces_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_body_forces_adjoint": (C.c_int, [C.POINTER(g4c_body_forces_adjoint_t), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),

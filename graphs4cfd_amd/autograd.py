@@ -614,6 +614,33 @@ def sample_points(sampler, x: Tensor) -> Tensor:
     return _SamplePoints.apply(x, sampler)
 
 
+# ------------------------------------------------------------------------------------- body forces
+class _BodyForces(torch.autograd.Function):
+    """`BodyForces.forces` (wall False) and `BodyForces.wall` (wall True): today's launch forward, the transpose of its linear part
+    (g4c_body_forces_adjoint) backward.  The map is affine in x and the geometry is constant: nothing is saved but the operator and
+    the number of columns of x."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, op, wall: bool):
+        ctx.op, ctx.wall, ctx.nf = op, wall, int(x.size(1))
+        return op._wall(x.detach()) if wall else op._forces(x.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy: Tensor):
+        # (`forces(x).sum().backward()` hands over a stride-0 expanded tensor, a column slice a strided one: made dense first)
+        gy = gy.contiguous()
+        return (ctx.op._adjoint(None, gy, ctx.nf) if ctx.wall else ctx.op._adjoint(gy, None, ctx.nf)), None, None
+
+
+def body_forces(op, x: Tensor) -> Tensor:
+    return _BodyForces.apply(x, op, False)
+
+
+def body_wall(op, x: Tensor) -> Tensor:
+    return _BodyForces.apply(x, op, True)
+
+
 # ------------------------------------------------------------------------------------- gathers / interpolation / projections
 # (gMuS-GNN and REMuS-GNN: nn/mugs_gnn.py restriction + knn_interpolate, nn/blocks.py:34-48,88-114,408-456).  Forward: the
 # inference kernels.  The adjoints are linear maps with static coefficients: an elementwise product (torch) followed, where rows

@@ -7,14 +7,18 @@ at the node: it points out of the body into the fluid; every operation is exact 
 within 29 binades of each other, and the areas of a loop then sum to exactly zero —, ds = |area[w]|, the unit normal unit[w] = area[w] / ds and the arm[w] = pos − centre.  With the pressure P and the
 stress s = mu (∇u + ∇uᵀ) at the node — the velocity gradient is `gfd.MeshGradient`'s —, the pressure force is Σ −P area, the viscous
 force Σ s · area, the moments Σ arm × traction.  One launch (`g4c_body_forces`, csrc/body_forces.hip) forms them: one workgroup per
-body, fp64 sums in a fixed order, so the bits are a function of the data alone.  The geometry is built once per mesh, in fp64."""
+body, fp64 sums in a fixed order, so the bits are a function of the data alone.  The geometry is built once per mesh, in fp64.
+
+The map from the fields to the loads is affine with constant geometry; `BodyForces.adjoint` applies the transpose of its linear part
+(`g4c_body_forces_adjoint`), and `forces` / `wall` of a tensor that requires grad are recorded for autograd with it as their backward
+(`gfd.nn.ForceLoss` trains against drag, lift and the wall loads)."""
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, plan
 from .mesh_gradient import MeshGradient, check_mesh
 
 WALL = 4                    # the reference's code of a wall node in graph.bound
@@ -201,7 +205,11 @@ class BodyForces:
     their moments about the centre; `wall(x)` [W, 2] float32: the surface pressure and the wall shear at every wall item;
     `history(x, n)` [n, B, 6]: the same for the n steps held in x [N, >= nf n] (a target; nf: the fields of a step).  `items` [W]
     the node rows, body after body (`body_offsets` [B + 1]), `area`, `unit`, `arm` [W, 2] float64, `angle` [W] — what Cp(θ) is plotted
-    against —, `centre` [B, 2], `n_bodies`, `gradient`."""
+    against —, `centre` [B, 2], `n_bodies`, `gradient`.
+
+    `forces` and `wall` of an x that requires grad are recorded for autograd: their backward is `adjoint(gF, gwall, nf)` [N, nf], the
+    transpose of the map's linear part (no gradient reaches the mesh or the wall geometry); `history` is not differentiable.  The
+    node-side tables the adjoint walks are built on its first use."""
 
     def __init__(self, graph, nodes=None, bodies=None, loops=None, centre=None, *, mu: float = 0.0, pressure: Optional[int] = None,
                  velocity=None, scale=None, shift=None, gradient: Optional[MeshGradient] = None, power: int = 2,
@@ -221,6 +229,7 @@ class BodyForces:
         if gradient is None and self.mu != 0:
             gradient = MeshGradient(graph, power, edge_vectors)
         self.gradient = gradient
+        self._adjoint_tables = None
 
     @property
     def n_items(self) -> int:
@@ -253,23 +262,111 @@ class BodyForces:
         return cur
 
     def forces(self, x: torch.Tensor) -> torch.Tensor:
-        """[B, 6] float64: (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv) of the fields x [N, F] (float32, rows of unit stride)."""
+        """[B, 6] float64: (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv) of the fields x [N, F] (float32, rows of unit stride).  Of an x that requires
+        grad (with grad enabled) the result carries a `grad_fn` whose backward is `adjoint(gF=...)`."""
         x = self._x(x, self.fields_needed())
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd as _ag
+            return _ag.body_forces(self, x)
+        return self._forces(x)
+
+    def _forces(self, x: torch.Tensor) -> torch.Tensor:
         stats = torch.zeros((1, self.n_bodies, _lib.FORCES_NSUM), dtype=torch.float64, device=self.area.device)
         self._launch(x, stats, 0, 0)
         return stats[0]
 
     def wall(self, x: torch.Tensor) -> torch.Tensor:
-        """[W, 2] float32: the surface pressure and the wall shear of the fields x [N, F] at every wall item."""
+        """[W, 2] float32: the surface pressure and the wall shear of the fields x [N, F] at every wall item.  Of an x that requires
+        grad (with grad enabled) the result carries a `grad_fn` whose backward is `adjoint(gwall=...)`."""
         x = self._x(x, self.fields_needed())
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd as _ag
+            return _ag.body_wall(self, x)
+        return self._wall(x)
+
+    def _wall(self, x: torch.Tensor) -> torch.Tensor:
         stats = torch.zeros((1, self.n_bodies, _lib.FORCES_NSUM), dtype=torch.float64, device=self.area.device)
         wall = torch.empty((self.n_items, 2), dtype=torch.float32, device=self.area.device)
         self._launch(x, stats, 0, 0, wall=wall)
         return wall
 
+    def _node_side(self) -> dict:
+        """The node-side tables of the adjoint (include/g4c.h): item_body [W]; own_off [N + 1] / own_item [W], the items grouped by
+        their node, ascending; and, for mu != 0, in_off [N + 1] / in_item [Q] / in_g [Q, 2]: the pairs (item w, in-edge e of its node)
+        grouped by the sender of e, ascending CSR position e, then w, within a sender, the weights copied into that order.  Built on
+        the first adjoint and kept: the plain forward pays nothing."""
+        if self._adjoint_tables is None:
+            n_items, n = self.n_items, self.n_nodes
+            viscous = self.mu != 0
+            if viscous and n_items * max(int(self.gradient.max_deg), 0) > 2 ** 31 - 1:
+                raise NotImplementedError(f"BodyForces.adjoint: up to {n_items} · {int(self.gradient.max_deg)} (items · in-edges) list "
+                                          f"entries do not fit the int32 offsets")
+            dev = self._item32.device
+            sizes = (self.body_offsets[1:] - self.body_offsets[:-1]).to(torch.int64)
+            item_body = torch.repeat_interleave(torch.arange(self.n_bodies, dtype=torch.int32, device=dev), sizes, output_size=n_items)
+            own = plan.gather_csr(self._item32, n)
+            own_item = own.perm if own.perm is not None else torch.arange(n_items, dtype=torch.int32, device=dev)
+            tabs = dict(item_body=item_body.contiguous(), own_off=own.off, own_item=own_item.contiguous())
+            if viscous:
+                gr = self.gradient
+                off = gr.off.to(torch.int64)
+                first = off[self.items]
+                deg = off[self.items + 1] - first
+                q = int(deg.sum())
+                w = torch.repeat_interleave(torch.arange(n_items, dtype=torch.int64, device=dev), deg, output_size=q)
+                e = first[w] + (torch.arange(q, dtype=torch.int64, device=dev) - (torch.cumsum(deg, 0) - deg)[w])
+                order = torch.argsort(e, stable=True)          # ascending CSR position; a node that is an item twice: ascending w
+                w, e = w[order], e[order]
+                sender = gr.src.index_select(0, e).contiguous() if q else torch.zeros(0, dtype=torch.int32, device=dev)
+                if q:
+                    by = plan.build_csr(sender, n, dev)          # (a stable grouping; not cached: `sender` lives only here)
+                    if by.perm is not None:
+                        perm = by.perm.to(torch.int64)
+                        w, e = w[perm], e[perm]
+                    in_off = by.off
+                else:
+                    in_off = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+                tabs.update(in_off=in_off, in_item=w.to(torch.int32).contiguous(),
+                            in_g=gr.g.index_select(0, e).contiguous() if q else torch.zeros((0, 2), dtype=torch.float32, device=dev))
+            self._adjoint_tables = tabs
+        return self._adjoint_tables
+
+    def _adjoint(self, gF, gwall, nf: int, out=None, hw=None) -> torch.Tensor:
+        t = self._node_side()
+        c = self.constants()
+        c.pop("p_shift")
+        gr = self.gradient if self.mu != 0 else None
+        return ops.body_forces_adjoint(gF, gwall, t["item_body"], self.area, self.unit, self.arm, t["own_off"], t["own_item"], self.n_bodies,
+                                       nf, **c, g=None if gr is None else gr.g, off=None if gr is None else gr.off, in_off=t.get("in_off"),
+                                       in_item=t.get("in_item"), in_g=t.get("in_g"), hw=hw, out=out)
+
+    def adjoint(self, gF: Optional[torch.Tensor] = None, gwall: Optional[torch.Tensor] = None, nf: Optional[int] = None) -> torch.Tensor:
+        """[N, nf] float32: the transpose of the linear part of `forces` and `wall`, applied to gF [B, 6] (float64) and gwall [W, 2]
+        (float32), either may be None (zeros); both are made dense first.  For all x,
+
+            ⟨forces(x) − forces(0), gF⟩ + ⟨wall(x) − wall(0), gwall⟩ = ⟨x, adjoint(gF, gwall)⟩   up to rounding
+
+        (forces(0) and wall(0) are what `shift` alone gives).  nf defaults to the length of `scale`, else to `fields_needed()`.  Two
+        small launches (`g4c_body_forces_adjoint`): per item, then a gather per node in a fixed order, no atomics.  A node that
+        neither is a wall node nor sends to one gets zeros."""
+        if nf is None:
+            nf = len(self.scale) if self.scale is not None else self.fields_needed()
+        if not _integer(nf) or nf < self.fields_needed():
+            raise ValueError(f"nf: {nf!r} fields, the operator reads field {self.fields_needed() - 1}")
+        for name, t, dtype, shape in (("gF", gF, torch.float64, (self.n_bodies, _lib.FORCES_NSUM)),
+                                      ("gwall", gwall, torch.float32, (self.n_items, 2))):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected a {str(dtype).replace('torch.', '')} tensor {list(shape)}, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+            if t.device != self.area.device:
+                raise ValueError(f"{name}: on '{t.device}', the operator is on '{self.area.device}' (there is no CPU fallback)")
+        return self._adjoint(None if gF is None else gF.detach().contiguous(), None if gwall is None else gwall.detach().contiguous(), nf)
+
     def history(self, x: torch.Tensor, n: int, nf: Optional[int] = None) -> torch.Tensor:
         """[n, B, 6] float64: `forces` of the n steps held in x [N, >= nf n] — a target: step t in the columns nf t .. nf (t + 1).
-        nf defaults to the length of `scale`, else to x's columns // n.  n launches."""
+        nf defaults to the length of `scale`, else to x's columns // n.  n launches.  Not differentiable: no gradient reaches x."""
         if not _integer(n) or n < 1:
             raise ValueError(f"n: expected a number of steps >= 1, got {n!r}")
         if nf is None:

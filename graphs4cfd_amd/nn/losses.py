@@ -271,3 +271,195 @@ class SampleLoss(nn.Module):
             sq = sq * mask[:, None].to(sq.dtype)
         term = self.weight * (sq.sum() / (kept * nfp))
         return term if loss is None else loss + term
+
+
+class ForceLoss(nn.Module):
+    """`GraphLoss(lambda_d)` plus the error of the loads on the bodies in the flow — what a load cell and pressure taps measure (new
+    functionality — the reference has none):
+
+        node_weight · GraphLoss(lambda_d)(graph, pred, target)
+          + weight · mean over the bodies and `components` of ((F(pred) − F_ref) / force_scale)²
+          + wall["pressure"] · mean_w (P_w(pred) − P_w(target))² + wall["shear"] · mean_w (shear_w(pred) − shear_w(target))²
+
+    F is `gfd.BodyForces(graph, ...).forces`: per body the totals 'fx' = Fp_x + Fv_x, 'fy' and 'm' (the moment about the centre), kept
+    in float64 until the mean and then cast to the prediction's dtype.  F_ref is forces(target) when `values` is None, otherwise
+    `getattr(graph, values)[:, C·t : C·(t + 1)]` — measured loads [B, C·T] per graph, C = len(components), for output step t = `step`
+    (`takes_step`: `Trainer` passes step=t; `values=` without a step is a ValueError).  The wall term (Cp(θ) and the wall shear, from
+    `BodyForces.wall`) exists when `wall` gives one of its two weights.  `mu`, `pressure`, `velocity`, `scale`, `shift`, `centre`,
+    `power` mean what they mean in `BodyForces`; `edge_vectors` is None or the name of a graph attribute holding the unscaled, wrapped
+    [E, 2] edge vectors (a periodic mesh).
+
+    The wall on a collated batch: `nodes` is None (`graph.bound == 4`) or the name of a per-node graph attribute [N], bool or integer
+    (non-zero: a wall node); `bodies` is None — one body per graph of `graph.batch`: a wall node's label is its batch number — or the
+    name of a per-node integer attribute whose value at a wall node, combined with the batch number, labels its body.  The gradient
+    operator is built on the batch as it is (a collated batch is block-diagonal).  The operator is kept (one entry) while the batch's
+    `pos`, `edge_index` (when mu != 0), `batch` and the tensors the nodes, bodies and vectors came from are the same tensor objects,
+    unmodified (identity and `_version`, never an address) — `Trainer.train_epoch` calls the loss once per output step of the same
+    batch; `builds` counts the operators built.
+
+    Both loads are differentiable (`g4c_body_forces_adjoint` in the backward).  With `weight == 0` and no live wall weight nothing is
+    built or launched and the value is node_weight · GraphLoss bit for bit; `node_weight == 0` skips `GraphLoss` (training on loads
+    alone).  HIP device only."""
+
+    takes_step = True
+    COMPONENTS = {"fx": (0, 2), "fy": (1, 3), "m": (4, 5)}          # the columns of BodyForces.forces each total adds
+
+    def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, mu=0.0, pressure=None, velocity=None, scale=None, shift=None,
+                 components=("fx", "fy"), force_scale=1.0, wall=None, values=None, nodes=None, bodies=None, centre=None, power=2,
+                 edge_vectors=None):
+        super().__init__()
+        self.lambda_d = _number(lambda_d, "lambda_d")
+        self.weight = _number(weight, "weight", "a finite weight >= 0")
+        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
+        if isinstance(mu, bool) or not isinstance(mu, (int, float)) or not math.isfinite(mu):
+            raise ValueError(f"mu: expected a finite number (the dynamic viscosity), got {mu!r}")
+        if pressure is not None and (isinstance(pressure, bool) or not isinstance(pressure, int) or pressure < 0):
+            raise ValueError(f"pressure: expected a field number, got {pressure!r}")
+        if velocity is not None:
+            try:
+                velocity = tuple(velocity)
+            except TypeError:
+                raise ValueError(f"velocity: expected 2 field numbers, got {velocity!r}") from None
+            if len(velocity) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in velocity):
+                raise ValueError(f"velocity: expected 2 field numbers, got {velocity!r}")
+        factors = {}
+        for name, v in (("scale", scale), ("shift", shift)):
+            if v is not None:
+                try:
+                    v = [float(q) for q in (v.tolist() if torch.is_tensor(v) else v)]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name}: expected one number per field, got {v!r}") from None
+                if not v or not all(math.isfinite(q) for q in v):
+                    raise ValueError(f"{name}: expected one finite number per field, got {v!r}")
+            factors[name] = v
+        if isinstance(components, str):
+            components = (components,)
+        try:
+            components = tuple(components)
+        except TypeError:
+            raise ValueError(f"components: expected distinct names of 'fx', 'fy', 'm', got {components!r}") from None
+        if not components or any(c not in self.COMPONENTS for c in components) or len(set(components)) != len(components):
+            raise ValueError(f"components: expected distinct names of 'fx', 'fy', 'm', got {components!r}")
+        if isinstance(force_scale, bool) or not isinstance(force_scale, (int, float)) or not math.isfinite(force_scale) or force_scale <= 0:
+            raise ValueError(f"force_scale: expected a finite number > 0, got {force_scale!r}")
+        if wall is not None:
+            if not isinstance(wall, dict) or not set(wall) <= {"pressure", "shear"}:
+                raise TypeError(f"wall: expected None or a dict with the weights 'pressure' and / or 'shear', got {wall!r}")
+        wall = dict(wall or {})
+        self.wall_pressure = _number(wall.get("pressure", 0.0), "wall['pressure']", "a finite weight >= 0")
+        self.wall_shear = _number(wall.get("shear", 0.0), "wall['shear']", "a finite weight >= 0")
+        if values is not None and (not isinstance(values, str) or not values or "index" in values):
+            raise ValueError(f"values: expected None or the name of a graph attribute holding [B, C·T] measured loads (without 'index' in "
+                             f"it: such attributes collate along the last dimension), got {values!r}")
+        for name, v in (("nodes", nodes), ("bodies", bodies), ("edge_vectors", edge_vectors)):
+            if v is not None and (not isinstance(v, str) or not v):
+                raise TypeError(f"{name}: expected None or the name of a graph attribute, got {v!r}")
+        if centre is not None:
+            try:
+                c = torch.as_tensor(centre, dtype=torch.float64).reshape(-1, 2)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"centre: expected [B, 2] numbers, got {centre!r}") from None
+            if not c.numel() or not bool(torch.isfinite(c).all()):
+                raise ValueError(f"centre: expected [B, 2] finite numbers, got {centre!r}")
+        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+            raise ValueError(f"power: expected 0, 1 or 2 (an edge weighs |d|^-power), got {power!r}")
+        self.base = GraphLoss(lambda_d)
+        self.mu, self.pressure, self.velocity, self.scale, self.shift = float(mu), pressure, velocity, factors["scale"], factors["shift"]
+        self.components, self.force_scale, self.wall, self.values = components, float(force_scale), wall, values
+        self.nodes, self.bodies, self.centre, self.power, self.edge_vectors = nodes, bodies, centre, power, edge_vectors
+        self._cache = None          # ([(tensor, its version), ...], BodyForces)
+        self.builds = 0             # operators built so far (a batch seen again costs none)
+
+    def _attr(self, graph, arg, name, n):
+        t = getattr(graph, name, None)
+        if not torch.is_tensor(t) or t.dtype.is_floating_point or t.is_complex() or t.numel() != n:
+            raise ValueError(f"{arg}: graph.{name}: expected a per-node {'bool or ' if arg == 'nodes' else ''}integer tensor [{n}], got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        return t
+
+    def operator(self, graph):
+        """The `BodyForces` of `graph` — of all its graphs, when it is a batch —: the cached one while the tensors it was built from
+        are the same objects, unmodified (identity and `_version`: an address says nothing, the allocator hands a freed batch's to the
+        next one)."""
+        from ..body_forces import WALL, BodyForces
+        pos = getattr(graph, "pos", None)
+        if not torch.is_tensor(pos) or pos.dim() != 2:
+            raise ValueError("graph: ForceLoss needs graph.pos [N, 2]")
+        n = int(pos.size(0))
+        batch = getattr(graph, "batch", None)
+        if self.nodes is None:
+            flag = getattr(graph, "bound", None)
+            if not torch.is_tensor(flag) or flag.numel() != n:
+                raise ValueError("nodes: the graph has no `bound` [N] to take the wall nodes (bound == 4) from, and no nodes= names an attribute")
+        else:
+            flag = self._attr(graph, "nodes", self.nodes, n)
+        label = None if self.bodies is None else self._attr(graph, "bodies", self.bodies, n)
+        if label is not None and label.dtype == torch.bool:
+            raise ValueError(f"bodies: graph.{self.bodies}: expected a per-node integer tensor [{n}], got torch.bool")
+        vec = None
+        if self.edge_vectors is not None:
+            vec = getattr(graph, self.edge_vectors, None)
+            if not torch.is_tensor(vec):
+                raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
+        ei = getattr(graph, "edge_index", None) if self.mu != 0 else None
+        key = [t for t in (pos, ei, batch, flag, label, vec)]
+        hit = self._cache
+        if hit is not None and len(hit[0]) == len(key) and all(a is t and (t is None or v == t._version) for (a, v), t in zip(hit[0], key)):
+            return hit[1]
+        if batch is not None and (not torch.is_tensor(batch) or batch.numel() != n):
+            raise ValueError(f"graph: graph.batch names {getattr(batch, 'numel', lambda: 0)()} nodes, graph.pos has {n}")
+        mask = (flag.reshape(-1) == WALL) if self.nodes is None else (flag.reshape(-1) != 0)
+        rows = torch.nonzero(mask).flatten()
+        labels = None
+        if batch is not None or label is not None:
+            labels = torch.zeros_like(rows) if batch is None else batch.reshape(-1)[rows].long()
+            if label is not None:
+                own = label.reshape(-1)[rows].long()
+                if own.numel():
+                    lo = int(own.min())
+                    labels = labels * (int(own.max()) - lo + 1) + (own - lo)
+        op = BodyForces(graph, nodes=rows, bodies=labels, centre=self.centre, mu=self.mu, pressure=self.pressure, velocity=self.velocity,
+                        scale=self.scale, shift=self.shift, power=self.power, edge_vectors=vec)
+        self._cache = ([(t, None if t is None else t._version) for t in key], op)
+        self.builds += 1
+        return op
+
+    def _totals(self, sums):
+        return torch.stack([sums[:, self.COMPONENTS[c][0]] + sums[:, self.COMPONENTS[c][1]] for c in self.components], dim=1)
+
+    def forward(self, graph, pred, target, step=None):
+        loss = None
+        if self.node_weight > 0:
+            loss = self.base(graph, pred, target)
+            if self.node_weight != 1.0:
+                loss = self.node_weight * loss
+        on_wall = self.wall_pressure > 0 or self.wall_shear > 0
+        if self.weight == 0 and not on_wall:
+            return pred.sum() * 0.0 if loss is None else loss
+        if self.weight > 0 and self.values is not None and step is None:
+            raise ValueError("step: ForceLoss(values=...) needs the output step: call loss(graph, pred, target, step=t)")
+        op = self.operator(graph)
+        if self.weight > 0:
+            if self.values is None:
+                with torch.no_grad():
+                    ref = self._totals(op.forces(target.detach()))
+            else:
+                obs, nc, t = getattr(graph, self.values, None), len(self.components), int(step)
+                if not torch.is_tensor(obs) or obs.dim() != 2 or int(obs.size(0)) != op.n_bodies:
+                    raise ValueError(f"values: graph.{self.values}: expected measured loads [{op.n_bodies}, C·T], got "
+                                     f"{tuple(getattr(obs, 'shape', ()))}")
+                if t < 0 or nc * (t + 1) > int(obs.size(1)):
+                    raise ValueError(f"step: {t}: graph.{self.values} holds {int(obs.size(1))} columns, {nc} per step")
+                ref = obs[:, nc * t: nc * (t + 1)].to(torch.float64)
+            d = (self._totals(op.forces(pred)) - ref) / self.force_scale
+            term = (self.weight * d.square().mean()).to(pred.dtype)
+            loss = term if loss is None else loss + term
+        if on_wall:
+            with torch.no_grad():
+                ref = op.wall(target.detach())
+            d = op.wall(pred) - ref
+            for w, k in ((self.wall_pressure, 0), (self.wall_shear, 1)):
+                if w > 0:
+                    term = w * d[:, k].square().mean()
+                    loss = term if loss is None else loss + term
+        return loss

@@ -1057,6 +1057,88 @@ def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: T
     return cur
 
 
+def body_forces_adjoint(gF: Optional[Tensor], gwall: Optional[Tensor], item_body: Tensor, area: Tensor, unit: Tensor, arm: Tensor,
+                        own_off: Tensor, own_item: Tensor, n_bodies: int, nf: int, *, pcol: int, ucol: int = 0, vcol: int = 1,
+                        mu: float = 0.0, p_scale: float = 1.0, u_scale: float = 1.0, v_scale: float = 1.0, g: Optional[Tensor] = None,
+                        off: Optional[Tensor] = None, in_off: Optional[Tensor] = None, in_item: Optional[Tensor] = None,
+                        in_g: Optional[Tensor] = None, hw: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """g4c_body_forces_adjoint: the transpose of the linear part of `body_forces`' map x -> (stats [B, 6], wall [W, 2]), applied to
+    gF float64 [B, 6] and gwall float32 [W, 2] (contiguous; either may be None: zeros): gx float32 [N, nf], every element written (+0
+    where nothing arrives).  area / unit / arm float64 [W, 2] and the constants as for `body_forces` (p_shift drops out).  The node
+    side, built once per wall (`gfd.BodyForces` does it): item_body int32 [W] the body of every item; own_off int32 [N + 1] / own_item
+    int32 [W] the items grouped by their node, ascending; and, for mu != 0, off int32 [N + 1] / g float32 [E, 2] of the gradient and
+    in_off int32 [N + 1] / in_item int32 [Q] / in_g float32 [Q, 2]: the (item, in-edge of its node) pairs grouped by the edge's sender,
+    ascending CSR position then item within a sender, with the weights copied into that order.  Two launches (per item into the scratch
+    hw float32 [W, 5], then one thread per node), fp32 sums in a fixed order (include/g4c.h), no atomics: the same bits on every run.
+    `out`: the tensor to write into; `hw`: the scratch to use."""
+    what = "body_forces_adjoint"
+    for name, v in (("n_bodies", n_bodies), ("nf", nf)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < (1 if name == "nf" else 0):
+            raise ValueError(f"{name}: {what}: expected an integer >= {1 if name == 'nf' else 0}, got {v!r}")
+    for name, v in (("mu", mu), ("p_scale", p_scale), ("u_scale", u_scale), ("v_scale", v_scale)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name}: {what}: expected a number, got {v!r}")
+    viscous = float(mu) != 0.0
+    for name, c in (("pcol", pcol),) + ((("ucol", ucol), ("vcol", vcol)) if viscous else ()):
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < nf:
+            raise ValueError(f"{name}: {what}: expected a column 0 .. {nf - 1}, got {c!r}")
+    if viscous and len({pcol, ucol, vcol}) != 3:
+        raise ValueError(f"ucol: {what}: pcol = {pcol}, ucol = {ucol} and vcol = {vcol} must be distinct")
+    _mesh_arg(what, item_body, "item_body", torch.int32, dim=1)
+    n_items = int(item_body.size(0))
+    for name, tab in (("area", area), ("unit", unit), ("arm", arm)):
+        _mesh_arg(what, tab, name, torch.float64, shape=(n_items, 2))
+    _mesh_arg(what, own_off, "own_off", torch.int32, dim=1)
+    n_nodes = int(own_off.size(0)) - 1
+    if n_nodes < 0:
+        raise ValueError(f"own_off: {what}: expected [n_nodes + 1], got shape {tuple(own_off.shape)}")
+    _mesh_arg(what, own_item, "own_item", torch.int32, shape=(n_items,))
+    if gF is not None:
+        _mesh_arg(what, gF, "gF", torch.float64, shape=(n_bodies, _lib.FORCES_NSUM))
+    if gwall is not None:
+        _mesh_arg(what, gwall, "gwall", torch.float32, shape=(n_items, 2))
+    n_entries = 0
+    if viscous:
+        for name, tab in (("g", g), ("off", off), ("in_off", in_off), ("in_item", in_item), ("in_g", in_g)):
+            if tab is None:
+                raise ValueError(f"{name}: {what}: mu != 0 needs the gradient's g and off and the in-tables")
+        _mesh_arg(what, g, "g", torch.float32, dim=2)
+        if int(g.size(1)) != 2:
+            raise ValueError(f"g: {what}: expected [E, 2] (the operator is 2-D), got shape {tuple(g.shape)}")
+        _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+        _mesh_arg(what, in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
+        _mesh_arg(what, in_item, "in_item", torch.int32, dim=1)
+        n_entries = int(in_item.size(0))
+        if n_entries >= 2 ** 31:
+            raise NotImplementedError(f"in_item: {what}: {n_entries} list entries do not fit the int32 offsets")
+        _mesh_arg(what, in_g, "in_g", torch.float32, shape=(n_entries, 2))
+    else:
+        g = off = in_off = in_item = in_g = None
+        ucol = vcol = 0
+    if hw is not None:
+        _mesh_arg(what, hw, "hw", torch.float32, shape=(n_items, 5))
+    if out is not None:
+        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nf))
+        for name, t in (("gF", gF), ("gwall", gwall), ("hw", hw)):
+            if t is not None and out.numel() and t.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                raise ValueError(f"out: {what}: out shares its storage with {name}")
+    dev = _mesh_devices(what, ("item_body", item_body), ("area", area), ("unit", unit), ("arm", arm), ("own_off", own_off),
+                        ("own_item", own_item), ("gF", gF), ("gwall", gwall), ("g", g), ("off", off), ("in_off", in_off),
+                        ("in_item", in_item), ("in_g", in_g), ("hw", hw), ("out", out))
+    if hw is None:
+        hw = torch.empty((n_items, 5), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    a = _lib.g4c_body_forces_adjoint_t(gF=_lib.ptr(gF), gwall=_lib.ptr(gwall), nf=nf, pcol=pcol, ucol=ucol, vcol=vcol, mu=float(mu),
+                                       p_scale=float(p_scale), u_scale=float(u_scale), v_scale=float(v_scale), g=_lib.ptr(g),
+                                       off=_lib.ptr(off), item_body=_lib.ptr(item_body), area=_lib.ptr(area), unit=_lib.ptr(unit),
+                                       arm=_lib.ptr(arm), own_off=_lib.ptr(own_off), own_item=_lib.ptr(own_item), in_off=_lib.ptr(in_off),
+                                       in_item=_lib.ptr(in_item), in_g=_lib.ptr(in_g), hw=_lib.ptr(hw), gx=_lib.ptr(out))
+    _lib.check(lib.g4c_body_forces_adjoint(C.byref(a), n_nodes, n_bodies, n_items, n_entries, _lib.stream_handle(dev)))
+    return out
+
+
 def _sample_tables(what, idx, coef):
     """The j-major tables of ops.sample_*: idx int32 [k, P] (and coef float32 [k, P]) -> (k, P); ValueError naming the argument."""
     _mesh_arg(what, idx, "idx", torch.int32, dim=2)

@@ -679,6 +679,60 @@ typedef struct g4c_body_forces {
 } g4c_body_forces_t;
 int g4c_body_forces(const g4c_body_forces_t *bf /*host*/, int64_t n_bodies, int64_t n_items, void *stream);
 
+/* g4c_body_forces_adjoint — the transpose of the linear part of g4c_body_forces' map x -> (the six sums per body, wall[W, 2]): its
+ * backward (p_shift drops out; the (float) casts of wall count as the identity).  Inputs gF[n_bodies, 6] fp64 and gwall[n_items, 2]
+ * fp32, either may be NULL (zeros); output gx[n_nodes, nf] fp32, dense.  Two launches on the same stream, no contraction anywhere
+ * (every product is rounded before it is added):
+ *   1. per wall item w of body b = item_body[w], ONE thread, fp64, staged into hw[n_items, 5] fp32 = (H_w[u][0], H_w[u][1], H_w[v][0],
+ *      H_w[v][1], cp_w).  With a = area[w], r = arm[w], n̂ = unit[w], t̂ = (−n̂_y, n̂_x), gs = (double)gwall[w][1]:
+ *        A   = gF[b][FVX] − r_y·gF[b][MV]                    Bc = gF[b][FVY] + r_x·gF[b][MV]
+ *        dxx = mu·(A·a_x + gs·(t̂_x·n̂_x))
+ *        dxy = mu·((A·a_y + Bc·a_x) + gs·(t̂_y·n̂_x + t̂_x·n̂_y))
+ *        dyy = mu·(Bc·a_y + gs·(t̂_y·n̂_y))
+ *        H_w[u][0] = (float)(u_scale·(2·dxx))   H_w[u][1] = (float)(u_scale·dxy)
+ *        H_w[v][0] = (float)(v_scale·dxy)       H_w[v][1] = (float)(v_scale·(2·dyy))
+ *        cp_w = (float)(p_scale·((double)gwall[w][0] − ((gF[b][FPX]·a_x + gF[b][FPY]·a_y) + gF[b][MP]·(r_x·a_y − r_y·a_x))))
+ *      With mu == 0 the four H are +0 and unit is not read.
+ *   2. per node j, ONE thread, fp32.  own(j) = own_item[own_off[j] .. own_off[j + 1]): the items w with item[w] == j, ascending w (a
+ *      node may be an item of several bodies).  in(j) = in_off[j] .. in_off[j + 1]: the pairs (w, e) with e an in-edge of item[w] and
+ *      src_e == j, by ASCENDING CSR position e, then ascending w — the order in which g4c_mesh_derived_adjoint walks j's out-edges —
+ *      with in_item[q] = w and in_g[q] = g[e] copied into that order, so the walk streams them and only the row of hw is a gather.
+ *        p = +0; over own(j): p += cp_w.
+ *        mu != 0: acc[f] = +0 for f = u, v; over in(j) ascending, for a = 0, 1: acc[f] += in_g[q][a] · H_w[f][a]; then for every w of
+ *        own(j), over j's own in-edges e = off[j] .. in CSR order, for a = 0, 1: acc[f] −= g[e][a] · H_w[f][a].
+ *        gx[j, pcol] = p, gx[j, ucol] = acc[u], gx[j, vcol] = acc[v]; EVERY other column of the row is +0 (sign bit clear), and with
+ *        mu == 0 so are the velocity columns: g, off and the in-tables are then not read and may be NULL.
+ *      When every node is an item at most once, gx[:, (ucol, vcol)] has the bits of g4c_mesh_derived_adjoint applied to a dense
+ *      [n_nodes, 4] gradient that holds H_w at the wall rows and +0 elsewhere (its extra terms are g · (+0)).
+ * Both launches: at most 1024 workgroups of 256, the items / nodes dealt gid, gid + grid, ..., four list entries per trip with their
+ * loads in flight together and the additions in order; plain loads and stores, no LDS, no atomics, nothing passes between threads: the
+ * bits are a function of the data alone and a numpy loop reproduces them.  The tables are trusted as g4c_body_forces trusts item:
+ * item_body in [0, n_bodies), own_item and in_item in [0, n_items), the offset arrays ascending from 0 to n_items / n_entries.
+ * n_nodes == 0 launches nothing; n_items == 0, n_bodies == 0 or gF == gwall == NULL zero-fills gx (nothing else is read).
+ * G4C_EINVAL before any launch: null pointers, negative sizes (or n_entries > 2^31 − 1), nf < 1, a column >= nf, pcol / ucol / vcol
+ * not distinct when mu != 0, mu != 0 without g, off or the in-tables, gx overlapping gF, gwall or hw (by their sizes). */
+typedef struct g4c_body_forces_adjoint {
+    const double *gF;            /* [n_bodies, G4C_FORCES_NSUM] or NULL */
+    const float *gwall;          /* [n_items, 2] or NULL */
+    int32_t nf, pcol, ucol, vcol;          /* ucol, vcol are not read when mu == 0 */
+    double mu, p_scale, u_scale, v_scale;
+    const float *g;              /* [E, 2], CSR order; may be NULL, with off and the in-tables, when mu == 0 */
+    const int32_t *off;          /* [n_nodes + 1] */
+    const int32_t *item_body;    /* [n_items] the body of every item */
+    const double *area;          /* [n_items, 2] */
+    const double *unit;          /* [n_items, 2] */
+    const double *arm;           /* [n_items, 2] */
+    const int32_t *own_off;      /* [n_nodes + 1] */
+    const int32_t *own_item;     /* [n_items] */
+    const int32_t *in_off;       /* [n_nodes + 1] */
+    const int32_t *in_item;      /* [n_entries] */
+    const float *in_g;           /* [n_entries, 2] */
+    float *hw;                   /* [n_items, 5] scratch, written by the first launch */
+    float *gx;                   /* [n_nodes, nf] */
+} g4c_body_forces_adjoint_t;
+int g4c_body_forces_adjoint(const g4c_body_forces_adjoint_t *a /*host*/, int64_t n_nodes, int64_t n_bodies, int64_t n_items,
+                            int64_t n_entries, void *stream);
+
 /* Values at points that are no mesh nodes (csrc/point_sample.hip): a moving-least-squares interpolation with a linear basis over the
  * k nearest nodes of every point, 1 <= k <= G4C_SAMPLE_MAX_K (above: G4C_EUNSUPPORTED).  The tables idx and coef are j-major, [k, P]:
  * neighbour j of point p at [j * n_points + p], nearest first, node rows of `x` / `pos`.
