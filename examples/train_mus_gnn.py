@@ -6,7 +6,7 @@ The NsCircle HDF5 file is replaced by a synthetic array in the same record layou
 code | u v p per time step], NaN-padded to the largest mesh): decaying travelling waves on random point clouds — there is no
 network / h5py here; with the real file pass path="NsCircle.h5" instead of data=.
 
-    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss | --force-loss]
+    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss | --force-loss | --residual-loss]
 
 --flow-loss trains with gfd.nn.FlowLoss: GraphLoss plus a continuity penalty (the divergence of the predicted velocity) and a
 vorticity-matching term, both through the differentiable least-squares mesh gradient (gfd.MeshGradient).  The mesh is periodic in y,
@@ -23,6 +23,13 @@ round it, through the differentiable body forces (gfd.BodyForces): the wall is `
 by angle round the mean of its nodes (the synthetic records mark a small disc of nodes; in the real file the code marks the cylinder's
 surface).  The wall moves with the mesh, so the augmentations stay.  mu = 0: the pressure force alone — on this mesh, periodic in y, a viscous
 term would take edge_vectors="edge_attr" as --flow-loss does.  The loads are in the scaled units of the fields (values=None: those of the target).
+
+--residual-loss trains with gfd.nn.ResidualLoss: GraphLoss plus the residual of the incompressible momentum and continuity equations of the
+prediction minus that of the target (reference="target": the records' frame spacing is not a solver's time step), through the differentiable
+quadratic-fit operator (gfd.MeshJet) on its own stencil of the 12 nearest nodes of every graph of the batch.  That search is not periodic: the
+nodes next to the seam in y get a one-sided stencil, which a quadratic fit takes in its stride (on the graph's own periodic edges, k=None with
+edge_vectors="edge_attr", six neighbours condition five unknowns badly).  The fields are in their scaled units; pass scale= and shift= to
+weigh the terms as the physical equation does.
 """
 import argparse, math, os, sys
 import torch
@@ -35,9 +42,10 @@ ap.add_argument("--epochs", type=int, default=8); ap.add_argument("--folder", de
 ap.add_argument("--flow-loss", action="store_true", help="train with FlowLoss (continuity + vorticity terms) instead of GraphLoss")
 ap.add_argument("--sample-loss", action="store_true", help="train with SampleLoss (GraphLoss plus the error on a raster over the wake) instead of GraphLoss")
 ap.add_argument("--force-loss", action="store_true", help="train with ForceLoss (GraphLoss plus the error of the loads on the cylinder) instead of GraphLoss")
+ap.add_argument("--residual-loss", action="store_true", help="train with ResidualLoss (GraphLoss plus the momentum and continuity residuals) instead of GraphLoss")
 a = ap.parse_args()
-if a.flow_loss + a.sample_loss + a.force_loss > 1:
-    ap.error("--flow-loss, --sample-loss and --force-loss are separate runs")
+if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss > 1:
+    ap.error("--flow-loss, --sample-loss, --force-loss and --residual-loss are separate runs")
 T = 20                                                        # time steps per simulation
 # a 64 x 32 raster over the wake of the cylinder at (1, 0.5), in the coordinates of graph.pos
 WAKE = torch.stack(torch.meshgrid(torch.linspace(1.2, 3.0, 64), torch.linspace(0.1, 0.9, 32), indexing="ij"), -1).reshape(-1, 2)
@@ -50,6 +58,7 @@ train_config = gfd.nn.TrainConfig(
     training_loss   = (gfd.nn.losses.FlowLoss(lambda_d=0.25, terms={"div": 0.1, "vort": 0.05}, zero=("div",), edge_vectors="edge_attr")
                        if a.flow_loss else gfd.nn.losses.SampleLoss(WAKE, lambda_d=0.25, weight=1.0) if a.sample_loss
                        else gfd.nn.losses.ForceLoss(lambda_d=0.25, weight=1.0, pressure=2, wall={"pressure": 0.5}) if a.force_loss
+                       else gfd.nn.losses.ResidualLoss(lambda_d=0.25, weight=1e-3, nu=1e-3, dt=0.1, pressure=2) if a.residual_loss
                        else gfd.nn.losses.GraphLoss(lambda_d=0.25)),
     validation_loss = gfd.nn.losses.GraphLoss(),
     epochs          = a.epochs,

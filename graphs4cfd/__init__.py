@@ -9,7 +9,7 @@ import sys as _sys
 
 import graphs4cfd_amd as _impl
 from graphs4cfd_amd import *                                                                                # noqa: F401,F403
-from graphs4cfd_amd import Graph, DataLoader, Collater, MeshGradient, BodyForces, PointSampler, Tracers, Modes, SnapshotModes, DynamicModes, nn, transforms, metrics, datasets, plan, ops, synthetic      # noqa: F401
+from graphs4cfd_amd import Graph, DataLoader, Collater, MeshGradient, MeshJet, BodyForces, PointSampler, Tracers, Modes, SnapshotModes, DynamicModes, nn, transforms, metrics, datasets, plan, ops, synthetic      # noqa: F401
 
 __version__ = _impl.__version__
 

@@ -14,6 +14,7 @@ the reference's name (`import graphs4cfd as gfd`, the alias package at the repos
 from .graph import Graph
 from . import nn, plan, ops, synthetic, transforms, metrics, datasets
 from .loader import DataLoader, Collater
+from .mesh_jet import MeshJet                          # quadratic least-squares fit: first and second derivatives, own kNN stencil
 from .mesh_gradient import MeshGradient                # least-squares gradient over the mesh's edges: divergence, vorticity, gradients
 from .body_forces import BodyForces                    # drag, lift and wall loads of a 2-D flow on the bodies it passes, from the wall nodes
 from .point_sampler import PointSampler                # node fields at points, rakes and rasters: a linear moving-least-squares fit over the k nearest nodes

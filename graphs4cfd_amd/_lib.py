@@ -106,6 +106,7 @@ class g4c_rollout_spectrum_t(C.Structure):
 
 
 DERIVED_MAX_COLS, DERIVED_MAX_TERMS = 8, 3         # G4C_DERIVED_MAX_COLS / _TERMS
+JET_MAX_FIELDS = 4                                  # G4C_JET_MAX_FIELDS
 DERIVED_SQ, DERIVED_ABS, DERIVED_MAX_ABS, DERIVED_NSTAT = range(4)     # G4C_DERIVED_*
 
 
@@ -222,6 +223,12 @@ _SIGNATURES = {
     "g4c_mesh_derived": (C.c_int, [C.c_void_p, C.POINTER(g4c_mesh_derived_t), C.POINTER(g4c_derived_program_t), C.c_int64, C.c_void_p]),
     "g4c_mesh_derived_adjoint": (C.c_int, [C.c_void_p, C.POINTER(g4c_derived_program_t), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "g4c_mesh_jet_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "g4c_mesh_jet": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(g4c_derived_program_t),
+                               C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "g4c_mesh_jet_adjoint": (C.c_int, [C.c_void_p, C.POINTER(g4c_derived_program_t), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_body_forces": (C.c_int, [C.POINTER(g4c_body_forces_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_body_forces_adjoint": (C.c_int, [C.POINTER(g4c_body_forces_adjoint_t), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,

@@ -593,6 +593,26 @@ def mesh_derived(op, x: Tensor, prog) -> Tensor:
     return _MeshDerived.apply(x, op, prog)
 
 
+class _MeshJet(torch.autograd.Function):
+    """`MeshJet.derived`: the plain launch forward, its transpose (g4c_mesh_jet_adjoint) backward.  The map is linear in x and the
+    rows are constants: nothing is saved but the operator and the program."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, op, prog):
+        out = ops.mesh_jet(x.detach(), op.off, op.c, op.src, prog)
+        ctx.op, ctx.prog, ctx.nf = op, prog, int(x.size(1))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy: Tensor):
+        return ctx.op._adjoint(gy.contiguous(), ctx.prog, ctx.nf), None, None
+
+
+def mesh_jet(op, x: Tensor, prog) -> Tensor:
+    return _MeshJet.apply(x, op, prog)
+
+
 # ------------------------------------------------------------------------------------- off-node samples
 class _SamplePoints(torch.autograd.Function):
     """`PointSampler.sample`: today's launch forward, its transpose (g4c_sample_points_adjoint) backward.  The map is linear in x and

@@ -463,3 +463,210 @@ class ForceLoss(nn.Module):
                     term = w * d[:, k].square().mean()
                     loss = term if loss is None else loss + term
         return loss
+
+
+class ResidualLoss(nn.Module):
+    """`GraphLoss(lambda_d)` plus the residual of the incompressible momentum and continuity equations the model is a surrogate
+    for — a physics-informed term (new functionality — the reference has none):
+
+        node_weight · GraphLoss(lambda_d)(graph, pred, target)
+          + weight · [ mean over the counted nodes and components a of (R_a(pred) − R_a(ref))² + continuity · mean (C(pred) − C(ref))² ]
+
+        R_a(x) = (U_a − U_a^prev) / dt + Σ_b U_b ∂_b U_a + (1 / ρ) ∂_a P − ν ∇²U_a          C(x) = Σ_a ∂_a U_a
+
+    U = scale · x + shift is the physical field (`BodyForces`' convention: one number per field, default 1 and 0), `velocity` its
+    velocity columns (default 0 .. dim − 1), `pressure` its pressure column (default: the first column that is no velocity component —
+    dim, with the default velocity).  U^prev is the last input step
+    `graph.field[:, −F:]` in the same units, detached — `Trainer` feeds the prediction back into it that way.  `reference="target"`
+    subtracts the same expression of `target`, computed under `no_grad`: the dataset's frame spacing is not the solver's time step,
+    so the truth's own discrete residual is not zero; `reference="zero"` drives the residual itself to zero.  `nu` is a number, or
+    the name of a per-node graph attribute [N] or [N, 1] (1 / Re per sample: it collates along the nodes); `dt`, `rho` are numbers.
+    `mask` is None or the name of a per-node attribute (non-zero: the node is counted); degenerate nodes never count.
+
+    The derivatives are `gfd.MeshJet`'s (a quadratic fit: ∇² from a composed linear gradient does not converge): `k` its own stencil
+    (default 12; 20 is the suggestion in 3-D) or None for the graph's in-edges, then with `edge_vectors` None or the name of a graph
+    attribute holding the unscaled, wrapped [E, dim] vectors (a periodic mesh); `edge_vectors` together with `k` is a ValueError.
+    All derivatives of one tensor come from ONE `MeshJet.derived` launch in 2-D (grad u, grad v, grad p, ∇²u, ∇²v: eight columns)
+    and from two in 3-D (fifteen columns); the products are torch arithmetic, and their gradients reach the model through
+    `MeshJet.adjoint` (`g4c_mesh_jet_adjoint`).  No double backward.  The operator is kept (one entry) while the tensors it was
+    built from are the same objects, unmodified (identity and `_version`) — `Trainer.train_epoch` calls the loss once per output
+    step of the same batch; `builds` counts the operators built.  With `weight == 0` nothing is built or launched and the value is
+    node_weight · GraphLoss bit for bit; `node_weight == 0` skips `GraphLoss`.  HIP device only."""
+
+    def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, nu, dt, rho=1.0, velocity=None, pressure=None, scale=None, shift=None,
+                 continuity=1.0, reference="target", k=12, power=2, edge_vectors=None, mask=None):
+        super().__init__()
+        from ..mesh_jet import MAX_K
+        self.lambda_d = _number(lambda_d, "lambda_d")
+        self.weight = _number(weight, "weight", "a finite weight >= 0")
+        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
+        if isinstance(nu, str):
+            if not nu:
+                raise ValueError(f"nu: expected a finite number >= 0 or the name of a per-node graph attribute, got {nu!r}")
+        else:
+            nu = _number(nu, "nu", "a finite number >= 0 (the kinematic viscosity) or the name of a per-node graph attribute")
+        for name, v in (("dt", dt), ("rho", rho)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+                raise ValueError(f"{name}: expected a finite number > 0, got {v!r}")
+        if velocity is not None:
+            try:
+                velocity = tuple(velocity)
+            except TypeError:
+                raise ValueError(f"velocity: expected 2 or 3 distinct field numbers, got {velocity!r}") from None
+            if (len(velocity) not in (2, 3) or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in velocity)
+                    or len(set(velocity)) != len(velocity)):
+                raise ValueError(f"velocity: expected 2 or 3 distinct field numbers, got {velocity!r}")
+        if pressure is not None and (isinstance(pressure, bool) or not isinstance(pressure, int) or pressure < 0
+                                     or (velocity is not None and pressure in velocity)):
+            raise ValueError(f"pressure: expected a field number that is no velocity component, got {pressure!r}")
+        factors = {}
+        for name, v in (("scale", scale), ("shift", shift)):
+            if v is not None:
+                try:
+                    v = [float(q) for q in (v.tolist() if torch.is_tensor(v) else v)]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name}: expected one number per field, got {v!r}") from None
+                if not v or not all(math.isfinite(q) for q in v):
+                    raise ValueError(f"{name}: expected one finite number per field, got {v!r}")
+            factors[name] = v
+        self.continuity = _number(continuity, "continuity", "a finite weight >= 0")
+        if reference not in ("target", "zero"):
+            raise ValueError(f"reference: expected 'target' or 'zero', got {reference!r}")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 5 <= k <= MAX_K):
+            raise ValueError(f"k: expected None (the graph's in-edges) or an integer 5 <= k <= {MAX_K} (9 <= k in 3-D), got {k!r}")
+        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+            raise ValueError(f"power: expected 0, 1 or 2 (a stencil entry weighs |d|^-power), got {power!r}")
+        for name, v in (("edge_vectors", edge_vectors), ("mask", mask)):
+            if v is not None and (not isinstance(v, str) or not v):
+                raise ValueError(f"{name}: expected None or the name of a graph attribute, got {v!r}")
+        if edge_vectors is not None and k is not None:
+            raise ValueError("edge_vectors: they belong to the graph's edges; pass k=None with them (the operator's own stencil search "
+                             "is not periodic)")
+        self.base = GraphLoss(lambda_d)
+        self.nu, self.dt, self.rho = nu, float(dt), float(rho)
+        self.velocity, self.pressure, self.scale, self.shift = velocity, pressure, factors["scale"], factors["shift"]
+        self.reference, self.k, self.power, self.edge_vectors, self.mask = reference, k, power, edge_vectors, mask
+        self._cache = None          # ([(tensor, its version), ...], MeshJet)
+        self.builds = 0             # operators built so far (a batch seen again costs none)
+
+    def operator(self, graph):
+        """The `MeshJet` of `graph` — of all its graphs, when it is a batch —: the cached one while the tensors it was built from are
+        the same objects, unmodified (identity and `_version`: an address says nothing, the allocator hands a freed batch's to the
+        next one)."""
+        from ..mesh_jet import MeshJet
+        vec = None
+        if self.k is not None:
+            key = [getattr(graph, "pos", None), getattr(graph, "batch", None)]
+        else:
+            if self.edge_vectors is not None:
+                vec = getattr(graph, self.edge_vectors, None)
+                if not torch.is_tensor(vec):
+                    raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
+            key = [getattr(graph, "edge_index", None), getattr(graph, "pos", None) if vec is None else vec]
+        hit = self._cache
+        if (hit is not None and len(hit[0]) == len(key)
+                and all(a is t and (not torch.is_tensor(t) or v == t._version) for (a, v), t in zip(hit[0], key))):
+            return hit[1]
+        op = MeshJet(graph, k=self.k, power=self.power, edge_vectors=vec)
+        self._cache = ([(t, t._version if torch.is_tensor(t) else None) for t in key], op)
+        self.builds += 1
+        return op
+
+    @staticmethod
+    def _launches(names, columns, fields):
+        """`names` packed greedily into launches of at most 8 columns and 4 distinct fields each."""
+        from .. import _lib
+        out, cur, nc, used = [], [], 0, set()
+        for name, c, f in zip(names, columns, fields):
+            if cur and (nc + c > _lib.DERIVED_MAX_COLS or len(used | {f}) > _lib.JET_MAX_FIELDS):
+                out.append(cur)
+                cur, nc, used = [], 0, set()
+            cur.append(name)
+            nc += c
+            used.add(f)
+        return out + [cur]
+
+    def _residual(self, op, x, prev, vel, p, nu, scale, shift):
+        """(R [N, dim], C [N]) of the fields x [N, F] (in the model's units)."""
+        dim = op.dim
+        if dim == 2:          # grad u, grad v, grad p, ∇²u, ∇²v: exactly eight columns, one launch
+            fields = [vel[0], vel[1], p, vel[0], vel[1]]
+            names = [f"grad:{f}" for f in fields[:3]] + [f"lap:{f}" for f in fields[3:]]
+        else:                 # fifteen columns: (grad u, grad v, ∇²u, ∇²v) and (grad w, grad p, ∇²w) — two launches
+            fields = [vel[0], vel[1], vel[0], vel[1], vel[2], p, vel[2]]
+            names = [f"{kind}:{f}" for kind, f in zip(("grad", "grad", "lap", "lap", "grad", "grad", "lap"), fields)]
+        widths = [dim if name.startswith("grad") else 1 for name in names]
+        d = {}
+        for group in self._launches(names, widths, fields):
+            out = op.derived(x, tuple(group), field_scale=scale)          # the derivatives of the PHYSICAL fields: the shift drops out
+            c0 = 0
+            for name in group:
+                w = widths[names.index(name)]
+                d[name] = out[:, c0:c0 + w]
+                c0 += w
+        sc = x.new_tensor(scale)
+        u = x * sc + x.new_tensor(shift)
+        u_prev = prev * sc + x.new_tensor(shift)
+        rows = []
+        for a, fa in enumerate(vel):
+            g = d[f"grad:{fa}"]
+            adv = u[:, vel[0]] * g[:, 0]
+            for b in range(1, dim):
+                adv = adv + u[:, vel[b]] * g[:, b]
+            rows.append((u[:, fa] - u_prev[:, fa]) / self.dt + adv + d[f"grad:{p}"][:, a] / self.rho - nu * d[f"lap:{fa}"][:, 0])
+        cont = d[f"grad:{vel[0]}"][:, 0]
+        for a in range(1, dim):
+            cont = cont + d[f"grad:{vel[a]}"][:, a]
+        return torch.stack(rows, dim=1), cont
+
+    def forward(self, graph, pred, target):
+        loss = None
+        if self.node_weight > 0:
+            loss = self.base(graph, pred, target)
+            if self.node_weight != 1.0:
+                loss = self.node_weight * loss
+        if self.weight == 0:
+            return pred.sum() * 0.0 if loss is None else loss
+        op = self.operator(graph)
+        n, nf, dim = op.n_nodes, int(pred.size(1)), op.dim
+        vel = tuple(range(dim)) if self.velocity is None else self.velocity
+        p = self.pressure if self.pressure is not None else next(f for f in range(len(vel) + 1) if f not in vel)
+        if len(vel) != dim:
+            raise ValueError(f"velocity: {vel!r} on a mesh of {dim} dimensions")
+        if max(vel + (p,)) >= nf or p in vel:
+            raise ValueError(f"pressure: the fields {vel!r} and {p} of a prediction with {nf} columns")
+        for name, v in (("scale", self.scale), ("shift", self.shift)):
+            if v is not None and len(v) != nf:
+                raise ValueError(f"{name}: expected {nf} numbers (one per field), got {len(v)}")
+        scale = [1.0] * nf if self.scale is None else self.scale
+        shift = [0.0] * nf if self.shift is None else self.shift
+        field = getattr(graph, "field", None)
+        if not torch.is_tensor(field) or field.dim() != 2 or int(field.size(0)) != n or int(field.size(1)) < nf:
+            raise ValueError(f"graph: ResidualLoss needs graph.field [{n}, >= {nf}] (its last {nf} columns are the previous step), got "
+                             f"{tuple(getattr(field, 'shape', ()))}")
+        prev = field[:, -nf:].detach().to(pred.dtype)
+        nu = self.nu
+        if isinstance(nu, str):
+            nu = getattr(graph, self.nu, None)
+            if not torch.is_tensor(nu) or nu.numel() != n or not nu.dtype.is_floating_point:
+                raise ValueError(f"nu: graph.{self.nu}: expected a per-node floating-point tensor [{n}] or [{n}, 1], got "
+                                 f"{getattr(nu, 'dtype', type(nu).__name__)} {tuple(getattr(nu, 'shape', ()))}")
+            nu = nu.detach().reshape(-1).to(pred.dtype)
+        counted = ~op.degenerate
+        if self.mask is not None:
+            m = getattr(graph, self.mask, None)
+            if not torch.is_tensor(m) or m.numel() != n:
+                raise ValueError(f"mask: graph.{self.mask}: expected a per-node tensor [{n}], got {tuple(getattr(m, 'shape', ()))}")
+            counted = counted & (m.reshape(-1) != 0)
+        r, c = self._residual(op, pred, prev, vel, p, nu, scale, shift)
+        if self.reference == "target":
+            with torch.no_grad():
+                r0, c0 = self._residual(op, target.detach(), prev, vel, p, nu, scale, shift)
+            r, c = r - r0, c - c0
+        keep = counted.to(pred.dtype)
+        count = keep.sum().clamp(min=1.0)
+        term = (r.square() * keep[:, None]).sum() / (count * dim)
+        if self.continuity > 0:
+            term = term + self.continuity * ((c.square() * keep).sum() / count)
+        term = self.weight * term
+        return term if loss is None else loss + term

@@ -834,13 +834,19 @@ def mesh_gradient_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=N
     return g, src, degenerate
 
 
-def derived_program(program, nf: Optional[int] = None, dim: Optional[int] = None) -> "_lib.g4c_derived_program_t":
+def derived_program(program, nf: Optional[int] = None, dim: Optional[int] = None, order: int = 1) -> "_lib.g4c_derived_program_t":
     """A program of `mesh_derived` — a sequence of columns, each a sequence of 1 .. 3 terms (field, axis, coef): the column is
     Σ coef · ∂_axis x[:, field] — as the library's g4c_derived_program_t (returned unchanged if it is one already).  ValueError
-    naming `program` on anything else; fields and axes are checked against nf / dim when those are given."""
+    naming `program` on anything else; fields and axes are checked against nf / dim when those are given.  `order=2` is a program
+    of `mesh_jet`: with `dim`, axis ranges over 0 .. Q − 1, Q = dim + dim (dim + 1) / 2 — the first derivatives, then the second ones
+    xx, xy, yy (2-D) or xx, xy, xz, yy, yz, zz (3-D)."""
     if isinstance(program, _lib.g4c_derived_program_t):
         return program
-    what = "mesh_derived"
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"order: derived_program: expected 1 (mesh_derived) or 2 (mesh_jet), got {order!r}")
+    what = "mesh_derived" if order == 1 else "mesh_jet"
+    if order == 2 and dim is not None:
+        dim = jet_size(dim)
     try:
         cols = [[tuple(t) for t in col] for col in program]
     except TypeError:
@@ -861,7 +867,146 @@ def derived_program(program, nf: Optional[int] = None, dim: Optional[int] = None
             if a < 0 or (dim is not None and a >= dim):
                 raise ValueError(f"program: {what}: column {c} term {k}: axis {a} of {dim}")
             p.field[c][k], p.axis[c][k], p.coef[c][k] = f, a, float(coef)
+    if order == 2:
+        _jet_fields(what, p)
     return p
+
+
+def jet_size(dim: int) -> int:
+    """Q = dim + dim (dim + 1) / 2: the derivatives per field of a quadratic fit on a mesh of `dim` dimensions (5 or 9)."""
+    if isinstance(dim, bool) or dim not in (2, 3):
+        raise ValueError(f"dim: mesh_jet: expected 2 or 3, got {dim!r}")
+    return dim + dim * (dim + 1) // 2
+
+
+def _jet_dim(what, c, name="c") -> int:
+    """The mesh's dimension from the width of a table of rows [S, Q]."""
+    _mesh_arg(what, c, name, torch.float32, dim=2)
+    if int(c.size(1)) not in (5, 9):
+        raise ValueError(f"{name}: {what}: expected [S, 5] (2-D) or [S, 9] (3-D), got shape {tuple(c.shape)}")
+    return 2 if int(c.size(1)) == 5 else 3
+
+
+def mesh_jet_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
+    """g4c_mesh_jet_weights: the rows of a weighted least-squares quadratic fit over a stencil, once per mesh.  The stencil comes as
+    `mesh_gradient_weights` takes the in-edges: `csr` (off int32 [N + 1], perm int32 [S] or None) groups its entries by receiver,
+    src32 int32 [S] their senders and rel float32 [S, dim] their vectors receiver - sender in the caller's numbering; power 0, 1 or
+    2.  Returns (c float32 [S, Q], src int32 [S], degenerate uint8 [N]) in CSR order, jet(i) = Σ_s c[s] (x[src[s]] - x[i]) with the
+    first derivatives in columns 0 .. dim - 1 and the second ones after them (include/g4c.h has the arithmetic).  `out`: the three
+    tensors to write into; an empty stencil launches nothing (then a fresh `degenerate` is all ones)."""
+    what = "mesh_jet_weights"
+    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
+        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
+    _mesh_arg(what, rel, "rel", torch.float32, dim=2)
+    n_entries, dim = int(rel.size(0)), int(rel.size(1))
+    if dim not in (2, 3):
+        raise ValueError(f"rel: {what}: expected [S, 2] or [S, 3], got shape {tuple(rel.shape)}")
+    Q = jet_size(dim)
+    off, perm = getattr(csr, "off", None), getattr(csr, "perm", None)
+    _mesh_arg(what, off, "csr.off", torch.int32, dim=1)
+    if off.numel() < 1:
+        raise ValueError(f"csr.off: {what}: expected [n_nodes + 1], got shape {tuple(off.shape)}")
+    n_nodes = int(off.numel()) - 1
+    if int(getattr(csr, "n", n_entries)) != n_entries:
+        raise ValueError(f"csr: {what}: a plan of {csr.n} entries for rel of {n_entries}")
+    if perm is not None:
+        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_entries,))
+    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_entries,))
+    if out is not None:
+        c, src, degenerate = out
+        _mesh_arg(what, c, "out[0]", torch.float32, shape=(n_entries, Q))
+        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_entries,))
+        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
+    else:
+        c = src = degenerate = None
+    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", c), ("out[1]", src),
+                        ("out[2]", degenerate))
+    if out is None:
+        c = torch.empty((n_entries, Q), dtype=torch.float32, device=dev)
+        src = torch.empty((n_entries,), dtype=torch.int32, device=dev)
+        degenerate = torch.ones((n_nodes,), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_mesh_jet_weights(_lib.ptr(off), _lib.ptr(perm), _lib.ptr(src32), _lib.ptr(rel), dim, power, n_nodes, n_entries,
+                                        _lib.ptr(c), _lib.ptr(src), _lib.ptr(degenerate), _lib.stream_handle(dev)))
+    return c, src, degenerate
+
+
+def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optional[Tensor] = None, *, nf: Optional[int] = None) -> Tensor:
+    """g4c_mesh_jet: the columns of `program` (`derived_program(.., order=2)`: axis 0 .. Q - 1) of the fields x[:, :nf] (float32
+    [N, x_ld], rows of unit stride; nf defaults to every column) by the quadratic fit (c float32 [S, Q], src int32 [S], off int32
+    [N + 1]: the outputs of `mesh_jet_weights` and the stencil's offsets) into out float32 [N, nd] — one thread per node, fp32, its
+    entries in CSR order: the same bits on every run.  At most 4 distinct fields per program."""
+    what = "mesh_jet"
+    dim = _jet_dim(what, c)
+    n_entries = int(c.size(0))
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or int(x.size(1)) < 1:
+        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
+    n_nodes, cols = int(x.size(0)), int(x.size(1))
+    nf = cols if nf is None else int(nf)
+    if not 1 <= nf <= cols:
+        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
+    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
+        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, src, "src", torch.int32, shape=(n_entries,))
+    prog = derived_program(program, nf, dim, order=2)
+    _jet_fields(what, prog)
+    nd = int(prog.nd)
+    if out is not None:
+        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nd))
+    dev = _mesh_devices(what, ("x", x), ("off", off), ("c", c), ("src", src), ("out", out))
+    if out is None:
+        out = torch.empty((n_nodes, nd), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_mesh_jet(_lib.ptr(x), x_ld, nf, dim, _lib.ptr(c), _lib.ptr(src), _lib.ptr(off), C.byref(prog), n_nodes, n_entries,
+                                _lib.ptr(out), _lib.stream_handle(dev)))
+    return out
+
+
+def _jet_fields(what, prog) -> None:
+    fields = {int(prog.field[c][k]) for c in range(int(prog.nd)) for k in range(int(prog.n_terms[c]))}
+    if len(fields) > _lib.JET_MAX_FIELDS:
+        raise ValueError(f"program: {what}: {len(fields)} distinct fields (at most {_lib.JET_MAX_FIELDS} per program)")
+
+
+def mesh_jet_adjoint(gy: Tensor, off: Tensor, c: Tensor, out_off: Tensor, out_c: Tensor, out_dst: Tensor, program, nf: int,
+                     gx: Optional[Tensor] = None) -> Tensor:
+    """g4c_mesh_jet_adjoint: the transpose of `mesh_jet`'s map x[:, :nf] -> out, applied to gy float32 [N, nd] (contiguous): gx
+    float32 [N, nf], every column written (a field the program does not differentiate gets zeros).  off and c as for `mesh_jet`;
+    the sender side, built once per operator: with perm the CSR positions grouped by SENDER, ascending within a sender
+    (`plan.gather_csr(src, N)`), out_off int32 [N + 1] its offsets, out_c float32 [S, Q] = c[perm] and out_dst int32 [S] the
+    receivers of those positions.  One thread per node, fp32, a fixed order (include/g4c.h), no atomics.  `gx`: the tensor to write
+    into (not gy)."""
+    what = "mesh_jet_adjoint"
+    dim = _jet_dim(what, c)
+    n_entries, Q = int(c.size(0)), int(c.size(1))
+    if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
+        raise ValueError(f"nf: {what}: expected a number of fields >= 1, got {nf!r}")
+    prog = derived_program(program, nf, dim, order=2)
+    _jet_fields(what, prog)
+    nd = int(prog.nd)
+    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
+    if int(gy.size(1)) != nd:
+        raise ValueError(f"gy: {what}: expected [n_nodes, {nd}] (one column per column of the program), got shape {tuple(gy.shape)}")
+    n_nodes = int(gy.size(0))
+    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
+    _mesh_arg(what, out_c, "out_c", torch.float32, shape=(n_entries, Q))
+    _mesh_arg(what, out_dst, "out_dst", torch.int32, shape=(n_entries,))
+    if gx is not None:
+        _mesh_arg(what, gx, "gx", torch.float32, shape=(n_nodes, nf))
+        if gx is gy or (gx.numel() and gy.numel() and gx.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
+            raise ValueError(f"gx: {what}: gx shares its storage with gy")
+    dev = _mesh_devices(what, ("gy", gy), ("off", off), ("c", c), ("out_off", out_off), ("out_c", out_c), ("out_dst", out_dst), ("gx", gx))
+    if gx is None:
+        gx = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.g4c_mesh_jet_adjoint(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(c), _lib.ptr(off), _lib.ptr(out_c), _lib.ptr(out_dst),
+                                        _lib.ptr(out_off), n_nodes, n_entries, _lib.ptr(gx), _lib.stream_handle(dev)))
+    return gx
 
 
 def mesh_derived_scratch(n_nodes: int, nd: int, device) -> Tensor:

@@ -631,6 +631,51 @@ int g4c_mesh_derived_adjoint(const float *gy, const g4c_derived_program_t *prog 
                              const int32_t *off, const float *out_g, const int32_t *out_dst, const int32_t *out_off,
                              int64_t n_nodes, int64_t n_edges, float *gx, void *stream);
 
+/* First and second derivatives on the mesh: a weighted least-squares fit of a quadratic through the node's own value, over a
+ * stencil the caller brings — the mesh's in-edges or a wider one (csrc/mesh_jet.hip).  Q = dim + dim (dim + 1) / 2 unknowns per node
+ * (5 or 9): the first derivatives 0 .. dim − 1, then the second ones xx, xy, yy (2-D) or xx, xy, xz, yy, yz, zz (3-D).
+ *
+ * g4c_mesh_jet_weights — once per mesh.  The stencil in CSR form exactly as g4c_mesh_gradient_weights takes the in-edges: the s-th
+ * entry of node i is pe = perm[off[i] + s] (perm == NULL: off[i] + s), src32[S] the senders, rel[S, dim] fp32 receiver − sender.  One
+ * thread per node, fp64, no contraction, in this order.  Per entry: d = −rel, r² = Σ_a d_a d_a from 0, w = 1, 1 / sqrt(r²) or 1 / r²
+ * (power 0, 1, 2); the row b = (d_0 .., then for a <= b' in the order above t = d_a d_b', halved where a == b'), so that for a quadratic
+ * x[src] − x[i] = Σ_q b_q jet_q.  The normal matrix, lower triangle, A_ij += (w b_i) b_j over the entries in CSR order.  Scaled to a
+ * unit diagonal: sc_i = 1 / sqrt(A_ii), A_ij <- (A_ij sc_i) sc_j.  Cholesky L Lᵀ = A by columns j = 0 .. Q − 1: pivot_j = A_jj − L_j0² −
+ * .. − L_j,j−1² (subtracted one by one), L_jj = sqrt(pivot_j), inv_j = 1 / L_jj, and for i > j  L_ij = (A_ij − L_i0 L_j0 − ..) inv_j.  Per
+ * entry then y_i = (b_i sc_i − L_i0 y_0 − .. − L_i,i−1 y_i−1) inv_i for i ascending, z_i = (y_i − L_i+1,i z_i+1 − .. − L_Q−1,i z_Q−1) inv_i
+ * for i descending, and c[s][i] = (float)((w sc_i) z_i).  The node is DEGENERATE — every c of it +0, degenerate[i] = 1 — iff it has
+ * fewer than Q entries, or a weight is not finite (a zero-length vector under power >= 1), or some pivot is not > 1e-12 (that is <=
+ * the threshold, or no number): the threshold sits on the unit-diagonal matrix, where it is invariant under x -> λx.
+ * Outputs in CSR order: c[S, Q] fp32 with jet(i) = Σ_s c[s] (x[src_s] − x[i]), src[S] = src32[pe], degenerate[n_nodes].  n_nodes == 0
+ * or n_entries == 0 launches nothing, writes nothing and succeeds.  dim 2 or 3 (G4C_EUNSUPPORTED); power outside 0 .. 2, negative
+ * sizes, null pointers: G4C_EINVAL before any launch. */
+#define G4C_JET_MAX_FIELDS 4
+int g4c_mesh_jet_weights(const int32_t *off, const int32_t *perm /*or NULL*/, const int32_t *src32, const float *rel, int32_t dim,
+                         int32_t power, int64_t n_nodes, int64_t n_entries, float *c, int32_t *src, uint8_t *degenerate, void *stream);
+
+/* g4c_mesh_jet — per call: out[n_nodes, nd] (dense) from x[n_nodes, x_ld] (its first nf columns are the fields) by a program as
+ * g4c_mesh_derived's, whose `axis` ranges over 0 .. Q − 1: 0 .. dim − 1 the first derivatives, dim .. Q − 1 the second ones in the
+ * order above.  nd <= 8 columns of 1 .. 3 terms, at most G4C_JET_MAX_FIELDS distinct fields (more: G4C_EUNSUPPORTED).  fp32, no
+ * contraction, one thread per node: for every field f the program names and q = 0 .. Q − 1, J[f][q] = 0, then over the entries e of
+ * node i in CSR order diff = x[src_e, f] − x[i, f], p = c[e][q] · diff (rounded), J[f][q] += p; column = (coef₀ J₀ + coef₁ J₁) + coef₂ J₂
+ * with every product rounded and the terms added left to right from the first.  A numpy.float32 loop reproduces the bits.  No step
+ * index, snapshots or statistics: this launch is not part of the rollout.  n_nodes == 0 launches nothing; an empty stencil
+ * (n_entries == 0; c and src may be NULL) writes zeros.  G4C_EINVAL before any launch: null pointers, negative sizes, x_ld < nf, a
+ * field or derivative out of range, a column without terms. */
+int g4c_mesh_jet(const float *x, int32_t x_ld, int32_t nf, int32_t dim, const float *c, const int32_t *src, const int32_t *off,
+                 const g4c_derived_program_t *prog /*host*/, int64_t n_nodes, int64_t n_entries, float *out, void *stream);
+
+/* g4c_mesh_jet_adjoint — the transpose of g4c_mesh_jet's map x -> out, in g4c_mesh_derived_adjoint's form and order with Q in the
+ * place of dim: H_i[f][q] = +0, then += coef[c][k] · gy[i, c] over the terms that pick (f, q) in program order; acc[f] = +0; over the
+ * entries node j SENDS, by ascending CSR position (out_off[n_nodes + 1], out_c[S, Q] = c[perm[·]], out_dst[S] — the sender-side
+ * tables, built once per operator), for q = 0 .. Q − 1: acc[f] += out_c[·][q] · H_dst[f][q]; then over j's own entries in CSR order,
+ * for q = 0 .. Q − 1: acc[f] −= c[e][q] · H_j[f][q].  No atomics.  EVERY column of gx[n_nodes, nf] is written: a field the program does
+ * not name gets +0; n_entries == 0 zero-fills gx (the tables may be NULL); n_nodes == 0 launches nothing.  G4C_EINVAL before any
+ * launch: null pointers, negative sizes, gx overlapping gy, a field or derivative out of range; G4C_EUNSUPPORTED as g4c_mesh_jet. */
+int g4c_mesh_jet_adjoint(const float *gy, const g4c_derived_program_t *prog /*host*/, int32_t dim, int32_t nf, const float *c,
+                         const int32_t *off, const float *out_c, const int32_t *out_dst, const int32_t *out_off, int64_t n_nodes,
+                         int64_t n_entries, float *gx, void *stream);
+
 /* g4c_body_forces (csrc/body_forces.hip) — the force of a 2-D flow on the bodies it passes, once per step: AFTER the forward and
  * BEFORE the step's closing launch (it reads the step index t = step[0] and never writes it; with step == NULL, t = t0).  A body's
  * wall is a closed polygon of W_b items, each a mesh node with an area vector (the outward normal times the length lumped at the

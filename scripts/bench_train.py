@@ -2,7 +2,7 @@
 MuS-GNN on a synthetic mesh, on the GPU (fused forward, recompute backward: autograd.py) and — on a bounded sample — with
 the oracle on the host cores (torch autograd over the op-for-op restatement = what the reference's fit() executes).
 Usage: python scripts/bench_train.py [--nodes 100000] [--model NsThreeScaleGNN] [--steps 10] [--cpu-steps 1] [--phases] [--mixed [--saved-bf16]]
-       [--flow-loss | --sample-loss | --force-loss]
+       [--flow-loss | --sample-loss | --force-loss | --residual-loss]
 --flow-loss: the same run with FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) on the GPU (a continuity penalty and a vorticity-matching
 term through the differentiable mesh gradient: two `derived` launches and their adjoints per step; the host-side sample keeps GraphLoss).
 --sample-loss: the same run with SampleLoss(a 128 × 64 raster over the wake window [0.5, 1] × [0.25, 0.75], 0.25, weight=1.0): GraphLoss plus
@@ -11,6 +11,9 @@ the error at 8 192 points that are no nodes, through the differentiable point sa
 picked from the mesh — nearest to a circle of radius 0.1 round (0.5, 0.5): the synthetic mesh has no `bound` —: GraphLoss plus the error of drag,
 lift and the wall loads through the differentiable body forces: a `forces` and a `wall` launch on the prediction and on the target and the two
 adjoints per step.
+--residual-loss: the same run with ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1): GraphLoss plus the momentum and continuity residuals
+through the differentiable quadratic-fit operator (gfd.MeshJet, its own k = 12 stencil): a `derived` launch of eight columns on the prediction and
+on the target and one adjoint per step.
 --mixed: the same step in mixed precision (what fit(mixed_precision=True) selects: every matrix product on bf16-rounded operands).
 --saved-bf16 (with --mixed): the rows the forward keeps for the backward as bf16 (TrainConfig(saved_activations="bf16"))."""
 import argparse, json, os, sys, time
@@ -30,9 +33,10 @@ ap.add_argument("--saved-bf16", action="store_true", help="with --mixed: saved a
 ap.add_argument("--flow-loss", action="store_true", help="FlowLoss(0.25, terms={'div': 0.1, 'vort': 0.05}) instead of GraphLoss(0.25) on the GPU")
 ap.add_argument("--sample-loss", action="store_true", help="SampleLoss(a 128 x 64 raster over the wake window, 0.25) instead of GraphLoss(0.25) on the GPU")
 ap.add_argument("--force-loss", action="store_true", help="ForceLoss(0.25, mu=1e-3, wall=...) on a loop of 256 nodes instead of GraphLoss(0.25) on the GPU")
+ap.add_argument("--residual-loss", action="store_true", help="ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1) instead of GraphLoss(0.25) on the GPU")
 a = ap.parse_args()
-if a.flow_loss + a.sample_loss + a.force_loss > 1:
-    ap.error("--flow-loss, --sample-loss and --force-loss are separate runs")
+if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss > 1:
+    ap.error("--flow-loss, --sample-loss, --force-loss and --residual-loss are separate runs")
 if a.saved_bf16 and not a.mixed:
     ap.error("--saved-bf16 needs --mixed")
 if a.mixed:
@@ -60,6 +64,8 @@ elif a.force_loss:
     g.wall = torch.zeros(a.nodes, dtype=torch.bool, device=dev)
     g.wall[ring] = True
     crit = gfd.nn.ForceLoss(0.25, weight=1.0, mu=1e-3, wall={"pressure": 0.5, "shear": 0.5}, nodes="wall")
+elif a.residual_loss:
+    crit = gfd.nn.ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1)
 else:
     crit = gfd.nn.FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) if a.flow_loss else gfd.nn.GraphLoss(lambda_d=0.25)
 opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)        # (as GNN.fit does on the GPU)
