@@ -571,16 +571,15 @@ def segment_reduce(src: Tensor, csr, mean: bool, act: int, src_act: int) -> Tens
 
 
 # ------------------------------------------------------------------------------------- mesh derivatives
-class _MeshDerived(torch.autograd.Function):
-    """`MeshGradient.derived`: today's launch forward, its transpose (g4c_mesh_derived_adjoint) backward.  The map is linear in x and
-    the weights are constants: nothing is saved but the operator and the program."""
+class _StencilDerived(torch.autograd.Function):
+    """`MeshGradient.derived` and `MeshJet.derived`: the operator's plain launch forward, its transpose (g4c_mesh_derived_adjoint,
+    g4c_mesh_jet_adjoint) backward.  The map is linear in x and the table is a constant: nothing is saved but the operator and the
+    program."""
 
     @staticmethod
     def forward(ctx, x: Tensor, op, prog):
-        cur = _buf(op.n_nodes, int(prog.nd), op.g.device)
-        ops.mesh_derived(x.detach(), op.off, op.g, op.src, prog, cur)
         ctx.op, ctx.prog, ctx.nf = op, prog, int(x.size(1))
-        return cur
+        return op._launch(x.detach(), prog)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -589,28 +588,8 @@ class _MeshDerived(torch.autograd.Function):
         return ctx.op._adjoint(gy.contiguous(), ctx.prog, ctx.nf), None, None
 
 
-def mesh_derived(op, x: Tensor, prog) -> Tensor:
-    return _MeshDerived.apply(x, op, prog)
-
-
-class _MeshJet(torch.autograd.Function):
-    """`MeshJet.derived`: the plain launch forward, its transpose (g4c_mesh_jet_adjoint) backward.  The map is linear in x and the
-    rows are constants: nothing is saved but the operator and the program."""
-
-    @staticmethod
-    def forward(ctx, x: Tensor, op, prog):
-        out = ops.mesh_jet(x.detach(), op.off, op.c, op.src, prog)
-        ctx.op, ctx.prog, ctx.nf = op, prog, int(x.size(1))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy: Tensor):
-        return ctx.op._adjoint(gy.contiguous(), ctx.prog, ctx.nf), None, None
-
-
-def mesh_jet(op, x: Tensor, prog) -> Tensor:
-    return _MeshJet.apply(x, op, prog)
+def stencil_derived(op, x: Tensor, prog) -> Tensor:
+    return _StencilDerived.apply(x, op, prog)
 
 
 # ------------------------------------------------------------------------------------- off-node samples

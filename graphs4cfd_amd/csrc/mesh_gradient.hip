@@ -5,10 +5,12 @@
 //                              `cur`, to a strided snapshot slot, and reduced to per-step norms;
 //   g4c_mesh_derived_adjoint   the transpose of that linear map (its backward): a scatter to the senders taken as a gather over a
 //                              sender-side CSR, one thread per node in a fixed order.
+// The program, the forward's node body and the adjoint are the stencil operators' common ones (stencil_op.h, shared with mesh_jet.hip).
 // A node's sum is taken by ONE thread over its in-edges in CSR order, in fp32 without contraction: the bits are a function of the
 // data alone.  The norms follow the records' rule (rollout_record.hip): register accumulators, rows dealt gid, gid + grid, ..., a
 // xor butterfly per wave, the waves in order through LDS, one partial set per workgroup, a second one-workgroup launch.  No atomics.
 #include "g4c_common.h"
+#include "stencil_op.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
 // bits, and the fp64 weights differ from their restatement by the library's square root and division at most.
@@ -16,16 +18,11 @@
 
 namespace {
 
-constexpr int MG_THREADS = 256;
-constexpr int MG_MAX_BLOCKS = 1024;          // as the records: 4 workgroups of 256 per CU on 256 CUs
+constexpr int MG_THREADS = ST_THREADS;
 constexpr int MG_HEADER = 8;                 // scratch[0]: the step whose partials follow (-1: none); the partials start at 64 bytes
-constexpr int MAX_COLS = G4C_DERIVED_MAX_COLS, MAX_TERMS = G4C_DERIVED_MAX_TERMS, NSTAT = G4C_DERIVED_NSTAT;
-constexpr int MAX_USED = 8;                  // distinct fields one program may differentiate
-
-inline long long mg_blocks(long long n_nodes) {
-    const long long b = (n_nodes + MG_THREADS - 1) / MG_THREADS;
-    return b < 1 ? 1 : (b > MG_MAX_BLOCKS ? MG_MAX_BLOCKS : b);
-}
+constexpr int NSTAT = G4C_DERIVED_NSTAT;
+constexpr int MAX_USED = gradient_traits::MAX_USED;
+using mg_prog_t = stencil_prog_t<MAX_USED>;          // (read from the kernel arguments: in scalar registers, so it is kept small)
 
 // ------------------------------------------------------------------------------------------------------------------ weights
 template <int DIM>
@@ -131,16 +128,6 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_gradient_weights_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------ per step
-// The program as the kernel reads it (in scalar registers, so it is kept small): its distinct fields in the order of their first
-// appearance, and per term the derivative it picks — row = (place of its field in that list) * dim + axis — and its coefficient.
-struct mg_prog_t {
-    int nd;
-    unsigned char n_terms[MAX_COLS];
-    unsigned char row[MAX_COLS][MAX_TERMS];
-    float coef[MAX_COLS][MAX_TERMS];
-    int field[MAX_USED];
-};
-
 __device__ __forceinline__ double mg_combine(int j, double a, double b) { return j % NSTAT == G4C_DERIVED_MAX_ABS ? fmax(a, b) : a + b; }
 
 // The workgroup's 256 sets of nstat (<= MAX_COLS * NSTAT) values -> one set at dst: rec_block_reduce of rollout_record.hip with a
@@ -195,52 +182,12 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_derived_kernel(const float *_
     for (long long n = gid; n < n_nodes; n += stride) {
         // (no contraction: every product is rounded to fp32 before it is added, so a plain numpy.float32 loop gives the same bits)
 #pragma clang fp contract(off)
-        float xi[NU], G[NU][DIM];
-        const float *xr = x + n * d.x_ld;
-#pragma unroll
-        for (int f = 0; f < NU; ++f) {
-            xi[f] = xr[p.field[f]];
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) G[f][a] = 0.f;
-        }
-        const int e0 = d.off[n], e1 = d.off[n + 1];
-        // (four in-edges at a time: their index, row and weight loads are in flight together — the adds keep the CSR order)
-#pragma unroll 4
-        for (int e = e0; e < e1; ++e) {
-            const float *xs = x + (long long)d.src[e] * d.x_ld;
-            float ge[DIM];
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) ge[a] = d.g[(long long)e * DIM + a];
-#pragma unroll
-            for (int f = 0; f < NU; ++f) {
-                const float diff = xs[p.field[f]] - xi[f];
-#pragma unroll
-                for (int a = 0; a < DIM; ++a) {
-                    const float pr = ge[a] * diff;
-                    G[f][a] += pr;
-                }
-            }
-        }
-        // The program picks its derivatives by run-time (wave-uniform) numbers: they go through this thread's own column of LDS, so
-        // that the pick is an address, not a chain of selects over registers (whose hoisted conditions spilt hundreds of SGPRs).
-        // No barrier: a thread reads back only what it wrote itself.
-#pragma unroll
-        for (int f = 0; f < NU; ++f) {
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) mine[f * DIM + a][threadIdx.x] = G[f][a];
-        }
+        stencil_accumulate<DIM, NU, 4>(x, d.x_ld, n, d.g, d.src, d.off, p, mine);
         float *cur = d.cur + n * nd;
 #pragma unroll
         for (int c = 0; c < MAX_COLS; ++c) {
             if (c < nd) {                           // (wave-uniform, as every test on the program is)
-                float q = 0.f;
-#pragma unroll
-                for (int k = 0; k < MAX_TERMS; ++k) {
-                    if (k < p.n_terms[c]) {
-                        const float pr = p.coef[c][k] * mine[p.row[c][k]][threadIdx.x];
-                        q = k == 0 ? pr : q + pr;
-                    }
-                }
+                const float q = stencil_column<gradient_traits>(p, c, mine);
                 cur[c] = q;
                 if (snap) snap[n * nd + c] = q;
                 if constexpr (STATS) {
@@ -283,179 +230,13 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_derived_stats_kernel(const do
 
 template <int DIM, int NU>
 void derived_launch(const float *x, const g4c_mesh_derived_t &d, const mg_prog_t &p, long long n_nodes, hipStream_t s) {
-    const int blocks = (int)mg_blocks(n_nodes);
+    const int blocks = (int)stencil_blocks(n_nodes);
     if (d.stats) {
         mesh_derived_kernel<DIM, NU, true><<<dim3((unsigned)blocks), dim3(MG_THREADS), 0, s>>>(x, d, p, n_nodes);
         mesh_derived_stats_kernel<<<dim3(1), dim3(MG_THREADS), 0, s>>>(d.scratch, blocks, p.nd, d.stats, d.max_steps);
     } else {
         mesh_derived_kernel<DIM, NU, false><<<dim3((unsigned)blocks), dim3(MG_THREADS), 0, s>>>(x, d, p, n_nodes);
     }
-}
-
-template <int DIM>
-void derived_launch_dim(int nu, const float *x, const g4c_mesh_derived_t &d, const mg_prog_t &p, long long n_nodes, hipStream_t s) {
-    // (a list shorter than its instantiation is padded with its first field: the spare accumulators are never picked)
-    if (nu <= 1) derived_launch<DIM, 1>(x, d, p, n_nodes, s);
-    else if (nu == 2) derived_launch<DIM, 2>(x, d, p, n_nodes, s);
-    else if (nu == 3) derived_launch<DIM, 3>(x, d, p, n_nodes, s);
-    else if (nu == 4) derived_launch<DIM, 4>(x, d, p, n_nodes, s);
-    else derived_launch<DIM, MAX_USED>(x, d, p, n_nodes, s);
-}
-
-// The caller's program (1 <= nd <= MAX_COLS checked by the caller) as the kernels read it, and the number of distinct fields.
-int mg_program(const char *me, const g4c_derived_program_t *prog, int nf, int dim, mg_prog_t &u, int &nu) {
-    u.nd = prog->nd;
-    nu = 0;
-    for (int c = 0; c < prog->nd; ++c) {
-        G4C_REQUIRE(prog->n_terms[c] >= 1, G4C_EINVAL, "%s: column %d has %d terms", me, c, prog->n_terms[c]);
-        G4C_REQUIRE(prog->n_terms[c] <= MAX_TERMS, G4C_EUNSUPPORTED, "%s: column %d has %d terms (1 .. %d are supported)", me, c,
-                    prog->n_terms[c], MAX_TERMS);
-    }
-    for (int c = 0; c < prog->nd; ++c) {
-        u.n_terms[c] = (unsigned char)prog->n_terms[c];
-        for (int k = 0; k < prog->n_terms[c]; ++k) {
-            const int f = prog->field[c][k], a = prog->axis[c][k];
-            G4C_REQUIRE(f >= 0 && f < nf, G4C_EINVAL, "%s: column %d term %d: field %d out of range (nf=%d)", me, c, k, f, nf);
-            G4C_REQUIRE(a >= 0 && a < dim, G4C_EINVAL, "%s: column %d term %d: axis %d out of range (dim=%d)", me, c, k, a, dim);
-            int at = 0;
-            while (at < nu && u.field[at] != f) ++at;
-            if (at == nu) {
-                G4C_REQUIRE(nu < MAX_USED, G4C_EUNSUPPORTED, "%s: the program differentiates more than %d distinct fields", me, MAX_USED);
-                u.field[nu++] = f;
-            }
-            u.row[c][k] = (unsigned char)(at * dim + a);
-            u.coef[c][k] = prog->coef[c][k];
-        }
-    }
-    for (int f = nu; f < MAX_USED; ++f) u.field[f] = u.field[0];
-    return G4C_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ adjoint
-// mg_prog_t transposed: per derivative row r = (place of the field) * dim + axis the terms that pick it — t0[r] .. t0[r + 1], in
-// program order — each the column of gy it reads and its coefficient.  Read by wave-uniform numbers from the kernel arguments.
-struct mg_adj_t {
-    int nd, nu, nf;
-    unsigned char t0[MAX_USED * 3 + 1];
-    unsigned char col[MAX_COLS * MAX_TERMS];
-    float coef[MAX_COLS * MAX_TERMS];
-    int field[MAX_USED];
-};
-
-void mg_transpose(const mg_prog_t &u, int nu, int nf, int dim, mg_adj_t &t) {
-    t.nd = u.nd;
-    t.nu = nu;
-    t.nf = nf;
-    int n = 0;
-    for (int r = 0; r < MAX_USED * 3; ++r) {
-        t.t0[r] = (unsigned char)n;
-        if (r >= nu * dim) continue;
-        for (int c = 0; c < u.nd; ++c)
-            for (int k = 0; k < u.n_terms[c]; ++k)
-                if (u.row[c][k] == r) {
-                    t.col[n] = (unsigned char)c;
-                    t.coef[n] = u.coef[c][k];
-                    ++n;
-                }
-    }
-    t.t0[MAX_USED * 3] = (unsigned char)n;
-    for (int f = 0; f < MAX_USED; ++f) t.field[f] = u.field[f];
-}
-
-// H_i (include/g4c.h): every row from +0, its terms added in program order.  The counts and columns are the same in every lane.
-template <int DIM, int NU>
-__device__ __forceinline__ void mg_adjoint_rows(const float *__restrict__ gy, long long i, const mg_adj_t &p, float (&h)[NU][DIM]) {
-    const float *r = gy + i * p.nd;
-#pragma unroll
-    for (int f = 0; f < NU; ++f) {
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) {
-            float s = 0.f;
-            const int t1 = p.t0[f * DIM + a + 1];
-            for (int t = p.t0[f * DIM + a]; t < t1; ++t) {
-                const float pr = p.coef[t] * r[p.col[t]];
-                s += pr;
-            }
-            h[f][a] = s;
-        }
-    }
-}
-
-template <int DIM, int NU>
-__global__ __launch_bounds__(MG_THREADS) void mesh_derived_adjoint_kernel(
-    const float *__restrict__ gy, const float *__restrict__ g, const int *__restrict__ off, const float *__restrict__ out_g,
-    const int *__restrict__ out_dst, const int *__restrict__ out_off, const mg_adj_t p, long long n_nodes, float *__restrict__ gx) {
-    const long long stride = (long long)gridDim.x * MG_THREADS;
-    for (long long n = (long long)blockIdx.x * MG_THREADS + threadIdx.x; n < n_nodes; n += stride) {
-#pragma clang fp contract(off)
-        float acc[NU];
-#pragma unroll
-        for (int f = 0; f < NU; ++f) acc[f] = 0.f;
-        if (g) {          // (a mesh without a single edge has no tables: every row is zero)
-            // the edges this node sends, in ascending CSR position: their weights and receivers were copied into that order once per
-            // mesh, so they stream as the forward's do and only the receiver's row of gy is a gather (four edges at a time: their
-            // receiver, weight and row loads are in flight together — the adds keep the order)
-            const int q0 = out_off[n], q1 = out_off[n + 1];
-#pragma unroll 4
-            for (int q = q0; q < q1; ++q) {
-                float ge[DIM], h[NU][DIM];
-#pragma unroll
-                for (int a = 0; a < DIM; ++a) ge[a] = out_g[(long long)q * DIM + a];
-                mg_adjoint_rows<DIM, NU>(gy, out_dst[q], p, h);
-#pragma unroll
-                for (int f = 0; f < NU; ++f) {
-#pragma unroll
-                    for (int a = 0; a < DIM; ++a) {
-                        const float pr = ge[a] * h[f][a];
-                        acc[f] += pr;
-                    }
-                }
-            }
-            // the diagonal: this node's own in-edges in CSR order
-            float hj[NU][DIM];
-            mg_adjoint_rows<DIM, NU>(gy, n, p, hj);
-            const int e0 = off[n], e1 = off[n + 1];
-#pragma unroll 4
-            for (int e = e0; e < e1; ++e) {
-#pragma unroll
-                for (int a = 0; a < DIM; ++a) {
-                    const float ga = g[(long long)e * DIM + a];
-#pragma unroll
-                    for (int f = 0; f < NU; ++f) {
-                        const float pr = ga * hj[f][a];
-                        acc[f] -= pr;
-                    }
-                }
-            }
-        }
-        // every column of the row: a field the program does not name gets +0 (the fields of the list are distinct below nu)
-        float *row = gx + n * p.nf;
-        for (int c = 0; c < p.nf; ++c) {
-            float v = 0.f;
-#pragma unroll
-            for (int f = 0; f < NU; ++f)
-                if (f < p.nu && p.field[f] == c) v = acc[f];
-            row[c] = v;
-        }
-    }
-}
-
-template <int DIM, int NU>
-void adjoint_launch(const float *gy, const float *g, const int *off, const float *out_g, const int *out_dst, const int *out_off,
-                    const mg_adj_t &p, long long n_nodes, float *gx, hipStream_t s) {
-    mesh_derived_adjoint_kernel<DIM, NU><<<dim3((unsigned)mg_blocks(n_nodes)), dim3(MG_THREADS), 0, s>>>(gy, g, off, out_g, out_dst, out_off, p,
-                                                                                                      n_nodes, gx);
-}
-
-template <int DIM>
-void adjoint_launch_dim(int nu, const float *gy, const float *g, const int *off, const float *out_g, const int *out_dst, const int *out_off,
-                        const mg_adj_t &p, long long n_nodes, float *gx, hipStream_t s) {
-    // (the rows of a list shorter than its instantiation have no terms: their accumulators stay +0 and are not written)
-    if (nu <= 1) adjoint_launch<DIM, 1>(gy, g, off, out_g, out_dst, out_off, p, n_nodes, gx, s);
-    else if (nu == 2) adjoint_launch<DIM, 2>(gy, g, off, out_g, out_dst, out_off, p, n_nodes, gx, s);
-    else if (nu == 3) adjoint_launch<DIM, 3>(gy, g, off, out_g, out_dst, out_off, p, n_nodes, gx, s);
-    else if (nu == 4) adjoint_launch<DIM, 4>(gy, g, off, out_g, out_dst, out_off, p, n_nodes, gx, s);
-    else adjoint_launch<DIM, MAX_USED>(gy, g, off, out_g, out_dst, out_off, p, n_nodes, gx, s);
 }
 
 }  // namespace
@@ -486,7 +267,7 @@ extern "C" int g4c_mesh_gradient_weights(const int32_t *off, const int32_t *perm
 extern "C" int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd) {
     G4C_REQUIRE(n_nodes >= 0 && nd >= 1, G4C_EINVAL, "g4c_mesh_derived_scratch_doubles: bad sizes n_nodes=%lld nd=%d", (long long)n_nodes, nd);
     G4C_REQUIRE(nd <= MAX_COLS, G4C_EUNSUPPORTED, "g4c_mesh_derived_scratch_doubles: nd=%d columns (1 .. %d are supported)", nd, MAX_COLS);
-    return MG_HEADER + mg_blocks(n_nodes) * nd * NSTAT;
+    return MG_HEADER + stencil_blocks(n_nodes) * nd * NSTAT;
 }
 
 extern "C" int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d, const g4c_derived_program_t *prog, int64_t n_nodes,
@@ -501,7 +282,7 @@ extern "C" int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d, con
     G4C_REQUIRE(prog->nd <= MAX_COLS, G4C_EUNSUPPORTED, "%s: nd=%d columns (1 .. %d are supported)", me, prog->nd, MAX_COLS);
     mg_prog_t u = {};
     int nu = 0;
-    if (const int rc = mg_program(me, prog, d->nf, d->dim, u, nu)) return rc;
+    if (const int rc = stencil_program<gradient_traits>(me, prog, d->nf, d->dim, d->dim, u, nu)) return rc;
     G4C_REQUIRE(d->every > 0 || !d->snap, G4C_EINVAL, "%s: a snapshot buffer with every=0", me);
     G4C_REQUIRE(!d->stats || d->scratch, G4C_EINVAL, "%s: stats without scratch", me);
     G4C_REQUIRE(d->step || (!d->snap && !d->stats), G4C_EINVAL, "%s: snapshots or stats without a step index", me);
@@ -512,41 +293,18 @@ extern "C" int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d, con
     hipStream_t s = (hipStream_t)stream;
     g4c_mesh_derived_t dd = *d;
     if (dd.every == 0 || dd.n_snap == 0) dd.snap = nullptr;
-    if (dd.dim == 2)
-        derived_launch_dim<2>(nu, x, dd, u, n_nodes, s);
-    else
-        derived_launch_dim<3>(nu, x, dd, u, n_nodes, s);
+    launch_nu<MAX_USED>(nu, [&](auto NU) {
+        if (dd.dim == 2)
+            derived_launch<2, decltype(NU)::value>(x, dd, u, n_nodes, s);
+        else
+            derived_launch<3, decltype(NU)::value>(x, dd, u, n_nodes, s);
+    });
     return g4c::check_launch(me);
 }
 
 extern "C" int g4c_mesh_derived_adjoint(const float *gy, const g4c_derived_program_t *prog, int32_t dim, int32_t nf, const float *g,
                                         const int32_t *off, const float *out_g, const int32_t *out_dst, const int32_t *out_off,
                                         int64_t n_nodes, int64_t n_edges, float *gx, void *stream) {
-    const char *me = "g4c_mesh_derived_adjoint";
-    G4C_REQUIRE(prog, G4C_EINVAL, "%s: null pointer", me);
-    G4C_REQUIRE(n_nodes >= 0 && n_edges >= 0 && n_edges <= 0x7fffffffll && nf >= 1 && prog->nd >= 1, G4C_EINVAL,
-                "%s: bad sizes n_nodes=%lld n_edges=%lld nf=%d nd=%d", me, (long long)n_nodes, (long long)n_edges, nf, prog->nd);
-    G4C_REQUIRE(dim == 2 || dim == 3, G4C_EUNSUPPORTED, "%s: dim=%d (2 or 3 are supported)", me, dim);
-    G4C_REQUIRE(prog->nd <= MAX_COLS, G4C_EUNSUPPORTED, "%s: nd=%d columns (1 .. %d are supported)", me, prog->nd, MAX_COLS);
-    mg_prog_t u = {};
-    int nu = 0;
-    if (const int rc = mg_program(me, prog, nf, dim, u, nu)) return rc;
-    if (n_nodes == 0) return G4C_OK;
-    G4C_REQUIRE(gy && gx, G4C_EINVAL, "%s: null pointer", me);
-    G4C_REQUIRE(n_edges == 0 || (g && off && out_g && out_dst && out_off), G4C_EINVAL, "%s: null pointer", me);
-    {          // gx [n_nodes, nf] and gy [n_nodes, nd] must not share a byte: a thread reads rows of gy that other threads' rows of gx would cover
-        const char *a = (const char *)gy, *b = (const char *)gx;
-        const long long na = n_nodes * prog->nd * 4ll, nb = n_nodes * nf * 4ll;
-        G4C_REQUIRE(a + na <= b || b + nb <= a, G4C_EINVAL, "%s: gx aliases gy", me);
-    }
-    mg_adj_t t = {};
-    mg_transpose(u, nu, nf, dim, t);
-    g4c::DeviceGuard on_device(gx);
-    hipStream_t s = (hipStream_t)stream;
-    if (n_edges == 0) g = nullptr;
-    if (dim == 2)
-        adjoint_launch_dim<2>(nu, gy, g, off, out_g, out_dst, out_off, t, n_nodes, gx, s);
-    else
-        adjoint_launch_dim<3>(nu, gy, g, off, out_g, out_dst, out_off, t, n_nodes, gx, s);
-    return g4c::check_launch(me);
+    return stencil_adjoint<gradient_traits, 2, 3>("g4c_mesh_derived_adjoint", 0x7fffffffll, gy, prog, dim, nf, g, off, out_g, out_dst,
+                                                  out_off, n_nodes, n_edges, gx, stream);
 }

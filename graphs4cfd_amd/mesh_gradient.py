@@ -129,7 +129,83 @@ def check_mesh(graph, power, edge_vectors) -> int:
     return int(edge_vectors.size(1))
 
 
-class MeshGradient:
+class _StencilOperator:
+    """What `MeshGradient` and `MeshJet` share: a table of fp32 rows per stencil entry in CSR order (`off`, `src`, and the table under
+    the attribute `_table` names — read at every call), applied by one launch per call and transposed by one launch in the backward.
+    A subclass names its table and supplies `_columns` / `_terms` (names -> labels / program terms), `_order` (`ops.derived_program`),
+    `_launch` (the plain forward) and `_adjoint_op` (the `ops` function of the transpose)."""
+
+    _table = _columns = _terms = _order = _adjoint_op = None
+
+    def _launch(self, x: torch.Tensor, prog) -> torch.Tensor:
+        raise NotImplementedError
+
+    def columns(self, names) -> List[str]:
+        return type(self)._columns(names, self.dim)
+
+    def program(self, names, nf: int, velocity=None, field_scale=None):
+        return ops.derived_program(type(self)._terms(names, self.dim, int(nf), velocity, field_scale), int(nf), self.dim, order=self._order)
+
+    def _x(self, x) -> torch.Tensor:
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or int(x.size(0)) != self.n_nodes or int(x.size(1)) < 1:
+            raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, F], got {getattr(x, 'dtype', type(x).__name__)} "
+                             f"{tuple(getattr(x, 'shape', ()))}")
+        return x
+
+    def derived(self, x: torch.Tensor, names, velocity=None, field_scale=None) -> torch.Tensor:
+        """[N, nd]: the columns of `names` of the fields x [N, F] (float32, rows of unit stride).  `velocity` defaults to fields
+        0 .. dim − 1; `field_scale` [F] (default ones) multiplies into the coefficients — it undoes an affine scaling of the fields
+        (the offsets drop out of every derivative)."""
+        x = self._x(x)
+        prog = self.program(names, int(x.size(1)), velocity, field_scale)
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd as _ag
+            return _ag.stencil_derived(self, x, prog)
+        return self._launch(x, prog)
+
+    def _sender_side(self):
+        """(out_off, out_table, out_dst): the stencil entries grouped by sender, ascending CSR position within a sender — the offsets
+        of that grouping, and the rows and receivers copied into its order.  Built on the first adjoint and kept: the plain forward
+        pays nothing."""
+        if self._adjoint_tables is None:
+            table = getattr(self, self._table)
+            n_entries = int(self.src.numel())
+            deg = (self.off[1:] - self.off[:-1]).to(torch.int64)
+            dst = torch.repeat_interleave(torch.arange(self.n_nodes, dtype=torch.int32, device=self.off.device), deg, output_size=n_entries)
+            out = plan.gather_csr(self.src, self.n_nodes)
+            if out.perm is not None:          # (None: the senders are grouped already)
+                perm = out.perm.to(torch.int64)
+                self._adjoint_tables = (out.off, table.index_select(0, perm).contiguous(), dst.index_select(0, perm).contiguous())
+            else:
+                self._adjoint_tables = (out.off, table, dst.contiguous())
+        return self._adjoint_tables
+
+    def _gy(self, gy, nd: int) -> torch.Tensor:
+        device = getattr(self, self._table).device
+        if not torch.is_tensor(gy) or gy.dtype != torch.float32 or gy.dim() != 2 or tuple(gy.shape) != (self.n_nodes, nd):
+            raise ValueError(f"gy: expected a float32 tensor [{self.n_nodes}, {nd}] (one column per derived column), got "
+                             f"{getattr(gy, 'dtype', type(gy).__name__)} {tuple(getattr(gy, 'shape', ()))}")
+        if gy.device != device:
+            raise ValueError(f"gy: on '{gy.device}', the operator is on '{device}' (there is no CPU fallback)")
+        return gy.detach().contiguous()
+
+    def _adjoint(self, gy: torch.Tensor, prog, nf: int) -> torch.Tensor:
+        out_off, out_table, out_dst = self._sender_side()
+        return type(self)._adjoint_op(gy, self.off, getattr(self, self._table), out_off, out_table, out_dst, prog, nf)
+
+    def adjoint(self, gy: torch.Tensor, names, nf: int, velocity=None, field_scale=None) -> torch.Tensor:
+        """[N, nf]: the transpose of `derived(·, names, velocity, field_scale)` on nf fields, applied to gy [N, nd] (float32; made
+        dense first) — for all x and gy, ⟨derived(x), gy⟩ = ⟨x, adjoint(gy)⟩ up to rounding.  One launch (`g4c_mesh_derived_adjoint`
+        or `g4c_mesh_jet_adjoint`): a gather over the entries a node SENDS, in a fixed order, no atomics.  A field `names` does not
+        differentiate gets zeros."""
+        if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
+            raise ValueError(f"nf: expected the number of fields (>= 1), got {nf!r}")
+        terms = type(self)._terms(names, self.dim, nf, velocity, field_scale)
+        gy = self._gy(gy, len(terms))
+        return self._adjoint(gy, ops.derived_program(terms, nf, self.dim, order=self._order), nf)
+
+
+class MeshGradient(_StencilOperator):
     """The least-squares gradient over the edges of `graph` (a Graph on the GPU with `edge_index` [2, E], row = sender, col =
     receiver, and `pos`), built once; `power` 0, 1 or 2 weighs an edge by |d|^(−power).
 
@@ -163,68 +239,13 @@ class MeshGradient:
         self.degenerate = degenerate.bool()
         self._adjoint_tables = None
 
-    def columns(self, names) -> List[str]:
-        return derived_columns(names, self.dim)
+    _table, _order = "g", 1
+    _columns, _terms, _adjoint_op = staticmethod(derived_columns), staticmethod(derived_terms), staticmethod(ops.mesh_derived_adjoint)
 
-    def program(self, names, nf: int, velocity=None, field_scale=None):
-        return ops.derived_program(derived_terms(names, self.dim, int(nf), velocity, field_scale), int(nf), self.dim)
-
-    def _x(self, x) -> torch.Tensor:
-        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or int(x.size(0)) != self.n_nodes or int(x.size(1)) < 1:
-            raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, F], got {getattr(x, 'dtype', type(x).__name__)} "
-                             f"{tuple(getattr(x, 'shape', ()))}")
-        return x
-
-    def derived(self, x: torch.Tensor, names, velocity=None, field_scale=None) -> torch.Tensor:
-        """[N, nd]: the columns of `names` of the fields x [N, F] (float32, rows of unit stride).  `velocity` defaults to fields
-        0 .. dim − 1; `field_scale` [F] (default ones) multiplies into the coefficients — it undoes an affine scaling of the fields
-        (the offsets drop out of a gradient)."""
-        x = self._x(x)
-        if torch.is_grad_enabled() and x.requires_grad:
-            from . import autograd as _ag
-            return _ag.mesh_derived(self, x, self.program(names, int(x.size(1)), velocity, field_scale))
-        prog = self.program(names, int(x.size(1)), velocity, field_scale)
+    def _launch(self, x: torch.Tensor, prog) -> torch.Tensor:
         cur = torch.empty((self.n_nodes, int(prog.nd)), dtype=torch.float32, device=self.g.device)
         ops.mesh_derived(x, self.off, self.g, self.src, prog, cur)
         return cur
-
-    def _sender_side(self):
-        """(out_off, out_g, out_dst): the edges grouped by sender, ascending CSR position within a sender — the offsets of that
-        grouping, and the weights and receivers copied into its order.  Built on the first adjoint and kept: the plain forward pays
-        nothing."""
-        if self._adjoint_tables is None:
-            n_edges = int(self.src.numel())
-            deg = (self.off[1:] - self.off[:-1]).to(torch.int64)
-            dst = torch.repeat_interleave(torch.arange(self.n_nodes, dtype=torch.int32, device=self.off.device), deg, output_size=n_edges)
-            out = plan.gather_csr(self.src, self.n_nodes)
-            if out.perm is not None:          # (None: the senders are grouped already)
-                perm = out.perm.to(torch.int64)
-                self._adjoint_tables = (out.off, self.g.index_select(0, perm).contiguous(), dst.index_select(0, perm).contiguous())
-            else:
-                self._adjoint_tables = (out.off, self.g, dst.contiguous())
-        return self._adjoint_tables
-
-    def _gy(self, gy, nd: int) -> torch.Tensor:
-        if not torch.is_tensor(gy) or gy.dtype != torch.float32 or gy.dim() != 2 or tuple(gy.shape) != (self.n_nodes, nd):
-            raise ValueError(f"gy: expected a float32 tensor [{self.n_nodes}, {nd}] (one column per derived column), got "
-                             f"{getattr(gy, 'dtype', type(gy).__name__)} {tuple(getattr(gy, 'shape', ()))}")
-        if gy.device != self.g.device:
-            raise ValueError(f"gy: on '{gy.device}', the operator is on '{self.g.device}' (there is no CPU fallback)")
-        return gy.detach().contiguous()
-
-    def _adjoint(self, gy: torch.Tensor, prog, nf: int) -> torch.Tensor:
-        out_off, out_g, out_dst = self._sender_side()
-        return ops.mesh_derived_adjoint(gy, self.off, self.g, out_off, out_g, out_dst, prog, nf)
-
-    def adjoint(self, gy: torch.Tensor, names, nf: int, velocity=None, field_scale=None) -> torch.Tensor:
-        """[N, nf]: the transpose of `derived(·, names, velocity, field_scale)` on nf fields, applied to gy [N, nd] (float32; made
-        dense first) — for all x and gy, ⟨derived(x), gy⟩ = ⟨x, adjoint(gy)⟩ up to rounding.  One launch (`g4c_mesh_derived_adjoint`): a
-        gather over the edges a node SENDS, in a fixed order, no atomics.  A field `names` does not differentiate gets zeros."""
-        if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
-            raise ValueError(f"nf: expected the number of fields (>= 1), got {nf!r}")
-        terms = derived_terms(names, self.dim, nf, velocity, field_scale)
-        gy = self._gy(gy, len(terms))
-        return self._adjoint(gy, ops.derived_program(terms, nf, self.dim), nf)
 
     def gradient(self, x: torch.Tensor) -> torch.Tensor:
         """[N, F, dim]: ∂_a x[:, f]."""

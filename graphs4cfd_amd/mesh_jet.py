@@ -21,7 +21,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib, ops, plan
-from .mesh_gradient import AXES, _names, check_mesh, derived_columns, derived_terms
+from .mesh_gradient import AXES, _names, _StencilOperator, check_mesh, derived_columns, derived_terms
 
 MAX_COLUMNS = _lib.DERIVED_MAX_COLS
 MAX_K = 32
@@ -109,7 +109,7 @@ def check_stencil(graph, k, power, edge_vectors) -> int:
     return dim
 
 
-class MeshJet:
+class MeshJet(_StencilOperator):
     """The quadratic least-squares fit over a stencil of `graph` (a Graph on the GPU), built once; `power` 0, 1 or 2 weighs a stencil
     entry by |d|^(−power).
 
@@ -178,66 +178,11 @@ class MeshJet:
         off = torch.arange(0, n * k + 1, k, dtype=torch.int32, device=pos.device)
         return SimpleNamespace(off=off, perm=None, n=n * k), src.to(torch.int32), rel
 
-    def columns(self, names) -> List[str]:
-        return jet_columns(names, self.dim)
+    _table, _order = "c", 2
+    _columns, _terms, _adjoint_op = staticmethod(jet_columns), staticmethod(jet_terms), staticmethod(ops.mesh_jet_adjoint)
 
-    def program(self, names, nf: int, velocity=None, field_scale=None):
-        return ops.derived_program(jet_terms(names, self.dim, int(nf), velocity, field_scale), int(nf), self.dim, order=2)
-
-    def _x(self, x) -> torch.Tensor:
-        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or int(x.size(0)) != self.n_nodes or int(x.size(1)) < 1:
-            raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, F], got {getattr(x, 'dtype', type(x).__name__)} "
-                             f"{tuple(getattr(x, 'shape', ()))}")
-        return x
-
-    def derived(self, x: torch.Tensor, names, velocity=None, field_scale=None) -> torch.Tensor:
-        """[N, nd]: the columns of `names` of the fields x [N, F] (float32, rows of unit stride).  `velocity` defaults to fields
-        0 .. dim − 1; `field_scale` [F] (default ones) multiplies into the coefficients — it undoes an affine scaling of the fields
-        (the offsets drop out of every derivative)."""
-        x = self._x(x)
-        prog = self.program(names, int(x.size(1)), velocity, field_scale)
-        if torch.is_grad_enabled() and x.requires_grad:
-            from . import autograd as _ag
-            return _ag.mesh_jet(self, x, prog)
+    def _launch(self, x: torch.Tensor, prog) -> torch.Tensor:
         return ops.mesh_jet(x, self.off, self.c, self.src, prog)
-
-    def _sender_side(self):
-        """(out_off, out_c, out_dst): the stencil entries grouped by sender, ascending CSR position within a sender — the offsets of
-        that grouping, and the rows and receivers copied into its order.  Built on the first adjoint and kept: the plain forward pays
-        nothing."""
-        if self._adjoint_tables is None:
-            n_entries = int(self.src.numel())
-            deg = (self.off[1:] - self.off[:-1]).to(torch.int64)
-            dst = torch.repeat_interleave(torch.arange(self.n_nodes, dtype=torch.int32, device=self.off.device), deg, output_size=n_entries)
-            out = plan.gather_csr(self.src, self.n_nodes)
-            if out.perm is not None:          # (None: the senders are grouped already)
-                perm = out.perm.to(torch.int64)
-                self._adjoint_tables = (out.off, self.c.index_select(0, perm).contiguous(), dst.index_select(0, perm).contiguous())
-            else:
-                self._adjoint_tables = (out.off, self.c, dst.contiguous())
-        return self._adjoint_tables
-
-    def _gy(self, gy, nd: int) -> torch.Tensor:
-        if not torch.is_tensor(gy) or gy.dtype != torch.float32 or gy.dim() != 2 or tuple(gy.shape) != (self.n_nodes, nd):
-            raise ValueError(f"gy: expected a float32 tensor [{self.n_nodes}, {nd}] (one column per derived column), got "
-                             f"{getattr(gy, 'dtype', type(gy).__name__)} {tuple(getattr(gy, 'shape', ()))}")
-        if gy.device != self.c.device:
-            raise ValueError(f"gy: on '{gy.device}', the operator is on '{self.c.device}' (there is no CPU fallback)")
-        return gy.detach().contiguous()
-
-    def _adjoint(self, gy: torch.Tensor, prog, nf: int) -> torch.Tensor:
-        out_off, out_c, out_dst = self._sender_side()
-        return ops.mesh_jet_adjoint(gy, self.off, self.c, out_off, out_c, out_dst, prog, nf)
-
-    def adjoint(self, gy: torch.Tensor, names, nf: int, velocity=None, field_scale=None) -> torch.Tensor:
-        """[N, nf]: the transpose of `derived(·, names, velocity, field_scale)` on nf fields, applied to gy [N, nd] (float32; made
-        dense first) — for all x and gy, ⟨derived(x), gy⟩ = ⟨x, adjoint(gy)⟩ up to rounding.  One launch (`g4c_mesh_jet_adjoint`): a
-        gather over the entries a node SENDS, in a fixed order, no atomics.  A field `names` does not differentiate gets zeros."""
-        if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
-            raise ValueError(f"nf: expected the number of fields (>= 1), got {nf!r}")
-        terms = jet_terms(names, self.dim, nf, velocity, field_scale)
-        gy = self._gy(gy, len(terms))
-        return self._adjoint(gy, ops.derived_program(terms, nf, self.dim, order=2), nf)
 
     def __repr__(self):
         stencil = "in-edges" if self.k is None else f"k={self.k}"

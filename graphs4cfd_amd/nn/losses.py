@@ -30,7 +30,102 @@ def _number(v, name, what="a finite number >= 0"):
     return float(v)
 
 
-class FlowLoss(nn.Module):
+def _power(v, noun):
+    if isinstance(v, bool) or not isinstance(v, int) or v not in (0, 1, 2):
+        raise ValueError(f"power: expected 0, 1 or 2 ({noun} weighs |d|^-power), got {v!r}")
+    return v
+
+
+def _field_numbers(v, name, noun, lengths=None, distinct=False):
+    """None, or `v` as a tuple of field numbers >= 0: `lengths` the allowed counts (None: any but none), `distinct`: none twice."""
+    if v is None:
+        return None
+    try:
+        v = tuple(v)
+    except TypeError:
+        raise ValueError(f"{name}: expected {noun}, got {v!r}") from None
+    if ((not v if lengths is None else len(v) not in lengths) or any(isinstance(f, bool) or not isinstance(f, int) or f < 0 for f in v)
+            or (distinct and len(set(v)) != len(v))):
+        raise ValueError(f"{name}: expected {noun}, got {v!r}")
+    return v
+
+
+def _per_field(v, name, noun):
+    """None, or `v` (a tensor or a sequence) as a list of floats: one finite `noun` per field."""
+    if v is None:
+        return None
+    try:
+        v = [float(q) for q in (v.tolist() if torch.is_tensor(v) else v)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: expected one {noun} per field, got {v!r}") from None
+    if not v or not all(math.isfinite(q) for q in v):
+        raise ValueError(f"{name}: expected one finite {noun} per field, got {v!r}")
+    return v
+
+
+def _attribute(v, name, what="a graph attribute", kind=ValueError):
+    if v is not None and (not isinstance(v, str) or not v):
+        raise kind(f"{name}: expected None or the name of {what}, got {v!r}")
+    return v
+
+
+def _values(v, noun):
+    if v is not None and (not isinstance(v, str) or not v or "index" in v):
+        raise ValueError(f"values: expected None or the name of a graph attribute holding {noun} (without 'index' in it: such "
+                         f"attributes collate along the last dimension), got {v!r}")
+    return v
+
+
+class _OperatorLoss(nn.Module):
+    """What `FlowLoss`, `SampleLoss`, `ForceLoss` and `ResidualLoss` share: node_weight · `GraphLoss(lambda_d)` in front of their own
+    term, the operator that term needs — built from tensors of the batch and kept while those are the same objects, unmodified —
+    and the columns of an observed attribute that belong to one output step."""
+
+    def __init__(self, lambda_d, weight=1.0, node_weight=1.0):
+        super().__init__()
+        self.lambda_d = _number(lambda_d, "lambda_d")
+        self.weight = _number(weight, "weight", "a finite weight >= 0")
+        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
+        self.base = GraphLoss(lambda_d)
+        self._cache = None          # ([(tensor or None, its version), ...], what `build` returned)
+        self.builds = 0             # operators built so far (a batch seen again costs none)
+
+    def keep(self, tensors, build):
+        """`build()`, or what it returned last time when every entry of `tensors` (tensors, or None) is the object it was then,
+        unmodified — identity and `_version`: an address says nothing, the allocator hands a freed batch's to the next one.  One
+        entry is kept."""
+        hit = self._cache
+        if (hit is None or len(hit[0]) != len(tensors)
+                or not all(a is t and (not torch.is_tensor(t) or v == t._version) for (a, v), t in zip(hit[0], tensors))):
+            self._cache = ([(t, t._version if torch.is_tensor(t) else None) for t in tensors], build())
+            self.builds += 1
+        return self._cache[1]
+
+    def node_term(self, graph, pred, target):
+        """node_weight · GraphLoss, or None at node_weight == 0; at exactly 1.0 it is not multiplied (GraphLoss's bits)."""
+        if not self.node_weight > 0:
+            return None
+        loss = self.base(graph, pred, target)
+        return loss if self.node_weight == 1.0 else self.node_weight * loss
+
+    @staticmethod
+    def nothing_more(pred, loss):
+        """The value when the loss's own term is absent: the node term, or a zero that still depends on pred."""
+        return pred.sum() * 0.0 if loss is None else loss
+
+    @staticmethod
+    def observed(graph, name, rows, per_step, step, what):
+        """Columns per_step · t .. per_step · (t + 1) of graph.<name> [rows, per_step · T] for output step t = `step`."""
+        obs = getattr(graph, name, None)
+        if not torch.is_tensor(obs) or obs.dim() != 2 or int(obs.size(0)) != rows:
+            raise ValueError(f"values: graph.{name}: expected {what}, got {tuple(getattr(obs, 'shape', ()))}")
+        t = int(step)
+        if t < 0 or per_step * (t + 1) > int(obs.size(1)):
+            raise ValueError(f"step: {t}: graph.{name} holds {int(obs.size(1))} columns, {per_step} per step")
+        return obs[:, per_step * t: per_step * (t + 1)]
+
+
+class FlowLoss(_OperatorLoss):
     """`GraphLoss(lambda_d)` plus penalties on what the mesh's least-squares gradient (`gfd.MeshGradient`) makes of the prediction
     (new functionality — the reference has none):
 
@@ -49,8 +144,7 @@ class FlowLoss(nn.Module):
     objects, unmodified — `Trainer.train_epoch` calls the loss once per output step of the same batch.  HIP device only."""
 
     def __init__(self, lambda_d=0, terms=None, zero=("div",), power=2, velocity=None, field_scale=None, edge_vectors=None):
-        super().__init__()
-        self.lambda_d = _number(lambda_d, "lambda_d")
+        super().__init__(lambda_d)
         if terms is None:
             terms = {}
         if not isinstance(terms, dict):
@@ -66,33 +160,16 @@ class FlowLoss(nn.Module):
             raise ValueError(f"zero: expected a tuple of names, got {zero!r}") from None
         for name in zero:
             self._name(name, "zero")
-        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-            raise ValueError(f"power: expected 0, 1 or 2 (an edge weighs |d|^-power), got {power!r}")
-        if velocity is not None:
-            try:
-                velocity = tuple(velocity)
-            except TypeError:
-                raise ValueError(f"velocity: expected 2 or 3 field numbers, got {velocity!r}") from None
-            if len(velocity) not in (2, 3) or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in velocity):
-                raise ValueError(f"velocity: expected 2 or 3 field numbers, got {velocity!r}")
-        if field_scale is not None:
-            try:
-                field_scale = [float(v) for v in (field_scale.tolist() if torch.is_tensor(field_scale) else field_scale)]
-            except (TypeError, ValueError):
-                raise ValueError(f"field_scale: expected one factor per field, got {field_scale!r}") from None
-            if not field_scale or not all(math.isfinite(v) for v in field_scale):
-                raise ValueError(f"field_scale: expected one finite factor per field, got {field_scale!r}")
-        if edge_vectors is not None and (not isinstance(edge_vectors, str) or not edge_vectors):
-            raise ValueError(f"edge_vectors: expected None or the name of a graph attribute holding [E, dim] vectors, got {edge_vectors!r}")
-        self.base = GraphLoss(lambda_d)
+        power = _power(power, "an edge")
+        velocity = _field_numbers(velocity, "velocity", "2 or 3 field numbers", lengths=(2, 3))
+        field_scale = _per_field(field_scale, "field_scale", "factor")
+        _attribute(edge_vectors, "edge_vectors", "a graph attribute holding [E, dim] vectors")
         live = [(name, float(w)) for name, w in terms.items() if w > 0]
         self.terms = dict(terms)
         self.zero = zero
         self._on_error = [(n, w) for n, w in live if n not in zero]          # D(pred − target)
         self._on_pred = [(n, w) for n, w in live if n in zero]               # D(pred)
         self.power, self.velocity, self.field_scale, self.edge_vectors = power, velocity, field_scale, edge_vectors
-        self._cache = None          # (edge_index, its version, the vectors / pos tensor, its version, MeshGradient)
-        self.builds = 0             # operators built so far (a batch seen again costs none)
 
     @staticmethod
     def _name(name, arg):
@@ -111,17 +188,10 @@ class FlowLoss(nn.Module):
             vec = getattr(graph, self.edge_vectors, None)
             if not torch.is_tensor(vec):
                 raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
-        hit = self._cache
-        if (hit is not None and hit[0] is ei and hit[2] is vec and torch.is_tensor(ei) and torch.is_tensor(vec) and hit[1] == ei._version
-                and hit[3] == vec._version):
-            return hit[4]
-        op = MeshGradient(graph, power=self.power, edge_vectors=None if self.edge_vectors is None else vec)
-        self._cache = (ei, ei._version, vec, vec._version, op)
-        self.builds += 1
-        return op
+        return self.keep([ei, vec], lambda: MeshGradient(graph, power=self.power, edge_vectors=None if self.edge_vectors is None else vec))
 
     def forward(self, graph, pred, target):
-        loss = self.base(graph, pred, target)
+        loss = self.node_term(graph, pred, target)
         if not self._on_error and not self._on_pred:
             return loss
         op = self.operator(graph)
@@ -140,7 +210,7 @@ class FlowLoss(nn.Module):
         return loss
 
 
-class SampleLoss(nn.Module):
+class SampleLoss(_OperatorLoss):
     """`GraphLoss(lambda_d)` plus the error at points that are no nodes — sparse, off-node observations: a PIV window, a wake rake, a
     few taps (new functionality — the reference has none):
 
@@ -167,50 +237,34 @@ class SampleLoss(nn.Module):
     takes_step = True
 
     def __init__(self, points, lambda_d=0, weight=1.0, node_weight=1.0, values=None, fields=None, k=None, power=2, max_distance=None):
-        super().__init__()
         from ..point_sampler import MAX_K
         if not torch.is_tensor(points) or not points.dtype.is_floating_point or points.dim() != 2 or int(points.size(1)) not in (2, 3):
             raise ValueError(f"points: expected a floating-point tensor [P, 2] or [P, 3], got "
                              f"{getattr(points, 'dtype', type(points).__name__)} {tuple(getattr(points, 'shape', ()))}")
         if points.device.type == "cpu" and not bool(torch.isfinite(points).all()):
             raise ValueError("points: a coordinate that is not finite")
-        self.lambda_d = _number(lambda_d, "lambda_d")
-        self.weight = _number(weight, "weight", "a finite weight >= 0")
-        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
-        if values is not None and (not isinstance(values, str) or not values or "index" in values):
-            raise ValueError(f"values: expected None or the name of a graph attribute holding [P, F'·T] observations (without 'index' in "
-                             f"it: such attributes collate along the last dimension), got {values!r}")
-        if fields is not None:
-            try:
-                fields = tuple(fields)
-            except TypeError:
-                raise ValueError(f"fields: expected distinct column numbers >= 0, got {fields!r}") from None
-            if not fields or any(isinstance(f, bool) or not isinstance(f, int) or f < 0 for f in fields) or len(set(fields)) != len(fields):
-                raise ValueError(f"fields: expected distinct column numbers >= 0, got {fields!r}")
+        super().__init__(lambda_d, weight, node_weight)
+        values = _values(values, "[P, F'·T] observations")
+        fields = _field_numbers(fields, "fields", "distinct column numbers >= 0", distinct=True)
         if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K):
             raise ValueError(f"k: expected None or an integer 1 <= k <= {MAX_K}, got {k!r}")
-        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-            raise ValueError(f"power: expected 0, 1 or 2 (a neighbour weighs |d|^-power), got {power!r}")
+        power = _power(power, "a neighbour")
         if max_distance is not None:
             max_distance = _number(max_distance, "max_distance", "None or a finite distance >= 0")
-        self.base = GraphLoss(lambda_d)
         self.points, self.values, self.fields, self.k, self.power, self.max_distance = points.detach(), values, fields, k, power, max_distance
-        self._cache = None          # (pos, its version, batch, its version, sampler, kept mask or None, kept count)
-        self.builds = 0             # samplers built so far (a batch seen again costs none)
 
     def sampler(self, graph):
         """(the `PointSampler` of `graph` — of all its graphs, when it is a batch —, the bool [P] mask of the kept points or None for
         all, their number): the cached ones while graph.pos and graph.batch are the objects they were built from, unmodified
         (identity and `_version`, never an address)."""
-        from ..graph import Graph
-        from ..point_sampler import PointSampler
         pos, batch = getattr(graph, "pos", None), getattr(graph, "batch", None)
         if not torch.is_tensor(pos):
             raise ValueError("graph: SampleLoss needs graph.pos")
-        hit = self._cache
-        if (hit is not None and hit[0] is pos and hit[1] == pos._version and hit[2] is batch
-                and (batch is None or hit[3] == batch._version)):
-            return hit[4:]
+        return self.keep([pos, batch], lambda: self._build(graph, pos, batch))
+
+    def _build(self, graph, pos, batch):
+        from ..graph import Graph
+        from ..point_sampler import PointSampler
         n = int(pos.size(0))
         counts = [n] if batch is None else torch.bincount(batch).tolist()
         if sum(counts) != n:
@@ -229,18 +283,12 @@ class SampleLoss(nn.Module):
         if self.max_distance is not None:
             mask = s.distance <= self.max_distance
             kept = int(mask.sum())
-        self._cache = (pos, pos._version, batch, None if batch is None else batch._version, s, mask, kept)
-        self.builds += 1
         return s, mask, kept
 
     def forward(self, graph, pred, target, step=None):
-        loss = None
-        if self.node_weight > 0:
-            loss = self.base(graph, pred, target)
-            if self.node_weight != 1.0:
-                loss = self.node_weight * loss
+        loss = self.node_term(graph, pred, target)
         if self.weight == 0:
-            return pred.sum() * 0.0 if loss is None else loss
+            return self.nothing_more(pred, loss)
         if self.values is not None and step is None:
             raise ValueError("step: SampleLoss(values=...) needs the output step: call loss(graph, pred, target, step=t)")
         s, mask, kept = self.sampler(graph)
@@ -249,23 +297,17 @@ class SampleLoss(nn.Module):
             raise ValueError(f"fields: column {max(cols)} of a prediction with {int(pred.size(1))} columns")
         nfp = len(cols)
         if kept == 0:
-            return pred.sum() * 0.0 if loss is None else loss
+            return self.nothing_more(pred, loss)
         if self.values is None:
             d = s.sample(pred - target)          # S is linear: S·pred − S·target in one launch
             if self.fields is not None:
                 d = d[:, cols]
         else:
-            obs = getattr(graph, self.values, None)
-            if not torch.is_tensor(obs) or obs.dim() != 2 or int(obs.size(0)) != s.n_points:
-                raise ValueError(f"values: graph.{self.values}: expected observations [{s.n_points}, F'·T], got "
-                                 f"{tuple(getattr(obs, 'shape', ()))}")
-            t = int(step)
-            if t < 0 or nfp * (t + 1) > int(obs.size(1)):
-                raise ValueError(f"step: {t}: graph.{self.values} holds {int(obs.size(1))} columns, {nfp} per step")
+            obs = self.observed(graph, self.values, s.n_points, nfp, step, f"observations [{s.n_points}, F'·T]")
             sp = s.sample(pred)
             if self.fields is not None:
                 sp = sp[:, cols]
-            d = sp - obs[:, nfp * t: nfp * (t + 1)].to(sp.dtype)
+            d = sp - obs.to(sp.dtype)
         sq = d.square()
         if mask is not None:
             sq = sq * mask[:, None].to(sq.dtype)
@@ -273,7 +315,7 @@ class SampleLoss(nn.Module):
         return term if loss is None else loss + term
 
 
-class ForceLoss(nn.Module):
+class ForceLoss(_OperatorLoss):
     """`GraphLoss(lambda_d)` plus the error of the loads on the bodies in the flow — what a load cell and pressure taps measure (new
     functionality — the reference has none):
 
@@ -307,31 +349,13 @@ class ForceLoss(nn.Module):
     def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, mu=0.0, pressure=None, velocity=None, scale=None, shift=None,
                  components=("fx", "fy"), force_scale=1.0, wall=None, values=None, nodes=None, bodies=None, centre=None, power=2,
                  edge_vectors=None):
-        super().__init__()
-        self.lambda_d = _number(lambda_d, "lambda_d")
-        self.weight = _number(weight, "weight", "a finite weight >= 0")
-        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
+        super().__init__(lambda_d, weight, node_weight)
         if isinstance(mu, bool) or not isinstance(mu, (int, float)) or not math.isfinite(mu):
             raise ValueError(f"mu: expected a finite number (the dynamic viscosity), got {mu!r}")
         if pressure is not None and (isinstance(pressure, bool) or not isinstance(pressure, int) or pressure < 0):
             raise ValueError(f"pressure: expected a field number, got {pressure!r}")
-        if velocity is not None:
-            try:
-                velocity = tuple(velocity)
-            except TypeError:
-                raise ValueError(f"velocity: expected 2 field numbers, got {velocity!r}") from None
-            if len(velocity) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in velocity):
-                raise ValueError(f"velocity: expected 2 field numbers, got {velocity!r}")
-        factors = {}
-        for name, v in (("scale", scale), ("shift", shift)):
-            if v is not None:
-                try:
-                    v = [float(q) for q in (v.tolist() if torch.is_tensor(v) else v)]
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name}: expected one number per field, got {v!r}") from None
-                if not v or not all(math.isfinite(q) for q in v):
-                    raise ValueError(f"{name}: expected one finite number per field, got {v!r}")
-            factors[name] = v
+        velocity = _field_numbers(velocity, "velocity", "2 field numbers", lengths=(2,))
+        scale, shift = _per_field(scale, "scale", "number"), _per_field(shift, "shift", "number")
         if isinstance(components, str):
             components = (components,)
         try:
@@ -348,12 +372,9 @@ class ForceLoss(nn.Module):
         wall = dict(wall or {})
         self.wall_pressure = _number(wall.get("pressure", 0.0), "wall['pressure']", "a finite weight >= 0")
         self.wall_shear = _number(wall.get("shear", 0.0), "wall['shear']", "a finite weight >= 0")
-        if values is not None and (not isinstance(values, str) or not values or "index" in values):
-            raise ValueError(f"values: expected None or the name of a graph attribute holding [B, C·T] measured loads (without 'index' in "
-                             f"it: such attributes collate along the last dimension), got {values!r}")
+        values = _values(values, "[B, C·T] measured loads")
         for name, v in (("nodes", nodes), ("bodies", bodies), ("edge_vectors", edge_vectors)):
-            if v is not None and (not isinstance(v, str) or not v):
-                raise TypeError(f"{name}: expected None or the name of a graph attribute, got {v!r}")
+            _attribute(v, name, kind=TypeError)
         if centre is not None:
             try:
                 c = torch.as_tensor(centre, dtype=torch.float64).reshape(-1, 2)
@@ -361,14 +382,10 @@ class ForceLoss(nn.Module):
                 raise ValueError(f"centre: expected [B, 2] numbers, got {centre!r}") from None
             if not c.numel() or not bool(torch.isfinite(c).all()):
                 raise ValueError(f"centre: expected [B, 2] finite numbers, got {centre!r}")
-        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-            raise ValueError(f"power: expected 0, 1 or 2 (an edge weighs |d|^-power), got {power!r}")
-        self.base = GraphLoss(lambda_d)
-        self.mu, self.pressure, self.velocity, self.scale, self.shift = float(mu), pressure, velocity, factors["scale"], factors["shift"]
+        power = _power(power, "an edge")
+        self.mu, self.pressure, self.velocity, self.scale, self.shift = float(mu), pressure, velocity, scale, shift
         self.components, self.force_scale, self.wall, self.values = components, float(force_scale), wall, values
         self.nodes, self.bodies, self.centre, self.power, self.edge_vectors = nodes, bodies, centre, power, edge_vectors
-        self._cache = None          # ([(tensor, its version), ...], BodyForces)
-        self.builds = 0             # operators built so far (a batch seen again costs none)
 
     def _attr(self, graph, arg, name, n):
         t = getattr(graph, name, None)
@@ -381,7 +398,6 @@ class ForceLoss(nn.Module):
         """The `BodyForces` of `graph` — of all its graphs, when it is a batch —: the cached one while the tensors it was built from
         are the same objects, unmodified (identity and `_version`: an address says nothing, the allocator hands a freed batch's to the
         next one)."""
-        from ..body_forces import WALL, BodyForces
         pos = getattr(graph, "pos", None)
         if not torch.is_tensor(pos) or pos.dim() != 2:
             raise ValueError("graph: ForceLoss needs graph.pos [N, 2]")
@@ -402,10 +418,10 @@ class ForceLoss(nn.Module):
             if not torch.is_tensor(vec):
                 raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
         ei = getattr(graph, "edge_index", None) if self.mu != 0 else None
-        key = [t for t in (pos, ei, batch, flag, label, vec)]
-        hit = self._cache
-        if hit is not None and len(hit[0]) == len(key) and all(a is t and (t is None or v == t._version) for (a, v), t in zip(hit[0], key)):
-            return hit[1]
+        return self.keep([pos, ei, batch, flag, label, vec], lambda: self._build(graph, n, batch, flag, label, vec))
+
+    def _build(self, graph, n, batch, flag, label, vec):
+        from ..body_forces import WALL, BodyForces
         if batch is not None and (not torch.is_tensor(batch) or batch.numel() != n):
             raise ValueError(f"graph: graph.batch names {getattr(batch, 'numel', lambda: 0)()} nodes, graph.pos has {n}")
         mask = (flag.reshape(-1) == WALL) if self.nodes is None else (flag.reshape(-1) != 0)
@@ -418,24 +434,17 @@ class ForceLoss(nn.Module):
                 if own.numel():
                     lo = int(own.min())
                     labels = labels * (int(own.max()) - lo + 1) + (own - lo)
-        op = BodyForces(graph, nodes=rows, bodies=labels, centre=self.centre, mu=self.mu, pressure=self.pressure, velocity=self.velocity,
-                        scale=self.scale, shift=self.shift, power=self.power, edge_vectors=vec)
-        self._cache = ([(t, None if t is None else t._version) for t in key], op)
-        self.builds += 1
-        return op
+        return BodyForces(graph, nodes=rows, bodies=labels, centre=self.centre, mu=self.mu, pressure=self.pressure, velocity=self.velocity,
+                          scale=self.scale, shift=self.shift, power=self.power, edge_vectors=vec)
 
     def _totals(self, sums):
         return torch.stack([sums[:, self.COMPONENTS[c][0]] + sums[:, self.COMPONENTS[c][1]] for c in self.components], dim=1)
 
     def forward(self, graph, pred, target, step=None):
-        loss = None
-        if self.node_weight > 0:
-            loss = self.base(graph, pred, target)
-            if self.node_weight != 1.0:
-                loss = self.node_weight * loss
+        loss = self.node_term(graph, pred, target)
         on_wall = self.wall_pressure > 0 or self.wall_shear > 0
         if self.weight == 0 and not on_wall:
-            return pred.sum() * 0.0 if loss is None else loss
+            return self.nothing_more(pred, loss)
         if self.weight > 0 and self.values is not None and step is None:
             raise ValueError("step: ForceLoss(values=...) needs the output step: call loss(graph, pred, target, step=t)")
         op = self.operator(graph)
@@ -444,13 +453,8 @@ class ForceLoss(nn.Module):
                 with torch.no_grad():
                     ref = self._totals(op.forces(target.detach()))
             else:
-                obs, nc, t = getattr(graph, self.values, None), len(self.components), int(step)
-                if not torch.is_tensor(obs) or obs.dim() != 2 or int(obs.size(0)) != op.n_bodies:
-                    raise ValueError(f"values: graph.{self.values}: expected measured loads [{op.n_bodies}, C·T], got "
-                                     f"{tuple(getattr(obs, 'shape', ()))}")
-                if t < 0 or nc * (t + 1) > int(obs.size(1)):
-                    raise ValueError(f"step: {t}: graph.{self.values} holds {int(obs.size(1))} columns, {nc} per step")
-                ref = obs[:, nc * t: nc * (t + 1)].to(torch.float64)
+                ref = self.observed(graph, self.values, op.n_bodies, len(self.components), step,
+                                    f"measured loads [{op.n_bodies}, C·T]").to(torch.float64)
             d = (self._totals(op.forces(pred)) - ref) / self.force_scale
             term = (self.weight * d.square().mean()).to(pred.dtype)
             loss = term if loss is None else loss + term
@@ -465,7 +469,7 @@ class ForceLoss(nn.Module):
         return loss
 
 
-class ResidualLoss(nn.Module):
+class ResidualLoss(_OperatorLoss):
     """`GraphLoss(lambda_d)` plus the residual of the incompressible momentum and continuity equations the model is a surrogate
     for — a physics-informed term (new functionality — the reference has none):
 
@@ -495,11 +499,8 @@ class ResidualLoss(nn.Module):
 
     def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, nu, dt, rho=1.0, velocity=None, pressure=None, scale=None, shift=None,
                  continuity=1.0, reference="target", k=12, power=2, edge_vectors=None, mask=None):
-        super().__init__()
+        super().__init__(lambda_d, weight, node_weight)
         from ..mesh_jet import MAX_K
-        self.lambda_d = _number(lambda_d, "lambda_d")
-        self.weight = _number(weight, "weight", "a finite weight >= 0")
-        self.node_weight = _number(node_weight, "node_weight", "a finite weight >= 0")
         if isinstance(nu, str):
             if not nu:
                 raise ValueError(f"nu: expected a finite number >= 0 or the name of a per-node graph attribute, got {nu!r}")
@@ -508,46 +509,25 @@ class ResidualLoss(nn.Module):
         for name, v in (("dt", dt), ("rho", rho)):
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
                 raise ValueError(f"{name}: expected a finite number > 0, got {v!r}")
-        if velocity is not None:
-            try:
-                velocity = tuple(velocity)
-            except TypeError:
-                raise ValueError(f"velocity: expected 2 or 3 distinct field numbers, got {velocity!r}") from None
-            if (len(velocity) not in (2, 3) or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in velocity)
-                    or len(set(velocity)) != len(velocity)):
-                raise ValueError(f"velocity: expected 2 or 3 distinct field numbers, got {velocity!r}")
+        velocity = _field_numbers(velocity, "velocity", "2 or 3 distinct field numbers", lengths=(2, 3), distinct=True)
         if pressure is not None and (isinstance(pressure, bool) or not isinstance(pressure, int) or pressure < 0
                                      or (velocity is not None and pressure in velocity)):
             raise ValueError(f"pressure: expected a field number that is no velocity component, got {pressure!r}")
-        factors = {}
-        for name, v in (("scale", scale), ("shift", shift)):
-            if v is not None:
-                try:
-                    v = [float(q) for q in (v.tolist() if torch.is_tensor(v) else v)]
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name}: expected one number per field, got {v!r}") from None
-                if not v or not all(math.isfinite(q) for q in v):
-                    raise ValueError(f"{name}: expected one finite number per field, got {v!r}")
-            factors[name] = v
+        scale, shift = _per_field(scale, "scale", "number"), _per_field(shift, "shift", "number")
         self.continuity = _number(continuity, "continuity", "a finite weight >= 0")
         if reference not in ("target", "zero"):
             raise ValueError(f"reference: expected 'target' or 'zero', got {reference!r}")
         if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 5 <= k <= MAX_K):
             raise ValueError(f"k: expected None (the graph's in-edges) or an integer 5 <= k <= {MAX_K} (9 <= k in 3-D), got {k!r}")
-        if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-            raise ValueError(f"power: expected 0, 1 or 2 (a stencil entry weighs |d|^-power), got {power!r}")
-        for name, v in (("edge_vectors", edge_vectors), ("mask", mask)):
-            if v is not None and (not isinstance(v, str) or not v):
-                raise ValueError(f"{name}: expected None or the name of a graph attribute, got {v!r}")
+        power = _power(power, "a stencil entry")
+        _attribute(edge_vectors, "edge_vectors")
+        _attribute(mask, "mask")
         if edge_vectors is not None and k is not None:
             raise ValueError("edge_vectors: they belong to the graph's edges; pass k=None with them (the operator's own stencil search "
                              "is not periodic)")
-        self.base = GraphLoss(lambda_d)
         self.nu, self.dt, self.rho = nu, float(dt), float(rho)
-        self.velocity, self.pressure, self.scale, self.shift = velocity, pressure, factors["scale"], factors["shift"]
+        self.velocity, self.pressure, self.scale, self.shift = velocity, pressure, scale, shift
         self.reference, self.k, self.power, self.edge_vectors, self.mask = reference, k, power, edge_vectors, mask
-        self._cache = None          # ([(tensor, its version), ...], MeshJet)
-        self.builds = 0             # operators built so far (a batch seen again costs none)
 
     def operator(self, graph):
         """The `MeshJet` of `graph` — of all its graphs, when it is a batch —: the cached one while the tensors it was built from are
@@ -563,14 +543,7 @@ class ResidualLoss(nn.Module):
                 if not torch.is_tensor(vec):
                     raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
             key = [getattr(graph, "edge_index", None), getattr(graph, "pos", None) if vec is None else vec]
-        hit = self._cache
-        if (hit is not None and len(hit[0]) == len(key)
-                and all(a is t and (not torch.is_tensor(t) or v == t._version) for (a, v), t in zip(hit[0], key))):
-            return hit[1]
-        op = MeshJet(graph, k=self.k, power=self.power, edge_vectors=vec)
-        self._cache = ([(t, t._version if torch.is_tensor(t) else None) for t in key], op)
-        self.builds += 1
-        return op
+        return self.keep(key, lambda: MeshJet(graph, k=self.k, power=self.power, edge_vectors=vec))
 
     @staticmethod
     def _launches(names, columns, fields):
@@ -620,13 +593,9 @@ class ResidualLoss(nn.Module):
         return torch.stack(rows, dim=1), cont
 
     def forward(self, graph, pred, target):
-        loss = None
-        if self.node_weight > 0:
-            loss = self.base(graph, pred, target)
-            if self.node_weight != 1.0:
-                loss = self.node_weight * loss
+        loss = self.node_term(graph, pred, target)
         if self.weight == 0:
-            return pred.sum() * 0.0 if loss is None else loss
+            return self.nothing_more(pred, loss)
         op = self.operator(graph)
         n, nf, dim = op.n_nodes, int(pred.size(1)), op.dim
         vel = tuple(range(dim)) if self.velocity is None else self.velocity

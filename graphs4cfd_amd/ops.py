@@ -798,40 +798,46 @@ def mesh_gradient_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=N
     |rel|^(-power).  Returns (g float32 [E, dim], src int32 [E], degenerate uint8 [N]) with the edges in CSR order: the s-th in-edge
     of node i at position off[i] + s (include/g4c.h has the arithmetic).  `out`: the three tensors to write into; a mesh without
     edges or nodes launches nothing (then a fresh `degenerate` is all ones)."""
-    what = "mesh_gradient_weights"
+    return _stencil_weights("mesh_gradient_weights", "g4c_mesh_gradient_weights", lambda dim: dim, "edges", "E", rel, csr, src32, power, out)
+
+
+def _stencil_weights(what, fn, width, entries, letter, rel, csr, src32, power, out):
+    """The checks and the launch of `mesh_gradient_weights` and `mesh_jet_weights`: `fn` the name of the library's function,
+    `width(dim)` the row width of its table, `entries` / `letter` what a stencil entry is called in a message ("edges" / "E",
+    "entries" / "S")."""
     if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
         raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
     _mesh_arg(what, rel, "rel", torch.float32, dim=2)
-    n_edges, dim = int(rel.size(0)), int(rel.size(1))
+    n_entries, dim = int(rel.size(0)), int(rel.size(1))
     if dim not in (2, 3):
-        raise ValueError(f"rel: {what}: expected [E, 2] or [E, 3], got shape {tuple(rel.shape)}")
+        raise ValueError(f"rel: {what}: expected [{letter}, 2] or [{letter}, 3], got shape {tuple(rel.shape)}")
+    W = width(dim)
     off, perm = getattr(csr, "off", None), getattr(csr, "perm", None)
     _mesh_arg(what, off, "csr.off", torch.int32, dim=1)
     if off.numel() < 1:
         raise ValueError(f"csr.off: {what}: expected [n_nodes + 1], got shape {tuple(off.shape)}")
     n_nodes = int(off.numel()) - 1
-    if int(getattr(csr, "n", n_edges)) != n_edges:
-        raise ValueError(f"csr: {what}: a plan of {csr.n} edges for rel of {n_edges}")
+    if int(getattr(csr, "n", n_entries)) != n_entries:
+        raise ValueError(f"csr: {what}: a plan of {csr.n} {entries} for rel of {n_entries}")
     if perm is not None:
-        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_edges,))
-    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_edges,))
+        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_entries,))
+    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_entries,))
     if out is not None:
-        g, src, degenerate = out
-        _mesh_arg(what, g, "out[0]", torch.float32, shape=(n_edges, dim))
-        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_edges,))
+        table, src, degenerate = out
+        _mesh_arg(what, table, "out[0]", torch.float32, shape=(n_entries, W))
+        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_entries,))
         _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
     else:
-        g = src = degenerate = None
-    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", g), ("out[1]", src),
+        table = src = degenerate = None
+    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", table), ("out[1]", src),
                         ("out[2]", degenerate))
     if out is None:
-        g = torch.empty((n_edges, dim), dtype=torch.float32, device=dev)
-        src = torch.empty((n_edges,), dtype=torch.int32, device=dev)
+        table = torch.empty((n_entries, W), dtype=torch.float32, device=dev)
+        src = torch.empty((n_entries,), dtype=torch.int32, device=dev)
         degenerate = torch.ones((n_nodes,), dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.g4c_mesh_gradient_weights(_lib.ptr(off), _lib.ptr(perm), _lib.ptr(src32), _lib.ptr(rel), dim, power, n_nodes, n_edges,
-                                             _lib.ptr(g), _lib.ptr(src), _lib.ptr(degenerate), _lib.stream_handle(dev)))
-    return g, src, degenerate
+    _lib.check(getattr(_lib.load(), fn)(_lib.ptr(off), _lib.ptr(perm), _lib.ptr(src32), _lib.ptr(rel), dim, power, n_nodes, n_entries,
+                                        _lib.ptr(table), _lib.ptr(src), _lib.ptr(degenerate), _lib.stream_handle(dev)))
+    return table, src, degenerate
 
 
 def derived_program(program, nf: Optional[int] = None, dim: Optional[int] = None, order: int = 1) -> "_lib.g4c_derived_program_t":
@@ -894,51 +900,12 @@ def mesh_jet_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
     2.  Returns (c float32 [S, Q], src int32 [S], degenerate uint8 [N]) in CSR order, jet(i) = Σ_s c[s] (x[src[s]] - x[i]) with the
     first derivatives in columns 0 .. dim - 1 and the second ones after them (include/g4c.h has the arithmetic).  `out`: the three
     tensors to write into; an empty stencil launches nothing (then a fresh `degenerate` is all ones)."""
-    what = "mesh_jet_weights"
-    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
-    _mesh_arg(what, rel, "rel", torch.float32, dim=2)
-    n_entries, dim = int(rel.size(0)), int(rel.size(1))
-    if dim not in (2, 3):
-        raise ValueError(f"rel: {what}: expected [S, 2] or [S, 3], got shape {tuple(rel.shape)}")
-    Q = jet_size(dim)
-    off, perm = getattr(csr, "off", None), getattr(csr, "perm", None)
-    _mesh_arg(what, off, "csr.off", torch.int32, dim=1)
-    if off.numel() < 1:
-        raise ValueError(f"csr.off: {what}: expected [n_nodes + 1], got shape {tuple(off.shape)}")
-    n_nodes = int(off.numel()) - 1
-    if int(getattr(csr, "n", n_entries)) != n_entries:
-        raise ValueError(f"csr: {what}: a plan of {csr.n} entries for rel of {n_entries}")
-    if perm is not None:
-        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_entries,))
-    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_entries,))
-    if out is not None:
-        c, src, degenerate = out
-        _mesh_arg(what, c, "out[0]", torch.float32, shape=(n_entries, Q))
-        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_entries,))
-        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
-    else:
-        c = src = degenerate = None
-    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", c), ("out[1]", src),
-                        ("out[2]", degenerate))
-    if out is None:
-        c = torch.empty((n_entries, Q), dtype=torch.float32, device=dev)
-        src = torch.empty((n_entries,), dtype=torch.int32, device=dev)
-        degenerate = torch.ones((n_nodes,), dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.g4c_mesh_jet_weights(_lib.ptr(off), _lib.ptr(perm), _lib.ptr(src32), _lib.ptr(rel), dim, power, n_nodes, n_entries,
-                                        _lib.ptr(c), _lib.ptr(src), _lib.ptr(degenerate), _lib.stream_handle(dev)))
-    return c, src, degenerate
+    return _stencil_weights("mesh_jet_weights", "g4c_mesh_jet_weights", jet_size, "entries", "S", rel, csr, src32, power, out)
 
 
-def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optional[Tensor] = None, *, nf: Optional[int] = None) -> Tensor:
-    """g4c_mesh_jet: the columns of `program` (`derived_program(.., order=2)`: axis 0 .. Q - 1) of the fields x[:, :nf] (float32
-    [N, x_ld], rows of unit stride; nf defaults to every column) by the quadratic fit (c float32 [S, Q], src int32 [S], off int32
-    [N + 1]: the outputs of `mesh_jet_weights` and the stencil's offsets) into out float32 [N, nd] — one thread per node, fp32, its
-    entries in CSR order: the same bits on every run.  At most 4 distinct fields per program."""
-    what = "mesh_jet"
-    dim = _jet_dim(what, c)
-    n_entries = int(c.size(0))
+def _mesh_fields(what, x, nf):
+    """(n_nodes, nf, x_ld) of the fields x[:, :nf] of `mesh_derived` and `mesh_jet`: float32 [N, >= 1] with rows of unit stride, nf
+    defaulting to every column, x_ld the row stride in elements."""
     if not torch.is_tensor(x) or x.dtype != torch.float32:
         raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
     if x.dim() != 2 or int(x.size(1)) < 1:
@@ -949,7 +916,18 @@ def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optio
         raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
     if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
         raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    return n_nodes, nf, max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+
+
+def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optional[Tensor] = None, *, nf: Optional[int] = None) -> Tensor:
+    """g4c_mesh_jet: the columns of `program` (`derived_program(.., order=2)`: axis 0 .. Q - 1) of the fields x[:, :nf] (float32
+    [N, x_ld], rows of unit stride; nf defaults to every column) by the quadratic fit (c float32 [S, Q], src int32 [S], off int32
+    [N + 1]: the outputs of `mesh_jet_weights` and the stencil's offsets) into out float32 [N, nd] — one thread per node, fp32, its
+    entries in CSR order: the same bits on every run.  At most 4 distinct fields per program."""
+    what = "mesh_jet"
+    dim = _jet_dim(what, c)
+    n_entries = int(c.size(0))
+    n_nodes, nf, x_ld = _mesh_fields(what, x, nf)
     _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
     _mesh_arg(what, src, "src", torch.int32, shape=(n_entries,))
     prog = derived_program(program, nf, dim, order=2)
@@ -982,11 +960,18 @@ def mesh_jet_adjoint(gy: Tensor, off: Tensor, c: Tensor, out_off: Tensor, out_c:
     into (not gy)."""
     what = "mesh_jet_adjoint"
     dim = _jet_dim(what, c)
-    n_entries, Q = int(c.size(0)), int(c.size(1))
+    return _stencil_adjoint(what, "g4c_mesh_jet_adjoint", dim, 2, "c", gy, off, c, out_off, out_c, out_dst, program, nf, gx)
+
+
+def _stencil_adjoint(what, fn, dim, order, name, gy, off, table, out_off, out_table, out_dst, program, nf, gx):
+    """The checks and the launch of `mesh_derived_adjoint` and `mesh_jet_adjoint` behind the check of their table (`name`: "g" or
+    "c"), which gave `dim`: `fn` the name of the library's function, `order` the program's (`derived_program`)."""
+    n_entries, W = int(table.size(0)), int(table.size(1))
     if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
         raise ValueError(f"nf: {what}: expected a number of fields >= 1, got {nf!r}")
-    prog = derived_program(program, nf, dim, order=2)
-    _jet_fields(what, prog)
+    prog = derived_program(program, nf, dim, order=order)
+    if order == 2:
+        _jet_fields(what, prog)
     nd = int(prog.nd)
     _mesh_arg(what, gy, "gy", torch.float32, dim=2)
     if int(gy.size(1)) != nd:
@@ -994,18 +979,18 @@ def mesh_jet_adjoint(gy: Tensor, off: Tensor, c: Tensor, out_off: Tensor, out_c:
     n_nodes = int(gy.size(0))
     _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
     _mesh_arg(what, out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, out_c, "out_c", torch.float32, shape=(n_entries, Q))
+    _mesh_arg(what, out_table, f"out_{name}", torch.float32, shape=(n_entries, W))
     _mesh_arg(what, out_dst, "out_dst", torch.int32, shape=(n_entries,))
     if gx is not None:
         _mesh_arg(what, gx, "gx", torch.float32, shape=(n_nodes, nf))
         if gx is gy or (gx.numel() and gy.numel() and gx.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
             raise ValueError(f"gx: {what}: gx shares its storage with gy")
-    dev = _mesh_devices(what, ("gy", gy), ("off", off), ("c", c), ("out_off", out_off), ("out_c", out_c), ("out_dst", out_dst), ("gx", gx))
+    dev = _mesh_devices(what, ("gy", gy), ("off", off), (name, table), ("out_off", out_off), (f"out_{name}", out_table), ("out_dst", out_dst),
+                        ("gx", gx))
     if gx is None:
         gx = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.g4c_mesh_jet_adjoint(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(c), _lib.ptr(off), _lib.ptr(out_c), _lib.ptr(out_dst),
-                                        _lib.ptr(out_off), n_nodes, n_entries, _lib.ptr(gx), _lib.stream_handle(dev)))
+    _lib.check(getattr(_lib.load(), fn)(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(table), _lib.ptr(off), _lib.ptr(out_table),
+                                        _lib.ptr(out_dst), _lib.ptr(out_off), n_nodes, n_entries, _lib.ptr(gx), _lib.stream_handle(dev)))
     return gx
 
 
@@ -1032,17 +1017,7 @@ def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: T
     n_edges, dim = int(g.size(0)), int(g.size(1))
     if dim not in (2, 3):
         raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.dim() != 2 or int(x.size(1)) < 1:
-        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
-    n_nodes, cols = int(x.size(0)), int(x.size(1))
-    nf = cols if nf is None else int(nf)
-    if not 1 <= nf <= cols:
-        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
-    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
-        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+    n_nodes, nf, x_ld = _mesh_fields(what, x, nf)
     _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
     _mesh_arg(what, src, "src", torch.int32, shape=(n_edges,))
     prog = derived_program(program, nf, dim)
@@ -1091,32 +1066,10 @@ def mesh_derived_adjoint(gy: Tensor, off: Tensor, g: Tensor, out_off: Tensor, ou
     same bits on every run.  `gx`: the tensor to write into (not gy)."""
     what = "mesh_derived_adjoint"
     _mesh_arg(what, g, "g", torch.float32, dim=2)
-    n_edges, dim = int(g.size(0)), int(g.size(1))
+    dim = int(g.size(1))
     if dim not in (2, 3):
         raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
-    if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
-        raise ValueError(f"nf: {what}: expected a number of fields >= 1, got {nf!r}")
-    prog = derived_program(program, nf, dim)
-    nd = int(prog.nd)
-    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
-    if int(gy.size(1)) != nd:
-        raise ValueError(f"gy: {what}: expected [n_nodes, {nd}] (one column per column of the program), got shape {tuple(gy.shape)}")
-    n_nodes = int(gy.size(0))
-    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, out_g, "out_g", torch.float32, shape=(n_edges, dim))
-    _mesh_arg(what, out_dst, "out_dst", torch.int32, shape=(n_edges,))
-    if gx is not None:
-        _mesh_arg(what, gx, "gx", torch.float32, shape=(n_nodes, nf))
-        if gx is gy or (gx.numel() and gy.numel() and gx.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
-            raise ValueError(f"gx: {what}: gx shares its storage with gy")
-    dev = _mesh_devices(what, ("gy", gy), ("off", off), ("g", g), ("out_off", out_off), ("out_g", out_g), ("out_dst", out_dst), ("gx", gx))
-    if gx is None:
-        gx = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.g4c_mesh_derived_adjoint(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(g), _lib.ptr(off), _lib.ptr(out_g), _lib.ptr(out_dst),
-                                            _lib.ptr(out_off), n_nodes, n_edges, _lib.ptr(gx), _lib.stream_handle(dev)))
-    return gx
+    return _stencil_adjoint(what, "g4c_mesh_derived_adjoint", dim, 1, "g", gy, off, g, out_off, out_g, out_dst, program, nf, gx)
 
 
 def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: Tensor, arm: Tensor, cur: Tensor, *, pcol: int,
