@@ -118,4 +118,23 @@ __device__ __forceinline__ float act_t(float x) {
     return x;
 }
 
+// The extrema of the diagnostics (include/g4c.h, "non-finite samples"): a maximum or minimum over samples of which one is NaN IS NaN
+// — fmax / fmin would drop it, and a record would read better than the rollout was.  Compares and selects; ±Inf are ordinary values.
+// `!(a < b)` holds when a >= b and when either is NaN; the inner select then keeps whichever NaN there is.  Commutative in the value
+// (two NaNs may differ in their payload, +0 and -0 in their sign: which one is kept depends on the order of the arguments, and every
+// caller's order is fixed).  (Of the forms tried, this one keeps the waves per SIMD of every instantiation of the records' kernels;
+// `(a >= b || a != a) ? a : b` cost the three- and five-field ones a wave.)
+__device__ __forceinline__ double nan_max(double a, double b) { return !(a < b) ? (b != b ? b : a) : b; }
+__device__ __forceinline__ double nan_min(double a, double b) { return !(a > b) ? (b != b ? b : a) : b; }
+
+// The maximum over the 64 lanes of a wave, in every lane: fmax in the xor butterfly (one instruction per level), and NaN if any lane
+// held one — a ballot before the butterfly, one select after it, in place of a compare and a select at each of the six levels.  The
+// NaN is the canonical quiet one in every lane, whatever the payloads were.  Every lane of the wave must be active.
+__device__ __forceinline__ double wave_nan_max(double x) {
+    const bool any_nan = __builtin_amdgcn_ballot_w64(x != x) != 0ull;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
+    return any_nan ? __builtin_nan("") : x;
+}
+
 }  // namespace g4c

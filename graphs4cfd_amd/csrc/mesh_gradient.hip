@@ -128,18 +128,23 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_gradient_weights_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------ per step
-__device__ __forceinline__ double mg_combine(int j, double a, double b) { return j % NSTAT == G4C_DERIVED_MAX_ABS ? fmax(a, b) : a + b; }
+__device__ __forceinline__ double mg_combine(int j, double a, double b) { return j % NSTAT == G4C_DERIVED_MAX_ABS ? g4c::nan_max(a, b) : a + b; }
 
 // The workgroup's 256 sets of nstat (<= MAX_COLS * NSTAT) values -> one set at dst: rec_block_reduce of rollout_record.hip with a
 // run-time count (the loops are unrolled over the maximum and guarded by a wave-uniform test: every index is a compile-time one).
+// As there, the maximum carries a NaN through every stage (g4c::nan_max, and g4c::wave_nan_max in the butterfly).
 __device__ __forceinline__ void mg_block_reduce(double (&a)[MAX_COLS * NSTAT], int nstat, double *__restrict__ dst) {
     __shared__ double part[MG_THREADS / 64][MAX_COLS * NSTAT];
 #pragma unroll
     for (int j = 0; j < MAX_COLS * NSTAT; ++j) {
         if (j < nstat) {
             double x = a[j];
+            if (j % NSTAT == G4C_DERIVED_MAX_ABS) {
+                x = g4c::wave_nan_max(x);
+            } else {
 #pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) x = mg_combine(j, x, __shfl_xor(x, m, 64));
+                for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+            }
             a[j] = x;
         }
     }
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_derived_kernel(const float *_
                         const double sq = qd * qd;
                         acc[c * NSTAT + G4C_DERIVED_SQ] += sq;
                         acc[c * NSTAT + G4C_DERIVED_ABS] += aq;
-                        acc[c * NSTAT + G4C_DERIVED_MAX_ABS] = fmax(acc[c * NSTAT + G4C_DERIVED_MAX_ABS], aq);
+                        acc[c * NSTAT + G4C_DERIVED_MAX_ABS] = g4c::nan_max(acc[c * NSTAT + G4C_DERIVED_MAX_ABS], aq);
                     }
                 }
             }

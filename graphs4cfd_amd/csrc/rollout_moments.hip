@@ -2,7 +2,8 @@
 // and the step's closing launch.  It reads the prediction (and, for the statistics of the error, the target's columns of the step),
 // and keeps per node and field a pivot (the first sample), the sum of the shifted samples, the sums of their pairwise products, and
 // the extrema — all fp64, plane-major, one add per accumulator and accumulated step, each accumulator owned by one thread: the bits
-// depend on the data alone.  No LDS, no scratch, nothing between workgroups.
+// depend on the data alone.  No LDS, no scratch, nothing between workgroups.  The extrema carry a NaN sample (g4c::nan_min / nan_max)
+// and keep it until the window's origin is rewritten.
 #include "g4c_common.h"
 
 namespace {
@@ -61,8 +62,8 @@ __global__ __launch_bounds__(MOM_THREADS) void rollout_moments_kernel(const floa
             for (int f = 0; f < NF; ++f) {
                 d[f] = x[f] - d[f];
                 m.sum[f * ld + n] = s[f] + d[f];
-                m.lo[f * ld + n] = fmin(lo[f], x[f]);
-                m.hi[f * ld + n] = fmax(hi[f], x[f]);
+                m.lo[f * ld + n] = g4c::nan_min(lo[f], x[f]);
+                m.hi[f * ld + n] = g4c::nan_max(hi[f], x[f]);
             }
             int p = 0;
 #pragma unroll

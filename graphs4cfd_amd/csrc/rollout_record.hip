@@ -22,21 +22,29 @@ inline long long rec_blocks(long long n_nodes) {
 }
 
 __device__ __forceinline__ double rec_combine(int j, double a, double b) {
-    return j % NSTAT == G4C_REC_MAX_ABS_ERR ? fmax(a, b) : a + b;
+    return j % NSTAT == G4C_REC_MAX_ABS_ERR ? g4c::nan_max(a, b) : a + b;
 }
 
 // The workgroup's 256 sets of NF * NSTAT values -> one set at dst.  A 6-level xor butterfly inside each wave (both lanes of a pair
 // form the same commutative sum or maximum, so every lane ends with the wave's value), then the four waves in order: the order is
 // fixed by the lane and wave numbers, never by arrival.  Everything stays in registers (compile-time indices) and 4 * NF * 48 bytes
-// of LDS.
+// of LDS.  The maximum carries a NaN at any node through every stage: g4c::nan_max in the thread's loop, between the four waves and
+// over the partials of the workgroups, g4c::wave_nan_max in the butterfly (fmax at its six levels, and NaN if a ballot found one in
+// any lane — cheaper than a compare and a select per level).  After a NaN every lane of a wave holds the same canonical quiet NaN;
+// of two NaNs of different waves or partials the one kept depends on the order of the arguments, which is fixed: two runs give the
+// same bits.
 template <int NF>
 __device__ __forceinline__ void rec_block_reduce(double (&a)[NF * NSTAT], double *__restrict__ dst) {
     __shared__ double part[REC_THREADS / 64][NF * NSTAT];
 #pragma unroll
     for (int j = 0; j < NF * NSTAT; ++j) {
         double x = a[j];
+        if (j % NSTAT == G4C_REC_MAX_ABS_ERR) {
+            x = g4c::wave_nan_max(x);
+        } else {
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) x = rec_combine(j, x, __shfl_xor(x, m, 64));
+            for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+        }
         a[j] = x;
     }
     const int wave = threadIdx.x >> 6;
@@ -101,7 +109,7 @@ __global__ __launch_bounds__(REC_THREADS) void rollout_advance_record_kernel(
                     double *a = acc + c * NSTAT;
                     a[G4C_REC_SQ_ERR] += d * d;
                     a[G4C_REC_ABS_ERR] += ad;
-                    a[G4C_REC_MAX_ABS_ERR] = fmax(a[G4C_REC_MAX_ABS_ERR], ad);
+                    a[G4C_REC_MAX_ABS_ERR] = g4c::nan_max(a[G4C_REC_MAX_ABS_ERR], ad);
                     a[G4C_REC_TGT_SUM] += yt;
                     a[G4C_REC_TGT_SQ_SUM] += yt * yt;
                     a[G4C_REC_ABS_ERR_MASK] += masked ? ad : 0.0;

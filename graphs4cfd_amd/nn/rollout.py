@@ -545,7 +545,10 @@ class RolloutMoments:
     [N, nf, nf] = Σ d_f d_g / count − (Σd_f / count)(Σd_g / count) (symmetric, population-normalised; the shift by the first sample
     keeps it well-conditioned when the mean is far larger than the fluctuation), `var` = its diagonal, `std` = √max(var, 0).
     `count == 0` (no step of the window was taken) raises on the derived quantities.  Works on tensors of any device.
-    `snapshots`: the rollout's `result()` when `GNN.time_statistics(every=)` kept any, else None."""
+    `snapshots`: the rollout's `result()` when `GNN.time_statistics(every=)` kept any, else None.
+    Non-finite samples: a NaN sample at a node makes `min` and `max` of that node and field NaN, as it makes `sum` and `mean` (they
+    are NOT the extrema of the other samples), and they stay NaN for the rest of the window; ±inf are ordinary values.  Other nodes
+    and fields are untouched."""
 
     def __init__(self, count: int, origin: int, stride: int, pivot: torch.Tensor, sum: torch.Tensor, sum2: torch.Tensor,
                  min: torch.Tensor, max: torch.Tensor, snapshots: Optional[torch.Tensor] = None):
@@ -863,7 +866,9 @@ class RolloutDerived:
     each [steps, nd] — from `sums` [steps, nd, 3] = (Σq², Σ|q|, max|q|), which the step accumulated on the device in fp64 in a fixed
     order (fp64 host tensors).  `snapshots` [N, nd * (max_steps // k)]: the columns of steps k - 1, 2k - 1, ... (`derived_every=k`), else
     None; `moments`: their per-node time statistics (`RolloutMoments`, `derived_moments=`), else None; `degenerate` bool [N]: the
-    nodes whose neighbours do not span the space — their derivatives are 0.  Rows are the caller's numbering."""
+    nodes whose neighbours do not span the space — their derivatives are 0.  Rows are the caller's numbering.
+    Non-finite samples: a column that is NaN at any node of a step has `max_abs` = NaN at that step (not the maximum over the other
+    nodes), as `rms` and `mean_abs` are; +inf where the largest |q| is.  Other steps and columns are untouched."""
 
     def __init__(self, names, columns, sums: torch.Tensor, n_nodes: int, snapshots: Optional[torch.Tensor] = None,
                  moments: Optional["RolloutMoments"] = None, degenerate: Optional[torch.Tensor] = None):
@@ -1268,7 +1273,11 @@ class RolloutErrors:
     `mae_masked` = Σ|d| over the masked (Dirichlet) nodes / their number (None without a mask) — with d = prediction − target and
     y = the target, all from `sums` [steps, nf, 6] = (Σd², Σ|d|, max|d|, Σy, Σy², Σ_masked|d|), which the step's last launch
     accumulated on the device in fp64 in a fixed order.  `snapshots` / `probes`: the rollout's `result()` / `probes()` when it kept
-    any, else None.  `moments` / `error_moments`: None unless `GNN.evaluate` was asked for them."""
+    any, else None.  `moments` / `error_moments`: None unless `GNN.evaluate` was asked for them.
+    Non-finite samples (a rollout that blew up, a target with holes): `mse`, `mae` AND `max_abs` of a step and field are NaN when d is
+    NaN at any node — `max_abs` is never the maximum over the remaining nodes: a record does not read better than the rollout was —
+    and inf where the largest |d| is.  A row outside the mask contributes nothing to `mae_masked`, whatever it holds.  Every other
+    step and field is untouched."""
 
     def __init__(self, sums: torch.Tensor, n_nodes: int, n_masked: Optional[int] = None, snapshots: Optional[torch.Tensor] = None,
                  probes: Optional[torch.Tensor] = None):

@@ -473,7 +473,11 @@ int g4c_rollout_advance(float *field, int32_t field_cols, const float *pred, int
  * stats[t][f] = { sum d^2, sum |d|, max |d|, sum y, sum y^2, sum |d| over the rows with mask != 0 } (y = the target), accumulated in
  * fp64 without floating-point atomics in an order that depends on (n_nodes, nf) alone: bit-identical between runs and between captured
  * and eager launches.  stats[t] is overwritten.  The workgroups' partials go through `scratch` and are combined by a second, one-
- * workgroup launch on the same stream (rollout_record_stats_kernel). */
+ * workgroup launch on the same stream (rollout_record_stats_kernel).
+ * NON-FINITE SAMPLES (the rule of every in-step diagnostic): (1) sums follow IEEE — NaN where a NaN or an Inf − Inf
+ * entered; (2) an extremum over samples of which one is NaN IS NaN, at every stage of the reduction (±Inf are ordinary values): a
+ * record never reads better than the rollout was; (3) masks select — a row outside `mask` contributes nothing to
+ * G4C_REC_ABS_ERR_MASK, whatever it holds; (4) a poisoned value changes only the outputs that depend on it. */
 typedef struct g4c_rollout_rec {
     int32_t max_steps;           /* capacity of probe_out / stats / target, in steps */
     /* snapshots: step t (0-based) is kept iff every > 0 and (t + 1) % every == 0, in slot (t + 1) / every - 1, while slot < n_snap */
@@ -490,6 +494,7 @@ typedef struct g4c_rollout_rec {
     double *stats;               /* [max_steps][nf][G4C_REC_NSTAT] */
     double *scratch;             /* g4c_rollout_record_scratch_doubles(n_nodes, nf) doubles */
 } g4c_rollout_rec_t;
+/* G4C_REC_MAX_ABS_ERR is NaN when |d| is NaN at any node (not the maximum over the other nodes); +Inf when the largest |d| is. */
 enum { G4C_REC_SQ_ERR, G4C_REC_ABS_ERR, G4C_REC_MAX_ABS_ERR, G4C_REC_TGT_SUM, G4C_REC_TGT_SQ_SUM, G4C_REC_ABS_ERR_MASK, G4C_REC_NSTAT };
 /* Size of `scratch` in doubles (host; negative G4C_E* code for n_nodes < 0, nf < 1 or nf > 8). */
 int64_t g4c_rollout_record_scratch_doubles(int64_t n_nodes, int32_t nf);
@@ -503,8 +508,9 @@ int g4c_rollout_advance_record(float *field, int32_t field_cols, const float *pr
  * stride == 0, origin = window[0] read on the device (a captured launch follows a rewritten origin); an accumulated step leaves
  * window[1] = t, any other step touches nothing.  At t == origin the accumulators are STORED, not read: pivot = lo = hi = x, sum =
  * sum2 = 0 (no memset is ever needed; running through the origin again replaces the record).  On later steps, with d_f = x_f - pivot_f:
- * sum_f += d_f, sum2_fg += d_f d_g (the product rounded to fp64 once, then added: no fused multiply-add), lo = fmin(lo, x),
- * hi = fmax(hi, x).  Every accumulator receives one add per accumulated step, in time order, from one thread: the bits are a function
+ * sum_f += d_f, sum2_fg += d_f d_g (the product rounded to fp64 once, then added: no fused multiply-add), lo = min(lo, x),
+ * hi = max(hi, x), both NaN once either argument is (not fmin / fmax: after a NaN sample lo and hi of that node and field are NaN,
+ * as its sums are, and stay NaN until the origin is run through again; ±Inf are ordinary values).  Every accumulator receives one add per accumulated step, in time order, from one thread: the bits are a function
  * of the data alone (no atomics, nothing depends on the grid).
  * All accumulators are fp64 and plane-major: plane p of node n at base[p * plane_ld + n], plane_ld >= n_nodes.  sum2 holds the
  * nf (nf + 1) / 2 pairs f <= g in the order (0,0), (0,1), ..., (0,nf-1), (1,1), ...   nf = 1 .. 8 (G4C_EUNSUPPORTED above).
@@ -584,6 +590,7 @@ int g4c_mesh_gradient_weights(const int32_t *off, const int32_t *perm /*or NULL*
  * their buffers.  n_nodes == 0 launches nothing and succeeds. */
 #define G4C_DERIVED_MAX_COLS 8
 #define G4C_DERIVED_MAX_TERMS 3
+/* G4C_DERIVED_MAX_ABS is NaN when q is NaN at any node (the records' rule for non-finite samples, above), as the two sums are. */
 enum { G4C_DERIVED_SQ, G4C_DERIVED_ABS, G4C_DERIVED_MAX_ABS, G4C_DERIVED_NSTAT };
 typedef struct g4c_derived_program {
     int32_t nd;

@@ -8,7 +8,8 @@ One call, at step index t, with the sample x = pred (or pred - sub[:, nf t : nf 
   accumulated iff n > 0, 0 <= t < max_steps, t >= origin and (t - origin) % stride == 0; otherwise NOTHING changes;
   t == origin: pivot = lo = hi = x, sum = sum2 = 0 — stored, whatever the state held;
   later:       d = x - pivot; sum += d; sum2[fg] += d_f * d_g (numpy rounds the product to fp64, then adds: two roundings, no fused
-               multiply-add); lo = fmin(lo, x); hi = fmax(hi, x);
+               multiply-add); lo = minimum(lo, x); hi = maximum(hi, x) — numpy's NaN-propagating pair, not fmin / fmax: after a NaN
+               sample lo and hi are NaN, as the sums are, until the origin is run through again (±Inf are ordinary values);
   and last = t.
 Each accumulator gets one add per accumulated step, in time order: the device's bits must equal these exactly, on any data.
 
@@ -76,7 +77,7 @@ def accumulate(st: Dict[str, np.ndarray], pred, t: int, max_steps: int, stride: 
         for p, (f, g) in enumerate(pairs(nf, wrong)):
             prod = d[f] * d[g]
             out["sum2"][p] += prod
-        out["lo"], out["hi"] = np.fmin(out["lo"], x), np.fmax(out["hi"], x)
+        out["lo"], out["hi"] = np.minimum(out["lo"], x), np.maximum(out["hi"], x)
     out["window"][1] = t
     return out
 

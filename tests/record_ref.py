@@ -6,7 +6,8 @@ Records of step t (0-based), for 0 <= t < max_steps and a mesh of at least one n
   snapshots   every = k > 0 keeps the steps with (t + 1) % k == 0 in slot (t + 1) // k - 1, while the slot exists;
   probes      probe_out[t] = pred[probe_rows] (a row outside the mesh is left as it was);
   statistics  with y = target[:, nf t : nf (t + 1)] and d = pred - y in fp64, per field: [sum d^2, sum |d|, max |d|, sum y, sum y^2,
-              sum |d| over the rows of `mask`] — stats[t] is replaced.
+              sum |d| over the rows of `mask`] — stats[t] is replaced.  Non-finite samples: the sums follow IEEE, max |d| is NaN when
+              |d| is NaN at any node (torch's max propagates), and a row outside the mask contributes nothing whatever it holds.
 
 Two ways of comparing, as in oracle/grad_ref.py: `same` (bit for bit — data movement on any data, every statistic on small integers,
 whose sums are exact in fp64 in any order, and max |d| on any data: one rounding of d on each side) and `stats_close` (the five sums
@@ -50,7 +51,7 @@ def step_stats(pred: Tensor, target: Tensor, t: int, mask: Optional[Tensor], wro
     s[:, MAX_ABS_ERR] = ad.max(0).values if p.size(0) else 0.0
     s[:, TGT_SUM] = y.sum(0)
     s[:, TGT_SQ_SUM] = (y * y).sum(0)
-    s[:, ABS_ERR_MASK] = (ad * m[:, None]).sum(0)
+    s[:, ABS_ERR_MASK] = torch.where(m[:, None], ad, torch.zeros_like(ad)).sum(0)          # the mask selects: never ad * m
     a = s.clone()
     a[:, TGT_SUM] = y.abs().sum(0)
     return s, a
