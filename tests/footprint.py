@@ -105,6 +105,48 @@ def assert_footprint(whole, view, written_rows=None, what="", inside=True):
                                  f"column {int(at[0, 1]) - c0}) relative to the [{n}, {cols}] window")
 
 
+def assert_footprint_chunked(whole, view, written_rows=None, what="", inside=True, chunk_rows=1 << 20):
+    """`assert_footprint` for an arena too tall for masks of its own size (tests/test_gpu_tall.py): the same two demands, checked
+    `chunk_rows` rows of `whole` at a time.  `written_rows`: None (the whole window) or a bool mask over the window's rows (on the
+    arena's device)."""
+    idt, pat = PATTERN[whole.element_size()]
+    r0, c0, n, cols = _window(whole, view)
+    assert written_rows is None or (written_rows.dtype == torch.bool and tuple(written_rows.shape) == (n,))
+    ints = whole.view(idt)
+    for lo in range(0, int(whole.size(0)), chunk_rows):
+        hi = min(lo + chunk_rows, int(whole.size(0)))
+        changed = ints[lo:hi] != pat
+        own = torch.zeros(changed.shape, dtype=torch.bool, device=whole.device)
+        a, b = max(lo, r0), min(hi, r0 + n)
+        if a < b:
+            if written_rows is None:
+                own[a - lo:b - lo, c0:c0 + cols] = True
+            else:
+                own[a - lo:b - lo, c0:c0 + cols] = written_rows[a - r0:b - r0, None]
+        stray = changed & ~own
+        if bool(stray.any()):
+            at = torch.nonzero(stray)
+            raise AssertionError(f"{what}: {int(at.size(0))} element(s) written outside what the launch owns, the first at (row "
+                                 f"{int(at[0, 0]) + lo - r0}, column {int(at[0, 1]) - c0}) relative to the [{n}, {cols}] window")
+        if inside:
+            left = own & ~changed
+            if bool(left.any()):
+                at = torch.nonzero(left)
+                raise AssertionError(f"{what}: {int(at.size(0))} owned element(s) left unwritten, the first at (row "
+                                     f"{int(at[0, 0]) + lo - r0}, column {int(at[0, 1]) - c0}) relative to the [{n}, {cols}] window")
+
+
+def equal_bits_chunked(a, b, chunk_rows=1 << 20):
+    """Bit equality of two tensors of one shape and dtype, `chunk_rows` of the first dimension at a time: None, or the first row
+    (index into the first dimension) at which they differ."""
+    assert a.shape == b.shape and a.dtype == b.dtype
+    for lo in range(0, int(a.size(0)), chunk_rows):
+        x, y = _int_view(a[lo:lo + chunk_rows]), _int_view(b[lo:lo + chunk_rows])
+        if not torch.equal(x, y):
+            return lo + int(torch.nonzero((x != y).reshape(x.size(0), -1).any(1))[0])
+    return None
+
+
 @contextlib.contextmanager
 def frozen(*tensors, what=""):
     """Bit-exact copies of `tensors` (any dtype, any strides; None entries are skipped) on entry, bit equality on exit."""

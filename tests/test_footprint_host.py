@@ -130,3 +130,35 @@ def test_frozen_rejects_a_one_bit_change(dtype):
         with pytest.raises(AssertionError, match=r"the first at \(0, 0\)"):
             with FP.frozen(t):
                 bits[0, 0] ^= 1
+
+
+@pytest.mark.parametrize("chunk", [1, 7, 1000])
+def test_the_chunked_forms_agree_with_the_whole_ones(chunk):
+    """assert_footprint_chunked / equal_bits_chunked (tall arenas: tests/test_gpu_tall.py) accept and reject what the whole-tensor forms
+    do, whatever the chunk: a clean arena, a stray element in a guard row and in a row nobody owns, an owned element left unwritten."""
+    view, whole = FP.arena(20, 8, torch.float32, guard_rows=3, col0=0, pad_cols=0)
+    rows = torch.zeros(20, dtype=torch.bool)
+    rows[[0, 5, 19]] = True
+    view[rows] = 1.0
+    FP.assert_footprint(whole, view, rows)
+    FP.assert_footprint_chunked(whole, view, rows, chunk_rows=chunk)
+    for r, c, inside in ((1, 2, False), (3 + 6, 0, False), (3 + 5, 4, True)):          # guard row, unowned row, owned element
+        keep = whole[r, c].clone()
+        if inside:
+            FP.fill(whole[r:r + 1, c:c + 1])
+        else:
+            whole[r, c] = 2.0
+        for check in (lambda: FP.assert_footprint(whole, view, rows), lambda: FP.assert_footprint_chunked(whole, view, rows, chunk_rows=chunk)):
+            with pytest.raises(AssertionError, match="left unwritten" if inside else "outside what the launch owns"):
+                check()
+        whole[r, c] = keep
+    FP.assert_footprint_chunked(whole, view, rows, chunk_rows=chunk)
+    view[:] = 1.0
+    FP.assert_footprint_chunked(whole, view, chunk_rows=chunk)
+    a = torch.arange(60, dtype=torch.float32).reshape(20, 3)
+    b = a.clone()
+    assert FP.equal_bits_chunked(a, b, chunk_rows=chunk) is None
+    b[13, 1] = -b[13, 1]
+    assert FP.equal_bits_chunked(a, b, chunk_rows=chunk) == 13
+    n = torch.full((4, 2), float("nan"))
+    assert FP.equal_bits_chunked(n, n.clone(), chunk_rows=chunk) is None          # (bits, not floats: NaN equals the same NaN)

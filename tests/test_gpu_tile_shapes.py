@@ -157,6 +157,26 @@ def test_a_source_of_2_gib_runs_the_generic_kernel(tile_form):
     assert all(torch.equal(a, b) for a, b in zip(b_far, b_near))
 
 
+def test_an_output_of_2_gib_runs_the_generic_kernel(tile_form):
+    """The output rows go through a buffer descriptor with 32-bit offsets too: an output whose rows lie 8 300 000 floats apart (33 of
+    them; only the 128 columns the launch owns are written) takes the all-runtime kernel, the sources being compact, and holds what
+    the same launch writes into a compact output.  (tests/test_gpu_tall.py has the same decision at the production leading dimension:
+    16.8 million rows.)"""
+    lib = tile_form
+    upd, nxt = mlps(3)
+    m, ld = 33, 8_300_000
+    assert (m + 32) * ld * 4 >= 2 ** 31
+    srcs = [Source(**rows(m, 7, False)), Source(**rows(m, 8, False))]
+    far = torch.full((m, ld), SENTINEL, device=DEV)
+    lib.g4c_mlp_shapes_enable(1)
+    upd.run(srcs, m, "selu", out=far[:, :H])
+    s_far, k_far = int(lib.g4c_mlp_last_shape()), int(lib.g4c_mlp_last_kernel())
+    b_near, s_near, k_near = launch(lib, 1, upd, nxt, m, 0, srcs)
+    assert (s_far, s_near) == (GENERIC, NODE) and k_far == k_near == TILE_KERNEL[False]
+    assert torch.equal(far[:, :H], b_near[0][:m])
+    assert bool((far[:, H:H + 4096] == SENTINEL).all()) and bool((far[:, -4096:] == SENTINEL).all())
+
+
 def test_one_field_off_the_shape_runs_the_generic_kernel(tile_form):
     """Each launch matches the node-update shape in all but one field: shape 0, still the tile kernel."""
     lib = tile_form
