@@ -26,9 +26,9 @@ term would take edge_vectors="edge_attr" as --flow-loss does.  The loads are in 
 
 --residual-loss trains with gfd.nn.ResidualLoss: GraphLoss plus the residual of the incompressible momentum and continuity equations of the
 prediction minus that of the target (reference="target": the records' frame spacing is not a solver's time step), through the differentiable
-quadratic-fit operator (gfd.MeshJet) on its own stencil of the 12 nearest nodes of every graph of the batch.  That search is not periodic: the
-nodes next to the seam in y get a one-sided stencil, which a quadratic fit takes in its stride (on the graph's own periodic edges, k=None with
-edge_vectors="edge_attr", six neighbours condition five unknowns badly).  The fields are in their scaled units; pass scale= and shift= to
+quadratic-fit operator (gfd.MeshJet) on its own stencil of the 12 nearest nodes of every graph of the batch.  Without period= that search knows no
+seam: the nodes next to the seam in y get a one-sided stencil (ResidualLoss(period=(None, "auto")) wraps it; on the graph's own periodic
+edges, k=None with edge_vectors="edge_attr", six neighbours condition five unknowns badly).  The fields are in their scaled units; pass scale= and shift= to
 weigh the terms as the physical equation does.
 """
 import argparse, math, os, sys

@@ -164,6 +164,14 @@ class g4c_tracer_t(C.Structure):
                 ("status", C.c_void_p), ("stopped", C.c_void_p), ("release", C.c_void_p), ("vel", C.c_void_p)]
 
 
+class g4c_periodic_grid_t(C.Structure):             # the cell grid of the periodic searches (csrc/knn_periodic.hip)
+    _fields_ = [("n_cells", C.c_int32 * 3), ("origin", C.c_float * 3), ("period", C.c_float * 3), ("cell", C.c_double * 3)]
+
+
+class g4c_tracer_periodic_t(C.Structure):
+    _fields_ = [("base", g4c_tracer_t), ("period", C.c_float * 3), ("cell", C.c_double * 3)]
+
+
 # g4c_snapshot_* (csrc/snapshot_modes.hip): the envelope and the tile sizes the tests walk
 SNAPSHOT_MAX_ROWS = 1024                           # G4C_SNAPSHOT_MAX_ROWS: Ma, Mb, R
 SNAPSHOT_MAX_COLUMNS = 2 ** 31 - 1                 # G4C_SNAPSHOT_MAX_COLUMNS: L
@@ -210,6 +218,10 @@ _SIGNATURES = {
                                C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "g4c_knn_grid_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "g4c_knn_grid_periodic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(g4c_periodic_grid_t), C.c_int32,
+                                        C.c_void_p, C.c_void_p]),
+    "g4c_knn_grid_query_periodic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(g4c_periodic_grid_t),
+                                              C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "g4c_rollout_advance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_rollout_record_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
@@ -233,10 +245,13 @@ _SIGNATURES = {
     "g4c_body_forces_adjoint": (C.c_int, [C.POINTER(g4c_body_forces_adjoint_t), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "g4c_sample_weights_periodic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_sample_points": (C.c_int, [C.c_void_p, C.POINTER(g4c_sample_points_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_sample_points_adjoint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p]),
     "g4c_tracer_advance": (C.c_int, [C.POINTER(g4c_tracer_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_tracer_advance_periodic": (C.c_int, [C.POINTER(g4c_tracer_periodic_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_snapshot_mean": (C.c_int, [C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_snapshot_gram_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "g4c_snapshot_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t),

@@ -12,6 +12,7 @@
 // the data alone.  The tables are j-major [k, P]: lane p reads consecutive addresses.  Plain loads and stores, no atomics.
 #include "g4c_common.h"
 #include "point_fit.h"
+#include "knn_periodic.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
 // bits, and the fp64 coefficients differ from their restatement by the library's square root and division at most.
@@ -47,6 +48,43 @@ __global__ __launch_bounds__(PS_THREADS) void sample_weights_kernel(const float 
         return r2;
     };
     const bool degen = g4c::mls_fit<DIM, 0>(k, power, nb, [&](double r20) { distance[p] = (float)sqrt(r20); },          // point_fit.h
+                                            [&](int j, float c) { coef[(long long)j * n_points + p] = c; });
+    degenerate[p] = degen ? 1 : 0;
+}
+
+// The same fit in the wrapped metric (g4c_sample_weights_periodic): the point is wrapped into the period first, and the neighbour
+// lambda wraps every d_j.  A kernel of its own: sample_weights_kernel keeps its body and its bits.
+template <int DIM>
+__global__ __launch_bounds__(PS_THREADS) void sample_weights_periodic_kernel(const float *__restrict__ pos, const float *__restrict__ q,
+                                                                            const int *__restrict__ idx, int k, int power,
+                                                                            long long n_points, float o0, float o1, float o2, float l0,
+                                                                            float l1, float l2, float *__restrict__ coef,
+                                                                            float *__restrict__ distance,
+                                                                            unsigned char *__restrict__ degenerate) {
+    const long long p = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+    if (p >= n_points) return;
+    const float org[3] = {o0, o1, o2}, per32[3] = {l0, l1, l2};
+    double qd[DIM], per[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        float v = q[p * DIM + a];
+        if (per32[a] > 0.f) v = g4c::wrap_coordinate(v, org[a], per32[a]);          // knn_periodic.h
+        qd[a] = (double)v;
+        per[a] = (double)per32[a];
+    }
+    auto nb = [&](int j, double (&d)[DIM]) -> double {          // d_j = the wrapped pos[idx_j] - q, returns r2_j
+        const long long i = idx[(long long)j * n_points + p];
+        double r2 = 0.0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            d[a] = (double)pos[i * DIM + a] - qd[a];
+            if (per[a] > 0.0) d[a] = g4c::wrapped_offset(d[a], per[a]);
+            const double sq = d[a] * d[a];
+            r2 += sq;
+        }
+        return r2;
+    };
+    const bool degen = g4c::mls_fit<DIM, 0>(k, power, nb, [&](double r20) { distance[p] = (float)sqrt(r20); },
                                             [&](int j, float c) { coef[(long long)j * n_points + p] = c; });
     degenerate[p] = degen ? 1 : 0;
 }
@@ -165,6 +203,39 @@ extern "C" int g4c_sample_weights(const float *pos, const float *queries, const 
         sample_weights_kernel<2><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, coef, distance, degenerate);
     else
         sample_weights_kernel<3><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, coef, distance, degenerate);
+    return g4c::check_launch(me);
+}
+
+extern "C" int g4c_sample_weights_periodic(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
+                                           int64_t n_nodes, int64_t n_points, const float *origin /*host[3]*/,
+                                           const float *period /*host[3]*/, float *coef, float *distance, uint8_t *degenerate,
+                                           void *stream) {
+    const char *me = "g4c_sample_weights_periodic";
+    G4C_REQUIRE(n_nodes >= 0 && n_points >= 0 && k >= 1, G4C_EINVAL, "%s: bad sizes n_nodes=%lld n_points=%lld k=%d", me,
+                (long long)n_nodes, (long long)n_points, k);
+    G4C_REQUIRE(power >= 0 && power <= 2, G4C_EINVAL, "%s: power=%d (0, 1 or 2)", me, power);
+    G4C_REQUIRE(dim == 2 || dim == 3, G4C_EUNSUPPORTED, "%s: dim=%d (2 or 3 are supported)", me, dim);
+    G4C_REQUIRE(k <= PS_MAX_K, G4C_EUNSUPPORTED, "%s: k=%d neighbours (1 .. %d are supported)", me, k, PS_MAX_K);
+    G4C_REQUIRE(origin && period, G4C_EINVAL, "%s: null pointer", me);
+    float o[3] = {0.f, 0.f, 0.f}, l[3] = {0.f, 0.f, 0.f};
+    for (int a = 0; a < dim; ++a) {
+        o[a] = origin[a];
+        l[a] = period[a];
+        G4C_REQUIRE(l[a] >= 0.f && l[a] < __builtin_inff() && (l[a] == 0.f || (o[a] == o[a] && fabsf(o[a]) < __builtin_inff())),
+                    G4C_EINVAL, "%s: axis %d: period %g (0: not periodic) from origin %g", me, a, (double)l[a], (double)o[a]);
+    }
+    if (n_points == 0) return G4C_OK;
+    G4C_REQUIRE(n_nodes >= k, G4C_EINVAL, "%s: k=%d neighbours of n_nodes=%lld", me, k, (long long)n_nodes);
+    G4C_REQUIRE(pos && queries && idx && coef && distance && degenerate, G4C_EINVAL, "%s: null pointer", me);
+    g4c::DeviceGuard on_device(pos);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n_points + PS_THREADS - 1) / PS_THREADS);
+    if (dim == 2)
+        sample_weights_periodic_kernel<2><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, o[0], o[1], o[2],
+                                                                                   l[0], l[1], l[2], coef, distance, degenerate);
+    else
+        sample_weights_periodic_kernel<3><<<dim3(blocks), dim3(PS_THREADS), 0, s>>>(pos, queries, idx, k, power, n_points, o[0], o[1], o[2],
+                                                                                   l[0], l[1], l[2], coef, distance, degenerate);
     return g4c::check_launch(me);
 }
 

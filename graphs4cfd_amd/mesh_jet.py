@@ -86,9 +86,18 @@ def jet_terms(names, dim: int, nf: int, velocity=None, field_scale=None) -> List
     return prog
 
 
-def check_stencil(graph, k, power, edge_vectors) -> int:
+def check_stencil(graph, k, power, edge_vectors, period=None) -> int:
     """The arguments of `MeshJet` on the tensors as they were passed (nothing is moved, the library is not touched): the mesh's
     dimension, or ValueError naming the argument."""
+    if period is not None:
+        if edge_vectors is not None:
+            raise ValueError("period: it belongs to the operator's own search (k=); edge_vectors belong to the graph's edges — on a "
+                             "periodic mesh pass the wrapped edge_attr OR k= with period=")
+        if k is None:
+            raise ValueError("period: with k=None the stencil is the graph's in-edges and nothing is searched; pass k= (<= 16) with "
+                             "period=, or the wrapped edge_attr as edge_vectors")
+        if isinstance(k, int) and not isinstance(k, bool) and k > PERIODIC_MAX_K:
+            raise ValueError(f"k: the periodic search returns at most {PERIODIC_MAX_K} neighbours, got k={k!r} with period=")
     if k is None:
         try:
             return check_mesh(graph, power, edge_vectors)
@@ -98,7 +107,7 @@ def check_stencil(graph, k, power, edge_vectors) -> int:
         raise ValueError(f"power: expected 0, 1 or 2 (a stencil entry weighs |d|^-power), got {power!r}")
     if edge_vectors is not None:
         raise ValueError("edge_vectors: they belong to the graph's edges; with k= the operator searches a stencil of its own over "
-                         "graph.pos (not periodic) — pass one of the two")
+                         "graph.pos — pass one of the two")
     pos = getattr(graph, "pos", None)
     if not torch.is_tensor(pos) or pos.dim() != 2 or int(pos.size(1)) not in (2, 3) or not pos.dtype.is_floating_point:
         raise ValueError("graph: MeshJet(k=) needs graph.pos [N, 2] or [N, 3]")
@@ -106,7 +115,13 @@ def check_stencil(graph, k, power, edge_vectors) -> int:
     Q = ops.jet_size(dim)
     if isinstance(k, bool) or not isinstance(k, int) or not Q <= k <= MAX_K:
         raise ValueError(f"k: expected None (the graph's in-edges) or an integer {Q} <= k <= {MAX_K} on a {dim}-D mesh, got {k!r}")
+    if period is not None:
+        from .synthetic import check_period
+        check_period(period, dim, "MeshJet")
     return dim
+
+
+PERIODIC_MAX_K = 16          # the periodic search's limit (g4c_knn_grid_periodic)
 
 
 class MeshJet(_StencilOperator):
@@ -118,8 +133,12 @@ class MeshJet(_StencilOperator):
     rows for 5 unknowns — most of its nodes are not degenerate but are badly conditioned (scaled pivots down to 1e-5 on a random
     cloud, against 1e-2 with 12 neighbours), and their second derivatives are noisy.
     `k=int`: the stencil is the k nearest other nodes of `graph.pos` (`knn_neighbours_device`), Q <= k <= 32, searched per graph of
-    `graph.batch` when the graph is a collated batch (graphs of a batch overlap in space).  That search is not periodic, and
-    `edge_vectors` together with `k` is a ValueError.  Suggested: k = 12 in 2-D, 20 in 3-D (2 Q + 2; not tuned).
+    `graph.batch` when the graph is a collated batch (graphs of a batch overlap in space).  `edge_vectors` together with `k` is a
+    ValueError.  Suggested: k = 12 in 2-D, 20 in 3-D (2 Q + 2; not tuned).
+    `period` (with `k=int`, k <= 16; one entry per axis: None, a length >= the extent, or "auto", the extent — as `connect_knn`'s):
+    the stencil is searched in the wrapped metric (`knn_neighbours_device(period=)`) and its offsets are wrapped, so a node at the
+    seam of a periodic mesh gets a two-sided stencil.  In a batch each graph is searched from its own origin, with its own "auto"
+    extent.  `period` with `k=None` or `edge_vectors` is a ValueError.
 
     `derived(x, names)` [N, nd] with the names of `MeshGradient` — 'div', 'vort', 'grad:<f>', here from the quadratic fit's first
     derivatives — and 'lap:<f>' (one column, Σ_a ∂_a∂_a) and 'hess:<f>' (Q − dim columns: xx, xy, yy or xx, xy, xz, yy, yz, zz);
@@ -129,8 +148,8 @@ class MeshJet(_StencilOperator):
     of the same linear map (`g4c_mesh_jet_adjoint`; the rows c are constants: no gradient reaches the mesh, and there is no double
     backward).  The sender-side tables the adjoint walks are built on its first use.  HIP device only."""
 
-    def __init__(self, graph, k: Optional[int] = None, power: int = 2, edge_vectors: Optional[torch.Tensor] = None):
-        self.dim = check_stencil(graph, k, power, edge_vectors)
+    def __init__(self, graph, k: Optional[int] = None, power: int = 2, edge_vectors: Optional[torch.Tensor] = None, period=None):
+        self.dim = check_stencil(graph, k, power, edge_vectors, period)
         self.k, self.power = k, power
         self.n_nodes = int(graph.num_nodes)
         if k is None:
@@ -148,7 +167,7 @@ class MeshJet(_StencilOperator):
             pos = graph.pos
             if pos.device.type != "cuda":
                 raise ValueError(f"graph: MeshJet runs on a HIP device only, graph.pos is on '{pos.device}' (there is no CPU fallback)")
-            csr, src32, rel = self._own_stencil(pos.detach().to(torch.float32), getattr(graph, "batch", None), k)
+            csr, src32, rel = self._own_stencil(pos.detach().to(torch.float32), getattr(graph, "batch", None), k, period)
             self.max_deg = k
         self.off = csr.off
         self.c, self.src, degenerate = ops.mesh_jet_weights(rel, csr, src32, power)
@@ -156,9 +175,11 @@ class MeshJet(_StencilOperator):
         self._adjoint_tables = None
 
     @staticmethod
-    def _own_stencil(pos, batch, k):
-        """(csr, src32 [N·k], rel [N·k, dim]): the k nearest other nodes of every node within its own graph, nearest first."""
-        from .synthetic import knn_neighbours_device
+    def _own_stencil(pos, batch, k, period=None):
+        """(csr, src32 [N·k], rel [N·k, dim]): the k nearest other nodes of every node within its own graph, nearest first.  With
+        `period`: in the wrapped metric of each graph's own frame, rel the fp32 rounding of the search's wrapped fp64 offset."""
+        from .synthetic import check_period, knn_neighbours_device, periodic_frame
+        per = check_period(period, int(pos.size(1)), "MeshJet")
         n = int(pos.size(0))
         if batch is None:
             counts = [n]
@@ -169,12 +190,26 @@ class MeshJet(_StencilOperator):
         if min(counts) <= k:
             raise ValueError(f"k: {k} neighbours of a graph with {min(counts)} nodes (a node's stencil holds k OTHER nodes)")
         nbr, a = torch.empty((n, k), dtype=torch.long, device=pos.device), 0
+        lengths = None if per is None else torch.zeros((n, int(pos.size(1))), dtype=torch.float32, device=pos.device)
         for c in counts:          # (contiguous ranges: `collate` numbers the nodes graph after graph)
-            knn_neighbours_device(pos[a:a + c].contiguous(), k, out=nbr[a:a + c])
+            own = pos[a:a + c].contiguous()
+            if per is None:
+                knn_neighbours_device(own, k, out=nbr[a:a + c])
+            else:
+                L = periodic_frame(own, per, "MeshJet")[1]
+                knn_neighbours_device(own, k, out=nbr[a:a + c], period=[v or None for v in L])
+                lengths[a:a + c] = torch.tensor(L, dtype=torch.float32, device=pos.device)
             nbr[a:a + c] += a
             a += c
         src = nbr.reshape(-1)
         rel = (pos.repeat_interleave(k, dim=0) - pos[src]).contiguous()
+        if per is not None:
+            # the search's own rule on the fp64 difference (strict, applied once; a length 0: not periodic), so rel is the image
+            # the search ranked; rounded to fp32 once — where nothing wraps that IS the fp32 difference above
+            L = lengths.repeat_interleave(k, dim=0).double()
+            d = pos.double().repeat_interleave(k, dim=0) - pos.double()[src]
+            d = torch.where((L > 0) & (d > 0.5 * L), d - L, torch.where((L > 0) & (d < -0.5 * L), d + L, d))
+            rel = d.to(torch.float32).contiguous()
         off = torch.arange(0, n * k + 1, k, dtype=torch.int32, device=pos.device)
         return SimpleNamespace(off=off, perm=None, n=n * k), src.to(torch.int32), rel
 

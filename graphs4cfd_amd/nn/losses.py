@@ -222,7 +222,8 @@ class SampleLoss(_OperatorLoss):
     no pressure), F' of them.  ref is S·target when `values` is None (a loss weighted towards a region: no data beyond the node
     targets), otherwise `getattr(graph, values)[:, F'·t : F'·(t + 1)]` — observations [P, F'·T] per graph, for output step t = `step`
     (`takes_step`: `Trainer` passes step=t; `values=` without a step is a ValueError).  `max_distance` drops the points farther than
-    that from their nearest node (inside a body, outside the domain); with no point kept the term is 0.
+    that from their nearest node (inside a body, outside the domain); with no point kept the term is 0.  `period`: `PointSampler`'s,
+    passed to each graph's sampler (a periodic mesh: the points next to the seam are fitted from both sides of it).
 
     `node_weight == 0` skips `GraphLoss` (training on observations alone); `weight == 0` launches nothing, builds nothing and is
     node_weight · GraphLoss bit for bit.  The sample is differentiable (`g4c_sample_points_adjoint` in the backward).
@@ -236,8 +237,10 @@ class SampleLoss(_OperatorLoss):
 
     takes_step = True
 
-    def __init__(self, points, lambda_d=0, weight=1.0, node_weight=1.0, values=None, fields=None, k=None, power=2, max_distance=None):
+    def __init__(self, points, lambda_d=0, weight=1.0, node_weight=1.0, values=None, fields=None, k=None, power=2, max_distance=None,
+                 period=None):
         from ..point_sampler import MAX_K
+        from ..synthetic import check_period
         if not torch.is_tensor(points) or not points.dtype.is_floating_point or points.dim() != 2 or int(points.size(1)) not in (2, 3):
             raise ValueError(f"points: expected a floating-point tensor [P, 2] or [P, 3], got "
                              f"{getattr(points, 'dtype', type(points).__name__)} {tuple(getattr(points, 'shape', ()))}")
@@ -252,6 +255,7 @@ class SampleLoss(_OperatorLoss):
         if max_distance is not None:
             max_distance = _number(max_distance, "max_distance", "None or a finite distance >= 0")
         self.points, self.values, self.fields, self.k, self.power, self.max_distance = points.detach(), values, fields, k, power, max_distance
+        self.period = check_period(period, int(points.size(1)), "SampleLoss")
 
     def sampler(self, graph):
         """(the `PointSampler` of `graph` — of all its graphs, when it is a batch —, the bool [P] mask of the kept points or None for
@@ -270,11 +274,11 @@ class SampleLoss(_OperatorLoss):
         if sum(counts) != n:
             raise ValueError(f"graph: graph.batch names {sum(counts)} nodes, graph.pos has {n}")
         if len(counts) == 1:
-            s = PointSampler(graph, self.points, k=self.k, power=self.power)
+            s = PointSampler(graph, self.points, k=self.k, power=self.power, period=self.period)
         else:
             parts, a = [], 0
             for c in counts:          # (contiguous ranges: `collate` numbers the nodes graph after graph)
-                one = PointSampler(Graph(pos=pos[a:a + c]), self.points, k=self.k, power=self.power)
+                one = PointSampler(Graph(pos=pos[a:a + c]), self.points, k=self.k, power=self.power, period=self.period)
                 parts.append((one._idx + a, one._coef, one.distance, one.degenerate))
                 a += c
             idx, coef, distance, degenerate = (torch.cat(t, dim=-1).contiguous() for t in zip(*parts))
@@ -490,6 +494,7 @@ class ResidualLoss(_OperatorLoss):
     The derivatives are `gfd.MeshJet`'s (a quadratic fit: ∇² from a composed linear gradient does not converge): `k` its own stencil
     (default 12; 20 is the suggestion in 3-D) or None for the graph's in-edges, then with `edge_vectors` None or the name of a graph
     attribute holding the unscaled, wrapped [E, dim] vectors (a periodic mesh); `edge_vectors` together with `k` is a ValueError.
+    `period` (with `k`, k <= 16): `MeshJet`'s — the stencil search and its offsets are wrapped, per graph of a batch.
     All derivatives of one tensor come from ONE `MeshJet.derived` launch in 2-D (grad u, grad v, grad p, ∇²u, ∇²v: eight columns)
     and from two in 3-D (fifteen columns); the products are torch arithmetic, and their gradients reach the model through
     `MeshJet.adjoint` (`g4c_mesh_jet_adjoint`).  No double backward.  The operator is kept (one entry) while the tensors it was
@@ -498,9 +503,9 @@ class ResidualLoss(_OperatorLoss):
     node_weight · GraphLoss bit for bit; `node_weight == 0` skips `GraphLoss`.  HIP device only."""
 
     def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, nu, dt, rho=1.0, velocity=None, pressure=None, scale=None, shift=None,
-                 continuity=1.0, reference="target", k=12, power=2, edge_vectors=None, mask=None):
+                 continuity=1.0, reference="target", k=12, power=2, edge_vectors=None, mask=None, period=None):
         super().__init__(lambda_d, weight, node_weight)
-        from ..mesh_jet import MAX_K
+        from ..mesh_jet import MAX_K, PERIODIC_MAX_K
         if isinstance(nu, str):
             if not nu:
                 raise ValueError(f"nu: expected a finite number >= 0 or the name of a per-node graph attribute, got {nu!r}")
@@ -523,8 +528,18 @@ class ResidualLoss(_OperatorLoss):
         _attribute(edge_vectors, "edge_vectors")
         _attribute(mask, "mask")
         if edge_vectors is not None and k is not None:
-            raise ValueError("edge_vectors: they belong to the graph's edges; pass k=None with them (the operator's own stencil search "
-                             "is not periodic)")
+            raise ValueError("edge_vectors: they belong to the graph's edges; pass k=None with them (on a periodic mesh: the wrapped "
+                             "edge_attr with k=None, or k= with period=)")
+        if period is not None:
+            if edge_vectors is not None or k is None:
+                raise ValueError("period: it belongs to the operator's own stencil search: pass k= (<= 16) with it, and no edge_vectors")
+            if k > PERIODIC_MAX_K:
+                raise ValueError(f"k: the periodic search returns at most {PERIODIC_MAX_K} neighbours, got k={k!r} with period=")
+            try:
+                period = list(period)
+            except TypeError:
+                raise ValueError(f"period: expected one entry per axis (None, a length > 0 or \"auto\"), got {period!r}") from None
+        self.period = period
         self.nu, self.dt, self.rho = nu, float(dt), float(rho)
         self.velocity, self.pressure, self.scale, self.shift = velocity, pressure, scale, shift
         self.reference, self.k, self.power, self.edge_vectors, self.mask = reference, k, power, edge_vectors, mask
@@ -543,7 +558,7 @@ class ResidualLoss(_OperatorLoss):
                 if not torch.is_tensor(vec):
                     raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
             key = [getattr(graph, "edge_index", None), getattr(graph, "pos", None) if vec is None else vec]
-        return self.keep(key, lambda: MeshJet(graph, k=self.k, power=self.power, edge_vectors=vec))
+        return self.keep(key, lambda: MeshJet(graph, k=self.k, power=self.power, edge_vectors=vec, period=self.period))
 
     @staticmethod
     def _launches(names, columns, fields):

@@ -289,7 +289,7 @@ class GNN(nn.Module):
               **options) -> "RolloutTracers":
         """Roll the model out for n_out steps and return the particles its velocity carried (`RolloutTracers`: paths, last positions,
         status, stopped) — `seeds` [S, dim] with `dt` and the options of `gfd.Tracers` (scheme, k, power, velocity, scale, shift, box,
-        max_distance, release), or a `gfd.Tracers` built on this graph (a streak) — advected on the device inside the step.  No
+        max_distance, release, period — a periodic domain: `.paths` then hold wrapped positions), or a `gfd.Tracers` built on this graph (a streak) — advected on the device inside the step.  No
         prediction is held.  every = k keeps the positions after steps k - 1, 2k - 1, ... (`.paths`; 0 keeps none).  One graph only:
         a list of graphs overlaps in space."""
         assert n_out > 0, "n_out must be greater than 0."

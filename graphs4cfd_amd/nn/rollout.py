@@ -85,8 +85,9 @@ class Rollout:
         k - 1, 2k - 1, ... (0 keeps no series); `sample_moments` (the forms `moments` takes) and `sample_spectrum` (a `gfd.Spectrum`)
         accumulate the time statistics and Fourier modes of the sampled prediction at every point, by the kernels the nodes use.
         `samples()` returns them (`RolloutSamples`), the points in the caller's order; after `rewind()` or a recomputation the
-        accumulators hold the steps taken since and the slots of the steps run again are overwritten.  The neighbour search is not
-        periodic (`gfd.PointSampler`), and a list of graphs — they overlap in space — is refused.
+        accumulators hold the steps taken since and the slots of the steps run again are overwritten.  A tensor of points is searched without
+        a period; on a periodic mesh pass a `gfd.PointSampler(graph, points, period=...)`.  A list of graphs — they overlap in
+        space — is refused.
 
         Lagrangian tracers (opt-in, no record either): `tracers` — a `gfd.Tracers` built on this graph, or a tuple (seeds [S, dim], dt)
         (tracers with their defaults are built here) — moves a copy of the particles through every step: one `g4c_tracer_advance`

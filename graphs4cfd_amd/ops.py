@@ -1248,13 +1248,30 @@ def _sample_tables(what, idx, coef):
     return k, n_points
 
 
-def sample_weights(pos: Tensor, queries: Tensor, idx: Tensor, power: int = 2, out=None):
+def _periodic_axes(what: str, name: str, v, dim: int):
+    """`dim` finite numbers >= 0 (0: an axis that is not periodic) padded to 3 floats; ValueError naming the argument."""
+    try:
+        vals = [float(c) for c in v]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: {what}: expected {dim} numbers >= 0, got {v!r}") from None
+    if len(vals) not in (dim, 3) or not all(0.0 <= c < float("inf") for c in vals) or any(vals[dim:]):
+        raise ValueError(f"{name}: {what}: expected {dim} finite numbers >= 0 (0: the axis is not periodic), got {v!r}")
+    return vals[:dim] + [0.0] * (3 - dim)
+
+
+def sample_weights(pos: Tensor, queries: Tensor, idx: Tensor, power: int = 2, out=None, *, origin=None, period=None):
     """g4c_sample_weights: the coefficients of a moving-least-squares fit with a linear basis, once per set of points.  pos float32
     [N, dim] the nodes, queries float32 [P, dim] the points, idx int32 [k, P] (j-major, nearest first: `knn_query_device`'s rows,
     transposed) their k <= 16 nearest nodes; power 0, 1 or 2 weighs a neighbour by its distance^(-power).  Returns (coef float32
     [k, P], distance float32 [P] — to the nearest node —, degenerate uint8 [P]); include/g4c.h has the arithmetic.  `out`: the three
-    tensors to write into; no points launch nothing."""
+    tensors to write into; no points launch nothing.
+
+    `period` (dim fp32 lengths, 0 an axis that is not periodic) with `origin` (dim numbers, the cloud's minimum): the fit over wrapped
+    offsets (g4c_sample_weights_periodic) — the points are wrapped into the period, every offset by `connect_knn`'s rule; idx are
+    then `knn_query_device(period=)`'s rows and distance is the wrapped one."""
     what = "sample_weights"
+    if (origin is None) != (period is None):
+        raise ValueError(f"period: {what}: origin and period come together")
     if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
         raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
     _mesh_arg(what, pos, "pos", torch.float32, dim=2)
@@ -1278,6 +1295,15 @@ def sample_weights(pos: Tensor, queries: Tensor, idx: Tensor, power: int = 2, ou
         distance = torch.empty((n_points,), dtype=torch.float32, device=dev)
         degenerate = torch.empty((n_points,), dtype=torch.uint8, device=dev)
     lib = _lib.load()
+    if period is not None:
+        per, org = _periodic_axes(what, "period", period, dim), [float(o) for o in origin]
+        if len(org) not in (dim, 3) or not all(abs(o) < float("inf") for o in org):
+            raise ValueError(f"origin: {what}: expected {dim} finite numbers, got {origin!r}")
+        org = org[:dim] + [0.0] * (3 - dim)
+        _lib.check(lib.g4c_sample_weights_periodic(_lib.ptr(pos), _lib.ptr(queries), _lib.ptr(idx), dim, power, k, n_nodes, n_points,
+                                                   (C.c_float * 3)(*org), (C.c_float * 3)(*per), _lib.ptr(coef), _lib.ptr(distance),
+                                                   _lib.ptr(degenerate), _lib.stream_handle(dev)))
+        return coef, distance, degenerate
     _lib.check(lib.g4c_sample_weights(_lib.ptr(pos), _lib.ptr(queries), _lib.ptr(idx), dim, power, k, n_nodes, n_points, _lib.ptr(coef),
                                       _lib.ptr(distance), _lib.ptr(degenerate), _lib.stream_handle(dev)))
     return coef, distance, degenerate
@@ -1480,6 +1506,14 @@ def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, stat
                            n_slots=0 if series is None else int(series.size(0)), series=_lib.ptr(series), q=_lib.ptr(q),
                            status=_lib.ptr(status), stopped=_lib.ptr(stopped), release=_lib.ptr(release), vel=_lib.ptr(vel))
     lib = _lib.load()
+    if "periods" in grid:          # (`synthetic._bin_cloud_periodic`'s grid: the periodic launch)
+        periods = _periodic_axes(what, "grid['periods']", grid["periods"], dim)
+        cell = _periodic_axes(what, "grid['cells']", list(grid.get("cells") or ())[:dim], dim)[:dim] + [1.0] * (3 - dim)
+        if not all(c > 0.0 for c in cell):
+            raise ValueError(f"grid['cells']: {what}: expected {dim} cell sizes > 0, got {grid.get('cells')!r}")
+        trp = _lib.g4c_tracer_periodic_t(base=tr, period=(C.c_float * 3)(*periods), cell=(C.c_double * 3)(*cell))
+        _lib.check(lib.g4c_tracer_advance_periodic(C.byref(trp), n_nodes, n_particles, _lib.stream_handle(dev)))
+        return q
     _lib.check(lib.g4c_tracer_advance(C.byref(tr), n_nodes, n_particles, _lib.stream_handle(dev)))
     return q
 

@@ -77,30 +77,42 @@ class PointSampler:
     is sampled from the nodes nearest to it: mask by `distance`; `degenerate` bool [P]: the points whose neighbours do not span the
     space (Shepard's weights there: exact on constants only).  `PointSampler.line` and `PointSampler.grid` build rakes and rasters.
 
-    The search is NOT periodic: a point near the seam of a periodic mesh uses the neighbours on its own side; the fit is then
-    one-sided, and still exact on linear fields.
+    `period` (one entry per axis: None, a length >= the mesh's extent, or "auto", the extent; as `connect_knn`'s): the search and the
+    fit run in the wrapped metric (`knn_query_device(period=)`, `g4c_sample_weights_periodic`) — a point next to the seam is fitted
+    from both sides of it, `distance` is the wrapped distance, and a point may lie periods away (wrapped exactly as far as fp32
+    resolves (point − origin) / period).  Finite points are the caller's to provide: a device coordinate that is not finite is
+    searched from the origin along a periodic axis; along another axis the point has no neighbours — its row names node 0 and its
+    coefficients are NaN.  `sampler.period` keeps (origin, lengths): the mesh's minimum and the fp32 periods, 0 for an axis that is
+    not periodic.  All None: the plain search.
 
     `sample` of an x that requires grad is recorded for autograd: its backward is `adjoint(gy)` [N, F], the transpose of the same
     linear map (`g4c_sample_points_adjoint`; the coefficients are constants: no gradient reaches the points or the mesh).  The
     node-side tables the adjoint walks are built on its first use.  `PointSampler.from_tables` takes tables fitted elsewhere."""
 
-    def __init__(self, graph, points: torch.Tensor, k: Optional[int] = None, power: int = 2):
+    def __init__(self, graph, points: torch.Tensor, k: Optional[int] = None, power: int = 2, period=None):
         self.dim, self.k = check_points(graph, points, k, power)
+        from .synthetic import check_period, knn_query_device, periodic_frame
+        per = check_period(period, self.dim, "PointSampler")
         pos = graph.pos
         if pos.device.type != "cuda":
             raise ValueError(f"graph: PointSampler runs on a HIP device only, graph.pos is on '{pos.device}' (there is no CPU fallback)")
-        from .synthetic import knn_query_device
         self.power, self.n_nodes, self.shape = power, int(pos.size(0)), None
         dev = pos.device
         pos32 = pos.detach().to(torch.float32).contiguous()
         self.points = points.detach().to(dev, torch.float32).contiguous()
         n_points = int(self.points.size(0))
+        # (origin, lengths) of the periodic frame — the cloud's minimum and the fp32 periods, 0 a non-periodic axis — or None
+        self.period = None if per is None else periodic_frame(pos32, per, "PointSampler")
+        wrapped = {} if self.period is None else dict(origin=self.period[0], period=self.period[1])
         if n_points:
-            nearest = knn_query_device(pos32, self.points, self.k)                          # [P, k] int64, nearest first
+            nearest = knn_query_device(pos32, self.points, self.k,                          # [P, k] int64, nearest first
+                                       period=None if per is None else [L or None for L in self.period[1]])
+            if per is not None:          # (a point that is not finite along a non-periodic axis has the row −1: it never forms an address)
+                nearest = nearest.clamp_(min=0)
             self._idx = nearest.t().to(torch.int32).contiguous()                            # j-major: lane p reads consecutive entries
         else:
             self._idx = torch.empty((self.k, 0), dtype=torch.int32, device=dev)
-        self._coef, self.distance, degenerate = ops.sample_weights(pos32, self.points, self._idx, power)
+        self._coef, self.distance, degenerate = ops.sample_weights(pos32, self.points, self._idx, power, **wrapped)
         self.degenerate = degenerate.bool()
         self._adjoint_tables = None
 
@@ -127,7 +139,7 @@ class PointSampler:
                 raise ValueError(f"{name}: expected a tensor [{n_points}], got {tuple(getattr(t, 'shape', ()))}")
         s = cls.__new__(cls)
         s.dim = None if points is None else int(points.size(1))
-        s.k, s.power, s.n_nodes, s.shape = k, None, n_nodes, None
+        s.k, s.power, s.n_nodes, s.shape, s.period = k, None, n_nodes, None, None
         s.points = None if points is None else points.detach().to(idx.device, torch.float32).contiguous()
         s._idx, s._coef = idx, coef.detach()
         s.distance = None if distance is None else distance.detach().to(idx.device, torch.float32)

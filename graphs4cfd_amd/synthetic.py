@@ -96,16 +96,142 @@ def _knn_out(out: Optional[torch.Tensor], rows: int, k: int, dev, who: str) -> t
     return out
 
 
-def knn_neighbours_device(pos: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def check_period(period, dim: int, who: str = "period"):
+    """`period` of the periodic searches -> None (no periodic axis: today's call) or a list of `dim` entries, each None, "auto" or a
+    finite float > 0; ValueError naming `period`.  Nothing is read from a device."""
+    if period is None:
+        return None
+    try:
+        per = list(period)
+    except TypeError:
+        raise ValueError(f"period: {who}: expected {dim} entries (None, a length > 0 or \"auto\"), got {period!r}") from None
+    if len(per) != dim:
+        raise ValueError(f"period: {who}: expected {dim} entries, one per axis (None, a length > 0 or \"auto\"), got {period!r}")
+    out = []
+    for ax, d in enumerate(per):
+        if d is None or (isinstance(d, str) and d == "auto"):
+            out.append(d)
+            continue
+        if isinstance(d, (bool, str)) or not isinstance(d, (int, float, np.floating, np.integer)) or not (np.isfinite(d) and d > 0):
+            raise ValueError(f"period: {who}: axis {ax}: expected None, \"auto\" or a finite length > 0, got {d!r}")
+        out.append(float(d))
+    return None if all(d is None for d in out) else out
+
+
+def period_lengths(per: list, lo: torch.Tensor, hi: torch.Tensor, who: str = "period") -> List[float]:
+    """The fp32 period per axis (0.0: not periodic) of a cloud with fp32 corners lo / hi (host tensors): "auto" is the extent
+    hi − lo as an fp32, rounded up; a given length is rounded to fp32 and must be at least the extent (ValueError naming `period`)."""
+    lengths = []
+    for ax, d in enumerate(per):
+        if d is None:
+            lengths.append(0.0)
+            continue
+        ext = np.float32(float(hi[ax]) - float(lo[ax]))
+        if float(ext) < float(hi[ax]) - float(lo[ax]):          # (the extent of the fp32 cloud as an fp32, rounded up: never shorter)
+            ext = np.nextafter(ext, np.float32(np.inf))
+        L = ext if isinstance(d, str) else np.float32(d)
+        if not (np.isfinite(L) and L > 0):
+            raise ValueError(f"period: {who}: axis {ax}: a period of {float(L)} (\"auto\" needs an extent along the axis)")
+        if float(L) < float(hi[ax]) - float(lo[ax]):
+            raise ValueError(f"period: {who}: axis {ax}: the period {float(L)} is shorter than the cloud's extent "
+                             f"{float(hi[ax]) - float(lo[ax])}")
+        lengths.append(float(L))
+    return lengths
+
+
+def periodic_frame(pos: torch.Tensor, per: list, who: str = "period") -> Tuple[List[float], List[float]]:
+    """(origin, lengths) of the periodic frame of a cloud [n, dim]: the minimum of its fp32 rounding per axis, and `period_lengths`
+    (fp32 values, 0.0 for an axis that is not periodic).  `per`: `check_period`'s list.  One copy of the corners to the host."""
+    if int(pos.size(0)) < 1:
+        raise ValueError(f"period: {who}: an empty point cloud has no extent")
+    p32 = pos.detach().float()
+    lo, hi = p32.min(0)[0].cpu(), p32.max(0)[0].cpu()
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(hi).all())):
+        raise ValueError(f"{who}: non-finite coordinate in the point cloud")
+    return [float(v) for v in lo], period_lengths(per, lo, hi, who)
+
+
+MAX_PERIODIC_CELLS = 2 ** 26          # cells of a periodic search grid (its offsets: 256 MiB; the library itself takes < 2^31)
+
+
+def _periodic_grid_shape(lo: torch.Tensor, hi: torch.Tensor, n: int, k: int, lengths: Sequence[float], who: str):
+    """(cell size per axis in fp64, cells per axis, both padded to 3) of the periodic search grid: `_grid_shape`'s h; a periodic
+    axis is tiled exactly, nc = max(1, floor(L / h)) cells of L / nc; another axis keeps h and `_grid_shape`'s count."""
+    h, n_cells = _grid_shape(lo, hi, n, k, who)
+    dim = int(lo.numel())
+    cells, counts = [1.0] * 3, [1] * 3
+    for ax in range(dim):
+        L = lengths[ax]
+        if L > 0.0:
+            counts[ax] = max(1, int(np.floor(L / h)))
+            cells[ax] = L / counts[ax]
+        else:
+            counts[ax], cells[ax] = n_cells[ax], float(h)
+    # (before anything of that size is allocated: a period far above the extent multiplies the cells, which are sized by the cloud)
+    if counts[0] * counts[1] * counts[2] > MAX_PERIODIC_CELLS:
+        raise ValueError(f"period: {who}: the periods {list(lengths)} over cells of {h:g} give {counts[0]} x {counts[1]} x {counts[2]} cells, "
+                         f"more than {MAX_PERIODIC_CELLS}: a period so far above the cloud's extent is not searched")
+    return cells, counts
+
+
+def _bin_cloud_periodic(pos: torch.Tensor, k: int, per: list, who: str = "g4c_knn_grid_periodic") -> dict:
+    """`_bin_cloud` for the periodic searches (`g4c_knn_grid[_query]_periodic`, `g4c_tracer_advance_periodic`): the origin is the
+    fp32 cloud's minimum, a periodic axis is tiled exactly from it, the points are stable-sorted by their cell (the device's formula:
+    floor((x − origin) / cell) in fp64, clamped).  `per`: `check_period`'s list.  "periods": fp32 lengths, 0.0 a non-periodic axis."""
+    import ctypes as C
+    from . import _lib
+    dev = _lib.require_hip(pos)
+    if pos.dim() != 2 or int(pos.size(1)) not in (2, 3):
+        raise ValueError(f"{who}: points of shape {tuple(pos.shape)}, must be [n, 2] or [n, 3]")
+    n, dim = int(pos.size(0)), int(pos.size(1))
+    if n < 1:
+        raise ValueError(f"{who}: n=0, an empty point cloud")
+    p32 = pos.detach().float().contiguous()
+    lo, hi = p32.min(0)[0].cpu(), p32.max(0)[0].cpu()
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(hi).all())):
+        raise ValueError(f"{who}: non-finite coordinate in the point cloud")
+    lengths = period_lengths(per, lo, hi, who)
+    cells, n_cells = _periodic_grid_shape(lo, hi, n, k, lengths, who)
+    org = [float(v) for v in lo] + [0.0] * (3 - dim)
+    lengths3 = lengths + [0.0] * (3 - dim)
+    grid = dict(dev=dev, n=n, dim=dim, n_cells=n_cells, cells=cells, periods=lengths3, origin=org, org=(C.c_float * 3)(*org),
+                h=float(min(cells[:dim])),          # (`_bin_cloud`'s keys, for the callers that read them; the periodic entries take `cells`)
+                c_grid=_lib.g4c_periodic_grid_t(n_cells=(C.c_int32 * 3)(*n_cells), origin=(C.c_float * 3)(*org),
+                                                period=(C.c_float * 3)(*lengths3), cell=(C.c_double * 3)(*cells)))
+    coord = ((p32.double() - lo.double().to(dev)) / torch.tensor(cells[:dim], dtype=torch.float64, device=dev)).floor().long()
+    stride = [1, n_cells[0], n_cells[0] * n_cells[1]]
+    cell = torch.zeros(n, dtype=torch.long, device=dev)
+    for ax in range(dim):
+        cell += coord[:, ax].clamp_(0, n_cells[ax] - 1) * stride[ax]
+    cell_sorted, order = torch.sort(cell, stable=True)
+    total = n_cells[0] * n_cells[1] * n_cells[2]
+    grid.update(order=order.int(), pos_sorted=p32[order].contiguous(),
+                cell_start=torch.searchsorted(cell_sorted, torch.arange(total + 1, device=dev)).int())
+    return grid
+
+
+def knn_neighbours_device(pos: torch.Tensor, k: int, out: Optional[torch.Tensor] = None, period=None) -> torch.Tensor:
     """[n, k] int64 indices of the k nearest OTHER points of every point of `pos` (a device tensor), nearest first:
     the k-d-tree query of `connect_knn` as an exact cell-grid search on the GPU (`g4c_knn_grid`, csrc/knn_grid.hip).
     The cloud searched is the float32 rounding of `pos`; distances are float64 sums over those coordinates.  The rows are
     the host path's (`knn_neighbours` on the same float32 cloud) whenever no two candidate distances of a centre are
     exactly equal; among equal distances both are correct k-nearest sets, and the order among them and which are kept at
-    the k-th distance follow the cell-sorted order here, the k-d tree's on the host.  `out`: written in place if given."""
+    the k-th distance follow the cell-sorted order here, the k-d tree's on the host.  `out`: written in place if given.
+
+    `period` (one entry per axis: None, a length >= the cloud's extent, or "auto", the extent): the search runs in the wrapped
+    metric (`g4c_knn_grid_periodic`, csrc/knn_periodic.hip; include/g4c.h has the metric) — along a periodic axis the offset to a
+    neighbour is wrapped by `connect_knn`'s rule, the origin is the cloud's minimum.  All None: today's call, bit for bit."""
     import ctypes as C
     from . import _lib
+    per = check_period(period, int(pos.size(1)) if pos.dim() == 2 else 0, "knn_neighbours_device") if period is not None else None
     lib = _lib.load()
+    if per is not None:
+        who = "knn_neighbours_device (g4c_knn_grid_periodic)"
+        g = _bin_cloud_periodic(pos, k, per, who)
+        out = _knn_out(out, g["n"], k, g["dev"], who)
+        _lib.check(lib.g4c_knn_grid_periodic(_lib.ptr(g["pos_sorted"]), _lib.ptr(g["order"]), _lib.ptr(g["cell_start"]), g["n"], g["dim"],
+                                             C.byref(g["c_grid"]), k, _lib.ptr(out), _lib.stream_handle(g["dev"])))
+        return out
     g = _bin_cloud(pos, k, "knn_neighbours_device (g4c_knn_grid)")
     out = _knn_out(out, g["n"], k, g["dev"], "knn_neighbours_device (g4c_knn_grid)")
     _lib.check(lib.g4c_knn_grid(_lib.ptr(g["pos_sorted"]), _lib.ptr(g["cell_sorted"]), _lib.ptr(g["order"]),
@@ -114,17 +240,34 @@ def knn_neighbours_device(pos: torch.Tensor, k: int, out: Optional[torch.Tensor]
     return out
 
 
-def knn_query_device(points: torch.Tensor, queries: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def knn_query_device(points: torch.Tensor, queries: torch.Tensor, k: int, out: Optional[torch.Tensor] = None, period=None) -> torch.Tensor:
     """[len(queries), k] int64 indices of the k nearest `points` of every query (device tensors), nearest first
     (`g4c_knn_grid_query`): `knn_neighbours` on the GPU, over the float32 roundings of both clouds, with the tie rule of
     `knn_neighbours_device`.  Queries may lie anywhere, outside the cloud's box included; only the cloud's corners are
-    tested for finiteness (the queries' are never brought to the host: finite queries are the caller's to provide).  `out`: written in place if given."""
+    tested for finiteness (the queries' are never brought to the host: finite queries are the caller's to provide).  `out`: written in place if given.
+
+    `period`: as `knn_neighbours_device` (`g4c_knn_grid_query_periodic`); the periods and the origin are the CLOUD's.  A query may lie
+    periods away: it is wrapped into the period on the device, by the fp32 sequence of include/g4c.h — exactly, as far as fp32 resolves
+    (query − origin) / period (about 2^24 periods); farther off the wrapped value is finite but no longer the query's image, and a
+    coordinate that is not finite, or whose wrap overflows, is searched from the origin."""
     import ctypes as C
     from . import _lib
     lib = _lib.load()
     who = "knn_query_device (g4c_knn_grid_query)"
     if points.dim() != 2 or queries.dim() != 2 or int(queries.size(1)) != int(points.size(1)):
         raise ValueError(f"{who}: points {tuple(points.shape)} and queries {tuple(queries.shape)} must be [n, dim] and [m, dim]")
+    per = check_period(period, int(points.size(1)), "knn_query_device") if period is not None else None
+    if per is not None:
+        who = "knn_query_device (g4c_knn_grid_query_periodic)"
+        g = _bin_cloud_periodic(points, k, per, who)
+        q32 = queries.detach().float().contiguous()
+        _lib.require_hip(g["pos_sorted"], q32)
+        m = int(q32.size(0))
+        out = _knn_out(out, m, k, g["dev"], who)
+        _lib.check(lib.g4c_knn_grid_query_periodic(_lib.ptr(g["pos_sorted"]), _lib.ptr(g["order"]), _lib.ptr(g["cell_start"]), g["n"],
+                                                   g["dim"], C.byref(g["c_grid"]), _lib.ptr(q32), m, k, _lib.ptr(out),
+                                                   _lib.stream_handle(g["dev"])))
+        return out
     g = _bin_cloud(points, k, who)
     q32 = queries.detach().float().contiguous()
     _lib.require_hip(g["pos_sorted"], q32)

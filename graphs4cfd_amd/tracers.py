@@ -7,8 +7,9 @@ cell-grid search of `knn_query_device`, the coefficients of `gfd.PointSampler`'s
 velocity as their fp32 sum nearest first, v = scale u + shift, and q += dt v (Euler) or Heun's predictor–corrector, whose second
 stage reads the NEXT time level at the predicted position.  A particle is `waiting` (0) before its release step, `moving` (1), and
 frozen once it `left` the box (2), got `far`ther than max_distance from every node (3 — the search knows no boundary: this is how a
-particle that enters a body or leaves the mesh is stopped) or its position is no longer finite (4); `stopped` holds the step.  The
-search is not periodic and walls do not reflect."""
+particle that enters a body or leaves the mesh is stopped) or its position is no longer finite (4); `stopped` holds the step.
+With `period=` the domain is periodic along the named axes (`g4c_tracer_advance_periodic`): a particle that crosses a periodic face
+comes back in through the opposite one and stays moving.  Walls do not reflect."""
 from __future__ import annotations
 
 import math
@@ -38,7 +39,7 @@ def _numbers(name: str, v, dim: int, *, infinite: bool = False):
 
 
 def check_tracers(graph, seeds, dt, scheme="heun", k=None, power=2, velocity=None, scale=None, shift=None, box=None, max_distance=None,
-                  release=None, nf: Optional[int] = None) -> dict:
+                  release=None, nf: Optional[int] = None, period=None) -> dict:
     """The arguments of `Tracers` on the tensors as they were passed (nothing is moved, the library is not touched) -> what the launch
     needs, as a dict; ValueError / TypeError naming the argument.  `nf`: the columns the velocity is taken from, when known."""
     try:
@@ -46,6 +47,8 @@ def check_tracers(graph, seeds, dt, scheme="heun", k=None, power=2, velocity=Non
     except ValueError as e:
         msg = str(e)
         raise ValueError("seeds:" + msg[len("points:"):] if msg.startswith("points:") else msg) from None
+    from .synthetic import check_period
+    period = check_period(period, dim, "Tracers")
     n = int(seeds.size(0))
     if isinstance(dt, bool) or not isinstance(dt, (int, float)):
         raise TypeError(f"dt: expected a number (the time between two predictions), got {dt!r}")
@@ -99,7 +102,7 @@ def check_tracers(graph, seeds, dt, scheme="heun", k=None, power=2, velocity=Non
         release = release.detach().to(torch.int32)
     return dict(dim=dim, k=k, power=power, dt=float(dt), scheme=SCHEMES[scheme], scheme_name=scheme, velocity=velocity, scale=scale, shift=shift,
                 box_lo=lo, box_hi=hi, max_distance=float(max_distance), seeds=seeds.detach().to(torch.float32), release=release,
-                n_nodes=int(graph.pos.size(0)), groups=None)
+                n_nodes=int(graph.pos.size(0)), groups=None, period=period)
 
 
 class TracerState:
@@ -107,10 +110,13 @@ class TracerState:
     positions `q` [P, dim], `status`, `stopped`, `vel`, and — with every > 0 — the `series` of max_steps // every slots."""
 
     def __init__(self, spec: dict, pos: torch.Tensor, every: int = 0, max_steps: int = 0):
-        from .synthetic import _bin_cloud
+        from .synthetic import _bin_cloud, _bin_cloud_periodic
         dev = pos.device
         self.spec, self.every, self.max_steps = spec, int(every), int(max_steps)
-        self.grid = _bin_cloud(pos, spec["k"], "Tracers (g4c_tracer_advance)")
+        if spec.get("period") is None:
+            self.grid = _bin_cloud(pos, spec["k"], "Tracers (g4c_tracer_advance)")
+        else:          # (the periodic grid: `ops.tracer_advance` takes the periodic launch with it)
+            self.grid = _bin_cloud_periodic(pos, spec["k"], spec["period"], "Tracers (g4c_tracer_advance_periodic)")
         self.seeds, self.release = spec["seeds"].to(dev).contiguous(), spec["release"].to(dev).contiguous()
         n, dim = int(self.seeds.size(0)), spec["dim"]
         self.q = self.seeds.clone()
@@ -159,6 +165,11 @@ class Tracers:
     box        (lo, hi): a particle that leaves it is frozen where it left (status 2; corners may be infinite);
     max_distance  a particle farther than this from every node is frozen (status 3): inside a body, outside the mesh.
     release    int [S]: the first step each particle moves at (default 0).
+    period     one entry per axis — None, a length >= the mesh's extent, or "auto", the extent (as `connect_knn`'s): along such an
+               axis every stage searches and fits in the wrapped metric, and the new position is wrapped into [origin, origin +
+               length), origin the mesh's minimum, before it is stored, tested against `box` and recorded.  A particle that crosses
+               a periodic face stays moving.  Recorded `paths` therefore hold WRAPPED positions: a jump of more than half a period
+               between two slots is a crossing (no winding count is kept).
 
     Give `box` or `max_distance` whenever particles can leave the mesh: the search is exact, and for a particle D away from the cloud it
     grows ring by ring to D / cell size rings, scanning every block on the way — the whole grid at every stage of every step until the
@@ -171,8 +182,8 @@ class Tracers:
 
     def __init__(self, graph, seeds: torch.Tensor, dt: float, *, scheme: str = "heun", k: Optional[int] = None, power: int = 2,
                  velocity: Optional[Sequence[int]] = None, scale=None, shift=None, box=None, max_distance: Optional[float] = None,
-                 release=None):
-        self._spec = check_tracers(graph, seeds, dt, scheme, k, power, velocity, scale, shift, box, max_distance, release)
+                 release=None, period=None):
+        self._spec = check_tracers(graph, seeds, dt, scheme, k, power, velocity, scale, shift, box, max_distance, release, period=period)
         pos = graph.pos
         if pos.device.type != "cuda":
             raise ValueError(f"graph: Tracers run on a HIP device only, graph.pos is on '{pos.device}' (there is no CPU fallback)")

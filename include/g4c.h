@@ -454,6 +454,43 @@ int g4c_knn_grid_query(const float *pos_sorted, const int32_t *order, const int3
                        const int32_t *n_cells, const float *origin, float cell_size, const float *q_pos,
                        const int32_t *q_cell, int64_t m, int32_t k, int64_t *out, void *stream);
 
+/* The same two searches in the WRAPPED metric of a domain that is periodic along some axes (csrc/knn_periodic.hip; the search under
+ * the periodic sampler, jet and tracers).  This is the library's own metric, not the chord embedding connect_knn ranks by.
+ *
+ * Axis a is periodic when period[a] > 0 (0: not periodic).  With o = origin[a] (the cloud's minimum) and L = period[a] >= the cloud's
+ * extent, every cloud coordinate lies in [o, o + L].  All of the following is fixed, so that a numpy loop repeats it bit for bit:
+ *   wrap      a QUERY coordinate q (a particle's; never a cloud point's) is first brought into [o, o + L) in fp32, every operation
+ *             rounded once and nothing contracted:  f = floorf((q − o) / L);  w = q − (f · L);  if (w < o) w = w + L;
+ *             if (w >= o + L) w = w − L   (o + L rounded to fp32).  A self search takes the cloud's points as they are.
+ *             The result is ALWAYS finite: where the sequence gives no finite number (q not finite, or q − o, (q − o) / L or f · L
+ *             overflows — with L < 1 a finite |q − o| above FLT_MAX · L does) w = o.  A search from a wrapped coordinate therefore
+ *             has finite distances to every point and returns k indices whenever n >= k: no row holds −1 because of a periodic
+ *             axis.  The wrap is exact to the fp32 resolution of (q − o) / L: beyond |q − o| ~ 2^24 L the rounded product is whole
+ *             periods off and w, though finite, lies outside [o, o + L) — the neighbours are then those of that w.
+ *   offset    from q to p, both widened to fp64: t = p − q, then t − L if t > L / 2, t + L if t < −L / 2 (strict; connect_knn's rule),
+ *             applied once.  A non-periodic axis: t = p − q.
+ *   distance  the fp64 sum over the axes of t², as g4c_knn_grid forms it.
+ * Images of two points that coincide are duplicates, as duplicated points are in g4c_knn_grid.
+ *
+ * The grid: a periodic axis is tiled exactly, n_cells[a] cells of cell[a] = L / n_cells[a] (fp64); a non-periodic axis has cells of
+ * the caller's size from origin[a], as g4c_knn_grid's.  The cell of a coordinate x is floor((x − origin[a]) / cell[a]) in fp64, clamped
+ * to 0 .. n_cells[a] − 1; the caller sorts the cloud by it (cell id = x + n_cells[0]*(y + n_cells[1]*z)); the queries' cells are formed
+ * on the device, after the wrap.  Ring R scans the min(2R + 1, n_cells[a]) distinct cells c − R .. c + R modulo n_cells[a] of a periodic
+ * axis, and the search ends when the k-th distance is inside the nearest face of the block that has cells behind it (both faces of a
+ * periodic axis until 2R + 1 >= n_cells[a]) or the block is the whole grid.  Exact; ties follow the scan order.
+ * pos_sorted, order, cell_start, out: as g4c_knn_grid[_query].  Limits: dim 2 or 3, k <= 16, n < 2^31; self n > k, query n >= k. */
+typedef struct g4c_periodic_grid {
+    int32_t n_cells[3];          /* unused axes: 1 */
+    float origin[3];             /* the cloud's minimum along each axis */
+    float period[3];             /* L per axis; 0: the axis is not periodic */
+    double cell[3];              /* the cell size per axis */
+} g4c_periodic_grid_t;
+int g4c_knn_grid_periodic(const float *pos_sorted, const int32_t *order, const int32_t *cell_start, int64_t n, int32_t dim,
+                          const g4c_periodic_grid_t *grid /*host*/, int32_t k, int64_t *out, void *stream);
+int g4c_knn_grid_query_periodic(const float *pos_sorted, const int32_t *order, const int32_t *cell_start, int64_t n, int32_t dim,
+                                const g4c_periodic_grid_t *grid /*host*/, const float *q_pos, int64_t m, int32_t k, int64_t *out,
+                                void *stream);
+
 /* ---------------------------------------------------------------- rollout (nn/model.py:303-327)
  * One step's bookkeeping without host involvement: t = *step;
  * outputs[:, nf*t : nf*(t+1)] = pred;  field = roll(field, -nf, dim=1); field[:, -nf:] = pred;
@@ -802,6 +839,14 @@ int g4c_body_forces_adjoint(const g4c_body_forces_adjoint_t *a /*host*/, int64_t
 int g4c_sample_weights(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
                        int64_t n_nodes, int64_t n_points, float *coef, float *distance, uint8_t *degenerate, void *stream);
 
+/* The same fit over wrapped offsets (the periodic searches above have the metric): origin and period are host arrays of 3, period[a]
+ * == 0 an axis that is not periodic.  The point is wrapped into the period first (the fp32 wrap sequence), then d_j = (double)pos[idx_j]
+ * − (double)q' with the offset rule applied per periodic axis; everything after d_j is g4c_sample_weights', statement for statement.
+ * distance is the wrapped distance to the nearest node.  With every period 0 the outputs are g4c_sample_weights' bits. */
+int g4c_sample_weights_periodic(const float *pos, const float *queries, const int32_t *idx, int32_t dim, int32_t power, int32_t k,
+                                int64_t n_nodes, int64_t n_points, const float *origin, const float *period, float *coef,
+                                float *distance, uint8_t *degenerate, void *stream);
+
 /* g4c_sample_points — cur[p, f] = Σ_j coef[j, p] · x[idx[j, p], f] for f < nf, fp32, j ascending, every product rounded before it is
  * added (the first product starts the sum): one thread per (point, chunk of 4 columns), so the bits are a function of the data alone
  * and a numpy.float32 loop reproduces them.  The same launch serves nf = 3 inside a step (AFTER the forward, BEFORE the step's closing
@@ -899,6 +944,26 @@ typedef struct g4c_tracer {
     float *vel;                  /* [n_particles, dim] the first stage's physical velocity, or NULL */
 } g4c_tracer_t;
 int g4c_tracer_advance(const g4c_tracer_t *tr /*host*/, int64_t n_nodes, int64_t n_particles, void *stream);
+
+/* The same step in a domain that is periodic along some axes: g4c_tracer_t as it is, and after it the periods and the per-axis cell
+ * sizes of the periodic grid (g4c_periodic_grid_t: base.n_cells and base.origin are that grid's, base.cell_size is not read).
+ * Differences from the seven points above:
+ *   3. a stage first wraps a COPY of its position r (the wrap sequence above, per periodic axis), forms its cell from the wrapped
+ *      copy, searches by g4c_knn_grid_query_periodic's ring search and fits g4c_sample_weights_periodic's coefficients;
+ *   5. the updates add to the STORED position q (itself wrapped by the step before: a first position is taken as given);
+ *   6. q' is wrapped (the same sequence) BEFORE it is stored, tested against the box and written to the series: a particle that
+ *      crosses a periodic face stays moving, and the series holds wrapped positions — a jump of more than L / 2 between two slots
+ *      is a crossing.
+ *   2'. A position "does not wrap" when the wrap sequence reaches no finite number by itself (above).  It is treated as a position
+ *      that is not finite, wherever a position is tested: q[p] before the first stage, Heun's q* before the second, and q' before it
+ *      is stored — status 4, stopped[p] = t, q unchanged.  No stage ever starts from the origin standing in for such a position.
+ * Everything else, the errors included, is g4c_tracer_advance's; a period must be finite and >= 0, a cell size finite and > 0. */
+typedef struct g4c_tracer_periodic {
+    g4c_tracer_t base;
+    float period[3];             /* L per axis; 0: the axis is not periodic */
+    double cell[3];              /* the cell size per axis */
+} g4c_tracer_periodic_t;
+int g4c_tracer_advance_periodic(const g4c_tracer_periodic_t *tr /*host*/, int64_t n_nodes, int64_t n_particles, void *stream);
 
 /* g4c_snapshot_mean / _gram / _combine (csrc/snapshot_modes.hip) — the three launches of POD and DMD by the method of snapshots that
  * touch L-sized data (graphs4cfd_amd/modes.py holds the M-sized algebra; the reference has no counterpart).  They run AFTER a
