@@ -1,7 +1,7 @@
 """Drop-in use of the MI355X path with the reference's API: build a mesh with `gfd.transforms`, create (or load) a MuS-GNN,
 roll it out with `solve`.  With a trained checkpoint of the reference: `gfd.nn.NsThreeScaleGNN(checkpoint="NsThreeScaleGNN.chk")`.
 
-    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy] [--streak streak.npy] [--body 64]
+    python examples/rollout_mus_gnn.py [--nodes 20000] [--steps 50] [--checkpoint file.chk] [--raster vorticity.npy] [--streak streak.npy] [--body 64] [--integrals]
 """
 import argparse, os, sys, time
 import torch
@@ -14,6 +14,7 @@ ap.add_argument("--checkpoint", default=None)
 ap.add_argument("--raster", default=None, help="write the vorticity of the last step on a 256 x 256 raster to this .npy file")
 ap.add_argument("--streak", default=None, help="write the streaklines of five seeds after the last step to this .npy file")
 ap.add_argument("--body", type=int, default=0, help="mark the W nodes nearest to a circle as a wall (bound == 4) and print its force coefficients")
+ap.add_argument("--integrals", action="store_true", help="print the kinetic-energy drift and the relative L2 error, weighted by the nodes' Voronoi areas")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -64,6 +65,13 @@ if getattr(graph, "bound", None) is not None and bool((graph.bound == 4).any()):
     fo = model.forces(graph, a.steps, mu=rho * nu, discard=a.steps // 4, spectrum=gfd.Spectrum(bins=range(a.steps // 2 + 1)))
     cd, cl, _ = fo.coefficients(rho, U, D)
     print(f"mean Cd {float(cd[a.steps // 4:, 0].mean()):.4f}, r.m.s. Cl {float(cl[a.steps // 4:, 0].std(unbiased=False)):.4f}, St {fo.strouhal(D, U):.4f} (dt = 1)")
+if a.integrals:                                             # integrals over the domain, not means over node rows: every node weighs its Voronoi cell
+    cells = gfd.ControlVolumes(graph.to(dev), bodies=True if a.body else None)      # built once per mesh; a wall node's cell ends at the wall's tangent
+    ig = model.integrals(graph, a.steps, ("volume", "ke", "enstrophy", "div2"), cells)
+    print(f"domain area {ig.volume:.4f} over {int((~cells.degenerate).sum())} cells; kinetic-energy drift over {a.steps} steps "
+          f"{float(ig.drift('ke')[-1]):+.3e}, enstrophy {float(ig['enstrophy'][-1]):.3e}, ||div||_L2 {float(ig['div2'][-1]) ** 0.5:.3e}")
+    graph.target = out                                      # (stands in for the ground truth a dataset carries: the error is then 0)
+    print("relative L2 error per step:", " ".join(f"{v:.3e}" for v in model.integrals(graph, a.steps, ("rel_l2",), cells)["rel_l2"].tolist()))
 if a.raster:                                                # the picture of a field: sampled on the device inside the step, no plotting dependency
     import numpy as np
     raster = gfd.PointSampler.grid(graph, (256, 256))          # the mesh's bounding box; .distance masks points far from every node

@@ -17,6 +17,7 @@ from .loader import DataLoader, Collater
 from .mesh_jet import MeshJet                          # quadratic least-squares fit: first and second derivatives, own kNN stencil
 from .mesh_gradient import MeshGradient                # least-squares gradient over the mesh's edges: divergence, vorticity, gradients
 from .body_forces import BodyForces                    # drag, lift and wall loads of a 2-D flow on the bodies it passes, from the wall nodes
+from .control_volumes import ControlVolumes            # Voronoi areas of the nodes of a 2-D cloud, wall-clipped: what turns node sums into integrals
 from .point_sampler import PointSampler                # node fields at points, rakes and rasters: a linear moving-least-squares fit over the k nearest nodes
 from .tracers import Tracers                           # Lagrangian tracers: pathlines and streaklines through the velocity at the nodes
 from .ops import check_f16_range, f16_range_report     # clipped values of the default arithmetic are reported, never silent (ops.py)

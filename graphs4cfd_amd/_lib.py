@@ -172,6 +172,29 @@ class g4c_tracer_periodic_t(C.Structure):
     _fields_ = [("base", g4c_tracer_t), ("period", C.c_float * 3), ("cell", C.c_double * 3)]
 
 
+# g4c_voronoi_cells / g4c_weighted_integrals (csrc/control_volumes.hip)
+VORONOI_MAX_VERTS = 32                             # G4C_VORONOI_MAX_VERTS
+VORONOI_BOX, VORONOI_WALL, VORONOI_DUPLICATE, VORONOI_OVERFLOW = 1, 2, 4, 8     # G4C_VORONOI_*: bits of `flags`
+INTEGRALS_MAX_ENTRIES = 8                          # G4C_INTEGRALS_MAX_ENTRIES
+
+
+class g4c_voronoi_cells_t(C.Structure):
+    _fields_ = [("pos_sorted", C.c_void_p), ("order", C.c_void_p), ("cell_start", C.c_void_p), ("n_cells", C.c_int32 * 3),
+                ("origin", C.c_float * 3), ("cell_size", C.c_float), ("box_lo", C.c_double * 2), ("box_hi", C.c_double * 2),
+                ("normals", C.c_void_p), ("area", C.c_void_p), ("centroid", C.c_void_p), ("nvert", C.c_void_p), ("flags", C.c_void_p),
+                ("rings", C.c_void_p)]
+
+
+class g4c_integral_program_t(C.Structure):
+    _fields_ = [("ne", C.c_int32), ("a", C.c_int32 * INTEGRALS_MAX_ENTRIES), ("b", C.c_int32 * INTEGRALS_MAX_ENTRIES)]
+
+
+class g4c_weighted_integrals_t(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_ld", C.c_int32), ("x_step", C.c_int32), ("sub", C.c_void_p), ("sub_ld", C.c_int32),
+                ("sub_step", C.c_int32), ("nz", C.c_int32), ("w", C.c_void_p), ("step", C.c_void_p), ("t_host", C.c_int32),
+                ("max_steps", C.c_int32), ("stats", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 # g4c_snapshot_* (csrc/snapshot_modes.hip): the envelope and the tile sizes the tests walk
 SNAPSHOT_MAX_ROWS = 1024                           # G4C_SNAPSHOT_MAX_ROWS: Ma, Mb, R
 SNAPSHOT_MAX_COLUMNS = 2 ** 31 - 1                 # G4C_SNAPSHOT_MAX_COLUMNS: L
@@ -252,6 +275,9 @@ _SIGNATURES = {
                                             C.c_void_p]),
     "g4c_tracer_advance": (C.c_int, [C.POINTER(g4c_tracer_t), C.c_int64, C.c_int64, C.c_void_p]),
     "g4c_tracer_advance_periodic": (C.c_int, [C.POINTER(g4c_tracer_periodic_t), C.c_int64, C.c_int64, C.c_void_p]),
+    "g4c_voronoi_cells": (C.c_int, [C.POINTER(g4c_voronoi_cells_t), C.c_int64, C.c_void_p]),
+    "g4c_weighted_integrals_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
+    "g4c_weighted_integrals": (C.c_int, [C.POINTER(g4c_weighted_integrals_t), C.POINTER(g4c_integral_program_t), C.c_int64, C.c_void_p]),
     "g4c_snapshot_mean": (C.c_int, [C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_snapshot_gram_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "g4c_snapshot_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t),

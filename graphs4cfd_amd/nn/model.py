@@ -23,8 +23,8 @@ from torch import nn
 from .. import _lib, ops
 from ..graph import Graph
 # the rollout and what rides along in its step live in rollout.py; every name stays importable from here
-from .rollout import (KEYWORDS, REORDER_MIN_NODES, Rollout, RolloutDerived, RolloutErrors, RolloutForces, RolloutMoments,      # noqa: F401
-                      RolloutSamples, RolloutSpectrum, Spectrum, _check_moments, _check_parts, _check_records, _check_spectrum)
+from .rollout import (KEYWORDS, REORDER_MIN_NODES, Rollout, RolloutDerived, RolloutErrors, RolloutForces, RolloutIntegrals,      # noqa: F401
+                      RolloutMoments, RolloutSamples, RolloutSpectrum, Spectrum, _check_moments, _check_parts, _check_records, _check_spectrum)
 
 
 def collate(graphs: List[Graph]) -> Graph:
@@ -223,6 +223,7 @@ class GNN(nn.Module):
         modes (a `gfd.Modes`; needs every >= 1: the kept snapshots are its data) attaches the modal analysis of the prediction and of
         the target's columns of the same steps (`.modes`: `.prediction`, `.target` — `SnapshotModes` — and `.alignment`, the principal
         cosines between the two mode subspaces), formed after the rollout: no launch inside the step.
+        (The errors weighted by the nodes' control volumes — 'rel_l2', the mesh-independent relative L2 error — are `integrals()`'s.)
         A list of graphs is collated as in `solve`."""
         records = {k: v for k, v in locals().items() if k in KEYWORDS}          # (the keywords this signature shares with `Rollout`)
         if modes is not None:
@@ -336,6 +337,29 @@ class GNN(nn.Module):
                            wall_moments=window if wall else None) as ro:
             ro.run(n_out)
             return ro.forces()
+
+    def integrals(self, graph: Union[Graph, List[Graph]], n_out: int, names=("volume", "ke"), volumes=None, velocity=(0, 1), *,
+                  capture: Optional[bool] = None, derived_options: Optional[dict] = None, **options) -> "RolloutIntegrals":
+        """Roll the model out for n_out steps and return the integrals of every predicted step over the domain (`RolloutIntegrals`:
+        `values` [steps, names], `drift(name)`), the node sums weighted by the nodes' control volumes — `volumes` a `gfd.ControlVolumes`
+        of this graph, or None: one is built here (2-D; options box, bodies) —, formed on the device inside the step in fp64 in a
+        fixed order.  names: 'volume', 'int:<f>', 'mean:<f>', 'ke' (½ ∫ |u|², `velocity` the fields of u and v), 'circulation' (∫ ω),
+        'enstrophy' (½ ∫ ω²), 'div2' (∫ div²); the derived columns the last three read ('vort', 'div') are added by themselves, formed
+        with `derived_options` (as in `diagnostics`).  'l2:<f>', 'l2' and 'rel_l2' — the errors against a target, 'rel_l2' =
+        √(Σ_f ∫ (prediction − target)² / Σ_f ∫ target²) the mesh-independent relative L2 error — roll out against `graph.target`
+        ([N, >= num_fields * n_out]), as `evaluate` does.  No prediction is held.  A list of graphs is collated as in `solve`: each
+        graph gets its own cells."""
+        assert n_out > 0, "n_out must be greater than 0."
+        wanted = ((names,) if isinstance(names, str) else names) if isinstance(names, (str, tuple, list)) else ()
+        need = [d for d, users in (("vort", ("circulation", "enstrophy")), ("div", ("div2",))) if any(u in wanted for u in users)]
+        against = any(isinstance(nm, str) and (nm in ("l2", "rel_l2") or nm.startswith("l2:")) for nm in wanted)
+        if against and not torch.is_tensor(getattr(graph[0] if type(graph) is list else graph, "target", None)):
+            raise ValueError("integrals: 'l2:<f>', 'l2' and 'rel_l2' are errors against the target: the graph has no `target`")
+        with self._rollout(graph, n_out, capture, "integrals()", evaluate=against, every=0, integrals=names, integral_volumes=volumes,
+                           integral_options=dict(options, velocity=velocity), derived=tuple(need) or None,
+                           derived_options=derived_options if need else None) as ro:
+            ro.run(n_out)
+            return ro.integrals()
 
     def time_statistics(self, graph: Union[Graph, List[Graph]], n_out: int, *, discard: int = 0, stride: int = 1, every: int = 0,
                         capture: Optional[bool] = None) -> "RolloutMoments":

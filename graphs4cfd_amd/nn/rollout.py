@@ -6,7 +6,7 @@ enqueues its launches of a step (`launch`), is told when steps are about to be t
 (`read`).  `_PARTS` lists them in launch order; `Rollout` loops over those asked for and never reaches inside one.  `_check_parts`
 turns the keywords into checked specs, once per call: `Rollout.__init__` calls it, and so does `GNN._rollout` before it collates or
 moves anything.  The result classes (`RolloutErrors`, `RolloutMoments`, `RolloutSpectrum`, `RolloutDerived`, `RolloutSamples`,
-`RolloutForces`) and the request `Spectrum` live here too; nn/model.py re-exports every name."""
+`RolloutForces`, `RolloutIntegrals`) and the request `Spectrum` live here too; nn/model.py re-exports every name."""
 from __future__ import annotations
 
 import functools
@@ -104,9 +104,35 @@ class Rollout:
         (pressure, wall shear) at every wall item, `force_spectrum` (a `gfd.Spectrum`) the Fourier modes of the total — the lift's
         dominant frequency is the shedding frequency —, by the kernels the nodes use.  `target_forces=True` (needs `target=`) adds one
         more launch per step on the target's columns.  `forces()` returns them (`RolloutForces`); steps run again after `rewind()` or
-        a recomputation overwrite their rows, the accumulators hold the steps taken since.  A list of graphs is refused."""
+        a recomputation overwrite their rows, the accumulators hold the steps taken since.  A list of graphs is refused.
+
+        Integrals over the domain (opt-in, no record either; 2-D; keywords of `Rollout.open`, which takes every keyword of this
+        signature and these three): `integrals` — a tuple of names: 'volume', 'int:<f>' (∫ field f),
+        'mean:<f>' (∫ f / volume), 'ke' (½ ∫ |u|²), 'circulation' (∫ ω), 'enstrophy' (½ ∫ ω²), 'div2' (∫ div²) and, with `target=`,
+        'l2:<f>' (√∫ (prediction − target)² of field f), 'l2' (over all fields) and 'rel_l2' (that over √∫ target²) — are the sums over the
+        nodes weighted by the nodes' control volumes: `integral_volumes`, a `gfd.ControlVolumes` of this graph (None: one is built here,
+        with `box` and `bodies` of `integral_options`), permuted into the rollout's numbering once.  'circulation' and 'enstrophy' read
+        the 'vort' column, 'div2' the 'div' column of `derived=`, which must name them.  One `g4c_weighted_integrals` launch (and its
+        one-workgroup sum) per source and step — the prediction, prediction − target, the target, the derived columns, as far as the
+        names need them — behind the derived columns' launches.  `integral_options`: velocity (the fields of u and v, default (0, 1)),
+        box, bodies.  `integrals()` returns them (`RolloutIntegrals`); steps run again after `rewind()` or a recomputation overwrite
+        their rows."""
         specs = _check_parts(locals(), graph, int(model.num_fields), int(max_steps), target is not None)
         self._build(specs, model, graph, max_steps, capture, reorder, label, every, probes, target, mask)
+
+    @classmethod
+    def open(cls, model: "GNN", graph: Graph, max_steps: int, *, capture: bool = True, reorder: Optional[bool] = None, label: str = "Rollout",
+             **keywords) -> "Rollout":
+        """`Rollout(model, graph, max_steps, ...)` with every record and part named by keyword: those of the constructor's signature and
+        the parts that came after it — `integrals=`, `integral_volumes=`, `integral_options=` (`KEYWORDS` lists them all).  The
+        constructor's own signature stays what its callers know."""
+        if set(keywords) - set(KEYWORDS):
+            raise TypeError(f"Rollout.open: unexpected keyword argument(s) {sorted(set(keywords) - set(KEYWORDS))}")
+        kw = {**KEYWORDS, **keywords}
+        specs = _check_parts(kw, graph, int(model.num_fields), int(max_steps), kw["target"] is not None)
+        ro = cls.__new__(cls)
+        ro._build(specs, model, graph, max_steps, capture, reorder, label, kw["every"], kw["probes"], kw["target"], kw["mask"])
+        return ro
 
     @classmethod
     def _checked(cls, specs: dict, model: "GNN", graph: Graph, max_steps: int, capture: bool, label: str, **keywords) -> "Rollout":
@@ -353,6 +379,11 @@ class Rollout:
         every body per step, their time statistics and Fourier modes, the wall's statistics) — validated first, like `result()`; one
         device -> host copy of [steps_done, B, 6] sums."""
         return self._read("forces")
+
+    def integrals(self) -> "RolloutIntegrals":
+        """What `integrals=` asked for, of the `steps_done` steps taken (`RolloutIntegrals`: the integrals over the domain per step,
+        weighted by the nodes' control volumes) — validated first, like `result()`; one device -> host copy of the sums."""
+        return self._read("integrals")
 
     def modes(self, spec) -> "SnapshotModes":
         """The modal analysis `spec` (a `gfd.Modes`) asks for of the snapshots kept so far (`SnapshotModes`; mean and modes in the
@@ -1224,6 +1255,214 @@ class RolloutForces:
                 f"wall_moments={self.wall_moments is not None}, spectrum={self.spectrum is not None}, target={self.target is not None})")
 
 
+class _Integrals(_Part):
+    """The integrals of a `Rollout` over the domain and the launches that form them: per source — the prediction, prediction − target,
+    the target, the derived columns — a program of up to 8 entries, the sums [max_steps, ne] and a scratch, and ONE copy of the control
+    volumes' areas in the rollout's node numbering (permuted here, once: a captured step allocates and permutes nothing)."""
+    name = "integrals"
+    SOURCES = ("prediction", "error", "target", "derived")
+
+    @staticmethod
+    def plan(names, nf: int, velocity=(0, 1), derived_columns=None, has_target: bool = True):
+        """names -> (per source its list of entries, per name its recipe (kind, [(source, entry index), ...])).  ValueError naming
+        `integrals` on an unknown name, a field out of range, a missing derived column or target, or more than 8 entries a source."""
+        names = (names,) if isinstance(names, str) else names
+        if not isinstance(names, (tuple, list)) or not len(names) or not all(isinstance(nm, str) for nm in names):
+            raise ValueError(f"integrals: expected a non-empty tuple of names ('volume', 'int:<f>', 'mean:<f>', 'ke', 'circulation', "
+                             f"'enstrophy', 'div2', 'l2:<f>', 'l2', 'rel_l2'), got {names!r}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"integrals: a name is repeated in {tuple(names)!r}")
+        try:
+            velocity = tuple(velocity)
+        except TypeError:
+            raise ValueError(f"integral_options: velocity: expected 2 field numbers, got {velocity!r}") from None
+        if len(velocity) != 2 or not all(_integer(v) and 0 <= v < nf for v in velocity):
+            raise ValueError(f"integral_options: velocity: expected 2 field numbers below {nf}, got {velocity!r}")
+        entries = {src: [] for src in _Integrals.SOURCES}
+
+        def slot(src, a, b=-1):
+            if (a, b) not in entries[src]:
+                entries[src].append((a, b))
+            return (src, entries[src].index((a, b)))
+
+        def field(nm):
+            tail = nm.split(":", 1)[1]
+            if not tail.isdigit() or int(tail) >= nf:
+                raise ValueError(f"integrals: {nm!r}: expected a field number below {nf} after the colon")
+            return int(tail)
+
+        def column(nm, label):
+            if derived_columns is None or label not in derived_columns:
+                raise ValueError(f"integrals: {nm!r} reads the {label!r} column of the derived fields: add {label!r} to derived=")
+            return derived_columns.index(label)
+
+        def target(nm):
+            if not has_target:
+                raise ValueError(f"integrals: {nm!r} is an error against the target: it needs target= (GNN.integrals reads graph.target)")
+
+        recipes = []
+        for nm in names:
+            if nm == "volume":
+                recipes.append(("sum", [slot("prediction", -1)]))
+            elif nm.startswith("int:"):
+                recipes.append(("sum", [slot("prediction", field(nm))]))
+            elif nm.startswith("mean:"):
+                recipes.append(("ratio", [slot("prediction", field(nm)), slot("prediction", -1)]))
+            elif nm == "ke":
+                recipes.append(("half", [slot("prediction", v, v) for v in velocity]))
+            elif nm == "circulation":
+                recipes.append(("sum", [slot("derived", column(nm, "vort"))]))
+            elif nm == "enstrophy":
+                c = column(nm, "vort")
+                recipes.append(("half", [slot("derived", c, c)]))
+            elif nm == "div2":
+                c = column(nm, "div")
+                recipes.append(("sum", [slot("derived", c, c)]))
+            elif nm.startswith("l2:"):
+                target(nm)
+                f = field(nm)
+                recipes.append(("root", [slot("error", f, f)]))
+            elif nm in ("l2", "rel_l2"):
+                target(nm)
+                num = [slot("error", f, f) for f in range(nf)]
+                den = [slot("target", f, f) for f in range(nf)]          # (`l2` keeps ∫ target² in `sums` too: the norm it is read against)
+                recipes.append(("root" if nm == "l2" else "rel", [num, den]))
+            else:
+                raise ValueError(f"integrals: unknown name {nm!r} ('volume', 'int:<f>', 'mean:<f>', 'ke', 'circulation', 'enstrophy', 'div2', "
+                                 f"'l2:<f>', 'l2' and 'rel_l2' are known)")
+        for src, e in entries.items():
+            if len(e) > _lib.INTEGRALS_MAX_ENTRIES:
+                raise ValueError(f"integrals: {tuple(names)!r} need {len(e)} sums over the {src}, at most {_lib.INTEGRALS_MAX_ENTRIES} fit one launch")
+        return entries, recipes
+
+    @staticmethod
+    def check(kw, ctx, specs):
+        """The `integrals=` / `integral_volumes=` / `integral_options=` arguments against the caller's graph -> names, entries, recipes,
+        volumes, options."""
+        from ..control_volumes import ControlVolumes, check_volumes
+        from ..mesh_gradient import derived_columns
+        names, volumes, options = kw["integrals"], kw["integral_volumes"], kw["integral_options"]
+        if names is None or names is False:
+            if volumes is not None or options:
+                raise ValueError("integrals: integral_volumes / integral_options were given without integrals=")
+            return None
+        options = dict(options or {})
+        unknown = set(options) - {"velocity", "box", "bodies"}
+        if unknown:
+            raise ValueError(f"integral_options: unknown option(s) {sorted(unknown)} (velocity, box, bodies)")
+        derived = specs.get("derived")
+        entries, recipes = _Integrals.plan(names, ctx.nf, options.get("velocity", (0, 1)),
+                                           None if derived is None else derived_columns(derived["names"], 2), ctx.has_target)
+        if volumes is not None:
+            if not isinstance(volumes, ControlVolumes):
+                raise TypeError(f"integral_volumes: expected a gfd.ControlVolumes of this graph or None, got {type(volumes).__name__}")
+            if ctx.in_list:
+                raise ValueError("integral_volumes: the volumes of a list of graphs: leave it None (each graph of the batch gets its own cells)")
+            if volumes.n_nodes != int(ctx.graph.num_nodes):
+                raise ValueError(f"integral_volumes: a ControlVolumes over {volumes.n_nodes} nodes for a graph of {int(ctx.graph.num_nodes)}")
+            if "box" in options or "bodies" in options:
+                raise ValueError("integral_options: box / bodies were given together with integral_volumes= (the volumes carry their own)")
+        else:
+            if ctx.in_list and options.get("bodies") is not None:
+                raise ValueError("integral_options: bodies of a list of graphs: build the gfd.ControlVolumes of the collated graph yourself")
+            for graph in ctx.graphs:
+                check_volumes(graph, options.get("box"), options.get("bodies"))
+        return dict(names=tuple((names,) if isinstance(names, str) else names), entries=entries, recipes=recipes, volumes=volumes,
+                    options=options)
+
+    def __init__(self, ro: "Rollout", spec: dict):
+        from ..control_volumes import ControlVolumes
+        dev, n, steps = ro.field.device, int(ro.graph.num_nodes), ro.max_steps
+        self.names, self.recipes, self.nf, self.max_steps = spec["names"], spec["recipes"], ro.nf, steps
+        volumes = spec["volumes"]
+        if volumes is None:          # (on the caller's graph: its numbering, its batch — each graph of a batch has its own cells)
+            volumes = ControlVolumes(ro._caller_graph, spec["options"].get("box"), spec["options"].get("bodies"))
+        self.volumes = volumes
+        w = volumes.area.to(dev)
+        self.w = (w[ro._perm.to(dev)] if ro._perm is not None else w).contiguous()
+        self.programs, self.sums, self.scratch = {}, {}, {}
+        for src, entries in spec["entries"].items():
+            if entries:
+                nz = ro._derived.nd if src == "derived" else ro.nf
+                self.programs[src] = ops.integral_program(entries, nz)
+                self.sums[src] = torch.zeros((steps, len(entries)), dtype=torch.float64, device=dev)
+                self.scratch[src] = ops.weighted_integrals_scratch(n, len(entries), dev)
+        self.target = ro._rec.target if ("error" in self.programs or "target" in self.programs) else None
+        self.cur = ro._derived.cur if "derived" in self.programs else None
+
+    def launch(self, ro: "Rollout", pred: torch.Tensor) -> None:
+        nf, step = self.nf, ro.step_counter
+        for src, prog in self.programs.items():
+            if src == "prediction":
+                ops.weighted_integrals(pred, self.w, prog, self.sums[src], self.scratch[src], nz=nf, step=step)
+            elif src == "error":
+                ops.weighted_integrals(pred, self.w, prog, self.sums[src], self.scratch[src], nz=nf, sub=self.target, sub_step=nf, step=step)
+            elif src == "target":
+                ops.weighted_integrals(self.target, self.w, prog, self.sums[src], self.scratch[src], nz=nf, x_step=nf, step=step)
+            else:
+                ops.weighted_integrals(self.cur, self.w, prog, self.sums[src], self.scratch[src], nz=int(self.cur.size(1)), step=step)
+
+    def read(self, ro: "Rollout") -> "RolloutIntegrals":
+        sums = {src: s[:ro.steps_done].cpu() for src, s in self.sums.items()}
+        return RolloutIntegrals(self.names, self.recipes, sums, float(self.volumes.total), {src: [(int(p.a[e]), int(p.b[e])) for e in range(int(p.ne))]
+                                                                                            for src, p in self.programs.items()})
+
+
+class RolloutIntegrals:
+    """Integrals of a rollout over the domain (`Rollout.integrals()`, `GNN.integrals()`, `GNN.evaluate(integrals=)`), per step taken,
+    fp64 host tensors: `values` [steps, names] in the order of `names`; `sums` — per source ('prediction', 'error' = prediction −
+    target, 'target', 'derived') the raw Σ_i area_i z_i[a] z_i[b] [steps, entries] the step formed on the device in fp64 in a fixed order,
+    `entries` their column pairs (−1: the constant 1); `volume`: Σ area of the control volumes.  'ke' and 'enstrophy' are half their
+    sums, 'mean:<f>' is ∫ f over the 'volume' sum of the same step, 'l2:<f>' and 'l2' the square roots, 'rel_l2' = √(Σ_f ∫ (p − t)² / Σ_f
+    ∫ t²).  `drift(name)` = value / first value − 1.  A NaN at a node of non-zero area makes the integrals that read its column NaN at
+    that step; a node of zero area contributes nothing whatever it holds."""
+
+    def __init__(self, names, recipes, sums: dict, volume: float, entries: dict):
+        self.names, self.sums, self.volume, self.entries = tuple(names), sums, float(volume), entries
+        self._recipes = recipes
+        steps = int(next(iter(sums.values())).size(0)) if sums else 0
+
+        def take(ref):
+            if isinstance(ref, list):
+                out = torch.zeros(steps, dtype=torch.float64)
+                for r in ref:          # (in the order of the fields)
+                    out = out + take(r)
+                return out
+            return sums[ref[0]][:, ref[1]]
+
+        cols = []
+        for kind, refs in recipes:
+            if kind == "sum":
+                cols.append(take(refs[0]))
+            elif kind == "half":
+                cols.append(0.5 * take(list(refs)))
+            elif kind == "ratio":
+                cols.append(take(refs[0]) / take(refs[1]))
+            elif kind == "root":
+                cols.append(take(refs[0]).sqrt())
+            else:
+                cols.append((take(refs[0]) / take(refs[1])).sqrt())
+        self.values = torch.stack(cols, dim=1) if cols else torch.zeros((steps, 0), dtype=torch.float64)
+
+    @property
+    def steps(self) -> int:
+        return int(self.values.size(0))
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        """[steps]: the values of one name."""
+        if name not in self.names:
+            raise KeyError(f"{name!r} is not among {self.names}")
+        return self.values[:, self.names.index(name)]
+
+    def drift(self, name: str) -> torch.Tensor:
+        """[steps]: value / first value − 1 (the kinetic energy's drift over the rollout)."""
+        v = self[name]
+        return v / v[0] - 1.0
+
+    def __repr__(self):
+        return f"RolloutIntegrals(names={self.names}, steps={self.steps}, volume={self.volume:.6g})"
+
+
 class _Records:
     """The record buffers of a `Rollout` and the launch that fills them.  Everything is allocated here, once, in the rollout's node
     numbering (probe rows, target rows and mask rows are mapped through the Morton permutation at construction), so a captured
@@ -1310,12 +1549,14 @@ class RolloutErrors:
 
 
 # The parts of a step, in the order `Rollout._one` launches them (the records' closing launch comes last, outside this list) ...
-_PARTS = (_Derived, _Samples, _Forces, _NodeMoments, _ErrorMoments, _NodeSpectrum, _TargetSpectrum, _DerivedSpectrum, _Tracers)
+_PARTS = (_Derived, _Integrals, _Samples, _Forces, _NodeMoments, _ErrorMoments, _NodeSpectrum, _TargetSpectrum, _DerivedSpectrum, _Tracers)
 # ... and in the order their keywords are checked: the precedence of the argument errors
-_CHECKED = (_Derived, _DerivedSpectrum, _NodeSpectrum, _TargetSpectrum, _Samples, _Tracers, _Forces, _NodeMoments, _ErrorMoments)
+_CHECKED = (_Derived, _DerivedSpectrum, _NodeSpectrum, _TargetSpectrum, _Samples, _Tracers, _Forces, _NodeMoments, _ErrorMoments, _Integrals)
 # every keyword of `Rollout` that asks for a record or a part, with its default: named once, in the signature of `Rollout.__init__`
 KEYWORDS = {name: p.default for name, p in inspect.signature(Rollout.__init__).parameters.items()
             if name not in ("self", "model", "graph", "max_steps", "capture", "reorder", "label")}
+# ... and those of the parts `Rollout.open` and `GNN._rollout` take beyond that signature
+KEYWORDS.update(integrals=None, integral_volumes=None, integral_options=None)
 
 
 def _check_parts(keywords: dict, graph, nf: int, max_steps: int, has_target: bool) -> dict:

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -1516,6 +1517,166 @@ def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, stat
         return q
     _lib.check(lib.g4c_tracer_advance(C.byref(tr), n_nodes, n_particles, _lib.stream_handle(dev)))
     return q
+
+
+def _box_arg(what: str, box):
+    """`box` -> (lo_x, lo_y, hi_x, hi_y) as floats: four finite numbers with lo < hi per axis."""
+    try:
+        vals = [float(c) for c in (box.reshape(-1).tolist() if torch.is_tensor(box) else box)]
+    except (TypeError, ValueError, AttributeError):
+        raise ValueError(f"box: {what}: expected (lo_x, lo_y, hi_x, hi_y), got {box!r}") from None
+    if len(vals) != 4 or not all(math.isfinite(v) for v in vals) or not (vals[0] < vals[2] and vals[1] < vals[3]):
+        raise ValueError(f"box: {what}: expected four finite numbers (lo_x, lo_y, hi_x, hi_y) with lo < hi, got {box!r}")
+    return vals
+
+
+def voronoi_cells(grid: dict, box, normals: Optional[Tensor] = None, out=None):
+    """g4c_voronoi_cells: per node of a 2-D cloud the polygon (its Voronoi cell) ∩ (`box` = (lo_x, lo_y, hi_x, hi_y)) ∩ (the half-plane
+    (x − pos_i)·normals[i] >= 0 where normals[i] != 0), once per mesh.  `grid`: the cloud's cell grid (`synthetic._bin_cloud` of the
+    node positions); normals float64 [N, 2] in the caller's node order or None.  Returns (area float64 [N], centroid float64 [N, 2],
+    nvert int32 [N], flags uint8 [N] — bits `_lib.VORONOI_BOX / _WALL / _DUPLICATE / _OVERFLOW` —, rings int32 [N]) in the caller's node
+    order; `out`: the five tensors to write into.  include/g4c.h has the construction; a cell of more than `_lib.VORONOI_MAX_VERTS`
+    vertices gets OVERFLOW and the area +0."""
+    what = "voronoi_cells"
+    for key in ("pos_sorted", "order", "cell_start", "n_cells", "org", "h", "dim", "n"):
+        if not isinstance(grid, dict) or key not in grid:
+            raise ValueError(f"grid: {what}: expected the cell grid of the node cloud (synthetic._bin_cloud), got {type(grid).__name__}"
+                             f"{'' if not isinstance(grid, dict) else f' without {key!r}'}")
+    if "periods" in grid:
+        raise ValueError(f"grid: {what}: a periodic grid (control volumes on periodic axes are out of scope)")
+    dim, n = int(grid["dim"]), int(grid["n"])
+    if dim != 2:
+        raise ValueError(f"grid: {what} is 2-D only, the cloud has {dim} dimensions (3-D cells are out of scope)")
+    _mesh_arg(what, grid["pos_sorted"], "grid['pos_sorted']", torch.float32, shape=(n, 2))
+    _mesh_arg(what, grid["order"], "grid['order']", torch.int32, shape=(n,))
+    cells = [int(c) for c in grid["n_cells"]]
+    if len(cells) != 3 or not all(c >= 1 for c in cells) or cells[2] != 1:
+        raise ValueError(f"grid['n_cells']: {what}: expected [nx, ny, 1] cells, got {cells!r}")
+    _mesh_arg(what, grid["cell_start"], "grid['cell_start']", torch.int32, shape=(cells[0] * cells[1] + 1,))
+    box = _box_arg(what, box)
+    if normals is not None:
+        _mesh_arg(what, normals, "normals", torch.float64, shape=(n, 2))
+    shapes = (("out[0]", torch.float64, (n,)), ("out[1]", torch.float64, (n, 2)), ("out[2]", torch.int32, (n,)),
+              ("out[3]", torch.uint8, (n,)), ("out[4]", torch.int32, (n,)))
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 5:
+            raise ValueError(f"out: {what}: expected the five tensors (area, centroid, nvert, flags, rings)")
+        for (name, dtype, shape), t in zip(shapes, out):
+            _mesh_arg(what, t, name, dtype, shape=shape)
+    dev = _mesh_devices(what, ("grid", grid["pos_sorted"]), ("grid['order']", grid["order"]), ("grid['cell_start']", grid["cell_start"]),
+                        ("normals", normals), *((name, t) for (name, _, _), t in zip(shapes, out or ())))
+    if out is None:
+        out = tuple(torch.zeros(shape, dtype=dtype, device=dev) for _, dtype, shape in shapes)
+    area, centroid, nvert, flags, rings = out
+    vc = _lib.g4c_voronoi_cells_t(pos_sorted=_lib.ptr(grid["pos_sorted"]), order=_lib.ptr(grid["order"]), cell_start=_lib.ptr(grid["cell_start"]),
+                                  n_cells=(C.c_int32 * 3)(*cells), origin=grid["org"], cell_size=float(grid["h"]),
+                                  box_lo=(C.c_double * 2)(box[0], box[1]), box_hi=(C.c_double * 2)(box[2], box[3]), normals=_lib.ptr(normals),
+                                  area=_lib.ptr(area), centroid=_lib.ptr(centroid), nvert=_lib.ptr(nvert), flags=_lib.ptr(flags),
+                                  rings=_lib.ptr(rings))
+    _lib.check(_lib.load().g4c_voronoi_cells(C.byref(vc), n, _lib.stream_handle(dev)))
+    return area, centroid, nvert, flags, rings
+
+
+def integral_program(entries, nz: Optional[int] = None) -> "_lib.g4c_integral_program_t":
+    """The program of `weighted_integrals`: 1 .. `_lib.INTEGRALS_MAX_ENTRIES` entries (a, b) — the sum of w · z[a] · z[b]; a column of −1
+    stands for 1, so (a, −1) is the integral of z[a] and (−1, −1) the sum of the weights — over samples of `nz` columns.  A program that
+    is one already is checked against nz and returned."""
+    if isinstance(entries, _lib.g4c_integral_program_t):
+        pairs = [(int(entries.a[e]), int(entries.b[e])) for e in range(int(entries.ne))]
+    else:
+        try:
+            pairs = [tuple(e) for e in entries]
+        except TypeError:
+            raise ValueError(f"entries: expected a sequence of column pairs (a, b), got {entries!r}") from None
+    if not 1 <= len(pairs) <= _lib.INTEGRALS_MAX_ENTRIES:
+        raise ValueError(f"entries: expected 1 .. {_lib.INTEGRALS_MAX_ENTRIES} pairs (a, b), got {len(pairs)}")
+    if nz is not None and (isinstance(nz, bool) or not isinstance(nz, int) or nz < 1):
+        raise ValueError(f"nz: expected a number of columns >= 1, got {nz!r}")
+    for e, pair in enumerate(pairs):
+        if len(pair) != 2 or not all(isinstance(c, int) and not isinstance(c, bool) and c >= -1 for c in pair):
+            raise ValueError(f"entries: entry {e}: expected two columns (a, b), each >= 0 or −1 (the constant 1), got {pair!r}")
+        if nz is not None and max(pair) >= nz:
+            raise ValueError(f"entries: entry {e}: column {max(pair)} of samples with {nz} columns")
+    if isinstance(entries, _lib.g4c_integral_program_t):
+        return entries
+    p = _lib.g4c_integral_program_t(ne=len(pairs))
+    for e, (a, b) in enumerate(pairs):
+        p.a[e], p.b[e] = a, b
+    return p
+
+
+def _integrals_scratch_doubles(n_nodes: int, ne: int) -> int:
+    return 8 + min(max(-(-int(n_nodes) // 256), 1), 1024) * int(ne)
+
+
+def weighted_integrals_scratch(n_nodes: int, ne: int, device) -> Tensor:
+    """The `scratch` buffer of `weighted_integrals` for n_nodes rows and ne entries (g4c_weighted_integrals_scratch_doubles)."""
+    n = int(_lib.load().g4c_weighted_integrals_scratch_doubles(int(n_nodes), int(ne)))
+    if n < 0:
+        _lib.check(n)
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def _integrals_source(what: str, x, name: str, n_nodes: Optional[int], nz: int, x_step: int, max_steps: int):
+    """A source of weighted_integrals: float32 [N, >= nz] (x_step 0) or [N, >= x_step max_steps] (x_step >= nz), rows of unit stride ->
+    (N, its leading dimension)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if isinstance(x_step, bool) or not isinstance(x_step, int) or not (x_step == 0 or x_step >= nz):
+        raise ValueError(f"{name}_step: {what}: expected 0 (one step) or the columns of a step >= nz = {nz}, got {x_step!r}")
+    need = nz if x_step == 0 else x_step * max_steps
+    if x.dim() != 2 or int(x.size(1)) < need or (n_nodes is not None and int(x.size(0)) != n_nodes):
+        raise ValueError(f"{name}: {what}: expected [{'N' if n_nodes is None else n_nodes}, >= {need}], got shape {tuple(x.shape)}")
+    n, cols = int(x.size(0)), int(x.size(1))
+    if (n > 0 and cols > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) < cols):
+        raise ValueError(f"{name}: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+    ld = max(int(x.stride(0)), cols) if n > 1 else cols
+    if ld >= 2 ** 31:
+        raise ValueError(f"{name}: {what}: a row stride of {ld} elements does not fit")
+    return n, ld
+
+
+def weighted_integrals(x: Tensor, w: Tensor, entries, stats: Tensor, scratch: Tensor, *, nz: Optional[int] = None, sub: Optional[Tensor] = None,
+                       x_step: int = 0, sub_step: int = 0, step: Optional[Tensor] = None, t: int = 0) -> Tensor:
+    """g4c_weighted_integrals: stats[t, e] = Σ_i w[i] · z_i[a_e] · z_i[b_e] over the entries (a_e, b_e) of `entries` (`integral_program`).
+    The sample z_i is x[i, x_step t : x_step t + nz] — x float32 [N, >= nz] with x_step 0 (a prediction, the derived columns), or
+    [N, >= x_step max_steps] with x_step = the columns of a step (a target holding every step) — or, with `sub` (same rules, sub_step),
+    that minus sub's, the difference formed in fp64.  nz defaults to x's columns (x_step 0) or x_step.  w float64 [N]: a row of weight 0
+    contributes nothing whatever it holds.  stats float64 [max_steps, ne] (row t overwritten), scratch from
+    `weighted_integrals_scratch`.  The step index is `step[0]` (int32, read on the device, never written) or, without `step`, `t`;
+    a step outside 0 <= t < max_steps writes nothing.  fp64 sums in a fixed order, no atomics: the bits are a function of the data
+    alone.  Returns stats."""
+    what = "weighted_integrals"
+    if nz is None:
+        nz = x_step if (isinstance(x_step, int) and x_step > 0) else (int(x.size(1)) if torch.is_tensor(x) and x.dim() == 2 else 0)
+    if isinstance(nz, bool) or not isinstance(nz, int) or nz < 1:
+        raise ValueError(f"nz: {what}: expected a number of columns >= 1, got {nz!r}")
+    prog = integral_program(entries, nz)
+    ne = int(prog.ne)
+    if not torch.is_tensor(stats) or stats.dtype != torch.float64 or stats.dim() != 2 or int(stats.size(1)) != ne or not stats.is_contiguous():
+        raise ValueError(f"stats: {what}: expected a contiguous float64 [max_steps, ne = {ne}], got {getattr(stats, 'dtype', type(stats).__name__)} "
+                         f"{tuple(getattr(stats, 'shape', ()))}")
+    max_steps = int(stats.size(0))
+    n_nodes, x_ld = _integrals_source(what, x, "x", None, nz, x_step, max_steps)
+    sub_ld = 0
+    if sub is not None:
+        _, sub_ld = _integrals_source(what, sub, "sub", n_nodes, nz, sub_step, max_steps)
+    _mesh_arg(what, w, "w", torch.float64, shape=(n_nodes,))
+    _mesh_arg(what, scratch, "scratch", torch.float64, dim=1)
+    need = _integrals_scratch_doubles(n_nodes, ne)
+    if scratch.numel() < need:
+        raise ValueError(f"scratch: {what}: {scratch.numel()} doubles, needs {need} (weighted_integrals_scratch)")
+    if step is not None:
+        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
+            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
+    elif isinstance(t, bool) or not isinstance(t, int):
+        raise ValueError(f"t: {what}: expected a step index, got {t!r}")
+    dev = _mesh_devices(what, ("x", x), ("sub", sub), ("w", w), ("stats", stats), ("scratch", scratch), ("step", step))
+    wi = _lib.g4c_weighted_integrals_t(x=_lib.ptr(x), x_ld=x_ld, x_step=x_step, sub=_lib.ptr(sub), sub_ld=sub_ld, sub_step=sub_step, nz=nz,
+                                       w=_lib.ptr(w), step=_lib.ptr(step), t_host=int(t), max_steps=max_steps, stats=_lib.ptr(stats),
+                                       scratch=_lib.ptr(scratch))
+    _lib.check(_lib.load().g4c_weighted_integrals(C.byref(wi), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
+    return stats
 
 
 def _snapshot_rows(what: str, x, name: str):

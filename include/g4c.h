@@ -999,6 +999,90 @@ int g4c_snapshot_gram(const float *a, const double *mean_a, const g4c_snapshot_s
 int g4c_snapshot_combine(const float *x, const double *mean, const g4c_snapshot_sel_t *sel /*host*/, const double *C, int64_t ldc, int32_t R,
                          int64_t L, float *out /*[R, L]*/, void *stream);
 
+/* Node control volumes (csrc/control_volumes.hip) — the areas that turn the node sums of the diagnostics into integrals over a 2-D
+ * domain, and the sums weighted by them.  The reference has no counterpart: a kNN cloud has no cells.
+ *
+ * g4c_voronoi_cells, once per mesh.  Node i gets the polygon  (its Voronoi cell within the cloud) ∩ (the box [box_lo, box_hi]) ∩
+ * (optionally the half-plane {x : (x − pos_i)·n_i >= 0} through the node itself, n_i = normals[i] != (0, 0): a wall node, whose cell
+ * would otherwise reach into the body).  One thread per node, fp64 without contraction on the fp32 positions (g4c_mesh_jet_weights'
+ * conventions), the polygon — at most G4C_VORONOI_MAX_VERTS vertices, relative to the node, counter-clockwise — in the thread's own
+ * LDS column.  The cloud's cell grid (pos_sorted, order, cell_start, n_cells, origin, cell_size) is the one g4c_knn_grid takes.
+ *   1. The polygon starts as the box: (lo_x, lo_y), (hi_x, lo_y), (hi_x, hi_y), (lo_x, hi_y), each minus the node.
+ *   2. A clip keeps {v : s(v) = c − (v_x a + v_y b) >= 0}: Sutherland-Hodgman, vertex by vertex from vertex 0; a vertex with s >= 0 is
+ *      kept (exactly on the line: kept), and an edge whose ends have s of strictly opposite signs adds its crossing
+ *      v + (s / (s − s')) (v' − v), v the edge's first vertex.  A polygon with no vertex of s < 0 is left as it is.
+ *   3. The wall half-plane first: (a, b, c) = (−n_x, −n_y, 0).
+ *   4. The node's cell is floor(((double)pos − (double)origin) / (double)cell_size) clamped per axis.  Ring rho = 0, 1, ... of the grid
+ *      about it (the cells at Chebyshev distance rho that lie in the grid) is walked row by row, y ascending: a first or last row is
+ *      one run of sorted points from its first cell to its last, any other row its left cell, then its right one; every point j but
+ *      the node itself clips by the bisector: r = pos_j − pos_i, (a, b, c) = (r_x, r_y, ½ |r|²).  A point at zero distance cuts
+ *      nothing and sets DUPLICATE (in both nodes of the pair).
+ *   5. Before ring rho >= 1: R² = the largest |v|² of the polygon's vertices, lb = the least distance from the node to a face of the
+ *      block of rings < rho that has cells behind it, less 1e-5 cell_size.  The walk stops if lb > 0 and lb² > 4 R² (no unseen point
+ *      can cut the polygon), or when no ring is left in the grid.  rings[i] = the rings walked: what to look at when a box far
+ *      larger than the cloud makes the hull nodes scan the grid.
+ *   6. A clip that would give more than G4C_VORONOI_MAX_VERTS vertices stops the node: flag OVERFLOW, area +0, nvert 0.  A polygon
+ *      left with fewer than 3 vertices is empty: area +0, nvert 0.
+ *   7. area = ½ Σ_j (x_j y_j+1 − x_j+1 y_j) about the node in vertex order, centroid = pos_i + Σ_j (v_j + v_j+1) cross_j / (3 Σ cross);
+ *      a sum that is not > 0 gives area +0, and every row of area +0 has the node as its centroid.  BOX: an edge of the final polygon
+ *      lies on the box; WALL: the node has a normal.
+ * Outputs are in the caller's node order (row order[s] for sorted point s); every row is written.  The grid is trusted as
+ * g4c_knn_grid trusts it.  G4C_EINVAL before any launch: a bad grid, an empty or non-finite box, n_nodes outside [0, 2^31), a null
+ * pointer (normals may be NULL).  n_nodes == 0 launches nothing. */
+#define G4C_VORONOI_MAX_VERTS 32
+#define G4C_VORONOI_BOX 1
+#define G4C_VORONOI_WALL 2
+#define G4C_VORONOI_DUPLICATE 4
+#define G4C_VORONOI_OVERFLOW 8
+typedef struct g4c_voronoi_cells {
+    const float *pos_sorted;     /* [n_nodes, 2] the cloud in cell-sorted order */
+    const int32_t *order;        /* [n_nodes] node row of each sorted point */
+    const int32_t *cell_start;   /* [n_cells[0] n_cells[1] + 1] first sorted point of each cell */
+    int32_t n_cells[3];          /* (the third is not read) */
+    float origin[3], cell_size;
+    double box_lo[2], box_hi[2];
+    const double *normals;       /* [n_nodes, 2] by node row, (0, 0): none; or NULL */
+    double *area;                /* [n_nodes] */
+    double *centroid;            /* [n_nodes, 2] */
+    int32_t *nvert;              /* [n_nodes] */
+    uint8_t *flags;              /* [n_nodes] G4C_VORONOI_* */
+    int32_t *rings;              /* [n_nodes] */
+} g4c_voronoi_cells_t;
+int g4c_voronoi_cells(const g4c_voronoi_cells_t *vc /*host*/, int64_t n_nodes, void *stream);
+
+/* g4c_weighted_integrals, once per step and source: stats[t][e] = Σ_i w_i z_i[a_e] z_i[b_e] for the ne <= G4C_INTEGRALS_MAX_ENTRIES
+ * entries (a_e, b_e) of the program; a column of −1 stands for 1.  The sample is z_i[c] = (double)x[i x_ld + x_step t + c] — x_step == 0:
+ * a prediction or the derived columns `cur`; x_step = nf: a target holding every step, read by the same code — or, with sub, that
+ * minus (double)sub[i sub_ld + sub_step t + c], the difference formed in fp64, where it is exact.  The product z[a] z[b] is rounded to
+ * fp64 once, then multiplied by w_i and rounded once, then added.  A row with w_i == 0 contributes nothing whatever it holds.
+ * Two launches in a fixed order, no atomics: at most 1024 workgroups of 256 — a function of n_nodes alone —, thread tid of workgroup b
+ * adds the rows 256 b + tid, + 256 · workgroups, ... from +0 in that order, a xor butterfly 32, 16, .., 1 per wave of 64, the four waves
+ * added in order; then one workgroup whose thread i adds the partials of workgroups i, i + 256, ... and reduces the same way.  scratch:
+ * g4c_weighted_integrals_scratch_doubles(n_nodes, ne) doubles.  t = step[0] read on the device and never written (step NULL: t_host);
+ * stats[t] is OVERWRITTEN iff 0 <= t < max_steps, any other step writes no statistic: capturable, and bit-identical between captured
+ * and eager steps.  G4C_EINVAL before any launch: bad sizes, an entry outside [−1, nz), a leading dimension below what the columns and
+ * steps need, a null pointer; G4C_EUNSUPPORTED: ne > G4C_INTEGRALS_MAX_ENTRIES. */
+#define G4C_INTEGRALS_MAX_ENTRIES 8
+typedef struct g4c_integral_program {
+    int32_t ne;
+    int32_t a[G4C_INTEGRALS_MAX_ENTRIES], b[G4C_INTEGRALS_MAX_ENTRIES];
+} g4c_integral_program_t;
+typedef struct g4c_weighted_integrals {
+    const float *x;              /* [n_nodes, x_ld] */
+    int32_t x_ld, x_step;        /* x_step 0, or >= nz with x_ld >= x_step max_steps */
+    const float *sub;            /* [n_nodes, sub_ld] or NULL */
+    int32_t sub_ld, sub_step;
+    int32_t nz;                  /* columns of a sample */
+    const double *w;             /* [n_nodes] */
+    const int32_t *step;         /* device; NULL: t = t_host */
+    int32_t t_host, max_steps;
+    double *stats;               /* [max_steps][ne] */
+    double *scratch;
+} g4c_weighted_integrals_t;
+int64_t g4c_weighted_integrals_scratch_doubles(int64_t n_nodes, int32_t ne);
+int g4c_weighted_integrals(const g4c_weighted_integrals_t *wi /*host*/, const g4c_integral_program_t *prog /*host*/, int64_t n_nodes,
+                           void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,
