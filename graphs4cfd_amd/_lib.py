@@ -233,6 +233,8 @@ _SIGNATURES = {
     "g4c_mlp_last_row_ranges": (C.c_int, []),
     "g4c_mlp_shapes_enable": (C.c_int, [C.c_int]),
     "g4c_mlp_last_shape": (C.c_int, []),
+    "g4c_mlp_tile_form": (C.c_int, [C.c_int]),
+    "g4c_mlp_last_tile_rows": (C.c_int, []),
     "g4c_project_to_edges": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
     "g4c_edge_scalar_to_node_vector": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,

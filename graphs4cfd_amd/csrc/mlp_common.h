@@ -360,9 +360,11 @@ struct Launch {
     // the tile kernel's two policy inputs, settled by the launcher's choose step: the deep weight ring of a small launch, and whether
     // a launch that matches a compile-time shape may run it
     bool deep_ring, shapes;
+    int tile_form;           // ... and the form a shaped launch runs in (g4c_mlp_tile_form: 0 32-row tiles, 1 64-row tiles)
 };
-// what a family's launch ran: g4c_mlp_last_kernel() / g4c_mlp_last_shape() of the call
-struct Ran { int kernel = G4C_KERNEL_NONE, shape = G4C_TILE_SHAPE_GENERIC, ranges = 0; };          // (ranges: workgroups of the row-range form, else 0)
+// what a family's launch ran: g4c_mlp_last_kernel() / g4c_mlp_last_shape() / g4c_mlp_last_tile_rows() of the call
+// (ranges: workgroups of the row-range form, else 0; tile_rows: rows per workgroup of a tile-kernel launch, else 0)
+struct Ran { int kernel = G4C_KERNEL_NONE, shape = G4C_TILE_SHAPE_GENERIC, ranges = 0, tile_rows = 0; };
 
 // What the envelopes of the two column-split message kernels (mlp_bx6i.hip, mlp_ws.hip) share: an inference launch of ONE weighted
 // 128-wide 16-byte addressable block and no or two aligned 128-wide additive blocks, no narrow blocks, heads or residual; 128-wide

@@ -668,6 +668,7 @@ constexpr int G4C_SEG_CHUNKS = 1;
 constexpr int G4C_SEG_INFLIGHT = 6;     // rows of a segment in flight per column chunk when a source is aggregated on load
 constexpr int G4C_BX6_MINW = 4;         // workgroups per CU the instantiations are register-limited for (launch_bounds)
 constexpr int G4C_F16_MINW = 4;
+constexpr int G4C_RT2_MINW = 3;         // ... of the 64-row shaped instantiations: 192 rows in flight per CU
 // RT = 1: 32-row tile.  RT = 2: 64-row tile — every weight fragment feeds two row tiles (half the L2 -> register weight
 // traffic per row, which is what this kernel stalls on) and every memory round trip of the tile's critical path serves
 // twice the rows.
@@ -698,22 +699,27 @@ __device__ __forceinline__ f32x4 mul_row4_bf16(const Params &p, int l, long long
     return r;
 }
 
+// Workgroups per CU the registers of an instantiation are bounded for: two on the deep ring, three for 64-row tiles (168 registers), else
+// four (128)
 template <int RT, bool VEC, bool FULL, int SP, bool SAVE = false, int RD6 = 2, bool TRACK = true, class SH = TileShapeGeneric>
-__global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX6_MINW)) void mlp_bx6_kernel(const Params p) {
+__global__ __launch_bounds__(256, RD6 > 2 ? 2 : (RT == 2 ? G4C_RT2_MINW : (SP == 2 ? G4C_F16_MINW : G4C_BX6_MINW))) void mlp_bx6_kernel(const Params p) {
     static_assert(TRACK || (SP == 2 && !SAVE), "the tracker-free instantiations: f16x3 stream, inference");
     constexpr bool SHAPED = SH::ID != G4C_TILE_SHAPE_GENERIC;
-    static_assert(!SHAPED || (RT == 1 && VEC && FULL && SP == 2 && !SAVE && RD6 == 2), "launch shapes: the chip-filling f16x3 inference form");
-    static_assert(RT == 1, "64-row tiles (RT = 2) measured slower in every arithmetic (split streams, round 3: 480 against 446 us; rounded-bf16 mode, round 6, "
-                           "500k-row edge update with heads: 288 against 255 us) and cannot take the fused aggregation: not instantiated");
+    static_assert(!SHAPED || (VEC && FULL && SP == 2 && !SAVE && RD6 == 2), "launch shapes: the chip-filling f16x3 inference form");
+    static_assert(RT == 1 || (RT == 2 && SHAPED),
+                  "64-row tiles (RT = 2): the shaped f16x3 inference instantiations only (three workgroups per CU at no more than 168 registers).  Everywhere "
+                  "else they measured slower (split streams, round 3: 480 against 446 us, at 203 registers; rounded-bf16 mode, round 6, "
+                  "500k-row edge update with heads: 288 against 255 us) and cannot take the fused aggregation: not instantiated");
     constexpr int ROWS = 32 * RT, NW = 4;
     constexpr int PLN = ROWS * HB;              // one bf16 operand plane [ROWS][136]
     // three operand planes; the fp32 final tile [ROWS][132] aliases them
     constexpr int BUF_FLOATS = (SP == 2 ? 2 : 3) * PLN / 2;      // (SP == 2: two planes; [ROWS][132] floats still fit in [2][ROWS][136] halves)
     static_assert(BUF_FLOATS >= ROWS * HS, "final tile must fit");
-    // RT = 2 keeps three workgroups per CU (<= 54.6 KB of LDS each): two index slots per kind (the launcher checks) and the
-    // biases read from global memory (L1 hits) instead of an LDS copy
+    // RT = 2 keeps three workgroups per CU (<= 53 KB of LDS each): two index slots per kind (a shape has at most one indexed source).
+    // (Two f16x3 planes of 64 rows leave room for the biases' LDS copy: 38 KB in all.  LDS_BIAS false — biases from global memory — is
+    // the form three planes would need.)
     constexpr int NSLOT = RT == 2 ? 2 : G4C_MAX_SRC;
-    constexpr bool LDS_BIAS = RT == 1;
+    constexpr bool LDS_BIAS = RT == 1 || SP == 2;
     constexpr int BIAS_FLOATS = LDS_BIAS ? G4C_MAX_LAYERS * NP : 0;
     // SMALL (the deep-ring instantiation of launches of few tiles: one or two workgroups per CU, LDS to spare): the fp32 final tile
     // has its own buffer instead of aliasing the planes — one barrier less in front of the heads — and both heads' MFMA blocks run
@@ -1070,7 +1076,8 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         for (int s = 0; s < p.n_src; ++s) block0(s, s + 1 < p.n_src, std::integral_constant<int, 0>{});
     }
     G4C_STAMPW(4);
-    for (int l = 0;; ++l) {
+    // one layer boundary: the epilogue of layer l, then (unless it was the last: true) the block of layer l + 1
+    auto layer_step = [&](const int l) __attribute__((always_inline)) -> bool {
         const bool last = (l == n_layers - 1);
         if (last) {
             // final tile in fp32 for the LayerNorm / store epilogue (aliases the operand planes: everybody finished
@@ -1094,7 +1101,7 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
                 }
             __syncthreads();
             G4C_STAMPW(5 + 2 * l);
-            break;
+            return true;
         }
 #pragma unroll
         for (int t = 0; t < RT; ++t)
@@ -1137,9 +1144,25 @@ __global__ __launch_bounds__(256, RD6 > 2 ? 2 : (SP == 2 ? G4C_F16_MINW : G4C_BX
         wofs += 2u * BLOCK6;
         __syncthreads();
         G4C_STAMPW(6 + 2 * l);
+        return false;
+    };
+    if constexpr (RT == 2) {
+        // (64-row tiles: unrolled over the shape's layers.  Rolled, hipcc keeps the finished layer's four accumulators beside the next
+        // layer's across the loop's back edge: 196 registers instead of 138.)
+#pragma unroll
+        for (int l = 0; l < SH::N_LAYERS; ++l) if (layer_step(l)) break;
+    } else {
+        for (int l = 0;; ++l) if (layer_step(l)) break;
     }
     G4C_STAMPW(12);
-    split_finish<NW, ROWS, SHAPED>(p, sH, sGB, wave, lane, row0, mlim);
+    if constexpr (RT == 1) {
+        split_finish<NW, ROWS, SHAPED>(p, sH, sGB, wave, lane, row0, mlim);
+    } else {
+        // a 64-row tile finishes as its two 32-row tiles would: a row's LayerNorm sums run over the same eight lanes of sixteen columns
+        // in the same order, and each half stores through a descriptor of its own rows below mlim
+#pragma unroll
+        for (int t = 0; t < RT; ++t) split_finish<NW, 32, SHAPED>(p, sH + 32 * t * HS, sGB, wave, lane, row0 + 32 * t, mlim);
+    }
     G4C_STAMPW(13);
     if constexpr (!SHAPED)
     if (p.agg) {
@@ -1284,6 +1307,19 @@ G4C_TILE_ISA(false)
 template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeUp<3, 0>>(const Params);
 template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeUp<3, 2>>(const Params);
 template __global__ void mlp_bx6_kernel<1, true, true, 2, false, 2, true, TileShapeDown<3>>(const Params);
+// the 64-row tile form (g4c_mlp_tile_form; tests/test_tile_forms_isa.py): every instantiation tile_go_rows64 launches
+#define G4C_TILE_ISA(TRACK)                                                                                              \
+    template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, TRACK, TileShapeNode<2, 0>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, TRACK, TileShapeNode<2, 2>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, TRACK, TileShapeNode<3, 0>>(const Params);       \
+    template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, TRACK, TileShapeNode<3, 2>>(const Params);
+G4C_TILE_ISA(true)
+G4C_TILE_ISA(false)
+#undef G4C_TILE_ISA
+template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, true, TileShapeUp<2, 0>>(const Params);
+template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, true, TileShapeUp<2, 2>>(const Params);
+template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, true, TileShapeUp<3, 0>>(const Params);
+template __global__ void mlp_bx6_kernel<2, true, true, 2, false, 2, true, TileShapeUp<3, 2>>(const Params);
 #endif
 
 }  // namespace
@@ -1399,6 +1435,34 @@ static void tile_go_full(int shape, const Launch &L, hipStream_t st) {
     }
 #undef G4C_FULL
 }
+// The tile form of a shaped launch (g4c_mlp_tile_form; Launch::tile_form) — 1: 64-row tiles (a weight fragment feeds two row tiles:
+// half the weight stream per row), registers bounded for three workgroups per CU.  Same arithmetic in the same order per row:
+// bit-identical to form 0.  False: the shape has no 64-row form or the launch does not fit it — the caller launches form 0.
+// (A 32-row form bounded for FIVE workgroups per CU was measured beside it and is not built: scripts/variants/r23_tile_five_workgroups.patch.)
+template <bool TRACK>
+static bool tile_go_rows64(int shape, const Launch &L, hipStream_t st) {
+    Params p = L.p;
+    const bool l3 = p.n_layers == 3, h2 = p.n_heads == 2;
+    // (a whole last tile of 64 rows inside the 32-bit offsets of the row descriptors, as tile_shape_of asks for 32)
+    for (int s = 0; s < p.n_src; ++s)
+        if (!p.src[s].idx && (p.M + 64) * (long long)p.src[s].ld * 4 >= (1LL << 31)) return false;
+    if ((p.M + 64) * (long long)p.out_ld * 4 >= (1LL << 31)) return false;
+    p.n_tiles = (int)((L.row_count + 63) / 64);
+#define G4C_ROWS64(...) mlp_bx6_kernel<2, true, true, 2, false, 2, TRACK, __VA_ARGS__><<<dim3(p.n_tiles), dim3(256), 0, st>>>(p)
+    if (shape == G4C_TILE_SHAPE_NODE) {
+        if (l3) { if (h2) G4C_ROWS64(TileShapeNode<3, 2>); else G4C_ROWS64(TileShapeNode<3, 0>); }
+        else { if (h2) G4C_ROWS64(TileShapeNode<2, 2>); else G4C_ROWS64(TileShapeNode<2, 0>); }
+    } else if constexpr (TRACK) {
+        // (DownMP's shape has no 64-row form: its headline launch did not move, 49.5 against 49.6 us — DESIGN.md 6, round 23)
+        if (shape != G4C_TILE_SHAPE_UP) return false;
+        if (l3) { if (h2) G4C_ROWS64(TileShapeUp<3, 2>); else G4C_ROWS64(TileShapeUp<3, 0>); }
+        else { if (h2) G4C_ROWS64(TileShapeUp<2, 2>); else G4C_ROWS64(TileShapeUp<2, 0>); }
+    } else {
+        return false;          // (the UpMP shape has no tracker-free form)
+    }
+#undef G4C_ROWS64
+    return true;
+}
 // The other rung: (SAVE, RD6) of a split SP — the training form on the two-step ring; inference on the deep ring when the launch is small
 template <int SP>
 static void tile_go_sp(const Launch &L, bool full, hipStream_t st) {
@@ -1420,6 +1484,10 @@ int tile_launch(const Launch &L, hipStream_t st, Ran &ran) {
     const bool cert = infer_full && p.range_certified;
     ran.kernel = cert ? G4C_KERNEL_MLP_BX6_CERT : G4C_KERNEL_MLP_BX6;
     ran.shape = shape;
+    ran.tile_rows = 32;
+    if (shape != G4C_TILE_SHAPE_GENERIC && L.tile_form == 1 && (cert ? tile_go_rows64<false>(shape, L, st) : tile_go_rows64<true>(shape, L, st)))
+        ran.tile_rows = 64;
+    else
     if (cert) tile_go_full<false>(shape, L, st);
     else if (shape != G4C_TILE_SHAPE_GENERIC) tile_go_full<true>(shape, L, st);
     else if (L.f16x2) tile_go_sp<2>(L, full, st);

@@ -16,7 +16,7 @@
 //   bx6i              split-operand stream; g4c_mlp_bx6i_enable 2, or 1 and >= 400 000 rows    next row
 //   tile              split-operand stream.  At most g4c_mlp_small_launch_tiles tiles: the     -
 //                     deep weight ring; above, with g4c_mlp_shapes_enable: a compile-time
-//                     shape where one matches
+//                     shape where one matches, in the form g4c_mlp_tile_form names
 //   split             G4C_WFMT_FP32                                                            -
 //
 // (A stream in the row-split k order can run on no other kernel: outside the envelope the call fails instead of computing something else.)
@@ -37,12 +37,22 @@ std::atomic<int> g_deep_tiles{512};     // launches of at most this many 32-row 
 #define G4C_TILE_SHAPES_DEFAULT 1
 #endif
 std::atomic<int> g_shapes{G4C_TILE_SHAPES_DEFAULT};
+// the form a shaped chip-filling launch of the tile kernel runs in (mlp_fused.hip tile_go_rows64): 0 32-row tiles, 1 64-row tiles
+// (-DG4C_TILE_FORM_DEFAULT=: A/B legs, as above).  64-row tiles run three workgroups per CU, so a launch takes them from
+// TILE_ROWS64_FILL times the small-launch limit on (1 536 32-row tiles at the default 512 = 768 64-row tiles, three per CU of 256):
+// below that they leave CUs short of workgroups (replayed headline step, the coarse levels' UpMP / DownMP launches at positions 16 and
+// 25: 18.6 against 17.6 us and 32.7 against 31.8)
+#ifndef G4C_TILE_FORM_DEFAULT
+#define G4C_TILE_FORM_DEFAULT 1
+#endif
+std::atomic<int> g_tile_form{G4C_TILE_FORM_DEFAULT};
 
 // mlp_ws_kernel against the two-way instantiation of mlp_bx6i_kernel, which it replaces, on the level-1 message launch: 322 us against
 // 339 us with the fused aggregation, 288 against 292 without; same-box sweeps of round 3: ahead of the tile kernel from ~20 k rows
 constexpr long long WS_MIN_ROWS = 20000;
 // mlp_bx6i_kernel needs a full machine of its two workgroups per CU: same-box crossover against the tile kernel ~300 k rows
 constexpr long long BX6I_MIN_ROWS = 400000;
+constexpr long long TILE_ROWS64_FILL = 3;
 
 int knob(std::atomic<int> &k, int value, int max_value) {
     const int prev = k.load(std::memory_order_relaxed);
@@ -333,6 +343,7 @@ bool at_size(const std::atomic<int> &mode_knob, long long min_rows, const Launch
 LaunchFn choose(Launch &L) {
     L.deep_ring = L.p.n_tiles <= g_deep_tiles.load(std::memory_order_relaxed);
     L.shapes = g_shapes.load(std::memory_order_relaxed) != 0;
+    L.tile_form = L.p.n_tiles > TILE_ROWS64_FILL * g_deep_tiles.load(std::memory_order_relaxed) ? g_tile_form.load(std::memory_order_relaxed) : 0;
     if (L.pre) {
         G4C_REQUIRE(!L.has_node, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) with upd: the fused MP layer has no such form");
         G4C_REQUIRE(L.f16x2, nullptr, "g4c_mlp_run: every source additive (first layer precomputed) needs the f16x3 format (G4C_WFMT_F16X2), got w_format %d", L.fmt);
@@ -404,6 +415,8 @@ extern "C" int g4c_mlp_ws_enable(int on) { return knob(g_ws_mode, on, 2); }
 extern "C" int g4c_mlp_bx6i_enable(int on) { return knob(g_bx6i_mode, on, 2); }
 extern "C" int g4c_mlp_small_launch_tiles(int n_tiles) { return knob(g_deep_tiles, n_tiles, INT_MAX); }
 extern "C" int g4c_mlp_shapes_enable(int on) { return knob(g_shapes, on, 1); }
+extern "C" int g4c_mlp_tile_form(int form) { return knob(g_tile_form, form, 1); }
+extern "C" int g4c_mlp_last_tile_rows(void) { return g_last.tile_rows; }
 extern "C" int g4c_mlp_last_kernel(void) { return g_last.kernel; }
 extern "C" int g4c_mlp_last_shape(void) { return g_last.shape; }
 extern "C" int g4c_mlp_last_row_ranges(void) { return g_last.ranges; }

@@ -394,6 +394,16 @@ int g4c_mlp_last_row_ranges(void);
 #define G4C_TILE_SHAPE_DOWN 3
 int g4c_mlp_shapes_enable(int on);
 int g4c_mlp_last_shape(void);
+/* The form a launch that runs a shape takes (process-wide, like the switches above).  Both forms compute the same rows bit for bit: a
+ * row's arithmetic does not depend on its tile.
+ *   0  32-row tiles, registers bounded for four workgroups per CU
+ *   1  64-row tiles (a weight fragment feeds two row tiles: half the weight stream per row), three workgroups per CU (the default):
+ *      G4C_TILE_SHAPE_NODE and G4C_TILE_SHAPE_UP launches of more than three times g4c_mlp_small_launch_tiles 32-row tiles whose direct
+ *      sources and output stay below 2^31 bytes with a whole last tile of 64 rows; every other launch runs form 0
+ * g4c_mlp_tile_form: sets the form, returns the previous one; a negative argument only queries.  g4c_mlp_last_tile_rows: rows per
+ * workgroup of the calling thread's most recent g4c_mlp_run when the tile kernel ran it (32 or 64), else 0. */
+int g4c_mlp_tile_form(int form);
+int g4c_mlp_last_tile_rows(void);
 
 /* Tiles of whole segments for the fused aggregation (g4c_mlp_io_t.tile_rows / tile_seg): returns the tile count, -1 if a segment is
  * longer than max_rows. */
