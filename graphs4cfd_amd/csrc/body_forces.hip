@@ -2,17 +2,18 @@
 // node and the velocity's least-squares gradient there (the loop of mesh_derived_kernel, mesh_gradient.hip: fp32, the in-edges in CSR
 // order), the stress and the two tractions on the item's area vector in fp64, and per body the six sums Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv.
 // A wall is hundreds of items: ONE workgroup of 256 per body takes its items tid, tid + 256, ... into register accumulators, a xor
-// butterfly per wave, the four waves in order through LDS (the records' rule, rollout_record.hip) — no second launch, no atomics,
-// nothing passes between workgroups: the bits are a function of the data alone.
+// butterfly per wave, the four waves in order through LDS (the step-record core's order, step_record.h) — no second launch, no
+// atomics, nothing passes between workgroups: the bits are a function of the data alone.
 // g4c_body_forces_adjoint, below it, is the transpose of that map's linear part (its backward): two small launches, per item and per node.
 #include "g4c_common.h"
+#include "step_record.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the bits.
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BF_THREADS = 256;
+constexpr int BF_THREADS = g4c::THREADS;
 constexpr int BF_WAVES = BF_THREADS / 64;
 constexpr int NSUM = G4C_FORCES_NSUM;
 
@@ -82,15 +83,11 @@ __global__ __launch_bounds__(BF_THREADS) void body_forces_kernel(const g4c_body_
         }
     }
 
-    // the records' reduction: a 6-level xor butterfly per wave, then the four waves in order through LDS
+    // the step-record core's order (step_record.h): the butterfly per wave, then the four waves in order through LDS — in thread 0
+    // alone, which needs all six sums to form `cur`
     __shared__ double part[BF_WAVES][NSUM];
 #pragma unroll
-    for (int j = 0; j < NSUM; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-        acc[j] = v;
-    }
+    for (int j = 0; j < NSUM; ++j) acc[j] = g4c::wave_sum(acc[j]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int j = 0; j < NSUM; ++j) part[threadIdx.x >> 6][j] = acc[j];
@@ -157,13 +154,9 @@ extern "C" int g4c_body_forces(const g4c_body_forces_t *bf, int64_t n_bodies, in
 // in-list in a fixed order.  Nothing passes between threads.
 namespace {
 
-constexpr int BFA_MAX_BLOCKS = 1024;          // as the sibling adjoints: 4 workgroups of 256 per CU on 256 CUs
 constexpr int HW = 5;                         // hw[w] = (H[u][0], H[u][1], H[v][0], H[v][1], cp)
 
-inline unsigned bfa_blocks(long long n) {
-    const long long b = (n + BF_THREADS - 1) / BF_THREADS;
-    return (unsigned)(b < 1 ? 1 : (b > BFA_MAX_BLOCKS ? BFA_MAX_BLOCKS : b));
-}
+inline unsigned bfa_blocks(long long n) { return (unsigned)g4c::blocks_or_one(n); }          // as the sibling adjoints
 
 template <bool VISCOUS>
 __global__ __launch_bounds__(BF_THREADS) void body_forces_adjoint_items_kernel(const g4c_body_forces_adjoint_t d, long long n_items) {

@@ -13,6 +13,7 @@
 // density.  The polygon lives in the thread's own LDS column, as mesh_jet_kernel keeps its derivatives: a runtime-indexed private array
 // would go to scratch memory.
 #include "g4c_common.h"
+#include "step_record.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop over Python floats
 // reproduces the bits.
@@ -199,43 +200,9 @@ __global__ __launch_bounds__(VC_THREADS) void voronoi_cells_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------ integrals
-constexpr int WI_THREADS = 256;
-// The grid — and with it the order of every sum — is a function of n_nodes alone (rollout_record.hip's rule).
-constexpr int WI_MAX_BLOCKS = 1024;
-// scratch: [0] the step index whose partials follow (-1: none), [1 .. 8) unused, then [workgroup][ne]
-constexpr int WI_HEADER = 8;
+// The grid, the scratch ([workgroup][ne] behind the header) and the reduction are the step-record core's (step_record.h): all sums.
+constexpr int WI_THREADS = g4c::THREADS;
 constexpr int WI_MAX_ENTRIES = G4C_INTEGRALS_MAX_ENTRIES;
-
-inline long long wi_blocks(long long n_nodes) {
-    const long long b = (n_nodes + WI_THREADS - 1) / WI_THREADS;
-    return b < 1 ? 1 : (b > WI_MAX_BLOCKS ? WI_MAX_BLOCKS : b);
-}
-
-// The workgroup's 256 sets of NE sums -> one set at dst: a 6-level xor butterfly inside each wave, then the four waves in order.
-template <int NE>
-__device__ __forceinline__ void wi_block_reduce(double (&a)[NE], double *__restrict__ dst) {
-    __shared__ double part[WI_THREADS / 64][NE];
-#pragma unroll
-    for (int j = 0; j < NE; ++j) {
-        double x = a[j];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        a[j] = x;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < NE; ++j) part[wave][j] = a[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < NE) {
-        const int j = threadIdx.x;
-        double x = part[0][j];
-#pragma unroll
-        for (int w = 1; w < WI_THREADS / 64; ++w) x += part[w][j];
-        dst[j] = x;
-    }
-}
 
 template <int NE>
 __global__ __launch_bounds__(WI_THREADS) void weighted_integrals_kernel(
@@ -272,34 +239,16 @@ __global__ __launch_bounds__(WI_THREADS) void weighted_integrals_kernel(
         }
     }
     // (`live` is the same in every workgroup: nobody writes the step index before the step's closing launch)
-    if (live) wi_block_reduce<NE>(acc, scratch + WI_HEADER + (long long)blockIdx.x * NE);
-    if (blockIdx.x == 0 && threadIdx.x == 0) scratch[0] = live ? (double)t : -1.0;
-}
-
-// The workgroups' partials -> stats[t], one workgroup behind the launch above on the same stream: thread i adds the partials of
-// workgroups i, i + 256, ... in order, then the same reduction.
-template <int NE>
-__global__ __launch_bounds__(WI_THREADS) void weighted_integrals_sum_kernel(const double *__restrict__ scratch, int n_blocks,
-                                                                           double *__restrict__ stats, int max_steps) {
-    const double tt = scratch[0];
-    if (!(tt >= 0.0 && tt < (double)max_steps)) return;
-    double acc[NE];
-#pragma unroll
-    for (int e = 0; e < NE; ++e) acc[e] = 0.0;
-    for (int b = threadIdx.x; b < n_blocks; b += WI_THREADS) {
-        const double *q = scratch + WI_HEADER + (long long)b * NE;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) acc[e] += q[e];
-    }
-    wi_block_reduce<NE>(acc, stats + (long long)(int)tt * NE);
+    if (live) g4c::block_reduce<g4c::all_sums>(acc, NE, g4c::partials(scratch, blockIdx.x, NE));
+    if (blockIdx.x == 0 && threadIdx.x == 0) g4c::post_step(scratch, live, t);
 }
 
 template <int NE>
 void wi_launch(const g4c_weighted_integrals_t &wi, const g4c_integral_program_t &p, long long n_nodes, hipStream_t s) {
-    const int blocks = (int)wi_blocks(n_nodes);
+    const int blocks = (int)g4c::blocks_or_one(n_nodes);
     weighted_integrals_kernel<NE><<<dim3((unsigned)blocks), dim3(WI_THREADS), 0, s>>>(
         wi.x, wi.x_ld, wi.x_step, wi.sub, wi.sub_ld, wi.sub_step, wi.w, p, wi.step, wi.t_host, wi.max_steps, n_nodes, wi.scratch);
-    weighted_integrals_sum_kernel<NE><<<dim3(1), dim3(WI_THREADS), 0, s>>>(wi.scratch, blocks, wi.stats, wi.max_steps);
+    g4c::partials_kernel<g4c::all_sums, NE, true><<<dim3(1), dim3(WI_THREADS), 0, s>>>(wi.scratch, blocks, NE, wi.stats, wi.max_steps);
 }
 
 }  // namespace
@@ -335,7 +284,7 @@ extern "C" int64_t g4c_weighted_integrals_scratch_doubles(int64_t n_nodes, int32
     G4C_REQUIRE(n_nodes >= 0 && ne >= 1, G4C_EINVAL, "g4c_weighted_integrals_scratch_doubles: bad sizes n_nodes=%lld ne=%d", (long long)n_nodes, ne);
     G4C_REQUIRE(ne <= WI_MAX_ENTRIES, G4C_EUNSUPPORTED, "g4c_weighted_integrals_scratch_doubles: ne=%d entries (1 .. %d are supported)", ne,
                 WI_MAX_ENTRIES);
-    return WI_HEADER + wi_blocks(n_nodes) * ne;
+    return g4c::HEADER + g4c::blocks_or_one(n_nodes) * ne;
 }
 
 extern "C" int g4c_weighted_integrals(const g4c_weighted_integrals_t *wi, const g4c_integral_program_t *prog, int64_t n_nodes, void *stream) {

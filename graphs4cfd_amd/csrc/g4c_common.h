@@ -127,6 +127,14 @@ __device__ __forceinline__ float act_t(float x) {
 __device__ __forceinline__ double nan_max(double a, double b) { return !(a < b) ? (b != b ? b : a) : b; }
 __device__ __forceinline__ double nan_min(double a, double b) { return !(a > b) ? (b != b ? b : a) : b; }
 
+// The sum over the 64 lanes of a wave, in every lane: a 6-level xor butterfly (both lanes of a pair form the same commutative sum).
+// The order is fixed by the lane numbers.  Every lane of the wave must be active.
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
+
 // The maximum over the 64 lanes of a wave, in every lane: fmax in the xor butterfly (one instruction per level), and NaN if any lane
 // held one — a ballot before the butterfly, one select after it, in place of a compare and a select at each of the six levels.  The
 // NaN is the canonical quiet one in every lane, whatever the payloads were.  Every lane of the wave must be active.

@@ -7,10 +7,11 @@
 //                              sender-side CSR, one thread per node in a fixed order.
 // The program, the forward's node body and the adjoint are the stencil operators' common ones (stencil_op.h, shared with mesh_jet.hip).
 // A node's sum is taken by ONE thread over its in-edges in CSR order, in fp32 without contraction: the bits are a function of the
-// data alone.  The norms follow the records' rule (rollout_record.hip): register accumulators, rows dealt gid, gid + grid, ..., a
-// xor butterfly per wave, the waves in order through LDS, one partial set per workgroup, a second one-workgroup launch.  No atomics.
+// data alone.  The norms are register accumulators over rows dealt gid, gid + grid, ..., reduced by the step-record core
+// (step_record.h): one partial set per workgroup, a second one-workgroup launch.  No atomics.
 #include "g4c_common.h"
 #include "stencil_op.h"
+#include "step_record.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
 // bits, and the fp64 weights differ from their restatement by the library's square root and division at most.
@@ -19,8 +20,9 @@
 namespace {
 
 constexpr int MG_THREADS = ST_THREADS;
-constexpr int MG_HEADER = 8;                 // scratch[0]: the step whose partials follow (-1: none); the partials start at 64 bytes
 constexpr int NSTAT = G4C_DERIVED_NSTAT;
+// scratch (step_record.h): the header, then [workgroup][nd][NSTAT]; of every column's set one position is a maximum
+using mg_policy = g4c::max_at<NSTAT, G4C_DERIVED_MAX_ABS>;
 constexpr int MAX_USED = gradient_traits::MAX_USED;
 using mg_prog_t = stencil_prog_t<MAX_USED>;          // (read from the kernel arguments: in scalar registers, so it is kept small)
 
@@ -128,42 +130,6 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_gradient_weights_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------ per step
-__device__ __forceinline__ double mg_combine(int j, double a, double b) { return j % NSTAT == G4C_DERIVED_MAX_ABS ? g4c::nan_max(a, b) : a + b; }
-
-// The workgroup's 256 sets of nstat (<= MAX_COLS * NSTAT) values -> one set at dst: rec_block_reduce of rollout_record.hip with a
-// run-time count (the loops are unrolled over the maximum and guarded by a wave-uniform test: every index is a compile-time one).
-// As there, the maximum carries a NaN through every stage (g4c::nan_max, and g4c::wave_nan_max in the butterfly).
-__device__ __forceinline__ void mg_block_reduce(double (&a)[MAX_COLS * NSTAT], int nstat, double *__restrict__ dst) {
-    __shared__ double part[MG_THREADS / 64][MAX_COLS * NSTAT];
-#pragma unroll
-    for (int j = 0; j < MAX_COLS * NSTAT; ++j) {
-        if (j < nstat) {
-            double x = a[j];
-            if (j % NSTAT == G4C_DERIVED_MAX_ABS) {
-                x = g4c::wave_nan_max(x);
-            } else {
-#pragma unroll
-                for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-            }
-            a[j] = x;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < MAX_COLS * NSTAT; ++j)
-            if (j < nstat) part[wave][j] = a[j];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nstat) {
-        const int j = threadIdx.x;
-        double x = part[0][j];
-#pragma unroll
-        for (int w = 1; w < MG_THREADS / 64; ++w) x = mg_combine(j, x, part[w][j]);
-        dst[j] = x;
-    }
-}
-
 template <int DIM, int NU, bool STATS>
 __global__ __launch_bounds__(MG_THREADS) void mesh_derived_kernel(const float *__restrict__ x, const g4c_mesh_derived_t d,
                                                                  const mg_prog_t p, long long n_nodes) {
@@ -172,10 +138,8 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_derived_kernel(const float *_
     const bool live = t >= 0 && t < d.max_steps;
     // every record address below is formed from a checked t
     float *snap = nullptr;
-    if (d.snap && t >= 0 && d.every > 0 && (t + 1) % d.every == 0) {
-        const int slot = (t + 1) / d.every - 1;
-        if (slot < d.n_snap) snap = d.snap + (long long)slot * n_nodes * nd;
-    }
+    int slot;
+    if (d.snap && t >= 0 && d.every > 0 && g4c::snapshot_slot(t, d.every, d.n_snap, slot)) snap = d.snap + (long long)slot * n_nodes * nd;
     const bool stats = STATS && live;
     __shared__ float mine[NU * DIM][MG_THREADS];
     double acc[STATS ? MAX_COLS * NSTAT : 1];
@@ -209,36 +173,17 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_derived_kernel(const float *_
     }
     if constexpr (STATS) {
         // (`stats` is the same in every workgroup: nothing in this launch writes the step index)
-        if (stats) mg_block_reduce(acc, nd * NSTAT, d.scratch + MG_HEADER + (long long)blockIdx.x * (nd * NSTAT));
-        if (gid == 0) d.scratch[0] = stats ? (double)t : -1.0;
+        if (stats) g4c::block_reduce<mg_policy>(acc, nd * NSTAT, g4c::partials(d.scratch, blockIdx.x, nd * NSTAT));
+        if (gid == 0) g4c::post_step(d.scratch, stats, t);
     }
-}
-
-// The workgroups' partials -> stats[t], one workgroup, behind the launch above on the same stream (rollout_record_stats_kernel's
-// order: thread i adds the partials of workgroups i, i + 256, ..., then the same reduction).  stats[t] is overwritten.
-__global__ __launch_bounds__(MG_THREADS) void mesh_derived_stats_kernel(const double *__restrict__ scratch, int n_blocks, int nd,
-                                                                       double *__restrict__ stats, int max_steps) {
-    const double tt = scratch[0];
-    if (!(tt >= 0.0 && tt < (double)max_steps)) return;
-    const int nstat = nd * NSTAT;
-    double acc[MAX_COLS * NSTAT];
-#pragma unroll
-    for (int j = 0; j < MAX_COLS * NSTAT; ++j) acc[j] = 0.0;
-    for (int b = threadIdx.x; b < n_blocks; b += MG_THREADS) {
-        const double *q = scratch + MG_HEADER + (long long)b * nstat;
-#pragma unroll
-        for (int j = 0; j < MAX_COLS * NSTAT; ++j)
-            if (j < nstat) acc[j] = mg_combine(j, acc[j], q[j]);
-    }
-    mg_block_reduce(acc, nstat, stats + (long long)(int)tt * nstat);
 }
 
 template <int DIM, int NU>
 void derived_launch(const float *x, const g4c_mesh_derived_t &d, const mg_prog_t &p, long long n_nodes, hipStream_t s) {
-    const int blocks = (int)stencil_blocks(n_nodes);
+    const int blocks = (int)g4c::blocks_or_one(n_nodes);
     if (d.stats) {
         mesh_derived_kernel<DIM, NU, true><<<dim3((unsigned)blocks), dim3(MG_THREADS), 0, s>>>(x, d, p, n_nodes);
-        mesh_derived_stats_kernel<<<dim3(1), dim3(MG_THREADS), 0, s>>>(d.scratch, blocks, p.nd, d.stats, d.max_steps);
+        g4c::partials_kernel<mg_policy, MAX_COLS, false><<<dim3(1), dim3(MG_THREADS), 0, s>>>(d.scratch, blocks, p.nd, d.stats, d.max_steps);
     } else {
         mesh_derived_kernel<DIM, NU, false><<<dim3((unsigned)blocks), dim3(MG_THREADS), 0, s>>>(x, d, p, n_nodes);
     }
@@ -272,7 +217,7 @@ extern "C" int g4c_mesh_gradient_weights(const int32_t *off, const int32_t *perm
 extern "C" int64_t g4c_mesh_derived_scratch_doubles(int64_t n_nodes, int32_t nd) {
     G4C_REQUIRE(n_nodes >= 0 && nd >= 1, G4C_EINVAL, "g4c_mesh_derived_scratch_doubles: bad sizes n_nodes=%lld nd=%d", (long long)n_nodes, nd);
     G4C_REQUIRE(nd <= MAX_COLS, G4C_EUNSUPPORTED, "g4c_mesh_derived_scratch_doubles: nd=%d columns (1 .. %d are supported)", nd, MAX_COLS);
-    return MG_HEADER + stencil_blocks(n_nodes) * nd * NSTAT;
+    return g4c::HEADER + g4c::blocks_or_one(n_nodes) * nd * NSTAT;
 }
 
 extern "C" int g4c_mesh_derived(const float *x, const g4c_mesh_derived_t *d, const g4c_derived_program_t *prog, int64_t n_nodes,

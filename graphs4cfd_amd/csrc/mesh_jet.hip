@@ -228,7 +228,7 @@ extern "C" int g4c_mesh_jet(const float *x, int32_t x_ld, int32_t nf, int32_t di
     G4C_REQUIRE(n_entries == 0 || (c && src), G4C_EINVAL, "%s: null pointer", me);
     g4c::DeviceGuard on_device(x);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)stencil_blocks(n_nodes)), block(JT_THREADS);
+    const dim3 grid((unsigned)g4c::blocks_or_one(n_nodes)), block(JT_THREADS);
     launch_nu<MAX_USED>(nu, [&](auto NU) {
         if (dim == 2)
             mesh_jet_kernel<2, decltype(NU)::value><<<grid, block, 0, s>>>(x, x_ld, c, src, off, u, n_nodes, out);

@@ -13,6 +13,7 @@
 #include "g4c_common.h"
 #include "point_fit.h"
 #include "knn_periodic.h"
+#include "step_record.h"
 
 // No contraction anywhere in this file: every product is rounded before it is added, so a plain host loop reproduces the per-step
 // bits, and the fp64 coefficients differ from their restatement by the library's square root and division at most.
@@ -20,8 +21,7 @@
 
 namespace {
 
-constexpr int PS_THREADS = 256;
-constexpr int PS_MAX_BLOCKS = 1024;          // as the records: 4 workgroups of 256 per CU on 256 CUs
+constexpr int PS_THREADS = g4c::THREADS;          // the per-step launches take g4c::blocks(items) workgroups (step_record.h)
 constexpr int PS_MAX_K = G4C_SAMPLE_MAX_K;
 constexpr int PS_CHUNK = 4;                  // columns one thread sums: nf = 3 is one chunk, a whole target ceil(F / 4) per point
 
@@ -98,10 +98,9 @@ __global__ __launch_bounds__(PS_THREADS) void sample_points_kernel(const float *
     const int t = s.step ? s.step[0] : -1;
     // the slot address is formed from a checked t
     float *series = nullptr;
-    if (s.series && t >= 0 && t < s.max_steps && s.every > 0 && (t + 1) % s.every == 0) {
-        const int slot = (t + 1) / s.every - 1;
-        if (slot < s.n_slots) series = s.series + (long long)slot * n_points * F;
-    }
+    int slot;
+    if (s.series && t >= 0 && t < s.max_steps && s.every > 0 && g4c::snapshot_slot(t, s.every, s.n_slots, slot))
+        series = s.series + (long long)slot * n_points * F;
     const int n_chunks = (F + PS_CHUNK - 1) / PS_CHUNK;
     const long long items = n_points * n_chunks;
     const long long stride = (long long)gridDim.x * PS_THREADS;
@@ -258,9 +257,7 @@ extern "C" int g4c_sample_points(const float *x, const g4c_sample_points_t *sp, 
     g4c_sample_points_t d = *sp;
     if (d.every == 0 || d.n_slots == 0) d.series = nullptr;
     const long long items = (long long)n_points * ((d.nf + PS_CHUNK - 1) / PS_CHUNK);
-    long long blocks = (items + PS_THREADS - 1) / PS_THREADS;
-    if (blocks > PS_MAX_BLOCKS) blocks = PS_MAX_BLOCKS;
-    sample_points_kernel<<<dim3((unsigned)blocks), dim3(PS_THREADS), 0, s>>>(x, d, (long long)n_points);
+    sample_points_kernel<<<dim3((unsigned)g4c::blocks(items)), dim3(PS_THREADS), 0, s>>>(x, d, (long long)n_points);
     return g4c::check_launch(me);
 }
 
@@ -282,8 +279,6 @@ extern "C" int g4c_sample_points_adjoint(const float *gy, const int32_t *in_off,
     hipStream_t s = (hipStream_t)stream;
     if (n_points == 0) in_off = nullptr;
     const long long items = (long long)n_nodes * ((nf + PS_CHUNK - 1) / PS_CHUNK);
-    long long blocks = (items + PS_THREADS - 1) / PS_THREADS;
-    if (blocks > PS_MAX_BLOCKS) blocks = PS_MAX_BLOCKS;
-    sample_points_adjoint_kernel<<<dim3((unsigned)blocks), dim3(PS_THREADS), 0, s>>>(gy, in_off, in_pt, in_coef, nf, (long long)n_nodes, gx);
+    sample_points_adjoint_kernel<<<dim3((unsigned)g4c::blocks(items)), dim3(PS_THREADS), 0, s>>>(gy, in_off, in_pt, in_coef, nf, (long long)n_nodes, gx);
     return g4c::check_launch(me);
 }

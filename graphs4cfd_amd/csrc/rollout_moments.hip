@@ -5,12 +5,11 @@
 // depend on the data alone.  No LDS, no scratch, nothing between workgroups.  The extrema carry a NaN sample (g4c::nan_min / nan_max)
 // and keep it until the window's origin is rewritten.
 #include "g4c_common.h"
+#include "step_record.h"
 
 namespace {
 
-constexpr int MOM_THREADS = 256;
-// as the records (rollout_record.hip): 4 workgroups of 256 per CU on 256 CUs; beyond 262 144 rows a thread takes several
-constexpr int MOM_MAX_BLOCKS = 1024;
+constexpr int MOM_THREADS = g4c::THREADS;          // a launch takes g4c::blocks(n_nodes) workgroups (step_record.h)
 
 template <int NF, bool SUB>
 __global__ __launch_bounds__(MOM_THREADS) void rollout_moments_kernel(const float *__restrict__ pred, const g4c_rollout_moments_t m,
@@ -82,8 +81,7 @@ __global__ __launch_bounds__(MOM_THREADS) void rollout_moments_kernel(const floa
 
 template <int NF>
 void mom_launch(const float *pred, const g4c_rollout_moments_t &m, const int *step, long long n_nodes, hipStream_t s) {
-    long long b = (n_nodes + MOM_THREADS - 1) / MOM_THREADS;
-    b = b > MOM_MAX_BLOCKS ? MOM_MAX_BLOCKS : b;
+    const long long b = g4c::blocks(n_nodes);
     if (m.sub)
         rollout_moments_kernel<NF, true><<<dim3((unsigned)b), dim3(MOM_THREADS), 0, s>>>(pred, m, step, n_nodes);
     else

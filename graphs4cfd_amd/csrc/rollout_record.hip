@@ -3,64 +3,14 @@
 // prediction's rows at a list of probe nodes, and per-field error sums of the step against a target, all addressed by the step
 // index the launch reads on the device (so a captured launch records every replay in its own slot).
 #include "g4c_common.h"
+#include "step_record.h"
 
 namespace {
 
-constexpr int REC_THREADS = 256;
-// Rows are dealt to at most this many workgroups of 256 (4 per CU on 256 CUs): beyond 262 144 rows a thread takes several, and the
-// statistics' partials (one set per workgroup) stay a few hundred KB at any mesh size.  The grid — and with it the order of every
-// sum — is a function of n_nodes alone.
-constexpr int REC_MAX_BLOCKS = 1024;
-// scratch: [0] the step index whose partials follow (-1: none — the step was outside the record), [1 .. 8) unused (the partials start
-// on a 64-byte boundary), then [workgroup][nf][G4C_REC_NSTAT]
-constexpr int REC_HEADER = 8;
+constexpr int REC_THREADS = g4c::THREADS;
 constexpr int NSTAT = G4C_REC_NSTAT;
-
-inline long long rec_blocks(long long n_nodes) {
-    const long long b = (n_nodes + REC_THREADS - 1) / REC_THREADS;
-    return b < 1 ? 1 : (b > REC_MAX_BLOCKS ? REC_MAX_BLOCKS : b);
-}
-
-__device__ __forceinline__ double rec_combine(int j, double a, double b) {
-    return j % NSTAT == G4C_REC_MAX_ABS_ERR ? g4c::nan_max(a, b) : a + b;
-}
-
-// The workgroup's 256 sets of NF * NSTAT values -> one set at dst.  A 6-level xor butterfly inside each wave (both lanes of a pair
-// form the same commutative sum or maximum, so every lane ends with the wave's value), then the four waves in order: the order is
-// fixed by the lane and wave numbers, never by arrival.  Everything stays in registers (compile-time indices) and 4 * NF * 48 bytes
-// of LDS.  The maximum carries a NaN at any node through every stage: g4c::nan_max in the thread's loop, between the four waves and
-// over the partials of the workgroups, g4c::wave_nan_max in the butterfly (fmax at its six levels, and NaN if a ballot found one in
-// any lane — cheaper than a compare and a select per level).  After a NaN every lane of a wave holds the same canonical quiet NaN;
-// of two NaNs of different waves or partials the one kept depends on the order of the arguments, which is fixed: two runs give the
-// same bits.
-template <int NF>
-__device__ __forceinline__ void rec_block_reduce(double (&a)[NF * NSTAT], double *__restrict__ dst) {
-    __shared__ double part[REC_THREADS / 64][NF * NSTAT];
-#pragma unroll
-    for (int j = 0; j < NF * NSTAT; ++j) {
-        double x = a[j];
-        if (j % NSTAT == G4C_REC_MAX_ABS_ERR) {
-            x = g4c::wave_nan_max(x);
-        } else {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        }
-        a[j] = x;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < NF * NSTAT; ++j) part[wave][j] = a[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < NF * NSTAT) {
-        const int j = threadIdx.x;
-        double x = part[0][j];
-#pragma unroll
-        for (int w = 1; w < REC_THREADS / 64; ++w) x = rec_combine(j, x, part[w][j]);
-        dst[j] = x;
-    }
-}
+// scratch (step_record.h): the header, then [workgroup][nf][G4C_REC_NSTAT]; of every field's set one position is a maximum
+using rec_policy = g4c::max_at<NSTAT, G4C_REC_MAX_ABS_ERR>;
 
 // NF > 0: nf == NF, rec.target is given and the statistics are formed (NF * NSTAT fp64 accumulators per thread, in registers);
 // NF == 0: any nf, no statistics — the launch of g4c_rollout_advance with the snapshot slot and the probes added.
@@ -73,10 +23,8 @@ __global__ __launch_bounds__(REC_THREADS) void rollout_advance_record_kernel(
     // a step index outside [0, max_steps) leaves no record at all: every record address below is formed from a checked t
     const bool live = t >= 0 && t < rec.max_steps;
     float *snap = nullptr;
-    if (live && rec.every > 0 && (t + 1) % rec.every == 0) {
-        const int slot = (t + 1) / rec.every - 1;
-        if (slot < rec.n_snap) snap = rec.snap + (long long)slot * n_nodes * nf;
-    }
+    int slot;
+    if (live && rec.every > 0 && g4c::snapshot_slot(t, rec.every, rec.n_snap, slot)) snap = rec.snap + (long long)slot * n_nodes * nf;
     const bool stats = NF > 0 && live;
     double acc[NF ? NF * NSTAT : 1];
 #pragma unroll
@@ -125,8 +73,8 @@ __global__ __launch_bounds__(REC_THREADS) void rollout_advance_record_kernel(
     }
     if constexpr (NF > 0) {
         // (`stats` is the same in every workgroup: all of them read the step index before anybody bumps it)
-        if (stats) rec_block_reduce<NF>(acc, rec.scratch + REC_HEADER + (long long)blockIdx.x * (NF * NSTAT));
-        if (gid == 0) rec.scratch[0] = stats ? (double)t : -1.0;
+        if (stats) g4c::block_reduce<rec_policy>(acc, NF * NSTAT, g4c::partials(rec.scratch, blockIdx.x, NF * NSTAT));
+        if (gid == 0) g4c::post_step(rec.scratch, stats, t);
     }
     // probes: pred's rows at the listed nodes (pred is only read by this launch); a row outside the mesh writes nothing
     if (live && rec.n_probe > 0) {
@@ -146,33 +94,13 @@ __global__ __launch_bounds__(REC_THREADS) void rollout_advance_record_kernel(
     }
 }
 
-// The workgroups' partials -> stats[t], one workgroup, behind the launch above on the same stream (the launch boundary is what makes
-// the partials visible: the alternative — the last workgroup under a fence — puts a write-back of every XCD's L2 into each of
-// several hundred workgroups, which rollout_advance_kernel measured at twice this launch).  Thread i adds the partials of workgroups
-// i, i + 256, ... in order, then the same reduction as above: the order depends on the number of workgroups alone.
-template <int NF>
-__global__ __launch_bounds__(REC_THREADS) void rollout_record_stats_kernel(
-    const double *__restrict__ scratch, int n_blocks, double *__restrict__ stats, int max_steps) {
-    const double tt = scratch[0];
-    if (!(tt >= 0.0 && tt < (double)max_steps)) return;
-    double acc[NF * NSTAT];
-#pragma unroll
-    for (int j = 0; j < NF * NSTAT; ++j) acc[j] = 0.0;
-    for (int b = threadIdx.x; b < n_blocks; b += REC_THREADS) {
-        const double *p = scratch + REC_HEADER + (long long)b * (NF * NSTAT);
-#pragma unroll
-        for (int j = 0; j < NF * NSTAT; ++j) acc[j] = rec_combine(j, acc[j], p[j]);
-    }
-    rec_block_reduce<NF>(acc, stats + (long long)(int)tt * (NF * NSTAT));
-}
-
 template <int NF>
 void rec_launch(float *field, int field_cols, const float *pred, int nf, const g4c_rollout_rec_t &rec, int *step, long long n_nodes,
                 hipStream_t s) {
-    const int blocks = (int)rec_blocks(n_nodes);
+    const int blocks = (int)g4c::blocks_or_one(n_nodes);
     rollout_advance_record_kernel<NF><<<dim3((unsigned)blocks), dim3(REC_THREADS), 0, s>>>(field, field_cols, pred, nf, rec, step, n_nodes);
     if constexpr (NF > 0)
-        rollout_record_stats_kernel<NF><<<dim3(1), dim3(REC_THREADS), 0, s>>>(rec.scratch, blocks, rec.stats, rec.max_steps);
+        g4c::partials_kernel<rec_policy, NF, true><<<dim3(1), dim3(REC_THREADS), 0, s>>>(rec.scratch, blocks, NF, rec.stats, rec.max_steps);
 }
 
 }  // namespace
@@ -180,7 +108,7 @@ void rec_launch(float *field, int field_cols, const float *pred, int nf, const g
 extern "C" int64_t g4c_rollout_record_scratch_doubles(int64_t n_nodes, int32_t nf) {
     G4C_REQUIRE(n_nodes >= 0 && nf >= 1, G4C_EINVAL, "g4c_rollout_record_scratch_doubles: bad sizes n_nodes=%lld nf=%d", (long long)n_nodes, nf);
     G4C_REQUIRE(nf <= 8, G4C_EUNSUPPORTED, "g4c_rollout_record_scratch_doubles: statistics of nf=%d fields (1 .. 8 are supported)", nf);
-    return REC_HEADER + rec_blocks(n_nodes) * nf * NSTAT;
+    return g4c::HEADER + g4c::blocks_or_one(n_nodes) * nf * NSTAT;
 }
 
 extern "C" int g4c_rollout_advance_record(float *field, int32_t field_cols, const float *pred, int32_t nf, const g4c_rollout_rec_t *rec,

@@ -5,12 +5,11 @@
 // accumulator owned by one thread: the bits depend on the data and the table alone.  No sin / cos, no LDS, no scratch, nothing
 // between workgroups.
 #include "g4c_common.h"
+#include "step_record.h"
 
 namespace {
 
-constexpr int SPEC_THREADS = 256;
-// as the moments (rollout_moments.hip): 4 workgroups of 256 per CU on 256 CUs; beyond 262 144 rows a thread takes several
-constexpr int SPEC_MAX_BLOCKS = 1024;
+constexpr int SPEC_THREADS = g4c::THREADS;          // a launch takes g4c::blocks(n_nodes) workgroups a group of bins (step_record.h)
 // bins of one thread: blockIdx.y walks the groups of SPEC_BINS bins (the last one may be shorter), so a 10k-node mesh with K = 32
 // still has 160 workgroups, and a thread holds 2 * SPEC_BINS accumulators of one field between its loads and its stores
 constexpr int SPEC_BINS = 8;
@@ -123,8 +122,7 @@ extern "C" int g4c_rollout_spectrum(const float *x, int32_t nf, const g4c_rollou
     G4C_REQUIRE(s->n_bins <= 64, G4C_EUNSUPPORTED, "%s: n_bins=%d frequencies (1 .. 64 are supported)", me, s->n_bins);
     if (n_nodes == 0) return G4C_OK;
     g4c::DeviceGuard on_device(step);
-    long long b = (n_nodes + SPEC_THREADS - 1) / SPEC_THREADS;
-    b = b > SPEC_MAX_BLOCKS ? SPEC_MAX_BLOCKS : b;
+    const long long b = g4c::blocks(n_nodes);
     const unsigned groups = (unsigned)((s->n_bins + SPEC_BINS - 1) / SPEC_BINS);
     rollout_spectrum_kernel<<<dim3((unsigned)b, groups), dim3(SPEC_THREADS), 0, (hipStream_t)stream>>>(x, *s, s->tw, step, nf, n_nodes);
     return g4c::check_launch(me);

@@ -10,20 +10,15 @@
 #include <type_traits>
 
 #include "g4c_common.h"
+#include "step_record.h"
 
 // No contraction in anything below (nor in the file that includes this): every product is rounded before it is added.
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int ST_THREADS = 256;
-constexpr int ST_MAX_BLOCKS = 1024;          // as the records: 4 workgroups of 256 per CU on 256 CUs
+constexpr int ST_THREADS = g4c::THREADS;          // the forward and the adjoint launch g4c::blocks_or_one(n_nodes) workgroups (step_record.h)
 constexpr int MAX_COLS = G4C_DERIVED_MAX_COLS, MAX_TERMS = G4C_DERIVED_MAX_TERMS;
-
-inline long long stencil_blocks(long long n_nodes) {
-    const long long b = (n_nodes + ST_THREADS - 1) / ST_THREADS;
-    return b < 1 ? 1 : (b > ST_MAX_BLOCKS ? ST_MAX_BLOCKS : b);
-}
 
 // What differs between the operators:
 //   MAX_USED, MAX_W   distinct fields one program may differentiate, and the widest row (they size the program);
@@ -317,7 +312,7 @@ int stencil_adjoint(const char *me, long long limit, const float *gy, const g4c_
     g4c::DeviceGuard on_device(gx);
     hipStream_t s = (hipStream_t)stream;
     if (n_entries == 0) w = nullptr;
-    const dim3 grid((unsigned)stencil_blocks(n_nodes)), block(ST_THREADS);
+    const dim3 grid((unsigned)g4c::blocks_or_one(n_nodes)), block(ST_THREADS);
     launch_nu<Traits::MAX_USED>(nu, [&](auto NU) {
         if (dim == 2)
             stencil_adjoint_kernel<W2, decltype(NU)::value, Traits><<<grid, block, 0, s>>>(gy, w, off, out_w, out_dst, out_off, t, n_nodes, gx);

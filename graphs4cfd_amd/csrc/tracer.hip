@@ -9,6 +9,7 @@
 #include "g4c_common.h"
 #include "point_fit.h"
 #include "knn_periodic.h"
+#include "step_record.h"
 
 #include <cmath>
 
@@ -18,8 +19,7 @@
 
 namespace {
 
-constexpr int TR_THREADS = 256;
-constexpr int TR_MAX_BLOCKS = 1024;          // as the samples: 4 workgroups of 256 per CU on 256 CUs
+constexpr int TR_THREADS = g4c::THREADS;          // a launch takes g4c::blocks(n_particles) workgroups (step_record.h)
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }          // (false for NaN)
 
@@ -82,10 +82,9 @@ __global__ __launch_bounds__(TR_THREADS) void tracer_advance_kernel(const g4c_tr
     const bool in_range = t >= 0 && t < s.max_steps;
     // the slot address is formed from a checked t
     float *series = nullptr;
-    if (s.series && in_range && s.every > 0 && (t + 1) % s.every == 0) {
-        const int slot = (t + 1) / s.every - 1;
-        if (slot < s.n_slots) series = s.series + (long long)slot * n_particles * DIM;
-    }
+    int slot;
+    if (s.series && in_range && s.every > 0 && g4c::snapshot_slot(t, s.every, s.n_slots, slot))
+        series = s.series + (long long)slot * n_particles * DIM;
     const long long stride = (long long)gridDim.x * TR_THREADS;
     for (long long p = (long long)blockIdx.x * TR_THREADS + threadIdx.x; p < n_particles; p += stride) {
         float q[DIM];
@@ -225,10 +224,9 @@ __global__ __launch_bounds__(TR_THREADS) void tracer_advance_periodic_kernel(con
     const bool in_range = t >= 0 && t < s.max_steps;
     // the slot address is formed from a checked t
     float *series = nullptr;
-    if (s.series && in_range && s.every > 0 && (t + 1) % s.every == 0) {
-        const int slot = (t + 1) / s.every - 1;
-        if (slot < s.n_slots) series = s.series + (long long)slot * n_particles * DIM;
-    }
+    int slot;
+    if (s.series && in_range && s.every > 0 && g4c::snapshot_slot(t, s.every, s.n_slots, slot))
+        series = s.series + (long long)slot * n_particles * DIM;
     const long long stride = (long long)gridDim.x * TR_THREADS;
     for (long long p = (long long)blockIdx.x * TR_THREADS + threadIdx.x; p < n_particles; p += stride) {
         float q[DIM];
@@ -356,9 +354,7 @@ extern "C" int g4c_tracer_advance_periodic(const g4c_tracer_periodic_t *tr, int6
     if (d.base.every == 0 || d.base.n_slots == 0) d.base.series = nullptr;
     for (int a = d.base.dim; a < 3; ++a) { d.period[a] = 0.f; d.cell[a] = 1.0; }
     const bool heun = d.base.scheme == G4C_TRACER_HEUN;
-    long long blocks = (n_particles + TR_THREADS - 1) / TR_THREADS;
-    if (blocks > TR_MAX_BLOCKS) blocks = TR_MAX_BLOCKS;
-    const dim3 grid((unsigned)blocks), block(TR_THREADS);
+    const dim3 grid((unsigned)g4c::blocks(n_particles)), block(TR_THREADS);
 #define G4C_TRACERP_LAUNCH(DIM_, KM_, SCHEME_) tracer_advance_periodic_kernel<DIM_, KM_, SCHEME_><<<grid, block, 0, s>>>(d, (long long)n_particles)
 #define G4C_TRACERP_SCHEME(DIM_, KM_)                                    \
     do {                                                                 \
@@ -382,9 +378,7 @@ extern "C" int g4c_tracer_advance(const g4c_tracer_t *tr, int64_t n_nodes, int64
     hipStream_t s = (hipStream_t)stream;
     g4c_tracer_t d = *tr;
     if (d.every == 0 || d.n_slots == 0) d.series = nullptr;
-    long long blocks = (n_particles + TR_THREADS - 1) / TR_THREADS;
-    if (blocks > TR_MAX_BLOCKS) blocks = TR_MAX_BLOCKS;
-    const dim3 grid((unsigned)blocks), block(TR_THREADS);
+    const dim3 grid((unsigned)g4c::blocks(n_particles)), block(TR_THREADS);
 #define G4C_TRACER_LAUNCH(DIM_, KM_, SCHEME_) tracer_advance_kernel<DIM_, KM_, SCHEME_><<<grid, block, 0, s>>>(d, (long long)n_particles)
 #define G4C_TRACER_SCHEME(DIM_, KM_)                                    \
     do {                                                                \

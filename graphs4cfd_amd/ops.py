@@ -480,13 +480,18 @@ def rollout_advance(field: Tensor, pred: Tensor, outputs: Tensor, step: Tensor, 
                                        out_ld, _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def _scratch_doubles(fn: str, n_nodes: int, count: int) -> int:
+    """The library's own size (g4c_*_scratch_doubles) of a step-record scratch: a header and one partial set per workgroup."""
+    n = int(getattr(_lib.load(), fn)(int(n_nodes), int(count)))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
 def rollout_record_scratch(n_nodes: int, nf: int, device) -> Tensor:
     """The `scratch` buffer of rollout_advance_record's statistics for a mesh of n_nodes and nf fields (the size is the library's:
     g4c_rollout_record_scratch_doubles)."""
-    n = int(_lib.load().g4c_rollout_record_scratch_doubles(int(n_nodes), int(nf)))
-    if n < 0:
-        _lib.check(n)
-    return torch.zeros(n, dtype=torch.float64, device=device)
+    return torch.zeros(_scratch_doubles("g4c_rollout_record_scratch_doubles", n_nodes, nf), dtype=torch.float64, device=device)
 
 
 def rollout_advance_record(field: Tensor, pred: Tensor, step: Tensor, nf: int, max_steps: int, *, snap: Optional[Tensor] = None,
@@ -567,9 +572,7 @@ def rollout_advance_record(field: Tensor, pred: Tensor, step: Tensor, nf: int, m
     lib = _lib.load()
     dev = _lib.require_hip(field, pred, step, snap, probe_rows, probe_out, target, mask, stats, scratch)
     if target is not None:
-        need = int(lib.g4c_rollout_record_scratch_doubles(n_nodes, nf))
-        if need < 0:
-            _lib.check(need)
+        need = _scratch_doubles("g4c_rollout_record_scratch_doubles", n_nodes, nf)
         if int(scratch.numel()) < need:
             raise ValueError(f"scratch: {what}: {need} doubles for {n_nodes} nodes x {nf} fields, got {int(scratch.numel())}")
     rec = _lib.g4c_rollout_rec_t(max_steps=max_steps, snap=_lib.ptr(snap), every=every, n_snap=0 if snap is None else int(snap.size(0)),
@@ -997,10 +1000,7 @@ def _stencil_adjoint(what, fn, dim, order, name, gy, off, table, out_off, out_ta
 
 def mesh_derived_scratch(n_nodes: int, nd: int, device) -> Tensor:
     """The `scratch` buffer of mesh_derived's statistics for a mesh of n_nodes and nd columns (g4c_mesh_derived_scratch_doubles)."""
-    n = int(_lib.load().g4c_mesh_derived_scratch_doubles(int(n_nodes), int(nd)))
-    if n < 0:
-        _lib.check(n)
-    return torch.zeros(n, dtype=torch.float64, device=device)
+    return torch.zeros(_scratch_doubles("g4c_mesh_derived_scratch_doubles", n_nodes, nd), dtype=torch.float64, device=device)
 
 
 def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: Tensor, *, step: Optional[Tensor] = None, every: int = 0,
@@ -1611,10 +1611,7 @@ def _integrals_scratch_doubles(n_nodes: int, ne: int) -> int:
 
 def weighted_integrals_scratch(n_nodes: int, ne: int, device) -> Tensor:
     """The `scratch` buffer of `weighted_integrals` for n_nodes rows and ne entries (g4c_weighted_integrals_scratch_doubles)."""
-    n = int(_lib.load().g4c_weighted_integrals_scratch_doubles(int(n_nodes), int(ne)))
-    if n < 0:
-        _lib.check(n)
-    return torch.zeros(n, dtype=torch.float64, device=device)
+    return torch.zeros(_scratch_doubles("g4c_weighted_integrals_scratch_doubles", n_nodes, ne), dtype=torch.float64, device=device)
 
 
 def _integrals_source(what: str, x, name: str, n_nodes: Optional[int], nz: int, x_step: int, max_steps: int):

@@ -520,7 +520,7 @@ int g4c_rollout_advance(float *field, int32_t field_cols, const float *pred, int
  * stats[t][f] = { sum d^2, sum |d|, max |d|, sum y, sum y^2, sum |d| over the rows with mask != 0 } (y = the target), accumulated in
  * fp64 without floating-point atomics in an order that depends on (n_nodes, nf) alone: bit-identical between runs and between captured
  * and eager launches.  stats[t] is overwritten.  The workgroups' partials go through `scratch` and are combined by a second, one-
- * workgroup launch on the same stream (rollout_record_stats_kernel).
+ * workgroup launch on the same stream (g4c::partials_kernel, csrc/step_record.h).
  * NON-FINITE SAMPLES (the rule of every in-step diagnostic): (1) sums follow IEEE — NaN where a NaN or an Inf − Inf
  * entered; (2) an extremum over samples of which one is NaN IS NaN, at every stage of the reduction (±Inf are ordinary values): a
  * record never reads better than the rollout was; (3) masks select — a row outside `mask` contributes nothing to

@@ -12,7 +12,7 @@ its tests share.  Nothing here calls graphs4cfd_amd.
     tv = mu (sxx a_x + sxy a_y, sxy a_x + syy a_y); the moments r_x t_y − r_y t_x; wall = ((float)P, (float)(mu ((t̂_x sxx + t̂_y sxy) n̂_x
     + (t̂_x sxy + t̂_y syy) n̂_y))), t̂ = (−n̂_y, n̂_x).  mu == 0 skips the gradient: the viscous terms and the shear are 0.
 (c) `sum_plain`: numpy's fp64 sum per body; `sum_tree`: the kernel's own order — thread tid adds the items tid, tid + 256, ... of its
-    body in that order from 0, a xor butterfly 32, 16, .., 1 per wave of 64, the four waves added in order.
+    body in that order from 0, then the step-record core's workgroup reduction (tests/step_sum_ref.py).
 (d) `sum_bound`: the records' bound on a sum of n terms in any fixed order, 2 (n + 4) 2⁻⁵³ Σ|terms|.
 
 The lumped rule integrates the FORCE of a linear pressure exactly on any polygon (it is the trapezoid rule edge by edge).  The MOMENT's
@@ -24,9 +24,9 @@ from __future__ import annotations
 import numpy as np
 
 import gradient_ref as GR
+from step_sum_ref import THREADS, WAVE, _reduce          # noqa: F401
 
 F32, F64, I32 = np.float32, np.float64, np.int32
-THREADS, WAVE = 256, 64
 NAMES = ("Fp_x", "Fp_y", "Fv_x", "Fv_y", "Mp", "Mv")
 
 
@@ -168,19 +168,12 @@ def sum_plain(T: np.ndarray, body_offsets) -> np.ndarray:
 
 def sum_tree(T: np.ndarray, body_offsets) -> np.ndarray:
     out = np.zeros((len(body_offsets) - 1, T.shape[1]), F64)
-    lane = np.arange(THREADS)
     for b, (a, e) in enumerate(zip(body_offsets[:-1], body_offsets[1:])):
         acc = np.zeros((THREADS, T.shape[1]), F64)
         for w0 in range(int(a), int(e), THREADS):
             blk = T[w0:min(w0 + THREADS, int(e))]
             acc[:blk.shape[0]] = acc[:blk.shape[0]] + blk
-        for m in (32, 16, 8, 4, 2, 1):
-            acc = acc + acc[lane ^ m]
-        waves = acc[::WAVE]
-        s = waves[0]
-        for wv in range(1, THREADS // WAVE):
-            s = s + waves[wv]
-        out[b] = s
+        out[b] = _reduce(acc)
     return out
 
 

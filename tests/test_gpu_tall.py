@@ -432,7 +432,7 @@ def test_rollout_advance_record_probes_and_statistics_tall():
     and the error statistics.  Integer predictions and targets: every sum is exact in fp64 in any order, so stats[t] equals plain
     fp64 torch sums on the device bit for bit; the probe slot equals pred[probe_rows]; every other slot and row of stats keeps its
     pattern."""
-    RAN.append("rollout_advance_record_kernel<3>, rollout_record_stats_kernel<3>")
+    RAN.append("rollout_advance_record_kernel<3>, g4c::partials_kernel (3 fields)")
     n, nf, steps = RA_NODES, RA_NF, 700
     plane = n * nf
     cross = [2 ** 31 // (4 * plane), 2 ** 32 // (4 * plane), 2 ** 31 // plane]
