@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._args import Args, record_scratch_doubles
 from .plan import CsrPlan
 
 Tensor = torch.Tensor
@@ -179,23 +180,18 @@ class Source:
 
 # ---- argument checks of the helper launches below: shapes, strides and dtypes only (host metadata — never index VALUES, which would
 # synchronise the stream and break graph capture), and before require_hip, so that a malformed call is refused the same way with or
-# without a device.  TypeError for a dtype, ValueError for a shape; the message names the argument.
+# without a device.  The checks themselves live in _args.py (`Args`): a wrapper says what it expects of each argument, in the order it
+# blames them, and adds no check of its own that `Args` already has (DESIGN.md §5 "The wrapper checks").  A wrong dtype is a
+# TypeError in the wrappers down to rollout_* and in snapshot_*, a ValueError in the mesh_* / body_forces* / sample_* / tracer_advance /
+# voronoi_cells / weighted_integrals family (`Args(what, TypeError)` / `Args(what)`); a wrong shape is a ValueError everywhere; the
+# message names the argument first.  The three helpers below are the row-matrix, index and vector forms of the first group, whose
+# messages carry no function name.
+_plain = Args(None, TypeError)
+
+
 def _rows_f32(t: Tensor, name: str, cols: Optional[int] = None, min_rows: int = 0, min_cols: int = 0) -> Tensor:
     """A float32 [rows, cols] tensor the launch addresses as t[r * ld + c]: unit column stride, rows that do not overlap."""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    if t.dim() != 2:
-        raise ValueError(f"{name}: expected a 2-D tensor, got shape {tuple(t.shape)}")
-    if t.size(1) > 1 and t.stride(1) != 1:
-        raise ValueError(f"{name}: expected unit column stride, got strides {tuple(t.stride())}")
-    if t.size(0) > 1 and t.stride(0) < t.size(1):
-        raise ValueError(f"{name}: rows overlap (row stride {t.stride(0)} < {t.size(1)} columns)")
-    if cols is not None and int(t.size(1)) != cols:
-        raise ValueError(f"{name}: expected {cols} columns, got shape {tuple(t.shape)}")
-    if int(t.size(1)) < min_cols:
-        raise ValueError(f"{name}: expected at least {min_cols} columns, got shape {tuple(t.shape)}")
+    _plain.strided_rows(t, name, cols=cols, min_cols=min_cols)
     if int(t.size(0)) < min_rows:
         raise ValueError(f"{name}: expected at least {min_rows} rows, got shape {tuple(t.shape)}")
     return t
@@ -205,12 +201,7 @@ def _index_i32(t: Optional[Tensor], name: str, n: Optional[int] = None, at_least
     """An int32 index vector (contiguous, 1-D) of exactly `n` / at least `at_least` entries; None passes."""
     if t is None:
         return None
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.int32:
-        raise TypeError(f"{name}: expected int32, got {t.dtype}")
-    if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
-        raise ValueError(f"{name}: expected a contiguous 1-D tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    _plain.tensor(t, name, torch.int32, dim=1)
     if n is not None and t.numel() != n:
         raise ValueError(f"{name}: expected {n} entries, got {t.numel()}")
     if at_least is not None and t.numel() < at_least:
@@ -219,14 +210,8 @@ def _index_i32(t: Optional[Tensor], name: str, n: Optional[int] = None, at_least
 
 
 def _vector_f32(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
-    if t is None:
-        return None
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    if t.dim() != 1 or t.numel() != n or (n > 1 and t.stride(0) != 1):
-        raise ValueError(f"{name}: expected a contiguous vector of {n} entries, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if t is not None:
+        _plain.tensor(t, name, torch.float32, shape=(n,))
     return t
 
 
@@ -275,10 +260,7 @@ def segment_reduce(src: Tensor, csr: CsrPlan, mean: bool, act: int = _lib.ACT_NO
 
 def activation_(x: Tensor, act: int) -> Tensor:
     """In-place activation of a contiguous tensor (g4c_activation_inplace)."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise TypeError(f"x: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if not x.is_contiguous():
-        raise ValueError("x: activation_ needs a contiguous tensor")
+    Args("activation_", TypeError).tensor(x, "x", torch.float32)
     act = _act_arg(act, "act")
     lib = _lib.load()
     dev = _lib.require_hip(x)
@@ -298,8 +280,7 @@ def weighted_segment_mean(x: Tensor, x_idx32: Tensor, w: Tensor, csr: CsrPlan, o
         return _ag.weighted_segment_mean(x, x_idx32, w, csr)
     x = _f32_2d(x, "x")
     width = int(x.size(1))
-    if not torch.is_tensor(w) or w.dtype != torch.float32:
-        raise TypeError(f"w: expected a float32 tensor, got {getattr(w, 'dtype', type(w).__name__)}")
+    _plain.dtype(w, "w", torch.float32)
     w = w.reshape(-1).contiguous()
     _csr_arg(csr, "csr")
     if csr.perm is not None:
@@ -364,8 +345,7 @@ def edge_scalar_to_node_vector(e: Tensor, unit_inv: Tensor, n_nodes: int, k: int
     n_nodes, k = int(n_nodes), int(k)
     if n_nodes < 0 or k <= 0:
         raise ValueError(f"n_nodes / k: expected n_nodes >= 0 and k > 0, got {n_nodes}, {k}")
-    if not torch.is_tensor(unit_inv) or unit_inv.dtype != torch.float32:
-        raise TypeError(f"edgeUnitVectorInverse: expected a float32 tensor, got {getattr(unit_inv, 'dtype', type(unit_inv).__name__)}")
+    _plain.dtype(unit_inv, "edgeUnitVectorInverse", torch.float32)
     if unit_inv.numel() != n_nodes * 2 * k:
         raise ValueError(f"edgeUnitVectorInverse: expected {n_nodes} x 2 x {k} entries, got shape {tuple(unit_inv.shape)}")
     unit_inv = unit_inv.contiguous()
@@ -373,8 +353,7 @@ def edge_scalar_to_node_vector(e: Tensor, unit_inv: Tensor, n_nodes: int, k: int
     if int(e.size(0)) != n_nodes * k:
         raise ValueError(f"edge_attr: {int(e.size(0))} edges cannot be viewed as {n_nodes} nodes x {k} incoming edges")
     if out is not None:
-        if not torch.is_tensor(out) or out.dtype != torch.float32:
-            raise TypeError(f"out: expected a float32 tensor, got {getattr(out, 'dtype', type(out).__name__)}")
+        _plain.dtype(out, "out", torch.float32)
         if tuple(out.shape) != (n_nodes, 2 * n_feat) or out.stride(1) != 1:
             raise ValueError(f"out must be a float32 [{n_nodes}, {2 * n_feat}] tensor with unit column stride")
     lib = _lib.load()
@@ -450,15 +429,10 @@ def layer_norm(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], eps: 
 
 def rollout_advance(field: Tensor, pred: Tensor, outputs: Tensor, step: Tensor, nf: int) -> None:
     nf = int(nf)
+    a = Args("rollout_advance", TypeError)
     for t, name in ((field, "field"), (pred, "pred"), (outputs, "outputs")):
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise TypeError(f"{name}: expected a float32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: rollout_advance needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
-    if not torch.is_tensor(step) or step.dtype != torch.int32:
-        raise TypeError("step: rollout_advance: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
-    if step.dim() != 1 or step.numel() < 2 or not step.is_contiguous():
-        raise ValueError("step: rollout_advance: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+        a.tensor(t, name, torch.float32)
+    a.step_index(step, entries=2)          # ([step index, the launch's ticket counter (zero)])
     if field.dim() != 2 or nf <= 0 or int(field.size(1)) < nf:
         raise ValueError(f"field: expected [n_nodes, >= nf = {nf}], got shape {tuple(field.shape)}")
     n_nodes = int(field.size(0))
@@ -507,68 +481,41 @@ def rollout_advance_record(field: Tensor, pred: Tensor, step: Tensor, nf: int, m
     rollout_record_scratch."""
     nf, max_steps, every = int(nf), int(max_steps), int(every)
     what = "rollout_advance_record"
-
-    def dense(t, name, dtypes, shape=None):
-        if not torch.is_tensor(t) or t.dtype not in dtypes:
-            raise TypeError(f"{name}: {what}: expected a {' / '.join(str(d).replace('torch.', '') for d in dtypes)} tensor, got "
-                            f"{getattr(t, 'dtype', type(t).__name__)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: {what} needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: {what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-
-    dense(field, "field", (torch.float32,))
-    dense(pred, "pred", (torch.float32,))
-    if not torch.is_tensor(step) or step.dtype != torch.int32:
-        raise TypeError(f"step: {what}: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
-    if step.dim() != 1 or step.numel() < 2 or not step.is_contiguous():
-        raise ValueError(f"step: {what}: `step` is an int32 tensor of two entries — [step index, the launch's ticket counter (zero)]")
+    a = Args(what, TypeError)
+    a.tensor(field, "field", torch.float32)
+    a.tensor(pred, "pred", torch.float32)
+    a.step_index(step, entries=2)          # ([step index, the launch's ticket counter (zero)])
     if field.dim() != 2 or nf <= 0 or int(field.size(1)) < nf:
         raise ValueError(f"field: expected [n_nodes, >= nf = {nf}], got shape {tuple(field.shape)}")
     n_nodes = int(field.size(0))
     if tuple(pred.shape) != (n_nodes, nf):
         raise ValueError(f"pred: expected shape ({n_nodes}, {nf}), got {tuple(pred.shape)}")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    if every < 0:
-        raise ValueError(f"every: {what}: {every} (0 keeps no snapshot, k > 0 every k-th step)")
-    if (every > 0) != (snap is not None):
-        raise ValueError(f"snap: {what}: every = {every} {'needs' if every else 'takes no'} snapshot buffer")
+    a.at_least(max_steps, "max_steps", 0)
+    a.lattice(every, max_steps, snap, "snap", "snapshot")
     if snap is not None:
-        dense(snap, "snap", (torch.float32,))
+        a.tensor(snap, "snap", torch.float32)
         if snap.dim() != 3 or tuple(snap.shape[1:]) != (n_nodes, nf):
             raise ValueError(f"snap: {what}: expected [n_snap, {n_nodes}, {nf}], got {tuple(snap.shape)}")
     if (probe_rows is None) != (probe_out is None):
         raise ValueError(f"probe_{'out' if probe_out is None else 'rows'}: {what}: probe_rows and probe_out come together")
     n_probe = 0
     if probe_rows is not None:
-        dense(probe_rows, "probe_rows", (torch.int32,))
-        if probe_rows.dim() != 1:
-            raise ValueError(f"probe_rows: {what}: expected a 1-D index tensor, got shape {tuple(probe_rows.shape)}")
+        a.tensor(probe_rows, "probe_rows", torch.int32, dim=1)
         n_probe = int(probe_rows.numel())
-        dense(probe_out, "probe_out", (torch.float32,), (max_steps, n_probe, nf))
+        a.tensor(probe_out, "probe_out", torch.float32, shape=(max_steps, n_probe, nf))
     target_ld = 0
     if target is None:
         for t, name in ((mask, "mask"), (stats, "stats"), (scratch, "scratch")):
             if t is not None:
                 raise ValueError(f"{name}: {what}: given without a target")
     else:
-        if not torch.is_tensor(target) or target.dtype != torch.float32:
-            raise TypeError(f"target: {what}: expected a float32 tensor, got {getattr(target, 'dtype', type(target).__name__)}")
-        if target.dim() != 2 or int(target.size(0)) != n_nodes or int(target.size(1)) < nf * max_steps:
-            raise ValueError(f"target: {what}: expected [{n_nodes}, >= nf * max_steps = {nf * max_steps}], got {tuple(target.shape)}")
-        cols = int(target.size(1))
-        if (cols > 1 and target.stride(1) != 1) or (n_nodes > 1 and target.stride(0) < cols):
-            raise ValueError(f"target: {what} needs rows of unit stride, got shape {tuple(target.shape)} strides {tuple(target.stride())}")
-        target_ld = max(int(target.stride(0)), cols) if n_nodes > 1 else cols
+        _, _, target_ld = a.strided_rows(target, "target", rows=n_nodes, min_cols=nf * max_steps)
         if mask is not None:
-            dense(mask, "mask", (torch.uint8, torch.bool), (n_nodes,))
+            a.tensor(mask, "mask", (torch.uint8, torch.bool), shape=(n_nodes,))
         if stats is None or scratch is None:
             raise ValueError(f"{'stats' if stats is None else 'scratch'}: {what}: a target needs stats and scratch")
-        dense(stats, "stats", (torch.float64,), (max_steps, nf, _lib.REC_NSTAT))
-        dense(scratch, "scratch", (torch.float64,))
-        if scratch.dim() != 1:
-            raise ValueError(f"scratch: {what}: expected a 1-D tensor, got shape {tuple(scratch.shape)}")
+        a.tensor(stats, "stats", torch.float64, shape=(max_steps, nf, _lib.REC_NSTAT))
+        a.tensor(scratch, "scratch", torch.float64, dim=1)
     lib = _lib.load()
     dev = _lib.require_hip(field, pred, step, snap, probe_rows, probe_out, target, mask, stats, scratch)
     if target is not None:
@@ -598,46 +545,23 @@ def rollout_moments(pred: Tensor, step: Tensor, nf: int, max_steps: int, window:
     is not written: the step's closing launch (rollout_advance / rollout_advance_record) bumps it afterwards."""
     nf, max_steps, stride = int(nf), int(max_steps), int(stride)
     what = "rollout_moments"
-    if not torch.is_tensor(pred) or pred.dtype != torch.float32:
-        raise TypeError(f"pred: {what}: expected a float32 tensor, got {getattr(pred, 'dtype', type(pred).__name__)}")
+    a = Args(what, TypeError)
+    a.dtype(pred, "pred", torch.float32)
     if nf <= 0 or pred.dim() != 2 or int(pred.size(1)) != nf or not pred.is_contiguous():
         raise ValueError(f"pred: {what}: expected a contiguous [n_nodes, nf = {nf}], got shape {tuple(pred.shape)} strides {tuple(pred.stride())}")
     n_nodes = int(pred.size(0))
-    for t, name in ((step, "step"), (window, "window")):
-        if not torch.is_tensor(t) or t.dtype != torch.int32:
-            raise TypeError(f"{name}: {what}: expected an int32 tensor of two entries, got {getattr(t, 'dtype', type(t).__name__)}")
-        if t.dim() != 1 or t.numel() < 2 or not t.is_contiguous():
-            raise ValueError(f"{name}: {what}: expected an int32 tensor of two entries, got shape {tuple(t.shape)}")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    if stride < 1:
-        raise ValueError(f"stride: {what}: {stride} (>= 1)")
-    lds = set()
-    for t, name, planes in ((pivot, "pivot", nf), (sum, "sum", nf), (sum2, "sum2", moment_pairs(nf)), (lo, "lo", nf), (hi, "hi", nf)):
-        if not torch.is_tensor(t) or t.dtype != torch.float64:
-            raise TypeError(f"{name}: {what}: expected a float64 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-        if tuple(t.shape) != (planes, n_nodes):
-            raise ValueError(f"{name}: {what}: expected shape ({planes}, {n_nodes}), got {tuple(t.shape)}")
-        if n_nodes > 1 and t.stride(1) != 1:
-            raise ValueError(f"{name}: {what} needs unit stride along the nodes, got strides {tuple(t.stride())}")
-        if planes > 1 and n_nodes > 0:
-            lds.add(int(t.stride(0)))
-    if len(lds) > 1 or (lds and min(lds) < n_nodes):
-        raise ValueError(f"pivot: {what}: the accumulators need one common plane stride >= n_nodes = {n_nodes}, got {sorted(lds)}")
+    a.step_index(step, entries=2)
+    a.step_index(window, "window", entries=2)
+    a.at_least(max_steps, "max_steps", 0)
+    a.at_least(stride, "stride", 1)
+    plane_ld = a.planes_f64(n_nodes, ("pivot", pivot, nf), ("sum", sum, nf), ("sum2", sum2, moment_pairs(nf)), ("lo", lo, nf), ("hi", hi, nf))
     sub_ld = 0
     if sub is not None:
-        if not torch.is_tensor(sub) or sub.dtype != torch.float32:
-            raise TypeError(f"sub: {what}: expected a float32 tensor, got {getattr(sub, 'dtype', type(sub).__name__)}")
-        if sub.dim() != 2 or int(sub.size(0)) != n_nodes or int(sub.size(1)) < nf * max_steps:
-            raise ValueError(f"sub: {what}: expected [{n_nodes}, >= nf * max_steps = {nf * max_steps}], got {tuple(sub.shape)}")
-        cols = int(sub.size(1))
-        if (n_nodes > 0 and cols > 1 and sub.stride(1) != 1) or (n_nodes > 1 and sub.stride(0) < cols):
-            raise ValueError(f"sub: {what} needs rows of unit stride, got shape {tuple(sub.shape)} strides {tuple(sub.stride())}")
-        sub_ld = max(int(sub.stride(0)), cols) if n_nodes > 1 else cols
+        _, _, sub_ld = a.strided_rows(sub, "sub", rows=n_nodes, min_cols=nf * max_steps)
     lib = _lib.load()
     dev = _lib.require_hip(pred, step, window, pivot, sum, sum2, lo, hi, sub)
     m = _lib.g4c_rollout_moments_t(max_steps=max_steps, stride=stride, window=_lib.ptr(window), sub=_lib.ptr(sub), sub_ld=sub_ld,
-                                   plane_ld=lds.pop() if lds else max(n_nodes, 1), pivot=_lib.ptr(pivot), sum=_lib.ptr(sum),
+                                   plane_ld=plane_ld, pivot=_lib.ptr(pivot), sum=_lib.ptr(sum),
                                    sum2=_lib.ptr(sum2), lo=_lib.ptr(lo), hi=_lib.ptr(hi))
     _lib.check(lib.g4c_rollout_moments(_lib.ptr(pred), nf, C.byref(m), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
@@ -725,74 +649,29 @@ def rollout_spectrum(x: Tensor, step: Tensor, nf: int, max_steps: int, window: T
     `step` is not written: the step's closing launch bumps it afterwards."""
     nf, max_steps, stride, x_step = int(nf), int(max_steps), int(stride), int(x_step)
     what = "rollout_spectrum"
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise TypeError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    a = Args(what, TypeError)
+    a.dtype(x, "x", torch.float32)
     if nf <= 0 or x_step not in (0, nf):
         raise ValueError(f"x_step: {what}: nf = {nf} (>= 1) and x_step = {x_step} (0: x is the sample, nf: x holds every step's columns)")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    cols = nf * max_steps if x_step else nf
-    if x.dim() != 2 or (int(x.size(1)) < cols if x_step else int(x.size(1)) != cols):
-        raise ValueError(f"x: {what}: expected [n_nodes, {'>= nf * max_steps' if x_step else 'nf'} = {cols}], got shape {tuple(x.shape)}")
-    n_nodes, width = int(x.size(0)), int(x.size(1))
-    if (n_nodes > 0 and width > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < width):
-        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    x_ld = max(int(x.stride(0)), width) if n_nodes > 1 else width
-    if x_ld >= 2 ** 31:
-        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
-    for t, name in ((step, "step"), (window, "window")):
-        if not torch.is_tensor(t) or t.dtype != torch.int32:
-            raise TypeError(f"{name}: {what}: expected an int32 tensor of two entries, got {getattr(t, 'dtype', type(t).__name__)}")
-        if t.dim() != 1 or t.numel() < 2 or not t.is_contiguous():
-            raise ValueError(f"{name}: {what}: expected an int32 tensor of two entries, got shape {tuple(t.shape)}")
-    if stride < 1:
-        raise ValueError(f"stride: {what}: {stride} (>= 1)")
-    if not torch.is_tensor(tw) or tw.dtype != torch.float64:
-        raise TypeError(f"tw: {what}: expected a float64 tensor, got {getattr(tw, 'dtype', type(tw).__name__)}")
+    a.at_least(max_steps, "max_steps", 0)
+    if x_step:
+        n_nodes, _, x_ld = a.strided_rows(x, "x", min_cols=nf * max_steps)
+    else:
+        n_nodes, _, x_ld = a.strided_rows(x, "x", cols=nf)
+    a.step_index(step, entries=2)
+    a.step_index(window, "window", entries=2)
+    a.at_least(stride, "stride", 1)
+    a.dtype(tw, "tw", torch.float64)
     if tw.dim() != 3 or int(tw.size(2)) != 2 or int(tw.size(0)) < 1 or int(tw.size(1)) < 1 or not tw.is_contiguous():
         raise ValueError(f"tw: {what}: expected a contiguous [samples >= 1, K >= 1, 2], got shape {tuple(tw.shape)} strides {tuple(tw.stride())}")
     samples, K = int(tw.size(0)), int(tw.size(1))
-    lds = set()
-    for t, name, planes in ((pivot, "pivot", nf), (sum, "sum", nf), (re, "re", nf * K), (im, "im", nf * K)):
-        if not torch.is_tensor(t) or t.dtype != torch.float64:
-            raise TypeError(f"{name}: {what}: expected a float64 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-        if tuple(t.shape) != (planes, n_nodes):
-            raise ValueError(f"{name}: {what}: expected shape ({planes}, {n_nodes}), got {tuple(t.shape)}")
-        if n_nodes > 1 and t.stride(1) != 1:
-            raise ValueError(f"{name}: {what} needs unit stride along the nodes, got strides {tuple(t.stride())}")
-        if planes > 1 and n_nodes > 0:
-            lds.add(int(t.stride(0)))
-    if len(lds) > 1 or (lds and min(lds) < n_nodes):
-        raise ValueError(f"pivot: {what}: the accumulators need one common plane stride >= n_nodes = {n_nodes}, got {sorted(lds)}")
+    plane_ld = a.planes_f64(n_nodes, ("pivot", pivot, nf), ("sum", sum, nf), ("re", re, nf * K), ("im", im, nf * K))
     lib = _lib.load()
     dev = _lib.require_hip(x, step, window, tw, pivot, sum, re, im)
     s = _lib.g4c_rollout_spectrum_t(max_steps=max_steps, stride=stride, n_samples=samples, n_bins=K, window=_lib.ptr(window), tw=_lib.ptr(tw),
-                                    x_ld=x_ld, x_step=x_step, plane_ld=lds.pop() if lds else max(n_nodes, 1), pivot=_lib.ptr(pivot),
+                                    x_ld=x_ld, x_step=x_step, plane_ld=plane_ld, pivot=_lib.ptr(pivot),
                                     sum=_lib.ptr(sum), re=_lib.ptr(re), im=_lib.ptr(im))
     _lib.check(lib.g4c_rollout_spectrum(_lib.ptr(x), nf, C.byref(s), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
-
-
-def _mesh_arg(what, t, name, dtype, shape=None, dim=None):
-    """dtype, contiguity and shape of one tensor argument of ops.mesh_*: ValueError naming the argument."""
-    if not torch.is_tensor(t) or t.dtype != dtype:
-        raise ValueError(f"{name}: {what}: expected a {str(dtype).replace('torch.', '')} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: {what} needs a contiguous tensor, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
-    if dim is not None and t.dim() != dim:
-        raise ValueError(f"{name}: {what}: expected a {dim}-D tensor, got shape {tuple(t.shape)}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: {what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-
-
-def _mesh_devices(what, first, *named):
-    """Every tensor on the HIP device of the first one: ValueError naming the argument (nothing is moved, there is no CPU path)."""
-    name0, t0 = first
-    if t0.device.type != "cuda":
-        raise ValueError(f"{name0}: {what} runs on a HIP device only, got a tensor on '{t0.device}' (there is no CPU fallback)")
-    for name, t in named:
-        if t is not None and t.device != t0.device:
-            raise ValueError(f"{name}: {what}: on '{t.device}', {name0} is on '{t0.device}'")
-    return t0.device
 
 
 def mesh_gradient_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
@@ -809,31 +688,31 @@ def _stencil_weights(what, fn, width, entries, letter, rel, csr, src32, power, o
     """The checks and the launch of `mesh_gradient_weights` and `mesh_jet_weights`: `fn` the name of the library's function,
     `width(dim)` the row width of its table, `entries` / `letter` what a stencil entry is called in a message ("edges" / "E",
     "entries" / "S")."""
-    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
-    _mesh_arg(what, rel, "rel", torch.float32, dim=2)
+    a = Args(what)
+    a.choice(power, "power", (0, 1, 2), "0, 1 or 2")
+    a.tensor(rel, "rel", torch.float32, dim=2)
     n_entries, dim = int(rel.size(0)), int(rel.size(1))
     if dim not in (2, 3):
         raise ValueError(f"rel: {what}: expected [{letter}, 2] or [{letter}, 3], got shape {tuple(rel.shape)}")
     W = width(dim)
     off, perm = getattr(csr, "off", None), getattr(csr, "perm", None)
-    _mesh_arg(what, off, "csr.off", torch.int32, dim=1)
+    a.tensor(off, "csr.off", torch.int32, dim=1)
     if off.numel() < 1:
         raise ValueError(f"csr.off: {what}: expected [n_nodes + 1], got shape {tuple(off.shape)}")
     n_nodes = int(off.numel()) - 1
     if int(getattr(csr, "n", n_entries)) != n_entries:
         raise ValueError(f"csr: {what}: a plan of {csr.n} {entries} for rel of {n_entries}")
     if perm is not None:
-        _mesh_arg(what, perm, "csr.perm", torch.int32, shape=(n_entries,))
-    _mesh_arg(what, src32, "src32", torch.int32, shape=(n_entries,))
+        a.tensor(perm, "csr.perm", torch.int32, shape=(n_entries,))
+    a.tensor(src32, "src32", torch.int32, shape=(n_entries,))
     if out is not None:
         table, src, degenerate = out
-        _mesh_arg(what, table, "out[0]", torch.float32, shape=(n_entries, W))
-        _mesh_arg(what, src, "out[1]", torch.int32, shape=(n_entries,))
-        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
+        a.tensor(table, "out[0]", torch.float32, shape=(n_entries, W))
+        a.tensor(src, "out[1]", torch.int32, shape=(n_entries,))
+        a.tensor(degenerate, "out[2]", torch.uint8, shape=(n_nodes,))
     else:
         table = src = degenerate = None
-    dev = _mesh_devices(what, ("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", table), ("out[1]", src),
+    dev = a.same_device(("rel", rel), ("csr.off", off), ("csr.perm", perm), ("src32", src32), ("out[0]", table), ("out[1]", src),
                         ("out[2]", degenerate))
     if out is None:
         table = torch.empty((n_entries, W), dtype=torch.float32, device=dev)
@@ -889,11 +768,11 @@ def jet_size(dim: int) -> int:
     return dim + dim * (dim + 1) // 2
 
 
-def _jet_dim(what, c, name="c") -> int:
+def _jet_dim(a: Args, c, name="c") -> int:
     """The mesh's dimension from the width of a table of rows [S, Q]."""
-    _mesh_arg(what, c, name, torch.float32, dim=2)
+    a.tensor(c, name, torch.float32, dim=2)
     if int(c.size(1)) not in (5, 9):
-        raise ValueError(f"{name}: {what}: expected [S, 5] (2-D) or [S, 9] (3-D), got shape {tuple(c.shape)}")
+        raise a.fail(name, f"expected [S, 5] (2-D) or [S, 9] (3-D), got shape {tuple(c.shape)}")
     return 2 if int(c.size(1)) == 5 else 3
 
 
@@ -907,20 +786,14 @@ def mesh_jet_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
     return _stencil_weights("mesh_jet_weights", "g4c_mesh_jet_weights", jet_size, "entries", "S", rel, csr, src32, power, out)
 
 
-def _mesh_fields(what, x, nf):
-    """(n_nodes, nf, x_ld) of the fields x[:, :nf] of `mesh_derived` and `mesh_jet`: float32 [N, >= 1] with rows of unit stride, nf
-    defaulting to every column, x_ld the row stride in elements."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.dim() != 2 or int(x.size(1)) < 1:
-        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
-    n_nodes, cols = int(x.size(0)), int(x.size(1))
+def _fields(a: Args, x, nf):
+    """(n_nodes, nf, x_ld) of the fields x[:, :nf] of `mesh_derived`, `mesh_jet` and `sample_points`: float32 [N, >= 1] with rows of
+    unit stride, nf defaulting to every column, x_ld the row stride in elements."""
+    n_nodes, cols = a.rows(x, "x")
     nf = cols if nf is None else int(nf)
     if not 1 <= nf <= cols:
-        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
-    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
-        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    return n_nodes, nf, max(int(x.stride(0)), cols) if n_nodes > 1 else cols
+        raise a.fail("nf", f"{nf} fields of x with {cols} columns")
+    return n_nodes, nf, a.row_stride(x, "x")
 
 
 def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optional[Tensor] = None, *, nf: Optional[int] = None) -> Tensor:
@@ -929,17 +802,18 @@ def mesh_jet(x: Tensor, off: Tensor, c: Tensor, src: Tensor, program, out: Optio
     [N + 1]: the outputs of `mesh_jet_weights` and the stencil's offsets) into out float32 [N, nd] — one thread per node, fp32, its
     entries in CSR order: the same bits on every run.  At most 4 distinct fields per program."""
     what = "mesh_jet"
-    dim = _jet_dim(what, c)
+    a = Args(what)
+    dim = _jet_dim(a, c)
     n_entries = int(c.size(0))
-    n_nodes, nf, x_ld = _mesh_fields(what, x, nf)
-    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, src, "src", torch.int32, shape=(n_entries,))
+    n_nodes, nf, x_ld = _fields(a, x, nf)
+    a.tensor(off, "off", torch.int32, shape=(n_nodes + 1,))
+    a.tensor(src, "src", torch.int32, shape=(n_entries,))
     prog = derived_program(program, nf, dim, order=2)
     _jet_fields(what, prog)
     nd = int(prog.nd)
     if out is not None:
-        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nd))
-    dev = _mesh_devices(what, ("x", x), ("off", off), ("c", c), ("src", src), ("out", out))
+        a.tensor(out, "out", torch.float32, shape=(n_nodes, nd))
+    dev = a.same_device(("x", x), ("off", off), ("c", c), ("src", src), ("out", out))
     if out is None:
         out = torch.empty((n_nodes, nd), dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -962,40 +836,47 @@ def mesh_jet_adjoint(gy: Tensor, off: Tensor, c: Tensor, out_off: Tensor, out_c:
     (`plan.gather_csr(src, N)`), out_off int32 [N + 1] its offsets, out_c float32 [S, Q] = c[perm] and out_dst int32 [S] the
     receivers of those positions.  One thread per node, fp32, a fixed order (include/g4c.h), no atomics.  `gx`: the tensor to write
     into (not gy)."""
-    what = "mesh_jet_adjoint"
-    dim = _jet_dim(what, c)
-    return _stencil_adjoint(what, "g4c_mesh_jet_adjoint", dim, 2, "c", gy, off, c, out_off, out_c, out_dst, program, nf, gx)
+    a = Args("mesh_jet_adjoint")
+    dim = _jet_dim(a, c)
+    return _stencil_adjoint(a, "g4c_mesh_jet_adjoint", dim, 2, "c", gy, off, c, out_off, out_c, out_dst, program, nf, gx)
 
 
-def _stencil_adjoint(what, fn, dim, order, name, gy, off, table, out_off, out_table, out_dst, program, nf, gx):
+def _stencil_adjoint(a: Args, fn, dim, order, name, gy, off, table, out_off, out_table, out_dst, program, nf, gx):
     """The checks and the launch of `mesh_derived_adjoint` and `mesh_jet_adjoint` behind the check of their table (`name`: "g" or
     "c"), which gave `dim`: `fn` the name of the library's function, `order` the program's (`derived_program`)."""
+    what = a.what
     n_entries, W = int(table.size(0)), int(table.size(1))
-    if isinstance(nf, bool) or not isinstance(nf, int) or nf < 1:
-        raise ValueError(f"nf: {what}: expected a number of fields >= 1, got {nf!r}")
+    a.integer(nf, "nf", at_least=1)
     prog = derived_program(program, nf, dim, order=order)
     if order == 2:
         _jet_fields(what, prog)
     nd = int(prog.nd)
-    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
+    a.tensor(gy, "gy", torch.float32, dim=2)
     if int(gy.size(1)) != nd:
         raise ValueError(f"gy: {what}: expected [n_nodes, {nd}] (one column per column of the program), got shape {tuple(gy.shape)}")
     n_nodes = int(gy.size(0))
-    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, out_table, f"out_{name}", torch.float32, shape=(n_entries, W))
-    _mesh_arg(what, out_dst, "out_dst", torch.int32, shape=(n_entries,))
+    a.tensor(off, "off", torch.int32, shape=(n_nodes + 1,))
+    a.tensor(out_off, "out_off", torch.int32, shape=(n_nodes + 1,))
+    a.tensor(out_table, f"out_{name}", torch.float32, shape=(n_entries, W))
+    a.tensor(out_dst, "out_dst", torch.int32, shape=(n_entries,))
     if gx is not None:
-        _mesh_arg(what, gx, "gx", torch.float32, shape=(n_nodes, nf))
-        if gx is gy or (gx.numel() and gy.numel() and gx.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
-            raise ValueError(f"gx: {what}: gx shares its storage with gy")
-    dev = _mesh_devices(what, ("gy", gy), ("off", off), (name, table), ("out_off", out_off), (f"out_{name}", out_table), ("out_dst", out_dst),
+        a.tensor(gx, "gx", torch.float32, shape=(n_nodes, nf))
+        a.distinct_storage(gx, "gx", ("gy", gy), identity=True)
+    dev = a.same_device(("gy", gy), ("off", off), (name, table), ("out_off", out_off), (f"out_{name}", out_table), ("out_dst", out_dst),
                         ("gx", gx))
     if gx is None:
         gx = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
     _lib.check(getattr(_lib.load(), fn)(_lib.ptr(gy), C.byref(prog), dim, nf, _lib.ptr(table), _lib.ptr(off), _lib.ptr(out_table),
                                         _lib.ptr(out_dst), _lib.ptr(out_off), n_nodes, n_entries, _lib.ptr(gx), _lib.stream_handle(dev)))
     return gx
+
+
+def _gradient_table(a: Args, g, dims=(2, 3)):
+    """(E, dim) of the least-squares gradient's table g float32 [E, dim], dim one of `dims`."""
+    a.tensor(g, "g", torch.float32, dim=2)
+    if int(g.size(1)) not in dims:
+        raise a.fail("g", f"expected {' or '.join(f'[E, {d}]' for d in dims)}, got shape {tuple(g.shape)}")
+    return int(g.size(0)), int(g.size(1))
 
 
 def mesh_derived_scratch(n_nodes: int, nd: int, device) -> Tensor:
@@ -1014,41 +895,30 @@ def mesh_derived(x: Tensor, off: Tensor, g: Tensor, src: Tensor, program, cur: T
     at row t (overwritten; `scratch` from `mesh_derived_scratch`), in a fixed order: the same bits on every run."""
     what = "mesh_derived"
     every, max_steps = int(every), int(max_steps)
-    _mesh_arg(what, g, "g", torch.float32, dim=2)
-    n_edges, dim = int(g.size(0)), int(g.size(1))
-    if dim not in (2, 3):
-        raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
-    n_nodes, nf, x_ld = _mesh_fields(what, x, nf)
-    _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, src, "src", torch.int32, shape=(n_edges,))
+    a = Args(what)
+    n_edges, dim = _gradient_table(a, g)
+    n_nodes, nf, x_ld = _fields(a, x, nf)
+    a.tensor(off, "off", torch.int32, shape=(n_nodes + 1,))
+    a.tensor(src, "src", torch.int32, shape=(n_edges,))
     prog = derived_program(program, nf, dim)
     nd = int(prog.nd)
-    _mesh_arg(what, cur, "cur", torch.float32, shape=(n_nodes, nd))
-    if every < 0:
-        raise ValueError(f"every: {what}: {every} (0 keeps no snapshot, k > 0 every k-th step)")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    if (every > 0) != (snap is not None):
-        raise ValueError(f"snap: {what}: every = {every} {'needs a' if every else 'takes no'} snapshot buffer")
+    a.tensor(cur, "cur", torch.float32, shape=(n_nodes, nd))
+    a.lattice(every, max_steps, snap, "snap", "snapshot")
     if snap is not None:
-        _mesh_arg(what, snap, "snap", torch.float32, dim=3)
+        a.tensor(snap, "snap", torch.float32, dim=3)
         if tuple(snap.shape[1:]) != (n_nodes, nd):
             raise ValueError(f"snap: {what}: expected [n_snap, {n_nodes}, {nd}], got {tuple(snap.shape)}")
     if (stats is None) != (scratch is None):
         raise ValueError(f"{'scratch' if scratch is None else 'stats'}: {what}: stats and scratch come together")
     if stats is not None:
-        _mesh_arg(what, stats, "stats", torch.float64, shape=(max_steps, nd, _lib.DERIVED_NSTAT))
-        _mesh_arg(what, scratch, "scratch", torch.float64, dim=1)
-        need = 8 + min(max(-(-n_nodes // 256), 1), 1024) * nd * _lib.DERIVED_NSTAT
-        if scratch.numel() < need:
-            raise ValueError(f"scratch: {what}: {scratch.numel()} doubles, needs {need} (mesh_derived_scratch)")
+        a.tensor(stats, "stats", torch.float64, shape=(max_steps, nd, _lib.DERIVED_NSTAT))
+        a.scratch(scratch, "scratch", record_scratch_doubles(n_nodes, nd * _lib.DERIVED_NSTAT), "mesh_derived_scratch")
     if step is None:
         if snap is not None or stats is not None:
             raise ValueError(f"step: {what}: snapshots and stats are addressed by the step index: pass step=")
     else:
-        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
-            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
-    dev = _mesh_devices(what, ("x", x), ("off", off), ("g", g), ("src", src), ("cur", cur), ("step", step), ("snap", snap),
+        a.step_index(step)
+    dev = a.same_device(("x", x), ("off", off), ("g", g), ("src", src), ("cur", cur), ("step", step), ("snap", snap),
                         ("stats", stats), ("scratch", scratch))
     lib = _lib.load()
     d = _lib.g4c_mesh_derived_t(dim=dim, nf=nf, x_ld=x_ld, g=_lib.ptr(g), src=_lib.ptr(src), off=_lib.ptr(off), cur=_lib.ptr(cur),
@@ -1065,12 +935,9 @@ def mesh_derived_adjoint(gy: Tensor, off: Tensor, g: Tensor, out_off: Tensor, ou
     ascending within a sender (`plan.gather_csr(src, N)`), out_off int32 [N + 1] its offsets, out_g float32 [E, dim] = g[perm] and
     out_dst int32 [E] the receivers of those positions.  One thread per node, fp32, a fixed order (include/g4c.h), no atomics: the
     same bits on every run.  `gx`: the tensor to write into (not gy)."""
-    what = "mesh_derived_adjoint"
-    _mesh_arg(what, g, "g", torch.float32, dim=2)
-    dim = int(g.size(1))
-    if dim not in (2, 3):
-        raise ValueError(f"g: {what}: expected [E, 2] or [E, 3], got shape {tuple(g.shape)}")
-    return _stencil_adjoint(what, "g4c_mesh_derived_adjoint", dim, 1, "g", gy, off, g, out_off, out_g, out_dst, program, nf, gx)
+    a = Args("mesh_derived_adjoint")
+    _, dim = _gradient_table(a, g)
+    return _stencil_adjoint(a, "g4c_mesh_derived_adjoint", dim, 1, "g", gy, off, g, out_off, out_g, out_dst, program, nf, gx)
 
 
 def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: Tensor, arm: Tensor, cur: Tensor, *, pcol: int,
@@ -1090,61 +957,47 @@ def body_forces(x: Tensor, item: Tensor, body_off: Tensor, area: Tensor, unit: T
     of x: they are not checked.  Returns cur."""
     what = "body_forces"
     max_steps, t, x_step = int(max_steps), int(t), int(x_step)
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.dim() != 2 or int(x.size(1)) < 1:
-        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
-    n_nodes, cols = int(x.size(0)), int(x.size(1))
-    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
-        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
-    if x_ld >= 2 ** 31:
-        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
-    _mesh_arg(what, item, "item", torch.int32, dim=1)
+    a = Args(what)
+    n_nodes, cols, x_ld = a.strided_rows(x, "x")
+    a.tensor(item, "item", torch.int32, dim=1)
     n_items = int(item.size(0))
-    _mesh_arg(what, body_off, "body_off", torch.int32, dim=1)
+    a.tensor(body_off, "body_off", torch.int32, dim=1)
     n_bodies = int(body_off.size(0)) - 1
     if n_bodies < 0:
         raise ValueError(f"body_off: {what}: expected [n_bodies + 1], got shape {tuple(body_off.shape)}")
     for name, tab in (("area", area), ("unit", unit), ("arm", arm)):
-        _mesh_arg(what, tab, name, torch.float64, shape=(n_items, 2))
-    _mesh_arg(what, cur, "cur", torch.float32, shape=(n_bodies, 3))
+        a.tensor(tab, name, torch.float64, shape=(n_items, 2))
+    a.tensor(cur, "cur", torch.float32, shape=(n_bodies, 3))
     for name, v in (("mu", mu), ("p_scale", p_scale), ("p_shift", p_shift), ("u_scale", u_scale), ("v_scale", v_scale)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"{name}: {what}: expected a number, got {v!r}")
+        a.number(v, name)
     viscous = float(mu) != 0.0
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
+    a.at_least(max_steps, "max_steps", 0)
     if x_step < 0 or (x_step > 0 and max_steps < 1):
         raise ValueError(f"x_step: {what}: {x_step} (0: x holds the fields, nf: x holds the nf fields of each of max_steps = {max_steps} >= 1 steps)")
     width = x_step if x_step else cols
     for name, c in (("pcol", pcol),) + ((("ucol", ucol), ("vcol", vcol)) if viscous else ()):
-        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < width:
-            raise ValueError(f"{name}: {what}: expected a column 0 .. {width - 1}, got {c!r}")
+        a.column(c, name, width)
     if x_step and cols < x_step * max_steps:
         raise ValueError(f"x: {what}: {cols} columns, x_step = {x_step} and max_steps = {max_steps} need {x_step * max_steps}")
     if viscous:
         for name, tab in (("off", off), ("g", g), ("src", src)):
             if tab is None:
                 raise ValueError(f"{name}: {what}: mu != 0 needs the gradient's off, g and src")
-        _mesh_arg(what, g, "g", torch.float32, dim=2)
-        if int(g.size(1)) != 2:
-            raise ValueError(f"g: {what}: expected [E, 2] (the operator is 2-D), got shape {tuple(g.shape)}")
-        _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-        _mesh_arg(what, src, "src", torch.int32, shape=(int(g.size(0)),))
+        n_edges, _ = _gradient_table(a, g, dims=(2,))          # (the operator is 2-D)
+        a.tensor(off, "off", torch.int32, shape=(n_nodes + 1,))
+        a.tensor(src, "src", torch.int32, shape=(n_edges,))
     else:
         off = g = src = None
         ucol = vcol = 0
     if wall is not None:
-        _mesh_arg(what, wall, "wall", torch.float32, shape=(n_items, 2))
+        a.tensor(wall, "wall", torch.float32, shape=(n_items, 2))
     if stats is not None:
         if max_steps < 1:
             raise ValueError(f"max_steps: {what}: stats need max_steps >= 1, got {max_steps}")
-        _mesh_arg(what, stats, "stats", torch.float64, shape=(max_steps, n_bodies, _lib.FORCES_NSUM))
+        a.tensor(stats, "stats", torch.float64, shape=(max_steps, n_bodies, _lib.FORCES_NSUM))
     if step is not None:
-        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
-            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
-    dev = _mesh_devices(what, ("x", x), ("item", item), ("body_off", body_off), ("area", area), ("unit", unit), ("arm", arm), ("cur", cur),
+        a.step_index(step)
+    dev = a.same_device(("x", x), ("item", item), ("body_off", body_off), ("area", area), ("unit", unit), ("arm", arm), ("cur", cur),
                         ("off", off), ("g", g), ("src", src), ("wall", wall), ("stats", stats), ("step", step))
     lib = _lib.load()
     bf = _lib.g4c_body_forces_t(x=_lib.ptr(x), x_ld=x_ld, x_step=x_step, step=_lib.ptr(step), t0=t, pcol=pcol, ucol=ucol, vcol=vcol,
@@ -1171,57 +1024,51 @@ def body_forces_adjoint(gF: Optional[Tensor], gwall: Optional[Tensor], item_body
     hw float32 [W, 5], then one thread per node), fp32 sums in a fixed order (include/g4c.h), no atomics: the same bits on every run.
     `out`: the tensor to write into; `hw`: the scratch to use."""
     what = "body_forces_adjoint"
-    for name, v in (("n_bodies", n_bodies), ("nf", nf)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < (1 if name == "nf" else 0):
-            raise ValueError(f"{name}: {what}: expected an integer >= {1 if name == 'nf' else 0}, got {v!r}")
+    a = Args(what)
+    a.integer(n_bodies, "n_bodies", at_least=0)
+    a.integer(nf, "nf", at_least=1)
     for name, v in (("mu", mu), ("p_scale", p_scale), ("u_scale", u_scale), ("v_scale", v_scale)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"{name}: {what}: expected a number, got {v!r}")
+        a.number(v, name)
     viscous = float(mu) != 0.0
     for name, c in (("pcol", pcol),) + ((("ucol", ucol), ("vcol", vcol)) if viscous else ()):
-        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < nf:
-            raise ValueError(f"{name}: {what}: expected a column 0 .. {nf - 1}, got {c!r}")
+        a.column(c, name, nf)
     if viscous and len({pcol, ucol, vcol}) != 3:
         raise ValueError(f"ucol: {what}: pcol = {pcol}, ucol = {ucol} and vcol = {vcol} must be distinct")
-    _mesh_arg(what, item_body, "item_body", torch.int32, dim=1)
+    a.tensor(item_body, "item_body", torch.int32, dim=1)
     n_items = int(item_body.size(0))
     for name, tab in (("area", area), ("unit", unit), ("arm", arm)):
-        _mesh_arg(what, tab, name, torch.float64, shape=(n_items, 2))
-    _mesh_arg(what, own_off, "own_off", torch.int32, dim=1)
+        a.tensor(tab, name, torch.float64, shape=(n_items, 2))
+    a.tensor(own_off, "own_off", torch.int32, dim=1)
     n_nodes = int(own_off.size(0)) - 1
     if n_nodes < 0:
         raise ValueError(f"own_off: {what}: expected [n_nodes + 1], got shape {tuple(own_off.shape)}")
-    _mesh_arg(what, own_item, "own_item", torch.int32, shape=(n_items,))
+    a.tensor(own_item, "own_item", torch.int32, shape=(n_items,))
     if gF is not None:
-        _mesh_arg(what, gF, "gF", torch.float64, shape=(n_bodies, _lib.FORCES_NSUM))
+        a.tensor(gF, "gF", torch.float64, shape=(n_bodies, _lib.FORCES_NSUM))
     if gwall is not None:
-        _mesh_arg(what, gwall, "gwall", torch.float32, shape=(n_items, 2))
+        a.tensor(gwall, "gwall", torch.float32, shape=(n_items, 2))
     n_entries = 0
     if viscous:
         for name, tab in (("g", g), ("off", off), ("in_off", in_off), ("in_item", in_item), ("in_g", in_g)):
             if tab is None:
                 raise ValueError(f"{name}: {what}: mu != 0 needs the gradient's g and off and the in-tables")
-        _mesh_arg(what, g, "g", torch.float32, dim=2)
-        if int(g.size(1)) != 2:
-            raise ValueError(f"g: {what}: expected [E, 2] (the operator is 2-D), got shape {tuple(g.shape)}")
-        _mesh_arg(what, off, "off", torch.int32, shape=(n_nodes + 1,))
-        _mesh_arg(what, in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
-        _mesh_arg(what, in_item, "in_item", torch.int32, dim=1)
+        _gradient_table(a, g, dims=(2,))          # (the operator is 2-D)
+        a.tensor(off, "off", torch.int32, shape=(n_nodes + 1,))
+        a.tensor(in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
+        a.tensor(in_item, "in_item", torch.int32, dim=1)
         n_entries = int(in_item.size(0))
         if n_entries >= 2 ** 31:
             raise NotImplementedError(f"in_item: {what}: {n_entries} list entries do not fit the int32 offsets")
-        _mesh_arg(what, in_g, "in_g", torch.float32, shape=(n_entries, 2))
+        a.tensor(in_g, "in_g", torch.float32, shape=(n_entries, 2))
     else:
         g = off = in_off = in_item = in_g = None
         ucol = vcol = 0
     if hw is not None:
-        _mesh_arg(what, hw, "hw", torch.float32, shape=(n_items, 5))
+        a.tensor(hw, "hw", torch.float32, shape=(n_items, 5))
     if out is not None:
-        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nf))
-        for name, t in (("gF", gF), ("gwall", gwall), ("hw", hw)):
-            if t is not None and out.numel() and t.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                raise ValueError(f"out: {what}: out shares its storage with {name}")
-    dev = _mesh_devices(what, ("item_body", item_body), ("area", area), ("unit", unit), ("arm", arm), ("own_off", own_off),
+        a.tensor(out, "out", torch.float32, shape=(n_nodes, nf))
+        a.distinct_storage(out, "out", ("gF", gF), ("gwall", gwall), ("hw", hw))
+    dev = a.same_device(("item_body", item_body), ("area", area), ("unit", unit), ("arm", arm), ("own_off", own_off),
                         ("own_item", own_item), ("gF", gF), ("gwall", gwall), ("g", g), ("off", off), ("in_off", in_off),
                         ("in_item", in_item), ("in_g", in_g), ("hw", hw), ("out", out))
     if hw is None:
@@ -1238,14 +1085,14 @@ def body_forces_adjoint(gF: Optional[Tensor], gwall: Optional[Tensor], item_body
     return out
 
 
-def _sample_tables(what, idx, coef):
+def _sample_tables(a: Args, idx, coef):
     """The j-major tables of ops.sample_*: idx int32 [k, P] (and coef float32 [k, P]) -> (k, P); ValueError naming the argument."""
-    _mesh_arg(what, idx, "idx", torch.int32, dim=2)
+    a.tensor(idx, "idx", torch.int32, dim=2)
     k, n_points = int(idx.size(0)), int(idx.size(1))
     if not 1 <= k <= _lib.SAMPLE_MAX_K:
-        raise ValueError(f"idx: {what}: expected [k, P] with 1 <= k <= {_lib.SAMPLE_MAX_K} neighbours, got shape {tuple(idx.shape)}")
+        raise a.fail("idx", f"expected [k, P] with 1 <= k <= {_lib.SAMPLE_MAX_K} neighbours, got shape {tuple(idx.shape)}")
     if coef is not None:
-        _mesh_arg(what, coef, "coef", torch.float32, shape=(k, n_points))
+        a.tensor(coef, "coef", torch.float32, shape=(k, n_points))
     return k, n_points
 
 
@@ -1273,24 +1120,24 @@ def sample_weights(pos: Tensor, queries: Tensor, idx: Tensor, power: int = 2, ou
     what = "sample_weights"
     if (origin is None) != (period is None):
         raise ValueError(f"period: {what}: origin and period come together")
-    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
-    _mesh_arg(what, pos, "pos", torch.float32, dim=2)
+    a = Args(what)
+    a.choice(power, "power", (0, 1, 2), "0, 1 or 2")
+    a.tensor(pos, "pos", torch.float32, dim=2)
     n_nodes, dim = int(pos.size(0)), int(pos.size(1))
     if dim not in (2, 3):
         raise ValueError(f"pos: {what}: expected [N, 2] or [N, 3], got shape {tuple(pos.shape)}")
-    k, n_points = _sample_tables(what, idx, None)
-    _mesh_arg(what, queries, "queries", torch.float32, shape=(n_points, dim))
+    k, n_points = _sample_tables(a, idx, None)
+    a.tensor(queries, "queries", torch.float32, shape=(n_points, dim))
     if n_points > 0 and n_nodes < k:
         raise ValueError(f"idx: {what}: k = {k} neighbours of {n_nodes} nodes")
     if out is not None:
         coef, distance, degenerate = out
-        _mesh_arg(what, coef, "out[0]", torch.float32, shape=(k, n_points))
-        _mesh_arg(what, distance, "out[1]", torch.float32, shape=(n_points,))
-        _mesh_arg(what, degenerate, "out[2]", torch.uint8, shape=(n_points,))
+        a.tensor(coef, "out[0]", torch.float32, shape=(k, n_points))
+        a.tensor(distance, "out[1]", torch.float32, shape=(n_points,))
+        a.tensor(degenerate, "out[2]", torch.uint8, shape=(n_points,))
     else:
         coef = distance = degenerate = None
-    dev = _mesh_devices(what, ("pos", pos), ("queries", queries), ("idx", idx), ("out[0]", coef), ("out[1]", distance), ("out[2]", degenerate))
+    dev = a.same_device(("pos", pos), ("queries", queries), ("idx", idx), ("out[0]", coef), ("out[1]", distance), ("out[2]", degenerate))
     if out is None:
         coef = torch.empty((k, n_points), dtype=torch.float32, device=dev)
         distance = torch.empty((n_points,), dtype=torch.float32, device=dev)
@@ -1320,38 +1167,21 @@ def sample_points(x: Tensor, idx: Tensor, coef: Tensor, cur: Optional[Tensor] = 
     not checked."""
     what = "sample_points"
     every, max_steps = int(every), int(max_steps)
-    k, n_points = _sample_tables(what, idx, coef)
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"x: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.dim() != 2 or int(x.size(1)) < 1:
-        raise ValueError(f"x: {what}: expected [n_nodes, >= 1], got shape {tuple(x.shape)}")
-    n_nodes, cols = int(x.size(0)), int(x.size(1))
-    nf = cols if nf is None else int(nf)
-    if not 1 <= nf <= cols:
-        raise ValueError(f"nf: {what}: {nf} fields of x with {cols} columns")
-    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
-        raise ValueError(f"x: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    x_ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
-    if x_ld >= 2 ** 31:
-        raise ValueError(f"x: {what}: a row stride of {x_ld} elements does not fit the descriptor")
+    a = Args(what)
+    k, n_points = _sample_tables(a, idx, coef)
+    n_nodes, nf, x_ld = _fields(a, x, nf)
     if n_points > 0 and n_nodes < k:
         raise ValueError(f"idx: {what}: k = {k} neighbours of {n_nodes} nodes")
     if cur is not None:
-        _mesh_arg(what, cur, "cur", torch.float32, shape=(n_points, nf))
-    if every < 0:
-        raise ValueError(f"every: {what}: {every} (0 keeps no series, e > 0 every e-th step)")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    if (every > 0) != (series is not None):
-        raise ValueError(f"series: {what}: every = {every} {'needs a' if every else 'takes no'} series buffer")
+        a.tensor(cur, "cur", torch.float32, shape=(n_points, nf))
+    a.lattice(every, max_steps, series, "series", "series")
     if series is not None:
-        _mesh_arg(what, series, "series", torch.float32, shape=(max_steps // every, n_points, nf))
+        a.tensor(series, "series", torch.float32, shape=(max_steps // every, n_points, nf))
         if step is None:
             raise ValueError(f"step: {what}: the slots are addressed by the step index: pass step=")
     if step is not None:
-        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
-            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
-    dev = _mesh_devices(what, ("x", x), ("idx", idx), ("coef", coef), ("cur", cur), ("step", step), ("series", series))
+        a.step_index(step)
+    dev = a.same_device(("x", x), ("idx", idx), ("coef", coef), ("cur", cur), ("step", step), ("series", series))
     if cur is None:
         cur = torch.empty((n_points, nf), dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -1371,46 +1201,30 @@ def sample_points_adjoint(gy: Tensor, in_off: Tensor, in_pt: Tensor, in_coef: Te
     chunk of 4 columns), fp32, a fixed order (include/g4c.h), no atomics: the same bits on every run.  The index values are never
     read here.  `out`: the tensor to write into (not gy)."""
     what = "sample_points_adjoint"
-    if isinstance(n_nodes, bool) or not isinstance(n_nodes, int) or n_nodes < 0:
-        raise ValueError(f"n_nodes: {what}: expected a number of nodes >= 0, got {n_nodes!r}")
-    _mesh_arg(what, gy, "gy", torch.float32, dim=2)
+    a = Args(what)
+    a.integer(n_nodes, "n_nodes", at_least=0)
+    a.tensor(gy, "gy", torch.float32, dim=2)
     n_points, nf = int(gy.size(0)), int(gy.size(1))
     if nf < 1:
         raise ValueError(f"gy: {what}: expected [n_points, >= 1], got shape {tuple(gy.shape)}")
-    _mesh_arg(what, in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
-    _mesh_arg(what, in_pt, "in_pt", torch.int32, dim=1)
+    a.tensor(in_off, "in_off", torch.int32, shape=(n_nodes + 1,))
+    a.tensor(in_pt, "in_pt", torch.int32, dim=1)
     n_entries = int(in_pt.size(0))
     if n_entries >= 2 ** 31:
         raise NotImplementedError(f"in_pt: {what}: {n_entries} table entries do not fit the int32 offsets")
     if (n_entries > 0) != (n_points > 0) or (n_points > 0 and n_entries % n_points):
         raise ValueError(f"in_pt: {what}: expected [k * {n_points}] (k entries per point), got shape {tuple(in_pt.shape)}")
-    _mesh_arg(what, in_coef, "in_coef", torch.float32, shape=(n_entries,))
+    a.tensor(in_coef, "in_coef", torch.float32, shape=(n_entries,))
     if out is not None:
-        _mesh_arg(what, out, "out", torch.float32, shape=(n_nodes, nf))
-        if out is gy or (out.numel() and gy.numel() and out.untyped_storage().data_ptr() == gy.untyped_storage().data_ptr()):
-            raise ValueError(f"out: {what}: out shares its storage with gy")
-    dev = _mesh_devices(what, ("gy", gy), ("in_off", in_off), ("in_pt", in_pt), ("in_coef", in_coef), ("out", out))
+        a.tensor(out, "out", torch.float32, shape=(n_nodes, nf))
+        a.distinct_storage(out, "out", ("gy", gy), identity=True)
+    dev = a.same_device(("gy", gy), ("in_off", in_off), ("in_pt", in_pt), ("in_coef", in_coef), ("out", out))
     if out is None:
         out = torch.empty((n_nodes, nf), dtype=torch.float32, device=dev)
     lib = _lib.load()
     _lib.check(lib.g4c_sample_points_adjoint(_lib.ptr(gy), _lib.ptr(in_off), _lib.ptr(in_pt), _lib.ptr(in_coef), nf, n_nodes, n_points,
                                              _lib.ptr(out), _lib.stream_handle(dev)))
     return out
-
-
-def _tracer_nodes(what, x, name, n_nodes):
-    """A node tensor of tracer_advance: float32 [n_nodes, >= 1], rows of unit stride, any leading dimension -> its leading dimension."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.dim() != 2 or int(x.size(0)) != n_nodes or int(x.size(1)) < 1:
-        raise ValueError(f"{name}: {what}: expected [{n_nodes}, >= 1], got shape {tuple(x.shape)}")
-    cols = int(x.size(1))
-    if (n_nodes > 0 and cols > 1 and x.stride(1) != 1) or (n_nodes > 1 and x.stride(0) < cols):
-        raise ValueError(f"{name}: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    ld = max(int(x.stride(0)), cols) if n_nodes > 1 else cols
-    if ld >= 2 ** 31:
-        raise ValueError(f"{name}: {what}: a row stride of {ld} elements does not fit the descriptor")
-    return ld
 
 
 def _tracer_triple(what, name, v, dim, default):
@@ -1441,39 +1255,30 @@ def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, stat
     move nothing.  every = e > 0 and series float32 [n_slots, P, dim] keep every particle's position after steps e - 1, 2e - 1, ... in
     slots 0, 1, ...  include/g4c.h has the rule.  Returns q."""
     what = "tracer_advance"
-    for key in ("pos_sorted", "order", "cell_start", "n_cells", "org", "h", "dim", "n"):
-        if not isinstance(grid, dict) or key not in grid:
-            raise ValueError(f"grid: {what}: expected the cell grid of the node cloud (synthetic._bin_cloud), got {type(grid).__name__}"
-                             f"{'' if not isinstance(grid, dict) else f' without {key!r}'}")
-    dim, n_nodes = int(grid["dim"]), int(grid["n"])
-    every, max_steps, t = int(every), int(max_steps), int(t)
-    _mesh_arg(what, grid["pos_sorted"], "grid['pos_sorted']", torch.float32, shape=(n_nodes, dim))
-    _mesh_arg(what, grid["order"], "grid['order']", torch.int32, shape=(n_nodes,))
-    cells = [int(c) for c in grid["n_cells"]]
+    a = Args(what)
+    dim, n_nodes, cells = a.cell_grid(grid)
     if len(cells) == 3 and all(c >= 1 for c in cells):          # (the entry point refuses any other grid: the kernel reads cell_start by it)
-        _mesh_arg(what, grid["cell_start"], "grid['cell_start']", torch.int32, shape=(cells[0] * cells[1] * cells[2] + 1,))
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.SAMPLE_MAX_K:
-        raise ValueError(f"k: {what}: expected an integer 1 <= k <= {_lib.SAMPLE_MAX_K}, got {k!r}")
-    if isinstance(power, bool) or not isinstance(power, int) or power not in (0, 1, 2):
-        raise ValueError(f"power: {what}: expected 0, 1 or 2, got {power!r}")
-    if scheme not in (_lib.TRACER_EULER, _lib.TRACER_HEUN) or isinstance(scheme, bool):
-        raise ValueError(f"scheme: {what}: expected 0 (Euler) or 1 (Heun), got {scheme!r}")
-    x0_ld = _tracer_nodes(what, x0, "x0", n_nodes)
+        a.cell_start(grid, cells)
+    every, max_steps, t = int(every), int(max_steps), int(t)
+    a.integer(k, "k", at_least=1, at_most=_lib.SAMPLE_MAX_K)
+    a.choice(power, "power", (0, 1, 2), "0, 1 or 2")
+    a.choice(scheme, "scheme", (_lib.TRACER_EULER, _lib.TRACER_HEUN), "0 (Euler) or 1 (Heun)", integer=False)
+    _, _, x0_ld = a.strided_rows(x0, "x0", rows=n_nodes)          # (rows of unit stride, any leading dimension)
     if x1 is None:
         if scheme == _lib.TRACER_HEUN:
             raise ValueError(f"x1: {what}: Heun's second stage reads the node tensor of the next time level: pass x1=")
         x1_ld = 0
     else:
-        x1_ld = _tracer_nodes(what, x1, "x1", n_nodes)
-    _mesh_arg(what, q, "q", torch.float32, dim=2)
+        _, _, x1_ld = a.strided_rows(x1, "x1", rows=n_nodes)
+    a.tensor(q, "q", torch.float32, dim=2)
     n_particles = int(q.size(0))
     if int(q.size(1)) != dim:
         raise ValueError(f"q: {what}: expected [P, {dim}] (the mesh has {dim} dimensions), got {tuple(q.shape)}")
-    _mesh_arg(what, status, "status", torch.uint8, shape=(n_particles,))
-    _mesh_arg(what, stopped, "stopped", torch.int32, shape=(n_particles,))
-    _mesh_arg(what, release, "release", torch.int32, shape=(n_particles,))
+    a.tensor(status, "status", torch.uint8, shape=(n_particles,))
+    a.tensor(stopped, "stopped", torch.int32, shape=(n_particles,))
+    a.tensor(release, "release", torch.int32, shape=(n_particles,))
     if vel is not None:
-        _mesh_arg(what, vel, "vel", torch.float32, shape=(n_particles, dim))
+        a.tensor(vel, "vel", torch.float32, shape=(n_particles, dim))
     if n_particles > 0 and n_nodes < k:
         raise ValueError(f"k: {what}: {k} neighbours of {n_nodes} nodes")
     vcol = list(range(dim)) if vcol is None else [v for v in vcol]
@@ -1483,20 +1288,14 @@ def tracer_advance(grid: dict, x0: Tensor, x1: Optional[Tensor], q: Tensor, stat
     scale, shift = _tracer_triple(what, "scale", scale, dim, 1.0), _tracer_triple(what, "shift", shift, dim, 0.0)
     box_lo = _tracer_triple(what, "box_lo", box_lo, dim, float("-inf"))
     box_hi = _tracer_triple(what, "box_hi", box_hi, dim, float("inf"))
-    if every < 0:
-        raise ValueError(f"every: {what}: {every} (0 keeps no series, e > 0 every e-th step)")
-    if max_steps < 0:
-        raise ValueError(f"max_steps: {what}: {max_steps}")
-    if (every > 0) != (series is not None):
-        raise ValueError(f"series: {what}: every = {every} {'needs a' if every else 'takes no'} series buffer")
+    a.lattice(every, max_steps, series, "series", "series")
     if series is not None:
-        _mesh_arg(what, series, "series", torch.float32, dim=3)
+        a.tensor(series, "series", torch.float32, dim=3)
         if tuple(series.shape[1:]) != (n_particles, dim):
             raise ValueError(f"series: {what}: expected [n_slots, {n_particles}, {dim}], got {tuple(series.shape)}")
     if step is not None:
-        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
-            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
-    dev = _mesh_devices(what, ("q", q), ("x0", x0), ("x1", x1), ("status", status), ("stopped", stopped), ("release", release),
+        a.step_index(step)
+    dev = a.same_device(("q", q), ("x0", x0), ("x1", x1), ("status", status), ("stopped", stopped), ("release", release),
                         ("vel", vel), ("step", step), ("series", series), ("grid", grid["pos_sorted"]))
     tr = _lib.g4c_tracer_t(pos_sorted=_lib.ptr(grid["pos_sorted"]), order=_lib.ptr(grid["order"]), cell_start=_lib.ptr(grid["cell_start"]),
                            n_cells=(C.c_int32 * 3)(*grid["n_cells"]), origin=grid["org"], cell_size=float(grid["h"]), dim=dim, k=k,
@@ -1538,32 +1337,27 @@ def voronoi_cells(grid: dict, box, normals: Optional[Tensor] = None, out=None):
     order; `out`: the five tensors to write into.  include/g4c.h has the construction; a cell of more than `_lib.VORONOI_MAX_VERTS`
     vertices gets OVERFLOW and the area +0."""
     what = "voronoi_cells"
-    for key in ("pos_sorted", "order", "cell_start", "n_cells", "org", "h", "dim", "n"):
-        if not isinstance(grid, dict) or key not in grid:
-            raise ValueError(f"grid: {what}: expected the cell grid of the node cloud (synthetic._bin_cloud), got {type(grid).__name__}"
-                             f"{'' if not isinstance(grid, dict) else f' without {key!r}'}")
-    if "periods" in grid:
-        raise ValueError(f"grid: {what}: a periodic grid (control volumes on periodic axes are out of scope)")
-    dim, n = int(grid["dim"]), int(grid["n"])
-    if dim != 2:
-        raise ValueError(f"grid: {what} is 2-D only, the cloud has {dim} dimensions (3-D cells are out of scope)")
-    _mesh_arg(what, grid["pos_sorted"], "grid['pos_sorted']", torch.float32, shape=(n, 2))
-    _mesh_arg(what, grid["order"], "grid['order']", torch.int32, shape=(n,))
-    cells = [int(c) for c in grid["n_cells"]]
+    a = Args(what)
+    if isinstance(grid, dict):          # (this launch's own conditions on the grid as a whole go in front of cell_grid's tensor checks)
+        if "periods" in grid:
+            raise ValueError(f"grid: {what}: a periodic grid (control volumes on periodic axes are out of scope)")
+        if int(grid.get("dim", 2)) != 2:
+            raise ValueError(f"grid: {what} is 2-D only, the cloud has {grid['dim']} dimensions (3-D cells are out of scope)")
+    _, n, cells = a.cell_grid(grid)
     if len(cells) != 3 or not all(c >= 1 for c in cells) or cells[2] != 1:
         raise ValueError(f"grid['n_cells']: {what}: expected [nx, ny, 1] cells, got {cells!r}")
-    _mesh_arg(what, grid["cell_start"], "grid['cell_start']", torch.int32, shape=(cells[0] * cells[1] + 1,))
+    a.cell_start(grid, cells)
     box = _box_arg(what, box)
     if normals is not None:
-        _mesh_arg(what, normals, "normals", torch.float64, shape=(n, 2))
+        a.tensor(normals, "normals", torch.float64, shape=(n, 2))
     shapes = (("out[0]", torch.float64, (n,)), ("out[1]", torch.float64, (n, 2)), ("out[2]", torch.int32, (n,)),
               ("out[3]", torch.uint8, (n,)), ("out[4]", torch.int32, (n,)))
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 5:
             raise ValueError(f"out: {what}: expected the five tensors (area, centroid, nvert, flags, rings)")
         for (name, dtype, shape), t in zip(shapes, out):
-            _mesh_arg(what, t, name, dtype, shape=shape)
-    dev = _mesh_devices(what, ("grid", grid["pos_sorted"]), ("grid['order']", grid["order"]), ("grid['cell_start']", grid["cell_start"]),
+            a.tensor(t, name, dtype, shape=shape)
+    dev = a.same_device(("grid", grid["pos_sorted"]), ("grid['order']", grid["order"]), ("grid['cell_start']", grid["cell_start"]),
                         ("normals", normals), *((name, t) for (name, _, _), t in zip(shapes, out or ())))
     if out is None:
         out = tuple(torch.zeros(shape, dtype=dtype, device=dev) for _, dtype, shape in shapes)
@@ -1590,8 +1384,8 @@ def integral_program(entries, nz: Optional[int] = None) -> "_lib.g4c_integral_pr
             raise ValueError(f"entries: expected a sequence of column pairs (a, b), got {entries!r}") from None
     if not 1 <= len(pairs) <= _lib.INTEGRALS_MAX_ENTRIES:
         raise ValueError(f"entries: expected 1 .. {_lib.INTEGRALS_MAX_ENTRIES} pairs (a, b), got {len(pairs)}")
-    if nz is not None and (isinstance(nz, bool) or not isinstance(nz, int) or nz < 1):
-        raise ValueError(f"nz: expected a number of columns >= 1, got {nz!r}")
+    if nz is not None:
+        _plain.integer(nz, "nz", at_least=1)
     for e, pair in enumerate(pairs):
         if len(pair) != 2 or not all(isinstance(c, int) and not isinstance(c, bool) and c >= -1 for c in pair):
             raise ValueError(f"entries: entry {e}: expected two columns (a, b), each >= 0 or −1 (the constant 1), got {pair!r}")
@@ -1605,31 +1399,18 @@ def integral_program(entries, nz: Optional[int] = None) -> "_lib.g4c_integral_pr
     return p
 
 
-def _integrals_scratch_doubles(n_nodes: int, ne: int) -> int:
-    return 8 + min(max(-(-int(n_nodes) // 256), 1), 1024) * int(ne)
-
-
 def weighted_integrals_scratch(n_nodes: int, ne: int, device) -> Tensor:
     """The `scratch` buffer of `weighted_integrals` for n_nodes rows and ne entries (g4c_weighted_integrals_scratch_doubles)."""
     return torch.zeros(_scratch_doubles("g4c_weighted_integrals_scratch_doubles", n_nodes, ne), dtype=torch.float64, device=device)
 
 
-def _integrals_source(what: str, x, name: str, n_nodes: Optional[int], nz: int, x_step: int, max_steps: int):
+def _integrals_source(a: Args, x, name: str, n_nodes: Optional[int], nz: int, x_step: int, max_steps: int):
     """A source of weighted_integrals: float32 [N, >= nz] (x_step 0) or [N, >= x_step max_steps] (x_step >= nz), rows of unit stride ->
     (N, its leading dimension)."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    a.dtype(x, name, torch.float32)
     if isinstance(x_step, bool) or not isinstance(x_step, int) or not (x_step == 0 or x_step >= nz):
-        raise ValueError(f"{name}_step: {what}: expected 0 (one step) or the columns of a step >= nz = {nz}, got {x_step!r}")
-    need = nz if x_step == 0 else x_step * max_steps
-    if x.dim() != 2 or int(x.size(1)) < need or (n_nodes is not None and int(x.size(0)) != n_nodes):
-        raise ValueError(f"{name}: {what}: expected [{'N' if n_nodes is None else n_nodes}, >= {need}], got shape {tuple(x.shape)}")
-    n, cols = int(x.size(0)), int(x.size(1))
-    if (n > 0 and cols > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) < cols):
-        raise ValueError(f"{name}: {what} needs rows of unit stride, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
-    ld = max(int(x.stride(0)), cols) if n > 1 else cols
-    if ld >= 2 ** 31:
-        raise ValueError(f"{name}: {what}: a row stride of {ld} elements does not fit")
+        raise a.fail(f"{name}_step", f"expected 0 (one step) or the columns of a step >= nz = {nz}, got {x_step!r}")
+    n, _, ld = a.strided_rows(x, name, rows=n_nodes, min_cols=nz if x_step == 0 else x_step * max_steps)
     return n, ld
 
 
@@ -1646,29 +1427,25 @@ def weighted_integrals(x: Tensor, w: Tensor, entries, stats: Tensor, scratch: Te
     what = "weighted_integrals"
     if nz is None:
         nz = x_step if (isinstance(x_step, int) and x_step > 0) else (int(x.size(1)) if torch.is_tensor(x) and x.dim() == 2 else 0)
-    if isinstance(nz, bool) or not isinstance(nz, int) or nz < 1:
-        raise ValueError(f"nz: {what}: expected a number of columns >= 1, got {nz!r}")
+    a = Args(what)
+    a.integer(nz, "nz", at_least=1)
     prog = integral_program(entries, nz)
     ne = int(prog.ne)
-    if not torch.is_tensor(stats) or stats.dtype != torch.float64 or stats.dim() != 2 or int(stats.size(1)) != ne or not stats.is_contiguous():
-        raise ValueError(f"stats: {what}: expected a contiguous float64 [max_steps, ne = {ne}], got {getattr(stats, 'dtype', type(stats).__name__)} "
-                         f"{tuple(getattr(stats, 'shape', ()))}")
+    a.tensor(stats, "stats", torch.float64, dim=2)
+    if int(stats.size(1)) != ne:
+        raise ValueError(f"stats: {what}: expected [max_steps, ne = {ne}], got shape {tuple(stats.shape)}")
     max_steps = int(stats.size(0))
-    n_nodes, x_ld = _integrals_source(what, x, "x", None, nz, x_step, max_steps)
+    n_nodes, x_ld = _integrals_source(a, x, "x", None, nz, x_step, max_steps)
     sub_ld = 0
     if sub is not None:
-        _, sub_ld = _integrals_source(what, sub, "sub", n_nodes, nz, sub_step, max_steps)
-    _mesh_arg(what, w, "w", torch.float64, shape=(n_nodes,))
-    _mesh_arg(what, scratch, "scratch", torch.float64, dim=1)
-    need = _integrals_scratch_doubles(n_nodes, ne)
-    if scratch.numel() < need:
-        raise ValueError(f"scratch: {what}: {scratch.numel()} doubles, needs {need} (weighted_integrals_scratch)")
+        _, sub_ld = _integrals_source(a, sub, "sub", n_nodes, nz, sub_step, max_steps)
+    a.tensor(w, "w", torch.float64, shape=(n_nodes,))
+    a.scratch(scratch, "scratch", record_scratch_doubles(n_nodes, ne), "weighted_integrals_scratch")
     if step is not None:
-        if not torch.is_tensor(step) or step.dtype != torch.int32 or step.dim() != 1 or step.numel() < 1 or not step.is_contiguous():
-            raise ValueError(f"step: {what}: expected a contiguous int32 tensor whose first entry is the step index")
-    elif isinstance(t, bool) or not isinstance(t, int):
-        raise ValueError(f"t: {what}: expected a step index, got {t!r}")
-    dev = _mesh_devices(what, ("x", x), ("sub", sub), ("w", w), ("stats", stats), ("scratch", scratch), ("step", step))
+        a.step_index(step)
+    else:
+        a.integer(t, "t")
+    dev = a.same_device(("x", x), ("sub", sub), ("w", w), ("stats", stats), ("scratch", scratch), ("step", step))
     wi = _lib.g4c_weighted_integrals_t(x=_lib.ptr(x), x_ld=x_ld, x_step=x_step, sub=_lib.ptr(sub), sub_ld=sub_ld, sub_step=sub_step, nz=nz,
                                        w=_lib.ptr(w), step=_lib.ptr(step), t_host=int(t), max_steps=max_steps, stats=_lib.ptr(stats),
                                        scratch=_lib.ptr(scratch))
@@ -1676,17 +1453,16 @@ def weighted_integrals(x: Tensor, w: Tensor, entries, stats: Tensor, scratch: Te
     return stats
 
 
-def _snapshot_rows(what: str, x, name: str):
+def _snapshot_rows(a: Args, x, name: str):
     """A snapshot matrix float32 [rows >= 1, L >= 1] (or [rows, N, nf], read as L = N nf), contiguous -> (rows, L)."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise TypeError(f"{name}: {what}: expected a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    a.dtype(x, name, torch.float32)
     if x.dim() not in (2, 3) or int(x.size(0)) < 1 or x.numel() == 0:
-        raise ValueError(f"{name}: {what}: expected snapshots [rows >= 1, L >= 1] or [rows, N, nf], got shape {tuple(x.shape)}")
+        raise a.fail(name, f"expected snapshots [rows >= 1, L >= 1] or [rows, N, nf], got shape {tuple(x.shape)}")
     if not x.is_contiguous():
-        raise ValueError(f"{name}: {what} needs step-major contiguous snapshots, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
+        raise a.fail(name, f"needs step-major contiguous snapshots, got shape {tuple(x.shape)} strides {tuple(x.stride())}")
     rows, L = int(x.size(0)), x.numel() // int(x.size(0))
     if L > _lib.SNAPSHOT_MAX_COLUMNS:
-        raise NotImplementedError(f"{name}: {what}: L = {L} values in a snapshot (at most {_lib.SNAPSHOT_MAX_COLUMNS})")
+        raise a.fail(name, f"L = {L} values in a snapshot (at most {_lib.SNAPSHOT_MAX_COLUMNS})", NotImplementedError)
     return rows, L
 
 
@@ -1703,16 +1479,15 @@ def _snapshot_sel(what: str, sel, name: str, rows: int) -> "_lib.g4c_snapshot_se
     return _lib.g4c_snapshot_sel_t(rows=rows, first=first, stride=stride, count=count)
 
 
-def _snapshot_vector(what: str, t, name: str, L: int, dev) -> None:
+def _snapshot_vector(a: Args, t, name: str, L: int, dev) -> None:
     """An optional float64 [L] (or [N, nf] with N nf = L), contiguous, on the snapshots' device."""
     if t is None:
         return
-    if not torch.is_tensor(t) or t.dtype != torch.float64:
-        raise TypeError(f"{name}: {what}: expected a float64 tensor or None, got {getattr(t, 'dtype', type(t).__name__)}")
+    a.dtype(t, name, torch.float64)
     if t.numel() != L or not t.is_contiguous():
-        raise ValueError(f"{name}: {what}: expected {L} contiguous values, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+        raise a.fail(name, f"expected {L} contiguous values, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
     if t.device != dev:
-        raise ValueError(f"{name}: {what}: on '{t.device}', the snapshots are on '{dev}'")
+        raise a.fail(name, f"on '{t.device}', the snapshots are on '{dev}'")
 
 
 def snapshot_mean(x: Tensor, sel=None, out: Optional[Tensor] = None) -> Tensor:
@@ -1720,10 +1495,11 @@ def snapshot_mean(x: Tensor, sel=None, out: Optional[Tensor] = None) -> Tensor:
     (sel = (first, stride, count); None: all) of x float32 [rows, L] (or [rows, N, nf]) added in slot order, one division: bit for
     bit the plain fp64 loop."""
     what = "snapshot_mean"
-    rows, L = _snapshot_rows(what, x, "x")
+    a = Args(what, TypeError)
+    rows, L = _snapshot_rows(a, x, "x")
     s = _snapshot_sel(what, sel, "sel", rows)
     dev = x.device
-    _snapshot_vector(what, out, "out", L, dev)
+    _snapshot_vector(a, out, "out", L, dev)
     _lib.require_hip(x)
     if out is None:
         out = torch.empty(L, dtype=torch.float64, device=dev)
@@ -1753,12 +1529,13 @@ def snapshot_gram(a: Tensor, b: Optional[Tensor] = None, *, mean_a: Optional[Ten
     out: float64 [Ma, Mb] with rows of unit stride; scratch: a contiguous uint8 / float64 buffer of at least
     `snapshot_gram_scratch_bytes` bytes (allocated here when None)."""
     what = "snapshot_gram"
+    a_ = Args(what, TypeError)
     if b is None:
         if mean_b is not None or sel_b is not None:
             raise ValueError(f"mean_b: {what}: mean_b / sel_b were given without b")
         b, mean_b, sel_b = a, mean_a, sel_a
-    rows_a, L = _snapshot_rows(what, a, "a")
-    rows_b, Lb = _snapshot_rows(what, b, "b")
+    rows_a, L = _snapshot_rows(a_, a, "a")
+    rows_b, Lb = _snapshot_rows(a_, b, "b")
     if Lb != L:
         raise ValueError(f"b: {what}: snapshots of {Lb} values, a's hold {L}")
     sa, sb = _snapshot_sel(what, sel_a, "sel_a", rows_a), _snapshot_sel(what, sel_b, "sel_b", rows_b)
@@ -1769,13 +1546,12 @@ def snapshot_gram(a: Tensor, b: Optional[Tensor] = None, *, mean_a: Optional[Ten
     if b.device != dev:
         raise ValueError(f"b: {what}: on '{b.device}', a is on '{dev}'")
     for t, name in ((mean_a, "mean_a"), (mean_b, "mean_b"), (w, "w")):
-        _snapshot_vector(what, t, name, L, dev)
+        _snapshot_vector(a_, t, name, L, dev)
+    ld = sb.count
     if out is not None:
-        if not torch.is_tensor(out) or out.dtype != torch.float64 or out.device != dev:
-            raise TypeError(f"out: {what}: expected a float64 tensor on '{dev}', got {getattr(out, 'dtype', type(out).__name__)}")
-        if tuple(out.shape) != (sa.count, sb.count) or (sb.count > 1 and out.stride(1) != 1) or (sa.count > 1 and out.stride(0) < sb.count):
-            raise ValueError(f"out: {what}: expected [{sa.count}, {sb.count}] with rows of unit stride, got shape {tuple(out.shape)} strides "
-                             f"{tuple(out.stride())}")
+        if torch.is_tensor(out) and out.device != dev:
+            raise TypeError(f"out: {what}: on '{out.device}', a is on '{dev}'")
+        _, _, ld = a_.strided_rows(out, "out", torch.float64, rows=sa.count, cols=sb.count)
     # (g4c_snapshot_gram_scratch_bytes restated, so that a scratch that is too small is refused before the library is touched)
     nbi, nbj = -(-sa.count // _lib.SNAPSHOT_GRAM_BLOCK), -(-sb.count // _lib.SNAPSHOT_GRAM_BLOCK)
     blocks = nbi * (nbi + 1) // 2 if _gram_symmetric(a, mean_a, sa, b, mean_b, sb) else nbi * nbj
@@ -1788,7 +1564,6 @@ def snapshot_gram(a: Tensor, b: Optional[Tensor] = None, *, mean_a: Optional[Ten
         out = torch.empty((sa.count, sb.count), dtype=torch.float64, device=dev)
     if scratch is None:
         scratch = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    ld = int(out.stride(0)) if sa.count > 1 else sb.count
     _lib.check(_lib.load().g4c_snapshot_gram(_lib.ptr(a), _lib.ptr(mean_a), C.byref(sa), _lib.ptr(b), _lib.ptr(mean_b), C.byref(sb), _lib.ptr(w),
                                              L, _lib.ptr(out), ld, _lib.ptr(scratch), _lib.stream_handle(dev)))
     return out
@@ -1799,30 +1574,25 @@ def snapshot_combine(x: Tensor, coef: Tensor, *, mean: Optional[Tensor] = None, 
     float32 [rows, L] in slot order; coef float64 [count, R] with rows of unit stride (on the device), mean float64 [L] or None.
     Product and sum are rounded separately: bit for bit a plain fp64 loop rounded once to fp32."""
     what = "snapshot_combine"
-    rows, L = _snapshot_rows(what, x, "x")
+    a = Args(what, TypeError)
+    rows, L = _snapshot_rows(a, x, "x")
     s = _snapshot_sel(what, sel, "sel", rows)
     dev = x.device
-    if not torch.is_tensor(coef) or coef.dtype != torch.float64:
-        raise TypeError(f"coef: {what}: expected a float64 tensor, got {getattr(coef, 'dtype', type(coef).__name__)}")
-    if coef.dim() != 2 or int(coef.size(0)) != s.count or int(coef.size(1)) < 1 or (coef.size(1) > 1 and coef.stride(1) != 1) \
-            or (s.count > 1 and coef.stride(0) < coef.size(1)):
-        raise ValueError(f"coef: {what}: expected [count = {s.count}, R >= 1] with rows of unit stride, got shape {tuple(coef.shape)} strides "
-                         f"{tuple(coef.stride())}")
+    _, R, ldc = a.strided_rows(coef, "coef", torch.float64, rows=s.count)
     if coef.device != dev:
         raise ValueError(f"coef: {what}: on '{coef.device}', the snapshots are on '{dev}'")
-    R = int(coef.size(1))
     if R > _lib.SNAPSHOT_MAX_ROWS or s.count > _lib.SNAPSHOT_MAX_ROWS:
         raise NotImplementedError(f"coef: {what}: {s.count} snapshots into {R} combinations (at most {_lib.SNAPSHOT_MAX_ROWS} each)")
-    _snapshot_vector(what, mean, "mean", L, dev)
+    _snapshot_vector(a, mean, "mean", L, dev)
     if out is not None:
-        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev:
-            raise TypeError(f"out: {what}: expected a float32 tensor on '{dev}', got {getattr(out, 'dtype', type(out).__name__)}")
-        if out.numel() != R * L or int(out.size(0)) != R or not out.is_contiguous():
-            raise ValueError(f"out: {what}: expected a contiguous [{R}, {L}], got shape {tuple(out.shape)} strides {tuple(out.stride())}")
+        if torch.is_tensor(out) and out.device != dev:
+            raise TypeError(f"out: {what}: on '{out.device}', the snapshots are on '{dev}'")
+        a.tensor(out, "out", torch.float32)
+        if out.numel() != R * L or int(out.size(0)) != R:
+            raise ValueError(f"out: {what}: expected a contiguous [{R}, {L}], got shape {tuple(out.shape)}")
     _lib.require_hip(x)
     if out is None:
         out = torch.empty((R, L), dtype=torch.float32, device=dev)
-    ldc = int(coef.stride(0)) if s.count > 1 else R
     _lib.check(_lib.load().g4c_snapshot_combine(_lib.ptr(x), _lib.ptr(mean), C.byref(s), _lib.ptr(coef), ldc, R, L, _lib.ptr(out),
                                                 _lib.stream_handle(dev)))
     return out

@@ -126,7 +126,7 @@ class PointSampler:
         attribute is None, and `dim`, `power` are None)."""
         if isinstance(n_nodes, bool) or not isinstance(n_nodes, int) or n_nodes < 0:
             raise ValueError(f"n_nodes: expected a number of nodes >= 0, got {n_nodes!r}")
-        k, n_points = ops._sample_tables("PointSampler.from_tables", idx, coef)
+        k, n_points = ops._sample_tables(ops.Args("PointSampler.from_tables"), idx, coef)
         if idx.device.type != "cuda" or coef.device != idx.device:
             raise ValueError(f"idx: PointSampler runs on a HIP device only, idx is on '{idx.device}' and coef on '{coef.device}' "
                              "(there is no CPU fallback)")
