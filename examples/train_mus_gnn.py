@@ -6,7 +6,8 @@ The NsCircle HDF5 file is replaced by a synthetic array in the same record layou
 code | u v p per time step], NaN-padded to the largest mesh): decaying travelling waves on random point clouds — there is no
 network / h5py here; with the real file pass path="NsCircle.h5" instead of data=.
 
-    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss | --force-loss | --residual-loss]
+    python examples/train_mus_gnn.py [--samples 24] [--nodes 3000] [--epochs 8] [--flow-loss | --sample-loss | --force-loss | --residual-loss |
+                                                                                         --integral-loss]
 
 --flow-loss trains with gfd.nn.FlowLoss: GraphLoss plus a continuity penalty (the divergence of the predicted velocity) and a
 vorticity-matching term, both through the differentiable least-squares mesh gradient (gfd.MeshGradient).  The mesh is periodic in y,
@@ -30,6 +31,13 @@ quadratic-fit operator (gfd.MeshJet) on its own stencil of the 12 nearest nodes 
 seam: the nodes next to the seam in y get a one-sided stencil (ResidualLoss(period=(None, "auto")) wraps it; on the graph's own periodic
 edges, k=None with edge_vectors="edge_attr", six neighbours condition five unknowns badly).  The fields are in their scaled units; pass scale= and shift= to
 weigh the terms as the physical equation does.
+
+--integral-loss trains with gfd.nn.IntegralLoss: GraphLoss plus the area-weighted MSE — every node's error weighted by its control volume
+(gfd.ControlVolumes: the Voronoi cell of the node within its graph's cloud, clipped to the cloud's bounding box), so the loss is the mesh-independent
+L2 error a rollout reports and not a count of nodes — and the mismatch of the kinetic energy per unit area, through the differentiable domain
+integrals.  The cells are built from `graph.pos` of every batch, after the augmentations; they know no seam: the nodes next to the seam in y get
+the cell the box leaves them (periodic cells are out of scope), and the derivative-based terms ('enstrophy', 'div2') would take
+edge_vectors="edge_attr" as --flow-loss does.
 """
 import argparse, math, os, sys
 import torch
@@ -43,9 +51,10 @@ ap.add_argument("--flow-loss", action="store_true", help="train with FlowLoss (c
 ap.add_argument("--sample-loss", action="store_true", help="train with SampleLoss (GraphLoss plus the error on a raster over the wake) instead of GraphLoss")
 ap.add_argument("--force-loss", action="store_true", help="train with ForceLoss (GraphLoss plus the error of the loads on the cylinder) instead of GraphLoss")
 ap.add_argument("--residual-loss", action="store_true", help="train with ResidualLoss (GraphLoss plus the momentum and continuity residuals) instead of GraphLoss")
+ap.add_argument("--integral-loss", action="store_true", help="train with IntegralLoss (GraphLoss plus the area-weighted MSE and the kinetic-energy mismatch) instead of GraphLoss")
 a = ap.parse_args()
-if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss > 1:
-    ap.error("--flow-loss, --sample-loss, --force-loss and --residual-loss are separate runs")
+if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss + a.integral_loss > 1:
+    ap.error("--flow-loss, --sample-loss, --force-loss, --residual-loss and --integral-loss are separate runs")
 T = 20                                                        # time steps per simulation
 # a 64 x 32 raster over the wake of the cylinder at (1, 0.5), in the coordinates of graph.pos
 WAKE = torch.stack(torch.meshgrid(torch.linspace(1.2, 3.0, 64), torch.linspace(0.1, 0.9, 32), indexing="ij"), -1).reshape(-1, 2)
@@ -59,6 +68,7 @@ train_config = gfd.nn.TrainConfig(
                        if a.flow_loss else gfd.nn.losses.SampleLoss(WAKE, lambda_d=0.25, weight=1.0) if a.sample_loss
                        else gfd.nn.losses.ForceLoss(lambda_d=0.25, weight=1.0, pressure=2, wall={"pressure": 0.5}) if a.force_loss
                        else gfd.nn.losses.ResidualLoss(lambda_d=0.25, weight=1e-3, nu=1e-3, dt=0.1, pressure=2) if a.residual_loss
+                       else gfd.nn.losses.IntegralLoss(lambda_d=0.25, terms={"mse": 1.0, "ke": 0.5}) if a.integral_loss
                        else gfd.nn.losses.GraphLoss(lambda_d=0.25)),
     validation_loss = gfd.nn.losses.GraphLoss(),
     epochs          = a.epochs,

@@ -195,6 +195,12 @@ class g4c_weighted_integrals_t(C.Structure):
                 ("max_steps", C.c_int32), ("stats", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class g4c_weighted_integrals_adjoint_t(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_ld", C.c_int32), ("x_step", C.c_int32), ("sub", C.c_void_p), ("sub_ld", C.c_int32),
+                ("sub_step", C.c_int32), ("nz", C.c_int32), ("w", C.c_void_p), ("g", C.c_void_p), ("n_groups", C.c_int32),
+                ("group", C.c_void_p), ("t_host", C.c_int32), ("max_steps", C.c_int32), ("gx", C.c_void_p), ("gx_ld", C.c_int32)]
+
+
 # g4c_snapshot_* (csrc/snapshot_modes.hip): the envelope and the tile sizes the tests walk
 SNAPSHOT_MAX_ROWS = 1024                           # G4C_SNAPSHOT_MAX_ROWS: Ma, Mb, R
 SNAPSHOT_MAX_COLUMNS = 2 ** 31 - 1                 # G4C_SNAPSHOT_MAX_COLUMNS: L
@@ -280,6 +286,8 @@ _SIGNATURES = {
     "g4c_voronoi_cells": (C.c_int, [C.POINTER(g4c_voronoi_cells_t), C.c_int64, C.c_void_p]),
     "g4c_weighted_integrals_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
     "g4c_weighted_integrals": (C.c_int, [C.POINTER(g4c_weighted_integrals_t), C.POINTER(g4c_integral_program_t), C.c_int64, C.c_void_p]),
+    "g4c_weighted_integrals_adjoint": (C.c_int, [C.POINTER(g4c_weighted_integrals_adjoint_t), C.POINTER(g4c_integral_program_t), C.c_int64,
+                                                 C.c_void_p]),
     "g4c_snapshot_mean": (C.c_int, [C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_int64, C.c_void_p, C.c_void_p]),
     "g4c_snapshot_gram_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "g4c_snapshot_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t), C.c_void_p, C.c_void_p, C.POINTER(g4c_snapshot_sel_t),

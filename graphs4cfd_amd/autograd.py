@@ -640,6 +640,39 @@ def body_wall(op, x: Tensor) -> Tensor:
     return _BodyForces.apply(x, op, True)
 
 
+# ------------------------------------------------------------------------------------- domain integrals
+class _WeightedIntegrals(torch.autograd.Function):
+    """`ControlVolumes.integrate`: today's launch(es) forward, ONE launch of the transpose (g4c_weighted_integrals_adjoint) backward.
+    Unlike the linear operators above the map is quadratic in x: x is saved, and `sub` when there is one."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, volumes, prog, sub, args):
+        ctx.volumes, ctx.prog, ctx.args = volumes, prog, args
+        ctx.cols = int(x.size(1))
+        ctx.has_sub = sub is not None
+        ctx.save_for_backward(*((x,) if sub is None else (x, sub)))
+        nz, x_step, sub_step, t, weights, per_graph = args
+        return volumes._integrate(x.detach(), prog, sub, nz, x_step, sub_step, t, weights, per_graph)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        x, *rest = ctx.saved_tensors
+        nz, x_step, sub_step, t, weights, per_graph = ctx.args
+        gx = ctx.volumes.adjoint(g.contiguous(), x, ctx.prog, sub=rest[0] if ctx.has_sub else None, nz=nz, x_step=x_step, sub_step=sub_step,
+                                 t=t, per_graph=per_graph, weights=weights)
+        c0, width = x_step * t, int(gx.size(1))
+        if c0 != 0 or width != ctx.cols:          # (the sample is a window of wider rows: the columns beside it get zero)
+            full = torch.zeros((int(gx.size(0)), ctx.cols), dtype=gx.dtype, device=gx.device)
+            full[:, c0:c0 + width] = gx
+            gx = full
+        return gx, None, None, None, None
+
+
+def weighted_integrals(volumes, x: Tensor, prog, sub, nz, x_step, sub_step, t, weights, per_graph) -> Tensor:
+    return _WeightedIntegrals.apply(x, volumes, prog, None if sub is None else sub.detach(), (nz, x_step, sub_step, t, weights, per_graph))
+
+
 # ------------------------------------------------------------------------------------- gathers / interpolation / projections
 # (gMuS-GNN and REMuS-GNN: nn/mugs_gnn.py restriction + knn_interpolate, nn/blocks.py:34-48,88-114,408-456).  Forward: the
 # inference kernels.  The adjoints are linear maps with static coefficients: an elementwise product (torch) followed, where rows

@@ -9,8 +9,12 @@ can cut the polygon, in fp64 on the fp32 positions — exact for any cloud and a
 
 `integrate(x, entries)` is the standalone form of the rollout's per-step launch (`g4c_weighted_integrals`): fp64 sums of
 area · z[a] · z[b] in a fixed order.  The wall half-plane is tangent: round a convex body it leaves slivers between tangent and wall,
-so Σ area falls short of (box − bodies) by a little (tests/VOLUMES_MEASURED.md has the closure).  2-D only; periodic axes, 3-D cells
-and anything differentiable are out of scope."""
+so Σ area falls short of (box − bodies) by a little (tests/VOLUMES_MEASURED.md has the closure).
+
+The integrals are differentiable in x (the areas are constants of the mesh): `adjoint(g, x, entries)` is the transpose of `integrate`
+at x (`g4c_weighted_integrals_adjoint`: one launch, fp64 in a pinned order), `integrate` of a tensor that requires a gradient is
+recorded for autograd, and `integrate(..., per_graph=True)` keeps the graphs of a collated batch apart — what `gfd.nn.IntegralLoss`
+trains against.  2-D only; periodic axes and 3-D cells are out of scope."""
 from __future__ import annotations
 
 from typing import Optional
@@ -85,8 +89,9 @@ class ControlVolumes:
     `area` float64 [N], `centroid` float64 [N, 2], `nvert` int32 [N], `flags` uint8 [N] (bits `BOX`: the box cut the cell, `WALL`,
     `DUPLICATE`: another node at the same position — the pair shares one cell, each gets all of it —, `OVERFLOW`: more than
     `_lib.VORONOI_MAX_VERTS` vertices, area +0), `rings` int32 [N], `degenerate` bool [N] (area == 0), `total` (Σ area, a float),
-    `box` float64 [graphs, 4].  `integrate(x, entries)` [ne] float64: Σ_i area_i · x[i, a] · x[i, b] per entry (a, b), −1 for 1;
-    `weights(dtype)` the areas for `Modes(node_weights=)`."""
+    `box` float64 [graphs, 4], `counts` (the nodes of every graph, a list), `group` int32 [N] (the graph of every node).
+    `integrate(x, entries)` [ne] float64: Σ_i area_i · x[i, a] · x[i, b] per entry (a, b), −1 for 1 (`per_graph=True`: [graphs, ne]);
+    `adjoint(g, x, entries)` its transpose; `weights(dtype)` the areas for `Modes(node_weights=)`."""
 
     BOX, WALL, DUPLICATE, OVERFLOW = _lib.VORONOI_BOX, _lib.VORONOI_WALL, _lib.VORONOI_DUPLICATE, _lib.VORONOI_OVERFLOW
 
@@ -131,28 +136,79 @@ class ControlVolumes:
         self.box = torch.tensor(boxes, dtype=torch.float64)
         self.degenerate = self.area == 0
         self.total = float(self.area.sum())
+        self.counts = [int(c) for c in spec["counts"]]
+        self.group = torch.repeat_interleave(torch.arange(len(self.counts), dtype=torch.int32, device=dev),
+                                             torch.tensor(self.counts, device=dev), output_size=n)
 
     def weights(self, dtype=torch.float64) -> torch.Tensor:
         """The areas [N] as `dtype`: the `node_weights` of `gfd.Modes`."""
         return self.area.to(dtype)
 
     def integrate(self, x: torch.Tensor, entries, *, sub: Optional[torch.Tensor] = None, nz: Optional[int] = None, x_step: int = 0,
-                  sub_step: int = 0, t: int = 0, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  sub_step: int = 0, t: int = 0, weights: Optional[torch.Tensor] = None, per_graph: bool = False) -> torch.Tensor:
         """[ne] float64: Σ_i area_i · z_i[a] · z_i[b] for every entry (a, b) of `entries` (a column of −1 stands for 1), z the rows of
         x float32 [N, >= nz] — or of x − sub, formed in fp64.  With x_step = nf, x holds every step (a target) and `t` names the step.
-        The standalone form of the rollout's launch (`ops.weighted_integrals`): the same order, the same bits."""
+        The standalone form of the rollout's launch (`ops.weighted_integrals`): the same order, the same bits.
+
+        `per_graph=True`: [G, ne], row q the integrals over graph q of the batch alone — one launch over its (contiguous) row range,
+        bit for bit what a `ControlVolumes` of that graph returns.  When gradients are enabled and x requires one, the call is
+        recorded (`autograd._WeightedIntegrals`: the same launches on x.detach(), the same bits; `adjoint` in the backward, which
+        keeps x and `sub` — the map is quadratic); a `sub` that requires a gradient is a ValueError: subtract it in torch instead."""
         prog = ops.integral_program(entries, nz)
+        self._check_x(x, t)
+        if not isinstance(per_graph, bool):
+            raise ValueError(f"per_graph: expected a bool, got {per_graph!r}")
+        if torch.is_tensor(sub) and sub.requires_grad and torch.is_grad_enabled():
+            raise ValueError("sub: a `sub` that requires a gradient is not differentiated through: pass x − sub as x, or detach it")
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd
+            return autograd.weighted_integrals(self, x, prog, sub, nz, x_step, sub_step, t, weights, per_graph)
+        return self._integrate(x, prog, sub, nz, x_step, sub_step, t, weights, per_graph)
+
+    def _check_x(self, x, t):
         if not torch.is_tensor(x) or x.dim() != 2 or int(x.size(0)) != self.n_nodes:
             raise ValueError(f"x: expected a float32 tensor [{self.n_nodes}, >= 1], got {getattr(x, 'dtype', type(x).__name__)} "
                              f"{tuple(getattr(x, 'shape', ()))}")
         if isinstance(t, bool) or not isinstance(t, int) or t < 0:
             raise ValueError(f"t: expected a step index >= 0, got {t!r}")
+
+    def _integrate(self, x, prog, sub, nz, x_step, sub_step, t, weights, per_graph):
         dev = self.area.device
-        stats = torch.zeros((t + 1, int(prog.ne)), dtype=torch.float64, device=dev)
-        scratch = ops.weighted_integrals_scratch(self.n_nodes, int(prog.ne), dev)
-        ops.weighted_integrals(x, self.area if weights is None else weights, prog, stats, scratch, nz=nz, sub=sub, x_step=x_step,
-                               sub_step=sub_step, t=t)
-        return stats[t]
+        w = self.area if weights is None else weights
+        ne = int(prog.ne)
+        if not per_graph:
+            stats = torch.zeros((t + 1, ne), dtype=torch.float64, device=dev)
+            scratch = ops.weighted_integrals_scratch(self.n_nodes, ne, dev)
+            ops.weighted_integrals(x, w, prog, stats, scratch, nz=nz, sub=sub, x_step=x_step, sub_step=sub_step, t=t)
+            return stats[t]
+        if not torch.is_tensor(w) or w.dim() != 1 or int(w.size(0)) != self.n_nodes:
+            raise ValueError(f"weights: expected a float64 tensor [{self.n_nodes}], got {tuple(getattr(w, 'shape', ()))}")
+        if torch.is_tensor(sub) and (sub.dim() != 2 or int(sub.size(0)) != self.n_nodes):
+            raise ValueError(f"sub: expected a float32 tensor [{self.n_nodes}, >= 1], got {tuple(sub.shape)}")
+        stats = torch.zeros((len(self.counts), t + 1, ne), dtype=torch.float64, device=dev)
+        scratch = ops.weighted_integrals_scratch(max(self.counts), ne, dev)          # (the launches follow each other on one stream)
+        a = 0
+        for q, c in enumerate(self.counts):          # (contiguous ranges: `collate` numbers the nodes graph after graph)
+            ops.weighted_integrals(x[a:a + c], w[a:a + c], prog, stats[q], scratch, nz=nz, sub=None if sub is None else sub[a:a + c],
+                                   x_step=x_step, sub_step=sub_step, t=t)
+            a += c
+        return stats[:, t]
+
+    def adjoint(self, g: torch.Tensor, x: torch.Tensor, entries, *, sub: Optional[torch.Tensor] = None, nz: Optional[int] = None,
+                x_step: int = 0, sub_step: int = 0, t: int = 0, per_graph: bool = False,
+                weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The transpose of `integrate` at x: gx float32 [N, nz] = the derivative of Σ g · integrate(x, entries, ...) by the sample's
+        columns (x's columns x_step · t .. + nz), for g float64 [ne] — or [G, ne] with `per_graph=True`.  One launch
+        (`ops.weighted_integrals_adjoint`), fp64 in a fixed order, no atomics: the same bits on every run."""
+        prog = ops.integral_program(entries, nz)
+        self._check_x(x, t)
+        ne, groups = int(prog.ne), (len(self.counts) if per_graph else 1)
+        if not torch.is_tensor(g) or g.dtype != torch.float64 or tuple(g.shape) != ((groups, ne) if per_graph else (ne,)):
+            raise ValueError(f"g: expected a float64 tensor {[groups, ne] if per_graph else [ne]}, got "
+                             f"{getattr(g, 'dtype', type(g).__name__)} {tuple(getattr(g, 'shape', ()))}")
+        return ops.weighted_integrals_adjoint(x.detach(), self.area if weights is None else weights, prog,
+                                              g.detach().reshape(groups, ne).contiguous(), nz=nz, sub=None if sub is None else sub.detach(),
+                                              x_step=x_step, sub_step=sub_step, t=t, group=self.group if per_graph else None)
 
     def __repr__(self):
         return f"ControlVolumes(nodes={self.n_nodes}, graphs={int(self.box.size(0))}, total={self.total:.6g})"

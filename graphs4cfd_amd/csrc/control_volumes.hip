@@ -3,7 +3,8 @@
 //                           one half-plane through the node itself — a wall node's cell must not reach into the body), its area,
 //                           centroid, vertex count, flags and the rings of the cell grid it walked;
 //   g4c_weighted_integrals  per step: stats[t][e] = sum_i w_i z_i[a_e] z_i[b_e] for up to 8 entries, fp64 in a fixed order — one more
-//                           part of the captured step (the step index is read on the device and never written).
+//                           part of the captured step (the step index is read on the device and never written);
+//   g4c_weighted_integrals_adjoint  training: gx[i][c] = the derivative of Σ_q Σ_e g[q][e] I[q][e] by x[i][c], fp64 in a fixed order.
 // A kNN cloud has no cells: the areas are what turns the node sums of the diagnostics into integrals over the domain.
 //
 // The construction does not search a fixed k.  One thread per node walks the rings of the caller's cell grid (the binned cloud of
@@ -251,6 +252,83 @@ void wi_launch(const g4c_weighted_integrals_t &wi, const g4c_integral_program_t 
     g4c::partials_kernel<g4c::all_sums, NE, true><<<dim3(1), dim3(WI_THREADS), 0, s>>>(wi.scratch, blocks, NE, wi.stats, wi.max_steps);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ integrals, transposed
+// gx[i][c] = d (Σ_q Σ_e g[q][e] I[q][e]) / d x[i][c].  One thread per (node, column): item n nz + c of the [n_nodes, nz] block, so the lanes
+// of a wave store consecutive floats of gx (gx_ld == nz: whole cache lines; a thread per node would store with a stride of nz floats).
+// The three or four threads of a node read the same w, group, g and x: one cache line, fetched once.
+constexpr int WA_THREADS = g4c::THREADS;
+
+__global__ __launch_bounds__(WA_THREADS) void weighted_integrals_adjoint_kernel(
+    const float *__restrict__ x, int x_ld, long long x_off, const float *__restrict__ sub, int sub_ld, long long sub_off, int nz,
+    const double *__restrict__ w, const double *__restrict__ g, int n_groups, const int *__restrict__ group,
+    const g4c_integral_program_t kp, long long n_nodes, float *__restrict__ gx, int gx_ld) {
+    // The program is read from LDS, as in the forward (held in scalar registers over the loops it spilt them there) — once, into the
+    // thread's own registers: the loops below are unrolled over the 8 slots, a slot behind the program's end names no column.
+    __shared__ g4c_integral_program_t sp;
+    if (threadIdx.x == 0) sp = kp;
+    __syncthreads();
+    const int ne = sp.ne;
+    int pa[WI_MAX_ENTRIES], pb[WI_MAX_ENTRIES];
+#pragma unroll
+    for (int e = 0; e < WI_MAX_ENTRIES; ++e) {
+        pa[e] = e < ne ? sp.a[e] : -2;
+        pb[e] = e < ne ? sp.b[e] : -2;
+    }
+    // the workgroup's first item as (node, column), advanced by the grid's stride without a division in the loop
+    const long long stride = (long long)gridDim.x * WA_THREADS;
+    const long long dq = stride / nz;
+    const int dr = (int)(stride - dq * nz);
+    long long n0 = ((long long)blockIdx.x * WA_THREADS) / nz;
+    int c0 = (int)((long long)blockIdx.x * WA_THREADS - n0 * nz);
+    for (; n0 < n_nodes; n0 += dq, c0 += dr) {
+        if (c0 >= nz) { c0 -= nz; ++n0; }
+        const unsigned l = threadIdx.x + (unsigned)c0;
+        const unsigned dn = l / (unsigned)nz;
+        const long long n = n0 + dn;
+        const int c = (int)(l - dn * (unsigned)nz);
+        if (n >= n_nodes) continue;          // (no barrier below)
+        const double wn = w[n];
+        const int q = group ? group[n] : 0;
+        double acc = 0.0;
+        // a row of zero weight, or of a group outside [0, n_groups), is +0 whatever it holds: nothing of it is read
+        if (wn != 0.0 && q >= 0 && q < n_groups) {
+            const float *xr = x + n * x_ld + x_off;
+            const float *sr = sub ? sub + n * sub_ld + sub_off : nullptr;
+            const double *gq = g + (long long)q * ne;
+            // First the loads of all 8 slots, in flight together and without a branch: a slot that does not name column c (or lies
+            // behind the program's end) reads a valid address of the same cache lines — g of the last entry, the sample's column 0 —
+            // and is then SKIPPED by a select, not multiplied by zero.  Then the sums, in the order of the entries.  The other column
+            // of an entry is b when a == c and a when b == c (a == b == c: the same sample twice).
+            const float *sq = sr ? sr : xr;
+            double ge[WI_MAX_ENTRIES];
+            float xo[WI_MAX_ENTRIES], so[WI_MAX_ENTRIES];
+#pragma unroll
+            for (int e = 0; e < WI_MAX_ENTRIES; ++e) {
+                const int o = pa[e] == c ? pb[e] : pa[e];
+                const int os = o > 0 ? o : 0;
+                ge[e] = gq[e < ne ? e : ne - 1];
+                xo[e] = xr[os];
+                so[e] = sq[os];
+            }
+#pragma unroll
+            for (int e = 0; e < WI_MAX_ENTRIES; ++e) {
+                const bool ha = pa[e] == c, hb = pb[e] == c;
+                const int o = ha ? pb[e] : pa[e];
+                double z = (double)xo[e];
+                if (sr) z = z - (double)so[e];
+                z = o >= 0 ? z : 1.0;
+                const double gw = ge[e] * wn;
+                const double term = gw * z;
+                const double one = acc + term;
+                acc = ha ? one : acc;
+                const double two = acc + term;
+                acc = hb ? two : acc;
+            }
+        }
+        gx[n * gx_ld + c] = (float)acc;
+    }
+}
+
 }  // namespace
 
 extern "C" int g4c_voronoi_cells(const g4c_voronoi_cells_t *vc, int64_t n_nodes, void *stream) {
@@ -318,5 +396,37 @@ extern "C" int g4c_weighted_integrals(const g4c_weighted_integrals_t *wi, const 
         case 7: wi_launch<7>(*wi, *prog, n_nodes, s); break;
         default: wi_launch<8>(*wi, *prog, n_nodes, s); break;
     }
+    return g4c::check_launch(me);
+}
+
+extern "C" int g4c_weighted_integrals_adjoint(const g4c_weighted_integrals_adjoint_t *wa, const g4c_integral_program_t *prog, int64_t n_nodes,
+                                              void *stream) {
+    const char *me = "g4c_weighted_integrals_adjoint";
+    G4C_REQUIRE(wa && prog, G4C_EINVAL, "%s: null pointer", me);
+    G4C_REQUIRE(n_nodes >= 0 && wa->nz >= 1 && n_nodes <= (1LL << 62) / wa->nz && wa->max_steps >= 0 && prog->ne >= 1 && wa->n_groups >= 1,
+                G4C_EINVAL, "%s: bad sizes n_nodes=%lld nz=%d max_steps=%d ne=%d n_groups=%d", me, (long long)n_nodes, wa->nz, wa->max_steps,
+                prog->ne, wa->n_groups);
+    G4C_REQUIRE(prog->ne <= WI_MAX_ENTRIES, G4C_EUNSUPPORTED, "%s: ne=%d entries (1 .. %d are supported)", me, prog->ne, WI_MAX_ENTRIES);
+    for (int e = 0; e < prog->ne; ++e)
+        G4C_REQUIRE(prog->a[e] >= -1 && prog->a[e] < wa->nz && prog->b[e] >= -1 && prog->b[e] < wa->nz, G4C_EINVAL,
+                    "%s: entry %d = (%d, %d) outside [-1, nz = %d)", me, e, prog->a[e], prog->b[e], wa->nz);
+    // the step is the host's: every address of the launch is formed from it, so it is refused here and not skipped on the device
+    G4C_REQUIRE(wa->t_host >= 0 && wa->t_host < wa->max_steps, G4C_EINVAL, "%s: step t_host=%d outside [0, max_steps = %d)", me, wa->t_host,
+                wa->max_steps);
+    G4C_REQUIRE(wa->x_step == 0 ? wa->x_ld >= wa->nz : (wa->x_step >= wa->nz && (long long)wa->x_ld >= (long long)wa->x_step * wa->max_steps),
+                G4C_EINVAL, "%s: x_ld=%d x_step=%d for nz=%d columns and max_steps=%d", me, wa->x_ld, wa->x_step, wa->nz, wa->max_steps);
+    if (wa->sub)
+        G4C_REQUIRE(wa->sub_step == 0 ? wa->sub_ld >= wa->nz
+                                      : (wa->sub_step >= wa->nz && (long long)wa->sub_ld >= (long long)wa->sub_step * wa->max_steps),
+                    G4C_EINVAL, "%s: sub_ld=%d sub_step=%d for nz=%d columns and max_steps=%d", me, wa->sub_ld, wa->sub_step, wa->nz,
+                    wa->max_steps);
+    G4C_REQUIRE(wa->gx_ld >= wa->nz, G4C_EINVAL, "%s: gx_ld=%d for nz=%d columns", me, wa->gx_ld, wa->nz);
+    if (n_nodes == 0) return G4C_OK;
+    G4C_REQUIRE(wa->x && wa->w && wa->g && wa->gx, G4C_EINVAL, "%s: null pointer", me);
+    g4c::DeviceGuard on_device(wa->gx);
+    const unsigned blocks = (unsigned)g4c::blocks_or_one(n_nodes * wa->nz);
+    weighted_integrals_adjoint_kernel<<<dim3(blocks), dim3(WA_THREADS), 0, (hipStream_t)stream>>>(
+        wa->x, wa->x_ld, (long long)wa->x_step * wa->t_host, wa->sub, wa->sub_ld, (long long)wa->sub_step * wa->t_host, wa->nz, wa->w, wa->g,
+        wa->n_groups, wa->group, *prog, n_nodes, wa->gx, wa->gx_ld);
     return g4c::check_launch(me);
 }

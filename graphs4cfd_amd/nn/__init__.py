@@ -6,4 +6,4 @@ from .remus_gnn import NsRotEquiTreeScaleGNN
 from .model import GNN, TrainConfig, collate, Rollout, RolloutErrors, RolloutMoments, RolloutDerived, RolloutSpectrum, RolloutSamples, RolloutForces, RolloutIntegrals, Spectrum
 from ..tracers import RolloutTracers
 from ..modes import Modes, SnapshotModes, DynamicModes
-from .losses import FlowLoss, ForceLoss, GraphLoss, ResidualLoss, SampleLoss
+from .losses import FlowLoss, ForceLoss, GraphLoss, IntegralLoss, ResidualLoss, SampleLoss

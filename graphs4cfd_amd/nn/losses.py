@@ -654,3 +654,231 @@ class ResidualLoss(_OperatorLoss):
             term = term + self.continuity * ((c.square() * keep).sum() / count)
         term = self.weight * term
         return term if loss is None else loss + term
+
+
+class IntegralLoss(_OperatorLoss):
+    """`GraphLoss(lambda_d)` plus errors of integrals over the domain — the node rows weighted by their control volumes
+    (`gfd.ControlVolumes`: the Voronoi areas of the cloud), so that a refined wake or boundary layer counts by the area it covers
+    and not by its node count (new functionality — the reference has none):
+
+        node_weight · GraphLoss(lambda_d)(graph, pred, target) + weight · Σ_name terms[name] · T_name
+
+    Every T_name is the mean over the graphs of the batch of a per-graph value; V is the graph's ∫1, p and t the prediction and
+    the target, nf their columns:
+
+        'mse'       Σ_f ∫(p_f − t_f)² / (nf · V)       the area-weighted MSE: `F.mse_loss` when all areas are equal
+        'mse:<f>'   ∫(p_f − t_f)² / V                  the same for one field
+        'rel_mse'   Σ_f ∫(p_f − t_f)² / Σ_f ∫t_f²      the square of the rollout's 'rel_l2' (no root: smooth at 0)
+        'int:<f>', 'ke', 'circulation', 'enstrophy', 'div2'      ((I(p) − I(t)) / V)²
+
+    with I the rollout's integral of that name (`Rollout(integrals=)`: ∫p_f, ½∫(u² + v²) over `velocity`, ∫ω, ½∫ω², ∫(∇·u)²) —
+    the conserved quantities whose drift a rollout reports afterwards.  Dividing by V makes the matching terms intensive: no free
+    scale, and safe where the target's own integral is zero.  `terms`: a dict (or a sequence of pairs) of names to weights >= 0.
+
+    'circulation', 'enstrophy' and 'div2' read the 'vort' / 'div' columns of `MeshGradient.derived(pred, ...)` (`power`,
+    `edge_vectors` as in `FlowLoss`): that call is recorded, so their gradient chains into `MeshGradient.adjoint`.  Every integral
+    is one `ControlVolumes.integrate(..., per_graph=True)` — recorded for the prediction (`g4c_weighted_integrals_adjoint` in the
+    backward), under `no_grad` for the target; the few numbers behind them are combined in fp64 torch on the device (nothing is
+    read back, nothing synchronises) and the term is cast to the prediction's dtype before it joins the node term.
+
+    `box`, `bodies` (None or True: the wall from `graph.bound == 4`) are `ControlVolumes`'; `normals` is None or the name of a
+    per-node graph attribute [N, 2] holding the outward wall normals (zero rows: no wall; it collates along the nodes).  The
+    volumes — and the `MeshGradient` when a term needs it — are kept (one entry) while `graph.pos`, `graph.batch`, the normals
+    and the edge tensors are the same tensor objects, unmodified; `builds` counts the builds.  `node_weight == 0` skips `GraphLoss`;
+    `weight == 0` or no term of non-zero weight builds and launches nothing.  2-D, HIP device only."""
+
+    MATCHING = ("ke", "circulation", "enstrophy", "div2")
+    MAX_ENTRIES = 8          # _lib.INTEGRALS_MAX_ENTRIES: what one launch over a source sums (checked without the library)
+
+    def __init__(self, lambda_d=0, weight=1.0, node_weight=1.0, *, terms, velocity=(0, 1), box=None, bodies=None, normals=None, power=2,
+                 edge_vectors=None):
+        super().__init__(lambda_d, weight, node_weight)
+        pairs = list(terms.items()) if isinstance(terms, dict) else terms
+        try:
+            pairs = [tuple(p) for p in pairs]
+        except TypeError:
+            pairs = None
+        if not pairs or any(len(p) != 2 for p in pairs):
+            raise ValueError(f"terms: expected a non-empty dict of names ('mse', 'mse:<f>', 'rel_mse', 'int:<f>', 'ke', 'circulation', "
+                             f"'enstrophy', 'div2') to weights, got {terms!r}")
+        seen, self.terms = set(), []
+        for name, w in pairs:
+            key = self._name(name)
+            if key in seen:
+                raise ValueError(f"terms: {name!r} is named twice")
+            seen.add(key)
+            self.terms.append((key, _number(w, f"terms[{name!r}]", "a finite weight >= 0")))
+        velocity = _field_numbers(velocity, "velocity", "2 distinct field numbers", lengths=(2,), distinct=True)
+        if velocity is None:
+            raise ValueError("velocity: expected 2 distinct field numbers, got None")
+        if bodies is not None and bodies is not True:
+            raise TypeError(f"bodies: expected None or True (the wall from graph.bound == 4), got {type(bodies).__name__}")
+        _attribute(normals, "normals", "a per-node graph attribute holding [N, 2] wall normals")
+        if normals is not None and bodies is not None:
+            raise ValueError("normals: given together with bodies= (the bodies carry their own)")
+        if box is not None:
+            try:
+                rows = box.tolist() if torch.is_tensor(box) else list(box)
+                flat = [float(v) for r in rows for v in (r if isinstance(r, (list, tuple)) else [r])]
+            except (TypeError, ValueError):
+                flat = None
+            if not flat or len(flat) % 4 or not all(math.isfinite(v) for v in flat):
+                raise ValueError(f"box: expected (lo_x, lo_y, hi_x, hi_y), or one such box per graph of the batch, got {box!r}")
+        self.power = _power(power, "an edge")
+        _attribute(edge_vectors, "edge_vectors", "a graph attribute holding [E, 2] vectors")
+        self.velocity, self.box, self.bodies, self.normals, self.edge_vectors = velocity, box, bodies, normals, edge_vectors
+        self._live = [(n, w) for n, w in self.terms if w > 0]
+        self._derived = tuple(c for c in ("vort", "div") if any(self._column(n) == c for n, _ in self._live))
+
+    @staticmethod
+    def _name(name):
+        """`name` in its canonical form ('mse:01' is 'mse:1'), or ValueError naming `terms`."""
+        if isinstance(name, str):
+            if name in ("mse", "rel_mse") + IntegralLoss.MATCHING:
+                return name
+            head, _, tail = name.partition(":")
+            if head in ("mse", "int") and tail.isdigit():
+                return f"{head}:{int(tail)}"
+        raise ValueError(f"terms: unknown name {name!r} ('mse', 'mse:<f>', 'rel_mse', 'int:<f>', 'ke', 'circulation', 'enstrophy' and "
+                         f"'div2' are known)")
+
+    @staticmethod
+    def _column(name):
+        return {"circulation": "vort", "enstrophy": "vort", "div2": "div"}.get(name)
+
+    def plan(self, nf: int):
+        """Per source — 'error' (pred − target), 'target', 'fields' (pred, and target again), 'derived' — its entries, and per live term
+        (name, weight, kind, slots): `kind` 'mse' (Σ slots / (count · V)), 'rel' (Σ error slots / Σ target slots) or 'match' with a
+        factor (((factor · Σ slots)(pred) − (same)(target)) / V)².  ValueError naming `terms` / `velocity` on a field that the
+        prediction does not have or more than 8 entries over one source."""
+        if max(self.velocity) >= nf:
+            raise ValueError(f"velocity: the fields {self.velocity!r} of a prediction with {nf} columns")
+        entries = {"error": [], "target": [], "fields": [], "derived": []}
+
+        def slot(src, a, b=-1):
+            if (a, b) not in entries[src]:
+                entries[src].append((a, b))
+            return entries[src].index((a, b))
+
+        def field(name):
+            f = int(name.split(":")[1])
+            if f >= nf:
+                raise ValueError(f"terms: {name!r}: field {f} of a prediction with {nf} columns")
+            return f
+
+        recipes = []
+        for name, w in self._live:
+            if name == "mse":
+                recipes.append((name, w, "mse", [slot("error", f, f) for f in range(nf)]))
+            elif name.startswith("mse:"):
+                recipes.append((name, w, "mse", [slot("error", field(name), field(name))]))
+            elif name == "rel_mse":
+                recipes.append((name, w, "rel", ([slot("error", f, f) for f in range(nf)], [slot("target", f, f) for f in range(nf)])))
+            elif name.startswith("int:"):
+                recipes.append((name, w, ("fields", 1.0), [slot("fields", field(name))]))
+            elif name == "ke":
+                recipes.append((name, w, ("fields", 0.5), [slot("fields", v, v) for v in self.velocity]))
+            else:
+                c = self._derived.index(self._column(name))
+                recipes.append((name, w, ("derived", 0.5 if name == "enstrophy" else 1.0),
+                                [slot("derived", c, -1 if name == "circulation" else c)]))
+        for src, e in entries.items():
+            if len(e) > self.MAX_ENTRIES:
+                raise ValueError(f"terms: they need {len(e)} sums over the {src} source, at most {self.MAX_ENTRIES} fit one launch")
+        return entries, recipes
+
+    def _graph(self, graph, pred):
+        pos = getattr(graph, "pos", None)
+        if not torch.is_tensor(pos) or pos.dim() != 2:
+            raise ValueError("graph: IntegralLoss needs graph.pos [N, 2]")
+        if int(pos.size(1)) != 2:
+            raise ValueError(f"graph: IntegralLoss is 2-D only, graph.pos is {tuple(pos.shape)} (3-D cells are out of scope)")
+        if pos.device.type != "cuda" or pred.device.type != "cuda":
+            raise ValueError(f"graph: IntegralLoss runs on a HIP device only, graph.pos is on '{pos.device}' and the prediction on "
+                             f"'{pred.device}' (there is no CPU fallback)")
+        return pos
+
+    def operators(self, graph):
+        """(the `ControlVolumes` of `graph` — of all its graphs, when it is a batch —, V float64 [G] their ∫1, the `MeshGradient` the
+        derived terms read or None): the cached ones while graph.pos, graph.batch, the normals, graph.bound (with `bodies`) and — when
+        a derived term is live — graph.edge_index and the edge vectors are the objects they were built from, unmodified."""
+        pos, batch = graph.pos, getattr(graph, "batch", None)
+        nrm = None
+        if self.normals is not None:
+            nrm = getattr(graph, self.normals, None)
+            if not torch.is_tensor(nrm):
+                raise ValueError(f"normals: the graph has no tensor attribute {self.normals!r}")
+        bound = getattr(graph, "bound", None) if self.bodies else None
+        ei = vec = None
+        if self._derived:
+            ei = getattr(graph, "edge_index", None)
+            if self.edge_vectors is not None:
+                vec = getattr(graph, self.edge_vectors, None)
+                if not torch.is_tensor(vec):
+                    raise ValueError(f"edge_vectors: the graph has no tensor attribute {self.edge_vectors!r}")
+
+        def build():
+            from ..control_volumes import ControlVolumes
+            from ..mesh_gradient import MeshGradient
+            cv = ControlVolumes(graph, box=self.box, bodies=self.bodies, normals=nrm)
+            one = torch.zeros((cv.n_nodes, 1), dtype=torch.float32, device=cv.area.device)          # (the entry (−1, −1) reads no column)
+            V = cv.integrate(one, [(-1, -1)], per_graph=True)[:, 0]
+            return cv, V, (MeshGradient(graph, power=self.power, edge_vectors=vec) if self._derived else None)
+
+        return self.keep([pos, batch, nrm, bound, ei, vec], build)
+
+    def integrals(self, graph, pred, target):
+        """(V [G], sums, recipes): `sums` maps 'error', 'target', 'fields', 'fields_target', 'derived', 'derived_target' to the float64
+        [G, ne] integrals the live terms need (absent: not needed) — each `ControlVolumes.integrate(..., per_graph=True)` of
+        `plan(nf)`'s entries; those of the prediction are recorded for autograd."""
+        entries, recipes = self.plan(int(pred.size(1)))
+        cv, V, op = self.operators(graph)
+        tgt = target.detach()
+        sums = {}
+        if entries["error"]:
+            sums["error"] = cv.integrate(pred, entries["error"], sub=tgt, per_graph=True)
+        if entries["fields"]:
+            sums["fields"] = cv.integrate(pred, entries["fields"], per_graph=True)
+        if entries["derived"]:
+            sums["derived"] = cv.integrate(op.derived(pred, self._derived, velocity=self.velocity), entries["derived"], per_graph=True)
+        with torch.no_grad():
+            if entries["target"]:
+                sums["target"] = cv.integrate(tgt, entries["target"], per_graph=True)
+            if entries["fields"]:
+                sums["fields_target"] = cv.integrate(tgt, entries["fields"], per_graph=True)
+            if entries["derived"]:
+                sums["derived_target"] = cv.integrate(op.derived(tgt, self._derived, velocity=self.velocity), entries["derived"], per_graph=True)
+        return V, sums, recipes
+
+    @staticmethod
+    def _add(s, slots):
+        out = s[:, slots[0]]
+        for j in slots[1:]:          # (a fixed order: one add after the other)
+            out = out + s[:, j]
+        return out
+
+    def forward(self, graph, pred, target):
+        loss = self.node_term(graph, pred, target)
+        if self.weight == 0 or not self._live:
+            return self.nothing_more(pred, loss)
+        self.plan(int(pred.size(1)))          # (the terms against the prediction's columns first: refused the same way without a device)
+        self._graph(graph, pred)
+        V, sums, recipes = self.integrals(graph, pred, target)
+        total = None
+        for name, w, kind, slots in recipes:
+            if kind == "mse":
+                value = self._add(sums["error"], slots) / (len(slots) * V)
+            elif kind == "rel":
+                value = self._add(sums["error"], slots[0]) / self._add(sums["target"], slots[1])
+            else:
+                src, factor = kind
+                ip, it = self._add(sums[src], slots), self._add(sums[src + "_target"], slots)
+                if factor != 1.0:
+                    ip, it = factor * ip, factor * it
+                value = ((ip - it) / V).square()
+            part = w * value.mean()
+            total = part if total is None else total + part
+        if self.weight != 1.0:
+            total = self.weight * total
+        term = total.to(pred.dtype)
+        return term if loss is None else loss + term

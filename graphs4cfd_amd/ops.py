@@ -1453,6 +1453,53 @@ def weighted_integrals(x: Tensor, w: Tensor, entries, stats: Tensor, scratch: Te
     return stats
 
 
+def weighted_integrals_adjoint(x: Tensor, w: Tensor, entries, g: Tensor, *, nz: Optional[int] = None, sub: Optional[Tensor] = None,
+                               x_step: int = 0, sub_step: int = 0, t: int = 0, group: Optional[Tensor] = None,
+                               out: Optional[Tensor] = None) -> Tensor:
+    """g4c_weighted_integrals_adjoint: the transpose of `weighted_integrals`' map x -> I[q, e] = Σ_{i in group q} w[i] · z_i[a_e] · z_i[b_e],
+    applied to g float64 [G, ne] (on the device, never read on the host): gx float32 [N, nz],
+        gx[i, c] = Σ_e g[q_i, e] · w[i] · ([a_e == c] · z_i[b_e] + [b_e == c] · z_i[a_e])
+    in fp64 in the order of include/g4c.h, rounded to float32 once.  x, sub, nz, x_step, sub_step mean what they mean in
+    `weighted_integrals`; the step is `t` (host-given: training is not captured) and a strided source needs the columns of steps
+    0 .. t.  `group` int32 [N]: the group of every row (None: all rows in group 0, G == 1); a row of weight 0, or of a group outside
+    [0, G), is +0 in every column whatever it holds.  One thread per (node, column), no atomics: the same bits on every run.  `out`:
+    a caller-owned gx, float32 [N, nz] with rows of unit stride (a view of wider rows is fine: only its nz columns are written).
+    Returns gx."""
+    what = "weighted_integrals_adjoint"
+    if nz is None:
+        nz = x_step if (isinstance(x_step, int) and x_step > 0) else (int(x.size(1)) if torch.is_tensor(x) and x.dim() == 2 else 0)
+    a = Args(what)
+    a.integer(nz, "nz", at_least=1)
+    prog = integral_program(entries, nz)
+    ne = int(prog.ne)
+    a.integer(t, "t", at_least=0, at_most=2 ** 31 - 2)
+    max_steps = t + 1
+    n_nodes, x_ld = _integrals_source(a, x, "x", None, nz, x_step, max_steps)
+    sub_ld = 0
+    if sub is not None:
+        _, sub_ld = _integrals_source(a, sub, "sub", n_nodes, nz, sub_step, max_steps)
+    a.tensor(w, "w", torch.float64, shape=(n_nodes,))
+    a.tensor(g, "g", torch.float64, dim=2)
+    n_groups = int(g.size(0))
+    if int(g.size(1)) != ne or n_groups < 1 or n_groups >= 2 ** 31:
+        raise ValueError(f"g: {what}: expected [G >= 1, ne = {ne}], got shape {tuple(g.shape)}")
+    if group is not None:
+        a.tensor(group, "group", torch.int32, shape=(n_nodes,))
+    elif n_groups != 1:
+        raise ValueError(f"g: {what}: {n_groups} groups of rows need group= (without it every row is in group 0)")
+    if out is not None:
+        _, _, gx_ld = a.strided_rows(out, "out", rows=n_nodes, cols=nz)
+        a.distinct_storage(out, "out", ("x", x), ("sub", sub), ("w", w), ("g", g), ("group", group), identity=True)
+    dev = a.same_device(("x", x), ("sub", sub), ("w", w), ("g", g), ("group", group), ("out", out))
+    if out is None:
+        out, gx_ld = torch.empty((n_nodes, nz), dtype=torch.float32, device=dev), nz
+    wa = _lib.g4c_weighted_integrals_adjoint_t(x=_lib.ptr(x), x_ld=x_ld, x_step=x_step, sub=_lib.ptr(sub), sub_ld=sub_ld, sub_step=sub_step,
+                                               nz=nz, w=_lib.ptr(w), g=_lib.ptr(g), n_groups=n_groups, group=_lib.ptr(group), t_host=t,
+                                               max_steps=max_steps, gx=_lib.ptr(out), gx_ld=gx_ld)
+    _lib.check(_lib.load().g4c_weighted_integrals_adjoint(C.byref(wa), C.byref(prog), n_nodes, _lib.stream_handle(dev)))
+    return out
+
+
 def _snapshot_rows(a: Args, x, name: str):
     """A snapshot matrix float32 [rows >= 1, L >= 1] (or [rows, N, nf], read as L = N nf), contiguous -> (rows, L)."""
     a.dtype(x, name, torch.float32)

@@ -1093,6 +1093,40 @@ int64_t g4c_weighted_integrals_scratch_doubles(int64_t n_nodes, int32_t ne);
 int g4c_weighted_integrals(const g4c_weighted_integrals_t *wi /*host*/, const g4c_integral_program_t *prog /*host*/, int64_t n_nodes,
                            void *stream);
 
+/* g4c_weighted_integrals_adjoint: the transpose of the map x -> I[q][e] = Σ_{i in group q} w_i z_i[a_e] z_i[b_e] (the forward above,
+ * once per group of rows), applied to the upstream gradient g fp64 [n_groups, ne] — read on the device, never on the host —: gx float32
+ * [n_nodes, gx_ld >= nz], columns 0 .. nz − 1 of every row written and nothing else.  The samples z are the forward's (x, or x − sub in
+ * fp64, at the step t_host: the step is host-given only, training is not captured).  Node i, group q = group ? group[i] : 0, for every
+ * column c in 0 .. nz − 1:
+ *     acc = +0.0                                   (fp64)
+ *     for e = 0 .. ne − 1, in order:
+ *         gw = g[q][e] · w_i                       (rounded)
+ *         if a_e == c: acc += gw · z_i[b_e]        (the product rounded, then added; z of column −1 is 1.0)
+ *         if b_e == c: acc += gw · z_i[a_e]        (both hits when a_e == b_e == c: two adds, in this order)
+ *     gx[i][c] = (float) acc                       (round to nearest even, IEEE on overflow)
+ * No contraction; an entry that does not name column c is skipped, not multiplied by zero, so a NaN in g[q][e] or in a column of x
+ * changes only the outputs that depend on it.  A row with w_i == 0, or with group[i] outside [0, n_groups), is +0 in every column and
+ * reads neither x nor g (no address is formed from an unchecked index).  One thread per (node, column), no atomics: the bits are a
+ * function of the data alone.  n_nodes == 0: G4C_OK without a launch.  G4C_EINVAL before any launch: bad sizes, an entry outside
+ * [−1, nz), t_host outside [0, max_steps), a leading dimension below what the columns and steps need (the forward's rules; gx_ld < nz),
+ * a null pointer; G4C_EUNSUPPORTED: ne > G4C_INTEGRALS_MAX_ENTRIES. */
+typedef struct g4c_weighted_integrals_adjoint {
+    const float *x;              /* [n_nodes, x_ld] */
+    int32_t x_ld, x_step;        /* x_step 0, or >= nz with x_ld >= x_step max_steps */
+    const float *sub;            /* [n_nodes, sub_ld] or NULL */
+    int32_t sub_ld, sub_step;
+    int32_t nz;                  /* columns of a sample */
+    const double *w;             /* [n_nodes] */
+    const double *g;             /* [n_groups][ne], device */
+    int32_t n_groups;
+    const int32_t *group;        /* [n_nodes] the group of each row, or NULL: all rows in group 0 */
+    int32_t t_host, max_steps;
+    float *gx;                   /* [n_nodes, gx_ld] */
+    int32_t gx_ld;
+} g4c_weighted_integrals_adjoint_t;
+int g4c_weighted_integrals_adjoint(const g4c_weighted_integrals_adjoint_t *wa /*host*/, const g4c_integral_program_t *prog /*host*/,
+                                   int64_t n_nodes, void *stream);
+
 /* out[r, c] = a[r, a_col0 + c] + b[r, c]: the residual time step `field[:, -nf:] + output`
  * (nn/remus_gnn.py:199; the MuS-GNN decoder fuses it into g4c_mlp_run's epilogue instead). */
 int g4c_add_cols(const float *a, int32_t a_ld, int32_t a_col0, const float *b, int32_t b_ld,

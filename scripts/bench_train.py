@@ -2,7 +2,7 @@
 MuS-GNN on a synthetic mesh, on the GPU (fused forward, recompute backward: autograd.py) and — on a bounded sample — with
 the oracle on the host cores (torch autograd over the op-for-op restatement = what the reference's fit() executes).
 Usage: python scripts/bench_train.py [--nodes 100000] [--model NsThreeScaleGNN] [--steps 10] [--cpu-steps 1] [--phases] [--mixed [--saved-bf16]]
-       [--flow-loss | --sample-loss | --force-loss | --residual-loss]
+       [--flow-loss | --sample-loss | --force-loss | --residual-loss | --integral-loss]
 --flow-loss: the same run with FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) on the GPU (a continuity penalty and a vorticity-matching
 term through the differentiable mesh gradient: two `derived` launches and their adjoints per step; the host-side sample keeps GraphLoss).
 --sample-loss: the same run with SampleLoss(a 128 × 64 raster over the wake window [0.5, 1] × [0.25, 0.75], 0.25, weight=1.0): GraphLoss plus
@@ -14,6 +14,11 @@ adjoints per step.
 --residual-loss: the same run with ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1): GraphLoss plus the momentum and continuity residuals
 through the differentiable quadratic-fit operator (gfd.MeshJet, its own k = 12 stencil): a `derived` launch of eight columns on the prediction and
 on the target and one adjoint per step.
+--integral-loss: the same run with IntegralLoss(0.25, terms={"mse": 1.0, "rel_mse": 0.1, "ke": 1.0, "enstrophy": 0.01}): GraphLoss plus the
+area-weighted errors through the differentiable control-volume integrals (gfd.ControlVolumes): four `integrate` launches on the prediction and
+the target, a `derived` launch on each, and the adjoints of the prediction's three per step; "loss_ms" is the loss alone (its forward and backward on a leaf that stands for the
+prediction, device events; "graph_loss_ms" the same of GraphLoss(0.25)) and "operators_build_ms" what a fresh batch pays once (the control
+volumes and the mesh gradient).
 --mixed: the same step in mixed precision (what fit(mixed_precision=True) selects: every matrix product on bf16-rounded operands).
 --saved-bf16 (with --mixed): the rows the forward keeps for the backward as bf16 (TrainConfig(saved_activations="bf16"))."""
 import argparse, json, os, sys, time
@@ -34,9 +39,10 @@ ap.add_argument("--flow-loss", action="store_true", help="FlowLoss(0.25, terms={
 ap.add_argument("--sample-loss", action="store_true", help="SampleLoss(a 128 x 64 raster over the wake window, 0.25) instead of GraphLoss(0.25) on the GPU")
 ap.add_argument("--force-loss", action="store_true", help="ForceLoss(0.25, mu=1e-3, wall=...) on a loop of 256 nodes instead of GraphLoss(0.25) on the GPU")
 ap.add_argument("--residual-loss", action="store_true", help="ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1) instead of GraphLoss(0.25) on the GPU")
+ap.add_argument("--integral-loss", action="store_true", help="IntegralLoss(0.25, terms={'mse', 'rel_mse', 'ke', 'enstrophy'}) instead of GraphLoss(0.25) on the GPU")
 a = ap.parse_args()
-if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss > 1:
-    ap.error("--flow-loss, --sample-loss, --force-loss and --residual-loss are separate runs")
+if a.flow_loss + a.sample_loss + a.force_loss + a.residual_loss + a.integral_loss > 1:
+    ap.error("--flow-loss, --sample-loss, --force-loss, --residual-loss and --integral-loss are separate runs")
 if a.saved_bf16 and not a.mixed:
     ap.error("--saved-bf16 needs --mixed")
 if a.mixed:
@@ -66,6 +72,8 @@ elif a.force_loss:
     crit = gfd.nn.ForceLoss(0.25, weight=1.0, mu=1e-3, wall={"pressure": 0.5, "shear": 0.5}, nodes="wall")
 elif a.residual_loss:
     crit = gfd.nn.ResidualLoss(0.25, weight=1e-3, nu=1e-3, dt=0.1)
+elif a.integral_loss:
+    crit = gfd.nn.IntegralLoss(0.25, terms={"mse": 1.0, "rel_mse": 0.1, "ke": 1.0, "enstrophy": 0.01})
 else:
     crit = gfd.nn.FlowLoss(0.25, terms={"div": 0.1, "vort": 0.05}) if a.flow_loss else gfd.nn.GraphLoss(lambda_d=0.25)
 opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)        # (as GNN.fit does on the GPU)
@@ -111,6 +119,30 @@ out = {"workload": f"{a.model} H=128 training step (forward + {type(crit).__name
        "gpu_ms_forward_inference_eager": 1e3 * inf, "gpu_peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30,
        "loss": float(loss), "mlp_precision": gfd.ops.mlp_precision(), "train_precision": gfd.ops.train_precision(),
        "saved_precision": gfd.ops.saved_precision(), "loss_function": type(crit).__name__}
+if a.integral_loss:
+    # the loss alone: its forward and backward on a leaf that stands for the prediction (device events round `steps` calls), and the build
+    # a fresh batch pays once (host wall time, device work included)
+    leaf = torch.randn(a.nodes, nf, device=dev, requires_grad=True)
+    for fn_name, fn in (("loss_ms", lambda: crit(g, leaf, g.target).backward()),
+                        ("graph_loss_ms", lambda: gfd.nn.GraphLoss(lambda_d=0.25)(g, leaf, g.target).backward())):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out[fn_name] = e0.elapsed_time(e1) / a.steps
+    builds = []
+    for _ in range(3):
+        crit._cache = None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        crit.operators(g)
+        torch.cuda.synchronize()
+        builds.append(1e3 * (time.perf_counter() - t0))
+    out["operators_build_ms"] = sorted(builds)[1]
+    out["loss_share_of_step"] = out["loss_ms"] / out["gpu_ms_per_training_step"]
 if a.phases:
     from graphs4cfd_amd import autograd as A
     A.PROFILE = {}
