@@ -518,11 +518,8 @@ def _range_checked_forward(f):
                           f"65504) in {', '.join(hit[:8])}{' ...' if len(hit) > 8 else ''}: the forward was computed again in 'bf16x6' (fp32's "
                           "exponent range) — the result holds no clipped value.  gfd.set_mlp_precision('bf16x6') avoids the second pass.",
                           RuntimeWarning, stacklevel=2)
-            old = ops.set_mlp_precision("bf16x6")
-            try:
+            with ops.mlp_precision_as("bf16x6"):
                 out = f(self, graph, *args, **kwargs)
-            finally:
-                ops.set_mlp_precision(old)
         return out
     forward._g4c_range_checked = True
     return forward

@@ -18,21 +18,22 @@ from typing import Optional
 
 import torch
 
-from .. import _lib, ops, plan
+from .. import _lib, ops
+from .._stepper import StepDriver
 from ..graph import Graph
 
 
 REORDER_MIN_NODES = 50_000      # below, the gathered rows stay in L2 whatever the numbering
 
 
-class Rollout:
+class Rollout(StepDriver):
     """Device-resident autoregressive rollout state for one (model, Graph) pair (GNN.solve,
     nn/model.py:303-321).
 
     `step()` = one forward + one `g4c_rollout_advance` (writes outputs[:, nf*t:nf*(t+1)], shifts the
     history window, bumps the device-side step counter).  The first step runs eagerly and builds all
     static plans / packed weights; with `capture=True` the second step is captured into a hipGraph and
-    every later step is a replay: no host synchronisation, no per-kernel launch cost.
+    every later step is a replay: no host synchronisation, no per-kernel launch cost (`_stepper.StepDriver` decides which).
     The caller's `graph.field` is swapped for a private working copy and restored on close()."""
 
     def __init__(self, model: "GNN", graph: Graph, max_steps: int, capture: bool = True, reorder: Optional[bool] = None,
@@ -155,31 +156,16 @@ class Rollout:
             re = reorder_nodes(graph)
             if re is not None:
                 graph, self._perm = re
-        self.model, self.graph, self.capture = model, graph, capture
+        self.model, self.graph, self.label = model, graph, label
         self.nf = int(model.num_fields)
-        self.max_steps = int(max_steps)
         dev = graph.field.device
         self._orig_field = graph.field
-        self.field = graph.field.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        field = graph.field.to(torch.float32).clone(memory_format=torch.contiguous_format)
         # step-major [steps, N, nf]: a step's predictions are one contiguous block (`outputs` gives the reference's [N, nf * steps])
-        self._out_steps = None if recording else torch.zeros((self.max_steps, graph.num_nodes, self.nf), dtype=torch.float32, device=dev)
+        out_steps = None if recording else torch.zeros((int(max_steps), graph.num_nodes, self.nf), dtype=torch.float32, device=dev)
+        self._init_driver(field, out_steps, max_steps, capture)
         self._rec = _Records(self, int(every), probes, target, mask) if recording else None     # (its snapshots are `_out_steps`)
-        self.step_counter = torch.zeros(2, dtype=torch.int32, device=dev)          # [step index, g4c_rollout_advance's ticket]
-        self.steps_done = 0
-        self._hipgraph, self._epoch, self._pins = None, -1, None
         graph.field = self.field
-        # per-mesh constants (the encoders of edge_attr / angle_attr*): computed by the first eager step, read by every later one
-        self.static = ops.StaticCache()
-        # fp16 range flags of this rollout's own launches: every step (eager, captured, recomputed) runs in their scope
-        self.label = label
-        self.flags = ops.RangeFlags(dev)
-        # The default "f16x3" arithmetic is run OPTIMISTICALLY: its kernels flag every value that reached the end of the fp16 range
-        # (|x| >= 65504, clipped there), `result()` reads the flags, and a rollout that clipped anywhere is recomputed from the
-        # window it started from in "bf16x6" (fp32's exponent range; the reference's `solve` runs in fp32, nn/model.py:303-321) and
-        # stays in that arithmetic — so what `result()` hands out never contains a clipped value.
-        self._field0 = self.field.clone()        # the input window of slot `_first_slot`
-        self._first_slot = 0
-        self.exact_range = False                 # True once a clip made this rollout fall back to "bf16x6"
         self._parts = {}                         # name -> part, of those asked for, in launch order (a part may read an earlier one's buffers)
         for part in _PARTS:
             if specs[part.name] is not None:
@@ -205,11 +191,10 @@ class Rollout:
 
     @property
     def outputs(self) -> torch.Tensor:
-        """[N, nf * max_steps] in the rollout's node numbering, as `GNN.solve` lays its result out (nn/model.py:322-326) — a fresh
-        transposed copy of the step-major buffer on every access (no validation: `result()` is the delivered form)."""
+        """`StepDriver.outputs`, in the rollout's node numbering (`result()` is the delivered form)."""
         if self._out_steps is None:
             raise RuntimeError(f"{self.label}: every=0 keeps no snapshot of the predictions (probes() and errors() hold the records)")
-        return ops.steps_to_columns(self._out_steps)
+        return StepDriver.outputs.fget(self)
 
     def _one(self):
         with self.static, self.flags:
@@ -221,48 +206,6 @@ class Rollout:
             return
         ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
 
-    def step(self) -> None:
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"rollout buffer holds {self.max_steps} steps")
-        if self.exact_range and ops.mlp_precision() == "f16x3":
-            old = ops.set_mlp_precision("bf16x6")
-            try:
-                self._step()
-            finally:
-                ops.set_mlp_precision(old)
-        else:
-            self._step()
-
-    def _step(self) -> None:
-        with torch.no_grad():
-            if self._epoch != -1 and ops.weights_epoch() != self._epoch:
-                # the weights changed since the last eager step (captured or not yet): the packed images are stale, and repacking
-                # (allocations + pack launches) must not happen inside a capture — one eager step first
-                self._hipgraph, self._epoch = None, -1
-            elif self.static.stale():
-                # a per-mesh constant (edge_attr / angle_attr*) was edited in place, or the arithmetic changed: a captured step
-                # contains neither the encoder launches nor a look-up of their cached results, and a step ABOUT to be captured
-                #  would bake the recomputation — and, after a precision change, the repacking — into every replay:
-                # one eager step recomputes them, then the step is captured (again)
-                self._hipgraph, self._epoch = None, -1
-            if self.steps_done == 0 or not self.capture or self._epoch == -1:
-                self._one()                               # eager: builds the plans and the packed weight images
-                self._epoch = ops.weights_epoch()
-            elif self._hipgraph is None:
-                torch.cuda.synchronize(self.field.device)
-                self._pins = plan.snapshot()              # the graph bakes these pointers in: keep them past cache eviction
-                self._hipgraph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._hipgraph):   # records only; nothing executes during capture
-                    self._one()
-                self._hipgraph.replay()
-            else:
-                self._hipgraph.replay()
-        self.steps_done += 1
-
-    def run(self, n: int) -> None:
-        for _ in range(n):
-            self.step()
-
     def rewind(self) -> None:
         """Restart writing at step 0 (benchmarks: keeps the captured hipGraph and the current field).  Validates first: the
         field a later recomputation restarts from must not come from steps that clipped."""
@@ -273,41 +216,24 @@ class Rollout:
             self.step_counter[:1].fill_(1)
         self._field0.copy_(self.field)            # (a recomputation restarts here)
         self._first_slot = self.steps_done
-        for part in self._parts.values():
-            part.restart(self, False)
+        self._restarted(False)
 
-    def _recompute_exact(self, hit) -> None:
-        """Steps `_first_slot .. steps_done` again from the saved input window in "bf16x6"; the rollout stays in that arithmetic."""
-        n = self.steps_done - self._first_slot
+    def _restarted(self, again: bool) -> None:
+        for part in self._parts.values():
+            part.restart(self, again)
+
+    def _warn_clipped(self, hit, n: int) -> None:
         warnings.warn(f"{self.label}: the default 'f16x3' MLP arithmetic reached the end of the fp16 range (|x| >= 65504) in "
                       f"{', '.join(hit[:8])}{' ...' if len(hit) > 8 else ''}: the {n} step(s) were recomputed in 'bf16x6' (fp32's exponent "
                       "range) and this rollout continues in it — the result holds no clipped value.  gfd.set_mlp_precision('bf16x6') "
-                      "avoids the second pass for this model.", RuntimeWarning, stacklevel=3)
-        self.exact_range = True
-        self.field.copy_(self._field0)
-        self.step_counter.zero_()
-        if self._first_slot:
-            self.step_counter[:1].fill_(self._first_slot)
-        self._hipgraph, self._epoch = None, -1
-        self.steps_done = self._first_slot
-        for part in self._parts.values():
-            part.restart(self, True)
+                      "avoids the second pass for this model.", RuntimeWarning, stacklevel=3)      # (the caller of `validate()`)
+
+    def _rerun(self, n: int) -> None:
         field, self.graph.field = self.graph.field, self.field        # (after close() the graph holds its own field again)
         try:
             self.run(n)
         finally:
             self.graph.field = field
-
-    def validate(self) -> bool:
-        """Default "f16x3" arithmetic: read the range flags of this rollout's launches (its own buffer, one synchronisation) and, if
-        a value was clipped at the end of the fp16 range, recompute the steps in "bf16x6" (RuntimeWarning naming the MLPs).  Returns
-        True when that happened.  `result()` calls it, before or after close(); a benchmark calls it inside its timed region."""
-        if ops.mlp_precision() == "f16x3" and not self.exact_range:
-            hit = self.flags.take()
-            if hit:
-                self._recompute_exact(hit)
-                return True
-        return False
 
     def result(self) -> torch.Tensor:
         """`outputs` with its rows in the caller's node numbering — validated first (`validate()`): the tensor returned never
@@ -1467,7 +1393,7 @@ class _Records:
     """The record buffers of a `Rollout` and the launch that fills them.  Everything is allocated here, once, in the rollout's node
     numbering (probe rows, target rows and mask rows are mapped through the Morton permutation at construction), so a captured
     step allocates nothing; every slot is addressed by the device-side step index alone, so `rewind()` and a recomputation
-    (`Rollout._recompute_exact`) overwrite the records of the steps they run again."""
+    (`Rollout.validate`) overwrite the records of the steps they run again."""
 
     def __init__(self, ro: "Rollout", every: int, probes, target, mask):
         dev, n, nf, steps, perm = ro.field.device, int(ro.graph.num_nodes), ro.nf, ro.max_steps, ro._perm

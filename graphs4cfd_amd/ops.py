@@ -2043,6 +2043,16 @@ def set_mlp_precision(precision: str) -> str:
     return old
 
 
+@contextlib.contextmanager
+def mlp_precision_as(precision: str):
+    """`set_mlp_precision(precision)` for the launches issued inside; the previous setting is put back on the way out."""
+    old = set_mlp_precision(precision)
+    try:
+        yield
+    finally:
+        set_mlp_precision(old)
+
+
 TRAIN_PRECISIONS = ("bf16x6", "bf16")
 _TRAIN_PRECISION = "bf16x6"
 

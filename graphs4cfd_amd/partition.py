@@ -20,13 +20,18 @@ in tests only, an oracle-backed implementation that exercises the partition / ha
 """
 from __future__ import annotations
 
+import os
+import sys
+import warnings
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib, ops, plan
+from ._stepper import StepDriver
 from .graph import Graph
 from .ops import Source
 
@@ -98,7 +103,6 @@ def assign_owners(graph: Graph, levels: int, world: int, method: Optional[str] =
     parents, balanced by the number of level-1 nodes below each coarsest node.  `method` (default: environment variable
     G4C_PARTITION, else "rcb"): "rcb" = recursive coordinate bisection (compact blocks: the halo of a part grows with its
     perimeter, 2-3x fewer halo rows than strips at 8 ranks on a square / cubic domain), "strips" = slabs along x."""
-    import os
     method = method or os.environ.get("G4C_PARTITION", "rcb")
     if method not in ("rcb", "strips"):
         raise ValueError(f"unknown partition method {method!r} (rcb | strips)")
@@ -317,7 +321,6 @@ class HaloExchanger:
             return
         # (no per-rank shortcut for an empty halo: the exchange is a collective, every rank of the group has to enter it, with
         # zero-length splits if it has nothing to send or receive at this level)
-        import torch.distributed as dist
         width = int(v.size(1))
         n_send = sum(m.send_counts[level - 1])
         key = (level, width)
@@ -454,7 +457,6 @@ class MusPartitionedForward:
 
     def __init__(self, program: Sequence[str], mesh: LocalMesh, impl, exchanger: HaloExchanger, width: int, nf: int):
         self.program, self.mesh, self.impl, self.xch, self.width, self.nf = tuple(program), mesh, impl, exchanger, width, nf
-        import os
         # overlap every product exchange with the interior edges of the layer that consumes it (G4C_DIST_OVERLAP=0: off)
         self.overlap = os.environ.get("G4C_DIST_OVERLAP", "1") != "0"
 
@@ -520,13 +522,13 @@ class MusPartitionedForward:
         return impl.decode(v[: m.n_own[0]], m.inputs["field"], self.nf)
 
 
-class DistributedRollout:
+class DistributedRollout(StepDriver):
     """`Rollout` over a node-partitioned mesh: every rank advances its owned nodes; `outputs` holds the owned
-    rows ([n_own, nf*steps]); `gather_outputs()` assembles the global tensor on every rank (validation / I/O)."""
+    rows ([n_own, nf*steps]); `gather_outputs()` assembles the global tensor on every rank (validation / I/O).  The step state
+    machine is `_stepper.StepDriver`'s, shared with `nn.rollout.Rollout`; what differs is decided jointly over the ranks."""
 
     def __init__(self, model, graph_cpu: Graph, max_steps: int, rank: int, world: int, device: torch.device, group=None,
                  capture: bool = True):
-        import os
         capture = capture and os.environ.get("G4C_DIST_HIPGRAPH", "1") != "0"
         self.model, self.rank, self.world, self.device = model, rank, world, device
         program = model._PROGRAM
@@ -552,134 +554,64 @@ class DistributedRollout:
             self.mesh.decision_edges = uniform_edge_counts(parts)
             width = int(model.node_encoder.output_size)
             self.fwd = MusPartitionedForward(program, self.mesh, HipImpl(model), HaloExchanger(self.mesh, group), width, self.nf)
-        self.max_steps = max_steps
-        self.field = self.mesh.inputs["field"] = self.mesh.inputs["field"].clone()
-        self._out_steps = torch.zeros((max_steps, int(self.mesh.owned_global[0].numel()), self.nf), dtype=torch.float32, device=device)
-        self.step_counter = torch.zeros(2, dtype=torch.int32, device=device)          # [step index, g4c_rollout_advance's ticket]
-        self.steps_done = 0
-        self.capture = capture and device.type == "cuda"
-        self.capture_error = None if self.capture else "capture not requested"
-        self._hipgraph, self._epoch = None, -1
-        self.static = ops.StaticCache()        # per-mesh constants (edge / angle encoders), as nn.rollout.Rollout
-        self.flags = ops.RangeFlags(device)     # fp16 range flags of this rollout's own launches, as nn.rollout.Rollout
-        # optimistic "f16x3" (nn.rollout.Rollout): the input window the rollout started from, for the exact-range recomputation
-        self._field0 = self.field.clone()
-        self.exact_range = False
+        self.mesh.inputs["field"] = self.mesh.inputs["field"].clone()
+        out_steps = torch.zeros((max_steps, int(self.mesh.owned_global[0].numel()), self.nf), dtype=torch.float32, device=device)
+        self._init_driver(self.mesh.inputs["field"], out_steps, max_steps, capture and device.type == "cuda")
 
     def _one(self) -> None:
         with self.static, self.flags:
             pred = self.fwd.forward()
         ops.rollout_advance(self.field, pred, self._out_steps, self.step_counter, self.nf)
 
-    def step(self) -> None:
-        """Step 1 eager (plans, packing), step 2 captured into a hipGraph together with its RCCL halo
-        exchanges (every rank captures the same sequence), later steps replayed."""
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"rollout buffer holds {self.max_steps} steps")
-        if self.exact_range and ops.mlp_precision() == "f16x3":
-            old = ops.set_mlp_precision("bf16x6")
-            try:
-                self._step()
-            finally:
-                ops.set_mlp_precision(old)
-        else:
-            self._step()
+    def _any_rank(self, flag: bool) -> bool:
+        """`flag` on any rank: an int32 MAX all-reduce over the exchanger's group (in-process test transports have no group)."""
+        if self.world > 1 and dist.is_available() and dist.is_initialized():
+            torch.cuda.synchronize(self.device)
+            t = torch.tensor([1 if flag else 0], dtype=torch.int32, device=self.device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=getattr(self.fwd.xch, "group", None))
+            flag = int(t.item()) != 0
+        return flag
 
     def validate(self) -> bool:
-        """As nn.rollout.Rollout.validate, decided jointly: if ANY rank's launches clipped a value at the end of the fp16 range,
-        every rank recomputes its steps in "bf16x6" (the halo exchanges pair up again) and stays in that arithmetic."""
-        if ops.mlp_precision() != "f16x3" or self.exact_range or self.device.type != "cuda":
-            return False
-        hit = self.flags.take()
-        clipped = bool(hit)
-        import torch.distributed as dist
-        if self.world > 1 and dist.is_available() and dist.is_initialized():
-            flag = torch.tensor([1 if clipped else 0], dtype=torch.int32, device=self.device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=getattr(self.fwd.xch, "group", None))
-            clipped = int(flag.item()) != 0
-        if not clipped:
-            return False
-        import warnings
-        n = self.steps_done
+        """`StepDriver.validate`, decided jointly: if ANY rank's launches clipped a value at the end of the fp16 range, every rank
+        recomputes its steps in "bf16x6" (the halo exchanges pair up again) and stays in that arithmetic."""
+        return self.device.type == "cuda" and super().validate()
+
+    def _warn_clipped(self, hit, n: int) -> None:
         warnings.warn(f"DistributedRollout (rank {self.rank}): the default 'f16x3' MLP arithmetic reached the end of the fp16 range "
                       f"(|x| >= 65504){' in ' + ', '.join(hit[:8]) if hit else ' on another rank'}: the {n} step(s) were recomputed in "
-                      "'bf16x6' (fp32's exponent range) and this rollout continues in it.", RuntimeWarning, stacklevel=3)
-        self.exact_range = True
-        self.field.copy_(self._field0)
-        self.step_counter.zero_()
-        self._hipgraph, self._epoch = None, -1
-        self.steps_done = 0
-        self.run(n)
-        return True
+                      "'bf16x6' (fp32's exponent range) and this rollout continues in it.", RuntimeWarning,
+                      stacklevel=5)      # (the caller of what called `validate()`: of `gather_outputs()`)
 
-    def _step(self) -> None:
-        with torch.no_grad():
-            if self._epoch != -1 and ops.weights_epoch() != self._epoch:
-                # (as nn.rollout.Rollout: the weights changed — load_state_dict, fit, invalidate_packed — so the captured step's packed
-                # images are stale or freed; one eager step repacks, then the step is captured again.  Every rank sees the same
-                # epoch sequence as long as every rank updates its replica of the model, which a partitioned rollout requires anyway)
-                self._hipgraph, self._epoch = None, -1
-            elif self.static.stale():
-                # (a per-mesh constant edited in place, or another arithmetic — also just BEFORE the capture: as nn.rollout.Rollout — and, like new weights, something
-                # every rank has to do alike, or a replaying rank would pair its captured collectives with an eager rank's)
-                self._hipgraph, self._epoch = None, -1
-            if self.steps_done == 0 or not self.capture or self._epoch == -1:
+    def _capture(self) -> None:
+        """Step 2 is captured together with its RCCL halo exchanges (every rank captures the same sequence); on stacks where the
+        collective cannot be captured the rollout stays alive on eager launches (`capture_error` says why)."""
+        torch.cuda.synchronize(self.device)
+        hg, err = None, None
+        self._pins = plan.snapshot()       # the graph bakes the plans' pointers in: keep them past cache eviction
+        try:
+            hg = torch.cuda.CUDAGraph()
+            # (thread_local: the process group's watchdog thread polls its events while this thread captures; under
+            # the default global mode a call from that thread can invalidate the capture)
+            pg_live = dist.is_available() and dist.is_initialized()
+            with torch.cuda.graph(hg, capture_error_mode="thread_local" if (self.world > 1 or pg_live) else "global"):
                 self._one()
-                self._epoch = ops.weights_epoch()
-            elif self._hipgraph is None:
-                torch.cuda.synchronize(self.device)
-                hg, err = None, None
-                self._pins = plan.snapshot()       # the graph bakes the plans' pointers in: keep them past cache eviction
-                try:
-                    hg = torch.cuda.CUDAGraph()
-                    # (thread_local: the process group's watchdog thread polls its events while this thread captures; under
-                    # the default global mode a call from that thread can invalidate the capture)
-                    import torch.distributed as _dist
-                    pg_live = _dist.is_available() and _dist.is_initialized()
-                    with torch.cuda.graph(hg, capture_error_mode="thread_local" if (self.world > 1 or pg_live) else "global"):
-                        self._one()
-                except Exception as exc:   # keep the rollout alive on stacks where the collective cannot be captured
-                    hg, err = None, f"{type(exc).__name__}: {exc}"
-                # every rank takes the same path: one rank replaying while another launches eagerly would pair a captured
-                # collective with an eager one
-                ok = hg is not None
-                import torch.distributed as dist
-                if self.world > 1 and dist.is_available() and dist.is_initialized():     # (in-process test transports have no group)
-                    torch.cuda.synchronize(self.device)
-                    flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=self.device)
-                    dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=getattr(self.fwd.xch, "group", None))
-                    if ok and int(flag.item()) == 0:
-                        ok, err = False, "capture failed on another rank"
-                if ok:
-                    self._hipgraph = hg
-                    self._hipgraph.replay()
-                else:
-                    import sys
-                    self.capture_error = err
-                    print(f"[graphs4cfd_amd] rank {self.rank}: hipGraph capture of the partitioned step failed "
-                          f"({err}); continuing with eager launches", file=sys.stderr)
-                    self.capture, self._hipgraph = False, None
-                    torch.cuda.synchronize(self.device)
-                    self._one()
-            else:
-                self._hipgraph.replay()
-        self.steps_done += 1
-
-    @property
-    def captured(self) -> bool:
-        return self._hipgraph is not None
-
-    def run(self, n: int) -> None:
-        for _ in range(n):
-            self.step()
-
-    @property
-    def outputs(self) -> torch.Tensor:
-        """The owned rows as [n_own, nf * max_steps] (a transposed copy of the step-major buffer)."""
-        return ops.steps_to_columns(self._out_steps)
+        except Exception as exc:   # keep the rollout alive on stacks where the collective cannot be captured
+            hg, err = None, f"{type(exc).__name__}: {exc}"
+        # every rank takes the same path: one rank replaying while another launches eagerly would pair a captured
+        # collective with an eager one
+        if self._any_rank(hg is None):
+            self.capture_error = err or "capture failed on another rank"
+            print(f"[graphs4cfd_amd] rank {self.rank}: hipGraph capture of the partitioned step failed "
+                  f"({self.capture_error}); continuing with eager launches", file=sys.stderr)
+            self.capture = False
+            torch.cuda.synchronize(self.device)
+            self._one()
+        else:
+            self._hipgraph = hg
+            hg.replay()
 
     def gather_outputs(self) -> torch.Tensor:
-        import torch.distributed as dist
         self.validate()          # (a clipped rollout is recomputed in "bf16x6" on every rank before anything is gathered)
         mine = self.outputs
         full = torch.zeros((self.n_global, mine.size(1)), dtype=torch.float32, device=self.device)
