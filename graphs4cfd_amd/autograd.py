@@ -135,7 +135,7 @@ def segment_broadcast(dout: Tensor, csr, mean: bool, n_src_rows: int) -> Tensor:
 # GEMMs.  SAVE_ACTIVATIONS = False: the memory-light recompute path.
 SAVE_ACTIVATIONS = True
 FUSED_LINEAR = True
-HOIST_MIN_ROWS = 32768             # below: the step is host-bound, and hoisting a block costs five more launches than it saves
+HOIST_MIN_ROWS = 32768             # the BACKWARD's crossover (not the forward's, nn.blocks.HOIST_MIN_ROWS): below, the step is host-bound, and hoisting a block costs five more launches than it saves
 FUSED_LINEAR_MIN_ROWS = 65536      # below: packing the weights for one launch costs more host time than the fusion saves
 
 
@@ -221,7 +221,7 @@ def _wgrad_tile(g: Tensor, blk: Tensor, M: int, with_bias: bool, scratch: Tensor
 def _pad128(t: Tensor, c0: int, c1: int) -> Tensor:
     """Columns [c0, c1) of t as a 128-wide, 16-byte aligned window: a view when they already are one, else a zero-padded copy."""
     w = c1 - c0
-    if w == 128 and t.stride(1) == 1 and _ld(t) % 4 == 0 and (t.data_ptr() + 4 * c0) % 16 == 0:
+    if w == 128 and ops.vector_rows(t, c0):
         return t[:, c0:c1]
     p = torch.zeros((int(t.size(0)), 128), dtype=torch.float32, device=t.device)
     ops.copy_cols(t if t.stride(1) == 1 else t.contiguous(), p, 0, scol0=c0, width=w)

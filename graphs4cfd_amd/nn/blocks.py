@@ -12,6 +12,7 @@ blocks fuses the `F.selu` the model applies right after the block, nn/mus_gnn.py
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -23,7 +24,6 @@ from .. import _lib, ops, plan
 from ..graph import Graph
 from ..ops import Source
 
-import os
 # first-layer hoisting (MLP.run_hoisted) pays off only when the launch is throughput-bound
 HOIST_MIN_ROWS = 24576
 
@@ -293,17 +293,12 @@ class MLP(nn.Module):
 
     def run(self, sources: Sequence[Source], n_rows: int, activation=None, out: Optional[Tensor] = None,
             out_idx32: Optional[Tensor] = None, resid: Optional[Tensor] = None, resid_col0: int = 0) -> Tensor:
-        """cat(sources) -> MLP -> activation (+ resid), one fused launch."""
+        """cat(sources) -> MLP -> activation (+ resid), one fused launch: `run_coded` for an activation given as a callable or a name."""
         code = _lib.act_code(activation)
         if code is None and resid is not None:
             raise NotImplementedError("a residual after a non-fusable activation")
-        if not self.fits_one_launch():
-            y = self._run_stages(sources, n_rows, _lib.ACT_NONE if code is None else code, out=out, out_idx32=out_idx32, resid=resid,
-                                 resid_col0=resid_col0)
-            return _finish(y, activation, code)
-        sources = _split_wide(sources)
-        pk = self.packed(*_blocks(sources))
-        y = ops.mlp_forward(pk, sources, n_rows, _lib.ACT_NONE if code is None else code, out, out_idx32, resid, resid_col0)
+        y = self.run_coded(sources, n_rows, _lib.ACT_NONE if code is None else code, out=out, out_idx32=out_idx32, resid=resid,
+                           resid_col0=resid_col0)
         return _finish(y, activation, code)
 
     def run_coded(self, sources: Sequence[Source], n_rows: int, act_code: int = _lib.ACT_NONE, **kw) -> Tensor:
@@ -369,6 +364,25 @@ class MLP(nn.Module):
         ops.mlp_forward(pk, sources, n_rows, act_code, out=y, head_outs=outs)
         return y, ([ops.RsOrderedRows.tag(t) for t in outs] if rs_rows else outs)
 
+    def node_heads(self, w: int) -> Tuple[int, List[int]]:
+        """(k_cols, widths) of `run_with_heads` for this message MLP as the consumer [x | y[row] | y[col]] of a `w`-wide output y."""
+        return self.input_size - 2 * w, [w, w]
+
+    def run_feeding(self, sources: Sequence[Source], n_rows: int, act_code: int, consumer: "MLP", decision: Tuple[bool, bool],
+                    out: Optional[Tensor] = None, head_outs: Optional[Sequence[Optional[Tensor]]] = None,
+                    out_without_heads: bool = True) -> Tuple[Tensor, Optional[List[Tensor]]]:
+        """The one producer call: this MLP on `sources`, whose output is the node input of the message MLP `consumer`.  `decision` =
+        its `hoist_decision`: when it hoists, the launch carries its node-side products as heads (run_with_heads); otherwise, or when no
+        launch carries such heads, the plain launch.  Returns (y, products or None).  `out_without_heads=False` (the REMuS level
+        entries): `out` is the destination only beside heads."""
+        hoists, rs_rows = decision
+        if hoists:
+            got = self.run_with_heads(sources, n_rows, act_code, consumer, *consumer.node_heads(self.output_size), out=out,
+                                      head_outs=head_outs, rs_rows=rs_rows)
+            if got is not None:
+                return got
+        return self.run_coded(sources, n_rows, act_code, out=out if out_without_heads else None), None
+
     # -- first-layer hoisting ------------------------------------------------------------------
     def _packed_cols(self, *args, **kw) -> ops.PackedMLP:
         """The image `_cols_spec` describes (same arguments).  A name in front of them, which callers passed while every call site spelled
@@ -383,6 +397,20 @@ class MLP(nn.Module):
         weight columns are packed in that order."""
         return self._spec(seg_widths, seg_negate, None, [rs_in] * len(seg_widths), layers=(0, 1) if first_only else None,
                           cols=(a, b), bias=not first_only, stream=_lib.WFMT_BF16_RS if rs_order else 0, rs_rows=rs_rows)
+
+    def first_layer_product(self, a: int, b: int, t: Tensor, bound: Optional[float] = None,
+                            rs_rows: bool = False) -> Tuple[Tensor, Optional[float]]:
+        """The one product launch of a hoisted first layer: (W1[:, a:b] t over the rows of `t`, what the launch proves about it from
+        `bound` on |t|).  A block wider than 128 goes in as 128-wide chunks (not while recorded for autograd); in the rounded-bf16 mode a
+        128-wide product is stored as bf16 (PRODUCTS_BF16); `rs_rows`: in the row-split kernel's column order (ops.RsOrderedRows)."""
+        w_t, n_t = b - a, int(t.size(0))
+        chunks = [(c, min(128, w_t - c)) for c in range(0, w_t, 128)] if (w_t > 128 and not ops.grad_mode()) else [(0, w_t)]
+        pk1 = self._packed_cols(a, b, [w for _, w in chunks], [False] * len(chunks), True, rs_rows=rs_rows,
+                                rs_in=rs_rows and isinstance(t, ops.RsOrderedRows))
+        part16 = (torch.empty((n_t, 128), dtype=torch.bfloat16, device=t.device)
+                  if (ops.mlp_precision() == "bf16" and PRODUCTS_BF16 and pk1.n_out == 128 and pk1.precision == "bf16") else None)
+        part = ops.mlp_forward(pk1, [Source(t, col0=c, width=w, bound=bound) for c, w in chunks], n_t, out=part16)
+        return (ops.RsOrderedRows.tag(part) if rs_rows else part), ops.take_bounds().out
 
     def run_hoisted(self, k_sources: Sequence[Source], gathered: Sequence[Tuple[Tensor, Tensor]], n_rows: int,
                     act_code: int = _lib.ACT_NONE, products: Optional[Sequence[Tensor]] = None,
@@ -407,22 +435,14 @@ class MLP(nn.Module):
         # up-sampling — is hoisted at any size: its products are formed from 128-wide chunks, the launch itself keeps one block)
         too_many = (sum((s.width + 127) // 128 for s in plain) > _lib.MAX_SRC and any(s.width > 128 for s in plain)
                     and ops.mlp_precision() in ("bf16x6", "f16x3") and not ops.grad_mode())
-        if (n_rows < HOIST_MIN_ROWS or (ops.mlp_precision() == "bf16" and not HOIST_BF16) or ops.grad_mode()) and products is None and not too_many:
+        if not hoist_decision(self, n_rows, forced=products is not None or too_many, vetoes="consumer")[0]:
             return self.run_coded(plain, n_rows, act_code, **kw)
         kw_widths = [s.width for s in k_sources]
         off = sum(kw_widths)
         adds = []
         for j, (t, idx) in enumerate(gathered):
             w_t = int(t.size(1))
-            if products is not None:
-                part, part_bound = products[j], pb[j]
-            else:
-                chunks = [(c, min(128, w_t - c)) for c in range(0, w_t, 128)] if (w_t > 128 and not ops.grad_mode()) else [(0, w_t)]
-                pk1 = self._packed_cols(off, off + w_t, [w for _, w in chunks], [False] * len(chunks), True)
-                part16 = (torch.empty((int(t.size(0)), 128), dtype=torch.bfloat16, device=t.device)
-                          if (ops.mlp_precision() == "bf16" and PRODUCTS_BF16 and pk1.n_out == 128 and pk1.precision == "bf16") else None)
-                part = ops.mlp_forward(pk1, [Source(t, col0=c, width=w, bound=gb[j]) for c, w in chunks], int(t.size(0)), out=part16)
-                part_bound = ops.take_bounds().out
+            part, part_bound = (products[j], pb[j]) if products is not None else self.first_layer_product(off, off + w_t, t, gb[j])
             adds.append(Source(part, index=idx, additive=True, bound=part_bound))
             off += w_t
         if off != self.input_size:
@@ -439,10 +459,8 @@ class MLP(nn.Module):
             return 0
         if len(sources) != 2 or act_code not in (_lib.ACT_NONE, _lib.ACT_SELU) or not rs_rows or not set(kw) <= {"out"}:
             return 0
-        for s_ in sources:
-            if (s_.width != 128 or s_.col0 != 0 or s_.negate or s_.index is not None or s_.segments is not None or s_.additive
-                    or s_.pre_act != _lib.ACT_NONE or s_.tensor.dtype != torch.bfloat16 or s_.tensor.stride(0) % 8 or s_.tensor.data_ptr() % 16):
-                return 0
+        if not all(s_.whole_block(128, dtypes=(torch.bfloat16,)) and ops.vector_rows(s_.tensor) for s_ in sources):
+            return 0
         if not isinstance(sources[0].tensor, ops.RsOrderedRows):
             return 0
         lin = self._linears()
@@ -450,8 +468,7 @@ class MLP(nn.Module):
                 or getattr(self.MLP, "layer_norm", None) is None):
             return 0
         out = kw.get("out")
-        if out is not None and (out.dtype not in (torch.float32, torch.bfloat16) or out.stride(1) != 1 or out.data_ptr() % 16
-                                or out.stride(0) % (8 if out.dtype == torch.bfloat16 else 4)):
+        if out is not None and not (out.dtype in (torch.float32, torch.bfloat16) and ops.vector_rows(out)):
             return 0
         return 4 if isinstance(sources[1].tensor, ops.RsOrderedRows) else 5
 
@@ -477,8 +494,7 @@ class MLP(nn.Module):
         if not self.rs1_ready(n_rows, agg[0]) or len(k_sources) != 1 or len(gathered) != 2:
             return False
         x = k_sources[0]
-        if (x.width != 128 or x.col0 != 0 or x.negate or x.index is not None or x.segments is not None or x.additive
-                or x.pre_act not in (_lib.ACT_NONE, _lib.ACT_SELU)):
+        if not x.whole_block(128, pre_acts=(_lib.ACT_NONE, _lib.ACT_SELU)):
             return False
         if x.tensor.dtype == torch.bfloat16 and not (isinstance(x.tensor, ops.RsOrderedRows) and x.pre_act == _lib.ACT_NONE):
             return False
@@ -490,20 +506,12 @@ class MLP(nn.Module):
             return False
         if kw.get("rows_dtype") == torch.bfloat16 and kw.get("store_rows", True) and kw.get("rows_act", _lib.ACT_NONE) != _lib.ACT_SELU:
             return False
-        return (agg[1].dtype in (torch.float32, torch.bfloat16) and agg[1].stride(1) == 1 and agg[1].data_ptr() % 16 == 0
-                and agg[1].stride(0) % (8 if agg[1].dtype == torch.bfloat16 else 4) == 0)
+        return agg[1].dtype in (torch.float32, torch.bfloat16) and ops.vector_rows(agg[1])
 
     def _run_rs1(self, x: Source, gathered, n_rows: int, products, kw) -> Optional[Tensor]:
         adds = []
         for j, (t, idx) in enumerate(gathered):
-            if products is not None:
-                part = products[j]
-            else:        # this block's product W1[:, 128 (j + 1) : 128 (j + 2)] t, bf16 rows in the kernel's column order
-                tagged = isinstance(t, ops.RsOrderedRows)
-                pk1 = self._packed_cols(128 * (j + 1), 128 * (j + 2), [128], [False], True, rs_rows=True, rs_in=tagged)
-                part = torch.empty((int(t.size(0)), 128), dtype=torch.bfloat16, device=t.device)
-                ops.mlp_forward(pk1, [Source(t)], int(t.size(0)), out=part)
-                part = ops.RsOrderedRows.tag(part)
+            part = products[j] if products is not None else self.first_layer_product(128 * (j + 1), 128 * (j + 2), t, rs_rows=True)[0]
             adds.append(Source(part, index=idx, additive=True))
         pk = self._packed_cols(0, 128, [128], [False], False, rs_order=True)
         y = ops.mlp_forward(pk, [x] + adds, n_rows, _lib.ACT_NONE, **kw)
@@ -618,18 +626,18 @@ PRODUCTS_BF16 = True
 # and hoisted products — are in its own column order (ops.RsOrderedRows), 16 contiguous bytes per lane: the level-1 angle launch of
 # config 3 is bound by the NUMBER of memory instructions and 32-byte pieces, not by HBM bytes (2.5 M rows: 655 us on
 # mlp_ws_kernel<SP = 1>, 622 us on this kernel with natural-order 8-byte pieces, 520 us with 16-byte pieces).
-ROW_SPLIT_BF16 = __import__('os').environ.get('G4C_ROW_SPLIT_BF16', '1') != '0'      # (environment: same-box A/B runs)
+ROW_SPLIT_BF16 = os.environ.get('G4C_ROW_SPLIT_BF16', '1') != '0'      # (environment: same-box A/B runs)
 # ... and the aggregate of such a launch is stored as bf16 rows in the same order (G4C_AGG_OUT_BF16) when its reader is the layer's update
 # MLP in one launch: that reader rounds it to bf16 on load, so the operand is the same and two launches move half its bytes (2.5M-row
 # angle launch 521 -> 493 us, the 500k-row edge update 284 -> 254 us).
-AGGREGATE_BF16 = __import__('os').environ.get('G4C_AGGREGATE_BF16', '1') != '0'
+AGGREGATE_BF16 = os.environ.get('G4C_AGGREGATE_BF16', '1') != '0'
 # ... and the edge latents BETWEEN consecutive EdgeMPs of a level — read only by the next update MLP, which rounds them to bf16 on load —
 # are stored as bf16 rows by the update launch (out_dtype G4C_DTYPE_BF16 beside bf16 heads): the same operand, half the bytes in both launches.
-COMPACT_LATENTS = __import__('os').environ.get('G4C_COMPACT_LATENTS', '1') != '0'
+COMPACT_LATENTS = os.environ.get('G4C_COMPACT_LATENTS', '1') != '0'
 # ... and the update MLP of such a layer — [bf16 aggregate | bf16 e] -> two layers -> LayerNorm -> SELU -> e' (+ the next layer's two
 # product heads) — runs on the row-split UPDATE kernel (mlp_rs.hip, mlp_rs2_kernel: the five 128 x 128 weight blocks are all of a CU's
 # LDS, the bias / LayerNorm vectors live in registers), e' as bf16 rows in the kernel's order between consecutive EdgeMPs.
-UPDATE_ROW_SPLIT = __import__('os').environ.get('G4C_UPDATE_ROW_SPLIT', '1') != '0'
+UPDATE_ROW_SPLIT = os.environ.get('G4C_UPDATE_ROW_SPLIT', '1') != '0'
 RS1_MIN_ROWS = 20000
 
 
@@ -659,15 +667,36 @@ def will_fuse_layer(msg_mlp: MLP, upd_mlp: MLP, edge_index: Tensor, n_nodes: int
     return csr.perm is None and csr.tiles() is not None
 
 
+def hoist_decision(consumer: Optional[MLP], n_rows: int, csr=None, *, decision_rows: Optional[int] = None, forced: bool = False,
+                   layer: Optional[Tuple[MLP, Tensor, int]] = None, vetoes: str = "none") -> Tuple[bool, bool]:
+    """Will this message MLP hoist its first layer, and in which form: (hoists, rs_rows) for the launch of `consumer` over `n_rows` rows
+    whose receivers `csr` groups — asked by the consumer (MLP.run_hoisted) and by every producer of its node input (MLP.run_feeding), so
+    that they agree.  From HOIST_MIN_ROWS rows on (`decision_rows`: a count other than the launch's own — the partitioned forward's
+    smallest over the ranks); below that when `forced` (products handed in; too many gathered blocks for one launch) or when its `layer`
+    = (update MLP, edge_index, n_nodes) will fuse (will_fuse_layer).  `rs_rows`: the products take the row-split kernel's column order
+    (MLP.rs1_ready; never without `csr`).  `vetoes`: what else says no — the sites disagree and each keeps what it had (DESIGN.md
+    §4.1): "none" (the producers: MLP.run_with_heads declines by itself), "consumer" (run_hoisted: grad mode, bf16 without HOIST_BF16),
+    "bf16" (partition.HipImpl: the rounded-bf16 mode outright)."""
+    if vetoes not in ("none", "consumer", "bf16"):
+        raise ValueError(f"vetoes: {vetoes!r}")
+    yes = (n_rows if decision_rows is None else decision_rows) >= HOIST_MIN_ROWS
+    if vetoes == "consumer":
+        yes = yes and not ((ops.mlp_precision() == "bf16" and not HOIST_BF16) or ops.grad_mode())
+    elif vetoes == "bf16":
+        yes = yes and ops.mlp_precision() != "bf16"
+    yes = bool(yes or forced or (layer is not None and will_fuse_layer(consumer, *layer)))
+    return yes, bool(yes and csr is not None and consumer.rs1_ready(n_rows, csr))
+
+
 def _can_fuse_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e, edge_index: Tensor, csr, v_src, n_targets, v_out, compact_messages: bool) -> bool:
     if v_src is not None or n_targets is not None or v_out is not None or compact_messages:
         return False
     if not will_fuse_layer(msg_mlp, upd_mlp, edge_index, int(v.size(0))):
         return False
     e_t = e.tensor if isinstance(e, Source) else e
-    if isinstance(e, Source) and (e.index is not None or e.col0 != 0 or e.negate or e.segments is not None or e.additive):
+    if int(v.size(1)) != 128 or int(e_t.size(1)) != 128 or e_t.dtype != torch.float32:
         return False
-    return int(v.size(1)) == 128 and int(e_t.size(1)) == 128 and e_t.dtype == torch.float32
+    return not isinstance(e, Source) or e.whole_block(e.width, pre_acts=None)          # (any activation on load; its width is the pack's to check)
 
 
 def static_first_layer(msg_mlp: MLP, upd_mlp: MLP, e_src: Source, e_static, edge_index: Tensor, n_nodes: int, csr, hoists: bool) -> bool:
@@ -684,8 +713,7 @@ def static_first_layer(msg_mlp: MLP, upd_mlp: MLP, e_src: Source, e_static, edge
     lm = msg_mlp._linears()
     if len(lm) != 3 or any(l.out_features != 128 for l in lm) or msg_mlp.input_size != 384:
         return False
-    if (e_src.pre_act != _lib.ACT_NONE or e_src.index is not None or e_src.col0 != 0 or e_src.negate or e_src.segments is not None
-            or e_src.additive or e_src.width != 128 or e_src.tensor.dtype != torch.float32):
+    if not e_src.whole_block(128, dtypes=(torch.float32,)):
         return False
     if will_fuse_layer(msg_mlp, upd_mlp, edge_index, n_nodes):
         return False
@@ -705,9 +733,7 @@ def _static_first_message(msg_mlp: MLP, e_src: Source, e_static, gathered, n_row
         if products is not None:
             part, part_bound = products[j], (product_bounds[j] if product_bounds is not None else None)
         else:
-            part = ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True),
-                                   [Source(t, bound=gathered_bounds[j])], int(t.size(0)))
-            part_bound = ops.take_bounds().out
+            part, part_bound = msg_mlp.first_layer_product(H * (1 + j), H * (2 + j), t, gathered_bounds[j])
         adds.append(Source(part, index=idx, additive=True, bound=part_bound))
     return ops.mlp_forward_precomputed(msg_mlp._packed_cols(0, H, [H], [False], False), first, adds, n_rows, agg, store_rows=store_rows)
 
@@ -724,15 +750,12 @@ def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, 
     n_t = int(v.size(0))
     pb = [rb.product(0), rb.product(1)]
     if products is None:          # the node-side products of this layer's first layer: W1[:, H:2H] v, W1[:, 2H:3H] v (MLP.run_hoisted)
-        products = []
-        for j in range(2):
-            products.append(ops.mlp_forward(msg_mlp._packed_cols(H * (1 + j), H * (2 + j), [H], [False], True), [Source(v, bound=rb.v)], n_t))
-            pb[j] = ops.take_bounds().out
+        products, pb = zip(*[msg_mlp.first_layer_product(H * (1 + j), H * (2 + j), v, rb.v) for j in range(2)])
     pk_msg = msg_mlp._packed_cols(0, H, [H], [e_src.negate], False)
     srcs = [e_src, Source(products[0], index=ep.row, additive=True, bound=pb[0]), Source(products[1], index=ep.col, additive=True, bound=pb[1])]
     heads = None
     if next_msg is not None and next_msg.input_size == 3 * H and next_msg._linears()[0].out_features == H:
-        spec = upd_mlp._heads_spec(([H, H], [False, False]), next_msg, next_msg.input_size - 2 * H, [H, H])
+        spec = upd_mlp._heads_spec(([H, H], [False, False]), next_msg, *next_msg.node_heads(H))
         if spec is not None:
             pk_upd = upd_mlp._image(spec)
             heads = [torch.empty((n_t, H), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -743,6 +766,56 @@ def _fused_layer(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e_src: Source, ep, csr, 
     lb = ops.take_bounds()
     rb.v, rb.e, rb.products = lb.out, lb.e, (lb.heads if heads is not None else None)
     return v_new, e_new, heads
+
+
+def aggregate_of_rows(e_new: Tensor, csr, mean: bool, v_width: int, bound: Optional[float] = None) -> Source:
+    """The aggregate of stored message rows as the update MLP's first input block: the node launch averages each target's messages
+    while it gathers its input (g4c_src_t.seg_off: no separate pass, no aggregate in HBM) where it can, else a separate reduction."""
+    if ops.can_aggregate_on_load(csr, int(e_new.size(1)), [int(e_new.size(1)), v_width]):
+        return Source(e_new, segments=csr, seg_mean=mean, bound=bound)
+    return Source(ops.segment_reduce(e_new, csr, mean))
+
+
+def _messages_and_aggregate(msg_mlp: MLP, upd_mlp: MLP, e_src: Source, gathered, n_rows: int, csr, mean: bool, products, hoist_kw: dict,
+                            rb: Optional[ops.RangeBounds], keep_e: bool = True, compact_messages: bool = False, e_static=None,
+                            bf16_aggregate: bool = True) -> Tuple[Optional[Tensor], Source]:
+    """How an MP layer's aggregate reaches its update MLP, decided once: runs the message launch of `msg_mlp` on [e | senders[row] |
+    v[col]] (`gathered`, MLP.run_hoisted) and returns (e' or None, the aggregate as the update MLP's first input block); |e'| goes into
+    `rb` — None (partition.HipImpl): no bounds are kept, `hoist_kw` is empty.  `e_static`: static_first_layer said yes.
+    `bf16_aggregate=False` (HipImpl): fp32 where the row-split kernel could store the aggregate as bf16 rows."""
+    v, width, agg = gathered[1][0], msg_mlp.output_size, None
+    fp32 = dict(dtype=torch.float32, device=v.device)
+    if e_static is not None:
+        agg = torch.empty((csr.n_seg, width), **fp32)
+        e_new = _static_first_message(msg_mlp, e_src, e_static, gathered, n_rows, products, hoist_kw["gathered_bounds"],
+                                      hoist_kw["product_bounds"], (csr, agg, mean), keep_e)
+    elif ops.can_fuse_aggregation(csr, width):
+        # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_io_t.agg): no second pass
+        # over the messages; with keep_e=False (the model discards e', nn/mus_gnn.py:199-200) they are not even written
+        kw = dict(store_rows=keep_e, rows_dtype=torch.bfloat16 if compact_messages and COMPACT_MESSAGES else None,
+                  rows_act=_lib.ACT_SELU if compact_messages and COMPACT_MESSAGES else _lib.ACT_NONE)
+        if (bf16_aggregate and AGGREGATE_BF16 and ops.mlp_precision() == "bf16" and width == 128 and int(v.size(1)) == 128
+                and upd_mlp.fits_one_launch() and ops.effective_precision([128, 128]) == "bf16"):
+            # rounded-bf16 mode, message launch on the row-split kernel: the aggregate's one reader — this layer's update MLP — rounds it
+            # to bf16 on load, so it is stored that way, in the kernel's column order (the update MLP's pack follows): half the bytes
+            agg16 = torch.empty((csr.n_seg, 128), dtype=torch.bfloat16, device=v.device)
+            if msg_mlp._rs1_takes([e_src], gathered, n_rows, _lib.ACT_NONE, products, dict(kw, agg=(csr, agg16, mean))):
+                agg = agg16
+        agg = torch.empty((csr.n_seg, width), **fp32) if agg is None else agg
+        e_new = msg_mlp.run_hoisted([e_src], gathered, n_rows, products=products, agg=(csr, agg, mean), **hoist_kw, **kw)
+    elif ops.can_aggregate_on_load(csr, width, [width, int(v.size(1))]):          # (aggregate_of_rows: the node launch reads the rows)
+        e_new = msg_mlp.run_hoisted([e_src], gathered, n_rows, products=products, **hoist_kw)
+    elif ops.grad_mode():          # (recorded for autograd: the plain launch, then the differentiable reduction)
+        e_new = msg_mlp.run_hoisted([e_src], gathered, n_rows)
+    else:          # (the launch still reduces its own rows where the kernel can — ops.mlp_forward `agg` — and stores them)
+        agg = torch.empty((csr.n_seg, width), **fp32)
+        e_new = msg_mlp.run_hoisted([e_src], gathered, n_rows, products=products, agg=(csr, agg, mean), **hoist_kw)
+    e_bound = ops.take_bounds().out if rb is not None else None          # (nothing while recorded for autograd)
+    if rb is not None:
+        rb.e = e_bound
+    if agg is None:
+        return e_new, aggregate_of_rows(e_new, csr, mean, int(v.size(1)), e_bound)
+    return e_new, Source(ops.RsOrderedRows.tag(agg) if agg.dtype == torch.bfloat16 else agg, bound=ops.agg_bound(e_bound, csr, mean))
 
 
 def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, aggr: str, act_code: int,
@@ -795,72 +868,21 @@ def _mp_step(msg_mlp: MLP, upd_mlp: MLP, v: Tensor, e: Tensor, index: Tensor, ag
     v_in = Source(v, bound=rb.v)
     static_first = (e_static is not None and v_src is None and n_targets is None and v_out is None and not compact_messages
                     and static_first_layer(msg_mlp, upd_mlp, e_src, e_static, index, int(v.size(0)), csr,
-                                           ep.n_edges >= HOIST_MIN_ROWS or products is not None))
-    if static_first:
-        agg = torch.empty((csr.n_seg, 128), dtype=torch.float32, device=v.device)
-        e_new = _static_first_message(msg_mlp, e_src, e_static, [(senders, ep.row), (v, ep.col)], ep.n_edges, products,
-                                      hoist_kw["gathered_bounds"], hoist_kw["product_bounds"], (csr, agg, mean), keep_e)
-        rb.e = ops.take_bounds().out
-        agg_src = Source(agg, bound=ops.agg_bound(rb.e, csr, mean))
-    elif ops.can_fuse_aggregation(csr, msg_mlp.output_size):
-        # the edge launch reduces the rows it has just computed (whole CSR segments per row tile, g4c_mlp_io_t.agg):
-        # no second pass over the messages; with keep_e=False (the model discards e', nn/mus_gnn.py:199-200) they are not
-        # even written
-        kw = dict(store_rows=keep_e, rows_dtype=torch.bfloat16 if compact_messages and COMPACT_MESSAGES else None,
-                  rows_act=_lib.ACT_SELU if compact_messages and COMPACT_MESSAGES else _lib.ACT_NONE)
-        gathered = [(senders, ep.row), (v, ep.col)]
-        agg = None
-        if (AGGREGATE_BF16 and ops.mlp_precision() == "bf16" and msg_mlp.output_size == 128 and int(v.size(1)) == 128
-                and upd_mlp.fits_one_launch() and ops.effective_precision([128, 128]) == "bf16"):
-            # rounded-bf16 mode, message launch on the row-split kernel: the aggregate's one reader — this layer's update MLP — rounds it
-            # to bf16 on load, so it is stored that way (in the kernel's column order; the update MLP's pack takes the block's columns in
-            # the same order): the same operand, half the bytes in both launches
-            agg16 = torch.empty((csr.n_seg, 128), dtype=torch.bfloat16, device=v.device)
-            if msg_mlp._rs1_takes([e_src], gathered, ep.n_edges, _lib.ACT_NONE, products, dict(kw, agg=(csr, agg16, mean))):
-                agg = agg16
-        if agg is None:
-            agg = torch.empty((csr.n_seg, msg_mlp.output_size), dtype=torch.float32, device=v.device)
-        e_new = msg_mlp.run_hoisted([e_src], gathered, ep.n_edges, products=products, agg=(csr, agg, mean), **hoist_kw, **kw)
-        rb.e = ops.take_bounds().out
-        agg_src = Source(ops.RsOrderedRows.tag(agg) if agg.dtype == torch.bfloat16 else agg, bound=ops.agg_bound(rb.e, csr, mean))
-    elif ops.can_aggregate_on_load(csr, msg_mlp.output_size, [msg_mlp.output_size, int(v.size(1))]):
-        # the node launch averages each target's messages while it gathers its input (g4c_src_t.seg_off): no separate
-        # aggregation pass, no aggregate written to / re-read from HBM
-        e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges, products=products, **hoist_kw)
-        rb.e = ops.take_bounds().out
-        agg_src = Source(e_new, segments=csr, seg_mean=mean, bound=rb.e)
-    elif ops.grad_mode():
-        e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges)
-        rb.e = None
-        agg_src = Source(ops.segment_reduce(e_new, csr, mean))
-    else:
-        agg = torch.empty((csr.n_seg, msg_mlp.output_size), dtype=torch.float32, device=v.device)
-        e_new = msg_mlp.run_hoisted([e_src], [(senders, ep.row), (v, ep.col)], ep.n_edges,
-                                    products=products, agg=(csr, agg, mean), **hoist_kw)
-        rb.e = ops.take_bounds().out
-        agg_src = Source(agg, bound=ops.agg_bound(rb.e, csr, mean))
+                                           hoist_decision(msg_mlp, ep.n_edges, forced=products is not None)[0]))
+    e_new, agg_src = _messages_and_aggregate(msg_mlp, upd_mlp, e_src, [(senders, ep.row), (v, ep.col)], ep.n_edges, csr, mean, products,
+                                             hoist_kw, rb, keep_e, compact_messages, e_static if static_first else None)
     v16 = (compact_v and compact_latents_now(upd_mlp.output_size) and upd_mlp.fits_one_launch() and n_targets is None and v_out is None
            and ops.effective_precision([128, int(v.size(1))]) == "bf16")
-    if next_msg is not None:
-        nxt = None
-        nx_rows, nx_csr = (ep.n_edges, csr) if next_graph is None else next_graph
-        if nx_rows >= HOIST_MIN_ROWS:        # the consumer will hoist: give it its node-side terms from this launch
-            w = upd_mlp.output_size          # (width of v', the node input of the next layer's message MLP)
-            nxt = upd_mlp.run_with_heads([agg_src, v_in], int(v.size(0)), act_code, next_msg,
-                                         next_msg.input_size - 2 * w, [w, w], rs_rows=next_msg.rs1_ready(nx_rows, nx_csr),
-                                         out=torch.empty((int(v.size(0)), 128), dtype=torch.bfloat16, device=v.device) if v16 else None)
-        if nxt is None:
-            out16 = torch.empty((int(v.size(0)), 128), dtype=torch.bfloat16, device=v.device) if v16 else None
-            v_new = upd_mlp.run_coded([agg_src, v_in], int(v.size(0)), act_code, out=out16)
-            rb.v, rb.products = ops.take_bounds().out, None
-            return v_new, e_new, None
-        lb = ops.take_bounds()
-        rb.v, rb.products = lb.out, lb.heads
-        return nxt[0], e_new, nxt[1]
-    v_new = upd_mlp.run_coded([agg_src, v_in], n_t, act_code,
-                              out=torch.empty((n_t, 128), dtype=torch.bfloat16, device=v.device) if v16 else v_out)
-    rb.v, rb.products = ops.take_bounds().out, None
-    return v_new, e_new
+    out16 = torch.empty((n_t, 128), dtype=torch.bfloat16, device=v.device) if v16 else None
+    if next_msg is None:
+        v_new = upd_mlp.run_coded([agg_src, v_in], n_t, act_code, out=out16 if v16 else v_out)
+        rb.v, rb.products = ops.take_bounds().out, None
+        return v_new, e_new
+    nx_rows, nx_csr = (ep.n_edges, csr) if next_graph is None else next_graph
+    v_new, nxt = upd_mlp.run_feeding([agg_src, v_in], n_t, act_code, next_msg, hoist_decision(next_msg, nx_rows, nx_csr), out=out16)
+    lb = ops.take_bounds()
+    rb.v, rb.products = lb.out, (lb.heads if nxt is not None else None)
+    return v_new, e_new, nxt
 
 
 def compact_latents_now(width: int = 128) -> bool:
@@ -1117,11 +1139,15 @@ class UpEdgeMP(nn.Module):
         e1 = ops.project_to_edges(v1, ep.col, edgeUnitVector1, ep.n_edges, nfeat)
         # 4- skip connection + per-edge MLP
         code = _lib.act_code(activation)
-        if next_msg is not None and code is not None and next_graph is not None and next_graph[0] >= HOIST_MIN_ROWS:
-            w = self.up_mlp.output_size
-            out16 = torch.empty((ep.n_edges, 128), dtype=torch.bfloat16, device=pos.device) if compact_latents_now(w) else None
-            got = self.up_mlp.run_with_heads([Source(e1), Source(edge_attr1)], ep.n_edges, code, next_msg, next_msg.input_size - 2 * w, [w, w],
-                                             rs_rows=next_msg.rs1_ready(*next_graph), out=out16)      # (e1' is read by that EdgeMP only)
-            if got is not None:
-                return got
-        return self.up_mlp.run([Source(e1), Source(edge_attr1)], ep.n_edges, activation=activation), None
+        if next_msg is None or code is None or next_graph is None:
+            return self.up_mlp.run([Source(e1), Source(edge_attr1)], ep.n_edges, activation=activation), None
+        return level_entry_launch(self.up_mlp, [Source(e1), Source(edge_attr1)], ep.n_edges, code, next_msg, next_graph)
+
+
+def level_entry_launch(mlp: MLP, sources: Sequence[Source], n_rows: int, act_code: int, first: MLP, first_graph):
+    """A REMuS level's entry launch (an edge encoder, UpEdgeMP's per-edge MLP), read only by the level's next EdgeMP: (rows, products or
+    None) — the products of that EdgeMP's angle MLP `first` over `first_graph` = (angle rows, receiver CSR) when it hoists, compact rows."""
+    decision = hoist_decision(first, *first_graph)
+    out16 = (torch.empty((n_rows, 128), dtype=torch.bfloat16, device=sources[0].tensor.device)
+             if decision[0] and compact_latents_now(mlp.output_size) else None)
+    return mlp.run_feeding(sources, n_rows, act_code, first, decision, out=out16, out_without_heads=False)

@@ -60,17 +60,13 @@ class _MuSGNN(GNN):
         that will hoist its first layer, the launch also emits its node-side products (MLP.run_with_heads).
         Returns (output, products or None)."""
         nxt = self._PROGRAM[k] if k < len(self._PROGRAM) else ""
+        if not nxt.startswith("mp"):
+            return mlp.run_coded(sources, n_rows, act_code), None
         # (the consumer hoists from HOIST_MIN_ROWS edges on — and always when it runs as one fused launch per MP layer, whose message
         # part takes the products as additive rows: without them it would make them itself, two more launches at the level's entry)
-        n_edges = int(edge_index.size(1))
-        if nxt.startswith("mp") and (n_edges >= _blocks.HOIST_MIN_ROWS
-                                     or _blocks.will_fuse_layer(getattr(self, nxt).edge_mlp, getattr(self, nxt).node_mlp, edge_index, n_rows)):
-            cons = getattr(self, nxt).edge_mlp
-            w = mlp.output_size
-            res = mlp.run_with_heads(sources, n_rows, act_code, cons, cons.input_size - 2 * w, [w, w])
-            if res is not None:
-                return res
-        return mlp.run_coded(sources, n_rows, act_code), None
+        layer = getattr(self, nxt)
+        decision = _blocks.hoist_decision(layer.edge_mlp, int(edge_index.size(1)), layer=(layer.node_mlp, edge_index, n_rows))
+        return mlp.run_feeding(sources, n_rows, act_code, layer.edge_mlp, decision)
 
     def forward(self, graph: Graph, t: Optional[int] = None) -> torch.Tensor:
         field0 = graph.field

@@ -140,21 +140,15 @@ class NsRotEquiTreeScaleGNN(GNN):
             # project the node vectors along the edges, then [proj | glob[col] | omega[col]] -> encoder
             proj = ops.project_to_edges(g.field, ep.col, getattr(g, f"edgeUnitVector{s}"), ep.n_edges, nfeat)
             enc_src = [Source(proj), Source(g.glob, ep.col), Source(g.omega, ep.col)]
-            e[lvl] = None
+            enc = getattr(self, f"edge_encoder{s}")
             if ENTRY_PRODUCTS and lvl == 1 and self._PROGRAM[0][0] == "mp" and not ops.grad_mode():
-                # the level's first EdgeMP reads e next: its hoisted first-layer products come out of the encoder's launch
-                first = getattr(self, self._PROGRAM[0][1]).angle_mlp
-                n_ang = int(getattr(g, f"angle_index{s}").size(1))
-                if n_ang >= _blocks.HOIST_MIN_ROWS:
-                    enc = getattr(self, f"edge_encoder{s}")
-                    out16 = (torch.empty((ep.n_edges, 128), dtype=torch.bfloat16, device=proj.device)
-                             if _blocks.compact_latents_now(enc.output_size) else None)       # (e is read by that EdgeMP's update MLP only)
-                    got = enc.run_with_heads(enc_src, ep.n_edges, SELU, first, first.input_size - 2 * enc.output_size,
-                                             [enc.output_size] * 2, out=out16, rs_rows=first.rs1_ready(n_ang, plan.edge_csr(getattr(g, f"angle_index{s}"), ep.n_edges)[1]))
-                    if got is not None:
-                        e[lvl], entry_products = got
-            if e[lvl] is None:
-                e[lvl] = getattr(self, f"edge_encoder{s}").run_coded(enc_src, ep.n_edges, SELU)
+                # the level's first EdgeMP reads e next (and nothing else does): its hoisted first-layer products come out of the
+                # encoder's launch
+                a_idx = getattr(g, f"angle_index{s}")
+                e[lvl], entry_products = _blocks.level_entry_launch(enc, enc_src, ep.n_edges, SELU, getattr(self, self._PROGRAM[0][1]).angle_mlp,
+                                                                    (int(a_idx.size(1)), plan.edge_csr(a_idx, ep.n_edges)[1]))
+            else:
+                e[lvl] = enc.run_coded(enc_src, ep.n_edges, SELU)
             # (the angle attributes are static inside a rollout — nn/model.py:316-320 replaces graph.field only — so a Rollout
             # runs the five angle encoders once per mesh and weights, ops.StaticCache; a bare forward() launches them, like the
             # reference nn/remus_gnn.py:136-140)

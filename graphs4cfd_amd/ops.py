@@ -177,6 +177,20 @@ class Source:
         if segments is not None and (index is not None or additive or self.width != 128):
             raise ValueError("aggregation on load needs a 128-wide block without gather index")
 
+    def whole_block(self, width: int, pre_acts: Optional[Sequence[int]] = (_lib.ACT_NONE,), dtypes: Optional[Sequence[torch.dtype]] = None,
+                    product: bool = False) -> bool:
+        """A whole, plain block of `width` columns: from column 0, not negated, not aggregated on load, read row for row and multiplied
+        by its weights (`product=True`: gathered and added instead).  `pre_acts` / `dtypes`: what the caller's kernel admits, None: any."""
+        return (self.width == width and self.col0 == 0 and not self.negate and self.segments is None
+                and bool(self.additive) == product and (self.index is not None) == product
+                and (pre_acts is None or self.pre_act in pre_acts) and (dtypes is None or self.tensor.dtype in dtypes))
+
+
+def vector_rows(t: Tensor, col0: int = 0) -> bool:
+    """Rows a 16-byte vector store (or load) can address from column `col0` on: unit column stride, a 16-byte aligned first element, a
+    row stride of whole 16-byte pieces (8 bf16 values, 4 fp32 values)."""
+    return t.stride(1) == 1 and (t.data_ptr() + t.element_size() * col0) % 16 == 0 and _ld(t) % (16 // t.element_size()) == 0
+
 
 # ---- argument checks of the helper launches below: shapes, strides and dtypes only (host metadata — never index VALUES, which would
 # synchronise the stream and break graph capture), and before require_hip, so that a malformed call is refused the same way with or
@@ -2520,7 +2534,7 @@ def mlp_forward_precomputed(packed: PackedMLP, first: Tensor, products: Sequence
         raise RuntimeError(f"MLP weights on {packed.device}, inputs on {dev}")
     if packed.split != "f16x2" or packed.desc.n_layers != 3 or packed.seg_widths != (128,) or packed.n_out != 128 or packed.n_heads:
         raise NotImplementedError("mlp_forward_precomputed: a three-layer 128-wide MLP over one 128-wide block, packed for f16x3, no heads")
-    if len(products) != 2 or any(not s.additive or s.index is None or s.width != 128 or s.tensor.dtype != torch.float32 for s in products):
+    if len(products) != 2 or not all(s.whole_block(128, dtypes=(torch.float32,), product=True) for s in products):
         raise ValueError("mlp_forward_precomputed: two additive 128-wide fp32 sources gathered through an index")
     first = _rows_f32(first, "first", cols=128, min_rows=n_rows)
     if csr.tiles() is None or n_rows != csr.n:

@@ -368,13 +368,10 @@ class HipImpl:
                      pr_out: Optional[torch.Tensor]):
         """`mlp` -> v_out (own rows); when `next_name` is the MP layer that consumes v_out and hoists its first layer, the
         same launch also emits its products (own rows of `pr_out`, and W1c v as a fresh tensor).  Returns them or None."""
-        if next_name is not None and pr_out is not None:
-            nxt = getattr(self.m, next_name).edge_mlp
-            w = int(v_out.size(1))
-            res = mlp.run_with_heads(srcs, n_own, act, nxt, nxt.input_size - 2 * w, [w, w], out=v_out,
-                                     head_outs=[pr_out[:n_own], None])
-            if res is not None:
-                return pr_out, res[1][1]
+        if next_name is not None and pr_out is not None:          # (the caller asked `hoists`: the decision is taken)
+            _, prods = mlp.run_feeding(srcs, n_own, act, getattr(self.m, next_name).edge_mlp, (True, False), out=v_out,
+                                       head_outs=[pr_out[:n_own], None])
+            return None if prods is None else (pr_out, prods[1])
         mlp.run_coded(srcs, n_own, act, out=v_out)
         return None
 
@@ -389,7 +386,7 @@ class HipImpl:
         """Whether an MP layer with this many local edges multiplies its node-side first-layer terms per node
         (MLP.run_hoisted) — then the halo exchange can carry those products instead of the latents."""
         from .nn import blocks as _blocks
-        return n_edges >= _blocks.HOIST_MIN_ROWS and ops.mlp_precision() != "bf16"
+        return _blocks.hoist_decision(None, n_edges, vetoes="bf16")[0]
 
     def mp(self, name: str, v: torch.Tensor, e: torch.Tensor, e_pending: int, edge_index: torch.Tensor, n_own: int,
            v_out: torch.Tensor, products=None, next_name: Optional[str] = None, pr_out: Optional[torch.Tensor] = None,
@@ -398,6 +395,7 @@ class HipImpl:
         previous layer's node launch made them (and the halo rows of the first were exchanged): then `v`'s halo rows are
         not read at all.  `next_name` / `pr_out`: also emit the NEXT layer's products from this layer's node launch
         (own rows of `pr_out`, and a fresh tensor).  Returns (e', next products or None)."""
+        from .nn import blocks as _blocks
         blk = getattr(self.m, name)
         ep, csr = plan.edge_csr(edge_index, n_own)
         mean = blk.aggr == "mean"
@@ -415,21 +413,10 @@ class HipImpl:
                 if int(ids.numel()):
                     blk.edge_mlp.run_hoisted([Source(e, index=ids, pre_act=e_pending)], [(v, row), (v, col)], int(ids.numel()),
                                              products=products, out=e_new, out_idx32=ids)
-            if ops.can_aggregate_on_load(csr, blk.edge_mlp.output_size, [blk.edge_mlp.output_size, int(v.size(1))]):
-                agg_src = Source(e_new, segments=csr, seg_mean=mean)
-            else:
-                agg_src = Source(ops.segment_reduce(e_new, csr, mean))
-            return e_new, self._node_launch(blk.node_mlp, [agg_src, Source(v[:n_own])], n_own, SELU, v_out, next_name, pr_out)
-        if (not ops.can_fuse_aggregation(csr, blk.edge_mlp.output_size)
-                and ops.can_aggregate_on_load(csr, blk.edge_mlp.output_size, [blk.edge_mlp.output_size, int(v.size(1))])):
-            e_new = blk.edge_mlp.run_hoisted([Source(e, pre_act=e_pending)], [(v, ep.row), (v, ep.col)], ep.n_edges, products=products)
-            agg_src = Source(e_new, segments=csr, seg_mean=mean)
-        else:
-            # (the edge launch reduces its own rows where it can, ops.can_fuse_aggregation; otherwise a separate reduction)
-            agg = torch.empty((csr.n_seg, blk.edge_mlp.output_size), dtype=torch.float32, device=e.device)
-            e_new = blk.edge_mlp.run_hoisted([Source(e, pre_act=e_pending)], [(v, ep.row), (v, ep.col)], ep.n_edges,
-                                             products=products, agg=(csr, agg, mean))
-            agg_src = Source(agg)
+            agg_src = _blocks.aggregate_of_rows(e_new, csr, mean, int(v.size(1)))
+        else:          # (the single-mesh layer's route, blocks._mp_step — without range bounds, the aggregate always fp32)
+            e_new, agg_src = _blocks._messages_and_aggregate(blk.edge_mlp, blk.node_mlp, Source(e, pre_act=e_pending), [(v, ep.row), (v, ep.col)],
+                                                             ep.n_edges, csr, mean, products, {}, None, bf16_aggregate=False)
         return e_new, self._node_launch(blk.node_mlp, [agg_src, Source(v[:n_own])], n_own, SELU, v_out, next_name, pr_out)
 
     def down(self, name: str, v_own: torch.Tensor, rel: torch.Tensor, parent: torch.Tensor, n_coarse: int, e: torch.Tensor,
