@@ -15,6 +15,7 @@ ap.add_argument("--raster", default=None, help="write the vorticity of the last 
 ap.add_argument("--streak", default=None, help="write the streaklines of five seeds after the last step to this .npy file")
 ap.add_argument("--body", type=int, default=0, help="mark the W nodes nearest to a circle as a wall (bound == 4) and print its force coefficients")
 ap.add_argument("--integrals", action="store_true", help="print the kinetic-energy drift and the relative L2 error, weighted by the nodes' Voronoi areas")
+ap.add_argument("--welch", action="store_true", help="print the segment-averaged spectrum, the coherence with the ground truth and the frequency drift at a probe")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -72,6 +73,17 @@ if a.integrals:                                             # integrals over the
           f"{float(ig.drift('ke')[-1]):+.3e}, enstrophy {float(ig['enstrophy'][-1]):.3e}, ||div||_L2 {float(ig['div2'][-1]) ** 0.5:.3e}")
     graph.target = out                                      # (stands in for the ground truth a dataset carries: the error is then 0)
     print("relative L2 error per step:", " ".join(f"{v:.3e}" for v in model.integrals(graph, a.steps, ("rel_l2",), cells)["rel_l2"].tolist()))
+if a.welch:                                                 # spectra with a usable variance: half-overlapping Hann segments, averaged inside the step
+    seg = max(2 * (a.steps // 8), 4)                        # (some seven segments: one periodogram has 100 % scatter however long the rollout)
+    probe = int(((graph.pos - torch.tensor([0.7, 0.5], device=graph.pos.device)).norm(dim=1)).argmin())
+    graph.target = out                                      # (stands in for the ground truth a dataset carries: the coherence is then 1)
+    we = model.welch(graph, a.steps, seg, bins=range(seg // 2 + 1), overlap=0.5, reference="target", track=[probe])
+    k = int(we.band_power()[0].argmax())
+    print(f"Welch PSD of u over {we.segments} segments of {seg} steps: peak at {float(we.freqs[k]):.4f} cycles per step; coherence with the "
+          f"target there, median over the nodes: {float(we.coherence[:, 0, k].nanmedian()):.4f}")
+    print(f"dominant frequency of u at node {probe}, segment by segment:", " ".join(f"{f:.4f}" for f in we.dominant_by_segment(0, 0).tolist()))
+    lag = model.welch(graph, a.steps, seg, bins=range(seg // 2 + 1), overlap=0.5, reference=(probe, 0))      # phase lags behind the probe's u
+    print(f"phase lag of u behind node {probe} at that frequency: {float(lag.phase_lag[:, 0, k].min()):+.3f} .. {float(lag.phase_lag[:, 0, k].max()):+.3f} rad")
 if a.raster:                                                # the picture of a field: sampled on the device inside the step, no plotting dependency
     import numpy as np
     raster = gfd.PointSampler.grid(graph, (256, 256))          # the mesh's bounding box; .distance masks points far from every node

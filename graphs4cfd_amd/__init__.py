@@ -23,7 +23,8 @@ from .tracers import Tracers                           # Lagrangian tracers: pat
 from .ops import check_f16_range, f16_range_report     # clipped values of the default arithmetic are reported, never silent (ops.py)
 from .modes import Modes, SnapshotModes, DynamicModes    # POD and DMD of a rollout's snapshots from a device Gram matrix (Rollout.modes, GNN.modes)
 from .nn.model import Spectrum                           # a request for per-node Fourier modes of a rollout (Rollout(spectrum=), GNN.spectrum)
-from .nn.model import set_forward_validation            # bare forward() calls validate their own fp16 range (one flag read per call)
+from .nn.model import Welch                              # a request for segment-averaged spectra: Welch PSD, coherence, drift (Rollout.open(welch=), GNN.welch)
+from .nn.model import set_forward_validation           # bare forward() calls validate their own fp16 range (one flag read per call)
 from .ops import mlp_precision, set_mlp_precision      # "f16x3" (default: fp32-class two-way fp16 split on the matrix pipe) | "bf16x6" | "fp32" | "bf16" (opt-in)
 from .ops import train_precision, set_train_precision  # "bf16x6" (default) | "bf16": the backward's products of mixed-precision training
 

@@ -105,6 +105,18 @@ class g4c_rollout_spectrum_t(C.Structure):
                 ("sum", C.c_void_p), ("re", C.c_void_p), ("im", C.c_void_p)]
 
 
+WELCH_MAX_TRACK = 1024                              # most tracked rows g4c_rollout_welch keeps the per-segment power of
+
+
+class g4c_rollout_welch_t(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("stride", C.c_int32), ("seg_len", C.c_int32), ("hop", C.c_int32), ("n_bins", C.c_int32),
+                ("x_ld", C.c_int32), ("x_step", C.c_int32), ("ref_row", C.c_int32), ("ref_field", C.c_int32), ("n_track", C.c_int32),
+                ("max_segments", C.c_int32), ("window", C.c_void_p), ("tw", C.c_void_p), ("W", C.c_void_p), ("inv_L", C.c_double),
+                ("plane_ld", C.c_int64), ("pivot", C.c_void_p), ("sum", C.c_void_p), ("re", C.c_void_p), ("im", C.c_void_p),
+                ("pxx", C.c_void_p), ("cxr_re", C.c_void_p), ("cxr_im", C.c_void_p), ("ref_sum", C.c_void_p), ("ref_re", C.c_void_p),
+                ("ref_im", C.c_void_p), ("track", C.c_void_p), ("track_host", C.c_void_p), ("seg_power", C.c_void_p)]
+
+
 DERIVED_MAX_COLS, DERIVED_MAX_TERMS = 8, 3         # G4C_DERIVED_MAX_COLS / _TERMS
 JET_MAX_FIELDS = 4                                  # G4C_JET_MAX_FIELDS
 DERIVED_SQ, DERIVED_ABS, DERIVED_MAX_ABS, DERIVED_NSTAT = range(4)     # G4C_DERIVED_*
@@ -260,6 +272,7 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_rollout_moments": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_moments_t), C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_rollout_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_spectrum_t), C.c_void_p, C.c_int64, C.c_void_p]),
+    "g4c_rollout_welch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(g4c_rollout_welch_t), C.c_void_p, C.c_int64, C.c_void_p]),
     "g4c_mesh_gradient_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "g4c_mesh_derived_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),

@@ -24,7 +24,8 @@ from .. import _lib, ops
 from ..graph import Graph
 # the rollout and what rides along in its step live in rollout.py; every name stays importable from here
 from .rollout import (KEYWORDS, REORDER_MIN_NODES, Rollout, RolloutDerived, RolloutErrors, RolloutForces, RolloutIntegrals,      # noqa: F401
-                      RolloutMoments, RolloutSamples, RolloutSpectrum, Spectrum, _check_moments, _check_parts, _check_records, _check_spectrum)
+                      RolloutMoments, RolloutSamples, RolloutSpectrum, RolloutWelch, Spectrum, Welch, _check_moments, _check_parts,
+                      _check_records, _check_spectrum)
 
 
 def collate(graphs: List[Graph]) -> Graph:
@@ -392,6 +393,48 @@ class GNN(nn.Module):
             sp.snapshots = ro.result() if int(every) else None
             sp.derived = ro.derived_spectrum() if derived is not None else None
             return sp
+
+    def welch(self, graph: Union[Graph, List[Graph]], n_out: int, segment: int, bins=None, freqs=None, *, overlap=0, discard: int = 0,
+              stride: int = 1, dt: float = 1.0, taper: str = "hann", reference=None, track=None, target: bool = False,
+              capture: Optional[bool] = None) -> "RolloutWelch":
+        """Roll the model out for n_out steps and return the segment-averaged spectra of the prediction at every node (`RolloutWelch`:
+        power, psd, band_power, dominant; with a reference cross, coherence, phase_lag; with tracked rows spectrogram,
+        dominant_by_segment) — Welch's estimator over segments of `segment` samples of the steps discard, discard + stride, ... < n_out,
+        side by side (overlap = 0) or half overlapping (0.5), at the frequencies `bins` or `freqs` name (`gfd.Welch`), accumulated on the
+        device inside the step in fp64.  No prediction is held.  reference = (node, field): the coherence with and the phase lag behind
+        that signal; reference = "target": against `graph.target` ([N, >= num_fields * n_out]) at the same node and field — what is left
+        of the error once a slow phase drift is taken out — and then, or with target=True, `.target` is the spectrum of the target's
+        columns.  A list of graphs is collated as in `solve`: node and track are rows of the collated graph."""
+        assert n_out > 0, "n_out must be greater than 0."
+        if not isinstance(target, bool):
+            raise TypeError(f"target: expected a bool, got {target!r}")
+        against = target or reference == "target"
+        if against and not torch.is_tensor(getattr(graph[0] if type(graph) is list else graph, "target", None)):
+            raise ValueError("welch: reference='target' and target=True roll out against the target: the graph has no `target`")
+        spec = Welch(segment, bins, freqs, overlap=overlap, start=discard, stride=stride, dt=dt, taper=taper, reference=reference, track=track)
+        with self._rollout(graph, n_out, capture, "welch()", evaluate=against, every=0, welch=spec, target_welch=against) as ro:
+            ro.run(n_out)
+            we = ro.welch()
+            we.target = ro.target_welch() if against else None
+            return we
+
+    def evaluate_welch(self, graph: Union[Graph, List[Graph]], welch: "Welch", n_out: Optional[int] = None, *,
+                       capture: Optional[bool] = None) -> "RolloutErrors":
+        """`evaluate(graph, n_out)` with the spectral fidelity beside the errors of every step: `welch` (a `gfd.Welch`, as a rule with
+        reference="target") attaches the segment-averaged spectra of the prediction and of the target's columns (`.welch` /
+        `.target_welch`: `RolloutWelch`) — `.welch.coherence` per node, field and frequency separates wrong physics from a slow phase
+        drift, which per-step errors cannot.  (`evaluate` keeps the signature its callers know; this is its entry for `welch`.)"""
+        tgt = graph[0].target if type(graph) is list else graph.target
+        if n_out is None:
+            n_out = int(tgt.size(1)) // int(self.num_fields)
+        assert n_out > 0, "n_out must be greater than 0."
+        if not isinstance(welch, Welch):
+            raise TypeError(f"welch: expected a gfd.Welch, got {welch!r}")
+        with self._rollout(graph, n_out, capture, "evaluate_welch()", evaluate=True, every=0, welch=welch, target_welch=True) as ro:
+            ro.run(n_out)
+            errs = ro.errors()
+            errs.welch, errs.target_welch = ro.welch(), ro.target_welch()
+            return errs
 
     def modes(self, graph: Union[Graph, List[Graph]], n_out: int, modes=None, *, every: int = 1, capture: Optional[bool] = None, **spec):
         """Roll the model out for n_out steps and return the modal analysis of the predictions kept (`SnapshotModes`: POD singular

@@ -6,7 +6,7 @@ enqueues its launches of a step (`launch`), is told when steps are about to be t
 (`read`).  `_PARTS` lists them in launch order; `Rollout` loops over those asked for and never reaches inside one.  `_check_parts`
 turns the keywords into checked specs, once per call: `Rollout.__init__` calls it, and so does `GNN._rollout` before it collates or
 moves anything.  The result classes (`RolloutErrors`, `RolloutMoments`, `RolloutSpectrum`, `RolloutDerived`, `RolloutSamples`,
-`RolloutForces`, `RolloutIntegrals`) and the request `Spectrum` live here too; nn/model.py re-exports every name."""
+`RolloutForces`, `RolloutIntegrals`, `RolloutWelch`) and the requests `Spectrum` and `Welch` live here too; nn/model.py re-exports every name."""
 from __future__ import annotations
 
 import functools
@@ -117,7 +117,15 @@ class Rollout(StepDriver):
         one-workgroup sum) per source and step — the prediction, prediction − target, the target, the derived columns, as far as the
         names need them — behind the derived columns' launches.  `integral_options`: velocity (the fields of u and v, default (0, 1)),
         box, bodies.  `integrals()` returns them (`RolloutIntegrals`); steps run again after `rewind()` or a recomputation overwrite
-        their rows."""
+        their rows.
+
+        Segment-averaged spectra at every node (opt-in, no record either; keywords of `Rollout.open`): `welch` — a `gfd.Welch`: segments
+        of L samples of a lattice, side by side or half overlapping, K frequencies, a taper, a reference — accumulates Welch's estimate
+        of the power spectrum of the prediction and, with a reference (a node's signal, or the target at the same node), of the
+        cross-spectrum with it: one `g4c_rollout_welch` call (two launches) per step behind the spectra, in front of the closing launch.
+        `target_welch=True` (needs `target=` and `welch=`) the same of the target's columns.  `welch()` / `target_welch()` return them
+        (`RolloutWelch`: power, psd, coherence, phase_lag, spectrogram); after `rewind()` or a recomputation they hold the segments
+        closed since."""
         specs = _check_parts(locals(), graph, int(model.num_fields), int(max_steps), target is not None)
         self._build(specs, model, graph, max_steps, capture, reorder, label, every, probes, target, mask)
 
@@ -125,7 +133,8 @@ class Rollout(StepDriver):
     def open(cls, model: "GNN", graph: Graph, max_steps: int, *, capture: bool = True, reorder: Optional[bool] = None, label: str = "Rollout",
              **keywords) -> "Rollout":
         """`Rollout(model, graph, max_steps, ...)` with every record and part named by keyword: those of the constructor's signature and
-        the parts that came after it — `integrals=`, `integral_volumes=`, `integral_options=` (`KEYWORDS` lists them all).  The
+        the parts that came after it — `integrals=`, `integral_volumes=`, `integral_options=`, `welch=`, `target_welch=` (`KEYWORDS` lists
+        them all).  The
         constructor's own signature stays what its callers know."""
         if set(keywords) - set(KEYWORDS):
             raise TypeError(f"Rollout.open: unexpected keyword argument(s) {sorted(set(keywords) - set(KEYWORDS))}")
@@ -284,6 +293,16 @@ class Rollout(StepDriver):
     def derived_spectrum(self) -> "RolloutSpectrum":
         """The same of the derived columns (`derived_spectrum=`): its fields are `derived().columns`."""
         return self._read("derived_spectrum", "was")
+
+    def welch(self) -> "RolloutWelch":
+        """The segment-averaged spectra of the prediction `welch=` asked for (`RolloutWelch`, fp64 device tensors in the caller's rows) —
+        validated first, like `result()`; one device -> host copy of three integers per accumulator."""
+        return self._read("welch", "was")
+
+    def target_welch(self) -> "RolloutWelch":
+        """The same of the target's columns of the steps taken, by the same tables (`target_welch=True`)."""
+        part = self._parts.get("welch")
+        return self._deliver(part is not None and part.spec["target_welch"], "no target_welch= was asked for", lambda: part.read_target(self))
 
     def derived(self) -> "RolloutDerived":
         """The flow diagnostics `derived=` asked for, of the `steps_done` steps taken (`RolloutDerived`) — validated first, like
@@ -755,6 +774,305 @@ class RolloutSpectrum:
     def __repr__(self):
         return (f"RolloutSpectrum(count={self.count}, samples={self.samples}, origin={self.origin}, stride={self.stride}, taper={self.taper!r}, "
                 f"fields={self.fields}, bins={int(self.tw.size(1))}, nodes={int(self.pivot.size(0))})")
+
+
+class Welch:
+    """A request for segment-averaged spectra of a rollout at every node (`Rollout.open(welch=)`, `GNN.welch` builds one): Welch's
+    estimator over segments of `segment` samples (L >= 2) of the lattice start, start + stride, ..., each tapered ("hann" or "rect"),
+    its mean removed, transformed at K chosen frequencies — `bins` (integers 0 <= b <= L // 2: the frequencies b / (L stride dt)) or
+    `freqs` (cycles per unit of time, at most the Nyquist frequency), exactly one of them — and averaged.  `overlap`: 0 (segments side
+    by side) or 0.5 (each starts half a segment after the one before; L even).  `reference`: None, "target" (the rollout's target at
+    the same node and field: the coherence of prediction and ground truth) or (node, field) in the caller's numbering (one signal for
+    all nodes and fields: phase lags, the part of the wake locked to it) — with one, the cross-spectrum is averaged too.  `track`: node
+    rows (caller's numbering, at most 1024, repeats allowed) whose power is also kept segment by segment (`spectrogram`).  A last
+    partial segment contributes nothing.  Checked when the rollout is built."""
+
+    def __init__(self, segment, bins=None, freqs=None, *, overlap=0, start: int = 0, stride: int = 1, dt: float = 1.0, taper: str = "hann",
+                 reference=None, track=None):
+        self.segment, self.bins, self.freqs, self.overlap, self.start, self.stride = segment, bins, freqs, overlap, start, stride
+        self.dt, self.taper, self.reference, self.track = dt, taper, reference, track
+
+    def __repr__(self):
+        which = f"bins={self.bins!r}" if self.bins is not None else f"freqs={self.freqs!r}"
+        return (f"Welch({self.segment}, {which}, overlap={self.overlap}, start={self.start}, stride={self.stride}, dt={self.dt}, "
+                f"taper={self.taper!r}, reference={self.reference!r}, track={'None' if self.track is None else '[...]'})")
+
+
+def _check_welch(name: str, spec, nf: int, max_steps: int, n_nodes: int, has_target: bool):
+    """A `welch=` argument of `Rollout` -> the lattice, the segments and the host tables (a dict: start, stride, L, H, dt, taper, tw, w, W,
+    freqs, reference — None, "target" or (node, field) —, track — None or a list of rows —, max_segments), or None when none is asked
+    for.  Nothing is moved or allocated on a device."""
+    if spec is None:
+        return None
+    if not isinstance(spec, Welch):
+        raise TypeError(f"{name}: expected a gfd.Welch or None, got {spec!r}")
+    if not _integer(spec.segment) or not _integer(spec.start) or not _integer(spec.stride):
+        raise TypeError(f"{name}: segment, start and stride are integers, got {spec!r}")
+    if isinstance(spec.dt, bool) or not isinstance(spec.dt, (int, float)):
+        raise TypeError(f"{name}: dt: expected a number, got {spec.dt!r}")
+    if not isinstance(spec.taper, str):
+        raise TypeError(f"{name}: taper: expected 'rect' or 'hann', got {spec.taper!r}")
+    if isinstance(spec.overlap, bool) or not isinstance(spec.overlap, (int, float)) or spec.overlap not in (0, 0.5):
+        raise ValueError(f"{name}: overlap: expected 0 or 0.5 (segments side by side, or half overlapping), got {spec.overlap!r}")
+    L = spec.segment
+    if L < 2:
+        raise ValueError(f"{name}: segment {L} (>= 2 samples)")
+    if spec.overlap and L % 2:
+        raise ValueError(f"{name}: overlap 0.5 needs an even segment, got segment {L}")
+    H = L // 2 if spec.overlap else L
+    if spec.start < 0 or spec.start >= max_steps:
+        raise ValueError(f"{name}: start {spec.start} of a rollout of {max_steps} steps (0 <= start < max_steps)")
+    if spec.stride < 1:
+        raise ValueError(f"{name}: stride {spec.stride} (>= 1)")
+    lattice = len(range(spec.start, max_steps, spec.stride))
+    if lattice < L:
+        raise ValueError(f"{name}: segment {L} of the {lattice} steps {spec.start}, {spec.start + spec.stride}, ... < {max_steps}: not one "
+                         "segment would be complete")
+    try:
+        tw, w, freqs = ops.spectrum_table(bins=spec.bins, freqs=spec.freqs, samples=L, stride=spec.stride, dt=spec.dt, taper=spec.taper)
+    except (TypeError, ValueError) as e:
+        raise type(e)(f"{name}: {e}") from None
+    if nf > _lib.REC_MAX_NF:
+        raise NotImplementedError(f"{name}: the spectra cover up to {_lib.REC_MAX_NF} fields, got {nf}")
+    if int(tw.size(1)) > _lib.SPECTRUM_MAX_BINS:
+        raise NotImplementedError(f"{name}: {int(tw.size(1))} frequencies (at most {_lib.SPECTRUM_MAX_BINS} per spectrum)")
+    reference = spec.reference
+    if reference is not None and reference != "target":
+        if (isinstance(reference, str) or not isinstance(reference, (tuple, list)) or len(reference) != 2
+                or not all(_integer(v) for v in reference)):
+            raise TypeError(f"{name}: reference: expected None, 'target' or a pair of integers (node, field), got {reference!r}")
+        node, field = reference
+        if not 0 <= node < n_nodes or not 0 <= field < nf:
+            raise ValueError(f"{name}: reference: node {node} of {n_nodes} nodes, field {field} of {nf} fields")
+        reference = (int(node), int(field))
+    if reference == "target" and not has_target:
+        raise ValueError(f"{name}: reference='target': the coherence with the target needs target=")
+    track = spec.track
+    if track is not None:
+        if torch.is_tensor(track):
+            if track.dtype.is_floating_point or track.dtype == torch.bool or track.is_complex() or track.dim() != 1:
+                raise TypeError(f"{name}: track: expected a 1-D integer tensor or a sequence of node rows, got {track.dtype} {tuple(track.shape)}")
+            track = track.tolist()
+        elif isinstance(track, (str, bytes)) or not hasattr(track, "__iter__"):
+            raise TypeError(f"{name}: track: expected a 1-D integer tensor or a sequence of node rows, got {track!r}")
+        track = list(track)
+        if not all(_integer(v) for v in track):
+            raise TypeError(f"{name}: track: expected integers, got {track!r}")
+        if len(track) > _lib.WELCH_MAX_TRACK:
+            raise NotImplementedError(f"{name}: track: {len(track)} rows (at most {_lib.WELCH_MAX_TRACK})")
+        if track and (min(track) < 0 or max(track) >= n_nodes):
+            raise ValueError(f"{name}: track: rows {min(track)} .. {max(track)} of a graph of {n_nodes} nodes")
+        track = track or None
+    return dict(start=int(spec.start), stride=int(spec.stride), L=int(L), H=int(H), dt=float(spec.dt), taper=spec.taper, tw=tw, w=w,
+                W=ops.welch_weights(tw), freqs=freqs, reference=reference, track=track, max_segments=(lattice - L) // H + 1)
+
+
+class _WelchSet(_Accumulator):
+    """One Welch accumulator of a `Rollout` and the call that updates it: `ops.welch_planes` planes (two alternating sets of pivot, sum,
+    re, im; pxx; with a reference cxr_re, cxr_im) of the model's nf columns of the samples, the device-side window {origin, last,
+    closed}, and the tables `spec` (`_check_welch`) holds, uploaded once.  `restart()` is a fill of the window alone: segment 0 stores."""
+
+    def __init__(self, ro: "Rollout", spec: dict, reference: bool, x: Optional[torch.Tensor] = None, x_step: int = 0, tracked=None):
+        dev, nf, K = ro.field.device, ro.nf, int(spec["tw"].size(1))
+        self.node_rows, self.max_steps, self.start, self.stride, self.x, self.x_step = True, ro.max_steps, spec["start"], spec["stride"], x, x_step
+        self.nf, self.K, self.spec, self.reference = nf, K, spec, reference
+        self.planes = torch.zeros((ops.welch_planes(nf, K, reference), int(ro.graph.num_nodes)), dtype=torch.float64, device=dev)
+        parts = self.planes.split(ops.welch_split(nf, K, reference))
+        self.pivot, self.sum, self.re, self.im, self.pxx = parts[:5]
+        self.cxr = tuple(parts[5:]) if reference else None
+        self.window = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.tw, self.W = spec["tw"].to(dev), spec["W"].to(dev)
+        self.track = self.track_host = self.seg_power = None
+        if tracked is not None:
+            self.track_host = tracked.to(torch.int32).cpu().contiguous()
+            self.track = self.track_host.to(dev)
+            self.seg_power = torch.zeros((spec["max_segments"], int(tracked.numel()), nf, K), dtype=torch.float64, device=dev)
+        self.restart(ro, False)
+
+    def restart(self, ro: "Rollout", again: bool) -> None:
+        """origin = the first step of the lattice at or after the first slot; nothing accumulated, no segment closed."""
+        self.origin = _lattice_origin(self.start, self.stride, ro._first_slot)
+        self.window[:1].fill_(self.origin)
+        self.window[1:2].fill_(-1)
+        self.window[2:].fill_(0)
+
+    def launch(self, ro: "Rollout", pred: torch.Tensor, ref=None, ref_row: int = -1, ref_field: int = -1) -> None:
+        ops.rollout_welch(pred if self.x is None else self.x, ro.step_counter, self.nf, self.max_steps, self.window, self.tw, self.W, self.pivot,
+                          self.sum, self.re, self.im, self.pxx, hop=self.spec["H"], stride=self.stride, x_step=self.x_step, cxr=self.cxr,
+                          ref=ref, ref_row=ref_row, ref_field=ref_field, track=self.track, track_host=self.track_host,
+                          seg_power=self.seg_power)
+
+    def table(self, ro: "Rollout", planes: torch.Tensor) -> torch.Tensor:
+        """[nf K, N] as accumulated -> [N, nf, K] in the caller's rows."""
+        return self.rows(ro, planes).unflatten(1, (self.nf, self.K))
+
+
+class _Welch(_Part):
+    """The Welch spectra of a `Rollout`: the prediction's accumulator and, when `reference="target"` or `target_welch=True` asks for it,
+    the one over the target's columns, which is launched first (the prediction's close reads its finished sums).  A reference node and
+    the tracked rows are mapped into the rollout's numbering here, once."""
+    name = "welch"
+
+    @staticmethod
+    def check(kw, ctx, specs):
+        if not isinstance(kw["target_welch"], bool):
+            raise TypeError(f"target_welch: expected a bool, got {kw['target_welch']!r}")
+        n_nodes = sum(int(g.num_nodes) for g in ctx.graphs)
+        spec = _check_welch("welch", kw["welch"], ctx.nf, ctx.max_steps, n_nodes, ctx.has_target)
+        if kw["target_welch"] and (spec is None or not ctx.has_target):
+            raise ValueError("target_welch: the Welch spectrum of the target needs target= and welch= (it uses the same tables)")
+        return None if spec is None else dict(spec, target_welch=kw["target_welch"])
+
+    def __init__(self, ro: "Rollout", spec: dict):
+        dev, ref = ro.field.device, spec["reference"]
+        self.spec, self.ref_row, self.ref_field = spec, -1, -1
+        self.tgt = _WelchSet(ro, spec, False, x=ro._rec.target, x_step=ro.nf) if (ref == "target" or spec["target_welch"]) else None
+        tracked = None
+        if spec["track"] is not None:
+            tracked = torch.tensor(spec["track"], dtype=torch.long)
+            if ro._perm is not None:
+                tracked = ro._inv.cpu()[tracked]
+        if ref is not None and ref != "target":
+            self.ref_row, self.ref_field = (ref[0] if ro._perm is None else int(ro._inv[ref[0]])), ref[1]
+        self.pred = _WelchSet(ro, spec, ref is not None, tracked=tracked)
+        self.nested = [acc for acc in (self.tgt, self.pred) if acc is not None]
+        self.device = dev
+
+    def launch(self, ro: "Rollout", pred: torch.Tensor) -> None:
+        if self.tgt is not None:
+            self.tgt.launch(ro, pred)
+        if self.spec["reference"] == "target":
+            self.pred.launch(ro, pred, ref=(self.tgt.sum, self.tgt.re, self.tgt.im))
+        else:
+            self.pred.launch(ro, pred, ref_row=self.ref_row, ref_field=self.ref_field)
+
+    def _result(self, ro: "Rollout", acc: _WelchSet, **more) -> "RolloutWelch":
+        sp = self.spec
+        origin, _, closed = acc.window.tolist()
+        return RolloutWelch(closed, origin, sp["stride"], sp["L"], sp["H"], sp["dt"], sp["taper"], sp["freqs"], sp["w"], acc.table(ro, acc.pxx), **more)
+
+    def read_target(self, ro: "Rollout") -> "RolloutWelch":
+        return self._result(ro, self.tgt)
+
+    def read(self, ro: "Rollout") -> "RolloutWelch":
+        acc, ref, more = self.pred, self.spec["reference"], {}
+        pxx = acc.table(ro, acc.pxx)
+        if ref is not None:
+            more.update(cxr_re=acc.table(ro, acc.cxr[0]), cxr_im=acc.table(ro, acc.cxr[1]), reference=ref,
+                        ref_pxx=self.tgt.table(ro, self.tgt.pxx) if ref == "target" else pxx[ref[0], ref[1]].reshape(1, 1, -1))
+        if acc.seg_power is not None:
+            closed = int(acc.window[2])
+            more.update(seg_power=acc.seg_power[:closed].clone(), track=torch.tensor(self.spec["track"], dtype=torch.long))
+        return self._result(ro, acc, **more)
+
+
+class RolloutWelch:
+    """Segment-averaged spectra of a rollout at every node (`Rollout.welch()` / `target_welch()`, `GNN.welch()`) at the K frequencies
+    `freqs` (cycles per unit of time) over the `segments` closed segments of `segment` samples, `hop` samples apart, of the steps origin,
+    origin + stride, ...: the raw fp64 sums, as the device accumulated them — `pxx` [N, nf, K] = Σ_s |A_s|², A_s the tapered transform of
+    segment s with its mean removed; with a reference R, `cxr_re`, `cxr_im` [N, nf, K] = Σ_s A_s conj(R_s) and `ref_pxx` (Σ_s |R_s|²,
+    broadcast against pxx); with tracked rows `seg_power` [segments, P, nf, K] = |A_s|² at the rows `track` — and the taper `w` with `S` =
+    Σw and `S2` = Σw².  From them, `power` = pxx / (segments S²) — A cos(ωt + φ) on a bin gives (A / 2)², the scale of
+    `RolloutSpectrum.power` —; `psd` the one-sided density power S² / (fs S2), fs = 1 / (stride dt), doubled away from 0 and the Nyquist
+    frequency; `cross` = (cxr_re + i cxr_im) / (segments S²), complex; `coherence` = |Σ A conj R|² / (Σ|A|² Σ|R|²) in [0, 1] (identically 1
+    after one segment; NaN where either power is zero); `phase_lag` = arg cross, the phase of the node minus that of the reference;
+    `band_power(mask)` [nf, K] and `dominant(field, mask)` as in `RolloutSpectrum`; `spectrogram` = seg_power / S² and
+    `dominant_by_segment(p, field)` [segments]: the frequency of the largest power of tracked row p in every segment — its drift over
+    the rollout.  `segments == 0` raises on the derived quantities.  Works on tensors of any device.  `target`: the spectrum of the
+    target's columns when `GNN.welch` formed it, else None."""
+
+    def __init__(self, segments: int, origin: int, stride: int, segment: int, hop: int, dt: float, taper: str, freqs: torch.Tensor,
+                 w: torch.Tensor, pxx: torch.Tensor, cxr_re: Optional[torch.Tensor] = None, cxr_im: Optional[torch.Tensor] = None,
+                 ref_pxx: Optional[torch.Tensor] = None, seg_power: Optional[torch.Tensor] = None, track: Optional[torch.Tensor] = None,
+                 reference=None):
+        if pxx.dim() != 3 or tuple(freqs.shape) != (int(pxx.size(2)),) or tuple(w.shape) != (int(segment),):
+            raise ValueError(f"pxx: expected [N, nf, K] with freqs [K] and w [segment], got {tuple(pxx.shape)}, {tuple(freqs.shape)}, {tuple(w.shape)}")
+        if (cxr_re is None) != (cxr_im is None) or (cxr_re is None) != (ref_pxx is None):
+            raise ValueError("cxr_re: a cross-spectrum is cxr_re, cxr_im and ref_pxx together")
+        for t, name in ((cxr_re, "cxr_re"), (cxr_im, "cxr_im")):
+            if t is not None and t.shape != pxx.shape:
+                raise ValueError(f"{name}: expected shape {tuple(pxx.shape)}, got {tuple(t.shape)}")
+        if seg_power is not None and (track is None or seg_power.dim() != 4 or int(seg_power.size(0)) != int(segments)
+                                      or tuple(seg_power.shape[1:]) != (int(track.numel()),) + tuple(pxx.shape[1:])):
+            raise ValueError(f"seg_power: expected [segments, P, nf, K] with track [P], got {tuple(seg_power.shape)}")
+        if int(segments) < 0:
+            raise ValueError(f"segments: {segments}")
+        self.segments, self.origin, self.stride, self.segment, self.hop = int(segments), int(origin), int(stride), int(segment), int(hop)
+        self.dt, self.taper, self.freqs, self.w = float(dt), taper, freqs, w
+        self.S, self.S2 = float(w.to(torch.float64).sum()), float((w.to(torch.float64) ** 2).sum())
+        self.pxx, self.cxr_re, self.cxr_im, self.ref_pxx, self.seg_power, self.track = pxx, cxr_re, cxr_im, ref_pxx, seg_power, track
+        self.reference, self.target = reference, None
+
+    @property
+    def fields(self) -> int:
+        return int(self.pxx.size(1))
+
+    def _norm(self) -> float:
+        if self.segments <= 0:
+            raise RuntimeError("RolloutWelch: no segment was closed (segments == 0)")
+        return float(self.segments) * self.S * self.S
+
+    def _crossed(self):
+        if self.cxr_re is None:
+            raise RuntimeError("RolloutWelch: no reference= was asked for: there is no cross-spectrum")
+        return self._norm()
+
+    @property
+    def power(self) -> torch.Tensor:
+        return self.pxx / self._norm()
+
+    @property
+    def psd(self) -> torch.Tensor:
+        fs = 1.0 / (self.stride * self.dt)
+        f = self.freqs.to(torch.float64)
+        sides = (1.0 + ((f > 0) & (f < 0.5 * fs * (1.0 - 1e-12))).to(torch.float64)).to(self.pxx.device)
+        return self.power * (self.S * self.S / (fs * self.S2)) * sides
+
+    @property
+    def cross(self) -> torch.Tensor:
+        norm = self._crossed()
+        return torch.complex(self.cxr_re, self.cxr_im) / norm
+
+    @property
+    def coherence(self) -> torch.Tensor:
+        self._crossed()
+        return (self.cxr_re ** 2 + self.cxr_im ** 2) / (self.pxx * self.ref_pxx.to(self.pxx.device))
+
+    @property
+    def phase_lag(self) -> torch.Tensor:
+        self._crossed()
+        return torch.atan2(self.cxr_im, self.cxr_re)
+
+    def band_power(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[nf, K]: the power summed over the nodes (`mask` bool [N]: over those nodes only)."""
+        p = self.power
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (int(p.size(0)),):
+                raise ValueError(f"mask: expected a bool tensor of shape ({int(p.size(0))},), got {getattr(mask, 'dtype', type(mask).__name__)} "
+                                 f"{tuple(getattr(mask, 'shape', ()))}")
+            p = p[mask.to(p.device)]
+        return p.sum(0)
+
+    def dominant(self, field: int = 0, mask: Optional[torch.Tensor] = None) -> float:
+        """The frequency (of `freqs`) with the largest band power of `field`."""
+        return float(self.freqs[int(self.band_power(mask)[field].argmax())])
+
+    @property
+    def spectrogram(self) -> torch.Tensor:
+        """[segments, P, nf, K]: the power of every closed segment at the tracked rows, on the scale of `power`."""
+        if self.seg_power is None:
+            raise RuntimeError("RolloutWelch: no track= was asked for: there is no per-segment power")
+        self._norm()
+        return self.seg_power / (self.S * self.S)
+
+    def dominant_by_segment(self, p: int = 0, field: int = 0) -> torch.Tensor:
+        """[segments]: the frequency (of `freqs`) of the largest power of tracked row `p`, field `field`, in every closed segment."""
+        return self.freqs.to(self.spectrogram.device)[self.spectrogram[:, p, field].argmax(dim=1)]
+
+    def __repr__(self):
+        return (f"RolloutWelch(segments={self.segments}, segment={self.segment}, hop={self.hop}, origin={self.origin}, stride={self.stride}, "
+                f"taper={self.taper!r}, fields={self.fields}, bins={int(self.pxx.size(2))}, nodes={int(self.pxx.size(0))}, "
+                f"reference={self.reference!r})")
 
 
 class _Derived(_Part):
@@ -1451,6 +1769,7 @@ class RolloutErrors:
         self.moments = self.error_moments = None        # `RolloutMoments` when GNN.evaluate(moments= / error_moments=) asked for them
         self.derived = None                             # `RolloutDerived` when GNN.evaluate(derived=) asked for it
         self.spectrum = self.target_spectrum = None     # `RolloutSpectrum` when GNN.evaluate(spectrum=) asked for them
+        self.welch = self.target_welch = None           # `RolloutWelch` when GNN.evaluate_welch formed them
         n = float(n_nodes)
         sq, ab, mx, ty, ty2, abm = (sums[..., k] for k in range(_lib.REC_NSTAT))
         self.mse, self.mae, self.max_abs = sq / n, ab / n, mx
@@ -1475,14 +1794,15 @@ class RolloutErrors:
 
 
 # The parts of a step, in the order `Rollout._one` launches them (the records' closing launch comes last, outside this list) ...
-_PARTS = (_Derived, _Integrals, _Samples, _Forces, _NodeMoments, _ErrorMoments, _NodeSpectrum, _TargetSpectrum, _DerivedSpectrum, _Tracers)
+_PARTS = (_Derived, _Integrals, _Samples, _Forces, _NodeMoments, _ErrorMoments, _NodeSpectrum, _TargetSpectrum, _DerivedSpectrum, _Welch, _Tracers)
 # ... and in the order their keywords are checked: the precedence of the argument errors
-_CHECKED = (_Derived, _DerivedSpectrum, _NodeSpectrum, _TargetSpectrum, _Samples, _Tracers, _Forces, _NodeMoments, _ErrorMoments, _Integrals)
+_CHECKED = (_Derived, _DerivedSpectrum, _NodeSpectrum, _TargetSpectrum, _Samples, _Tracers, _Forces, _NodeMoments, _ErrorMoments, _Integrals,
+            _Welch)
 # every keyword of `Rollout` that asks for a record or a part, with its default: named once, in the signature of `Rollout.__init__`
 KEYWORDS = {name: p.default for name, p in inspect.signature(Rollout.__init__).parameters.items()
             if name not in ("self", "model", "graph", "max_steps", "capture", "reorder", "label")}
 # ... and those of the parts `Rollout.open` and `GNN._rollout` take beyond that signature
-KEYWORDS.update(integrals=None, integral_volumes=None, integral_options=None)
+KEYWORDS.update(integrals=None, integral_volumes=None, integral_options=None, welch=None, target_welch=False)
 
 
 def _check_parts(keywords: dict, graph, nf: int, max_steps: int, has_target: bool) -> dict:

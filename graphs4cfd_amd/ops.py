@@ -688,6 +688,98 @@ def rollout_spectrum(x: Tensor, step: Tensor, nf: int, max_steps: int, window: T
     _lib.check(lib.g4c_rollout_spectrum(_lib.ptr(x), nf, C.byref(s), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
 
 
+def welch_planes(nf: int, K: int, reference: bool) -> int:
+    """Planes of one Welch spectrum's accumulators: two sets of pivot and sum (nf each) and re and im (nf K each, plane f K + k), the
+    averaged power pxx (nf K) and, with a reference, the averaged cross-spectrum cxr_re, cxr_im (nf K each)."""
+    return 2 * spectrum_planes(nf, K) + (3 if reference else 1) * nf * K
+
+
+def welch_split(nf: int, K: int, reference: bool):
+    """The plane counts of (pivot, sum, re, im, pxx[, cxr_re, cxr_im]) in a buffer of `welch_planes` planes."""
+    return (2 * nf, 2 * nf, 2 * nf * K, 2 * nf * K) + (nf * K,) * (3 if reference else 1)
+
+
+def welch_weights(tw: Tensor) -> Tensor:
+    """W [K, 2] = Σ_q tw[q], the rows added one by one in order (the sum g4c_rollout_welch removes a segment's mean with)."""
+    W = torch.zeros(tw.shape[1:], dtype=torch.float64)
+    for q in range(int(tw.size(0))):
+        W = W + tw[q]
+    return W
+
+
+def rollout_welch(x: Tensor, step: Tensor, nf: int, max_steps: int, window: Tensor, tw: Tensor, W: Tensor, pivot: Tensor, sum: Tensor,
+                  re: Tensor, im: Tensor, pxx: Tensor, *, hop: int, stride: int = 1, x_step: int = 0, cxr=None, ref=None, ref_row: int = -1,
+                  ref_field: int = -1, track: Optional[Tensor] = None, track_host: Optional[Tensor] = None,
+                  seg_power: Optional[Tensor] = None) -> None:
+    """g4c_rollout_welch: add step t = step[0] (read on the device) to the segment(s) of Welch's estimator it belongs to and, when it
+    ends a segment, the segment's power (and cross-spectrum with a reference) to the averages.  x, step, stride, x_step: as in
+    `rollout_spectrum`.  window: int32 [3] on the device, {origin, last, closed}.  tw: float64 [L, K, 2] (`spectrum_table(samples=L)`, on
+    the device), L >= 2 the segment's samples; W: float64 [K, 2] (`welch_weights(tw)`, on the device); hop: L (no overlap) or L / 2.
+    pivot / sum: float64 [2 nf, N]; re / im: [2 nf K, N] (the two alternating sets); pxx: [nf K, N]; unit stride along the nodes and one
+    common plane stride.  A reference: cxr = (cxr_re, cxr_im), [nf K, N] each of the same plane stride, and ref = (sum, re, im) of the
+    reference's accumulator (None: this one's own), ref_row >= 0 one row for all rows (< 0: the same row), ref_field >= 0 one field for
+    all fields (< 0: the same field).  Tracked rows: track int32 [P] on the device, track_host the same on the host, seg_power float64
+    [max_segments, P, nf, K] on the device."""
+    nf, max_steps, stride, x_step, hop, ref_row, ref_field = int(nf), int(max_steps), int(stride), int(x_step), int(hop), int(ref_row), int(ref_field)
+    what = "rollout_welch"
+    a = Args(what, TypeError)
+    a.dtype(x, "x", torch.float32)
+    if nf <= 0 or x_step not in (0, nf):
+        raise ValueError(f"x_step: {what}: nf = {nf} (>= 1) and x_step = {x_step} (0: x is the sample, nf: x holds every step's columns)")
+    a.at_least(max_steps, "max_steps", 0)
+    if x_step:
+        n_nodes, _, x_ld = a.strided_rows(x, "x", min_cols=nf * max_steps)
+    else:
+        n_nodes, _, x_ld = a.strided_rows(x, "x", cols=nf)
+    a.step_index(step, entries=2)
+    a.step_index(window, "window", entries=3)
+    a.at_least(stride, "stride", 1)
+    a.dtype(tw, "tw", torch.float64)
+    if tw.dim() != 3 or int(tw.size(2)) != 2 or int(tw.size(0)) < 2 or int(tw.size(1)) < 1 or not tw.is_contiguous():
+        raise ValueError(f"tw: {what}: expected a contiguous [L >= 2, K >= 1, 2], got shape {tuple(tw.shape)} strides {tuple(tw.stride())}")
+    L, K = int(tw.size(0)), int(tw.size(1))
+    a.tensor(W, "W", torch.float64, shape=(K, 2))
+    planes = [("pivot", pivot, 2 * nf), ("sum", sum, 2 * nf), ("re", re, 2 * nf * K), ("im", im, 2 * nf * K), ("pxx", pxx, nf * K)]
+    with_ref = cxr is not None or ref is not None or ref_row >= 0 or ref_field >= 0
+    if with_ref:
+        if cxr is None or len(cxr) != 2:
+            raise ValueError(f"cxr: {what}: a reference needs cxr = (cxr_re, cxr_im)")
+        ref = (sum, re, im) if ref is None else tuple(ref)
+        if len(ref) != 3:
+            raise ValueError(f"ref: {what}: expected (sum, re, im) of the reference's accumulator, got {len(ref)} tensors")
+        planes += [("cxr_re", cxr[0], nf * K), ("cxr_im", cxr[1], nf * K), ("ref_sum", ref[0], 2 * nf), ("ref_re", ref[1], 2 * nf * K),
+                   ("ref_im", ref[2], 2 * nf * K)]
+        if ref_row >= max(n_nodes, 1):
+            raise ValueError(f"ref_row: {what}: row {ref_row} of {n_nodes} nodes")
+        if ref_field >= nf:
+            raise ValueError(f"ref_field: {what}: field {ref_field} of {nf} fields")
+    plane_ld = a.planes_f64(n_nodes, *planes)
+    n_track = max_segments = 0
+    if track is not None or track_host is not None or seg_power is not None:
+        if track is None or track_host is None or seg_power is None:
+            raise ValueError(f"track: {what}: tracked rows need track, track_host and seg_power")
+        a.tensor(track, "track", torch.int32, dim=1)
+        a.tensor(track_host, "track_host", torch.int32, shape=track.shape)
+        if track_host.device.type != "cpu":
+            raise ValueError(f"track_host: {what}: expected a host tensor, got one on '{track_host.device}'")
+        n_track = int(track.numel())
+        a.tensor(seg_power, "seg_power", torch.float64, dim=4)
+        if tuple(seg_power.shape[1:]) != (n_track, nf, K):
+            raise ValueError(f"seg_power: {what}: expected [max_segments, {n_track}, {nf}, {K}], got {tuple(seg_power.shape)}")
+        max_segments = int(seg_power.size(0))
+    lib = _lib.load()
+    dev = _lib.require_hip(x, step, window, tw, W, *(t for _, t, _ in planes), track, seg_power)
+    s = _lib.g4c_rollout_welch_t(max_steps=max_steps, stride=stride, seg_len=L, hop=hop, n_bins=K, x_ld=x_ld, x_step=x_step,
+                                 ref_row=ref_row if with_ref else -1, ref_field=ref_field if with_ref else -1, n_track=n_track,
+                                 max_segments=max_segments, window=_lib.ptr(window), tw=_lib.ptr(tw), W=_lib.ptr(W), inv_L=1.0 / L,
+                                 plane_ld=plane_ld, pivot=_lib.ptr(pivot), sum=_lib.ptr(sum), re=_lib.ptr(re), im=_lib.ptr(im),
+                                 pxx=_lib.ptr(pxx), cxr_re=_lib.ptr(cxr[0]) if with_ref else None, cxr_im=_lib.ptr(cxr[1]) if with_ref else None,
+                                 ref_sum=_lib.ptr(ref[0]) if with_ref else None, ref_re=_lib.ptr(ref[1]) if with_ref else None,
+                                 ref_im=_lib.ptr(ref[2]) if with_ref else None, track=_lib.ptr(track) if n_track else None,
+                                 track_host=_lib.ptr(track_host) if n_track else None, seg_power=_lib.ptr(seg_power) if n_track else None)
+    _lib.check(lib.g4c_rollout_welch(_lib.ptr(x), nf, C.byref(s), _lib.ptr(step), n_nodes, _lib.stream_handle(dev)))
+
+
 def mesh_gradient_weights(rel: Tensor, csr, src32: Tensor, power: int = 2, out=None):
     """g4c_mesh_gradient_weights: the least-squares gradient weights of a mesh, once per mesh.  `csr` is the CSR-by-target of its
     edges (`plan.edge_csr(edge_index, n_nodes)[1]`: off int32 [N + 1], perm int32 [E] or None), src32 int32 [E] their senders and rel

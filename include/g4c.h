@@ -607,6 +607,57 @@ typedef struct g4c_rollout_spectrum {
 int g4c_rollout_spectrum(const float *x, int32_t nf, const g4c_rollout_spectrum_t *s /*host*/, const int32_t *step, int64_t n_nodes,
                          void *stream);
 
+/* Segment-averaged spectra of a rollout at every node (csrc/rollout_welch.hip): Welch's estimator of the power spectrum, and of the
+ * cross-spectrum with a reference signal, at n_bins chosen frequencies.  One call per step and spectrum, behind g4c_rollout_spectrum
+ * and BEFORE the step's closing launch; it enqueues two kernels (accumulate, close), reads t = step[0] and origin = window[0] on the
+ * device, synchronises nothing, allocates nothing, and writes neither x nor step.  The sample x_f is that of g4c_rollout_spectrum
+ * (x_ld, x_step).  Step t is sample j = (t - origin) / stride iff 0 <= t < max_steps, t >= origin and (t - origin) % stride == 0; any
+ * other step touches nothing.  Sample j is position q = j - s hop of segment s when 0 <= q < seg_len; hop == seg_len (no overlap) or
+ * 2 hop == seg_len (half overlap): one or two segments.  Segment s lives in accumulator set c = s & 1: pivot and sum have 2 nf planes
+ * (plane c nf + f), re and im 2 nf n_bins (plane (c nf + f) n_bins + k).
+ * Accumulate: at q == 0 the set is STORED, pivot = x, sum = re = im = 0; else d = x - pivot, sum += d, re_fk += d tw[q,k,0], im_fk +=
+ * d tw[q,k,1] (tw: device fp64 [seg_len, n_bins, 2], any table will do); it leaves window[1] = t.
+ * Close: acts only when j is the last sample of a segment, j >= seg_len - 1 and (j - (seg_len - 1)) % hop == 0, s = (j - (seg_len - 1)) /
+ * hop.  With W[k] = Σ_q tw[q,k] (device fp64 [n_bins, 2], summed on the host) and inv_L = 1.0 / seg_len:
+ *   m = sum_f inv_L;  ar = re_fk - m W[k,0];  ai = im_fk - m W[k,1];  p = ar ar + ai ai;  pxx_fk = (s == 0) ? p : pxx_fk + p
+ * and, with a reference (ref_sum / ref_re / ref_im: the two sets of an accumulator of the same nf, n_bins and plane_ld — this one's own
+ * or one an earlier call of the step accumulated; ref_row >= 0: that row for every row, < 0: the same row; ref_field >= 0: that field
+ * for every field, < 0: the same field), (rr, ri) the same (ar, ai) of the reference's set s & 1,
+ *   cr = ar rr + ai ri;  ci = ai rr - ar ri  (X conj R);  cxr_re_fk, cxr_im_fk = (s == 0) ? cr, ci : + cr, ci
+ * and, for each of n_track rows track[p] (device; track_host: the same on the host, checked here) and s < max_segments,
+ * seg_power[s][p][f][k] = p of that row; it leaves window[2] = s + 1.  A last partial segment is never closed.
+ * Every operation above is rounded to fp64 on its own (no fused multiply-add), every accumulator belongs to one thread: the bits are
+ * a function of the data and the tables alone.  NaN and inf follow IEEE: a poisoned sample poisons its row and field of its
+ * segment(s) and from there its pxx; a poisoned reference every cxr and no pxx.
+ * All planes are fp64, plane p of node n at base[p * plane_ld + n], plane_ld >= n_nodes; pxx, cxr_re, cxr_im have nf n_bins planes.
+ * nf = 1 .. 8, n_bins = 1 .. 64, n_track <= 1024, hop in {seg_len, seg_len / 2} (G4C_EUNSUPPORTED); seg_len >= 2, track rows in range,
+ * x_step in {0, nf} (G4C_EINVAL), all before any launch.  n_nodes == 0 launches nothing and succeeds. */
+typedef struct g4c_rollout_welch {
+    int32_t max_steps;           /* capacity of the rollout (and of a target `x`), in steps */
+    int32_t stride;              /* >= 1 */
+    int32_t seg_len;             /* L >= 2: rows of `tw` */
+    int32_t hop;                 /* H: L or L / 2 */
+    int32_t n_bins;              /* K */
+    int32_t x_ld;                /* >= nf; >= nf * max_steps with x_step == nf */
+    int32_t x_step;              /* 0 or nf */
+    int32_t ref_row, ref_field;  /* >= 0: one row / field of the reference for all; < 0: the same row / field */
+    int32_t n_track;             /* P */
+    int32_t max_segments;        /* leading extent of seg_power */
+    int32_t *window;             /* device, {origin, last, closed} */
+    const double *tw;            /* device, [seg_len, n_bins, 2] */
+    const double *W;             /* device, [n_bins, 2] */
+    double inv_L;                /* 1.0 / seg_len */
+    int64_t plane_ld;
+    double *pivot, *sum, *re, *im;              /* 2 nf, 2 nf, 2 nf n_bins, 2 nf n_bins planes */
+    double *pxx;                                /* nf n_bins planes */
+    double *cxr_re, *cxr_im;                    /* nf n_bins planes each, or NULL without a reference */
+    const double *ref_sum, *ref_re, *ref_im;    /* the reference's sets, or NULL */
+    const int32_t *track;        /* device, [n_track] */
+    const int32_t *track_host;   /* host, [n_track]: the same rows */
+    double *seg_power;           /* device, [max_segments, n_track, nf, n_bins] */
+} g4c_rollout_welch_t;
+int g4c_rollout_welch(const float *x, int32_t nf, const g4c_rollout_welch_t *s /*host*/, const int32_t *step, int64_t n_nodes, void *stream);
+
 /* A least-squares gradient over the in-edges of a mesh, and the flow diagnostics of a rollout built on it (csrc/mesh_gradient.hip).
  *
  * g4c_mesh_gradient_weights — once per mesh.  Edges grouped by receiver: the s-th in-edge of node i is edge pe = perm[off[i] + s]
